@@ -9,7 +9,7 @@ solution: fused Jacobian+residual assembly (HIP), AMG setup, BiCGStab solve to r
 When the sequence converges (||F|| < 1e-8, :281) it restarts from the Stokes solution.
 metric = M-DOF/s = N_dof / (t_assemble + t_solve) per Newton iteration / 1e6  (SURVEY 8d).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 N>1: `python bench.py --gpus N` started as a plain command launches its own N ranks (one per GPU, torch.distributed.run
 on 127.0.0.1), relays rank 0's JSON line and exits with the workers' return code; started under an external
 torch.distributed.run (the driver's way) it runs as the rank it is given.  WORLD_SIZE != --gpus is an error.
@@ -84,6 +84,9 @@ def parse_args(argv=None):
                     help="no HIP: launch, partition, halo plans and one all-reduce on gloo (CPU rehearsal of --gpus N)")
     ap.add_argument("--launch-timeout", type=float, default=3000.0,
                     help="self-launched runs: kill the workers and exit non-zero after this many seconds")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="--gpus 1: after the timed steps write what the last timed Newton step returned (the solution vector, its "
+                         "residual norms and counts) as DIR/<name>.npy, at most 64 MB in all (a seeded sample of a larger vector)")
     return ap.parse_args(argv)
 
 
@@ -231,6 +234,12 @@ def run_weak_leg_guarded(out, rank, seconds, leg, key="weak_scaling", what="weak
 
 if __name__ == "__main__":
     _ARGS = parse_args()
+    if _ARGS.steps < 1 or _ARGS.warmup < 0:
+        print("error: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        sys.exit(2)
+    if _ARGS.dump_outputs and (_ARGS.gpus > 1 or _ARGS.dry_run):
+        print("error: --dump-outputs needs a run on one GPU (--gpus 1, no --dry-run)", file=sys.stderr)
+        sys.exit(2)
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != max(1, _ARGS.gpus):
         print(f"error: --gpus {_ARGS.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']} (start `python bench.py --gpus N` as a "
               "plain command, or run it under torch.distributed.run with --nproc-per-node N)", file=sys.stderr)
@@ -554,7 +563,8 @@ def halo_windows_selfcheck(P, world):
 
 def timed_newton_steps(P, U, steps, warmup, world):
     """W untimed + K timed Newton iterations of a real sequence from the Stokes solution U (restarted when it has
-    converged); barrier + synchronize on both sides, MAX over ranks.  Returns (ms_per_step, log)."""
+    converged); barrier + synchronize on both sides, MAX over ranks.  Returns (ms_per_step, log, w to go on from, (w, result)
+    of the last timed step)."""
     import torch
     import torch.distributed as dist
 
@@ -564,12 +574,13 @@ def timed_newton_steps(P, U, steps, warmup, world):
             dist.barrier()
             torch.cuda.synchronize()
 
-    state = {"w": U.clone(), "seq": 0}
+    state = {"w": U.clone(), "seq": 0, "last": None}
     log = []
 
     def step():
         w, r = P.newton_solve(state["w"])
         state["w"] = w
+        state["last"] = (w, r)                                          # (w stays this step's result after a restart)
         state["seq"] += 1
         log.append((r.fnorms[-1] if r.fnorms else float("nan"), r.ksp_its, r.reason))
         if r.reason == 2 or r.reason == 3 or state["seq"] >= 30:       # sequence converged: start over
@@ -596,15 +607,44 @@ def timed_newton_steps(P, U, steps, warmup, world):
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         _dist_allreduce(t, dist.ReduceOp.MAX)
         dt = float(t)
-    return dt / max(1, steps) * 1e3, log, state["w"]
+    return dt / max(1, steps) * 1e3, log, state["w"], state["last"]
 
 
-def leg_record(P, U, sres, args, cfg, world, n_dof_global, f64_rerun=True):
+DUMP_BYTES = 64_000_000                                # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, w, r):
+    """What a caller of the timed path (FlowProblem.newton_solve) received in the last timed step, as DIR/<name>.npy:
+    w.npy = the solution vector (float64; if it alone would exceed the budget, a sample at fixed, seeded indices, whose
+    positions go to w_index.npy), fnorms.npy = the step's residual norms, newton.npy = [its, reason, ksp_its]."""
+    os.makedirs(dirname, exist_ok=True)
+    import numpy as np
+    small = {"fnorms": np.asarray(r.fnorms, dtype=np.float64),
+             "newton": np.asarray([r.its, r.reason, r.ksp_its], dtype=np.float64)}
+    wh = w.detach().cpu().numpy().astype(np.float64, copy=False)
+    room = DUMP_BYTES - sum(a.nbytes for a in small.values()) - 4 * 128          # (128 B: an .npy header)
+    arrays = dict(small)
+    if wh.nbytes <= room:
+        arrays["w"] = wh
+    else:
+        k = room // 16                                 # value + index, both float64
+        idx = np.sort(np.random.default_rng(0).choice(wh.size, size=k, replace=False))
+        arrays["w"], arrays["w_index"] = wh[idx], idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step in {dirname}: " + ", ".join(f"{n}.npy {a.shape}" for n, a in arrays.items()),
+          file=sys.stderr, flush=True)
+
+
+def leg_record(P, U, sres, args, cfg, world, n_dof_global, f64_rerun=True, dump_dir=None):
     """The W + K timed Newton steps on handle P and every key of the line that belongs to THAT run of them: value, step time,
     transport, Newton log, phases, counters, the live roofline of the fine-level passes (HIP events around every launch) and
-    the all-f64 repetition.  One record per transport leg: the line never mixes keys of two runs."""
+    the all-f64 repetition.  One record per transport leg: the line never mixes keys of two runs.  dump_dir: write
+    the last timed step's outputs there (dump_outputs)."""
     comm = P.comm_info()
-    ms_per_step, log, w = timed_newton_steps(P, U, args.steps, args.warmup, world)
+    ms_per_step, log, w, last = timed_newton_steps(P, U, args.steps, args.warmup, world)
+    if dump_dir:
+        dump_outputs(dump_dir, *last)
     value = n_dof_global / (ms_per_step * 1e-3) / 1e6
     tm = P.timings()
     kt = P.kernel_times()
@@ -619,7 +659,7 @@ def leg_record(P, U, sres, args, cfg, world, n_dof_global, f64_rerun=True):
     fmt0 = int(P.options.amg_f32_matrix)
     if fmt0 and f64_rerun and not args.no_f64_rerun:
         P.set_options(amg_f32_matrix=0)
-        ms64, log64, _ = timed_newton_steps(P, U, args.steps, args.warmup, world)
+        ms64, log64, _, _ = timed_newton_steps(P, U, args.steps, args.warmup, world)
         all_f64 = {"value": round(n_dof_global / (ms64 * 1e-3) / 1e6, 3), "unit": "M-DOF/s", "ms_per_step": round(ms64, 3),
                    "ksp_its": [b for _, b, _ in log64]}
         P.set_options(amg_f32_matrix=fmt0)
@@ -785,7 +825,7 @@ def main():
     WATCHDOG.tick("stokes")
     halo_check = (halo_windows_selfcheck(P, world) if peers is not None else halo_overlap_selfcheck(P, world)) if dist_on else None
     WATCHDOG.tick("halo self-check")
-    rec = leg_record(P, U, sres, args, cfg, world, n_dof_global)
+    rec = leg_record(P, U, sres, args, cfg, world, n_dof_global, dump_dir=args.dump_outputs)
 
     def line_of(rec):
         """THE JSON line with every leg-specific key taken from ONE leg's record"""
@@ -913,7 +953,7 @@ def main():
                 Pw, nd_w, nt_w, desc_w, _ = build_problem("5", wcells, length, Re, world, rank, local_rank, opts, True, group=peers)
                 Uw, sw = Pw.stokes_solve()
                 if sw.reason > 0:
-                    ms_w, log_w, _ = timed_newton_steps(Pw, Uw, args.steps, args.warmup, world)
+                    ms_w, log_w, _, _ = timed_newton_steps(Pw, Uw, args.steps, args.warmup, world)
                     out["weak_scaling"] = {"value": round(nd_w / (ms_w * 1e-3) / 1e6, 3), "unit": "M-DOF/s",
                                            "ms_per_step": round(ms_w, 3), "scaling": "weak", "transport": Pw.comm_info()["transport"],
                                            "workload": f"{desc_w} = {nt_w} tets, {nd_w} dofs ({nt_w // world} tets per GPU)",

@@ -808,8 +808,9 @@ void ring_plan(Plan& plan, int r, int nranks, int halo_nodes) {
 }  // namespace
 
 int peer_selftest(int device, int nranks, int halo_nodes, int reps, double us_out[3]) {
-    // (one HIP hardware queue per rank besides the null stream's: with the runtime's default of 4 queues a fourth rank would share one,
-    // and a kernel waiting for a flag would sit in front of the kernel that raises it)
+    // (one HIP hardware queue per rank: two ranks whose streams share a queue deadlock, a kernel waiting for a flag sitting in front
+    // of the kernel that raises it.  The runtime hands out at most GPU_MAX_HW_QUEUES queues per stream priority and shares them
+    // beyond that, so every rank's stream gets a priority of its own -- low, high, normal -- and with it a queue of its own)
     if (nranks < 2 || nranks > 3 || halo_nodes < 1 || reps < 1 || !us_out) {
         set_error("sns_peer_selftest: 2 or 3 ranks, halo_nodes >= 1, reps >= 1");
         return SNS_E_ARG;
@@ -820,6 +821,9 @@ int peer_selftest(int device, int nranks, int halo_nodes, int reps, double us_ou
     std::vector<int> rcs((size_t)nranks, SNS_OK);
     std::vector<std::string> errs((size_t)nranks);
     std::vector<double> us((size_t)3 * nranks, 0.0);
+    int prio_least = 1, prio_greatest = -1;
+    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+    const int prio[3] = {prio_least, prio_greatest, (prio_least + prio_greatest) / 2};
     auto work = [&](int r) {
         auto fail = [&](int rc) { rcs[(size_t)r] = rc; errs[(size_t)r] = sns_last_error(); };
         hipStream_t st = nullptr;
@@ -856,7 +860,7 @@ int peer_selftest(int device, int nranks, int halo_nodes, int reps, double us_ou
         for (int q = 0; q < nranks; ++q) t.all.insert(t.all.end(), offers[(size_t)q].mine.begin(), offers[(size_t)q].mine.end());
         if (peer_plan_connect(&c, plan, t) != SNS_OK) fail(SNS_E_COMM);
         const int32_t ag_count = 2048;
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
+        if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio[r]) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
             hipEventCreate(&e1) != hipSuccess || hipMalloc((void**)&x, 4 * (size_t)n_local * sizeof(double)) != hipSuccess ||
             hipMalloc((void**)&ar, 8 * sizeof(double)) != hipSuccess || hipMalloc((void**)&ags, ag_count * sizeof(double)) != hipSuccess ||
             hipMalloc((void**)&agr, (size_t)ag_count * nranks * sizeof(double)) != hipSuccess ||

@@ -358,11 +358,41 @@ def test_bench_guarded_leg_reports_under_its_own_key():
     assert o == {"peer_transport": {"value": 2.0}, "weak_scaling": None}
 
 
-def test_bench_watchdog_turns_a_stalled_rank_into_a_nonzero_exit():
+def test_bench_watchdog_turns_a_stalled_rank_into_a_nonzero_exit(tmp_path):
     """A rank that stops making progress exits non-zero by itself (no re-exec); the launcher passes the failure on."""
     import time
     t0 = time.time()
+    # (the record of the failed first attempt goes to the test's own directory, not into the repository)
     rc, out, err = _run_bench(["--gpus", "2", "--dry-run", "--cells", "24,6,6"],
-                              {"SNS_DRYRUN_STALL_RANK": "1", "SNS_WATCHDOG_S": "2"}, timeout=120)
+                              {"SNS_DRYRUN_STALL_RANK": "1", "SNS_WATCHDOG_S": "2", "SNS_BENCH_LOG_DIR": str(tmp_path)}, timeout=120)
     assert rc != 0 and "watchdog: rank 1" in err
     assert time.time() - t0 < 100
+
+
+def test_bench_dump_outputs_are_bounded_and_reproducible(tmp_path):
+    """--dump-outputs: the last timed step's outputs as <name>.npy in float64, within 64 MB in all; a vector too large for
+    that is sampled at the same seeded indices every time.  --steps < 1, and a dump of a multi-rank or dry run, are refused."""
+    from types import SimpleNamespace
+    import bench
+    import numpy as np
+    import torch
+    r = SimpleNamespace(fnorms=[0.2, 3e-3], its=1, reason=5, ksp_its=43)
+    w = torch.arange(1000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "full"), w, r)
+    assert np.array_equal(np.load(str(tmp_path / "full" / "w.npy")), w.numpy())
+    assert np.array_equal(np.load(str(tmp_path / "full" / "fnorms.npy")), [0.2, 3e-3])
+    assert np.array_equal(np.load(str(tmp_path / "full" / "newton.npy")), [1, 5, 43])
+    big = torch.arange(9_000_000, dtype=torch.float64)                  # 72 MB
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, r)
+        files = list((tmp_path / d).iterdir())
+        assert sum(f.stat().st_size for f in files) <= 64_000_000
+        assert all(np.load(str(f)).dtype == np.float64 for f in files)
+    wa, ia = np.load(str(tmp_path / "a" / "w.npy")), np.load(str(tmp_path / "a" / "w_index.npy"))
+    assert np.array_equal(wa, ia) and np.array_equal(wa, np.load(str(tmp_path / "b" / "w.npy")))
+    assert len(wa) > 3_000_000 and np.all(np.diff(ia) > 0)
+    for args in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", str(tmp_path / "x")],
+                 ["--dry-run", "--dump-outputs", str(tmp_path / "x")]):
+        rc, out, err = _run_bench(args, timeout=120)
+        assert rc == 2 and "error:" in err, (args, rc, err[-1000:])
+    assert not (tmp_path / "x").exists()

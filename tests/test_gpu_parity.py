@@ -838,13 +838,14 @@ def test_delaunay_unstructured_mesh(gpu, n, seed):
     P.close()
 
 
-def test_dfg_pillar_benchmark_drag_and_pressure_drop(gpu):
+def test_dfg_pillar_benchmark_drag_and_pressure_drop(gpu, tmp_path, monkeypatch):
     """External known answer for the whole chain (mesh -> G-metric P1-P1 discretisation -> AMG/Newton -> traction
     functional): the pillar channel of Validation_Flow/DFG_3D_Validation.py (Re = 20; the 3D-1Z case of the DFG
     benchmark, literature C_d 6.05-6.25 (6.185), C_l 0.008-0.010, Delta p 0.165-0.175).  On body-centred-lattice Delaunay
     meshes of the geometry the solver gives C_d 6.318 / 6.262 / 6.236 / 6.196 and Delta p 0.161 / 0.160 / 0.163 / 0.166 at
     h = W/32, W/40, W/50, W/64 (2.1 ... 16.7 M tets, scripts/gpu_dfg3d.py); the coarsest of these runs here."""
     from stabilized_navier_stokes_flow_fenicsx_amd import drivers as D
+    monkeypatch.chdir(tmp_path)                                  # (the script writes its XDMF output to the working directory)
     # through the script's own entry point (DFG_3D_Validation.py; "builtin:32" = the gmsh-free mesh of the geometry)
     m, wh, (cd, cl), res = D.dfg_3d_main(["DFG_3D_Validation.py", "builtin:32"])
     assert res.reason > 0 and res.its <= 6
