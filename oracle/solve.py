@@ -41,17 +41,21 @@ def block_jacobi_inverse(A):
     return np.linalg.inv(D)
 
 
-def bicgstab_bj(A, b, x0=None, rtol=1e-8, atol=1e-50, maxit=10000, Dinv=None, history=None):
-    """Right-preconditioned BiCGStab, M = blockdiag_4x4(A).  Returns (x, its, reason).
+def bicgstab_bj(A, b, x0=None, rtol=1e-8, atol=1e-50, maxit=10000, Dinv=None, history=None, pc=None):
+    """Right-preconditioned BiCGStab, M = blockdiag_4x4(A) -- or `pc`, any callable v -> M^-1 v (e.g. the AMG cycle of
+    oracle/amg_cycle.py).  Returns (x, its, reason).
 
     Stopping: ||r|| <= max(rtol*||b||, atol) on the TRUE residual recurrence.
     """
     n = A.shape[0]
-    if Dinv is None:
-        Dinv = block_jacobi_inverse(A)
+    if pc is not None:
+        M = pc
+    else:
+        if Dinv is None:
+            Dinv = block_jacobi_inverse(A)
 
-    def M(v):
-        return np.einsum("nij,nj->ni", Dinv, v.reshape(-1, 4)).reshape(n)
+        def M(v):
+            return np.einsum("nij,nj->ni", Dinv, v.reshape(-1, 4)).reshape(n)
 
     x = np.zeros(n) if x0 is None else x0.copy()
     r = b - A @ x

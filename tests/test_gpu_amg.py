@@ -6,6 +6,8 @@
 Tolerances: the cycle's matrix data are fp32 copies here (amg_f32_matrix = 1: level matrices, D^-1 / B^-1, the dense inverse;
 vectors and arithmetic fp64), the oracle is all fp64: 1e-5 relative on a random vector (observed ~1e-7); with the default fp16
 copies the same comparison is a bound on the perturbation (< 0.1, as in test_fused_post_sweep_is_the_same_preconditioner).
+Against the oracle that quantizes the same data (oracle/amg_cycle.py build(fmt=...)) every format is the same operator to
+round-off: _BOUND.
 """
 import ctypes as C
 
@@ -53,10 +55,38 @@ def test_blocked_gauss_jordan_inverse_vs_numpy(N):
     assert lib.sns_dense_inverse(0, Z.shape[0], Z.data_ptr(), torch.empty_like(Z).data_ptr()) != 0
 
 
-def _problem(gpu, opts):
+def _renumbered(m, seed=0):
+    """the same mesh with randomly permuted node ids (gmsh-like numbering): the chooser takes pairwise aggregation on every level"""
+    from stabilized_navier_stokes_flow_fenicsx_amd import mesh as M
+    perm = np.random.default_rng(seed).permutation(m.num_nodes)
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    return M.TetMesh(m.points[perm].copy(), inv[m.tets].astype(np.int32), inv[m.facets].astype(np.int32), m.facet_tags.copy(),
+                     name=m.name, meta=dict(m.meta))
+
+
+def _mesh(kind):
+    """small meshes (<= 5 k nodes) that between them take every path of the low-precision copies: jitter -- the Kuhn lattice, odd
+    block counts <= 15 (k_lp_copies16's register path, odd tail); delaunay -- even counts, rows of 16 / 17 / > 20 blocks (loop path),
+    aggregates of more than 8 nodes; cavity -- Dirichlet-heavy (M's unit diagonal, empty coarse dofs); stretched -- cells 4:1 (the
+    strong-only filter of the aggregation); renumbered -- random node ids (pairwise aggregation on every level)"""
     from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B, mesh as M
-    m = M.duct_mesh((40, 10, 10), 4.0, jitter=0.15)
-    mask, g = B.duct_bcs(m).flatten()
+    if kind == "delaunay":
+        m = M.delaunay_duct_mesh(10, 2.0, seed=3)
+    elif kind == "cavity":
+        m = M.cavity_mesh(16)
+        return m, B.cavity_bcs(m).flatten()
+    elif kind == "stretched":
+        m = M.duct_mesh((40, 10, 10), 16.0, jitter=0.15)
+    elif kind == "renumbered":
+        m = _renumbered(M.duct_mesh((40, 10, 10), 4.0, jitter=0.15))
+    else:
+        m = M.duct_mesh((40, 10, 10), 4.0, jitter=0.15)
+    return m, B.duct_bcs(m).flatten()
+
+
+def _problem(gpu, opts, kind="jitter"):
+    m, (mask, g) = _mesh(kind)
     P = gpu(m, (mask, g), reynolds=60.0, **opts)
     U, r = P.stokes_solve()
     assert r.reason > 0
@@ -65,7 +95,9 @@ def _problem(gpu, opts):
     return m, mask, P, U, F
 
 
-def _oracle_cycle(P, mask, r, block, dense_rows):
+def _oracle_cycle(P, mask, r, block, dense_rows, kind=None, max_levels=12, fmt=None, fused_post=False, pts=None):
+    """oracle/amg_cycle.py's cycle on the GPU's hierarchy: fmt=None all fp64, fmt 0 / 1 / 2 the level data amg_f32_matrix = fmt
+    gives the passes (fused_post: the GPU's amg_fused_post), pts: the aggregation with coordinates as the product runs it"""
     from oracle import amg_cycle as AC
     import scipy.sparse as sp
     A = P.to_scipy()
@@ -77,19 +109,50 @@ def _oracle_cycle(P, mask, r, block, dense_rows):
     nl = len(hier)
     blk = tuple(l for l, c in enumerate(cyc) if c["kind"] == 1)
     assert blk == (tuple(range(1, nl - 1)) if block else ()), cyc
-    assert cyc[-1]["kind"] == (3 if dense_rows else 2), cyc
-    lv = AC.build(A, ~mask.astype(bool), dense_rows=dense_rows, block_levels=blk, graph=G)
+    assert cyc[-1]["kind"] == ((3 if dense_rows else 2) if kind is None else kind), cyc
+    lv = AC.build(A, ~mask.astype(bool), dense_rows=dense_rows, block_levels=blk, graph=G, max_levels=max_levels, pts=pts, fmt=fmt,
+                  fused_post=fused_post)
     assert [L.n for L in lv] == [h["rows"] for h in hier], ([L.n for L in lv], hier)
+    assert lv[-1].kind == cyc[-1]["kind"]
     sweeps = [(c["pre"], c["post"]) for c in cyc]
     om = [h["omega"] for h in hier]
     return AC.cycle(lv, 0, r, sweeps, om), lv
+
+
+def _maxrel(z, zo):
+    return float(np.abs(z - zo).max() / np.abs(zo).max())
+
+
+# pc_apply against the restatement of the same low-precision data: about 100 x the largest value observed on the MI355X over the
+# cases below (4.1e-13 on the cavity, <= 5e-15 on every other mesh, in every format, the fp32 Gauss-Jordan inverse included)
+_BOUND = {0: 5e-11, 1: 5e-11, 2: 5e-11}
+
+
+def _quantized_error(P, m, mask, r, block, dense_rows, fmt, fused, fuse_restrict=1, kind=None, max_levels=12, label=""):
+    """max|z - z_o| / max|z_o| of pc_apply with amg_f32_matrix = fmt, amg_fused_post = fused, amg_fuse_restrict against the oracle's
+    cycle on the same quantized data; asserts the level sizes (in _oracle_cycle) and that z is still a fixed linear operator"""
+    P.set_options(amg_f32_matrix=fmt, amg_fused_post=fused, amg_fuse_restrict=fuse_restrict)
+    P.pc_setup()
+    rd = torch.from_numpy(r).cuda()
+    z = P.pc_apply(rd).cpu().numpy()
+    zo, lv = _oracle_cycle(P, mask, r, block and fmt != 0, dense_rows, kind=kind, max_levels=max_levels, fmt=fmt,
+                           fused_post=bool(fused), pts=m.points)
+    z2 = P.pc_apply(-2.0 * rd).cpu().numpy()
+    assert rel(z2, -2.0 * z) < 1e-12
+    e = _maxrel(z, zo)
+    bound = _BOUND[fmt]
+    print(f"  {label} fmt {fmt} fused_post {fused} fuse_restrict {fuse_restrict} last kind {lv[-1].kind} levels "
+          f"{[L.n for L in lv]} which {[L.which for L in lv[:-1]]}: HIP vs quantized oracle {e:.2e} (bound {bound:.0e})")
+    return e, bound, lv
 
 
 @pytest.mark.parametrize("block,dense_rows", [(0, 0), (0, 100), (1, 0), (1, 100)])
 def test_vcycle_matches_the_scipy_restatement(gpu, block, dense_rows):
     """pc_apply of the HIP V-cycle == oracle/amg_cycle.py's restatement of the same cycle (same aggregates, Galerkin operators,
     sweeps, the GPU's own damping), for nodal-block and aggregate-block smoothing and for the coarsest level solved by the
-    one-workgroup inverse (dense_rows 0: 10 nodes) resp. the blocked Gauss-Jordan inverse (dense_rows 100: 78 nodes)."""
+    one-workgroup inverse (dense_rows 0: 10 nodes) resp. the blocked Gauss-Jordan inverse (dense_rows 100: 78 nodes).
+    Against the all-fp64 oracle the low-precision copies are a bounded perturbation; against the oracle that quantizes the same
+    data (build(fmt=...)) every (format, fused post-sweep) variant is the same operator to round-off."""
     m, mask, P, U, F = _problem(gpu, dict(amg_block_smooth=block, amg_dense_rows=dense_rows, amg_f32_matrix=1))
     P.pc_setup()
     hier = P.hierarchy()
@@ -113,6 +176,72 @@ def test_vcycle_matches_the_scipy_restatement(gpu, block, dense_rows):
     assert rel(z16, zo) < 0.1
     assert k32.reason > 0 and k16.reason > 0 and abs(k32.its - k16.its) <= 2
     assert rel(y16.cpu().numpy(), y32.cpu().numpy()) < 1e-6
+    # ... and each variant is exactly the operator of its own quantized data
+    errs = [_quantized_error(P, m, mask, r, block, dense_rows, fmt, fused, label=f"block {block} dense_rows {dense_rows}")
+            for fmt, fused in ((1, 0), (1, 1), (2, 0), (2, 1))]
+    assert all(e < b for e, b, _ in errs), [(e, b) for e, b, _ in errs]
+    P.close()
+
+
+# mesh, block smoothing, dense_rows, amg_max_levels, expected last-level kind, [(fmt, fused_post, fuse_restrict)]
+_CASES = {
+    "jitter-sweeps": ("jitter", 0, 100, 2, 4, [(0, 0, 0), (1, 1, 1), (2, 1, 0)]),
+    "delaunay-blocks-gj": ("delaunay", 1, 100, 12, 3, [(0, 0, 0), (2, 0, 1), (2, 1, 1)]),
+    "delaunay-nodal-small": ("delaunay", 0, 0, 12, 2, [(1, 0, 0), (2, 1, 1)]),
+    "cavity-blocks-small": ("cavity", 1, 0, 12, 2, [(1, 1, 1), (2, 1, 1), (2, 0, 0)]),
+    "stretched-blocks-gj": ("stretched", 1, 100, 12, 3, [(2, 1, 1), (1, 0, 1)]),
+    "renumbered-blocks-small": ("renumbered", 1, 100, 12, 2, [(2, 1, 1), (0, 0, 0)]),
+    "renumbered-nodal-sweeps": ("renumbered", 0, 100, 3, 4, [(2, 1, 1), (1, 1, 0)]),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_CASES))
+def test_vcycle_matches_the_scipy_restatement_on_more_meshes(gpu, case):
+    """the quantized comparison of test_vcycle_matches_the_scipy_restatement over a covering set of meshes (_mesh), smoothers,
+    coarsest solves (2 one-workgroup inverse, 3 blocked Gauss-Jordan, 4 sweeps only via amg_max_levels) and fusion switches:
+    pc_apply == the oracle on the same fp64 / fp32 / fp16 data within _BOUND -- a swapped pair half, a wrong row scale, a dropped
+    odd tail or M taken as Q(A) P move z by orders of magnitude more (tests/test_oracle_amg.py)."""
+    kind_mesh, block, dense_rows, max_levels, kind, variants = _CASES[case]
+    m, mask, P, U, F = _problem(gpu, dict(amg_block_smooth=block, amg_dense_rows=dense_rows, amg_max_levels=max_levels), kind_mesh)
+    r = np.random.default_rng(17).normal(size=m.num_dofs)
+    errs = [_quantized_error(P, m, mask, r, block, dense_rows, fmt, fused, fr, kind=kind, max_levels=max_levels, label=case)
+            for fmt, fused, fr in variants]
+    if kind_mesh == "renumbered":
+        assert all(L.which == 1 for L in errs[0][2][:-1]), [L.which for L in errs[0][2]]
+    assert all(e < b for e, b, _ in errs), [(e, b) for e, b, _ in errs]
+    P.close()
+
+
+def test_amg_preconditioned_bicgstab_iterates_match_the_oracle(gpu):
+    """krylov_solve with the default cycle (fp16 copies, fused post-sweep and restriction) runs kernels pc_apply never does: the
+    fine level's first sweep fused into k_bicg_s_first / k_bicg_xrp_first, k_bicg_dots5's five dot products, the device-resident
+    scalars.  Its iterate after 1, 2 and 5 iterations == oracle/solve.py's BiCGStab preconditioned with the quantized cycle, and the
+    full solve takes the same iterations (+-1) to the same solution (within rtol)."""
+    from oracle import amg_cycle as AC, solve as S
+    m, mask, P, U, F = _problem(gpu, dict(amg_retry_damping=0, ksp_type="bicgstab"))
+    P.pc_setup()
+    _, lv = _oracle_cycle(P, mask, np.zeros(m.num_dofs), 1, int(P.options.amg_dense_rows), kind=P.cycle()[-1]["kind"], fmt=2,
+                          fused_post=True, pts=m.points)
+    sweeps = [(c["pre"], c["post"]) for c in P.cycle()]
+    om = [h["omega"] for h in P.hierarchy()]
+    A = P.to_scipy()
+    b = F.cpu().numpy()
+    pc = lambda v: AC.cycle(lv, 0, v, sweeps, om)                # noqa: E731
+    rtol = float(P.options.ksp_rtol)
+    for k in (1, 2, 5):
+        P.set_options(ksp_max_it=k)
+        y, res = P.krylov_solve(F)
+        yo, its_o, _ = S.bicgstab_bj(A, b, rtol=rtol, maxit=k, pc=pc)
+        e = _maxrel(y.cpu().numpy(), yo)
+        print(f"  BiCGStab + AMG after {k} its: HIP vs oracle {e:.2e}")
+        assert res.its == its_o == k
+        assert e < 1e-13                                         # observed <= 1.1e-15
+    P.set_options(ksp_max_it=10000)
+    y, res = P.krylov_solve(F)
+    yo, its_o, reason_o = S.bicgstab_bj(A, b, rtol=rtol, maxit=10000, pc=pc)
+    print(f"  full solve: its {res.its} / oracle {its_o}, rel {rel(y.cpu().numpy(), yo):.2e}")
+    assert res.reason > 0 and reason_o > 0 and abs(res.its - its_o) <= 1
+    assert rel(y.cpu().numpy(), yo) < rtol                       # observed 2.7e-11
     P.close()
 
 

@@ -60,3 +60,168 @@ def test_cycle_is_linear_and_preconditions_for_both_smoothers_and_coarsest_solve
     # the aggregate-block schedule (half the sweeps) does the job of the nodal-block one
     assert its[(1, 0)] <= its[(0, 0)] + 3 and its[(1, 300)] <= its[(0, 300)] + 3, its
     assert max(its.values()) < 40, its
+
+
+# ---- the quantized restatement (build(fmt=...)): the rules of the GPU's low-precision copies, and how sharp a comparison with them is
+import scipy.sparse as sp                                                   # noqa: E402
+
+# tests/test_gpu_amg.py's bound on max|z - z_o| / max|z_o| for the fp16 copies (_BOUND[2] there): every planted defect below must
+# move z_o by at least 100 x this, so that a GPU cycle within the bound cannot have it
+GPU_BOUND_FP16 = 5e-11
+
+
+def _row(vals):
+    return sp.csr_matrix(np.asarray(vals, dtype=np.float64)[None, :])
+
+
+def test_fp16_copy_rounds_once_as_the_compiled_kernel_does():
+    """k_lp_copies16 reads (_Float16)(float)(a * (1 / s)), but the compiled kernel rounds ONCE, f64 -> f16 (oracle/amg_cycle.py
+    q16_rows; the GPU's pc_apply matches the single rounding to round-off and misses the double one by 1e-5).  1 + 2^-11 + 2^-40
+    with row max 2 is 0.5 + 2^-12 + 2^-41: above the fp16 tie, so it rounds up to 0.5 + 2^-11; through fp32 it would be the tie
+    itself and round to even (0.5)."""
+    a = 1.0 + 2.0 ** -11 + 2.0 ** -40
+    Xq, s, h = AC.q16_rows(_row([2.0, a, -2.0]))
+    assert s[0] == 2.0 and Xq.data[1] == 1.0 + 2.0 ** -10
+    assert float(np.float16(np.float32(a / 2.0))) * 2.0 == 1.0                  # the double rounding would differ
+    assert list(Xq.data) == [2.0, 1.0 + 2.0 ** -10, -2.0]
+    Bq, _, _ = AC.q16_binv(_row([2.0, a, -2.0]))
+    assert list(Bq.data) == [2.0, 1.0 + 2.0 ** -10, -2.0]
+
+
+def test_fp16_copy_subnormals_zero_rows_and_scale_rules():
+    # below 2^-24 max: fp16 subnormals (2^-24 steps), ties to even at 2^-25, zero below
+    vals = [1.0, 2.0 ** -20, 3 * 2.0 ** -26, 2.0 ** -25, 2.0 ** -27, 0.0, -2.0 ** -14 - 2.0 ** -24]
+    Xq, s, h = AC.q16_rows(_row(vals))
+    assert list(Xq.toarray()[0]) == [1.0, 2.0 ** -20, 2.0 ** -24, 0.0, 0.0, 0.0, -2.0 ** -14 - 2.0 ** -24]
+    assert np.all(np.isfinite(Xq.data))
+    # an all-zero row: scale 0, values 0 (no 0 * inf)
+    Z = sp.csr_matrix(np.array([[0.0, 0.0, 0.0], [2.0, -4.0, 0.5]]))
+    for q in (AC.q16_rows, AC.q16_binv):
+        Zq, s, _ = q(Z)
+        assert s[0] == 0.0 and np.all(Zq.toarray()[0] == 0.0) and np.all(Zq.toarray()[1] == [2.0, -4.0, 0.5])
+    # a row max fp32 cannot represent: k_lp_copies16 divides by f32(mx), k_binv<2> by mx itself; both store f32(mx)
+    mx = 1.0 + 2.0 ** -24 + 2.0 ** -40
+    s32 = float(np.float32(mx))
+    assert s32 == 1.0 + 2.0 ** -23
+    a = 0.536377
+    c, _, _ = AC.q16_rows(_row([mx, a]))
+    b, _, _ = AC.q16_binv(_row([mx, a]))
+    assert c.data[1] == s32 * float(np.float16(a * (1.0 / s32)))
+    assert b.data[1] == s32 * float(np.float16(a * (1.0 / mx)))
+    assert c.data[1] != b.data[1]
+
+
+def _graph(m):
+    t = m.tets
+    r, c = np.repeat(t, 4, axis=1).ravel(), np.tile(t, (1, 4)).ravel()
+    G = sp.csr_matrix((np.ones(len(r)), (r, c)), shape=(m.num_nodes, m.num_nodes))
+    G.data[:] = 1.0
+    return G
+
+
+def _renumbered(m, seed=0):
+    perm = np.random.default_rng(seed).permutation(m.num_nodes)
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    return M.TetMesh(m.points[perm].copy(), inv[m.tets].astype(np.int32), inv[m.facets].astype(np.int32), m.facet_tags.copy(),
+                     name=m.name, meta=dict(m.meta))
+
+
+def _ns_operator(m):
+    mask, g = B.duct_bcs(m).flatten()
+    w = np.zeros(m.num_dofs)
+    w[mask.astype(bool)] = g[mask.astype(bool)]
+    J, _ = asm.assemble_ns(m.points, m.tets, w, 60.0, mask, g)
+    return J.tocsr(), ~mask.astype(bool)
+
+
+def test_quantizers_off_is_the_fp64_cycle_bitwise():
+    A, _, free = _operator()
+    r = np.random.default_rng(3).normal(size=A.shape[0])
+    sw, om = [(1, 1), (1, 3), (2, 2), (2, 2)], [0.6] * 6
+    z0 = AC.cycle(AC.build(A, free, dense_rows=100, block_levels=(1,)), 0, r, sw, om)
+    z1 = AC.cycle(AC.build(A, free, dense_rows=100, block_levels=(1,), fmt=None, fused_post=False), 0, r, sw, om)
+    assert np.array_equal(z0, z1)
+    # the fused post-sweep over the EXACT M = A P is the same operator to round-off, the quantized formats are not far from it
+    lv = AC.build(A, free, dense_rows=100, block_levels=(1,))
+    for L in lv[:-1]:
+        L.Mq = (L.A @ L.P).tocsr()
+    assert np.abs(AC.cycle(lv, 0, r, sw, om) - z0).max() < 1e-12 * np.abs(z0).max()
+    for fmt in (1, 2):
+        z = AC.cycle(AC.build(A, free, dense_rows=100, block_levels=(1,), fmt=fmt, fused_post=True), 0, r, sw, om)
+        assert 0.0 < np.abs(z - z0).max() / np.abs(z0).max() < (1e-4 if fmt == 1 else 0.1)
+
+
+def test_planted_layout_defects_move_the_cycle_far_beyond_the_gpu_bound():
+    """One fp16 ulp in one entry of an odd-count row, the two halves of a pair swapped, a neighbouring row's scale, M taken as
+    Q(A) P instead of Q(A P): each changes z_o = cycle(r) by >= 100 x the GPU-vs-oracle bound of tests/test_gpu_amg.py."""
+    m = M.duct_mesh((24, 6, 6), 4.0, jitter=0.15)
+    A, free = _ns_operator(m)
+    r = np.random.default_rng(4).normal(size=A.shape[0])
+    sw, om = [(1, 1), (1, 3), (2, 2), (2, 2), (2, 2)], [0.6] * 6
+
+    def fresh():
+        return AC.build(A, free, dense_rows=100, block_levels=(1,), graph=_graph(m), pts=m.points, fmt=2, fused_post=True)
+
+    z0 = AC.cycle(fresh(), 0, r, sw, om)
+    Ab = A.tobsr((4, 4))
+    Ab.sort_indices()
+    cnt = np.diff(Ab.indptr)
+    i = int(np.flatnonzero(free.reshape(-1, 4).all(axis=1) & (cnt % 2 == 1))[len(cnt) // 3])   # an interior node, odd row
+    d = 4 * i                                                                                   # its first dof row
+    moved = {}
+    # one fp16 ulp of the row's entry of largest magnitude
+    lv = fresh()
+    Aq = lv[0].Aq
+    lo, hi = Aq.indptr[d], Aq.indptr[d + 1]
+    k = lo + int(np.argmax(np.abs(Aq.data[lo:hi])))
+    s = np.abs(Aq.data[lo:hi]).max()
+    h = np.float16(Aq.data[k] / s)
+    Aq.data[k] = s * float(np.nextafter(h, np.float16(0.0)))
+    moved["one ulp"] = AC.cycle(lv, 0, r, sw, om)
+    # the two blocks of a pair swapped in the node's 4 dof rows
+    lv = fresh()
+    Aq = lv[0].Aq
+    for q in range(4):
+        lo = Aq.indptr[d + q]
+        a = Aq.data[lo:lo + 8].copy()
+        Aq.data[lo:lo + 4], Aq.data[lo + 4:lo + 8] = a[4:8], a[0:4]
+    moved["pair swapped"] = AC.cycle(lv, 0, r, sw, om)
+    # the scale of the neighbouring dof row
+    lv = fresh()
+    Aq = lv[0].Aq
+    mq, _ = AC._row_max(Aq)
+    q = next(q for q in range(4) if mq[d + q] != mq[d + q + 1])
+    lo, hi = Aq.indptr[d + q], Aq.indptr[d + q + 1]
+    Aq.data[lo:hi] *= mq[d + q + 1] / mq[d + q]
+    moved["neighbour's scale"] = AC.cycle(lv, 0, r, sw, om)
+    # M = Q(A) P
+    lv = fresh()
+    for L in lv[:-1]:
+        L.Mq = (L.Aq @ L.P).tocsr()
+    moved["Q(A) P"] = AC.cycle(lv, 0, r, sw, om)
+    for name, z in moved.items():
+        e = np.abs(z - z0).max() / np.abs(z0).max()
+        print(f"  {name}: {e:.2e}")
+        assert e >= 100 * GPU_BOUND_FP16, (name, e)
+    assert cnt[i] % 2 == 1 and cnt[i] <= 16
+
+
+def test_aggregation_with_coordinates_follows_the_chooser():
+    """build(pts=...) aggregates as the product does with coordinates: the randomly renumbered duct takes pairwise aggregation on
+    every level, the duct stretched to cells of 4:1 the strong-only filter (other aggregates than the pattern alone gives), and on
+    the isotropic jittered duct the coordinates change nothing."""
+    def sizes(m, pts):
+        A, free = _ns_operator(m)
+        lv = AC.build(A, free, dense_rows=100, graph=_graph(m), pts=pts)
+        return [L.n for L in lv], [L.which for L in lv[:-1]]
+    base = M.duct_mesh((40, 10, 10), 4.0, jitter=0.15)
+    ren = _renumbered(base)
+    n, which = sizes(ren, ren.points)
+    assert which and all(w == 1 for w in which), which
+    assert n != sizes(ren, None)[0]
+    st = M.duct_mesh((40, 10, 10), 16.0, jitter=0.15)
+    n, which = sizes(st, st.points)
+    assert all(w == 0 for w in which) and n[1] != sizes(st, None)[0][1]
+    n, which = sizes(base, base.points)
+    assert all(w == 0 for w in which) and n == sizes(base, None)[0]
