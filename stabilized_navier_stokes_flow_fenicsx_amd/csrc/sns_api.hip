@@ -211,6 +211,7 @@ static int create_common(int dim, sns_handle* out, int32_t n_nodes, int64_t n_te
     h->r3_estimates = std::getenv("SNS_R3_SPECTRAL_ESTIMATE") != nullptr;
     h->pattern.reset(new HostPattern(std::move(P)));
     h->host_pts.assign(points, points + (size_t)3 * n_nodes);
+    SNS_TRY(plan_hierarchy(h.get()));                     // (the fine level alone until the hierarchy is built)
     *out = h.release();
     return SNS_OK;
 }
@@ -320,7 +321,8 @@ int sns_set_options(sns_handle h, const sns_options* o) {
             if (l < h->pong.size() && h->pong[l]) HIP_TRY(hipMemset(h->pong[l], 0, nb));
         }
     }
-    if (pc_changed || damping_changed) h->pc_ready = false;
+    h->plan = policy::plan_cycle(h->opt, h->facts);         // (the stored facts: no communication)
+    if (pc_changed || damping_changed || plan_buffer_missing(h)) h->pc_ready = false;
     if (damping_changed || pc_changed)
         for (auto& L : h->levels) { L.lambda_max = 0.0; L.omega_checked = 0.0; L.ritz_limit = 0.0; }   // re-estimate and re-verify
     return SNS_OK;
@@ -437,7 +439,7 @@ static int attach_common(sns_handle h, int rank, int nranks, const char* uid, Te
     // checked the same way when the hierarchy derives them)
     SNS_TRY(check_plan_symmetry(h, c.plans[0], 0));
     SNS_TRY(connect_plan(h, c.plans[0]));
-    return SNS_OK;
+    return plan_hierarchy(h);                            // (the fine level alone until the hierarchy is built)
 }
 
 
@@ -735,7 +737,7 @@ int sns_get_hierarchy(sns_handle h, int32_t* nlevels, int64_t rows[16], int64_t 
         const Level& L = h->levels[l];
         if (rows) rows[l] = L.n_owned;
         if (blocks) blocks[l] = L.nnzb;
-        if (sweeps) sweeps[l] = l + 1 < (int)h->levels.size() ? level_nu(h, l) : 0;      // the coarsest level is a dense inverse
+        if (sweeps) sweeps[l] = l + 1 < (int)h->levels.size() ? h->plan.level[(size_t)l].nu : 0;   // the coarsest level is a dense inverse
         if (omega) omega[l] = L.omega;
     }
     return SNS_OK;
@@ -779,17 +781,10 @@ int sns_get_cycle(sns_handle h, int32_t* nlevels, int32_t kind[16], int32_t nu_p
     const int nl = (int)std::min<size_t>(16, h->levels.size());
     *nlevels = nl;
     for (int l = 0; l < nl; ++l) {
-        const Level& L = h->levels[l];
-        nu_pre[l] = nu_post[l] = 0;
-        if (l + 1 == (int)h->levels.size() && nl > 1) {
-            kind[l] = L.dense_gj ? SNS_LEVEL_DIRECT_BLOCKED : (L.dense_inv || h->cg_N > 0) ? SNS_LEVEL_DIRECT : SNS_LEVEL_SWEEPS_ONLY;
-            continue;
-        }
-        kind[l] = block_active(h, l) ? SNS_LEVEL_AGGREGATE_BLOCKS : SNS_LEVEL_NODAL_BLOCKS;
-        int a = 1, b = 1;
-        level_sweeps(h, l, a, b);
-        nu_pre[l] = a;
-        nu_post[l] = b;
+        const policy::LevelPlan& P = h->plan.level[(size_t)l];
+        kind[l] = P.kind;
+        nu_pre[l] = P.pre;
+        nu_post[l] = P.post;
     }
     return SNS_OK;
 }

@@ -1,7 +1,6 @@
 // Shared internals of the C-ABI layer (round 5: csrc/sns_api.hip split into setup / cycle / Krylov / C-ABI translation units):
-// the context behind an sns_handle, the error / allocation helpers, the launch helpers of the level passes, the handle-side
-// predicates of the cycle (which gather the facts and ask csrc/sns_policy.h for every number) and the functions the translation
-// units call across each other.  Not installed; the public surface is include/sns.h.
+// the context behind an sns_handle, the error / allocation helpers, the launch helpers of the level passes and the functions the
+// translation units call across each other.  Not installed; the public surface is include/sns.h.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -105,7 +104,8 @@ struct sns_ctx {
     hipStream_t cap_stream = nullptr;
     hipStream_t gj_stream = nullptr;              // second stream of the dense coarsest level's elimination (bulk updates beside the pivot chain)
     hipGraphExec_t coarse_graph = nullptr;
-    std::vector<double> graph_sig;                // (omega per level, nu, nu_coarse, f32) the graph was captured with
+    std::vector<double> graph_sig;                // (graph level, omega per level) the graph was captured with ...
+    std::vector<policy::LevelPlan> graph_rows;    // ... and the plan rows it covers
     bool graph_disabled = false;
     int matrix_form = -1;
     int est_form = -1;                           // form of the matrix the levels' spectral estimates were last taken from
@@ -145,7 +145,6 @@ struct sns_ctx {
     // sweep; put_pending -- the last kernel of a window cycle put its result (the vector named), the next exchange of exactly that
     // vector is comm_put_carried; pc_then_op -- the caller of pc_apply promises that an operator application of the result follows
     // (only then may the fine level's last kernel carry the put: a round nobody consumes would void the windows' flow control)
-    bool fuse_puts = std::getenv("SNS_NO_CARRIED_PUT") == nullptr;      // (A/B switch of the harnesses; not an option)
     bool first_put_carried = false, child_put_carried = false, pc_then_op = false;
     const double* put_pending = nullptr;
     bool first_sweep_done = false;                   // the V-cycle's fine-level first sweep was done by the Krylov kernel that wrote its input
@@ -155,6 +154,10 @@ struct sns_ctx {
     int64_t ctr_retries = 0;                         // damping retries since sns_reset_timings
     int last_first_reason = 0;                       // reason of the FIRST attempt of the last solve (0 = no retry happened)
     std::unique_ptr<Comm> comm;
+    // what the V-cycle runs (csrc/sns_policy.h): the hierarchy's structure, agreed over the ranks when it is built, and the plan the
+    // options make of it (rebuilt by sns_set_options).  Every decision of the cycle reads plan.
+    policy::Facts facts;
+    policy::CyclePlan plan;
     // distributed coarsest level: global dense inverse, replicated on every rank
     int cg_maxn = 0;                              // padded owned coarsest nodes per rank
     int cg_N = 0;                                 // 4 * nranks * cg_maxn (0 = not used)
@@ -194,6 +197,8 @@ int global_sum(sns_ctx* h, double* v, int count);
 int host_allgather(sns_ctx* h, const std::vector<double>& mine, std::vector<double>& all);
 int check_plan_symmetry(sns_ctx* h, const Plan& p, int level);
 int connect_plan(sns_ctx* h, Plan& p);
+int plan_hierarchy(sns_ctx* h);
+const char* plan_buffer_missing(const sns_ctx* h);
 int build_hierarchy(sns_ctx* h, const HostPattern& fine);
 int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix);
 int timed_assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix);
@@ -212,7 +217,7 @@ int norm2(sns_ctx* h, const double* x, double* out);
 int dot(sns_ctx* h, const double* x, const double* y, double* out);
 }  // namespace sns
 
-// ---- small helpers, launch helpers and the cycle's predicates (internal linkage: every translation unit gets its own) ----------
+// ---- small helpers and launch helpers (internal linkage: every translation unit gets its own) -------------------------------
 namespace {
 
 // C-ABI layer (include/sns.h): context, assembly driver, operator hierarchy,
@@ -463,28 +468,15 @@ void launch_lp_fmt(sns_ctx* h, const Level& L, int32_t rows, const double* x, do
     }
 }
 
-inline int lp_format(const sns_ctx* h, const Level& L) {
-    if (h->opt.amg_f32_matrix == 2 && L.vals16) return 2;
-    if (h->opt.amg_f32_matrix && L.vals32) return 1;
-    return 0;
-}
-
+// (fmt: the level's plan, lp_fmt)
 template <int MODE>
-void launch_pc_spmv(sns_ctx* h, const Level& L, int32_t rows, const double* x, double* y, const double* b,
+void launch_pc_spmv(sns_ctx* h, const Level& L, int fmt, int32_t rows, const double* x, double* y, const double* b,
                     double omega, Split sp = Split()) {
-    const int fmt = lp_format(h, L);
     if (fmt == 2) launch_lp_fmt<MODE, 2>(h, L, rows, x, y, b, omega, sp);
     else if (fmt == 1) launch_lp_fmt<MODE, 1>(h, L, rows, x, y, b, omega, sp);
     else launch_spmv<MODE>(h, L, rows, x, y, b, omega, nullptr, sp);
 }
 
-
-// Do the level-0 passes of this handle read their ghost entries straight from the receive window (halo_windows)?
-inline bool fine_windows(const sns_ctx* h) {
-    const Comm* c = h->comm.get();
-    return c && c->windows() && c->nranks > 1 && h->opt.halo_windows && !h->team_overlap && !c->plans.empty() &&
-           c->plans[0].identity_recv && c->plans[0].win_recv[0] != nullptr;
-}
 
 // Level-0 pass whose input needs a halo exchange first (multi-GPU): the exchange of xe's ghost tail runs on the
 // handle's stream (every RCCL call stays on ONE stream, in program order) while the interior rows -- the rows
@@ -501,11 +493,11 @@ int exchange_and_spmv(sns_ctx* h, double* xe, const double* x, double* y, const 
     h->bnd_dot_blocks = 0;
     auto pass = [&](Split sp) {
         if constexpr (MODE == SPMV_B_MINUS_AX || MODE == SPMV_JACOBI) {
-            if (pc) { launch_pc_spmv<MODE>(h, L, rows, x, y, b, omega, sp); return; }
+            if (pc) { launch_pc_spmv<MODE>(h, L, h->plan.level[0].lp_fmt, rows, x, y, b, omega, sp); return; }
         }
         launch_spmv<MODE>(h, L, rows, x, y, b, omega, dotw, sp);
     };
-    if (dist && fine_windows(h) && xe == x) {
+    if (dist && h->plan.fine_windows && xe == x) {
         // window transports: ONE put launch; the pass reads the ghost entries from the receive window and its boundary waves
         // wait for the neighbours' flags themselves -- no unpack, no boundary launch, no second stream
         ++h->ctr_exchange;
@@ -561,33 +553,11 @@ int exchange_and_spmv(sns_ctx* h, double* xe, const double* x, double* y, const 
 }
 
 
-// Aggregate-block Jacobi smoother (amg_block_smooth, csrc/sns_block.hip), symbolic part: the member rows of every aggregate of
-// level L padded to 8 slots.  Levels whose aggregates can have more than 8 members (amg_agg_size > 8) keep the nodal blocks.
-// Aggregate blocks on the FINE level: always with amg_block_smooth = 2; with 1 on a partitioned handle whose share of the fine level is
-// at most amg_block_fine_rows rows per rank -- the latency-bound strong split, where 20 % fewer iterations (and collectives) outweigh
-// the inverse blocks' bytes.  Global counts only: every rank answers alike.
-inline bool fine_blocks_wanted(const sns_ctx* h) {
-    const Comm* c = h->comm.get();
-    return policy::fine_blocks(h->opt, (c && c->active()) ? c->nranks : 1, h->n_global_fine);
-}
-
-// Is level l smoothed with the aggregate blocks?  (options only, no device state: every rank of a partitioned run must answer alike)
-inline bool block_active(const sns_ctx* h, int l) {
-    if (l < 0 || l + 1 >= (int)h->levels.size()) return false;                 // the coarsest level is solved or point-smoothed
-    const Level& L = h->levels[l];
-    if (!L.blk_rows) return false;
-    if (l == 0 && !fine_blocks_wanted(h)) return false;
-    if (h->rep_level > 0 && l == h->rep_level - 1) return false;               // only the source of the replicated copy
-    // (rows per rank, the same figure on every rank: policy::blocks_allowed)
-    const bool replicated = h->rep_level > 0 && l >= h->rep_level;
-    const int nr = (h->comm && h->comm->active() && !replicated) ? std::max(1, h->comm->nranks) : 1;
-    return policy::blocks_allowed(h->opt, L.n_global, nr);
-}
-
-
-// one smoothing sweep y = x + w S (b - A x) of level l: S = the aggregates' inverse blocks where block_active, else the nodal D^-1
-inline void launch_sweep(sns_ctx* h, int l, const Level& L, int32_t rows, const double* x, double* y, const double* b, double omega) {
-    if (block_active(h, l) && L.binv32) {
+// one smoothing sweep y = x + w S (b - A x) of a level: S = the aggregates' inverse blocks where its plan has blocks, else the
+// nodal D^-1
+inline void launch_sweep(sns_ctx* h, const policy::LevelPlan& P, const Level& L, int32_t rows, const double* x, double* y,
+                         const double* b, double omega) {
+    if (P.blocks) {
         const int32_t ns = 8 * L.n_blk;
         const unsigned grid = (unsigned)((ns + 63) / 64);
         if (grid == 0) return;
@@ -599,15 +569,15 @@ inline void launch_sweep(sns_ctx* h, int l, const Level& L, int32_t rows, const 
                                (const void*)L.vals32, (const float*)nullptr, (const void*)L.binv32, x, y, b, omega, GhostSrc(), PutDst());
         return;
     }
-    launch_pc_spmv<SPMV_JACOBI>(h, L, rows, x, y, b, omega);
+    launch_pc_spmv<SPMV_JACOBI>(h, L, P.lp_fmt, rows, x, y, b, omega);
 }
 
 // first sweep of a cycle from the zero guess, z = w S b (omega = 1: S b alone, the spectral estimate's operator)
-inline void launch_first_sweep(sns_ctx* h, int l, const Level& L, int32_t rows, const double* b, double omega, double* z,
-                               PutDst* pd = nullptr) {
+inline void launch_first_sweep(sns_ctx* h, const policy::LevelPlan& P, const Level& L, int32_t rows, const double* b, double omega,
+                               double* z, PutDst* pd = nullptr) {
     if (rows <= 0) return;
     const int g4 = (int)((4 * (int64_t)rows + 255) / 256);
-    if (block_active(h, l) && L.binv32) {
+    if (P.blocks) {
         const int32_t ns = 8 * L.n_blk;
         if (L.binv_fmt == 2)
             hipLaunchKernelGGL((k_bfirst<2>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L.blk_rows,
@@ -618,163 +588,9 @@ inline void launch_first_sweep(sns_ctx* h, int l, const Level& L, int32_t rows, 
         return;
     }
     if (pd) *pd = PutDst();                              // (the nodal first sweeps do not carry a put)
-    if (false) {
-    } else if (lp_format(h, L) != 0 && L.dinv32) {
-        hipLaunchKernelGGL(k_bjacobi32, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv32, b, omega, z);
-    } else {
-        hipLaunchKernelGGL(k_bjacobi, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv, b, omega, z);
-    }
+    if (P.lp_fmt != 0) hipLaunchKernelGGL(k_bjacobi32, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv32, b, omega, z);
+    else hipLaunchKernelGGL(k_bjacobi, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv, b, omega, z);
 }
-
-
-// rows at or below which a level >= 1 ends the hierarchy (it is solved directly)
-inline int coarsest_rows(const sns_options& o) { return policy::coarsest_rows(o); }
-
-
-// |lambda|max of Dinv*A on level l by a few power iterations (device resident; one host sync).
-// The damped block-Jacobi smoother x += w Dinv (b - A x) needs w*|lambda|max < 2; on the reference's
-// operator the fixed w = 0.9 already diverges at 10 M tets, so w is capped per level at the smoothing-optimal 4/(3 |lambda|max).  (Measured cliff on the coarse
-// levels of the 10 M-tet Jacobian: w = 0.80 converges in 45 iterations, w >= 0.82 overflows, although the
-// dominant mode itself is still damped there -- the offending mode is not the one of largest modulus.)
-// (rank-local row count: with the option on, a level's ranks must all fall on the same side of the threshold -- the slab / RCB
-// partitions are balanced to a few rows; off (0, the default) no rank ever takes this path, empty ranks included)
-inline bool level_sx(const sns_ctx* h, const Level& L) {
-    return L.xg && h->opt.amg_sweep_exchange_rows > 0 && L.n_owned <= h->opt.amg_sweep_exchange_rows;
-}
-
-// sweeps per level: the fine level is the expensive one (1 sweep); level 1 and 2 are cheap and are where
-// plain aggregation needs the smoothing (4 and 6); levels >= 3 are launch-bound (2).  Measured on the
-// 10 M-tet Jacobian: (1,4,6,2) 40-42 its / 180-186 ms; (1,4,4,4) 45 / 204; (2,2,2,2) 54 / 323.
-// Large problems (amg_nu_scale_with_size): the plain-aggregation V-cycle loses convergence with its depth, and on a big mesh the
-// levels >= 2 cost next to nothing -- measured on one GPU (profiles/r3_deep_sweeps.txt): 81 M tets 73 / 82 -> 53 / 57 iterations and
-// 1743 -> 1303 ms per Newton step with 10 + 10 sweeps on level 2 and 8 + 8 below instead of 6 + 6 and 2 + 2; 24 M tets 52 / 55 -> 45 / 49
-// with 8 + 8 and 4 + 4; at 10 M tets the extra latency-bound passes cost what they save, so the schedule follows the GLOBAL fine size.
-inline int level_nu(const sns_ctx* h, int l) {
-    const int ll = (h->rep_level > 0 && l >= h->rep_level) ? l - 1 : l;      // the replicated copy is not a new level
-    // (global counts: every rank must arrive at the same schedule -- levels with exchanged sweeps are collective)
-    const int nlev = policy::depth_equivalent(h->opt, (int)h->levels.size() - (h->rep_level > 0 ? 1 : 0),
-                                              h->levels.back().dense_gj != nullptr, h->levels.back().n);
-    const bool small_aggregates = h->n_global_l1 > 0 && (double)h->n_global_fine < 6.0 * (double)h->n_global_l1;
-    const policy::ExtraSweeps e = policy::extra_sweeps(h->opt, h->n_global_fine, nlev, small_aggregates);
-    return policy::level_nu(h->opt, ll, block_active(h, l), e);
-}
-
-// one exchange after the coarse-grid correction makes a SINGLE post-smoothing sweep the exact global block-Jacobi
-// sweep; with several sweeps the ghost values would be frozen while the owned ones move, which measurably hurts
-// the Stokes operator (8 slabs of the 10 M-tet duct: 47 -> 65 iterations) -- so only where nu = 1 (the fine level)
-inline bool level_px(const sns_ctx* h, int l, const Level& L) {
-    return L.xg && !level_sx(h, L) && h->opt.amg_post_exchange && level_nu(h, l) == 1 && (l == 0 || !block_active(h, l));
-}
-
-// Partitioned level l >= 1 cycled with EXACT global sweeps over a window transport (amg_exact_sweeps, round 5): every sweep is
-// preceded by one put launch and reads its ghost entries from the receive window, the coarse-grid correction sits inside the
-// first post-sweep (M = A P), residual + restriction stay one launch -- the single-GPU cycle, distributed.  Options and the
-// hierarchy's global structure only: every rank answers alike.
-inline bool level_exact(const sns_ctx* h, int l) {
-    const Comm* c = h->comm.get();
-    if (!c || !c->windows() || c->nranks <= 1 || !h->opt.halo_windows || !h->opt.amg_exact_sweeps || h->team_overlap) return false;
-    if (l < 1 || l + 1 >= (int)h->levels.size() || (size_t)l >= c->plans.size()) return false;
-    const Level& L = h->levels[l];
-    if (!L.xg || (h->rep_level > 0 && l >= h->rep_level - 1)) return false;     // partitioned AND cycled (not the replicated tail's source)
-    if (level_sx(h, L) || !block_active(h, l) || !L.ap_rowptr) return false;
-    if (!h->opt.amg_fused_post || h->opt.amg_fuse_restrict == 0 || h->opt.pc_type != SNS_PC_AMG) return false;
-    if (!c->plans[l].identity_recv || !c->plans[l].win_recv[0]) return false;
-    const bool rep_src = h->rep_level > 0 && l + 1 == h->rep_level - 1;
-    if (rep_src) return L.ap_colind_rep != nullptr;                             // xc straight from the replicated solution
-    return (size_t)(l + 1) < c->plans.size() && c->plans[l + 1].identity_recv && c->plans[l + 1].win_recv[0] != nullptr;
-}
-
-inline bool uses_ghosts_in_sweeps(const sns_ctx* h, int l, const Level& L) {
-    return level_sx(h, L) || level_px(h, l, L) || level_exact(h, l);
-}
-
-// Stability limit of the smoother damping on level l from the dominant Ritz values of S A (S = the level's smoother blocks,
-// nodal or aggregate): M = 8 Arnoldi steps from the deterministic start vector of the power iteration (classical Gram-Schmidt
-// with one re-orthogonalisation, the FGMRES kernels; one host read per step), eigenvalues of the 8 x 8 Hessenberg matrix on the
-// host (sns_host_hessenberg_eigs).  |1 - w theta| < 1 needs w < 2 Re(theta) / |theta|^2: *limit = the minimum over the Ritz
-// values with |theta| >= 0.5 |theta|max (those a few Arnoldi steps have converged to).  The power iteration above sees the
-// modulus only; on a convection-dominated coarse level the dominant eigenvalues are complex, and a level that runs 1 + 6
-// sweeps amplifies a damping above the limit seven times per cycle (oracle/experiments/r4_damping.py).
-inline void level_sweeps(const sns_ctx* h, int l, int& nu_pre, int& nu_post);
-
-// sweeps before / after the coarse-grid correction on level l (the first pre-sweep is omega D^-1 b)
-inline void level_sweeps(const sns_ctx* h, int l, int& nu_pre, int& nu_post) {
-    const int ll = (h->rep_level > 0 && l >= h->rep_level) ? l - 1 : l;
-    // rank-local sweeps: a partitioned handle (any level: the rule of rounds 2-4) unless the level's sweeps are the exact global
-    // ones (level_exact: then it IS the single-GPU cycle)
-    const bool part = h->comm && h->comm->active() && h->comm->nranks > 1;
-    const bool exact = part && level_exact(h, l);
-    const policy::Sweeps s = policy::level_sweeps(h->opt, ll, block_active(h, l), part && !exact, level_nu(h, l), exact);
-    nu_pre = s.pre;
-    nu_post = s.post;
-}
-
-// Does the restriction from level l also do level l + 1's first sweep (k_restrict with dinv32_c)?  Only where that sweep is
-// the plain rank-local w Dc^-1 bc of a smoothed level on its fp32 D^-1 copy: not the dense coarsest level, not the level whose
-// cycle is the all-gather into the replicated tail (nor that tail's first level, whose right-hand side comes from the gather),
-// not a partitioned level whose sweeps exchange ghost values, not the experimental fine-cycle shapes.
-inline bool restrict_fuses_first(const sns_ctx* h, int l) {
-    const int nl = (int)h->levels.size();
-    const int c = l + 1;
-    if (l < 0 || c + 1 >= nl) return false;
-#ifdef SNS_HARNESS
-    if (std::getenv("SNS_NO_RESTRICT_FUSE")) return false;
-#endif
-    if (h->rep_level > 0 && (c == h->rep_level - 1 || l == h->rep_level - 1)) return false;
-    const Level& C = h->levels[c];
-    // (a partitioned coarse level qualifies too: its first sweep starts from zero and is rank-local by construction -- owned right-hand
-    // side, owned rows of the start buffer, the ghost tail stays as it is --, unless its sweeps exchange ghost values, whose damping
-    // and buffers follow the exchanging code path)
-    if ((C.xg || C.n != C.n_owned) && level_sx(h, C)) return false;
-    if (block_active(h, c)) return C.binv32 != nullptr;    // k_restrict_blk: restriction in the order of the coarse aggregates
-    return lp_format(h, C) != 0 && C.dinv32 != nullptr;
-}
-
-
-// The buffer a smoothed level's cycle starts from (its first sweep z = w D^-1 b is written there; after
-// nu_pre - 1 + nu_post ping-pong swaps the result must sit in x): the ONE place that knows the parity rule -- vcycle() and the
-// restriction of the level above (which writes that first sweep when restrict_fuses_first says so) both ask here.
-inline double* cycle_start_buffer(sns_ctx* h, int l, double* x) {
-    int nu_pre = 1, nu_post = 1;
-    level_sweeps(h, l, nu_pre, nu_post);
-    return ((nu_pre - 1 + nu_post) & 1) ? h->pong[l] : x;
-}
-
-
-// Does level l take the fused coarse-grid correction + first post-smoothing sweep (k_post_lp / k_bpost over M = A P)?  Serial levels
-// always (given M and a low-precision format); a partitioned fine level when its single post-sweep is the exact global one (px).
-// One place for the rule: vcycle() and the callers that choose the cycle's buffers ask here.
-inline bool level_fused_post(const sns_ctx* h, int l) {
-    if (l < 0 || l + 1 >= (int)h->levels.size()) return false;
-    const Level& L = h->levels[l];
-    int nu_pre = 1, nu_post = 1;
-    level_sweeps(h, l, nu_pre, nu_post);
-    const int fmt_l = lp_format(h, L);
-    const bool have_m = h->opt.amg_fused_post && L.ap_rowptr && fmt_l != 0 && L.dinv32 &&
-                        (fmt_l == 2 ? L.ap_vals16 != nullptr : L.ap_vals32 != nullptr) && nu_post >= 1 && !level_sx(h, L);
-    return have_m && (!L.xg || (l == 0 && level_px(h, l, L) && level_nu(h, l) == 1));
-}
-
-// A partitioned fine level in that mode never READS the ghost tails of its cycle buffers with the "ghosts are zero" assumption (no
-// rank-local sweep runs there: the first sweep starts from zero, the post-sweep goes over M): the halo of the residual can land in
-// the iterate's own tail, the tails need no clearing, and the cycle can run in the caller's vector.
-inline bool fine_tails_unused(const sns_ctx* h) {
-    return h->levels.size() >= 2 && h->levels[0].xg && !(h->rep_level == 1) && level_fused_post(h, 0);
-}
-
-
-// First level (>= 1) small enough that its kernels are launch-bound rather than bandwidth-bound: it and everything
-// below run as one graph.  10 M tets: level 2 (36 k rows; level 1 has 218 k rows = 46 us per sweep); 1 M tets: level 1.
-inline int serial_graph_level(const sns_ctx* h) {
-    int max_rows = policy::GRAPH_MAX_ROWS;
-#ifdef SNS_HARNESS
-    if (std::getenv("SNS_GRAPH_ROWS")) max_rows = std::atoi(std::getenv("SNS_GRAPH_ROWS"));
-#endif
-    for (int l = 1; l < (int)h->levels.size(); ++l)
-        if (h->levels[l].n <= max_rows) return l;
-    return 0;
-}
-
 
 // one aggregate-block sweep of a partitioned level with the ghost entries of x from the level's receive window
 inline void launch_sweep_windows(sns_ctx* h, const Level& L, const double* x, double* y, const double* b, double omega, const GhostSrc& gs,
@@ -788,40 +604,6 @@ inline void launch_sweep_windows(sns_ctx* h, const Level& L, const double* x, do
     else
         hipLaunchKernelGGL((k_bsweep<1, 1>), dim3(grid), dim3(256), 0, h->stream, ns, L.blk_rows, L.rowptr, L.colind,
                            (const void*)L.vals32, (const float*)nullptr, (const void*)L.binv32, x, y, b, omega, gs, pd);
-}
-
-
-// Do both halves of the all-gather of the replicated tail's right-hand side ride in solver kernels (AgPut in the residual +
-// restriction of the level above the source, AgGet in the tail's first sweep: k_bfirst_gather)?  The level above the source must
-// run the window cycle with the fused residual + restriction (a level >= 1), the tail's first level must take aggregate blocks,
-// and a rank's piece must fit the staging area.
-inline bool level_exact(const sns_ctx* h, int l);
-inline bool rep_gather_first(const sns_ctx* h) {
-    const Comm* c = h->comm.get();
-    if (!c || !c->windows() || c->nranks <= 1 || !h->opt.halo_windows || h->rep_level < 3) return false;
-    if (!level_exact(h, h->rep_level - 2)) return false;
-    const Level& C = h->levels[h->rep_level];
-    if (!block_active(h, h->rep_level) || !C.binv32 || C.n_blk <= 0 || !h->rep_rowmap) return false;
-    return (size_t)4 * h->rep_maxn * (size_t)c->nranks <= c->peer->ag_doubles;
-}
-
-// Does level l run the window form of the cycle (vcycle_windows)?  The fine level: its passes read the receive window and its
-// single post-sweep is the fused exact one; a level >= 1: level_exact.
-inline bool level_windows(const sns_ctx* h, int l) {
-    if (l == 0) {
-        const Comm* c = h->comm.get();
-        return fine_windows(h) && fine_tails_unused(h) && c->plans.size() > 1 && c->plans[1].identity_recv &&
-               c->plans[1].win_recv[0] != nullptr;
-    }
-    return level_exact(h, l);
-}
-
-// the put of the fine level's first sweep when a Krylov kernel runs that sweep (k_bfirst_bicg): empty unless the fine level runs
-// the window form of the cycle
-inline PutDst first_sweep_put(const sns_ctx* h) {
-    const Comm* c = h->comm.get();
-    if (!h->fuse_puts || !c || !c->peer || !level_windows(h, 0)) return PutDst();
-    return comm_put_dst(c, c->plans[0]);
 }
 
 

@@ -7,28 +7,17 @@ namespace sns {
 
 // Coarse part of the cycle (the graph level and below) as ONE hipGraph launch.  Captured on a private
 // stream (the caller's stream may be the legacy default stream, which cannot be captured), re-captured when
-// the per-level damping or the cycle shape changed.  Distributed runs keep direct launches (the exchange
-// inside the cycle is a host-driven RCCL group).  Any capture failure disables the graph for good.
+// the per-level damping or the plan of the levels it covers changed.  Distributed runs capture the replicated tail only (the
+// exchanges above it are host-driven).  Any capture failure disables the graph for good.
 int coarse_cycle(sns_ctx* h, int l, const double* b, double* x) {
-    const bool dist = h->comm && h->comm->active() && h->comm->nranks > 1;
-    // distributed runs: only the replicated tail is free of exchanges and can be captured
-    const int gl = dist ? h->rep_level : serial_graph_level(h);
+    const int gl = h->plan.graph_level;
     if (gl <= 0 || l != gl || h->graph_disabled || (int)h->levels.size() <= gl + 1) return vcycle(h, l, b, x);
-    std::vector<double> sig;
+    // signature: the graph level, whether its first sweeps are done outside the graph, every omega, the plan rows from the level
+    // above the graph down
+    std::vector<double> sig = {(double)gl, (double)h->plan.rep_gather_first};
     for (auto& L : h->levels) sig.push_back(L.omega);
-    sig.push_back(h->opt.amg_nu); sig.push_back(h->opt.amg_nu_coarse); sig.push_back(h->opt.amg_nu_deep);
-    sig.push_back(h->opt.amg_nu_l2);
-    sig.push_back(h->opt.amg_nu_l1_pre); sig.push_back(h->opt.amg_nu_l1_post);
-    sig.push_back(h->opt.amg_f32_matrix);
-    sig.push_back(h->opt.amg_fused_post);
-    sig.push_back(h->opt.amg_nu_scale_with_size);
-    sig.push_back(h->opt.amg_block_smooth); sig.push_back(h->opt.amg_bnu_l1); sig.push_back(h->opt.amg_bnu_l2);
-    sig.push_back(h->opt.amg_bnu_deep); sig.push_back(h->opt.amg_block_max_rows); sig.push_back(h->opt.amg_block_fine_rows);
-    sig.push_back(h->opt.amg_fuse_restrict);
-    sig.push_back(restrict_fuses_first(h, gl - 1) ? 1.0 : 0.0);
-    sig.push_back(rep_gather_first(h) ? 1.0 : 0.0);
-    sig.push_back(gl);
-    if (!h->coarse_graph || sig != h->graph_sig) {
+    const std::vector<policy::LevelPlan> rows(h->plan.level.begin() + (gl - 1), h->plan.level.end());
+    if (!h->coarse_graph || sig != h->graph_sig || rows != h->graph_rows) {
         if (h->coarse_graph) { (void)hipGraphExecDestroy(h->coarse_graph); h->coarse_graph = nullptr; }
         if (!h->cap_stream && hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) != hipSuccess) {
             h->graph_disabled = true;
@@ -53,6 +42,7 @@ int coarse_cycle(sns_ctx* h, int l, const double* b, double* x) {
             return vcycle(h, l, b, x);
         }
         h->graph_sig = sig;
+        h->graph_rows = rows;
     }
     HIP_TRY(hipGraphLaunch(h->coarse_graph, h->stream));
     return SNS_OK;
@@ -62,7 +52,7 @@ int coarse_cycle(sns_ctx* h, int l, const double* b, double* x) {
 // The V-cycle of a PARTITIONED level over a window transport (peer windows / the in-process team; round 5).  Every exchange is one
 // put launch (comm_put) and the pass behind it reads the ghost entries from the level's receive window, its boundary waves waiting
 // for the neighbours themselves: no staging copy, no unpack, no split pass.  Level 0: first sweep | put, residual | restriction
-// (+ level 1's first sweep) | coarse | put of level 1's solution, fused correction + post-sweep.  Level >= 1 (level_exact): the
+// (+ level 1's first sweep) | coarse | put of level 1's solution, fused correction + post-sweep.  Level >= 1 (plan exact): the
 // single-GPU schedule with exact global sweeps -- [put, sweep]* | put, residual + restriction (+ next first sweep) in one launch |
 // coarse | fused correction + first post-sweep (the coarse solution read straight from the replicated tail where that is the next
 // level, else after a put of it) | [put, sweep]*.
@@ -71,22 +61,23 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     Level& C = h->levels[l + 1];
     Comm* c = h->comm.get();
     const Plan& P = c->plans[l];
+    const policy::LevelPlan& Q = h->plan.level[(size_t)l];
+    const policy::LevelPlan& QC = h->plan.level[(size_t)l + 1];
     const int32_t rows = L.n_owned;
     const double om = L.omega;
-    int nu_pre = 1, nu_post = 1;
-    level_sweeps(h, l, nu_pre, nu_post);
-    double* cur = cycle_start_buffer(h, l, x);
+    const int nu_pre = Q.pre, nu_post = Q.post;
+    double* cur = Q.start_odd ? h->pong[l] : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
     double* oth = (cur == x) ? h->pong[l] : x;
     // The put of every exchange of this level's iterate rides in the kernel that PRODUCES the iterate (PutDst) where that is an
     // aggregate-block kernel: `carried` says whether the vector about to be exchanged has been put already
-    const bool blk = block_active(h, l) && L.binv32 != nullptr;
-    const PutDst pdl = (h->fuse_puts && blk && rows > 0) ? comm_put_dst(c, P) : PutDst();
+    const bool blk = Q.blocks != 0;
+    const PutDst pdl = (h->plan.fuse_puts && blk && rows > 0) ? comm_put_dst(c, P) : PutDst();
     bool carried = false;
     if (l == 0 && h->first_sweep_done) carried = h->first_put_carried;
-    else if (l > 0 && restrict_fuses_first(h, l - 1)) carried = h->child_put_carried;
+    else if (l > 0 && h->plan.level[(size_t)l - 1].fuses_next_first) carried = h->child_put_carried;
     else if (rows > 0) {
         PutDst pd1 = pdl;
-        launch_first_sweep(h, l, L, rows, b, om, cur, &pd1);
+        launch_first_sweep(h, Q, L, rows, b, om, cur, &pd1);
         carried = pd1.sr_ptr != nullptr;
     }
     h->first_put_carried = h->child_put_carried = false;
@@ -107,16 +98,16 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     const bool rep_src = h->rep_level > 0 && l + 1 == h->rep_level - 1;
     double* cb = rep_src ? h->rep_bsend : C.b;
     const double* cx = rep_src ? h->levels[h->rep_level].x + 4 * (size_t)h->rep_off : C.x;
-    const bool fuse = restrict_fuses_first(h, l);
+    const bool fuse = Q.fuses_next_first != 0;
     const float* dc = fuse ? C.dinv32 : nullptr;
-    double* zc = fuse ? cycle_start_buffer(h, l + 1, C.x) : nullptr;
-    const int fmt = lp_format(h, L);
+    double* zc = !fuse ? nullptr : QC.start_odd ? h->pong[l + 1] : C.x;
+    const int fmt = Q.lp_fmt;
     // residual (+ restriction): the true residual needs the neighbours' iterate
     SNS_TRY(put(P, cur, carried));
     carried = false;
     const GhostSrc gs = comm_ghost_src(c, P);
     // (the next level's first sweep, written by the restriction, is exchanged first thing in its cycle: put from here)
-    const PutDst pdc = (h->fuse_puts && fuse && block_active(h, l + 1) && !rep_src && level_windows(h, l + 1) && C.n_owned > 0 &&
+    const PutDst pdc = (h->plan.fuse_puts && fuse && QC.blocks && !rep_src && QC.windows && C.n_owned > 0 &&
                         (l == 0 || rows > 0))
                            ? comm_put_dst(c, c->plans[l + 1]) : PutDst();
     h->child_put_carried = pdc.sr_ptr != nullptr;
@@ -124,9 +115,9 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
         Split s3;
         s3.mode = 3;
         s3.gs = gs;
-        if (rows > 0) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, rows, cur, L.r, b, 0.0, s3);
+        if (rows > 0) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, fmt, rows, cur, L.r, b, 0.0, s3);
         if (C.n_owned > 0) {
-            if (fuse && block_active(h, 1)) {
+            if (fuse && QC.blocks) {
                 const int32_t ns = 8 * C.n_blk;
                 if (C.binv_fmt == 2)
                     hipLaunchKernelGGL((k_restrict_blk<2>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
@@ -142,8 +133,8 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     } else if (rows > 0 && C.n_owned > 0) {
         // (the level below is the source of the replicated tail: the restricted right-hand side goes straight into every rank's
         // all-gather staging area, the tail's first sweep waits for it -- rep_gather_first)
-        const AgPut agp = (rep_src && rep_gather_first(h)) ? comm_ag_put(c, 4 * (int64_t)h->rep_maxn) : AgPut();
-        const int mode = !fuse ? 0 : (block_active(h, l + 1) ? 2 : 1);
+        const AgPut agp = (rep_src && h->plan.rep_gather_first) ? comm_ag_put(c, 4 * (int64_t)h->rep_maxn) : AgPut();
+        const int mode = !fuse ? 0 : (QC.blocks ? 2 : 1);
         const int32_t* slots = mode == 2 ? C.blk_rows : nullptr;
         const int32_t n_slots = mode == 2 ? 8 * C.n_blk : C.n_owned;
         const unsigned grid = (unsigned)((n_slots + 7) / 8);
@@ -173,10 +164,10 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     h->put_pending = nullptr;
     // this level's result is exchanged next by the level above (its correction reads it) or, the fine level's, by the operator
     // application the caller of pc_apply has promised: the last kernel of the cycle puts it
-    const bool last_puts = pdl.sr_ptr && (l == 0 ? h->pc_then_op : level_windows(h, l - 1));
+    const bool last_puts = pdl.sr_ptr && (l == 0 ? h->pc_then_op : h->plan.level[(size_t)l - 1].windows != 0);
     if (rows > 0) {
         if (l == 0) time_begin(h, 4);
-        if (block_active(h, l) && L.binv32) {
+        if (blk) {
             const int32_t ns = 8 * L.n_blk;
             const unsigned gb = (unsigned)((ns + 63) / 64);
             const void* mv = fmt == 2 ? (const void*)L.ap_vals16 : (const void*)L.ap_vals32;
@@ -190,7 +181,7 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
             else           { if (fmt == 2) SNS_BPW(2, 0); else SNS_BPW(1, 0); }
 #undef SNS_BPW
         } else {
-            const int grid = (rows + 63) / 64;             // (nodal blocks: the fine level only, see level_exact)
+            const int grid = (rows + 63) / 64;             // (nodal blocks: the fine level only, see the plan's exact)
             if (fmt == 2)
                 hipLaunchKernelGGL((k_post_lp<2, 2>), dim3(grid), dim3(256), 0, h->stream, rows, L.ap_rowptr, L.ap_colind, L.ap_vals16,
                                    L.ap_scale16, xc, (const double*)cur, (const double*)L.r, L.dinv32, om, L.agg, L.free_mask, oth, gc);
@@ -225,19 +216,20 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     const bool last = (l + 1 == (int)h->levels.size());
     const double om = L.omega;
     const int g4 = (int)((4 * (int64_t)rows + 255) / 256);
+    const policy::LevelPlan& Q = h->plan.level[(size_t)l];
     if (h->rep_level > 0 && l == h->rep_level - 1) {
         // all-gather the right-hand side, cycle the replicated tail, keep my rows of the result
         Level& C = h->levels[h->rep_level];
         if (rows > 0 && b != h->rep_bsend)                   // (vcycle of the level above restricts straight into rep_bsend)
             HIP_TRY(hipMemcpyAsync(h->rep_bsend, b, 4 * (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         Comm* cm = h->comm.get();
-        if (rep_gather_first(h)) {
+        if (h->plan.rep_gather_first) {
             // both halves of the all-gather ride in solver kernels: the residual + restriction of the level above has stored this
             // rank's piece into every rank's staging area, the first sweep of the replicated level waits for the pieces itself
             SNS_TRY(peer_check(cm));
             SNS_TRY(comm_host_barrier(cm, h->stream));
             const int32_t ns = 8 * C.n_blk;
-            double* zc = cycle_start_buffer(h, h->rep_level, C.x);
+            double* zc = h->plan.level[(size_t)h->rep_level].start_odd ? h->pong[h->rep_level] : C.x;
             if (C.binv_fmt == 2)
                 hipLaunchKernelGGL((k_bfirst_gather<2>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
                                    (const void*)C.binv32, C.omega, zc, C.b, h->rep_rowmap, comm_ag_get(cm));
@@ -288,52 +280,49 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
         if (rows == 0) return SNS_OK;
         hipLaunchKernelGGL(k_bjacobi, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv, b, om, cur);
         for (int s = 0; s < 8; ++s) {       // even count: result ends in x
-            launch_pc_spmv<SPMV_JACOBI>(h, L, rows, cur, oth, b, om);
+            launch_pc_spmv<SPMV_JACOBI>(h, L, Q.lp_fmt, rows, cur, oth, b, om);
             std::swap(cur, oth);
         }
         return SNS_OK;
     }
-    if (level_windows(h, l)) return vcycle_windows(h, l, b, x);
-    const int nu = level_nu(h, l);
-    int nu_pre = nu, nu_post = nu;
-    level_sweeps(h, l, nu_pre, nu_post);
-    double* cur = cycle_start_buffer(h, l, x);
+    if (Q.windows) return vcycle_windows(h, l, b, x);
+    const policy::LevelPlan& QC = h->plan.level[(size_t)l + 1];
+    const int nu = Q.nu, nu_pre = Q.pre, nu_post = Q.post;
+    double* cur = Q.start_odd ? h->pong[l] : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
     double* oth = (cur == x) ? h->pong[l] : x;
     // distributed: on levels with few rows per rank the sweeps see the neighbours' current iterate (one small
     // exchange per sweep); on the big levels they stay rank-local (ghost values zero) and only the residual is exact
-    const bool sx = level_sx(h, L);
+    const bool sx = Q.sx != 0;
     // ... and the sweeps AFTER the coarse-grid correction take the neighbours' corrected iterate as (frozen) ghost
     // values: with zero ghosts they would see the whole correction as a residual along the partition interfaces
-    const bool px = level_px(h, l, L);
+    const bool px = Q.px != 0;
     const size_t ghost4 = 4 * (size_t)(L.n - rows);
-    const bool tails_unused = (l == 0) && fine_tails_unused(h);
+    const bool tails_unused = (l == 0) && h->plan.fine_tails_unused;
     if (px && ghost4 > 0 && !tails_unused) {
         HIP_TRY(hipMemsetAsync(cur + 4 * (size_t)rows, 0, ghost4 * sizeof(double), h->stream));
         HIP_TRY(hipMemsetAsync(oth + 4 * (size_t)rows, 0, ghost4 * sizeof(double), h->stream));
     }
     // first sweep from a zero guess: z = omega D^-1 b, with the D^-1 copy the other sweeps of this level read (already done
-    // by the restriction kernel of the level above where restrict_fuses_first says so)
-    if (rows > 0 && !(l > 0 && restrict_fuses_first(h, l - 1)) && !(l == 0 && h->first_sweep_done) &&
-        !(h->rep_level > 0 && l == h->rep_level && rep_gather_first(h)))
-        launch_first_sweep(h, l, L, rows, b, om, cur);
+    // by the restriction kernel of the level above where its plan fuses it)
+    if (rows > 0 && !(l > 0 && h->plan.level[(size_t)l - 1].fuses_next_first) && !(l == 0 && h->first_sweep_done) &&
+        !(h->rep_level > 0 && l == h->rep_level && h->plan.rep_gather_first))
+        launch_first_sweep(h, Q, L, rows, b, om, cur);
     if (l == 0) h->first_sweep_done = false;
     for (int s = 1; s < nu_pre; ++s) {
         if (sx) SNS_TRY(exchange_level(h, l, cur));
-        launch_sweep(h, l, L, rows, cur, oth, b, om);
+        launch_sweep(h, Q, L, rows, cur, oth, b, om);
         std::swap(cur, oth);
     }
     Level& C = h->levels[l + 1];
     // Below the fine level the residual and the restriction (+ the next level's first sweep) are ONE launch (k_resid_restrict):
     // `xres` is then the vector the residual reads and the pass itself is issued with the restriction further down.
-    const int fmt_rr = lp_format(h, L);
     // (amg_fuse_restrict = 2: a single-GPU fine level as well -- its residual kernel is the tuned k_spmv_lp, kept by default)
-    const bool rr_level = l >= 1 || (h->opt.amg_fuse_restrict >= 2 && !L.xg);
-    const bool rr_fused = rr_level && h->opt.amg_fuse_restrict != 0 && fmt_rr != 0 && rows > 0 && C.n_owned > 0 && L.m_ptr &&
-                          (!block_active(h, l + 1) || !restrict_fuses_first(h, l) || C.binv_fmt == fmt_rr);
+    const int fmt_rr = Q.lp_fmt;
+    const bool rr_fused = Q.fused_restrict && rows > 0 && C.n_owned > 0;
     const double* xres = cur;
     if (sx) {
         SNS_TRY(exchange_level(h, l, cur));
-        if (!rr_fused) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, rows, cur, L.r, b, 0.0);
+        if (!rr_fused) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, fmt_rr, rows, cur, L.r, b, 0.0);
     } else if (L.xg && tails_unused) {
         // (fine level, fused post-sweep: the halo lands in the iterate's own ghost tail, no copy into the exchange vector)
         SNS_TRY(exchange_and_spmv<SPMV_B_MINUS_AX>(h, cur, cur, L.r, b, 0.0, nullptr, true));
@@ -344,10 +333,10 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
         } else {
             SNS_TRY(exchange_level(h, l, L.xg));
             xres = L.xg;
-            if (!rr_fused) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, rows, L.xg, L.r, b, 0.0);
+            if (!rr_fused) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, fmt_rr, rows, L.xg, L.r, b, 0.0);
         }
     } else if (!rr_fused) {
-        launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, rows, cur, L.r, b, 0.0);
+        launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, fmt_rr, rows, cur, L.r, b, 0.0);
     }
     // the level below is only the source of the replicated tail: its right-hand side is restricted straight into the all-gather's
     // send buffer, and the correction is prolongated straight from this rank's rows of the replicated solution (no copies)
@@ -358,14 +347,14 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
         // the restriction also does the next level's first sweep (z = w Dc^-1 bc into the buffer that level starts from)
         const float* dc = nullptr;
         double* zc = nullptr;
-        const bool fuse = restrict_fuses_first(h, l);
+        const bool fuse = Q.fuses_next_first != 0;
         if (fuse) {
             dc = C.dinv32;
-            zc = cycle_start_buffer(h, l + 1, C.x);          // (coarse_cycle below is called with x = C.x)
+            zc = QC.start_odd ? h->pong[l + 1] : C.x;        // (the buffer its cycle starts from: coarse_cycle below is called with x = C.x)
         }
         if (rr_fused) {
             // mode of the coarse level's first sweep: 0 none, 1 nodal D^-1, 2 its aggregate blocks (walked in THEIR order)
-            const int mode = !fuse ? 0 : (block_active(h, l + 1) ? 2 : 1);
+            const int mode = !fuse ? 0 : (QC.blocks ? 2 : 1);
             const int32_t* slots = mode == 2 ? C.blk_rows : nullptr;
             const int32_t n_slots = mode == 2 ? 8 * C.n_blk : C.n_owned;
             const unsigned grid = (unsigned)((n_slots + 7) / 8);
@@ -379,7 +368,7 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
             else             { if (mode == 2) SNS_RR(1, 2); else if (mode == 1) SNS_RR(1, 1); else SNS_RR(1, 0); }
             if (l == 0) time_end(h);
 #undef SNS_RR
-        } else if (fuse && block_active(h, l + 1)) {
+        } else if (fuse && QC.blocks) {
             const int32_t ns = 8 * C.n_blk;
             if (C.binv_fmt == 2)
                 hipLaunchKernelGGL((k_restrict_blk<2>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
@@ -399,8 +388,8 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     // of A and the prolongation kernel disappears.  Serial levels always; a distributed fine level when its single
     // post-sweep is the exact global one (px): the ghost aggregates' corrections arrive by ONE level-(l+1) exchange
     // instead of the level-l halo of the corrected iterate.
-    const int fmt_l = lp_format(h, L);
-    const bool fused_post = level_fused_post(h, l);
+    const int fmt_l = Q.lp_fmt;
+    const bool fused_post = Q.fused_post != 0;
     if (fused_post) {
         const double* xc = cx;
         if (L.xg) {                                    // distributed fine level: xc incl. the neighbours' aggregates
@@ -413,7 +402,7 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
             const int grid = (rows + 63) / 64;
             const bool fine = (l == 0);
             if (fine) time_begin(h, 4);
-            if (block_active(h, l) && L.binv32) {
+            if (Q.blocks) {
                 const int32_t ns = 8 * L.n_blk;
                 const unsigned gb = (unsigned)((ns + 63) / 64);
                 if (fmt_l == 2)
@@ -464,7 +453,7 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     }
     for (int s = s_first; s < nu_post; ++s) {
         if (sx) SNS_TRY(exchange_level(h, l, cur));
-        launch_sweep(h, l, L, rows, cur, oth, b, om);
+        launch_sweep(h, Q, L, rows, cur, oth, b, om);
         std::swap(cur, oth);
     }
     // cur == x by construction of the start buffer
@@ -497,7 +486,7 @@ static int pc_apply_inner(sns_ctx* h, const double* r, double* z) {
                 // ranks, like PETSc's parallel default bjacobi).  z's ghost tail may hold halo data, so cycle
                 // in internal buffers whose tails are never written and copy the owned part out.
                 // (fine_tails_unused: nothing in the fine level's cycle reads a ghost tail as zero -- no internal buffer, no copy)
-                if (fine_tails_unused(h)) return vcycle(h, 0, r, z);
+                if (h->plan.fine_tails_unused) return vcycle(h, 0, r, z);
                 SNS_TRY(vcycle(h, 0, r, h->levels[0].x));
                 HIP_TRY(hipMemcpyAsync(z, h->levels[0].x, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
                 return SNS_OK;

@@ -689,15 +689,30 @@ extern "C" int sns_host_cycle_policy(const sns_options* opt, int nranks, int win
         sns::set_error("sns_host_cycle_policy: bad arguments (1..16 levels, rep_level 0 or in [2, nlevels))");
         return SNS_E_ARG;
     }
-    bool hb[16];
-    for (int l = 0; l < nlevels; ++l) hb[l] = has_blocks ? has_blocks[l] != 0 : true;
-    sns::policy::LevelRow rows[16];
-    sns::policy::cycle_table(*opt, nranks, windows != 0, nlevels, rows_global, rep_level, rows_global_l1, hb, rows);
+    // the hierarchy as the options and the global counts describe it: every level window-capable, M = A P everywhere, every rank
+    // within the sweep-exchange threshold, the last level solved as its size asks
+    sns::policy::Facts f;
+    f.nranks = nranks;
+    f.rep_level = rep_level;
+    f.rows.assign(rows_global, rows_global + nlevels);
+    f.max_owned.assign((size_t)nlevels, 0);
+    f.has_blocks.assign((size_t)nlevels, 1);
+    if (has_blocks)
+        for (int l = 0; l < nlevels; ++l) f.has_blocks[(size_t)l] = has_blocks[l] != 0;
+    f.has_ap.assign((size_t)nlevels, 1);
+    f.has_ap_rep.assign((size_t)nlevels, 1);
+    f.win_capable.assign((size_t)nlevels, 1);
+    f.rows_global_l1 = rows_global_l1;
+    f.windows = windows != 0;
+    f.rep_gather_fits = true;
+    f.last = sns::policy::coarsest_kind(*opt, rows_global[nlevels - 1]);
+    const sns::policy::CyclePlan p = sns::policy::plan_cycle(*opt, f);
     for (int l = 0; l < nlevels; ++l) {
-        kind[l] = rows[l].cycled ? rows[l].kind : -1;
-        nu_pre[l] = rows[l].pre;
-        nu_post[l] = rows[l].post;
-        if (exact) exact[l] = rows[l].exact;
+        const sns::policy::LevelPlan& q = p.level[(size_t)l];
+        kind[l] = q.cycled ? q.kind : -1;
+        nu_pre[l] = q.cycled ? q.pre : 0;
+        nu_post[l] = q.cycled ? q.post : 0;
+        if (exact) exact[l] = q.exact;
     }
     return SNS_OK;
 }

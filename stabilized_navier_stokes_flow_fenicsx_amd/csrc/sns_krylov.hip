@@ -29,15 +29,22 @@ int dot(sns_ctx* h, const double* x, const double* y, double* out) {
 
 // Can the Krylov kernel that writes the preconditioner's input also do the V-cycle's first fine-level sweep z = w D^-1 (input)
 // (k_bicg_s_first / k_bicg_xrp_first: one dependent launch and one read of the input less per cycle)?  Returns the buffer the
-// cycle of pc_apply(., zdst) starts from, or nullptr.
+// cycle of pc_apply(., zdst) starts from, or nullptr.  (n_owned, n_blk: a rank without rows or blocks launches nothing there)
 double* fused_first_sweep_target(sns_ctx* h, double* zdst) {
     if (h->opt.pc_type != SNS_PC_AMG || h->levels.size() < 2 || !h->pc_ready) return nullptr;
     const Level& L = h->levels[0];
-    if (lp_format(h, L) == 0 || !L.dinv32 || L.n_owned <= 0) return nullptr;
-    if (block_active(h, 0) && (!L.binv32 || L.n_blk <= 0)) return nullptr;      // (aggregate blocks: k_bfirst_bicg, see fused_vector_kernel)
+    const policy::LevelPlan& P = h->plan.level[0];
+    if (P.lp_fmt == 0 || L.n_owned <= 0) return nullptr;
+    if (P.blocks && L.n_blk <= 0) return nullptr;                // (aggregate blocks: k_bfirst_bicg, see fused_vector_kernel)
     if (h->rep_level == 1) return nullptr;                       // level 0 is only the source of the replicated copy
-    double* x = (h->n > h->n_owned && !fine_tails_unused(h)) ? h->levels[0].x : zdst;   // (as pc_apply chooses the cycle's vector)
-    return cycle_start_buffer(h, 0, x);
+    double* x = (h->n > h->n_owned && !h->plan.fine_tails_unused) ? h->levels[0].x : zdst;   // (as pc_apply chooses the cycle's vector)
+    return P.start_odd ? h->pong[0] : x;
+}
+
+// the put that kernel carries (k_bfirst_bicg): empty unless the fine level runs the window form of the cycle
+static PutDst fine_first_put(const sns_ctx* h) {
+    if (!h->plan.fuse_puts || !h->plan.level[0].windows) return PutDst();
+    return comm_put_dst(h->comm.get(), h->comm->plans[0]);
 }
 
 
@@ -98,10 +105,10 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
         for (its = 1;; ++its) {
             if (double* z1 = fused_first_sweep_target(h, sh)) {
                 const Level& L0 = h->levels[0];
-                if (block_active(h, 0)) {
+                if (h->plan.level[0].blocks) {
                     const int32_t ns = 8 * L0.n_blk;
                     const unsigned gb = (unsigned)((ns + 63) / 64);
-                    const PutDst pd0 = first_sweep_put(h);
+                    const PutDst pd0 = fine_first_put(h);
                     h->first_put_carried = pd0.sr_ptr != nullptr;
                     if (L0.binv_fmt == 2)
                         hipLaunchKernelGGL((k_bfirst_bicg<2, 1>), dim3(gb), dim3(256), 0, h->stream, ns, L0.blk_rows, (const void*)L0.binv32,
@@ -131,10 +138,10 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
             if (spec) {
                 if (double* z1 = fused_first_sweep_target(h, ph)) {
                     const Level& L0 = h->levels[0];
-                    if (block_active(h, 0)) {
+                    if (h->plan.level[0].blocks) {
                         const int32_t ns = 8 * L0.n_blk;
                         const unsigned gb = (unsigned)((ns + 63) / 64);
-                        const PutDst pd0 = first_sweep_put(h);
+                        const PutDst pd0 = fine_first_put(h);
                         h->first_put_carried = pd0.sr_ptr != nullptr;
                         if (L0.binv_fmt == 2)
                             hipLaunchKernelGGL((k_bfirst_bicg<2, 2>), dim3(gb), dim3(256), 0, h->stream, ns, L0.blk_rows,

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "sns.h"
 
@@ -79,7 +80,7 @@ inline int depth_equivalent(const sns_options& o, int nlevels_smoothed_and_last,
 // sweeps per half cycle of level `ll` (its number in the hierarchy as coarsened: the replicated copy is not a new level).
 // Nodal blocks: the fine level is the expensive one (1 sweep); levels 1 and 2 are cheap and are where plain aggregation needs
 // the smoothing (4 and 6); levels >= 3 are launch-bound (2).  Aggregate blocks: one sweep is worth about two nodal sweeps.
-inline int level_nu(const sns_options& o, int ll, bool blocks, const ExtraSweeps& e) {
+inline int half_cycle_sweeps(const sns_options& o, int ll, bool blocks, const ExtraSweeps& e) {
     if (blocks && ll >= 1) {
         if (ll >= 3) return std::max(1, o.amg_bnu_deep) + (e.deep + 1) / 2;
         if (ll == 2) return std::max(1, o.amg_bnu_l2) + (e.l2 + 1) / 2;
@@ -99,7 +100,7 @@ inline int level_nu(const sns_options& o, int ll, bool blocks, const ExtraSweeps
 // 10 M-tet duct needs 91 / 89 instead of 98 / 95 iterations for it (profiles/r5_l1_schedules.txt; 4 + 4 rank-local: 91 / 97).
 // amg_nu_l1_pre / _post fix the counts.
 struct Sweeps { int pre = 1, post = 1; };
-inline Sweeps level_sweeps(const sns_options& o, int ll, bool blocks, bool rank_local_sweeps, int nu, bool exact_partitioned = false) {
+inline Sweeps pre_post_sweeps(const sns_options& o, int ll, bool blocks, bool rank_local_sweeps, int nu, bool exact_partitioned = false) {
     Sweeps s;
     s.pre = s.post = nu;
     if (ll == 1) {
@@ -115,47 +116,134 @@ inline Sweeps level_sweeps(const sns_options& o, int ll, bool blocks, bool rank_
     return s;
 }
 
-// ---- the table: what a hierarchy of the given shape runs ------------------------------------------------------------------------
-// rows[l]: GLOBAL rows of level l as held (a replicated level: its rows); rep_level: first replicated level (0: none; the level
-// before it is only the source of the copy and is not cycled); windows: the transport reads ghost entries from receive windows
-// (peer / team) and amg_exact_sweeps applies; has_blocks[l]: the level's aggregates have at most 8 members (its smoother blocks
-// exist).  kind: SNS_LEVEL_* of include/sns.h.
-struct LevelRow { int kind = 0, pre = 0, post = 0, exact = 0, cycled = 1; };
-inline void cycle_table(const sns_options& o, int nranks, bool windows, int nlevels, const int64_t* rows, int rep_level,
-                        int64_t rows_global_l1, const bool* has_blocks, LevelRow* out) {
-    const int last = nlevels - 1;
-    const bool part = nranks > 1;
-    const int n_as_coarsened = nlevels - (rep_level > 0 ? 1 : 0);
-    const CoarsestKind ck = coarsest_kind(o, rows[last]);
-    const bool small_agg = rows_global_l1 > 0 && (double)rows[0] < 6.0 * (double)rows_global_l1;
-    const ExtraSweeps e = extra_sweeps(o, rows[0], depth_equivalent(o, n_as_coarsened, ck == COARSEST_BLOCKED_INVERSE && nlevels > 1, rows[last]),
-                                       small_agg);
-    for (int l = 0; l < nlevels; ++l) {
-        LevelRow r;
-        const bool replicated = rep_level > 0 && l >= rep_level;
-        const int ll = replicated ? l - 1 : l;
-        if (rep_level > 0 && l == rep_level - 1) { r.cycled = 0; out[l] = r; continue; }
-        if (l == last && nlevels > 1) {
-            r.kind = ck == COARSEST_BLOCKED_INVERSE ? SNS_LEVEL_DIRECT_BLOCKED : ck == COARSEST_SMALL_INVERSE ? SNS_LEVEL_DIRECT
-                                                                                                           : SNS_LEVEL_SWEEPS_ONLY;
-            if (part && rep_level == 0 && ck != COARSEST_SWEEPS) r.kind = SNS_LEVEL_DIRECT;      // the all-gathered dense system
-            out[l] = r;
-            continue;
-        }
-        const int sharing = (part && !replicated) ? nranks : 1;
-        bool blocks = has_blocks[l] && blocks_allowed(o, rows[l], sharing);
-        if (l == 0) blocks = blocks && fine_blocks(o, nranks, rows[0]);
-        const bool partitioned_level = part && !replicated;
-        r.exact = (partitioned_level && l >= 1 && windows && o.halo_windows && o.amg_exact_sweeps && blocks && o.amg_fused_post &&
-                   o.amg_fuse_restrict != 0 && !(o.amg_sweep_exchange_rows > 0))
-                      ? 1 : 0;
-        const int nu = level_nu(o, ll, blocks, e);
-        const Sweeps s = level_sweeps(o, ll, blocks, partitioned_level && !r.exact, nu, r.exact != 0);
-        r.kind = blocks ? SNS_LEVEL_AGGREGATE_BLOCKS : SNS_LEVEL_NODAL_BLOCKS;
-        r.pre = s.pre;
-        r.post = s.post;
-        out[l] = r;
+// ---- the plan: what a hierarchy of the given structure runs ----------------------------------------------------------------------
+// Facts: the hierarchy's structure as built.  rows[l]: GLOBAL rows of level l as held (a replicated level: its rows; its size is the
+// level count); rep_level: first replicated level (0: none; the level before it is only the source of the copy and is not cycled);
+// windows: the transport reads ghost entries from receive windows (peer / team); has_blocks[l]: the level's aggregates have at most
+// 8 members (its smoother blocks exist); has_ap[l]: M = A P exists (the fused post-sweep); has_ap_rep[l]: M's columns in the ids of
+// the replicated level below.  Agreed over the ranks by the caller: win_capable[l] -- every rank's plan of the level receives in
+// order straight into its window; max_owned[l] -- the most owned rows any rank holds on the level.  last: how the last level is
+// solved.  rep_gather_fits: a rank's piece of the replicated right-hand side fits the all-gather staging area.  The remaining
+// fields are the harnesses' A/B switches (not options).
+struct Facts {
+    int nranks = 1, rep_level = 0;
+    std::vector<int64_t> rows, max_owned;
+    std::vector<uint8_t> has_blocks, has_ap, has_ap_rep, win_capable;
+    int64_t rows_global_l1 = 0;
+    bool windows = false, rep_gather_fits = false;
+    CoarsestKind last = COARSEST_SWEEPS;
+    bool team_overlap = false, fuse_puts = true, restrict_fuse = true;
+    int graph_max_rows = GRAPH_MAX_ROWS;
+};
+
+// One level's row of the plan.  kind: SNS_LEVEL_* of include/sns.h; cycled = 0: only the source of the replicated copy; blocks: the
+// aggregate blocks smooth it; nu: sweeps per half cycle (half_cycle_sweeps); pre / post: sweeps before / after the coarse-grid correction (the
+// first pre-sweep is w S b from the zero guess); exact: exact global sweeps over the windows (amg_exact_sweeps); windows: the window
+// form of the cycle (vcycle_windows); sx: every sweep exchanges ghost values (amg_sweep_exchange_rows); px: one exchange after the
+// coarse-grid correction makes the single post-sweep the exact global one (amg_post_exchange); fused_post: coarse-grid correction +
+// first post-sweep over M = A P; fused_restrict: residual + restriction (+ next first sweep) in one launch (amg_fuse_restrict);
+// fuses_next_first: the restriction from this level also does the next level's first sweep; lp_fmt: the low-precision matrix copy
+// the smoother reads (0 none, 1 fp32, 2 fp16); start_odd: (pre - 1 + post) odd -- the cycle starts in the ping-pong buffer, so that
+// the result lands in x.
+struct LevelPlan {
+    int kind = SNS_LEVEL_NODAL_BLOCKS, cycled = 1, blocks = 0, nu = 0, pre = 0, post = 0;
+    int exact = 0, windows = 0, sx = 0, px = 0, fused_post = 0, fused_restrict = 0, fuses_next_first = 0, lp_fmt = 0, start_odd = 0;
+    bool ghost_sweeps() const { return sx || px || exact; }      // the level's sweeps see the neighbours' values
+    bool operator==(const LevelPlan& o) const {
+        return kind == o.kind && cycled == o.cycled && blocks == o.blocks && nu == o.nu && pre == o.pre && post == o.post &&
+               exact == o.exact && windows == o.windows && sx == o.sx && px == o.px && fused_post == o.fused_post &&
+               fused_restrict == o.fused_restrict && fuses_next_first == o.fuses_next_first && lp_fmt == o.lp_fmt &&
+               start_odd == o.start_odd;
     }
+};
+// fine_windows: the level-0 passes (operator applications included) read their ghost entries straight from the receive window;
+// fine_tails_unused: the partitioned fine level's cycle never reads a ghost tail as zero (no internal buffer, no copy);
+// rep_gather_first: both halves of the replicated tail's all-gather ride in solver kernels; graph_level: first level of the hipGraph
+// (0: none); fuse_puts: kernels carry the put of the vector they produce
+struct CyclePlan {
+    std::vector<LevelPlan> level;
+    int fine_windows = 0, fine_tails_unused = 0, rep_gather_first = 0, graph_level = 0, fuse_puts = 0;
+};
+
+inline CyclePlan plan_cycle(const sns_options& o, const Facts& f) {
+    CyclePlan p;
+    const int nl = (int)f.rows.size();
+    if (nl == 0) return p;
+    p.level.resize((size_t)nl);
+    const int last = nl - 1, R = f.rep_level;
+    const bool part = f.nranks > 1;
+    const bool amg = o.pc_type == SNS_PC_AMG;
+    const bool win = part && f.windows && o.halo_windows && !f.team_overlap;
+    auto partitioned = [&](int l) { return part && !(R > 0 && l >= R); };
+    auto fact = [](const std::vector<uint8_t>& v, int l) { return l >= 0 && (size_t)l < v.size() && v[(size_t)l] != 0; };
+    const bool small_agg = f.rows_global_l1 > 0 && (double)f.rows[0] < 6.0 * (double)f.rows_global_l1;
+    const ExtraSweeps e = extra_sweeps(o, f.rows[0], depth_equivalent(o, nl - (R > 0 ? 1 : 0), f.last == COARSEST_BLOCKED_INVERSE && nl > 1,
+                                                                      f.rows[last]), small_agg);
+    for (int l = 0; l < nl; ++l) {                          // what a level is and how it is smoothed
+        LevelPlan& q = p.level[(size_t)l];
+        const bool solved_last = l == last && nl > 1;
+        const bool rep_src = R > 0 && l == R - 1;
+        const int ll = (R > 0 && l >= R) ? l - 1 : l;      // the replicated copy is not a new level
+        q.cycled = rep_src ? 0 : 1;
+        q.blocks = !solved_last && !rep_src && fact(f.has_blocks, l) && (l > 0 || fine_blocks(o, f.nranks, f.rows[0])) &&
+                   blocks_allowed(o, f.rows[(size_t)l], partitioned(l) ? f.nranks : 1);
+        if (solved_last) {
+            q.kind = f.last == COARSEST_BLOCKED_INVERSE ? SNS_LEVEL_DIRECT_BLOCKED : f.last == COARSEST_SMALL_INVERSE ? SNS_LEVEL_DIRECT
+                                                                                                                      : SNS_LEVEL_SWEEPS_ONLY;
+            if (part && R == 0 && f.last != COARSEST_SWEEPS) q.kind = SNS_LEVEL_DIRECT;     // the all-gathered dense system
+        } else {
+            q.kind = q.blocks ? SNS_LEVEL_AGGREGATE_BLOCKS : SNS_LEVEL_NODAL_BLOCKS;
+        }
+        const bool direct = q.kind == SNS_LEVEL_DIRECT || q.kind == SNS_LEVEL_DIRECT_BLOCKED;
+        q.lp_fmt = (amg && !direct && !rep_src) ? (o.amg_f32_matrix == 2 ? 2 : o.amg_f32_matrix ? 1 : 0) : 0;
+        q.nu = half_cycle_sweeps(o, ll, q.blocks, e);
+        // (the most owned rows of any rank: a level's ranks all fall on the same side of the threshold)
+        q.sx = partitioned(l) && o.amg_sweep_exchange_rows > 0 && (size_t)l < f.max_owned.size() &&
+               f.max_owned[(size_t)l] <= (int64_t)o.amg_sweep_exchange_rows;
+        q.px = partitioned(l) && !q.sx && o.amg_post_exchange && q.nu == 1 && (l == 0 || !q.blocks);
+    }
+    for (int l = 0; l < nl; ++l) {                          // exact global sweeps: the window form of a level >= 1
+        LevelPlan& q = p.level[(size_t)l];
+        const bool rep_src_next = R > 0 && l + 1 == R - 1;  // (xc straight from the replicated solution)
+        q.exact = win && o.amg_exact_sweeps && amg && l >= 1 && l + 1 < nl && !(R > 0 && l >= R - 1) && !q.sx && q.blocks &&
+                  fact(f.has_ap, l) && o.amg_fused_post && o.amg_fuse_restrict != 0 && fact(f.win_capable, l) &&
+                  (rep_src_next ? fact(f.has_ap_rep, l) : fact(f.win_capable, l + 1));
+    }
+    for (int l = 0; l < nl; ++l) {                          // the sweep counts and what is fused into what
+        LevelPlan& q = p.level[(size_t)l];
+        const int ll = (R > 0 && l >= R) ? l - 1 : l;
+        if (l + 1 < nl || nl == 1) {
+            // rank-local sweeps: any level of a partitioned handle (the rule of rounds 2-4) unless its sweeps are the exact global ones
+            const Sweeps s = pre_post_sweeps(o, ll, q.blocks, part && !q.exact, q.nu, q.exact != 0);
+            q.pre = s.pre;
+            q.post = s.post;
+        }
+        q.start_odd = (q.pre + q.post > 0) && ((q.pre - 1 + q.post) & 1);
+        q.fused_post = l + 1 < nl && o.amg_fused_post && fact(f.has_ap, l) && q.lp_fmt != 0 && q.post >= 1 && !q.sx &&
+                       (!partitioned(l) || (l == 0 && q.px && q.nu == 1));
+        q.fused_restrict = (l >= 1 || (o.amg_fuse_restrict >= 2 && !partitioned(l))) && o.amg_fuse_restrict != 0 && q.lp_fmt != 0;
+        // the next level's first sweep is the plain rank-local w S bc of a smoothed level: not the dense coarsest level, not the
+        // level whose cycle is the all-gather into the replicated tail (nor that tail's first level), not a level whose sweeps
+        // exchange ghost values
+        const int c = l + 1;
+        if (c + 1 < nl && f.restrict_fuse && !(R > 0 && (c == R - 1 || l == R - 1))) {
+            const LevelPlan& C = p.level[(size_t)c];
+            q.fuses_next_first = !C.sx && (C.blocks || C.lp_fmt != 0);
+        }
+    }
+    p.fine_tails_unused = nl >= 2 && partitioned(0) && R != 1 && p.level[0].fused_post;
+    p.fine_windows = win && fact(f.win_capable, 0);
+    p.level[0].windows = p.fine_windows && p.fine_tails_unused && fact(f.win_capable, 1);
+    for (int l = 1; l < nl; ++l) p.level[(size_t)l].windows = p.level[(size_t)l].exact;
+    p.rep_gather_first = win && R >= 3 && p.level[(size_t)R - 2].exact && p.level[(size_t)R].blocks && f.rep_gather_fits;
+    if (part) {
+        p.graph_level = R;                                  // only the replicated tail is free of exchanges
+    } else {
+        for (int l = 1; l < nl && !p.graph_level; ++l)
+            if (f.rows[(size_t)l] <= (int64_t)f.graph_max_rows) p.graph_level = l;
+    }
+    p.fuse_puts = f.fuse_puts;
+    return p;
 }
 
 }  // namespace policy

@@ -143,7 +143,10 @@ int append_level(sns_ctx* h, const HostPattern& P, int32_t n_owned, bool with_xg
 int upload_block_rows(sns_ctx* h, int l, Level& L, const std::vector<int32_t>& m_ptr, const std::vector<int32_t>& m_idx,
                       int32_t nc_owned) {
     const int mode = h->opt.amg_block_smooth;
-    if (mode <= 0 || (l == 0 && !fine_blocks_wanted(h)) || nc_owned < 0) return SNS_OK;
+    if (mode <= 0 || nc_owned < 0) return SNS_OK;
+    // (the fine level: runs before the hierarchy's plan exists; global counts only, every rank answers alike)
+    const Comm* c = h->comm.get();
+    if (l == 0 && !policy::fine_blocks(h->opt, (c && c->active()) ? c->nranks : 1, h->n_global_fine)) return SNS_OK;
     // blocks = aggregates; an aggregate of more than 8 nodes (a leftover node joined a full neighbour) is split in member order
     std::vector<int32_t> rows, of((size_t)std::max(1, L.n), -1);
     rows.reserve((size_t)8 * std::max(1, nc_owned));
@@ -301,9 +304,10 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
         // ... and the level above the source reads the coarse solution of its fused correction + post-sweep straight from the
         // replicated solution: the columns of its M = A P (local ids of level R: owned, then ghosts) in the replicated level's ids
         Level& A = h->levels[R - 1];
-        if (R >= 2 && A.ap_colind && A.ap_nnz > 0) {
+        // (a rank without rows on that level uploads the empty list all the same: the plan asks whether it exists on every rank)
+        if (R >= 2 && A.ap_colind) {
             std::vector<int32_t> col((size_t)A.ap_nnz);
-            HIP_TRY(hipMemcpy(col.data(), A.ap_colind, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (!col.empty()) HIP_TRY(hipMemcpy(col.data(), A.ap_colind, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
             for (auto& j : col) {
                 if (j < n_owned) j = (int32_t)off[me] + j;
                 else {
@@ -346,7 +350,7 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
     HostPattern curp = std::move(G);
     int32_t n_own = NG;
     for (int l = h->rep_level; (int)h->levels.size() < o.amg_max_levels + 1; ++l) {
-        if (n_own <= coarsest_rows(o)) break;
+        if (n_own <= policy::coarsest_rows(o)) break;
         std::vector<int32_t> agg;
         int32_t nc = 0;
         aggregate_nodes(curp, n_own, std::min(255, std::max(2, o.amg_agg_size)), agg, nc,
@@ -423,13 +427,15 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
             // the replicated level must fit the scratch vectors sized by the local fine level
             double fits[1] = {g[0] <= (double)h->n_owned ? 0.0 : 1.0};
             SNS_TRY(global_sum(h, fits, 1));
-            if (policy::replicate_from(o, l, (int64_t)g[0], fits[0] == 0.0))
-                return build_replicated_tail(h, l, cur, n_owned, cur_pts);
+            if (policy::replicate_from(o, l, (int64_t)g[0], fits[0] == 0.0)) {
+                SNS_TRY(build_replicated_tail(h, l, cur, n_owned, cur_pts));
+                return plan_hierarchy(h);
+            }
         }
         double flag[1] = {n_owned > per_rank_coarse ? 1.0 : 0.0};
         SNS_TRY(global_sum(h, flag, 1));
         if (flag[0] == 0.0) break;
-        if (!dist && l >= 1 && n_owned <= coarsest_rows(o)) break;       // serial: this level is solved directly
+        if (!dist && l >= 1 && n_owned <= policy::coarsest_rows(o)) break;       // serial: this level is solved directly
         std::vector<int32_t> agg;
         int32_t nc_owned = 0;
         aggregate_nodes(cur, n_owned, std::min(255, std::max(2, o.amg_agg_size)), agg, nc_owned,
@@ -495,7 +501,7 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
         SNS_TRY(upload_block_rows(h, l, L, A.m_ptr, A.m_idx, nc_owned));
         // M = A P for the fused first post-smoothing sweep: every level of a serial hierarchy; in a partitioned one the fine
         // level only (its single post-sweep is the exact global sweep; the distributed coarse levels smooth rank-locally)
-        // ... and, on the window transports, every partitioned level: the exact-sweep cycle (level_exact) takes the fused post-sweep too
+        // ... and, on the window transports, every partitioned level: the exact-sweep cycle (plan exact) takes the fused post-sweep too
         if (!dist || l == 0 || c->windows()) SNS_TRY(upload_ap(h, L, cur, n_owned, A.agg));
         h->levels.emplace_back();
         h->slot_row.push_back(nullptr);
@@ -573,6 +579,54 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
         }
     }
     h->tm.amg_levels = (int)h->levels.size();
+    return plan_hierarchy(h);
+}
+
+
+// The plan of the cycle for the hierarchy just built (collective, once per hierarchy): its structure, the two per-rank facts agreed
+// over the ranks -- a level's plans receive in order straight into the windows on EVERY rank; the most owned rows of any rank --,
+// the harnesses' A/B switches, then csrc/sns_policy.h.  Every rank runs the same cycle whatever its ghost numbering or share.
+int plan_hierarchy(sns_ctx* h) {
+    const Comm* c = h->comm.get();
+    const int nl = (int)h->levels.size();
+    policy::Facts& f = h->facts;
+    f = policy::Facts();
+    f.nranks = (c && c->active()) ? std::max(1, c->nranks) : 1;
+    f.rep_level = h->rep_level;
+    f.rows_global_l1 = h->n_global_l1;
+    f.windows = c && c->windows();
+    f.team_overlap = h->team_overlap;
+    f.fuse_puts = std::getenv("SNS_NO_CARRIED_PUT") == nullptr;
+#ifdef SNS_HARNESS
+    f.restrict_fuse = std::getenv("SNS_NO_RESTRICT_FUSE") == nullptr;
+    if (std::getenv("SNS_GRAPH_ROWS")) f.graph_max_rows = std::atoi(std::getenv("SNS_GRAPH_ROWS"));
+#endif
+    const Level& last = h->levels.back();
+    f.last = last.dense_gj ? policy::COARSEST_BLOCKED_INVERSE
+                           : (last.dense_inv || h->cg_N > 0) ? policy::COARSEST_SMALL_INVERSE : policy::COARSEST_SWEEPS;
+    f.rep_gather_fits = h->rep_level > 0 && c && c->peer && h->levels[h->rep_level].n_blk > 0 &&
+                        (size_t)4 * h->rep_maxn * (size_t)c->nranks <= c->peer->ag_doubles;
+    std::vector<double> mine((size_t)2 * nl), all;
+    for (int l = 0; l < nl; ++l) {
+        const Level& L = h->levels[l];
+        f.rows.push_back(L.n_global);
+        f.has_blocks.push_back(L.blk_rows != nullptr);
+        f.has_ap.push_back(L.ap_rowptr != nullptr);
+        f.has_ap_rep.push_back(L.ap_colind_rep != nullptr);
+        const bool wc = c && (size_t)l < c->plans.size() && c->plans[l].identity_recv && c->plans[l].win_recv[0] != nullptr;
+        mine[(size_t)l] = wc ? 1.0 : 0.0;
+        mine[(size_t)nl + l] = (double)L.n_owned;
+    }
+    if (f.nranks > 1) SNS_TRY(host_allgather(h, mine, all));
+    else all = mine;
+    f.win_capable.assign((size_t)nl, 1);
+    f.max_owned.assign((size_t)nl, 0);
+    for (size_t r = 0; r < all.size() / mine.size(); ++r)
+        for (int l = 0; l < nl; ++l) {
+            if (all[r * mine.size() + l] == 0.0) f.win_capable[(size_t)l] = 0;
+            f.max_owned[(size_t)l] = std::max(f.max_owned[(size_t)l], (int64_t)all[r * mine.size() + nl + l]);
+        }
+    h->plan = policy::plan_cycle(h->opt, f);
     return SNS_OK;
 }
 
@@ -759,8 +813,14 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
 }
 
 
+// |lambda|max of Dinv*A on level l by a few power iterations (device resident; one host sync).
+// The damped block-Jacobi smoother x += w Dinv (b - A x) needs w*|lambda|max < 2; on the reference's
+// operator the fixed w = 0.9 already diverges at 10 M tets, so w is capped per level at the smoothing-optimal 4/(3 |lambda|max).  (Measured cliff on the coarse
+// levels of the 10 M-tet Jacobian: w = 0.80 converges in 45 iterations, w >= 0.82 overflows, although the
+// dominant mode itself is still damped there -- the offending mode is not the one of largest modulus.)
 int estimate_lambda_max(sns_ctx* h, int l, double* out) {
     Level& L = h->levels[l];
+    const policy::LevelPlan& P = h->plan.level[(size_t)l];
     const int32_t rows = L.n_owned;
     const int64_t nd = 4 * (int64_t)rows;
     const int g = vec_grid(nd), g4 = (int)((nd + 255) / 256);
@@ -771,7 +831,7 @@ int estimate_lambda_max(sns_ctx* h, int l, double* out) {
     // overkill; use b of the last solve if any, else the diagonal-inverse row sums: simplest robust choice = all ones
     if (rows > 0) hipLaunchKernelGGL(k_fill_pattern, dim3(g), dim3(256), 0, h->stream, nd, x);
     double* zero = nullptr;
-    if (lp_format(h, L) != 0) {
+    if (P.lp_fmt != 0) {
         SNS_TRY(get_vec(h, 13, &zero));                  // level sizes never exceed the fine level
         if (nd > 0) HIP_TRY(hipMemsetAsync(zero, 0, nd * sizeof(double), h->stream));
     }
@@ -779,15 +839,15 @@ int estimate_lambda_max(sns_ctx* h, int l, double* out) {
     const int iters = 12;
     // distributed levels whose sweeps see exchanged ghost values are damped for the GLOBAL operator; purely
     // rank-local sweeps (ghost values zero) for the rank-local one
-    const bool glob = uses_ghosts_in_sweeps(h, l, L);
+    const bool glob = P.ghost_sweeps();
     for (int it = 0; it < iters; ++it) {
         if (glob) SNS_TRY(exchange_level(h, l, x));
         // the spectrum of the matrix the sweeps actually read: with a low-precision copy y = 0 - A~ x (the sign does not
         // matter to ||Dinv A x||), half the bytes of the fp64 pass
-        if (lp_format(h, L) != 0 && zero) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, rows, x, y, zero, 0.0);
+        if (P.lp_fmt != 0 && zero) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, P.lp_fmt, rows, x, y, zero, 0.0);
         else launch_spmv<SPMV_AX>(h, L, rows, x, y, nullptr, 0.0, nullptr);
         if (rows > 0) {
-            if (block_active(h, l) && L.binv32) launch_first_sweep(h, l, L, rows, y, 1.0, z);      // the smoother's own blocks
+            if (P.blocks) launch_first_sweep(h, P, L, rows, y, 1.0, z);      // the smoother's own blocks
             else hipLaunchKernelGGL(k_bjacobi, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv, y, 1.0, z);
             hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, nd, x, z, h->partial);   // (x.z, z.z)
         }
@@ -806,18 +866,26 @@ int estimate_lambda_max(sns_ctx* h, int l, double* out) {
 }
 
 
+// Stability limit of the smoother damping on level l from the dominant Ritz values of S A (S = the level's smoother blocks,
+// nodal or aggregate): M = 8 Arnoldi steps from the deterministic start vector of the power iteration (classical Gram-Schmidt
+// with one re-orthogonalisation, the FGMRES kernels; one host read per step), eigenvalues of the 8 x 8 Hessenberg matrix on the
+// host (sns_host_hessenberg_eigs).  |1 - w theta| < 1 needs w < 2 Re(theta) / |theta|^2: *limit = the minimum over the Ritz
+// values with |theta| >= 0.5 |theta|max (those a few Arnoldi steps have converged to).  The power iteration above sees the
+// modulus only; on a convection-dominated coarse level the dominant eigenvalues are complex, and a level that runs 1 + 6
+// sweeps amplifies a damping above the limit seven times per cycle (oracle/experiments/r4_damping.py).
 int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
     constexpr int M = 8;
     Level& L = h->levels[l];
+    const policy::LevelPlan& P = h->plan.level[(size_t)l];
     const int32_t rows = L.n_owned;
     const int64_t nd = 4 * (int64_t)rows;
     *theta_max = 0.0;
     *limit = 1e30;
-    // levels whose sweeps see exchanged ghost values (level_exact): the GLOBAL operator's Ritz values -- one exchange per Arnoldi
+    // levels whose sweeps see exchanged ghost values (plan exact): the GLOBAL operator's Ritz values -- one exchange per Arnoldi
     // step, the dots summed over the ranks; collective, so every rank goes through it whatever its row count.  (Levels that
     // exchange per sweep by amg_sweep_exchange_rows / the fine level's single post-sweep: not estimated, as in round 4.)
-    const bool glob = level_exact(h, l);
-    if (!glob && (rows <= 0 || uses_ghosts_in_sweeps(h, l, L))) return SNS_OK;
+    const bool glob = P.exact != 0;
+    if (!glob && (rows <= 0 || P.ghost_sweeps())) return SNS_OK;
     const int g = std::max(1, vec_grid(nd));           // (a rank without rows on a collective level still launches: empty loops, zero partials)
     auto reduce = [&](int nred, double* dst) -> int {
         if (glob) return reduce_to(h, g, nred, dst);
@@ -844,7 +912,7 @@ int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
     SNS_TRY(reduce(2, sc + 16));
     hipLaunchKernelGGL(k_scale_by_rsqrt, dim3(g), dim3(256), 0, h->stream, nd, sc + 17, V, V);
     std::vector<double> H((size_t)M * M, 0.0);
-    const bool lp = lp_format(h, L) != 0;
+    const bool lp = P.lp_fmt != 0;
     int m_done = 0;
     for (int j = 0; j < M; ++j) {
         double* vj = V + (size_t)j * nd;
@@ -852,9 +920,9 @@ int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
         HIP_TRY(hipMemcpyAsync(xin, vj, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         if (glob) SNS_TRY(exchange_level(h, l, xin));
         // y = -A~ v (the copy the sweeps read) resp. + A v; w = S A v
-        if (lp) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, rows, xin, y, zero, 0.0);
+        if (lp) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, P.lp_fmt, rows, xin, y, zero, 0.0);
         else launch_spmv<SPMV_AX>(h, L, rows, xin, y, nullptr, 0.0, nullptr);
-        launch_first_sweep(h, l, L, rows, y, lp ? -1.0 : 1.0, w);
+        launch_first_sweep(h, P, L, rows, y, lp ? -1.0 : 1.0, w);
         for (int pass = 0; pass < 2; ++pass) {
             hipLaunchKernelGGL(k_multi_dot8, dim3(g), dim3(256), 0, h->stream, nd, j + 1, V, nd, w, h->partial);
             SNS_TRY(reduce(8, sc + 8 * pass));
@@ -896,6 +964,7 @@ int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
 // on the 10 M-tet Jacobian w = 0.8 converges and w = 0.85 on the coarse levels breaks BiCGStab down.
 int jacobi_growth(sns_ctx* h, int l, double omega, double* growth) {
     Level& L = h->levels[l];
+    const policy::LevelPlan& P = h->plan.level[(size_t)l];
     const int32_t rows = L.n_owned;
     const int64_t nd = 4 * (int64_t)rows;
     const int g = vec_grid(nd);
@@ -906,9 +975,9 @@ int jacobi_growth(sns_ctx* h, int l, double omega, double* growth) {
     SNS_TRY(get_vec(h, 13, &zero));                      // level sizes never exceed the fine level
     if (nd > 0) HIP_TRY(hipMemsetAsync(zero, 0, nd * sizeof(double), h->stream));
     // keep x0 intact (it seeds later trials): first sweep x0 -> xa, then ping-pong xa <-> xb
-    const bool glob = uses_ghosts_in_sweeps(h, l, L);
+    const bool glob = P.ghost_sweeps();
     if (glob) SNS_TRY(exchange_level(h, l, x0));
-    launch_sweep(h, l, L, rows, x0, xa, zero, omega);
+    launch_sweep(h, P, L, rows, x0, xa, zero, omega);
     double* cur = xa;
     double* oth = xb;
     const int sweeps = 6;
@@ -919,7 +988,7 @@ int jacobi_growth(sns_ctx* h, int l, double omega, double* growth) {
             else reduce_local(h, g, 2, h->d_scal + 48 + (s == 2 ? 0 : 2));
         }
         if (glob) SNS_TRY(exchange_level(h, l, cur));
-        launch_sweep(h, l, L, rows, cur, oth, zero, omega);
+        launch_sweep(h, P, L, rows, cur, oth, zero, omega);
         std::swap(cur, oth);
     }
     double v[4];
@@ -951,9 +1020,10 @@ int pc_setup(sns_ctx* h) {
                                h->rep_valmap, h->rep_vrecv, C.vals);
             continue;
         }
+        const policy::LevelPlan& P = h->plan.level[(size_t)l];
         if (rows > 0)
             hipLaunchKernelGGL(k_dinv, dim3((rows + 255) / 256), dim3(256), 0, h->stream, rows, L.diag, L.vals, L.dinv);
-        if (block_active(h, l)) {
+        if (P.blocks) {
             // the aggregates' inverse diagonal blocks, from the fp64 operator (what the nodal D^-1 is to the point smoother)
             // ... in the format of the level's matrix copy (fp32, or fp16 with row scales: half the bytes of a block sweep's extra stream)
             const int bf = h->opt.amg_f32_matrix == 2 ? 2 : 1;
@@ -975,8 +1045,8 @@ int pc_setup(sns_ctx* h) {
             any_block = true;
         }
         L.omega = h->opt.amg_omega * h->damping_backoff;
-        const bool direct = (L.dense_inv || L.dense_gj || h->cg_N > 0) && l + 1 == nl && nl > 1;   // solved, not smoothed
-        if (h->opt.pc_type == SNS_PC_AMG && h->opt.amg_f32_matrix && !direct) {
+        const bool direct = l + 1 == nl && nl > 1 && (P.kind == SNS_LEVEL_DIRECT || P.kind == SNS_LEVEL_DIRECT_BLOCKED);   // solved
+        if (P.lp_fmt != 0) {
             if (!L.dinv32) SNS_TRY(dev_alloc(&L.dinv32, (size_t)16 * std::max(1, L.n)));
             if (rows > 0)
                 hipLaunchKernelGGL(k_cvt_f32, dim3(vec_grid(16 * (int64_t)rows)), dim3(256), 0, h->stream, 16 * (int64_t)rows,
@@ -1028,17 +1098,15 @@ int pc_setup(sns_ctx* h) {
             // ... but not from the Stokes operator to a Jacobian (or to another Reynolds number): round 3 took the first three
             // Jacobians' damping from the Stokes solve's estimate, which is what let level 1 of the jittered 120 x 30 x 30 duct
             // run at w = 0.72 where its own spectrum allows 0.48 (tests/test_gpu_parity.py::test_damping_backoff_...)
-            if ((rows > 0 || uses_ghosts_in_sweeps(h, l, L)) && (!(lam > 0.0) || (h->pc_setups & 3) == 0 || new_operator))
+            if ((rows > 0 || P.ghost_sweeps()) && (!(lam > 0.0) || (h->pc_setups & 3) == 0 || new_operator))
                 SNS_TRY(estimate_lambda_max(h, l, &lam));
             const bool fresh = !(L.lambda_max > 0.0) || (h->pc_setups & 3) == 0 || new_operator;
             L.lambda_max = lam;
             if (lam > 0.0) L.omega = std::min(h->opt.amg_omega, (4.0 / 3.0) / lam) * h->damping_backoff;
             // levels that run 3 or more sweeps per cycle: the stability limit of the dominant (complex) Ritz values as well
             if (h->opt.amg_ritz_limit && l + 1 < nl) {
-                int a = 1, b = 1;
-                level_sweeps(h, l, a, b);
-                if (a + b >= 3) {
-                    if (fresh && (rows > 0 || level_exact(h, l))) {
+                if (P.pre + P.post >= 3) {
+                    if (fresh && (rows > 0 || P.exact)) {
                         double tmax = 0.0, lim = 1e30;
                         SNS_TRY(arnoldi_ritz(h, l, &tmax, &lim));
                         L.ritz_limit = lim;
@@ -1053,12 +1121,7 @@ int pc_setup(sns_ctx* h) {
             // and backing its damping off for the sake of a few complex outliers weakens the smoothing of everything else
             // (jittered 120 x 30 x 30 duct, Re 200: 56 iterations this way, 82 with the check on every level, 85 without it; the
             // option that switched between the three, amg_growth_check, was retired in round 5)
-            bool check_growth = false;
-            if (l + 1 < nl) {
-                int a = 1, b = 1;
-                level_sweeps(h, l, a, b);
-                check_growth = a + b >= 3;
-            }
+            const bool check_growth = l + 1 < nl && P.pre + P.post >= 3;
             if (fresh && lam > 0.0 && !check_growth) L.omega_checked = 0.0;
             if (fresh && lam > 0.0 && check_growth) {
                 // verify the damping on the dominant mode; back off until a sweep contracts it by >= 10 %
@@ -1075,17 +1138,13 @@ int pc_setup(sns_ctx* h) {
             }
             if (h->opt.monitor) std::printf("    AMG level %d: n %d |lambda|max(Dinv A) %.4f omega %.4f\n", l, rows, lam, L.omega);
         }
-        if (l + 1 < nl && L.ap_rowptr && h->opt.amg_fused_post && h->opt.pc_type == SNS_PC_AMG && lp_format(h, L) != 0 &&
-            rows > 0) {
-            // numeric part of M = A P, straight into the level's low-precision format (no fp64 copy of M)
-            const unsigned gq = (unsigned)((4 * (int64_t)rows + 255) / 256);
-            if (lp_format(h, L) == 2) {
-                // (written together with the fp16 copy of A above)
-            } else {
-                if (!L.ap_vals32) SNS_TRY(dev_alloc(&L.ap_vals32, (size_t)L.ap_nnz * 16));
-                hipLaunchKernelGGL(k_ap_cvt32, dim3(gq), dim3(256), 0, h->stream, rows, L.ap_rowptr, L.ap_colind, L.ap_ptr,
-                                   L.ap_idx, L.vals, L.agg, L.free_mask, (float4*)L.ap_vals32);
-            }
+        if (l + 1 < nl && L.ap_rowptr && h->opt.amg_fused_post && P.lp_fmt == 1) {
+            // numeric part of M = A P, straight into the level's low-precision format (no fp64 copy of M; fp16: written together
+            // with the fp16 copy of A above).  (Allocated on a rank without rows too: the plan asks for it on every rank.)
+            if (!L.ap_vals32) SNS_TRY(dev_alloc(&L.ap_vals32, (size_t)L.ap_nnz * 16));
+            if (rows > 0)
+                hipLaunchKernelGGL(k_ap_cvt32, dim3((unsigned)((4 * (int64_t)rows + 255) / 256)), dim3(256), 0, h->stream, rows,
+                                   L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.vals, L.agg, L.free_mask, (float4*)L.ap_vals32);
         }
         if (l + 1 < nl) {
             Level& C = h->levels[l + 1];
@@ -1132,6 +1191,10 @@ int pc_setup(sns_ctx* h) {
                                h->d_sing);
         }
     }
+    if (const char* miss = plan_buffer_missing(h)) {
+        set_error(std::string("AMG setup: the cycle's plan needs ") + miss + ", which the setup did not allocate");
+        return SNS_E_STATE;
+    }
     ++h->pc_setups;
     h->est_form = h->matrix_form;
     h->est_re = h->opt.reynolds;
@@ -1168,6 +1231,22 @@ int pc_setup(sns_ctx* h) {
         }
     h->pc_ready = true;
     return SNS_OK;
+}
+
+
+// The device buffers the cycle reads because its plan says so (nullptr: all there).  pc_setup allocates them from the same plan;
+// after sns_set_options a changed plan may ask for one it has not made yet.
+const char* plan_buffer_missing(const sns_ctx* h) {
+    if (h->opt.pc_type != SNS_PC_AMG) return nullptr;
+    for (size_t l = 0; l < h->plan.level.size() && l < h->levels.size(); ++l) {
+        const policy::LevelPlan& P = h->plan.level[l];
+        const Level& L = h->levels[l];
+        if (P.blocks && (!L.binv32 || L.binv_fmt != (P.lp_fmt == 2 ? 2 : 1))) return "a level's aggregate-block inverses";
+        if (P.lp_fmt != 0 && (!L.dinv32 || !(P.lp_fmt == 2 ? (const void*)L.vals16 : (const void*)L.vals32)))
+            return "a level's low-precision matrix copy";
+        if (P.fused_post && !(P.lp_fmt == 2 ? (const void*)L.ap_vals16 : (const void*)L.ap_vals32)) return "a level's M = A P";
+    }
+    return nullptr;
 }
 
 

@@ -856,3 +856,103 @@ def test_hierarchy_policy_table(built_lib):
     assert T(serial, amg_nu_l1_pre=2, amg_nu_l1_post=2)[1] == (1, 2, 2)
     # aggregate blocks only where the level is small enough per rank, when limited (amg_block_max_rows)
     assert T(serial, amg_block_max_rows=8192) == [(0, 1, 1), (0, 1, 6), (0, 6, 6), (1, 2, 2), (3, 0, 0)]
+
+
+def test_cycle_plan_columns(built_lib, tmp_path):
+    """The rest of the cycle's plan (csrc/sns_policy.h: policy::plan_cycle, what the handle's V-cycle reads) for the hierarchies on
+    record: per level (fused_post, fuses_next_first, windows, px, sx, start parity) and the handle-wide (fine_tails_unused,
+    rep_gather_first, graph_level) -- the values the handle-side predicates of csrc/sns_ctx.h gave before the plan replaced them.
+    Built like the sanitizer test: a small main over the header, no ABI."""
+    import shutil
+    import subprocess
+    from stabilized_navier_stokes_flow_fenicsx_amd import _lib
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "cycle_plan")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
+                            "-I", os.path.join(root, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
+                            os.path.join(root, "tests", "cycle_plan_main.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    SMALL, BLOCKED = 0, 1                                     # policy::CoarsestKind of the last level
+
+    def plan_of(rows, nranks=1, rep=0, l1=None, windows=False, last=BLOCKED, blocks=None, ap=None, ap_rep=None, wc=None,
+                owned=None, fits=True, **kw):
+        n = len(rows)
+        opt = tmp_path / "opt.bin"
+        opt.write_bytes(ctypes.string_at(ctypes.byref(_lib.default_options(**kw)), ctypes.sizeof(_lib.SnsOptions)))
+        ones, zeros = [1] * n, [0] * n
+        lines = [f"{nranks} {rep} {n} {rows[1] if l1 is None else l1} {int(windows)} {last} {int(fits)} 0"]
+        for v in (rows, owned or [-(-r // nranks) for r in rows], blocks or ones[:-1] + [0], ap or ones[:-1] + [0], ap_rep or zeros,
+                  wc or zeros):
+            lines.append(" ".join(str(int(x)) for x in v))
+        run = subprocess.run([exe, str(opt)], input="\n".join(lines) + "\n", capture_output=True, text=True)
+        assert run.returncode == 0, run.returncode
+        out = [list(map(int, ln.split())) for ln in run.stdout.split("\n") if ln.strip()]
+        keys = ("kind", "cycled", "blocks", "nu", "pre", "post", "exact", "windows", "sx", "px", "fused_post", "fused_restrict",
+                "fuses_next_first", "lp_fmt", "start_odd")
+        levels = [dict(zip(keys, r)) for r in out[:-1]]
+        return levels, dict(zip(("fine_windows", "fine_tails_unused", "rep_gather_first", "graph_level", "fuse_puts"), out[-1]))
+
+    col = lambda P, k: [q[k] for q in P[0]]
+    cyc = lambda P: [(q["kind"], q["pre"], q["post"]) for q in P[0]]
+    top = lambda P: (P[1]["fine_tails_unused"], P[1]["rep_gather_first"], P[1]["graph_level"])
+
+    # the 10.1 M-tet duct on one GPU: every smoothed level takes the fused post-sweep, the restrictions above levels 1-3 do their
+    # first sweep, the graph starts at level 2 (36 k rows)
+    serial = plan_of([1738576, 218044, 27436, 3800, 475], blocks=[0, 1, 1, 1, 0])
+    assert cyc(serial) == [(0, 1, 1), (1, 1, 3), (1, 4, 4), (1, 2, 2), (3, 0, 0)]
+    assert col(serial, "fused_post") == [1, 1, 1, 1, 0] and col(serial, "fuses_next_first") == [1, 1, 1, 0, 0]
+    assert col(serial, "fused_restrict") == [0, 1, 1, 1, 0] and col(serial, "lp_fmt") == [2, 2, 2, 2, 0]
+    assert col(serial, "windows") == col(serial, "px") == col(serial, "sx") == [0] * 5
+    assert col(serial, "start_odd") == [1, 1, 1, 1, 0] and top(serial) == (0, 0, 2)
+
+    # its 8-way split over RCCL: M = A P on the fine level and the replicated tail only, level 2 only the source of the tail (no
+    # aggregates of its own), the fine level's single post-sweep the exact global one (px), the graph over the replicated tail
+    part = [1738576, 218044, 28880, 30027, 4454, 721, 136]
+    tail = dict(nranks=8, rep=3, l1=218044, blocks=[1, 1, 0, 1, 1, 1, 0])
+    rccl = plan_of(part, ap=[1, 0, 0, 1, 1, 1, 0], **tail)
+    assert cyc(rccl) == [(1, 1, 1), (1, 4, 4), (0, 6, 6), (1, 4, 4), (1, 2, 2), (1, 2, 2), (3, 0, 0)]
+    assert col(rccl, "cycled") == [1, 1, 0, 1, 1, 1, 1]
+    assert col(rccl, "fused_post") == [1, 0, 0, 1, 1, 1, 0] and col(rccl, "fuses_next_first") == [1, 0, 0, 1, 1, 0, 0]
+    assert col(rccl, "px") == [1, 0, 0, 0, 0, 0, 0] and col(rccl, "sx") == [0] * 7 and col(rccl, "windows") == [0] * 7
+    assert col(rccl, "start_odd") == [1, 1, 1, 1, 1, 1, 0] and top(rccl) == (1, 0, 3)
+
+    # ... over a window transport: level 1 runs the exact sweeps (1 + 4, even: it starts in x), the fine level the window form,
+    # and both halves of the tail's all-gather ride in kernels
+    wtail = dict(ap=[1, 1, 0, 1, 1, 1, 0], ap_rep=[0, 1, 0, 0, 0, 0, 0], wc=[1, 1, 1, 0, 0, 0, 0], windows=True, **tail)
+    win = plan_of(part, **wtail)
+    assert cyc(win) == [(1, 1, 1), (1, 1, 4), (0, 6, 6), (1, 4, 4), (1, 2, 2), (1, 2, 2), (3, 0, 0)]
+    assert col(win, "exact") == [0, 1, 0, 0, 0, 0, 0] and col(win, "windows") == [1, 1, 0, 0, 0, 0, 0]
+    assert col(win, "fused_post") == [1, 0, 0, 1, 1, 1, 0] and col(win, "fuses_next_first") == [1, 0, 0, 1, 1, 0, 0]
+    assert col(win, "px") == [1, 0, 0, 0, 0, 0, 0] and col(win, "start_odd") == [1, 0, 1, 1, 1, 1, 0]
+    assert top(win) == (1, 1, 3) and win[1]["fine_windows"] == 1
+    # ... without amg_exact_sweeps: level 1 back to 4 + 4 rank-local sweeps, the fine level keeps its window form
+    loc = plan_of(part, amg_exact_sweeps=0, **wtail)
+    assert cyc(loc) == cyc(rccl) and col(loc, "windows") == [1, 0, 0, 0, 0, 0, 0] and col(loc, "start_odd") == col(rccl, "start_odd")
+    assert top(loc) == (1, 0, 3)
+    # one level not window-capable on some rank (ghosts out of order): that level and the level whose window form reads its
+    # window fall back to the exchange form -- on every rank, the capability being agreed
+    wc1 = plan_of(part, **dict(wtail, wc=[1, 0, 1, 0, 0, 0, 0]))
+    assert col(wc1, "windows") == [0] * 7 and col(wc1, "exact") == [0] * 7 and cyc(wc1) == cyc(rccl)
+    assert top(wc1) == (1, 0, 3) and wc1[1]["fine_windows"] == 1
+    wc0 = plan_of(part, **dict(wtail, wc=[0, 1, 1, 0, 0, 0, 0]))
+    assert col(wc0, "windows") == [0, 1, 0, 0, 0, 0, 0] and wc0[1]["fine_windows"] == 0 and cyc(wc0) == cyc(win)
+    # amg_sweep_exchange_rows: levels whose every rank holds at most that many rows exchange per sweep (sx), not the others
+    sx = plan_of(part, amg_sweep_exchange_rows=30000, owned=[217322, 27256, 3610, 30027, 4454, 721, 136], **wtail)
+    assert col(sx, "sx") == [0, 1, 1, 0, 0, 0, 0] and col(sx, "px") == [1, 0, 0, 0, 0, 0, 0] and col(sx, "exact") == [0] * 7
+
+    # the team test's replicated shapes (4 ranks, windows): "-rep" -- level 1 the source, the tail from level 2 down to the small
+    # inverse; its level 2 is level 1 as coarsened and keeps the partitioned handle's rank-local 4 + 4
+    rep = plan_of([1225, 218, 218, 37, 7], nranks=4, rep=2, windows=True, last=SMALL, blocks=[1, 0, 1, 1, 0], ap=[1, 0, 1, 1, 0],
+                  ap_rep=[1, 0, 0, 0, 0], wc=[1, 1, 0, 0, 0], amg_coarse_size=24, amg_replicate_rows=1 << 20, amg_dense_rows=0)
+    assert cyc(rep) == [(1, 1, 1), (0, 4, 4), (1, 4, 4), (1, 4, 4), (2, 0, 0)]
+    assert col(rep, "fused_post") == [1, 0, 1, 1, 0] and col(rep, "fuses_next_first") == [0, 0, 1, 0, 0]
+    assert col(rep, "windows") == [1, 0, 0, 0, 0] and col(rep, "px") == [1, 0, 0, 0, 0] and col(rep, "sx") == [0] * 5
+    assert col(rep, "start_odd") == [1, 1, 1, 1, 0] and top(rep) == (1, 0, 2)
+    # "-rep-dense": the replicated level 1 is itself the last level, solved by the blocked inverse
+    dense = plan_of([1225, 218, 218], nranks=4, rep=2, windows=True, blocks=[1, 0, 0], ap=[1, 0, 0], ap_rep=[1, 0, 0],
+                    wc=[1, 1, 0], amg_replicate_rows=1 << 20)
+    assert cyc(dense) == [(1, 1, 1), (0, 4, 4), (3, 0, 0)]
+    assert col(dense, "fused_post") == [1, 0, 0] and col(dense, "fuses_next_first") == [0, 0, 0]
+    assert col(dense, "windows") == [1, 0, 0] and col(dense, "start_odd") == [1, 1, 0] and top(dense) == (1, 0, 2)
