@@ -215,6 +215,16 @@ typedef struct {
                                produces the iterate -- instead of amg_bnu_l2 + amg_bnu_l2 rank-local sweeps with an unfused
                                correction (8-way split of the 10 M-tet duct: 31 / 34 instead of 36 / 36 BiCGStab iterations with 6
                                instead of 9 level-1 launches per cycle).  0, and always over RCCL (an exchange per sweep costs a send / recv group there): round 4's cycle */
+    int    amg_aggregation; /* (ABI 8) how the FINE level is aggregated.  0 (default): from the sparsity pattern and the node coordinates
+                               (greedy sweep / pairwise by centroids), as before.  1: by operator strength -- s_ij = || D_i^-1/2 A_ij
+                               D_j^-1/2 ||_F of the first assembled operator (the Stokes operator of a Newton run), pairwise heavy-edge
+                               matching of its strong couplings into aggregates of at most 8 nodes (sns_host_aggregate_strength), frozen
+                               for the handle's lifetime -- and the fine level smoothed with the aggregates' dense blocks as under
+                               amg_block_smooth = 2 (SNS_LEVEL_AGGREGATE_BLOCKS; amg_block_smooth = 0 or amg_f32_matrix = 0 still turn
+                               the blocks off altogether).  For sliver-rich
+                               meshes: a sliver's four nodes share an aggregate and its coupling no longer sets the damping of the whole
+                               level.  Levels >= 1 keep the default aggregation either way.  Fixed when the hierarchy is built; 1 needs
+                               an assembled operator then (SNS_E_STATE otherwise), amg_agg_size <= 8, and a 3-D handle (SNS_E_ARG) */
 } sns_options;
 
 SNS_API void sns_default_options(sns_options* opt);
@@ -224,7 +234,7 @@ SNS_API const char* sns_version(void);
  * and the fixed-size out-arrays of the getters below have grown (sns_get_counters / sns_get_kernel_times: 4 -> 8 entries in
  * round 3), so a binding built against an older header would pass short buffers: bindings compare both numbers with the
  * header they were written against before making any other call (the ctypes mirror does, _lib.py) and refuse on a mismatch. */
-#define SNS_ABI_VERSION 7
+#define SNS_ABI_VERSION 8
 SNS_API int sns_abi_version(void);
 SNS_API int64_t sns_options_size(void);
 
@@ -376,6 +386,10 @@ SNS_API int sns_get_element_scratch(sns_handle h, const double** Ke_dev, const d
 #define SNS_EXPORT_VALS   2   /* double [nnzb*16]         */
 #define SNS_EXPORT_KE     3   /* double [n_tets*256]      */
 #define SNS_EXPORT_FE     4   /* double [n_tets*16]       */
+#define SNS_EXPORT_STRENGTH 5 /* float [nnzb]: the strength || D_i^-1/2 A_ij D_j^-1/2 ||_F of every block slot of the CURRENT fine
+                                 operator (owned rows; 0 on the diagonal slot and on ghost rows), computed into dst by the
+                                 strength kernel -- what amg_aggregation = 1 aggregates by.  Collective on a partitioned handle */
+#define SNS_EXPORT_AGG0   6   /* int32 [n_local]: the level-0 aggregate map as built (-1: node takes no part; ghost nodes -1) */
 SNS_API int sns_export(sns_handle h, int what, void* dst_dev, int64_t nbytes);
 /* timing of the phases of the last solve, milliseconds (HIP events)           */
 typedef struct {
@@ -461,6 +475,14 @@ SNS_API int sns_host_aggregate(int32_t n_nodes, const int32_t* rowptr, const int
  * greedy sweep, = sns_host_aggregate.                                          */
 SNS_API int sns_host_aggregate_pts(int32_t n_nodes, const int32_t* rowptr, const int32_t* colind, int32_t n_active, int max_agg,
                            const double* pts, int32_t* agg_out, int32_t* n_agg_out, int32_t* which_out);
+
+/* (amg_aggregation = 1) aggregation of the first n_active nodes by operator strength: strength[nnzb] = one value per block slot
+ * (what SNS_EXPORT_STRENGTH returns: || D_i^-1/2 A_ij D_j^-1/2 ||_F in the point-diagonally balanced basis), symmetrised by the
+ * larger of s_ij and s_ji; pairwise heavy-edge matching of the strong graph, nodes -> pairs -> quadruples -> octets.  At most
+ * max_agg (1..8) members per aggregate, every aggregate connected in the strong graph; agg_out[n_nodes] gets the aggregate id
+ * (-1 for inactive nodes).  What the hierarchy build runs on level 0 (sns_export SNS_EXPORT_AGG0).                       */
+SNS_API int sns_host_aggregate_strength(int32_t n_nodes, const int32_t* rowptr, const int32_t* colind, int32_t n_active,
+                                        int max_agg, const float* strength, int32_t* agg_out, int32_t* n_agg_out);
 
 /* owned rows (i < n_owned) of a local pattern that reference a ghost column (>= n_owned): the boundary rows of the
  * interior / boundary split of the multi-GPU SpMV -- interior rows are computed while the halo is in flight

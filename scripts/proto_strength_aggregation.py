@@ -1,0 +1,154 @@
+"""CPU prototype (scipy) of the fine-level aggregation by operator strength (amg_aggregation = 1), run BEFORE the HIP path was
+written: does an aggregation that keeps a sliver's four nodes together, smoothed with the aggregates' dense blocks, remove the
+sliver mesh's iteration penalty?  The 2 x 2 of fine-level aggregation (geometric = sns_host_aggregate_pts, strength =
+sns_host_aggregate_strength on the numpy strength below) and fine-level smoother (nodal 4 x 4 blocks, aggregate blocks =
+amg_block_smooth = 2); levels >= 1 are the same in all four cases (greedy pattern aggregation, nodal blocks, sweeps 1/4/6/2 as
+oracle.proto_amg).  Two-stream channel, Re 50, on a Delaunay mesh of the jittered cubic (sliver-rich) or the body-centred lattice;
+BiCGStab iterations to rtol 1e-8 for the Stokes operator and for the Navier-Stokes Jacobian at the Stokes solution.
+
+    python scripts/proto_strength_aggregation.py 24 cubic [seed]
+"""
+import os
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+from oracle import cport, proto_amg as PA  # noqa: E402
+from stabilized_navier_stokes_flow_fenicsx_amd import _lib, bcs as B, mesh as M  # noqa: E402
+
+
+def strength(rowptr, colind, vals):
+    """s_ij = || D_i^-1/2 A_ij D_j^-1/2 ||_F per block slot (D = |point diagonal|), 0 on the diagonal slot: what k_strength computes."""
+    n = len(rowptr) - 1
+    V = vals.reshape(-1, 4, 4)
+    rows = np.repeat(np.arange(n), np.diff(rowptr))
+    dg = V[rows == colind][:, np.arange(4), np.arange(4)]
+    d = np.zeros((n, 4))
+    d[rows[rows == colind]] = np.abs(dg)
+    si = np.where(d > 0, 1.0 / np.sqrt(np.where(d > 0, d, 1.0)), 0.0)
+    S = si[rows][:, :, None] * V * si[colind][:, None, :]
+    s = np.sqrt((S * S).sum(axis=(1, 2)))
+    s[rows == colind] = 0.0
+    return s.astype(np.float32)
+
+
+def aggregate_block_inv(A, agg, nc):
+    """Block-diagonal inverse of A over the aggregates; an aggregate of more than 8 nodes is split into blocks of at most 8
+    (32 dofs) in node order, as the smoother blocks of csrc/sns_block.hip are."""
+    nodes = np.lexsort((np.arange(len(agg)), agg))
+    first = np.searchsorted(agg[nodes], agg[nodes], side="left")
+    blk_of = np.empty(len(agg), np.int64)
+    blk_of[nodes] = agg[nodes].astype(np.int64) * 64 + (np.arange(len(agg)) - first) // 8
+    _, agg = np.unique(blk_of, return_inverse=True)
+    nc = int(agg.max()) + 1
+    n4 = A.shape[0]
+    node = np.arange(n4) // 4
+    a_of = agg[node]
+    order = np.lexsort((np.arange(n4), a_of))
+    start = np.searchsorted(a_of[order], np.arange(nc + 1))
+    size = np.diff(start)
+    assert size.max() <= 32
+    pos = np.empty(n4, np.int64)
+    pos[order] = np.arange(n4) - start[a_of[order]]
+    C = A.tocoo()
+    keep = a_of[C.row] == a_of[C.col]
+    r, c, v = C.row[keep], C.col[keep], C.data[keep]
+    Bk = np.zeros((nc, 32, 32))
+    Bk[a_of[r], pos[r], pos[c]] = v
+    pad = np.arange(32)[None, :] >= size[:, None]
+    Bk[:, np.arange(32), np.arange(32)] += pad
+    Bi = np.linalg.inv(Bk)
+    # scatter back: entry (i, j) of the inverse for every pair of dofs in one aggregate
+    rr, cc, vv = [], [], []
+    for s in np.unique(size):
+        ags = np.nonzero(size == s)[0]
+        mem = order[start[ags][:, None] + np.arange(s)[None, :]]              # (k, s) dofs
+        rr.append(np.repeat(mem, s, axis=1).ravel())
+        cc.append(np.tile(mem, (1, s)).ravel())
+        vv.append(Bi[ags][:, :s, :s].reshape(len(ags), -1).ravel())
+    return sp.csr_matrix((np.concatenate(vv), (np.concatenate(rr), np.concatenate(cc))), shape=A.shape)
+
+
+def hierarchy(A, free, agg0, nc0, fine_blocks):
+    """proto_amg.setup with the fine aggregation given and (optionally) the aggregate-block fine smoother."""
+    levels = []
+    n = A.shape[0] // 4
+    L = PA.Level()
+    L.A, L.n = A.tocsr(), n
+    L.Dinv = aggregate_block_inv(L.A, agg0, nc0) if fine_blocks else PA.block_diag_inv(L.A, n)
+    lam = PA.lam_max(L.A, L.Dinv, its=30)
+    L.omega = min(0.8, 4.0 / (3.0 * lam))
+    L.lam = lam
+    dof = np.arange(4 * n)
+    col = 4 * agg0[dof // 4].astype(np.int64) + dof % 4
+    L.P = sp.csr_matrix((free.astype(np.float64), (dof, col)), shape=(4 * n, 4 * nc0))
+    Ac = (L.P.T @ L.A @ L.P).tocsr()
+    empty = np.asarray(abs(Ac).sum(axis=1)).ravel() == 0
+    if empty.any():
+        Ac = Ac + sp.diags(empty.astype(np.float64))
+    levels.append(L)
+    levels += PA.setup(Ac, None, coarse_size=256)
+    return levels
+
+
+def solve(A, b, levels):
+    M_ = spla.LinearOperator(A.shape, matvec=lambda v: PA.cycle(levels, 0, v, sched=(1, 4, 6, 2)))
+    its = [0]
+    x, info = spla.bicgstab(A, b, rtol=1e-8, atol=0.0, M=M_, maxiter=600, callback=lambda xk: its.__setitem__(0, its[0] + 1))
+    return x, its[0], info
+
+
+def sliver_together(m, agg, frac=0.01):
+    q, _ = M.tet_quality(m)
+    worst = np.argsort(q, kind="stable")[: max(1, int(frac * len(q)))]
+    a = agg[m.tets[worst]]
+    return float(np.mean((a == a[:, :1]).all(axis=1)))
+
+
+def main():
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 24
+    lattice = sys.argv[2] if len(sys.argv) > 2 else "cubic"
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+    Re = 50.0
+    m = M.delaunay_channel_mesh(n, lattice=lattice, seed=seed)
+    q, dih = M.tet_quality(m)
+    mask, g = B.channel_bcs(m, *B.two_stream_profiles(0.5)).flatten()
+    free = mask == 0
+    rp, ci = cport.pattern(m.num_nodes, m.tets)
+    vals, F = cport.assemble("stokes", m.points, m.tets, None, Re, mask, g, rp, ci)
+    As = cport.to_scipy(m.num_nodes, rp, ci, vals)
+    print(f"delaunay {lattice} n={n} seed {seed}: {m.num_tets} tets {m.num_nodes} nodes; radius ratio 0.1 % / 1 % quantile "
+          f"{np.quantile(q, 0.001):.3f} / {np.quantile(q, 0.01):.3f}, min dihedral {dih.min():.2f} deg", flush=True)
+    t0 = time.time()
+    s = strength(rp, ci, vals)
+    agg_s, nc_s = _lib.host_aggregate_strength(rp, ci, s, max_agg=8)
+    t_s = time.time() - t0
+    agg_g, nc_g, which = _lib.host_aggregate(rp, ci, None, 8, m.points)
+    print(f"  aggregates: geometric {nc_g} ({m.num_nodes / nc_g:.2f} nodes each, {'pairwise' if which else 'greedy'}); strength "
+          f"{nc_s} ({m.num_nodes / nc_s:.2f} each, {t_s:.2f} s); worst 1 % of tets with all four nodes in one aggregate: "
+          f"geometric {sliver_together(m, agg_g):.3f}, strength {sliver_together(m, agg_s):.3f}", flush=True)
+    bs = -F
+    # the Navier-Stokes Jacobian at the Stokes solution (the first Newton step's operator)
+    levels = hierarchy(As, free, agg_g, nc_g, False)
+    xs, _, _ = solve(As, bs, levels)
+    vj, Fj = cport.assemble("ns", m.points, m.tets, xs, Re, mask, g, rp, ci)
+    Aj = cport.to_scipy(m.num_nodes, rp, ci, vj)
+    for case, (agg, nc, blocks) in (("A geometric + nodal", (agg_g, nc_g, False)), ("B geometric + aggregate blocks", (agg_g, nc_g, True)),
+                                    ("C strength + nodal", (agg_s, nc_s, False)), ("D strength + aggregate blocks", (agg_s, nc_s, True))):
+        out = []
+        for name, A, b in (("stokes", As, bs), ("ns", Aj, -Fj)):
+            t0 = time.time()
+            levels = hierarchy(A, free, agg, nc, blocks)
+            _, its, info = solve(A, b, levels)
+            out.append(f"{name} its {its:4d}{'' if info == 0 else ' (info %d)' % info}  lambda_max {levels[0].lam:.2f} "
+                       f"omega {levels[0].omega:.2f}  {time.time() - t0:.0f}s")
+        print(f"  {case:32s} " + "   ".join(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

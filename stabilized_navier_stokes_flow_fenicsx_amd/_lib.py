@@ -50,6 +50,7 @@ class SnsOptions(C.Structure):
         ("amg_fuse_restrict", C.c_int),
         ("halo_windows", C.c_int),
         ("amg_exact_sweeps", C.c_int),
+        ("amg_aggregation", C.c_int),
     ]
 
 
@@ -60,11 +61,11 @@ class SnsTimings(C.Structure):
 
 
 # constants of sns.h
-ABI_VERSION = 7                          # SNS_ABI_VERSION of the header this mirror was written against
+ABI_VERSION = 8                          # SNS_ABI_VERSION of the header this mirror was written against
 FORM_STOKES, FORM_NS = 0, 1
 KSP_BICGSTAB, KSP_FGMRES, KSP_TFQMR = 0, 1, 2
 PC_NONE, PC_BJACOBI, PC_AMG = 0, 1, 2
-EXPORT_ROWPTR, EXPORT_COLIND, EXPORT_VALS, EXPORT_KE, EXPORT_FE = 0, 1, 2, 3, 4
+EXPORT_ROWPTR, EXPORT_COLIND, EXPORT_VALS, EXPORT_KE, EXPORT_FE, EXPORT_STRENGTH, EXPORT_AGG0 = 0, 1, 2, 3, 4, 5, 6
 KSP_NAMES = {"bicgstab": KSP_BICGSTAB, "bcgs": KSP_BICGSTAB, "fgmres": KSP_FGMRES, "gmres": KSP_FGMRES, "tfqmr": KSP_TFQMR}
 PC_NAMES = {"none": PC_NONE, "bjacobi": PC_BJACOBI, "jacobi": PC_BJACOBI, "amg": PC_AMG}
 
@@ -128,6 +129,7 @@ _SIGNATURES = [
     ("sns_host_pattern", C.c_int, [C.c_int32, C.c_int64, _P, C.POINTER(C.c_int64), _P, _P, _P, _P]),
     ("sns_host_aggregate", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int, _P, C.POINTER(C.c_int32)]),
     ("sns_host_aggregate_pts", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("sns_host_aggregate_strength", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int, _P, _P, C.POINTER(C.c_int32)]),
     ("sns_host_boundary_rows", C.c_int, [C.c_int32, _P, _P, _P, C.POINTER(C.c_int32)]),
     ("sns_host_cycle_policy", C.c_int, [C.POINTER(SnsOptions), C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     ("sns_host_hessenberg_eigs", C.c_int, [C.c_int, _P, _P, _P]),
@@ -216,6 +218,24 @@ def host_aggregate(rowptr, colind, n_active=None, max_agg=8, pts=None):
     check(lib.sns_host_aggregate_pts(n, rowptr.ctypes.data, colind.ctypes.data, n if n_active is None else n_active,
                                      max_agg, pts.ctypes.data, agg.ctypes.data, C.byref(nc), C.byref(which)))
     return agg, nc.value, which.value
+
+
+def host_aggregate_strength(rowptr, colind, strength, n_active=None, max_agg=8):
+    """(agg, n_agg) of the aggregation by operator strength (amg_aggregation = 1): ``strength`` = one value per block slot of the
+    pattern (SNS_EXPORT_STRENGTH), as the hierarchy build aggregates level 0 (sns_host_aggregate_strength)."""
+    import numpy as np
+    lib = load()
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+    colind = np.ascontiguousarray(colind, dtype=np.int32)
+    strength = np.ascontiguousarray(strength, dtype=np.float32)
+    n = len(rowptr) - 1
+    if len(strength) != len(colind):
+        raise ValueError("strength needs one value per block slot")
+    agg = np.empty(n, np.int32)
+    nc = C.c_int32()
+    check(lib.sns_host_aggregate_strength(n, rowptr.ctypes.data, colind.ctypes.data, n if n_active is None else n_active,
+                                          max_agg, strength.ctypes.data, agg.ctypes.data, C.byref(nc)))
+    return agg, nc.value
 
 
 def host_boundary_rows(n_owned: int, rowptr, colind):

@@ -63,6 +63,7 @@ void sns_default_options(sns_options* o) {
     o->amg_fuse_restrict = 1;
     o->halo_windows = 1;
     o->amg_exact_sweeps = 1;
+    o->amg_aggregation = 0;
 }
 
 
@@ -75,6 +76,17 @@ int sns_abi_version(void) { return SNS_ABI_VERSION; }
 int64_t sns_options_size(void) { return (int64_t)sizeof(sns_options); }
 
 
+// amg_aggregation: 0 or 1; 1 on 3-D handles only (the strength kernel reads the 4 x 4 blocks of the P1-P1 tet operator) and with
+// aggregates that fit the 32 x 32 smoother blocks
+static int check_aggregation_option(int dim, const sns_options& o) {
+    if (o.amg_aggregation == 0) return SNS_OK;
+    if (o.amg_aggregation != 1 || dim != 3 || o.amg_agg_size > policy::STRENGTH_MAX_AGG) {
+        set_error("amg_aggregation: 0, or 1 on a 3-D handle with amg_agg_size <= 8");
+        return SNS_E_ARG;
+    }
+    return SNS_OK;
+}
+
 // dim 3: points [n*3], cells [E*4];  dim 2: points [n*2], cells [E*3]
 static int create_common(int dim, sns_handle* out, int32_t n_nodes, int64_t n_tets, const double* points_in,
                          const int32_t* cells_in, const uint8_t* bc_mask_in, const double* bc_val_in, int device,
@@ -84,6 +96,7 @@ static int create_common(int dim, sns_handle* out, int32_t n_nodes, int64_t n_te
         return SNS_E_ARG;
     }
     *out = nullptr;
+    if (opt) SNS_TRY(check_aggregation_option(dim, *opt));
     const int npe = dim + 1;
     // host validation: vertex ids in range, non-degenerate cells (kernels divide by det J)
     for (int64_t t = 0; t < n_tets; ++t) {
@@ -233,9 +246,17 @@ int sns_create_2d(sns_handle* out, int32_t n_nodes, int64_t n_tris, const double
 
 namespace {
 
-int ensure_hierarchy(sns_ctx* h) {
+// assembles_next: the caller (a solve driver) assembles next -- with amg_aggregation = 1, which aggregates the fine level by the
+// assembled operator, the hierarchy waits for that assembly (the driver calls here again once it is done); any other caller
+// without an assembled operator gets SNS_E_STATE and the handle stays as it was
+int ensure_hierarchy(sns_ctx* h, bool assembles_next = false) {
     if (!h->pattern) return SNS_OK;                       // already built
     if (h->opt.pc_type != SNS_PC_AMG) return SNS_OK;      // built when (if) AMG is first asked for
+    if (h->opt.amg_aggregation == 1 && !h->has_matrix) {
+        if (assembles_next) return SNS_OK;
+        set_error("amg_aggregation = 1: the hierarchy is built from the assembled operator; assemble first");
+        return SNS_E_STATE;
+    }
     int rc = build_hierarchy(h, *h->pattern);
     h->pattern.reset();
     return rc;
@@ -298,6 +319,7 @@ int sns_set_stream(sns_handle h, void* s) {
 
 int sns_set_options(sns_handle h, const sns_options* o) {
     if (!h || !o) return SNS_E_ARG;
+    SNS_TRY(check_aggregation_option(h->dim, *o));
     const bool pc_changed = (o->pc_type != h->opt.pc_type) || (o->amg_f32_matrix != h->opt.amg_f32_matrix) ||
                             (o->amg_fused_post != h->opt.amg_fused_post) || (o->amg_block_smooth != h->opt.amg_block_smooth);
     const bool damping_changed = (o->amg_omega != h->opt.amg_omega);
@@ -538,7 +560,7 @@ int sns_krylov_solve(sns_handle h, const double* b, double* x, int* its, int* re
 
 int sns_stokes_solve(sns_handle h, double* U, int* ksp_its, int* reason, double* rnorm) {
     if (!h || !U || !ksp_its || !reason || !rnorm) return SNS_E_ARG;
-    SNS_TRY(ensure_hierarchy(h));
+    SNS_TRY(ensure_hierarchy(h, true));
     const int64_t nd = nred_of(h), ld = ld_of(h);
     if (!h->nw_F) {
         SNS_TRY(dev_alloc(&h->nw_F, (size_t)ld)); SNS_TRY(dev_alloc(&h->nw_y, (size_t)ld));
@@ -548,6 +570,7 @@ int sns_stokes_solve(sns_handle h, double* U, int* ksp_its, int* reason, double*
     }
     // one Newton step of the linear problem from w = 0:  A U = -F(0),  F(0) = lifting, F_B = -g   (:198-214)
     SNS_TRY(timed_assemble(h, SNS_FORM_STOKES, nullptr, h->nw_F, true));
+    SNS_TRY(ensure_hierarchy(h));
     hipLaunchKernelGGL(k_scale_copy, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, -1.0, h->nw_F, h->nw_F);
     HIP_TRY(hipMemsetAsync(U, 0, nd * sizeof(double), h->stream));
     SNS_TRY(krylov(h, h->nw_F, U, ksp_its, reason, rnorm));
@@ -565,7 +588,7 @@ int sns_stokes_solve(sns_handle h, double* U, int* ksp_its, int* reason, double*
 int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int* total_ksp, double* hist,
                      int hist_cap) {
     if (!h || !w || !its_out || !reason_out) return SNS_E_ARG;
-    SNS_TRY(ensure_hierarchy(h));
+    SNS_TRY(ensure_hierarchy(h, true));
     const sns_options& o = h->opt;
     const int64_t nd = nred_of(h), ld = ld_of(h);
     const int g = vec_grid(nd);
@@ -580,6 +603,7 @@ int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int
     auto record = [&](double f) { if (hist && nh < hist_cap) hist[nh] = f; ++nh; };
     SNS_TRY(halo_exchange(h, w));
     SNS_TRY(timed_assemble(h, SNS_FORM_NS, w, F, true));
+    SNS_TRY(ensure_hierarchy(h));
     double f, f0;
     SNS_TRY(norm2(h, F, &f));
     f0 = f;
@@ -691,6 +715,22 @@ int sns_export(sns_handle h, int what, void* dst, int64_t nbytes) {
         case SNS_EXPORT_VALS: src = L.vals; need = L.nnzb * 16 * 8; break;
         case SNS_EXPORT_KE: src = h->Ke; need = h->E * 256 * 8; break;
         case SNS_EXPORT_FE: src = h->Fe; need = h->E * 16 * 8; break;
+        case SNS_EXPORT_STRENGTH: {
+            if (!h->has_matrix) { set_error("sns_export: strength before a matrix was assembled"); return SNS_E_STATE; }
+            if (nbytes != L.nnzb * 4) { set_error("sns_export: size mismatch, need " + std::to_string(L.nnzb * 4)); return SNS_E_ARG; }
+            double* scale = nullptr;
+            SNS_TRY(dev_alloc(&scale, 4 * (size_t)L.n));
+            const int rc = compute_strength(h, (float*)dst, scale);
+            const int rs = rc == SNS_OK ? sync_stream(h) : rc;
+            (void)hipFree(scale);
+            return rs;
+        }
+        case SNS_EXPORT_AGG0: {
+            if (h->agg0.empty()) { set_error("sns_export: aggregate map before the hierarchy was built"); return SNS_E_STATE; }
+            if (nbytes != (int64_t)L.n * 4) { set_error("sns_export: size mismatch, need " + std::to_string((int64_t)L.n * 4)); return SNS_E_ARG; }
+            HIP_TRY(hipMemcpyAsync(dst, h->agg0.data(), (size_t)nbytes, hipMemcpyHostToDevice, h->stream));
+            return sync_stream(h);
+        }
         default: set_error("sns_export: unknown array"); return SNS_E_ARG;
     }
     if (!src) { set_error("sns_export: array not produced yet"); return SNS_E_STATE; }

@@ -178,6 +178,7 @@ struct sns_ctx {
     std::vector<std::vector<int32_t>> ghost_own;
     std::unique_ptr<HostPattern> pattern;      // kept until the (lazy) hierarchy build
     std::vector<double> host_pts;              // ... with the node coordinates (3 per node): the aggregation's strength filter on anisotropic meshes
+    std::vector<int32_t> agg0;                 // the level-0 aggregate map as built (owned nodes; -1 elsewhere): SNS_EXPORT_AGG0
     // optional per-launch timing of the fine-level SpMV family
     bool time_kernels = false;
     std::vector<std::array<hipEvent_t, 2>> ev_pool;
@@ -213,6 +214,8 @@ int op_apply_dot(sns_ctx* h, double* x, double* y, const double* dotw);
 int op_residual(sns_ctx* h, double* x, const double* b, double* r);
 // csrc/sns_krylov.hip: BiCGStab / TFQMR / FGMRES and the solve driver with the damping retry
 int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm);
+// csrc/sns_strength.hip: the strength of the fine-level couplings (amg_aggregation = 1, SNS_EXPORT_STRENGTH)
+int compute_strength(sns_ctx* h, float* out, double* scale);
 int norm2(sns_ctx* h, const double* x, double* out);
 int dot(sns_ctx* h, const double* x, const double* y, double* out);
 }  // namespace sns

@@ -548,6 +548,103 @@ void build_ap_pattern(const HostPattern& F, int32_t n_rows, const std::vector<in
     }
 }
 
+// Aggregation by operator strength (amg_aggregation = 1, the fine level only): pairwise heavy-edge matching in the style of Notay's
+// pairwise aggregation.  The measure s (one value per block slot, k_strength) is symmetrised, s_ij <- max(s_ij, s_ji), and an edge is
+// strong when s_ij >= STRENGTH_THETA x the strongest coupling of i or of j.  log2(max_agg) passes (nodes -> pairs -> quadruples ->
+// octets) each match the strongest remaining strong edges first, ties broken by (min id, max id); between clusters the strength is
+// the sum of their members' strong couplings.  Single nodes left over join their strongest adjacent cluster with room.  A sliver's
+// four nodes are coupled far more strongly to each other than to anything else, so they end up in one aggregate -- one block of
+// the aggregate-block smoother -- instead of setting the damping of the whole level.  A node without a strong edge (all its dofs
+// Dirichlet) is an aggregate of its own.
+void aggregate_strength(const HostPattern& F, int32_t n_active, int max_agg, const float* strength, std::vector<int32_t>& agg,
+                        int32_t& nc) {
+    struct Edge { int32_t a, b; double w; };
+    // strong edges i < j of the active nodes, with their symmetrised strength
+    std::vector<double> smax((size_t)n_active, 0.0);
+    auto sym = [&](int32_t i, int32_t k) -> double {
+        const int32_t j = F.colind[k];
+        const int32_t* b = F.colind.data() + F.rowptr[j];
+        const int32_t* e = F.colind.data() + F.rowptr[(size_t)j + 1];
+        const int32_t* t = std::lower_bound(b, e, i);
+        const double sji = (t != e && *t == i) ? (double)strength[t - F.colind.data()] : 0.0;
+        return std::max((double)strength[k], sji);
+    };
+    for (int32_t i = 0; i < n_active; ++i)
+        for (int32_t k = F.rowptr[i]; k < F.rowptr[i + 1]; ++k) {
+            const int32_t j = F.colind[k];
+            if (j != i && j < n_active) smax[i] = std::max(smax[i], sym(i, k));
+        }
+    std::vector<Edge> strong;
+    for (int32_t i = 0; i < n_active; ++i)
+        for (int32_t k = F.rowptr[i]; k < F.rowptr[i + 1]; ++k) {
+            const int32_t j = F.colind[k];
+            if (j <= i || j >= n_active) continue;
+            const double w = sym(i, k);
+            if (w > 0.0 && (w >= policy::STRENGTH_THETA * smax[i] || w >= policy::STRENGTH_THETA * smax[j])) strong.push_back({i, j, w});
+        }
+    auto heaviest_first = [](const Edge& x, const Edge& y) {
+        if (x.w != y.w) return x.w > y.w;
+        return x.a != y.a ? x.a < y.a : x.b < y.b;
+    };
+    std::vector<int32_t> of((size_t)n_active), size_((size_t)n_active, 1), newid;
+    std::iota(of.begin(), of.end(), 0);
+    int32_t ncl = n_active;
+    std::vector<Edge> ce;                                   // edges between clusters, summed
+    auto cluster_edges = [&]() {
+        ce.clear();
+        for (const Edge& e : strong) {
+            const int32_t a = of[e.a], b = of[e.b];
+            if (a != b) ce.push_back({std::min(a, b), std::max(a, b), e.w});
+        }
+        std::sort(ce.begin(), ce.end(), [](const Edge& x, const Edge& y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+        size_t m = 0;
+        for (size_t k = 0; k < ce.size(); ++k) {
+            if (m > 0 && ce[m - 1].a == ce[k].a && ce[m - 1].b == ce[k].b) ce[m - 1].w += ce[k].w;
+            else ce[m++] = ce[k];
+        }
+        ce.resize(m);
+        std::sort(ce.begin(), ce.end(), heaviest_first);
+    };
+    for (int round = 1; (1 << round) <= max_agg; ++round) {
+        cluster_edges();
+        std::vector<int32_t> partner((size_t)ncl, -1);
+        for (const Edge& e : ce)
+            if (partner[e.a] < 0 && partner[e.b] < 0 && size_[e.a] + size_[e.b] <= max_agg) { partner[e.a] = e.b; partner[e.b] = e.a; }
+        // new ids in the order of the clusters' smallest member (cluster ids already run in that order)
+        newid.assign((size_t)ncl, -1);
+        std::vector<int32_t> nsize;
+        for (int32_t a = 0; a < ncl; ++a) {
+            if (newid[a] >= 0) continue;
+            newid[a] = (int32_t)nsize.size();
+            int32_t s = size_[a];
+            if (partner[a] >= 0) { newid[partner[a]] = newid[a]; s += size_[partner[a]]; }
+            nsize.push_back(s);
+        }
+        for (int32_t i = 0; i < n_active; ++i) of[i] = newid[of[i]];
+        size_.swap(nsize);
+        ncl = (int32_t)size_.size();
+    }
+    // single nodes left over join their strongest adjacent cluster of at least two members that still has room
+    cluster_edges();
+    std::vector<int32_t> target((size_t)ncl, -1);
+    for (const Edge& e : ce) {
+        for (int side = 0; side < 2; ++side) {
+            const int32_t s = side ? e.b : e.a, c = side ? e.a : e.b;
+            if (size_[s] != 1 || target[s] >= 0 || size_[c] < 2 || target[c] >= 0 || size_[c] >= max_agg) continue;
+            target[s] = c;
+            ++size_[c];
+        }
+    }
+    newid.assign((size_t)ncl, -1);
+    nc = 0;
+    for (int32_t a = 0; a < ncl; ++a)
+        if (target[a] < 0) newid[a] = nc++;
+    for (int32_t a = 0; a < ncl; ++a)
+        if (target[a] >= 0) newid[a] = newid[target[a]];
+    agg.assign((size_t)F.n, -1);
+    for (int32_t i = 0; i < n_active; ++i) agg[i] = newid[of[i]];
+}
+
 void build_aggregation_active(const HostPattern& F, int32_t n_active, int max_agg, HostAggregation& A) {
     std::vector<int32_t> agg;
     int32_t nc = 0;
@@ -606,6 +703,26 @@ extern "C" int sns_host_aggregate_pts(int32_t n, const int32_t* rowptr, const in
     std::copy(agg.begin(), agg.end(), agg_out);
     if (n_agg_out) *n_agg_out = nc;
     if (which_out) *which_out = which;
+    return SNS_OK;
+}
+
+extern "C" int sns_host_aggregate_strength(int32_t n, const int32_t* rowptr, const int32_t* colind, int32_t n_active, int max_agg,
+                                           const float* strength, int32_t* agg_out, int32_t* n_agg_out) {
+    if (n <= 0 || !rowptr || !colind || !strength || !agg_out || n_active < 0 || n_active > n || max_agg < 1 ||
+        max_agg > sns::policy::STRENGTH_MAX_AGG) {
+        sns::set_error("sns_host_aggregate_strength: bad arguments (1 <= max_agg <= 8)");
+        return SNS_E_ARG;
+    }
+    sns::HostPattern F;
+    F.n = n;
+    F.rowptr.assign(rowptr, rowptr + n + 1);
+    F.nnzb = rowptr[n];
+    F.colind.assign(colind, colind + F.nnzb);
+    std::vector<int32_t> agg;
+    int32_t nc = 0;
+    sns::aggregate_strength(F, n_active, max_agg, strength, agg, nc);
+    std::copy(agg.begin(), agg.end(), agg_out);
+    if (n_agg_out) *n_agg_out = nc;
     return SNS_OK;
 }
 

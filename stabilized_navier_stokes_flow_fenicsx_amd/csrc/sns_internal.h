@@ -110,6 +110,10 @@ struct Level {
 
 void aggregate_nodes(const HostPattern& F, int32_t n_active, int max_agg, std::vector<int32_t>& agg, int32_t& nc,
                      const double* pts = nullptr, int* which = nullptr);
+// aggregation of nodes [0, n_active) by operator strength: `strength` = one value per block slot of F (k_strength); the aggregates
+// have at most max_agg members, are connected in the strong graph and do not depend on the node numbering (ties aside)
+void aggregate_strength(const HostPattern& F, int32_t n_active, int max_agg, const float* strength, std::vector<int32_t>& agg,
+                        int32_t& nc);
 void set_error(const std::string& s);
 
 }  // namespace sns

@@ -394,6 +394,29 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
 }
 
 
+// Level 0 aggregated by operator strength (amg_aggregation = 1): the strength of the assembled fine operator (csrc/sns_strength.hip),
+// copied to the host, and sns_host.cpp's aggregate_strength over the owned nodes.  The fp32 strength is freed again.
+static int aggregate_fine_by_strength(sns_ctx* h, const HostPattern& fine, std::vector<int32_t>& agg, int32_t& nc) {
+    const Level& L = h->levels[0];
+    if (!h->has_matrix) { set_error("amg_aggregation = 1: the hierarchy is built from the assembled operator; assemble first"); return SNS_E_STATE; }
+    float* s_dev = nullptr;
+    double* scale = nullptr;
+    SNS_TRY(dev_alloc(&s_dev, (size_t)L.nnzb));
+    int rc = dev_alloc(&scale, 4 * (size_t)L.n);
+    if (rc == SNS_OK) rc = compute_strength(h, s_dev, scale);
+    std::vector<float> s((size_t)L.nnzb);
+    if (rc == SNS_OK && L.nnzb > 0 && hipMemcpyAsync(s.data(), s_dev, s.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
+        set_error("amg_aggregation = 1: copy of the strength to the host failed");
+        rc = SNS_E_HIP;
+    }
+    if (rc == SNS_OK && hipStreamSynchronize(h->stream) != hipSuccess) { set_error("amg_aggregation = 1: strength kernel failed"); rc = SNS_E_HIP; }
+    (void)hipFree(s_dev);
+    if (scale) (void)hipFree(scale);
+    if (rc != SNS_OK) return rc;
+    aggregate_strength(fine, h->n_owned, std::min(h->opt.amg_agg_size, policy::STRENGTH_MAX_AGG), s.data(), agg, nc);
+    return SNS_OK;
+}
+
 // Build the aggregation hierarchy (symbolic, once per mesh; collective over the ranks).
 // Aggregates never cross ranks, but the Galerkin operators keep every cross-rank coupling:
 // a ghost fine node's aggregate becomes a ghost coarse node, and each level gets its own
@@ -438,8 +461,13 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
         if (!dist && l >= 1 && n_owned <= policy::coarsest_rows(o)) break;       // serial: this level is solved directly
         std::vector<int32_t> agg;
         int32_t nc_owned = 0;
-        aggregate_nodes(cur, n_owned, std::min(255, std::max(2, o.amg_agg_size)), agg, nc_owned,
-                        cur_pts.size() == (size_t)3 * cur.n ? cur_pts.data() : nullptr);
+        if (l == 0 && o.amg_aggregation == 1) {
+            SNS_TRY(aggregate_fine_by_strength(h, cur, agg, nc_owned));
+        } else {
+            aggregate_nodes(cur, n_owned, std::min(255, std::max(2, o.amg_agg_size)), agg, nc_owned,
+                            cur_pts.size() == (size_t)3 * cur.n ? cur_pts.data() : nullptr);
+        }
+        if (l == 0) h->agg0 = agg;
         double prog[2] = {(double)n_owned, (double)nc_owned};
         SNS_TRY(global_sum(h, prog, 2));
         if (prog[1] >= prog[0] || prog[1] == 0.0) break;      // no progress anywhere

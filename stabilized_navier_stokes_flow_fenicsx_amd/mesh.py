@@ -343,6 +343,31 @@ def delaunay_channel_mesh(n: int = 16, *, length: float = 4.0, seed: int = 0, la
                    meta={"lo": lo, "hi": hi, "tags": tags, "kind": "channel", "inner_half_width": inner_half_width, "h": h})
 
 
+def tet_quality(mesh: TetMesh) -> tuple[np.ndarray, np.ndarray]:
+    """Per-tet shape quality: (radius ratio 3 r_in / r_circ, minimum dihedral angle in degrees).  The radius ratio is 1 for the
+    regular tet and tends to 0 for a flattened one (a sliver: four nearly coplanar vertices with no short edge); the Kuhn tet of
+    the structured meshes has sqrt(3) / (1 + sqrt(2)) = 0.717 and a minimum dihedral angle of 45 degrees."""
+    X = np.asarray(mesh.points, dtype=np.float64)[np.asarray(mesh.tets, dtype=np.int64)]
+    a, b, c = X[:, 1] - X[:, 0], X[:, 2] - X[:, 0], X[:, 3] - X[:, 0]
+    six_v = np.abs(np.einsum("ij,ij->i", a, np.cross(b, c)))
+    # face k is the face opposite vertex k; its area-weighted normal (orientation fixed below to point away from vertex k)
+    n = np.stack([np.cross(X[:, (k + 2) % 4] - X[:, (k + 1) % 4], X[:, (k + 3) % 4] - X[:, (k + 1) % 4]) for k in range(4)], axis=1)
+    to_k = X - X[:, [1, 2, 3, 0]]
+    n *= -np.sign(np.einsum("tkj,tkj->tk", n, to_k))[:, :, None]
+    area2 = np.linalg.norm(n, axis=2)                                       # twice the face areas
+    r_in = 3.0 * (six_v / 6.0) / (0.5 * area2.sum(axis=1))
+    cc = (np.einsum("ij,ij->i", a, a)[:, None] * np.cross(b, c) + np.einsum("ij,ij->i", b, b)[:, None] * np.cross(c, a)
+          + np.einsum("ij,ij->i", c, c)[:, None] * np.cross(a, b))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r_circ = np.linalg.norm(cc, axis=1) / np.maximum(2.0 * six_v, 1e-300)
+        ratio = np.where(six_v > 0, 3.0 * r_in / r_circ, 0.0)
+        u = n / np.maximum(area2, 1e-300)[:, :, None]
+    # the dihedral angle at the edge shared by faces k and l is pi minus the angle between their outward normals
+    dih = np.stack([np.arccos(np.clip(-np.einsum("ij,ij->i", u[:, k], u[:, l]), -1.0, 1.0))
+                    for k in range(4) for l in range(k + 1, 4)], axis=1)
+    return ratio, np.degrees(dih.min(axis=1))
+
+
 DFG_TAGS = {"inlet": 2, "outlet": 3, "wall": 4, "obstacle": 5}   # DFG_3D_Validation.py:104-109
 
 
