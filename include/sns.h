@@ -223,8 +223,11 @@ typedef struct {
                                amg_block_smooth = 2 (SNS_LEVEL_AGGREGATE_BLOCKS; amg_block_smooth = 0 or amg_f32_matrix = 0 still turn
                                the blocks off altogether).  For sliver-rich
                                meshes: a sliver's four nodes share an aggregate and its coupling no longer sets the damping of the whole
-                               level.  Levels >= 1 keep the default aggregation either way.  Fixed when the hierarchy is built; 1 needs
-                               an assembled operator then (SNS_E_STATE otherwise), amg_agg_size <= 8, and a 3-D handle (SNS_E_ARG) */
+                               level.  Levels >= 1 keep the default aggregation either way.  2: the IDENTICAL map as 1, built on the
+                               device (parallel locally-dominant matching, csrc/sns_aggregate.hip); only the map is copied to the host
+                               (10 M tets: 76 ms instead of 0.95 s for 1's host matcher).  Fixed when the hierarchy is built; 1
+                               and 2 need an assembled operator then (SNS_E_STATE otherwise), amg_agg_size <= 8, and a 3-D handle
+                               (SNS_E_ARG) */
 } sns_options;
 
 SNS_API void sns_default_options(sns_options* opt);
@@ -476,7 +479,7 @@ SNS_API int sns_host_aggregate(int32_t n_nodes, const int32_t* rowptr, const int
 SNS_API int sns_host_aggregate_pts(int32_t n_nodes, const int32_t* rowptr, const int32_t* colind, int32_t n_active, int max_agg,
                            const double* pts, int32_t* agg_out, int32_t* n_agg_out, int32_t* which_out);
 
-/* (amg_aggregation = 1) aggregation of the first n_active nodes by operator strength: strength[nnzb] = one value per block slot
+/* (amg_aggregation = 1; 2 builds the same map on the device) aggregation of the first n_active nodes by operator strength: strength[nnzb] = one value per block slot
  * (what SNS_EXPORT_STRENGTH returns: || D_i^-1/2 A_ij D_j^-1/2 ||_F in the point-diagonally balanced basis), symmetrised by the
  * larger of s_ij and s_ji; pairwise heavy-edge matching of the strong graph, nodes -> pairs -> quadruples -> octets.  At most
  * max_agg (1..8) members per aggregate, every aggregate connected in the strong graph; agg_out[n_nodes] gets the aggregate id

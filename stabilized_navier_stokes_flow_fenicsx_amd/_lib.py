@@ -222,7 +222,8 @@ def host_aggregate(rowptr, colind, n_active=None, max_agg=8, pts=None):
 
 def host_aggregate_strength(rowptr, colind, strength, n_active=None, max_agg=8):
     """(agg, n_agg) of the aggregation by operator strength (amg_aggregation = 1): ``strength`` = one value per block slot of the
-    pattern (SNS_EXPORT_STRENGTH), as the hierarchy build aggregates level 0 (sns_host_aggregate_strength)."""
+    pattern (SNS_EXPORT_STRENGTH), as the hierarchy build aggregates level 0 (sns_host_aggregate_strength).  amg_aggregation = 2
+    builds the identical map on the device."""
     import numpy as np
     lib = load()
     rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)

@@ -1,0 +1,609 @@
+// Aggregation of the fine level by operator strength ON THE DEVICE (amg_aggregation = 2): the identical map that sns_host.cpp's
+// aggregate_strength (amg_aggregation = 1) builds from the same strength, with only that map (4 B per node) copied to the host.
+//
+// The host function is a greedy heavy-edge matching over a strict total order (weight descending, then (min id, max id)
+// ascending).  Over a strict total order the greedy result equals LOCALLY-DOMINANT matching: match every pair (a, b) where b is
+// a's best eligible partner and a is b's, and repeat.  Each step matches at least the heaviest pending edge, so it always makes
+// progress; a step that matches nothing while edges are pending is a bug and ends the build with SNS_E_HIP.  For a fixed cluster
+// the order of its candidates is (weight descending, other id ascending).  The stages:
+//   k_agg_smax / k_agg_strong   the strong graph: s_ij <- max(s_ij, s_ji) (the transposed slot by binary search in the sorted row
+//                               j), smax per owned node, strong when w > 0 and w >= STRENGTH_THETA x smax of i or of j; one fp32
+//                               weight per block slot (0 = not strong) -- a max of fp32 values, exact in fp32
+//   k_agg_count / k_agg_fill    contraction to clusters: per cluster its members' strong slots into other clusters, insertion-
+//                               sorted by the other cluster (stable) and merged, the weights summed in fp64 in member / slot order.
+//                               The sums hold at most 16 fp32 terms within a few binary orders of magnitude: exact, so they do not
+//                               depend on the order and match the host's.  No float atomics anywhere
+//   k_agg_best / k_agg_match / k_agg_dirty
+//                               one matching step (pairwise rounds; size filter size_a + size_b <= max_agg) over the clusters
+//                               whose best partner may have changed
+//   k_agg_lead ... k_agg_merge  renumbering in the order of the clusters' smallest member: a cluster leads when it is unmatched or
+//                               the smaller of its pair, an exclusive scan of the leader flags gives the new ids
+//   k_agg_lbest / k_agg_laccept / k_agg_lcommit
+//                               leftover singles join their strongest adjacent cluster of >= 2 members with room: the pending edge
+//                               (s, c) is accepted when it is s's best pending edge and fewer than room_c pending edges at c are
+//                               heavier -- the sequential b-matching's result
+// A step is three launches; the host reads three 4-byte counters (pending, matched, next list) after it.  No grid-wide barrier, no
+// persistent kernel.  A rank without owned rows launches nothing.
+#include "sns_ctx.h"
+
+namespace sns {
+
+namespace {
+
+constexpr int AGG_TPB = 256;
+constexpr int SCAN_ITEMS = 4;                          // per thread: 1024 per block
+constexpr int SCAN_BLOCK = AGG_TPB * SCAN_ITEMS;
+
+inline unsigned agg_blocks(int64_t n) { return (unsigned)((n + AGG_TPB - 1) / AGG_TPB); }
+
+// (w1, d1) before (w2, d2) in the matcher's order for a fixed cluster: heavier first, then the smaller other id
+__device__ inline bool agg_before(double w1, int32_t d1, double w2, int32_t d2) { return w1 > w2 || (w1 == w2 && d1 < d2); }
+
+__device__ inline float agg_sym(int32_t i, int32_t k, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                const float* __restrict__ s) {
+    const int32_t j = colind[k];
+    int32_t lo = rowptr[j], hi = rowptr[j + 1];
+    const int32_t end = hi;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (colind[mid] < i) lo = mid + 1;
+        else hi = mid;
+    }
+    const float sji = (lo < end && colind[lo] == i) ? s[lo] : 0.0f;
+    const float sij = s[k];
+    return sij < sji ? sji : sij;
+}
+
+// ---- exclusive scan of int32 counts into int64 offsets out[0..n] (out[n] = total), three launches ---------------------------------
+__device__ inline int64_t block_exclusive_scan(int64_t v, int64_t* lds, int64_t* total) {
+    const int t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (int off = 1; off < AGG_TPB; off <<= 1) {
+        const int64_t add = t >= off ? lds[t - off] : 0;
+        __syncthreads();
+        lds[t] += add;
+        __syncthreads();
+    }
+    const int64_t incl = lds[t];
+    *total = lds[AGG_TPB - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_scan_sums(int32_t n, const int32_t* __restrict__ in, int64_t* __restrict__ bsum) {
+    __shared__ int64_t lds[AGG_TPB];
+    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
+    int64_t v = 0;
+    for (int q = 0; q < SCAN_ITEMS; ++q)
+        if (base + q < n) v += in[base + q];
+    int64_t tot;
+    block_exclusive_scan(v, lds, &tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_scan_top(int32_t nb, int64_t* __restrict__ bsum, int32_t n, int64_t* __restrict__ out) {
+    __shared__ int64_t lds[AGG_TPB];
+    int64_t carry = 0;
+    for (int32_t b0 = 0; b0 < nb; b0 += AGG_TPB) {
+        const int32_t b = b0 + (int32_t)threadIdx.x;
+        const int64_t v = b < nb ? bsum[b] : 0;
+        int64_t tot;
+        const int64_t ex = block_exclusive_scan(v, lds, &tot);
+        if (b < nb) bsum[b] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) out[n] = carry;
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_scan_apply(int32_t n, const int32_t* __restrict__ in, const int64_t* __restrict__ bsum,
+                                                        int64_t* __restrict__ out) {
+    __shared__ int64_t lds[AGG_TPB];
+    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + (int64_t)threadIdx.x * SCAN_ITEMS;
+    int32_t v[SCAN_ITEMS];
+    int64_t sum = 0;
+    for (int q = 0; q < SCAN_ITEMS; ++q) {
+        v[q] = base + q < n ? in[base + q] : 0;
+        sum += v[q];
+    }
+    int64_t tot;
+    int64_t run = bsum[blockIdx.x] + block_exclusive_scan(sum, lds, &tot);
+    for (int q = 0; q < SCAN_ITEMS; ++q)
+        if (base + q < n) {
+            out[base + q] = run;
+            run += v[q];
+        }
+}
+
+// ---- the strong graph ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(AGG_TPB) void k_agg_smax(int32_t n_act, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                      const float* __restrict__ s, float* __restrict__ smax) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i >= n_act) return;
+    float m = 0.0f;
+    for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+        const int32_t j = colind[k];
+        if (j == i || j >= n_act) continue;
+        const float w = agg_sym(i, k, rowptr, colind, s);
+        m = m < w ? w : m;
+    }
+    smax[i] = m;
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_strong(int32_t n_act, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                        const float* __restrict__ s, const float* __restrict__ smax, float* __restrict__ sw) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i >= n_act) return;
+    const double ti = policy::STRENGTH_THETA * (double)smax[i];
+    for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+        const int32_t j = colind[k];
+        float out = 0.0f;
+        if (j != i && j < n_act) {
+            const float w = agg_sym(i, k, rowptr, colind, s);
+            const double wd = (double)w;
+            if (wd > 0.0 && (wd >= ti || wd >= policy::STRENGTH_THETA * (double)smax[j])) out = w;
+        }
+        sw[k] = out;
+    }
+}
+
+// ---- contraction to clusters: mem[moff[c] .. moff[c + 1]) = the members of cluster c, of[i] = cluster of node i ----------------
+__global__ __launch_bounds__(AGG_TPB) void k_agg_count(int32_t ncl, const int64_t* __restrict__ moff, const int32_t* __restrict__ mem,
+                                                       const int32_t* __restrict__ of, const int32_t* __restrict__ rowptr,
+                                                       const int32_t* __restrict__ colind, const float* __restrict__ sw,
+                                                       int32_t* __restrict__ cnt) {
+    const int32_t c = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (c >= ncl) return;
+    int32_t r = 0;
+    for (int64_t q = moff[c]; q < moff[c + 1]; ++q) {
+        const int32_t i = mem[q];
+        for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
+            if (sw[k] > 0.0f && of[colind[k]] != c) ++r;
+    }
+    cnt[c] = r;
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_fill(int32_t ncl, const int64_t* __restrict__ moff, const int32_t* __restrict__ mem,
+                                                      const int32_t* __restrict__ of, const int32_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ colind, const float* __restrict__ sw,
+                                                      const int64_t* __restrict__ eoff, int32_t* __restrict__ nbr,
+                                                      double* __restrict__ wgt, int32_t* __restrict__ ecnt) {
+    const int32_t c = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (c >= ncl) return;
+    const int64_t e0 = eoff[c];
+    int32_t m = 0;
+    for (int64_t q = moff[c]; q < moff[c + 1]; ++q) {
+        const int32_t i = mem[q];
+        for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+            const float w = sw[k];
+            const int32_t d = w > 0.0f ? of[colind[k]] : c;
+            if (d == c) continue;
+            // stable insertion by d: the entries of one d keep member / slot order
+            int32_t p = m;
+            while (p > 0 && nbr[e0 + p - 1] > d) {
+                nbr[e0 + p] = nbr[e0 + p - 1];
+                wgt[e0 + p] = wgt[e0 + p - 1];
+                --p;
+            }
+            nbr[e0 + p] = d;
+            wgt[e0 + p] = (double)w;
+            ++m;
+        }
+    }
+    int32_t u = 0;
+    for (int32_t p = 0; p < m; ++p) {
+        const int32_t d = nbr[e0 + p];
+        const double w = wgt[e0 + p];
+        if (u > 0 && nbr[e0 + u - 1] == d) {
+            wgt[e0 + u - 1] += w;
+        } else {
+            nbr[e0 + u] = d;
+            wgt[e0 + u] = w;
+            ++u;
+        }
+    }
+    ecnt[c] = u;
+}
+
+// ---- pairwise rounds ---------------------------------------------------------------------------------------------------------------
+// A cluster's best eligible partner changes only when that partner is matched: eligibility only shrinks and the order is fixed.
+// So a step recomputes `best` for the DIRTY clusters alone -- every cluster in a round's first step, then the unmatched clusters
+// whose best was matched in the step before -- and every new mutual pair has a dirty member.  A dirty cluster with an eligible
+// edge therefore means a match in the same step, and a step without dirty clusters with eligible edges ends the round.
+// ctr[0] = dirty clusters with an eligible edge, ctr[1] = clusters matched in this step (listed in `matched`), ctr[2] = the next
+// step's dirty clusters (listed in `next`; the order of a list does not matter, its members' work is independent)
+__global__ __launch_bounds__(AGG_TPB) void k_agg_best(int32_t nlist, const int32_t* __restrict__ list, int32_t mark, int max_agg,
+                                                      const int64_t* __restrict__ eoff, const int32_t* __restrict__ ecnt,
+                                                      const int32_t* __restrict__ nbr, const double* __restrict__ wgt,
+                                                      const int32_t* __restrict__ size, const int32_t* __restrict__ partner,
+                                                      int32_t* __restrict__ best, int32_t* __restrict__ dirty, int32_t* __restrict__ ctr) {
+    const int32_t t = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (t >= nlist) return;
+    const int32_t c = list[t];
+    const int32_t sc = size[c];
+    const int64_t e0 = eoff[c];
+    int32_t b = -1;
+    double bw = 0.0;
+    for (int32_t p = 0; p < ecnt[c]; ++p) {
+        const int32_t d = nbr[e0 + p];
+        if (partner[d] >= 0 || sc + size[d] > max_agg) continue;
+        const double w = wgt[e0 + p];
+        if (b < 0 || agg_before(w, d, bw, b)) { b = d; bw = w; }
+    }
+    best[c] = b;
+    dirty[c] = mark;
+    if (b >= 0) atomicAdd(&ctr[0], 1);
+}
+
+// a mutual pair (c, d) is taken by c when d is not dirty (its best is older and already c) or when c is the smaller of the two
+__global__ __launch_bounds__(AGG_TPB) void k_agg_match(int32_t nlist, const int32_t* __restrict__ list, int32_t mark,
+                                                       const int32_t* __restrict__ best, const int32_t* __restrict__ dirty,
+                                                       int32_t* __restrict__ partner, int32_t* __restrict__ matched, int32_t* __restrict__ ctr) {
+    const int32_t t = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (t >= nlist) return;
+    const int32_t c = list[t];
+    const int32_t d = best[c];
+    if (d >= 0 && best[d] == c && (dirty[d] != mark || c < d)) {
+        partner[c] = d;
+        partner[d] = c;
+        const int32_t q = atomicAdd(&ctr[1], 2);
+        matched[q] = c;
+        matched[q + 1] = d;
+    }
+}
+
+// the next step's dirty clusters: unmatched neighbours of a newly matched cluster whose best it was
+__global__ __launch_bounds__(AGG_TPB) void k_agg_dirty(int32_t nmax, const int32_t* __restrict__ matched, const int64_t* __restrict__ eoff,
+                                                       const int32_t* __restrict__ ecnt, const int32_t* __restrict__ nbr,
+                                                       const int32_t* __restrict__ best, const int32_t* __restrict__ partner,
+                                                       int32_t* __restrict__ next, int32_t* __restrict__ ctr) {
+    const int32_t t = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (t >= nmax || t >= ctr[1]) return;
+    const int32_t m = matched[t];
+    const int64_t e0 = eoff[m];
+    for (int32_t p = 0; p < ecnt[m]; ++p) {
+        const int32_t x = nbr[e0 + p];
+        if (partner[x] < 0 && best[x] == m) next[atomicAdd(&ctr[2], 1)] = x;
+    }
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_seq(int32_t n, int32_t* __restrict__ list) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i < n) list[i] = i;
+}
+
+// leader flags: unmatched, or the smaller of its pair
+__global__ __launch_bounds__(AGG_TPB) void k_agg_lead(int32_t ncl, const int32_t* __restrict__ partner, int32_t* __restrict__ lead) {
+    const int32_t c = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (c >= ncl) return;
+    const int32_t p = partner[c];
+    lead[c] = (p < 0 || c < p) ? 1 : 0;
+}
+
+// new id and size of every leader's merged cluster
+__global__ __launch_bounds__(AGG_TPB) void k_agg_newid(int32_t ncl, const int32_t* __restrict__ partner, const int32_t* __restrict__ lead,
+                                                       const int64_t* __restrict__ scan, const int32_t* __restrict__ size,
+                                                       int32_t* __restrict__ newid, int32_t* __restrict__ nsize) {
+    const int32_t c = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (c >= ncl) return;
+    const int32_t p = partner[c];
+    newid[c] = (int32_t)(lead[c] ? scan[c] : scan[p]);
+    if (lead[c]) nsize[scan[c]] = size[c] + (p >= 0 ? size[p] : 0);
+}
+
+// member lists of the new clusters (the leader's members, then its partner's) at nmoff[new id]
+__global__ __launch_bounds__(AGG_TPB) void k_agg_merge(int32_t ncl, const int32_t* __restrict__ partner, const int32_t* __restrict__ lead,
+                                                       const int32_t* __restrict__ newid, const int64_t* __restrict__ moff,
+                                                       const int32_t* __restrict__ mem, const int64_t* __restrict__ nmoff,
+                                                       int32_t* __restrict__ nmem) {
+    const int32_t c = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (c >= ncl || !lead[c]) return;
+    int64_t o = nmoff[newid[c]];
+    for (int64_t q = moff[c]; q < moff[c + 1]; ++q) nmem[o++] = mem[q];
+    const int32_t p = partner[c];
+    if (p >= 0)
+        for (int64_t q = moff[p]; q < moff[p + 1]; ++q) nmem[o++] = mem[q];
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_relabel(int32_t n_act, const int32_t* __restrict__ newid, int32_t* __restrict__ of) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i < n_act) of[i] = newid[of[i]];
+}
+
+// ---- leftover singles --------------------------------------------------------------------------------------------------------------
+// (s, c) is pending while s is a single without target and c has >= 2 members and room (max_agg - size - fill > 0)
+__global__ __launch_bounds__(AGG_TPB) void k_agg_lbest(int32_t ncl, int max_agg, const int64_t* __restrict__ eoff, const int32_t* __restrict__ ecnt,
+                                                       const int32_t* __restrict__ nbr, const double* __restrict__ wgt,
+                                                       const int32_t* __restrict__ size, const int32_t* __restrict__ fill,
+                                                       const int32_t* __restrict__ target, int32_t* __restrict__ best,
+                                                       double* __restrict__ bestw, int32_t* __restrict__ ctr) {
+    const int32_t x = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (x >= ncl) return;
+    int32_t b = -1;
+    double bw = 0.0;
+    if (size[x] == 1 && target[x] < 0) {
+        const int64_t e0 = eoff[x];
+        for (int32_t p = 0; p < ecnt[x]; ++p) {
+            const int32_t d = nbr[e0 + p];
+            if (size[d] < 2 || max_agg - size[d] - fill[d] <= 0) continue;
+            const double w = wgt[e0 + p];
+            if (b < 0 || agg_before(w, d, bw, b)) { b = d; bw = w; }
+        }
+    }
+    best[x] = b;
+    bestw[x] = bw;
+    if (b >= 0) atomicAdd(&ctr[0], 1);
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_laccept(int32_t ncl, int max_agg, const int64_t* __restrict__ eoff, const int32_t* __restrict__ ecnt,
+                                                         const int32_t* __restrict__ nbr, const double* __restrict__ wgt,
+                                                         const int32_t* __restrict__ size, const int32_t* __restrict__ fill,
+                                                         const int32_t* __restrict__ target, const int32_t* __restrict__ best,
+                                                         const double* __restrict__ bestw, int32_t* __restrict__ choose,
+                                                         int32_t* __restrict__ ctr) {
+    const int32_t x = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (x >= ncl) return;
+    const int32_t c = best[x];
+    int32_t out = -1;
+    if (c >= 0) {
+        const double wx = bestw[x];
+        const int32_t room = max_agg - size[c] - fill[c];
+        const int64_t e0 = eoff[c];
+        int32_t heavier = 0;
+        for (int32_t p = 0; p < ecnt[c] && heavier < room; ++p) {
+            const int32_t s = nbr[e0 + p];
+            if (size[s] != 1 || target[s] >= 0) continue;
+            if (agg_before(wgt[e0 + p], s, wx, x)) ++heavier;
+        }
+        if (heavier < room) {
+            out = c;
+            atomicAdd(&ctr[1], 1);
+        }
+    }
+    choose[x] = out;
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_lcommit(int32_t ncl, const int32_t* __restrict__ choose, int32_t* __restrict__ target,
+                                                         int32_t* __restrict__ fill) {
+    const int32_t x = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (x >= ncl) return;
+    const int32_t c = choose[x];
+    if (c >= 0) {
+        target[x] = c;
+        atomicAdd(&fill[c], 1);
+    }
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_keep(int32_t ncl, const int32_t* __restrict__ target, int32_t* __restrict__ keep) {
+    const int32_t x = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (x < ncl) keep[x] = target[x] < 0 ? 1 : 0;
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_final(int32_t n, int32_t n_act, const int32_t* __restrict__ of, const int32_t* __restrict__ target,
+                                                       const int64_t* __restrict__ scan, int32_t* __restrict__ agg) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i >= n) return;
+    int32_t a = -1;
+    if (i < n_act) {
+        const int32_t c = of[i];
+        const int32_t t = target[c];
+        a = (int32_t)scan[t >= 0 ? t : c];
+    }
+    agg[i] = a;
+}
+
+__global__ __launch_bounds__(AGG_TPB) void k_agg_iota(int32_t n, int32_t* __restrict__ a, int32_t* __restrict__ b, int32_t* __restrict__ one) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i >= n) return;
+    a[i] = i;
+    b[i] = i;
+    one[i] = 1;
+}
+
+// device scratch, freed on every way out
+struct AggScratch {
+    std::vector<void*> ptrs;
+    template <class T>
+    int alloc(T** p, size_t count) {
+        SNS_TRY(dev_alloc(p, count));
+        ptrs.push_back((void*)*p);
+        return SNS_OK;
+    }
+    ~AggScratch() {
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+};
+
+struct Scanner {
+    sns_ctx* h;
+    int64_t* bsum;
+    // out[0..n] <- exclusive scan of in[0..n), out[n] = total
+    int run(const int32_t* in, int32_t n, int64_t* out) {
+        const int32_t nb = (int32_t)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
+        if (nb > 0) hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)nb), dim3(AGG_TPB), 0, h->stream, n, in, bsum);
+        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(AGG_TPB), 0, h->stream, nb, bsum, n, out);
+        if (nb > 0) hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(AGG_TPB), 0, h->stream, n, in, bsum, out);
+        HIP_TRY(hipGetLastError());
+        return SNS_OK;
+    }
+};
+
+template <class T>
+int read_back(sns_ctx* h, const T* src, T* dst, size_t count) {
+    HIP_TRY(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return SNS_OK;
+}
+
+}  // namespace
+
+// agg[n] (host) <- the level-0 aggregation by operator strength of the owned nodes, built on the device; nc = aggregates.  The
+// same map as aggregate_strength(level-0 pattern, n_owned, max_agg, strength).  Collective on a partitioned handle (the strength's
+// halo exchange of the scales).
+int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc) {
+    const Level& L = h->levels[0];
+    const int32_t n = L.n, n_act = h->n_owned;
+    agg.assign((size_t)n, -1);
+    nc = 0;
+    AggScratch S;
+    float* sw = nullptr;                                            // strong-slot weights, one per block slot (0: not strong)
+    {
+        // the strength (collective) and the strong graph; the strength is freed again before the matching
+        float *s = nullptr, *smax = nullptr;
+        double* scale = nullptr;
+        int rc = dev_alloc(&s, (size_t)L.nnzb);
+        if (rc == SNS_OK) rc = dev_alloc(&scale, 4 * (size_t)n);
+        if (rc == SNS_OK) rc = compute_strength(h, s, scale);
+        if (rc == SNS_OK && n_act > 0) rc = dev_alloc(&smax, (size_t)n_act);
+        if (rc == SNS_OK && n_act > 0) rc = S.alloc(&sw, (size_t)L.nnzb);
+        bool failed = false;
+        if (rc == SNS_OK && n_act > 0) {
+            hipLaunchKernelGGL(k_agg_smax, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, h->stream, n_act, L.rowptr, L.colind, s, smax);
+            hipLaunchKernelGGL(k_agg_strong, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, h->stream, n_act, L.rowptr, L.colind, s, smax, sw);
+            failed = hipGetLastError() != hipSuccess;
+        }
+        if (rc == SNS_OK && !failed) failed = hipStreamSynchronize(h->stream) != hipSuccess;
+        if (failed) {
+            set_error("amg_aggregation = 2: strength or strong-graph kernel failed");
+            rc = SNS_E_HIP;
+        }
+        if (s) (void)hipFree(s);
+        if (scale) (void)hipFree(scale);
+        if (smax) (void)hipFree(smax);
+        if (rc != SNS_OK) return rc;
+        if (n_act == 0) return SNS_OK;
+    }
+    const size_t na = (size_t)n_act;
+    int32_t *of, *mem, *nmem, *size, *nsize, *partner, *best, *flag, *newid, *cnt, *ecnt, *nbr, *ctr, *fill, *target, *choose, *list, *next, *dirty, *matched;
+    int64_t *moff, *nmoff, *eoff, *scan, *bsum;
+    double *wgt, *bestw;
+    SNS_TRY(S.alloc(&of, na));
+    SNS_TRY(S.alloc(&mem, na));
+    SNS_TRY(S.alloc(&nmem, na));
+    SNS_TRY(S.alloc(&size, na));
+    SNS_TRY(S.alloc(&nsize, na));
+    SNS_TRY(S.alloc(&partner, na));
+    SNS_TRY(S.alloc(&best, na));
+    SNS_TRY(S.alloc(&flag, na));
+    SNS_TRY(S.alloc(&newid, na));
+    SNS_TRY(S.alloc(&cnt, na));
+    SNS_TRY(S.alloc(&ecnt, na));
+    SNS_TRY(S.alloc(&fill, na));
+    SNS_TRY(S.alloc(&target, na));
+    SNS_TRY(S.alloc(&choose, na));
+    SNS_TRY(S.alloc(&bestw, na));
+    SNS_TRY(S.alloc(&list, na));
+    SNS_TRY(S.alloc(&next, na));
+    SNS_TRY(S.alloc(&dirty, na));
+    SNS_TRY(S.alloc(&matched, na));
+    SNS_TRY(S.alloc(&ctr, 3));
+    SNS_TRY(S.alloc(&moff, na + 1));
+    SNS_TRY(S.alloc(&nmoff, na + 1));
+    SNS_TRY(S.alloc(&eoff, na + 1));
+    SNS_TRY(S.alloc(&scan, na + 1));
+    SNS_TRY(S.alloc(&bsum, na / SCAN_BLOCK + 1));
+    Scanner scanner{h, bsum};
+    const hipStream_t st = h->stream;
+    // every node its own cluster: of = mem = identity, size 1, moff = 0, 1, 2, ...
+    hipLaunchKernelGGL(k_agg_iota, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, of, mem, size);
+    SNS_TRY(scanner.run(size, n_act, moff));
+    // the strong directed slots bound every contraction's entries
+    int64_t cap = 0;
+    {
+        hipLaunchKernelGGL(k_agg_count, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, moff, mem, of, L.rowptr, L.colind, sw, cnt);
+        SNS_TRY(scanner.run(cnt, n_act, eoff));
+        SNS_TRY(read_back(h, eoff + n_act, &cap, 1));
+    }
+    SNS_TRY(S.alloc(&nbr, (size_t)std::max<int64_t>(cap, 1)));
+    SNS_TRY(S.alloc(&wgt, (size_t)std::max<int64_t>(cap, 1)));
+    int32_t ncl = n_act;
+    // contraction of the strong graph to the current clusters: (nbr, wgt)[eoff[c] .. + ecnt[c]) per cluster
+    auto contract = [&]() -> int {
+        hipLaunchKernelGGL(k_agg_count, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, moff, mem, of, L.rowptr, L.colind, sw, cnt);
+        SNS_TRY(scanner.run(cnt, ncl, eoff));
+        int64_t tot = 0;
+        SNS_TRY(read_back(h, eoff + ncl, &tot, 1));
+        if (tot > cap) { set_error("amg_aggregation = 2: contraction exceeds the strong edges"); return SNS_E_HIP; }
+        hipLaunchKernelGGL(k_agg_fill, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, moff, mem, of, L.rowptr, L.colind, sw, eoff,
+                           nbr, wgt, ecnt);
+        HIP_TRY(hipGetLastError());
+        return SNS_OK;
+    };
+    for (int round = 1; (1 << round) <= max_agg; ++round) {
+        SNS_TRY(contract());
+        HIP_TRY(hipMemsetAsync(partner, 0xff, (size_t)ncl * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(dirty, 0, (size_t)ncl * sizeof(int32_t), st));
+        hipLaunchKernelGGL(k_agg_seq, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, list);
+        // locally-dominant matching steps; each productive step matches at least one pair
+        int32_t nlist = ncl;
+        for (int32_t step = 0;; ++step) {
+            if (step > ncl / 2 + 1) { set_error("amg_aggregation = 2: matching did not finish"); return SNS_E_HIP; }
+            const int32_t mark = step + 1, nmax = (int32_t)std::min<int64_t>(2 * (int64_t)nlist, ncl);
+            HIP_TRY(hipMemsetAsync(ctr, 0, 3 * sizeof(int32_t), st));
+            hipLaunchKernelGGL(k_agg_best, dim3(agg_blocks(nlist)), dim3(AGG_TPB), 0, st, nlist, list, mark, max_agg, eoff, ecnt, nbr, wgt,
+                               size, partner, best, dirty, ctr);
+            hipLaunchKernelGGL(k_agg_match, dim3(agg_blocks(nlist)), dim3(AGG_TPB), 0, st, nlist, list, mark, best, dirty, partner, matched, ctr);
+            hipLaunchKernelGGL(k_agg_dirty, dim3(agg_blocks(nmax)), dim3(AGG_TPB), 0, st, nmax, matched, eoff, ecnt, nbr, best, partner, next, ctr);
+            HIP_TRY(hipGetLastError());
+            int32_t c3[3] = {0, 0, 0};
+            SNS_TRY(read_back(h, ctr, c3, 3));
+            if (c3[0] == 0) break;                              // no eligible edge left anywhere
+            if (c3[1] == 0) {
+                set_error("amg_aggregation = 2: a matching step matched nothing with " + std::to_string(c3[0]) + " clusters pending");
+                return SNS_E_HIP;
+            }
+            std::swap(list, next);
+            nlist = c3[2];
+            if (nlist == 0) break;                              // every best is current and no pair is mutual: none left
+        }
+        // renumber in the order of the clusters' smallest member
+        hipLaunchKernelGGL(k_agg_lead, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, partner, flag);
+        SNS_TRY(scanner.run(flag, ncl, scan));
+        int64_t nnew = 0;
+        SNS_TRY(read_back(h, scan + ncl, &nnew, 1));
+        hipLaunchKernelGGL(k_agg_newid, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, partner, flag, scan, size, newid, nsize);
+        SNS_TRY(scanner.run(nsize, (int32_t)nnew, nmoff));
+        hipLaunchKernelGGL(k_agg_merge, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, partner, flag, newid, moff, mem, nmoff, nmem);
+        hipLaunchKernelGGL(k_agg_relabel, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, newid, of);
+        HIP_TRY(hipGetLastError());
+        std::swap(mem, nmem);
+        std::swap(moff, nmoff);
+        std::swap(size, nsize);
+        ncl = (int32_t)nnew;
+    }
+    // single nodes left over join their strongest adjacent cluster of at least two members that still has room
+    SNS_TRY(contract());
+    HIP_TRY(hipMemsetAsync(target, 0xff, (size_t)ncl * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(fill, 0, (size_t)ncl * sizeof(int32_t), st));
+    for (int32_t step = 0;; ++step) {
+        if (step > ncl + 1) { set_error("amg_aggregation = 2: leftover assignment did not finish"); return SNS_E_HIP; }
+        HIP_TRY(hipMemsetAsync(ctr, 0, 2 * sizeof(int32_t), st));
+        hipLaunchKernelGGL(k_agg_lbest, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, max_agg, eoff, ecnt, nbr, wgt, size, fill, target,
+                           best, bestw, ctr);
+        hipLaunchKernelGGL(k_agg_laccept, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, max_agg, eoff, ecnt, nbr, wgt, size, fill, target,
+                           best, bestw, choose, ctr);
+        hipLaunchKernelGGL(k_agg_lcommit, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, choose, target, fill);
+        HIP_TRY(hipGetLastError());
+        int32_t c2[2] = {0, 0};
+        SNS_TRY(read_back(h, ctr, c2, 2));
+        if (c2[0] == 0) break;
+        if (c2[1] == 0) {
+            set_error("amg_aggregation = 2: a leftover step accepted nothing with " + std::to_string(c2[0]) + " singles pending");
+            return SNS_E_HIP;
+        }
+    }
+    // the clusters without a target numbered in order; a targeted single takes its target's id
+    hipLaunchKernelGGL(k_agg_keep, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, target, flag);
+    SNS_TRY(scanner.run(flag, ncl, scan));
+    int32_t* agg_dev = newid;                                       // (n_act entries: reused only when n == n_act)
+    if (n > n_act) SNS_TRY(S.alloc(&agg_dev, (size_t)n));
+    hipLaunchKernelGGL(k_agg_final, dim3(agg_blocks(n)), dim3(AGG_TPB), 0, st, n, n_act, of, target, scan, agg_dev);
+    HIP_TRY(hipGetLastError());
+    int64_t total = 0;
+    SNS_TRY(read_back(h, scan + ncl, &total, 1));
+    SNS_TRY(read_back(h, agg_dev, agg.data(), (size_t)n));
+    nc = (int32_t)total;
+    return SNS_OK;
+}
+
+}  // namespace sns

@@ -216,6 +216,8 @@ int op_residual(sns_ctx* h, double* x, const double* b, double* r);
 int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm);
 // csrc/sns_strength.hip: the strength of the fine-level couplings (amg_aggregation = 1, SNS_EXPORT_STRENGTH)
 int compute_strength(sns_ctx* h, float* out, double* scale);
+// csrc/sns_aggregate.hip: aggregate_strength's map of the owned nodes, built on the device (amg_aggregation = 2)
+int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc);
 int norm2(sns_ctx* h, const double* x, double* out);
 int dot(sns_ctx* h, const double* x, const double* y, double* out);
 }  // namespace sns

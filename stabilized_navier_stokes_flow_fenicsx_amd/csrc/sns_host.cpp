@@ -555,7 +555,7 @@ void build_ap_pattern(const HostPattern& F, int32_t n_rows, const std::vector<in
 // the sum of their members' strong couplings.  Single nodes left over join their strongest adjacent cluster with room.  A sliver's
 // four nodes are coupled far more strongly to each other than to anything else, so they end up in one aggregate -- one block of
 // the aggregate-block smoother -- instead of setting the damping of the whole level.  A node without a strong edge (all its dofs
-// Dirichlet) is an aggregate of its own.
+// Dirichlet) is an aggregate of its own.  csrc/sns_aggregate.hip builds the identical map on the device (amg_aggregation = 2).
 void aggregate_strength(const HostPattern& F, int32_t n_active, int max_agg, const float* strength, std::vector<int32_t>& agg,
                         int32_t& nc) {
     struct Edge { int32_t a, b; double w; };

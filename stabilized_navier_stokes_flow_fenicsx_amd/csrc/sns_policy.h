@@ -39,21 +39,21 @@ constexpr int DISTRIBUTED_DENSE_MAX_DOFS = 640;
 // (10 M tets: level 2, 36 k rows; level 1 has 218 k rows = 46 us per sweep)
 constexpr int GRAPH_MAX_ROWS = 150000;
 
-// ---- operator-strength aggregation of the fine level (amg_aggregation = 1) -------------------------------------------------------
+// ---- operator-strength aggregation of the fine level (amg_aggregation = 1, 2) -----------------------------------------------------
 // s_ij = || D_i^-1/2 A_ij D_j^-1/2 ||_F of the first assembled operator (k_strength), symmetrised s_ij <- max(s_ij, s_ji); the
 // edge (i, j) is strong when s_ij >= STRENGTH_THETA x the strongest coupling of i or of j.  The aggregates come from pairwise
-// heavy-edge matching of the strong graph (sns_host.cpp: aggregate_strength).
+// heavy-edge matching of the strong graph (1: sns_host.cpp aggregate_strength; 2: the same map on the device, sns_aggregate.hip).
 constexpr double STRENGTH_THETA = 0.25;
 // the aggregates must fit the 32 x 32 smoother blocks of csrc/sns_block.hip
 constexpr int STRENGTH_MAX_AGG = 8;
 
 // ---- smoother kind ---------------------------------------------------------------------------------------------------------------
 // aggregate blocks on the FINE level: always with amg_block_smooth = 2 and with the aggregation by operator strength
-// (amg_aggregation = 1: its aggregates are made to hold a sliver's nodes in one block -- with nodal blocks they gain nothing,
+// (amg_aggregation = 1 or 2: its aggregates are made to hold a sliver's nodes in one block -- with nodal blocks they gain nothing,
 // scripts/proto_strength_aggregation.py); with 1 on a partitioned handle whose share of the fine level is at most
 // amg_block_fine_rows rows per rank -- the latency-bound strong split
 inline bool fine_blocks(const sns_options& o, int nranks, int64_t rows_global_fine) {
-    if (o.amg_block_smooth >= 2 || o.amg_aggregation == 1) return true;
+    if (o.amg_block_smooth >= 2 || o.amg_aggregation >= 1) return true;
     if (o.amg_block_smooth < 1 || o.amg_block_fine_rows <= 0) return false;
     if (nranks < 2 || rows_global_fine <= 0) return false;
     return rows_global_fine <= (int64_t)o.amg_block_fine_rows * nranks;

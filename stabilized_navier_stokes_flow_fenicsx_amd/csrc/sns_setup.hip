@@ -394,11 +394,16 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
 }
 
 
-// Level 0 aggregated by operator strength (amg_aggregation = 1): the strength of the assembled fine operator (csrc/sns_strength.hip),
-// copied to the host, and sns_host.cpp's aggregate_strength over the owned nodes.  The fp32 strength is freed again.
+// Level 0 aggregated by operator strength: the strength of the assembled fine operator (csrc/sns_strength.hip) and aggregate_strength
+// over the owned nodes -- amg_aggregation = 1: the strength copied to the host and sns_host.cpp's matcher; 2: the same map built on
+// the device (csrc/sns_aggregate.hip), only the map copied.  The fp32 strength and the device scratch are freed again.
 static int aggregate_fine_by_strength(sns_ctx* h, const HostPattern& fine, std::vector<int32_t>& agg, int32_t& nc) {
     const Level& L = h->levels[0];
-    if (!h->has_matrix) { set_error("amg_aggregation = 1: the hierarchy is built from the assembled operator; assemble first"); return SNS_E_STATE; }
+    if (!h->has_matrix) {
+        set_error("amg_aggregation = " + std::to_string(h->opt.amg_aggregation) + ": the hierarchy is built from the assembled operator; assemble first");
+        return SNS_E_STATE;
+    }
+    if (h->opt.amg_aggregation == 2) return aggregate_strength_device(h, std::min(h->opt.amg_agg_size, policy::STRENGTH_MAX_AGG), agg, nc);
     float* s_dev = nullptr;
     double* scale = nullptr;
     SNS_TRY(dev_alloc(&s_dev, (size_t)L.nnzb));
@@ -461,7 +466,7 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
         if (!dist && l >= 1 && n_owned <= policy::coarsest_rows(o)) break;       // serial: this level is solved directly
         std::vector<int32_t> agg;
         int32_t nc_owned = 0;
-        if (l == 0 && o.amg_aggregation == 1) {
+        if (l == 0 && o.amg_aggregation >= 1) {
             SNS_TRY(aggregate_fine_by_strength(h, cur, agg, nc_owned));
         } else {
             aggregate_nodes(cur, n_owned, std::min(255, std::max(2, o.amg_agg_size)), agg, nc_owned,

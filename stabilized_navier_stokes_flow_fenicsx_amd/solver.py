@@ -54,6 +54,10 @@ class FlowProblem:
     G-metric forms) or a ``mesh2d.TriMesh`` (2-D UGN forms of the lid-driven / DFG-2D scripts; "stokes" and "ns"
     then name the 2-D forms, see sns_create_2d in include/sns.h).
 
+    Keyword options are fields of ``sns_options`` (include/sns.h).  For sliver-rich meshes ``amg_aggregation=1`` aggregates the
+    fine level by operator strength with the host matcher; ``amg_aggregation=2`` builds the identical aggregates on the GPU,
+    which is what large meshes want (the host matcher alone takes about 1 s at 10 M tets).
+
     Replaces what ``functionspace`` / ``dirichletbc`` / ``create_matrix`` /
     ``fem.form`` build for the reference (:127-147, :45-46, :271-272).
     """
