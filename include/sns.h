@@ -227,7 +227,12 @@ typedef struct {
                                device (parallel locally-dominant matching, csrc/sns_aggregate.hip); only the map is copied to the host
                                (10 M tets: 76 ms instead of 0.95 s for 1's host matcher).  Fixed when the hierarchy is built; 1
                                and 2 need an assembled operator then (SNS_E_STATE otherwise), amg_agg_size <= 8, and a 3-D handle
-                               (SNS_E_ARG) */
+                               (SNS_E_ARG).  3 (hybrid): 0's map, with only the aggregates that cut a dominant coupling (a row
+                               whose strongest outside coupling exceeds 4 x max(its strongest inside coupling, its mean coupling))
+                               dissolved and their nodes re-matched as 2 matches, on the device; a handle with more than 1 % of its
+                               rows marked re-matches everything (2's map).  The fine-level aggregate blocks come only when some
+                               rank re-matched; with nothing marked the run is 0's bit for bit, at the cost of the strength kernel
+                               and one mark pass.  Same rules as 1 and 2 */
 } sns_options;
 
 SNS_API void sns_default_options(sns_options* opt);

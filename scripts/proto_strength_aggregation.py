@@ -7,6 +7,14 @@ oracle.proto_amg).  Two-stream channel, Re 50, on a Delaunay mesh of the jittere
 BiCGStab iterations to rtol 1e-8 for the Stokes operator and for the Navier-Stokes Jacobian at the Stokes solution.
 
     python scripts/proto_strength_aggregation.py 24 cubic [seed]
+
+Variant H (amg_aggregation = 3, the hybrid): the geometric map, with only the geometric aggregates that cut a dominant coupling
+dissolved and re-matched by strength (hybrid_map of tests/test_host_hybrid_aggregation.py); aggregate blocks on the fine level only when something was re-matched.
+`hybrid` picks KAPPA -- the smallest candidate that marks no node on the structured and the body-centred Delaunay channels -- and
+reports A / D / H (and H without the PHI fallback) on the half-jittered channel and the sliver meshes
+(profiles/proto_hybrid_aggregation.txt); names after `hybrid` select the meshes:
+
+    python scripts/proto_strength_aggregation.py hybrid [half n=24 ...]
 """
 import os
 import sys
@@ -17,9 +25,12 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 
 from oracle import cport, proto_amg as PA  # noqa: E402
 from stabilized_navier_stokes_flow_fenicsx_amd import _lib, bcs as B, mesh as M  # noqa: E402
+# the hybrid rule (KAPPA, PHI) and the half-jittered channel: one numpy statement, shared with the tests
+from test_host_hybrid_aggregation import half_jittered_channel, hybrid_map  # noqa: E402
 
 
 def strength(rowptr, colind, vals):
@@ -110,7 +121,68 @@ def sliver_together(m, agg, frac=0.01):
     return float(np.mean((a == a[:, :1]).all(axis=1)))
 
 
+KAPPAS = (1.5, 2.0, 3.0, 4.0, 8.0)
+
+
+def _setup(m):
+    """(free, rp, ci, Stokes BSR values, scipy Stokes, -F, strength) of the two-stream channel at Re 50."""
+    mask, g = B.channel_bcs(m, *B.two_stream_profiles(0.5)).flatten()
+    rp, ci = cport.pattern(m.num_nodes, m.tets)
+    vals, F = cport.assemble("stokes", m.points, m.tets, None, 50.0, mask, g, rp, ci)
+    return mask, g, rp, ci, vals, cport.to_scipy(m.num_nodes, rp, ci, vals), -F, strength(rp, ci, vals)
+
+
+def hybrid():
+    """KAPPA from the good meshes, then A / D / H on the sliver meshes."""
+    good = [("structured 96x24x24", lambda: M.channel_mesh((96, 24, 24))), ("structured 140x35x35", lambda: M.channel_mesh((140, 35, 35))),
+            ("delaunay bcc n=28 seed 0", lambda: M.delaunay_channel_mesh(28, seed=0)),
+            ("delaunay bcc n=28 seed 1", lambda: M.delaunay_channel_mesh(28, seed=1))]
+    counts = {}
+    for name, make in good:
+        m = make()
+        _, _, rp, ci, _, _, _, s = _setup(m)
+        g, _, _ = _lib.host_aggregate(rp, ci, None, 8, m.points)
+        row = []
+        for kappa in KAPPAS:
+            _, _, marked, F = hybrid_map(rp, ci, s, g, m.num_nodes, 8, kappa, phi=1.0)
+            counts.setdefault(kappa, 0)
+            counts[kappa] += int(marked.sum())
+            row.append(f"kappa {kappa:g}: marked {int(marked.sum())} |F| {int(F.sum())}")
+        print(f"{name:28s} {m.num_tets:8d} tets {m.num_nodes:7d} nodes | " + " | ".join(row), flush=True)
+    kappa = next(k for k in KAPPAS if counts[k] == 0)
+    print(f"KAPPA = {kappa:g} (smallest candidate marking no node on the four good meshes)", flush=True)
+    bad = [(f"delaunay cubic n={n} seed {seed}", lambda n=n, seed=seed: M.delaunay_channel_mesh(n, lattice="cubic", seed=seed))
+           for n, seed in ((24, 0), (24, 1), (35, 0), (35, 1))]
+    bad.insert(0, ("half-jittered channel 48x12x12", lambda: half_jittered_channel()[0]))
+    if len(sys.argv) > 2:
+        bad = [b for b in bad if any(k in b[0] for k in sys.argv[2:])]
+    for label, make in bad:
+        m = make()
+        mask, gv, rp, ci, vals, As, bs, s = _setup(m)
+        free = mask == 0
+        g, ng, _ = _lib.host_aggregate(rp, ci, None, 8, m.points)
+        agg_s, nc_s = _lib.host_aggregate_strength(rp, ci, s, max_agg=8)
+        agg_h, nc_h, marked, F = hybrid_map(rp, ci, s, g, m.num_nodes, 8, kappa)
+        agg_p, nc_p, _, Fp = hybrid_map(rp, ci, s, g, m.num_nodes, 8, kappa, phi=1.0)
+        print(f"{label}: {m.num_tets} tets {m.num_nodes} nodes; marked {marked.mean():.4f} "
+              f"({int(marked.sum())}), |F| {int(F.sum())} ({F.mean():.3f}); aggregates geometric {ng} strength {nc_s} hybrid {nc_h}", flush=True)
+        xs, _, _ = solve(As, bs, hierarchy(As, free, g, ng, False))
+        vj, Fj = cport.assemble("ns", m.points, m.tets, xs, 50.0, mask, gv, rp, ci)
+        Aj = cport.to_scipy(m.num_nodes, rp, ci, vj)
+        for case, (agg, nc, blocks) in (("A geometric + nodal", (g, ng, False)), ("D strength + aggregate blocks", (agg_s, nc_s, True)),
+                                        ("H hybrid + aggregate blocks", (agg_h, nc_h, bool(F.any()))),
+                                        ("H without PHI (partial)", (agg_p, nc_p, bool(Fp.any())))):
+            out = []
+            for name, A, b in (("stokes", As, bs), ("ns", Aj, -Fj)):
+                t0 = time.time()
+                _, its, info = solve(A, b, hierarchy(A, free, agg, nc, blocks))
+                out.append(f"{name} its {its:4d}{'' if info == 0 else ' (info %d)' % info}  {time.time() - t0:.0f}s")
+            print(f"  {case:32s} " + "   ".join(out), flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "hybrid":
+        return hybrid()
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 24
     lattice = sys.argv[2] if len(sys.argv) > 2 else "cubic"
     seed = int(sys.argv[3]) if len(sys.argv) > 3 else 0

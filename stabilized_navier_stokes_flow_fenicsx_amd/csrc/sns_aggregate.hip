@@ -400,6 +400,102 @@ __global__ __launch_bounds__(AGG_TPB) void k_agg_iota(int32_t n, int32_t* __rest
     one[i] = 1;
 }
 
+// ---- the hybrid (amg_aggregation = 3): geometric aggregates re-matched where they cut a dominant coupling ----------------------
+// gsize[a] <- members of geometric aggregate a (integer atomics: the counts do not depend on the order)
+__global__ __launch_bounds__(AGG_TPB) void k_hyb_size(int32_t n_act, const int32_t* __restrict__ g, int32_t* __restrict__ gsize) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i < n_act) atomicAdd(&gsize[g[i]], 1);
+}
+
+// one lane per owned row: cut = the strongest symmetrised coupling to an owned node of another geometric aggregate, ref = the
+// strongest inside its own or the row's mean over its owned neighbours (summed in fp64 in slot order), whichever is larger -- the
+// mean alone for a singleton; cut > HYBRID_KAPPA x ref marks the row, which dissolves its aggregate (every writer stores the same 1)
+__global__ __launch_bounds__(AGG_TPB) void k_hyb_mark(int32_t n_act, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                      const float* __restrict__ s, const int32_t* __restrict__ g,
+                                                      const int32_t* __restrict__ gsize, double kappa, int32_t* __restrict__ dis,
+                                                      int32_t* __restrict__ nmark) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i >= n_act) return;
+    const int32_t gi = g[i];
+    float cut = 0.0f, kept = 0.0f;
+    double sum = 0.0;
+    int32_t cnt = 0;
+    for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+        const int32_t j = colind[k];
+        if (j == i || j >= n_act) continue;
+        const float w = agg_sym(i, k, rowptr, colind, s);
+        sum += (double)w;
+        ++cnt;
+        if (g[j] == gi) kept = kept < w ? w : kept;
+        else cut = cut < w ? w : cut;
+    }
+    const double mean = cnt > 0 ? sum / (double)cnt : 0.0;
+    const double ref = gsize[gi] == 1 ? mean : fmax((double)kept, mean);
+    if ((double)cut > kappa * ref) {
+        dis[gi] = 1;
+        atomicAdd(nmark, 1);
+    }
+}
+
+// inF[i] <- node i lies in a dissolved aggregate; keep[a] <- aggregate a is kept (all = 1: everything is dissolved)
+__global__ __launch_bounds__(AGG_TPB) void k_hyb_flags(int32_t n_act, int32_t ng, int32_t all, const int32_t* __restrict__ g,
+                                                       const int32_t* __restrict__ dis, int32_t* __restrict__ inF, int32_t* __restrict__ keep) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i < n_act) inF[i] = all ? 1 : dis[g[i]];
+    if (i < ng) keep[i] = all ? 0 : 1 - dis[i];
+}
+
+// the induced subgraph of F: its rows in increasing node order (fnode[fpos[i]] = i) and per row the slots into F
+__global__ __launch_bounds__(AGG_TPB) void k_hyb_count(int32_t n_act, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                       const int32_t* __restrict__ inF, const int64_t* __restrict__ fpos,
+                                                       int32_t* __restrict__ fnode, int32_t* __restrict__ cnt) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i >= n_act || !inF[i]) return;
+    int32_t c = 0;
+    for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+        const int32_t j = colind[k];
+        if (j < n_act && inF[j]) ++c;
+    }
+    const int64_t r = fpos[i];
+    fnode[r] = i;
+    cnt[r] = c;
+}
+
+// the subgraph's rows (the columns renumbered by fpos: increasing, so each row stays sorted) and the raw strength of its slots
+__global__ __launch_bounds__(AGG_TPB) void k_hyb_fill(int32_t nF, const int32_t* __restrict__ fnode, int32_t n_act,
+                                                      const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                      const float* __restrict__ s, const int32_t* __restrict__ inF,
+                                                      const int64_t* __restrict__ fpos, const int64_t* __restrict__ soff,
+                                                      int32_t* __restrict__ srowptr, int32_t* __restrict__ scolind, float* __restrict__ ss) {
+    const int32_t r = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (r >= nF) return;
+    const int32_t i = fnode[r];
+    int64_t p = soff[r];
+    srowptr[r] = (int32_t)p;
+    if (r == nF - 1) srowptr[nF] = (int32_t)soff[nF];
+    for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+        const int32_t j = colind[k];
+        if (j < n_act && inF[j]) {
+            scolind[p] = (int32_t)fpos[j];
+            ss[p] = s[k];
+            ++p;
+        }
+    }
+}
+
+// the final map: kept geometric aggregates first, in order of their old ids (kpos), then F's aggregates (nkept = kpos[ng] + the
+// subgraph's id); -1 for the ghosts
+__global__ __launch_bounds__(AGG_TPB) void k_hyb_merge(int32_t n, int32_t n_act, int32_t ng, const int32_t* __restrict__ g,
+                                                       const int32_t* __restrict__ inF, const int64_t* __restrict__ fpos,
+                                                       const int64_t* __restrict__ kpos, const int32_t* __restrict__ sagg,
+                                                       int32_t* __restrict__ agg) {
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * AGG_TPB + threadIdx.x);
+    if (i >= n) return;
+    int32_t a = -1;
+    if (i < n_act) a = inF[i] ? (int32_t)kpos[ng] + sagg[fpos[i]] : (int32_t)kpos[g[i]];
+    agg[i] = a;
+}
+
 // device scratch, freed on every way out
 struct AggScratch {
     std::vector<void*> ptrs;
@@ -435,43 +531,32 @@ int read_back(sns_ctx* h, const T* src, T* dst, size_t count) {
     return SNS_OK;
 }
 
-}  // namespace
+// The strong graph and the matching over a graph VIEW: rows [0, n) of (rowptr, colind) -- sorted columns, so that the transposed
+// slot is found by binary search -- of which the first n_act are aggregated; level 0 of the handle (amg_aggregation = 2) or the
+// induced subgraph of the hybrid's dissolved aggregates (3).  `who` names the option in the error messages.
+struct GraphView {
+    const int32_t* rowptr;
+    const int32_t* colind;
+    int32_t n, n_act;
+};
 
-// agg[n] (host) <- the level-0 aggregation by operator strength of the owned nodes, built on the device; nc = aggregates.  The
-// same map as aggregate_strength(level-0 pattern, n_owned, max_agg, strength).  Collective on a partitioned handle (the strength's
-// halo exchange of the scales).
-int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc) {
-    const Level& L = h->levels[0];
-    const int32_t n = L.n, n_act = h->n_owned;
-    agg.assign((size_t)n, -1);
+// sw[nnz of G] <- the strong-slot weights of G from its raw strength s (0: not strong); smax is scratch
+int strong_slots(sns_ctx* h, const GraphView& G, const float* s, float* smax, float* sw) {
+    if (G.n_act <= 0) return SNS_OK;
+    hipLaunchKernelGGL(k_agg_smax, dim3(agg_blocks(G.n_act)), dim3(AGG_TPB), 0, h->stream, G.n_act, G.rowptr, G.colind, s, smax);
+    hipLaunchKernelGGL(k_agg_strong, dim3(agg_blocks(G.n_act)), dim3(AGG_TPB), 0, h->stream, G.n_act, G.rowptr, G.colind, s, smax, sw);
+    HIP_TRY(hipGetLastError());
+    return SNS_OK;
+}
+
+// agg_dev[G.n] <- the map of aggregate_strength over G's first n_act nodes (-1 beyond), nc = aggregates; sw = strong_slots' weights
+int match_strong(sns_ctx* h, const GraphView& G, const float* sw, int max_agg, const std::string& who, AggScratch& S, int32_t* agg_dev,
+                 int32_t& nc) {
+    const int32_t n = G.n, n_act = G.n_act;
     nc = 0;
-    AggScratch S;
-    float* sw = nullptr;                                            // strong-slot weights, one per block slot (0: not strong)
-    {
-        // the strength (collective) and the strong graph; the strength is freed again before the matching
-        float *s = nullptr, *smax = nullptr;
-        double* scale = nullptr;
-        int rc = dev_alloc(&s, (size_t)L.nnzb);
-        if (rc == SNS_OK) rc = dev_alloc(&scale, 4 * (size_t)n);
-        if (rc == SNS_OK) rc = compute_strength(h, s, scale);
-        if (rc == SNS_OK && n_act > 0) rc = dev_alloc(&smax, (size_t)n_act);
-        if (rc == SNS_OK && n_act > 0) rc = S.alloc(&sw, (size_t)L.nnzb);
-        bool failed = false;
-        if (rc == SNS_OK && n_act > 0) {
-            hipLaunchKernelGGL(k_agg_smax, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, h->stream, n_act, L.rowptr, L.colind, s, smax);
-            hipLaunchKernelGGL(k_agg_strong, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, h->stream, n_act, L.rowptr, L.colind, s, smax, sw);
-            failed = hipGetLastError() != hipSuccess;
-        }
-        if (rc == SNS_OK && !failed) failed = hipStreamSynchronize(h->stream) != hipSuccess;
-        if (failed) {
-            set_error("amg_aggregation = 2: strength or strong-graph kernel failed");
-            rc = SNS_E_HIP;
-        }
-        if (s) (void)hipFree(s);
-        if (scale) (void)hipFree(scale);
-        if (smax) (void)hipFree(smax);
-        if (rc != SNS_OK) return rc;
-        if (n_act == 0) return SNS_OK;
+    if (n_act <= 0) {
+        if (n > 0) HIP_TRY(hipMemsetAsync(agg_dev, 0xff, (size_t)n * sizeof(int32_t), h->stream));
+        return SNS_OK;
     }
     const size_t na = (size_t)n_act;
     int32_t *of, *mem, *nmem, *size, *nsize, *partner, *best, *flag, *newid, *cnt, *ecnt, *nbr, *ctr, *fill, *target, *choose, *list, *next, *dirty, *matched;
@@ -510,7 +595,7 @@ int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg
     // the strong directed slots bound every contraction's entries
     int64_t cap = 0;
     {
-        hipLaunchKernelGGL(k_agg_count, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, moff, mem, of, L.rowptr, L.colind, sw, cnt);
+        hipLaunchKernelGGL(k_agg_count, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, moff, mem, of, G.rowptr, G.colind, sw, cnt);
         SNS_TRY(scanner.run(cnt, n_act, eoff));
         SNS_TRY(read_back(h, eoff + n_act, &cap, 1));
     }
@@ -519,12 +604,12 @@ int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg
     int32_t ncl = n_act;
     // contraction of the strong graph to the current clusters: (nbr, wgt)[eoff[c] .. + ecnt[c]) per cluster
     auto contract = [&]() -> int {
-        hipLaunchKernelGGL(k_agg_count, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, moff, mem, of, L.rowptr, L.colind, sw, cnt);
+        hipLaunchKernelGGL(k_agg_count, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, moff, mem, of, G.rowptr, G.colind, sw, cnt);
         SNS_TRY(scanner.run(cnt, ncl, eoff));
         int64_t tot = 0;
         SNS_TRY(read_back(h, eoff + ncl, &tot, 1));
-        if (tot > cap) { set_error("amg_aggregation = 2: contraction exceeds the strong edges"); return SNS_E_HIP; }
-        hipLaunchKernelGGL(k_agg_fill, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, moff, mem, of, L.rowptr, L.colind, sw, eoff,
+        if (tot > cap) { set_error(who + ": contraction exceeds the strong edges"); return SNS_E_HIP; }
+        hipLaunchKernelGGL(k_agg_fill, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, moff, mem, of, G.rowptr, G.colind, sw, eoff,
                            nbr, wgt, ecnt);
         HIP_TRY(hipGetLastError());
         return SNS_OK;
@@ -537,7 +622,7 @@ int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg
         // locally-dominant matching steps; each productive step matches at least one pair
         int32_t nlist = ncl;
         for (int32_t step = 0;; ++step) {
-            if (step > ncl / 2 + 1) { set_error("amg_aggregation = 2: matching did not finish"); return SNS_E_HIP; }
+            if (step > ncl / 2 + 1) { set_error(who + ": matching did not finish"); return SNS_E_HIP; }
             const int32_t mark = step + 1, nmax = (int32_t)std::min<int64_t>(2 * (int64_t)nlist, ncl);
             HIP_TRY(hipMemsetAsync(ctr, 0, 3 * sizeof(int32_t), st));
             hipLaunchKernelGGL(k_agg_best, dim3(agg_blocks(nlist)), dim3(AGG_TPB), 0, st, nlist, list, mark, max_agg, eoff, ecnt, nbr, wgt,
@@ -549,7 +634,7 @@ int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg
             SNS_TRY(read_back(h, ctr, c3, 3));
             if (c3[0] == 0) break;                              // no eligible edge left anywhere
             if (c3[1] == 0) {
-                set_error("amg_aggregation = 2: a matching step matched nothing with " + std::to_string(c3[0]) + " clusters pending");
+                set_error(who + ": a matching step matched nothing with " + std::to_string(c3[0]) + " clusters pending");
                 return SNS_E_HIP;
             }
             std::swap(list, next);
@@ -576,7 +661,7 @@ int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg
     HIP_TRY(hipMemsetAsync(target, 0xff, (size_t)ncl * sizeof(int32_t), st));
     HIP_TRY(hipMemsetAsync(fill, 0, (size_t)ncl * sizeof(int32_t), st));
     for (int32_t step = 0;; ++step) {
-        if (step > ncl + 1) { set_error("amg_aggregation = 2: leftover assignment did not finish"); return SNS_E_HIP; }
+        if (step > ncl + 1) { set_error(who + ": leftover assignment did not finish"); return SNS_E_HIP; }
         HIP_TRY(hipMemsetAsync(ctr, 0, 2 * sizeof(int32_t), st));
         hipLaunchKernelGGL(k_agg_lbest, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, max_agg, eoff, ecnt, nbr, wgt, size, fill, target,
                            best, bestw, ctr);
@@ -588,21 +673,169 @@ int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg
         SNS_TRY(read_back(h, ctr, c2, 2));
         if (c2[0] == 0) break;
         if (c2[1] == 0) {
-            set_error("amg_aggregation = 2: a leftover step accepted nothing with " + std::to_string(c2[0]) + " singles pending");
+            set_error(who + ": a leftover step accepted nothing with " + std::to_string(c2[0]) + " singles pending");
             return SNS_E_HIP;
         }
     }
     // the clusters without a target numbered in order; a targeted single takes its target's id
     hipLaunchKernelGGL(k_agg_keep, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, target, flag);
     SNS_TRY(scanner.run(flag, ncl, scan));
-    int32_t* agg_dev = newid;                                       // (n_act entries: reused only when n == n_act)
-    if (n > n_act) SNS_TRY(S.alloc(&agg_dev, (size_t)n));
     hipLaunchKernelGGL(k_agg_final, dim3(agg_blocks(n)), dim3(AGG_TPB), 0, st, n, n_act, of, target, scan, agg_dev);
     HIP_TRY(hipGetLastError());
     int64_t total = 0;
     SNS_TRY(read_back(h, scan + ncl, &total, 1));
-    SNS_TRY(read_back(h, agg_dev, agg.data(), (size_t)n));
     nc = (int32_t)total;
+    return SNS_OK;
+}
+
+}  // namespace
+
+// agg[n] (host) <- the level-0 aggregation by operator strength of the owned nodes, built on the device; nc = aggregates.  The
+// same map as aggregate_strength(level-0 pattern, n_owned, max_agg, strength).  Collective on a partitioned handle (the strength's
+// halo exchange of the scales).
+int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc) {
+    const Level& L = h->levels[0];
+    const int32_t n = L.n, n_act = h->n_owned;
+    const GraphView G{L.rowptr, L.colind, n, n_act};
+    agg.assign((size_t)n, -1);
+    nc = 0;
+    AggScratch S;
+    float* sw = nullptr;                                            // strong-slot weights, one per block slot (0: not strong)
+    {
+        // the strength (collective) and the strong graph; the strength is freed again before the matching
+        float *s = nullptr, *smax = nullptr;
+        double* scale = nullptr;
+        int rc = dev_alloc(&s, (size_t)L.nnzb);
+        if (rc == SNS_OK) rc = dev_alloc(&scale, 4 * (size_t)n);
+        if (rc == SNS_OK) rc = compute_strength(h, s, scale);
+        if (rc == SNS_OK && n_act > 0) rc = dev_alloc(&smax, (size_t)n_act);
+        if (rc == SNS_OK && n_act > 0) rc = S.alloc(&sw, (size_t)L.nnzb);
+        bool failed = false;
+        if (rc == SNS_OK && n_act > 0) failed = strong_slots(h, G, s, smax, sw) != SNS_OK;
+        if (rc == SNS_OK && !failed) failed = hipStreamSynchronize(h->stream) != hipSuccess;
+        if (failed) {
+            set_error("amg_aggregation = 2: strength or strong-graph kernel failed");
+            rc = SNS_E_HIP;
+        }
+        if (s) (void)hipFree(s);
+        if (scale) (void)hipFree(scale);
+        if (smax) (void)hipFree(smax);
+        if (rc != SNS_OK) return rc;
+        if (n_act == 0) return SNS_OK;
+    }
+    int32_t* agg_dev = nullptr;
+    SNS_TRY(S.alloc(&agg_dev, (size_t)n));
+    SNS_TRY(match_strong(h, G, sw, max_agg, "amg_aggregation = 2", S, agg_dev, nc));
+    SNS_TRY(read_back(h, agg_dev, agg.data(), (size_t)n));
+    return SNS_OK;
+}
+
+// The hybrid (amg_aggregation = 3): agg[n] (host) <- the geometric map g of the owned nodes (ng aggregates, what amg_aggregation = 0
+// builds) with every aggregate that cuts a dominant coupling dissolved and its nodes F re-matched by aggregate_strength on the
+// induced subgraph of F (policy::HYBRID_KAPPA; everything when more than policy::HYBRID_PHI of the rows are marked: the map of
+// amg_aggregation = 2); `rematched` = F is not empty on this rank.  When it is empty nothing runs after the mark step and the
+// map is g itself.  Collective on a partitioned handle (the strength's halo exchange of the scales).
+int aggregate_hybrid_device(sns_ctx* h, int max_agg, const std::vector<int32_t>& g, int32_t ng, std::vector<int32_t>& agg, int32_t& nc,
+                            bool& rematched) {
+    const Level& L = h->levels[0];
+    const int32_t n = L.n, n_act = h->n_owned;
+    const std::string who = "amg_aggregation = 3";
+    agg = g;
+    nc = ng;
+    rematched = false;
+    for (int32_t i = 0; i < n_act; ++i)
+        if (g[(size_t)i] < 0 || g[(size_t)i] >= ng) { set_error(who + ": the geometric map is not total over the owned nodes"); return SNS_E_STATE; }
+    AggScratch S;
+    // the fp32 strength: freed as soon as the subgraph holds the slots it needs (before the matching, as amg_aggregation = 2 does)
+    float* s = nullptr;
+    struct FreeStrength {
+        float** p;
+        ~FreeStrength() {
+            if (*p) (void)hipFree(*p);
+        }
+    } free_s{&s};
+    {
+        double* scale = nullptr;
+        int rc = dev_alloc(&s, (size_t)std::max<int64_t>(1, L.nnzb));
+        if (rc == SNS_OK) rc = dev_alloc(&scale, 4 * (size_t)n);
+        if (rc == SNS_OK) rc = compute_strength(h, s, scale);
+        if (scale) (void)hipFree(scale);
+        if (rc != SNS_OK) return rc;
+    }
+    if (n_act == 0) return SNS_OK;
+    const hipStream_t st = h->stream;
+    const size_t na = (size_t)n_act, nga = (size_t)std::max(1, ng);
+    int32_t *d_g, *gsize, *dis, *inF, *keep, *nmark;
+    int64_t *fpos, *kpos, *bsum;
+    SNS_TRY(S.alloc(&d_g, na));
+    SNS_TRY(S.alloc(&gsize, nga));
+    SNS_TRY(S.alloc(&dis, nga));
+    SNS_TRY(S.alloc(&inF, na));
+    SNS_TRY(S.alloc(&keep, nga));
+    SNS_TRY(S.alloc(&nmark, 1));
+    SNS_TRY(S.alloc(&fpos, na + 1));
+    SNS_TRY(S.alloc(&kpos, nga + 1));
+    SNS_TRY(S.alloc(&bsum, std::max(na, nga) / SCAN_BLOCK + 1));
+    Scanner scanner{h, bsum};
+    HIP_TRY(hipMemcpyAsync(d_g, g.data(), na * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(gsize, 0, nga * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(dis, 0, nga * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(nmark, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_hyb_size, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, d_g, gsize);
+    hipLaunchKernelGGL(k_hyb_mark, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, L.rowptr, L.colind, s, d_g, gsize,
+                       policy::HYBRID_KAPPA, dis, nmark);
+    HIP_TRY(hipGetLastError());
+    int32_t marked = 0;
+    SNS_TRY(read_back(h, nmark, &marked, 1));
+    if (marked == 0) return SNS_OK;                                 // nothing dissolved: the geometric map
+    // more than HYBRID_PHI of the rows marked: everything dissolved (the map of amg_aggregation = 2)
+    const int32_t all = (double)marked > policy::HYBRID_PHI * (double)n_act ? 1 : 0;
+    hipLaunchKernelGGL(k_hyb_flags, dim3(agg_blocks(std::max(n_act, ng))), dim3(AGG_TPB), 0, st, n_act, ng, all, d_g, dis, inF, keep);
+    HIP_TRY(hipGetLastError());
+    SNS_TRY(scanner.run(inF, n_act, fpos));
+    int64_t nF = 0;
+    SNS_TRY(read_back(h, fpos + n_act, &nF, 1));
+    if (nF == 0) { set_error(who + ": marked rows without a dissolved aggregate"); return SNS_E_HIP; }
+    const int32_t nf = (int32_t)nF;
+    SNS_TRY(scanner.run(keep, ng, kpos));
+    int32_t *fnode, *cnt, *srowptr, *scolind, *sagg, *agg_dev;
+    int64_t* soff;
+    float *ss, *smax, *sw;
+    SNS_TRY(S.alloc(&fnode, (size_t)nf));
+    SNS_TRY(S.alloc(&cnt, (size_t)nf));
+    SNS_TRY(S.alloc(&soff, (size_t)nf + 1));
+    SNS_TRY(S.alloc(&srowptr, (size_t)nf + 1));
+    hipLaunchKernelGGL(k_hyb_count, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, L.rowptr, L.colind, inF, fpos, fnode, cnt);
+    HIP_TRY(hipGetLastError());
+    SNS_TRY(scanner.run(cnt, nf, soff));
+    int64_t nnz = 0;
+    SNS_TRY(read_back(h, soff + nf, &nnz, 1));
+    if (nnz > (int64_t)L.nnzb) { set_error(who + ": the induced subgraph exceeds the pattern"); return SNS_E_HIP; }
+    const size_t nz = (size_t)std::max<int64_t>(nnz, 1);
+    SNS_TRY(S.alloc(&scolind, nz));
+    SNS_TRY(S.alloc(&ss, nz));
+    hipLaunchKernelGGL(k_hyb_fill, dim3(agg_blocks(nf)), dim3(AGG_TPB), 0, st, nf, fnode, n_act, L.rowptr, L.colind, s, inF, fpos, soff,
+                       srowptr, scolind, ss);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipFree(s));
+    s = nullptr;
+    SNS_TRY(S.alloc(&sw, nz));
+    SNS_TRY(S.alloc(&smax, (size_t)nf));
+    SNS_TRY(S.alloc(&sagg, (size_t)nf));
+    SNS_TRY(S.alloc(&agg_dev, (size_t)std::max(1, n)));
+    // the matching of amg_aggregation = 2, unchanged, on the subgraph
+    const GraphView G{srowptr, scolind, nf, nf};
+    SNS_TRY(strong_slots(h, G, ss, smax, sw));
+    int32_t snc = 0;
+    SNS_TRY(match_strong(h, G, sw, max_agg, who, S, sagg, snc));
+    hipLaunchKernelGGL(k_hyb_merge, dim3(agg_blocks(n)), dim3(AGG_TPB), 0, st, n, n_act, ng, d_g, inF, fpos, kpos, sagg, agg_dev);
+    HIP_TRY(hipGetLastError());
+    int64_t nkept = 0;
+    SNS_TRY(read_back(h, kpos + ng, &nkept, 1));
+    SNS_TRY(read_back(h, agg_dev, agg.data(), (size_t)n));
+    nc = (int32_t)nkept + snc;
+    rematched = true;
     return SNS_OK;
 }
 

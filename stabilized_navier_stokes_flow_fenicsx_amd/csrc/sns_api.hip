@@ -76,12 +76,12 @@ int sns_abi_version(void) { return SNS_ABI_VERSION; }
 int64_t sns_options_size(void) { return (int64_t)sizeof(sns_options); }
 
 
-// amg_aggregation: 0, 1 or 2; 1 and 2 (the same map, built on the host / on the device) on 3-D handles only (the strength kernel
-// reads the 4 x 4 blocks of the P1-P1 tet operator) and with aggregates that fit the 32 x 32 smoother blocks
+// amg_aggregation: 0, 1, 2 or 3; 1 and 2 (the same map, built on the host / on the device) and 3 (the hybrid) on 3-D handles only
+// (the strength kernel reads the 4 x 4 blocks of the P1-P1 tet operator) and with aggregates that fit the 32 x 32 smoother blocks
 static int check_aggregation_option(int dim, const sns_options& o) {
     if (o.amg_aggregation == 0) return SNS_OK;
-    if ((o.amg_aggregation != 1 && o.amg_aggregation != 2) || dim != 3 || o.amg_agg_size > policy::STRENGTH_MAX_AGG) {
-        set_error("amg_aggregation: 0, or 1 or 2 on a 3-D handle with amg_agg_size <= 8");
+    if (o.amg_aggregation < 1 || o.amg_aggregation > 3 || dim != 3 || o.amg_agg_size > policy::STRENGTH_MAX_AGG) {
+        set_error("amg_aggregation: 0, or 1, 2 or 3 on a 3-D handle with amg_agg_size <= 8");
         return SNS_E_ARG;
     }
     return SNS_OK;
@@ -246,7 +246,7 @@ int sns_create_2d(sns_handle* out, int32_t n_nodes, int64_t n_tris, const double
 
 namespace {
 
-// assembles_next: the caller (a solve driver) assembles next -- with amg_aggregation = 1 or 2, which aggregates the fine level by the
+// assembles_next: the caller (a solve driver) assembles next -- with amg_aggregation = 1, 2 or 3, which aggregates the fine level by the
 // assembled operator, the hierarchy waits for that assembly (the driver calls here again once it is done); any other caller
 // without an assembled operator gets SNS_E_STATE and the handle stays as it was
 int ensure_hierarchy(sns_ctx* h, bool assembles_next = false) {

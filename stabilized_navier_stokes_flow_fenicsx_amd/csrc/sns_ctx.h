@@ -179,6 +179,8 @@ struct sns_ctx {
     std::unique_ptr<HostPattern> pattern;      // kept until the (lazy) hierarchy build
     std::vector<double> host_pts;              // ... with the node coordinates (3 per node): the aggregation's strength filter on anisotropic meshes
     std::vector<int32_t> agg0;                 // the level-0 aggregate map as built (owned nodes; -1 elsewhere): SNS_EXPORT_AGG0
+    bool fine_rematched_local = false;         // amg_aggregation = 3 re-matched level-0 nodes of this rank ...
+    bool fine_rematched = false;               // ... of some rank (agreed over the ranks: the fine-level aggregate blocks)
     // optional per-launch timing of the fine-level SpMV family
     bool time_kernels = false;
     std::vector<std::array<hipEvent_t, 2>> ev_pool;
@@ -218,6 +220,9 @@ int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double
 int compute_strength(sns_ctx* h, float* out, double* scale);
 // csrc/sns_aggregate.hip: aggregate_strength's map of the owned nodes, built on the device (amg_aggregation = 2)
 int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc);
+// ... and the hybrid (amg_aggregation = 3): the geometric map g (ng aggregates) re-matched where it cuts a dominant coupling
+int aggregate_hybrid_device(sns_ctx* h, int max_agg, const std::vector<int32_t>& g, int32_t ng, std::vector<int32_t>& agg, int32_t& nc,
+                            bool& rematched);
 int norm2(sns_ctx* h, const double* x, double* out);
 int dot(sns_ctx* h, const double* x, const double* y, double* out);
 }  // namespace sns

@@ -39,21 +39,33 @@ constexpr int DISTRIBUTED_DENSE_MAX_DOFS = 640;
 // (10 M tets: level 2, 36 k rows; level 1 has 218 k rows = 46 us per sweep)
 constexpr int GRAPH_MAX_ROWS = 150000;
 
-// ---- operator-strength aggregation of the fine level (amg_aggregation = 1, 2) -----------------------------------------------------
+// ---- operator-strength aggregation of the fine level (amg_aggregation = 1, 2, 3) --------------------------------------------------
 // s_ij = || D_i^-1/2 A_ij D_j^-1/2 ||_F of the first assembled operator (k_strength), symmetrised s_ij <- max(s_ij, s_ji); the
 // edge (i, j) is strong when s_ij >= STRENGTH_THETA x the strongest coupling of i or of j.  The aggregates come from pairwise
 // heavy-edge matching of the strong graph (1: sns_host.cpp aggregate_strength; 2: the same map on the device, sns_aggregate.hip).
 constexpr double STRENGTH_THETA = 0.25;
 // the aggregates must fit the 32 x 32 smoother blocks of csrc/sns_block.hip
 constexpr int STRENGTH_MAX_AGG = 8;
+// the hybrid (amg_aggregation = 3): an owned node is marked when its strongest coupling to another geometric aggregate exceeds
+// HYBRID_KAPPA x the larger of its strongest coupling inside its own and its row's mean coupling (the mean alone for a singleton);
+// the geometric aggregates holding a marked node are dissolved and re-matched by strength (sns_aggregate.hip).  The smallest
+// candidate of {1.5, 2, 3, 4, 8} that marks no node on the structured and the body-centred Delaunay channels
+// (profiles/proto_hybrid_aggregation.txt)
+constexpr double HYBRID_KAPPA = 4.0;
+// ... and when more than HYBRID_PHI of a handle's owned rows are marked, every aggregate is dissolved (the map of amg_aggregation
+// = 2): re-matching only the dissolved aggregates of the jittered-cubic channel (2 % of its rows marked) needs more iterations
+// than the geometric map (profiles/proto_hybrid_aggregation.txt, profiles/hybrid_aggregation.txt)
+constexpr double HYBRID_PHI = 0.01;
 
 // ---- smoother kind ---------------------------------------------------------------------------------------------------------------
 // aggregate blocks on the FINE level: always with amg_block_smooth = 2 and with the aggregation by operator strength
 // (amg_aggregation = 1 or 2: its aggregates are made to hold a sliver's nodes in one block -- with nodal blocks they gain nothing,
-// scripts/proto_strength_aggregation.py); with 1 on a partitioned handle whose share of the fine level is at most
-// amg_block_fine_rows rows per rank -- the latency-bound strong split
-inline bool fine_blocks(const sns_options& o, int nranks, int64_t rows_global_fine) {
-    if (o.amg_block_smooth >= 2 || o.amg_aggregation >= 1) return true;
+// scripts/proto_strength_aggregation.py); with the hybrid (3) when it re-matched level 0 on some rank (`rematched`, agreed over
+// the ranks) -- otherwise its map is the geometric one and it smooths as 0 does; with 1 on a partitioned handle whose share of the
+// fine level is at most amg_block_fine_rows rows per rank -- the latency-bound strong split
+inline bool fine_blocks(const sns_options& o, int nranks, int64_t rows_global_fine, bool rematched = false) {
+    if (o.amg_block_smooth >= 2 || o.amg_aggregation == 1 || o.amg_aggregation == 2) return true;
+    if (o.amg_aggregation == 3 && rematched) return true;
     if (o.amg_block_smooth < 1 || o.amg_block_fine_rows <= 0) return false;
     if (nranks < 2 || rows_global_fine <= 0) return false;
     return rows_global_fine <= (int64_t)o.amg_block_fine_rows * nranks;
@@ -133,14 +145,15 @@ inline Sweeps pre_post_sweeps(const sns_options& o, int ll, bool blocks, bool ra
 // 8 members (its smoother blocks exist); has_ap[l]: M = A P exists (the fused post-sweep); has_ap_rep[l]: M's columns in the ids of
 // the replicated level below.  Agreed over the ranks by the caller: win_capable[l] -- every rank's plan of the level receives in
 // order straight into its window; max_owned[l] -- the most owned rows any rank holds on the level.  last: how the last level is
-// solved.  rep_gather_fits: a rank's piece of the replicated right-hand side fits the all-gather staging area.  The remaining
-// fields are the harnesses' A/B switches (not options).
+// solved.  rep_gather_fits: a rank's piece of the replicated right-hand side fits the all-gather staging area.  fine_rematched:
+// the hybrid aggregation (amg_aggregation = 3) re-matched level-0 nodes on some rank.  The remaining fields are the harnesses'
+// A/B switches (not options).
 struct Facts {
     int nranks = 1, rep_level = 0;
     std::vector<int64_t> rows, max_owned;
     std::vector<uint8_t> has_blocks, has_ap, has_ap_rep, win_capable;
     int64_t rows_global_l1 = 0;
-    bool windows = false, rep_gather_fits = false;
+    bool windows = false, rep_gather_fits = false, fine_rematched = false;
     CoarsestKind last = COARSEST_SWEEPS;
     bool team_overlap = false, fuse_puts = true, restrict_fuse = true;
     int graph_max_rows = GRAPH_MAX_ROWS;
@@ -195,7 +208,7 @@ inline CyclePlan plan_cycle(const sns_options& o, const Facts& f) {
         const bool rep_src = R > 0 && l == R - 1;
         const int ll = (R > 0 && l >= R) ? l - 1 : l;      // the replicated copy is not a new level
         q.cycled = rep_src ? 0 : 1;
-        q.blocks = !solved_last && !rep_src && fact(f.has_blocks, l) && (l > 0 || fine_blocks(o, f.nranks, f.rows[0])) &&
+        q.blocks = !solved_last && !rep_src && fact(f.has_blocks, l) && (l > 0 || fine_blocks(o, f.nranks, f.rows[0], f.fine_rematched)) &&
                    blocks_allowed(o, f.rows[(size_t)l], partitioned(l) ? f.nranks : 1);
         if (solved_last) {
             q.kind = f.last == COARSEST_BLOCKED_INVERSE ? SNS_LEVEL_DIRECT_BLOCKED : f.last == COARSEST_SMALL_INVERSE ? SNS_LEVEL_DIRECT

@@ -146,7 +146,7 @@ int upload_block_rows(sns_ctx* h, int l, Level& L, const std::vector<int32_t>& m
     if (mode <= 0 || nc_owned < 0) return SNS_OK;
     // (the fine level: runs before the hierarchy's plan exists; global counts only, every rank answers alike)
     const Comm* c = h->comm.get();
-    if (l == 0 && !policy::fine_blocks(h->opt, (c && c->active()) ? c->nranks : 1, h->n_global_fine)) return SNS_OK;
+    if (l == 0 && !policy::fine_blocks(h->opt, (c && c->active()) ? c->nranks : 1, h->n_global_fine, h->fine_rematched)) return SNS_OK;
     // blocks = aggregates; an aggregate of more than 8 nodes (a leftover node joined a full neighbour) is split in member order
     std::vector<int32_t> rows, of((size_t)std::max(1, L.n), -1);
     rows.reserve((size_t)8 * std::max(1, nc_owned));
@@ -396,14 +396,23 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
 
 // Level 0 aggregated by operator strength: the strength of the assembled fine operator (csrc/sns_strength.hip) and aggregate_strength
 // over the owned nodes -- amg_aggregation = 1: the strength copied to the host and sns_host.cpp's matcher; 2: the same map built on
-// the device (csrc/sns_aggregate.hip), only the map copied.  The fp32 strength and the device scratch are freed again.
-static int aggregate_fine_by_strength(sns_ctx* h, const HostPattern& fine, std::vector<int32_t>& agg, int32_t& nc) {
+// the device (csrc/sns_aggregate.hip), only the map copied; 3: the geometric map of amg_aggregation = 0 (`pts`: the node
+// coordinates or null, as 0 passes them), re-matched by strength on the device only where it cuts a dominant coupling
+// (h->fine_rematched_local).  The fp32 strength and the device scratch are freed again.
+static int aggregate_fine_by_strength(sns_ctx* h, const HostPattern& fine, const double* pts, std::vector<int32_t>& agg, int32_t& nc) {
     const Level& L = h->levels[0];
     if (!h->has_matrix) {
         set_error("amg_aggregation = " + std::to_string(h->opt.amg_aggregation) + ": the hierarchy is built from the assembled operator; assemble first");
         return SNS_E_STATE;
     }
-    if (h->opt.amg_aggregation == 2) return aggregate_strength_device(h, std::min(h->opt.amg_agg_size, policy::STRENGTH_MAX_AGG), agg, nc);
+    const int max_agg = std::min(h->opt.amg_agg_size, policy::STRENGTH_MAX_AGG);
+    if (h->opt.amg_aggregation == 3) {
+        std::vector<int32_t> g;
+        int32_t ng = 0;
+        aggregate_nodes(fine, h->n_owned, std::min(255, std::max(2, h->opt.amg_agg_size)), g, ng, pts);
+        return aggregate_hybrid_device(h, max_agg, g, ng, agg, nc, h->fine_rematched_local);
+    }
+    if (h->opt.amg_aggregation == 2) return aggregate_strength_device(h, max_agg, agg, nc);
     float* s_dev = nullptr;
     double* scale = nullptr;
     SNS_TRY(dev_alloc(&s_dev, (size_t)L.nnzb));
@@ -434,6 +443,7 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
     int32_t n_owned = h->n_owned;
     std::vector<double> cur_pts = h->dim == 3 ? std::move(h->host_pts) : std::vector<double>();   // coordinates of `cur`'s nodes (coarse: centroids)
     h->host_pts = std::vector<double>();
+    h->fine_rematched_local = h->fine_rematched = false;
     {
         double ng[1] = {(double)h->n_owned};
         SNS_TRY(global_sum(h, ng, 1));
@@ -466,15 +476,17 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
         if (!dist && l >= 1 && n_owned <= policy::coarsest_rows(o)) break;       // serial: this level is solved directly
         std::vector<int32_t> agg;
         int32_t nc_owned = 0;
+        const double* pts = cur_pts.size() == (size_t)3 * cur.n ? cur_pts.data() : nullptr;
         if (l == 0 && o.amg_aggregation >= 1) {
-            SNS_TRY(aggregate_fine_by_strength(h, cur, agg, nc_owned));
+            SNS_TRY(aggregate_fine_by_strength(h, cur, pts, agg, nc_owned));
         } else {
-            aggregate_nodes(cur, n_owned, std::min(255, std::max(2, o.amg_agg_size)), agg, nc_owned,
-                            cur_pts.size() == (size_t)3 * cur.n ? cur_pts.data() : nullptr);
+            aggregate_nodes(cur, n_owned, std::min(255, std::max(2, o.amg_agg_size)), agg, nc_owned, pts);
         }
         if (l == 0) h->agg0 = agg;
-        double prog[2] = {(double)n_owned, (double)nc_owned};
-        SNS_TRY(global_sum(h, prog, 2));
+        // (+ whether the hybrid re-matched level-0 nodes of some rank: the fine level's blocks below are uploaded on every rank or none)
+        double prog[3] = {(double)n_owned, (double)nc_owned, (l == 0 && h->fine_rematched_local) ? 1.0 : 0.0};
+        SNS_TRY(global_sum(h, prog, 3));
+        if (l == 0) h->fine_rematched = prog[2] > 0.0;
         if (prog[1] >= prog[0] || prog[1] == 0.0) break;      // no progress anywhere
         if (l == 0) h->n_global_l1 = (int64_t)prog[1];
         int32_t nc_total = nc_owned;
@@ -639,7 +651,9 @@ int plan_hierarchy(sns_ctx* h) {
                            : (last.dense_inv || h->cg_N > 0) ? policy::COARSEST_SMALL_INVERSE : policy::COARSEST_SWEEPS;
     f.rep_gather_fits = h->rep_level > 0 && c && c->peer && h->levels[h->rep_level].n_blk > 0 &&
                         (size_t)4 * h->rep_maxn * (size_t)c->nranks <= c->peer->ag_doubles;
-    std::vector<double> mine((size_t)2 * nl), all;
+    // per level: window-capable, owned rows; last: the hybrid re-matched level-0 nodes of this rank
+    std::vector<double> mine((size_t)2 * nl + 1), all;
+    mine[(size_t)2 * nl] = h->fine_rematched_local ? 1.0 : 0.0;
     for (int l = 0; l < nl; ++l) {
         const Level& L = h->levels[l];
         f.rows.push_back(L.n_global);
@@ -654,11 +668,13 @@ int plan_hierarchy(sns_ctx* h) {
     else all = mine;
     f.win_capable.assign((size_t)nl, 1);
     f.max_owned.assign((size_t)nl, 0);
-    for (size_t r = 0; r < all.size() / mine.size(); ++r)
+    for (size_t r = 0; r < all.size() / mine.size(); ++r) {
+        if (all[r * mine.size() + 2 * (size_t)nl] != 0.0) f.fine_rematched = true;
         for (int l = 0; l < nl; ++l) {
             if (all[r * mine.size() + l] == 0.0) f.win_capable[(size_t)l] = 0;
             f.max_owned[(size_t)l] = std::max(f.max_owned[(size_t)l], (int64_t)all[r * mine.size() + nl + l]);
         }
+    }
     h->plan = policy::plan_cycle(h->opt, f);
     return SNS_OK;
 }
