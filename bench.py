@@ -9,13 +9,16 @@ solution: fused Jacobian+residual assembly (HIP), AMG setup, BiCGStab solve to r
 When the sequence converges (||F|| < 1e-8, :281) it restarts from the Stokes solution.
 metric = M-DOF/s = N_dof / (t_assemble + t_solve) per Newton iteration / 1e6  (SURVEY 8d).
 
-  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run does only what the headline needs: set-up, W + K Newton steps, the outputs of --dump-outputs and the JSON line.
+--full adds what takes runs of its own: the all-fp64 repetition of the timed steps (all_f64_preconditioner), the assembly
+kernels timed alone (roofline.assembly_kernels), the CPU baseline of the same step (cpu_baseline) and, for N>1, the weak layout.
 N>1: `python bench.py --gpus N` started as a plain command launches its own N ranks (one per GPU, torch.distributed.run
 on 127.0.0.1), relays rank 0's JSON line and exits with the workers' return code; started under an external
 torch.distributed.run (the driver's way) it runs as the rank it is given.  WORLD_SIZE != --gpus is an error.
 The HEADLINE is what north_star states -- the SAME 10.1 M-tet duct element-partitioned into N x-slabs (strong
 scaling; every rank meshes only its own slab), halo exchange and dot-product all-reduces on RCCL inside libsns.so.
-The weak layout (duct refined by N^(1/3) per direction, every GPU keeps a ~10.1 M-tet slab) is timed afterwards and
+With --full the weak layout (duct refined by N^(1/3) per direction, every GPU keeps a ~10.1 M-tet slab) is timed afterwards and
 reported under "weak_scaling" in the same JSON line (--no-weak skips it).
 --config 3 / 4 / 4u time the other full-size BASELINE configs as secondary lines; the default (5) is the headline.
 --dry-run: the launch + partition + halo-plan + collective path WITHOUT any HIP call (gloo on the CPU): what the
@@ -52,17 +55,20 @@ def parse_args(argv=None):
     ap.add_argument("--length", type=float, default=4.0, help="duct length")
     ap.add_argument("--re", type=float, default=None)
     ap.add_argument("--ksp", type=str, default="bicgstab")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run what takes runs of its own: the all-fp64 repetition of the timed steps, "
+                         "the assembly kernels timed alone, the CPU baseline and (N>1) the weak layout")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-maxit", type=int, default=1500,
                     help="iteration bound of the CPU baseline's Krylov solve (the 10.1 M-tet headline workload stops by "
                          "its own criterion after ~740 tfqmr iterations = ~100 s on 16 cores)")
-    ap.add_argument("--no-f64-rerun", action="store_true", help="skip the all-fp64 repetition of the timed steps")
+    ap.add_argument("--no-f64-rerun", action="store_true", help="--full: skip the all-fp64 repetition of the timed steps")
     ap.add_argument("--budget", type=float, default=540.0,
                     help="N>1: wall-clock seconds the whole run of a rank may take (the driver gives the bench 600 s): the secondary legs "
                          "(peer-window transport, weak layout) share what is left of it after the headline -- each at most its own "
                          "--peer-timeout / --weak-timeout, and a leg that would start with less than 20 s left is skipped -- so the one "
                          "JSON line is out, and every rank has exited 0, inside the budget whatever the legs do")
-    ap.add_argument("--no-weak", action="store_true", help="N>1: skip the weak-scaling layout after the headline")
+    ap.add_argument("--no-weak", action="store_true", help="N>1, --full: skip the weak-scaling layout after the headline")
     ap.add_argument("--weak-timeout", type=float, default=300.0,
                     help="N>1: seconds the weak-scaling leg may take; after that the line is printed with "
                          "weak_scaling = {error: timeout} and every rank exits 0 (the headline is never lost to it)")
@@ -480,12 +486,12 @@ def dry_run(args, cfg, cells, length, world, rank):
     if os.environ.get("SNS_DRYRUN_PEER_STALL") and ok:
         # test hook: the peer-transport leg never comes back -- its deadline comes out of --budget like in a real run
         out["peer_transport"] = None
-        secs = leg_seconds(args.budget, args.peer_timeout, 2)
+        secs = leg_seconds(args.budget, args.peer_timeout, 2 if args.full else 1)
         if secs > 0:
             run_weak_leg_guarded(out, rank, secs, lambda: time.sleep(36000), key="peer_transport", what="peer-transport")
         else:
             out["peer_transport"] = {"skipped": "less than 20 s of --budget left"}
-    if os.environ.get("SNS_DRYRUN_WEAK_STALL") and ok:
+    if os.environ.get("SNS_DRYRUN_WEAK_STALL") and ok and args.full:
         # test hook: the deadline of the weak-scaling leg with real ranks -- a leg that never comes back (on every rank, as a
         # stuck collective would look) must still end in ONE line on rank 0's stdout and N clean exits
         out["weak_scaling"] = None
@@ -640,7 +646,7 @@ def leg_record(P, U, sres, args, cfg, world, n_dof_global, f64_rerun=True, dump_
     """The W + K timed Newton steps on handle P and every key of the line that belongs to THAT run of them: value, step time,
     transport, Newton log, phases, counters, the live roofline of the fine-level passes (HIP events around every launch) and
     the all-f64 repetition.  One record per transport leg: the line never mixes keys of two runs.  dump_dir: write
-    the last timed step's outputs there (dump_outputs)."""
+    the last timed step's outputs there (dump_outputs).  The assembly timed alone and the all-f64 repetition run with --full only."""
     comm = P.comm_info()
     ms_per_step, log, w, last = timed_newton_steps(P, U, args.steps, args.warmup, world)
     if dump_dir:
@@ -651,13 +657,13 @@ def leg_record(P, U, sres, args, cfg, world, n_dof_global, f64_rerun=True, dump_
     s = P.sizes()
     ctr = P.counters()
     # K1 (Jacobian + residual assembly) timed on its own after the timed region: HIP events around 5 passes
-    asm_ms = P.bench_assemble(w, "ns", 5)
+    asm_ms = P.bench_assemble(w, "ns", 5) if args.full else None
     asm_bytes = 2480.0 * s["n_tets"]                   # 2480 B/tet
     # the same K steps once more with EVERY array in fp64 (no fp32 copies inside the preconditioner), reported
     # beside the headline so that the effect of the mixed-precision preconditioner is on record
     all_f64 = None
     fmt0 = int(P.options.amg_f32_matrix)
-    if fmt0 and f64_rerun and not args.no_f64_rerun:
+    if fmt0 and f64_rerun and args.full and not args.no_f64_rerun:
         P.set_options(amg_f32_matrix=0)
         ms64, log64, _, _ = timed_newton_steps(P, U, args.steps, args.warmup, world)
         all_f64 = {"value": round(n_dof_global / (ms64 * 1e-3) / 1e6, 3), "unit": "M-DOF/s", "ms_per_step": round(ms64, 3),
@@ -736,7 +742,8 @@ def leg_record(P, U, sres, args, cfg, world, n_dof_global, f64_rerun=True, dump_
                                                           "achieved_tflops": round(17680.0 * s["n_tets"] / (asm_ms * 1e-3) / 1e12, 2),
                                                           "peak_tflops": 78.6,
                                                           "frac": round(17680.0 * s["n_tets"] / (asm_ms * 1e-3) / 1e12 / 78.6, 4)}
-                                                         if P.options.assembly_fused else None)}}
+                                                         if P.options.assembly_fused else None)}
+                                        if asm_ms is not None else None}
     return {"value": round(value, 3), "ms_per_step": round(ms_per_step, 3), "transport": comm["transport"], "rccl_ranks": comm["rccl_ranks"],
             "log": log, "phase_ms_per_step": {"assemble": round(tm.assemble_ms / args.steps, 3),
                                               "pc_setup": round(tm.pc_setup_ms / args.steps, 3),
@@ -844,15 +851,15 @@ def main():
             "dtype": "f64", "data": "synthetic",
             "precision_note": ("operator, residuals, Krylov recurrences and reductions in f64; the AMG preconditioner's "
                                "smoother/residual passes read a " + {1: "fp32", 2: "row-scaled fp16"}[fmt] + " copy of the level "
-                               "matrices (vectors and arithmetic f64; same Krylov iteration counts); the strict all-f64 "
-                               "figure of the same steps is under all_f64_preconditioner") if fmt else "all f64",
+                               "matrices (vectors and arithmetic f64; same Krylov iteration counts); with --full the strict "
+                               "all-f64 figure of the same steps is under all_f64_preconditioner") if fmt else "all f64",
             "config": {"workload": f"BASELINE config {cfg}: {desc} = {n_tets_global} tets, "
                                    f"{n_dof_global} dofs, Re={Re:g}, Newton iteration (assemble J+F, AMG setup, "
                                    f"{args.ksp} rtol 1e-8, bt line search)",
                        "parallelism": (f"element partition x{world} ({'x-slabs' if cfg == '5' else 'RCB'}), "
                                        f"{n_tets_global // world} tets per GPU" if world > 1 else "single GPU"),
                        "scaling_note": "strong: the one mesh split N ways (north_star: >= 6x at 8 GPUs on the 10 M-tet duct); "
-                                       "the weak layout is under weak_scaling",
+                                       "with --full the weak layout is under weak_scaling",
                        "newton_log_fnorm_kspits_reason": [(float(f"{a:.3e}"), b, c) for a, b, c in rec["log"]],
                        "phase_ms_per_step": rec["phase_ms_per_step"],
                        "krylov_loop_last_solve": rec["krylov_loop_last_solve"],
@@ -870,7 +877,8 @@ def main():
         # out of time): whatever happens later, the record of the run holds it
         print("[bench] headline measured: " + json.dumps({k: out[k] for k in ("value", "unit", "n_gpus", "ms_per_step", "transport")}),
               file=sys.stderr, flush=True)
-    U_host = U.cpu().numpy() if (rank == 0 and world == 1 and not dist_on and host is not None) else None
+    U_host = (U.cpu().numpy() if (args.full and not args.no_cpu_baseline and rank == 0 and world == 1 and not dist_on
+                                  and host is not None) else None)
     P.close()
     del P, U
     torch.cuda.empty_cache()
@@ -884,7 +892,8 @@ def main():
     # deadline taken from --budget and every device-side wait inside it is bounded: a transport problem costs this key, not
     # the line.)
     WATCHDOG.tick("headline done")
-    legs_left = (1 if (dist_on and not args.no_peer and peers is None) else 0) + (1 if (cfg == "5" and dist_on and not args.no_weak) else 0)
+    weak = cfg == "5" and dist_on and args.full and not args.no_weak
+    legs_left = (1 if (dist_on and not args.no_peer and peers is None) else 0) + (1 if weak else 0)
     if dist_on and not args.no_peer and peers is None:
         box = {}
 
@@ -941,7 +950,7 @@ def main():
 
     # ---- second key for N > 1: the weak layout (every GPU keeps the single-GPU share) --------------------------
     WATCHDOG.tick("peer leg done")
-    if cfg == "5" and dist_on and not args.no_weak:
+    if weak:
         sc = float(world) ** (1.0 / 3.0)
         wcells = tuple(int(round(c * sc)) for c in cells)
 
@@ -974,7 +983,7 @@ def main():
             out["weak_scaling"] = {"skipped": "less than 20 s of --budget left"}
 
     if rank == 0:
-        if U_host is not None and not args.no_cpu_baseline:
+        if U_host is not None:
             mesh, (mask, g) = host
             WATCHDOG.limit = 0 if WATCHDOG.limit <= 0 else max(WATCHDOG.limit, 3600.0)      # a long host-only leg
             WATCHDOG.tick("cpu baseline")

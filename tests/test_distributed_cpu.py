@@ -279,13 +279,13 @@ def test_bench_repeats_a_crashed_launch_once_without_the_two_stream_overlap(tmp_
 
 
 def test_bench_weak_leg_deadline_keeps_the_headline_line():
-    """a weak-scaling leg that hangs (here: on both ranks, for good) must not cost the headline.  After
-    --weak-timeout seconds rank 0 prints THE line with weak_scaling = {error: timeout ...}, every rank leaves with exit code 0
-    (no re-exec, no child), and the launcher reports success with exactly one line."""
+    """a weak-scaling leg (--full) that hangs (here: on both ranks, for good) must not cost the headline.
+    After --weak-timeout seconds rank 0 prints THE line with weak_scaling = {error: timeout ...}, every rank leaves with exit
+    code 0 (no re-exec, no child), and the launcher reports success with exactly one line."""
     import json
     import time
     t0 = time.time()
-    rc, out, err = _run_bench(["--gpus", "2", "--dry-run", "--cells", "24,6,6", "--weak-timeout", "3"],
+    rc, out, err = _run_bench(["--gpus", "2", "--dry-run", "--cells", "24,6,6", "--weak-timeout", "3", "--full"],
                               {"SNS_DRYRUN_WEAK_STALL": "1", "SNS_WATCHDOG_S": "600"}, timeout=300)
     assert rc == 0, err[-2000:]
     assert time.time() - t0 < 200
@@ -294,6 +294,14 @@ def test_bench_weak_leg_deadline_keeps_the_headline_line():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and "timeout" in d["weak_scaling"]["error"]
     assert "weak-scaling leg exceeded" in err
+    # a plain run (no --full) has no weak leg to wait for: the same hook is never reached
+    t0 = time.time()
+    rc, out, err = _run_bench(["--gpus", "2", "--dry-run", "--cells", "24,6,6", "--weak-timeout", "300"],
+                              {"SNS_DRYRUN_WEAK_STALL": "1", "SNS_WATCHDOG_S": "600"}, timeout=300)
+    assert rc == 0, err[-2000:]
+    assert time.time() - t0 < 200
+    d = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][0])
+    assert "weak_scaling" not in d and "weak-scaling leg" not in err
     # in-process: a leg that finishes in time returns normally and leaves the line to the caller
     import bench
     o = {"weak_scaling": None}
@@ -318,7 +326,7 @@ def test_bench_secondary_legs_share_one_budget():
            "SNS_BENCH_RESERVE_S": "4"}
     t0 = time.time()
     rc, out, err = _run_bench(["--gpus", "2", "--dry-run", "--cells", "24,6,6", "--budget", "24", "--peer-timeout", "300",
-                               "--weak-timeout", "300"], env, timeout=200)
+                               "--weak-timeout", "300", "--full"], env, timeout=200)
     took = time.time() - t0
     assert rc == 0, err[-2000:]
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]
@@ -327,7 +335,7 @@ def test_bench_secondary_legs_share_one_budget():
     assert "timeout" in d["peer_transport"]["error"] and "peer-transport leg exceeded" in err
     assert took < 24 + 25, took                     # (the budget + the launcher's own start-up and teardown)
     # no room at all: both legs are skipped, the line still comes
-    rc, out, err = _run_bench(["--gpus", "2", "--dry-run", "--cells", "24,6,6", "--budget", "1"], env, timeout=200)
+    rc, out, err = _run_bench(["--gpus", "2", "--dry-run", "--cells", "24,6,6", "--budget", "1", "--full"], env, timeout=200)
     assert rc == 0, err[-2000:]
     d = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][0])
     assert "skipped" in d["peer_transport"] and "skipped" in d["weak_scaling"]

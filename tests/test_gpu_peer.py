@@ -147,7 +147,7 @@ def test_protocol_selftest_between_concurrent_queues(nranks, halo_nodes):
 
 
 def test_bench_py_runs_two_ranks_end_to_end_on_one_gpu(tmp_path):
-    """`python bench.py --gpus 2 --transport peer --shared-gpu`: the launcher, two rank processes on cuda:0 bootstrapped over gloo, the
+    """`python bench.py --gpus 2 --transport peer --shared-gpu --full`: the launcher, two rank processes on cuda:0 bootstrapped over gloo, the
     slab partition, the timed Newton steps over peer windows, the weak leg and ONE JSON line -- the whole multi-rank flow of the
     bench on a 1-GPU box (RCCL cannot do that).  The line says it is a rehearsal; its timings mean nothing."""
     if not torch.cuda.is_available():
@@ -157,7 +157,7 @@ def test_bench_py_runs_two_ranks_end_to_end_on_one_gpu(tmp_path):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["SNS_BENCH_LOG_DIR"] = str(tmp_path)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--transport", "peer", "--shared-gpu", "--steps", "2",
-                        "--warmup", "1", "--cells", "64,16,16", "--no-f64-rerun", "--weak-timeout", "200", "--launch-timeout", "400"],
+                        "--warmup", "1", "--cells", "64,16,16", "--full", "--no-f64-rerun", "--weak-timeout", "200", "--launch-timeout", "400"],
                        capture_output=True, text=True, env=env, timeout=460)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
