@@ -462,6 +462,33 @@ SNS_API int sns_streamtrace(int32_t n_nodes, int64_t n_tets, const double* pts_d
                     double max_step, double rtol, double atol, double x_stop, double speed_min,
                     double* pos_out_dev, double* t_out_dev, int32_t* status_out_dev,
                     int32_t* steps_out_dev, void* hip_stream);
+/* ---- point location and P1 evaluation at arbitrary points (row a9: interpolate.locate_points on the
+ *      device; what interpolate_nonmatching and Function.eval with a bb_tree do for the reference,
+ *      NavierStokesChannelFlow.py:175-194, streamtrace.py) ------------------------------------------
+ * No handle.  All arrays are device memory; n_missed_out is a HOST pointer (may be NULL).  Both calls
+ * return after their work on hip_stream has finished.
+ * sns_locate_points: for each of the n_query points query_dev (n_query x 3) the tet tet_out_dev[q]
+ * and its barycentric coordinates lam_out_dev (n_query x 4, clipped to [0,1] and divided by their
+ * sum) by the rule of interpolate.locate_points: a uniform bucket grid over the tets' bounding boxes
+ * (the host's lo / res / h); the FIRST candidate of the point's bucket (ascending tet id) whose
+ * smallest coordinate is >= -padding, else the candidate with the largest smallest coordinate (the
+ * first on ties); a point without a candidate takes the tet of the nearest centroid over all tets
+ * (lowest index on ties) and counts in *n_missed_out.  Deterministic: repeated calls give the same
+ * bits.  Temporary device memory, allocated and freed inside the call: 8 B per (tet, bucket) pair,
+ * i.e. 8 n_tets x buckets per tet (8 on a Delaunay mesh, 24 on a structured duct whose nodes lie on
+ * bucket faces: 200 MB at 1 M tets), 12 B per bucket (about n_tets / 6 buckets), 4 B per query
+ * point, and 24 B per tet when some point misses.
+ * SNS_E_ARG: negative sizes, n_tets or n_query >= 2^31, padding < 0 or NaN; SNS_E_MESH: no tets, a
+ * node id outside [0, n_nodes), non-finite coordinates.  n_query == 0: no-op, SNS_OK.             */
+SNS_API int sns_locate_points(int32_t n_nodes, int64_t n_tets, const double* pts_dev, const int32_t* tets_dev,
+                      int64_t n_query, const double* query_dev, double padding,
+                      int32_t* tet_out_dev, double* lam_out_dev, int64_t* n_missed_out, void* hip_stream);
+/* out[q*ncomp+c] = sum_a lam[q,a] * vals[tets[tet[q],a]*ncomp+c], 1 <= ncomp <= 4 (vals: n_nodes x
+ * ncomp, e.g. the nodal [ux,uy,uz,p] of a solution with ncomp = 4); a tet id outside [0, n_tets)
+ * gives NaN.  SNS_E_ARG for ncomp outside 1..4 or negative sizes, SNS_E_MESH for n_tets == 0;
+ * n_query == 0: no-op, SNS_OK.                                                                     */
+SNS_API int sns_eval_p1(int64_t n_tets, const int32_t* tets_dev, int32_t ncomp, const double* vals_dev,
+                int64_t n_query, const int32_t* tet_dev, const double* lam_dev, double* out_dev, void* hip_stream);
 
 /* ---- host-only symbolic utilities (no GPU needed; used by sns_create and by
  *      the CPU test-suite) ------------------------------------------------------

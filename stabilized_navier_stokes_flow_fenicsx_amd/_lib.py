@@ -126,6 +126,8 @@ _SIGNATURES = [
     ("sns_bench_collective", C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("sns_streamtrace", C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int, C.c_double, C.c_double,
                                   C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
+    ("sns_locate_points", C.c_int, [C.c_int32, C.c_int64, _P, _P, C.c_int64, _P, C.c_double, _P, _P, C.POINTER(C.c_int64), _P]),
+    ("sns_eval_p1", C.c_int, [C.c_int64, _P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
     ("sns_host_pattern", C.c_int, [C.c_int32, C.c_int64, _P, C.POINTER(C.c_int64), _P, _P, _P, _P]),
     ("sns_host_aggregate", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int, _P, C.POINTER(C.c_int32)]),
     ("sns_host_aggregate_pts", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

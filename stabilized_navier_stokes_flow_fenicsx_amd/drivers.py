@@ -262,10 +262,11 @@ def _from_global_host(P, xg):
     return P.scatter(xg) if getattr(P, "part", None) is not None else torch.from_numpy(np.ascontiguousarray(xg)).to(P.device)
 
 
-def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0"):
+def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", interp_device=None):
     """The reference's three-stage continuation (:468-549): Stokes on the 0.1 mesh ->
     Navier-Stokes on the 0.1 mesh -> Navier-Stokes on the user mesh, each stage
-    warm-started from the previous one."""
+    warm-started from the previous one.  ``interp_device`` (e.g. "cuda:0") runs the coarse-to-fine
+    interpolation on that GPU instead of the host (interpolate_initial_guess)."""
     import torch
     from .solver import solve_navier_stokes, solve_stokes_problem
     Re, img_fname, flowrate_ratio, channel_mesh_size = parse_arguments(argv)
@@ -287,7 +288,7 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0"):
     Pf = _problem(msh_f, bcs_f, reynolds=float(Re), ksp_type=snes_ksp_type, device=device)
     if rank == 0:
         print("Interpolating Coarse NS Flow", flush=True)
-    w0 = interpolate_initial_guess(msh, w_coarse_host, msh_f)
+    w0 = interpolate_initial_guess(msh, w_coarse_host, msh_f, device=interp_device)
     w, u, p = solve_navier_stokes(Pf, _from_global_host(Pf, w0), rank, continuation=_continuation())
     wg = _to_global_host(Pf, w)
     out = dict(msh=msh_f, w=wg, u=wg.reshape(-1, 4)[:, :3].copy(), p=wg.reshape(-1, 4)[:, 3].copy(), Re=Re, img_fname=img_fname,

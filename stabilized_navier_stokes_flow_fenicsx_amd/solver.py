@@ -199,6 +199,19 @@ class FlowProblem:
         ng = self.global_mesh.num_nodes if self.global_mesh is not None else self.n_global_nodes
         return PT.gather_owned(self.part, x_local, ng, self.group.dist_group if isinstance(self.group, PeerGroup) else self.group)
 
+    def eval_at(self, w, pts, padding: float = 1e-6) -> np.ndarray:
+        """Nodal [ux, uy, uz, p] of the solution ``w`` at the points ``pts`` (m,3) -> (m,4) numpy: point location and P1
+        evaluation on this problem's device (interpolate.eval_points; what ``Function.eval`` with a bounding-box tree gives a
+        DOLFINx user).  Single-GPU 3-D problems only."""
+        from .interpolate import eval_points
+        if self.part is not None:
+            raise NotImplementedError("eval_at covers single-GPU problems: a partitioned problem holds only its rank's part of "
+                                      "the mesh; gather the solution and evaluate it on the global mesh with "
+                                      "interpolate.eval_points")
+        if self.dim != 3:
+            raise NotImplementedError("eval_at covers 3-D tet meshes only")
+        return eval_points(self.mesh, self._vec(w).view(-1, 4), pts, self.device, padding)
+
     # -- lifetime -----------------------------------------------------------
     def close(self):
         if getattr(self, "h", None):

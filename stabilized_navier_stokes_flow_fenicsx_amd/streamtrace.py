@@ -5,7 +5,8 @@ seed with its own ``scipy.integrate.solve_ivp(RK45, max_step=0.125, t in [0, 20]
 bounding-box-tree lookup per velocity evaluation, a thread pool for the forward pass (:208-250) and
 an MPI task farm for the reverse pass (:385-446).  Here all seeds are traced by one HIP kernel
 (``sns_streamtrace``, csrc/sns_trace.hip: same RK45, controller, events); the host only builds the
-tet face adjacency and locates the seeds' starting tets.
+tet face adjacency and, by default, locates the seeds' starting tets (``locate="device"``: sns_locate_points on
+the tracing device, the same rule).
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .interpolate import locate_points
+from .interpolate import _DeviceMesh, locate_points, locate_points_device
 from .mesh import TetMesh
 
 X_STOP_FORWARD = 3.7      # position_event            streamtrace.py:180-183
@@ -41,8 +42,9 @@ def tet_face_neighbors(tets: np.ndarray) -> np.ndarray:
 
 def run_streamtrace(mesh: TetMesh, velocity, seeds, *, reverse: bool = False, x_stop: float | None = None,
                     t_end: float = 20.0, max_step: float = 0.125, rtol: float = 1e-3, atol: float = 1e-6,
-                    speed_min: float = 1e-6, device="cuda:0", nbr=None):
-    """Trace ``seeds`` (m,3) through ``velocity`` (n,3); returns dict(pos, t, status, steps) (numpy)."""
+                    speed_min: float = 1e-6, device="cuda:0", nbr=None, locate: str = "host"):
+    """Trace ``seeds`` (m,3) through ``velocity`` (n,3); returns dict(pos, t, status, steps, seed_tet) (numpy).
+    ``locate``: where the seeds' starting tets are found, "host" (interpolate.locate_points) or "device"."""
     import torch
     lib = _lib.load()
     if not torch.cuda.is_available():
@@ -56,11 +58,19 @@ def run_streamtrace(mesh: TetMesh, velocity, seeds, *, reverse: bool = False, x_
         x_stop = X_STOP_REVERSE if reverse else X_STOP_FORWARD
     if nbr is None:
         nbr = tet_face_neighbors(mesh.tets)
-    seed_tet, _ = locate_points(mesh, seeds) if len(seeds) else (np.zeros(0, np.int64), None)
+    if locate not in ("host", "device"):
+        raise ValueError(f"locate must be 'host' or 'device', got {locate!r}")
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dtype=dt)
-    d_pts, d_tets = t(mesh.points, torch.float64), t(mesh.tets, torch.int32)
+    d_seeds = t(seeds, torch.float64)
+    if locate == "device":
+        dm = _DeviceMesh(mesh, dev)
+        d_pts, d_tets = dm.pts, dm.tets
+        d_st = locate_points_device(dm, d_seeds)[0]
+    else:
+        seed_tet, _ = locate_points(mesh, seeds) if len(seeds) else (np.zeros(0, np.int64), None)
+        d_pts, d_tets = t(mesh.points, torch.float64), t(mesh.tets, torch.int32)
+        d_st = t(seed_tet.astype(np.int32), torch.int32)
     d_nbr, d_vel = t(nbr, torch.int32), t(vel, torch.float64)
-    d_seeds, d_st = t(seeds, torch.float64), t(seed_tet.astype(np.int32), torch.int32)
     m = len(seeds)
     pos = torch.empty((m, 3), dtype=torch.float64, device=dev)
     tt = torch.empty(m, dtype=torch.float64, device=dev)
@@ -72,7 +82,8 @@ def run_streamtrace(mesh: TetMesh, velocity, seeds, *, reverse: bool = False, x_
         _lib.check(lib.sns_streamtrace(mesh.num_nodes, mesh.num_tets, p(d_pts), p(d_tets), p(d_nbr), p(d_vel), m,
                                        p(d_seeds), p(d_st), 1 if reverse else 0, t_end, max_step, rtol, atol,
                                        float(x_stop), speed_min, p(pos), p(tt), p(status), p(steps), stream))
-    return dict(pos=pos.cpu().numpy(), t=tt.cpu().numpy(), status=status.cpu().numpy(), steps=steps.cpu().numpy())
+    return dict(pos=pos.cpu().numpy(), t=tt.cpu().numpy(), status=status.cpu().numpy(), steps=steps.cpu().numpy(),
+                seed_tet=d_st.cpu().numpy())
 
 
 def make_rev_streamtrace_seeds(minx, maxx, miny, maxy, numpoints, x_plane: float = 3.9):
