@@ -159,9 +159,6 @@ def load():
     if lib.sns_abi_version() != ABI_VERSION or lib.sns_options_size() != C.sizeof(SnsOptions):
         raise ImportError(f"{LIB_PATH}: ABI {lib.sns_abi_version()} / sizeof(sns_options) {lib.sns_options_size()} does not match "
                           f"this binding ({ABI_VERSION} / {C.sizeof(SnsOptions)}): rebuild the library or update _lib.py")
-    if hasattr(lib, "sns_bench_variants"):           # experiment build only (make HARNESS=1, csrc/sns_harness.h)
-        lib.sns_bench_variants.restype = C.c_int
-        lib.sns_bench_variants.argtypes = [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
     _lib = lib
     return lib
 

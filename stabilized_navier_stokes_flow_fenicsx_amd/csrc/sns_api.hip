@@ -872,55 +872,6 @@ int sns_bench_spmv(sns_handle h, const double* x, double* y, int reps, double* m
     return SNS_OK;
 }
 
-#ifdef SNS_HARNESS
-
-// interleaved A/B micro-benchmark of kernel variants on the assembled level-0 operator (methodology:
-// variants timed alternately in ONE process).  ms_out[v] = average launch ms of variant v.
-//   which 0: fp64 y = Ax, default loads (0) vs non-temporal matrix stream (1, production)
-//   which 3: fp64 y = Ax, production (0: first 16 blocks up-front) vs the stepped loop of round 1 / early round 2 (1)
-//   which 1: low-precision Jacobi sweep, fp16 row-scaled (0) vs fp32 (1) (needs both copies: SNS_BOTH_LP=1)
-SNS_API int sns_bench_variants(sns_handle h, int which, int rounds, int reps, double ms_out[2]) {   // (harness build only: not in sns.h)
-    if (!h || !ms_out || rounds <= 0 || reps <= 0) return SNS_E_ARG;
-    if (!h->has_matrix) { set_error("bench_variants before a matrix was assembled"); return SNS_E_STATE; }
-    Level& L = h->levels[0];
-    const int32_t rows = h->n_owned;
-    double *x, *y, *b;
-    SNS_TRY(get_vec(h, 10, &x)); SNS_TRY(get_vec(h, 11, &y)); SNS_TRY(get_vec(h, 12, &b));
-    hipLaunchKernelGGL(k_fill_pattern, dim3(vec_grid(4 * (int64_t)rows)), dim3(256), 0, h->stream, 4 * (int64_t)rows, x);
-    if (which == 1 && (!L.vals16 || !L.vals32)) { set_error("which 1 needs both the fp16 and the fp32 copy (SNS_BOTH_LP=1)"); return SNS_E_STATE; }
-    const int saved_fmt = h->opt.amg_f32_matrix;
-    double tot[2] = {0, 0};
-    for (int r = 0; r < rounds; ++r)
-        for (int v = 0; v < 2; ++v) {
-            HIP_TRY(hipEventRecord(h->ev0, h->stream));
-            for (int i = 0; i < reps; ++i) {
-                const int grid = (rows + 31) / 32;
-                if (which == 3) {
-                    if (v) hipLaunchKernelGGL((k_spmv<SPMV_AX, 1, 3, 0>), dim3(grid), dim3(256), 0, h->stream, rows, L.rowptr, L.colind, L.vals, x, y, nullptr, L.dinv, 0.0, nullptr, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0);
-                    else hipLaunchKernelGGL((k_spmv<SPMV_AX, 1, 1, 0>), dim3(grid), dim3(256), 0, h->stream, rows, L.rowptr, L.colind, L.vals, x, y, nullptr, L.dinv, 0.0, nullptr, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0);
-                } else if (which == 0) {
-                    if (v) hipLaunchKernelGGL((k_spmv<SPMV_AX, 1, 1, 0>), dim3(grid), dim3(256), 0, h->stream, rows, L.rowptr, L.colind, L.vals, x, y, nullptr, L.dinv, 0.0, nullptr, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0);
-                    else hipLaunchKernelGGL((k_spmv<SPMV_AX, 1, 0, 0>), dim3(grid), dim3(256), 0, h->stream, rows, L.rowptr, L.colind, L.vals, x, y, nullptr, L.dinv, 0.0, nullptr, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0);
-                } else {
-                    h->opt.amg_f32_matrix = v ? 1 : 2;
-                    launch_pc_spmv<SPMV_JACOBI>(h, L, rows, x, y, b, 0.7);
-                }
-            }
-            HIP_TRY(hipEventRecord(h->ev1, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            tot[v] += ms / reps;
-        }
-    h->opt.amg_f32_matrix = saved_fmt;
-    ms_out[0] = tot[0] / rounds;
-    ms_out[1] = tot[1] / rounds;
-    HIP_TRY(hipGetLastError());
-    return SNS_OK;
-}
-
-#endif  // SNS_HARNESS
-
 int sns_bench_assemble(sns_handle h, int form, const double* w, double* F, int reps, double* ms_avg) {
     if (!h || reps <= 0 || !ms_avg) return SNS_E_ARG;
     SNS_TRY(assemble(h, form, w, F, true));

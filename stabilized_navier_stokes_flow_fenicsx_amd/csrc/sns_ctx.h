@@ -13,10 +13,10 @@
 #include <deque>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sns_comm.h"
-#include "sns_harness.h"
 #include "sns_internal.h"
 #include "sns_kernels.h"
 #include "sns_policy.h"
@@ -412,16 +412,6 @@ void launch_spmv(sns_ctx* h, const Level& L, int32_t rows, const double* x, doub
         time_end(h, st);
     } else if (fine) {
         time_begin(h, MODE);
-#ifdef SNS_HARNESS                                     // in-solver A/B of the stepped loop (harness build only)
-        if constexpr (MODE == SPMV_AX || MODE == SPMV_AX_DOT) {
-            if (std::getenv("SNS_FP64_STEPPED")) {
-                hipLaunchKernelGGL((k_spmv<MODE, 1, 3, 0>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, L.vals,
-                                   x, y, b, L.dinv, omega, dotw, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0, GhostSrc());
-                time_end(h);
-                return;
-            }
-        }
-#endif
         hipLaunchKernelGGL((k_spmv<MODE, 1, 1, 0>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, L.vals,
                            x, y, b, L.dinv, omega, dotw, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0, GhostSrc());
         time_end(h);
@@ -432,59 +422,72 @@ void launch_spmv(sns_ctx* h, const Level& L, int32_t rows, const double* x, doub
 }
 
 
+// The format of a level's low-precision copies (amg_f32_matrix: 1 = fp32, 2 = fp16 with row scales; a plan's lp_fmt, a level's
+// binv_fmt) as a compile-time constant.  dispatch: fn(Int<V>()) for the V of Vs equal to v, the last of Vs where none is
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+template <int V, int... Vs, class Fn>
+inline void dispatch(int v, Fn&& fn) {
+    if constexpr (sizeof...(Vs) == 0) fn(Int<V>());
+    else if (v == V) fn(Int<V>());
+    else dispatch<Vs...>(v, fn);
+}
+
+template <class Fn>
+inline void with_fmt(int fmt, Fn&& fn) { dispatch<2, 1>(fmt, fn); }
+
+// a level's matrix copy in format F -- values and row scales (nullptr in fp32) -- and the same of M = A P
+struct LpMat {
+    const void* vals;
+    const float* scale;
+};
+template <int F>
+inline LpMat lp_mat(const Level& L) { return F == 2 ? LpMat{L.vals16, L.scale16} : LpMat{L.vals32, nullptr}; }
+template <int F>
+inline LpMat ap_mat(const Level& L) { return F == 2 ? LpMat{L.ap_vals16, L.ap_scale16} : LpMat{L.ap_vals32, nullptr}; }
+
+
 // Preconditioner passes (Jacobi sweep, residual) of the AMG cycle on the low-precision copy of the level matrix
-// (amg_f32_matrix: 1 = fp32, 2 = fp16 with row scales).
 template <int MODE, int FINE, int SPLIT, int FMT>
 void launch_lp(sns_ctx* h, const Level& L, int32_t rows, hipStream_t st, const double* x, double* y, const double* b,
                double omega, const GhostSrc& gs = GhostSrc()) {
     const int grid = (rows + 63) / 64;
     if (grid == 0) return;
-    const void* vals = FMT == 2 ? (const void*)L.vals16 : (const void*)L.vals32;
-#ifdef SNS_HARNESS                                         // in-solver A/B of the stepped loop (harness build only)
-    if constexpr (FMT == 2 && FINE == 1 && SPLIT == 0) {
-        if (std::getenv("SNS_LP_STEPPED")) {
-            hipLaunchKernelGGL((k_spmv_lp<MODE, 1, 0, 2, 0>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, vals,
-                               L.scale16, x, y, b, L.dinv32, omega, (const int32_t*)nullptr, (const uint8_t*)nullptr, GhostSrc());
-            return;
-        }
-    }
-#endif
-    hipLaunchKernelGGL((k_spmv_lp<MODE, FINE, SPLIT, FMT, 1>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, vals,
-                       L.scale16, x, y, b, L.dinv32, omega, SPLIT == 2 ? h->bnd_rows : (const int32_t*)nullptr,
+    hipLaunchKernelGGL((k_spmv_lp<MODE, FINE, SPLIT, FMT, 1>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind,
+                       lp_mat<FMT>(L).vals, L.scale16, x, y, b, L.dinv32, omega, SPLIT == 2 ? h->bnd_rows : (const int32_t*)nullptr,
                        SPLIT == 1 ? h->bnd_flag : (const uint8_t*)nullptr, gs);
 }
 
-template <int MODE, int FMT>
-void launch_lp_fmt(sns_ctx* h, const Level& L, int32_t rows, const double* x, double* y, const double* b, double omega,
-                   Split sp) {
-    hipStream_t st = sp.stream ? sp.stream : h->stream;
-    const bool fine = (&L == &h->levels[0]);
-    if (fine && sp.mode == 1) {
-        time_begin(h, MODE, st);
-        launch_lp<MODE, 1, 1, FMT>(h, L, rows, st, x, y, b, omega);
-        time_end(h, st);
-    } else if (fine && sp.mode == 2) {
-        launch_lp<MODE, 1, 2, FMT>(h, L, h->n_bnd, st, x, y, b, omega);
-    } else if (fine && sp.mode == 3) {
-        time_begin(h, MODE, st);
-        launch_lp<MODE, 1, 3, FMT>(h, L, rows, st, x, y, b, omega, sp.gs);
-        time_end(h, st);
-    } else if (fine) {
-        time_begin(h, MODE);
-        launch_lp<MODE, 1, 0, FMT>(h, L, rows, st, x, y, b, omega);
-        time_end(h);
-    } else {
-        launch_lp<MODE, 0, 0, FMT>(h, L, rows, st, x, y, b, omega);
-    }
-}
-
-// (fmt: the level's plan, lp_fmt)
+// (fmt: the level's plan, lp_fmt; 0 = the fp64 operator)
 template <int MODE>
 void launch_pc_spmv(sns_ctx* h, const Level& L, int fmt, int32_t rows, const double* x, double* y, const double* b,
                     double omega, Split sp = Split()) {
-    if (fmt == 2) launch_lp_fmt<MODE, 2>(h, L, rows, x, y, b, omega, sp);
-    else if (fmt == 1) launch_lp_fmt<MODE, 1>(h, L, rows, x, y, b, omega, sp);
-    else launch_spmv<MODE>(h, L, rows, x, y, b, omega, nullptr, sp);
+    if (fmt == 0) {
+        launch_spmv<MODE>(h, L, rows, x, y, b, omega, nullptr, sp);
+        return;
+    }
+    hipStream_t st = sp.stream ? sp.stream : h->stream;
+    const bool fine = (&L == &h->levels[0]);
+    with_fmt(fmt, [&](auto F) {
+        if (fine && sp.mode == 1) {
+            time_begin(h, MODE, st);
+            launch_lp<MODE, 1, 1, F>(h, L, rows, st, x, y, b, omega);
+            time_end(h, st);
+        } else if (fine && sp.mode == 2) {
+            launch_lp<MODE, 1, 2, F>(h, L, h->n_bnd, st, x, y, b, omega);
+        } else if (fine && sp.mode == 3) {
+            time_begin(h, MODE, st);
+            launch_lp<MODE, 1, 3, F>(h, L, rows, st, x, y, b, omega, sp.gs);
+            time_end(h, st);
+        } else if (fine) {
+            time_begin(h, MODE);
+            launch_lp<MODE, 1, 0, F>(h, L, rows, st, x, y, b, omega);
+            time_end(h);
+        } else {
+            launch_lp<MODE, 0, 0, F>(h, L, rows, st, x, y, b, omega);
+        }
+    });
 }
 
 
@@ -564,22 +567,24 @@ int exchange_and_spmv(sns_ctx* h, double* xe, const double* x, double* y, const 
 
 
 // one smoothing sweep y = x + w S (b - A x) of a level: S = the aggregates' inverse blocks where its plan has blocks, else the
-// nodal D^-1
+// nodal D^-1.  gs: the ghost entries of x come from this receive window (the window form of the cycle; blocks only); pd: the put
+// the sweep carries
 inline void launch_sweep(sns_ctx* h, const policy::LevelPlan& P, const Level& L, int32_t rows, const double* x, double* y,
-                         const double* b, double omega) {
-    if (P.blocks) {
-        const int32_t ns = 8 * L.n_blk;
-        const unsigned grid = (unsigned)((ns + 63) / 64);
-        if (grid == 0) return;
-        if (L.binv_fmt == 2)
-            hipLaunchKernelGGL((k_bsweep<2, 0>), dim3(grid), dim3(256), 0, h->stream, ns, L.blk_rows, L.rowptr, L.colind,
-                               (const void*)L.vals16, L.scale16, (const void*)L.binv32, x, y, b, omega, GhostSrc(), PutDst());
-        else
-            hipLaunchKernelGGL((k_bsweep<1, 0>), dim3(grid), dim3(256), 0, h->stream, ns, L.blk_rows, L.rowptr, L.colind,
-                               (const void*)L.vals32, (const float*)nullptr, (const void*)L.binv32, x, y, b, omega, GhostSrc(), PutDst());
+                         const double* b, double omega, const GhostSrc* gs = nullptr, const PutDst& pd = PutDst()) {
+    if (!P.blocks) {
+        launch_pc_spmv<SPMV_JACOBI>(h, L, P.lp_fmt, rows, x, y, b, omega);
         return;
     }
-    launch_pc_spmv<SPMV_JACOBI>(h, L, P.lp_fmt, rows, x, y, b, omega);
+    const int32_t ns = 8 * L.n_blk;
+    const unsigned grid = (unsigned)((ns + 63) / 64);
+    if (grid == 0) return;
+    with_fmt(L.binv_fmt, [&](auto F) {
+        dispatch<1, 0>(gs != nullptr, [&](auto G) {
+            const LpMat A = lp_mat<F>(L);
+            hipLaunchKernelGGL((k_bsweep<F, G>), dim3(grid), dim3(256), 0, h->stream, ns, L.blk_rows, L.rowptr, L.colind, A.vals,
+                               A.scale, (const void*)L.binv32, x, y, b, omega, gs ? *gs : GhostSrc(), pd);
+        });
+    });
 }
 
 // first sweep of a cycle from the zero guess, z = w S b (omega = 1: S b alone, the spectral estimate's operator)
@@ -589,31 +594,15 @@ inline void launch_first_sweep(sns_ctx* h, const policy::LevelPlan& P, const Lev
     const int g4 = (int)((4 * (int64_t)rows + 255) / 256);
     if (P.blocks) {
         const int32_t ns = 8 * L.n_blk;
-        if (L.binv_fmt == 2)
-            hipLaunchKernelGGL((k_bfirst<2>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L.blk_rows,
+        with_fmt(L.binv_fmt, [&](auto F) {
+            hipLaunchKernelGGL((k_bfirst<F>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L.blk_rows,
                                (const void*)L.binv32, b, omega, z, pd ? *pd : PutDst());
-        else
-            hipLaunchKernelGGL((k_bfirst<1>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L.blk_rows,
-                               (const void*)L.binv32, b, omega, z, pd ? *pd : PutDst());
+        });
         return;
     }
     if (pd) *pd = PutDst();                              // (the nodal first sweeps do not carry a put)
     if (P.lp_fmt != 0) hipLaunchKernelGGL(k_bjacobi32, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv32, b, omega, z);
     else hipLaunchKernelGGL(k_bjacobi, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv, b, omega, z);
-}
-
-// one aggregate-block sweep of a partitioned level with the ghost entries of x from the level's receive window
-inline void launch_sweep_windows(sns_ctx* h, const Level& L, const double* x, double* y, const double* b, double omega, const GhostSrc& gs,
-                                 const PutDst& pd = PutDst()) {
-    const int32_t ns = 8 * L.n_blk;
-    const unsigned grid = (unsigned)((ns + 63) / 64);
-    if (grid == 0) return;
-    if (L.binv_fmt == 2)
-        hipLaunchKernelGGL((k_bsweep<2, 1>), dim3(grid), dim3(256), 0, h->stream, ns, L.blk_rows, L.rowptr, L.colind,
-                           (const void*)L.vals16, L.scale16, (const void*)L.binv32, x, y, b, omega, gs, pd);
-    else
-        hipLaunchKernelGGL((k_bsweep<1, 1>), dim3(grid), dim3(256), 0, h->stream, ns, L.blk_rows, L.rowptr, L.colind,
-                           (const void*)L.vals32, (const float*)nullptr, (const void*)L.binv32, x, y, b, omega, gs, pd);
 }
 
 

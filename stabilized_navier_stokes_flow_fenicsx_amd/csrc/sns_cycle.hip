@@ -49,6 +49,83 @@ int coarse_cycle(sns_ctx* h, int l, const double* b, double* x) {
 }
 
 
+// ---- the stages both forms of the cycle launch ----------------------------------------------------------------------------------
+
+// Restriction of level l's residual into the coarse right-hand side cb, with the coarse level's first sweep (into the buffer its
+// cycle starts from) where the plan fuses it.  fused: the residual b - A x is computed in the same launch (k_resid_restrict), else
+// L.r holds it (k_restrict_blk onto the coarse level's aggregate blocks, k_restrict).  gs: the ghost entries of x from this receive
+// window (the window form); agp / pd: the all-gather piece / the put the launch carries
+static void launch_restrict(sns_ctx* h, int l, bool fused, const double* x, const double* b, double* cb, const GhostSrc* gs = nullptr,
+                            const AgPut& agp = AgPut(), const PutDst& pd = PutDst()) {
+    const Level& L = h->levels[l];
+    const Level& C = h->levels[l + 1];
+    const policy::LevelPlan& Q = h->plan.level[(size_t)l];
+    const policy::LevelPlan& QC = h->plan.level[(size_t)l + 1];
+    const bool fuse = Q.fuses_next_first != 0;
+    const float* dc = fuse ? C.dinv32 : nullptr;
+    double* zc = !fuse ? nullptr : QC.start_odd ? h->pong[l + 1] : C.x;   // (the coarse cycle is called with x = C.x)
+    if (fused) {
+        // mode of the coarse level's first sweep: 0 none, 1 nodal D^-1, 2 its aggregate blocks (walked in THEIR order)
+        const int mode = !fuse ? 0 : (QC.blocks ? 2 : 1);
+        const int32_t* slots = mode == 2 ? C.blk_rows : nullptr;
+        const int32_t n_slots = mode == 2 ? 8 * C.n_blk : C.n_owned;
+        const unsigned grid = (unsigned)((n_slots + 7) / 8);
+        if (l == 0) time_begin(h, SPMV_B_MINUS_AX);                      // (bench.py's per-launch accounting of the fine-level passes)
+        with_fmt(Q.lp_fmt, [&](auto F) {
+            dispatch<2, 1, 0>(mode, [&](auto M) {
+                dispatch<1, 0>(gs != nullptr, [&](auto G) {
+                    const LpMat A = lp_mat<F>(L);
+                    hipLaunchKernelGGL((k_resid_restrict<F, M, G>), dim3(grid), dim3(256), 0, h->stream, C.n_owned, n_slots, slots,
+                                       L.m_ptr, L.m_idx, L.free_mask, L.rowptr, L.colind, A.vals, A.scale, x, b, L.r, cb, dc,
+                                       (const void*)C.binv32, C.omega, zc, gs ? *gs : GhostSrc(), agp, pd);
+                });
+            });
+        });
+        if (l == 0) time_end(h);
+    } else if (fuse && QC.blocks) {
+        const int32_t ns = 8 * C.n_blk;
+        with_fmt(C.binv_fmt, [&](auto F) {
+            hipLaunchKernelGGL((k_restrict_blk<F>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows, L.m_ptr,
+                               L.m_idx, L.free_mask, L.r, cb, (const void*)C.binv32, C.omega, zc, pd);
+        });
+    } else {
+        hipLaunchKernelGGL(k_restrict, dim3((unsigned)((4 * (int64_t)C.n_owned + 255) / 256)), dim3(256), 0, h->stream,
+                           C.n_owned, L.m_ptr, L.m_idx, L.free_mask, L.r, cb, dc, C.omega, zc);
+    }
+}
+
+// Fused coarse-grid correction + first post-smoothing sweep of level l over M = A P: y = (x + P xc) + w S (r - M xc), r the
+// residual restricted before (k_bpost on the aggregate blocks, else k_post_lp).  xc_own: this rank's rows of the coarse solution,
+// apc: M's column ids, gc: the window form's source of the ghost aggregates' part of xc (k_bpost reads it where it has a window), pd:
+// the put the launch carries.  Level 0 is timed as mode 4
+static void launch_post(sns_ctx* h, int l, const double* xc, const double* xc_own, const int32_t* apc, const double* x, double* y,
+                        const GhostSrc* gc = nullptr, const PutDst& pd = PutDst()) {
+    const Level& L = h->levels[l];
+    const policy::LevelPlan& Q = h->plan.level[(size_t)l];
+    const int32_t rows = L.n_owned;
+    const GhostSrc g = gc ? *gc : GhostSrc();
+    if (l == 0) time_begin(h, 4);
+    with_fmt(Q.lp_fmt, [&](auto F) {
+        const LpMat M = ap_mat<F>(L);
+        if (Q.blocks) {
+            const int32_t ns = 8 * L.n_blk;
+            dispatch<1, 0>(g.win[0] != nullptr, [&](auto G) {
+                hipLaunchKernelGGL((k_bpost<F, G>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L.blk_rows,
+                                   L.ap_rowptr, apc, M.vals, M.scale, (const void*)L.binv32, xc, xc_own, x, (const double*)L.r,
+                                   L.omega, L.agg, L.free_mask, y, g, pd);
+            });
+        } else {
+            // (nodal blocks: FINE 1 the fine level, 0 a coarse one, 2 the fine level of the window form)
+            dispatch<2, 1, 0>(gc ? 2 : l == 0 ? 1 : 0, [&](auto FINE) {
+                hipLaunchKernelGGL((k_post_lp<F, FINE>), dim3((rows + 63) / 64), dim3(256), 0, h->stream, rows, L.ap_rowptr, apc,
+                                   M.vals, M.scale, xc, x, (const double*)L.r, L.dinv32, L.omega, L.agg, L.free_mask, y, g);
+            });
+        }
+    });
+    if (l == 0) time_end(h);
+}
+
+
 // The V-cycle of a PARTITIONED level over a window transport (peer windows / the in-process team; round 5).  Every exchange is one
 // put launch (comm_put) and the pass behind it reads the ghost entries from the level's receive window, its boundary waves waiting
 // for the neighbours themselves: no staging copy, no unpack, no split pass.  Level 0: first sweep | put, residual | restriction
@@ -72,6 +149,7 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     // aggregate-block kernel: `carried` says whether the vector about to be exchanged has been put already
     const bool blk = Q.blocks != 0;
     const PutDst pdl = (h->plan.fuse_puts && blk && rows > 0) ? comm_put_dst(c, P) : PutDst();
+    const GhostSrc gs = comm_ghost_src(c, P);
     bool carried = false;
     if (l == 0 && h->first_sweep_done) carried = h->first_put_carried;
     else if (l > 0 && h->plan.level[(size_t)l - 1].fuses_next_first) carried = h->child_put_carried;
@@ -90,7 +168,7 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
         SNS_TRY(put(P, cur, carried));
         carried = false;
         if (rows > 0 && blk) {
-            launch_sweep_windows(h, L, cur, oth, b, om, comm_ghost_src(c, P), pdl);
+            launch_sweep(h, Q, L, rows, cur, oth, b, om, &gs, pdl);
             carried = pdl.sr_ptr != nullptr;
         }
         std::swap(cur, oth);
@@ -99,13 +177,9 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     double* cb = rep_src ? h->rep_bsend : C.b;
     const double* cx = rep_src ? h->levels[h->rep_level].x + 4 * (size_t)h->rep_off : C.x;
     const bool fuse = Q.fuses_next_first != 0;
-    const float* dc = fuse ? C.dinv32 : nullptr;
-    double* zc = !fuse ? nullptr : QC.start_odd ? h->pong[l + 1] : C.x;
-    const int fmt = Q.lp_fmt;
     // residual (+ restriction): the true residual needs the neighbours' iterate
     SNS_TRY(put(P, cur, carried));
     carried = false;
-    const GhostSrc gs = comm_ghost_src(c, P);
     // (the next level's first sweep, written by the restriction, is exchanged first thing in its cycle: put from here)
     const PutDst pdc = (h->plan.fuse_puts && fuse && QC.blocks && !rep_src && QC.windows && C.n_owned > 0 &&
                         (l == 0 || rows > 0))
@@ -115,37 +189,13 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
         Split s3;
         s3.mode = 3;
         s3.gs = gs;
-        if (rows > 0) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, fmt, rows, cur, L.r, b, 0.0, s3);
-        if (C.n_owned > 0) {
-            if (fuse && QC.blocks) {
-                const int32_t ns = 8 * C.n_blk;
-                if (C.binv_fmt == 2)
-                    hipLaunchKernelGGL((k_restrict_blk<2>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
-                                       L.m_ptr, L.m_idx, L.free_mask, L.r, cb, (const void*)C.binv32, C.omega, zc, pdc);
-                else
-                    hipLaunchKernelGGL((k_restrict_blk<1>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
-                                       L.m_ptr, L.m_idx, L.free_mask, L.r, cb, (const void*)C.binv32, C.omega, zc, pdc);
-            } else {
-                hipLaunchKernelGGL(k_restrict, dim3((unsigned)((4 * (int64_t)C.n_owned + 255) / 256)), dim3(256), 0, h->stream,
-                                   C.n_owned, L.m_ptr, L.m_idx, L.free_mask, L.r, cb, dc, C.omega, zc);
-            }
-        }
+        if (rows > 0) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, Q.lp_fmt, rows, cur, L.r, b, 0.0, s3);
+        if (C.n_owned > 0) launch_restrict(h, l, false, nullptr, nullptr, cb, nullptr, AgPut(), pdc);
     } else if (rows > 0 && C.n_owned > 0) {
         // (the level below is the source of the replicated tail: the restricted right-hand side goes straight into every rank's
         // all-gather staging area, the tail's first sweep waits for it -- rep_gather_first)
         const AgPut agp = (rep_src && h->plan.rep_gather_first) ? comm_ag_put(c, 4 * (int64_t)h->rep_maxn) : AgPut();
-        const int mode = !fuse ? 0 : (QC.blocks ? 2 : 1);
-        const int32_t* slots = mode == 2 ? C.blk_rows : nullptr;
-        const int32_t n_slots = mode == 2 ? 8 * C.n_blk : C.n_owned;
-        const unsigned grid = (unsigned)((n_slots + 7) / 8);
-        const void* vals = fmt == 2 ? (const void*)L.vals16 : (const void*)L.vals32;
-        const float* sc16 = fmt == 2 ? L.scale16 : nullptr;
-#define SNS_RRW(F, M)                                                                                                              \
-    hipLaunchKernelGGL((k_resid_restrict<F, M, 1>), dim3(grid), dim3(256), 0, h->stream, C.n_owned, n_slots, slots, L.m_ptr, L.m_idx, \
-                       L.free_mask, L.rowptr, L.colind, vals, sc16, (const double*)cur, b, L.r, cb, dc, (const void*)C.binv32, C.omega, zc, gs, agp, pdc)
-        if (fmt == 2) { if (mode == 2) SNS_RRW(2, 2); else if (mode == 1) SNS_RRW(2, 1); else SNS_RRW(2, 0); }
-        else          { if (mode == 2) SNS_RRW(1, 2); else if (mode == 1) SNS_RRW(1, 1); else SNS_RRW(1, 0); }
-#undef SNS_RRW
+        launch_restrict(h, l, true, cur, b, cb, &gs, agp, pdc);
     }
     SNS_TRY(coarse_cycle(h, l + 1, cb, rep_src ? nullptr : C.x));
     // fused coarse-grid correction + first post-smoothing sweep over M = A P; the ghost aggregates' part of the coarse solution:
@@ -165,41 +215,19 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     // this level's result is exchanged next by the level above (its correction reads it) or, the fine level's, by the operator
     // application the caller of pc_apply has promised: the last kernel of the cycle puts it
     const bool last_puts = pdl.sr_ptr && (l == 0 ? h->pc_then_op : h->plan.level[(size_t)l - 1].windows != 0);
-    if (rows > 0) {
-        if (l == 0) time_begin(h, 4);
-        if (blk) {
-            const int32_t ns = 8 * L.n_blk;
-            const unsigned gb = (unsigned)((ns + 63) / 64);
-            const void* mv = fmt == 2 ? (const void*)L.ap_vals16 : (const void*)L.ap_vals32;
-            const float* ms = fmt == 2 ? L.ap_scale16 : nullptr;
-#define SNS_BPW(F, G)                                                                                                          \
-    hipLaunchKernelGGL((k_bpost<F, G>), dim3(gb), dim3(256), 0, h->stream, ns, L.blk_rows, L.ap_rowptr, apc, mv, ms,             \
-                       (const void*)L.binv32, xc, cx, (const double*)cur, (const double*)L.r, om, L.agg, L.free_mask, oth, gc,                   \
-                       (nu_post > 1 || last_puts) ? pdl : PutDst())
-            carried = (nu_post > 1 || last_puts) && pdl.sr_ptr != nullptr;
-            if (gc.win[0]) { if (fmt == 2) SNS_BPW(2, 1); else SNS_BPW(1, 1); }
-            else           { if (fmt == 2) SNS_BPW(2, 0); else SNS_BPW(1, 0); }
-#undef SNS_BPW
-        } else {
-            const int grid = (rows + 63) / 64;             // (nodal blocks: the fine level only, see the plan's exact)
-            if (fmt == 2)
-                hipLaunchKernelGGL((k_post_lp<2, 2>), dim3(grid), dim3(256), 0, h->stream, rows, L.ap_rowptr, L.ap_colind, L.ap_vals16,
-                                   L.ap_scale16, xc, (const double*)cur, (const double*)L.r, L.dinv32, om, L.agg, L.free_mask, oth, gc);
-            else
-                hipLaunchKernelGGL((k_post_lp<1, 2>), dim3(grid), dim3(256), 0, h->stream, rows, L.ap_rowptr, L.ap_colind,
-                                   (const void*)L.ap_vals32, (const float*)nullptr, xc, (const double*)cur, (const double*)L.r, L.dinv32,
-                                   om, L.agg, L.free_mask, oth, gc);
-        }
-        if (l == 0) time_end(h);
+    if (rows > 0) {                                        // (nodal blocks: the fine level only, see the plan's exact)
+        const PutDst pd = (nu_post > 1 || last_puts) ? pdl : PutDst();
+        launch_post(h, l, xc, cx, apc, cur, oth, &gc, pd);
+        carried = pd.sr_ptr != nullptr;
     }
     std::swap(cur, oth);
     for (int s = 1; s < nu_post; ++s) {
         SNS_TRY(put(P, cur, carried));
         carried = false;
         if (rows > 0 && blk) {
-            const bool more = s + 1 < nu_post || last_puts;
-            launch_sweep_windows(h, L, cur, oth, b, om, comm_ghost_src(c, P), more ? pdl : PutDst());
-            carried = more && pdl.sr_ptr != nullptr;
+            const PutDst pd = (s + 1 < nu_post || last_puts) ? pdl : PutDst();
+            launch_sweep(h, Q, L, rows, cur, oth, b, om, &gs, pd);
+            carried = pd.sr_ptr != nullptr;
         }
         std::swap(cur, oth);
     }
@@ -209,84 +237,91 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
 }
 
 
-// V-cycle on level l: x <- approx A_l^-1 b  (x overwritten; zero initial guess)
-int vcycle(sns_ctx* h, int l, const double* b, double* x) {
+// The level above the replicated tail (l = rep_level - 1): all-gather the right-hand side, cycle the replicated tail, keep my rows
+// of the result
+static int enter_replicated_tail(sns_ctx* h, int l, const double* b, double* x) {
+    const int32_t rows = h->levels[l].n_owned;
+    Level& C = h->levels[h->rep_level];
+    if (rows > 0 && b != h->rep_bsend)                   // (vcycle of the level above restricts straight into rep_bsend)
+        HIP_TRY(hipMemcpyAsync(h->rep_bsend, b, 4 * (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    Comm* cm = h->comm.get();
+    if (h->plan.rep_gather_first) {
+        // both halves of the all-gather ride in solver kernels: the residual + restriction of the level above has stored this
+        // rank's piece into every rank's staging area, the first sweep of the replicated level waits for the pieces itself
+        SNS_TRY(peer_check(cm));
+        SNS_TRY(comm_host_barrier(cm, h->stream));
+        const int32_t ns = 8 * C.n_blk;
+        double* zc = h->plan.level[(size_t)h->rep_level].start_odd ? h->pong[h->rep_level] : C.x;
+        with_fmt(C.binv_fmt, [&](auto F) {
+            hipLaunchKernelGGL((k_bfirst_gather<F>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
+                               (const void*)C.binv32, C.omega, zc, C.b, h->rep_rowmap, comm_ag_get(cm));
+        });
+    } else if (cm->windows() && h->opt.halo_windows && h->rep_doff &&
+        (size_t)4 * h->rep_maxn * (size_t)cm->nranks <= cm->peer->ag_doubles) {
+        // (every rank's rows land where the replicated level keeps them: no gather kernel behind the all-gather)
+        SNS_TRY(comm_allgatherv(cm, h->rep_bsend, C.b, 4 * h->rep_maxn, h->rep_doff, h->rep_dcnt, h->stream));
+    } else {
+        SNS_TRY(comm_allgather(cm, h->rep_bsend, h->rep_brecv, 4 * h->rep_maxn, h->stream));
+        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((4 * (int64_t)h->rep_NG + 255) / 256)), dim3(256), 0, h->stream,
+                           h->rep_NG, h->rep_rowmap, h->rep_brecv, C.b);
+    }
+    SNS_TRY(coarse_cycle(h, h->rep_level, C.b, C.x));
+    if (rows > 0 && x)                                   // (x == nullptr: the caller reads its rows of C.x in place)
+        HIP_TRY(hipMemcpyAsync(x, C.x + 4 * (size_t)h->rep_off, 4 * (size_t)rows * sizeof(double),
+                               hipMemcpyDeviceToDevice, h->stream));
+    return SNS_OK;
+}
+
+// The last level: the all-gathered global dense inverse, the dense inverse, its fp32 copy from the blocked Gauss-Jordan
+// elimination, or -- too large for a dense solve -- a fixed number of Jacobi sweeps (still a linear operator)
+static int solve_last_level(sns_ctx* h, int l, const double* b, double* x) {
     Level& L = h->levels[l];
     const int32_t rows = L.n_owned;
-    const bool last = (l + 1 == (int)h->levels.size());
-    const double om = L.omega;
-    const int g4 = (int)((4 * (int64_t)rows + 255) / 256);
+    if (h->cg_N > 0) {
+        const int N = h->cg_N, mr = 4 * h->cg_maxn;
+        HIP_TRY(hipMemsetAsync(h->cg_send, 0, mr * sizeof(double), h->stream));
+        if (rows > 0)
+            HIP_TRY(hipMemcpyAsync(h->cg_send, b, 4 * (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice,
+                                   h->stream));
+        SNS_TRY(comm_allgather(h->comm.get(), h->cg_send, h->cg_recv, mr, h->stream));
+        if (rows > 0)
+            hipLaunchKernelGGL(k_dense_matvec, dim3((4 * rows + 3) / 4), dim3(256), 0, h->stream, N,
+                               h->cg_full + (size_t)h->comm->rank * mr * N, h->cg_recv, x, 4 * rows);
+        return SNS_OK;
+    }
+    if (L.dense_inv) {
+        const int N = 4 * L.n;
+        hipLaunchKernelGGL(k_dense_matvec, dim3((N + 3) / 4), dim3(256), 0, h->stream, N, L.dense_inv, b, x, N);
+        return SNS_OK;
+    }
+    if (L.dense_x32) {
+        const int N = 4 * L.n;
+        hipLaunchKernelGGL(k_dense_matvec32, dim3((N + 3) / 4), dim3(256), 0, h->stream, N, L.dense_np, L.dense_x32, b, x);
+        return SNS_OK;
+    }
+    double* cur = x;
+    double* oth = h->pong[l];
+    if (rows == 0) return SNS_OK;
+    hipLaunchKernelGGL(k_bjacobi, dim3((unsigned)((4 * (int64_t)rows + 255) / 256)), dim3(256), 0, h->stream, rows, L.dinv, b,
+                       L.omega, cur);
+    for (int s = 0; s < 8; ++s) {       // even count: result ends in x
+        launch_pc_spmv<SPMV_JACOBI>(h, L, h->plan.level[(size_t)l].lp_fmt, rows, cur, oth, b, L.omega);
+        std::swap(cur, oth);
+    }
+    return SNS_OK;
+}
+
+
+// V-cycle on level l: x <- approx A_l^-1 b  (x overwritten; zero initial guess)
+int vcycle(sns_ctx* h, int l, const double* b, double* x) {
+    if (h->rep_level > 0 && l == h->rep_level - 1) return enter_replicated_tail(h, l, b, x);
+    if (l + 1 == (int)h->levels.size()) return solve_last_level(h, l, b, x);
     const policy::LevelPlan& Q = h->plan.level[(size_t)l];
-    if (h->rep_level > 0 && l == h->rep_level - 1) {
-        // all-gather the right-hand side, cycle the replicated tail, keep my rows of the result
-        Level& C = h->levels[h->rep_level];
-        if (rows > 0 && b != h->rep_bsend)                   // (vcycle of the level above restricts straight into rep_bsend)
-            HIP_TRY(hipMemcpyAsync(h->rep_bsend, b, 4 * (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        Comm* cm = h->comm.get();
-        if (h->plan.rep_gather_first) {
-            // both halves of the all-gather ride in solver kernels: the residual + restriction of the level above has stored this
-            // rank's piece into every rank's staging area, the first sweep of the replicated level waits for the pieces itself
-            SNS_TRY(peer_check(cm));
-            SNS_TRY(comm_host_barrier(cm, h->stream));
-            const int32_t ns = 8 * C.n_blk;
-            double* zc = h->plan.level[(size_t)h->rep_level].start_odd ? h->pong[h->rep_level] : C.x;
-            if (C.binv_fmt == 2)
-                hipLaunchKernelGGL((k_bfirst_gather<2>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
-                                   (const void*)C.binv32, C.omega, zc, C.b, h->rep_rowmap, comm_ag_get(cm));
-            else
-                hipLaunchKernelGGL((k_bfirst_gather<1>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
-                                   (const void*)C.binv32, C.omega, zc, C.b, h->rep_rowmap, comm_ag_get(cm));
-        } else if (cm->windows() && h->opt.halo_windows && h->rep_doff &&
-            (size_t)4 * h->rep_maxn * (size_t)cm->nranks <= cm->peer->ag_doubles) {
-            // (every rank's rows land where the replicated level keeps them: no gather kernel behind the all-gather)
-            SNS_TRY(comm_allgatherv(cm, h->rep_bsend, C.b, 4 * h->rep_maxn, h->rep_doff, h->rep_dcnt, h->stream));
-        } else {
-            SNS_TRY(comm_allgather(cm, h->rep_bsend, h->rep_brecv, 4 * h->rep_maxn, h->stream));
-            hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((4 * (int64_t)h->rep_NG + 255) / 256)), dim3(256), 0, h->stream,
-                               h->rep_NG, h->rep_rowmap, h->rep_brecv, C.b);
-        }
-        SNS_TRY(coarse_cycle(h, h->rep_level, C.b, C.x));
-        if (rows > 0 && x)                                   // (x == nullptr: the caller reads its rows of C.x in place)
-            HIP_TRY(hipMemcpyAsync(x, C.x + 4 * (size_t)h->rep_off, 4 * (size_t)rows * sizeof(double),
-                                   hipMemcpyDeviceToDevice, h->stream));
-        return SNS_OK;
-    }
-    if (last) {
-        if (h->cg_N > 0) {
-            const int N = h->cg_N, mr = 4 * h->cg_maxn;
-            HIP_TRY(hipMemsetAsync(h->cg_send, 0, mr * sizeof(double), h->stream));
-            if (rows > 0)
-                HIP_TRY(hipMemcpyAsync(h->cg_send, b, 4 * (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice,
-                                       h->stream));
-            SNS_TRY(comm_allgather(h->comm.get(), h->cg_send, h->cg_recv, mr, h->stream));
-            if (rows > 0)
-                hipLaunchKernelGGL(k_dense_matvec, dim3((4 * rows + 3) / 4), dim3(256), 0, h->stream, N,
-                                   h->cg_full + (size_t)h->comm->rank * mr * N, h->cg_recv, x, 4 * rows);
-            return SNS_OK;
-        }
-        if (L.dense_inv) {
-            const int N = 4 * L.n;
-            hipLaunchKernelGGL(k_dense_matvec, dim3((N + 3) / 4), dim3(256), 0, h->stream, N, L.dense_inv, b, x, N);
-            return SNS_OK;
-        }
-        if (L.dense_x32) {
-            const int N = 4 * L.n;
-            hipLaunchKernelGGL(k_dense_matvec32, dim3((N + 3) / 4), dim3(256), 0, h->stream, N, L.dense_np, L.dense_x32, b, x);
-            return SNS_OK;
-        }
-        // coarsest level too large for the dense solve: a fixed number of Jacobi sweeps (still a linear operator)
-        double* cur = x;
-        double* oth = h->pong[l];
-        if (rows == 0) return SNS_OK;
-        hipLaunchKernelGGL(k_bjacobi, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv, b, om, cur);
-        for (int s = 0; s < 8; ++s) {       // even count: result ends in x
-            launch_pc_spmv<SPMV_JACOBI>(h, L, Q.lp_fmt, rows, cur, oth, b, om);
-            std::swap(cur, oth);
-        }
-        return SNS_OK;
-    }
     if (Q.windows) return vcycle_windows(h, l, b, x);
-    const policy::LevelPlan& QC = h->plan.level[(size_t)l + 1];
+    Level& L = h->levels[l];
+    Level& C = h->levels[l + 1];
+    const int32_t rows = L.n_owned;
+    const double om = L.omega;
     const int nu = Q.nu, nu_pre = Q.pre, nu_post = Q.post;
     double* cur = Q.start_odd ? h->pong[l] : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
     double* oth = (cur == x) ? h->pong[l] : x;
@@ -313,16 +348,14 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
         launch_sweep(h, Q, L, rows, cur, oth, b, om);
         std::swap(cur, oth);
     }
-    Level& C = h->levels[l + 1];
     // Below the fine level the residual and the restriction (+ the next level's first sweep) are ONE launch (k_resid_restrict):
     // `xres` is then the vector the residual reads and the pass itself is issued with the restriction further down.
     // (amg_fuse_restrict = 2: a single-GPU fine level as well -- its residual kernel is the tuned k_spmv_lp, kept by default)
-    const int fmt_rr = Q.lp_fmt;
     const bool rr_fused = Q.fused_restrict && rows > 0 && C.n_owned > 0;
     const double* xres = cur;
     if (sx) {
         SNS_TRY(exchange_level(h, l, cur));
-        if (!rr_fused) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, fmt_rr, rows, cur, L.r, b, 0.0);
+        if (!rr_fused) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, Q.lp_fmt, rows, cur, L.r, b, 0.0);
     } else if (L.xg && tails_unused) {
         // (fine level, fused post-sweep: the halo lands in the iterate's own ghost tail, no copy into the exchange vector)
         SNS_TRY(exchange_and_spmv<SPMV_B_MINUS_AX>(h, cur, cur, L.r, b, 0.0, nullptr, true));
@@ -333,54 +366,17 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
         } else {
             SNS_TRY(exchange_level(h, l, L.xg));
             xres = L.xg;
-            if (!rr_fused) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, fmt_rr, rows, L.xg, L.r, b, 0.0);
+            if (!rr_fused) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, Q.lp_fmt, rows, L.xg, L.r, b, 0.0);
         }
     } else if (!rr_fused) {
-        launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, fmt_rr, rows, cur, L.r, b, 0.0);
+        launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, Q.lp_fmt, rows, cur, L.r, b, 0.0);
     }
     // the level below is only the source of the replicated tail: its right-hand side is restricted straight into the all-gather's
     // send buffer, and the correction is prolongated straight from this rank's rows of the replicated solution (no copies)
     const bool rep_src = h->rep_level > 0 && l + 1 == h->rep_level - 1;
     double* cb = rep_src ? h->rep_bsend : C.b;
     const double* cx = rep_src ? h->levels[h->rep_level].x + 4 * (size_t)h->rep_off : C.x;
-    if (C.n_owned > 0) {
-        // the restriction also does the next level's first sweep (z = w Dc^-1 bc into the buffer that level starts from)
-        const float* dc = nullptr;
-        double* zc = nullptr;
-        const bool fuse = Q.fuses_next_first != 0;
-        if (fuse) {
-            dc = C.dinv32;
-            zc = QC.start_odd ? h->pong[l + 1] : C.x;        // (the buffer its cycle starts from: coarse_cycle below is called with x = C.x)
-        }
-        if (rr_fused) {
-            // mode of the coarse level's first sweep: 0 none, 1 nodal D^-1, 2 its aggregate blocks (walked in THEIR order)
-            const int mode = !fuse ? 0 : (QC.blocks ? 2 : 1);
-            const int32_t* slots = mode == 2 ? C.blk_rows : nullptr;
-            const int32_t n_slots = mode == 2 ? 8 * C.n_blk : C.n_owned;
-            const unsigned grid = (unsigned)((n_slots + 7) / 8);
-            const void* vals = fmt_rr == 2 ? (const void*)L.vals16 : (const void*)L.vals32;
-            const float* sc16 = fmt_rr == 2 ? L.scale16 : nullptr;
-#define SNS_RR(F, M)                                                                                                            \
-    hipLaunchKernelGGL((k_resid_restrict<F, M, 0>), dim3(grid), dim3(256), 0, h->stream, C.n_owned, n_slots, slots, L.m_ptr, L.m_idx, \
-                       L.free_mask, L.rowptr, L.colind, vals, sc16, xres, b, L.r, cb, dc, (const void*)C.binv32, C.omega, zc, GhostSrc(), AgPut(), PutDst())
-            if (l == 0) time_begin(h, SPMV_B_MINUS_AX);                      // (bench.py's per-launch accounting of the fine-level passes)
-            if (fmt_rr == 2) { if (mode == 2) SNS_RR(2, 2); else if (mode == 1) SNS_RR(2, 1); else SNS_RR(2, 0); }
-            else             { if (mode == 2) SNS_RR(1, 2); else if (mode == 1) SNS_RR(1, 1); else SNS_RR(1, 0); }
-            if (l == 0) time_end(h);
-#undef SNS_RR
-        } else if (fuse && QC.blocks) {
-            const int32_t ns = 8 * C.n_blk;
-            if (C.binv_fmt == 2)
-                hipLaunchKernelGGL((k_restrict_blk<2>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
-                                   L.m_ptr, L.m_idx, L.free_mask, L.r, cb, (const void*)C.binv32, C.omega, zc, PutDst());
-            else
-                hipLaunchKernelGGL((k_restrict_blk<1>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
-                                   L.m_ptr, L.m_idx, L.free_mask, L.r, cb, (const void*)C.binv32, C.omega, zc, PutDst());
-        } else {
-            hipLaunchKernelGGL(k_restrict, dim3((unsigned)((4 * (int64_t)C.n_owned + 255) / 256)), dim3(256), 0, h->stream,
-                               C.n_owned, L.m_ptr, L.m_idx, L.free_mask, L.r, cb, dc, C.omega, zc);
-        }
-    }
+    if (C.n_owned > 0) launch_restrict(h, l, rr_fused, xres, b, cb);
     SNS_TRY(coarse_cycle(h, l + 1, cb, rep_src ? nullptr : C.x));
     int s_first = 0;
     // Fused coarse-grid correction + first post-smoothing sweep (k_post_lp): z = (cur + P xc) + om Dinv (r - M xc) with
@@ -388,7 +384,6 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     // of A and the prolongation kernel disappears.  Serial levels always; a distributed fine level when its single
     // post-sweep is the exact global one (px): the ghost aggregates' corrections arrive by ONE level-(l+1) exchange
     // instead of the level-l halo of the corrected iterate.
-    const int fmt_l = Q.lp_fmt;
     const bool fused_post = Q.fused_post != 0;
     if (fused_post) {
         const double* xc = cx;
@@ -398,44 +393,12 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
             SNS_TRY(exchange_level(h, l + 1, C.xg));
             xc = C.xg;
         }
-        if (rows > 0) {
-            const int grid = (rows + 63) / 64;
-            const bool fine = (l == 0);
-            if (fine) time_begin(h, 4);
-            if (Q.blocks) {
-                const int32_t ns = 8 * L.n_blk;
-                const unsigned gb = (unsigned)((ns + 63) / 64);
-                if (fmt_l == 2)
-                    hipLaunchKernelGGL((k_bpost<2, 0>), dim3(gb), dim3(256), 0, h->stream, ns, L.blk_rows, L.ap_rowptr, L.ap_colind,
-                                       (const void*)L.ap_vals16, L.ap_scale16, (const void*)L.binv32, xc, xc, (const double*)cur,
-                                       (const double*)L.r, om, L.agg, L.free_mask, oth, GhostSrc(), PutDst());
-                else
-                    hipLaunchKernelGGL((k_bpost<1, 0>), dim3(gb), dim3(256), 0, h->stream, ns, L.blk_rows, L.ap_rowptr, L.ap_colind,
-                                       (const void*)L.ap_vals32, (const float*)nullptr, (const void*)L.binv32, xc, xc,
-                                       (const double*)cur, (const double*)L.r, om, L.agg, L.free_mask, oth, GhostSrc(), PutDst());
-            } else if (fmt_l == 2) {
-                if (fine)
-                    hipLaunchKernelGGL((k_post_lp<2, 1>), dim3(grid), dim3(256), 0, h->stream, rows, L.ap_rowptr, L.ap_colind,
-                                       L.ap_vals16, L.ap_scale16, xc, cur, L.r, L.dinv32, om, L.agg, L.free_mask, oth, GhostSrc());
-                else
-                    hipLaunchKernelGGL((k_post_lp<2, 0>), dim3(grid), dim3(256), 0, h->stream, rows, L.ap_rowptr, L.ap_colind,
-                                       L.ap_vals16, L.ap_scale16, xc, cur, L.r, L.dinv32, om, L.agg, L.free_mask, oth, GhostSrc());
-            } else {
-                if (fine)
-                    hipLaunchKernelGGL((k_post_lp<1, 1>), dim3(grid), dim3(256), 0, h->stream, rows, L.ap_rowptr, L.ap_colind,
-                                       (const void*)L.ap_vals32, (const float*)nullptr, xc, cur, L.r, L.dinv32, om, L.agg,
-                                       L.free_mask, oth, GhostSrc());
-                else
-                    hipLaunchKernelGGL((k_post_lp<1, 0>), dim3(grid), dim3(256), 0, h->stream, rows, L.ap_rowptr, L.ap_colind,
-                                       (const void*)L.ap_vals32, (const float*)nullptr, xc, cur, L.r, L.dinv32, om, L.agg,
-                                       L.free_mask, oth, GhostSrc());
-            }
-            if (fine) time_end(h);
-        }
+        if (rows > 0) launch_post(h, l, xc, xc, L.ap_colind, cur, oth);
         std::swap(cur, oth);
         s_first = 1;
     } else if (rows > 0) {
-        hipLaunchKernelGGL(k_prolong_add, dim3(g4), dim3(256), 0, h->stream, rows, L.agg, L.free_mask, cx, cur);
+        hipLaunchKernelGGL(k_prolong_add, dim3((unsigned)((4 * (int64_t)rows + 255) / 256)), dim3(256), 0, h->stream, rows, L.agg,
+                           L.free_mask, cx, cur);
     }
     if (fused_post) {
         // (the post-sweep is done; a partitioned fine level got its neighbours' corrections through xc)

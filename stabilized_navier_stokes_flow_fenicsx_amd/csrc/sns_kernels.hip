@@ -1381,8 +1381,8 @@ __global__ __launch_bounds__(256) void k_spmv(int32_t n_rows, const int32_t* __r
         if (NT == 1) {
             // production: the first 16 blocks of the row (all of it on a tet mesh's fine level) are requested UP-FRONT --
             // four index loads, sixteen 16-B matrix loads, eight x loads: three dependent round trips per row instead of
-            // two per step of 4 blocks plus two per tail block (A/B: 0.583 -> 0.523 ms at 10 M tets, sns_bench_variants 3;
-            // NT == 3 keeps the stepped loop for that harness).  Missing blocks are masked (zero values, own x block).
+            // two per step of 4 blocks plus two per tail block (A/B: 0.583 -> 0.523 ms at 10 M tets).  Missing
+            // blocks are masked (zero values, own x block).
             const int32_t cnt = e - s;
             const int32_t own = live ? row : 0;
             int32_t c[4];
@@ -1410,35 +1410,21 @@ __global__ __launch_bounds__(256) void k_spmv(int32_t n_rows, const int32_t* __r
             k = (cnt > 16) ? s + 16 : e;
             vp += 128;
         }
-        if (NT == 2) {          // harness variant: r1e loop (4 broadcast index loads, 8-B x loads, scalar tail), nt stream
-            for (; k + 3 < e; k += 4) {
-                const int32_t c0 = colind[k], c1 = colind[k + 1], c2 = colind[k + 2], c3 = colind[k + 3];
-                const double2 a0 = ld_stream(vp), a1 = ld_stream(vp + 8), a2 = ld_stream(vp + 16), a3 = ld_stream(vp + 24);
-                const double g0 = x[4 * (int64_t)c0 + jq], g1 = x[4 * (int64_t)c1 + jq];
-                const double g2 = x[4 * (int64_t)c2 + jq], g3 = x[4 * (int64_t)c3 + jq];
-                acc0 += a0.x * quad_perm<0x88>(g0) + a0.y * quad_perm<0xDD>(g0);
-                acc1 += a1.x * quad_perm<0x88>(g1) + a1.y * quad_perm<0xDD>(g1);
-                acc0 += a2.x * quad_perm<0x88>(g2) + a2.y * quad_perm<0xDD>(g2);
-                acc1 += a3.x * quad_perm<0x88>(g3) + a3.y * quad_perm<0xDD>(g3);
-                vp += 32;
-            }
-        } else {
-            for (; k + 3 < e; k += 4) {           // rows longer than 16 blocks (coarse levels); NT 0 / 3: the whole row
-                const int32_t cme = colind[k + jq];
-                const double2 a0 = (NT ? ld_stream(vp) : vp[0]), a1 = (NT ? ld_stream(vp + 8) : vp[8]),
-                              a2 = (NT ? ld_stream(vp + 16) : vp[16]), a3 = (NT ? ld_stream(vp + 24) : vp[24]);
-                const int32_t cA = __builtin_amdgcn_mov_dpp(cme, 0x50, 0xF, 0xF, true);      // ids of blocks [0,0,1,1]
-                const int32_t cB = __builtin_amdgcn_mov_dpp(cme, 0xFA, 0xF, 0xF, true);      // ids of blocks [2,2,3,3]
-                if (SPLIT == 3) gr.arrive(gs, cme >= gr.n_own);
-                const double2 gA = *reinterpret_cast<const double2*>((SPLIT == 3 ? gr.ptr(x, cA) : x + 4 * (int64_t)cA) + 2 * (jq & 1));
-                const double2 gB = *reinterpret_cast<const double2*>((SPLIT == 3 ? gr.ptr(x, cB) : x + 4 * (int64_t)cB) + 2 * (jq & 1));
-                // lane (.., hf) takes its pair from quad lane hf (block 0 / 2) or 2 + hf (block 1 / 3)
-                acc0 += a0.x * quad_perm<0x44>(gA.x) + a0.y * quad_perm<0x44>(gA.y);
-                acc1 += a1.x * quad_perm<0xEE>(gA.x) + a1.y * quad_perm<0xEE>(gA.y);
-                acc0 += a2.x * quad_perm<0x44>(gB.x) + a2.y * quad_perm<0x44>(gB.y);
-                acc1 += a3.x * quad_perm<0xEE>(gB.x) + a3.y * quad_perm<0xEE>(gB.y);
-                vp += 32;
-            }
+        for (; k + 3 < e; k += 4) {           // rows longer than 16 blocks (coarse levels); NT 0: the whole row
+            const int32_t cme = colind[k + jq];
+            const double2 a0 = (NT ? ld_stream(vp) : vp[0]), a1 = (NT ? ld_stream(vp + 8) : vp[8]),
+                          a2 = (NT ? ld_stream(vp + 16) : vp[16]), a3 = (NT ? ld_stream(vp + 24) : vp[24]);
+            const int32_t cA = __builtin_amdgcn_mov_dpp(cme, 0x50, 0xF, 0xF, true);      // ids of blocks [0,0,1,1]
+            const int32_t cB = __builtin_amdgcn_mov_dpp(cme, 0xFA, 0xF, 0xF, true);      // ids of blocks [2,2,3,3]
+            if (SPLIT == 3) gr.arrive(gs, cme >= gr.n_own);
+            const double2 gA = *reinterpret_cast<const double2*>((SPLIT == 3 ? gr.ptr(x, cA) : x + 4 * (int64_t)cA) + 2 * (jq & 1));
+            const double2 gB = *reinterpret_cast<const double2*>((SPLIT == 3 ? gr.ptr(x, cB) : x + 4 * (int64_t)cB) + 2 * (jq & 1));
+            // lane (.., hf) takes its pair from quad lane hf (block 0 / 2) or 2 + hf (block 1 / 3)
+            acc0 += a0.x * quad_perm<0x44>(gA.x) + a0.y * quad_perm<0x44>(gA.y);
+            acc1 += a1.x * quad_perm<0xEE>(gA.x) + a1.y * quad_perm<0xEE>(gA.y);
+            acc0 += a2.x * quad_perm<0x44>(gB.x) + a2.y * quad_perm<0x44>(gB.y);
+            acc1 += a3.x * quad_perm<0xEE>(gB.x) + a3.y * quad_perm<0xEE>(gB.y);
+            vp += 32;
         }
         for (; k < e; ++k) {
             const double2 a0 = (NT ? ld_stream(vp) : vp[0]);
@@ -1496,12 +1482,6 @@ __global__ __launch_bounds__(256) void k_spmv(int32_t n_rows, const int32_t* __r
                                                 double*, const double*, const double*, double, const double*, double*, \
                                                 const int32_t*, const uint8_t*, int, GhostSrc);
 SNS_INST_SPMV(SPMV_AX, 1, 1, 0)
-#ifdef SNS_HARNESS      // A/B variants of the experiment harness only (make HARNESS=1): not in the shipped library
-SNS_INST_SPMV(SPMV_AX, 1, 0, 0)
-SNS_INST_SPMV(SPMV_AX, 1, 2, 0)
-SNS_INST_SPMV(SPMV_AX, 1, 3, 0)
-SNS_INST_SPMV(SPMV_AX_DOT, 1, 3, 0)
-#endif
 SNS_INST_SPMV(SPMV_B_MINUS_AX, 1, 1, 0)
 SNS_INST_SPMV(SPMV_JACOBI, 1, 1, 0)
 SNS_INST_SPMV(SPMV_AX_DOT, 1, 1, 0)
@@ -1721,9 +1701,6 @@ __global__ __launch_bounds__(256) void k_spmv_lp(int32_t n_rows, const int32_t* 
     SNS_INST_LP(SPMV_JACOBI, 0, 0, T, 1)
 SNS_INST_LP_FMT(1)
 SNS_INST_LP_FMT(2)
-#ifdef SNS_HARNESS
-SNS_INST_LP(SPMV_B_MINUS_AX, 1, 0, 2, 0) SNS_INST_LP(SPMV_JACOBI, 1, 0, 2, 0)      // in-solver A/B of the stepped loop
-#endif
 
 // k_post_lp: the FIRST post-smoothing sweep of a V-cycle level fused with the coarse-grid correction (round 3).
 // With x2 = x1 + P xc the sweep z = x2 + w Dinv (b - A x2) equals

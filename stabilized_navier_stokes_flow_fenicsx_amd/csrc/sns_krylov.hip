@@ -47,6 +47,38 @@ static PutDst fine_first_put(const sns_ctx* h) {
     return comm_put_dst(h->comm.get(), h->comm->plans[0]);
 }
 
+// BiCGStab's vector update in front of the preconditioner application pc_apply(., zdst): OP 1 s = r - alpha v (k_bicg_s), OP 2 the
+// x / r update with the next p (k_bicg_xrp).  Where fused_first_sweep_target allows it, the same launch does the cycle's first
+// fine-level sweep: on the aggregate blocks (k_bfirst_bicg, carrying the put of the window form) or nodal
+template <int OP>
+static void bicg_update(sns_ctx* h, double* zdst, const double* sc, const double* ph, const double* sh, const double* t, const double* v,
+                        double* x, double* r, double* p, double* s) {
+    const int64_t nd = nred_of(h);
+    const int g = vec_grid(nd);
+    double* z1 = fused_first_sweep_target(h, zdst);
+    if (!z1) {
+        if (OP == 1) hipLaunchKernelGGL(k_bicg_s, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, s);
+        else hipLaunchKernelGGL(k_bicg_xrp, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, v, x, r, p);
+        return;
+    }
+    const Level& L0 = h->levels[0];
+    if (h->plan.level[0].blocks) {
+        const int32_t ns = 8 * L0.n_blk;
+        const PutDst pd0 = fine_first_put(h);
+        h->first_put_carried = pd0.sr_ptr != nullptr;
+        with_fmt(L0.binv_fmt, [&](auto F) {
+            hipLaunchKernelGGL((k_bfirst_bicg<F, OP>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L0.blk_rows,
+                               (const void*)L0.binv32, L0.omega, z1, sc, ph, sh, t, v, x, r, p, s, pd0);
+        });
+    } else if (OP == 1) {
+        hipLaunchKernelGGL(k_bicg_s_first, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, s, L0.dinv32, L0.omega, z1);
+    } else {
+        hipLaunchKernelGGL(k_bicg_xrp_first, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, v, x, r, p, L0.dinv32, L0.omega,
+                           z1);
+    }
+    h->first_sweep_done = true;
+}
+
 
 // ---- BiCGStab (right-preconditioned; the recurrences of oracle/solve.py:bicgstab_bj) ----
 // Latency-lean formulation: rho / alpha / omega / beta live on the device (sc[]), the vector kernels read them
@@ -103,28 +135,7 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
         double best_rn = rn;
         int best_it = 0;
         for (its = 1;; ++its) {
-            if (double* z1 = fused_first_sweep_target(h, sh)) {
-                const Level& L0 = h->levels[0];
-                if (h->plan.level[0].blocks) {
-                    const int32_t ns = 8 * L0.n_blk;
-                    const unsigned gb = (unsigned)((ns + 63) / 64);
-                    const PutDst pd0 = fine_first_put(h);
-                    h->first_put_carried = pd0.sr_ptr != nullptr;
-                    if (L0.binv_fmt == 2)
-                        hipLaunchKernelGGL((k_bfirst_bicg<2, 1>), dim3(gb), dim3(256), 0, h->stream, ns, L0.blk_rows, (const void*)L0.binv32,
-                                           L0.omega, z1, sc, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, v,
-                                           (double*)nullptr, r, (double*)nullptr, s, pd0);
-                    else
-                        hipLaunchKernelGGL((k_bfirst_bicg<1, 1>), dim3(gb), dim3(256), 0, h->stream, ns, L0.blk_rows, (const void*)L0.binv32,
-                                           L0.omega, z1, sc, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, v,
-                                           (double*)nullptr, r, (double*)nullptr, s, pd0);
-                } else {
-                    hipLaunchKernelGGL(k_bicg_s_first, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, s, L0.dinv32, L0.omega, z1);
-                }
-                h->first_sweep_done = true;
-            } else {
-                hipLaunchKernelGGL(k_bicg_s, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, s);
-            }
+            bicg_update<1>(h, sh, sc, nullptr, nullptr, nullptr, v, nullptr, r, nullptr, s);
             h->pc_then_op = true;
             SNS_TRY(pc_apply(h, s, sh));
             SNS_TRY(op_apply(h, sh, t));
@@ -136,29 +147,7 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
             // rides on the x / r update (k_bicg_xrp)
             const bool spec = its < o.ksp_max_it;
             if (spec) {
-                if (double* z1 = fused_first_sweep_target(h, ph)) {
-                    const Level& L0 = h->levels[0];
-                    if (h->plan.level[0].blocks) {
-                        const int32_t ns = 8 * L0.n_blk;
-                        const unsigned gb = (unsigned)((ns + 63) / 64);
-                        const PutDst pd0 = fine_first_put(h);
-                        h->first_put_carried = pd0.sr_ptr != nullptr;
-                        if (L0.binv_fmt == 2)
-                            hipLaunchKernelGGL((k_bfirst_bicg<2, 2>), dim3(gb), dim3(256), 0, h->stream, ns, L0.blk_rows,
-                                               (const void*)L0.binv32, L0.omega, z1, sc, (const double*)ph, (const double*)sh,
-                                               (const double*)t, (const double*)v, x, r, p, s, pd0);
-                        else
-                            hipLaunchKernelGGL((k_bfirst_bicg<1, 2>), dim3(gb), dim3(256), 0, h->stream, ns, L0.blk_rows,
-                                               (const void*)L0.binv32, L0.omega, z1, sc, (const double*)ph, (const double*)sh,
-                                               (const double*)t, (const double*)v, x, r, p, s, pd0);
-                    } else {
-                        hipLaunchKernelGGL(k_bicg_xrp_first, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, v, x, r, p,
-                                           L0.dinv32, L0.omega, z1);
-                    }
-                    h->first_sweep_done = true;
-                } else {
-                    hipLaunchKernelGGL(k_bicg_xrp, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, v, x, r, p);
-                }
+                bicg_update<2>(h, ph, sc, ph, sh, t, v, x, r, p, s);
                 SNS_TRY(first_half(true));
             } else {
                 hipLaunchKernelGGL(k_bicg_xr, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, x, r);

@@ -146,8 +146,8 @@ inline Sweeps pre_post_sweeps(const sns_options& o, int ll, bool blocks, bool ra
 // the replicated level below.  Agreed over the ranks by the caller: win_capable[l] -- every rank's plan of the level receives in
 // order straight into its window; max_owned[l] -- the most owned rows any rank holds on the level.  last: how the last level is
 // solved.  rep_gather_fits: a rank's piece of the replicated right-hand side fits the all-gather staging area.  fine_rematched:
-// the hybrid aggregation (amg_aggregation = 3) re-matched level-0 nodes on some rank.  The remaining fields are the harnesses'
-// A/B switches (not options).
+// the hybrid aggregation (amg_aggregation = 3) re-matched level-0 nodes on some rank.  team_overlap / fuse_puts: the switches
+// SNS_TEAM_OVERLAP / SNS_NO_CARRIED_PUT (not options).
 struct Facts {
     int nranks = 1, rep_level = 0;
     std::vector<int64_t> rows, max_owned;
@@ -155,8 +155,7 @@ struct Facts {
     int64_t rows_global_l1 = 0;
     bool windows = false, rep_gather_fits = false, fine_rematched = false;
     CoarsestKind last = COARSEST_SWEEPS;
-    bool team_overlap = false, fuse_puts = true, restrict_fuse = true;
-    int graph_max_rows = GRAPH_MAX_ROWS;
+    bool team_overlap = false, fuse_puts = true;
 };
 
 // One level's row of the plan.  kind: SNS_LEVEL_* of include/sns.h; cycled = 0: only the source of the replicated copy; blocks: the
@@ -249,7 +248,7 @@ inline CyclePlan plan_cycle(const sns_options& o, const Facts& f) {
         // level whose cycle is the all-gather into the replicated tail (nor that tail's first level), not a level whose sweeps
         // exchange ghost values
         const int c = l + 1;
-        if (c + 1 < nl && f.restrict_fuse && !(R > 0 && (c == R - 1 || l == R - 1))) {
+        if (c + 1 < nl && !(R > 0 && (c == R - 1 || l == R - 1))) {
             const LevelPlan& C = p.level[(size_t)c];
             q.fuses_next_first = !C.sx && (C.blocks || C.lp_fmt != 0);
         }
@@ -263,7 +262,7 @@ inline CyclePlan plan_cycle(const sns_options& o, const Facts& f) {
         p.graph_level = R;                                  // only the replicated tail is free of exchanges
     } else {
         for (int l = 1; l < nl && !p.graph_level; ++l)
-            if (f.rows[(size_t)l] <= (int64_t)f.graph_max_rows) p.graph_level = l;
+            if (f.rows[(size_t)l] <= (int64_t)GRAPH_MAX_ROWS) p.graph_level = l;
     }
     p.fuse_puts = f.fuse_puts;
     return p;

@@ -186,9 +186,6 @@ int upload_ap(sns_ctx* h, Level& L, const HostPattern& fine, int32_t n_rows, con
     SNS_TRY(dev_upload(&L.ap_colind, M.colind, h->stream));
     SNS_TRY(dev_upload(&L.ap_ptr, M.ap_ptr, h->stream));
     SNS_TRY(dev_upload(&L.ap_idx, M.ap_idx, h->stream));
-#ifdef SNS_HARNESS
-    if (std::getenv("SNS_AP_GENERIC")) std::fill(M.nib.begin(), M.nib.end(), ~0ull);      // A/B: every row through the one-block-per-step loops
-#endif
     SNS_TRY(dev_upload(&L.ap_nib, M.nib, h->stream));
     return SNS_OK;
 }
@@ -630,7 +627,7 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
 
 // The plan of the cycle for the hierarchy just built (collective, once per hierarchy): its structure, the two per-rank facts agreed
 // over the ranks -- a level's plans receive in order straight into the windows on EVERY rank; the most owned rows of any rank --,
-// the harnesses' A/B switches, then csrc/sns_policy.h.  Every rank runs the same cycle whatever its ghost numbering or share.
+// the switches SNS_TEAM_OVERLAP / SNS_NO_CARRIED_PUT, then csrc/sns_policy.h.  Every rank runs the same cycle whatever its ghost numbering or share.
 int plan_hierarchy(sns_ctx* h) {
     const Comm* c = h->comm.get();
     const int nl = (int)h->levels.size();
@@ -642,10 +639,6 @@ int plan_hierarchy(sns_ctx* h) {
     f.windows = c && c->windows();
     f.team_overlap = h->team_overlap;
     f.fuse_puts = std::getenv("SNS_NO_CARRIED_PUT") == nullptr;
-#ifdef SNS_HARNESS
-    f.restrict_fuse = std::getenv("SNS_NO_RESTRICT_FUSE") == nullptr;
-    if (std::getenv("SNS_GRAPH_ROWS")) f.graph_max_rows = std::atoi(std::getenv("SNS_GRAPH_ROWS"));
-#endif
     const Level& last = h->levels.back();
     f.last = last.dense_gj ? policy::COARSEST_BLOCKED_INVERSE
                            : (last.dense_inv || h->cg_N > 0) ? policy::COARSEST_SMALL_INVERSE : policy::COARSEST_SWEEPS;
@@ -1083,14 +1076,11 @@ int pc_setup(sns_ctx* h) {
                 L.binv32 = pb;
                 L.binv_fmt = bf;
             }
-            if (L.n_blk > 0) {
-                if (bf == 2)
-                    hipLaunchKernelGGL((k_binv<2>), dim3((unsigned)((L.n_blk + 7) / 8)), dim3(256), 0, h->stream, L.n_blk, L.blk_rows,
+            if (L.n_blk > 0)
+                with_fmt(bf, [&](auto F) {
+                    hipLaunchKernelGGL((k_binv<F>), dim3((unsigned)((L.n_blk + 7) / 8)), dim3(256), 0, h->stream, L.n_blk, L.blk_rows,
                                        L.blk_of, L.rowptr, L.colind, L.vals, L.binv32, h->d_sing);
-                else
-                    hipLaunchKernelGGL((k_binv<1>), dim3((unsigned)((L.n_blk + 7) / 8)), dim3(256), 0, h->stream, L.n_blk, L.blk_rows,
-                                       L.blk_of, L.rowptr, L.colind, L.vals, L.binv32, h->d_sing);
-            }
+                });
             any_block = true;
         }
         L.omega = h->opt.amg_omega * h->damping_backoff;
@@ -1129,11 +1119,7 @@ int pc_setup(sns_ctx* h) {
                                            (const int32_t*)nullptr, (const uint8_t*)nullptr, (uint2*)nullptr, (float*)nullptr);
                 }
             }
-            bool want32 = h->opt.amg_f32_matrix != 2;
-#ifdef SNS_HARNESS
-            if (std::getenv("SNS_BOTH_LP")) want32 = true;       // the fp16-vs-fp32 A/B needs both copies
-#endif
-            if (want32) {
+            if (h->opt.amg_f32_matrix != 2) {
                 if (!L.vals32) SNS_TRY(dev_alloc(&L.vals32, (size_t)L.nnzb * 16));
                 if (L.nnzb > 0)
                     hipLaunchKernelGGL(k_cvt_f32, dim3(vec_grid(L.nnzb * 16)), dim3(256), 0, h->stream, L.nnzb * 16, L.vals,
