@@ -356,6 +356,20 @@ SNS_API int sns_residual(sns_handle h, int form, const double* w_dev, double* F_
  * zeroed, unit diagonal) into the handle's BSR matrix; if F_dev != NULL the
  * residual is produced by the same fused element pass.                        */
 SNS_API int sns_jacobian(sns_handle h, int form, const double* w_dev, double* F_dev);
+/* Weighted moments of the RAW residual (variationally consistent boundary forces):
+ * out[c] = sum over owned nodes i of phi[i] * R_raw(w)[4 i + c], c = 0..3, summed over the ranks
+ * (the handle's all-reduce; every rank returns the same value).  R_raw is the residual of the form
+ * assembled WITHOUT lifting and without F_B = w_B - g (DOLFINx assemble_vector(F) alone): on rows
+ * that are not Dirichlet rows it is what sns_residual returns for a state that satisfies the
+ * Dirichlet data; w need not satisfy it.  phi_dev: one double per local node (owned + ghost; ghost
+ * entries are ignored).  With phi = the indicator of the nodes of a tagged surface, -out[0..2] is the
+ * force the fluid exerts on it (pseudo-traction -p I + nu grad u, n = -FacetNormal as
+ * boundary_traction_force).  Honours corrected_convection and sns_set_form_variant; 2-D handles
+ * leave out[2] = 0.  SNS_FORM_STOKES with w_dev == NULL evaluates at w = 0.  Only the cells with a
+ * vertex i < n_owned and phi[i] != 0 are visited; deterministic (fixed-order reduction, no atomics).
+ * Returns after out_host is written.  SNS_E_ARG: null handle / phi / out, bad form, NS form without
+ * a state.                                                                    */
+SNS_API int sns_residual_moments(sns_handle h, int form, const double* w_dev, const double* phi_dev, double out_host[4]);
 /* MatMult with the assembled operator: y = A x (halo exchange inside).        */
 SNS_API int sns_spmv(sns_handle h, const double* x_dev, double* y_dev);
 /* PCSetUp / PCApply for the current matrix.                                   */

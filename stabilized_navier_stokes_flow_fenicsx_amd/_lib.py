@@ -101,6 +101,7 @@ _SIGNATURES = [
     ("sns_attach_peer", C.c_int, [_H, _P, C.c_int32, C.c_int, _P, _P, _P, _P, _P]),
     ("sns_residual", C.c_int, [_H, C.c_int, _P, _P]),
     ("sns_jacobian", C.c_int, [_H, C.c_int, _P, _P]),
+    ("sns_residual_moments", C.c_int, [_H, C.c_int, _P, _P, _P]),
     ("sns_spmv", C.c_int, [_H, _P, _P]),
     ("sns_pc_setup", C.c_int, [_H]),
     ("sns_pc_apply", C.c_int, [_H, _P, _P]),

@@ -275,6 +275,7 @@ int sns_destroy(sns_handle h) {
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(h->tets); fr(h->pts); fr(h->bc_mask); fr(h->bc_val);
     fr(h->nt_ptr); fr(h->nt_idx); fr(h->c_ptr); fr(h->c_idx); fr(h->od_order); fr(h->gext); fr(h->Ke); fr(h->Fe);
+    fr(h->rm_off); fr(h->rm_cells); fr(h->rm_Fe); fr(h->rm_nomask);
     for (auto& L : h->levels) {
         fr(L.rowptr); fr(L.colind); fr(L.diag); fr(L.vals); fr(L.dinv); fr(L.agg); fr(L.m_ptr); fr(L.m_idx);
         fr(L.r_ptr); fr(L.r_idx); fr(L.free_mask); fr(L.x); fr(L.b); fr(L.r); fr(L.dense_inv); fr(L.dense_gj); fr(L.dense_work); fr(L.dense_x32); fr(L.vals32); fr(L.vals16); fr(L.scale16); fr(L.dinv32);
@@ -529,6 +530,80 @@ int sns_residual(sns_handle h, int form, const double* w, double* F) {
 int sns_jacobian(sns_handle h, int form, const double* w, double* F) {
     if (!h) return SNS_E_ARG;
     return timed_assemble(h, form, w, F, true);
+}
+
+int sns_residual_moments(sns_handle h, int form, const double* w, const double* phi, double out[4]) {
+    if (!h || !phi || !out) { set_error("sns_residual_moments: null handle or pointer"); return SNS_E_ARG; }
+    if (form != SNS_FORM_STOKES && form != SNS_FORM_NS) { set_error("bad form"); return SNS_E_ARG; }
+    if (form == SNS_FORM_NS && !w) { set_error("NS form needs a state vector"); return SNS_E_ARG; }
+    if (h->E == 0) { set_error("empty mesh"); return SNS_E_ARG; }
+    const int64_t ndof = 4 * (int64_t)h->n;
+    if (!w) {                                        // linear form without a state: R_raw(0) = 0, still one collective pass
+        double* z = nullptr;
+        SNS_TRY(get_vec(h, 13, &z));
+        HIP_TRY(hipMemsetAsync(z, 0, ndof * sizeof(double), h->stream));
+        w = z;
+    }
+    // support of the functional behind the owned rows: count, scan, fetch the size, scatter
+    const int64_t nb = (h->E + 255) / 256;
+    if (!h->rm_off) SNS_TRY(dev_alloc(&h->rm_off, (size_t)nb));
+    hipLaunchKernelGGL(k_support_count, dim3((unsigned)nb), dim3(256), 0, h->stream, h->E, h->tets, h->n_owned, phi, h->rm_off);
+    hipLaunchKernelGGL(k_support_scan, dim3(1), dim3(256), 0, h->stream, nb, h->rm_off, h->d_scal + 100);
+    double total = 0.0;
+    SNS_TRY(fetch(h, h->d_scal + 100, 1, &total));
+    const int64_t nc = (int64_t)total;
+    if (nc > h->rm_cap) {
+        if (h->rm_cells) { HIP_TRY(hipFree(h->rm_cells)); h->rm_cells = nullptr; }
+        if (h->rm_Fe) { HIP_TRY(hipFree(h->rm_Fe)); h->rm_Fe = nullptr; }
+        h->rm_cap = 0;
+        SNS_TRY(dev_alloc(&h->rm_cells, (size_t)4 * nc));
+        SNS_TRY(dev_alloc(&h->rm_Fe, (size_t)16 * nc));
+        h->rm_cap = nc;
+    }
+    if (nc > 0) {
+        hipLaunchKernelGGL(k_support_scatter, dim3((unsigned)nb), dim3(256), 0, h->stream, h->E, h->tets, h->n_owned, phi,
+                           h->rm_off, h->rm_cells);
+        // element residuals of the compacted cells, by the kernels the residual of the same form uses; no lifting: the
+        // one-lane-per-cell kernels have none, the staged kernel gets an all-zero Dirichlet mask
+        const unsigned g1 = (unsigned)((nc + 255) / 256);
+        const double nu = 1.0 / h->opt.reynolds;
+        if (h->dim == 2) {
+            if (form == SNS_FORM_NS)
+                hipLaunchKernelGGL(k_residual_tri, dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w, nu, h->rm_Fe);
+            else
+                hipLaunchKernelGGL(k_residual_tri_stokes, dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w,
+                                   h->opt.stokes_viscosity, h->opt.stokes_beta, h->rm_Fe);
+        } else if (form == SNS_FORM_NS && h->fv.is_default()) {
+            if (!h->opt.corrected_convection)
+                hipLaunchKernelGGL((k_residual_tet<false>), dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w, nu, h->rm_Fe);
+            else
+                hipLaunchKernelGGL((k_residual_tet<true>), dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w, nu, h->rm_Fe);
+        } else {
+            if (!h->rm_nomask) {
+                SNS_TRY(dev_alloc(&h->rm_nomask, (size_t)ndof));
+                HIP_TRY(hipMemset(h->rm_nomask, 0, (size_t)ndof));
+            }
+            const unsigned ge = (unsigned)((nc + EL_TETS_PER_BLOCK - 1) / EL_TETS_PER_BLOCK);
+            if (form == SNS_FORM_STOKES)
+                hipLaunchKernelGGL((k_element<SNS_FORM_STOKES, false>), dim3(ge), dim3(256), 0, h->stream, nc, h->rm_cells,
+                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv);
+            else if (!h->opt.corrected_convection)
+                hipLaunchKernelGGL((k_element<SNS_FORM_NS, false>), dim3(ge), dim3(256), 0, h->stream, nc, h->rm_cells,
+                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv);
+            else
+                hipLaunchKernelGGL((k_element<SNS_FORM_NS, true>), dim3(ge), dim3(256), 0, h->stream, nc, h->rm_cells,
+                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv);
+        }
+    }
+    // fixed-order two-stage reduction (grid fixed by the support size), then the handle's all-reduce over the ranks
+    const int gm = (int)std::max<int64_t>(1, std::min<int64_t>((nc + 255) / 256, 2048));
+    hipLaunchKernelGGL(k_moments_partial, dim3(gm), dim3(256), 0, h->stream, nc, h->rm_cells, h->dim + 1, h->n_owned, phi,
+                       h->rm_Fe, h->partial);
+    SNS_TRY(reduce_to(h, gm, 4, h->d_scal + 104));
+    HIP_TRY(hipGetLastError());
+    SNS_TRY(fetch(h, h->d_scal + 104, 4, out));
+    if (h->dim == 2) out[2] = 0.0;
+    return SNS_OK;
 }
 
 int sns_spmv(sns_handle h, const double* x, double* y) {

@@ -88,6 +88,13 @@ struct sns_ctx {
     double* gext = nullptr;            // Dirichlet data extended by zero (the state the Stokes lifting term is taken at)
     int64_t n_od = 0;
     double *Ke = nullptr, *Fe = nullptr;
+    // residual moments (sns_residual_moments): per-256-cell support counts / offsets, the compacted connectivity and its
+    // element residuals (capacity rm_cap cells, grown on demand), and an all-zero Dirichlet mask for the staged element kernel
+    int64_t* rm_off = nullptr;
+    int32_t* rm_cells = nullptr;
+    double* rm_Fe = nullptr;
+    int64_t rm_cap = 0;
+    uint8_t* rm_nomask = nullptr;
     // operator hierarchy; levels[0] is the assembled fine operator.  A deque: references to a level stay valid
     // while coarser levels are appended (a vector reallocation under a live Level& once handed a kernel dangling
     // pointers)

@@ -172,5 +172,14 @@ __global__ void k_unpack(int32_t m, const int32_t* idx, const double* buf, doubl
 __global__ void k_fill_pattern(int64_t n, double* x);
 __global__ void k_scale_by_rsqrt(int64_t n, const double* s2, const double* x, double* y);
 __global__ void k_fill_slot_row(int32_t n, const int32_t* rowptr, int32_t* slot_row);
+// residual moments (sns_residual_moments): support compaction of the cells, 2-D Stokes element residuals, weighted sums
+__global__ void k_support_count(int64_t n_cells, const int32_t* cells, int32_t n_owned, const double* phi, int64_t* cnt);
+__global__ void k_support_scan(int64_t nb, int64_t* cnt, double* total);
+__global__ void k_support_scatter(int64_t n_cells, const int32_t* cells, int32_t n_owned, const double* phi, const int64_t* off,
+                                  int32_t* cells_c);
+__global__ void k_residual_tri_stokes(int64_t n_tris, const int32_t* tets, const double* pts, const double* w, double nu_s,
+                                      double beta, double* Fe);
+__global__ void k_moments_partial(int64_t n_c, const int32_t* cells_c, int npe, int32_t n_owned, const double* phi,
+                                  const double* Fe, double* partial);
 
 }  // namespace sns

@@ -2809,4 +2809,119 @@ __global__ __launch_bounds__(256) void k_fill_slot_row(int32_t n, const int32_t*
     for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) slot_row[k] = i;
 }
 
+
+// ============================================================================
+// Residual moments (sns_residual_moments): out[c] = sum over owned rows i of phi_i * R_raw(w)[4 i + c], R_raw = the
+// assembled residual without lifting and without F_B = w_B - g.  The element residuals come from the unchanged element
+// kernels (k_residual_tet / k_element / k_residual_tri, or k_residual_tri_stokes below) run over a COMPACTED copy of the
+// connectivity: only the cells with a vertex i < n_owned and phi_i != 0 (the support of the functional behind an owned
+// row), so a surface functional costs O(surface).  Compaction: per-256-cell counts, one-workgroup exclusive scan, scatter
+// in cell order (order-preserving, no atomics).  The moments: one lane per compacted cell, block partials, k_reduce_final.
+// ============================================================================
+__device__ __forceinline__ bool support_cell(const int4 tv, int32_t n_owned, const double* __restrict__ phi) {
+    const int32_t nd[4] = {tv.x, tv.y, tv.z, tv.w};
+    bool f = false;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) f |= nd[a] < n_owned && phi[nd[a]] != 0.0;
+    return f;
+}
+
+__global__ __launch_bounds__(256) void k_support_count(int64_t n_cells, const int32_t* __restrict__ cells, int32_t n_owned,
+                                                       const double* __restrict__ phi, int64_t* __restrict__ cnt) {
+    __shared__ int wsum[4];
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool f = t < n_cells && support_cell(*reinterpret_cast<const int4*>(cells + 4 * t), n_owned, phi);
+    const unsigned long long m = __ballot(f);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[blockIdx.x] = (int64_t)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+}
+
+// one workgroup: cnt[0..nb) -> exclusive offsets in place; total -> *total (a double, for the host fetch)
+__global__ __launch_bounds__(256) void k_support_scan(int64_t nb, int64_t* __restrict__ cnt, double* __restrict__ total) {
+    __shared__ int64_t s[256];
+    const int tid = threadIdx.x;
+    const int64_t seg = (nb + 255) / 256, b0 = min(nb, tid * seg), b1 = min(nb, b0 + seg);
+    int64_t mine = 0;
+    for (int64_t b = b0; b < b1; ++b) mine += cnt[b];
+    s[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {                  // inclusive Hillis-Steele scan of the 256 segment sums
+        const int64_t v = tid >= o ? s[tid - o] : 0;
+        __syncthreads();
+        s[tid] += v;
+        __syncthreads();
+    }
+    int64_t run = s[tid] - mine;
+    for (int64_t b = b0; b < b1; ++b) {
+        const int64_t c = cnt[b];
+        cnt[b] = run;
+        run += c;
+    }
+    if (tid == 255) *total = (double)s[255];
+}
+
+__global__ __launch_bounds__(256) void k_support_scatter(int64_t n_cells, const int32_t* __restrict__ cells, int32_t n_owned,
+                                                         const double* __restrict__ phi, const int64_t* __restrict__ off,
+                                                         int32_t* __restrict__ cells_c) {
+    __shared__ int wsum[4];
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int4 tv = make_int4(0, 0, 0, 0);
+    if (t < n_cells) tv = *reinterpret_cast<const int4*>(cells + 4 * t);
+    const bool f = t < n_cells && support_cell(tv, n_owned, phi);
+    const unsigned long long m = __ballot(f);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) wsum[wv] = __popcll(m);
+    __syncthreads();
+    int base = 0;
+    for (int k = 0; k < wv; ++k) base += wsum[k];
+    if (f) {
+        const int64_t pos = off[blockIdx.x] + base + __popcll(m & ((1ull << lane) - 1ull));
+        *reinterpret_cast<int4*>(cells_c + 4 * pos) = tv;
+    }
+}
+
+// element residuals of the 2-D Stokes form (the rows tri_block_accumulate_stokes produces for k_fused_diag), one lane per
+// triangle, in the layout of k_residual_tri: Fe[16 t + 4 a + c], uz and vertex 3 zero
+__global__ __launch_bounds__(256) void k_residual_tri_stokes(int64_t n_tris, const int32_t* __restrict__ tets,
+                                                             const double* __restrict__ pts, const double* __restrict__ w,
+                                                             double nu_s, double beta, double* __restrict__ Fe) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tris) return;
+    const int4 tv = *reinterpret_cast<const int4*>(tets + 4 * t);
+    double2* o = reinterpret_cast<double2*>(Fe + 16 * t);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        double acc[16], R[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.0;
+        tri_block_accumulate_stokes(tv, pts, w, nu_s, beta, a, a, true, acc, R);
+        o[2 * a] = make_double2(R[0], R[1]);
+        o[2 * a + 1] = make_double2(0.0, R[3]);
+    }
+    o[6] = make_double2(0.0, 0.0);
+    o[7] = make_double2(0.0, 0.0);
+}
+
+// partial moments: lane = compacted cell (grid-stride over a fixed grid), sum_a [node < n_owned] phi_node Fe[cell][a][c]
+__global__ __launch_bounds__(256) void k_moments_partial(int64_t n_c, const int32_t* __restrict__ cells_c, int npe,
+                                                         int32_t n_owned, const double* __restrict__ phi,
+                                                         const double* __restrict__ Fe, double* __restrict__ partial) {
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_c; t += (int64_t)gridDim.x * blockDim.x) {
+        const int4 tv = *reinterpret_cast<const int4*>(cells_c + 4 * t);
+        const int32_t nd[4] = {tv.x, tv.y, tv.z, tv.w};
+        const double2* fe = reinterpret_cast<const double2*>(Fe + 16 * t);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            if (a >= npe || nd[a] >= n_owned) continue;
+            const double ph = phi[nd[a]];
+            if (ph == 0.0) continue;
+            const double2 f01 = fe[2 * a], f23 = fe[2 * a + 1];
+            v[0] += ph * f01.x; v[1] += ph * f01.y; v[2] += ph * f23.x; v[3] += ph * f23.y;
+        }
+    }
+    block_reduce_store<4>(v, partial);
+}
+
 }  // namespace sns

@@ -12,6 +12,10 @@ Mirrors the post-processing of the reference's DFG benchmark script
 For P1 fields grad u is constant in the tet behind a boundary facet and p is linear on the facet, so the
 facet integrals are exact with  area * (stress(grad u, mean of the 3 nodal p) . n).  Host side (numpy): the
 obstacle surface holds O(N^(2/3)) facets, there is nothing to accelerate.
+
+``reaction_force`` is the variationally consistent (residual-based) alternative: F = -R_raw(w)(phi e_c), the raw residual
+tested with the P1 function phi that is 1 on the surface's nodes and 0 elsewhere.  It runs on the
+device (sns_residual_moments) over the cells behind the surface only, and on a partitioned problem needs no gather.
 """
 from __future__ import annotations
 
@@ -67,3 +71,32 @@ def drag_lift_coefficients(force: np.ndarray, rho: float = 1.0, Uc: float = 0.2,
     """(C_d, C_l) = 2 F / (rho Uc^2 Lc)  (DFG_3D_Validation.py:345-346,364-365; defaults are the script's)."""
     s = 2.0 / (rho * Uc * Uc * Lc)
     return s * float(force[0]), s * float(force[1])
+
+
+def tag_node_weights(mesh: TetMesh, tag: int, *, rim_tags=(), rim_weight: float = 1.0, part=None) -> np.ndarray:
+    """Nodal weights phi of the surface tagged ``tag`` (the P1 indicator of its facets' nodes): 1 on those nodes, 0 elsewhere;
+    nodes that also lie on a facet tagged one of ``rim_tags`` (the rim where the surface meets a no-slip wall) get
+    ``rim_weight``.  With ``part`` (partition.LocalPart of ``mesh``) the weights are returned in that rank's local node
+    numbering (owned nodes first, then ghosts); sns_residual_moments reads only the owned ones, so every node counts once
+    over the ranks."""
+    phi = np.zeros(mesh.num_nodes)
+    phi[mesh.facet_nodes(tag)] = 1.0
+    if len(rim_tags) and rim_weight != 1.0:
+        other = np.unique(mesh.facets[np.isin(mesh.facet_tags, np.asarray(rim_tags))].ravel())
+        phi[other[phi[other] != 0.0]] = rim_weight
+    return np.ascontiguousarray(phi[part.l2g]) if part is not None else phi
+
+
+def reaction_force(problem, w, tag: int, *, mesh: TetMesh | None = None, rim_tags=(), rim_weight: float = 1.0,
+                   form: str = "ns") -> np.ndarray:
+    """Residual-based force on the surface tagged ``tag``: F = -R_raw(w)(phi e_c), c = 0..2, phi = tag_node_weights, as a
+    3-vector in the convention of boundary_traction_force (drag_lift_coefficients takes either).  ``w``: the problem's
+    local device (or numpy) state.  ``mesh``: the tagged global mesh; defaults to the problem's own (the global mesh of a
+    ``FlowProblem.distributed`` rank, whose local part carries no facet tags).  Every rank returns the same force."""
+    part = getattr(problem, "part", None)
+    if mesh is None:
+        mesh = getattr(problem, "global_mesh", None) if part is not None else problem.mesh
+        if mesh is None:
+            raise ValueError("reaction_force: pass the tagged global mesh of this partitioned problem")
+    phi = tag_node_weights(mesh, tag, rim_tags=rim_tags, rim_weight=rim_weight, part=part)
+    return -problem.residual_moments(w, phi, form)[:3]

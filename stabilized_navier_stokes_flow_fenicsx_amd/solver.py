@@ -269,6 +269,20 @@ class FlowProblem:
         check(self.lib.sns_jacobian(self.h, _FORMS[form], _ptr(w), _ptr(F)))
         return F
 
+    def residual_moments(self, w, phi, form="ns") -> np.ndarray:
+        """sum_i phi_i R_raw(w)[4 i + c], c = 0..3, over the owned nodes of every rank (sns_residual_moments): R_raw is the
+        residual without lifting and without the Dirichlet rows' w_B - g, so ``-out[:3]`` is the force on the surface whose
+        node indicator is ``phi`` (functionals.reaction_force).  ``phi``: numpy or a device tensor, one weight per local node
+        (owned + ghost, the handle's numbering).  ``w`` may violate its Dirichlet data; None evaluates the Stokes form at 0."""
+        w = None if w is None else self._vec(w)
+        if isinstance(phi, np.ndarray):
+            phi = torch.from_numpy(np.ascontiguousarray(phi, dtype=np.float64)).to(self.device)
+        if phi.dtype != torch.float64 or phi.device.type != "cuda" or not phi.is_contiguous() or phi.numel() != self.n_local:
+            raise ValueError(f"phi: expected a contiguous float64 vector of {self.n_local} node weights")
+        out = (C.c_double * 4)()
+        check(self.lib.sns_residual_moments(self.h, _FORMS[form], _ptr(w), _ptr(phi), out))
+        return np.array(out[:], dtype=np.float64)
+
     def spmv(self, x, out=None) -> torch.Tensor:
         x = self._vec(x)
         out = self.zeros() if out is None else self._vec(out)
