@@ -370,12 +370,14 @@ SNS_API int sns_jacobian(sns_handle h, int form, const double* w_dev, double* F_
  * Returns after out_host is written.  SNS_E_ARG: null handle / phi / out, bad form, NS form without
  * a state.                                                                    */
 SNS_API int sns_residual_moments(sns_handle h, int form, const double* w_dev, const double* phi_dev, double out_host[4]);
-/* MatMult with the assembled operator: y = A x (halo exchange inside).        */
+/* MatMult with the assembled operator: y = A x (halo exchange inside).  Acts on whatever
+ * the handle holds: y = A^T x after sns_transpose_operator.                   */
 SNS_API int sns_spmv(sns_handle h, const double* x_dev, double* y_dev);
-/* PCSetUp / PCApply for the current matrix.                                   */
+/* PCSetUp / PCApply for the current matrix (of A^T while the handle is transposed). */
 SNS_API int sns_pc_setup(sns_handle h);
 SNS_API int sns_pc_apply(sns_handle h, const double* r_dev, double* z_dev);
-/* KSPSolve: A x = b with the handle's ksp/pc options; x_dev holds the initial
+/* KSPSolve: A x = b with the handle's ksp/pc options (A^T x = b while the handle is
+ * transposed); x_dev holds the initial
  * guess on entry.  rnorm = 2-norm of the TRUE residual b - A x at exit.  With
  * amg_retry_damping (default on) a solve that ends in DIVERGED_BREAKDOWN or
  * DIVERGED_NANORINF (or, BiCGStab, stagnates for amg_retry_stall_its iterations: first-attempt
@@ -386,6 +388,33 @@ SNS_API int sns_pc_apply(sns_handle h, const double* r_dev, double* z_dev);
  * iterations (DIVERGED_ITS) is never retried.                                    */
 SNS_API int sns_krylov_solve(sns_handle h, const double* b_dev, double* x_dev,
                      int* its, int* reason, double* rnorm);
+/* ---- adjoint solves: MatTranspose / KSPSolveTranspose on the Jacobian the SNES callback J assembled
+ *      (NavierStokesChannelFlow.py:69-75) --------------------------------------------------------------
+ * sns_transpose_operator flips the assembled fine operator IN PLACE between A and A^T and toggles the handle's flag.
+ * The P1-P1 pattern is structurally symmetric with sorted rows and the Dirichlet rule zeroes rows and columns, so A^T
+ * keeps rowptr / colind: block (i, j) of A^T is the transposed 4 x 4 block of slot (j, i), and the transpose is a
+ * permutation of vals (csrc/sns_transpose.hip; pure data movement, a second call restores the bits).  The slot -> partner
+ * map (4 B per block) is built at the first call and kept by the handle.  The preconditioner must be set up again
+ * (sns_pc_setup, or the next solve does it) and re-estimates its smoother damping: the caps were taken on the other
+ * operator.  The hierarchy of the flipped values is the hierarchy of A^T (P^T A^T P = (P^T A P)^T); the cycle's sweep
+ * schedules stay as they are.  Every assembly into the handle (sns_jacobian, and those inside sns_stokes_solve /
+ * sns_newton_solve) overwrites vals with A and clears the flag.  sns_spmv, sns_pc_setup, sns_pc_apply, sns_krylov_solve,
+ * sns_get_bsr and sns_export act on whatever the handle holds.
+ * SNS_E_STATE: no assembled matrix; a handle with a communicator attached (any transport, also the local-only split: a
+ * rank's ghost rows are not complete rows of A).  SNS_E_MESH: the pattern is not structurally symmetric; nothing is
+ * modified.  2-D handles work as they are.                                                                          */
+SNS_API int sns_transpose_operator(sns_handle h);
+SNS_API int sns_operator_is_transposed(sns_handle h, int* flag);
+/* A^T lam = g_dev with the handle's ksp / pc options, lam_dev holding the initial guess on entry: transpose,
+ * sns_pc_setup, the Krylov solve (damping retry as in sns_krylov_solve), transpose back -- also after a solve that did
+ * not converge, not after SNS_E_HIP / SNS_E_COMM -- and the preconditioner marked stale, so that the handle holds A as
+ * before and the next solve sets up for it.  rnorm = 2-norm of the TRUE residual g - A^T lam at the end of the Krylov
+ * solve; a converged solve then returns lam_B = g_B exactly on the Dirichlet dofs (unit rows and columns of A), which
+ * only removes their part of that residual.  With g = dJ/dw of a
+ * functional J at a converged state w and A the Jacobian assembled there, dJ/dq = dJ/dq|explicit - lam . dF/dq for a
+ * parameter q of the residual F (solver.reynolds_sensitivity): one linear solve instead of two nonlinear ones per
+ * parameter.  Errors as sns_transpose_operator and sns_krylov_solve.                                                 */
+SNS_API int sns_adjoint_solve(sns_handle h, const double* g_dev, double* lam_dev, int* its, int* reason, double* rnorm);
 /* solve_stokes_problem (:197-218): assemble + lift + KSP; U_dev receives U.   */
 SNS_API int sns_stokes_solve(sns_handle h, double* U_dev, int* ksp_its, int* reason, double* rnorm);
 /* solve_navier_stokes (:268-312): SNES newtonls + bt; w_dev updated in place
@@ -395,7 +424,8 @@ SNS_API int sns_newton_solve(sns_handle h, double* w_dev, int* its, int* reason,
                      int* total_ksp_its, double* fnorm_hist, int hist_cap);
 
 /* ---- introspection (tests, profiling) --------------------------------------*/
-/* device pointers of the assembled BSR4 operator (block row-major 4x4)        */
+/* device pointers of the assembled BSR4 operator (block row-major 4x4); the values are those of A^T while the handle
+ * is transposed (sns_transpose_operator), like SNS_EXPORT_VALS below                                                */
 SNS_API int sns_get_bsr(sns_handle h, int32_t* n_rows, int64_t* nnzb, const int32_t** rowptr_dev,
                 const int32_t** colind_dev, const double** vals_dev);
 /* element-level output of the last sns_jacobian call: Ke [n_tets][a][b][c][d]

@@ -106,6 +106,9 @@ _SIGNATURES = [
     ("sns_pc_setup", C.c_int, [_H]),
     ("sns_pc_apply", C.c_int, [_H, _P, _P]),
     ("sns_krylov_solve", C.c_int, [_H, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("sns_transpose_operator", C.c_int, [_H]),
+    ("sns_operator_is_transposed", C.c_int, [_H, C.POINTER(C.c_int)]),
+    ("sns_adjoint_solve", C.c_int, [_H, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("sns_stokes_solve", C.c_int, [_H, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("sns_newton_solve", C.c_int, [_H, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_double), C.c_int]),

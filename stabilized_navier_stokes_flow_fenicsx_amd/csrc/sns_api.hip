@@ -275,7 +275,7 @@ int sns_destroy(sns_handle h) {
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(h->tets); fr(h->pts); fr(h->bc_mask); fr(h->bc_val);
     fr(h->nt_ptr); fr(h->nt_idx); fr(h->c_ptr); fr(h->c_idx); fr(h->od_order); fr(h->gext); fr(h->Ke); fr(h->Fe);
-    fr(h->rm_off); fr(h->rm_cells); fr(h->rm_Fe); fr(h->rm_nomask);
+    fr(h->rm_off); fr(h->rm_cells); fr(h->rm_Fe); fr(h->rm_nomask); fr(h->tr_partner);
     for (auto& L : h->levels) {
         fr(L.rowptr); fr(L.colind); fr(L.diag); fr(L.vals); fr(L.dinv); fr(L.agg); fr(L.m_ptr); fr(L.m_idx);
         fr(L.r_ptr); fr(L.r_idx); fr(L.free_mask); fr(L.x); fr(L.b); fr(L.r); fr(L.dense_inv); fr(L.dense_gj); fr(L.dense_work); fr(L.dense_x32); fr(L.vals32); fr(L.vals16); fr(L.scale16); fr(L.dinv32);
@@ -361,6 +361,7 @@ int sns_set_form_variant(sns_handle h, double c_inverse, double lsic_scale, doub
     if (one_point_quadrature) fv.qa = fv.qb = 0.25;
     h->fv = fv;
     h->has_matrix = false;
+    h->transposed = false;
     h->pc_ready = false;
     return SNS_OK;
 }
@@ -630,6 +631,39 @@ int sns_krylov_solve(sns_handle h, const double* b, double* x, int* its, int* re
     if (!h || !b || !x || !its || !reason || !rnorm) return SNS_E_ARG;
     SNS_TRY(ensure_hierarchy(h));
     return krylov(h, b, x, its, reason, rnorm);
+}
+
+
+int sns_transpose_operator(sns_handle h) {
+    if (!h) return SNS_E_ARG;
+    return transpose_operator(h);
+}
+
+int sns_operator_is_transposed(sns_handle h, int* flag) {
+    if (!h || !flag) return SNS_E_ARG;
+    *flag = h->transposed ? 1 : 0;
+    return SNS_OK;
+}
+
+int sns_adjoint_solve(sns_handle h, const double* g, double* lam, int* its, int* reason, double* rnorm) {
+    if (!h || !g || !lam || !its || !reason || !rnorm) return SNS_E_ARG;
+    SNS_TRY(transpose_operator(h));                      // (SNS_E_STATE / SNS_E_MESH: nothing was modified)
+    int rc = ensure_hierarchy(h);
+    if (rc == SNS_OK) rc = krylov(h, g, lam, its, reason, rnorm);
+    // the Dirichlet rows AND columns of A are unit rows: lam_B = g_B exactly, and a converged solve hands that back (as
+    // sns_stokes_solve does with the Dirichlet data); the other rows' residual does not see it
+    if (rc == SNS_OK && *reason > 0) {
+        const int64_t nd = nred_of(h);
+        hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, h->bc_mask, g, 1e300, lam);
+        rc = sync_stream(h);
+    }
+    // back to A, after a solve that did not converge too; a HIP or transport error leaves the device state undefined
+    if (rc == SNS_E_HIP || rc == SNS_E_COMM) return rc;
+    const std::string err = g_err;
+    const int rb = transpose_operator(h);
+    h->pc_ready = false;
+    if (rc != SNS_OK) { set_error(err); return rc; }
+    return rb;
 }
 
 

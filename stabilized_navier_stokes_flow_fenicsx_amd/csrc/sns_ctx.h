@@ -115,6 +115,8 @@ struct sns_ctx {
     std::vector<policy::LevelPlan> graph_rows;    // ... and the plan rows it covers
     bool graph_disabled = false;
     int matrix_form = -1;
+    bool transposed = false;                     // vals holds A^T (sns_transpose_operator); every assembly clears it
+    int32_t* tr_partner = nullptr;               // [nnzb] slot (i, j) -> slot (j, i), built at the first transpose (csrc/sns_transpose.hip)
     int est_form = -1;                           // form of the matrix the levels' spectral estimates were last taken from
     double est_re = 0.0;                         // ... and its Reynolds number
     // reductions
@@ -225,6 +227,8 @@ int op_residual(sns_ctx* h, double* x, const double* b, double* r);
 int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm);
 // csrc/sns_strength.hip: the strength of the fine-level couplings (amg_aggregation = 1, SNS_EXPORT_STRENGTH)
 int compute_strength(sns_ctx* h, float* out, double* scale);
+// csrc/sns_transpose.hip: flip the fine operator between A and A^T in place
+int transpose_operator(sns_ctx* h);
 // csrc/sns_aggregate.hip: aggregate_strength's map of the owned nodes, built on the device (amg_aggregation = 2)
 int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc);
 // ... and the hybrid (amg_aggregation = 3): the geometric map g (ng aggregates) re-matched where it cuts a dominant coupling

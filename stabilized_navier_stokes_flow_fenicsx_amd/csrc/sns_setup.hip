@@ -736,6 +736,7 @@ int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matri
     }
     if (want_matrix) {
         h->has_matrix = true;
+        h->transposed = false;
         h->pc_ready = false;
         h->matrix_form = form;
     }
@@ -778,6 +779,7 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         hipLaunchKernelGGL((k_fused_diag<SNS_FORM_STOKES, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag,
                            h->c_ptr, h->c_idx, h->tets, h->pts, h->gext, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F);
         h->has_matrix = true;
+        h->transposed = false;
         h->pc_ready = false;
         h->matrix_form = form;
         HIP_TRY(hipGetLastError());
@@ -812,6 +814,7 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
                                    h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F);
         }
         h->has_matrix = true;
+        h->transposed = false;
         h->pc_ready = false;
         h->matrix_form = form;
         HIP_TRY(hipGetLastError());
@@ -842,6 +845,7 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         hipLaunchKernelGGL(k_gather_matrix, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.nnzb,
                            h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->bc_mask, h->Ke, L.vals);
         h->has_matrix = true;
+        h->transposed = false;
         h->pc_ready = false;
         h->matrix_form = form;
     }

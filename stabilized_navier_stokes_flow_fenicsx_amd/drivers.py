@@ -428,6 +428,28 @@ def lid_driven_stokes_main(argv=None):
     return msh, Ug.ravel(), res
 
 
+def _print_reynolds_sensitivities(P, w, wg, grads, grads_nu, names):
+    """SNS_SENSITIVITY=1 (opt-in; single-GPU runs): d<name>/dRe at the converged state for the functionals whose gradients
+    are the rows of ``grads`` (``grads_nu``: their derivative with respect to nu at fixed state, the explicit part), one
+    adjoint solve each (solver.reynolds_sensitivity)."""
+    from .solver import reynolds_sensitivity
+    if getattr(P, "part", None) is not None:
+        if _rank() == 0:
+            print("SNS_SENSITIVITY: adjoint solves run on single-GPU problems only; skipped", flush=True)
+        return None
+    Re = float(P.options.reynolds)
+    out = []
+    for name, g, gnu in zip(names, grads, grads_nu):
+        d, _, res = reynolds_sensitivity(P, w, g, dJ_dRe_explicit=-float(gnu @ wg) / Re ** 2)
+        print(f"d{name}/dRe: {d} (adjoint solve: {res.its} its, reason {res.reason})", flush=True)
+        out.append(d)
+    return out
+
+
+def _sensitivity():
+    return os.environ.get("SNS_SENSITIVITY", "0") == "1"
+
+
 def dfg_2d_main(argv=None):
     """DFG_2D_Validation.py <msh file> (:22-28): Stokes with unit viscosity and mu_T = 0.2 h^2 (:101-125), NS with
     nu = 1e-3 and the UGN stabilisation from the Stokes field (:141-187), drag / lift and their relative errors
@@ -479,6 +501,9 @@ def dfg_2d_main(argv=None):
         print(f"Cd Percent Error: {[(cd - M2.DFG2D_CD_REF) / M2.DFG2D_CD_REF]}", flush=True)
         write_xdmf("DFG2DValidationPressure", msh, "Pressure", wg.reshape(-1, 4)[:, 3].copy())
         write_xdmf("DFG2DValidationVelocity", msh, "Velocity", wg.reshape(-1, 4)[:, :2].copy())
+    if _sensitivity():
+        G1, G0 = M2.drag_lift_2d_gradient(msh, 1.0), M2.drag_lift_2d_gradient(msh, 0.0)
+        _print_reynolds_sensitivities(P, w, wg, G0 + nu * (G1 - G0), G1 - G0, ("C_d", "C_l"))
     r = P.last_newton
     P.close()
     return msh, wg, (cd, cl), r
@@ -518,6 +543,11 @@ def dfg_3d_main(argv=None):
         print(f"Coefficient of Drag: {cd}", flush=True)
         write_xdmf("DFGValidationPressureNavierStokes", msh, "Pressure", wg.reshape(-1, 4)[:, 3].copy())
         write_xdmf("DFGValidationVelocityNavierStokes", msh, "Velocity", wg.reshape(-1, 4)[:, :3].copy())
+    if _sensitivity():
+        sc = Fn.drag_lift_coefficients(np.ones(3))[0]
+        ob = msh.meta["tags"]["obstacle"]
+        G1, G0 = sc * Fn.boundary_traction_gradient(msh, 1.0, ob)[:2], sc * Fn.boundary_traction_gradient(msh, 0.0, ob)[:2]
+        _print_reynolds_sensitivities(P, w, wg, G0 + nu * (G1 - G0), G1 - G0, ("C_d", "C_l"))
     r = P.last_newton
     P.close()
     return msh, wg, (cd, cl), r

@@ -67,6 +67,58 @@ def boundary_traction_force(mesh: TetMesh, w: np.ndarray, nu: float, tag: int) -
     return np.einsum("fij,fj->i", stress, n_area)
 
 
+def boundary_traction_gradient(mesh: TetMesh, nu: float, tag: int) -> np.ndarray:
+    """d(boundary_traction_force)/dw as a (3, 4 n) array G: the force is linear in the state, ``G @ w`` equals
+    ``boundary_traction_force(mesh, w, nu, tag)`` up to the rounding of a reordered sum.  Built from the same arrays
+    (parent tets, P1 gradients, oriented facet areas); G is affine in nu, so the force's explicit nu-derivative at fixed w
+    is ``(boundary_traction_gradient(mesh, 1, tag) - boundary_traction_gradient(mesh, 0, tag)) @ w``.  Row c is the
+    right-hand side of the adjoint solve for force component c (solver.reynolds_sensitivity)."""
+    G = np.zeros((3, 4 * mesh.num_nodes))
+    ids = mesh.find(tag)
+    if len(ids) == 0:
+        return G
+    par = facet_parent_tets(mesh, ids)
+    tn = mesh.tets[par].astype(np.int64)                     # (F,4)
+    X = mesh.points[tn]
+    J = np.stack([X[:, 1] - X[:, 0], X[:, 2] - X[:, 0], X[:, 3] - X[:, 0]], axis=2)
+    K = np.linalg.inv(J)
+    g = np.concatenate([-K.sum(axis=1, keepdims=True), K], axis=1)                      # (F,4,3) grad phi_a
+    fn = mesh.facets[ids].astype(np.int64)
+    P = mesh.points[fn]
+    cr = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    opp = tn.sum(axis=1) - fn.sum(axis=1)
+    sgn = np.sign(np.einsum("fi,fi->f", cr, P[:, 0] - mesh.points[opp]))
+    n_area = -0.5 * cr * sgn[:, None]
+    # force_i = sum_f nu (gu_ij + gu_ji) nA_j - pm nA_i,  gu_ij = sum_a u_i(a) g_aj
+    gn = nu * np.einsum("faj,fj->fa", g, n_area)             # u_i(a) -> force_i
+    gx = nu * np.einsum("fai,fj->faij", g, n_area)           # u_j(a) -> force_i
+    for i in range(3):
+        np.add.at(G[i], 4 * tn + i, gn)
+        for j in range(3):
+            np.add.at(G[i], 4 * tn + j, gx[:, :, i, j])
+        np.add.at(G[i], 4 * fn + 3, np.repeat(-n_area[:, i:i + 1] / 3.0, 3, axis=1))
+    return G
+
+
+def point_value_gradient(mesh: TetMesh, pts, comp: int = 3, padding: float = 1e-6, device=None) -> np.ndarray:
+    """d(value of component ``comp`` of the P1 solution at the points ``pts`` (m,3))/dw as an (m, 4 n) array: the
+    barycentric weights of ``interpolate.locate_points`` -- what ``FlowProblem.eval_at`` evaluates with -- in the columns
+    of the containing tet's nodes.  ``device`` locates on the GPU."""
+    from .interpolate import locate_points
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+    tet, lam = locate_points(mesh, pts, padding, device=device)
+    G = np.zeros((len(pts), 4 * mesh.num_nodes))
+    cols = 4 * mesh.tets[np.asarray(tet, dtype=np.int64)].astype(np.int64) + comp
+    np.add.at(G, (np.arange(len(pts))[:, None], cols), np.asarray(lam, dtype=np.float64))
+    return G
+
+
+def pressure_difference_gradient(mesh: TetMesh, p_front, p_back, padding: float = 1e-6, device=None) -> np.ndarray:
+    """d(p(p_front) - p(p_back))/dw as a dof vector (the DFG benchmarks' pressure drop across the obstacle)."""
+    G = point_value_gradient(mesh, np.stack([np.asarray(p_front, float), np.asarray(p_back, float)]), 3, padding, device)
+    return G[0] - G[1]
+
+
 def drag_lift_coefficients(force: np.ndarray, rho: float = 1.0, Uc: float = 0.2, Lc: float = 0.1 * 0.41):
     """(C_d, C_l) = 2 F / (rho Uc^2 Lc)  (DFG_3D_Validation.py:345-346,364-365; defaults are the script's)."""
     s = 2.0 / (rho * Uc * Uc * Lc)

@@ -440,6 +440,40 @@ def drag_lift_2d(mesh: TriMesh, w, nu: float, tag: int | None = None, U_mean: fl
     return cd, cl
 
 
+def drag_lift_2d_gradient(mesh: TriMesh, nu: float, tag: int | None = None, U_mean: float = 0.2, L: float = 0.1) -> np.ndarray:
+    """d(C_D, C_L)/dw of ``drag_lift_2d`` as a (2, 4 n) array G, built from the same arrays: both coefficients are linear
+    in the state, ``G @ w`` equals ``drag_lift_2d(mesh, w, nu, tag)`` up to the rounding of a reordered sum.  G is affine in
+    nu (explicit nu-derivative at fixed w: (G(nu = 1) - G(nu = 0)) @ w).  The rows are the right-hand sides of the adjoint
+    solves of solver.reynolds_sensitivity."""
+    tag = DFG2D_TAGS["obstacle"] if tag is None else tag
+    ids = mesh.find(tag)
+    G = np.zeros((2, 4 * mesh.num_nodes))
+    par = edge_parent_tris(mesh, ids)
+    tn = mesh.tris[par].astype(np.int64)
+    X = mesh.points[tn]
+    J = np.stack([X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]], axis=2)
+    K = np.linalg.inv(J)
+    g = np.concatenate([-K.sum(axis=1, keepdims=True), K], axis=1)    # (F,3,2)
+    fn = mesh.facets[ids].astype(np.int64)
+    P = mesh.points[fn]
+    tv = P[:, 1] - P[:, 0]
+    ln = np.linalg.norm(tv, axis=1)
+    nf = np.stack([tv[:, 1], -tv[:, 0]], axis=1) / ln[:, None]
+    opp = tn.sum(axis=1) - fn.sum(axis=1)
+    sgn = np.sign(np.einsum("fi,fi->f", nf, P[:, 0] - mesh.points[opp]))
+    n = -nf * sgn[:, None]
+    tt = np.stack([n[:, 1], -n[:, 0]], axis=1)
+    # dut = tt_i gu_ij n_j,  gu_ij = sum_a u_i(a) g_aj  ->  d dut / d u_i(a) = tt_i (g_a . n)
+    ddut = np.einsum("fi,faj,fj->fai", tt, g, n)                      # (F,3,2)
+    c = 2.0 / (U_mean ** 2 * L)
+    for i in range(2):
+        np.add.at(G[0], 4 * tn + i, c * (ln * nu * n[:, 1])[:, None] * ddut[:, :, i])
+        np.add.at(G[1], 4 * tn + i, -c * (ln * nu * n[:, 0])[:, None] * ddut[:, :, i])
+    np.add.at(G[0], 4 * fn + 3, np.repeat((-c * ln * n[:, 0] / 2.0)[:, None], 2, axis=1))
+    np.add.at(G[1], 4 * fn + 3, np.repeat((-c * ln * n[:, 1] / 2.0)[:, None], 2, axis=1))
+    return G
+
+
 def drag_lift_2d_reaction(problem, w, tag: int | None = None, U_mean: float = 0.2, L: float = 0.1):
     """(C_D, C_L) from the residual-based force on the obstacle (functionals.reaction_force on a 2-D problem): F = -R_raw(w)
     tested with the indicator of the obstacle's nodes, C = 2 F / (U^2 L) with the constants of ``drag_lift_2d``.  Same limit

@@ -305,6 +305,28 @@ class FlowProblem:
         check(self.lib.sns_krylov_solve(self.h, _ptr(b), _ptr(x), C.byref(its), C.byref(reason), C.byref(rn)))
         return x, KrylovResult(its.value, reason.value, rn.value)
 
+    def transpose_operator(self):
+        """Flip the assembled fine operator in place between A and A^T (sns_transpose_operator): ``spmv``, ``pc_setup``,
+        ``pc_apply``, ``krylov_solve``, ``bsr`` and ``to_scipy`` then act on A^T until the next call or the next assembly
+        (``jacobian``, ``stokes_solve``, ``newton_solve``), which restores A.  Single-GPU problems only."""
+        check(self.lib.sns_transpose_operator(self.h))
+
+    @property
+    def operator_transposed(self) -> bool:
+        f = C.c_int()
+        check(self.lib.sns_operator_is_transposed(self.h, C.byref(f)))
+        return bool(f.value)
+
+    def adjoint_solve(self, g, x0=None):
+        """A^T lam = g with the operator the handle holds and its ksp / pc options (sns_adjoint_solve: transpose, set-up,
+        Krylov solve, transpose back); the handle holds A again afterwards.  Returns (lam, KrylovResult) like
+        ``krylov_solve``; ``rnorm`` is the true residual norm ||g - A^T lam||."""
+        g = self._vec(g)
+        x = self.zeros() if x0 is None else self._vec(x0).clone()
+        its, reason, rn = C.c_int(), C.c_int(), C.c_double()
+        check(self.lib.sns_adjoint_solve(self.h, _ptr(g), _ptr(x), C.byref(its), C.byref(reason), C.byref(rn)))
+        return x, KrylovResult(its.value, reason.value, rn.value)
+
     def stokes_solve(self):
         U = self.zeros()
         its, reason, rn = C.c_int(), C.c_int(), C.c_double()
@@ -578,6 +600,47 @@ def newton_with_reynolds_continuation(problem: FlowProblem, w: torch.Tensor, max
     w.copy_(cur)
     r.ksp_its = total_ksp
     return w, r
+
+
+def residual_reynolds_derivative(problem: FlowProblem, w, rel_step: float = 1e-4) -> torch.Tensor:
+    """dF/dRe at the state ``w``: central difference of ``problem.residual(w)`` at Re (1 +- rel_step); the problem's
+    options are restored afterwards.  Zero on the Dirichlet rows (F_B = w_B - g does not depend on Re)."""
+    w = problem._vec(w)
+    Re = float(problem.options.reynolds)
+    try:
+        problem.set_options(reynolds=Re * (1.0 + rel_step))
+        Fp = problem.residual(w, "ns")
+        problem.set_options(reynolds=Re * (1.0 - rel_step))
+        Fm = problem.residual(w, "ns")
+    finally:
+        problem.set_options(reynolds=Re)
+    return (Fp - Fm) / (2.0 * Re * rel_step)
+
+
+def reynolds_sensitivity(problem: FlowProblem, w, grad_J, dJ_dRe_explicit: float = 0.0, rel_step: float = 1e-4):
+    """Total derivative dJ/dRe of a functional J(w(Re), Re) at a converged state ``w`` (F(w; Re) = 0) by ONE adjoint solve
+    with the Jacobian Newton assembles anyway, instead of the two extra nonlinear solves of a finite difference:
+
+        A = dF/dw at w  (``problem.jacobian(w)``),    A^T lam = grad_J  (``problem.adjoint_solve``),
+        dJ/dRe = dJ_dRe_explicit - lam . dF/dRe       (dF/dRe: ``residual_reynolds_derivative``)
+
+    ``grad_J``: dJ/dw as a dof vector (numpy or device), e.g. a row of ``functionals.boundary_traction_gradient``.  This is
+    the total derivative because the Dirichlet values do not move with Re (dw_B = 0): the assembled operator is the Jacobian
+    of F on the free dofs and the identity on the Dirichlet dofs, where dF_B/dRe = 0.  A functional that depends on
+    nu = 1/Re explicitly -- the traction's 2 nu sym grad u term -- contributes ``dJ_dRe_explicit`` = dJ/dnu * (-1/Re^2) at
+    fixed w; for the traction, which is linear in nu:
+
+        G1, G0 = boundary_traction_gradient(mesh, 1.0, tag), boundary_traction_gradient(mesh, 0.0, tag)
+        explicit = -((G1 - G0)[0] @ w) / Re**2        # drag component
+
+    Returns (dJ/dRe, lam, KrylovResult of the adjoint solve).  The handle is left with the Jacobian at w assembled and the
+    caller's options.  Single-GPU problems."""
+    w = problem._vec(w)
+    g = problem._vec(grad_J if isinstance(grad_J, torch.Tensor) else np.asarray(grad_J, dtype=np.float64).ravel())
+    problem.jacobian(w, "ns")
+    lam, res = problem.adjoint_solve(g)
+    dF = residual_reynolds_derivative(problem, w, rel_step)
+    return float(dJ_dRe_explicit) - float(torch.dot(lam, dF)), lam, res
 
 
 def solve_navier_stokes(problem: FlowProblem, w: torch.Tensor, rank: int = 0, continuation: bool = False):
