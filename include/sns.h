@@ -422,6 +422,30 @@ SNS_API int sns_stokes_solve(sns_handle h, double* U_dev, int* ksp_its, int* rea
  * (snes_monitor :276), at most hist_cap entries.                              */
 SNS_API int sns_newton_solve(sns_handle h, double* w_dev, int* its, int* reason,
                      int* total_ksp_its, double* fnorm_hist, int hist_cap);
+/* Time term of the 3-D NS form.  The reference has no counterpart: all of its forms are steady; this is the standard
+ * VMS / SUPG-PSPG extension of its G-metric form (:220-251).  With the discrete time derivative u_t = sigma u + d (d_dev:
+ * 4*n_local doubles, node-blocked like the state, pressure slots ignored; copied into a buffer the handle owns) every NS
+ * assembly of the handle from this call on -- sns_residual, sns_jacobian, sns_newton_solve, sns_residual_moments,
+ * sns_bench_assemble -- takes the transient form: (u_t, v) joins the Galerkin part, res_M becomes res_M + u_t in the SUPG
+ * and the PSPG term, and tau = (theta + u.Gu + C_I nu^2 G:G)^-1/2 (nu_LSIC = 1/(tr G tau) with the same tau; theta =
+ * 4/dt^2 is the usual choice, 0 keeps the steady tau).  The Jacobian is the exact Gateaux derivative with d held fixed.
+ * BDF1: sigma = 1/dt, d = -u^n/dt;  BDF2: sigma = 3/(2 dt), d = (-2 u^n + u^(n-1)/2)/dt.  sigma = 0, theta = 0 and
+ * d_dev = NULL remove the term: the handle is the steady handle again, bit for bit.  The Stokes form ignores the term;
+ * sns_set_form_variant and corrected_convection apply as for the steady form.  An assembled matrix stays what it was;
+ * a change of sigma or theta makes the next preconditioner set-up re-estimate its smoother damping.
+ * SNS_E_ARG: a 2-D handle; sigma or theta negative or not finite; sigma > 0 without d_dev.  SNS_E_STATE: a handle with
+ * a communicator attached (any transport, also the local-only split; as for the adjoint solves).                     */
+SNS_API int sns_set_time_term(sns_handle h, double sigma, double theta, const double* d_dev);
+/* One implicit time step of the transient form above (the reference has no counterpart).  On entry w_dev = u^n with
+ * p^n as the pressure guess and wprev_dev = u^(n-1) (ignored, may be NULL, for order 1).  Builds d on the device (order
+ * 1: BDF1, order 2: BDF2), sets the term with theta = theta_coeff / dt^2 and runs the Newton loop of sns_newton_solve
+ * (same options, same line search) from the guess u^n.  On exit w_dev = u^(n+1) and, where given, wprev_dev = u^n.  The
+ * term stays set, so sns_residual_moments returns the force consistent with the step just taken.  Non-convergence is
+ * reported through *reason as everywhere else; w_dev and wprev_dev then hold their entry values.  total_ksp_its may be
+ * NULL.  SNS_E_ARG: order outside {1, 2}, dt <= 0, order 2 without wprev_dev, and as sns_set_time_term; SNS_E_STATE
+ * as there.                                                                                                          */
+SNS_API int sns_time_step(sns_handle h, double* w_dev, double* wprev_dev, double dt, int order, double theta_coeff,
+                          int* its, int* reason, int* total_ksp_its);
 
 /* ---- introspection (tests, profiling) --------------------------------------*/
 /* device pointers of the assembled BSR4 operator (block row-major 4x4); the values are those of A^T while the handle

@@ -275,7 +275,7 @@ int sns_destroy(sns_handle h) {
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(h->tets); fr(h->pts); fr(h->bc_mask); fr(h->bc_val);
     fr(h->nt_ptr); fr(h->nt_idx); fr(h->c_ptr); fr(h->c_idx); fr(h->od_order); fr(h->gext); fr(h->Ke); fr(h->Fe);
-    fr(h->rm_off); fr(h->rm_cells); fr(h->rm_Fe); fr(h->rm_nomask); fr(h->tr_partner);
+    fr(h->rm_off); fr(h->rm_cells); fr(h->rm_Fe); fr(h->rm_nomask); fr(h->tr_partner); fr(h->tt_d); fr(h->tt_w0);
     for (auto& L : h->levels) {
         fr(L.rowptr); fr(L.colind); fr(L.diag); fr(L.vals); fr(L.dinv); fr(L.agg); fr(L.m_ptr); fr(L.m_idx);
         fr(L.r_ptr); fr(L.r_idx); fr(L.free_mask); fr(L.x); fr(L.b); fr(L.r); fr(L.dense_inv); fr(L.dense_gj); fr(L.dense_work); fr(L.dense_x32); fr(L.vals32); fr(L.vals16); fr(L.scale16); fr(L.dinv32);
@@ -575,10 +575,12 @@ int sns_residual_moments(sns_handle h, int form, const double* w, const double* 
                 hipLaunchKernelGGL(k_residual_tri_stokes, dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w,
                                    h->opt.stokes_viscosity, h->opt.stokes_beta, h->rm_Fe);
         } else if (form == SNS_FORM_NS && h->fv.is_default()) {
-            if (!h->opt.corrected_convection)
-                hipLaunchKernelGGL((k_residual_tet<false>), dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w, nu, h->rm_Fe);
-            else
-                hipLaunchKernelGGL((k_residual_tet<true>), dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w, nu, h->rm_Fe);
+            dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
+                dispatch<1, 0>(h->tt_on, [&](auto T) {
+                    hipLaunchKernelGGL((k_residual_tet<C() != 0, T() != 0>), dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells,
+                                       h->pts, w, nu, h->rm_Fe, h->tt);
+                });
+            });
         } else {
             if (!h->rm_nomask) {
                 SNS_TRY(dev_alloc(&h->rm_nomask, (size_t)ndof));
@@ -587,13 +589,15 @@ int sns_residual_moments(sns_handle h, int form, const double* w, const double* 
             const unsigned ge = (unsigned)((nc + EL_TETS_PER_BLOCK - 1) / EL_TETS_PER_BLOCK);
             if (form == SNS_FORM_STOKES)
                 hipLaunchKernelGGL((k_element<SNS_FORM_STOKES, false>), dim3(ge), dim3(256), 0, h->stream, nc, h->rm_cells,
-                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv);
-            else if (!h->opt.corrected_convection)
-                hipLaunchKernelGGL((k_element<SNS_FORM_NS, false>), dim3(ge), dim3(256), 0, h->stream, nc, h->rm_cells,
-                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv);
+                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv, TimeTerm());
             else
-                hipLaunchKernelGGL((k_element<SNS_FORM_NS, true>), dim3(ge), dim3(256), 0, h->stream, nc, h->rm_cells,
-                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv);
+                dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
+                    dispatch<1, 0>(h->tt_on, [&](auto T) {
+                        hipLaunchKernelGGL((k_element<SNS_FORM_NS, C() != 0, T() != 0>), dim3(ge), dim3(256), 0, h->stream, nc,
+                                           h->rm_cells, h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe,
+                                           h->fv, h->tt);
+                    });
+                });
         }
     }
     // fixed-order two-stage reduction (grid fixed by the support size), then the handle's all-reduce over the ranks
@@ -694,9 +698,9 @@ int sns_stokes_solve(sns_handle h, double* U, int* ksp_its, int* reason, double*
 }
 
 
-int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int* total_ksp, double* hist,
-                     int hist_cap) {
-    if (!h || !w || !its_out || !reason_out) return SNS_E_ARG;
+// The Newton loop (newtonls + bt of the reference, :255-272) on whatever NS form the handle carries: the steady form for
+// sns_newton_solve, the transient form of the step for sns_time_step.
+static int newton_run(sns_ctx* h, double* w, int* its_out, int* reason_out, int* total_ksp, double* hist, int hist_cap) {
     SNS_TRY(ensure_hierarchy(h, true));
     const sns_options& o = h->opt;
     const int64_t nd = nred_of(h), ld = ld_of(h);
@@ -791,6 +795,77 @@ int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int
     *reason_out = reason;
     if (total_ksp) *total_ksp = ksp_total;
     return SNS_OK;
+}
+
+int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int* total_ksp, double* hist,
+                     int hist_cap) {
+    if (!h || !w || !its_out || !reason_out) return SNS_E_ARG;
+    return newton_run(h, w, its_out, reason_out, total_ksp, hist, hist_cap);
+}
+
+int sns_set_time_term(sns_handle h, double sigma, double theta, const double* d_dev) {
+    if (!h) return SNS_E_ARG;
+    if (h->dim != 3) { set_error("sns_set_time_term: 3-D handles only"); return SNS_E_ARG; }
+    if (!(sigma >= 0.0) || !std::isfinite(sigma) || !(theta >= 0.0) || !std::isfinite(theta)) {
+        set_error("sns_set_time_term: sigma and theta must be finite and >= 0");
+        return SNS_E_ARG;
+    }
+    if (sigma > 0.0 && !d_dev) { set_error("sns_set_time_term: sigma > 0 needs a history vector"); return SNS_E_ARG; }
+    if (h->comm) { set_error("sns_set_time_term: not with a communicator attached (partitioned time stepping is not built)"); return SNS_E_STATE; }
+    if (sigma != h->tt.sigma || theta != h->tt.theta) {   // another operator: re-estimate the smoother's damping caps
+        h->est_form = -1;
+        h->pc_ready = false;
+    }
+    if (sigma == 0.0 && theta == 0.0 && !d_dev) {         // back to the steady form (the buffer stays with the handle)
+        h->tt = TimeTerm();
+        h->tt_on = false;
+        return SNS_OK;
+    }
+    const size_t ld = (size_t)ld_of(h);
+    if (!h->tt_d) SNS_TRY(dev_alloc(&h->tt_d, ld));
+    if (d_dev) HIP_TRY(hipMemcpyAsync(h->tt_d, d_dev, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    else HIP_TRY(hipMemsetAsync(h->tt_d, 0, ld * sizeof(double), h->stream));
+    SNS_TRY(sync_stream(h));                              // the caller may free d_dev
+    h->tt.sigma = sigma;
+    h->tt.theta = theta;
+    h->tt.d = h->tt_d;
+    h->tt_on = true;
+    return SNS_OK;
+}
+
+int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, double theta_coeff, int* its, int* reason,
+                  int* ksp_its) {
+    if (!h || !w || !its || !reason) return SNS_E_ARG;
+    if (order != 1 && order != 2) { set_error("sns_time_step: order must be 1 or 2"); return SNS_E_ARG; }
+    if (!(dt > 0.0) || !std::isfinite(dt)) { set_error("sns_time_step: dt must be positive"); return SNS_E_ARG; }
+    if (order == 2 && !wprev) { set_error("sns_time_step: BDF2 needs the state before w"); return SNS_E_ARG; }
+    if (h->dim != 3) { set_error("sns_time_step: 3-D handles only"); return SNS_E_ARG; }
+    if (!(theta_coeff >= 0.0) || !std::isfinite(theta_coeff)) { set_error("sns_time_step: theta_coeff must be finite and >= 0"); return SNS_E_ARG; }
+    if (h->comm) { set_error("sns_time_step: not with a communicator attached (partitioned time stepping is not built)"); return SNS_E_STATE; }
+    const int64_t ld = ld_of(h);
+    const int g = vec_grid(ld);
+    // BDF1: u_t = (u - u^n) / dt;  BDF2: u_t = (3 u - 4 u^n + u^(n-1)) / (2 dt).  d in a workspace vector (copied by
+    // sns_set_time_term), the entry state in a buffer of its own (a step that does not converge restores it)
+    double *d = nullptr, *w0 = nullptr;
+    SNS_TRY(get_vec(h, 13, &d));
+    if (!h->tt_w0) SNS_TRY(dev_alloc(&h->tt_w0, (size_t)ld));
+    w0 = h->tt_w0;
+    const double sigma = (order == 1 ? 1.0 : 1.5) / dt;
+    hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, ld, (order == 1 ? -1.0 : -2.0) / dt, w, d);
+    if (order == 2) hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, h->stream, ld, 0.5 / dt, wprev, 1.0, d);
+    HIP_TRY(hipMemcpyAsync(w0, w, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    SNS_TRY(sns_set_time_term(h, sigma, theta_coeff / (dt * dt), d));
+    const int rc = newton_run(h, w, its, reason, ksp_its, nullptr, 0);
+    if (rc != SNS_OK) {                                   // the entry state also where the loop gave up with an error
+        if (rc != SNS_E_HIP) (void)hipMemcpy(w, w0, ld * sizeof(double), hipMemcpyDeviceToDevice);
+        return rc;
+    }
+    if (*reason > 0) {
+        if (wprev) HIP_TRY(hipMemcpyAsync(wprev, w0, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(w, w0, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
+    return sync_stream(h);
 }
 
 

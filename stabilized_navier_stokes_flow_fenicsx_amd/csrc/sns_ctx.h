@@ -105,6 +105,12 @@ struct sns_ctx {
     int* d_piv = nullptr;
     int* d_sing = nullptr;
     FormVariant fv;                              // sns_set_form_variant (diagnostic; default = the reference's form)
+    // sns_set_time_term: the transient 3-D NS form.  tt.d points at tt_d, the handle's copy of the history (4*n doubles,
+    // allocated at the first set); tt_on selects the TT instantiations of the NS assembly kernels
+    TimeTerm tt;
+    double* tt_d = nullptr;
+    double* tt_w0 = nullptr;                     // sns_time_step: the state on entry
+    bool tt_on = false;
     bool has_matrix = false, pc_ready = false;
     int pc_setups = 0;
     // hipGraph of the launch-bound coarse part of the V-cycle (levels >= graph_level; serial runs only)

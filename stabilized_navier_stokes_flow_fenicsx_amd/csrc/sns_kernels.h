@@ -28,26 +28,35 @@ struct FormVariant {
     bool is_default() const { return ci == 36.0 && lsic == 1.0 && pspg == 1.0 && qa == 0.1381966011250105 && qb == 0.5854101966249685; }
 };
 
-template <int FORM, bool corrected>
+// Time term of the 3-D NS form (sns_set_time_term; the reference has no unsteady form): u_t = sigma u + d with the nodal
+// history d (node-blocked like the state, pressure slots unused), (u_t, v) added to the Galerkin part, u_t added to the
+// strong residual res_M of the SUPG/PSPG term, theta added under the root of tau.  The kernels take it as the compile-time
+// variant TT; the steady instantiations (TT = false) never read the struct.
+struct TimeTerm {
+    double sigma = 0.0, theta = 0.0;
+    const double* d = nullptr;
+};
+
+template <int FORM, bool corrected, bool TT = false>
 __global__ void k_element(int64_t n_tets, const int32_t* tets, const double* pts, const double* w,
                           const uint8_t* bc_mask, const double* bc_val, double nu, int store_K, double* Ke,
-                          double* Fe, FormVariant fv);
-template <int FORM, bool corrected>
+                          double* Fe, FormVariant fv, TimeTerm tt);
+template <int FORM, bool corrected, bool TT = false>
 __global__ void k_fused_offdiag(int64_t n_od, const int32_t* od_order, const int64_t* c_ptr, const int32_t* c_idx, const int32_t* slot_row,
                                 const int32_t* colind, const int32_t* tets, const double* pts, const double* w,
-                                const uint8_t* bc_mask, double nu, double aux, double* vals);
-template <int FORM, bool corrected>
+                                const uint8_t* bc_mask, double nu, double aux, double* vals, TimeTerm tt);
+template <int FORM, bool corrected, bool TT = false>
 __global__ void k_fused_diag(int32_t n_rows, const int32_t* diag, const int64_t* c_ptr, const int32_t* c_idx,
                              const int32_t* tets, const double* pts, const double* w, const uint8_t* bc_mask,
-                             const double* bc_val, double nu, double aux, double* vals, double* F);
-template <int FORM, bool corrected>
+                             const double* bc_val, double nu, double aux, double* vals, double* F, TimeTerm tt);
+template <int FORM, bool corrected, bool TT = false>
 __global__ void k_fused_lift(int32_t n_rows, const int32_t* diag, const int64_t* c_ptr, const int32_t* c_idx,
                              const int32_t* tets, const double* pts, const double* w, const uint8_t* bc_mask,
-                             const double* dl, double nu, double* F);
+                             const double* dl, double nu, double* F, TimeTerm tt);
 __global__ void k_bc_defect(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, const double* w, double* dl);
-template <bool corrected>
+template <bool corrected, bool TT = false>
 __global__ void k_residual_tet(int64_t n_tets, const int32_t* tets, const double* pts, const double* w, double nu,
-                               double* Fe);
+                               double* Fe, TimeTerm tt);
 __global__ void k_residual_tri(int64_t n_tris, const int32_t* tets, const double* pts, const double* w, double nu,
                                double* Fe);
 __global__ void k_bc_residual(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, const double* w, double* F);

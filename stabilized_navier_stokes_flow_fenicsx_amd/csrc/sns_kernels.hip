@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "sns_kernels.h"
 
@@ -50,21 +51,28 @@ struct TetLds {
     double q[4][16];   // per point: u[3], p, tau, nuL, Gu[3], conv[3], s[4]
 };
 
+// ... with a time term (TT): the nodal history and the per-point u_t = sigma u + d
+struct TetLdsT : TetLds {
+    double D[12];      // d [a][i]
+    double ut[4][3];
+};
+
 __device__ __forceinline__ double phi_q(int q, int a) { return q == a ? QB : QA; }
 
-template <int FORM, bool corrected>
+template <int FORM, bool corrected, bool TT>
 __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int32_t* __restrict__ tets,
                                                     const double* __restrict__ pts,
                                                     const double* __restrict__ w,
                                                     const uint8_t* __restrict__ bc_mask,
                                                     const double* __restrict__ bc_val, double nu,
                                                     int store_K, double* __restrict__ Ke,
-                                                    double* __restrict__ Fe, FormVariant fv) {
+                                                    double* __restrict__ Fe, FormVariant fv, TimeTerm tt) {
     // staging data and the output transpose tile share LDS (the tile is written after a barrier
     // that retires every read of the staging data): 34.8 KB per workgroup -> 4 workgroups per CU
-    constexpr size_t SH_BYTES = sizeof(TetLds) * EL_TETS, TILE_BYTES = sizeof(double) * EL_TPB * 17;
+    using Lds = std::conditional_t<TT, TetLdsT, TetLds>;
+    constexpr size_t SH_BYTES = sizeof(Lds) * EL_TETS, TILE_BYTES = sizeof(double) * EL_TPB * 17;
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[SH_BYTES > TILE_BYTES ? SH_BYTES : TILE_BYTES];
-    TetLds* sh = reinterpret_cast<TetLds*>(lds_raw);
+    Lds* sh = reinterpret_cast<Lds*>(lds_raw);
     double* tile = reinterpret_cast<double*>(lds_raw);
 
     const int tid = threadIdx.x;
@@ -73,7 +81,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
     const int a = l >> 2, b = l & 3;
     const int64_t t = (int64_t)blockIdx.x * EL_TETS + tl;
     const bool live = t < n_tets;
-    TetLds& S = sh[tl];
+    Lds& S = sh[tl];
 
     // ---- stage nodal data ----------------------------------------------------
     if (live) {
@@ -82,6 +90,9 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
         const double wv = w ? w[dof] : 0.0;
         S.W[l] = wv;
         S.GW[l] = bc_mask[dof] ? (bc_val[dof] - wv) : 0.0;
+        if constexpr (TT) {
+            if (b < 3) S.D[3 * a + b] = tt.d[dof];
+        }
         if (l < 12) {
             const int32_t nv = tets[4 * t + l / 3];
             S.X[l] = pts[3 * (int64_t)nv + l % 3];
@@ -194,7 +205,21 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
 #pragma unroll
             for (int j = 0; j < 3; ++j)                       // res_M :241  (reference: dot(u, grad(u)) = (grad u)^T u)
                 r[j] = (corrected ? conv[j] : (gu[0][j] * u[0] + gu[1][j] * u[1] + gu[2][j] * u[2])) + gp[j];
-            const double tau = 1.0 / sqrt(uGu + fv.ci * nu * nu * GG);                    // :237-238 (C_I = 36)
+            double theta = 0.0;
+            if constexpr (TT) {
+                // u_t = sigma u + d at the point, into res_M; theta under the root of tau
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    double dq = 0.0;
+#pragma unroll
+                    for (int aa = 0; aa < 4; ++aa) dq += ((q == aa) ? fv.qb : fv.qa) * S.D[3 * aa + i];
+                    const double ut = tt.sigma * u[i] + dq;
+                    S.ut[q][i] = ut;
+                    r[i] += ut;
+                }
+                theta = tt.theta;
+            }
+            const double tau = 1.0 / sqrt(theta + uGu + fv.ci * nu * nu * GG);            // :237-238 (C_I = 36)
             const double nuL = fv.lsic / (trG * tau);                                    // :249
             double* Q = S.q[q];
             Q[0] = u[0]; Q[1] = u[1]; Q[2] = u[2]; Q[3] = p; Q[4] = tau; Q[5] = nuL;
@@ -258,13 +283,15 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                     if (!corrected) {
                         // d(r.g_a) = u_j g_a.g_b + phi_b ((grad u) g_a)_j
                         cu[j] = dtau * sa + tau * (u[j] * gab + pb * guga_a[j]);
+                        if constexpr (TT) cu[j] += tau * tt.sigma * pb * ga[j];      // d(u_t.g_a)
                     } else {
                         cu[j] = dtau;                                              // used differently below
                     }
                 }
                 if (!need_blocks) {
                 } else if (!corrected) {
-                    const double A1 = pa * ugb + nu * gab + tau * sa * pb;
+                    double A1 = pa * ugb + nu * gab + tau * sa * pb;
+                    if constexpr (TT) A1 += tt.sigma * pa * pb;                       // mass
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -286,8 +313,15 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
 #pragma unroll
                     for (int j = 0; j < 3; ++j)
                         gp[j] = S.W[3] * S.g[j] + S.W[7] * S.g[3 + j] + S.W[11] * S.g[6 + j] + S.W[15] * S.g[9 + j];
-                    const double r[3] = {r0 + gp[0], r1 + gp[1], r2 + gp[2]};
-                    const double A1 = pa * ugb + nu * gab + tau * uga * ugb;
+                    double r[3] = {r0 + gp[0], r1 + gp[1], r2 + gp[2]};
+                    double A1 = pa * ugb + nu * gab + tau * uga * ugb;
+                    double mp = 0.0;                                                  // d(tau u_t.g_a) / d u_(b,i) / g_a[i]
+                    if constexpr (TT) {
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) r[i] += S.ut[q][i];
+                        A1 += tt.sigma * pb * (pa + tau * uga);                       // mass + SUPG of u_t
+                        mp = fv.pspg * tau * tt.sigma * pb;
+                    }
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -301,6 +335,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                         acc[4 * i + 3] += -pb * ga[i] + tau * uga * gb[i];       // d r_i / d p_b = g_b[i]
                         // continuity row: phi_a g_b[j] + d(tau r.g_a)
                         acc[12 + i] += pa * gb[i] + fv.pspg * (cu[i] * sa + tau * (ugb * ga[i] + pb * guga_a[i]));
+                        if constexpr (TT) acc[12 + i] += mp * ga[i];
                     }
                     acc[15] += fv.pspg * tau * gab;
                 }
@@ -310,6 +345,10 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
 #pragma unroll
                         for (int i = 0; i < 3; ++i)
                             Rl[i] += Q[9 + i] * pa + nu * guga_a[i] - p * ga[i] + tau * u[i] * sa + nuL * divu * ga[i];
+                        if constexpr (TT) {
+#pragma unroll
+                            for (int i = 0; i < 3; ++i) Rl[i] += pa * S.ut[q][i];
+                        }
                     } else {
                         double gp[3];
 #pragma unroll
@@ -323,6 +362,10 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                         for (int i = 0; i < 3; ++i)
                             Rl[i] += Q[9 + i] * pa + nu * vg[i] - p * ga[i] + tau * uga * (Q[9 + i] + gp[i]) +
                                      nuL * divu * ga[i];
+                        if constexpr (TT) {
+#pragma unroll
+                            for (int i = 0; i < 3; ++i) Rl[i] += (pa + tau * uga) * S.ut[q][i];
+                        }
                     }
                     Rl[3] += pa * divu + fv.pspg * tau * sa;
                 }
@@ -373,12 +416,15 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
     }
 }
 
-#define SNS_INST_ELEMENT(F, C)                                                                              \
-    template __global__ void k_element<F, C>(int64_t, const int32_t*, const double*, const double*,            \
-                                             const uint8_t*, const double*, double, int, double*, double*, FormVariant);
-SNS_INST_ELEMENT(SNS_FORM_STOKES, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, true)
+#define SNS_INST_ELEMENT(F, C, T)                                                                           \
+    template __global__ void k_element<F, C, T>(int64_t, const int32_t*, const double*, const double*,         \
+                                                const uint8_t*, const double*, double, int, double*, double*,  \
+                                                FormVariant, TimeTerm);
+SNS_INST_ELEMENT(SNS_FORM_STOKES, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, true)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, true)
 
 // quad-permute a double with DPP moves (no LDS, no memory traffic); CTRL = quad_perm encoding
 template <int CTRL>
@@ -398,10 +444,10 @@ __device__ __forceinline__ double quad_perm(double v) {
 // when the state satisfies the Dirichlet data (no lifting term, :65), i.e. every Newton iterate
 // after the first update; the staged k_element path handles the rest.
 // ============================================================================
-template <bool corrected>
+template <bool corrected, bool TT>
 __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double* __restrict__ pts,
                                                      const double* __restrict__ w, double nu, int a, int b,
-                                                     bool want_res, double acc[16], double Ra[4]) {
+                                                     bool want_res, double acc[16], double Ra[4], const TimeTerm& tt) {
     const int32_t nd[4] = {tv.x, tv.y, tv.z, tv.w};
     double X[4][3], W[4][4];
 #pragma unroll
@@ -456,7 +502,22 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
     }
     const double divu = gu[0][0] + gu[1][1] + gu[2][2];
     const double wd = fabs(det) * (1.0 / 24.0);
-    const double itrG = 1.0 / trG, nu36GG = 36.0 * nu * nu * GG;
+    const double itrG = 1.0 / trG;
+    // the part of tau^-2 that does not depend on the point: theta (time term) + C_I nu^2 G:G
+    const double m0 = (TT ? tt.theta : 0.0) + 36.0 * nu * nu * GG;
+    // time term: the nodal u_t = sigma u + d once, interpolated per point below (one more 3-vector gather per vertex)
+    double UT[TT ? 4 : 1][3];
+    if constexpr (TT) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const double* dp = tt.d + 4 * (int64_t)nd[v];
+            const double2 d01 = *reinterpret_cast<const double2*>(dp);
+            UT[v][0] = tt.sigma * W[v][0] + d01.x;
+            UT[v][1] = tt.sigma * W[v][1] + d01.y;
+            UT[v][2] = tt.sigma * W[v][2] + dp[2];
+        }
+    }
+    const double sg = TT ? tt.sigma : 0.0;
     // runtime-indexed rows of g: select with predication (keeps everything in registers)
     double ga[3], gb[3];
 #pragma unroll
@@ -492,8 +553,18 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             r[j] = (corrected ? conv[j] : (gu[0][j] * u[0] + gu[1][j] * u[1] + gu[2][j] * u[2])) + gp[j];
+        double ut[3] = {0.0, 0.0, 0.0};
+        if constexpr (TT) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const double ph = phi_q(q, v);
+                ut[0] += ph * UT[v][0]; ut[1] += ph * UT[v][1]; ut[2] += ph * UT[v][2];
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) r[j] += ut[j];           // res_M gains u_t
+        }
         // tau = m^-1/2, nu_LSIC = 1/(trG tau) = m tau / trG: one rsqrt per point, no divisions
-        const double mq = uGu + nu36GG;
+        const double mq = uGu + m0;
         const double tau = rsqrt(mq);
         const double nuL = mq * tau * itrG;
         const double sa = r[0] * ga[0] + r[1] * ga[1] + r[2] * ga[2];
@@ -509,9 +580,11 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
             const double dnuL = (tw * itrG) * pb * Gu[j];
             cg[j] = dnuL * divu + (wd * nuL) * gb[j];
             cu[j] = corrected ? dtau : dtau * sa + tw * (u[j] * gab + pb * guga[j]);
+            if constexpr (TT && !corrected) cu[j] += (tw * sg * pb) * ga[j];               // d(u_t.g_a)
         }
         if (!corrected) {
-            const double A1 = wpa * ugb + (wd * nu) * gab + tw * sa * pb;
+            double A1 = wpa * ugb + (wd * nu) * gab + tw * sa * pb;
+            if constexpr (TT) A1 += sg * wpa * pb;                                         // mass
             const double ppw = wpa * pb, tgw = tw * gab;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -523,8 +596,10 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
             }
             acc[15] += tgw;
         } else {
-            const double A1 = wpa * ugb + (wd * nu) * gab + tw * uga * ugb;
+            double A1 = wpa * ugb + (wd * nu) * gab + tw * uga * ugb;
             const double cgu = wpa * pb + tw * uga * pb;       // coefficient of gu[i][j]
+            if constexpr (TT) A1 += sg * cgu;                   // mass + SUPG of u_t
+            const double mp = TT ? tw * sg * pb : 0.0;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -533,6 +608,7 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
                 acc[5 * i] += A1;
                 acc[4 * i + 3] += tw * uga * gb[i] - wpb * ga[i];
                 acc[12 + i] += wpa * gb[i] + cu[i] * sa + tw * (ugb * ga[i] + pb * guga[i]);
+                if constexpr (TT) acc[12 + i] += mp * ga[i];
             }
             acc[15] += tw * gab;
         }
@@ -542,6 +618,10 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
                 Ra[i] += wpa * conv[i] + (wd * nu) * visc[i] - (wd * p) * ga[i] +
                          (corrected ? tw * uga * r[i] : tw * u[i] * sa) + (wd * nuL) * divu * ga[i];
             Ra[3] += wpa * divu + tw * sa;
+            if constexpr (TT) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) Ra[i] += wpa * ut[i];
+            }
         }
     }
 }
@@ -826,19 +906,20 @@ __device__ __forceinline__ void tri_block_accumulate_stokes(const int4 tv, const
 
 // one interface for the four forms (aux: Stokes 2-D pressure-stabilisation coefficient beta; nu: 1/Re, or the
 // Stokes 2-D viscosity)
-template <int FORM, bool corrected>
+template <int FORM, bool corrected, bool TT>
 __device__ __forceinline__ void block_accumulate(const int4 tv, const double* __restrict__ pts,
                                                  const double* __restrict__ w, double nu, double aux, int a, int b,
-                                                 bool want_res, double acc[16], double Ra[4]) {
+                                                 bool want_res, double acc[16], double Ra[4], const TimeTerm& tt) {
+    static_assert(!TT || FORM == SNS_FORM_NS, "the time term exists in the 3-D NS form only");
     if constexpr (FORM == SNS_FORM_STOKES) tet_block_accumulate_stokes(tv, pts, w, a, b, want_res, acc, Ra);
-    else if constexpr (FORM == SNS_FORM_NS) tet_block_accumulate<corrected>(tv, pts, w, nu, a, b, want_res, acc, Ra);
+    else if constexpr (FORM == SNS_FORM_NS) tet_block_accumulate<corrected, TT>(tv, pts, w, nu, a, b, want_res, acc, Ra, tt);
     else if constexpr (FORM == SNS_FORM_STOKES_2D) tri_block_accumulate_stokes(tv, pts, w, nu, aux, a, b, want_res, acc, Ra);
     else tri_block_accumulate_ugn(tv, pts, w, nu, a, b, want_res, acc, Ra);
 }
 constexpr bool form_is_linear(int form) { return form == SNS_FORM_STOKES || form == SNS_FORM_STOKES_2D; }
 
 // off-diagonal BSR blocks: one lane per slot, slots taken from the host's count-sorted list
-template <int FORM, bool corrected>
+template <int FORM, bool corrected, bool TT>
 __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32_t* __restrict__ od_order,
                                                        const int64_t* __restrict__ c_ptr,
                                                        const int32_t* __restrict__ c_idx,
@@ -847,7 +928,7 @@ __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32
                                                        const int32_t* __restrict__ tets,
                                                        const double* __restrict__ pts, const double* __restrict__ w,
                                                        const uint8_t* __restrict__ bc_mask, double nu,
-                                                       double aux, double* __restrict__ vals) {
+                                                       double aux, double* __restrict__ vals, TimeTerm tt) {
     const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= n_od) return;
     const int64_t s = od_order[lane];
@@ -872,7 +953,7 @@ __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32
             id = (uint32_t)c_idx[k];
             tv = *reinterpret_cast<const int4*>(tets + 4 * (int64_t)(id >> 4));
         }
-        block_accumulate<FORM, corrected>(tvc, pts, w, nu, aux, (idc >> 2) & 3, idc & 3, false, acc, nullptr);
+        block_accumulate<FORM, corrected, TT>(tvc, pts, w, nu, aux, (idc >> 2) & 3, idc & 3, false, acc, nullptr, tt);
     }
     const uchar4 mr = *reinterpret_cast<const uchar4*>(bc_mask + 4 * (int64_t)row);
     const uchar4 mc = *reinterpret_cast<const uchar4*>(bc_mask + 4 * (int64_t)col);
@@ -888,14 +969,14 @@ __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32
 }
 
 // diagonal blocks + node residuals: 4 lanes per node share the ~24 incident tets, DPP quad sums in a fixed order
-template <int FORM, bool corrected>
+template <int FORM, bool corrected, bool TT>
 __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_t* __restrict__ diag,
                                                     const int64_t* __restrict__ c_ptr,
                                                     const int32_t* __restrict__ c_idx,
                                                     const int32_t* __restrict__ tets, const double* __restrict__ pts,
                                                     const double* __restrict__ w, const uint8_t* __restrict__ bc_mask,
                                                     const double* __restrict__ bc_val, double nu, double aux,
-                                                    double* __restrict__ vals, double* __restrict__ F) {
+                                                    double* __restrict__ vals, double* __restrict__ F, TimeTerm tt) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t node = gid >> 2;
     const int q = (int)(gid & 3);
@@ -922,7 +1003,7 @@ __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_
                 id = (uint32_t)c_idx[k];
                 tv = *reinterpret_cast<const int4*>(tets + 4 * (int64_t)(id >> 4));
             }
-            block_accumulate<FORM, corrected>(tvc, pts, w, nu, aux, a, a, true, acc, R);
+            block_accumulate<FORM, corrected, TT>(tvc, pts, w, nu, aux, a, a, true, acc, R, tt);
         }
     }
     // quad sums: (l0 + l1) + (l2 + l3), identical on every lane
@@ -965,13 +1046,14 @@ __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_
 // Lifting term of a state that violates its Dirichlet data (:65): F_free += A0[:,B] (g - x_B), A0 = the unconstrained
 // Jacobian.  Same work split as k_fused_diag (4 lanes per node, DPP quad sums); only tets with a violated Dirichlet
 // dof (dl != 0 on one of their nodes) cost anything: their blocks (a,b) are recomputed and applied to dl_b.
-template <int FORM, bool corrected>
+template <int FORM, bool corrected, bool TT>
 __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_t* __restrict__ diag,
                                                     const int64_t* __restrict__ c_ptr,
                                                     const int32_t* __restrict__ c_idx,
                                                     const int32_t* __restrict__ tets, const double* __restrict__ pts,
                                                     const double* __restrict__ w, const uint8_t* __restrict__ bc_mask,
-                                                    const double* __restrict__ dl, double nu, double* __restrict__ F) {
+                                                    const double* __restrict__ dl, double nu, double* __restrict__ F,
+                                                    TimeTerm tt) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t node = gid >> 2;
     const int q = (int)(gid & 3);
@@ -993,7 +1075,7 @@ __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_
                 double blk[16];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) blk[e] = 0.0;
-                block_accumulate<FORM, corrected>(tv, pts, w, nu, 0.0, a, b, false, blk, nullptr);
+                block_accumulate<FORM, corrected, TT>(tv, pts, w, nu, 0.0, a, b, false, blk, nullptr, tt);
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
                     R[c] += blk[4 * c] * d01.x + blk[4 * c + 1] * d01.y + blk[4 * c + 2] * d23.x + blk[4 * c + 3] * d23.y;
@@ -1012,12 +1094,15 @@ __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_
     const double rq = q == 0 ? R[0] : (q == 1 ? R[1] : (q == 2 ? R[2] : R[3]));
     if (!bc_mask[dof]) F[dof] += rq;
 }
-#define SNS_INST_LIFT(FM, C)                                                                                        \
-    template __global__ void k_fused_lift<FM, C>(int32_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
-                                                 const double*, const double*, const uint8_t*, const double*, double, double*);
-SNS_INST_LIFT(SNS_FORM_NS, false)
-SNS_INST_LIFT(SNS_FORM_NS, true)
-SNS_INST_LIFT(SNS_FORM_UGN_2D, false)
+#define SNS_INST_LIFT(FM, C, T)                                                                                        \
+    template __global__ void k_fused_lift<FM, C, T>(int32_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
+                                                    const double*, const double*, const uint8_t*, const double*, double,   \
+                                                    double*, TimeTerm);
+SNS_INST_LIFT(SNS_FORM_NS, false, false)
+SNS_INST_LIFT(SNS_FORM_NS, true, false)
+SNS_INST_LIFT(SNS_FORM_UGN_2D, false, false)
+SNS_INST_LIFT(SNS_FORM_NS, false, true)
+SNS_INST_LIFT(SNS_FORM_NS, true, true)
 
 // dl = g - w on Dirichlet dofs, 0 elsewhere
 __global__ __launch_bounds__(256) void k_bc_defect(int64_t ndof, const uint8_t* __restrict__ bc_mask,
@@ -1027,18 +1112,20 @@ __global__ __launch_bounds__(256) void k_bc_defect(int64_t ndof, const uint8_t* 
         dl[i] = bc_mask[i] ? (bc_val[i] - w[i]) : 0.0;
 }
 
-#define SNS_INST_FUSED(FM, C)                                                                                      \
-    template __global__ void k_fused_offdiag<FM, C>(int64_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
+#define SNS_INST_FUSED(FM, C, T)                                                                                   \
+    template __global__ void k_fused_offdiag<FM, C, T>(int64_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
                                                 const int32_t*, const int32_t*, const double*, const double*,       \
-                                                const uint8_t*, double, double, double*);                           \
-    template __global__ void k_fused_diag<FM, C>(int32_t, const int32_t*, const int64_t*, const int32_t*,               \
+                                                const uint8_t*, double, double, double*, TimeTerm);                 \
+    template __global__ void k_fused_diag<FM, C, T>(int32_t, const int32_t*, const int64_t*, const int32_t*,            \
                                              const int32_t*, const double*, const double*, const uint8_t*,          \
-                                             const double*, double, double, double*, double*);
-SNS_INST_FUSED(SNS_FORM_NS, false)
-SNS_INST_FUSED(SNS_FORM_NS, true)
-SNS_INST_FUSED(SNS_FORM_STOKES, false)
-SNS_INST_FUSED(SNS_FORM_STOKES_2D, false)
-SNS_INST_FUSED(SNS_FORM_UGN_2D, false)
+                                             const double*, double, double, double*, double*, TimeTerm);
+SNS_INST_FUSED(SNS_FORM_NS, false, false)
+SNS_INST_FUSED(SNS_FORM_NS, true, false)
+SNS_INST_FUSED(SNS_FORM_STOKES, false, false)
+SNS_INST_FUSED(SNS_FORM_STOKES_2D, false, false)
+SNS_INST_FUSED(SNS_FORM_UGN_2D, false, false)
+SNS_INST_FUSED(SNS_FORM_NS, false, true)
+SNS_INST_FUSED(SNS_FORM_NS, true, true)
 
 // residual-only pass of the 2-D UGN form: one lane per triangle, Fe[16 t + 4 a + c] (same layout as the tet kernel,
 // so k_gather_residual serves both)
@@ -1112,11 +1199,11 @@ __global__ __launch_bounds__(256) void k_bc_residual(int64_t ndof, const uint8_t
 // Residual-only element pass for states that already satisfy the Dirichlet data (no lifting term):
 // ONE LANE PER TET, every lane busy (the fused kernel keeps 12 of 16 lanes idle in its per-point
 // phase).  Used by the line search (F(x - lambda y), :51-67 without the Jacobian).
-template <bool corrected>
+template <bool corrected, bool TT>
 __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int32_t* __restrict__ tets,
                                                       const double* __restrict__ pts,
                                                       const double* __restrict__ w, double nu,
-                                                      double* __restrict__ Fe) {
+                                                      double* __restrict__ Fe, TimeTerm tt) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tets) return;
     const int4 tv = *reinterpret_cast<const int4*>(tets + 4 * t);
@@ -1174,6 +1261,17 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
     }
     const double divu = gu[0][0] + gu[1][1] + gu[2][2];
     const double wd = fabs(det) * (1.0 / 24.0);
+    double UT[TT ? 4 : 1][3];                              // nodal u_t = sigma u + d
+    if constexpr (TT) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const double* dp = tt.d + 4 * (int64_t)nd[a];
+            const double2 d01 = *reinterpret_cast<const double2*>(dp);
+            UT[a][0] = tt.sigma * W[a][0] + d01.x;
+            UT[a][1] = tt.sigma * W[a][1] + d01.y;
+            UT[a][2] = tt.sigma * W[a][2] + dp[2];
+        }
+    }
     double R[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -1197,7 +1295,17 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             r[j] = (corrected ? conv[j] : (gu[0][j] * u[0] + gu[1][j] * u[1] + gu[2][j] * u[2])) + gp[j];
-        const double tau = 1.0 / sqrt(uGu + 36.0 * nu * nu * GG);
+        double ut[3] = {0.0, 0.0, 0.0};
+        if constexpr (TT) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const double ph = phi_q(q, a);
+                ut[0] += ph * UT[a][0]; ut[1] += ph * UT[a][1]; ut[2] += ph * UT[a][2];
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) r[j] += ut[j];
+        }
+        const double tau = 1.0 / sqrt((TT ? tt.theta : 0.0) + uGu + 36.0 * nu * nu * GG);
         const double nuL = 1.0 / (trG * tau);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -1209,6 +1317,7 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
                 const double visc = gu[i][0] * g[a][0] + gu[i][1] * g[a][1] + gu[i][2] * g[a][2];
                 const double supg = corrected ? tau * uga * r[i] : tau * u[i] * sa;
                 R[a][i] += conv[i] * pa + nu * visc - p * g[a][i] + supg + nuL * divu * g[a][i];
+                if constexpr (TT) R[a][i] += pa * ut[i];
             }
             R[a][3] += pa * divu + tau * sa;
         }
@@ -1220,8 +1329,10 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
         o[2 * a + 1] = make_double2(wd * R[a][2], wd * R[a][3]);
     }
 }
-template __global__ void k_residual_tet<false>(int64_t, const int32_t*, const double*, const double*, double, double*);
-template __global__ void k_residual_tet<true>(int64_t, const int32_t*, const double*, const double*, double, double*);
+template __global__ void k_residual_tet<false, false>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm);
+template __global__ void k_residual_tet<true, false>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm);
+template __global__ void k_residual_tet<false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm);
+template __global__ void k_residual_tet<true, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm);
 
 // BSR slot <- sum over its contributing element blocks (fixed order => bitwise
 // reproducible), Dirichlet rows AND columns zeroed, unit diagonal (:74).

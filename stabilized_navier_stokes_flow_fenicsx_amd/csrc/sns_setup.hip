@@ -696,11 +696,11 @@ int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matri
         if (want_matrix)
             hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_STOKES_2D, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
                                h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, state,
-                               h->bc_mask, nu_s, beta, L.vals);
+                               h->bc_mask, nu_s, beta, L.vals, TimeTerm());
         if (want_matrix || F)
             hipLaunchKernelGGL((k_fused_diag<SNS_FORM_STOKES_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
                                L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, state, h->bc_mask, h->bc_val, nu_s, beta,
-                               want_matrix ? L.vals : (double*)nullptr, F);
+                               want_matrix ? L.vals : (double*)nullptr, F, TimeTerm());
         if (w && F) hipLaunchKernelGGL(k_bc_residual, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, F);
     } else {
         const double nu = 1.0 / h->opt.reynolds;
@@ -716,9 +716,10 @@ int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matri
         if (want_matrix) {
             hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_UGN_2D, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
                                h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, w, h->bc_mask,
-                               nu, 0.0, L.vals);
+                               nu, 0.0, L.vals, TimeTerm());
             hipLaunchKernelGGL((k_fused_diag<SNS_FORM_UGN_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F);
+                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F,
+                               TimeTerm());
         } else {
             if (!h->Fe) SNS_TRY(dev_alloc(&h->Fe, (size_t)h->E * 16));
             hipLaunchKernelGGL(k_residual_tri, dim3((unsigned)((h->E + 255) / 256)), dim3(256), 0, h->stream, h->E,
@@ -731,7 +732,7 @@ int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matri
             SNS_TRY(get_vec(h, 13, &dl));
             hipLaunchKernelGGL(k_bc_defect, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, dl);
             hipLaunchKernelGGL((k_fused_lift<SNS_FORM_UGN_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F);
+                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F, TimeTerm());
         }
     }
     if (want_matrix) {
@@ -775,9 +776,9 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         const unsigned gd = (unsigned)((4 * (int64_t)h->n_owned + 255) / 256);
         hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_STOKES, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
                            h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, h->gext,
-                           h->bc_mask, nu, 0.0, L.vals);
+                           h->bc_mask, nu, 0.0, L.vals, TimeTerm());
         hipLaunchKernelGGL((k_fused_diag<SNS_FORM_STOKES, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag,
-                           h->c_ptr, h->c_idx, h->tets, h->pts, h->gext, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F);
+                           h->c_ptr, h->c_idx, h->tets, h->pts, h->gext, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F, TimeTerm());
         h->has_matrix = true;
         h->transposed = false;
         h->pc_ready = false;
@@ -790,28 +791,27 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         // state that violates its Dirichlet data adds the lifting term in a third pass over the boundary tets
         const unsigned go = (unsigned)((h->n_od + 255) / 256);
         const unsigned gd = (unsigned)((4 * (int64_t)h->n_owned + 255) / 256);
-        if (!h->opt.corrected_convection) {
-            hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_NS, false>), dim3(go), dim3(256), 0, h->stream, h->n_od, h->od_order, h->c_ptr, h->c_idx,
-                               h->slot_row[0], L.colind, h->tets, h->pts, w, h->bc_mask, nu, 0.0, L.vals);
-            hipLaunchKernelGGL((k_fused_diag<SNS_FORM_NS, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag, h->c_ptr,
-                               h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F);
-        } else {
-            hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_NS, true>), dim3(go), dim3(256), 0, h->stream, h->n_od, h->od_order, h->c_ptr, h->c_idx,
-                               h->slot_row[0], L.colind, h->tets, h->pts, w, h->bc_mask, nu, 0.0, L.vals);
-            hipLaunchKernelGGL((k_fused_diag<SNS_FORM_NS, true>), dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag, h->c_ptr,
-                               h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F);
-        }
+        // (C: corrected convection, T: the handle has a time term -- both compile-time variants of the kernels)
+        dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
+            dispatch<1, 0>(h->tt_on, [&](auto T) {
+                hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_NS, C() != 0, T() != 0>), dim3(go), dim3(256), 0, h->stream, h->n_od,
+                                   h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, w, h->bc_mask, nu, 0.0,
+                                   L.vals, h->tt);
+                hipLaunchKernelGGL((k_fused_diag<SNS_FORM_NS, C() != 0, T() != 0>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
+                                   L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F, h->tt);
+            });
+        });
         if (!fast_residual && F) {
             double* dl = nullptr;
             SNS_TRY(get_vec(h, 13, &dl));
             const int64_t ndof = 4 * (int64_t)h->n;
             hipLaunchKernelGGL(k_bc_defect, dim3(vec_grid(ndof)), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, dl);
-            if (!h->opt.corrected_convection)
-                hipLaunchKernelGGL((k_fused_lift<SNS_FORM_NS, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag, h->c_ptr,
-                                   h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F);
-            else
-                hipLaunchKernelGGL((k_fused_lift<SNS_FORM_NS, true>), dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag, h->c_ptr,
-                                   h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F);
+            dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
+                dispatch<1, 0>(h->tt_on, [&](auto T) {
+                    hipLaunchKernelGGL((k_fused_lift<SNS_FORM_NS, C() != 0, T() != 0>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
+                                       L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F, h->tt);
+                });
+            });
         }
         h->has_matrix = true;
         h->transposed = false;
@@ -825,20 +825,23 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
     double* Fe = F ? h->Fe : nullptr;
     if (fast_residual) {
         const unsigned gt = (unsigned)((h->E + 255) / 256);
-        if (!h->opt.corrected_convection)
-            hipLaunchKernelGGL((k_residual_tet<false>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w, nu, h->Fe);
-        else
-            hipLaunchKernelGGL((k_residual_tet<true>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w, nu, h->Fe);
+        dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
+            dispatch<1, 0>(h->tt_on, [&](auto T) {
+                hipLaunchKernelGGL((k_residual_tet<C() != 0, T() != 0>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w,
+                                   nu, h->Fe, h->tt);
+            });
+        });
     } else if (grid > 0) {
         if (form == SNS_FORM_STOKES)
             hipLaunchKernelGGL((k_element<SNS_FORM_STOKES, false>), dim3(grid), dim3(256), 0, h->stream, h->E, h->tets,
-                               h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv);
-        else if (!h->opt.corrected_convection)
-            hipLaunchKernelGGL((k_element<SNS_FORM_NS, false>), dim3(grid), dim3(256), 0, h->stream, h->E, h->tets,
-                               h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv);
+                               h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv, TimeTerm());
         else
-            hipLaunchKernelGGL((k_element<SNS_FORM_NS, true>), dim3(grid), dim3(256), 0, h->stream, h->E, h->tets,
-                               h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv);
+            dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
+                dispatch<1, 0>(h->tt_on, [&](auto T) {
+                    hipLaunchKernelGGL((k_element<SNS_FORM_NS, C() != 0, T() != 0>), dim3(grid), dim3(256), 0, h->stream, h->E,
+                                       h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv, h->tt);
+                });
+            });
     }
     if (want_matrix) {
         const int64_t nth = L.nnzb * 8;

@@ -569,3 +569,67 @@ def streamtrace_main(argv=None):
     out = ST.for_and_rev_streamtrace_files(50, img_fname, Re, folder, out_dir=os.path.dirname(os.path.abspath(img_fname)))
     print(f"{len(out['final_output'])} of {len(out['rev_seeds'])} reverse seeds end inside the inner inlet contour", flush=True)
     return out
+
+
+def strouhal_from_lift(t, cl, diameter: float = 0.1, u_mean: float = 1.0, skip: float = 0.5):
+    """St = f D / U_mean with f from the upward zero crossings of the lift about its mean over the last ``1 - skip`` of the
+    record (linear interpolation between samples).  Returns (St, number of crossings); St is nan with fewer than two."""
+    t, cl = np.asarray(t, dtype=np.float64), np.asarray(cl, dtype=np.float64)
+    k0 = int(skip * len(t))
+    t, c = t[k0:], cl[k0:] - cl[k0:].mean()
+    up = np.nonzero((c[:-1] < 0.0) & (c[1:] >= 0.0))[0]
+    if len(up) < 2:
+        return float("nan"), len(up)
+    tc = t[up] - c[up] * (t[up + 1] - t[up]) / (c[up + 1] - c[up])
+    return float(diameter / (np.diff(tc).mean() * u_mean)), len(up)
+
+
+def run_dfg2d2_slab(n: float = 2, dt: float = 0.01, n_steps: int = 800, *, theta_coeff: float = 4.0, corrected_convection: int = 1,
+                    device=None, verbose: bool = True, **options):
+    """The unsteady DFG benchmark 2D-2 (Re = 100: inlet peak 1.5, mean 1.0, nu = 1e-3) through the 3-D kernels, on the
+    one-cell slab of ``mesh2d.dfg2d_slab_problem(n, u_max=1.5)``.  NOT in the reference (which has no unsteady form and
+    runs 2D-1 only); the steady sibling is ``test_gpu_2d``'s slab series.  Starts from the Stokes solution, steps with
+    BDF2 (``solver.solve_unsteady``) and samples C_d(t), C_l(t) per step with the residual-based force
+    (``functionals.reaction_force``, consistent with the step's time term).  Prints max C_d, max C_l and the Strouhal
+    number of the lift's zero crossings next to the Schaefer-Turek brackets (3.22-3.24, 0.99-1.01, 0.295-0.305), which a
+    first-order P1-P1 discretisation on these meshes is not expected to hit.  Returns a dict with the time series, the
+    per-step records and the three numbers."""
+    import torch
+    from . import functionals as Fn, mesh2d as M2
+    from .solver import FlowProblem, solve_unsteady
+    nu = 1e-3
+    m3, (mask, g), thick = M2.dfg2d_slab_problem(n, u_max=1.5)
+    opts = dict(reynolds=1.0 / nu, corrected_convection=corrected_convection, snes_atol=1e-13, snes_rtol=1e-6, snes_stol=1e-9,
+                ksp_rtol=1e-8)
+    opts.update(options)
+    P = FlowProblem(m3, (mask, g), device=device or f"cuda:{torch.cuda.current_device()}", **opts)
+    U, rs = P.stokes_solve()
+    if rs.reason <= 0:
+        raise RuntimeError(f"Stokes start did not converge (reason {rs.reason})")
+    U.view(-1, 4)[:, 3] *= nu                              # (unit-viscosity Stokes pressure -> the NS scaling)
+    ob = m3.meta["tags"]["obstacle"]
+    ts, cds, cls = [], [], []
+
+    def sample(step, t, w):
+        cd, cl = Fn.drag_lift_coefficients(Fn.reaction_force(P, w, ob), Uc=1.0, Lc=0.1 * thick)
+        ts.append(t), cds.append(cd), cls.append(cl)
+        if verbose and step % 50 == 0:
+            print(f"  step {step:5d} t {t:7.3f}  C_d {cd:8.4f}  C_l {cl:+8.4f}", flush=True)
+
+    t0 = time.time()
+    w, recs = solve_unsteady(P, U, dt, n_steps, order=2, theta_coeff=theta_coeff, callback=sample)
+    seconds = time.time() - t0
+    P.close()
+    half = len(ts) // 2
+    cd_max = max(cds[half:]) if ts else float("nan")
+    cl_max = max(cls[half:]) if ts else float("nan")
+    st, ncross = strouhal_from_lift(ts, cls) if len(ts) > 4 else (float("nan"), 0)
+    its = np.array([r["its"] for r in recs], dtype=np.float64)
+    kits = np.array([r["ksp_its"] for r in recs], dtype=np.float64)
+    if verbose:
+        print(f"DFG 2D-2 on the slab, level {n}: {m3.num_tets} tets, dt {dt}, {len(ts)} of {n_steps} steps converged in {seconds:.1f} s, "
+              f"Newton its / step {its.mean():.2f}, Krylov its / step {kits.mean():.1f}", flush=True)
+        print(f"max C_d {cd_max:.4f} (3.22-3.24)   max C_l {cl_max:.4f} (0.99-1.01)   St {st:.4f} (0.295-0.305; {ncross} upward crossings)",
+              flush=True)
+    return dict(t=np.array(ts), cd=np.array(cds), cl=np.array(cls), records=recs, cd_max=cd_max, cl_max=cl_max, strouhal=st,
+                crossings=ncross, n_tets=m3.num_tets, seconds=seconds, w=w, points=m3.points)

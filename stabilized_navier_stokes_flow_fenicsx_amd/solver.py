@@ -47,6 +47,7 @@ class NewtonResult:
     ksp_its: int
     fnorms: list
     seconds: float
+    ptc_steps: int = 0          # pseudo-steps taken before the closing solve (solver.pseudo_transient_solve)
 
 
 class FlowProblem:
@@ -343,6 +344,32 @@ class FlowProblem:
         dt = time.time() - t0
         return w, NewtonResult(its.value, reason.value, kits.value, list(hist[:its.value + 1]), dt)
 
+    # -- time stepping (no counterpart in the reference, whose forms are all steady) ---------------------------------
+    def set_time_term(self, sigma: float, theta: float, d):
+        """Every NS assembly of this problem from now on takes the transient form with u_t = sigma u + d
+        (sns_set_time_term): (u_t, v) in the Galerkin part, res_M + u_t in the SUPG / PSPG term, theta under the root of
+        tau.  ``d``: a dof vector (numpy or device; pressure slots ignored, copied by the handle) or None for d = 0.
+        Single-GPU 3-D problems."""
+        d = None if d is None else self._vec(d)
+        check(self.lib.sns_set_time_term(self.h, float(sigma), float(theta), _ptr(d)))
+
+    def clear_time_term(self):
+        """Back to the steady form, bit for bit."""
+        check(self.lib.sns_set_time_term(self.h, 0.0, 0.0, None))
+
+    def time_step(self, w, wprev, dt: float, order: int = 2, theta_coeff: float = 4.0):
+        """One BDF step (sns_time_step): on entry ``w`` = u^n (with p^n as the pressure guess) and ``wprev`` = u^(n-1)
+        (None allowed for order 1); on exit ``w`` = u^(n+1) and ``wprev`` = u^n, both updated in place.  theta =
+        theta_coeff / dt^2 enters tau.  A step that does not converge (``reason`` <= 0) leaves both as they were.  The
+        time term stays set, so ``residual_moments`` gives the force consistent with the step.  Returns (w, NewtonResult)."""
+        w = self._vec(w)
+        wprev = None if wprev is None else self._vec(wprev)
+        its, reason, kits = C.c_int(), C.c_int(), C.c_int()
+        t0 = time.time()
+        check(self.lib.sns_time_step(self.h, _ptr(w), _ptr(wprev), float(dt), int(order), float(theta_coeff), C.byref(its),
+                                     C.byref(reason), C.byref(kits)))
+        return w, NewtonResult(its.value, reason.value, kits.value, [], time.time() - t0)
+
     # -- introspection ----------------------------------------------------------
     def sizes(self):
         nl, no, nt, nz = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
@@ -602,6 +629,73 @@ def newton_with_reynolds_continuation(problem: FlowProblem, w: torch.Tensor, max
     return w, r
 
 
+def solve_unsteady(problem: FlowProblem, w0, dt: float, n_steps: int, order: int = 2, theta_coeff: float = 4.0, callback=None):
+    """``n_steps`` implicit steps of size ``dt`` from the state ``w0`` (not modified): BDF1 for the first step, then BDF
+    of the given order (1 or 2).  ``callback(step, t, w)`` runs after every converged step (step = 1.., t = step dt) with
+    the time term of that step still set -- the place to sample forces (``functionals.reaction_force``) or write output.
+    Stops at the first step that does not converge.  Returns (w, records): the final state and one dict per step with
+    ``its``, ``ksp_its`` and ``reason``.  NOT in the reference.  The problem keeps the last step's time term;
+    ``problem.clear_time_term()`` returns it to the steady form."""
+    if order not in (1, 2):
+        raise ValueError("order must be 1 or 2")
+    w = problem._vec(w0).clone()
+    wprev = w.clone()
+    records = []
+    for step in range(1, int(n_steps) + 1):
+        _, res = problem.time_step(w, wprev, dt, order=1 if step == 1 else order, theta_coeff=theta_coeff)
+        records.append(dict(its=res.its, ksp_its=res.ksp_its, reason=res.reason))
+        if res.reason <= 0:
+            break
+        if callback is not None:
+            callback(step, step * dt, w)
+    return w, records
+
+
+def pseudo_transient_solve(problem: FlowProblem, w0, dt0: float, growth: float = 10.0, max_steps: int = 60,
+                           switch_rtol: float = 1e-2, verbose: bool = False):
+    """Pseudo-transient continuation to the STEADY solution for guesses Newton does not converge from.  Each pseudo-step
+    is ONE linearised BDF1 step with theta = 0 (so the fixed point is exactly the steady solution), written with the
+    primitives: ``set_time_term(1/dt, 0, -w/dt)``, ``jacobian`` with the fused residual, ``krylov_solve``, update.  At the
+    linearisation point u_t = 0, so the steady residual (one ``residual`` call per step) is the step's residual; dt follows its reduction (switched evolution
+    relaxation: dt <- dt * |F_prev| / |F|, by at most ``growth`` per step either way).  Once |F| has dropped by
+    ``switch_rtol`` (or after ``max_steps``) the time term is cleared and a plain ``newton_solve`` finishes.  NOT in the
+    reference.  Returns (w, NewtonResult of the closing solve, with the pseudo-steps' Krylov iterations added and their
+    count in ``result.ptc_steps``)."""
+    w = problem._vec(w0).clone()
+    F = problem.zeros()
+    dt, f0, fprev, ksp, steps = float(dt0), None, None, 0, 0
+    try:
+        for _ in range(int(max_steps)):
+            # u_t = 0 at the linearisation point whatever dt is, so the steady residual decides dt BEFORE the one assembly
+            problem.clear_time_term()
+            f = float(torch.linalg.vector_norm(problem.residual(w, "ns")[:4 * problem.n_owned]))
+            if not np.isfinite(f):
+                raise RuntimeError(f"pseudo_transient_solve: non-finite steady residual after {steps} pseudo-steps (dt0 too large?)")
+            if f0 is None:
+                f0 = f
+            if verbose:
+                print(f"  ptc step {steps + 1}: dt {dt:.3e}  |F_steady| {f:.6e}", flush=True)
+            if f <= switch_rtol * f0:
+                break
+            if fprev is not None:
+                dt *= min(growth, max(fprev / f, 1.0 / growth))
+            fprev = f
+            problem.set_time_term(1.0 / dt, 0.0, w * (-1.0 / dt))
+            problem.jacobian(w, "ns", residual_out=F)
+            y, kres = problem.krylov_solve(F)
+            ksp += kres.its
+            if kres.reason <= 0:
+                break
+            w -= y
+            steps += 1
+    finally:
+        problem.clear_time_term()
+    w, res = problem.newton_solve(w)
+    res.ksp_its += ksp
+    res.ptc_steps = steps
+    return w, res
+
+
 def residual_reynolds_derivative(problem: FlowProblem, w, rel_step: float = 1e-4) -> torch.Tensor:
     """dF/dRe at the state ``w``: central difference of ``problem.residual(w)`` at Re (1 +- rel_step); the problem's
     options are restored afterwards.  Zero on the Dirichlet rows (F_B = w_B - g does not depend on Re)."""
@@ -643,17 +737,21 @@ def reynolds_sensitivity(problem: FlowProblem, w, grad_J, dJ_dRe_explicit: float
     return float(dJ_dRe_explicit) - float(torch.dot(lam, dF)), lam, res
 
 
-def solve_navier_stokes(problem: FlowProblem, w: torch.Tensor, rank: int = 0, continuation: bool = False):
+def solve_navier_stokes(problem: FlowProblem, w: torch.Tensor, rank: int = 0, continuation=False, ptc_dt0: float = 1.0):
     """``solve_navier_stokes(a, w, dF, bcs, W, ksp_type, comm, rank)`` (:268-312).
 
     ``w`` is updated in place (``snes.solve(None, w)`` :293); returns
     ``(w, u, p)`` with u (n,3) and p (n,) the collapsed sub-functions (:310-312).
-    ``continuation=True`` (not in the reference) retries a failed solve with Reynolds-number continuation.
+    ``continuation=True`` (not in the reference) retries a failed solve with Reynolds-number continuation;
+    ``continuation="ptc"`` goes through pseudo-transient continuation (``pseudo_transient_solve`` from ``ptc_dt0``).
     """
     if rank == 0:
         print("Running SNES solver", flush=True)
         print("Start Nonlinear Solve", flush=True)
-    if continuation:
+    if continuation == "ptc":
+        w_ptc, res = pseudo_transient_solve(problem, w, ptc_dt0, verbose=(rank == 0))
+        w.copy_(w_ptc)
+    elif continuation:
         w, res = newton_with_reynolds_continuation(problem, w, verbose=(rank == 0))
     else:
         w, res = problem.newton_solve(w)
