@@ -370,6 +370,32 @@ SNS_API int sns_jacobian(sns_handle h, int form, const double* w_dev, double* F_
  * Returns after out_host is written.  SNS_E_ARG: null handle / phi / out, bad form, NS form without
  * a state.                                                                    */
 SNS_API int sns_residual_moments(sns_handle h, int form, const double* w_dev, const double* phi_dev, double out_host[4]);
+/* Shape gradient of the raw residual, contracted with a dof vector (the reference has no counterpart):
+ *     gX[3 k + j] = sum_i lam[i] * d R_raw(w; X)[i] / d X[k][j],   k = local node, j = 0..2
+ * with R_raw as for sns_residual_moments (no lifting, no F_B = w_B - g; w need not satisfy the Dirichlet data) and
+ * everything but the node coordinates held fixed: the state w, the Dirichlet values, nu, the time-term history d.
+ * lam_dev (4*n_local doubles) is used as given, Dirichlet rows included: the caller zeroes the rows it does not want.
+ * With lam = an adjoint vector (sns_adjoint_solve) masked on the Dirichlet dofs this is the lam . dF/dX of the adjoint
+ * formula dJ/dX = dJ/dX|explicit - lam . dF/dX; with lam = phi e_c it is minus the explicit X-derivative of the
+ * residual-based force of sns_residual_moments.  gX_dev (3*n_local doubles) is overwritten; 2-D handles write
+ * gX[3 k + 2] = 0, nodes of no cell get 0.  One element pass (one lane per cell, exact reverse-mode derivative of the
+ * cell's scalar lam_e . R_e through K = J^-1, |det J|, G and, in 2-D, h) plus a fixed-order sum over each node's cells:
+ * no atomics, bitwise reproducible.
+ * SNS_FORM_NS on a 3-D handle: the G-metric form (:220-251) with corrected_convection, sns_set_form_variant (one-point
+ * quadrature included) and a time term that is set ((u_t, v), res_M + u_t and theta under the root of tau all depend on X
+ * through det J, K and G).  SNS_FORM_NS on a 2-D handle: the UGN form; the derivative is that of the branch each
+ * conditional takes at the state (|u| <= 1e-8, Re_UGN <= 3) and of the longest edge for h = CellDiameter, which is what
+ * differentiating the form as written gives.  It is UNDEFINED where two edges of a cell tie for the longest or a
+ * conditional sits on its switch point.  The Stokes forms are not supported (SNS_E_ARG): their stabilisation depends on h
+ * as well, and nobody takes an adjoint of the start-up solve.
+ * The per-cell gradients are staged in the handle's element scratch: after the call the Fe array of
+ * sns_get_element_scratch / SNS_EXPORT_FE holds Ge [n_cells][a][4] = the cell's gradient with respect to its vertex a
+ * (components 0..2, slot 3 zero) instead of element residuals.  Nothing else of the handle changes: the assembled matrix,
+ * the preconditioner state, the transposed flag, the options and the time term stay bit for bit.
+ * SNS_E_ARG: null handle / w / lam / gX, a form other than SNS_FORM_NS.  SNS_E_STATE: a handle with a communicator
+ * attached (any transport, also the local-only split; as for the adjoint solves).  Returns after gX_dev is written. */
+SNS_API int sns_residual_shape_gradient(sns_handle h, int form, const double* w_dev, const double* lam_dev,
+                                        double* gX_dev);
 /* MatMult with the assembled operator: y = A x (halo exchange inside).  Acts on whatever
  * the handle holds: y = A^T x after sns_transpose_operator.                   */
 SNS_API int sns_spmv(sns_handle h, const double* x_dev, double* y_dev);

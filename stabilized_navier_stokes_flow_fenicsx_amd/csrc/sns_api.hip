@@ -611,6 +611,19 @@ int sns_residual_moments(sns_handle h, int form, const double* w, const double* 
     return SNS_OK;
 }
 
+int sns_residual_shape_gradient(sns_handle h, int form, const double* w, const double* lam, double* gX) {
+    if (!h || !w || !lam || !gX) { set_error("sns_residual_shape_gradient: null handle or pointer"); return SNS_E_ARG; }
+    if (form != SNS_FORM_NS) {
+        set_error(form == SNS_FORM_STOKES ? "sns_residual_shape_gradient: the Stokes forms are not supported" : "bad form");
+        return SNS_E_ARG;
+    }
+    if (h->comm) {
+        set_error("sns_residual_shape_gradient: not with a communicator attached (partitioned shape gradients are not built)");
+        return SNS_E_STATE;
+    }
+    return residual_shape_gradient(h, w, lam, gX);
+}
+
 int sns_spmv(sns_handle h, const double* x, double* y) {
     if (!h || !x || !y) return SNS_E_ARG;
     if (!h->has_matrix) { set_error("spmv before a matrix was assembled"); return SNS_E_STATE; }

@@ -235,6 +235,8 @@ int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double
 int compute_strength(sns_ctx* h, float* out, double* scale);
 // csrc/sns_transpose.hip: flip the fine operator between A and A^T in place
 int transpose_operator(sns_ctx* h);
+// csrc/sns_shape.hip: lam . dR_raw/dX of the NS form by one element pass (uses the element scratch Fe)
+int residual_shape_gradient(sns_ctx* h, const double* w, const double* lam, double* gX);
 // csrc/sns_aggregate.hip: aggregate_strength's map of the owned nodes, built on the device (amg_aggregation = 2)
 int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc);
 // ... and the hybrid (amg_aggregation = 3): the geometric map g (ng aggregates) re-matched where it cuts a dominant coupling

@@ -446,6 +446,26 @@ def _print_reynolds_sensitivities(P, w, wg, grads, grads_nu, names):
     return out
 
 
+def _print_radius_sensitivities(P, msh, w, wg, nu):
+    """SNS_SHAPE_SENSITIVITY=1 (opt-in; single-GPU runs): dC_d/dr and dC_l/dr, r the cylinder radius, at the converged
+    state: the node gradients of solver.shape_sensitivity (one adjoint solve and one element pass each) contracted with
+    the radial field mesh2d.dfg2d_radial_field."""
+    from . import mesh2d as M2
+    from .solver import shape_sensitivity
+    if getattr(P, "part", None) is not None:
+        if _rank() == 0:
+            print("SNS_SHAPE_SENSITIVITY: adjoint solves run on single-GPU problems only; skipped", flush=True)
+        return None
+    G, E, V = M2.drag_lift_2d_gradient(msh, nu), M2.drag_lift_2d_shape_gradient(msh, wg, nu), M2.dfg2d_radial_field(msh)
+    out = []
+    for k, name in enumerate(("C_d", "C_l")):
+        dJ, _, res = shape_sensitivity(P, w, G[k], E[k])
+        d = float((dJ.cpu().numpy() * V).sum())
+        print(f"d{name}/dr: {d} (adjoint solve: {res.its} its, reason {res.reason})", flush=True)
+        out.append(d)
+    return out
+
+
 def _sensitivity():
     return os.environ.get("SNS_SENSITIVITY", "0") == "1"
 
@@ -504,6 +524,8 @@ def dfg_2d_main(argv=None):
     if _sensitivity():
         G1, G0 = M2.drag_lift_2d_gradient(msh, 1.0), M2.drag_lift_2d_gradient(msh, 0.0)
         _print_reynolds_sensitivities(P, w, wg, G0 + nu * (G1 - G0), G1 - G0, ("C_d", "C_l"))
+    if os.environ.get("SNS_SHAPE_SENSITIVITY", "0") == "1":
+        _print_radius_sensitivities(P, msh, w, wg, nu)
     r = P.last_newton
     P.close()
     return msh, wg, (cd, cl), r

@@ -100,6 +100,43 @@ def boundary_traction_gradient(mesh: TetMesh, nu: float, tag: int) -> np.ndarray
     return G
 
 
+def boundary_traction_shape_gradient(mesh: TetMesh, w: np.ndarray, nu: float, tag: int) -> np.ndarray:
+    """d(boundary_traction_force)/dX at FIXED state ``w`` as a (3, n, 3) array: entry [c, k, j] is the derivative of force
+    component c with respect to coordinate j of node k.  This is the explicit part dJ/dX of ``solver.shape_sensitivity``
+    for a traction functional.  The force depends on the coordinates through the P1 gradients of the tets behind the
+    tagged facets and through the facets' area vectors, so the result is non-zero only on the nodes of those tets.  Exact:
+    reverse-mode autograd over the same expressions as ``boundary_traction_force`` on those few cells (the orientation
+    sign of a facet is piecewise constant)."""
+    import torch
+    out = np.zeros((3, mesh.num_nodes, 3))
+    ids = mesh.find(tag)
+    if len(ids) == 0:
+        return out
+    W = np.asarray(w, dtype=np.float64).reshape(-1, 4)
+    par = facet_parent_tets(mesh, ids)
+    tn = mesh.tets[par].astype(np.int64)
+    fn = mesh.facets[ids].astype(np.int64)
+    nodes = np.unique(tn)
+    Xn = torch.tensor(mesh.points[nodes], dtype=torch.float64, requires_grad=True)
+    X = Xn[torch.from_numpy(np.searchsorted(nodes, tn))]                               # (F,4,3)
+    P = Xn[torch.from_numpy(np.searchsorted(nodes, fn))]                               # (F,3,3)
+    J = torch.stack([X[:, 1] - X[:, 0], X[:, 2] - X[:, 0], X[:, 3] - X[:, 0]], dim=2)
+    K = torch.linalg.inv(J)
+    g = torch.cat([-K.sum(dim=1, keepdim=True), K], dim=1)
+    gu = torch.einsum("fai,faj->fij", torch.from_numpy(W[tn][:, :, :3]), g)
+    cr = torch.linalg.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    opp = tn.sum(axis=1) - fn.sum(axis=1)
+    Pn = mesh.points[fn]
+    sgn = np.sign(np.einsum("fi,fi->f", np.cross(Pn[:, 1] - Pn[:, 0], Pn[:, 2] - Pn[:, 0]), Pn[:, 0] - mesh.points[opp]))
+    n_area = -0.5 * cr * torch.from_numpy(sgn)[:, None]
+    pm = torch.from_numpy(W[fn][:, :, 3].mean(axis=1))
+    stress = nu * (gu + gu.transpose(1, 2)) - pm[:, None, None] * torch.eye(3, dtype=torch.float64)
+    force = torch.einsum("fij,fj->i", stress, n_area)
+    for c in range(3):
+        out[c, nodes] = torch.autograd.grad(force[c], Xn, retain_graph=True)[0].numpy()
+    return out
+
+
 def point_value_gradient(mesh: TetMesh, pts, comp: int = 3, padding: float = 1e-6, device=None) -> np.ndarray:
     """d(value of component ``comp`` of the P1 solution at the points ``pts`` (m,3))/dw as an (m, 4 n) array: the
     barycentric weights of ``interpolate.locate_points`` -- what ``FlowProblem.eval_at`` evaluates with -- in the columns

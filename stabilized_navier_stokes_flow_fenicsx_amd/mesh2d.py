@@ -474,6 +474,62 @@ def drag_lift_2d_gradient(mesh: TriMesh, nu: float, tag: int | None = None, U_me
     return G
 
 
+def drag_lift_2d_shape_gradient(mesh: TriMesh, w, nu: float, tag: int | None = None, U_mean: float = 0.2, L: float = 0.1) -> np.ndarray:
+    """d(C_D, C_L)/dX of ``drag_lift_2d`` at FIXED state ``w`` as a (2, n, 3) array (z column zero): the explicit part
+    dJ/dX of ``solver.shape_sensitivity``.  Non-zero only on the nodes of the triangles behind the tagged edges.  Exact:
+    reverse-mode autograd over the same expressions as ``drag_lift_2d`` on those few cells (an edge's orientation sign is
+    piecewise constant)."""
+    import torch
+    tag = DFG2D_TAGS["obstacle"] if tag is None else tag
+    out = np.zeros((2, mesh.num_nodes, 3))
+    ids = mesh.find(tag)
+    if len(ids) == 0:
+        return out
+    W = np.asarray(w, dtype=np.float64).reshape(-1, 4)
+    par = edge_parent_tris(mesh, ids)
+    tn = mesh.tris[par].astype(np.int64)
+    fn = mesh.facets[ids].astype(np.int64)
+    nodes = np.unique(tn)
+    Xn = torch.tensor(mesh.points[nodes][:, :2], dtype=torch.float64, requires_grad=True)
+    X = Xn[torch.from_numpy(np.searchsorted(nodes, tn))]              # (F,3,2)
+    P = Xn[torch.from_numpy(np.searchsorted(nodes, fn))]              # (F,2,2)
+    J = torch.stack([X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]], dim=2)
+    K = torch.linalg.inv(J)
+    g = torch.cat([-K.sum(dim=1, keepdim=True), K], dim=1)
+    gu = torch.einsum("fai,faj->fij", torch.from_numpy(W[tn][:, :, :2]), g)
+    tv = P[:, 1] - P[:, 0]
+    ln = torch.linalg.norm(tv, dim=1)
+    nf = torch.stack([tv[:, 1], -tv[:, 0]], dim=1) / ln[:, None]
+    opp = tn.sum(axis=1) - fn.sum(axis=1)
+    Pn = mesh.points[fn][:, :, :2]
+    tvn = Pn[:, 1] - Pn[:, 0]
+    sgn = np.sign(np.einsum("fi,fi->f", np.stack([tvn[:, 1], -tvn[:, 0]], axis=1), Pn[:, 0] - mesh.points[opp][:, :2]))
+    n = -nf * torch.from_numpy(sgn)[:, None]
+    tt = torch.stack([n[:, 1], -n[:, 0]], dim=1)
+    dut = torch.einsum("fi,fij,fj->f", tt, gu, n)
+    pm = torch.from_numpy(W[fn][:, :, 3].mean(axis=1))
+    c = 2.0 / (U_mean ** 2 * L)
+    cd = c * torch.sum(ln * (nu * dut * n[:, 1] - pm * n[:, 0]))
+    cl = -c * torch.sum(ln * (nu * dut * n[:, 0] + pm * n[:, 1]))
+    out[0, nodes, :2] = torch.autograd.grad(cd, Xn, retain_graph=True)[0].numpy()
+    out[1, nodes, :2] = torch.autograd.grad(cl, Xn)[0].numpy()
+    return out
+
+
+def dfg2d_radial_field(mesh: TriMesh, cx: float = 0.2, cy: float = 0.2, radius: float = 0.05, r_out: float = 0.12) -> np.ndarray:
+    """Deformation field of a change of the cylinder radius as an (n, 3) array (z column zero): V = (x - c)/|x - c| psi(|x - c|)
+    with psi = 1 for r <= radius, falling C^2 (quintic smoothstep) to 0 at r_out -- inside the 0.15 gap between the cylinder
+    and the channel walls, so walls, inlet and outlet stay where they are.  dJ/dr = sum(dJ/dX * V) for a gradient of
+    ``solver.shape_sensitivity``."""
+    r = mesh.points[:, :2] - np.array([cx, cy])
+    rn = np.linalg.norm(r, axis=1)
+    s = np.clip((rn - radius) / (r_out - radius), 0.0, 1.0)
+    psi = 1.0 - s ** 3 * (10.0 - 15.0 * s + 6.0 * s * s)
+    V = np.zeros((mesh.num_nodes, 3))
+    V[:, :2] = r / np.maximum(rn, 1e-300)[:, None] * psi[:, None]
+    return V
+
+
 def drag_lift_2d_reaction(problem, w, tag: int | None = None, U_mean: float = 0.2, L: float = 0.1):
     """(C_D, C_L) from the residual-based force on the obstacle (functionals.reaction_force on a 2-D problem): F = -R_raw(w)
     tested with the indicator of the obstacle's nodes, C = 2 F / (U^2 L) with the constants of ``drag_lift_2d``.  Same limit

@@ -284,6 +284,18 @@ class FlowProblem:
         check(self.lib.sns_residual_moments(self.h, _FORMS[form], _ptr(w), _ptr(phi), out))
         return np.array(out[:], dtype=np.float64)
 
+    def residual_shape_gradient(self, w, lam, form="ns") -> torch.Tensor:
+        """``lam . dR_raw(w; X)/dX`` as a device tensor (n_nodes, 3) (sns_residual_shape_gradient): the derivative of the raw
+        residual (no lifting, no Dirichlet rows' w_B - g) with respect to every node coordinate, contracted with the dof vector
+        ``lam``, at fixed state, Dirichlet values, nu and time-term history.  ``lam`` is used as given -- zero the Dirichlet
+        rows of an adjoint vector first (``solver.shape_sensitivity`` does).  One element pass, exact derivative, bitwise
+        reproducible; the z column of a 2-D problem is 0.  NS form only; single-GPU problems.  Overwrites the handle's
+        element scratch (``export(SNS_EXPORT_FE, ...)``), nothing else."""
+        w, lam = self._vec(w), self._vec(lam)
+        out = torch.empty(self.n_local, 3, dtype=torch.float64, device=self.device)
+        check(self.lib.sns_residual_shape_gradient(self.h, _FORMS[form], _ptr(w), _ptr(lam), _ptr(out)))
+        return out
+
     def spmv(self, x, out=None) -> torch.Tensor:
         x = self._vec(x)
         out = self.zeros() if out is None else self._vec(out)
@@ -735,6 +747,44 @@ def reynolds_sensitivity(problem: FlowProblem, w, grad_J, dJ_dRe_explicit: float
     lam, res = problem.adjoint_solve(g)
     dF = residual_reynolds_derivative(problem, w, rel_step)
     return float(dJ_dRe_explicit) - float(torch.dot(lam, dF)), lam, res
+
+
+def shape_sensitivity(problem: FlowProblem, w, grad_J, dJ_dX_explicit=None):
+    """Gradient dJ/dX of a functional J(w(X), X) with respect to EVERY node coordinate at a converged state ``w``
+    (F(w; X) = 0), for the price of one adjoint solve and one element pass:
+
+        A = dF/dw at w  (``problem.jacobian(w)``),    A^T lam = grad_J  (``problem.adjoint_solve``),    lam_B := 0,
+        dJ/dX = dJ_dX_explicit - lam . dF/dX          (``problem.residual_shape_gradient(w, lam)``)
+
+    ``grad_J``: dJ/dw as a dof vector (numpy or device).  ``dJ_dX_explicit``: (n_nodes, 3), the derivative of J with respect
+    to the coordinates at FIXED w (``functionals.boundary_traction_shape_gradient``, ``mesh2d.drag_lift_2d_shape_gradient``;
+    None for a functional without one, such as a point value in a cell that does not move).  Assumptions:
+
+      * ``w`` is converged; the error of the result is of the order of the residual.
+      * The Dirichlet values are held AT THE NODES and do not follow the coordinates (dw_B = 0): a node of an inlet that moves
+        keeps its value.  That is why ``lam`` is zeroed on the Dirichlet dofs: the rows F_B = w_B - g do not depend on X.
+      * The result is the gradient with respect to every node, boundary and interior; contract it with a deformation field V
+        (n_nodes, 3) for a directional derivative: ``(dJdX * V).sum()``.
+      * The components on interior nodes are mesh-motion terms of the discrete problem; they vanish only in the limit h -> 0.
+
+    The residual-based force (``functionals.reaction_force``) cannot serve as J here: its dJ/dw needs the Dirichlet-row x
+    free-column block of the UNCONSTRAINED Jacobian, which the handle does not hold (the assembled operator has unit rows
+    there).  Its explicit part alone is ``-problem.residual_shape_gradient(w, phi e_c)``.
+
+    Returns (dJ/dX as a device tensor (n_nodes, 3), lam, KrylovResult of the adjoint solve).  The handle is left as
+    ``reynolds_sensitivity`` leaves it: the Jacobian at w assembled, the caller's options.  Single-GPU problems."""
+    w = problem._vec(w)
+    g = problem._vec(grad_J if isinstance(grad_J, torch.Tensor) else np.asarray(grad_J, dtype=np.float64).ravel())
+    problem.jacobian(w, "ns")
+    lam, res = problem.adjoint_solve(g)
+    lam[torch.from_numpy(problem.bc_mask.astype(bool)).to(lam.device)] = 0.0
+    dJ = -problem.residual_shape_gradient(w, lam)
+    if dJ_dX_explicit is not None:
+        e = dJ_dX_explicit
+        if not isinstance(e, torch.Tensor):
+            e = torch.from_numpy(np.ascontiguousarray(e, dtype=np.float64))
+        dJ += e.to(dJ.device).reshape(dJ.shape)
+    return dJ, lam, res
 
 
 def solve_navier_stokes(problem: FlowProblem, w: torch.Tensor, rank: int = 0, continuation=False, ptc_dt0: float = 1.0):
