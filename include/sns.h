@@ -472,6 +472,32 @@ SNS_API int sns_set_time_term(sns_handle h, double sigma, double theta, const do
  * as there.                                                                                                          */
 SNS_API int sns_time_step(sns_handle h, double* w_dev, double* wprev_dev, double dt, int order, double theta_coeff,
                           int* its, int* reason, int* total_ksp_its);
+/* Generalised-Newtonian viscosity of the 3-D NS form (the reference has no counterpart: every form of it has the constant
+ * nu = 1/Re).  law = SNS_LAW_CARREAU: on each tet, with eps = sym(grad u) (constant on a P1 tet) and
+ *   s = 2 eps:eps (= gamma_dot^2),   nu_e = nu0 (r + (1 - r) (1 + lambda^2 s)^((n-1)/2)),   nu0 = 1/Re, r = nu_inf_ratio,
+ * every NS assembly of the handle from this call on -- sns_residual, sns_jacobian, sns_newton_solve, sns_adjoint_solve's
+ * operator, sns_residual_moments, sns_bench_assemble -- takes
+ *   - the viscous Galerkin term in the stress-divergence form (2 nu_e eps(u), grad v).  The reference's nu (grad u, grad v)
+ *     (:244) is a momentum flux only for a constant nu; for a constant nu the two differ by nu (grad u^T, grad v), so a
+ *     Carreau law with lambda = 0 or n = 1 is NOT the law-off handle: it is the Newtonian stress-divergence form;
+ *   - res_M unchanged (div(2 nu_e eps(u)) vanishes inside a P1 element, as div sigma does at :240-241);
+ *   - tau = (u.Gu + C_I nu_e^2 G:G)^-1/2 and nu_LSIC = 1/(tr G tau) with that tau.
+ * The Jacobian is the exact Gateaux derivative: with d nu_e = nu'(s) 4 eps(u):grad(du) the velocity-velocity part gains
+ * nu_e (grad du^T, grad v) and the rank-one block 4 |T| nu' (2 eps g_a)(eps g_b)^T, and d tau, d nu_LSIC gain the
+ * derivative of nu_e under the root.  s enters without a square root, so the form is smooth at rest.  law =
+ * SNS_LAW_NEWTONIAN clears the law (the other arguments are ignored): the handle is the Newtonian handle again, bit for
+ * bit.  The Stokes form ignores the law; sns_set_form_variant and corrected_convection apply as without one.  An assembled
+ * matrix stays what it was; a change of law makes the next preconditioner set-up re-estimate its smoother damping.
+ * SNS_E_ARG: a 2-D handle; an unknown law; lambda negative or not finite; n <= 0 or not finite; nu_inf_ratio negative or
+ * not finite.  SNS_E_STATE: a handle with a communicator attached; a handle with a time term set (sns_set_time_term and
+ * sns_time_step refuse the same way while a law is set, and so does sns_residual_shape_gradient: the mesh derivative of
+ * nu_e is not built).                                                                                                  */
+#define SNS_LAW_NEWTONIAN 0
+#define SNS_LAW_CARREAU 1
+SNS_API int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double nu_inf_ratio);
+/* Per-tet viscosity of the state w_dev under the handle's law: nu_dev[t] = nu_e (nu0 = 1/Re without a law),
+ * gamma_dot_dev[t] = sqrt(2 eps:eps); n_tets doubles each, either may be NULL.  SNS_E_ARG: a 2-D handle, no state.    */
+SNS_API int sns_element_viscosity(sns_handle h, const double* w_dev, double* nu_dev, double* gamma_dot_dev);
 
 /* ---- introspection (tests, profiling) --------------------------------------*/
 /* device pointers of the assembled BSR4 operator (block row-major 4x4); the values are those of A^T while the handle

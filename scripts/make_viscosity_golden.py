@@ -1,0 +1,96 @@
+"""Writes tests/golden/viscosity_cases.npz, the fixture of the viscosity-law tests (tests/test_host_viscosity.py,
+tests/test_gpu_viscosity.py), from the CPU oracle tests/viscosity_oracle.py alone:
+
+  el_X, el_W, el_Re, el_lam          the element cases: 4 regular + 3 sliver tets with random states, Re in [5, 200] and
+                                     lambda in [0.1, 10] (log-uniform); the tests cross them with n and r
+  el_F                               the oracle's residuals of those cases at (n, r) = (0.7, 0.05), both convection readings
+  duct_stokes                        the Stokes start on the jittered duct of DUCT
+  duct_law, duct_newton, duct_low    LU-Newton fields: the law of DUCT, the reference's Newtonian form, the law at n = n_low
+  ratio_law, ratio_newton            centreline-to-mean outlet velocity of the first two
+
+    python scripts/make_viscosity_golden.py [--out FILE]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+# the Newton case of the tests: a 1152-tet jittered duct, plug inflow, no-slip walls
+DUCT = dict(cells=(12, 4, 4), length=3.0, jitter=0.15, Re=10.0, lam=3.0, n=0.5, r=0.01, n_low=0.3)
+OUT = os.path.join(ROOT, "tests", "golden", "viscosity_cases.npz")
+
+
+def random_tets(rng, n, sliver=False):
+    X = rng.normal(size=(n, 4, 3))
+    if sliver:
+        X[:, 3] = X[:, :3].mean(axis=1) + 1e-3 * rng.normal(size=(n, 3))      # fourth vertex almost in the opposite face
+    return X
+
+
+def duct_problem():
+    from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B, mesh as M
+    m = M.duct_mesh(DUCT["cells"], DUCT["length"], jitter=DUCT["jitter"])
+    mask, g = B.duct_bcs(m).flatten()
+    return m, mask, g
+
+
+def centreline_to_mean(m, w):
+    """u_x at the outlet node nearest the axis over the mean of u_x over the outlet nodes."""
+    out = m.facet_nodes(m.meta["tags"]["outlet"])
+    ux = np.asarray(w).reshape(-1, 4)[out, 0]
+    c = out[np.argmin(np.sum(m.points[out, 1:] ** 2, axis=1))]
+    return float(np.asarray(w).reshape(-1, 4)[c, 0] / ux.mean())
+
+
+def newtonian_field(m, mask, g, Re, w0, tol=1e-12, max_it=40):
+    """LU-Newton on the reference's form (oracle/assemble.assemble_ns)."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+    from oracle import assemble as asm
+    x = w0.copy()
+    for _ in range(max_it):
+        J, F = asm.assemble_ns(m.points, m.tets, x, Re, mask, g)
+        y = spla.splu(sp.csc_matrix(J)).solve(F)
+        x = x - y
+        if np.linalg.norm(y) <= tol * np.linalg.norm(x):
+            return x
+    raise RuntimeError("oracle Newton did not converge")
+
+
+def build():
+    import viscosity_oracle as VO
+    rng = np.random.default_rng(20260)
+    X = np.concatenate([random_tets(rng, 4), random_tets(rng, 3, sliver=True)])
+    W = rng.normal(size=(7, 16))
+    Re = rng.uniform(5.0, 200.0, size=7)
+    lam = 10.0 ** rng.uniform(-1.0, 1.0, size=7)
+    el_F = np.stack([np.concatenate([VO.element(X[i][None], W[i][None], Re[i], lam[i], 0.7, 0.05, corrected_convection=c,
+                                                want_jac=False)[0] for i in range(7)]) for c in (False, True)])
+    m, mask, g = duct_problem()
+    D = DUCT
+    w0 = VO.stokes_start(m.points, m.tets, mask, g)
+    w_law, _ = VO.newton(m.points, m.tets, mask, g, D["Re"], D["lam"], D["n"], D["r"], w0)
+    w_low, _ = VO.newton(m.points, m.tets, mask, g, D["Re"], D["lam"], D["n_low"], D["r"], w_law)
+    w_newt = newtonian_field(m, mask, g, D["Re"], w0)
+    return dict(el_X=X, el_W=W, el_Re=Re, el_lam=lam, el_F=el_F, cells=np.array(D["cells"]), length=D["length"], jitter=D["jitter"],
+                Re=D["Re"], lam=D["lam"], n=D["n"], r=D["r"], n_low=D["n_low"], duct_stokes=w0, duct_law=w_law, duct_newton=w_newt,
+                duct_low=w_low, ratio_law=centreline_to_mean(m, w_law), ratio_newton=centreline_to_mean(m, w_newt))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=OUT)
+    args = ap.parse_args()
+    out = build()
+    np.savez_compressed(args.out, **out)
+    print(f"{args.out}: ratio_law {out['ratio_law']:.6f} ratio_newton {out['ratio_newton']:.6f}")
+
+
+if __name__ == "__main__":
+    main()

@@ -65,6 +65,7 @@ ABI_VERSION = 8                          # SNS_ABI_VERSION of the header this mi
 FORM_STOKES, FORM_NS = 0, 1
 KSP_BICGSTAB, KSP_FGMRES, KSP_TFQMR = 0, 1, 2
 PC_NONE, PC_BJACOBI, PC_AMG = 0, 1, 2
+LAW_NEWTONIAN, LAW_CARREAU = 0, 1
 EXPORT_ROWPTR, EXPORT_COLIND, EXPORT_VALS, EXPORT_KE, EXPORT_FE, EXPORT_STRENGTH, EXPORT_AGG0 = 0, 1, 2, 3, 4, 5, 6
 KSP_NAMES = {"bicgstab": KSP_BICGSTAB, "bcgs": KSP_BICGSTAB, "fgmres": KSP_FGMRES, "gmres": KSP_FGMRES, "tfqmr": KSP_TFQMR}
 PC_NAMES = {"none": PC_NONE, "bjacobi": PC_BJACOBI, "jacobi": PC_BJACOBI, "amg": PC_AMG}
@@ -114,6 +115,8 @@ _SIGNATURES = [
     ("sns_set_time_term", C.c_int, [_H, C.c_double, C.c_double, _P]),
     ("sns_time_step", C.c_int, [_H, _P, _P, C.c_double, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                 C.POINTER(C.c_int)]),
+    ("sns_set_viscosity_law", C.c_int, [_H, C.c_int, C.c_double, C.c_double, C.c_double]),
+    ("sns_element_viscosity", C.c_int, [_H, _P, _P, _P]),
     ("sns_newton_solve", C.c_int, [_H, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_double), C.c_int]),
     ("sns_get_bsr", C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P),

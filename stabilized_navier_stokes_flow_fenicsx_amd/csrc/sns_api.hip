@@ -576,9 +576,9 @@ int sns_residual_moments(sns_handle h, int form, const double* w, const double* 
                                    h->opt.stokes_viscosity, h->opt.stokes_beta, h->rm_Fe);
         } else if (form == SNS_FORM_NS && h->fv.is_default()) {
             dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-                dispatch<1, 0>(h->tt_on, [&](auto T) {
-                    hipLaunchKernelGGL((k_residual_tet<C() != 0, T() != 0>), dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells,
-                                       h->pts, w, nu, h->rm_Fe, h->tt);
+                dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
+                    hipLaunchKernelGGL((k_residual_tet<C() != 0, V() == 1, V() == 2>), dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells,
+                                       h->pts, w, nu, h->rm_Fe, h->tt, h->vl);
                 });
             });
         } else {
@@ -589,13 +589,13 @@ int sns_residual_moments(sns_handle h, int form, const double* w, const double* 
             const unsigned ge = (unsigned)((nc + EL_TETS_PER_BLOCK - 1) / EL_TETS_PER_BLOCK);
             if (form == SNS_FORM_STOKES)
                 hipLaunchKernelGGL((k_element<SNS_FORM_STOKES, false>), dim3(ge), dim3(256), 0, h->stream, nc, h->rm_cells,
-                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv, TimeTerm());
+                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv, TimeTerm(), ViscosityLaw());
             else
                 dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-                    dispatch<1, 0>(h->tt_on, [&](auto T) {
-                        hipLaunchKernelGGL((k_element<SNS_FORM_NS, C() != 0, T() != 0>), dim3(ge), dim3(256), 0, h->stream, nc,
+                    dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
+                        hipLaunchKernelGGL((k_element<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(ge), dim3(256), 0, h->stream, nc,
                                            h->rm_cells, h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe,
-                                           h->fv, h->tt);
+                                           h->fv, h->tt, h->vl);
                     });
                 });
         }
@@ -619,6 +619,10 @@ int sns_residual_shape_gradient(sns_handle h, int form, const double* w, const d
     }
     if (h->comm) {
         set_error("sns_residual_shape_gradient: not with a communicator attached (partitioned shape gradients are not built)");
+        return SNS_E_STATE;
+    }
+    if (h->vl_on) {
+        set_error("sns_residual_shape_gradient: not with a viscosity law set (the mesh derivative of nu_e is not built)");
         return SNS_E_STATE;
     }
     return residual_shape_gradient(h, w, lam, gX);
@@ -825,6 +829,10 @@ int sns_set_time_term(sns_handle h, double sigma, double theta, const double* d_
     }
     if (sigma > 0.0 && !d_dev) { set_error("sns_set_time_term: sigma > 0 needs a history vector"); return SNS_E_ARG; }
     if (h->comm) { set_error("sns_set_time_term: not with a communicator attached (partitioned time stepping is not built)"); return SNS_E_STATE; }
+    if (h->vl_on && !(sigma == 0.0 && theta == 0.0 && !d_dev)) {
+        set_error("sns_set_time_term: not with a viscosity law set (the transient form has no law)");
+        return SNS_E_STATE;
+    }
     if (sigma != h->tt.sigma || theta != h->tt.theta) {   // another operator: re-estimate the smoother's damping caps
         h->est_form = -1;
         h->pc_ready = false;
@@ -846,6 +854,47 @@ int sns_set_time_term(sns_handle h, double sigma, double theta, const double* d_
     return SNS_OK;
 }
 
+int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double nu_inf_ratio) {
+    if (!h) return SNS_E_ARG;
+    if (h->dim != 3) { set_error("sns_set_viscosity_law: 3-D handles only"); return SNS_E_ARG; }
+    if (law != SNS_LAW_NEWTONIAN && law != SNS_LAW_CARREAU) { set_error("sns_set_viscosity_law: unknown law"); return SNS_E_ARG; }
+    if (law == SNS_LAW_CARREAU) {
+        if (!(lambda >= 0.0) || !std::isfinite(lambda)) { set_error("sns_set_viscosity_law: lambda must be finite and >= 0"); return SNS_E_ARG; }
+        if (!(n > 0.0) || !std::isfinite(n)) { set_error("sns_set_viscosity_law: n must be finite and > 0"); return SNS_E_ARG; }
+        if (!(nu_inf_ratio >= 0.0) || !std::isfinite(nu_inf_ratio)) {
+            set_error("sns_set_viscosity_law: nu_inf_ratio must be finite and >= 0");
+            return SNS_E_ARG;
+        }
+    }
+    if (h->comm) { set_error("sns_set_viscosity_law: not with a communicator attached (partitioned handles have no law)"); return SNS_E_STATE; }
+    if (h->tt_on) { set_error("sns_set_viscosity_law: not with a time term set (the transient form has no law)"); return SNS_E_STATE; }
+    ViscosityLaw vl;
+    if (law == SNS_LAW_CARREAU) { vl.lambda = lambda; vl.n = n; vl.r = nu_inf_ratio; }
+    const bool on = law == SNS_LAW_CARREAU;
+    if (on != h->vl_on || vl.lambda != h->vl.lambda || vl.n != h->vl.n || vl.r != h->vl.r) {
+        h->est_form = -1;                                 // another operator: re-estimate the smoother's damping caps
+        h->pc_ready = false;
+    }
+    h->vl = vl;
+    h->vl_on = on;
+    return SNS_OK;
+}
+
+int sns_element_viscosity(sns_handle h, const double* w, double* nu_dev, double* gamma_dot_dev) {
+    if (!h || !w) { set_error("sns_element_viscosity: null handle or state"); return SNS_E_ARG; }
+    if (h->dim != 3) { set_error("sns_element_viscosity: 3-D handles only"); return SNS_E_ARG; }
+    if (h->E > 0 && (nu_dev || gamma_dot_dev)) {
+        const unsigned gt = (unsigned)((h->E + 255) / 256);
+        const double nu = 1.0 / h->opt.reynolds;
+        dispatch<1, 0>(h->vl_on, [&](auto V) {
+            hipLaunchKernelGGL((k_element_viscosity<V() != 0>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w, nu,
+                               h->vl, nu_dev, gamma_dot_dev);
+        });
+        HIP_TRY(hipGetLastError());
+    }
+    return sync_stream(h);
+}
+
 int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, double theta_coeff, int* its, int* reason,
                   int* ksp_its) {
     if (!h || !w || !its || !reason) return SNS_E_ARG;
@@ -855,6 +904,7 @@ int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, 
     if (h->dim != 3) { set_error("sns_time_step: 3-D handles only"); return SNS_E_ARG; }
     if (!(theta_coeff >= 0.0) || !std::isfinite(theta_coeff)) { set_error("sns_time_step: theta_coeff must be finite and >= 0"); return SNS_E_ARG; }
     if (h->comm) { set_error("sns_time_step: not with a communicator attached (partitioned time stepping is not built)"); return SNS_E_STATE; }
+    if (h->vl_on) { set_error("sns_time_step: not with a viscosity law set (the transient form has no law)"); return SNS_E_STATE; }
     const int64_t ld = ld_of(h);
     const int g = vec_grid(ld);
     // BDF1: u_t = (u - u^n) / dt;  BDF2: u_t = (3 u - 4 u^n + u^(n-1)) / (2 dt).  d in a workspace vector (copied by

@@ -111,6 +111,9 @@ struct sns_ctx {
     double* tt_d = nullptr;
     double* tt_w0 = nullptr;                     // sns_time_step: the state on entry
     bool tt_on = false;
+    // sns_set_viscosity_law: the generalised-Newtonian 3-D NS form; vl_on selects the VL instantiations (never with tt_on)
+    ViscosityLaw vl;
+    bool vl_on = false;
     bool has_matrix = false, pc_ready = false;
     int pc_setups = 0;
     // hipGraph of the launch-bound coarse part of the V-cycle (levels >= graph_level; serial runs only)
@@ -455,6 +458,10 @@ inline void dispatch(int v, Fn&& fn) {
 
 template <class Fn>
 inline void with_fmt(int fmt, Fn&& fn) { dispatch<2, 1>(fmt, fn); }
+
+// the compile-time variant of the 3-D NS assembly kernels a handle runs: 0 the reference's steady form, 1 with a time term
+// (TT), 2 with a viscosity law (VL); the two are never on together
+inline int ns_variant(const sns_ctx* h) { return h->vl_on ? 2 : (h->tt_on ? 1 : 0); }
 
 // a level's matrix copy in format F -- values and row scales (nullptr in fp32) -- and the same of M = A P
 struct LpMat {

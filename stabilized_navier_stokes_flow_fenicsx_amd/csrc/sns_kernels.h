@@ -37,26 +37,40 @@ struct TimeTerm {
     const double* d = nullptr;
 };
 
-template <int FORM, bool corrected, bool TT = false>
+// Generalised-Newtonian viscosity of the 3-D NS form (sns_set_viscosity_law): the Carreau law on the per-tet shear rate,
+//   s = 2 eps:eps (= gamma_dot^2, eps = sym grad u, constant on a P1 tet),
+//   nu_e = nu0 (r + (1 - r) (1 + lambda^2 s)^((n-1)/2)),  nu0 = 1/Re,  r = nu_inf / nu0.
+// With it the viscous Galerkin term is the stress-divergence form (2 nu_e eps(u), grad v) and nu_e replaces nu under the root
+// of tau.  The kernels take it as the compile-time variant VL; the Newtonian instantiations (VL = false) never read the struct.
+struct ViscosityLaw {
+    double lambda = 0.0, n = 1.0, r = 0.0;
+};
+
+template <int FORM, bool corrected, bool TT = false, bool VL = false>
 __global__ void k_element(int64_t n_tets, const int32_t* tets, const double* pts, const double* w,
                           const uint8_t* bc_mask, const double* bc_val, double nu, int store_K, double* Ke,
-                          double* Fe, FormVariant fv, TimeTerm tt);
-template <int FORM, bool corrected, bool TT = false>
+                          double* Fe, FormVariant fv, TimeTerm tt, ViscosityLaw vl);
+template <int FORM, bool corrected, bool TT = false, bool VL = false>
 __global__ void k_fused_offdiag(int64_t n_od, const int32_t* od_order, const int64_t* c_ptr, const int32_t* c_idx, const int32_t* slot_row,
                                 const int32_t* colind, const int32_t* tets, const double* pts, const double* w,
-                                const uint8_t* bc_mask, double nu, double aux, double* vals, TimeTerm tt);
-template <int FORM, bool corrected, bool TT = false>
+                                const uint8_t* bc_mask, double nu, double aux, double* vals, TimeTerm tt, ViscosityLaw vl);
+template <int FORM, bool corrected, bool TT = false, bool VL = false>
 __global__ void k_fused_diag(int32_t n_rows, const int32_t* diag, const int64_t* c_ptr, const int32_t* c_idx,
                              const int32_t* tets, const double* pts, const double* w, const uint8_t* bc_mask,
-                             const double* bc_val, double nu, double aux, double* vals, double* F, TimeTerm tt);
-template <int FORM, bool corrected, bool TT = false>
+                             const double* bc_val, double nu, double aux, double* vals, double* F, TimeTerm tt,
+                             ViscosityLaw vl);
+template <int FORM, bool corrected, bool TT = false, bool VL = false>
 __global__ void k_fused_lift(int32_t n_rows, const int32_t* diag, const int64_t* c_ptr, const int32_t* c_idx,
                              const int32_t* tets, const double* pts, const double* w, const uint8_t* bc_mask,
-                             const double* dl, double nu, double* F, TimeTerm tt);
+                             const double* dl, double nu, double* F, TimeTerm tt, ViscosityLaw vl);
 __global__ void k_bc_defect(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, const double* w, double* dl);
-template <bool corrected, bool TT = false>
+template <bool corrected, bool TT = false, bool VL = false>
 __global__ void k_residual_tet(int64_t n_tets, const int32_t* tets, const double* pts, const double* w, double nu,
-                               double* Fe, TimeTerm tt);
+                               double* Fe, TimeTerm tt, ViscosityLaw vl);
+// per tet: nu_e of the law (nu0 where LAW is false) and gamma_dot = sqrt(2 eps:eps); either output may be null
+template <bool LAW>
+__global__ void k_element_viscosity(int64_t n_tets, const int32_t* tets, const double* pts, const double* w, double nu,
+                                    ViscosityLaw vl, double* nu_e, double* gamma_dot);
 __global__ void k_residual_tri(int64_t n_tris, const int32_t* tets, const double* pts, const double* w, double nu,
                                double* Fe);
 __global__ void k_bc_residual(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, const double* w, double* F);

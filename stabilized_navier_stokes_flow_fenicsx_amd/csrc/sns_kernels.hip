@@ -57,19 +57,49 @@ struct TetLdsT : TetLds {
     double ut[4][3];
 };
 
+// ... with a viscosity law (VL): eps g_a per vertex and the tet's nu_e, d nu_e / d s, 4 C_I nu_e nu' G:G
+struct TetLdsV : TetLds {
+    double eg[12];     // (eps g_a) [a][i]
+    double vs[3];
+};
+
 __device__ __forceinline__ double phi_q(int q, int a) { return q == a ? QB : QA; }
 
-template <int FORM, bool corrected, bool TT>
+// s = 2 eps:eps (= gamma_dot^2) of a constant grad u, eps = sym(grad u)
+__device__ __forceinline__ double shear_rate2(const double gu[3][3]) {
+    const double a = gu[0][1] + gu[1][0], b = gu[0][2] + gu[2][0], c = gu[1][2] + gu[2][1];
+    return 2.0 * (gu[0][0] * gu[0][0] + gu[1][1] * gu[1][1] + gu[2][2] * gu[2][2]) + a * a + b * b + c * c;
+}
+// (eps v)_i = 1/2 ((grad u) v + (grad u)^T v)_i
+__device__ __forceinline__ void eps_apply(const double gu[3][3], const double v[3], double out[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        out[i] = 0.5 * ((gu[i][0] + gu[0][i]) * v[0] + (gu[i][1] + gu[1][i]) * v[1] + (gu[i][2] + gu[2][i]) * v[2]);
+}
+// Carreau law on s: nu_e = nu0 (r + (1 - r) (1 + lambda^2 s)^((n-1)/2)) and dnu = d nu_e / d s.  No square root of s:
+// smooth at rest.  n = 1 gives nu_e == nu0 in every bit (exp(0) = 1, r + (1 - r) rounds to 1).
+__device__ __forceinline__ void carreau(const ViscosityLaw& vl, double nu0, double s, double& nu_e, double& dnu) {
+    const double l2 = vl.lambda * vl.lambda;
+    const double x = 1.0 + l2 * s;
+    const double e = 0.5 * (vl.n - 1.0);
+    const double pw = exp(e * log(x));
+    nu_e = nu0 * (vl.r + (1.0 - vl.r) * pw);
+    dnu = nu0 * (1.0 - vl.r) * e * l2 * (pw / x);
+}
+
+template <int FORM, bool corrected, bool TT, bool VL>
 __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int32_t* __restrict__ tets,
                                                     const double* __restrict__ pts,
                                                     const double* __restrict__ w,
                                                     const uint8_t* __restrict__ bc_mask,
                                                     const double* __restrict__ bc_val, double nu,
                                                     int store_K, double* __restrict__ Ke,
-                                                    double* __restrict__ Fe, FormVariant fv, TimeTerm tt) {
+                                                    double* __restrict__ Fe, FormVariant fv, TimeTerm tt,
+                                                    ViscosityLaw vl) {
+    static_assert(!VL || (FORM == SNS_FORM_NS && !TT), "the viscosity law exists in the steady 3-D NS form only");
     // staging data and the output transpose tile share LDS (the tile is written after a barrier
     // that retires every read of the staging data): 34.8 KB per workgroup -> 4 workgroups per CU
-    using Lds = std::conditional_t<TT, TetLdsT, TetLds>;
+    using Lds = std::conditional_t<TT, TetLdsT, std::conditional_t<VL, TetLdsV, TetLds>>;
     constexpr size_t SH_BYTES = sizeof(Lds) * EL_TETS, TILE_BYTES = sizeof(double) * EL_TPB * 17;
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[SH_BYTES > TILE_BYTES ? SH_BYTES : TILE_BYTES];
     Lds* sh = reinterpret_cast<Lds*>(lds_raw);
@@ -154,6 +184,22 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                 gu[i][j] = W[i] * g[0][j] + W[4 + i] * g[1][j] + W[8 + i] * g[2][j] + W[12 + i] * g[3][j];
         }
         const double divu = gu[0][0] + gu[1][1] + gu[2][2];
+        double nu_t = nu;                                 // the tet's viscosity
+        if constexpr (VL) {
+            double dnu;
+            carreau(vl, nu, shear_rate2(gu), nu_t, dnu);
+            if (q == 0) {
+#pragma unroll
+                for (int aa = 0; aa < 4; ++aa) {
+                    double e3[3];
+                    eps_apply(gu, g[aa], e3);
+                    S.eg[3 * aa] = e3[0]; S.eg[3 * aa + 1] = e3[1]; S.eg[3 * aa + 2] = e3[2];
+                }
+                S.vs[0] = nu_t;
+                S.vs[1] = dnu;
+                S.vs[2] = 4.0 * fv.ci * nu_t * dnu * GG;   // d(C_I nu_e^2 G:G)/2 = vs[2] (eps g_b) . du_b
+            }
+        }
         if (q == 0) {
 #pragma unroll
             for (int aa = 0; aa < 4; ++aa)
@@ -219,7 +265,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                 }
                 theta = tt.theta;
             }
-            const double tau = 1.0 / sqrt(theta + uGu + fv.ci * nu * nu * GG);            // :237-238 (C_I = 36)
+            const double tau = 1.0 / sqrt(theta + uGu + fv.ci * nu_t * nu_t * GG);        // :237-238 (C_I = 36)
             const double nuL = fv.lsic / (trG * tau);                                    // :249
             double* Q = S.q[q];
             Q[0] = u[0]; Q[1] = u[1]; Q[2] = u[2]; Q[3] = p; Q[4] = tau; Q[5] = nuL;
@@ -247,6 +293,18 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
         const double ga[3] = {ga0, ga1, ga2}, gb[3] = {gb0, gb1, gb2};
         const double gab = ga0 * gb0 + ga1 * gb1 + ga2 * gb2;
         const double wd = S.sc[0], divu = S.sc[1], trG = S.sc[2];
+        // viscosity law: nu_e for nu, the viscous term 2 nu_e eps g_a, d tau and d nu_LSIC gain kb = 4 C_I nu_e nu' G:G eps g_b
+        // (eps g_a and eps g_b stay in LDS: only kb lives across the quadrature loop)
+        auto eg = [&](int k) -> double {
+            if constexpr (VL) return S.eg[k];
+            else return 0.0;
+        };
+        double nu_t = nu, kb[3] = {0.0, 0.0, 0.0};
+        if constexpr (VL) {
+            nu_t = S.vs[0];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) kb[j] = S.vs[2] * eg(3 * b + j);
+        }
         if (FORM == SNS_FORM_STOKES) {
             const double vol = 4.0 * wd;
             const double muT = 0.2 * S.sc[3];                                            // :169
@@ -277,8 +335,12 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                 const double t3 = tau * tau * tau;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    const double dtau = -t3 * pb * Gu[j];                         // d tau / d u_(b,j)
-                    const double dnuL = fv.lsic * (tau / trG) * pb * Gu[j];       // d nu_L
+                    double dtau = -t3 * pb * Gu[j];                               // d tau / d u_(b,j)
+                    double dnuL = fv.lsic * (tau / trG) * pb * Gu[j];             // d nu_L
+                    if constexpr (VL) {
+                        dtau -= t3 * kb[j];
+                        dnuL += fv.lsic * (tau / trG) * kb[j];
+                    }
                     cg[j] = dnuL * divu + nuL * gb[j];
                     if (!corrected) {
                         // d(r.g_a) = u_j g_a.g_b + phi_b ((grad u) g_a)_j
@@ -290,7 +352,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                 }
                 if (!need_blocks) {
                 } else if (!corrected) {
-                    double A1 = pa * ugb + nu * gab + tau * sa * pb;
+                    double A1 = pa * ugb + nu_t * gab + tau * sa * pb;
                     if constexpr (TT) A1 += tt.sigma * pa * pb;                       // mass
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
@@ -314,7 +376,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                     for (int j = 0; j < 3; ++j)
                         gp[j] = S.W[3] * S.g[j] + S.W[7] * S.g[3 + j] + S.W[11] * S.g[6 + j] + S.W[15] * S.g[9 + j];
                     double r[3] = {r0 + gp[0], r1 + gp[1], r2 + gp[2]};
-                    double A1 = pa * ugb + nu * gab + tau * uga * ugb;
+                    double A1 = pa * ugb + nu_t * gab + tau * uga * ugb;
                     double mp = 0.0;                                                  // d(tau u_t.g_a) / d u_(b,i) / g_a[i]
                     if constexpr (TT) {
 #pragma unroll
@@ -344,7 +406,8 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                     if (!corrected) {
 #pragma unroll
                         for (int i = 0; i < 3; ++i)
-                            Rl[i] += Q[9 + i] * pa + nu * guga_a[i] - p * ga[i] + tau * u[i] * sa + nuL * divu * ga[i];
+                            Rl[i] += Q[9 + i] * pa + (VL ? 2.0 * nu_t * eg(3 * a + i) : nu * guga_a[i]) - p * ga[i] + tau * u[i] * sa +
+                                     nuL * divu * ga[i];
                         if constexpr (TT) {
 #pragma unroll
                             for (int i = 0; i < 3; ++i) Rl[i] += pa * S.ut[q][i];
@@ -360,7 +423,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                                               gum[6] * ga0 + gum[7] * ga1 + gum[8] * ga2};
 #pragma unroll
                         for (int i = 0; i < 3; ++i)
-                            Rl[i] += Q[9 + i] * pa + nu * vg[i] - p * ga[i] + tau * uga * (Q[9 + i] + gp[i]) +
+                            Rl[i] += Q[9 + i] * pa + (VL ? 2.0 * nu_t * eg(3 * a + i) : nu * vg[i]) - p * ga[i] + tau * uga * (Q[9 + i] + gp[i]) +
                                      nuL * divu * ga[i];
                         if constexpr (TT) {
 #pragma unroll
@@ -368,6 +431,18 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                         }
                     }
                     Rl[3] += pa * divu + fv.pspg * tau * sa;
+                }
+            }
+            if constexpr (VL) {
+                // point-independent: the transpose half of 2 nu_e d eps, and the rank-one 2 (eps g_a) d nu_e^T
+                if (need_blocks) {
+                    const double c1 = 4.0 * nu_t, c2 = 32.0 * S.vs[1];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const double ei = c2 * S.eg[3 * a + i], gi = c1 * gb[i];
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) acc[4 * i + j] += gi * ga[j] + ei * S.eg[3 * b + j];
+                    }
                 }
             }
 #pragma unroll
@@ -416,15 +491,17 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
     }
 }
 
-#define SNS_INST_ELEMENT(F, C, T)                                                                           \
-    template __global__ void k_element<F, C, T>(int64_t, const int32_t*, const double*, const double*,         \
-                                                const uint8_t*, const double*, double, int, double*, double*,  \
-                                                FormVariant, TimeTerm);
-SNS_INST_ELEMENT(SNS_FORM_STOKES, false, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, false, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, true, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, false, true)
-SNS_INST_ELEMENT(SNS_FORM_NS, true, true)
+#define SNS_INST_ELEMENT(F, C, T, V)                                                                        \
+    template __global__ void k_element<F, C, T, V>(int64_t, const int32_t*, const double*, const double*,      \
+                                                   const uint8_t*, const double*, double, int, double*, double*, \
+                                                   FormVariant, TimeTerm, ViscosityLaw);
+SNS_INST_ELEMENT(SNS_FORM_STOKES, false, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, true, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, true, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, false, true)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, false, true)
 
 // quad-permute a double with DPP moves (no LDS, no memory traffic); CTRL = quad_perm encoding
 template <int CTRL>
@@ -444,10 +521,11 @@ __device__ __forceinline__ double quad_perm(double v) {
 // when the state satisfies the Dirichlet data (no lifting term, :65), i.e. every Newton iterate
 // after the first update; the staged k_element path handles the rest.
 // ============================================================================
-template <bool corrected, bool TT>
+template <bool corrected, bool TT, bool VL>
 __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double* __restrict__ pts,
                                                      const double* __restrict__ w, double nu, int a, int b,
-                                                     bool want_res, double acc[16], double Ra[4], const TimeTerm& tt) {
+                                                     bool want_res, double acc[16], double Ra[4], const TimeTerm& tt,
+                                                     const ViscosityLaw& vl) {
     const int32_t nd[4] = {tv.x, tv.y, tv.z, tv.w};
     double X[4][3], W[4][4];
 #pragma unroll
@@ -503,8 +581,11 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
     const double divu = gu[0][0] + gu[1][1] + gu[2][2];
     const double wd = fabs(det) * (1.0 / 24.0);
     const double itrG = 1.0 / trG;
+    // viscosity law: nu_e and nu' = d nu_e / d s once per contribution
+    double nu_t = nu, dnu = 0.0;
+    if constexpr (VL) carreau(vl, nu, shear_rate2(gu), nu_t, dnu);
     // the part of tau^-2 that does not depend on the point: theta (time term) + C_I nu^2 G:G
-    const double m0 = (TT ? tt.theta : 0.0) + 36.0 * nu * nu * GG;
+    const double m0 = (TT ? tt.theta : 0.0) + 36.0 * nu_t * nu_t * GG;
     // time term: the nodal u_t = sigma u + d once, interpolated per point below (one more 3-vector gather per vertex)
     double UT[TT ? 4 : 1][3];
     if constexpr (TT) {
@@ -531,6 +612,22 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
     for (int j = 0; j < 3; ++j) {
         visc[j] = gu[j][0] * ga[0] + gu[j][1] * ga[1] + gu[j][2] * ga[2];                   // (grad u) g_a
         guga[j] = corrected ? (ga[0] * gu[0][j] + ga[1] * gu[1][j] + ga[2] * gu[2][j]) : visc[j];
+    }
+    // law: eps g_a, and kb = 4 C_I nu_e nu' G:G eps g_b carrying d(nu_e) into d tau and d nu_LSIC; the viscous Galerkin
+    // term 2 nu_e eps g_a replaces nu (grad u) g_a; its derivative's point-independent part goes in once, up front
+    double kb[VL ? 3 : 1];
+    if constexpr (VL) {
+        double ea[3], eb[3];
+        eps_apply(gu, ga, ea);
+        eps_apply(gu, gb, eb);
+        const double vol = 4.0 * wd, c1 = vol * nu_t, c2 = 8.0 * vol * dnu, kap = 4.0 * 36.0 * nu_t * dnu * GG;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[4 * i + j] += c1 * gb[i] * ga[j] + c2 * ea[i] * eb[j];
+            visc[i] = 2.0 * ea[i];
+            kb[i] = kap * eb[i];
+        }
     }
     // the quadrature weight wd is folded into the per-point coefficients, so every term lands directly in the
     // caller's accumulators (no per-contribution block)
@@ -576,14 +673,18 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
         double cu[3], cg[3];                                   // both carry the weight
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const double dtau = -t3w * pb * Gu[j];
-            const double dnuL = (tw * itrG) * pb * Gu[j];
+            double dtau = -t3w * pb * Gu[j];
+            double dnuL = (tw * itrG) * pb * Gu[j];
+            if constexpr (VL) {
+                dtau -= t3w * kb[j];
+                dnuL += (tw * itrG) * kb[j];
+            }
             cg[j] = dnuL * divu + (wd * nuL) * gb[j];
             cu[j] = corrected ? dtau : dtau * sa + tw * (u[j] * gab + pb * guga[j]);
             if constexpr (TT && !corrected) cu[j] += (tw * sg * pb) * ga[j];               // d(u_t.g_a)
         }
         if (!corrected) {
-            double A1 = wpa * ugb + (wd * nu) * gab + tw * sa * pb;
+            double A1 = wpa * ugb + (wd * nu_t) * gab + tw * sa * pb;
             if constexpr (TT) A1 += sg * wpa * pb;                                         // mass
             const double ppw = wpa * pb, tgw = tw * gab;
 #pragma unroll
@@ -596,7 +697,7 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
             }
             acc[15] += tgw;
         } else {
-            double A1 = wpa * ugb + (wd * nu) * gab + tw * uga * ugb;
+            double A1 = wpa * ugb + (wd * nu_t) * gab + tw * uga * ugb;
             const double cgu = wpa * pb + tw * uga * pb;       // coefficient of gu[i][j]
             if constexpr (TT) A1 += sg * cgu;                   // mass + SUPG of u_t
             const double mp = TT ? tw * sg * pb : 0.0;
@@ -615,7 +716,7 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
         if (want_res) {
 #pragma unroll
             for (int i = 0; i < 3; ++i)
-                Ra[i] += wpa * conv[i] + (wd * nu) * visc[i] - (wd * p) * ga[i] +
+                Ra[i] += wpa * conv[i] + (wd * nu_t) * visc[i] - (wd * p) * ga[i] +
                          (corrected ? tw * uga * r[i] : tw * u[i] * sa) + (wd * nuL) * divu * ga[i];
             Ra[3] += wpa * divu + tw * sa;
             if constexpr (TT) {
@@ -906,20 +1007,22 @@ __device__ __forceinline__ void tri_block_accumulate_stokes(const int4 tv, const
 
 // one interface for the four forms (aux: Stokes 2-D pressure-stabilisation coefficient beta; nu: 1/Re, or the
 // Stokes 2-D viscosity)
-template <int FORM, bool corrected, bool TT>
+template <int FORM, bool corrected, bool TT, bool VL>
 __device__ __forceinline__ void block_accumulate(const int4 tv, const double* __restrict__ pts,
                                                  const double* __restrict__ w, double nu, double aux, int a, int b,
-                                                 bool want_res, double acc[16], double Ra[4], const TimeTerm& tt) {
+                                                 bool want_res, double acc[16], double Ra[4], const TimeTerm& tt,
+                                                 const ViscosityLaw& vl) {
     static_assert(!TT || FORM == SNS_FORM_NS, "the time term exists in the 3-D NS form only");
+    static_assert(!VL || (FORM == SNS_FORM_NS && !TT), "the viscosity law exists in the steady 3-D NS form only");
     if constexpr (FORM == SNS_FORM_STOKES) tet_block_accumulate_stokes(tv, pts, w, a, b, want_res, acc, Ra);
-    else if constexpr (FORM == SNS_FORM_NS) tet_block_accumulate<corrected, TT>(tv, pts, w, nu, a, b, want_res, acc, Ra, tt);
+    else if constexpr (FORM == SNS_FORM_NS) tet_block_accumulate<corrected, TT, VL>(tv, pts, w, nu, a, b, want_res, acc, Ra, tt, vl);
     else if constexpr (FORM == SNS_FORM_STOKES_2D) tri_block_accumulate_stokes(tv, pts, w, nu, aux, a, b, want_res, acc, Ra);
     else tri_block_accumulate_ugn(tv, pts, w, nu, a, b, want_res, acc, Ra);
 }
 constexpr bool form_is_linear(int form) { return form == SNS_FORM_STOKES || form == SNS_FORM_STOKES_2D; }
 
 // off-diagonal BSR blocks: one lane per slot, slots taken from the host's count-sorted list
-template <int FORM, bool corrected, bool TT>
+template <int FORM, bool corrected, bool TT, bool VL>
 __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32_t* __restrict__ od_order,
                                                        const int64_t* __restrict__ c_ptr,
                                                        const int32_t* __restrict__ c_idx,
@@ -928,7 +1031,8 @@ __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32
                                                        const int32_t* __restrict__ tets,
                                                        const double* __restrict__ pts, const double* __restrict__ w,
                                                        const uint8_t* __restrict__ bc_mask, double nu,
-                                                       double aux, double* __restrict__ vals, TimeTerm tt) {
+                                                       double aux, double* __restrict__ vals, TimeTerm tt,
+                                                       ViscosityLaw vl) {
     const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= n_od) return;
     const int64_t s = od_order[lane];
@@ -953,7 +1057,7 @@ __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32
             id = (uint32_t)c_idx[k];
             tv = *reinterpret_cast<const int4*>(tets + 4 * (int64_t)(id >> 4));
         }
-        block_accumulate<FORM, corrected, TT>(tvc, pts, w, nu, aux, (idc >> 2) & 3, idc & 3, false, acc, nullptr, tt);
+        block_accumulate<FORM, corrected, TT, VL>(tvc, pts, w, nu, aux, (idc >> 2) & 3, idc & 3, false, acc, nullptr, tt, vl);
     }
     const uchar4 mr = *reinterpret_cast<const uchar4*>(bc_mask + 4 * (int64_t)row);
     const uchar4 mc = *reinterpret_cast<const uchar4*>(bc_mask + 4 * (int64_t)col);
@@ -969,14 +1073,15 @@ __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32
 }
 
 // diagonal blocks + node residuals: 4 lanes per node share the ~24 incident tets, DPP quad sums in a fixed order
-template <int FORM, bool corrected, bool TT>
+template <int FORM, bool corrected, bool TT, bool VL>
 __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_t* __restrict__ diag,
                                                     const int64_t* __restrict__ c_ptr,
                                                     const int32_t* __restrict__ c_idx,
                                                     const int32_t* __restrict__ tets, const double* __restrict__ pts,
                                                     const double* __restrict__ w, const uint8_t* __restrict__ bc_mask,
                                                     const double* __restrict__ bc_val, double nu, double aux,
-                                                    double* __restrict__ vals, double* __restrict__ F, TimeTerm tt) {
+                                                    double* __restrict__ vals, double* __restrict__ F, TimeTerm tt,
+                                                    ViscosityLaw vl) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t node = gid >> 2;
     const int q = (int)(gid & 3);
@@ -1003,7 +1108,7 @@ __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_
                 id = (uint32_t)c_idx[k];
                 tv = *reinterpret_cast<const int4*>(tets + 4 * (int64_t)(id >> 4));
             }
-            block_accumulate<FORM, corrected, TT>(tvc, pts, w, nu, aux, a, a, true, acc, R, tt);
+            block_accumulate<FORM, corrected, TT, VL>(tvc, pts, w, nu, aux, a, a, true, acc, R, tt, vl);
         }
     }
     // quad sums: (l0 + l1) + (l2 + l3), identical on every lane
@@ -1046,14 +1151,14 @@ __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_
 // Lifting term of a state that violates its Dirichlet data (:65): F_free += A0[:,B] (g - x_B), A0 = the unconstrained
 // Jacobian.  Same work split as k_fused_diag (4 lanes per node, DPP quad sums); only tets with a violated Dirichlet
 // dof (dl != 0 on one of their nodes) cost anything: their blocks (a,b) are recomputed and applied to dl_b.
-template <int FORM, bool corrected, bool TT>
+template <int FORM, bool corrected, bool TT, bool VL>
 __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_t* __restrict__ diag,
                                                     const int64_t* __restrict__ c_ptr,
                                                     const int32_t* __restrict__ c_idx,
                                                     const int32_t* __restrict__ tets, const double* __restrict__ pts,
                                                     const double* __restrict__ w, const uint8_t* __restrict__ bc_mask,
                                                     const double* __restrict__ dl, double nu, double* __restrict__ F,
-                                                    TimeTerm tt) {
+                                                    TimeTerm tt, ViscosityLaw vl) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t node = gid >> 2;
     const int q = (int)(gid & 3);
@@ -1075,7 +1180,7 @@ __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_
                 double blk[16];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) blk[e] = 0.0;
-                block_accumulate<FORM, corrected, TT>(tv, pts, w, nu, 0.0, a, b, false, blk, nullptr, tt);
+                block_accumulate<FORM, corrected, TT, VL>(tv, pts, w, nu, 0.0, a, b, false, blk, nullptr, tt, vl);
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
                     R[c] += blk[4 * c] * d01.x + blk[4 * c + 1] * d01.y + blk[4 * c + 2] * d23.x + blk[4 * c + 3] * d23.y;
@@ -1094,15 +1199,17 @@ __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_
     const double rq = q == 0 ? R[0] : (q == 1 ? R[1] : (q == 2 ? R[2] : R[3]));
     if (!bc_mask[dof]) F[dof] += rq;
 }
-#define SNS_INST_LIFT(FM, C, T)                                                                                        \
-    template __global__ void k_fused_lift<FM, C, T>(int32_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
-                                                    const double*, const double*, const uint8_t*, const double*, double,   \
-                                                    double*, TimeTerm);
-SNS_INST_LIFT(SNS_FORM_NS, false, false)
-SNS_INST_LIFT(SNS_FORM_NS, true, false)
-SNS_INST_LIFT(SNS_FORM_UGN_2D, false, false)
-SNS_INST_LIFT(SNS_FORM_NS, false, true)
-SNS_INST_LIFT(SNS_FORM_NS, true, true)
+#define SNS_INST_LIFT(FM, C, T, V)                                                                                     \
+    template __global__ void k_fused_lift<FM, C, T, V>(int32_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
+                                                       const double*, const double*, const uint8_t*, const double*, double, \
+                                                       double*, TimeTerm, ViscosityLaw);
+SNS_INST_LIFT(SNS_FORM_NS, false, false, false)
+SNS_INST_LIFT(SNS_FORM_NS, true, false, false)
+SNS_INST_LIFT(SNS_FORM_UGN_2D, false, false, false)
+SNS_INST_LIFT(SNS_FORM_NS, false, true, false)
+SNS_INST_LIFT(SNS_FORM_NS, true, true, false)
+SNS_INST_LIFT(SNS_FORM_NS, false, false, true)
+SNS_INST_LIFT(SNS_FORM_NS, true, false, true)
 
 // dl = g - w on Dirichlet dofs, 0 elsewhere
 __global__ __launch_bounds__(256) void k_bc_defect(int64_t ndof, const uint8_t* __restrict__ bc_mask,
@@ -1112,20 +1219,22 @@ __global__ __launch_bounds__(256) void k_bc_defect(int64_t ndof, const uint8_t* 
         dl[i] = bc_mask[i] ? (bc_val[i] - w[i]) : 0.0;
 }
 
-#define SNS_INST_FUSED(FM, C, T)                                                                                   \
-    template __global__ void k_fused_offdiag<FM, C, T>(int64_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
+#define SNS_INST_FUSED(FM, C, T, V)                                                                                \
+    template __global__ void k_fused_offdiag<FM, C, T, V>(int64_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
                                                 const int32_t*, const int32_t*, const double*, const double*,       \
-                                                const uint8_t*, double, double, double*, TimeTerm);                 \
-    template __global__ void k_fused_diag<FM, C, T>(int32_t, const int32_t*, const int64_t*, const int32_t*,            \
+                                                const uint8_t*, double, double, double*, TimeTerm, ViscosityLaw);   \
+    template __global__ void k_fused_diag<FM, C, T, V>(int32_t, const int32_t*, const int64_t*, const int32_t*,         \
                                              const int32_t*, const double*, const double*, const uint8_t*,          \
-                                             const double*, double, double, double*, double*, TimeTerm);
-SNS_INST_FUSED(SNS_FORM_NS, false, false)
-SNS_INST_FUSED(SNS_FORM_NS, true, false)
-SNS_INST_FUSED(SNS_FORM_STOKES, false, false)
-SNS_INST_FUSED(SNS_FORM_STOKES_2D, false, false)
-SNS_INST_FUSED(SNS_FORM_UGN_2D, false, false)
-SNS_INST_FUSED(SNS_FORM_NS, false, true)
-SNS_INST_FUSED(SNS_FORM_NS, true, true)
+                                             const double*, double, double, double*, double*, TimeTerm, ViscosityLaw);
+SNS_INST_FUSED(SNS_FORM_NS, false, false, false)
+SNS_INST_FUSED(SNS_FORM_NS, true, false, false)
+SNS_INST_FUSED(SNS_FORM_STOKES, false, false, false)
+SNS_INST_FUSED(SNS_FORM_STOKES_2D, false, false, false)
+SNS_INST_FUSED(SNS_FORM_UGN_2D, false, false, false)
+SNS_INST_FUSED(SNS_FORM_NS, false, true, false)
+SNS_INST_FUSED(SNS_FORM_NS, true, true, false)
+SNS_INST_FUSED(SNS_FORM_NS, false, false, true)
+SNS_INST_FUSED(SNS_FORM_NS, true, false, true)
 
 // residual-only pass of the 2-D UGN form: one lane per triangle, Fe[16 t + 4 a + c] (same layout as the tet kernel,
 // so k_gather_residual serves both)
@@ -1199,11 +1308,12 @@ __global__ __launch_bounds__(256) void k_bc_residual(int64_t ndof, const uint8_t
 // Residual-only element pass for states that already satisfy the Dirichlet data (no lifting term):
 // ONE LANE PER TET, every lane busy (the fused kernel keeps 12 of 16 lanes idle in its per-point
 // phase).  Used by the line search (F(x - lambda y), :51-67 without the Jacobian).
-template <bool corrected, bool TT>
+template <bool corrected, bool TT, bool VL>
 __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int32_t* __restrict__ tets,
                                                       const double* __restrict__ pts,
                                                       const double* __restrict__ w, double nu,
-                                                      double* __restrict__ Fe, TimeTerm tt) {
+                                                      double* __restrict__ Fe, TimeTerm tt, ViscosityLaw vl) {
+    static_assert(!(VL && TT), "the viscosity law exists in the steady 3-D NS form only");
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tets) return;
     const int4 tv = *reinterpret_cast<const int4*>(tets + 4 * t);
@@ -1261,6 +1371,11 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
     }
     const double divu = gu[0][0] + gu[1][1] + gu[2][2];
     const double wd = fabs(det) * (1.0 / 24.0);
+    double nu_t = nu;                                      // viscosity law: the tet's nu_e
+    if constexpr (VL) {
+        double dnu;
+        carreau(vl, nu, shear_rate2(gu), nu_t, dnu);
+    }
     double UT[TT ? 4 : 1][3];                              // nodal u_t = sigma u + d
     if constexpr (TT) {
 #pragma unroll
@@ -1305,7 +1420,7 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
 #pragma unroll
             for (int j = 0; j < 3; ++j) r[j] += ut[j];
         }
-        const double tau = 1.0 / sqrt((TT ? tt.theta : 0.0) + uGu + 36.0 * nu * nu * GG);
+        const double tau = 1.0 / sqrt((TT ? tt.theta : 0.0) + uGu + 36.0 * nu_t * nu_t * GG);
         const double nuL = 1.0 / (trG * tau);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -1314,9 +1429,10 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
             const double uga = u[0] * g[a][0] + u[1] * g[a][1] + u[2] * g[a][2];
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                const double visc = gu[i][0] * g[a][0] + gu[i][1] * g[a][1] + gu[i][2] * g[a][2];
+                double visc = gu[i][0] * g[a][0] + gu[i][1] * g[a][1] + gu[i][2] * g[a][2];
+                if constexpr (VL) visc += gu[0][i] * g[a][0] + gu[1][i] * g[a][1] + gu[2][i] * g[a][2];      // 2 (eps g_a)_i
                 const double supg = corrected ? tau * uga * r[i] : tau * u[i] * sa;
-                R[a][i] += conv[i] * pa + nu * visc - p * g[a][i] + supg + nuL * divu * g[a][i];
+                R[a][i] += conv[i] * pa + nu_t * visc - p * g[a][i] + supg + nuL * divu * g[a][i];
                 if constexpr (TT) R[a][i] += pa * ut[i];
             }
             R[a][3] += pa * divu + tau * sa;
@@ -1329,10 +1445,72 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
         o[2 * a + 1] = make_double2(wd * R[a][2], wd * R[a][3]);
     }
 }
-template __global__ void k_residual_tet<false, false>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm);
-template __global__ void k_residual_tet<true, false>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm);
-template __global__ void k_residual_tet<false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm);
-template __global__ void k_residual_tet<true, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm);
+template __global__ void k_residual_tet<false, false>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
+template __global__ void k_residual_tet<true, false>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
+template __global__ void k_residual_tet<false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
+template __global__ void k_residual_tet<true, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
+template __global__ void k_residual_tet<false, false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
+template __global__ void k_residual_tet<true, false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
+
+// Per-tet viscosity of a state (sns_element_viscosity): one lane per tet, nu_e of the law (nu0 without one) and
+// gamma_dot = sqrt(2 eps:eps).
+template <bool LAW>
+__global__ __launch_bounds__(256) void k_element_viscosity(int64_t n_tets, const int32_t* __restrict__ tets,
+                                                           const double* __restrict__ pts, const double* __restrict__ w,
+                                                           double nu, ViscosityLaw vl, double* __restrict__ nu_e,
+                                                           double* __restrict__ gamma_dot) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tets) return;
+    const int4 tv = *reinterpret_cast<const int4*>(tets + 4 * t);
+    const int32_t nd[4] = {tv.x, tv.y, tv.z, tv.w};
+    double X[4][3], U[4][3];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const double* pp = pts + 3 * (int64_t)nd[a];
+        X[a][0] = pp[0]; X[a][1] = pp[1]; X[a][2] = pp[2];
+        const double* wp = w + 4 * (int64_t)nd[a];
+        const double2 w0 = *reinterpret_cast<const double2*>(wp);
+        U[a][0] = w0.x; U[a][1] = w0.y; U[a][2] = wp[2];
+    }
+    double J[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        J[i][0] = X[1][i] - X[0][i];
+        J[i][1] = X[2][i] - X[0][i];
+        J[i][2] = X[3][i] - X[0][i];
+    }
+    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+    const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+    const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
+    const double id = 1.0 / det;
+    double K[3][3];
+    K[0][0] = c00 * id; K[1][0] = c01 * id; K[2][0] = c02 * id;
+    K[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
+    K[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
+    K[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
+    K[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
+    K[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
+    K[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+    double g[4][3], gu[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        g[1][j] = K[0][j]; g[2][j] = K[1][j]; g[3][j] = K[2][j];
+        g[0][j] = -(K[0][j] + K[1][j] + K[2][j]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) gu[i][j] = U[0][i] * g[0][j] + U[1][i] * g[1][j] + U[2][i] * g[2][j] + U[3][i] * g[3][j];
+    }
+    const double s = shear_rate2(gu);
+    double nu_t = nu;
+    if constexpr (LAW) {
+        double dnu;
+        carreau(vl, nu, s, nu_t, dnu);
+    }
+    if (nu_e) nu_e[t] = nu_t;
+    if (gamma_dot) gamma_dot[t] = sqrt(s);
+}
+template __global__ void k_element_viscosity<false>(int64_t, const int32_t*, const double*, const double*, double, ViscosityLaw, double*, double*);
+template __global__ void k_element_viscosity<true>(int64_t, const int32_t*, const double*, const double*, double, ViscosityLaw, double*, double*);
 
 // BSR slot <- sum over its contributing element blocks (fixed order => bitwise
 // reproducible), Dirichlet rows AND columns zeroed, unit diagonal (:74).

@@ -696,11 +696,11 @@ int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matri
         if (want_matrix)
             hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_STOKES_2D, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
                                h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, state,
-                               h->bc_mask, nu_s, beta, L.vals, TimeTerm());
+                               h->bc_mask, nu_s, beta, L.vals, TimeTerm(), ViscosityLaw());
         if (want_matrix || F)
             hipLaunchKernelGGL((k_fused_diag<SNS_FORM_STOKES_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
                                L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, state, h->bc_mask, h->bc_val, nu_s, beta,
-                               want_matrix ? L.vals : (double*)nullptr, F, TimeTerm());
+                               want_matrix ? L.vals : (double*)nullptr, F, TimeTerm(), ViscosityLaw());
         if (w && F) hipLaunchKernelGGL(k_bc_residual, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, F);
     } else {
         const double nu = 1.0 / h->opt.reynolds;
@@ -716,10 +716,10 @@ int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matri
         if (want_matrix) {
             hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_UGN_2D, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
                                h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, w, h->bc_mask,
-                               nu, 0.0, L.vals, TimeTerm());
+                               nu, 0.0, L.vals, TimeTerm(), ViscosityLaw());
             hipLaunchKernelGGL((k_fused_diag<SNS_FORM_UGN_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
                                L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F,
-                               TimeTerm());
+                               TimeTerm(), ViscosityLaw());
         } else {
             if (!h->Fe) SNS_TRY(dev_alloc(&h->Fe, (size_t)h->E * 16));
             hipLaunchKernelGGL(k_residual_tri, dim3((unsigned)((h->E + 255) / 256)), dim3(256), 0, h->stream, h->E,
@@ -732,7 +732,7 @@ int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matri
             SNS_TRY(get_vec(h, 13, &dl));
             hipLaunchKernelGGL(k_bc_defect, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, dl);
             hipLaunchKernelGGL((k_fused_lift<SNS_FORM_UGN_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F, TimeTerm());
+                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F, TimeTerm(), ViscosityLaw());
         }
     }
     if (want_matrix) {
@@ -776,9 +776,9 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         const unsigned gd = (unsigned)((4 * (int64_t)h->n_owned + 255) / 256);
         hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_STOKES, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
                            h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, h->gext,
-                           h->bc_mask, nu, 0.0, L.vals, TimeTerm());
+                           h->bc_mask, nu, 0.0, L.vals, TimeTerm(), ViscosityLaw());
         hipLaunchKernelGGL((k_fused_diag<SNS_FORM_STOKES, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag,
-                           h->c_ptr, h->c_idx, h->tets, h->pts, h->gext, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F, TimeTerm());
+                           h->c_ptr, h->c_idx, h->tets, h->pts, h->gext, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F, TimeTerm(), ViscosityLaw());
         h->has_matrix = true;
         h->transposed = false;
         h->pc_ready = false;
@@ -791,14 +791,14 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         // state that violates its Dirichlet data adds the lifting term in a third pass over the boundary tets
         const unsigned go = (unsigned)((h->n_od + 255) / 256);
         const unsigned gd = (unsigned)((4 * (int64_t)h->n_owned + 255) / 256);
-        // (C: corrected convection, T: the handle has a time term -- both compile-time variants of the kernels)
+        // (C: corrected convection, V: 1 = the handle has a time term, 2 = a viscosity law -- compile-time variants of the kernels)
         dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-            dispatch<1, 0>(h->tt_on, [&](auto T) {
-                hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_NS, C() != 0, T() != 0>), dim3(go), dim3(256), 0, h->stream, h->n_od,
+            dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
+                hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(go), dim3(256), 0, h->stream, h->n_od,
                                    h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, w, h->bc_mask, nu, 0.0,
-                                   L.vals, h->tt);
-                hipLaunchKernelGGL((k_fused_diag<SNS_FORM_NS, C() != 0, T() != 0>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                                   L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F, h->tt);
+                                   L.vals, h->tt, h->vl);
+                hipLaunchKernelGGL((k_fused_diag<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
+                                   L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F, h->tt, h->vl);
             });
         });
         if (!fast_residual && F) {
@@ -807,9 +807,9 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
             const int64_t ndof = 4 * (int64_t)h->n;
             hipLaunchKernelGGL(k_bc_defect, dim3(vec_grid(ndof)), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, dl);
             dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-                dispatch<1, 0>(h->tt_on, [&](auto T) {
-                    hipLaunchKernelGGL((k_fused_lift<SNS_FORM_NS, C() != 0, T() != 0>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                                       L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F, h->tt);
+                dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
+                    hipLaunchKernelGGL((k_fused_lift<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
+                                       L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F, h->tt, h->vl);
                 });
             });
         }
@@ -826,20 +826,20 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
     if (fast_residual) {
         const unsigned gt = (unsigned)((h->E + 255) / 256);
         dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-            dispatch<1, 0>(h->tt_on, [&](auto T) {
-                hipLaunchKernelGGL((k_residual_tet<C() != 0, T() != 0>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w,
-                                   nu, h->Fe, h->tt);
+            dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
+                hipLaunchKernelGGL((k_residual_tet<C() != 0, V() == 1, V() == 2>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w,
+                                   nu, h->Fe, h->tt, h->vl);
             });
         });
     } else if (grid > 0) {
         if (form == SNS_FORM_STOKES)
             hipLaunchKernelGGL((k_element<SNS_FORM_STOKES, false>), dim3(grid), dim3(256), 0, h->stream, h->E, h->tets,
-                               h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv, TimeTerm());
+                               h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv, TimeTerm(), ViscosityLaw());
         else
             dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-                dispatch<1, 0>(h->tt_on, [&](auto T) {
-                    hipLaunchKernelGGL((k_element<SNS_FORM_NS, C() != 0, T() != 0>), dim3(grid), dim3(256), 0, h->stream, h->E,
-                                       h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv, h->tt);
+                dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
+                    hipLaunchKernelGGL((k_element<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(grid), dim3(256), 0, h->stream, h->E,
+                                       h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv, h->tt, h->vl);
                 });
             });
     }

@@ -46,6 +46,41 @@ def _continuation() -> bool:
     return bool(os.environ.get("SNS_CONTINUATION"))
 
 
+def _viscosity_law():
+    """SNS_VISCOSITY_LAW=carreau:<lambda>,<n>,<ratio>: the Navier-Stokes legs of DuctStokesFlow.py and
+    NavierStokesChannelFlow.py run with the Carreau law (FlowProblem.set_viscosity_law; the Stokes start stays Newtonian).
+    Returns (lambda, n, ratio) or None."""
+    spec = os.environ.get("SNS_VISCOSITY_LAW")
+    if not spec:
+        return None
+    kind, _, args = spec.partition(":")
+    vals = [float(v) for v in args.split(",")] if args else []
+    if kind != "carreau" or len(vals) != 3:
+        raise ValueError("SNS_VISCOSITY_LAW=carreau:<lambda>,<n>,<ratio>")
+    return tuple(vals)
+
+
+def _solve_ns(P, w, rank):
+    """solve_navier_stokes as the reference calls it; with SNS_VISCOSITY_LAW the problem takes the law first
+    (SNS_CONTINUATION=1 then also walks the power-law index down from 1) and the range of nu_e is printed."""
+    from .solver import newton_with_law_continuation, solve_navier_stokes
+    law = _viscosity_law()
+    if law is None:
+        return solve_navier_stokes(P, w, rank, continuation=_continuation())
+    P.set_viscosity_law(*law)
+    if _continuation():
+        w0 = w.clone()
+        w, res = newton_with_law_continuation(P, w, verbose=(rank == 0))
+        if res.reason <= 0:
+            w = w0
+    out = solve_navier_stokes(P, w, rank, continuation=_continuation())
+    nu, _ = P.element_viscosity(out[0])
+    if rank == 0:
+        print(f"Viscosity law carreau lambda={law[0]:g} n={law[1]:g} ratio={law[2]:g}: min / max nu_e = "
+              f"{float(nu.min()):.6e} / {float(nu.max()):.6e}", flush=True)
+    return out
+
+
 def _rank():
     try:
         import torch.distributed as dist
@@ -268,7 +303,7 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
     warm-started from the previous one.  ``interp_device`` (e.g. "cuda:0") runs the coarse-to-fine
     interpolation on that GPU instead of the host (interpolate_initial_guess)."""
     import torch
-    from .solver import solve_navier_stokes, solve_stokes_problem
+    from .solver import solve_stokes_problem
     Re, img_fname, flowrate_ratio, channel_mesh_size = parse_arguments(argv)
     rank = _rank()
     if rank == 0:
@@ -280,7 +315,7 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
     # Solve Coarse Navier Stokes
     if rank == 0:
         print("Interpolating Stokes Flow", flush=True)
-    w_coarse, u, p = solve_navier_stokes(P, U_stokes.clone(), rank, continuation=_continuation())
+    w_coarse, u, p = _solve_ns(P, U_stokes.clone(), rank)
     w_coarse_host = _to_global_host(P, w_coarse)
     P.close()
     # Solve Navier Stokes With User Defined Mesh
@@ -289,7 +324,7 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
     if rank == 0:
         print("Interpolating Coarse NS Flow", flush=True)
     w0 = interpolate_initial_guess(msh, w_coarse_host, msh_f, device=interp_device)
-    w, u, p = solve_navier_stokes(Pf, _from_global_host(Pf, w0), rank, continuation=_continuation())
+    w, u, p = _solve_ns(Pf, _from_global_host(Pf, w0), rank)
     wg = _to_global_host(Pf, w)
     out = dict(msh=msh_f, w=wg, u=wg.reshape(-1, 4)[:, :3].copy(), p=wg.reshape(-1, 4)[:, 3].copy(), Re=Re, img_fname=img_fname,
                channel_mesh_size=channel_mesh_size, flowrate_ratio=flowrate_ratio, newton=Pf.last_newton)
@@ -340,6 +375,8 @@ def duct_stokes_main(argv=None):
     M.write_msh2(msh, f"{gmsh_fname}.msh")                        # gmsh.write(f'{gmsh_fname}.msh') :141
     P = _problem(msh, B.duct_bcs(msh))
     U, res = P.stokes_solve()
+    if _viscosity_law() is not None:                              # opt-in: a Navier-Stokes leg with the law, from the Stokes start
+        U = _solve_ns(P, U.clone(), _rank())[0]
     W = _to_global_host(P, U).reshape(-1, 4)
     u, p = W[:, :3], W[:, 3]
     if _rank() == 0:

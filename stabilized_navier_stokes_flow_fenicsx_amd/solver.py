@@ -103,6 +103,7 @@ class FlowProblem:
         check(create(C.byref(h), len(pts), len(tets), pts.ctypes.data, tets.ctypes.data,
                      self.bc_mask.ctypes.data, self.bc_val.ctypes.data, idx, C.byref(self.options)))
         self.h = h
+        self.viscosity_law = None                      # (lambda, n, nu_inf_ratio) while set_viscosity_law is in force
         self.n_local = len(pts)
         self.n_owned = len(pts)
         with torch.cuda.device(self.device):
@@ -382,6 +383,30 @@ class FlowProblem:
                                      C.byref(reason), C.byref(kits)))
         return w, NewtonResult(its.value, reason.value, kits.value, [], time.time() - t0)
 
+    # -- generalised-Newtonian viscosity (no counterpart in the reference: nu = 1/Re everywhere) ----------------------
+    def set_viscosity_law(self, lam: float, n: float, nu_inf_ratio: float = 0.0):
+        """Every NS assembly of this problem from now on takes the Carreau law (sns_set_viscosity_law): on each tet
+        nu_e = nu0 (r + (1 - r)(1 + lam^2 s)^((n-1)/2)) with s = 2 eps:eps, nu0 = 1/Re and r = ``nu_inf_ratio``; the viscous
+        term becomes (2 nu_e eps(u), grad v), nu_e enters tau, the Jacobian stays the exact derivative.  n < 1 shear-thins.
+        Single-GPU 3-D problems; not together with a time term."""
+        check(self.lib.sns_set_viscosity_law(self.h, _lib.LAW_CARREAU, float(lam), float(n), float(nu_inf_ratio)))
+        self.viscosity_law = (float(lam), float(n), float(nu_inf_ratio))
+
+    def clear_viscosity_law(self):
+        """Back to the Newtonian form of the reference, bit for bit."""
+        check(self.lib.sns_set_viscosity_law(self.h, _lib.LAW_NEWTONIAN, 0.0, 1.0, 0.0))
+        self.viscosity_law = None
+
+    def element_viscosity(self, w):
+        """(nu_e, gamma_dot) of the state ``w``: one value per tet, device tensors (sns_element_viscosity); nu_e = 1/Re
+        everywhere without a law."""
+        w = self._vec(w)
+        nt = self.sizes()["n_tets"]
+        nu = torch.empty(nt, dtype=torch.float64, device=self.device)
+        gd = torch.empty(nt, dtype=torch.float64, device=self.device)
+        check(self.lib.sns_element_viscosity(self.h, _ptr(w), _ptr(nu), _ptr(gd)))
+        return nu, gd
+
     # -- introspection ----------------------------------------------------------
     def sizes(self):
         nl, no, nt, nz = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
@@ -639,6 +664,43 @@ def newton_with_reynolds_continuation(problem: FlowProblem, w: torch.Tensor, max
     w.copy_(cur)
     r.ksp_its = total_ksp
     return w, r
+
+
+def newton_with_law_continuation(problem: FlowProblem, w: torch.Tensor, steps: int = 4, max_bisections: int = 6,
+                                 verbose: bool = False):
+    """Newton at the problem's viscosity law (``problem.set_viscosity_law``) by continuation in the power-law index: the
+    index walks from 1 (nu_e = nu0: the Newtonian stress-divergence form) to the law's n in ``steps`` equal steps in log n,
+    each stage starting from the previous solution; a stage that does not converge gets the geometric midpoint between it
+    and the last converged index put in front of it (at most ``max_bisections`` times in all).  lambda and nu_inf_ratio
+    stay at the law's values.  NOT in the reference: opt-in robustness, modelled on ``newton_with_reynolds_continuation``.
+    Returns (w, result of the last stage); on failure ``w`` is unchanged and the result is the failed stage's.  The
+    problem's law is the target law afterwards either way."""
+    law = getattr(problem, "viscosity_law", None)
+    if law is None:
+        raise ValueError("newton_with_law_continuation needs a viscosity law: call problem.set_viscosity_law first")
+    lam, n, r = law
+    todo = [float(np.exp(np.log(n) * k / int(steps))) for k in range(int(steps))] + [n]      # n^(k/steps): 1 ... n
+    cur, n_done, res = w.clone(), None, None
+    total_ksp = bisections = 0
+    try:
+        while todo:
+            problem.set_viscosity_law(lam, todo[0], r)
+            w_try, res = problem.newton_solve(cur.clone())
+            total_ksp += res.ksp_its
+            if verbose:
+                print(f"  continuation: n {todo[0]:g}: SNES reason {res.reason}, {res.its} its, {res.ksp_its} ksp its", flush=True)
+            if res.reason > 0:
+                cur, n_done = w_try, todo.pop(0)
+                continue
+            bisections += 1
+            if n_done is None or bisections > max_bisections:
+                return w, res
+            todo.insert(0, float(np.sqrt(n_done * todo[0])))
+    finally:
+        problem.set_viscosity_law(lam, n, r)
+    w.copy_(cur)
+    res.ksp_its = total_ksp
+    return w, res
 
 
 def solve_unsteady(problem: FlowProblem, w0, dt: float, n_steps: int, order: int = 2, theta_coeff: float = 4.0, callback=None):

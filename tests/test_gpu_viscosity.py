@@ -1,0 +1,418 @@
+"""Generalised-Newtonian (Carreau) viscosity of the 3-D NS form on the GPU (sns_set_viscosity_law, sns_element_viscosity;
+solver.newton_with_law_continuation), everything through the C-ABI.
+
+The reference has a constant viscosity; the yardstick is the test-side oracle tests/viscosity_oracle.py (literal restatement,
+autograd Jacobian, LU-Newton) whose own checks are tests/test_host_viscosity.py, and its fields in
+tests/golden/viscosity_cases.npz.  Tolerances as in tests/test_gpu_transient.py: operators 1e-12 relative, the two assembly
+paths against each other 1e-13, Krylov-converged fields 1e-6, J dw against central differences of the residual 1e-6."""
+import numpy as np
+import pytest
+import torch
+
+import viscosity_oracle as VO
+from conftest import rel
+from oracle import forms_literal as FL
+from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B
+from stabilized_navier_stokes_flow_fenicsx_amd import functionals as Fn
+from stabilized_navier_stokes_flow_fenicsx_amd import mesh as M
+from stabilized_navier_stokes_flow_fenicsx_amd import mesh2d as M2
+from stabilized_navier_stokes_flow_fenicsx_amd import solver as S
+from stabilized_navier_stokes_flow_fenicsx_amd.solver import FlowProblem, SnsError
+from test_gpu_adjoint import TIGHT as ADJ_TIGHT
+from test_gpu_adjoint import _adjoint_identity, _check_sensitivities
+from test_host_viscosity import FIXTURE, golden_script
+
+pytestmark = pytest.mark.gpu
+TIGHT = dict(ksp_rtol=1e-11, snes_rtol=1e-10, snes_atol=1e-14, snes_stol=1e-14)
+G = golden_script()
+D = G.DUCT
+LAW = (D["lam"], D["n"], D["r"])
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()
+
+
+def _one_tet(X):
+    return M.TetMesh(np.ascontiguousarray(X), np.array([[0, 1, 2, 3]], np.int32), np.zeros((0, 3), np.int32), np.zeros(0, np.int32))
+
+
+def _fields_close(a, b, tol=1e-6):
+    a, b = np.asarray(a).reshape(-1, 4), np.asarray(b).reshape(-1, 4)
+    return rel(a[:, :3], b[:, :3]) < tol and rel(a[:, 3], b[:, 3]) < tol
+
+
+# ---- 1. element level ------------------------------------------------------------------------------------------------
+N_R = [(n, r) for n in (0.3, 0.7, 1.0, 1.5) for r in (0.0, 0.05)]
+
+
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_element_matrices_against_the_oracle(corrected):
+    fx = np.load(FIXTURE)
+    X, Ws = fx["el_X"], fx["el_W"]
+    none = (np.zeros(16, np.uint8), np.zeros(16))
+    for i in range(len(X)):
+        W, Re, lam = Ws[i], float(fx["el_Re"][i]), float(fx["el_lam"][i])
+        assert 5.0 <= Re <= 200.0 and 0.1 <= lam <= 10.0
+        oracle = {nr: VO.element(X[i][None], W[None], Re, lam, *nr, corrected_convection=bool(corrected)) for nr in N_R}
+        assert rel(oracle[(0.7, 0.05)][0][0], fx["el_F"][corrected][i]) < 1e-12        # (the fixture's record)
+        for fused in (0, 1):
+            P = FlowProblem(_one_tet(X[i]), none, reynolds=Re, corrected_convection=corrected, pc_type="bjacobi", assembly_fused=fused)
+            for nr in N_R:
+                Fo, Jo = oracle[nr]
+                P.set_viscosity_law(lam, *nr)
+                F = P.zeros()
+                P.jacobian(_dev(W), "ns", residual_out=F)
+                tag = (i, fused, nr)
+                if not fused:                                        # the staged kernel's own output
+                    Ke = P.element_matrices().cpu().numpy()[0]
+                    assert rel(Ke.transpose(0, 2, 1, 3).reshape(16, 16), Jo[0]) < 1e-12, tag
+                assert rel(P.to_scipy().toarray(), Jo[0]) < 1e-12, tag
+                assert rel(F.cpu().numpy(), Fo[0]) < 1e-12, tag
+                assert rel(P.residual(_dev(W), "ns").cpu().numpy(), Fo[0]) < 1e-12, tag      # one lane per tet
+            P.close()
+
+
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_perturbed_form_variant_with_a_law(corrected):
+    rng = np.random.default_rng(62)
+    X = G.random_tets(rng, 2)
+    none = (np.zeros(16, np.uint8), np.zeros(16))
+    base = dict(FL.VARIANT)
+    try:
+        FL.VARIANT.update(ci=144.0, lsic=4.0, pspg=-1.0, one_point=True)
+        for i in range(2):
+            W = rng.normal(size=16)
+            Fo, Jo = VO.element(X[i][None], W[None], 40.0, 2.0, 0.4, 0.05, corrected_convection=bool(corrected))
+            P = FlowProblem(_one_tet(X[i]), none, reynolds=40.0, corrected_convection=corrected, pc_type="bjacobi")
+            P.set_form_variant(c_inverse=144.0, lsic_scale=4.0, pspg_sign=-1.0, one_point_quadrature=True)
+            P.set_viscosity_law(2.0, 0.4, 0.05)
+            F = P.zeros()
+            P.jacobian(_dev(W), "ns", residual_out=F)
+            assert rel(P.to_scipy().toarray(), Jo[0]) < 1e-12 and rel(F.cpu().numpy(), Fo[0]) < 1e-12
+            assert rel(P.residual(_dev(W), "ns").cpu().numpy(), Fo[0]) < 1e-12
+            P.close()
+    finally:
+        FL.VARIANT.update(base)
+
+
+# ---- 2. global level -------------------------------------------------------------------------------------------------
+def _channel():
+    m = M.channel_mesh((9, 5, 4), jitter=0.2)
+    mask, g = B.channel_bcs(m, *B.two_stream_profiles(0.4)).flatten()
+    return m, mask, g
+
+
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_fused_staged_and_oracle_agree_globally(corrected):
+    rng = np.random.default_rng(63)
+    m, mask, g = _channel()
+    m.tets = np.ascontiguousarray(np.take_along_axis(m.tets, np.argsort(rng.random(m.tets.shape), axis=1), axis=1))
+    Bm = mask.astype(bool)
+    w = rng.normal(size=m.num_dofs) * 0.5
+    w[Bm] = g[Bm]
+    w2 = w.copy()
+    w2[np.nonzero(Bm)[0][::3]] += 0.3                              # violates the Dirichlet data: lifting (k_fused_lift)
+    Re, law = 17.0, (2.0, 0.5, 0.02)
+    kw = dict(corrected_convection=bool(corrected))
+    P = FlowProblem(m, (mask, g), reynolds=Re, corrected_convection=corrected)
+    P.set_viscosity_law(*law)
+    for state in (w, w2):
+        Jo, Fo = VO.assemble(m.points, m.tets, state, Re, *law, mask, g, **kw)
+        got = []
+        for fused in (1, 0):
+            P.set_options(assembly_fused=fused)
+            F = P.zeros()
+            P.jacobian(_dev(state), "ns", residual_out=F)
+            got.append((P.to_scipy(), F.cpu().numpy()))
+            assert abs(got[-1][0] - Jo).max() < 1e-12 * abs(Jo).max(), fused
+            assert rel(got[-1][1], Fo) < 1e-12, fused
+            assert rel(P.residual(_dev(state), "ns").cpu().numpy(), Fo) < 1e-12, fused
+        assert abs(got[0][0] - got[1][0]).max() < 1e-13 * abs(got[1][0]).max()
+        assert rel(got[0][1], got[1][1]) < 1e-13
+    P.close()
+
+
+# ---- 3. no-op --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [1, 0])
+def test_cleared_law_is_bitwise_the_newtonian_handle(fused):
+    rng = np.random.default_rng(64)
+    m, mask, g = _channel()
+    w = rng.normal(size=m.num_dofs) * 0.5
+    w[mask.astype(bool)] = g[mask.astype(bool)]
+    wd = _dev(w)
+
+    def system(P):
+        F = P.zeros()
+        P.jacobian(wd, "ns", residual_out=F)
+        return P.bsr()[2].clone(), F.clone(), P.residual(wd, "ns")
+
+    P0 = FlowProblem(m, (mask, g), reynolds=30.0, assembly_fused=fused)
+    v0, F0, R0 = system(P0)
+    nu0, gd0 = P0.element_viscosity(wd)
+    assert torch.all(nu0 == 1.0 / 30.0) and float(gd0.min()) >= 0.0 and float(gd0.max()) > 0.0
+    P0.close()
+    P1 = FlowProblem(m, (mask, g), reynolds=30.0, assembly_fused=fused)
+    P1.clear_viscosity_law()                                       # set_viscosity_law(0, ...) on a fresh handle
+    v1, F1, R1 = system(P1)
+    assert torch.equal(v0, v1) and torch.equal(F0, F1) and torch.equal(R0, R1)
+    P1.set_viscosity_law(2.0, 0.5, 0.01)
+    v2, F2, _ = system(P1)
+    assert not torch.equal(v0, v2) and not torch.equal(F0, F2)     # (the law does something)
+    nu2, gd2 = P1.element_viscosity(wd)
+    assert torch.equal(gd0, gd2) and float(nu2.max()) <= 1.0 / 30.0 and float(nu2.min()) < 0.5 / 30.0      # (nu0 only where nothing shears)
+    P1.set_viscosity_law(2.0, 1.0, 0.05)                           # n = 1 with lambda > 0: nu_e == nu0 in every bit
+    assert torch.all(P1.element_viscosity(wd)[0] == 1.0 / 30.0)
+    P1.clear_viscosity_law()
+    v3, F3, R3 = system(P1)
+    assert torch.equal(v0, v3) and torch.equal(F0, F3) and torch.equal(R0, R3)
+    P1.close()
+
+
+# ---- 4. Jacobian against central differences ------------------------------------------------------------------------
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_jacobian_against_central_differences_of_the_residual(corrected):
+    m = M.duct_mesh((30, 24, 24), 4.0)                             # 103 680 tets
+    mask, g = B.duct_bcs(m).flatten()
+    P = FlowProblem(m, (mask, g), reynolds=80.0, corrected_convection=corrected)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    gen = torch.Generator(device="cuda").manual_seed(65)
+    P.set_viscosity_law(3.0, 0.5, 0.0)
+    free = torch.from_numpy(1.0 - P.bc_mask.astype(np.float64)).cuda()
+    eps = 1e-4
+    for k in range(3):
+        dw = torch.randn(P.ndof, dtype=torch.float64, device="cuda", generator=gen) * free * 1e-2
+        fd = (P.residual(U + eps * dw, "ns") - P.residual(U - eps * dw, "ns")) / (2 * eps)
+        for fused in (1, 0):
+            P.set_options(assembly_fused=fused)
+            P.jacobian(U, "ns")
+            e = float((P.spmv(dw) - fd).norm() / fd.norm())
+            print(f"corrected {corrected} direction {k} fused {fused}: |J dw - fd| / |fd| = {e:.3e}")
+            assert e < 1e-6
+    P.close()
+
+
+# ---- 5 - 7. Newton on the fixture's duct -------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def duct_runs():
+    """The jittered (12, 4, 4) duct from the Stokes solution: (mesh, Stokes result, law state + result, Newtonian state + result)."""
+    m, mask, g = G.duct_problem()
+    P = FlowProblem(m, (mask, g), reynolds=D["Re"], **TIGHT)
+    U, sres = P.stokes_solve()
+    wn, rn = P.newton_solve(U.clone())
+    P.set_viscosity_law(*LAW)
+    wl, rl = P.newton_solve(U.clone())
+    nu, gd = P.element_viscosity(wl)
+    P.close()
+    return m, sres, wl.cpu().numpy(), rl, wn.cpu().numpy(), rn, nu.cpu().numpy(), gd.cpu().numpy()
+
+
+def test_newton_on_the_duct_matches_the_lu_oracle(duct_runs):
+    fx = np.load(FIXTURE)
+    m, sres, wl, rl, wn, rn, _, _ = duct_runs
+    assert sres.reason > 0
+    e = (rel(wl.reshape(-1, 4)[:, :3], fx["duct_law"].reshape(-1, 4)[:, :3]), rel(wl.reshape(-1, 4)[:, 3], fx["duct_law"].reshape(-1, 4)[:, 3]))
+    print(f"law-on Newton: {rl.its} its, {rl.ksp_its} ksp its, reason {rl.reason}; rel err u {e[0]:.2e} p {e[1]:.2e}; "
+          f"Newtonian: {rn.its} its, {rn.ksp_its} ksp its")
+    # reason > 0 means every Krylov solve converged: a failed one ends the loop with SNS_SNES_DIVERGED_LINEAR_SOLVE
+    assert rl.reason > 0 and rn.reason > 0, (rl, rn)
+    assert _fields_close(wl, fx["duct_law"]), e
+    assert _fields_close(wn, fx["duct_newton"])
+    assert not _fields_close(wl, wn, 1e-3)                         # (the law's field is another field)
+
+
+def test_element_viscosity_against_the_oracle(duct_runs):
+    m, _, wl, _, _, _, nu, gd = duct_runs
+    nu_o, gd_o = VO.element_viscosity(m.points, m.tets, wl, D["Re"], *LAW)
+    assert np.abs(nu / nu_o - 1.0).max() < 1e-13
+    assert np.abs(gd - gd_o).max() < 1e-13 * gd_o.max()
+    assert nu.max() <= 1.0 / D["Re"] and nu.min() >= D["r"] / D["Re"]
+    # the converged state shears hardest at the wall: the tet of smallest nu_e touches it, and the tets without a wall node
+    # are on average more viscous than those with one
+    wall = np.zeros(m.num_nodes, bool)
+    wall[m.facet_nodes(m.meta["tags"]["wall"])] = True
+    at_wall = wall[m.tets].any(axis=1)
+    assert at_wall[np.argmin(nu)] and 0 < at_wall.sum() < len(at_wall)
+    assert nu[at_wall].mean() < nu[~at_wall].mean()
+
+
+def test_shear_thinning_blunts_the_outlet_profile(duct_runs):
+    fx = np.load(FIXTURE)
+    m, _, wl, _, wn, _, _, _ = duct_runs
+    r_law, r_newt = G.centreline_to_mean(m, wl), G.centreline_to_mean(m, wn)
+    margin = 0.5 * (float(fx["ratio_newton"]) - float(fx["ratio_law"]))      # half of what the CPU oracle's own two runs show
+    print(f"centreline / mean outlet velocity: law {r_law:.6f} (oracle {float(fx['ratio_law']):.6f}), "
+          f"Newtonian {r_newt:.6f} (oracle {float(fx['ratio_newton']):.6f}), margin {margin:.6f}")
+    assert margin > 0.0 and r_law < r_newt - margin
+
+
+# ---- 8. forces ---------------------------------------------------------------------------------------------------------
+def test_residual_moments_with_the_law_against_the_oracle():
+    rng = np.random.default_rng(67)
+    fx = np.load(FIXTURE)
+    m, mask, g = G.duct_problem()
+    P = FlowProblem(m, (mask, g), reynolds=D["Re"])
+    P.set_viscosity_law(*LAW)
+    wh = fx["duct_law"] + 0.05 * rng.normal(size=m.num_dofs)        # (may violate the Dirichlet data: raw residual)
+    base = dict(FL.VARIANT)
+    try:
+        for variant in (False, True):                               # the one-lane-per-tet leg, then the staged leg (rm_nomask)
+            if variant:
+                FL.VARIANT.update(ci=144.0, lsic=4.0)
+                P.set_form_variant(c_inverse=144.0, lsic_scale=4.0)
+            F, _ = VO.raw(m.points, m.tets, wh, D["Re"], *LAW, want_jac=False)
+            for phi in (rng.uniform(-1.0, 1.0, size=m.num_nodes), (m.points[:, 0] < 0.5).astype(np.float64)):
+                out = P.residual_moments(_dev(wh), phi)
+                ref = (phi[:, None] * F.reshape(-1, 4)).sum(axis=0)
+                assert np.abs(out - ref).max() <= 1e-12 * np.linalg.norm(ref), (variant, out, ref)
+    finally:
+        FL.VARIANT.update(base)
+    Fs, _ = VO.raw(m.points, m.tets, wh, D["Re"], 0.0, 1.0, 0.0, want_jac=False)
+    assert np.abs(F - Fs).max() > 1e-6 * np.abs(Fs).max()          # (the law's residual is another residual)
+    P.close()
+
+
+# ---- 9, 10. adjoint ----------------------------------------------------------------------------------------------------
+def test_adjoint_identity_on_a_law_on_jacobian():
+    m = M.duct_mesh((40, 10, 10), 2.0)
+    P = FlowProblem(m, B.duct_bcs(m).flatten(), reynolds=25.0)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    P.set_viscosity_law(*LAW)
+    P.jacobian(U, "ns")
+    A = P.to_scipy()
+    rng = np.random.default_rng(69)
+    free = P.bc_mask == 0
+    for vanish in (True, False):
+        b, gg = rng.normal(size=P.ndof), rng.normal(size=P.ndof)
+        if vanish:
+            b, gg = b * free, gg * free
+        _adjoint_identity(P, A, b, gg, f"law vanish={vanish}")
+    P.close()
+
+
+def test_reynolds_sensitivity_of_the_pressure_drop_with_the_law():
+    """d(dp)/dRe from ONE adjoint solve on the law-on Jacobian against the Richardson value of central differences of full
+    law-on Newton solves: step 1e-2 and band as tests/test_gpu_adjoint.py::test_duct3d_sensitivity_against_independent_solves."""
+    m = M.duct_mesh((24, 8, 8), 2.0, jitter=0.2)
+    P = FlowProblem(m, B.duct_bcs(m).flatten(), reynolds=25.0, **ADJ_TIGHT)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    P.set_viscosity_law(*LAW)
+    w, nres = P.newton_solve(U)
+    assert nres.reason > 0
+    pa, pb = np.array([0.5, 0.03, -0.02]), np.array([1.5, 0.03, -0.02])
+    gp = Fn.pressure_difference_gradient(m, pa, pb)
+    out = _check_sensitivities(P, w, 25.0, ("dp",), lambda wh, nu: np.array([gp @ wh]), lambda nu: np.stack([gp]))
+    P.close()
+    name, adj, tan, tb, Dstar, band = out[0]
+    assert band <= 0.01 * abs(Dstar), (name, band, Dstar)
+    assert abs(adj - Dstar) <= band, (name, adj, Dstar, band)
+
+
+# ---- 11. error paths ---------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_newtonian_handle():
+    fx = np.load(FIXTURE)
+    m, mask, g = G.duct_problem()
+    wd = _dev(fx["duct_newton"])
+
+    def system(P):
+        F = P.zeros()
+        P.jacobian(wd, "ns", residual_out=F)
+        return P.bsr()[2].clone(), F.clone()
+
+    P = FlowProblem(m, (mask, g), reynolds=D["Re"], **TIGHT)
+    v0, F0 = system(P)
+
+    def same_bits():
+        v, F = system(P)
+        return torch.equal(v, v0) and torch.equal(F, F0)
+
+    bad = [(-1.0, 0.5, 0.0), (float("nan"), 0.5, 0.0), (float("inf"), 0.5, 0.0), (1.0, 0.0, 0.0), (1.0, -0.5, 0.0), (1.0, float("nan"), 0.0),
+           (1.0, 0.5, -0.1), (1.0, 0.5, float("nan"))]
+    for lam, n, r in bad:
+        with pytest.raises(SnsError) as e:
+            P.set_viscosity_law(lam, n, r)
+        assert e.value.code == -1 and "sns_set_viscosity_law" in str(e.value), (lam, n, r)
+        assert same_bits(), (lam, n, r)
+    for law in (2, -1):                                             # an unknown law
+        assert P.lib.sns_set_viscosity_law(P.h, law, 1.0, 0.5, 0.0) == -1 and b"unknown law" in P.lib.sns_last_error()
+    assert same_bits()
+    # law and time term exclude each other, in either order
+    P.set_time_term(0.0, 7.0, None)
+    with pytest.raises(SnsError) as e:
+        P.set_viscosity_law(*LAW)
+    assert e.value.code == -3
+    P.clear_time_term()
+    assert same_bits()
+    P.set_viscosity_law(*LAW)
+    with pytest.raises(SnsError) as e:
+        P.set_time_term(1.0, 0.0, P.zeros())
+    assert e.value.code == -3
+    with pytest.raises(SnsError) as e:
+        P.time_step(wd.clone(), None, 0.1, order=1)
+    assert e.value.code == -3
+    P.clear_time_term()                                             # (clearing a term that is not set stays allowed)
+    with pytest.raises(SnsError) as e:
+        P.residual_shape_gradient(wd, wd)
+    assert e.value.code == -3 and "viscosity law" in str(e.value)
+    assert not same_bits()                                          # (the law is still on ...)
+    P.clear_viscosity_law()
+    assert same_bits()                                              # (... and gone)
+    w, res = P.newton_solve(_dev(fx["duct_stokes"]))
+    assert res.reason > 0 and _fields_close(w.cpu().numpy(), fx["duct_newton"])
+    P.close()
+    # 2-D handles
+    m2 = M2.dfg_2d_mesh(0.5)
+    P2 = FlowProblem(m2, M2.dfg2d_bcs(m2).flatten(), reynolds=100.0)
+    with pytest.raises(SnsError) as e:
+        P2.set_viscosity_law(*LAW)
+    assert e.value.code == -1
+    with pytest.raises(SnsError) as e:
+        P2.element_viscosity(P2.zeros())
+    assert e.value.code == -1
+    P2.close()
+    # a handle with an owned / ghost split attached (no transport needed): SNS_E_STATE, as for the time term
+    from stabilized_navier_stokes_flow_fenicsx_amd import partition as PT
+    part = PT.build_local_part(m, mask, g, PT.rcb_partition(m.points, 2), 0, 2)
+    R = FlowProblem(part.mesh, (part.bc_mask, part.bc_val), part=part, group="local-only", reynolds=D["Re"])
+    with pytest.raises(SnsError) as e:
+        R.set_viscosity_law(*LAW)
+    assert e.value.code == -3
+    R.close()
+
+
+def test_stokes_form_ignores_the_law():
+    m, mask, g = G.duct_problem()
+    P = FlowProblem(m, (mask, g), reynolds=D["Re"])
+    F0 = P.zeros()
+    P.jacobian(None, "stokes", residual_out=F0)
+    v0 = P.bsr()[2].clone()
+    P.set_viscosity_law(*LAW)
+    F1 = P.zeros()
+    P.jacobian(None, "stokes", residual_out=F1)
+    assert torch.equal(v0, P.bsr()[2]) and torch.equal(F0, F1)
+    for fused in (1, 0):                                            # ... also its residual at a state, on both paths
+        P.set_options(assembly_fused=fused)
+        R1 = P.residual(F0, "stokes")
+        P.clear_viscosity_law()
+        assert torch.equal(R1, P.residual(F0, "stokes"))
+        P.set_viscosity_law(*LAW)
+    P.close()
+
+
+# ---- 12. continuation ----------------------------------------------------------------------------------------------------
+def test_law_continuation_reaches_the_low_index():
+    fx = np.load(FIXTURE)
+    m, mask, g = G.duct_problem()
+    P = FlowProblem(m, (mask, g), reynolds=D["Re"], **TIGHT)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    P.set_viscosity_law(D["lam"], D["n_low"], D["r"])
+    w, r = S.newton_with_law_continuation(P, U.clone(), steps=4)
+    print(f"continuation to n = {D['n_low']}: reason {r.reason}, last stage {r.its} its, {r.ksp_its} ksp its in all")
+    assert r.reason > 0, r
+    assert P.viscosity_law == (D["lam"], D["n_low"], D["r"])
+    assert _fields_close(w.cpu().numpy(), fx["duct_low"])
+    P.close()
