@@ -245,6 +245,12 @@ SNS_API const char* sns_version(void);
 #define SNS_ABI_VERSION 8
 SNS_API int sns_abi_version(void);
 SNS_API int64_t sns_options_size(void);
+/* Bytes of device memory the library holds right now in this process: every allocation behind the handles, their halo plans
+ * and the scratch of the calls in flight, over all devices and threads.  Read-only; it is back at its earlier value once
+ * everything created since has been destroyed (device-wide free memory is shared with other processes and says nothing
+ * about that).  Not counted: the peer / team transport's windows (sns_peer_create, sns_attach_team), which are shared through
+ * IPC and live until sns_peer_destroy / sns_team_destroy. */
+SNS_API int64_t sns_live_device_bytes(void);
 
 /* ---- setup: replaces gmshio.model_to_mesh + functionspace + create_matrix +
  *      locate_dofs_topological/dirichletbc (:111,:127-147,:271-272) ----------

@@ -79,6 +79,7 @@ _SIGNATURES = [
     ("sns_version", C.c_char_p, []),
     ("sns_abi_version", C.c_int, []),
     ("sns_options_size", C.c_int64, []),
+    ("sns_live_device_bytes", C.c_int64, []),
     ("sns_create", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_int, C.POINTER(SnsOptions)]),
     ("sns_create_2d", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_int, C.POINTER(SnsOptions)]),
     ("sns_destroy", C.c_int, [_H]),

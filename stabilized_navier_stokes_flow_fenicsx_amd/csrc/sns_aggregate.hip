@@ -496,20 +496,6 @@ __global__ __launch_bounds__(AGG_TPB) void k_hyb_merge(int32_t n, int32_t n_act,
     agg[i] = a;
 }
 
-// device scratch, freed on every way out
-struct AggScratch {
-    std::vector<void*> ptrs;
-    template <class T>
-    int alloc(T** p, size_t count) {
-        SNS_TRY(dev_alloc(p, count));
-        ptrs.push_back((void*)*p);
-        return SNS_OK;
-    }
-    ~AggScratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-};
-
 struct Scanner {
     sns_ctx* h;
     int64_t* bsum;
@@ -550,7 +536,7 @@ int strong_slots(sns_ctx* h, const GraphView& G, const float* s, float* smax, fl
 }
 
 // agg_dev[G.n] <- the map of aggregate_strength over G's first n_act nodes (-1 beyond), nc = aggregates; sw = strong_slots' weights
-int match_strong(sns_ctx* h, const GraphView& G, const float* sw, int max_agg, const std::string& who, AggScratch& S, int32_t* agg_dev,
+int match_strong(sns_ctx* h, const GraphView& G, const float* sw, int max_agg, const std::string& who, int32_t* agg_dev,
                  int32_t& nc) {
     const int32_t n = G.n, n_act = G.n_act;
     nc = 0;
@@ -559,34 +545,35 @@ int match_strong(sns_ctx* h, const GraphView& G, const float* sw, int max_agg, c
         return SNS_OK;
     }
     const size_t na = (size_t)n_act;
-    int32_t *of, *mem, *nmem, *size, *nsize, *partner, *best, *flag, *newid, *cnt, *ecnt, *nbr, *ctr, *fill, *target, *choose, *list, *next, *dirty, *matched;
-    int64_t *moff, *nmoff, *eoff, *scan, *bsum;
-    double *wgt, *bestw;
-    SNS_TRY(S.alloc(&of, na));
-    SNS_TRY(S.alloc(&mem, na));
-    SNS_TRY(S.alloc(&nmem, na));
-    SNS_TRY(S.alloc(&size, na));
-    SNS_TRY(S.alloc(&nsize, na));
-    SNS_TRY(S.alloc(&partner, na));
-    SNS_TRY(S.alloc(&best, na));
-    SNS_TRY(S.alloc(&flag, na));
-    SNS_TRY(S.alloc(&newid, na));
-    SNS_TRY(S.alloc(&cnt, na));
-    SNS_TRY(S.alloc(&ecnt, na));
-    SNS_TRY(S.alloc(&fill, na));
-    SNS_TRY(S.alloc(&target, na));
-    SNS_TRY(S.alloc(&choose, na));
-    SNS_TRY(S.alloc(&bestw, na));
-    SNS_TRY(S.alloc(&list, na));
-    SNS_TRY(S.alloc(&next, na));
-    SNS_TRY(S.alloc(&dirty, na));
-    SNS_TRY(S.alloc(&matched, na));
-    SNS_TRY(S.alloc(&ctr, 3));
-    SNS_TRY(S.alloc(&moff, na + 1));
-    SNS_TRY(S.alloc(&nmoff, na + 1));
-    SNS_TRY(S.alloc(&eoff, na + 1));
-    SNS_TRY(S.alloc(&scan, na + 1));
-    SNS_TRY(S.alloc(&bsum, na / SCAN_BLOCK + 1));
+    // (device scratch, freed on every way out)
+    DevBuf<int32_t> of, mem, nmem, size, nsize, partner, best, flag, newid, cnt, ecnt, nbr, ctr, fill, target, choose, list, next, dirty, matched;
+    DevBuf<int64_t> moff, nmoff, eoff, scan, bsum;
+    DevBuf<double> wgt, bestw;
+    SNS_TRY(of.alloc(na));
+    SNS_TRY(mem.alloc(na));
+    SNS_TRY(nmem.alloc(na));
+    SNS_TRY(size.alloc(na));
+    SNS_TRY(nsize.alloc(na));
+    SNS_TRY(partner.alloc(na));
+    SNS_TRY(best.alloc(na));
+    SNS_TRY(flag.alloc(na));
+    SNS_TRY(newid.alloc(na));
+    SNS_TRY(cnt.alloc(na));
+    SNS_TRY(ecnt.alloc(na));
+    SNS_TRY(fill.alloc(na));
+    SNS_TRY(target.alloc(na));
+    SNS_TRY(choose.alloc(na));
+    SNS_TRY(bestw.alloc(na));
+    SNS_TRY(list.alloc(na));
+    SNS_TRY(next.alloc(na));
+    SNS_TRY(dirty.alloc(na));
+    SNS_TRY(matched.alloc(na));
+    SNS_TRY(ctr.alloc(3));
+    SNS_TRY(moff.alloc(na + 1));
+    SNS_TRY(nmoff.alloc(na + 1));
+    SNS_TRY(eoff.alloc(na + 1));
+    SNS_TRY(scan.alloc(na + 1));
+    SNS_TRY(bsum.alloc(na / SCAN_BLOCK + 1));
     Scanner scanner{h, bsum};
     const hipStream_t st = h->stream;
     // every node its own cluster: of = mem = identity, size 1, moff = 0, 1, 2, ...
@@ -599,8 +586,8 @@ int match_strong(sns_ctx* h, const GraphView& G, const float* sw, int max_agg, c
         SNS_TRY(scanner.run(cnt, n_act, eoff));
         SNS_TRY(read_back(h, eoff + n_act, &cap, 1));
     }
-    SNS_TRY(S.alloc(&nbr, (size_t)std::max<int64_t>(cap, 1)));
-    SNS_TRY(S.alloc(&wgt, (size_t)std::max<int64_t>(cap, 1)));
+    SNS_TRY(nbr.alloc((size_t)std::max<int64_t>(cap, 1)));
+    SNS_TRY(wgt.alloc((size_t)std::max<int64_t>(cap, 1)));
     int32_t ncl = n_act;
     // contraction of the strong graph to the current clusters: (nbr, wgt)[eoff[c] .. + ecnt[c]) per cluster
     auto contract = [&]() -> int {
@@ -631,7 +618,7 @@ int match_strong(sns_ctx* h, const GraphView& G, const float* sw, int max_agg, c
             hipLaunchKernelGGL(k_agg_dirty, dim3(agg_blocks(nmax)), dim3(AGG_TPB), 0, st, nmax, matched, eoff, ecnt, nbr, best, partner, next, ctr);
             HIP_TRY(hipGetLastError());
             int32_t c3[3] = {0, 0, 0};
-            SNS_TRY(read_back(h, ctr, c3, 3));
+            SNS_TRY(read_back(h, ctr.get(), c3, 3));
             if (c3[0] == 0) break;                              // no eligible edge left anywhere
             if (c3[1] == 0) {
                 set_error(who + ": a matching step matched nothing with " + std::to_string(c3[0]) + " clusters pending");
@@ -670,7 +657,7 @@ int match_strong(sns_ctx* h, const GraphView& G, const float* sw, int max_agg, c
         hipLaunchKernelGGL(k_agg_lcommit, dim3(agg_blocks(ncl)), dim3(AGG_TPB), 0, st, ncl, choose, target, fill);
         HIP_TRY(hipGetLastError());
         int32_t c2[2] = {0, 0};
-        SNS_TRY(read_back(h, ctr, c2, 2));
+        SNS_TRY(read_back(h, ctr.get(), c2, 2));
         if (c2[0] == 0) break;
         if (c2[1] == 0) {
             set_error(who + ": a leftover step accepted nothing with " + std::to_string(c2[0]) + " singles pending");
@@ -699,34 +686,28 @@ int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg
     const GraphView G{L.rowptr, L.colind, n, n_act};
     agg.assign((size_t)n, -1);
     nc = 0;
-    AggScratch S;
-    float* sw = nullptr;                                            // strong-slot weights, one per block slot (0: not strong)
+    DevBuf<float> sw;                                               // strong-slot weights, one per block slot (0: not strong)
     {
         // the strength (collective) and the strong graph; the strength is freed again before the matching
-        float *s = nullptr, *smax = nullptr;
-        double* scale = nullptr;
-        int rc = dev_alloc(&s, (size_t)L.nnzb);
-        if (rc == SNS_OK) rc = dev_alloc(&scale, 4 * (size_t)n);
-        if (rc == SNS_OK) rc = compute_strength(h, s, scale);
-        if (rc == SNS_OK && n_act > 0) rc = dev_alloc(&smax, (size_t)n_act);
-        if (rc == SNS_OK && n_act > 0) rc = S.alloc(&sw, (size_t)L.nnzb);
-        bool failed = false;
-        if (rc == SNS_OK && n_act > 0) failed = strong_slots(h, G, s, smax, sw) != SNS_OK;
-        if (rc == SNS_OK && !failed) failed = hipStreamSynchronize(h->stream) != hipSuccess;
-        if (failed) {
-            set_error("amg_aggregation = 2: strength or strong-graph kernel failed");
-            rc = SNS_E_HIP;
+        DevBuf<float> s, smax;
+        DevBuf<double> scale;
+        SNS_TRY(s.alloc((size_t)L.nnzb));
+        SNS_TRY(scale.alloc(4 * (size_t)n));
+        SNS_TRY(compute_strength(h, s, scale));
+        if (n_act > 0) {
+            SNS_TRY(smax.alloc((size_t)n_act));
+            SNS_TRY(sw.alloc((size_t)L.nnzb));
         }
-        if (s) (void)hipFree(s);
-        if (scale) (void)hipFree(scale);
-        if (smax) (void)hipFree(smax);
-        if (rc != SNS_OK) return rc;
+        if ((n_act > 0 && strong_slots(h, G, s, smax, sw) != SNS_OK) || hipStreamSynchronize(h->stream) != hipSuccess) {
+            set_error("amg_aggregation = 2: strength or strong-graph kernel failed");
+            return SNS_E_HIP;
+        }
         if (n_act == 0) return SNS_OK;
     }
-    int32_t* agg_dev = nullptr;
-    SNS_TRY(S.alloc(&agg_dev, (size_t)n));
-    SNS_TRY(match_strong(h, G, sw, max_agg, "amg_aggregation = 2", S, agg_dev, nc));
-    SNS_TRY(read_back(h, agg_dev, agg.data(), (size_t)n));
+    DevBuf<int32_t> agg_dev;
+    SNS_TRY(agg_dev.alloc((size_t)n));
+    SNS_TRY(match_strong(h, G, sw, max_agg, "amg_aggregation = 2", agg_dev, nc));
+    SNS_TRY(read_back(h, agg_dev.get(), agg.data(), (size_t)n));
     return SNS_OK;
 }
 
@@ -745,37 +726,28 @@ int aggregate_hybrid_device(sns_ctx* h, int max_agg, const std::vector<int32_t>&
     rematched = false;
     for (int32_t i = 0; i < n_act; ++i)
         if (g[(size_t)i] < 0 || g[(size_t)i] >= ng) { set_error(who + ": the geometric map is not total over the owned nodes"); return SNS_E_STATE; }
-    AggScratch S;
     // the fp32 strength: freed as soon as the subgraph holds the slots it needs (before the matching, as amg_aggregation = 2 does)
-    float* s = nullptr;
-    struct FreeStrength {
-        float** p;
-        ~FreeStrength() {
-            if (*p) (void)hipFree(*p);
-        }
-    } free_s{&s};
+    DevBuf<float> s;
     {
-        double* scale = nullptr;
-        int rc = dev_alloc(&s, (size_t)std::max<int64_t>(1, L.nnzb));
-        if (rc == SNS_OK) rc = dev_alloc(&scale, 4 * (size_t)n);
-        if (rc == SNS_OK) rc = compute_strength(h, s, scale);
-        if (scale) (void)hipFree(scale);
-        if (rc != SNS_OK) return rc;
+        DevBuf<double> scale;
+        SNS_TRY(s.alloc((size_t)L.nnzb));
+        SNS_TRY(scale.alloc(4 * (size_t)n));
+        SNS_TRY(compute_strength(h, s, scale));
     }
     if (n_act == 0) return SNS_OK;
     const hipStream_t st = h->stream;
     const size_t na = (size_t)n_act, nga = (size_t)std::max(1, ng);
-    int32_t *d_g, *gsize, *dis, *inF, *keep, *nmark;
-    int64_t *fpos, *kpos, *bsum;
-    SNS_TRY(S.alloc(&d_g, na));
-    SNS_TRY(S.alloc(&gsize, nga));
-    SNS_TRY(S.alloc(&dis, nga));
-    SNS_TRY(S.alloc(&inF, na));
-    SNS_TRY(S.alloc(&keep, nga));
-    SNS_TRY(S.alloc(&nmark, 1));
-    SNS_TRY(S.alloc(&fpos, na + 1));
-    SNS_TRY(S.alloc(&kpos, nga + 1));
-    SNS_TRY(S.alloc(&bsum, std::max(na, nga) / SCAN_BLOCK + 1));
+    DevBuf<int32_t> d_g, gsize, dis, inF, keep, nmark;
+    DevBuf<int64_t> fpos, kpos, bsum;
+    SNS_TRY(d_g.alloc(na));
+    SNS_TRY(gsize.alloc(nga));
+    SNS_TRY(dis.alloc(nga));
+    SNS_TRY(inF.alloc(na));
+    SNS_TRY(keep.alloc(nga));
+    SNS_TRY(nmark.alloc(1));
+    SNS_TRY(fpos.alloc(na + 1));
+    SNS_TRY(kpos.alloc(nga + 1));
+    SNS_TRY(bsum.alloc(std::max(na, nga) / SCAN_BLOCK + 1));
     Scanner scanner{h, bsum};
     HIP_TRY(hipMemcpyAsync(d_g, g.data(), na * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(gsize, 0, nga * sizeof(int32_t), st));
@@ -786,7 +758,7 @@ int aggregate_hybrid_device(sns_ctx* h, int max_agg, const std::vector<int32_t>&
                        policy::HYBRID_KAPPA, dis, nmark);
     HIP_TRY(hipGetLastError());
     int32_t marked = 0;
-    SNS_TRY(read_back(h, nmark, &marked, 1));
+    SNS_TRY(read_back(h, nmark.get(), &marked, 1));
     if (marked == 0) return SNS_OK;                                 // nothing dissolved: the geometric map
     // more than HYBRID_PHI of the rows marked: everything dissolved (the map of amg_aggregation = 2)
     const int32_t all = (double)marked > policy::HYBRID_PHI * (double)n_act ? 1 : 0;
@@ -798,13 +770,13 @@ int aggregate_hybrid_device(sns_ctx* h, int max_agg, const std::vector<int32_t>&
     if (nF == 0) { set_error(who + ": marked rows without a dissolved aggregate"); return SNS_E_HIP; }
     const int32_t nf = (int32_t)nF;
     SNS_TRY(scanner.run(keep, ng, kpos));
-    int32_t *fnode, *cnt, *srowptr, *scolind, *sagg, *agg_dev;
-    int64_t* soff;
-    float *ss, *smax, *sw;
-    SNS_TRY(S.alloc(&fnode, (size_t)nf));
-    SNS_TRY(S.alloc(&cnt, (size_t)nf));
-    SNS_TRY(S.alloc(&soff, (size_t)nf + 1));
-    SNS_TRY(S.alloc(&srowptr, (size_t)nf + 1));
+    DevBuf<int32_t> fnode, cnt, srowptr, scolind, sagg, agg_dev;
+    DevBuf<int64_t> soff;
+    DevBuf<float> ss, smax, sw;
+    SNS_TRY(fnode.alloc((size_t)nf));
+    SNS_TRY(cnt.alloc((size_t)nf));
+    SNS_TRY(soff.alloc((size_t)nf + 1));
+    SNS_TRY(srowptr.alloc((size_t)nf + 1));
     hipLaunchKernelGGL(k_hyb_count, dim3(agg_blocks(n_act)), dim3(AGG_TPB), 0, st, n_act, L.rowptr, L.colind, inF, fpos, fnode, cnt);
     HIP_TRY(hipGetLastError());
     SNS_TRY(scanner.run(cnt, nf, soff));
@@ -812,28 +784,27 @@ int aggregate_hybrid_device(sns_ctx* h, int max_agg, const std::vector<int32_t>&
     SNS_TRY(read_back(h, soff + nf, &nnz, 1));
     if (nnz > (int64_t)L.nnzb) { set_error(who + ": the induced subgraph exceeds the pattern"); return SNS_E_HIP; }
     const size_t nz = (size_t)std::max<int64_t>(nnz, 1);
-    SNS_TRY(S.alloc(&scolind, nz));
-    SNS_TRY(S.alloc(&ss, nz));
+    SNS_TRY(scolind.alloc(nz));
+    SNS_TRY(ss.alloc(nz));
     hipLaunchKernelGGL(k_hyb_fill, dim3(agg_blocks(nf)), dim3(AGG_TPB), 0, st, nf, fnode, n_act, L.rowptr, L.colind, s, inF, fpos, soff,
                        srowptr, scolind, ss);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipFree(s));
-    s = nullptr;
-    SNS_TRY(S.alloc(&sw, nz));
-    SNS_TRY(S.alloc(&smax, (size_t)nf));
-    SNS_TRY(S.alloc(&sagg, (size_t)nf));
-    SNS_TRY(S.alloc(&agg_dev, (size_t)std::max(1, n)));
+    s.reset();
+    SNS_TRY(sw.alloc(nz));
+    SNS_TRY(smax.alloc((size_t)nf));
+    SNS_TRY(sagg.alloc((size_t)nf));
+    SNS_TRY(agg_dev.alloc((size_t)std::max(1, n)));
     // the matching of amg_aggregation = 2, unchanged, on the subgraph
     const GraphView G{srowptr, scolind, nf, nf};
     SNS_TRY(strong_slots(h, G, ss, smax, sw));
     int32_t snc = 0;
-    SNS_TRY(match_strong(h, G, sw, max_agg, who, S, sagg, snc));
+    SNS_TRY(match_strong(h, G, sw, max_agg, who, sagg, snc));
     hipLaunchKernelGGL(k_hyb_merge, dim3(agg_blocks(n)), dim3(AGG_TPB), 0, st, n, n_act, ng, d_g, inF, fpos, kpos, sagg, agg_dev);
     HIP_TRY(hipGetLastError());
     int64_t nkept = 0;
     SNS_TRY(read_back(h, kpos + ng, &nkept, 1));
-    SNS_TRY(read_back(h, agg_dev, agg.data(), (size_t)n));
+    SNS_TRY(read_back(h, agg_dev.get(), agg.data(), (size_t)n));
     nc = (int32_t)nkept + snc;
     rematched = true;
     return SNS_OK;

@@ -1,12 +1,32 @@
 // C-ABI layer (include/sns.h): handle life cycle, communicator attachment, the entry points of the hot path (residual /
 // Jacobian / SpMV / preconditioner / Krylov / Stokes / Newton) and the introspection getters.  Host code only launches kernels
-// and moves scalars; there is no CPU compute path.  (Round 5: the setup, cycle and Krylov parts live in csrc/sns_setup.hip,
-// sns_cycle.hip and sns_krylov.hip; shared internals in csrc/sns_ctx.h; the hierarchy's policy in csrc/sns_policy.h.)
+// and moves scalars; there is no CPU compute path.  (The setup, cycle and Krylov parts live in csrc/sns_setup.hip, sns_cycle.hip
+// and sns_krylov.hip; shared internals in csrc/sns_ctx.h; the hierarchy's policy in csrc/sns_policy.h.)  The handle owns its
+// device memory and HIP objects by type (csrc/sns_devbuf.h): sns_destroy is `delete h`, and a failing create frees what it made.
+#include <atomic>
+
 #include "sns_ctx.h"
 
 namespace sns {
 static thread_local std::string g_err;
 void set_error(const std::string& s) { g_err = s; }
+
+// the allocator behind every DevBuf, and the bytes it has handed out and not got back (sns_live_device_bytes)
+static std::atomic<int64_t> g_live_bytes{0};
+int dev_malloc_bytes(void** p, size_t bytes) {
+    *p = nullptr;
+    HIP_TRY(hipMalloc(p, bytes));
+    g_live_bytes += (int64_t)bytes;
+    return SNS_OK;
+}
+void dev_free_bytes(void* p, size_t bytes) {
+    (void)hipFree(p);
+    g_live_bytes -= (int64_t)bytes;
+}
+int dev_upload_bytes(void* dst, const void* src, size_t bytes) {
+    HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return SNS_OK;
+}
 
 }  // namespace sns
 
@@ -72,6 +92,8 @@ const char* sns_last_error(void) { return g_err.c_str(); }
 const char* sns_version(void) { return "sns 0.1 (gfx950)"; }
 
 int sns_abi_version(void) { return SNS_ABI_VERSION; }
+
+int64_t sns_live_device_bytes(void) { return g_live_bytes.load(); }
 
 int64_t sns_options_size(void) { return (int64_t)sizeof(sns_options); }
 
@@ -151,23 +173,23 @@ static int create_common(int dim, sns_handle* out, int32_t n_nodes, int64_t n_te
         set_error(e.what());
         return SNS_E_MESH;
     }
-    SNS_TRY(dev_alloc(&h->tets, (size_t)4 * n_tets));
+    SNS_TRY(h->tets.alloc((size_t)4 * n_tets));
     HIP_TRY(hipMemcpy(h->tets, tets, (size_t)4 * n_tets * sizeof(int32_t), hipMemcpyHostToDevice));
-    SNS_TRY(dev_alloc(&h->pts, (size_t)3 * n_nodes));
+    SNS_TRY(h->pts.alloc((size_t)3 * n_nodes));
     HIP_TRY(hipMemcpy(h->pts, points, (size_t)3 * n_nodes * sizeof(double), hipMemcpyHostToDevice));
-    SNS_TRY(dev_alloc(&h->bc_mask, (size_t)4 * n_nodes));
+    SNS_TRY(h->bc_mask.alloc((size_t)4 * n_nodes));
     HIP_TRY(hipMemcpy(h->bc_mask, bc_mask, (size_t)4 * n_nodes, hipMemcpyHostToDevice));
-    SNS_TRY(dev_alloc(&h->bc_val, (size_t)4 * n_nodes));
+    SNS_TRY(h->bc_val.alloc((size_t)4 * n_nodes));
     HIP_TRY(hipMemcpy(h->bc_val, bc_val, (size_t)4 * n_nodes * sizeof(double), hipMemcpyHostToDevice));
     {
         std::vector<double> ge((size_t)4 * n_nodes);
         for (size_t i = 0; i < ge.size(); ++i) ge[i] = bc_mask[i] ? bc_val[i] : 0.0;
-        SNS_TRY(dev_upload(&h->gext, ge, nullptr));
+        SNS_TRY(h->gext.upload(ge));
     }
-    SNS_TRY(dev_upload(&h->nt_ptr, M.nt_ptr, nullptr));
-    SNS_TRY(dev_upload(&h->nt_idx, M.nt_idx, nullptr));
-    SNS_TRY(dev_upload(&h->c_ptr, M.c_ptr, nullptr));
-    SNS_TRY(dev_upload(&h->c_idx, M.c_idx, nullptr));
+    SNS_TRY(h->nt_ptr.upload(M.nt_ptr));
+    SNS_TRY(h->nt_idx.upload(M.nt_idx));
+    SNS_TRY(h->c_ptr.upload(M.c_ptr));
+    SNS_TRY(h->c_idx.upload(M.c_idx));
     {
         // lane -> slot map of the scratch-free assembly: off-diagonal slots only, and inside every window of
         // 8192 consecutive slots ordered by descending contribution count, so that the lanes of a wave loop
@@ -192,31 +214,31 @@ static int create_common(int dim, sns_handle* out, int32_t n_nodes, int64_t n_te
             for (size_t c = bucket.size(); c-- > 0;) order.insert(order.end(), bucket[c].begin(), bucket[c].end());
         }
         h->n_od = (int64_t)order.size();
-        SNS_TRY(dev_upload(&h->od_order, order, nullptr));
+        SNS_TRY(h->od_order.upload(order));
     }
     h->levels.emplace_back();
-    h->slot_row.push_back(nullptr);
-    h->empty_c.push_back(nullptr);
-    h->pong.push_back(nullptr);
-    SNS_TRY(upload_pattern(h->levels[0], P, &h->slot_row[0], nullptr));
+    h->slot_row.emplace_back();
+    h->empty_c.emplace_back();
+    h->pong.emplace_back();
+    SNS_TRY(upload_pattern(h->levels[0], P, h->slot_row[0], nullptr));
     h->levels[0].n_owned = n_nodes;
     SNS_TRY(alloc_level_vectors(h->levels[0]));
-    SNS_TRY(dev_alloc(&h->pong[0], 4 * (size_t)n_nodes));
+    SNS_TRY(h->pong[0].alloc(4 * (size_t)n_nodes));
     HIP_TRY(hipMemset(h->pong[0], 0, 4 * (size_t)n_nodes * sizeof(double)));
     {   // free mask of level 0 = !bc
         std::vector<uint8_t> fm((size_t)4 * n_nodes);
         for (size_t i = 0; i < fm.size(); ++i) fm[i] = bc_mask[i] ? 0 : 1;
-        SNS_TRY(dev_upload(&h->levels[0].free_mask, fm, nullptr));
+        SNS_TRY(h->levels[0].free_mask.upload(fm));
     }
     // per-block partial sums: vector kernels use <= 2048 blocks x <= 8 sums, the fused SpMV+dot one block per 32 rows
-    SNS_TRY(dev_alloc(&h->partial, std::max<size_t>((size_t)65536 * 8, (size_t)n_nodes / 4 + 512)));
-    SNS_TRY(dev_alloc(&h->partial2, (size_t)4096 * 8));
-    SNS_TRY(dev_alloc(&h->d_scal, 256));
-    SNS_TRY(dev_alloc(&h->d_sing, 1));
+    SNS_TRY(h->partial.alloc(std::max<size_t>((size_t)65536 * 8, (size_t)n_nodes / 4 + 512)));
+    SNS_TRY(h->partial2.alloc((size_t)4096 * 8));
+    SNS_TRY(h->d_scal.alloc(256));
+    SNS_TRY(h->d_sing.alloc(1));
     HIP_TRY(hipMemset(h->d_sing, 0, sizeof(int)));
-    HIP_TRY(hipHostMalloc((void**)&h->h_scal, 1024 * sizeof(double), hipHostMallocDefault));
-    HIP_TRY(hipEventCreate(&h->ev0));
-    HIP_TRY(hipEventCreate(&h->ev1));
+    HIP_TRY(hipHostMalloc((void**)h->h_scal.put(), 1024 * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipEventCreate(h->ev0.put()));
+    HIP_TRY(hipEventCreate(h->ev1.put()));
     // the hierarchy is built lazily (first pc_setup) so that sns_attach_comm can shrink n_owned first
     HIP_TRY(hipDeviceSynchronize());
     h->tm = sns_timings{};
@@ -270,44 +292,7 @@ extern "C" {
 
 int sns_destroy(sns_handle h) {
     if (!h) return SNS_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    auto fr = [](void* p) { if (p) (void)hipFree(p); };
-    fr(h->tets); fr(h->pts); fr(h->bc_mask); fr(h->bc_val);
-    fr(h->nt_ptr); fr(h->nt_idx); fr(h->c_ptr); fr(h->c_idx); fr(h->od_order); fr(h->gext); fr(h->Ke); fr(h->Fe);
-    fr(h->rm_off); fr(h->rm_cells); fr(h->rm_Fe); fr(h->rm_nomask); fr(h->tr_partner); fr(h->tt_d); fr(h->tt_w0);
-    for (auto& L : h->levels) {
-        fr(L.rowptr); fr(L.colind); fr(L.diag); fr(L.vals); fr(L.dinv); fr(L.agg); fr(L.m_ptr); fr(L.m_idx);
-        fr(L.r_ptr); fr(L.r_idx); fr(L.free_mask); fr(L.x); fr(L.b); fr(L.r); fr(L.dense_inv); fr(L.dense_gj); fr(L.dense_work); fr(L.dense_x32); fr(L.vals32); fr(L.vals16); fr(L.scale16); fr(L.dinv32);
-        fr(L.ap_rowptr); fr(L.ap_colind); fr(L.ap_colind_rep); fr(L.ap_ptr); fr(L.ap_idx); fr(L.ap_nib); fr(L.ap_vals32); fr(L.ap_vals16); fr(L.ap_scale16); fr(L.blk_rows); fr(L.blk_of); fr(L.binv32);
-    }
-    for (auto p : h->slot_row) fr(p);
-    for (auto p : h->empty_c) fr(p);
-    for (auto p : h->pong) fr(p);
-    for (auto p : h->kv) fr(p);
-    for (auto& e : h->ev_pool) { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); }
-    fr(h->d_piv); fr(h->d_sing); fr(h->rep_valmap); fr(h->rep_rowmap); fr(h->rep_vsend); fr(h->rep_vrecv); fr(h->rep_bsend); fr(h->rep_brecv); fr(h->rep_doff); fr(h->rep_dcnt);
-    fr(h->arn_V);
-    fr(h->partial); fr(h->partial2); fr(h->d_scal); fr(h->gm_V); fr(h->gm_Z); fr(h->d_h);
-    fr(h->nw_F); fr(h->nw_y); fr(h->nw_w); fr(h->nw_t);
-    if (h->coarse_graph) (void)hipGraphExecDestroy(h->coarse_graph);
-    if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
-    if (h->gj_stream) (void)hipStreamDestroy(h->gj_stream);
-    if (h->h_scal) (void)hipHostFree(h->h_scal);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev_it) (void)hipEventDestroy(h->ev_it);
-    fr(h->bnd_rows); fr(h->bnd_flag);
-    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
-    if (h->ev_x) (void)hipEventDestroy(h->ev_x);
-    if (h->ev_side) (void)hipEventDestroy(h->ev_side);
-    fr(h->cg_colmap); fr(h->cg_rows); fr(h->cg_full); fr(h->cg_send); fr(h->cg_recv);
-    for (auto& L : h->levels) fr(L.xg);
-    if (h->comm) {
-        for (auto& p : h->comm->plans) plan_free(p);
-        if (h->comm->nccl) (void)ncclCommDestroy(h->comm->nccl);
-    }
-    delete h;
+    delete h;                                             // (~sns_ctx, csrc/sns_ctx.h)
     return SNS_OK;
 }
 
@@ -447,8 +432,8 @@ static int attach_common(sns_handle h, int rank, int nranks, const char* uid, Te
         for (int32_t q = 0; q < nb; ++q) flag[rows[q]] = 1;
         h->n_bnd = nb;
         rows.resize((size_t)std::max(1, nb));
-        SNS_TRY(dev_upload(&h->bnd_rows, rows, nullptr));
-        SNS_TRY(dev_upload(&h->bnd_flag, flag, nullptr));
+        SNS_TRY(h->bnd_rows.upload(rows));
+        SNS_TRY(h->bnd_flag.upload(flag));
         h->no_overlap = std::getenv("SNS_NO_OVERLAP") != nullptr;
         h->team_overlap = std::getenv("SNS_TEAM_OVERLAP") != nullptr;
     }
@@ -547,18 +532,16 @@ int sns_residual_moments(sns_handle h, int form, const double* w, const double* 
     }
     // support of the functional behind the owned rows: count, scan, fetch the size, scatter
     const int64_t nb = (h->E + 255) / 256;
-    if (!h->rm_off) SNS_TRY(dev_alloc(&h->rm_off, (size_t)nb));
+    if (!h->rm_off) SNS_TRY(h->rm_off.alloc((size_t)nb));
     hipLaunchKernelGGL(k_support_count, dim3((unsigned)nb), dim3(256), 0, h->stream, h->E, h->tets, h->n_owned, phi, h->rm_off);
     hipLaunchKernelGGL(k_support_scan, dim3(1), dim3(256), 0, h->stream, nb, h->rm_off, h->d_scal + 100);
     double total = 0.0;
     SNS_TRY(fetch(h, h->d_scal + 100, 1, &total));
     const int64_t nc = (int64_t)total;
     if (nc > h->rm_cap) {
-        if (h->rm_cells) { HIP_TRY(hipFree(h->rm_cells)); h->rm_cells = nullptr; }
-        if (h->rm_Fe) { HIP_TRY(hipFree(h->rm_Fe)); h->rm_Fe = nullptr; }
         h->rm_cap = 0;
-        SNS_TRY(dev_alloc(&h->rm_cells, (size_t)4 * nc));
-        SNS_TRY(dev_alloc(&h->rm_Fe, (size_t)16 * nc));
+        SNS_TRY(h->rm_cells.alloc((size_t)4 * nc));
+        SNS_TRY(h->rm_Fe.alloc((size_t)16 * nc));
         h->rm_cap = nc;
     }
     if (nc > 0) {
@@ -583,7 +566,7 @@ int sns_residual_moments(sns_handle h, int form, const double* w, const double* 
             });
         } else {
             if (!h->rm_nomask) {
-                SNS_TRY(dev_alloc(&h->rm_nomask, (size_t)ndof));
+                SNS_TRY(h->rm_nomask.alloc((size_t)ndof));
                 HIP_TRY(hipMemset(h->rm_nomask, 0, (size_t)ndof));
             }
             const unsigned ge = (unsigned)((nc + EL_TETS_PER_BLOCK - 1) / EL_TETS_PER_BLOCK);
@@ -688,16 +671,20 @@ int sns_adjoint_solve(sns_handle h, const double* g, double* lam, int* its, int*
 }
 
 
+// the four work vectors of the Stokes and Newton drivers (4*n doubles each, zeroed), allocated at the first solve
+static int ensure_newton_workspace(sns_ctx* h) {
+    if (h->nw_t) return SNS_OK;
+    const size_t ld = (size_t)ld_of(h);
+    for (DevBuf<double>* v : {&h->nw_F, &h->nw_y, &h->nw_w, &h->nw_t}) SNS_TRY(v->alloc(ld));
+    for (DevBuf<double>* v : {&h->nw_F, &h->nw_y, &h->nw_w, &h->nw_t}) HIP_TRY(hipMemset(*v, 0, ld * sizeof(double)));
+    return SNS_OK;
+}
+
 int sns_stokes_solve(sns_handle h, double* U, int* ksp_its, int* reason, double* rnorm) {
     if (!h || !U || !ksp_its || !reason || !rnorm) return SNS_E_ARG;
     SNS_TRY(ensure_hierarchy(h, true));
     const int64_t nd = nred_of(h), ld = ld_of(h);
-    if (!h->nw_F) {
-        SNS_TRY(dev_alloc(&h->nw_F, (size_t)ld)); SNS_TRY(dev_alloc(&h->nw_y, (size_t)ld));
-        SNS_TRY(dev_alloc(&h->nw_w, (size_t)ld)); SNS_TRY(dev_alloc(&h->nw_t, (size_t)ld));
-        HIP_TRY(hipMemset(h->nw_F, 0, ld * sizeof(double))); HIP_TRY(hipMemset(h->nw_y, 0, ld * sizeof(double)));
-        HIP_TRY(hipMemset(h->nw_w, 0, ld * sizeof(double))); HIP_TRY(hipMemset(h->nw_t, 0, ld * sizeof(double)));
-    }
+    SNS_TRY(ensure_newton_workspace(h));
     // one Newton step of the linear problem from w = 0:  A U = -F(0),  F(0) = lifting, F_B = -g   (:198-214)
     SNS_TRY(timed_assemble(h, SNS_FORM_STOKES, nullptr, h->nw_F, true));
     SNS_TRY(ensure_hierarchy(h));
@@ -722,12 +709,7 @@ static int newton_run(sns_ctx* h, double* w, int* its_out, int* reason_out, int*
     const sns_options& o = h->opt;
     const int64_t nd = nred_of(h), ld = ld_of(h);
     const int g = vec_grid(nd);
-    if (!h->nw_F) {
-        SNS_TRY(dev_alloc(&h->nw_F, (size_t)ld)); SNS_TRY(dev_alloc(&h->nw_y, (size_t)ld));
-        SNS_TRY(dev_alloc(&h->nw_w, (size_t)ld)); SNS_TRY(dev_alloc(&h->nw_t, (size_t)ld));
-        HIP_TRY(hipMemset(h->nw_F, 0, ld * sizeof(double))); HIP_TRY(hipMemset(h->nw_y, 0, ld * sizeof(double)));
-        HIP_TRY(hipMemset(h->nw_w, 0, ld * sizeof(double))); HIP_TRY(hipMemset(h->nw_t, 0, ld * sizeof(double)));
-    }
+    SNS_TRY(ensure_newton_workspace(h));
     double *F = h->nw_F, *y = h->nw_y, *wn = h->nw_w, *Fn = h->nw_t;
     int ksp_total = 0, nh = 0;
     auto record = [&](double f) { if (hist && nh < hist_cap) hist[nh] = f; ++nh; };
@@ -843,7 +825,7 @@ int sns_set_time_term(sns_handle h, double sigma, double theta, const double* d_
         return SNS_OK;
     }
     const size_t ld = (size_t)ld_of(h);
-    if (!h->tt_d) SNS_TRY(dev_alloc(&h->tt_d, ld));
+    if (!h->tt_d) SNS_TRY(h->tt_d.alloc(ld));
     if (d_dev) HIP_TRY(hipMemcpyAsync(h->tt_d, d_dev, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     else HIP_TRY(hipMemsetAsync(h->tt_d, 0, ld * sizeof(double), h->stream));
     SNS_TRY(sync_stream(h));                              // the caller may free d_dev
@@ -911,7 +893,7 @@ int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, 
     // sns_set_time_term), the entry state in a buffer of its own (a step that does not converge restores it)
     double *d = nullptr, *w0 = nullptr;
     SNS_TRY(get_vec(h, 13, &d));
-    if (!h->tt_w0) SNS_TRY(dev_alloc(&h->tt_w0, (size_t)ld));
+    if (!h->tt_w0) SNS_TRY(h->tt_w0.alloc((size_t)ld));
     w0 = h->tt_w0;
     const double sigma = (order == 1 ? 1.0 : 1.5) / dt;
     hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, ld, (order == 1 ? -1.0 : -2.0) / dt, w, d);
@@ -965,12 +947,10 @@ int sns_export(sns_handle h, int what, void* dst, int64_t nbytes) {
         case SNS_EXPORT_STRENGTH: {
             if (!h->has_matrix) { set_error("sns_export: strength before a matrix was assembled"); return SNS_E_STATE; }
             if (nbytes != L.nnzb * 4) { set_error("sns_export: size mismatch, need " + std::to_string(L.nnzb * 4)); return SNS_E_ARG; }
-            double* scale = nullptr;
-            SNS_TRY(dev_alloc(&scale, 4 * (size_t)L.n));
-            const int rc = compute_strength(h, (float*)dst, scale);
-            const int rs = rc == SNS_OK ? sync_stream(h) : rc;
-            (void)hipFree(scale);
-            return rs;
+            DevBuf<double> scale;
+            SNS_TRY(scale.alloc(4 * (size_t)L.n));
+            SNS_TRY(compute_strength(h, (float*)dst, scale));
+            return sync_stream(h);
         }
         case SNS_EXPORT_AGG0: {
             if (h->agg0.empty()) { set_error("sns_export: aggregate map before the hierarchy was built"); return SNS_E_STATE; }
@@ -1034,30 +1014,27 @@ int sns_dense_inverse(int device, int32_t N, const double* A, double* Ainv) {
     if (N <= 0 || !A || !Ainv) return SNS_E_ARG;
     HIP_TRY(hipSetDevice(device));
     const int Np = (N + 63) / 64 * 64;
-    double *W = nullptr, *work = nullptr;
-    int* sing = nullptr;
-    SNS_TRY(dev_alloc(&W, (size_t)Np * Np));
-    SNS_TRY(dev_alloc(&work, dense_gj_work_doubles(Np)));
-    SNS_TRY(dev_alloc(&sing, 1));
+    DevBuf<double> W, work;
+    DevBuf<int> sing;
+    Stream side, mainst;
+    SNS_TRY(W.alloc((size_t)Np * Np));
+    SNS_TRY(work.alloc(dense_gj_work_doubles(Np)));
+    SNS_TRY(sing.alloc(1));
     HIP_TRY(hipMemset(sing, 0, sizeof(int)));
     HIP_TRY(hipMemset(W, 0, (size_t)Np * Np * sizeof(double)));
     HIP_TRY(hipMemcpy2D(W, (size_t)Np * sizeof(double), A, (size_t)N * sizeof(double), (size_t)N * sizeof(double), N,
                         hipMemcpyDeviceToDevice));
     if (Np > N) hipLaunchKernelGGL(k_dense_pad_diag, dim3((Np - N + 255) / 256), dim3(256), 0, nullptr, N, Np, W);
-    hipStream_t side = nullptr;
-    if (std::getenv("SNS_GJ_TWO_STREAMS")) (void)hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
+    if (std::getenv("SNS_GJ_TWO_STREAMS")) (void)hipStreamCreateWithFlags(side.put(), hipStreamNonBlocking);
     HIP_TRY(hipDeviceSynchronize());                      // (the null stream does not order a non-blocking side stream)
-    hipStream_t mainst = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&mainst, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(mainst.put(), hipStreamNonBlocking));
     dense_gj_inverse(mainst, side, Np, W, work, sing);
     HIP_TRY(hipStreamSynchronize(mainst));
-    if (side) { HIP_TRY(hipStreamSynchronize(side)); (void)hipStreamDestroy(side); }
-    (void)hipStreamDestroy(mainst);
+    if (side) HIP_TRY(hipStreamSynchronize(side));
     HIP_TRY(hipMemcpy2D(Ainv, (size_t)N * sizeof(double), W, (size_t)Np * sizeof(double), (size_t)N * sizeof(double), N,
                         hipMemcpyDeviceToDevice));
     int hs = 0;
     HIP_TRY(hipMemcpy(&hs, sing, sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipFree(W); (void)hipFree(work); (void)hipFree(sing);
     HIP_TRY(hipGetLastError());
     if (hs) { set_error("sns_dense_inverse: zero or non-finite pivot"); return SNS_E_STATE; }
     return SNS_OK;
@@ -1136,15 +1113,15 @@ int sns_bench_collective(sns_handle h, int which, int count, int reps, double* m
     if (!h || reps <= 0 || !ms_avg || count < 0) return SNS_E_ARG;
     Comm* c = h->comm.get();
     if (!c || !c->active()) { set_error("sns_bench_collective: no communicator attached"); return SNS_E_STATE; }
-    double *snd = nullptr, *rcv = nullptr;
+    DevBuf<double> snd, rcv;
     if (which == 0) {
         if (c->plans.empty() || !h->levels[0].xg) { set_error("sns_bench_collective: no level-0 halo plan"); return SNS_E_STATE; }
     } else if (which == 1) {
         if (count < 1 || count > 32) { set_error("sns_bench_collective: all-reduce of 1..32 doubles"); return SNS_E_ARG; }
         HIP_TRY(hipMemsetAsync(h->d_scal + 64, 0, 32 * sizeof(double), h->stream));
     } else if (which == 2) {
-        SNS_TRY(dev_alloc(&snd, (size_t)std::max(1, count)));
-        SNS_TRY(dev_alloc(&rcv, (size_t)std::max(1, count) * c->nranks));
+        SNS_TRY(snd.alloc((size_t)std::max(1, count)));
+        SNS_TRY(rcv.alloc((size_t)std::max(1, count) * c->nranks));
         HIP_TRY(hipMemset(snd, 0, (size_t)std::max(1, count) * sizeof(double)));
     } else {
         return SNS_E_ARG;
@@ -1169,8 +1146,6 @@ int sns_bench_collective(sns_handle h, int which, int count, int reps, double* m
         *ms_avg = ms / reps;
     }
     if (which == 0) (void)hipMemset(h->levels[0].xg, 0, 4 * (size_t)h->levels[0].n * sizeof(double));   // (the cycle relies on zero ghosts there)
-    if (snd) (void)hipFree(snd);
-    if (rcv) (void)hipFree(rcv);
     return rc;
 }
 

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include "sns_devbuf.h"
 #include "sns_peer_dev.h"
 
 #include <condition_variable>
@@ -62,23 +63,23 @@ struct Plan {                                    // halo plan of one level (coun
     std::vector<int32_t> h_send_idx, h_recv_idx; // host copies (hierarchy setup)
     int32_t n_own = 0;                           // owned nodes of the level (the ghost nodes follow them)
     bool identity_recv = false;                  // recv_idx[q] == n_own + q: the receive buffer IS the ghost tail, in order
-    int32_t *send_idx = nullptr, *recv_idx = nullptr;   // device
-    double *send_buf = nullptr, *recv_buf = nullptr;    // device, 4 doubles per node (RCCL staging)
+    DevBuf<int32_t> send_idx, recv_idx;                 // device
+    DevBuf<double> send_buf, recv_buf;                  // device, 4 doubles per node (RCCL staging)
     // peer / team transport: receive buffers (by parity of the round) and arrival flags live in this rank's window; the device
     // arrays hold, per neighbour k, where this rank's data / flag go in THAT rank's window
     double* win_recv[2] = {nullptr, nullptr};
-    unsigned long long* win_flag = nullptr;
-    unsigned long long* d_seq = nullptr;         // device word: rounds put so far (k_halo_put advances it)
-    int32_t *d_send_ptr = nullptr;
-    int32_t *d_sr_ptr = nullptr, *d_sr_dst = nullptr;   // per owned row: its send entries, neighbour k << 27 | slot (PutDst)
+    unsigned long long* win_flag = nullptr;      // (borrowed, like win_recv: this rank's window)
+    DevBuf<unsigned long long> d_seq;            // device word: rounds put so far (k_halo_put advances it)
+    DevBuf<int32_t> d_send_ptr;
+    DevBuf<int32_t> d_sr_ptr, d_sr_dst;                 // per owned row: its send entries, neighbour k << 27 | slot (PutDst)
     int32_t n_sent_rows = 0;                     // owned rows with at least one send entry
-    unsigned int* d_expect = nullptr;            // PutDst::expect (comm_plan_put_groups) for the block slots expect_key / expect_slots
+    DevBuf<unsigned int> d_expect;               // PutDst::expect (comm_plan_put_groups) for the block slots expect_key / expect_slots
     unsigned int h_expect[2] = {0, 0};
-    const int32_t* expect_key = nullptr;
+    const int32_t* expect_key = nullptr;         // (borrowed: the level's blk_rows, compared only)
     int32_t expect_slots = 0;
-    double** d_put = nullptr;                    // [2][nn] remote payload addresses
-    unsigned long long** d_rflag = nullptr;      // [nn] remote flag addresses
-    unsigned int* d_done = nullptr;
+    DevBuf<double*> d_put;                       // [2][nn] remote payload addresses
+    DevBuf<unsigned long long*> d_rflag;         // [nn] remote flag addresses
+    DevBuf<unsigned int> d_done;
     Peer* owner = nullptr;                       // the communicator whose window holds win_recv (released in plan_free)
     int32_t n_send() const { return send_ptr.empty() ? 0 : send_ptr.back(); }
     int32_t n_recv() const { return recv_ptr.empty() ? 0 : recv_ptr.back(); }
@@ -98,6 +99,10 @@ struct Team {                                    // in-process communicator: a b
 };
 
 struct Comm {
+    Comm() = default;
+    Comm(const Comm&) = delete;
+    Comm& operator=(const Comm&) = delete;
+    ~Comm();                                     // the plans' window areas go back (plan_free), then the plans, the RCCL communicator last
     ncclComm_t nccl = nullptr;
     Team* team = nullptr;
     Peer* peer = nullptr;                        // peer transport: the caller's (sns_peer_destroy); team: the Team's

@@ -185,6 +185,10 @@ void Team::barrier() {
         cv.wait(lk, [&] { return gen != g; });
     }
 }
+Comm::~Comm() {
+    for (auto& p : plans) plan_free(p);
+    if (nccl) (void)ncclCommDestroy(nccl);
+}
 Team::~Team() {
     for (Peer* p : peers)
         if (p) (void)peer_destroy(p);
@@ -199,41 +203,22 @@ int comm_host_barrier(Comm* c, hipStream_t s) {
 
 int plan_upload(Plan& p) {
     const size_t ns = (size_t)p.n_send(), nr = (size_t)p.n_recv();
-    CHIP(hipMalloc((void**)&p.send_idx, std::max<size_t>(1, ns) * sizeof(int32_t)));
-    CHIP(hipMalloc((void**)&p.recv_idx, std::max<size_t>(1, nr) * sizeof(int32_t)));
+    CTRY(p.send_idx.alloc(ns));
+    CTRY(p.recv_idx.alloc(nr));
     if (ns) CHIP(hipMemcpy(p.send_idx, p.h_send_idx.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice));
     if (nr) CHIP(hipMemcpy(p.recv_idx, p.h_recv_idx.data(), nr * sizeof(int32_t), hipMemcpyHostToDevice));
-    CHIP(hipMalloc((void**)&p.send_buf, std::max<size_t>(1, 4 * ns) * sizeof(double)));
-    CHIP(hipMalloc((void**)&p.recv_buf, std::max<size_t>(1, 4 * nr) * sizeof(double)));
+    CTRY(p.send_buf.alloc(4 * ns));
+    CTRY(p.recv_buf.alloc(4 * nr));
     p.identity_recv = true;
     for (size_t q = 0; q < nr; ++q)
         if (p.h_recv_idx[q] != p.n_own + (int32_t)q) { p.identity_recv = false; break; }
     return SNS_OK;
 }
 
+// Gives the plan's area of the window back to its communicator.  The plan's own device arrays are released by its members
+// (DevBuf) when the plan goes; a plan is not used again after this.
 void plan_free(Plan& p) {
-    if (p.send_idx) (void)hipFree(p.send_idx);
-    if (p.recv_idx) (void)hipFree(p.recv_idx);
-    if (p.send_buf) (void)hipFree(p.send_buf);
-    if (p.recv_buf) (void)hipFree(p.recv_buf);
-    if (p.d_send_ptr) (void)hipFree(p.d_send_ptr);
-    if (p.d_sr_ptr) (void)hipFree(p.d_sr_ptr);
-    if (p.d_sr_dst) (void)hipFree(p.d_sr_dst);
-    p.d_sr_ptr = p.d_sr_dst = nullptr;
-    if (p.d_expect) (void)hipFree(p.d_expect);
-    p.d_expect = nullptr;
     p.expect_key = nullptr;
-    if (p.d_put) (void)hipFree(p.d_put);
-    if (p.d_rflag) (void)hipFree(p.d_rflag);
-    if (p.d_done) (void)hipFree(p.d_done);
-    if (p.d_seq) (void)hipFree(p.d_seq);
-    p.send_idx = p.recv_idx = nullptr;
-    p.send_buf = p.recv_buf = nullptr;
-    p.d_send_ptr = nullptr;
-    p.d_put = nullptr;
-    p.d_rflag = nullptr;
-    p.d_done = nullptr;
-    p.d_seq = nullptr;
     if (p.owner && p.win_recv[0]) {
         // the plan area of a window is a bump allocator: it is reclaimed as a whole when the last plan carved from it goes
         // (a communicator reused across problems -- bench legs, test suites -- would exhaust its window otherwise)
@@ -293,7 +278,7 @@ int comm_plan_put_groups(Comm* c, Plan& p, const int32_t* blk_rows, int32_t n_sl
     p.expect_key = nullptr;
     p.h_expect[0] = p.h_expect[1] = 0;
     if (!blk_rows || n_slots <= 0) return SNS_OK;
-    if (!p.d_expect) CHIP(hipMalloc((void**)&p.d_expect, 3 * sizeof(unsigned int)));
+    if (!p.d_expect) CTRY(p.d_expect.alloc(3));
     CHIP(hipMemsetAsync(p.d_expect, 0, 3 * sizeof(unsigned int), s));
     const int32_t ng = (n_slots + 7) / 8;
     hipLaunchKernelGGL(k_count_put_groups, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, n_slots, blk_rows, p.d_sr_ptr, p.d_expect);
@@ -591,6 +576,8 @@ int peer_close_mappings(Peer* p) {
     return SNS_OK;
 }
 
+// (Peer keeps its raw pointers: the window is shared through IPC, and the unmapping, the ranks' synchronisation and the frees
+// below are ordered by hand; the window is not counted by sns_live_device_bytes)
 int peer_destroy(Peer* p) {
     if (!p) return SNS_OK;
     (void)peer_close_mappings(p);                            // (no-op after an explicit first phase)
@@ -688,8 +675,7 @@ int peer_plan_connect(Comm* c, Plan& p, const PlanOffers& t) {
     }
     std::vector<int32_t> sp(p.send_ptr);
     if (sp.empty()) sp.assign(1, 0);
-    CHIP(hipMalloc((void**)&p.d_send_ptr, sp.size() * sizeof(int32_t)));
-    CHIP(hipMemcpy(p.d_send_ptr, sp.data(), sp.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    CTRY(p.d_send_ptr.upload(sp));
     {
         // per owned row: where it is sent (the put carried by the producing kernel, comm_put_dst)
         const int32_t no = std::max<int32_t>(p.n_own, 0);
@@ -709,19 +695,15 @@ int peer_plan_connect(Comm* c, Plan& p, const PlanOffers& t) {
             for (int k = 0; k < nn; ++k)
                 for (int32_t q = p.send_ptr[(size_t)k]; q < p.send_ptr[(size_t)k + 1]; ++q)
                     rd[(size_t)at[(size_t)p.h_send_idx[(size_t)q]]++] = (int32_t)(((uint32_t)k << 27) | (uint32_t)(q - p.send_ptr[(size_t)k]));
-            CHIP(hipMalloc((void**)&p.d_sr_ptr, rp.size() * sizeof(int32_t)));
-            CHIP(hipMemcpy(p.d_sr_ptr, rp.data(), rp.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            CHIP(hipMalloc((void**)&p.d_sr_dst, rd.size() * sizeof(int32_t)));
-            CHIP(hipMemcpy(p.d_sr_dst, rd.data(), rd.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            CTRY(p.d_sr_ptr.upload(rp));
+            CTRY(p.d_sr_dst.upload(rd));
         }
     }
-    CHIP(hipMalloc((void**)&p.d_put, put.size() * sizeof(double*)));
-    CHIP(hipMalloc((void**)&p.d_rflag, rflag.size() * sizeof(unsigned long long*)));
-    CHIP(hipMemcpy(p.d_put, put.data(), put.size() * sizeof(double*), hipMemcpyHostToDevice));
-    CHIP(hipMemcpy(p.d_rflag, rflag.data(), rflag.size() * sizeof(unsigned long long*), hipMemcpyHostToDevice));
-    CHIP(hipMalloc((void**)&p.d_done, sizeof(unsigned int)));
+    CTRY(p.d_put.upload(put));
+    CTRY(p.d_rflag.upload(rflag));
+    CTRY(p.d_done.alloc(1));
     CHIP(hipMemset(p.d_done, 0, sizeof(unsigned int)));
-    CHIP(hipMalloc((void**)&p.d_seq, sizeof(unsigned long long)));
+    CTRY(p.d_seq.alloc(1));
     CHIP(hipMemcpy(p.d_seq, &round0, sizeof(unsigned long long), hipMemcpyHostToDevice));
     return SNS_OK;
 }
@@ -826,12 +808,12 @@ int peer_selftest(int device, int nranks, int halo_nodes, int reps, double us_ou
     const int prio[3] = {prio_least, prio_greatest, (prio_least + prio_greatest) / 2};
     auto work = [&](int r) {
         auto fail = [&](int rc) { rcs[(size_t)r] = rc; errs[(size_t)r] = sns_last_error(); };
-        hipStream_t st = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        Stream st;
+        Event e0, e1;
         Comm c;
         Plan plan;
-        double *x = nullptr, *ar = nullptr, *ags = nullptr, *agr = nullptr;
-        int* bad = nullptr;
+        DevBuf<double> x, ar, ags, agr;
+        DevBuf<int> bad;
         char hd[64];
         int rc = SNS_OK;
         // every rank passes every barrier, whatever its own state: a failing rank must not strand the others
@@ -860,11 +842,10 @@ int peer_selftest(int device, int nranks, int halo_nodes, int reps, double us_ou
         for (int q = 0; q < nranks; ++q) t.all.insert(t.all.end(), offers[(size_t)q].mine.begin(), offers[(size_t)q].mine.end());
         if (peer_plan_connect(&c, plan, t) != SNS_OK) fail(SNS_E_COMM);
         const int32_t ag_count = 2048;
-        if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio[r]) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
-            hipEventCreate(&e1) != hipSuccess || hipMalloc((void**)&x, 4 * (size_t)n_local * sizeof(double)) != hipSuccess ||
-            hipMalloc((void**)&ar, 8 * sizeof(double)) != hipSuccess || hipMalloc((void**)&ags, ag_count * sizeof(double)) != hipSuccess ||
-            hipMalloc((void**)&agr, (size_t)ag_count * nranks * sizeof(double)) != hipSuccess ||
-            hipMalloc((void**)&bad, sizeof(int)) != hipSuccess || hipMemset(bad, 0, sizeof(int)) != hipSuccess ||
+        if (hipStreamCreateWithPriority(st.put(), hipStreamNonBlocking, prio[r]) != hipSuccess || hipEventCreate(e0.put()) != hipSuccess ||
+            hipEventCreate(e1.put()) != hipSuccess || x.alloc(4 * (size_t)n_local) != SNS_OK || ar.alloc(8) != SNS_OK ||
+            ags.alloc(ag_count) != SNS_OK || agr.alloc((size_t)ag_count * nranks) != SNS_OK ||
+            bad.alloc(1) != SNS_OK || hipMemset(bad, 0, sizeof(int)) != hipSuccess ||
             hipMemset(x, 0, 4 * (size_t)n_local * sizeof(double)) != hipSuccess)
             fail(SNS_E_HIP);
         team.barrier();
@@ -949,10 +930,8 @@ int peer_selftest(int device, int nranks, int halo_nodes, int reps, double us_ou
             if (go_on) {
                 const int64_t per = (int64_t)(pe->ag_doubles / (size_t)nranks);
                 const int64_t big = 3 * per + 1000;
-                double *ar40 = nullptr, *bs = nullptr, *br = nullptr;
-                if (hipMalloc((void**)&ar40, 40 * sizeof(double)) != hipSuccess || hipMalloc((void**)&bs, (size_t)big * sizeof(double)) != hipSuccess ||
-                    hipMalloc((void**)&br, (size_t)big * nranks * sizeof(double)) != hipSuccess)
-                    fail(SNS_E_HIP);
+                DevBuf<double> ar40, bs, br;
+                if (ar40.alloc(40) != SNS_OK || bs.alloc((size_t)big) != SNS_OK || br.alloc((size_t)big * nranks) != SNS_OK) fail(SNS_E_HIP);
                 team.barrier();
                 bool ok2 = true;
                 for (int q = 0; q < nranks; ++q) ok2 = ok2 && rcs[(size_t)q] == SNS_OK;
@@ -979,8 +958,7 @@ int peer_selftest(int device, int nranks, int halo_nodes, int reps, double us_ou
                     if (rc2 != SNS_OK) fail(rc2);
                     else if (peer_check(&c) != SNS_OK) fail(SNS_E_COMM);
                 }
-                team.barrier();                                          // (buffers of the round are read by nobody else: local frees)
-                (void)hipFree(ar40); (void)hipFree(bs); (void)hipFree(br);
+                team.barrier();                                          // (buffers of the round are read by nobody else: freed at the brace)
             }
             int dbad = 0;
             (void)hipMemcpy(&dbad, bad, sizeof(int), hipMemcpyDeviceToHost);
@@ -991,11 +969,8 @@ int peer_selftest(int device, int nranks, int halo_nodes, int reps, double us_ou
             }
         }
         team.barrier();                                              // nobody frees a window a peer may still store into
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
+        if (st) (void)hipStreamSynchronize(st);
         plan_free(plan);
-        (void)hipFree(x); (void)hipFree(ar); (void)hipFree(ags); (void)hipFree(agr); (void)hipFree(bad);
     };
     std::vector<std::thread> th;
     for (int r = 0; r < nranks; ++r) th.emplace_back(work, r);
@@ -1028,17 +1003,17 @@ int peer_check_links(Peer* pe, int rounds) {
     c.rank = pe->rank;
     c.nranks = pe->nranks;
     const int n = 4096, nr = pe->nranks, halo = 2048;
-    hipStream_t st = nullptr;
-    double *ar = nullptr, *ags = nullptr, *agr = nullptr, *x = nullptr, *off_s = nullptr, *off_r = nullptr;
-    int* bad = nullptr;
+    Stream st;
+    DevBuf<double> ar, ags, agr, x, off_s, off_r;
+    DevBuf<int> bad;
     int rc = SNS_OK, wrong = 0;
     Plan plan;
     auto body = [&]() -> int {
-        CHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        CHIP(hipMalloc((void**)&ar, 8 * sizeof(double)));
-        CHIP(hipMalloc((void**)&ags, n * sizeof(double)));
-        CHIP(hipMalloc((void**)&agr, (size_t)n * nr * sizeof(double)));
-        CHIP(hipMalloc((void**)&bad, sizeof(int)));
+        CHIP(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
+        CTRY(ar.alloc(8));
+        CTRY(ags.alloc(n));
+        CTRY(agr.alloc((size_t)n * nr));
+        CTRY(bad.alloc(1));
         CHIP(hipMemset(bad, 0, sizeof(int)));
         for (int it = 0; it < rounds; ++it) {
             const double tag = 3.0e6 * (it + 1);
@@ -1069,8 +1044,8 @@ int peer_check_links(Peer* pe, int rounds) {
             const int rco = peer_plan_offer(&c, plan, t);
             const size_t LEN = (size_t)3 * nr + 1;
             if (rco != SNS_OK) t.mine.assign(LEN, -2.0);
-            CHIP(hipMalloc((void**)&off_s, LEN * sizeof(double)));
-            CHIP(hipMalloc((void**)&off_r, LEN * nr * sizeof(double)));
+            CTRY(off_s.alloc(LEN));
+            CTRY(off_r.alloc(LEN * nr));
             CHIP(hipMemcpy(off_s, t.mine.data(), LEN * sizeof(double), hipMemcpyHostToDevice));
             CTRY(comm_allgather(&c, off_s, off_r, (int)LEN, st));
             CHIP(hipStreamSynchronize(st));
@@ -1082,7 +1057,7 @@ int peer_check_links(Peer* pe, int rounds) {
                 if (v == -2.0) { set_error("peer link check: a rank could not place the ring plan in its window"); return SNS_E_COMM; }
             CTRY(peer_plan_connect(&c, plan, t));
             const int32_t n_local = halo * (1 + nn);
-            CHIP(hipMalloc((void**)&x, 4 * (size_t)n_local * sizeof(double)));
+            CTRY(x.alloc(4 * (size_t)n_local));
             const unsigned gh = (unsigned)((4 * (int64_t)halo + 255) / 256);
             for (int it = 0; it < rounds; ++it) {
                 const double tag = 5.0e6 * (it + 1);
@@ -1110,11 +1085,10 @@ int peer_check_links(Peer* pe, int rounds) {
         return SNS_OK;
     };
     rc = body();
-    if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+    if (st) (void)hipStreamSynchronize(st);
     // (the ring plan's area goes back to the window; a peer still a round behind only ever writes rounds of THIS plan, which no
     // later plan mistakes for its own -- peer_plan_connect)
     plan_free(plan);
-    (void)hipFree(ar); (void)hipFree(ags); (void)hipFree(agr); (void)hipFree(bad); (void)hipFree(x); (void)hipFree(off_s); (void)hipFree(off_r);
     if (rc == SNS_OK && wrong != 0) {
         set_error("peer link check: rank " + std::to_string(pe->rank) + " read " + std::to_string(wrong) + " wrong values in " +
                   std::to_string(rounds) + " rounds (stores of a peer not visible: window memory type / peer access)");

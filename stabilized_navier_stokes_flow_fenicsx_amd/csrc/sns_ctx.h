@@ -1,6 +1,7 @@
-// Shared internals of the C-ABI layer (round 5: csrc/sns_api.hip split into setup / cycle / Krylov / C-ABI translation units):
-// the context behind an sns_handle, the error / allocation helpers, the launch helpers of the level passes and the functions the
-// translation units call across each other.  Not installed; the public surface is include/sns.h.
+// Shared internals of the C-ABI layer (csrc/sns_api.hip and the setup / cycle / Krylov / ... translation units beside it): the
+// context behind an sns_handle, the error helpers, the launch helpers of the level passes and the functions the translation
+// units call across each other.  The context owns its device memory and HIP objects by type (csrc/sns_devbuf.h): there is no
+// free list, ~sns_ctx releases everything.  Not installed; the public surface is include/sns.h.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -48,68 +49,65 @@ namespace sns {
         if (_r != SNS_OK) return _r;                                                                      \
     } while (0)
 
-template <class T>
-static inline int dev_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    HIP_TRY(hipMalloc((void**)p, count * sizeof(T)));
-    return SNS_OK;
-}
-
-template <class T>
-static inline int dev_upload(T** p, const std::vector<T>& v, hipStream_t) {
-    SNS_TRY(dev_alloc(p, v.size()));
-    if (!v.empty()) HIP_TRY(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return SNS_OK;
-}
-
 }  // namespace sns
 
 using namespace sns;
 
 struct sns_ctx {
+    // Release order: ~sns_ctx waits for the device and destroys the graph exec and the streams; then the members go in reverse
+    // order of declaration -- events and every buffer first, the communicator (declared first) last: its plans' window areas go
+    // back through plan_free, the plans' arrays are freed, the RCCL communicator is destroyed (~Comm, csrc/sns_comm.hip).
+    std::unique_ptr<Comm> comm;
+    ~sns_ctx() {
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+        coarse_graph.reset();
+        cap_stream.reset();
+        gj_stream.reset();
+        side_stream.reset();
+    }
     sns_options opt;
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;                // (borrowed: the caller's, sns_set_stream)
     // mesh (dim 3: tets; dim 2: triangles in a stride-4 connectivity, z component a Dirichlet dof)
     int dim = 3;
     int32_t n = 0, n_owned = 0;
     int64_t n_global_fine = 0;                   // fine-level rows over all ranks (set when the hierarchy is built)
     int64_t n_global_l1 = 0;                     // level-1 rows over all ranks (the sweep schedule must be the same on every rank)
     int64_t E = 0;
-    int32_t* tets = nullptr;
-    double* pts = nullptr;
-    uint8_t* bc_mask = nullptr;
-    double* bc_val = nullptr;
+    DevBuf<int32_t> tets;
+    DevBuf<double> pts;
+    DevBuf<uint8_t> bc_mask;
+    DevBuf<double> bc_val;
     // assembly maps
-    int64_t *nt_ptr = nullptr, *c_ptr = nullptr;
-    int32_t *nt_idx = nullptr, *c_idx = nullptr;
-    int32_t* od_order = nullptr;       // off-diagonal slots, locally sorted by contribution count (scratch-free assembly)
-    double* gext = nullptr;            // Dirichlet data extended by zero (the state the Stokes lifting term is taken at)
+    DevBuf<int64_t> nt_ptr, c_ptr;
+    DevBuf<int32_t> nt_idx, c_idx;
+    DevBuf<int32_t> od_order;          // off-diagonal slots, locally sorted by contribution count (scratch-free assembly)
+    DevBuf<double> gext;               // Dirichlet data extended by zero (the state the Stokes lifting term is taken at)
     int64_t n_od = 0;
-    double *Ke = nullptr, *Fe = nullptr;
+    DevBuf<double> Ke, Fe;
     // residual moments (sns_residual_moments): per-256-cell support counts / offsets, the compacted connectivity and its
     // element residuals (capacity rm_cap cells, grown on demand), and an all-zero Dirichlet mask for the staged element kernel
-    int64_t* rm_off = nullptr;
-    int32_t* rm_cells = nullptr;
-    double* rm_Fe = nullptr;
+    DevBuf<int64_t> rm_off;
+    DevBuf<int32_t> rm_cells;
+    DevBuf<double> rm_Fe;
     int64_t rm_cap = 0;
-    uint8_t* rm_nomask = nullptr;
+    DevBuf<uint8_t> rm_nomask;
     // operator hierarchy; levels[0] is the assembled fine operator.  A deque: references to a level stay valid
     // while coarser levels are appended (a vector reallocation under a live Level& once handed a kernel dangling
     // pointers)
     std::deque<Level> levels;
-    std::vector<int32_t*> slot_row;              // per level
-    std::vector<uint8_t*> empty_c;               // per level (coarse side), level l -> empty flags of level l+1
-    std::vector<double*> pong;                   // per level smoother ping-pong buffer
-    int* d_piv = nullptr;
-    int* d_sing = nullptr;
+    std::vector<DevBuf<int32_t>> slot_row;            // per level
+    std::vector<DevBuf<uint8_t>> empty_c;             // per level (coarse side), level l -> empty flags of level l+1
+    std::vector<DevBuf<double>> pong;                 // per level smoother ping-pong buffer
+    DevBuf<int> d_piv;
+    DevBuf<int> d_sing;
     FormVariant fv;                              // sns_set_form_variant (diagnostic; default = the reference's form)
     // sns_set_time_term: the transient 3-D NS form.  tt.d points at tt_d, the handle's copy of the history (4*n doubles,
     // allocated at the first set); tt_on selects the TT instantiations of the NS assembly kernels
     TimeTerm tt;
-    double* tt_d = nullptr;
-    double* tt_w0 = nullptr;                     // sns_time_step: the state on entry
+    DevBuf<double> tt_d;
+    DevBuf<double> tt_w0;                        // sns_time_step: the state on entry
     bool tt_on = false;
     // sns_set_viscosity_law: the generalised-Newtonian 3-D NS form; vl_on selects the VL instantiations (never with tt_on)
     ViscosityLaw vl;
@@ -117,61 +115,59 @@ struct sns_ctx {
     bool has_matrix = false, pc_ready = false;
     int pc_setups = 0;
     // hipGraph of the launch-bound coarse part of the V-cycle (levels >= graph_level; serial runs only)
-    hipStream_t cap_stream = nullptr;
-    hipStream_t gj_stream = nullptr;              // second stream of the dense coarsest level's elimination (bulk updates beside the pivot chain)
-    hipGraphExec_t coarse_graph = nullptr;
+    Stream cap_stream;
+    Stream gj_stream;                            // second stream of the dense coarsest level's elimination (bulk updates beside the pivot chain)
+    GraphExec coarse_graph;
     std::vector<double> graph_sig;                // (graph level, omega per level) the graph was captured with ...
     std::vector<policy::LevelPlan> graph_rows;    // ... and the plan rows it covers
     bool graph_disabled = false;
     int matrix_form = -1;
     bool transposed = false;                     // vals holds A^T (sns_transpose_operator); every assembly clears it
-    int32_t* tr_partner = nullptr;               // [nnzb] slot (i, j) -> slot (j, i), built at the first transpose (csrc/sns_transpose.hip)
+    DevBuf<int32_t> tr_partner;                  // [nnzb] slot (i, j) -> slot (j, i), built at the first transpose (csrc/sns_transpose.hip)
     int est_form = -1;                           // form of the matrix the levels' spectral estimates were last taken from
     double est_re = 0.0;                         // ... and its Reynolds number
     // reductions
-    double* partial = nullptr;                   // [max(65536*8, n/32)]
-    double* partial2 = nullptr;                  // second stage of long reductions
-    double* d_scal = nullptr;                    // [256]
-    double* h_scal = nullptr;                    // pinned [256]
+    DevBuf<double> partial;                      // [max(65536*8, n/32)]
+    DevBuf<double> partial2;                     // second stage of long reductions
+    DevBuf<double> d_scal;                       // [256]
+    PinnedDoubles h_scal;                        // pinned [256]
     // Krylov workspace
-    std::vector<double*> kv;                     // allocated vectors (4*n each)
-    double* gm_V = nullptr;                      // (m+1) * ld
-    double* gm_Z = nullptr;                      // m * ld
+    std::vector<DevBuf<double>> kv;                   // allocated vectors (4*n each)
+    DevBuf<double> gm_V;                         // (m+1) * ld
+    DevBuf<double> gm_Z;                         // m * ld
     int gm_m = 0;
-    double* d_h = nullptr;                       // device Hessenberg column scratch [3*(m+2)]
+    DevBuf<double> d_h;                          // device Hessenberg column scratch [3*(m+2)]
     // Newton workspace
-    double *nw_F = nullptr, *nw_y = nullptr, *nw_w = nullptr, *nw_t = nullptr;
+    DevBuf<double> nw_F, nw_y, nw_w, nw_t;
     sns_timings tm{};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_it = nullptr;
+    Event ev0, ev1, ev_it;
     // debug counters of the last Krylov solve (sns_get_counters): host syncs, all-reduces, halo exchanges
     int64_t ctr_host_syncs = 0, ctr_allreduce = 0, ctr_exchange = 0;
     int64_t last_ctr[3] = {0, 0, 0};                 // snapshot at the end of the last Krylov solve
     int bnd_dot_blocks = 0;
     int dot_partials = 0;                            // partial sums the last fused SpMV+dot pass left in h->partial
     // multi-GPU, level 0: owned rows with at least one ghost column (the only rows that must wait for the halo)
-    int32_t* bnd_rows = nullptr;
-    uint8_t* bnd_flag = nullptr;
+    DevBuf<int32_t> bnd_rows;
+    DevBuf<uint8_t> bnd_flag;
     int32_t n_bnd = 0;
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_x = nullptr, ev_side = nullptr;
+    Stream side_stream;
+    Event ev_x, ev_side;
     bool no_overlap = false;
     bool team_overlap = false;                       // SNS_TEAM_OVERLAP: the team transport takes the two-stream path too (tests)
-    double* arn_V = nullptr;                          // Arnoldi basis of the damping estimate, 9 vectors of the largest level >= ... asked for
-    size_t arn_cap = 0;
+    DevBuf<double> arn_V;                             // Arnoldi basis of the damping estimate, 9 vectors of the largest level >= ... asked for
     // the put half of a halo exchange carried by the kernel that produced the vector (PutDst, round 5): first_put_carried -- the
     // Krylov kernel that ran the fine level's first sweep put it too; child_put_carried -- the restriction put the next level's first
     // sweep; put_pending -- the last kernel of a window cycle put its result (the vector named), the next exchange of exactly that
     // vector is comm_put_carried; pc_then_op -- the caller of pc_apply promises that an operator application of the result follows
     // (only then may the fine level's last kernel carry the put: a round nobody consumes would void the windows' flow control)
     bool first_put_carried = false, child_put_carried = false, pc_then_op = false;
-    const double* put_pending = nullptr;
+    const double* put_pending = nullptr;             // (borrowed: compared only)
     bool first_sweep_done = false;                   // the V-cycle's fine-level first sweep was done by the Krylov kernel that wrote its input
     bool r3_estimates = false;                       // SNS_R3_SPECTRAL_ESTIMATE (tests of the retry path): round 3's policy -- spectral
                                                      // estimates every 4th setup whatever the operator (first Jacobians on the Stokes estimate)
     double damping_backoff = 1.0;                    // < 1 after a failed AMG-preconditioned solve: all level dampings scaled (krylov())
     int64_t ctr_retries = 0;                         // damping retries since sns_reset_timings
     int last_first_reason = 0;                       // reason of the FIRST attempt of the last solve (0 = no retry happened)
-    std::unique_ptr<Comm> comm;
     // what the V-cycle runs (csrc/sns_policy.h): the hierarchy's structure, agreed over the ranks when it is built, and the plan the
     // options make of it (rebuilt by sns_set_options).  Every decision of the cycle reads plan.
     policy::Facts facts;
@@ -186,12 +182,12 @@ struct sns_ctx {
     int rep_level = 0;
     int32_t rep_maxn = 0, rep_NG = 0, rep_off = 0;
     int64_t rep_maxnz = 0;
-    int32_t* rep_valmap = nullptr;                // [nranks*maxnz] gathered slot -> slot of the replicated level (-1: padding)
-    int32_t* rep_rowmap = nullptr;                // [NG] row of the replicated level -> gathered row (rank*maxn + i)
-    double *rep_vsend = nullptr, *rep_vrecv = nullptr, *rep_bsend = nullptr, *rep_brecv = nullptr;
-    int64_t *rep_doff = nullptr, *rep_dcnt = nullptr;   // [nranks] doubles: where rank r's right-hand side goes in the replicated level's b, and how much
-    int32_t* cg_colmap = nullptr;                 // local coarsest node -> global (padded) node id
-    double *cg_rows = nullptr, *cg_full = nullptr, *cg_send = nullptr, *cg_recv = nullptr;
+    DevBuf<int32_t> rep_valmap;                   // [nranks*maxnz] gathered slot -> slot of the replicated level (-1: padding)
+    DevBuf<int32_t> rep_rowmap;                   // [NG] row of the replicated level -> gathered row (rank*maxn + i)
+    DevBuf<double> rep_vsend, rep_vrecv, rep_bsend, rep_brecv;
+    DevBuf<int64_t> rep_doff, rep_dcnt;                 // [nranks] doubles: where rank r's right-hand side goes in the replicated level's b, and how much
+    DevBuf<int32_t> cg_colmap;                    // local coarsest node -> global (padded) node id
+    DevBuf<double> cg_rows, cg_full, cg_send, cg_recv;
     std::vector<std::vector<int32_t>> ghost_gid;  // per level: (owner rank, owner-local id) of each ghost node
     std::vector<std::vector<int32_t>> ghost_own;
     std::unique_ptr<HostPattern> pattern;      // kept until the (lazy) hierarchy build
@@ -201,7 +197,7 @@ struct sns_ctx {
     bool fine_rematched = false;               // ... of some rank (agreed over the ranks: the fine-level aggregate blocks)
     // optional per-launch timing of the fine-level SpMV family
     bool time_kernels = false;
-    std::vector<std::array<hipEvent_t, 2>> ev_pool;
+    std::vector<std::array<Event, 2>> ev_pool;
     std::vector<int> ev_mode;
     size_t ev_used = 0;
     double kt_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};            // modes 0..3 = SpmvMode, 4 = fused post-sweep on M = A P
@@ -213,7 +209,7 @@ struct sns_ctx {
 namespace sns {
 // csrc/sns_setup.hip: symbolic hierarchy, assembly driver, numeric setup of the preconditioner
 int alloc_level_vectors(Level& L);
-int upload_pattern(Level& L, const HostPattern& P, int32_t** slot_row, hipStream_t s);
+int upload_pattern(Level& L, const HostPattern& P, DevBuf<int32_t>& slot_row, hipStream_t s);
 int global_sum(sns_ctx* h, double* v, int count);
 int host_allgather(sns_ctx* h, const std::vector<double>& mine, std::vector<double>& all);
 int check_plan_symmetry(sns_ctx* h, const Plan& p, int level);
@@ -273,10 +269,9 @@ inline int sync_stream(sns_ctx* h) {
 inline void time_begin(sns_ctx* h, int mode, hipStream_t st = nullptr) {
     if (!h->time_kernels) return;
     if (h->ev_used == h->ev_pool.size()) {
-        std::array<hipEvent_t, 2> p;
-        (void)hipEventCreate(&p[0]);
-        (void)hipEventCreate(&p[1]);
-        h->ev_pool.push_back(p);
+        h->ev_pool.emplace_back();
+        (void)hipEventCreate(h->ev_pool.back()[0].put());
+        (void)hipEventCreate(h->ev_pool.back()[1].put());
         h->ev_mode.push_back(0);
     }
     h->ev_mode[h->ev_used] = mode;
@@ -463,7 +458,7 @@ inline void with_fmt(int fmt, Fn&& fn) { dispatch<2, 1>(fmt, fn); }
 // (TT), 2 with a viscosity law (VL); the two are never on together
 inline int ns_variant(const sns_ctx* h) { return h->vl_on ? 2 : (h->tt_on ? 1 : 0); }
 
-// a level's matrix copy in format F -- values and row scales (nullptr in fp32) -- and the same of M = A P
+// a level's matrix copy in format F -- values and row scales (nullptr in fp32) -- and the same of M = A P (borrowed pointers)
 struct LpMat {
     const void* vals;
     const float* scale;
@@ -570,9 +565,9 @@ int exchange_and_spmv(sns_ctx* h, double* xe, const double* x, double* y, const 
         if (!h->side_stream) {
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            HIP_TRY(hipStreamCreateWithPriority(&h->side_stream, hipStreamNonBlocking, lo));
-            HIP_TRY(hipEventCreateWithFlags(&h->ev_x, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&h->ev_side, hipEventDisableTiming));
+            HIP_TRY(hipStreamCreateWithPriority(h->side_stream.put(), hipStreamNonBlocking, lo));
+            HIP_TRY(hipEventCreateWithFlags(h->ev_x.put(), hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(h->ev_side.put(), hipEventDisableTiming));
         }
         HIP_TRY(hipEventRecord(h->ev_x, h->stream));                 // x (owned part) is ready
         HIP_TRY(hipStreamWaitEvent(h->side_stream, h->ev_x, 0));

@@ -1,6 +1,6 @@
 // The V-cycle (serial, partitioned over RCCL, partitioned over the window transports), the hipGraph of its launch-bound tail,
 // and the preconditioner / operator applications the Krylov methods call.
-// (round 5: one of the four translation units csrc/sns_api.hip was split into; shared internals in csrc/sns_ctx.h)
+// (shared internals in csrc/sns_ctx.h)
 #include "sns_ctx.h"
 
 namespace sns {
@@ -18,8 +18,8 @@ int coarse_cycle(sns_ctx* h, int l, const double* b, double* x) {
     for (auto& L : h->levels) sig.push_back(L.omega);
     const std::vector<policy::LevelPlan> rows(h->plan.level.begin() + (gl - 1), h->plan.level.end());
     if (!h->coarse_graph || sig != h->graph_sig || rows != h->graph_rows) {
-        if (h->coarse_graph) { (void)hipGraphExecDestroy(h->coarse_graph); h->coarse_graph = nullptr; }
-        if (!h->cap_stream && hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking) != hipSuccess) {
+        h->coarse_graph.reset();
+        if (!h->cap_stream && hipStreamCreateWithFlags(h->cap_stream.put(), hipStreamNonBlocking) != hipSuccess) {
             h->graph_disabled = true;
             return vcycle(h, l, b, x);
         }
@@ -33,14 +33,15 @@ int coarse_cycle(sns_ctx* h, int l, const double* b, double* x) {
             h->stream = user;
             ok = (hipStreamEndCapture(h->cap_stream, &graph) == hipSuccess) && rc == SNS_OK && graph;
         }
-        if (ok) ok = hipGraphInstantiate(&h->coarse_graph, graph, nullptr, nullptr, 0) == hipSuccess;
+        hipGraphExec_t exec = nullptr;
+        if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
         if (graph) (void)hipGraphDestroy(graph);
         if (!ok) {
             (void)hipGetLastError();
-            h->coarse_graph = nullptr;
             h->graph_disabled = true;
             return vcycle(h, l, b, x);
         }
+        *h->coarse_graph.put() = exec;
         h->graph_sig = sig;
         h->graph_rows = rows;
     }

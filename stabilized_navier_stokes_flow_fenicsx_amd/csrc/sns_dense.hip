@@ -24,6 +24,7 @@
 
 #include <cstdint>
 
+#include "sns_devbuf.h"
 #include "sns_kernels.h"
 
 namespace sns {
@@ -349,10 +350,10 @@ void dense_gj_inverse(hipStream_t s, hipStream_t side, int Np, double* A, double
     const int nb = Np / GB;
     double* RC = work;                                    // [2][R 64 x Np | CpT 64 x Np]
     double* P = work + (size_t)4 * GB * Np;               // [2][Pinv 4096 | PinvT 4096]
-    hipEvent_t e_panel = nullptr, e_bulk = nullptr, e_start = nullptr;
-    const bool two = side != nullptr && nb > 2 && hipEventCreateWithFlags(&e_panel, hipEventDisableTiming) == hipSuccess &&
-                     hipEventCreateWithFlags(&e_bulk, hipEventDisableTiming) == hipSuccess &&
-                     hipEventCreateWithFlags(&e_start, hipEventDisableTiming) == hipSuccess;
+    Event e_panel, e_bulk, e_start;
+    const bool two = side != nullptr && nb > 2 && hipEventCreateWithFlags(e_panel.put(), hipEventDisableTiming) == hipSuccess &&
+                     hipEventCreateWithFlags(e_bulk.put(), hipEventDisableTiming) == hipSuccess &&
+                     hipEventCreateWithFlags(e_start.put(), hipEventDisableTiming) == hipSuccess;
     hipLaunchKernelGGL(k_gj_first, dim3(1), dim3(256), 0, s, Np, A, P, P + 4096, singular);
     if (two) {                                            // whatever `side` did before must not overtake the matrix's producers on s
         (void)hipEventRecord(e_start, s);
@@ -375,12 +376,7 @@ void dense_gj_inverse(hipStream_t s, hipStream_t side, int Np, double* A, double
         hipLaunchKernelGGL(k_gj_update, dim3(nb * nb), dim3(256), 0, s, Np, p, 1, A, cur, R, CpT, nxt, nxt + 4096, singular);
         (void)hipEventRecord(e_bulk, side);
     }
-    if (two) {
-        (void)hipStreamWaitEvent(s, e_bulk, 0);
-        (void)hipEventDestroy(e_panel);
-        (void)hipEventDestroy(e_bulk);
-        (void)hipEventDestroy(e_start);
-    }
+    if (two) (void)hipStreamWaitEvent(s, e_bulk, 0);
 }
 
 }  // namespace sns

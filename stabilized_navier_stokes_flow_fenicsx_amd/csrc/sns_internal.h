@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "sns.h"
+#include "sns_devbuf.h"
 
 namespace sns {
 
@@ -55,52 +56,53 @@ void build_coarse_from_agg(const HostPattern& F, int32_t n_owned_fine, const std
                            int32_t nc_owned, int32_t nc_total, HostAggregation& A);
 
 // ---- device-side level of the operator hierarchy ----------------------------
+// (move-only: every device array is owned by the level, csrc/sns_devbuf.h)
 struct Level {
     int32_t n = 0;                       // local block rows (owned + ghost on level 0)
     int32_t n_owned = 0;                 // rows that are solved for (== n when serial)
     int64_t n_global = 0;                // rows of this level over all ranks (a replicated level: its own rows)
     int64_t nnzb = 0;
-    int32_t *rowptr = nullptr, *colind = nullptr, *diag = nullptr;
-    double* vals = nullptr;              // nnzb*16, block row-major
-    double* dinv = nullptr;              // n*16
-    float* vals32 = nullptr;             // fp32 copy of vals for the preconditioner passes (amg_f32_matrix)
-    void* vals16 = nullptr;              // fp16 copy, row-scaled (amg_f32_matrix = 2): 4 halfs per block row
-    float* scale16 = nullptr;            // its scales, one per dof row
-    float* dinv32 = nullptr;             // fp32 copy of dinv for the low-precision Jacobi sweeps
+    DevBuf<int32_t> rowptr, colind, diag;
+    DevBuf<double> vals;                 // nnzb*16, block row-major
+    DevBuf<double> dinv;                 // n*16
+    DevBuf<float> vals32;                // fp32 copy of vals for the preconditioner passes (amg_f32_matrix)
+    DevBuf<void> vals16;                 // fp16 copy, row-scaled (amg_f32_matrix = 2): 4 halfs per block row
+    DevBuf<float> scale16;               // its scales, one per dof row
+    DevBuf<float> dinv32;                // fp32 copy of dinv for the low-precision Jacobi sweeps
     // to the next coarser level
     int32_t nc = 0;
-    int32_t* agg = nullptr;              // n
-    int32_t *m_ptr = nullptr, *m_idx = nullptr;
-    int64_t* r_ptr = nullptr;
-    int32_t* r_idx = nullptr;
-    uint8_t* free_mask = nullptr;        // 4*n: 1 where dof takes part in transfer (level 0: !bc), else all 1
+    DevBuf<int32_t> agg;                 // n
+    DevBuf<int32_t> m_ptr, m_idx;
+    DevBuf<int64_t> r_ptr;
+    DevBuf<int32_t> r_idx;
+    DevBuf<uint8_t> free_mask;           // 4*n: 1 where dof takes part in transfer (level 0: !bc), else all 1
     // M = A P of this level for the fused first post-smoothing sweep (k_post_lp): pattern + gather lists (symbolic, once),
     // values per numeric setup straight into the level's low-precision format (k_lp_copies16 / k_ap_cvt32)
     int64_t ap_nnz = 0;
-    int32_t *ap_rowptr = nullptr, *ap_colind = nullptr, *ap_ptr = nullptr, *ap_idx = nullptr;
-    int32_t* ap_colind_rep = nullptr;    // partitioned level right above the replicated tail's source: M's columns in the ids of the replicated level
-    uint64_t* ap_nib = nullptr;          // per row: nibble j = the row-local M slot of block j (15: none); ~0 = row too long for k_lp_copies16's registers
-    float* ap_vals32 = nullptr;
-    void* ap_vals16 = nullptr;
-    float* ap_scale16 = nullptr;
+    DevBuf<int32_t> ap_rowptr, ap_colind, ap_ptr, ap_idx;
+    DevBuf<int32_t> ap_colind_rep;       // partitioned level right above the replicated tail's source: M's columns in the ids of the replicated level
+    DevBuf<uint64_t> ap_nib;             // per row: nibble j = the row-local M slot of block j (15: none); ~0 = row too long for k_lp_copies16's registers
+    DevBuf<float> ap_vals32;
+    DevBuf<void> ap_vals16;
+    DevBuf<float> ap_scale16;
     // aggregate-block Jacobi smoother (amg_block_smooth, csrc/sns_block.hip): member rows of every aggregate padded to 8 slots
     // (-1: none), built with the hierarchy; the aggregates' inverse diagonal blocks (fp32, 1024 floats each) per numeric setup
-    int32_t* blk_rows = nullptr;
-    int32_t* blk_of = nullptr;           // node -> its smoother block (-1: ghost node)
+    DevBuf<int32_t> blk_rows;
+    DevBuf<int32_t> blk_of;              // node -> its smoother block (-1: ghost node)
     int32_t n_blk = 0;                   // smoother blocks (= nc, plus one per aggregate of more than 8 nodes)
-    void* binv32 = nullptr;              // (fp32 blocks, or fp16 + row scales: the format of the level's matrix copy, binv_fmt)
+    DevBuf<void> binv32;                 // (fp32 blocks, or fp16 + row scales: the format of the level's matrix copy, binv_fmt)
     int binv_fmt = 0;
     // work vectors (4*n doubles)
-    double *x = nullptr, *b = nullptr, *r = nullptr;
-    double* xg = nullptr;                // distributed runs: copy of the iterate whose ghost tail is exchanged
+    DevBuf<double> x, b, r;
+    DevBuf<double> xg;                   // distributed runs: copy of the iterate whose ghost tail is exchanged
     // coarsest level: dense inverse (4n x 4n), row-major
-    double* dense_inv = nullptr;
+    DevBuf<double> dense_inv;
     // ... or, for a coarsest level of up to amg_dense_rows rows, the blocked Gauss-Jordan inverse (csrc/sns_dense.hip): the
     // Np x Np fp64 matrix the elimination works in (Np = 4n rounded up to a multiple of 64), its workspace, and the finished
     // inverse as fp32 (leading dimension Np) for the cycle's matvec
     int dense_np = 0;
-    double *dense_gj = nullptr, *dense_work = nullptr;
-    float* dense_x32 = nullptr;
+    DevBuf<double> dense_gj, dense_work;
+    DevBuf<float> dense_x32;
     // block-Jacobi damping actually used on this level (<= amg_omega, limited by 4/(3 |lambda|max(Dinv A)))
     double omega = 0.8;
     double lambda_max = 0.0;

@@ -1,5 +1,5 @@
 // Krylov methods on the device (BiCGStab with device-resident scalars, TFQMR, FGMRES) and the solve driver with the damping retry.
-// (round 5: one of the four translation units csrc/sns_api.hip was split into; shared internals in csrc/sns_ctx.h)
+// (shared internals in csrc/sns_ctx.h)
 #include "sns_ctx.h"
 
 namespace sns {
@@ -99,7 +99,7 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
     double* sc = h->d_scal + 128;                         // device scalar block of this solver
     double* red = h->d_scal + 144;                        // reduction results
     double* hpin = h->h_scal + 512;                       // pinned landing zone of (rr, flags)
-    if (!h->ev_it) HIP_TRY(hipEventCreateWithFlags(&h->ev_it, hipEventDisableTiming));
+    if (!h->ev_it) HIP_TRY(hipEventCreateWithFlags(h->ev_it.put(), hipEventDisableTiming));
     double bnorm, rn;
     SNS_TRY(norm2(h, b, &bnorm));
     SNS_TRY(op_residual(h, x, b, r));
@@ -295,10 +295,9 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
     const int64_t nd = nred_of(h), ld = ld_of(h);
     const int g = vec_grid(nd);
     if (h->gm_m != m) {
-        if (h->gm_V) { (void)hipFree(h->gm_V); (void)hipFree(h->gm_Z); (void)hipFree(h->d_h); }
-        SNS_TRY(dev_alloc(&h->gm_V, (size_t)(m + 1) * ld));
-        SNS_TRY(dev_alloc(&h->gm_Z, (size_t)m * ld));
-        SNS_TRY(dev_alloc(&h->d_h, (size_t)2 * (m + 16)));
+        SNS_TRY(h->gm_V.alloc((size_t)(m + 1) * ld));
+        SNS_TRY(h->gm_Z.alloc((size_t)m * ld));
+        SNS_TRY(h->d_h.alloc((size_t)2 * (m + 16)));
         HIP_TRY(hipMemset(h->gm_V, 0, (size_t)(m + 1) * ld * sizeof(double)));
         HIP_TRY(hipMemset(h->gm_Z, 0, (size_t)m * ld * sizeof(double)));
         h->gm_m = m;

@@ -367,21 +367,6 @@ __global__ __launch_bounds__(LOC_TPB) void k_eval_p1(int32_t nq, int32_t n_tets,
     for (int c = 0; c < NC; ++c) out[NC * (int64_t)q + c] = acc[c];
 }
 
-// device scratch of one call, freed on every return path
-struct LocScratch {
-    std::vector<void*> ptrs;
-    template <class T>
-    hipError_t alloc(T** p, size_t count) {
-        *p = nullptr;
-        const hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back((void*)*p);
-        return e;
-    }
-    ~LocScratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-};
-
 // the host's grid (interpolate.py): ext = max(hi - lo, 1e-300); res = max(1, round((E / 6) ** (1/3) * ext / ext.max() *
 // (ext.max() ** 3 / ext.prod()) ** (1/3))); h = ext / res -- the same operations in the same order (numpy's pow is libm's pow)
 void host_grid(const double lo[3], const double hi[3], int64_t n_tets, Grid& G, int64_t& ncell) {
@@ -414,6 +399,10 @@ void host_grid(const double lo[3], const double hi[3], int64_t n_tets, Grid& G, 
             return SNS_E_HIP;                                                                      \
         }                                                                                          \
     } while (0)
+#define LOC_ALLOC(buf, count)                                                                      \
+    do {                                                                                           \
+        if ((buf).alloc(count) != SNS_OK) return SNS_E_HIP;                                        \
+    } while (0)
 
 extern "C" int sns_locate_points(int32_t n_nodes, int64_t n_tets, const double* pts_dev, const int32_t* tets_dev,
                                  int64_t n_query, const double* query_dev, double padding, int32_t* tet_out_dev,
@@ -436,11 +425,10 @@ extern "C" int sns_locate_points(int32_t n_nodes, int64_t n_tets, const double* 
     hipStream_t s = (hipStream_t)hip_stream;
     const int32_t E = (int32_t)n_tets, nq = (int32_t)n_query;
     const int4* tets4 = (const int4*)tets_dev;
-    LocScratch S;
     // grid: exact min / max per block on the device, the rest on the host
     const int nbb = (int)std::min<int64_t>(BOUNDS_BLOCKS, (n_nodes + LOC_TPB - 1) / LOC_TPB);
-    double* d_part;
-    LOC_TRY(S.alloc(&d_part, 6 * (size_t)nbb));
+    DevBuf<double> d_part;                              // (device scratch of the call, freed on every return path)
+    LOC_ALLOC(d_part, 6 * (size_t)nbb);
     hipLaunchKernelGGL(k_loc_bounds, dim3(nbb), dim3(LOC_TPB), 0, s, n_nodes, pts_dev, d_part);
     std::vector<double> part(6 * (size_t)nbb);
     LOC_TRY(hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -465,13 +453,13 @@ extern "C" int sns_locate_points(int32_t n_nodes, int64_t n_tets, const double* 
     }
     const int32_t nc = (int32_t)ncell;
     // build: count, scan, fill, sort
-    int32_t *d_cnt, *d_bad;
-    int64_t *d_off, *d_bsum;
+    DevBuf<int32_t> d_cnt, d_bad;
+    DevBuf<int64_t> d_off, d_bsum;
     const int32_t nsb = (nc + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    LOC_TRY(S.alloc(&d_cnt, (size_t)nc));
-    LOC_TRY(S.alloc(&d_bad, 1));
-    LOC_TRY(S.alloc(&d_off, (size_t)nc + 1));
-    LOC_TRY(S.alloc(&d_bsum, (size_t)nsb));
+    LOC_ALLOC(d_cnt, (size_t)nc);
+    LOC_ALLOC(d_bad, 1);
+    LOC_ALLOC(d_off, (size_t)nc + 1);
+    LOC_ALLOC(d_bsum, (size_t)nsb);
     LOC_TRY(hipMemsetAsync(d_cnt, 0, (size_t)nc * sizeof(int32_t), s));
     LOC_TRY(hipMemsetAsync(d_bad, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(k_loc_count, dim3(loc_blocks(E)), dim3(LOC_TPB), 0, s, E, n_nodes, G, pts_dev, tets4, d_cnt, d_bad);
@@ -488,11 +476,11 @@ extern "C" int sns_locate_points(int32_t n_nodes, int64_t n_tets, const double* 
         set_error("sns_locate_points: a tet names a node outside [0, n_nodes)");
         return SNS_E_MESH;
     }
-    int32_t *d_raw, *d_list, *d_miss, *d_nmiss;
-    LOC_TRY(S.alloc(&d_raw, (size_t)total));
-    LOC_TRY(S.alloc(&d_list, (size_t)total));
-    LOC_TRY(S.alloc(&d_miss, (size_t)nq));
-    LOC_TRY(S.alloc(&d_nmiss, 1));
+    DevBuf<int32_t> d_raw, d_list, d_miss, d_nmiss;
+    LOC_ALLOC(d_raw, (size_t)total);
+    LOC_ALLOC(d_list, (size_t)total);
+    LOC_ALLOC(d_miss, (size_t)nq);
+    LOC_ALLOC(d_nmiss, 1);
     LOC_TRY(hipMemsetAsync(d_cnt, 0, (size_t)nc * sizeof(int32_t), s));
     LOC_TRY(hipMemsetAsync(d_nmiss, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(k_loc_fill, dim3(loc_blocks(E)), dim3(LOC_TPB), 0, s, E, G, pts_dev, tets4, d_off, d_cnt, d_raw);
@@ -505,8 +493,8 @@ extern "C" int sns_locate_points(int32_t n_nodes, int64_t n_tets, const double* 
     LOC_TRY(hipMemcpyAsync(&n_miss, d_nmiss, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     LOC_TRY(hipStreamSynchronize(s));
     if (n_miss > 0) {
-        double* d_cen;
-        LOC_TRY(S.alloc(&d_cen, 3 * (size_t)E));
+        DevBuf<double> d_cen;
+        LOC_ALLOC(d_cen, 3 * (size_t)E);
         hipLaunchKernelGGL(k_loc_centroids, dim3(loc_blocks(E)), dim3(LOC_TPB), 0, s, E, pts_dev, tets4, d_cen);
         hipLaunchKernelGGL(k_loc_nearest, dim3(n_miss), dim3(LOC_TPB), 0, s, E, d_miss, d_cen, pts_dev, tets4, query_dev,
                            tet_out_dev, lam_out_dev);

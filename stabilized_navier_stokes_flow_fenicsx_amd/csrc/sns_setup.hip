@@ -1,15 +1,15 @@
 // Setup side of the C-ABI layer: the symbolic AMG hierarchy (aggregation, halo plans per level, replicated tail), the assembly
 // driver, the spectral estimates of the smoother damping and the numeric setup of the preconditioner.
-// (round 5: one of the four translation units csrc/sns_api.hip was split into; shared internals in csrc/sns_ctx.h)
+// (shared internals in csrc/sns_ctx.h)
 #include "sns_ctx.h"
 
 namespace sns {
 
 int alloc_level_vectors(Level& L) {
     const size_t nd = 4 * (size_t)L.n;
-    SNS_TRY(dev_alloc(&L.x, nd));
-    SNS_TRY(dev_alloc(&L.b, nd));
-    SNS_TRY(dev_alloc(&L.r, nd));
+    SNS_TRY(L.x.alloc(nd));
+    SNS_TRY(L.b.alloc(nd));
+    SNS_TRY(L.r.alloc(nd));
     HIP_TRY(hipMemset(L.x, 0, nd * sizeof(double)));
     HIP_TRY(hipMemset(L.b, 0, nd * sizeof(double)));
     HIP_TRY(hipMemset(L.r, 0, nd * sizeof(double)));
@@ -17,16 +17,16 @@ int alloc_level_vectors(Level& L) {
 }
 
 
-int upload_pattern(Level& L, const HostPattern& P, int32_t** slot_row, hipStream_t s) {
+int upload_pattern(Level& L, const HostPattern& P, DevBuf<int32_t>& slot_row, hipStream_t s) {
     L.n = P.n;
     L.nnzb = P.nnzb;
-    SNS_TRY(dev_upload(&L.rowptr, P.rowptr, s));
-    SNS_TRY(dev_upload(&L.colind, P.colind, s));
-    SNS_TRY(dev_upload(&L.diag, P.diag, s));
-    SNS_TRY(dev_alloc(&L.vals, (size_t)P.nnzb * 16));
-    SNS_TRY(dev_alloc(&L.dinv, (size_t)P.n * 16));
-    SNS_TRY(dev_alloc(slot_row, (size_t)P.nnzb));
-    hipLaunchKernelGGL(k_fill_slot_row, dim3((P.n + 255) / 256), dim3(256), 0, s, P.n, L.rowptr, *slot_row);
+    SNS_TRY(L.rowptr.upload(P.rowptr));
+    SNS_TRY(L.colind.upload(P.colind));
+    SNS_TRY(L.diag.upload(P.diag));
+    SNS_TRY(L.vals.alloc((size_t)P.nnzb * 16));
+    SNS_TRY(L.dinv.alloc((size_t)P.n * 16));
+    SNS_TRY(slot_row.alloc((size_t)P.nnzb));
+    hipLaunchKernelGGL(k_fill_slot_row, dim3((P.n + 255) / 256), dim3(256), 0, s, P.n, L.rowptr, slot_row);
     return SNS_OK;
 }
 
@@ -48,22 +48,16 @@ int global_sum(sns_ctx* h, double* v, int count) {
 int host_allgather(sns_ctx* h, const std::vector<double>& mine, std::vector<double>& all) {
     Comm* c = h->comm.get();
     const size_t len = mine.size();
-    double *ds = nullptr, *dr = nullptr;
-    auto body = [&]() -> int {
-        SNS_TRY(dev_alloc(&ds, std::max<size_t>(1, len)));
-        SNS_TRY(dev_alloc(&dr, std::max<size_t>(1, len * c->nranks)));
-        HIP_TRY(hipMemcpy(ds, mine.data(), len * sizeof(double), hipMemcpyHostToDevice));
-        SNS_TRY(comm_allgather(c, ds, dr, (int)len, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        SNS_TRY(peer_check(c));
-        all.resize(len * c->nranks);
-        HIP_TRY(hipMemcpy(all.data(), dr, all.size() * sizeof(double), hipMemcpyDeviceToHost));
-        return SNS_OK;
-    };
-    const int rc = body();
-    if (ds) (void)hipFree(ds);
-    if (dr) (void)hipFree(dr);
-    return rc;
+    DevBuf<double> ds, dr;
+    SNS_TRY(ds.alloc(len));
+    SNS_TRY(dr.alloc(len * c->nranks));
+    HIP_TRY(hipMemcpy(ds, mine.data(), len * sizeof(double), hipMemcpyHostToDevice));
+    SNS_TRY(comm_allgather(c, ds, dr, (int)len, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    SNS_TRY(peer_check(c));
+    all.resize(len * c->nranks);
+    HIP_TRY(hipMemcpy(all.data(), dr, all.size() * sizeof(double), hipMemcpyDeviceToHost));
+    return SNS_OK;
 }
 
 
@@ -122,18 +116,18 @@ int connect_plan(sns_ctx* h, Plan& p) {
 
 int append_level(sns_ctx* h, const HostPattern& P, int32_t n_owned, bool with_xg) {
     h->levels.emplace_back();
-    h->slot_row.push_back(nullptr);
-    h->empty_c.push_back(nullptr);
-    h->pong.push_back(nullptr);
+    h->slot_row.emplace_back();
+    h->empty_c.emplace_back();
+    h->pong.emplace_back();
     Level& C = h->levels.back();
-    SNS_TRY(upload_pattern(C, P, &h->slot_row.back(), h->stream));
+    SNS_TRY(upload_pattern(C, P, h->slot_row.back(), h->stream));
     C.n_owned = n_owned;
     C.n_global = n_owned;                        // (append_level serves the replicated tail: every rank holds all rows)
     SNS_TRY(alloc_level_vectors(C));
-    SNS_TRY(dev_alloc(&h->pong.back(), 4 * (size_t)std::max(1, C.n)));
+    SNS_TRY(h->pong.back().alloc(4 * (size_t)std::max(1, C.n)));
     HIP_TRY(hipMemset(h->pong.back(), 0, 4 * (size_t)std::max(1, C.n) * sizeof(double)));
     if (with_xg) {
-        SNS_TRY(dev_alloc(&C.xg, 4 * (size_t)std::max(1, C.n)));
+        SNS_TRY(C.xg.alloc(4 * (size_t)std::max(1, C.n)));
         HIP_TRY(hipMemset(C.xg, 0, 4 * (size_t)std::max(1, C.n) * sizeof(double)));
     }
     return SNS_OK;
@@ -164,8 +158,8 @@ int upload_block_rows(sns_ctx* h, int l, Level& L, const std::vector<int32_t>& m
     }
     if (rows.empty()) rows.assign(8, -1);
     L.n_blk = nb;
-    SNS_TRY(dev_upload(&L.blk_rows, rows, h->stream));
-    SNS_TRY(dev_upload(&L.blk_of, of, h->stream));
+    SNS_TRY(L.blk_rows.upload(rows));
+    SNS_TRY(L.blk_of.upload(of));
     return SNS_OK;
 }
 
@@ -182,11 +176,11 @@ int upload_ap(sns_ctx* h, Level& L, const HostPattern& fine, int32_t n_rows, con
         return SNS_E_MESH;
     }
     L.ap_nnz = M.nnz;
-    SNS_TRY(dev_upload(&L.ap_rowptr, M.rowptr, h->stream));
-    SNS_TRY(dev_upload(&L.ap_colind, M.colind, h->stream));
-    SNS_TRY(dev_upload(&L.ap_ptr, M.ap_ptr, h->stream));
-    SNS_TRY(dev_upload(&L.ap_idx, M.ap_idx, h->stream));
-    SNS_TRY(dev_upload(&L.ap_nib, M.nib, h->stream));
+    SNS_TRY(L.ap_rowptr.upload(M.rowptr));
+    SNS_TRY(L.ap_colind.upload(M.colind));
+    SNS_TRY(L.ap_ptr.upload(M.ap_ptr));
+    SNS_TRY(L.ap_idx.upload(M.ap_idx));
+    SNS_TRY(L.ap_nib.upload(M.nib));
     return SNS_OK;
 }
 
@@ -199,14 +193,14 @@ int alloc_coarsest_solver(sns_ctx* h, Level& last) {
     const policy::CoarsestKind ck = policy::coarsest_kind(o, last.n);
     if (ck == policy::COARSEST_SMALL_INVERSE) {
         const size_t N = 4 * (size_t)last.n;
-        SNS_TRY(dev_alloc(&last.dense_inv, N * N));
-        SNS_TRY(dev_alloc(&h->d_piv, N));
+        SNS_TRY(last.dense_inv.alloc(N * N));
+        SNS_TRY(h->d_piv.alloc(N));
     } else if (ck == policy::COARSEST_BLOCKED_INVERSE) {
         const int Np = (4 * last.n + 63) / 64 * 64;
         last.dense_np = Np;
-        SNS_TRY(dev_alloc(&last.dense_gj, (size_t)Np * Np));
-        SNS_TRY(dev_alloc(&last.dense_work, dense_gj_work_doubles(Np)));
-        SNS_TRY(dev_alloc(&last.dense_x32, (size_t)Np * Np));
+        SNS_TRY(last.dense_gj.alloc((size_t)Np * Np));
+        SNS_TRY(last.dense_work.alloc(dense_gj_work_doubles(Np)));
+        SNS_TRY(last.dense_x32.alloc((size_t)Np * Np));
     }
     return SNS_OK;
 }
@@ -296,8 +290,8 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
         // window transports: the right-hand sides go straight to their rows of the replicated level (comm_allgatherv) ...
         std::vector<int64_t> doff((size_t)nr), dcnt((size_t)nr);
         for (int r = 0; r < nr; ++r) { doff[(size_t)r] = 4 * off[r]; dcnt[(size_t)r] = 4 * (int64_t)cnt[r]; }
-        SNS_TRY(dev_upload(&h->rep_doff, doff, h->stream));
-        SNS_TRY(dev_upload(&h->rep_dcnt, dcnt, h->stream));
+        SNS_TRY(h->rep_doff.upload(doff));
+        SNS_TRY(h->rep_dcnt.upload(dcnt));
         // ... and the level above the source reads the coarse solution of its fused correction + post-sweep straight from the
         // replicated solution: the columns of its M = A P (local ids of level R: owned, then ghosts) in the replicated level's ids
         Level& A = h->levels[R - 1];
@@ -313,18 +307,18 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
                     j = (int32_t)off[g_own[q]] + g_gid[q];
                 }
             }
-            SNS_TRY(dev_upload(&A.ap_colind_rep, col, h->stream));
+            SNS_TRY(A.ap_colind_rep.upload(col));
         }
     }
     SNS_TRY(append_level(h, G, NG, false));
     h->ghost_own.emplace_back();
     h->ghost_gid.emplace_back();
-    SNS_TRY(dev_upload(&h->rep_valmap, valmap, h->stream));
-    SNS_TRY(dev_upload(&h->rep_rowmap, rowmap, h->stream));
-    SNS_TRY(dev_alloc(&h->rep_vsend, (size_t)maxnz * 16));
-    SNS_TRY(dev_alloc(&h->rep_vrecv, (size_t)maxnz * 16 * nr));
-    SNS_TRY(dev_alloc(&h->rep_bsend, (size_t)maxn * 4));
-    SNS_TRY(dev_alloc(&h->rep_brecv, (size_t)maxn * 4 * nr));
+    SNS_TRY(h->rep_valmap.upload(valmap));
+    SNS_TRY(h->rep_rowmap.upload(rowmap));
+    SNS_TRY(h->rep_vsend.alloc((size_t)maxnz * 16));
+    SNS_TRY(h->rep_vrecv.alloc((size_t)maxnz * 16 * nr));
+    SNS_TRY(h->rep_bsend.alloc((size_t)maxn * 4));
+    SNS_TRY(h->rep_brecv.alloc((size_t)maxn * 4 * nr));
     HIP_TRY(hipMemset(h->rep_vsend, 0, (size_t)maxnz * 16 * sizeof(double)));
     HIP_TRY(hipMemset(h->rep_bsend, 0, (size_t)maxn * 4 * sizeof(double)));
     // the replicated level's node coordinates (all-gathered like its pattern), so that its aggregation sees shapes, not only numbers
@@ -371,11 +365,11 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
         {
             Level& L = h->levels[l];
             L.nc = nc;
-            SNS_TRY(dev_upload(&L.agg, A.agg, h->stream));
-            SNS_TRY(dev_upload(&L.m_ptr, A.m_ptr, h->stream));
-            SNS_TRY(dev_upload(&L.m_idx, A.m_idx, h->stream));
-            SNS_TRY(dev_upload(&L.r_ptr, A.r_ptr, h->stream));
-            SNS_TRY(dev_upload(&L.r_idx, A.r_idx, h->stream));
+            SNS_TRY(L.agg.upload(A.agg));
+            SNS_TRY(L.m_ptr.upload(A.m_ptr));
+            SNS_TRY(L.m_idx.upload(A.m_idx));
+            SNS_TRY(L.r_ptr.upload(A.r_ptr));
+            SNS_TRY(L.r_idx.upload(A.r_idx));
             SNS_TRY(upload_block_rows(h, l, L, A.m_ptr, A.m_idx, nc));
             SNS_TRY(upload_ap(h, L, curp, n_own, A.agg));
         }
@@ -395,7 +389,7 @@ int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_o
 // over the owned nodes -- amg_aggregation = 1: the strength copied to the host and sns_host.cpp's matcher; 2: the same map built on
 // the device (csrc/sns_aggregate.hip), only the map copied; 3: the geometric map of amg_aggregation = 0 (`pts`: the node
 // coordinates or null, as 0 passes them), re-matched by strength on the device only where it cuts a dominant coupling
-// (h->fine_rematched_local).  The fp32 strength and the device scratch are freed again.
+// (h->fine_rematched_local).  The fp32 strength and the device scratch are local.
 static int aggregate_fine_by_strength(sns_ctx* h, const HostPattern& fine, const double* pts, std::vector<int32_t>& agg, int32_t& nc) {
     const Level& L = h->levels[0];
     if (!h->has_matrix) {
@@ -410,20 +404,17 @@ static int aggregate_fine_by_strength(sns_ctx* h, const HostPattern& fine, const
         return aggregate_hybrid_device(h, max_agg, g, ng, agg, nc, h->fine_rematched_local);
     }
     if (h->opt.amg_aggregation == 2) return aggregate_strength_device(h, max_agg, agg, nc);
-    float* s_dev = nullptr;
-    double* scale = nullptr;
-    SNS_TRY(dev_alloc(&s_dev, (size_t)L.nnzb));
-    int rc = dev_alloc(&scale, 4 * (size_t)L.n);
-    if (rc == SNS_OK) rc = compute_strength(h, s_dev, scale);
+    DevBuf<float> s_dev;
+    DevBuf<double> scale;
+    SNS_TRY(s_dev.alloc((size_t)L.nnzb));
+    SNS_TRY(scale.alloc(4 * (size_t)L.n));
+    SNS_TRY(compute_strength(h, s_dev, scale));
     std::vector<float> s((size_t)L.nnzb);
-    if (rc == SNS_OK && L.nnzb > 0 && hipMemcpyAsync(s.data(), s_dev, s.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
+    if (L.nnzb > 0 && hipMemcpyAsync(s.data(), s_dev, s.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
         set_error("amg_aggregation = 1: copy of the strength to the host failed");
-        rc = SNS_E_HIP;
+        return SNS_E_HIP;
     }
-    if (rc == SNS_OK && hipStreamSynchronize(h->stream) != hipSuccess) { set_error("amg_aggregation = 1: strength kernel failed"); rc = SNS_E_HIP; }
-    (void)hipFree(s_dev);
-    if (scale) (void)hipFree(scale);
-    if (rc != SNS_OK) return rc;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) { set_error("amg_aggregation = 1: strength kernel failed"); return SNS_E_HIP; }
     aggregate_strength(fine, h->n_owned, std::min(h->opt.amg_agg_size, policy::STRENGTH_MAX_AGG), s.data(), agg, nc);
     return SNS_OK;
 }
@@ -452,7 +443,7 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
     h->ghost_own.assign(1, {});
     const int per_rank_coarse = dist ? std::max(1, o.amg_coarse_size / c->nranks) : o.amg_coarse_size;
     if (dist && !h->levels[0].xg) {
-        SNS_TRY(dev_alloc(&h->levels[0].xg, 4 * (size_t)h->levels[0].n));
+        SNS_TRY(h->levels[0].xg.alloc(4 * (size_t)h->levels[0].n));
         HIP_TRY(hipMemset(h->levels[0].xg, 0, 4 * (size_t)h->levels[0].n * sizeof(double)));
     }
     for (int l = 0; l + 1 < o.amg_max_levels; ++l) {
@@ -535,30 +526,30 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
         HostAggregation A;
         build_coarse_from_agg(cur, n_owned, agg, nc_owned, nc_total, A);
         L.nc = nc_owned;
-        SNS_TRY(dev_upload(&L.agg, A.agg, h->stream));
-        SNS_TRY(dev_upload(&L.m_ptr, A.m_ptr, h->stream));
-        SNS_TRY(dev_upload(&L.m_idx, A.m_idx, h->stream));
-        SNS_TRY(dev_upload(&L.r_ptr, A.r_ptr, h->stream));
-        SNS_TRY(dev_upload(&L.r_idx, A.r_idx, h->stream));
+        SNS_TRY(L.agg.upload(A.agg));
+        SNS_TRY(L.m_ptr.upload(A.m_ptr));
+        SNS_TRY(L.m_idx.upload(A.m_idx));
+        SNS_TRY(L.r_ptr.upload(A.r_ptr));
+        SNS_TRY(L.r_idx.upload(A.r_idx));
         SNS_TRY(upload_block_rows(h, l, L, A.m_ptr, A.m_idx, nc_owned));
         // M = A P for the fused first post-smoothing sweep: every level of a serial hierarchy; in a partitioned one the fine
         // level only (its single post-sweep is the exact global sweep; the distributed coarse levels smooth rank-locally)
         // ... and, on the window transports, every partitioned level: the exact-sweep cycle (plan exact) takes the fused post-sweep too
         if (!dist || l == 0 || c->windows()) SNS_TRY(upload_ap(h, L, cur, n_owned, A.agg));
         h->levels.emplace_back();
-        h->slot_row.push_back(nullptr);
-        h->empty_c.push_back(nullptr);
-        h->pong.push_back(nullptr);
+        h->slot_row.emplace_back();
+        h->empty_c.emplace_back();
+        h->pong.emplace_back();
         Level& C = h->levels.back();
         if (&h->levels[l] != &L) { set_error("internal: level storage moved"); return SNS_E_STATE; }
-        SNS_TRY(upload_pattern(C, A.coarse, &h->slot_row.back(), h->stream));
+        SNS_TRY(upload_pattern(C, A.coarse, h->slot_row.back(), h->stream));
         C.n_owned = nc_owned;
         C.n_global = (int64_t)prog[1];
         SNS_TRY(alloc_level_vectors(C));
-        SNS_TRY(dev_alloc(&h->pong.back(), 4 * (size_t)C.n));
+        SNS_TRY(h->pong.back().alloc(4 * (size_t)C.n));
         HIP_TRY(hipMemset(h->pong.back(), 0, 4 * (size_t)C.n * sizeof(double)));
         if (dist) {
-            SNS_TRY(dev_alloc(&C.xg, 4 * (size_t)C.n));
+            SNS_TRY(C.xg.alloc(4 * (size_t)C.n));
             HIP_TRY(hipMemset(C.xg, 0, 4 * (size_t)C.n * sizeof(double)));
             SNS_TRY(check_plan_symmetry(h, cplan, l + 1));
             SNS_TRY(plan_upload(cplan));
@@ -568,7 +559,7 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
         h->ghost_own.push_back(std::move(g_own));
         h->ghost_gid.push_back(std::move(g_gid));
         if (l == 0) {
-            SNS_TRY(dev_alloc(&h->empty_c[0], 4 * (size_t)std::max(1, nc_owned)));
+            SNS_TRY(h->empty_c[0].alloc(4 * (size_t)std::max(1, nc_owned)));
             if (nc_owned > 0)
                 hipLaunchKernelGGL(k_empty_coarse, dim3((unsigned)((4 * (int64_t)nc_owned + 255) / 256)), dim3(256), 0,
                                    h->stream, nc_owned, L.m_ptr, L.m_idx, L.free_mask, h->empty_c[0]);
@@ -611,12 +602,12 @@ int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
                 const auto& go = h->ghost_own.back();
                 const auto& gg = h->ghost_gid.back();
                 for (size_t q = 0; q < go.size(); ++q) cmap[(size_t)last.n_owned + q] = go[q] * h->cg_maxn + gg[q];
-                SNS_TRY(dev_upload(&h->cg_colmap, cmap, h->stream));
-                SNS_TRY(dev_alloc(&h->cg_rows, (size_t)4 * h->cg_maxn * N));
-                SNS_TRY(dev_alloc(&h->cg_full, (size_t)N * N));
-                SNS_TRY(dev_alloc(&h->cg_send, (size_t)4 * h->cg_maxn));
-                SNS_TRY(dev_alloc(&h->cg_recv, (size_t)N));
-                SNS_TRY(dev_alloc(&h->d_piv, (size_t)N));
+                SNS_TRY(h->cg_colmap.upload(cmap));
+                SNS_TRY(h->cg_rows.alloc((size_t)4 * h->cg_maxn * N));
+                SNS_TRY(h->cg_full.alloc((size_t)N * N));
+                SNS_TRY(h->cg_send.alloc((size_t)4 * h->cg_maxn));
+                SNS_TRY(h->cg_recv.alloc((size_t)N));
+                SNS_TRY(h->d_piv.alloc((size_t)N));
             }
         }
     }
@@ -721,7 +712,7 @@ int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matri
                                L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F,
                                TimeTerm(), ViscosityLaw());
         } else {
-            if (!h->Fe) SNS_TRY(dev_alloc(&h->Fe, (size_t)h->E * 16));
+            if (!h->Fe) SNS_TRY(h->Fe.alloc((size_t)h->E * 16));
             hipLaunchKernelGGL(k_residual_tri, dim3((unsigned)((h->E + 255) / 256)), dim3(256), 0, h->stream, h->E,
                                h->tets, h->pts, w, nu, h->Fe);
             hipLaunchKernelGGL(k_gather_residual, dim3(gd), dim3(256), 0, h->stream, h->n_owned, h->nt_ptr, h->nt_idx,
@@ -820,8 +811,8 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         HIP_TRY(hipGetLastError());
         return SNS_OK;
     }
-    if (want_matrix && !h->Ke) SNS_TRY(dev_alloc(&h->Ke, (size_t)h->E * 256));
-    if (!h->Fe) SNS_TRY(dev_alloc(&h->Fe, (size_t)h->E * 16));
+    if (want_matrix && !h->Ke) SNS_TRY(h->Ke.alloc((size_t)h->E * 256));
+    if (!h->Fe) SNS_TRY(h->Fe.alloc((size_t)h->E * 16));
     double* Fe = F ? h->Fe : nullptr;
     if (fast_residual) {
         const unsigned gt = (unsigned)((h->E + 255) / 256);
@@ -941,12 +932,7 @@ int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
         reduce_local(h, g, nred, dst);
         return SNS_OK;
     };
-    if (h->arn_cap < (size_t)(M + 1) * nd) {
-        if (h->arn_V) (void)hipFree(h->arn_V);
-        h->arn_V = nullptr;
-        SNS_TRY(dev_alloc(&h->arn_V, (size_t)(M + 1) * nd));
-        h->arn_cap = (size_t)(M + 1) * nd;
-    }
+    if (h->arn_V.count() < (size_t)(M + 1) * nd) SNS_TRY(h->arn_V.alloc((size_t)(M + 1) * nd));
     double* V = h->arn_V;
     double* y = L.r;
     double* zero = nullptr;
@@ -1076,11 +1062,8 @@ int pc_setup(sns_ctx* h) {
             // the aggregates' inverse diagonal blocks, from the fp64 operator (what the nodal D^-1 is to the point smoother)
             // ... in the format of the level's matrix copy (fp32, or fp16 with row scales: half the bytes of a block sweep's extra stream)
             const int bf = h->opt.amg_f32_matrix == 2 ? 2 : 1;
-            if (L.binv32 && L.binv_fmt != bf) { (void)hipFree(L.binv32); L.binv32 = nullptr; }
-            if (!L.binv32) {
-                uint8_t* pb = nullptr;
-                SNS_TRY(dev_alloc(&pb, binv_bytes_per_block(bf) * (size_t)std::max(1, L.n_blk)));
-                L.binv32 = pb;
+            if (!L.binv32 || L.binv_fmt != bf) {
+                SNS_TRY(L.binv32.alloc(binv_bytes_per_block(bf) * (size_t)std::max(1, L.n_blk)));
                 L.binv_fmt = bf;
             }
             if (L.n_blk > 0)
@@ -1093,41 +1076,37 @@ int pc_setup(sns_ctx* h) {
         L.omega = h->opt.amg_omega * h->damping_backoff;
         const bool direct = l + 1 == nl && nl > 1 && (P.kind == SNS_LEVEL_DIRECT || P.kind == SNS_LEVEL_DIRECT_BLOCKED);   // solved
         if (P.lp_fmt != 0) {
-            if (!L.dinv32) SNS_TRY(dev_alloc(&L.dinv32, (size_t)16 * std::max(1, L.n)));
+            if (!L.dinv32) SNS_TRY(L.dinv32.alloc((size_t)16 * std::max(1, L.n)));
             if (rows > 0)
                 hipLaunchKernelGGL(k_cvt_f32, dim3(vec_grid(16 * (int64_t)rows)), dim3(256), 0, h->stream, 16 * (int64_t)rows,
                                    L.dinv, L.dinv32);
             if (h->opt.amg_f32_matrix == 2) {
                 if (!L.vals16) {
-                    uint2* v16 = nullptr;
-                    SNS_TRY(dev_alloc(&v16, (size_t)L.nnzb * 4));
-                    L.vals16 = v16;
-                    SNS_TRY(dev_alloc(&L.scale16, (size_t)4 * std::max(1, L.n)));
+                    SNS_TRY(L.vals16.alloc(std::max<size_t>(1, (size_t)L.nnzb * 4) * sizeof(uint2)));
+                    SNS_TRY(L.scale16.alloc((size_t)4 * std::max(1, L.n)));
                 }
                 // ONE pass over the level's fp64 operator writes its fp16 copy and, where the level has one, the fp16 copy of
                 // M = A P for the fused post-smoothing sweep (k_lp_copies16)
                 const bool with_m = l + 1 < nl && L.ap_rowptr && L.ap_nib && h->opt.amg_fused_post;
                 if (with_m && !L.ap_vals16) {
-                    uint2* v16 = nullptr;
-                    SNS_TRY(dev_alloc(&v16, (size_t)L.ap_nnz * 4));
-                    L.ap_vals16 = v16;
-                    SNS_TRY(dev_alloc(&L.ap_scale16, (size_t)4 * std::max(1, L.n)));
+                    SNS_TRY(L.ap_vals16.alloc(std::max<size_t>(1, (size_t)L.ap_nnz * 4) * sizeof(uint2)));
+                    SNS_TRY(L.ap_scale16.alloc((size_t)4 * std::max(1, L.n)));
                 }
                 if (rows > 0) {
                     const unsigned grid = (unsigned)((rows + 31) / 32);
                     if (with_m)
                         hipLaunchKernelGGL((k_lp_copies16<1>), dim3(grid), dim3(128), 0, h->stream, rows, L.rowptr, L.vals,
-                                           (uint2*)L.vals16, L.scale16, L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.ap_nib, L.agg,
-                                           L.free_mask, (uint2*)L.ap_vals16, L.ap_scale16);
+                                           (uint2*)L.vals16.get(), L.scale16, L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.ap_nib, L.agg,
+                                           L.free_mask, (uint2*)L.ap_vals16.get(), L.ap_scale16);
                     else
                         hipLaunchKernelGGL((k_lp_copies16<0>), dim3(grid), dim3(128), 0, h->stream, rows, L.rowptr, L.vals,
-                                           (uint2*)L.vals16, L.scale16, (const int32_t*)nullptr, (const int32_t*)nullptr,
+                                           (uint2*)L.vals16.get(), L.scale16, (const int32_t*)nullptr, (const int32_t*)nullptr,
                                            (const int32_t*)nullptr, (const int32_t*)nullptr, (const uint64_t*)nullptr,
                                            (const int32_t*)nullptr, (const uint8_t*)nullptr, (uint2*)nullptr, (float*)nullptr);
                 }
             }
             if (h->opt.amg_f32_matrix != 2) {
-                if (!L.vals32) SNS_TRY(dev_alloc(&L.vals32, (size_t)L.nnzb * 16));
+                if (!L.vals32) SNS_TRY(L.vals32.alloc((size_t)L.nnzb * 16));
                 if (L.nnzb > 0)
                     hipLaunchKernelGGL(k_cvt_f32, dim3(vec_grid(L.nnzb * 16)), dim3(256), 0, h->stream, L.nnzb * 16, L.vals,
                                        L.vals32);
@@ -1183,10 +1162,10 @@ int pc_setup(sns_ctx* h) {
         if (l + 1 < nl && L.ap_rowptr && h->opt.amg_fused_post && P.lp_fmt == 1) {
             // numeric part of M = A P, straight into the level's low-precision format (no fp64 copy of M; fp16: written together
             // with the fp16 copy of A above).  (Allocated on a rank without rows too: the plan asks for it on every rank.)
-            if (!L.ap_vals32) SNS_TRY(dev_alloc(&L.ap_vals32, (size_t)L.ap_nnz * 16));
+            if (!L.ap_vals32) SNS_TRY(L.ap_vals32.alloc((size_t)L.ap_nnz * 16));
             if (rows > 0)
                 hipLaunchKernelGGL(k_ap_cvt32, dim3((unsigned)((4 * (int64_t)rows + 255) / 256)), dim3(256), 0, h->stream, rows,
-                                   L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.vals, L.agg, L.free_mask, (float4*)L.ap_vals32);
+                                   L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.vals, L.agg, L.free_mask, (float4*)L.ap_vals32.get());
         }
         if (l + 1 < nl) {
             Level& C = h->levels[l + 1];
@@ -1218,7 +1197,7 @@ int pc_setup(sns_ctx* h) {
             // (the two-stream schedule of dense_gj_inverse is opt-in: measured, it is SLOWER -- 3.9 against 2.4 ms at N = 1900 --
             // because the bulk update's 900 workgroups fill the chip and the pivot chain's few workgroups queue behind them)
             if (!h->gj_stream && std::getenv("SNS_GJ_TWO_STREAMS") &&
-                hipStreamCreateWithFlags(&h->gj_stream, hipStreamNonBlocking) != hipSuccess) h->gj_stream = nullptr;
+                hipStreamCreateWithFlags(h->gj_stream.put(), hipStreamNonBlocking) != hipSuccess) h->gj_stream.reset();
             dense_gj_inverse(h->stream, h->gj_stream, Np, L.dense_gj, L.dense_work, h->d_sing);
             const int64_t nn = (int64_t)Np * Np;
             hipLaunchKernelGGL(k_dense_to_f32, dim3((unsigned)((nn / 4 + 255) / 256)), dim3(256), 0, h->stream, nn, L.dense_gj,
@@ -1294,10 +1273,10 @@ const char* plan_buffer_missing(const sns_ctx* h) {
 
 int get_vec(sns_ctx* h, size_t k, double** out) {
     while (h->kv.size() <= k) {
-        double* p = nullptr;
-        SNS_TRY(dev_alloc(&p, (size_t)ld_of(h)));
+        DevBuf<double> p;
+        SNS_TRY(p.alloc((size_t)ld_of(h)));
         HIP_TRY(hipMemset(p, 0, (size_t)ld_of(h) * sizeof(double)));
-        h->kv.push_back(p);
+        h->kv.push_back(std::move(p));
     }
     *out = h->kv[k];
     return SNS_OK;

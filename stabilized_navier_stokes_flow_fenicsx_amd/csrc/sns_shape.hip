@@ -420,7 +420,7 @@ int residual_shape_gradient(sns_ctx* h, const double* w, const double* lam, doub
         if (h->n > 0) HIP_TRY(hipMemsetAsync(gX, 0, (size_t)3 * h->n * sizeof(double), h->stream));
         return sync_stream(h);
     }
-    if (!h->Fe) SNS_TRY(dev_alloc(&h->Fe, (size_t)h->E * 16));
+    if (!h->Fe) SNS_TRY(h->Fe.alloc((size_t)h->E * 16));
     const double nu = 1.0 / h->opt.reynolds;
     const unsigned gc = (unsigned)((h->E + 255) / 256);
     if (h->dim == 2)

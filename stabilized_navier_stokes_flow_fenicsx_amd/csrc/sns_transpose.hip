@@ -68,10 +68,10 @@ int transpose_operator(sns_ctx* h) {
     Level& L = h->levels[0];
     if (L.nnzb <= 0) return SNS_OK;
     if (!h->tr_partner) {
-        int32_t* partner = nullptr;
-        int* bad = nullptr;
-        SNS_TRY(dev_alloc(&partner, (size_t)L.nnzb));
-        if (dev_alloc(&bad, 1) != SNS_OK) { (void)hipFree(partner); return SNS_E_HIP; }
+        DevBuf<int32_t> partner;
+        DevBuf<int> bad;
+        SNS_TRY(partner.alloc((size_t)L.nnzb));
+        SNS_TRY(bad.alloc(1));
         int* h_bad = reinterpret_cast<int*>(h->h_scal + 770);
         *h_bad = 0;
         hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), h->stream);
@@ -82,14 +82,12 @@ int transpose_operator(sns_ctx* h) {
         }
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e == hipSuccess) e = hipGetLastError();
-        (void)hipFree(bad);
         if (e != hipSuccess || *h_bad) {
-            (void)hipFree(partner);
             if (e != hipSuccess) { set_error(std::string("sns_transpose_operator: ") + hipGetErrorString(e)); return SNS_E_HIP; }
             set_error("sns_transpose_operator: pattern not structurally symmetric");
             return SNS_E_MESH;
         }
-        h->tr_partner = partner;
+        h->tr_partner = std::move(partner);
     }
     hipLaunchKernelGGL(k_transpose_inplace, dim3((unsigned)((L.nnzb * 16 + 255) / 256)), dim3(256), 0, h->stream, L.nnzb,
                        h->tr_partner, L.vals);
