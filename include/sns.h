@@ -402,6 +402,31 @@ SNS_API int sns_residual_moments(sns_handle h, int form, const double* w_dev, co
  * attached (any transport, also the local-only split; as for the adjoint solves).  Returns after gX_dev is written. */
 SNS_API int sns_residual_shape_gradient(sns_handle h, int form, const double* w_dev, const double* lam_dev,
                                         double* gX_dev);
+/* Gradient recovery and derived fields of the P1 state (the reference has no counterpart).  w always has 4 dofs per node
+ * (u_x, u_y, u_z, p); both dimensions use the same layouts.
+ *   Recovered gradient, node i, component c, direction j = 0..2:
+ *       G[12 i + 3 c + j] = ( sum_{t in cells(i)} |t| d_j w_c|_t ) / ( sum_{t in cells(i)} |t| ),   |t| = |det J| / d!
+ *   the lumped-mass L2 projection of the piecewise-constant gradient onto P1.  Cells of either orientation count with a
+ *   positive weight; the sum runs in the fixed order of the node's cell list, so results are bitwise reproducible; a node of
+ *   no cell gets zeros.  2-D handles: column j = 2 is 0 and row c = 2 is the gradient of whatever the z dofs hold.
+ *   Derived nodal fields from the velocity rows G_u (S, Omega its symmetric and skew parts):
+ *       D[6 i + 0..2] = omega = curl u (2-D with u_z = 0: only k = 2 is non-zero),
+ *       D[6 i + 3] = Q = (|Omega|_F^2 - |S|_F^2) / 2,   D[6 i + 4] = shear rate sqrt(2 S:S),   D[6 i + 5] = div u = tr G_u.
+ *   The shear rate here is the RECOVERED NODAL value, not the per-cell value of sns_element_viscosity.
+ * Either output may be NULL (not both); G_dev: 12*n_local doubles, D_dev: 6*n_local doubles.  D does not depend, bit for bit,
+ * on whether G is stored.  One pass (4 lanes per node walk the node's cells), no atomics; reads w and the mesh only: no option,
+ * time term, viscosity law, form variant or transposed operator matters, and nothing of the handle is written.
+ * SNS_E_ARG: null handle / w, both outputs null.  SNS_E_STATE: a handle with a communicator attached (partitioned recovery
+ * is not built).  Returns after the outputs are written.                         */
+SNS_API int sns_recover_gradient(sns_handle h, const double* w_dev, double* G_dev, double* D_dev);
+/* Zienkiewicz-Zhu error indicator per cell, over the velocity rows only, with e_a = G_{node a} - grad u_h|_t:
+ *       eta2[t] = int_t |G_h(u) - grad u_h|_F^2 = |t| / ((d+1)(d+2)) * ( sum_a |e_a|_F^2 + |sum_a e_a|_F^2 )
+ * (exact: the integrand is the square of a P1 function), and gnorm2[t] = |t| |grad u_h|_t|_F^2, the scale for a relative
+ * indicator.  eta2_dev: n_cells doubles; gnorm2_dev: n_cells doubles or NULL; G_dev: a recovered gradient of w_dev from
+ * sns_recover_gradient, or NULL (then the handle recovers it into a temporary it frees before returning; same bits).
+ * Writes nothing of the handle.  SNS_E_ARG: null handle / w / eta2.  SNS_E_STATE: a handle with a communicator attached (the
+ * indicator would need a halo exchange of G).  Returns after the outputs are written. */
+SNS_API int sns_error_indicator(sns_handle h, const double* w_dev, const double* G_dev, double* eta2_dev, double* gnorm2_dev);
 /* MatMult with the assembled operator: y = A x (halo exchange inside).  Acts on whatever
  * the handle holds: y = A^T x after sns_transpose_operator.                   */
 SNS_API int sns_spmv(sns_handle h, const double* x_dev, double* y_dev);

@@ -611,6 +611,24 @@ int sns_residual_shape_gradient(sns_handle h, int form, const double* w, const d
     return residual_shape_gradient(h, w, lam, gX);
 }
 
+int sns_recover_gradient(sns_handle h, const double* w, double* G, double* D) {
+    if (!h || !w || (!G && !D)) { set_error("sns_recover_gradient: null handle, state or both outputs null"); return SNS_E_ARG; }
+    if (h->comm) {
+        set_error("sns_recover_gradient: not with a communicator attached (partitioned gradient recovery is not built)");
+        return SNS_E_STATE;
+    }
+    return recover_gradient(h, w, G, D);
+}
+
+int sns_error_indicator(sns_handle h, const double* w, const double* G, double* eta2, double* gnorm2) {
+    if (!h || !w || !eta2) { set_error("sns_error_indicator: null handle, state or eta2"); return SNS_E_ARG; }
+    if (h->comm) {
+        set_error("sns_error_indicator: not with a communicator attached (a partitioned indicator needs a halo exchange of G)");
+        return SNS_E_STATE;
+    }
+    return error_indicator(h, w, G, eta2, gnorm2);
+}
+
 int sns_spmv(sns_handle h, const double* x, double* y) {
     if (!h || !x || !y) return SNS_E_ARG;
     if (!h->has_matrix) { set_error("spmv before a matrix was assembled"); return SNS_E_STATE; }

@@ -236,6 +236,10 @@ int compute_strength(sns_ctx* h, float* out, double* scale);
 int transpose_operator(sns_ctx* h);
 // csrc/sns_shape.hip: lam . dR_raw/dX of the NS form by one element pass (uses the element scratch Fe)
 int residual_shape_gradient(sns_ctx* h, const double* w, const double* lam, double* gX);
+// csrc/sns_recover.hip: the nodal gradient of the P1 state recovered by volume-weighted averaging (G and / or the derived
+// fields D), and the Zienkiewicz-Zhu indicator per cell (G null: recovered into a temporary)
+int recover_gradient(sns_ctx* h, const double* w, double* G, double* D);
+int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, double* gnorm2);
 // csrc/sns_aggregate.hip: aggregate_strength's map of the owned nodes, built on the device (amg_aggregation = 2)
 int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc);
 // ... and the hybrid (amg_aggregation = 3): the geometric map g (ng aggregates) re-matched where it cuts a dominant coupling

@@ -328,6 +328,9 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
     wg = _to_global_host(Pf, w)
     out = dict(msh=msh_f, w=wg, u=wg.reshape(-1, 4)[:, :3].copy(), p=wg.reshape(-1, 4)[:, 3].copy(), Re=Re, img_fname=img_fname,
                channel_mesh_size=channel_mesh_size, flowrate_ratio=flowrate_ratio, newton=Pf.last_newton)
+    derived = _derived_fields(Pf, w)
+    if derived is not None:
+        out["derived"] = derived
     Pf.close()
     return out
 
@@ -337,6 +340,7 @@ def navier_stokes_channel_main(argv=None):
     r = solve_NS_flow(argv)
     folder, _ = make_output_folder(r["Re"], r["img_fname"], r["channel_mesh_size"])
     save_navier_stokes_solution(r["u"], r["p"], r["msh"], folder, r["Re"])
+    _write_derived_fields(r.get("derived"), r["msh"], lambda label: os.path.join(folder, f"Re{r['Re']}Channel{label}"))
     write_run_metadata(folder, r["Re"], r["img_fname"], r["flowrate_ratio"], r["channel_mesh_size"], r["msh"])
     if _rank() == 0:
         print(f"Run Time = {time.time() - t0:.2f} sec; output in {folder}", flush=True)
@@ -386,6 +390,7 @@ def duct_stokes_main(argv=None):
         print(f"Linf norm of pressure coefficient vector: {np.abs(p).max()}")
         write_xdmf("StokesDuctPressure", msh, "f", p)
         write_xdmf("StokesDuctVelcoity", msh, "f", u)             # (sic) file name of the reference :255
+    _write_derived_fields(_derived_fields(P, U), msh, lambda label: f"StokesDuct{label}")
     P.close()
     return msh, W, res
 
@@ -503,6 +508,34 @@ def _print_radius_sensitivities(P, msh, w, wg, nu):
     return out
 
 
+DERIVED_FIELD_NAMES = ("vorticity", "q_criterion", "shear_rate")
+
+
+def _derived_fields(P, w):
+    """SNS_DERIVED_FIELDS=1 (opt-in; single-GPU runs): the nodal vorticity, Q-criterion and shear rate of the state ``w`` from
+    the recovered gradient (``FlowProblem.derived_fields``) as a dict name -> host array, and one printed line with the
+    Zienkiewicz-Zhu estimate (``solver.zz_estimate``).  None without the switch: output and stdout stay as they are."""
+    if os.environ.get("SNS_DERIVED_FIELDS", "0") != "1":
+        return None
+    if getattr(P, "part", None) is not None:
+        if _rank() == 0:
+            print("SNS_DERIVED_FIELDS: gradient recovery runs on single-GPU problems only; skipped", flush=True)
+        return None
+    from .solver import zz_estimate
+    D = P.derived_fields(w).cpu().numpy()
+    eta, eta_rel, _ = zz_estimate(P, w)
+    print(f"ZZ error estimate of grad u: eta {eta} eta_rel {eta_rel}", flush=True)
+    return dict(vorticity=D[:, :3].copy(), q_criterion=D[:, 3].copy(), shear_rate=D[:, 4].copy())
+
+
+def _write_derived_fields(fields, msh, path_of):
+    """``path_of(label)`` -> file path without extension for the labels Vorticity, QCriterion, ShearRate."""
+    if fields is None or _rank() != 0:
+        return
+    for label, name in zip(("Vorticity", "QCriterion", "ShearRate"), DERIVED_FIELD_NAMES):
+        write_xdmf(path_of(label), msh, name, fields[name])
+
+
 def _sensitivity():
     return os.environ.get("SNS_SENSITIVITY", "0") == "1"
 
@@ -602,6 +635,7 @@ def dfg_3d_main(argv=None):
         print(f"Coefficient of Drag: {cd}", flush=True)
         write_xdmf("DFGValidationPressureNavierStokes", msh, "Pressure", wg.reshape(-1, 4)[:, 3].copy())
         write_xdmf("DFGValidationVelocityNavierStokes", msh, "Velocity", wg.reshape(-1, 4)[:, :3].copy())
+    _write_derived_fields(_derived_fields(P, w), msh, lambda label: f"DFGValidation{label}NavierStokes")
     if _sensitivity():
         sc = Fn.drag_lift_coefficients(np.ones(3))[0]
         ob = msh.meta["tags"]["obstacle"]

@@ -67,6 +67,39 @@ def boundary_traction_force(mesh: TetMesh, w: np.ndarray, nu: float, tag: int) -
     return np.einsum("fij,fj->i", stress, n_area)
 
 
+def wall_shear_stress(mesh: TetMesh, G, nu: float, tag: int):
+    """Wall shear stress at the nodes of the facets tagged ``tag``: ``(nodes, tau)`` with tau (len(nodes), 3),
+
+        tau_w = 2 nu S n - (n . 2 nu S n) n,     S = sym of the velocity rows of the recovered gradient ``G`` (n, 4, 3)
+
+    (``FlowProblem.recover_gradient``, as numpy), n the unit area-weighted nodal normal of those facets with the orientation of
+    ``boundary_traction_force`` (n = -outward normal of the fluid domain), so that the surface integral of tau_w is the
+    tangential viscous part of that force.  Assumes a CONSTANT viscosity ``nu``: with a viscosity law set, the stress of the
+    law is not what this returns.  3-D; ``mesh2d.wall_shear_stress_2d`` is the counterpart for triangle meshes.  Host numpy."""
+    ids = mesh.find(tag)
+    if len(ids) == 0:
+        return np.zeros(0, np.int64), np.zeros((0, 3))
+    tn = mesh.tets[facet_parent_tets(mesh, ids)].astype(np.int64)
+    fn = mesh.facets[ids].astype(np.int64)
+    P = mesh.points[fn]
+    cr = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    opp = tn.sum(axis=1) - fn.sum(axis=1)
+    sgn = np.sign(np.einsum("fi,fi->f", cr, P[:, 0] - mesh.points[opp]))
+    n_area = -0.5 * cr * sgn[:, None]                        # as in boundary_traction_force
+    return _tangential_stress(mesh.num_nodes, fn, n_area, G, nu)
+
+
+def _tangential_stress(num_nodes: int, fn: np.ndarray, n_area: np.ndarray, G, nu: float):
+    nrm = np.zeros((num_nodes, 3))
+    for a in range(fn.shape[1]):
+        np.add.at(nrm, fn[:, a], n_area)
+    nodes = np.unique(fn)
+    n = nrm[nodes] / np.linalg.norm(nrm[nodes], axis=1)[:, None]
+    U = np.asarray(G, dtype=np.float64).reshape(-1, 4, 3)[nodes, :3, :]
+    t = nu * np.einsum("kij,kj->ki", U + U.transpose(0, 2, 1), n)
+    return nodes, t - np.einsum("ki,ki->k", n, t)[:, None] * n
+
+
 def boundary_traction_gradient(mesh: TetMesh, nu: float, tag: int) -> np.ndarray:
     """d(boundary_traction_force)/dw as a (3, 4 n) array G: the force is linear in the state, ``G @ w`` equals
     ``boundary_traction_force(mesh, w, nu, tag)`` up to the rounding of a reordered sum.  Built from the same arrays

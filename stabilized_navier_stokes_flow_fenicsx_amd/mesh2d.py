@@ -440,6 +440,23 @@ def drag_lift_2d(mesh: TriMesh, w, nu: float, tag: int | None = None, U_mean: fl
     return cd, cl
 
 
+def wall_shear_stress_2d(mesh: TriMesh, G, nu: float, tag: int):
+    """``functionals.wall_shear_stress`` for a triangle mesh: (nodes, tau (len(nodes), 3)) at the nodes of the edges tagged
+    ``tag``, n = -FacetNormal as in ``drag_lift_2d``, length-weighted at the nodes; constant viscosity ``nu``."""
+    from .functionals import _tangential_stress
+    ids = mesh.find(tag)
+    if len(ids) == 0:
+        return np.zeros(0, np.int64), np.zeros((0, 3))
+    tn = mesh.tris[edge_parent_tris(mesh, ids)].astype(np.int64)
+    fn = mesh.facets[ids].astype(np.int64)
+    P = mesh.points[fn]
+    tv = P[:, 1] - P[:, 0]
+    nf = np.stack([tv[:, 1], -tv[:, 0], np.zeros(len(tv))], axis=1)          # |nf| = edge length
+    opp = tn.sum(axis=1) - fn.sum(axis=1)
+    sgn = np.sign(np.einsum("fi,fi->f", nf[:, :2], P[:, 0] - mesh.points[opp]))
+    return _tangential_stress(mesh.num_nodes, fn, -nf * sgn[:, None], G, nu)
+
+
 def drag_lift_2d_gradient(mesh: TriMesh, nu: float, tag: int | None = None, U_mean: float = 0.2, L: float = 0.1) -> np.ndarray:
     """d(C_D, C_L)/dw of ``drag_lift_2d`` as a (2, 4 n) array G, built from the same arrays: both coefficients are linear
     in the state, ``G @ w`` equals ``drag_lift_2d(mesh, w, nu, tag)`` up to the rounding of a reordered sum.  G is affine in

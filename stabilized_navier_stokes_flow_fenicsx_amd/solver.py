@@ -297,6 +297,41 @@ class FlowProblem:
         check(self.lib.sns_residual_shape_gradient(self.h, _FORMS[form], _ptr(w), _ptr(lam), _ptr(out)))
         return out
 
+    def _recover(self, w, want_G: bool, want_D: bool):
+        w = self._vec(w)
+        G = torch.empty(self.n_local, 4, 3, dtype=torch.float64, device=self.device) if want_G else None
+        D = torch.empty(self.n_local, 6, dtype=torch.float64, device=self.device) if want_D else None
+        check(self.lib.sns_recover_gradient(self.h, _ptr(w), _ptr(G), _ptr(D)))
+        return G, D
+
+    def recover_gradient(self, w) -> torch.Tensor:
+        """The gradient of the P1 state recovered at the nodes, a device tensor (n_nodes, 4, 3) (sns_recover_gradient):
+        ``G[i, c, j]`` = the volume-weighted mean over the cells of node i of d_j w_c, c in (u_x, u_y, u_z, p) -- the lumped-mass
+        L2 projection of the piecewise-constant gradient onto P1.  One pass over the node-to-cell lists in a fixed order: no
+        atomics, bitwise reproducible.  2-D problems: column j = 2 is 0.  Reads ``w`` and the mesh only; single-GPU problems."""
+        return self._recover(w, True, False)[0]
+
+    def derived_fields(self, w) -> torch.Tensor:
+        """Nodal fields derived from the recovered velocity gradient, a device tensor (n_nodes, 6): columns 0..2 the vorticity
+        curl u, 3 the Q-criterion (|Omega|^2 - |S|^2) / 2, 4 the shear rate sqrt(2 S:S), 5 div u (S, Omega the symmetric and
+        skew parts of the recovered gradient).  The gradient itself stays in registers and is not stored.  The shear rate is the
+        recovered nodal value, not the per-cell value of ``element_viscosity``."""
+        return self._recover(w, False, True)[1]
+
+    def error_indicator(self, w, G=None):
+        """Zienkiewicz-Zhu indicator per cell over the velocity components (sns_error_indicator): ``(eta2, gnorm2)``, device
+        tensors of length n_cells, eta2[t] = int_t |G_h(u) - grad u_h|^2 (exact) and gnorm2[t] = |t| |grad u_h|^2.  ``G``: the
+        tensor of ``recover_gradient(w)``; None recovers it into a temporary of the handle (same bits)."""
+        w = self._vec(w)
+        if G is not None and (G.dtype != torch.float64 or G.device.type != "cuda" or not G.is_contiguous()
+                              or G.numel() != 12 * self.n_local):
+            raise ValueError(f"expected a contiguous float64 device tensor of {12 * self.n_local} entries")
+        E = len(self.mesh.tris if self.dim == 2 else self.mesh.tets)
+        eta2 = torch.empty(E, dtype=torch.float64, device=self.device)
+        gn2 = torch.empty(E, dtype=torch.float64, device=self.device)
+        check(self.lib.sns_error_indicator(self.h, _ptr(w), _ptr(G), _ptr(eta2), _ptr(gn2)))
+        return eta2, gn2
+
     def spmv(self, x, out=None) -> torch.Tensor:
         x = self._vec(x)
         out = self.zeros() if out is None else self._vec(out)
@@ -847,6 +882,17 @@ def shape_sensitivity(problem: FlowProblem, w, grad_J, dJ_dX_explicit=None):
             e = torch.from_numpy(np.ascontiguousarray(e, dtype=np.float64))
         dJ += e.to(dJ.device).reshape(dJ.shape)
     return dJ, lam, res
+
+
+def zz_estimate(problem: FlowProblem, w):
+    """Global Zienkiewicz-Zhu estimate of the velocity gradient's error at the state ``w``: ``(eta, eta_rel, eta2)`` with
+    eta = sqrt(sum_t eta_t^2), eta_rel = eta / sqrt(sum_t g_t^2 + sum_t eta_t^2) (between 0 and 1) and eta2 the per-cell device
+    tensor of ``problem.error_indicator`` -- the map of where the mesh is too coarse.  Reduced in float64 with torch."""
+    eta2, gn2 = problem.error_indicator(w)
+    s = float(eta2.sum())
+    eta = s ** 0.5
+    den = (float(gn2.sum()) + s) ** 0.5
+    return eta, (eta / den if den > 0.0 else 0.0), eta2
 
 
 def solve_navier_stokes(problem: FlowProblem, w: torch.Tensor, rank: int = 0, continuation=False, ptc_dt0: float = 1.0):
