@@ -523,75 +523,7 @@ int sns_residual_moments(sns_handle h, int form, const double* w, const double* 
     if (form != SNS_FORM_STOKES && form != SNS_FORM_NS) { set_error("bad form"); return SNS_E_ARG; }
     if (form == SNS_FORM_NS && !w) { set_error("NS form needs a state vector"); return SNS_E_ARG; }
     if (h->E == 0) { set_error("empty mesh"); return SNS_E_ARG; }
-    const int64_t ndof = 4 * (int64_t)h->n;
-    if (!w) {                                        // linear form without a state: R_raw(0) = 0, still one collective pass
-        double* z = nullptr;
-        SNS_TRY(get_vec(h, 13, &z));
-        HIP_TRY(hipMemsetAsync(z, 0, ndof * sizeof(double), h->stream));
-        w = z;
-    }
-    // support of the functional behind the owned rows: count, scan, fetch the size, scatter
-    const int64_t nb = (h->E + 255) / 256;
-    if (!h->rm_off) SNS_TRY(h->rm_off.alloc((size_t)nb));
-    hipLaunchKernelGGL(k_support_count, dim3((unsigned)nb), dim3(256), 0, h->stream, h->E, h->tets, h->n_owned, phi, h->rm_off);
-    hipLaunchKernelGGL(k_support_scan, dim3(1), dim3(256), 0, h->stream, nb, h->rm_off, h->d_scal + 100);
-    double total = 0.0;
-    SNS_TRY(fetch(h, h->d_scal + 100, 1, &total));
-    const int64_t nc = (int64_t)total;
-    if (nc > h->rm_cap) {
-        h->rm_cap = 0;
-        SNS_TRY(h->rm_cells.alloc((size_t)4 * nc));
-        SNS_TRY(h->rm_Fe.alloc((size_t)16 * nc));
-        h->rm_cap = nc;
-    }
-    if (nc > 0) {
-        hipLaunchKernelGGL(k_support_scatter, dim3((unsigned)nb), dim3(256), 0, h->stream, h->E, h->tets, h->n_owned, phi,
-                           h->rm_off, h->rm_cells);
-        // element residuals of the compacted cells, by the kernels the residual of the same form uses; no lifting: the
-        // one-lane-per-cell kernels have none, the staged kernel gets an all-zero Dirichlet mask
-        const unsigned g1 = (unsigned)((nc + 255) / 256);
-        const double nu = 1.0 / h->opt.reynolds;
-        if (h->dim == 2) {
-            if (form == SNS_FORM_NS)
-                hipLaunchKernelGGL(k_residual_tri, dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w, nu, h->rm_Fe);
-            else
-                hipLaunchKernelGGL(k_residual_tri_stokes, dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells, h->pts, w,
-                                   h->opt.stokes_viscosity, h->opt.stokes_beta, h->rm_Fe);
-        } else if (form == SNS_FORM_NS && h->fv.is_default()) {
-            dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-                dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
-                    hipLaunchKernelGGL((k_residual_tet<C() != 0, V() == 1, V() == 2>), dim3(g1), dim3(256), 0, h->stream, nc, h->rm_cells,
-                                       h->pts, w, nu, h->rm_Fe, h->tt, h->vl);
-                });
-            });
-        } else {
-            if (!h->rm_nomask) {
-                SNS_TRY(h->rm_nomask.alloc((size_t)ndof));
-                HIP_TRY(hipMemset(h->rm_nomask, 0, (size_t)ndof));
-            }
-            const unsigned ge = (unsigned)((nc + EL_TETS_PER_BLOCK - 1) / EL_TETS_PER_BLOCK);
-            if (form == SNS_FORM_STOKES)
-                hipLaunchKernelGGL((k_element<SNS_FORM_STOKES, false>), dim3(ge), dim3(256), 0, h->stream, nc, h->rm_cells,
-                                   h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe, h->fv, TimeTerm(), ViscosityLaw());
-            else
-                dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-                    dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
-                        hipLaunchKernelGGL((k_element<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(ge), dim3(256), 0, h->stream, nc,
-                                           h->rm_cells, h->pts, w, h->rm_nomask, h->bc_val, nu, 0, (double*)nullptr, h->rm_Fe,
-                                           h->fv, h->tt, h->vl);
-                    });
-                });
-        }
-    }
-    // fixed-order two-stage reduction (grid fixed by the support size), then the handle's all-reduce over the ranks
-    const int gm = (int)std::max<int64_t>(1, std::min<int64_t>((nc + 255) / 256, 2048));
-    hipLaunchKernelGGL(k_moments_partial, dim3(gm), dim3(256), 0, h->stream, nc, h->rm_cells, h->dim + 1, h->n_owned, phi,
-                       h->rm_Fe, h->partial);
-    SNS_TRY(reduce_to(h, gm, 4, h->d_scal + 104));
-    HIP_TRY(hipGetLastError());
-    SNS_TRY(fetch(h, h->d_scal + 104, 4, out));
-    if (h->dim == 2) out[2] = 0.0;
-    return SNS_OK;
+    return residual_moments(h, form, w, phi, out);
 }
 
 int sns_residual_shape_gradient(sns_handle h, int form, const double* w, const double* lam, double* gX) {
@@ -910,7 +842,7 @@ int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, 
     // BDF1: u_t = (u - u^n) / dt;  BDF2: u_t = (3 u - 4 u^n + u^(n-1)) / (2 dt).  d in a workspace vector (copied by
     // sns_set_time_term), the entry state in a buffer of its own (a step that does not converge restores it)
     double *d = nullptr, *w0 = nullptr;
-    SNS_TRY(get_vec(h, 13, &d));
+    SNS_TRY(get_vec(h, VEC_SCRATCH, &d));
     if (!h->tt_w0) SNS_TRY(h->tt_w0.alloc((size_t)ld));
     w0 = h->tt_w0;
     const double sigma = (order == 1 ? 1.0 : 1.5) / dt;

@@ -207,7 +207,7 @@ struct sns_ctx {
 
 // ---- across the translation units ------------------------------------------------------------------------------------------------
 namespace sns {
-// csrc/sns_setup.hip: symbolic hierarchy, assembly driver, numeric setup of the preconditioner
+// csrc/sns_setup.hip: symbolic hierarchy, numeric setup of the preconditioner, workspace vectors
 int alloc_level_vectors(Level& L);
 int upload_pattern(Level& L, const HostPattern& P, DevBuf<int32_t>& slot_row, hipStream_t s);
 int global_sum(sns_ctx* h, double* v, int count);
@@ -217,10 +217,17 @@ int connect_plan(sns_ctx* h, Plan& p);
 int plan_hierarchy(sns_ctx* h);
 const char* plan_buffer_missing(const sns_ctx* h);
 int build_hierarchy(sns_ctx* h, const HostPattern& fine);
+int pc_setup(sns_ctx* h);
+// The workspace vectors h->kv (4*n doubles each, allocated in slot order up to the slot asked for).  VEC_SCRATCH serves the lifting's
+// BC defect, the snapped 2-D Stokes state, sns_time_step's BDF history, the moments' zero state and the zero vector of the three
+// spectral estimates.  What makes the sharing sound: every user writes the whole range it reads before reading it, and none
+// relies on the contents across a call into assemble / the estimates / the moments.
+enum VecSlot { VEC_KRYLOV = 0 /* .. 9, the Krylov methods */, VEC_ARNOLDI_IN = 12, VEC_SCRATCH = 13, VEC_SAVED_GUESS = 14 /* the retry */ };
+int get_vec(sns_ctx* h, size_t k, double** out);
+// csrc/sns_assemble.hip: the assembly driver over policy::plan_assembly, the residual moments on the same element pass
 int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix);
 int timed_assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix);
-int pc_setup(sns_ctx* h);
-int get_vec(sns_ctx* h, size_t k, double** out);
+int residual_moments(sns_ctx* h, int form, const double* w, const double* phi, double out[4]);
 // csrc/sns_cycle.hip: the V-cycle, the preconditioner and operator applications
 int vcycle(sns_ctx* h, int l, const double* b, double* x);
 int coarse_cycle(sns_ctx* h, int l, const double* b, double* x);
@@ -251,11 +258,6 @@ int dot(sns_ctx* h, const double* x, const double* y, double* out);
 
 // ---- small helpers and launch helpers (internal linkage: every translation unit gets its own) -------------------------------
 namespace {
-
-// C-ABI layer (include/sns.h): context, assembly driver, operator hierarchy,
-// Krylov (BiCGStab / FGMRES) and Newton drivers.  Host code only launches
-// kernels from sns_kernels.hip and moves scalars; there is no CPU compute path.
-#include <hip/hip_runtime.h>
 
 inline int vec_grid(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 2048); }
 

@@ -93,9 +93,8 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
     const int64_t nd = nred_of(h);
     const int g = vec_grid(nd);
     double *r, *rhat, *p, *v, *s, *t, *ph, *sh;
-    SNS_TRY(get_vec(h, 0, &r)); SNS_TRY(get_vec(h, 1, &rhat)); SNS_TRY(get_vec(h, 2, &p));
-    SNS_TRY(get_vec(h, 3, &v)); SNS_TRY(get_vec(h, 4, &s)); SNS_TRY(get_vec(h, 5, &t));
-    SNS_TRY(get_vec(h, 6, &ph)); SNS_TRY(get_vec(h, 7, &sh));
+    double** const vecs[] = {&r, &rhat, &p, &v, &s, &t, &ph, &sh};
+    for (int k = 0; k < 8; ++k) SNS_TRY(get_vec(h, VEC_KRYLOV + k, vecs[k]));
     double* sc = h->d_scal + 128;                         // device scalar block of this solver
     double* red = h->d_scal + 144;                        // reduction results
     double* hpin = h->h_scal + 512;                       // pinned landing zone of (rr, flags)
@@ -207,9 +206,8 @@ int tfqmr(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out,
     const int64_t nd = nred_of(h);
     const int g = vec_grid(nd);
     double *w, *y1, *y2, *u1, *u2, *d, *v, *xh, *rt, *tmp;
-    SNS_TRY(get_vec(h, 0, &w)); SNS_TRY(get_vec(h, 1, &y1)); SNS_TRY(get_vec(h, 2, &y2)); SNS_TRY(get_vec(h, 3, &u1));
-    SNS_TRY(get_vec(h, 4, &u2)); SNS_TRY(get_vec(h, 5, &d)); SNS_TRY(get_vec(h, 6, &v)); SNS_TRY(get_vec(h, 7, &xh));
-    SNS_TRY(get_vec(h, 8, &rt)); SNS_TRY(get_vec(h, 9, &tmp));
+    double** const vecs[] = {&w, &y1, &y2, &u1, &u2, &d, &v, &xh, &rt, &tmp};
+    for (int k = 0; k < 10; ++k) SNS_TRY(get_vec(h, VEC_KRYLOV + k, vecs[k]));
     auto axpby = [&](double a, const double* xx, double bb, double* yy) {
         hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, h->stream, nd, a, xx, bb, yy);
     };
@@ -432,7 +430,7 @@ int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double
     const bool can_retry = h->opt.pc_type == SNS_PC_AMG && h->opt.amg_retry_damping != 0 && h->damping_backoff > 0.4;
     double* x0 = nullptr;
     if (can_retry) {
-        SNS_TRY(get_vec(h, 14, &x0));
+        SNS_TRY(get_vec(h, VEC_SAVED_GUESS, &x0));
         HIP_TRY(hipMemcpyAsync(x0, x, nred_of(h) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     }
     int its_total = 0;

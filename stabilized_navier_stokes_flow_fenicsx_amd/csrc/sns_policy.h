@@ -4,6 +4,7 @@
 // hipGraph.  Pure host code over (options, a few global counts): no HIP, no handle, so that the table can be unit-tested on the
 // CPU (sns_host_cycle_policy, tests/test_host.py) and every rank of a partitioned run answers alike by construction.
 // The handle-side predicates of csrc/sns_cycle.hip / sns_setup.hip gather the facts and ask here; the numbers live nowhere else.
+// In the same idiom, at the end: the route of an assembly (plan_assembly, tests/assembly_plan_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -265,6 +266,75 @@ inline CyclePlan plan_cycle(const sns_options& o, const Facts& f) {
             if (f.rows[(size_t)l] <= (int64_t)GRAPH_MAX_ROWS) p.graph_level = l;
     }
     p.fuse_puts = f.fuse_puts;
+    return p;
+}
+
+// ---- the route of an assembly (csrc/sns_assemble.hip; the table is in DESIGN.md) ------------------------------------------------------
+// Facts: the call (form; state, matrix, residual asked for) and the handle (dim, opt.assembly_fused, a perturbed form variant, a
+// mesh with cells).  Whether w violates its Dirichlet data is learnt on the device: where bc_check says so the driver counts the
+// violations and asks again with the answer (`violated` is not read otherwise).
+struct AssemblyFacts {
+    int dim = 3, form = SNS_FORM_NS;
+    bool has_w = false, want_matrix = false, has_F = false, fused = false, variant = false, cells = false;
+};
+enum AssemblyRoute { ROUTE_FUSED_STOKES = 0, ROUTE_FUSED_NS = 1, ROUTE_STAGED = 2, ROUTE_STOKES_2D = 3, ROUTE_NS_2D = 4 };
+// element pass: none, the staged element kernel (16 cells per workgroup), the one-lane-per-cell residual kernel; state: w as
+// given, the Dirichlet data extended by zero, w with the data imposed
+enum ElementKernel { ELEMENT_NONE = 0, ELEMENT_STAGED = 1, ELEMENT_RESIDUAL = 2 };
+enum AssemblyState { STATE_W = 0, STATE_GEXT = 1, STATE_SNAPPED = 2 };
+// error != SNS_OK: refused with `message`.  The launches in the driver's order: the owner-lane passes offdiag / diag (diag writes
+// F too), the element pass (store_K: with matrices; Fe_out: with residuals), the two gathers, the lifting pass, the Dirichlet
+// rows of a 2-D Stokes residual; matrix: the fine operator is rewritten.
+struct AssemblyPlan {
+    int error = SNS_OK;
+    const char* message = "";
+    AssemblyRoute route = ROUTE_STAGED;
+    AssemblyState state = STATE_W;
+    ElementKernel element = ELEMENT_NONE;
+    bool bc_check = false, offdiag = false, diag = false, store_K = false, Fe_out = false, gather_matrix = false,
+         gather_residual = false, lift = false, bc_residual = false, matrix = false;
+};
+
+inline AssemblyPlan plan_assembly(const AssemblyFacts& f, bool violated = true) {
+    AssemblyPlan p;
+    auto refuse = [&](const char* why) { p.error = SNS_E_ARG; p.message = why; return p; };
+    if (f.form != SNS_FORM_STOKES && f.form != SNS_FORM_NS) return refuse("bad form");
+    const bool ns = f.form == SNS_FORM_NS;
+    if (ns && !f.has_w) return refuse("NS form needs a state vector");
+    p.matrix = f.want_matrix;
+    if (f.dim == 2) {                                       // always the owner-lane passes; fused and variant do not apply
+        if (!f.cells) return refuse("empty mesh");
+        p.route = ns ? ROUTE_NS_2D : ROUTE_STOKES_2D;
+        p.offdiag = f.want_matrix;
+        p.diag = f.want_matrix || (!ns && f.has_F);
+        if (ns) {
+            p.bc_check = f.has_F;
+            p.element = f.want_matrix ? ELEMENT_NONE : ELEMENT_RESIDUAL;
+            p.Fe_out = p.gather_residual = !f.want_matrix;
+            p.lift = f.has_F && violated;
+        } else {
+            p.state = f.has_w ? STATE_SNAPPED : STATE_GEXT;
+            p.bc_residual = f.has_w && f.has_F;
+        }
+        return p;
+    }
+    // (a perturbed form exists in the staged element kernel only: Jacobian AND residual go through it; with try_fused && !has_F
+    // the check's answer is not used: kept as it was)
+    const bool try_fused = f.want_matrix && f.fused && ns && f.cells && !f.variant;
+    p.bc_check = ns && f.cells && ((!f.want_matrix && f.has_F) || try_fused);
+    const bool fast_residual = p.bc_check && !violated && !f.variant;
+    if (try_fused || (!ns && !f.has_w && f.want_matrix && f.fused && f.cells)) {
+        p.route = ns ? ROUTE_FUSED_NS : ROUTE_FUSED_STOKES;
+        p.state = ns ? STATE_W : STATE_GEXT;
+        p.offdiag = p.diag = true;
+        p.lift = ns && f.has_F && !fast_residual;
+        return p;
+    }
+    p.element = fast_residual ? ELEMENT_RESIDUAL : f.cells ? ELEMENT_STAGED : ELEMENT_NONE;
+    p.store_K = p.element == ELEMENT_STAGED && f.want_matrix;
+    p.Fe_out = p.element == ELEMENT_RESIDUAL || (p.element == ELEMENT_STAGED && f.has_F);
+    p.gather_matrix = f.want_matrix;
+    p.gather_residual = f.has_F;
     return p;
 }
 

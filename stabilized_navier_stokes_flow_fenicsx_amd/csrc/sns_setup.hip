@@ -1,5 +1,5 @@
-// Setup side of the C-ABI layer: the symbolic AMG hierarchy (aggregation, halo plans per level, replicated tail), the assembly
-// driver, the spectral estimates of the smoother damping and the numeric setup of the preconditioner.
+// Setup side of the C-ABI layer: the symbolic AMG hierarchy (aggregation, halo plans per level, replicated tail), the spectral
+// estimates of the smoother damping, the numeric setup of the preconditioner and the workspace vectors.
 // (shared internals in csrc/sns_ctx.h)
 #include "sns_ctx.h"
 
@@ -664,195 +664,6 @@ int plan_hierarchy(sns_ctx* h) {
 }
 
 
-// 2-D handles (sns_create_2d): triangle P1-P1, Stokes with (stokes_viscosity, stokes_beta) and the UGN-stabilised
-// NS form of LidDrivenNavierStokesFlow.py:123-143 / DFG_2D_Validation.py:141-163.  Always the scratch-free path:
-// every BSR block by its owner lane, residual-only evaluations by one lane per triangle + the node gather.
-int assemble2d(sns_ctx* h, int form, const double* w, double* F, bool want_matrix) {
-    Level& L = h->levels[0];
-    const unsigned go = (unsigned)((h->n_od + 255) / 256);
-    const unsigned gd = (unsigned)((4 * (int64_t)h->n_owned + 255) / 256);
-    const int64_t ndof = 4 * (int64_t)h->n;
-    const int gv = vec_grid(ndof);
-    if (h->E == 0) { set_error("empty mesh"); return SNS_E_ARG; }
-    if (form == SNS_FORM_STOKES) {
-        const double nu_s = h->opt.stokes_viscosity, beta = h->opt.stokes_beta;
-        const double* state = h->gext;            // w == NULL: the system of LinearProblem(a, L, bcs), F(0) = lifting
-        if (w) {                                  // linear residual at w: state = w with the Dirichlet data imposed
-            double* tmp = nullptr;
-            SNS_TRY(get_vec(h, 13, &tmp));
-            HIP_TRY(hipMemcpyAsync(tmp, w, ndof * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            hipLaunchKernelGGL(k_snap_bc, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, 1e300, tmp);
-            state = tmp;
-        }
-        if (want_matrix)
-            hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_STOKES_2D, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
-                               h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, state,
-                               h->bc_mask, nu_s, beta, L.vals, TimeTerm(), ViscosityLaw());
-        if (want_matrix || F)
-            hipLaunchKernelGGL((k_fused_diag<SNS_FORM_STOKES_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, state, h->bc_mask, h->bc_val, nu_s, beta,
-                               want_matrix ? L.vals : (double*)nullptr, F, TimeTerm(), ViscosityLaw());
-        if (w && F) hipLaunchKernelGGL(k_bc_residual, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, F);
-    } else {
-        const double nu = 1.0 / h->opt.reynolds;
-        bool lifted = false;
-        if (F) {
-            hipLaunchKernelGGL(k_count_bc_violations, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w,
-                               h->partial);
-            reduce_local(h, gv, 1, h->d_scal + 60);
-            double nviol = 1.0;
-            SNS_TRY(fetch(h, h->d_scal + 60, 1, &nviol));
-            lifted = nviol != 0.0;
-        }
-        if (want_matrix) {
-            hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_UGN_2D, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
-                               h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, w, h->bc_mask,
-                               nu, 0.0, L.vals, TimeTerm(), ViscosityLaw());
-            hipLaunchKernelGGL((k_fused_diag<SNS_FORM_UGN_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F,
-                               TimeTerm(), ViscosityLaw());
-        } else {
-            if (!h->Fe) SNS_TRY(h->Fe.alloc((size_t)h->E * 16));
-            hipLaunchKernelGGL(k_residual_tri, dim3((unsigned)((h->E + 255) / 256)), dim3(256), 0, h->stream, h->E,
-                               h->tets, h->pts, w, nu, h->Fe);
-            hipLaunchKernelGGL(k_gather_residual, dim3(gd), dim3(256), 0, h->stream, h->n_owned, h->nt_ptr, h->nt_idx,
-                               h->bc_mask, h->bc_val, w, h->Fe, F);
-        }
-        if (lifted && F) {                       // F += A0[:,B] (g - x_B)   (apply_lifting)
-            double* dl = nullptr;
-            SNS_TRY(get_vec(h, 13, &dl));
-            hipLaunchKernelGGL(k_bc_defect, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, dl);
-            hipLaunchKernelGGL((k_fused_lift<SNS_FORM_UGN_2D, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                               L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F, TimeTerm(), ViscosityLaw());
-        }
-    }
-    if (want_matrix) {
-        h->has_matrix = true;
-        h->transposed = false;
-        h->pc_ready = false;
-        h->matrix_form = form;
-    }
-    HIP_TRY(hipGetLastError());
-    return SNS_OK;
-}
-
-
-int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix) {
-    if (form != SNS_FORM_STOKES && form != SNS_FORM_NS) { set_error("bad form"); return SNS_E_ARG; }
-    if (form == SNS_FORM_NS && !w) { set_error("NS form needs a state vector"); return SNS_E_ARG; }
-    if (h->dim == 2) return assemble2d(h, form, w, F, want_matrix);
-    const int grid = (int)((h->E + EL_TETS_PER_BLOCK - 1) / EL_TETS_PER_BLOCK);
-    const double nu = 1.0 / h->opt.reynolds;
-    bool fast_residual = false;
-    // (a perturbed form -- sns_set_form_variant -- exists in the staged element kernel only: Jacobian AND residual go through it)
-    const bool variant = !h->fv.is_default();
-    const bool try_fused = want_matrix && h->opt.assembly_fused && form == SNS_FORM_NS && h->E > 0 && !variant;
-    if (((!want_matrix && F) || try_fused) && form == SNS_FORM_NS && h->E > 0) {
-        // residual only: if the state satisfies the Dirichlet data there is no lifting term (:65) and the
-        // one-lane-per-tet kernel applies; otherwise the general fused kernel computes the lifted blocks
-        const int64_t ndof = 4 * (int64_t)h->n;
-        const int gv = vec_grid(ndof);
-        hipLaunchKernelGGL(k_count_bc_violations, dim3(gv), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w,
-                           h->partial);
-        reduce_local(h, gv, 1, h->d_scal + 60);
-        double nviol = 1.0;
-        SNS_TRY(fetch(h, h->d_scal + 60, 1, &nviol));
-        fast_residual = (nviol == 0.0) && !variant;
-    }
-    Level& L = h->levels[0];
-    if (form == SNS_FORM_STOKES && !w && want_matrix && h->opt.assembly_fused && h->E > 0) {
-        // the Stokes system of solve_stokes_problem (:197-218): constant element blocks, right-hand side F(0) =
-        // lifting A0[:,B] g (row a of A0 applied to the Dirichlet data extended by zero), F_B = -g
-        const unsigned go = (unsigned)((h->n_od + 255) / 256);
-        const unsigned gd = (unsigned)((4 * (int64_t)h->n_owned + 255) / 256);
-        hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_STOKES, false>), dim3(go), dim3(256), 0, h->stream, h->n_od,
-                           h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, h->gext,
-                           h->bc_mask, nu, 0.0, L.vals, TimeTerm(), ViscosityLaw());
-        hipLaunchKernelGGL((k_fused_diag<SNS_FORM_STOKES, false>), dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag,
-                           h->c_ptr, h->c_idx, h->tets, h->pts, h->gext, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F, TimeTerm(), ViscosityLaw());
-        h->has_matrix = true;
-        h->transposed = false;
-        h->pc_ready = false;
-        h->matrix_form = form;
-        HIP_TRY(hipGetLastError());
-        return SNS_OK;
-    }
-    if (try_fused) {
-        // scratch-free path: every BSR block (and every node residual) is computed by the lanes that own it; a
-        // state that violates its Dirichlet data adds the lifting term in a third pass over the boundary tets
-        const unsigned go = (unsigned)((h->n_od + 255) / 256);
-        const unsigned gd = (unsigned)((4 * (int64_t)h->n_owned + 255) / 256);
-        // (C: corrected convection, V: 1 = the handle has a time term, 2 = a viscosity law -- compile-time variants of the kernels)
-        dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-            dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
-                hipLaunchKernelGGL((k_fused_offdiag<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(go), dim3(256), 0, h->stream, h->n_od,
-                                   h->od_order, h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->tets, h->pts, w, h->bc_mask, nu, 0.0,
-                                   L.vals, h->tt, h->vl);
-                hipLaunchKernelGGL((k_fused_diag<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                                   L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, 0.0, L.vals, F, h->tt, h->vl);
-            });
-        });
-        if (!fast_residual && F) {
-            double* dl = nullptr;
-            SNS_TRY(get_vec(h, 13, &dl));
-            const int64_t ndof = 4 * (int64_t)h->n;
-            hipLaunchKernelGGL(k_bc_defect, dim3(vec_grid(ndof)), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, dl);
-            dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-                dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
-                    hipLaunchKernelGGL((k_fused_lift<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(gd), dim3(256), 0, h->stream, h->n_owned,
-                                       L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, w, h->bc_mask, dl, nu, F, h->tt, h->vl);
-                });
-            });
-        }
-        h->has_matrix = true;
-        h->transposed = false;
-        h->pc_ready = false;
-        h->matrix_form = form;
-        HIP_TRY(hipGetLastError());
-        return SNS_OK;
-    }
-    if (want_matrix && !h->Ke) SNS_TRY(h->Ke.alloc((size_t)h->E * 256));
-    if (!h->Fe) SNS_TRY(h->Fe.alloc((size_t)h->E * 16));
-    double* Fe = F ? h->Fe : nullptr;
-    if (fast_residual) {
-        const unsigned gt = (unsigned)((h->E + 255) / 256);
-        dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-            dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
-                hipLaunchKernelGGL((k_residual_tet<C() != 0, V() == 1, V() == 2>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w,
-                                   nu, h->Fe, h->tt, h->vl);
-            });
-        });
-    } else if (grid > 0) {
-        if (form == SNS_FORM_STOKES)
-            hipLaunchKernelGGL((k_element<SNS_FORM_STOKES, false>), dim3(grid), dim3(256), 0, h->stream, h->E, h->tets,
-                               h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv, TimeTerm(), ViscosityLaw());
-        else
-            dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-                dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
-                    hipLaunchKernelGGL((k_element<SNS_FORM_NS, C() != 0, V() == 1, V() == 2>), dim3(grid), dim3(256), 0, h->stream, h->E,
-                                       h->tets, h->pts, w, h->bc_mask, h->bc_val, nu, want_matrix ? 1 : 0, h->Ke, Fe, h->fv, h->tt, h->vl);
-                });
-            });
-    }
-    if (want_matrix) {
-        const int64_t nth = L.nnzb * 8;
-        hipLaunchKernelGGL(k_gather_matrix, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.nnzb,
-                           h->c_ptr, h->c_idx, h->slot_row[0], L.colind, h->bc_mask, h->Ke, L.vals);
-        h->has_matrix = true;
-        h->transposed = false;
-        h->pc_ready = false;
-        h->matrix_form = form;
-    }
-    if (F) {
-        const int64_t nth = 4 * (int64_t)h->n_owned;
-        hipLaunchKernelGGL(k_gather_residual, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream,
-                           h->n_owned, h->nt_ptr, h->nt_idx, h->bc_mask, h->bc_val, w, h->Fe, F);
-    }
-    HIP_TRY(hipGetLastError());
-    return SNS_OK;
-}
-
-
 // |lambda|max of Dinv*A on level l by a few power iterations (device resident; one host sync).
 // The damped block-Jacobi smoother x += w Dinv (b - A x) needs w*|lambda|max < 2; on the reference's
 // operator the fixed w = 0.9 already diverges at 10 M tets, so w is capped per level at the smoothing-optimal 4/(3 |lambda|max).  (Measured cliff on the coarse
@@ -872,7 +683,7 @@ int estimate_lambda_max(sns_ctx* h, int l, double* out) {
     if (rows > 0) hipLaunchKernelGGL(k_fill_pattern, dim3(g), dim3(256), 0, h->stream, nd, x);
     double* zero = nullptr;
     if (P.lp_fmt != 0) {
-        SNS_TRY(get_vec(h, 13, &zero));                  // level sizes never exceed the fine level
+        SNS_TRY(get_vec(h, VEC_SCRATCH, &zero));                  // level sizes never exceed the fine level
         if (nd > 0) HIP_TRY(hipMemsetAsync(zero, 0, nd * sizeof(double), h->stream));
     }
     double lam = 0.0;
@@ -937,8 +748,8 @@ int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
     double* y = L.r;
     double* zero = nullptr;
     double* xin = nullptr;                              // the SpMV input needs the level's full length (ghost tail = 0)
-    SNS_TRY(get_vec(h, 13, &zero));
-    SNS_TRY(get_vec(h, 12, &xin));
+    SNS_TRY(get_vec(h, VEC_SCRATCH, &zero));
+    SNS_TRY(get_vec(h, VEC_ARNOLDI_IN, &xin));
     HIP_TRY(hipMemsetAsync(zero, 0, nd * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(xin, 0, 4 * (size_t)L.n * sizeof(double), h->stream));
     double* sc = h->d_scal + 192;                      // [0, 8) pass-1 coefficients, [8, 16) pass 2, [16, 18) (w.w, w.w)
@@ -1007,7 +818,7 @@ int jacobi_growth(sns_ctx* h, int l, double omega, double* growth) {
     double* xa = L.x;
     double* xb = L.r;
     double* zero = nullptr;
-    SNS_TRY(get_vec(h, 13, &zero));                      // level sizes never exceed the fine level
+    SNS_TRY(get_vec(h, VEC_SCRATCH, &zero));                      // level sizes never exceed the fine level
     if (nd > 0) HIP_TRY(hipMemsetAsync(zero, 0, nd * sizeof(double), h->stream));
     // keep x0 intact (it seeds later trials): first sweep x0 -> xa, then ping-pong xa <-> xb
     const bool glob = P.ghost_sweeps();
@@ -1281,18 +1092,5 @@ int get_vec(sns_ctx* h, size_t k, double** out) {
     *out = h->kv[k];
     return SNS_OK;
 }
-
-
-int timed_assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix) {
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    SNS_TRY(assemble(h, form, w, F, want_matrix));
-    HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->tm.assemble_ms += ms;
-    return SNS_OK;
-}
-
 
 }  // namespace sns

@@ -95,6 +95,51 @@ def test_transpose_is_exact(case):
     P.close()
 
 
+# every route of the assembly driver that writes the matrix (csrc/sns_assemble.hip, DESIGN.md "Assembly routes"):
+# (2-D?, options, form, perturbed form variant?)
+MATRIX_ROUTES = {"fused_ns": (False, {}, "ns", False),
+                 "staged_ns": (False, {"assembly_fused": 0}, "ns", False),
+                 "variant_ns": (False, {"assembly_fused": 1}, "ns", True),
+                 "fused_stokes": (False, {}, "stokes", False),
+                 "staged_stokes": (False, {"assembly_fused": 0}, "stokes", False),
+                 "ns_2d": (True, {}, "ns", False),
+                 "stokes_2d": (True, {}, "stokes", False)}
+
+
+@pytest.mark.parametrize("route", list(MATRIX_ROUTES))
+def test_every_matrix_route_resets_the_matrix_state(route):
+    """The state change of a matrix-writing assembly is written once for all routes: after pc_setup and a flip, an assembly by
+    any of them clears the transposed flag, invalidates the preconditioner and gives the bits of the first assembly."""
+    two_d, opts, form, variant = MATRIX_ROUTES[route]
+    if two_d:
+        m, bcs, opt = _dfg2d()
+    else:
+        m = M.channel_mesh((5, 3, 3), jitter=0.2)
+        # a partial last workgroup in every kernel: 16 cells per workgroup of the element pass, 256 dofs of the node passes
+        assert len(m.tets) % 16 != 0 and (4 * len(m.points)) % 256 != 0
+        bcs, opt = B.channel_bcs(m, *B.two_stream_profiles(0.5)).flatten(), dict(reynolds=RE_DUCT)
+    P = FlowProblem(m, bcs, **opt, **opts)
+    w = None
+    if form == "ns":
+        w, res = P.stokes_solve()
+        assert res.reason > 0
+    if variant:
+        P.set_form_variant(c_inverse=30.0)
+    P.jacobian(w, form)
+    va0 = P.bsr()[2].cpu().numpy().copy()
+    P.pc_setup()
+    P.pc_apply(P.zeros())
+    P.transpose_operator()
+    assert P.operator_transposed
+    P.jacobian(w, form)
+    assert not P.operator_transposed
+    with pytest.raises(SnsError) as e:
+        P.pc_apply(P.zeros())
+    assert e.value.code == -3 and "pc_apply before pc_setup" in str(e.value)
+    assert np.array_equal(_bits(P.bsr()[2].cpu().numpy()), _bits(va0))
+    P.close()
+
+
 def test_transpose_needs_a_matrix_and_a_single_gpu_handle():
     m, bcs, opt = _structured()
     P = FlowProblem(m, bcs, **opt)

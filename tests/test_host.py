@@ -956,3 +956,78 @@ def test_cycle_plan_columns(built_lib, tmp_path):
     assert cyc(dense) == [(1, 1, 1), (0, 4, 4), (3, 0, 0)]
     assert col(dense, "fused_post") == [1, 0, 0] and col(dense, "fuses_next_first") == [0, 0, 0]
     assert col(dense, "windows") == [1, 0, 0] and col(dense, "start_odd") == [1, 1, 0] and top(dense) == (1, 0, 2)
+
+
+def test_assembly_plan_table(tmp_path):
+    """The route of an assembly (csrc/sns_policy.h: policy::plan_assembly, what the driver of csrc/sns_assemble.hip launches) for
+    every combination of its eight facts and the answer of the device-side Dirichlet check that the C ABI can reach, against a
+    transcription of the route table ("Assembly routes") written here and not derived from the header.  Built like
+    the cycle's plan: a small main over the header, no ABI."""
+    import itertools
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "assembly_plan")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
+                            "-I", os.path.join(ROOT, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
+                            os.path.join(ROOT, "tests", "assembly_plan_main.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    STOKES, NS, E_ARG = 0, 1, -1                                           # include/sns.h
+    FUSED_STOKES, FUSED_NS, STAGED, STOKES_2D, NS_2D = range(5)            # policy::AssemblyRoute
+    NONE, ELEMENT, RESIDUAL = range(3)                                      # policy::ElementKernel
+    W, GEXT, SNAPPED = range(3)                                             # policy::AssemblyState
+    KEYS = ("error", "route", "bc_check", "element", "store_K", "Fe", "lift", "gather_matrix", "gather_residual", "bc_residual",
+            "matrix", "offdiag", "diag", "state")
+
+    def expected(dim, form, w, m, F, fused, variant, cells, violated):
+        e = dict.fromkeys(KEYS, 0)
+        if form not in (STOKES, NS) or (form == NS and not w) or (dim == 2 and not cells):
+            return dict(error=E_ARG)
+        e["matrix"] = m                                   # every route that writes the matrix changes the matrix state
+        if dim == 2:                                      # fused and variant are ignored
+            if form == STOKES:
+                e.update(route=STOKES_2D, state=SNAPPED if w else GEXT, offdiag=m, diag=m or F, bc_residual=w and F)
+            else:
+                e.update(route=NS_2D, bc_check=F, lift=F and violated)
+                if m:
+                    e.update(offdiag=1, diag=1)
+                else:
+                    e.update(element=RESIDUAL, Fe=1, gather_residual=1)
+            return e
+        try_fused = m and fused and form == NS and cells and not variant
+        check = form == NS and cells and ((not m and F) or try_fused)
+        fast = check and not violated and not variant
+        e["bc_check"] = check
+        if form == STOKES and not w and m and fused and cells:
+            e.update(route=FUSED_STOKES, state=GEXT, offdiag=1, diag=1)
+        elif try_fused:
+            e.update(route=FUSED_NS, offdiag=1, diag=1, lift=F and not fast)
+        else:
+            kind = RESIDUAL if fast else ELEMENT if cells else NONE
+            e.update(route=STAGED, element=kind, store_K=kind == ELEMENT and m, Fe=kind == RESIDUAL or (kind == ELEMENT and F),
+                     gather_matrix=m, gather_residual=F)
+        return e
+
+    combos = [c for c in itertools.product((2, 3), (STOKES, NS, 7), *[(0, 1)] * 7)]
+    # the combinations the C ABI cannot reach, and there are no others: neither a matrix nor a residual asked for (sns_residual
+    # needs F, sns_jacobian wants the matrix) ...
+    reachable = [c for c in combos if c[3] or c[4]]
+    assert len(combos) - len(reachable) == 2 * 3 * 2 ** 5
+    run = subprocess.run([exe], input="".join(" ".join(map(str, c)) + "\n" for c in reachable), capture_output=True, text=True)
+    assert run.returncode == 0, run.returncode
+    rows = [dict(zip(KEYS, map(int, ln.split()))) for ln in run.stdout.split("\n") if ln.strip()]
+    assert len(rows) == len(reachable)
+    n_err = 0
+    for c, got in zip(reachable, rows):
+        want = expected(*c)
+        if want["error"]:
+            # ... and NS without a state past the argument check: refused (like a bad form and an empty 2-D mesh), no plan to compare
+            assert got["error"] == want["error"], (c, got)
+            n_err += 1
+            continue
+        assert got == {k: int(v) for k, v in want.items()}, (c, got, want)
+    assert 0 < n_err < len(reachable)
+    # the fast residual path exists, and only for a state that satisfies its data on the reference's form
+    fast = [c for c, r in zip(reachable, rows) if not r["error"] and r["route"] == STAGED and r["element"] == RESIDUAL]
+    assert fast and all(c[0] == 3 and c[1] == NS and not c[3] and c[4] and not c[6] and c[7] and not c[8] for c in fast)
