@@ -472,6 +472,46 @@ SNS_API int sns_operator_is_transposed(sns_handle h, int* flag);
  * parameter q of the residual F (solver.reynolds_sensitivity): one linear solve instead of two nonlinear ones per
  * parameter.  Errors as sns_transpose_operator and sns_krylov_solve.                                                 */
 SNS_API int sns_adjoint_solve(sns_handle h, const double* g_dev, double* lam_dev, int* its, int* reason, double* rnorm);
+/* ---- scalar transport on the flow mesh: four species through one solve (the reference has no counterpart; it answers "where
+ *      does the inner stream go" kinematically, with streamlines) ------------------------------------------------------------
+ * Species k = 0..3 in the node-blocked layout [c0, c1, c2, c3] of the flow state (c_dev, src_dev, cmask_dev, cval_dev, rhs_dev:
+ * 4*n_local entries each), carried by the P1 velocity u of the state w_dev (its pressure slots are ignored):
+ *     R_k(c; v) = int (sigma c + u.grad c - s_k)(v + tau_k u.grad v) + kappa_k grad c . grad v dx = 0,
+ *     tau_k = (theta + u.G u + C_I kappa_k^2 G:G)^(-1/2),   C_I = 36, G = K^T K (the flow form's metric, :232-237),
+ * tau_k taken at each point of the 4-point degree-2 rule every integral uses (:222).  Inside a P1 tet the Laplacian of c
+ * vanishes, so the strong residual is sigma c + u.grad c - s.  sigma >= 0 and theta >= 0 are shared by the species; src_dev is a
+ * nodal P1 source or NULL for zero.  Steady transport: sigma = theta = 0.  Age of fluid: s = 1, c = 0 at the inlet.  An implicit
+ * BDF1 step: sigma = 1/dt, s = c^n/dt, theta = 4/dt^2.  Cells of either orientation count with |det J|.
+ * Dirichlet data of the scalars are the caller's, independent of the flow's (cmask_dev / cval_dev), and are treated as the flow
+ * operator treats its own: rows and columns zeroed, diagonal one, b_i -= sum_{j in B} A0_ij g_j, b_B = g.  Every other boundary
+ * is natural (zero diffusive flux).  A species without a Dirichlet node under sigma = 0 is singular (constants lie in its
+ * kernel); this is NOT detected.  An unused species: constrain all of its dofs (identity rows).
+ * The species do not couple, so the operator is blockdiag(A_0..A_3) in the handle's BSR pattern: every 4 x 4 block is diagonal,
+ * stored with its twelve explicit zeros.  sns_scalar_system writes it into the handle's fine-level values (all of them) and the
+ * right-hand side into rhs_dev in one scratch-free owner-computes pass (csrc/sns_scalar.hip: no atomics, fixed summation order,
+ * bitwise reproducible; the only device memory it adds is the handle's copy of cmask, 4*n_local bytes).  It leaves the scalar
+ * operator as the handle's matrix under the contract of any assembly: the transposed flag is cleared, the preconditioner is
+ * stale, and the next sns_pc_setup re-estimates the smoother damping (also after a change of kappa, sigma or theta).
+ * sns_spmv, sns_pc_setup, sns_pc_apply, sns_krylov_solve, sns_transpose_operator, sns_adjoint_solve (lam_B = g_B on the SCALARS'
+ * Dirichlet dofs), sns_get_bsr and sns_export then act on it; the next sns_jacobian (or flow solve) restores the flow operator.
+ * The hierarchy keeps the aggregates it was built with; its transfer operators leave out the Dirichlet dofs of the operator in
+ * the handle, so the fine level's free mask is rewritten from cmask here and from the flow's mask at the next flow assembly (in
+ * place, O(n); the set-up that every assembly makes stale rebuilds what depends on it).  Where sns_scalar_system is the
+ * handle's first assembly the hierarchy is built at the following set-up from the scalar operator's pattern -- the same
+ * pattern -- and amg_aggregation = 1, 2 or 3 take their strengths from the scalar operator, for the rest of the handle's life.
+ * sns_scalar_solve = sns_scalar_system + sns_pc_setup + the Krylov solve with the handle's options (damping retry as in
+ * sns_krylov_solve); c_dev holds the guess on entry and the solution on exit, rnorm = the 2-norm of the TRUE residual; a
+ * converged solve returns the Dirichlet data exactly.  Neither call writes the time term, the viscosity law, the form variant or
+ * the options.  Not built: 2-D handles, partitioned handles, discontinuity capturing (expect over- and undershoots of a few
+ * per cent at sharp layers), any coupling of c back into the flow.
+ * SNS_E_ARG: null handle / w / kappa / mask / values / output; a 2-D handle; a kappa_k that is <= 0 or not finite; sigma or
+ * theta negative or not finite.  SNS_E_STATE: a handle with a communicator attached (any transport, also the local-only split).
+ * After an error the handle's matrix is untouched.  Both return after their outputs are written.                          */
+SNS_API int sns_scalar_system(sns_handle h, const double* w_dev, const double kappa[4], double sigma, double theta,
+                              const double* src_dev, const uint8_t* cmask_dev, const double* cval_dev, double* rhs_dev);
+SNS_API int sns_scalar_solve(sns_handle h, const double* w_dev, const double kappa[4], double sigma, double theta,
+                             const double* src_dev, const uint8_t* cmask_dev, const double* cval_dev, double* c_dev, int* its,
+                             int* reason, double* rnorm);
 /* solve_stokes_problem (:197-218): assemble + lift + KSP; U_dev receives U.   */
 SNS_API int sns_stokes_solve(sns_handle h, double* U_dev, int* ksp_its, int* reason, double* rnorm);
 /* solve_navier_stokes (:268-312): SNES newtonls + bt; w_dev updated in place

@@ -608,7 +608,9 @@ int sns_adjoint_solve(sns_handle h, const double* g, double* lam, int* its, int*
     // sns_stokes_solve does with the Dirichlet data); the other rows' residual does not see it
     if (rc == SNS_OK && *reason > 0) {
         const int64_t nd = nred_of(h);
-        hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, h->bc_mask, g, 1e300, lam);
+        // (the mask of the operator that was transposed: the scalars' own while the scalar operator is the handle's matrix)
+        const uint8_t* mask = h->matrix_form == SNS_FORM_SCALAR ? h->sc_mask.get() : h->bc_mask.get();
+        hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, mask, g, 1e300, lam);
         rc = sync_stream(h);
     }
     // back to A, after a solve that did not converge too; a HIP or transport error leaves the device state undefined
@@ -743,6 +745,46 @@ static int newton_run(sns_ctx* h, double* w, int* its_out, int* reason_out, int*
     *its_out = it;
     *reason_out = reason;
     if (total_ksp) *total_ksp = ksp_total;
+    return SNS_OK;
+}
+
+// the argument checks of the two scalar-transport entry points (`who`: the name in front of the message)
+static int scalar_check(const char* who, sns_ctx* h, const double* w, const double* kappa, double sigma, double theta,
+                        const uint8_t* cmask, const double* cval, const void* out) {
+    const std::string name(who);
+    if (!h || !w || !kappa || !cmask || !cval || !out) { set_error(name + ": null handle or pointer"); return SNS_E_ARG; }
+    if (h->dim != 3) { set_error(name + ": 3-D handles only"); return SNS_E_ARG; }
+    for (int k = 0; k < 4; ++k)
+        if (!(kappa[k] > 0.0) || !std::isfinite(kappa[k])) { set_error(name + ": every kappa must be finite and > 0"); return SNS_E_ARG; }
+    if (!(sigma >= 0.0) || !std::isfinite(sigma) || !(theta >= 0.0) || !std::isfinite(theta)) {
+        set_error(name + ": sigma and theta must be finite and >= 0");
+        return SNS_E_ARG;
+    }
+    if (h->comm) { set_error(name + ": not with a communicator attached (partitioned scalar transport is not built)"); return SNS_E_STATE; }
+    return SNS_OK;
+}
+
+int sns_scalar_system(sns_handle h, const double* w_dev, const double kappa[4], double sigma, double theta, const double* src_dev,
+                      const uint8_t* cmask_dev, const double* cval_dev, double* rhs_dev) {
+    SNS_TRY(scalar_check("sns_scalar_system", h, w_dev, kappa, sigma, theta, cmask_dev, cval_dev, rhs_dev));
+    return scalar_system(h, w_dev, kappa, sigma, theta, src_dev, cmask_dev, cval_dev, rhs_dev);
+}
+
+int sns_scalar_solve(sns_handle h, const double* w_dev, const double kappa[4], double sigma, double theta, const double* src_dev,
+                     const uint8_t* cmask_dev, const double* cval_dev, double* c_dev, int* its, int* reason, double* rnorm) {
+    SNS_TRY(scalar_check("sns_scalar_solve", h, w_dev, kappa, sigma, theta, cmask_dev, cval_dev, c_dev));
+    if (!its || !reason || !rnorm) { set_error("sns_scalar_solve: null output"); return SNS_E_ARG; }
+    SNS_TRY(ensure_hierarchy(h, true));
+    SNS_TRY(ensure_newton_workspace(h));
+    SNS_TRY(scalar_system(h, w_dev, kappa, sigma, theta, src_dev, cmask_dev, cval_dev, h->nw_F));
+    SNS_TRY(ensure_hierarchy(h));
+    SNS_TRY(krylov(h, h->nw_F, c_dev, its, reason, rnorm));
+    // the Dirichlet rows are identity rows: a converged solve hands back the exact data (as sns_stokes_solve does)
+    if (*reason > 0) {
+        const int64_t nd = nred_of(h);
+        hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, cmask_dev, cval_dev, 1e300, c_dev);
+        SNS_TRY(sync_stream(h));
+    }
     return SNS_OK;
 }
 

@@ -133,7 +133,11 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
     if (p.lift) SNS_TRY(lift(h, K, gd, w, F));
     if (p.bc_residual)
         hipLaunchKernelGGL(k_bc_residual, dim3(vec_grid(ndof)), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, F);
-    if (p.matrix) matrix_changed(h, form);
+    if (p.matrix) {
+        // after a scalar-transport assembly (csrc/sns_scalar.hip) the hierarchy's transfers leave out the flow's Dirichlet dofs again
+        if (h->matrix_form == SNS_FORM_SCALAR) SNS_TRY(fine_free_mask(h, h->bc_mask));
+        matrix_changed(h, form);
+    }
     HIP_TRY(hipGetLastError());
     return SNS_OK;
 }

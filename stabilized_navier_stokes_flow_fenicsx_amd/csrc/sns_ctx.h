@@ -53,6 +53,10 @@ namespace sns {
 
 using namespace sns;
 
+// internal id of the scalar-transport operator in sns_ctx::matrix_form / est_form (beside SNS_FORM_STOKES, SNS_FORM_NS and the two
+// 2-D ids of csrc/sns_kernels.h); no public entry point takes it
+#define SNS_FORM_SCALAR 4
+
 struct sns_ctx {
     // Release order: ~sns_ctx waits for the device and destroys the graph exec and the streams; then the members go in reverse
     // order of declaration -- events and every buffer first, the communicator (declared first) last: its plans' window areas go
@@ -126,6 +130,9 @@ struct sns_ctx {
     DevBuf<int32_t> tr_partner;                  // [nnzb] slot (i, j) -> slot (j, i), built at the first transpose (csrc/sns_transpose.hip)
     int est_form = -1;                           // form of the matrix the levels' spectral estimates were last taken from
     double est_re = 0.0;                         // ... and its Reynolds number
+    // sns_scalar_system (csrc/sns_scalar.hip): matrix_form = SNS_FORM_SCALAR while the scalar operator is the handle's matrix
+    DevBuf<uint8_t> sc_mask;                     // the scalars' Dirichlet mask of the last scalar assembly (4*n, allocated at the first)
+    double sc_par[6] = {0, 0, 0, 0, 0, 0};       // ... and its kappa[4], sigma, theta (another set: the estimates are taken again)
     // reductions
     DevBuf<double> partial;                      // [max(65536*8, n/32)]
     DevBuf<double> partial2;                     // second stage of long reductions
@@ -247,6 +254,11 @@ int residual_shape_gradient(sns_ctx* h, const double* w, const double* lam, doub
 // fields D), and the Zienkiewicz-Zhu indicator per cell (G null: recovered into a temporary)
 int recover_gradient(sns_ctx* h, const double* w, double* G, double* D);
 int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, double* gnorm2);
+// csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)
+int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sigma, double theta, const double* src,
+                  const uint8_t* cmask, const double* cval, double* rhs);
+// ... and the fine level's free mask (with the per-aggregate counts derived from it) set to the complement of a Dirichlet mask
+int fine_free_mask(sns_ctx* h, const uint8_t* dirichlet_mask);
 // csrc/sns_aggregate.hip: aggregate_strength's map of the owned nodes, built on the device (amg_aggregation = 2)
 int aggregate_strength_device(sns_ctx* h, int max_agg, std::vector<int32_t>& agg, int32_t& nc);
 // ... and the hybrid (amg_aggregation = 3): the geometric map g (ng aggregates) re-matched where it cuts a dominant coupling

@@ -331,6 +331,9 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
     derived = _derived_fields(Pf, w)
     if derived is not None:
         out["derived"] = derived
+    conc = _scalar_transport(Pf, w, msh_f)
+    if conc is not None:
+        out["concentration"] = conc
     Pf.close()
     return out
 
@@ -341,6 +344,8 @@ def navier_stokes_channel_main(argv=None):
     folder, _ = make_output_folder(r["Re"], r["img_fname"], r["channel_mesh_size"])
     save_navier_stokes_solution(r["u"], r["p"], r["msh"], folder, r["Re"])
     _write_derived_fields(r.get("derived"), r["msh"], lambda label: os.path.join(folder, f"Re{r['Re']}Channel{label}"))
+    if r.get("concentration") is not None and _rank() == 0:
+        write_xdmf(os.path.join(folder, f"Re{r['Re']}ChannelConcentration"), r["msh"], "Concentration", r["concentration"])
     write_run_metadata(folder, r["Re"], r["img_fname"], r["flowrate_ratio"], r["channel_mesh_size"], r["msh"])
     if _rank() == 0:
         print(f"Run Time = {time.time() - t0:.2f} sec; output in {folder}", flush=True)
@@ -391,6 +396,9 @@ def duct_stokes_main(argv=None):
         write_xdmf("StokesDuctPressure", msh, "f", p)
         write_xdmf("StokesDuctVelcoity", msh, "f", u)             # (sic) file name of the reference :255
     _write_derived_fields(_derived_fields(P, U), msh, lambda label: f"StokesDuct{label}")
+    conc = _scalar_transport(P, U, msh)
+    if conc is not None and _rank() == 0:
+        write_xdmf("StokesDuctConcentration", msh, "Concentration", conc)
     P.close()
     return msh, W, res
 
@@ -538,6 +546,50 @@ def _write_derived_fields(fields, msh, path_of):
 
 def _sensitivity():
     return os.environ.get("SNS_SENSITIVITY", "0") == "1"
+
+
+def inner_stream_inlet_data(msh):
+    """(mask, values), each (n, 1): the inlet-stream indicator as Dirichlet data of one scalar -- c = 1 on the inlet nodes of
+    the inner stream, 0 on the other inlet nodes.  A channel mesh carries the two inlet regions as facet tags (the inlet
+    pipeline's regions, or the synthetic centred square); a mesh with a single inlet tag (the duct) takes the centred square
+    of half width ``meta["inner_half_width"]`` (default 0.25) about the duct's axis."""
+    t = msh.meta["tags"]
+    n = msh.num_nodes
+    mask, val = np.zeros((n, 1), bool), np.zeros((n, 1))
+    if "inlet_1" in t:
+        inner, outer = msh.facet_nodes(t["inlet_1"]), msh.facet_nodes(t["inlet_2"])
+    else:
+        outer = msh.facet_nodes(t["inlet"])
+        a = float(msh.meta.get("inner_half_width", 0.25))
+        yz = msh.points[outer, 1:]
+        inner = outer[np.all(np.abs(yz) <= a * (1.0 + 1e-12), axis=1)]
+    mask[outer] = mask[inner] = True
+    val[inner] = 1.0
+    return mask, val
+
+
+def _scalar_transport(P, w, msh):
+    """SNS_SCALAR_PECLET=<Pe> (opt-in; single-GPU runs): after the flow solve, the steady transport of the inlet-stream
+    indicator (``inner_stream_inlet_data``) by the velocity of the state ``w`` with kappa = 1/Pe
+    (``solver.solve_scalar_transport``), as a host array (n,), and one printed line with its range over the outlet nodes.  None
+    without the switch: output and stdout stay as they are."""
+    pe = os.environ.get("SNS_SCALAR_PECLET", "")
+    if not pe:
+        return None
+    if getattr(P, "part", None) is not None:
+        if _rank() == 0:
+            print("SNS_SCALAR_PECLET: scalar transport runs on single-GPU problems only; skipped", flush=True)
+        return None
+    from .solver import solve_scalar_transport
+    pe = float(pe)
+    if not pe > 0.0:
+        raise ValueError("SNS_SCALAR_PECLET must be a positive Peclet number")
+    c, res = solve_scalar_transport(P, w, (1.0 / pe,), inner_stream_inlet_data(msh))
+    c = c[:, 0].cpu().numpy()
+    out = c[msh.facet_nodes(msh.meta["tags"]["outlet"])]
+    print(f"Scalar transport Pe {pe:g}: {res.its} iterations, reason {res.reason}; concentration at the outlet "
+          f"min {out.min()} max {out.max()}", flush=True)
+    return c
 
 
 def dfg_2d_main(argv=None):

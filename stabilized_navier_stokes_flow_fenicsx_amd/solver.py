@@ -442,6 +442,63 @@ class FlowProblem:
         check(self.lib.sns_element_viscosity(self.h, _ptr(w), _ptr(nu), _ptr(gd)))
         return nu, gd
 
+    # -- scalar transport on the flow mesh (no counterpart in the reference, which traces streamlines instead) --------
+    def _scalar_inputs(self, w, kappa, bcs, source):
+        """Device arguments of the two scalar entry points, padded to four species: the unused ones are constrained to 0
+        on every node (identity rows) with kappa 1."""
+        w = self._vec(w)
+        kap = np.atleast_1d(np.asarray(kappa, dtype=np.float64)).ravel()
+        k, n = len(kap), self.n_local
+        if not 1 <= k <= 4:
+            raise ValueError("kappa: one to four species")
+        mask, val = bcs
+        mask = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask).astype(bool).reshape(n, -1)
+        val = np.asarray(val.cpu() if isinstance(val, torch.Tensor) else val, dtype=np.float64).reshape(n, -1)
+        if mask.shape != (n, k) or val.shape != (n, k):
+            raise ValueError(f"scalar bcs: (mask, values), each of shape ({n}, {k})")
+        m4, v4, k4 = np.ones((n, 4), np.uint8), np.zeros((n, 4)), np.ones(4)
+        m4[:, :k], v4[:, :k], k4[:k] = mask, np.where(mask, val, 0.0), kap
+        src = None
+        if source is not None:
+            src = torch.zeros(n, 4, dtype=torch.float64, device=self.device)
+            src[:, :k] = self._columns(source, k)
+        return (w, k, (C.c_double * 4)(*k4), torch.from_numpy(m4.ravel()).to(self.device),
+                torch.from_numpy(v4.ravel()).to(self.device), src)
+
+    def _columns(self, x, k) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+        x = x.to(self.device, torch.float64).reshape(self.n_local, -1)
+        if x.shape[1] != k:
+            raise ValueError(f"expected shape ({self.n_local}, {k})")
+        return x
+
+    def scalar_system(self, w, kappa, bcs, *, sigma=0.0, theta=0.0, source=None) -> torch.Tensor:
+        """Assemble the transport operator of ``len(kappa)`` (one to four) scalars carried by the velocity of the state ``w``
+        into the handle and return its right-hand side (sns_scalar_system, where the form is written out): species k has
+        diffusivity ``kappa[k]``; ``sigma`` (reaction / 1/dt) and ``theta`` (under the root of tau) are shared.  ``bcs`` =
+        (mask, values), each (n, k): the scalars' own Dirichlet data; ``source``: nodal P1 source (n, k) or None.  The
+        right-hand side comes back as a dof vector of 4 n entries in the node-blocked layout (species k at [k::4]; the slots
+        of unused species hold 0), ready for ``krylov_solve`` / ``adjoint_solve``: the scalar operator is the handle's matrix
+        until the next flow assembly (``jacobian``, ``stokes_solve``, ``newton_solve``).  Single-GPU 3-D problems."""
+        w, _, kap, m, v, src = self._scalar_inputs(w, kappa, bcs, source)
+        rhs = self.zeros()
+        check(self.lib.sns_scalar_system(self.h, _ptr(w), kap, float(sigma), float(theta), _ptr(src), _ptr(m), _ptr(v), _ptr(rhs)))
+        return rhs
+
+    def scalar_solve(self, w, kappa, bcs, *, sigma=0.0, theta=0.0, source=None, c0=None):
+        """``scalar_system`` + preconditioner set-up + the Krylov solve with the problem's options (sns_scalar_solve).
+        ``c0``: initial guess (n, k), default 0.  Returns (c (n, k) device tensor, KrylovResult); a species without a
+        Dirichlet node under sigma = 0 is singular and is not detected."""
+        w, k, kap, m, v, src = self._scalar_inputs(w, kappa, bcs, source)
+        c = torch.zeros(self.n_local, 4, dtype=torch.float64, device=self.device)
+        if c0 is not None:
+            c[:, :k] = self._columns(c0, k)
+        its, reason, rn = C.c_int(), C.c_int(), C.c_double()
+        check(self.lib.sns_scalar_solve(self.h, _ptr(w), kap, float(sigma), float(theta), _ptr(src), _ptr(m), _ptr(v), _ptr(c),
+                                        C.byref(its), C.byref(reason), C.byref(rn)))
+        return c[:, :k].contiguous(), KrylovResult(its.value, reason.value, rn.value)
+
     # -- introspection ----------------------------------------------------------
     def sizes(self):
         nl, no, nt, nz = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
@@ -758,6 +815,43 @@ def solve_unsteady(problem: FlowProblem, w0, dt: float, n_steps: int, order: int
         if callback is not None:
             callback(step, step * dt, w)
     return w, records
+
+
+def solve_scalar_transport(problem: FlowProblem, w, kappa, bcs, source=None):
+    """Steady transport of one to four scalars by the velocity of the state ``w``: u.grad c - kappa_k Lap c = s_k with the
+    Dirichlet data ``bcs`` = (mask, values), each (n, k), and zero diffusive flux elsewhere (``FlowProblem.scalar_solve`` with
+    sigma = theta = 0).  The age of fluid is source = 1 with c = 0 at the inlet.  Returns (c (n, k), KrylovResult).  NOT in the
+    reference."""
+    return problem.scalar_solve(w, kappa, bcs, source=source)
+
+
+def advance_scalars(problem: FlowProblem, w, c0, dt: float, n_steps: int, order: int = 2, callback=None, *, kappa, bcs,
+                    source=None, theta_coeff: float = 4.0):
+    """``n_steps`` implicit steps of size ``dt`` of c_t + u.grad c - kappa_k Lap c = s_k from the nodal field ``c0`` (n, k; not
+    modified), each one ``FlowProblem.scalar_solve``: BDF1 for the first step, then BDF of the given order (1 or 2), i.e.
+    sigma = 1/dt with the source s + c^n/dt, resp. sigma = 3/(2 dt) with s + (2 c^n - c^(n-1)/2)/dt, and theta = theta_coeff /
+    dt^2 under the root of tau.  ``w``: the carrying state, or a callable ``step -> state`` (step = 1..) for a flow that moves,
+    e.g. the states ``solve_unsteady`` hands its callback.  ``callback(step, t, c)`` runs after every converged step.  Stops at
+    the first step that does not converge.  Returns (c, records), one dict(its, reason) per step.  NOT in the reference."""
+    if order not in (1, 2):
+        raise ValueError("order must be 1 or 2")
+    k = len(np.atleast_1d(np.asarray(kappa, dtype=np.float64)).ravel())
+    c = problem._columns(c0, k).clone()
+    cprev = c.clone()
+    s = None if source is None else problem._columns(source, k)
+    records = []
+    for step in range(1, int(n_steps) + 1):
+        o = 1 if step == 1 else order
+        hist = c / dt if o == 1 else (2.0 * c - 0.5 * cprev) / dt
+        cn, res = problem.scalar_solve(w(step) if callable(w) else w, kappa, bcs, sigma=(1.0 if o == 1 else 1.5) / dt,
+                                       theta=theta_coeff / (dt * dt), source=hist if s is None else hist + s, c0=c)
+        records.append(dict(its=res.its, reason=res.reason))
+        if res.reason <= 0:
+            break
+        cprev, c = c, cn
+        if callback is not None:
+            callback(step, step * dt, c)
+    return c, records
 
 
 def pseudo_transient_solve(problem: FlowProblem, w0, dt0: float, growth: float = 10.0, max_steps: int = 60,
