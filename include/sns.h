@@ -503,7 +503,7 @@ SNS_API int sns_adjoint_solve(sns_handle h, const double* g_dev, double* lam_dev
  * sns_krylov_solve); c_dev holds the guess on entry and the solution on exit, rnorm = the 2-norm of the TRUE residual; a
  * converged solve returns the Dirichlet data exactly.  Neither call writes the time term, the viscosity law, the form variant or
  * the options.  Not built: 2-D handles, partitioned handles, discontinuity capturing (expect over- and undershoots of a few
- * per cent at sharp layers), any coupling of c back into the flow.
+ * per cent at sharp layers).  The coupling of c back into the flow is sns_set_mixture below.
  * SNS_E_ARG: null handle / w / kappa / mask / values / output; a 2-D handle; a kappa_k that is <= 0 or not finite; sigma or
  * theta negative or not finite.  SNS_E_STATE: a handle with a communicator attached (any transport, also the local-only split).
  * After an error the handle's matrix is untouched.  Both return after their outputs are written.                          */
@@ -569,6 +569,43 @@ SNS_API int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n
 /* Per-tet viscosity of the state w_dev under the handle's law: nu_dev[t] = nu_e (nu0 = 1/Re without a law),
  * gamma_dot_dev[t] = sqrt(2 eps:eps); n_tets doubles each, either may be NULL.  SNS_E_ARG: a 2-D handle, no state.    */
 SNS_API int sns_element_viscosity(sns_handle h, const double* w_dev, double* nu_dev, double* gamma_dot_dev);
+/* Two external fields of the 3-D NS form (the reference has no counterpart: no form of it has a right-hand side, and its
+ * viscosity is the constant 1/Re).  Both are copied into buffers the handle owns (allocated at the first set); NULL clears.
+ *   sns_set_body_force         f_dev: 4*n_local doubles, node-blocked like the state, pressure slots ignored: a P1 force
+ *                              density f on the right-hand side of the momentum equation;
+ *   sns_set_element_viscosity  nu_dev: n_tets doubles nu_t, every one finite and > 0 (checked on the device: one reduction
+ *                              launch, one host read; a bad entry gives SNS_E_ARG and leaves the handle untouched).
+ * From the call on every NS assembly of the handle -- sns_residual, sns_jacobian, sns_newton_solve, sns_time_step,
+ * sns_adjoint_solve's operator, sns_residual_moments, sns_bench_assemble -- takes, with u_t = sigma u + d the handle's time
+ * term (0 without one) and a = u_t - f:
+ *   - (a, v) added to the Galerkin part (:243-246) and res_M = dot(u, grad(u)) + grad p + a in the SUPG and the PSPG term;
+ *   - without a viscosity field the reference's viscous term nu (grad u, grad v) (:244), nu = 1/Re: a body force alone does
+ *     not change the viscous form;
+ *   - with a viscosity field the stress-divergence form (2 nu_t eps(u), grad v), as under the Carreau law
+ *     (div(2 nu_t eps(u)) vanishes inside a P1 tet with a per-tet nu_t, so res_M has no viscous part);
+ *   - tau = (theta + u.Gu + C_I nu_t^2 G:G)^-1/2 and nu_LSIC = 1/(tr G tau), nu_t = 1/Re where no field is set.
+ * The Jacobian is the exact Gateaux derivative with f, nu_t and d held fixed (f enters it through d tau . res_M; against the
+ * law it gains nu_t (grad du^T, grad v) and no nu' terms).  The handle keeps the caller's d, the caller's f and the effective
+ * history d - f the kernels read, rewritten whenever d or f changes (sns_time_step included).  The Stokes form ignores both
+ * fields; sns_set_form_variant and corrected_convection apply as without them.  Clearing both gives back the handle as it
+ * was, bit for bit.  An assembled matrix stays what it was; a changed viscosity field makes the next preconditioner set-up
+ * re-estimate its smoother damping, a changed body force does not.
+ *   sns_set_mixture  the convenience for two miscible fluids: from a nodal P1 field m_dev (n_local doubles, typically species
+ *                    0 of a scalar solve) it sets, in one small kernel (csrc/sns_fields.hip),
+ *                      nu_t = (1/Re) exp(log_viscosity_ratio * 1/4 sum_a m_a)   (log-mixing rule at the centroid: positive
+ *                                                                               whatever over- or undershoot m has),
+ *                      f_a  = m_a * buoyancy                                    (Boussinesq; buoyancy = Ri * g_hat).
+ *                    It reads opt.reynolds AT THE CALL: a later sns_set_options does not rescale the field.
+ *                    log_viscosity_ratio == 0 clears the viscosity field, buoyancy == {0,0,0} (or NULL) clears the body
+ *                    force, m_dev == NULL clears both.
+ * sns_element_viscosity reports the field where one is set.
+ * SNS_E_ARG: a null handle; a 2-D handle; a viscosity entry that is <= 0 or not finite; a log ratio or buoyancy that is not
+ * finite.  SNS_E_STATE: a handle with a communicator attached (any transport, also the local-only split); a handle with a
+ * Carreau law set (sns_set_viscosity_law(CARREAU) refuses the same way while either field is set, and so does
+ * sns_residual_shape_gradient: the mesh derivative is not built with them).  After a refusal the handle is untouched.      */
+SNS_API int sns_set_body_force(sns_handle h, const double* f_dev);
+SNS_API int sns_set_element_viscosity(sns_handle h, const double* nu_dev);
+SNS_API int sns_set_mixture(sns_handle h, const double* m_dev, double log_viscosity_ratio, const double buoyancy[3]);
 
 /* ---- introspection (tests, profiling) --------------------------------------*/
 /* device pointers of the assembled BSR4 operator (block row-major 4x4); the values are those of A^T while the handle

@@ -123,6 +123,9 @@ _SIGNATURES = [
                                 C.POINTER(C.c_int)]),
     ("sns_set_viscosity_law", C.c_int, [_H, C.c_int, C.c_double, C.c_double, C.c_double]),
     ("sns_element_viscosity", C.c_int, [_H, _P, _P, _P]),
+    ("sns_set_body_force", C.c_int, [_H, _P]),
+    ("sns_set_element_viscosity", C.c_int, [_H, _P]),
+    ("sns_set_mixture", C.c_int, [_H, _P, C.c_double, C.POINTER(C.c_double)]),
     ("sns_newton_solve", C.c_int, [_H, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_double), C.c_int]),
     ("sns_get_bsr", C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P),

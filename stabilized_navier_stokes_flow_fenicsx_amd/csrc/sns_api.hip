@@ -540,6 +540,10 @@ int sns_residual_shape_gradient(sns_handle h, int form, const double* w, const d
         set_error("sns_residual_shape_gradient: not with a viscosity law set (the mesh derivative of nu_e is not built)");
         return SNS_E_STATE;
     }
+    if (h->bf_on || h->ev_on) {
+        set_error("sns_residual_shape_gradient: not with a body force or a viscosity field set (the mesh derivative is not built with them)");
+        return SNS_E_STATE;
+    }
     return residual_shape_gradient(h, w, lam, gX);
 }
 
@@ -812,20 +816,19 @@ int sns_set_time_term(sns_handle h, double sigma, double theta, const double* d_
         h->pc_ready = false;
     }
     if (sigma == 0.0 && theta == 0.0 && !d_dev) {         // back to the steady form (the buffer stays with the handle)
-        h->tt = TimeTerm();
+        h->tt.sigma = h->tt.theta = 0.0;
         h->tt_on = false;
-        return SNS_OK;
+        return refresh_history(h);                        // (a body force stays: the history is -f again)
     }
     const size_t ld = (size_t)ld_of(h);
     if (!h->tt_d) SNS_TRY(h->tt_d.alloc(ld));
     if (d_dev) HIP_TRY(hipMemcpyAsync(h->tt_d, d_dev, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     else HIP_TRY(hipMemsetAsync(h->tt_d, 0, ld * sizeof(double), h->stream));
-    SNS_TRY(sync_stream(h));                              // the caller may free d_dev
     h->tt.sigma = sigma;
     h->tt.theta = theta;
-    h->tt.d = h->tt_d;
     h->tt_on = true;
-    return SNS_OK;
+    SNS_TRY(refresh_history(h));                          // tt.d = the handle's d, or d - f under a body force
+    return sync_stream(h);                                // the caller may free d_dev
 }
 
 int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double nu_inf_ratio) {
@@ -842,6 +845,10 @@ int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double
     }
     if (h->comm) { set_error("sns_set_viscosity_law: not with a communicator attached (partitioned handles have no law)"); return SNS_E_STATE; }
     if (h->tt_on) { set_error("sns_set_viscosity_law: not with a time term set (the transient form has no law)"); return SNS_E_STATE; }
+    if (law == SNS_LAW_CARREAU && (h->bf_on || h->ev_on)) {
+        set_error("sns_set_viscosity_law: not with a body force or a viscosity field set");
+        return SNS_E_STATE;
+    }
     ViscosityLaw vl;
     if (law == SNS_LAW_CARREAU) { vl.lambda = lambda; vl.n = n; vl.r = nu_inf_ratio; }
     const bool on = law == SNS_LAW_CARREAU;
@@ -857,6 +864,10 @@ int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double
 int sns_element_viscosity(sns_handle h, const double* w, double* nu_dev, double* gamma_dot_dev) {
     if (!h || !w) { set_error("sns_element_viscosity: null handle or state"); return SNS_E_ARG; }
     if (h->dim != 3) { set_error("sns_element_viscosity: 3-D handles only"); return SNS_E_ARG; }
+    if (h->E > 0 && h->ev_on && nu_dev) {               // the field where one is set (gamma_dot below as without one)
+        HIP_TRY(hipMemcpyAsync(nu_dev, h->ev_nu, (size_t)h->E * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        nu_dev = nullptr;
+    }
     if (h->E > 0 && (nu_dev || gamma_dot_dev)) {
         const unsigned gt = (unsigned)((h->E + 255) / 256);
         const double nu = 1.0 / h->opt.reynolds;
@@ -867,6 +878,36 @@ int sns_element_viscosity(sns_handle h, const double* w, double* nu_dev, double*
         HIP_TRY(hipGetLastError());
     }
     return sync_stream(h);
+}
+
+// the checks the three field setters share (`who`: the name in front of the message)
+static int fields_check(const char* who, sns_ctx* h) {
+    const std::string name(who);
+    if (!h) { set_error(name + ": null handle"); return SNS_E_ARG; }
+    if (h->dim != 3) { set_error(name + ": 3-D handles only"); return SNS_E_ARG; }
+    if (h->comm) { set_error(name + ": not with a communicator attached (partitioned handles have no external fields)"); return SNS_E_STATE; }
+    if (h->vl_on) { set_error(name + ": not with a viscosity law set"); return SNS_E_STATE; }
+    return SNS_OK;
+}
+
+int sns_set_body_force(sns_handle h, const double* f_dev) {
+    SNS_TRY(fields_check("sns_set_body_force", h));
+    return set_body_force(h, f_dev);
+}
+
+int sns_set_element_viscosity(sns_handle h, const double* nu_dev) {
+    SNS_TRY(fields_check("sns_set_element_viscosity", h));
+    return set_element_viscosity(h, nu_dev);
+}
+
+int sns_set_mixture(sns_handle h, const double* m_dev, double log_viscosity_ratio, const double buoyancy[3]) {
+    SNS_TRY(fields_check("sns_set_mixture", h));
+    if (!std::isfinite(log_viscosity_ratio)) { set_error("sns_set_mixture: the log viscosity ratio must be finite"); return SNS_E_ARG; }
+    if (buoyancy && !(std::isfinite(buoyancy[0]) && std::isfinite(buoyancy[1]) && std::isfinite(buoyancy[2]))) {
+        set_error("sns_set_mixture: the buoyancy must be finite");
+        return SNS_E_ARG;
+    }
+    return set_mixture(h, m_dev, log_viscosity_ratio, buoyancy);
 }
 
 int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, double theta_coeff, int* its, int* reason,

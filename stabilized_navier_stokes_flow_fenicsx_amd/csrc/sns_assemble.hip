@@ -18,7 +18,7 @@ struct FormPass {
     ViscosityLaw vl;
 };
 
-// THE place where (corrected convection, ns_variant) becomes the <C, TT, VL> of the 3-D NS assembly kernels: a new compile-time
+// THE place where (corrected convection, ns_variant) becomes the <C, TT, VL, EV> of the 3-D NS assembly kernels: a new compile-time
 // variant is added to the kernels' instantiation lists (csrc/sns_kernels.hip) and here, nowhere else.
 FormPass form_pass(const sns_ctx* h, int form) {
     const double nu = 1.0 / h->opt.reynolds;
@@ -33,10 +33,11 @@ FormPass form_pass(const sns_ctx* h, int form) {
                 nullptr, nu, 0.0, TimeTerm(), ViscosityLaw()};
     FormPass k{};
     dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-        dispatch<2, 1, 0>(ns_variant(h), [&](auto V) {
-            constexpr bool c = C() != 0, tt = V() == 1, vl = V() == 2;
-            k = {&k_fused_offdiag<SNS_FORM_NS, c, tt, vl>, &k_fused_diag<SNS_FORM_NS, c, tt, vl>, &k_fused_lift<SNS_FORM_NS, c, tt, vl>,
-                 &k_element<SNS_FORM_NS, c, tt, vl>, &k_residual_tet<c, tt, vl>, nu, 0.0, h->tt, h->vl};
+        dispatch<3, 2, 1, 0>(ns_variant(h), [&](auto V) {
+            constexpr bool c = C() != 0, ev = V() == 3, tt = V() == 1 || ev, vl = V() == 2;
+            k = {&k_fused_offdiag<SNS_FORM_NS, c, tt, vl, ev>, &k_fused_diag<SNS_FORM_NS, c, tt, vl, ev>,
+                 &k_fused_lift<SNS_FORM_NS, c, tt, vl, ev>, &k_element<SNS_FORM_NS, c, tt, vl, ev>, &k_residual_tet<c, tt, vl, ev>,
+                 nu, 0.0, h->tt, h->vl};
         });
     });
     return k;
@@ -174,6 +175,7 @@ int residual_moments(sns_ctx* h, int form, const double* w, const double* phi, d
         h->rm_cap = 0;
         SNS_TRY(h->rm_cells.alloc((size_t)4 * nc));
         SNS_TRY(h->rm_Fe.alloc((size_t)16 * nc));
+        h->rm_nu.reset();
         h->rm_cap = nc;
     }
     if (nc > 0) {
@@ -188,7 +190,12 @@ int residual_moments(sns_ctx* h, int form, const double* w, const double* phi, d
             SNS_TRY(h->rm_nomask.alloc((size_t)ndof));
             HIP_TRY(hipMemset(h->rm_nomask, 0, (size_t)ndof));
         }
-        launch_element_pass(h, form, form_pass(h, form), kind, nc, h->rm_cells, w, h->rm_nomask, false, nullptr, h->rm_Fe);
+        FormPass K = form_pass(h, form);
+        if (form == SNS_FORM_NS && h->ev_on) {           // the element kernels index the field by the cell of their pass
+            SNS_TRY(support_nu(h, phi, nc));
+            K.tt.nu_t = h->rm_nu;
+        }
+        launch_element_pass(h, form, K, kind, nc, h->rm_cells, w, h->rm_nomask, false, nullptr, h->rm_Fe);
     }
     // fixed-order two-stage reduction (grid fixed by the support size), then the handle's all-reduce over the ranks
     const int gm = (int)std::max<int64_t>(1, std::min<int64_t>((nc + 255) / 256, 2048));

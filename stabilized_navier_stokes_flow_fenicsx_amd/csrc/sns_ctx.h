@@ -108,7 +108,7 @@ struct sns_ctx {
     DevBuf<int> d_sing;
     FormVariant fv;                              // sns_set_form_variant (diagnostic; default = the reference's form)
     // sns_set_time_term: the transient 3-D NS form.  tt.d points at tt_d, the handle's copy of the history (4*n doubles,
-    // allocated at the first set); tt_on selects the TT instantiations of the NS assembly kernels
+    // allocated at the first set), or at tt_eff below; tt_on selects the TT instantiations of the NS assembly kernels
     TimeTerm tt;
     DevBuf<double> tt_d;
     DevBuf<double> tt_w0;                        // sns_time_step: the state on entry
@@ -116,6 +116,13 @@ struct sns_ctx {
     // sns_set_viscosity_law: the generalised-Newtonian 3-D NS form; vl_on selects the VL instantiations (never with tt_on)
     ViscosityLaw vl;
     bool vl_on = false;
+    // sns_set_body_force / sns_set_element_viscosity (csrc/sns_fields.hip): the caller's f, the effective history tt_eff = d - f
+    // that tt.d points at while a force is on (d = tt_d under a time term, 0 without; rewritten whenever d or f changes; all zero
+    // for a viscosity field alone), and the per-cell nu_t behind tt.nu_t.  bf_on runs the TT instantiations, ev_on the EV ones
+    // (never with vl_on)
+    DevBuf<double> bf_f, tt_eff, ev_nu;
+    bool bf_on = false, ev_on = false;
+    DevBuf<double> rm_nu;                        // residual moments: nu_t of the compacted cells (capacity rm_cap)
     bool has_matrix = false, pc_ready = false;
     int pc_setups = 0;
     // hipGraph of the launch-bound coarse part of the V-cycle (levels >= graph_level; serial runs only)
@@ -257,6 +264,13 @@ int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, 
 // csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)
 int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sigma, double theta, const double* src,
                   const uint8_t* cmask, const double* cval, double* rhs);
+// csrc/sns_fields.hip: the external fields of the 3-D NS form (arguments checked by the entry points).  refresh_history points
+// tt.d at what the kernels read after d or f changed; support_nu gathers nu_t of the cells k_support_scatter keeps
+int refresh_history(sns_ctx* h);
+int set_body_force(sns_ctx* h, const double* f);
+int set_element_viscosity(sns_ctx* h, const double* nu);
+int set_mixture(sns_ctx* h, const double* m, double log_ratio, const double buoyancy[3]);
+int support_nu(sns_ctx* h, const double* phi, int64_t nc);
 // ... and the fine level's free mask (with the per-aggregate counts derived from it) set to the complement of a Dirichlet mask
 int fine_free_mask(sns_ctx* h, const uint8_t* dirichlet_mask);
 // csrc/sns_aggregate.hip: aggregate_strength's map of the owned nodes, built on the device (amg_aggregation = 2)
@@ -472,9 +486,10 @@ inline void dispatch(int v, Fn&& fn) {
 template <class Fn>
 inline void with_fmt(int fmt, Fn&& fn) { dispatch<2, 1>(fmt, fn); }
 
-// the compile-time variant of the 3-D NS assembly kernels a handle runs: 0 the reference's steady form, 1 with a time term
-// (TT), 2 with a viscosity law (VL); the two are never on together
-inline int ns_variant(const sns_ctx* h) { return h->vl_on ? 2 : (h->tt_on ? 1 : 0); }
+// the compile-time variant of the 3-D NS assembly kernels a handle runs: 0 the reference's steady form, 1 with a time term or
+// a body force (TT: the force rides in the effective history), 2 with a viscosity law (VL; never with the others), 3 with a
+// viscosity field (EV: contains the time term, so it serves the field with or without a time term or a force)
+inline int ns_variant(const sns_ctx* h) { return h->ev_on ? 3 : (h->vl_on ? 2 : ((h->tt_on || h->bf_on) ? 1 : 0)); }
 
 // a level's matrix copy in format F -- values and row scales (nullptr in fp32) -- and the same of M = A P (borrowed pointers)
 struct LpMat {

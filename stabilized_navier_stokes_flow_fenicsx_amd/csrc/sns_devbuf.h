@@ -3,7 +3,7 @@
 // `if (!h->x)` guards read as with raw pointers.  A struct made of them frees on every way out.  None may have static or
 // thread-local storage duration: it would be destroyed after the HIP runtime has shut down.
 // Pointers that are only borrowed stay raw and say so where they are declared: the kernel argument structs (GhostSrc, PutDst,
-// AgPut / AgGet, PeerArgs, TimeTerm::d, LpMat), a plan's places in its communicator's window, the caller's stream.
+// AgPut / AgGet, PeerArgs, TimeTerm::d and ::nu_t, LpMat), a plan's places in its communicator's window, the caller's stream.
 // DevBuf needs no HIP header (csrc/sns_internal.h is compiled by g++ too); the HIP owners exist under hipcc only.
 #pragma once
 #include <cstddef>

@@ -31,10 +31,15 @@ struct FormVariant {
 // Time term of the 3-D NS form (sns_set_time_term; the reference has no unsteady form): u_t = sigma u + d with the nodal
 // history d (node-blocked like the state, pressure slots unused), (u_t, v) added to the Galerkin part, u_t added to the
 // strong residual res_M of the SUPG/PSPG term, theta added under the root of tau.  The kernels take it as the compile-time
-// variant TT; the steady instantiations (TT = false) never read the struct.
+// variant TT; the steady instantiations (TT = false) never read the struct.  d is the EFFECTIVE history: the caller's d minus the
+// body force f of sns_set_body_force (a = u_t - f enters wherever u_t does).
+// Per-cell viscosity field (sns_set_element_viscosity): nu_t[cell of the pass] replaces nu; the viscous Galerkin term is the
+// stress-divergence form (2 nu_t eps(u), grad v), as under the law but with nu_t held fixed.  The compile-time variant EV, which
+// contains the time term (sigma = theta = 0 and a zero history where none is set); only the EV instantiations read nu_t.
 struct TimeTerm {
     double sigma = 0.0, theta = 0.0;
     const double* d = nullptr;
+    const double* nu_t = nullptr;
 };
 
 // Generalised-Newtonian viscosity of the 3-D NS form (sns_set_viscosity_law): the Carreau law on the per-tet shear rate,
@@ -46,25 +51,25 @@ struct ViscosityLaw {
     double lambda = 0.0, n = 1.0, r = 0.0;
 };
 
-template <int FORM, bool corrected, bool TT = false, bool VL = false>
+template <int FORM, bool corrected, bool TT = false, bool VL = false, bool EV = false>
 __global__ void k_element(int64_t n_tets, const int32_t* tets, const double* pts, const double* w,
                           const uint8_t* bc_mask, const double* bc_val, double nu, int store_K, double* Ke,
                           double* Fe, FormVariant fv, TimeTerm tt, ViscosityLaw vl);
-template <int FORM, bool corrected, bool TT = false, bool VL = false>
+template <int FORM, bool corrected, bool TT = false, bool VL = false, bool EV = false>
 __global__ void k_fused_offdiag(int64_t n_od, const int32_t* od_order, const int64_t* c_ptr, const int32_t* c_idx, const int32_t* slot_row,
                                 const int32_t* colind, const int32_t* tets, const double* pts, const double* w,
                                 const uint8_t* bc_mask, double nu, double aux, double* vals, TimeTerm tt, ViscosityLaw vl);
-template <int FORM, bool corrected, bool TT = false, bool VL = false>
+template <int FORM, bool corrected, bool TT = false, bool VL = false, bool EV = false>
 __global__ void k_fused_diag(int32_t n_rows, const int32_t* diag, const int64_t* c_ptr, const int32_t* c_idx,
                              const int32_t* tets, const double* pts, const double* w, const uint8_t* bc_mask,
                              const double* bc_val, double nu, double aux, double* vals, double* F, TimeTerm tt,
                              ViscosityLaw vl);
-template <int FORM, bool corrected, bool TT = false, bool VL = false>
+template <int FORM, bool corrected, bool TT = false, bool VL = false, bool EV = false>
 __global__ void k_fused_lift(int32_t n_rows, const int32_t* diag, const int64_t* c_ptr, const int32_t* c_idx,
                              const int32_t* tets, const double* pts, const double* w, const uint8_t* bc_mask,
                              const double* dl, double nu, double* F, TimeTerm tt, ViscosityLaw vl);
 __global__ void k_bc_defect(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, const double* w, double* dl);
-template <bool corrected, bool TT = false, bool VL = false>
+template <bool corrected, bool TT = false, bool VL = false, bool EV = false>
 __global__ void k_residual_tet(int64_t n_tets, const int32_t* tets, const double* pts, const double* w, double nu,
                                double* Fe, TimeTerm tt, ViscosityLaw vl);
 // per tet: nu_e of the law (nu0 where LAW is false) and gamma_dot = sqrt(2 eps:eps); either output may be null

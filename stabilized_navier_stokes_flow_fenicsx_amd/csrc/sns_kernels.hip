@@ -63,6 +63,12 @@ struct TetLdsV : TetLds {
     double vs[3];
 };
 
+// ... with a viscosity field (EV): the time term's data, eps g_a per vertex and the tet's nu_t
+struct TetLdsE : TetLdsT {
+    double eg[12];     // (eps g_a) [a][i]
+    double nue;
+};
+
 __device__ __forceinline__ double phi_q(int q, int a) { return q == a ? QB : QA; }
 
 // s = 2 eps:eps (= gamma_dot^2) of a constant grad u, eps = sym(grad u)
@@ -87,7 +93,7 @@ __device__ __forceinline__ void carreau(const ViscosityLaw& vl, double nu0, doub
     dnu = nu0 * (1.0 - vl.r) * e * l2 * (pw / x);
 }
 
-template <int FORM, bool corrected, bool TT, bool VL>
+template <int FORM, bool corrected, bool TT, bool VL, bool EV>
 __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int32_t* __restrict__ tets,
                                                     const double* __restrict__ pts,
                                                     const double* __restrict__ w,
@@ -97,9 +103,10 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                                                     double* __restrict__ Fe, FormVariant fv, TimeTerm tt,
                                                     ViscosityLaw vl) {
     static_assert(!VL || (FORM == SNS_FORM_NS && !TT), "the viscosity law exists in the steady 3-D NS form only");
+    static_assert(!EV || (FORM == SNS_FORM_NS && TT && !VL), "the viscosity field is a variant of the 3-D NS form with the time term");
     // staging data and the output transpose tile share LDS (the tile is written after a barrier
     // that retires every read of the staging data): 34.8 KB per workgroup -> 4 workgroups per CU
-    using Lds = std::conditional_t<TT, TetLdsT, std::conditional_t<VL, TetLdsV, TetLds>>;
+    using Lds = std::conditional_t<EV, TetLdsE, std::conditional_t<TT, TetLdsT, std::conditional_t<VL, TetLdsV, TetLds>>>;
     constexpr size_t SH_BYTES = sizeof(Lds) * EL_TETS, TILE_BYTES = sizeof(double) * EL_TPB * 17;
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[SH_BYTES > TILE_BYTES ? SH_BYTES : TILE_BYTES];
     Lds* sh = reinterpret_cast<Lds*>(lds_raw);
@@ -200,6 +207,18 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                 S.vs[2] = 4.0 * fv.ci * nu_t * dnu * GG;   // d(C_I nu_e^2 G:G)/2 = vs[2] (eps g_b) . du_b
             }
         }
+        if constexpr (EV) {
+            nu_t = tt.nu_t[t];
+            if (q == 0) {
+#pragma unroll
+                for (int aa = 0; aa < 4; ++aa) {
+                    double e3[3];
+                    eps_apply(gu, g[aa], e3);
+                    S.eg[3 * aa] = e3[0]; S.eg[3 * aa + 1] = e3[1]; S.eg[3 * aa + 2] = e3[2];
+                }
+                S.nue = nu_t;
+            }
+        }
         if (q == 0) {
 #pragma unroll
             for (int aa = 0; aa < 4; ++aa)
@@ -296,7 +315,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
         // viscosity law: nu_e for nu, the viscous term 2 nu_e eps g_a, d tau and d nu_LSIC gain kb = 4 C_I nu_e nu' G:G eps g_b
         // (eps g_a and eps g_b stay in LDS: only kb lives across the quadrature loop)
         auto eg = [&](int k) -> double {
-            if constexpr (VL) return S.eg[k];
+            if constexpr (VL || EV) return S.eg[k];
             else return 0.0;
         };
         double nu_t = nu, kb[3] = {0.0, 0.0, 0.0};
@@ -305,6 +324,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
 #pragma unroll
             for (int j = 0; j < 3; ++j) kb[j] = S.vs[2] * eg(3 * b + j);
         }
+        if constexpr (EV) nu_t = S.nue;
         if (FORM == SNS_FORM_STOKES) {
             const double vol = 4.0 * wd;
             const double muT = 0.2 * S.sc[3];                                            // :169
@@ -406,7 +426,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                     if (!corrected) {
 #pragma unroll
                         for (int i = 0; i < 3; ++i)
-                            Rl[i] += Q[9 + i] * pa + (VL ? 2.0 * nu_t * eg(3 * a + i) : nu * guga_a[i]) - p * ga[i] + tau * u[i] * sa +
+                            Rl[i] += Q[9 + i] * pa + ((VL || EV) ? 2.0 * nu_t * eg(3 * a + i) : nu * guga_a[i]) - p * ga[i] + tau * u[i] * sa +
                                      nuL * divu * ga[i];
                         if constexpr (TT) {
 #pragma unroll
@@ -423,7 +443,7 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                                               gum[6] * ga0 + gum[7] * ga1 + gum[8] * ga2};
 #pragma unroll
                         for (int i = 0; i < 3; ++i)
-                            Rl[i] += Q[9 + i] * pa + (VL ? 2.0 * nu_t * eg(3 * a + i) : nu * vg[i]) - p * ga[i] + tau * uga * (Q[9 + i] + gp[i]) +
+                            Rl[i] += Q[9 + i] * pa + ((VL || EV) ? 2.0 * nu_t * eg(3 * a + i) : nu * vg[i]) - p * ga[i] + tau * uga * (Q[9 + i] + gp[i]) +
                                      nuL * divu * ga[i];
                         if constexpr (TT) {
 #pragma unroll
@@ -442,6 +462,18 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
                         const double ei = c2 * S.eg[3 * a + i], gi = c1 * gb[i];
 #pragma unroll
                         for (int j = 0; j < 3; ++j) acc[4 * i + j] += gi * ga[j] + ei * S.eg[3 * b + j];
+                    }
+                }
+            }
+            if constexpr (EV) {
+                // point-independent: the transpose half of 2 nu_t d eps (nu_t is held fixed: no rank-one part)
+                if (need_blocks) {
+                    const double c1 = 4.0 * nu_t;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const double gi = c1 * gb[i];
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) acc[4 * i + j] += gi * ga[j];
                     }
                 }
             }
@@ -491,17 +523,19 @@ __global__ __launch_bounds__(EL_TPB, 3) void k_element(int64_t n_tets, const int
     }
 }
 
-#define SNS_INST_ELEMENT(F, C, T, V)                                                                        \
-    template __global__ void k_element<F, C, T, V>(int64_t, const int32_t*, const double*, const double*,      \
+#define SNS_INST_ELEMENT(F, C, T, V, E)                                                                     \
+    template __global__ void k_element<F, C, T, V, E>(int64_t, const int32_t*, const double*, const double*,      \
                                                    const uint8_t*, const double*, double, int, double*, double*, \
                                                    FormVariant, TimeTerm, ViscosityLaw);
-SNS_INST_ELEMENT(SNS_FORM_STOKES, false, false, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, false, false, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, true, false, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, false, true, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, true, true, false)
-SNS_INST_ELEMENT(SNS_FORM_NS, false, false, true)
-SNS_INST_ELEMENT(SNS_FORM_NS, true, false, true)
+SNS_INST_ELEMENT(SNS_FORM_STOKES, false, false, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, false, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, false, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, true, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, true, false, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, false, true, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, false, true, false)
+SNS_INST_ELEMENT(SNS_FORM_NS, false, true, false, true)
+SNS_INST_ELEMENT(SNS_FORM_NS, true, true, false, true)
 
 // quad-permute a double with DPP moves (no LDS, no memory traffic); CTRL = quad_perm encoding
 template <int CTRL>
@@ -521,7 +555,7 @@ __device__ __forceinline__ double quad_perm(double v) {
 // when the state satisfies the Dirichlet data (no lifting term, :65), i.e. every Newton iterate
 // after the first update; the staged k_element path handles the rest.
 // ============================================================================
-template <bool corrected, bool TT, bool VL>
+template <bool corrected, bool TT, bool VL, bool EV>
 __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double* __restrict__ pts,
                                                      const double* __restrict__ w, double nu, int a, int b,
                                                      bool want_res, double acc[16], double Ra[4], const TimeTerm& tt,
@@ -627,6 +661,18 @@ __device__ __forceinline__ void tet_block_accumulate(const int4 tv, const double
             for (int j = 0; j < 3; ++j) acc[4 * i + j] += c1 * gb[i] * ga[j] + c2 * ea[i] * eb[j];
             visc[i] = 2.0 * ea[i];
             kb[i] = kap * eb[i];
+        }
+    }
+    // viscosity field (nu = the cell's nu_t, handed over by the caller): 2 nu_t eps g_a likewise, nu_t held fixed
+    if constexpr (EV) {
+        double ea[3];
+        eps_apply(gu, ga, ea);
+        const double c1 = 4.0 * wd * nu_t;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[4 * i + j] += c1 * gb[i] * ga[j];
+            visc[i] = 2.0 * ea[i];
         }
     }
     // the quadrature weight wd is folded into the per-point coefficients, so every term lands directly in the
@@ -1007,22 +1053,23 @@ __device__ __forceinline__ void tri_block_accumulate_stokes(const int4 tv, const
 
 // one interface for the four forms (aux: Stokes 2-D pressure-stabilisation coefficient beta; nu: 1/Re, or the
 // Stokes 2-D viscosity)
-template <int FORM, bool corrected, bool TT, bool VL>
+template <int FORM, bool corrected, bool TT, bool VL, bool EV>
 __device__ __forceinline__ void block_accumulate(const int4 tv, const double* __restrict__ pts,
                                                  const double* __restrict__ w, double nu, double aux, int a, int b,
                                                  bool want_res, double acc[16], double Ra[4], const TimeTerm& tt,
                                                  const ViscosityLaw& vl) {
     static_assert(!TT || FORM == SNS_FORM_NS, "the time term exists in the 3-D NS form only");
     static_assert(!VL || (FORM == SNS_FORM_NS && !TT), "the viscosity law exists in the steady 3-D NS form only");
+    static_assert(!EV || (FORM == SNS_FORM_NS && TT && !VL), "the viscosity field is a variant of the 3-D NS form with the time term");
     if constexpr (FORM == SNS_FORM_STOKES) tet_block_accumulate_stokes(tv, pts, w, a, b, want_res, acc, Ra);
-    else if constexpr (FORM == SNS_FORM_NS) tet_block_accumulate<corrected, TT, VL>(tv, pts, w, nu, a, b, want_res, acc, Ra, tt, vl);
+    else if constexpr (FORM == SNS_FORM_NS) tet_block_accumulate<corrected, TT, VL, EV>(tv, pts, w, nu, a, b, want_res, acc, Ra, tt, vl);
     else if constexpr (FORM == SNS_FORM_STOKES_2D) tri_block_accumulate_stokes(tv, pts, w, nu, aux, a, b, want_res, acc, Ra);
     else tri_block_accumulate_ugn(tv, pts, w, nu, a, b, want_res, acc, Ra);
 }
 constexpr bool form_is_linear(int form) { return form == SNS_FORM_STOKES || form == SNS_FORM_STOKES_2D; }
 
 // off-diagonal BSR blocks: one lane per slot, slots taken from the host's count-sorted list
-template <int FORM, bool corrected, bool TT, bool VL>
+template <int FORM, bool corrected, bool TT, bool VL, bool EV>
 __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32_t* __restrict__ od_order,
                                                        const int64_t* __restrict__ c_ptr,
                                                        const int32_t* __restrict__ c_idx,
@@ -1057,7 +1104,9 @@ __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32
             id = (uint32_t)c_idx[k];
             tv = *reinterpret_cast<const int4*>(tets + 4 * (int64_t)(id >> 4));
         }
-        block_accumulate<FORM, corrected, TT, VL>(tvc, pts, w, nu, aux, (idc >> 2) & 3, idc & 3, false, acc, nullptr, tt, vl);
+        double nuc = nu;                             // viscosity field: the cell's nu_t, read once per contribution
+        if constexpr (EV) nuc = tt.nu_t[idc >> 4];
+        block_accumulate<FORM, corrected, TT, VL, EV>(tvc, pts, w, nuc, aux, (idc >> 2) & 3, idc & 3, false, acc, nullptr, tt, vl);
     }
     const uchar4 mr = *reinterpret_cast<const uchar4*>(bc_mask + 4 * (int64_t)row);
     const uchar4 mc = *reinterpret_cast<const uchar4*>(bc_mask + 4 * (int64_t)col);
@@ -1073,7 +1122,7 @@ __global__ __launch_bounds__(256) void k_fused_offdiag(int64_t n_od, const int32
 }
 
 // diagonal blocks + node residuals: 4 lanes per node share the ~24 incident tets, DPP quad sums in a fixed order
-template <int FORM, bool corrected, bool TT, bool VL>
+template <int FORM, bool corrected, bool TT, bool VL, bool EV>
 __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_t* __restrict__ diag,
                                                     const int64_t* __restrict__ c_ptr,
                                                     const int32_t* __restrict__ c_idx,
@@ -1103,12 +1152,14 @@ __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_
         while (k < k1) {
             const int a = (id >> 2) & 3;
             const int4 tvc = tv;
+            double nuc = nu;
+            if constexpr (EV) nuc = tt.nu_t[id >> 4];
             k += 4;
             if (k < k1) {
                 id = (uint32_t)c_idx[k];
                 tv = *reinterpret_cast<const int4*>(tets + 4 * (int64_t)(id >> 4));
             }
-            block_accumulate<FORM, corrected, TT, VL>(tvc, pts, w, nu, aux, a, a, true, acc, R, tt, vl);
+            block_accumulate<FORM, corrected, TT, VL, EV>(tvc, pts, w, nuc, aux, a, a, true, acc, R, tt, vl);
         }
     }
     // quad sums: (l0 + l1) + (l2 + l3), identical on every lane
@@ -1151,7 +1202,7 @@ __global__ __launch_bounds__(256) void k_fused_diag(int32_t n_rows, const int32_
 // Lifting term of a state that violates its Dirichlet data (:65): F_free += A0[:,B] (g - x_B), A0 = the unconstrained
 // Jacobian.  Same work split as k_fused_diag (4 lanes per node, DPP quad sums); only tets with a violated Dirichlet
 // dof (dl != 0 on one of their nodes) cost anything: their blocks (a,b) are recomputed and applied to dl_b.
-template <int FORM, bool corrected, bool TT, bool VL>
+template <int FORM, bool corrected, bool TT, bool VL, bool EV>
 __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_t* __restrict__ diag,
                                                     const int64_t* __restrict__ c_ptr,
                                                     const int32_t* __restrict__ c_idx,
@@ -1171,6 +1222,8 @@ __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_
             const int a = (id >> 2) & 3;
             const int4 tv = *reinterpret_cast<const int4*>(tets + 4 * (int64_t)(id >> 4));
             const int32_t nd[4] = {tv.x, tv.y, tv.z, tv.w};
+            double nuc = nu;
+            if constexpr (EV) nuc = tt.nu_t[id >> 4];
             constexpr int NPE = (FORM == SNS_FORM_UGN_2D || FORM == SNS_FORM_STOKES_2D) ? 3 : 4;
 #pragma unroll 1
             for (int b = 0; b < NPE; ++b) {
@@ -1180,7 +1233,7 @@ __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_
                 double blk[16];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) blk[e] = 0.0;
-                block_accumulate<FORM, corrected, TT, VL>(tv, pts, w, nu, 0.0, a, b, false, blk, nullptr, tt, vl);
+                block_accumulate<FORM, corrected, TT, VL, EV>(tv, pts, w, nuc, 0.0, a, b, false, blk, nullptr, tt, vl);
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
                     R[c] += blk[4 * c] * d01.x + blk[4 * c + 1] * d01.y + blk[4 * c + 2] * d23.x + blk[4 * c + 3] * d23.y;
@@ -1199,17 +1252,19 @@ __global__ __launch_bounds__(256) void k_fused_lift(int32_t n_rows, const int32_
     const double rq = q == 0 ? R[0] : (q == 1 ? R[1] : (q == 2 ? R[2] : R[3]));
     if (!bc_mask[dof]) F[dof] += rq;
 }
-#define SNS_INST_LIFT(FM, C, T, V)                                                                                     \
-    template __global__ void k_fused_lift<FM, C, T, V>(int32_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
+#define SNS_INST_LIFT(FM, C, T, V, E)                                                                                   \
+    template __global__ void k_fused_lift<FM, C, T, V, E>(int32_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
                                                        const double*, const double*, const uint8_t*, const double*, double, \
                                                        double*, TimeTerm, ViscosityLaw);
-SNS_INST_LIFT(SNS_FORM_NS, false, false, false)
-SNS_INST_LIFT(SNS_FORM_NS, true, false, false)
-SNS_INST_LIFT(SNS_FORM_UGN_2D, false, false, false)
-SNS_INST_LIFT(SNS_FORM_NS, false, true, false)
-SNS_INST_LIFT(SNS_FORM_NS, true, true, false)
-SNS_INST_LIFT(SNS_FORM_NS, false, false, true)
-SNS_INST_LIFT(SNS_FORM_NS, true, false, true)
+SNS_INST_LIFT(SNS_FORM_NS, false, false, false, false)
+SNS_INST_LIFT(SNS_FORM_NS, true, false, false, false)
+SNS_INST_LIFT(SNS_FORM_UGN_2D, false, false, false, false)
+SNS_INST_LIFT(SNS_FORM_NS, false, true, false, false)
+SNS_INST_LIFT(SNS_FORM_NS, true, true, false, false)
+SNS_INST_LIFT(SNS_FORM_NS, false, false, true, false)
+SNS_INST_LIFT(SNS_FORM_NS, true, false, true, false)
+SNS_INST_LIFT(SNS_FORM_NS, false, true, false, true)
+SNS_INST_LIFT(SNS_FORM_NS, true, true, false, true)
 
 // dl = g - w on Dirichlet dofs, 0 elsewhere
 __global__ __launch_bounds__(256) void k_bc_defect(int64_t ndof, const uint8_t* __restrict__ bc_mask,
@@ -1219,22 +1274,24 @@ __global__ __launch_bounds__(256) void k_bc_defect(int64_t ndof, const uint8_t* 
         dl[i] = bc_mask[i] ? (bc_val[i] - w[i]) : 0.0;
 }
 
-#define SNS_INST_FUSED(FM, C, T, V)                                                                                \
-    template __global__ void k_fused_offdiag<FM, C, T, V>(int64_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
+#define SNS_INST_FUSED(FM, C, T, V, E)                                                                              \
+    template __global__ void k_fused_offdiag<FM, C, T, V, E>(int64_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
                                                 const int32_t*, const int32_t*, const double*, const double*,       \
                                                 const uint8_t*, double, double, double*, TimeTerm, ViscosityLaw);   \
-    template __global__ void k_fused_diag<FM, C, T, V>(int32_t, const int32_t*, const int64_t*, const int32_t*,         \
+    template __global__ void k_fused_diag<FM, C, T, V, E>(int32_t, const int32_t*, const int64_t*, const int32_t*,         \
                                              const int32_t*, const double*, const double*, const uint8_t*,          \
                                              const double*, double, double, double*, double*, TimeTerm, ViscosityLaw);
-SNS_INST_FUSED(SNS_FORM_NS, false, false, false)
-SNS_INST_FUSED(SNS_FORM_NS, true, false, false)
-SNS_INST_FUSED(SNS_FORM_STOKES, false, false, false)
-SNS_INST_FUSED(SNS_FORM_STOKES_2D, false, false, false)
-SNS_INST_FUSED(SNS_FORM_UGN_2D, false, false, false)
-SNS_INST_FUSED(SNS_FORM_NS, false, true, false)
-SNS_INST_FUSED(SNS_FORM_NS, true, true, false)
-SNS_INST_FUSED(SNS_FORM_NS, false, false, true)
-SNS_INST_FUSED(SNS_FORM_NS, true, false, true)
+SNS_INST_FUSED(SNS_FORM_NS, false, false, false, false)
+SNS_INST_FUSED(SNS_FORM_NS, true, false, false, false)
+SNS_INST_FUSED(SNS_FORM_STOKES, false, false, false, false)
+SNS_INST_FUSED(SNS_FORM_STOKES_2D, false, false, false, false)
+SNS_INST_FUSED(SNS_FORM_UGN_2D, false, false, false, false)
+SNS_INST_FUSED(SNS_FORM_NS, false, true, false, false)
+SNS_INST_FUSED(SNS_FORM_NS, true, true, false, false)
+SNS_INST_FUSED(SNS_FORM_NS, false, false, true, false)
+SNS_INST_FUSED(SNS_FORM_NS, true, false, true, false)
+SNS_INST_FUSED(SNS_FORM_NS, false, true, false, true)
+SNS_INST_FUSED(SNS_FORM_NS, true, true, false, true)
 
 // residual-only pass of the 2-D UGN form: one lane per triangle, Fe[16 t + 4 a + c] (same layout as the tet kernel,
 // so k_gather_residual serves both)
@@ -1308,12 +1365,13 @@ __global__ __launch_bounds__(256) void k_bc_residual(int64_t ndof, const uint8_t
 // Residual-only element pass for states that already satisfy the Dirichlet data (no lifting term):
 // ONE LANE PER TET, every lane busy (the fused kernel keeps 12 of 16 lanes idle in its per-point
 // phase).  Used by the line search (F(x - lambda y), :51-67 without the Jacobian).
-template <bool corrected, bool TT, bool VL>
+template <bool corrected, bool TT, bool VL, bool EV>
 __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int32_t* __restrict__ tets,
                                                       const double* __restrict__ pts,
                                                       const double* __restrict__ w, double nu,
                                                       double* __restrict__ Fe, TimeTerm tt, ViscosityLaw vl) {
     static_assert(!(VL && TT), "the viscosity law exists in the steady 3-D NS form only");
+    static_assert(!EV || (TT && !VL), "the viscosity field is a variant of the 3-D NS form with the time term");
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tets) return;
     const int4 tv = *reinterpret_cast<const int4*>(tets + 4 * t);
@@ -1376,6 +1434,7 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
         double dnu;
         carreau(vl, nu, shear_rate2(gu), nu_t, dnu);
     }
+    if constexpr (EV) nu_t = tt.nu_t[t];                   // viscosity field: by the cell of this pass
     double UT[TT ? 4 : 1][3];                              // nodal u_t = sigma u + d
     if constexpr (TT) {
 #pragma unroll
@@ -1430,7 +1489,7 @@ __global__ __launch_bounds__(256) void k_residual_tet(int64_t n_tets, const int3
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 double visc = gu[i][0] * g[a][0] + gu[i][1] * g[a][1] + gu[i][2] * g[a][2];
-                if constexpr (VL) visc += gu[0][i] * g[a][0] + gu[1][i] * g[a][1] + gu[2][i] * g[a][2];      // 2 (eps g_a)_i
+                if constexpr (VL || EV) visc += gu[0][i] * g[a][0] + gu[1][i] * g[a][1] + gu[2][i] * g[a][2];      // 2 (eps g_a)_i
                 const double supg = corrected ? tau * uga * r[i] : tau * u[i] * sa;
                 R[a][i] += conv[i] * pa + nu_t * visc - p * g[a][i] + supg + nuL * divu * g[a][i];
                 if constexpr (TT) R[a][i] += pa * ut[i];
@@ -1451,6 +1510,8 @@ template __global__ void k_residual_tet<false, true>(int64_t, const int32_t*, co
 template __global__ void k_residual_tet<true, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
 template __global__ void k_residual_tet<false, false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
 template __global__ void k_residual_tet<true, false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
+template __global__ void k_residual_tet<false, true, false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
+template __global__ void k_residual_tet<true, true, false, true>(int64_t, const int32_t*, const double*, const double*, double, double*, TimeTerm, ViscosityLaw);
 
 // Per-tet viscosity of a state (sns_element_viscosity): one lane per tet, nu_e of the law (nu0 without one) and
 // gamma_dot = sqrt(2 eps:eps).

@@ -325,13 +325,16 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
         print("Interpolating Coarse NS Flow", flush=True)
     w0 = interpolate_initial_guess(msh, w_coarse_host, msh_f, device=interp_device)
     w, u, p = _solve_ns(Pf, _from_global_host(Pf, w0), rank)
+    coupled = _coupled_flow(Pf, w, msh_f)                          # opt-in: the two-way coupling replaces the one-way transport
+    if coupled is not None:
+        w = coupled[0]
     wg = _to_global_host(Pf, w)
     out = dict(msh=msh_f, w=wg, u=wg.reshape(-1, 4)[:, :3].copy(), p=wg.reshape(-1, 4)[:, 3].copy(), Re=Re, img_fname=img_fname,
                channel_mesh_size=channel_mesh_size, flowrate_ratio=flowrate_ratio, newton=Pf.last_newton)
     derived = _derived_fields(Pf, w)
     if derived is not None:
         out["derived"] = derived
-    conc = _scalar_transport(Pf, w, msh_f)
+    conc = coupled[1] if coupled is not None else _scalar_transport(Pf, w, msh_f)
     if conc is not None:
         out["concentration"] = conc
     Pf.close()
@@ -386,6 +389,9 @@ def duct_stokes_main(argv=None):
     U, res = P.stokes_solve()
     if _viscosity_law() is not None:                              # opt-in: a Navier-Stokes leg with the law, from the Stokes start
         U = _solve_ns(P, U.clone(), _rank())[0]
+    coupled = _coupled_flow(P, U, msh)                             # opt-in: a coupled Navier-Stokes leg from the state so far
+    if coupled is not None:
+        U = coupled[0]
     W = _to_global_host(P, U).reshape(-1, 4)
     u, p = W[:, :3], W[:, 3]
     if _rank() == 0:
@@ -396,7 +402,7 @@ def duct_stokes_main(argv=None):
         write_xdmf("StokesDuctPressure", msh, "f", p)
         write_xdmf("StokesDuctVelcoity", msh, "f", u)             # (sic) file name of the reference :255
     _write_derived_fields(_derived_fields(P, U), msh, lambda label: f"StokesDuct{label}")
-    conc = _scalar_transport(P, U, msh)
+    conc = coupled[1] if coupled is not None else _scalar_transport(P, U, msh)
     if conc is not None and _rank() == 0:
         write_xdmf("StokesDuctConcentration", msh, "Concentration", conc)
     P.close()
@@ -590,6 +596,38 @@ def _scalar_transport(P, w, msh):
     print(f"Scalar transport Pe {pe:g}: {res.its} iterations, reason {res.reason}; concentration at the outlet "
           f"min {out.min()} max {out.max()}", flush=True)
     return c
+
+
+def _coupled_flow(P, w, msh):
+    """SNS_VISCOSITY_RATIO=<r> and / or SNS_BUOYANCY=<gx>,<gy>,<gz>, together with SNS_SCALAR_PECLET=<Pe> (opt-in; single-GPU
+    runs): the inlet-stream indicator carried by the flow acts back on it -- the inner stream is r times as viscous (log-mixing
+    rule) and feels the Boussinesq force c * (gx, gy, gz) -- and ``solver.solve_coupled_flow`` from the state ``w`` takes the
+    place of the one-way transport.  Returns (state, concentration (n,) host array) after one printed line with the outer
+    iteration count and the line of ``_scalar_transport``; None without the switches: output and stdout stay as they are."""
+    ratio, buoy, pe = (os.environ.get(k, "") for k in ("SNS_VISCOSITY_RATIO", "SNS_BUOYANCY", "SNS_SCALAR_PECLET"))
+    if not ratio and not buoy:
+        return None
+    if not pe:
+        raise ValueError("SNS_VISCOSITY_RATIO / SNS_BUOYANCY need SNS_SCALAR_PECLET=<Pe>: the coupling acts through the transported scalar")
+    if getattr(P, "part", None) is not None:
+        if _rank() == 0:
+            print("SNS_VISCOSITY_RATIO / SNS_BUOYANCY: the coupled solve runs on single-GPU problems only; skipped", flush=True)
+        return None
+    from .solver import solve_coupled_flow
+    pe, r = float(pe), float(ratio) if ratio else 1.0
+    b = tuple(float(x) for x in buoy.split(",")) if buoy else (0.0, 0.0, 0.0)
+    if not pe > 0.0 or not r > 0.0 or len(b) != 3:
+        raise ValueError("SNS_SCALAR_PECLET and SNS_VISCOSITY_RATIO must be positive, SNS_BUOYANCY three numbers gx,gy,gz")
+    w, c, recs = solve_coupled_flow(P, w, (1.0 / pe,), inner_stream_inlet_data(msh), log_viscosity_ratio=float(np.log(r)), buoyancy=b)
+    last = recs[-1]
+    c = c[:, 0].cpu().numpy()
+    out = c[msh.facet_nodes(msh.meta["tags"]["outlet"])]
+    print(f"Coupled flow (viscosity ratio {r:g}, buoyancy {b[0]:g},{b[1]:g},{b[2]:g}): {len(recs)} outer iterations, "
+          f"{'converged' if last['converged'] else 'NOT converged'}, last change of c {last['change']}; Newton reason "
+          f"{last['newton_reason']}, scalar reason {last['scalar_reason']}", flush=True)
+    print(f"Scalar transport Pe {pe:g}: {last['scalar_its']} iterations, reason {last['scalar_reason']}; concentration at the outlet "
+          f"min {out.min()} max {out.max()}", flush=True)
+    return w, c
 
 
 def dfg_2d_main(argv=None):

@@ -434,13 +434,52 @@ class FlowProblem:
 
     def element_viscosity(self, w):
         """(nu_e, gamma_dot) of the state ``w``: one value per tet, device tensors (sns_element_viscosity); nu_e = 1/Re
-        everywhere without a law."""
+        everywhere without a law, the viscosity field where one is set."""
         w = self._vec(w)
         nt = self.sizes()["n_tets"]
         nu = torch.empty(nt, dtype=torch.float64, device=self.device)
         gd = torch.empty(nt, dtype=torch.float64, device=self.device)
         check(self.lib.sns_element_viscosity(self.h, _ptr(w), _ptr(nu), _ptr(gd)))
         return nu, gd
+
+    # -- external fields of the 3-D NS form (no counterpart in the reference: no right-hand side, nu = 1/Re everywhere) ----
+    def set_body_force(self, f):
+        """Every NS assembly of this problem from now on has the nodal P1 force density ``f`` on the right-hand side of the
+        momentum equation (sns_set_body_force): with a = u_t - f, (a, v) in the Galerkin part and res_M + a in the SUPG / PSPG
+        term.  ``f``: a dof vector (numpy or device; pressure slots ignored, copied by the handle).  The viscous form is not
+        changed.  Single-GPU 3-D problems; not together with a viscosity law."""
+        check(self.lib.sns_set_body_force(self.h, _ptr(self._vec(f))))
+
+    def clear_body_force(self):
+        check(self.lib.sns_set_body_force(self.h, None))
+
+    def set_element_viscosity(self, nu):
+        """Every NS assembly of this problem from now on takes the per-tet viscosity ``nu`` (n_tets values, each finite and
+        > 0; sns_set_element_viscosity): the viscous term becomes (2 nu_t eps(u), grad v), nu_t enters tau, the Jacobian is the
+        exact derivative with nu_t held fixed.  Single-GPU 3-D problems; not together with a viscosity law."""
+        if not isinstance(nu, torch.Tensor):
+            nu = torch.from_numpy(np.ascontiguousarray(nu, dtype=np.float64))
+        nu = nu.to(self.device, torch.float64).contiguous().reshape(-1)
+        if nu.numel() != self.sizes()["n_tets"]:
+            raise ValueError("set_element_viscosity: one value per tet")
+        check(self.lib.sns_set_element_viscosity(self.h, _ptr(nu)))
+
+    def clear_element_viscosity(self):
+        check(self.lib.sns_set_element_viscosity(self.h, None))
+
+    def set_mixture(self, m, log_viscosity_ratio: float = 0.0, buoyancy=(0.0, 0.0, 0.0)):
+        """Both fields from a nodal P1 mixture fraction ``m`` (n values; sns_set_mixture): nu_t = (1/Re) exp(
+        ``log_viscosity_ratio`` * mean of m over the tet's vertices) with the Reynolds number the problem has NOW, and f =
+        m * ``buoyancy`` (Boussinesq, buoyancy = Ri * g_hat).  A zero log ratio clears the viscosity field, a zero buoyancy
+        the body force, ``m`` = None both."""
+        if m is not None:
+            if not isinstance(m, torch.Tensor):
+                m = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float64))
+            m = m.to(self.device, torch.float64).contiguous().reshape(-1)
+            if m.numel() != self.n_local:
+                raise ValueError("set_mixture: one value per node")
+        b = (C.c_double * 3)(*[float(x) for x in buoyancy])
+        check(self.lib.sns_set_mixture(self.h, _ptr(m), float(log_viscosity_ratio), b))
 
     # -- scalar transport on the flow mesh (no counterpart in the reference, which traces streamlines instead) --------
     def _scalar_inputs(self, w, kappa, bcs, source):
@@ -823,6 +862,45 @@ def solve_scalar_transport(problem: FlowProblem, w, kappa, bcs, source=None):
     sigma = theta = 0).  The age of fluid is source = 1 with c = 0 at the inlet.  Returns (c (n, k), KrylovResult).  NOT in the
     reference."""
     return problem.scalar_solve(w, kappa, bcs, source=source)
+
+
+def solve_coupled_flow(problem: FlowProblem, w0, kappa, scalar_bcs, *, log_viscosity_ratio=0.0, buoyancy=(0.0, 0.0, 0.0), species=0,
+                       source=None, c0=None, max_outer=30, rtol=1e-8, relax=1.0):
+    """Steady two-way coupling of the flow with the scalars it carries, by fixed-point iteration: per outer step
+    ``problem.set_mixture`` from species ``species`` of c (viscosity nu0 exp(log_viscosity_ratio m), force m * buoyancy),
+    ``newton_solve`` from the last state, ``scalar_solve`` carried by the new state (``kappa``, ``scalar_bcs``, ``source`` as
+    there), c <- c + relax (c_new - c).  Starts from the state ``w0`` (not modified) and ``c0`` (n, k; default 0) and stops when
+    ||c_new - c|| <= rtol ||c_new|| with a converged Newton solve, at the first solve that fails, or after ``max_outer`` steps.
+    Returns (w, c, records): one dict per outer step with ``newton_its``, ``ksp_its``, ``newton_reason``, ``scalar_its``,
+    ``scalar_reason`` (None where the flow solve failed) and ``change`` = ||c_new - c|| / ||c_new||; the loop converged iff the
+    last record has ``converged``.  The fields stay set: the converged ones on success, the last step's on a failure
+    (``problem.set_mixture(None)`` clears them).  NOT in the reference."""
+    k = len(np.atleast_1d(np.asarray(kappa, dtype=np.float64)).ravel())
+    if not 0 <= int(species) < k:
+        raise ValueError("species: an index into kappa")
+    w = problem._vec(w0).clone()
+    c = torch.zeros(problem.n_local, k, dtype=torch.float64, device=problem.device) if c0 is None else problem._columns(c0, k).clone()
+    records = []
+    for _ in range(int(max_outer)):
+        problem.set_mixture(c[:, species], log_viscosity_ratio, buoyancy)
+        w, nres = problem.newton_solve(w)
+        rec = dict(newton_its=nres.its, ksp_its=nres.ksp_its, newton_reason=nres.reason, scalar_its=None, scalar_reason=None,
+                   change=None, converged=False)
+        records.append(rec)
+        if nres.reason <= 0:
+            break
+        cn, sres = problem.scalar_solve(w, kappa, scalar_bcs, source=source, c0=c)
+        rec.update(scalar_its=sres.its, scalar_reason=sres.reason)
+        if sres.reason <= 0:
+            break
+        change = float(torch.linalg.norm(cn - c)) / max(float(torch.linalg.norm(cn)), 1e-300)
+        rec["change"] = change
+        c = c + relax * (cn - c)
+        if change <= rtol:
+            rec["converged"] = True
+            problem.set_mixture(c[:, species], log_viscosity_ratio, buoyancy)
+            break
+    return w, c, records
 
 
 def advance_scalars(problem: FlowProblem, w, c0, dt: float, n_steps: int, order: int = 2, callback=None, *, kappa, bcs,

@@ -1,0 +1,549 @@
+"""Body force and per-cell viscosity field of the 3-D NS form on the GPU (sns_set_body_force, sns_set_element_viscosity,
+sns_set_mixture; solver.solve_coupled_flow), everything through the C-ABI.
+
+The reference has no right-hand side and a constant viscosity; the yardstick is the test-side oracle tests/fields_oracle.py
+(literal restatement, autograd Jacobian, LU-Newton, the same fixed-point loop) whose own checks are tests/test_host_fields.py,
+and its fields in tests/golden/fields_cases.npz.  Tolerances as in tests/test_gpu_viscosity.py and tests/test_gpu_transient.py:
+operators and residuals 1e-12 relative, the two assembly paths against each other 1e-13, Krylov-converged fields 1e-6, J dw
+against central differences of the residual 1e-6."""
+import numpy as np
+import pytest
+import torch
+
+import fields_oracle as FO
+from conftest import rel
+from oracle import forms_literal as FL
+from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B
+from stabilized_navier_stokes_flow_fenicsx_amd import mesh as M
+from stabilized_navier_stokes_flow_fenicsx_amd import mesh2d as M2
+from stabilized_navier_stokes_flow_fenicsx_amd import solver as S
+from stabilized_navier_stokes_flow_fenicsx_amd.solver import FlowProblem, SnsError
+from test_gpu_adjoint import _adjoint_identity
+from test_host_fields import FIXTURE, golden_script, patch_problem
+
+pytestmark = pytest.mark.gpu
+TIGHT = dict(ksp_rtol=1e-11, snes_rtol=1e-10, snes_atol=1e-14, snes_stol=1e-14)
+G = golden_script()
+C = G.COUPLED
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()
+
+
+def _one_tet(X):
+    return M.TetMesh(np.ascontiguousarray(X), np.array([[0, 1, 2, 3]], np.int32), np.zeros((0, 3), np.int32), np.zeros(0, np.int32))
+
+
+def _fields_close(a, b, tol=1e-6):
+    a, b = np.asarray(a).reshape(-1, 4), np.asarray(b).reshape(-1, 4)
+    return rel(a[:, :3], b[:, :3]) < tol and rel(a[:, 3], b[:, 3]) < tol
+
+
+def _dofs(x3, rng):
+    """(n, 3) nodal vectors as a dof vector; the pressure slots hold noise (they are ignored)."""
+    return np.concatenate([x3, rng.normal(size=(len(x3), 1))], axis=1).ravel()
+
+
+def _system(P, wd):
+    F = P.zeros()
+    P.jacobian(wd, "ns", residual_out=F)
+    return P.bsr()[2].clone(), F.clone(), P.residual(wd, "ns")
+
+
+# ---- 1. element level ------------------------------------------------------------------------------------------------
+# (body force, viscosity field, time term)
+COMBOS = [(1, 0, 0), (0, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1)]
+
+
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_element_matrices_against_the_oracle(corrected):
+    rng = np.random.default_rng(81)
+    fx = np.load(FIXTURE)
+    X, Ws = fx["el_X"], fx["el_W"]
+    none = (np.zeros(16, np.uint8), np.zeros(16))
+    for i in range(len(X)):
+        W, Re = Ws[i], float(fx["el_Re"][i])
+        D, Fn, nu = fx["el_D"][i], fx["el_F"][i], fx["el_nu"][i:i + 1]
+        sigma, theta = float(fx["el_sigma"][i]), float(fx["el_theta"][i])
+        oracle = {}
+        for bf, ev, tt in COMBOS:
+            oracle[(bf, ev, tt)] = FO.element(X[i][None], W[None], D[None] if tt else None, Fn[None] if bf else None, nu if ev else None, Re,
+                                              sigma if tt else 0.0, theta if tt else 0.0, bool(ev), corrected_convection=bool(corrected))
+        assert rel(oracle[(1, 1, 1)][0][0], fx["el_R"][corrected][i]) < 1e-12      # (the fixture's record)
+        for fused in (0, 1):
+            P = FlowProblem(_one_tet(X[i]), none, reynolds=Re, corrected_convection=corrected, pc_type="bjacobi", assembly_fused=fused)
+            for combo in COMBOS:
+                bf, ev, tt = combo
+                Fo, Jo = oracle[combo]
+                if tt:
+                    P.set_time_term(sigma, theta, _dev(_dofs(D, rng)))
+                else:
+                    P.clear_time_term()
+                P.set_body_force(_dev(_dofs(Fn, rng))) if bf else P.clear_body_force()
+                P.set_element_viscosity(nu) if ev else P.clear_element_viscosity()
+                F = P.zeros()
+                P.jacobian(_dev(W), "ns", residual_out=F)
+                tag = (i, fused, combo)
+                if not fused:                                        # the staged kernel's own output
+                    Ke = P.element_matrices().cpu().numpy()[0]
+                    assert rel(Ke.transpose(0, 2, 1, 3).reshape(16, 16), Jo[0]) < 1e-12, tag
+                assert rel(P.to_scipy().toarray(), Jo[0]) < 1e-12, tag
+                assert rel(F.cpu().numpy(), Fo[0]) < 1e-12, tag
+                assert rel(P.residual(_dev(W), "ns").cpu().numpy(), Fo[0]) < 1e-12, tag      # one lane per tet
+            P.close()
+
+
+# ---- 2. global level -------------------------------------------------------------------------------------------------
+def _channel():
+    m = M.channel_mesh((9, 5, 4), jitter=0.2)
+    mask, g = B.channel_bcs(m, *B.two_stream_profiles(0.4)).flatten()
+    return m, mask, g
+
+
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_fused_staged_and_oracle_agree_globally(corrected):
+    rng = np.random.default_rng(82)
+    m, mask, g = _channel()
+    m.tets = np.ascontiguousarray(np.take_along_axis(m.tets, np.argsort(rng.random(m.tets.shape), axis=1), axis=1))
+    Bm = mask.astype(bool)
+    w = rng.normal(size=m.num_dofs) * 0.5
+    w[Bm] = g[Bm]
+    w2 = w.copy()
+    w2[np.nonzero(Bm)[0][::3]] += 0.3                              # violates the Dirichlet data: lifting (k_fused_lift)
+    Re = 17.0
+    f, d = rng.normal(size=m.num_dofs), rng.normal(size=m.num_dofs)
+    nu = 10.0 ** rng.uniform(-2.0, 0.0, size=m.num_tets)
+    P = FlowProblem(m, (mask, g), reynolds=Re, corrected_convection=corrected)
+    # a body force alone (the TT instantiations on -f), then both fields under a time term (the EV instantiations)
+    for kw in (dict(f=f), dict(f=f, nu_t=nu, d=d, sigma=6.0, theta=900.0)):
+        P.set_body_force(_dev(f))
+        if "nu_t" in kw:
+            P.set_element_viscosity(nu)
+            P.set_time_term(kw["sigma"], kw["theta"], _dev(d))
+        for state in (w, w2):
+            Jo, Fo = FO.assemble(m.points, m.tets, state, Re, mask, g, corrected_convection=bool(corrected), **kw)
+            got = []
+            for fused in (1, 0):
+                P.set_options(assembly_fused=fused)
+                F = P.zeros()
+                P.jacobian(_dev(state), "ns", residual_out=F)
+                got.append((P.to_scipy(), F.cpu().numpy()))
+                assert abs(got[-1][0] - Jo).max() < 1e-12 * abs(Jo).max(), (fused, sorted(kw))
+                assert rel(got[-1][1], Fo) < 1e-12, (fused, sorted(kw))
+                assert rel(P.residual(_dev(state), "ns").cpu().numpy(), Fo) < 1e-12, (fused, sorted(kw))
+            assert abs(got[0][0] - got[1][0]).max() < 1e-13 * abs(got[1][0]).max()
+            assert rel(got[0][1], got[1][1]) < 1e-13
+    P.close()
+
+
+# ---- 3. perturbed form variant ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_perturbed_form_variant_with_both_fields(corrected):
+    rng = np.random.default_rng(83)
+    X = G.random_tets(rng, 2)
+    none = (np.zeros(16, np.uint8), np.zeros(16))
+    base = dict(FL.VARIANT)
+    try:
+        FL.VARIANT.update(ci=144.0, lsic=4.0, pspg=-1.0, one_point=True)
+        for i in range(2):
+            W, Fn, nu = rng.normal(size=16), rng.normal(size=(4, 3)), np.array([0.07 * (i + 1)])
+            Fo, Jo = FO.element(X[i][None], W[None], None, Fn[None], nu, 40.0, 0.0, 0.0, True, corrected_convection=bool(corrected))
+            P = FlowProblem(_one_tet(X[i]), none, reynolds=40.0, corrected_convection=corrected, pc_type="bjacobi")
+            P.set_form_variant(c_inverse=144.0, lsic_scale=4.0, pspg_sign=-1.0, one_point_quadrature=True)
+            P.set_body_force(_dev(_dofs(Fn, rng)))
+            P.set_element_viscosity(nu)
+            F = P.zeros()
+            P.jacobian(_dev(W), "ns", residual_out=F)
+            assert rel(P.to_scipy().toarray(), Jo[0]) < 1e-12 and rel(F.cpu().numpy(), Fo[0]) < 1e-12
+            assert rel(P.residual(_dev(W), "ns").cpu().numpy(), Fo[0]) < 1e-12
+            P.close()
+    finally:
+        FL.VARIANT.update(base)
+
+
+# ---- 4. patch test with a body force ---------------------------------------------------------------------------------
+def test_patch_test_with_a_body_force():
+    m, mask, g, w, f, Re = patch_problem()
+    free = torch.from_numpy(mask == 0).cuda()
+    P = FlowProblem(m, (mask, g), reynolds=Re, corrected_convection=1, **TIGHT)
+    U, sres = P.stokes_solve()
+    assert sres.reason > 0
+    wd = _dev(w)
+    for nu in (None, np.full(m.num_tets, 0.37)):                   # the reference's viscous form; the stress-divergence form
+        P.set_element_viscosity(nu) if nu is not None else P.clear_element_viscosity()
+        P.clear_body_force()
+        off = float(P.residual(wd, "ns")[free].abs().max())
+        P.set_body_force(_dev(f))
+        for fused in (1, 0):
+            P.set_options(assembly_fused=fused)
+            F = P.zeros()
+            P.jacobian(wd, "ns", residual_out=F)
+            on = max(float(F[free].abs().max()), float(P.residual(wd, "ns")[free].abs().max()))
+            print(f"patch test, viscosity field {nu is not None}, fused {fused}: max |F_free| {on:.2e}, with the force cleared {off:.2e}")
+            assert on <= 1e-12 * off
+    P.clear_element_viscosity()
+    x, res = P.newton_solve(U.clone())
+    e = rel(x.cpu().numpy(), w)
+    print(f"patch Newton: {res.its} its, reason {res.reason}, rel err {e:.2e}")
+    assert res.reason > 0 and _fields_close(x.cpu().numpy(), w)
+    P.close()
+
+
+# ---- 5. no-op and refusals -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [1, 0])
+def test_cleared_fields_are_bitwise_the_handle_as_it_was(fused):
+    rng = np.random.default_rng(85)
+    m, mask, g = _channel()
+    w = rng.normal(size=m.num_dofs) * 0.5
+    w[mask.astype(bool)] = g[mask.astype(bool)]
+    wd = _dev(w)
+    f, nu, d = _dev(rng.normal(size=m.num_dofs)), 10.0 ** rng.uniform(-2.0, 0.0, size=m.num_tets), _dev(rng.normal(size=m.num_dofs))
+    P0 = FlowProblem(m, (mask, g), reynolds=30.0, assembly_fused=fused)
+    s0 = _system(P0, wd)
+    P0.set_time_term(5.0, 100.0, d)
+    t0 = _system(P0, wd)
+    P0.close()
+    P = FlowProblem(m, (mask, g), reynolds=30.0, assembly_fused=fused)
+    P.clear_body_force()                                           # clearing what is not set, on a fresh handle
+    P.clear_element_viscosity()
+    P.set_mixture(None)
+    assert all(torch.equal(a, b) for a, b in zip(s0, _system(P, wd)))
+    P.set_body_force(f)
+    s1 = _system(P, wd)
+    assert not torch.equal(s0[1], s1[1]) and not torch.equal(s0[0], s1[0])       # (f is in F, and in J through d tau . res_M)
+    P.set_element_viscosity(nu)
+    s2 = _system(P, wd)
+    assert not torch.equal(s1[0], s2[0]) and not torch.equal(s1[1], s2[1])
+    assert torch.equal(P.element_viscosity(wd)[0], _dev(nu))
+    P.set_time_term(5.0, 100.0, d)                                 # both fields under a time term ...
+    assert not torch.equal(s2[0], _system(P, wd)[0])
+    P.clear_body_force()
+    P.clear_element_viscosity()                                    # ... and the term alone: variant 1 with the caller's own d
+    assert all(torch.equal(a, b) for a, b in zip(t0, _system(P, wd)))
+    P.set_body_force(f)
+    P.clear_time_term()                                            # the force stays when the term goes
+    assert torch.equal(s1[1], _system(P, wd)[1])
+    P.clear_body_force()
+    assert all(torch.equal(a, b) for a, b in zip(s0, _system(P, wd)))            # variant 0
+    assert torch.all(P.element_viscosity(wd)[0] == 1.0 / 30.0)
+    P.close()
+
+
+def test_refusals_leave_the_handle_untouched():
+    rng = np.random.default_rng(86)
+    fx = np.load(FIXTURE)
+    m, mask, g, _, _ = G.duct_problem()
+    wd = _dev(fx["unc_w"])
+    f, nu = _dev(rng.normal(size=m.num_dofs)), 10.0 ** rng.uniform(-2.0, 0.0, size=m.num_tets)
+    P = FlowProblem(m, (mask, g), reynolds=C["Re"])
+    s0 = _system(P, wd)
+
+    def same_bits(ref=s0):
+        return all(torch.equal(a, b) for a, b in zip(ref, _system(P, wd)))
+
+    for bad in (0.0, -1.0, float("nan"), float("inf")):            # one bad entry among good ones
+        x = nu.copy()
+        x[len(x) // 3] = bad
+        with pytest.raises(SnsError) as e:
+            P.set_element_viscosity(x)
+        assert e.value.code == -1 and "sns_set_element_viscosity" in str(e.value), bad
+        assert same_bits(), bad
+    for lr, bu in ((float("nan"), (0.0, 0.0, 0.0)), (1.0, (0.0, float("inf"), 0.0))):
+        with pytest.raises(SnsError) as e:
+            P.set_mixture(np.ones(m.num_nodes), lr, bu)
+        assert e.value.code == -1 and same_bits()
+    with pytest.raises(SnsError) as e:                             # a mixture fraction whose viscosity overflows
+        P.set_mixture(np.full(m.num_nodes, 1e6), 1.0, (0.0, -1.0, 0.0))
+    assert e.value.code == -1 and same_bits()
+    # the fields and the Carreau law exclude each other, in either order
+    P.set_viscosity_law(3.0, 0.5, 0.01)
+    s_law = _system(P, wd)
+    for call in (lambda: P.set_body_force(f), lambda: P.set_element_viscosity(nu), lambda: P.set_mixture(np.ones(m.num_nodes), 1.0, (0, 1, 0))):
+        with pytest.raises(SnsError) as e:
+            call()
+        assert e.value.code == -3 and same_bits(s_law)
+    P.clear_viscosity_law()
+    for setter, clear in ((lambda: P.set_body_force(f), P.clear_body_force), (lambda: P.set_element_viscosity(nu), P.clear_element_viscosity)):
+        setter()
+        s_on = _system(P, wd)
+        with pytest.raises(SnsError) as e:
+            P.set_viscosity_law(3.0, 0.5, 0.01)
+        assert e.value.code == -3 and same_bits(s_on)
+        with pytest.raises(SnsError) as e:
+            P.residual_shape_gradient(wd, wd)
+        assert e.value.code == -3 and same_bits(s_on)
+        P.clear_viscosity_law()                                    # (clearing a law that is not set stays allowed)
+        clear()
+        assert same_bits()
+    P.close()
+    # 2-D handles
+    m2 = M2.dfg_2d_mesh(0.5)
+    P2 = FlowProblem(m2, M2.dfg2d_bcs(m2).flatten(), reynolds=100.0)
+    with pytest.raises(SnsError) as e:
+        P2.set_body_force(P2.zeros())
+    assert e.value.code == -1 and "3-D handles only" in str(e.value)
+    assert P2.lib.sns_set_element_viscosity(P2.h, None) == -1 and P2.lib.sns_set_mixture(P2.h, None, 0.0, None) == -1
+    P2.close()
+    # a handle with an owned / ghost split attached (no transport needed): SNS_E_STATE, as for the time term
+    from stabilized_navier_stokes_flow_fenicsx_amd import partition as PT
+    part = PT.build_local_part(m, mask, g, PT.rcb_partition(m.points, 2), 0, 2)
+    R = FlowProblem(part.mesh, (part.bc_mask, part.bc_val), part=part, group="local-only", reynolds=C["Re"])
+    assert R.lib.sns_set_body_force(R.h, None) == -3 and R.lib.sns_set_element_viscosity(R.h, None) == -3
+    assert R.lib.sns_set_mixture(R.h, None, 0.0, None) == -3
+    R.close()
+
+
+def test_the_fields_buffers_go_with_the_handle():
+    """sns_live_device_bytes is back where it was after sns_destroy: the copies of f and nu_t, the effective history and the
+    moments' compacted field are DevBuf members of the handle."""
+    from stabilized_navier_stokes_flow_fenicsx_amd import _lib
+    rng = np.random.default_rng(93)
+    m, mask, g = _channel()
+    base = int(_lib.load().sns_live_device_bytes())
+    P = FlowProblem(m, (mask, g), reynolds=30.0)
+    before = int(_lib.load().sns_live_device_bytes())
+    P.set_mixture(rng.uniform(size=m.num_nodes), 1.0, (0.0, -1.0, 0.0))
+    P.set_time_term(2.0, 0.0, P.zeros())
+    wd = _dev(rng.normal(size=m.num_dofs))
+    P.residual_moments(wd, (m.points[:, 0] < 0.5).astype(np.float64))
+    assert int(_lib.load().sns_live_device_bytes()) >= before + 8 * (2 * m.num_dofs + m.num_tets)      # f, d - f, nu_t
+    P.close()
+    assert int(_lib.load().sns_live_device_bytes()) == base
+
+
+def test_stokes_form_ignores_the_fields():
+    rng = np.random.default_rng(87)
+    m, mask, g, _, _ = G.duct_problem()
+    f, nu = _dev(rng.normal(size=m.num_dofs)), 10.0 ** rng.uniform(-2.0, 0.0, size=m.num_tets)
+    P = FlowProblem(m, (mask, g), reynolds=C["Re"])
+    F0 = P.zeros()
+    P.jacobian(None, "stokes", residual_out=F0)
+    v0 = P.bsr()[2].clone()
+    P.set_body_force(f)
+    P.set_element_viscosity(nu)
+    F1 = P.zeros()
+    P.jacobian(None, "stokes", residual_out=F1)
+    assert torch.equal(v0, P.bsr()[2]) and torch.equal(F0, F1)
+    for fused in (1, 0):                                            # ... also its residual at a state, on both paths
+        P.set_options(assembly_fused=fused)
+        R1 = P.residual(F0, "stokes")
+        P.set_mixture(None)
+        assert torch.equal(R1, P.residual(F0, "stokes"))
+        P.set_body_force(f)
+        P.set_element_viscosity(nu)
+    P.close()
+
+
+# ---- 6. Jacobian against central differences ------------------------------------------------------------------------
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_jacobian_against_central_differences_of_the_residual(corrected):
+    m = M.duct_mesh((30, 24, 24), 4.0)                             # 103 680 tets
+    mask, g = B.duct_bcs(m).flatten()
+    P = FlowProblem(m, (mask, g), reynolds=80.0, corrected_convection=corrected)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    gen = torch.Generator(device="cuda").manual_seed(88)
+    P.set_mixture(G.smooth_m(m.points), np.log(4.0), (0.5, -2.0, 0.3))
+    free = torch.from_numpy(1.0 - P.bc_mask.astype(np.float64)).cuda()
+    eps = 1e-4
+    for k in range(3):
+        dw = torch.randn(P.ndof, dtype=torch.float64, device="cuda", generator=gen) * free * 1e-2
+        fd = (P.residual(U + eps * dw, "ns") - P.residual(U - eps * dw, "ns")) / (2 * eps)
+        for fused in (1, 0):
+            P.set_options(assembly_fused=fused)
+            P.jacobian(U, "ns")
+            e = float((P.spmv(dw) - fd).norm() / fd.norm())
+            print(f"corrected {corrected} direction {k} fused {fused}: |J dw - fd| / |fd| = {e:.3e}")
+            assert e < 1e-6
+    P.close()
+
+
+# ---- 7. the mixture rule ---------------------------------------------------------------------------------------------
+def test_set_mixture_against_the_oracle():
+    rng = np.random.default_rng(89)
+    m, mask, g = _channel()
+    mm = rng.uniform(-0.2, 1.2, size=m.num_nodes)                  # over- and undershoots
+    Re, lr, bu = 30.0, float(np.log(20.0)), (0.3, -2.0, 0.7)
+    nu_o, f_o = FO.mixture_fields(m.points, m.tets, mm, Re, lr, bu)
+    w = rng.normal(size=m.num_dofs) * 0.5
+    w[mask.astype(bool)] = g[mask.astype(bool)]
+    wd = _dev(w)
+    P = FlowProblem(m, (mask, g), reynolds=Re)
+    P.set_mixture(mm, lr, bu)
+    nu = P.element_viscosity(wd)[0].cpu().numpy()
+    assert np.abs(nu / nu_o - 1.0).max() < 1e-13 and nu.min() > 0.0
+    # f to the last bit: the force set by hand from the oracle's f gives the same bits of F and J
+    s_mix = _system(P, wd)
+    P.set_body_force(_dev(f_o))
+    assert all(torch.equal(a, b) for a, b in zip(s_mix, _system(P, wd)))
+    # reynolds is read at the call: a later change of the option does not rescale the field
+    P.set_options(reynolds=60.0)
+    assert torch.equal(P.element_viscosity(wd)[0], _dev(nu))
+    P.set_options(reynolds=Re)
+    # the clears of the convenience
+    P.set_mixture(mm, 0.0, bu)                                     # a zero log ratio clears the viscosity field
+    assert torch.all(P.element_viscosity(wd)[0] == 1.0 / Re)
+    s_f = _system(P, wd)
+    P.clear_element_viscosity()
+    assert all(torch.equal(a, b) for a, b in zip(s_f, _system(P, wd)))
+    P.set_mixture(mm, lr, (0.0, 0.0, 0.0))                         # a zero buoyancy clears the force
+    s_nu = _system(P, wd)
+    P.clear_body_force()
+    P.set_element_viscosity(nu_o)
+    s_nu2 = _system(P, wd)
+    assert rel(s_nu[1].cpu().numpy(), s_nu2[1].cpu().numpy()) < 1e-12
+    P.set_mixture(None)
+    Q = FlowProblem(m, (mask, g), reynolds=Re)
+    assert all(torch.equal(a, b) for a, b in zip(_system(Q, wd), _system(P, wd)))
+    Q.close()
+    P.close()
+
+
+# ---- 8. one BDF2 step ------------------------------------------------------------------------------------------------
+def test_time_steps_with_both_fields_against_the_oracle():
+    fx = np.load(FIXTURE)
+    m, mask, g, w0, Re = G.step_problem()
+    st = G.STEP
+    P = FlowProblem(m, (mask, g), reynolds=Re, **TIGHT)
+    P.set_mixture(G.smooth_m(m.points), st["log_ratio"], st["buoyancy"])
+    w, wprev = _dev(w0), _dev(w0)
+    for n, want in ((1, fx["step_w1"]), (2, fx["step_w2"])):
+        _, res = P.time_step(w, wprev, st["dt"], order=n, theta_coeff=st["theta_coeff"])
+        e = (rel(w.cpu().numpy().reshape(-1, 4)[:, :3], want.reshape(-1, 4)[:, :3]), rel(w.cpu().numpy().reshape(-1, 4)[:, 3], want.reshape(-1, 4)[:, 3]))
+        print(f"BDF{n} with both fields: its {res.its} ksp {res.ksp_its}  rel err u {e[0]:.2e} p {e[1]:.2e}")
+        assert res.reason > 0 and _fields_close(w.cpu().numpy(), want), (n, e)
+    assert _fields_close(wprev.cpu().numpy(), fx["step_w1"])
+    assert not _fields_close(fx["step_w2"], w0, 1e-3)
+    P.close()
+    # a step that does not converge reports its reason and restores both states
+    Q = FlowProblem(m, (mask, g), reynolds=Re, snes_max_it=1, snes_rtol=1e-14, snes_atol=1e-30, snes_stol=0.0)
+    Q.set_mixture(G.smooth_m(m.points), st["log_ratio"], st["buoyancy"])
+    w, wprev = _dev(w0), _dev(0.5 * w0)
+    _, r = Q.time_step(w, wprev, 0.1, order=2)
+    assert r.reason < 0 and torch.equal(w, _dev(w0)) and torch.equal(wprev, _dev(0.5 * w0))
+    Q.close()
+
+
+# ---- 9, 10. the coupled fixed point ----------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def coupled_runs():
+    """name -> (w, c, records) of solver.solve_coupled_flow on the fixture's duct from the Stokes solution: the viscosity ratio alone,
+    the buoyancy alone, and ratio 1 without buoyancy."""
+    m, mask, g, cm, cv = G.duct_problem()
+    P = FlowProblem(m, (mask, g), reynolds=C["Re"], **TIGHT)
+    U, sres = P.stokes_solve()
+    assert sres.reason > 0
+    runs = {}
+    for name, kw in (("visc", C["visc"]), ("buoy", C["buoy"]), ("unc", dict(log_ratio=0.0, buoyancy=(0.0, 0.0, 0.0)))):
+        w, c, recs = S.solve_coupled_flow(P, U, (C["kappa"],), (cm[:, None], cv[:, None]), log_viscosity_ratio=kw["log_ratio"],
+                                          buoyancy=kw["buoyancy"], rtol=C["rtol"])
+        runs[name] = (w.cpu().numpy(), c[:, 0].cpu().numpy(), recs)
+    P.close()
+    return m, runs
+
+
+@pytest.mark.parametrize("name", ["visc", "buoy"])
+def test_coupled_fixed_point_against_the_oracle(coupled_runs, name):
+    fx = np.load(FIXTURE)
+    _, runs = coupled_runs
+    w, c, recs = runs[name]
+    wo, co = fx[name + "_w"], fx[name + "_c"]
+    e = (rel(w.reshape(-1, 4)[:, :3], wo.reshape(-1, 4)[:, :3]), rel(w.reshape(-1, 4)[:, 3], wo.reshape(-1, 4)[:, 3]), rel(c, co))
+    print(f"{name}: {len(recs)} outer steps (oracle {int(fx[name + '_outer'])}, factor {float(fx[name + '_factor']):.3f}); "
+          f"Newton its {[r['newton_its'] for r in recs]}, ksp {[r['ksp_its'] for r in recs]}, scalar its {[r['scalar_its'] for r in recs]}; "
+          f"rel err u {e[0]:.2e} p {e[1]:.2e} c {e[2]:.2e}")
+    assert all(r["newton_reason"] > 0 and r["scalar_reason"] > 0 for r in recs), recs
+    assert recs[-1]["converged"] and len(recs) <= int(fx[name + "_outer"]) + 2
+    assert _fields_close(w, wo) and rel(c, co) < 1e-6, e
+    wu, cu, _ = runs["unc"]
+    assert _fields_close(wu, fx["unc_w"]) and rel(cu, fx["unc_c"]) < 1e-6
+    assert not _fields_close(w, wu, 1e-3)                          # (the coupled field is another field)
+
+
+def test_a_more_viscous_inner_stream_is_the_slower_one(coupled_runs):
+    fx = np.load(FIXTURE)
+    m, runs = coupled_runs
+    v, u = G.inner_outlet_mean(m, *runs["visc"][:2]), G.inner_outlet_mean(m, *runs["unc"][:2])
+    margin = 0.5 * (float(fx["inner_unc"]) - float(fx["inner_visc"]))       # half of what the CPU oracle's own two runs show
+    print(f"mean outlet u_x where c > 0.5: ratio 4 {v:.6f} (oracle {float(fx['inner_visc']):.6f}), ratio 1 {u:.6f} "
+          f"(oracle {float(fx['inner_unc']):.6f}), margin {margin:.6f}")
+    assert margin > 0.0 and v < u - margin
+
+
+# ---- 11. forces ------------------------------------------------------------------------------------------------------
+def test_residual_moments_with_both_fields_against_the_oracle():
+    rng = np.random.default_rng(91)
+    fx = np.load(FIXTURE)
+    m, mask, g, _, _ = G.duct_problem()
+    P = FlowProblem(m, (mask, g), reynolds=C["Re"])
+    nu_t, f = FO.mixture_fields(m.points, m.tets, fx["visc_c"], C["Re"], np.log(4.0), (0.4, -2.0, 0.1))
+    P.set_mixture(fx["visc_c"], np.log(4.0), (0.4, -2.0, 0.1))
+    wh = fx["visc_w"] + 0.05 * rng.normal(size=m.num_dofs)         # (may violate the Dirichlet data: raw residual)
+    base = dict(FL.VARIANT)
+    try:
+        for variant in (False, True):                               # the one-lane-per-tet leg, then the staged leg (rm_nomask)
+            if variant:
+                FL.VARIANT.update(ci=144.0, lsic=4.0)
+                P.set_form_variant(c_inverse=144.0, lsic_scale=4.0)
+            F, _ = FO.raw(m.points, m.tets, wh, C["Re"], f=f, nu_t=nu_t, want_jac=False)
+            for phi in (rng.uniform(-1.0, 1.0, size=m.num_nodes), (m.points[:, 0] < 0.5).astype(np.float64)):
+                out = P.residual_moments(_dev(wh), phi)
+                ref = (phi[:, None] * F.reshape(-1, 4)).sum(axis=0)
+                assert np.abs(out - ref).max() <= 1e-12 * np.linalg.norm(ref), (variant, out, ref)
+    finally:
+        FL.VARIANT.update(base)
+    P.close()
+
+
+# ---- 12. adjoint -----------------------------------------------------------------------------------------------------
+def test_adjoint_identity_on_a_fields_on_jacobian():
+    m = M.duct_mesh((40, 10, 10), 2.0)
+    P = FlowProblem(m, B.duct_bcs(m).flatten(), reynolds=25.0)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    P.set_mixture(G.smooth_m(m.points), np.log(4.0), (0.5, -2.0, 0.3))
+    P.jacobian(U, "ns")
+    A = P.to_scipy()
+    rng = np.random.default_rng(92)
+    free = P.bc_mask == 0
+    for vanish in (True, False):
+        b, gg = rng.normal(size=P.ndof), rng.normal(size=P.ndof)
+        if vanish:
+            b, gg = b * free, gg * free
+        _adjoint_identity(P, A, b, gg, f"fields vanish={vanish}")
+    P.close()
+
+
+# ---- 13. end to end --------------------------------------------------------------------------------------------------
+def test_duct_driver_with_the_coupling_switches(tmp_path, monkeypatch, capsys):
+    """DuctStokesFlow.py at the size of the driver test of tests/test_gpu_parity.py with SNS_SCALAR_PECLET, without and with
+    SNS_VISCOSITY_RATIO / SNS_BUOYANCY: the coupled run writes the same files and adds one line with the outer iteration count."""
+    import os
+    from stabilized_navier_stokes_flow_fenicsx_amd import drivers as D
+    argv = ["DuctStokesFlow.py", "ductmesh", "0.25", "2.0"]
+    monkeypatch.setenv("SNS_SCALAR_PECLET", "250")
+    runs = {}
+    for switch in ("0", "1"):
+        d = tmp_path / switch
+        d.mkdir()
+        monkeypatch.chdir(d)
+        if switch == "1":
+            monkeypatch.setenv("SNS_VISCOSITY_RATIO", "4")
+            monkeypatch.setenv("SNS_BUOYANCY", "0,-1,0")
+        else:
+            monkeypatch.delenv("SNS_VISCOSITY_RATIO", raising=False)
+            monkeypatch.delenv("SNS_BUOYANCY", raising=False)
+        msh, W, res = D.duct_stokes_main(argv)
+        assert res.reason > 0
+        runs[switch] = (W, capsys.readouterr().out.splitlines(), sorted(os.listdir(d)))
+    (W0, out0, files0), (W1, out1, files1) = runs["0"], runs["1"]
+    assert files0 == files1 and "StokesDuctConcentration.h5" in files0
+    extra = [ln for ln in out1 if ln.startswith("Coupled flow")]
+    assert len(extra) == 1 and " outer iterations, converged" in extra[0], out1
+    assert len(out1) == len(out0) + 1 and not any(ln.startswith("Coupled flow") for ln in out0)
+    assert sum(ln.startswith("Scalar transport Pe 250:") for ln in out1) == 1
+    assert rel(W1, W0) > 1e-3                                       # (the coupled flow is another flow)
+    monkeypatch.delenv("SNS_SCALAR_PECLET")
+    with pytest.raises(ValueError):
+        D._coupled_flow(None, None, msh)                            # the coupling acts through the transported scalar

@@ -1,0 +1,147 @@
+"""The 3-D NS form with a body force and a per-cell viscosity field on the CPU: the test-side oracle (tests/fields_oracle.py)
+against the two oracles it generalises (tests/transient_oracle.py, tests/viscosity_oracle.py), the patch test with a body force on
+the oracle itself, the binding of the three new entry points, and the fixture tests/golden/fields_cases.npz against its recipe
+scripts/make_fields_golden.py (the GPU tests reproduce its fields)."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, rel
+
+torch = pytest.importorskip("torch")
+
+import fields_oracle as FO  # noqa: E402
+import transient_oracle as TO  # noqa: E402
+import viscosity_oracle as VO  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(GOLDEN, "fields_cases.npz")
+
+
+def golden_script():
+    spec = importlib.util.spec_from_file_location("make_fields_golden", os.path.join(ROOT, "scripts", "make_fields_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def patch_problem():
+    """The patch test with a body force: on the jittered (6, 3, 3) duct u = A x + b with tr A = 0 and p = g.x + p0 (random, fixed
+    seed) solve the corrected-convection form with f = A u + g at the nodes (exactly P1), velocity Dirichlet = exact on every
+    boundary node, pressure Dirichlet = exact on the outlet nodes.  Returns (mesh, mask, data, exact state, force, Re)."""
+    from stabilized_navier_stokes_flow_fenicsx_amd import mesh as M
+    rng = np.random.default_rng(71)
+    m = M.duct_mesh((6, 3, 3), 2.0, jitter=0.2)
+    A = rng.normal(size=(3, 3))
+    A -= np.eye(3) * np.trace(A) / 3.0
+    b, gp, p0 = rng.normal(size=3), rng.normal(size=3), rng.normal()
+    u = m.points @ A.T + b
+    w = np.concatenate([u, (m.points @ gp + p0)[:, None]], axis=1)
+    f = np.zeros_like(w)
+    f[:, :3] = u @ A.T + gp
+    mask = np.zeros((m.num_nodes, 4), np.uint8)
+    tags = m.meta["tags"]
+    for t in tags.values():
+        mask[m.facet_nodes(t), :3] = 1
+    mask[m.facet_nodes(tags["outlet"]), 3] = 1
+    mask = mask.ravel()
+    return m, mask, np.where(mask, w.ravel(), 0.0), w.ravel(), f.ravel(), 20.0
+
+
+@pytest.mark.parametrize("corrected", [False, True])
+def test_without_fields_it_is_the_transient_oracle(corrected):
+    rng = np.random.default_rng(72)
+    X = golden_script().random_tets(rng, 6)
+    W, D = rng.normal(size=(6, 16)), rng.normal(size=(6, 4, 3))
+    for sigma, theta in ((0.0, 0.0), (7.0, 0.0), (20.0, 1600.0)):
+        a = FO.residual(X, torch.as_tensor(W), D, None, np.full(6, 1.0 / 37.0), 37.0, sigma, theta, False, corrected_convection=corrected)
+        b = TO.transient_residual(X, torch.as_tensor(W), D, 37.0, sigma, theta, corrected_convection=corrected)
+        assert rel(a.numpy(), b.numpy()) < 1e-14
+        # ... and a force is a history of the other sign
+        F = rng.normal(size=(6, 4, 3))
+        a = FO.residual(X, torch.as_tensor(W), D, F, None, 37.0, sigma, theta, False, corrected_convection=corrected)
+        b = TO.transient_residual(X, torch.as_tensor(W), D - F, 37.0, sigma, theta, corrected_convection=corrected)
+        assert rel(a.numpy(), b.numpy()) < 1e-14
+
+
+@pytest.mark.parametrize("corrected", [False, True])
+def test_uniform_stress_divergence_form_is_the_law_at_n_one(corrected):
+    rng = np.random.default_rng(73)
+    X = golden_script().random_tets(rng, 6)
+    W = rng.normal(size=(6, 16))
+    a = FO.residual(X, torch.as_tensor(W), None, None, None, 37.0, 0.0, 0.0, True, corrected_convection=corrected)
+    b = VO.law_residual(X, torch.as_tensor(W), 37.0, 2.5, 1.0, 0.05, corrected_convection=corrected)
+    assert rel(a.numpy(), b.numpy()) < 1e-14
+    nu = 10.0 ** rng.uniform(-3.0, 0.0, size=6)
+    c = FO.residual(X, torch.as_tensor(W), None, None, nu, 37.0, 0.0, 0.0, True, corrected_convection=corrected)
+    assert rel(c.numpy(), a.numpy()) > 1e-3                                       # (the field is something)
+
+
+def test_autograd_jacobian_against_central_differences():
+    rng = np.random.default_rng(74)
+    X = golden_script().random_tets(rng, 4)
+    W, D, F = rng.normal(size=(4, 16)), rng.normal(size=(4, 4, 3)), rng.normal(size=(4, 4, 3))
+    nu = 10.0 ** rng.uniform(-2.0, 0.0, size=4)
+    args = (D, F, nu, 20.0, 5.0, 100.0, True)
+    _, J = FO.element(X, W, *args)
+    h = 1e-6
+    for k in range(16):
+        dW = np.zeros_like(W)
+        dW[:, k] = h
+        Fp, _ = FO.element(X, W + dW, *args, want_jac=False)
+        Fm, _ = FO.element(X, W - dW, *args, want_jac=False)
+        assert rel(J[:, :, k], (Fp - Fm) / (2 * h)) < 1e-7
+
+
+def test_mixture_fields_closed_form():
+    pts = np.array([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 1]])
+    tets = np.array([[0, 1, 2, 3], [1, 2, 3, 4]], np.int32)
+    m = np.array([0.0, 1.0, 1.0, 0.0, 2.0])
+    nu, f = FO.mixture_fields(pts, tets, m, 8.0, np.log(16.0), (0.0, -3.0, 0.5))
+    assert rel(nu, [0.125 * 4.0, 0.125 * 16.0]) < 1e-15                           # 16^(1/2), 16^1
+    assert np.array_equal(f.reshape(5, 4), m[:, None] * np.array([0.0, -3.0, 0.5, 0.0])[None, :])
+    nu, f = FO.mixture_fields(pts, tets, -m, 8.0, 50.0, (0.0, 0.0, 0.0))          # undershoot: still positive
+    assert np.all(nu > 0.0) and not f.any()
+
+
+def test_patch_test_with_a_body_force_on_the_oracle():
+    m, mask, g, w, f, Re = patch_problem()
+    free = mask == 0
+    for kw in (dict(), dict(nu_t=np.full(m.num_tets, 0.37))):                     # the reference's viscous form; the stress-divergence form
+        _, F = FO.assemble(m.points, m.tets, w, Re, mask, g, f=f, corrected_convection=True, **kw)
+        _, F0 = FO.assemble(m.points, m.tets, w, Re, mask, g, corrected_convection=True, **kw)
+        print(f"patch test {sorted(kw)}: max |F_free| {np.abs(F[free]).max():.2e}, with the force cleared {np.abs(F0[free]).max():.2e}")
+        assert np.abs(F[free]).max() <= 1e-12 * np.abs(F0[free]).max()
+    x, _ = FO.newton(m.points, m.tets, mask, g, Re, np.where(free, 0.0, w), f=f, corrected_convection=True)
+    assert rel(x, w) < 1e-10
+
+
+def test_the_new_entry_points_are_bound():
+    import ctypes as C
+    from stabilized_navier_stokes_flow_fenicsx_amd import _lib
+    assert {"sns_set_body_force", "sns_set_element_viscosity", "sns_set_mixture"} <= set(_lib.SYMBOLS)
+    assert _lib.ABI_VERSION == 8
+    lib = _lib.load()
+    assert lib.sns_set_body_force.argtypes == [C.c_void_p, C.c_void_p]
+    assert lib.sns_set_element_viscosity.argtypes == [C.c_void_p, C.c_void_p]
+    assert lib.sns_set_mixture.argtypes == [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double)]
+    for call in (lambda: lib.sns_set_body_force(None, None), lambda: lib.sns_set_element_viscosity(None, None),
+                 lambda: lib.sns_set_mixture(None, None, 0.0, None)):
+        assert call() == -1                                                       # SNS_E_ARG without a handle, no GPU touched
+
+
+def test_fixture_regenerates_from_the_script():
+    G = golden_script()
+    fx = np.load(FIXTURE)
+    assert os.path.getsize(FIXTURE) < 165000
+    a = G.build()
+    assert set(a) == set(fx.files)
+    for k in a:
+        tol = 0.0 if k.startswith("el_") and k != "el_R" else 1e-9               # inputs: the seeded draws themselves
+        assert rel(np.asarray(a[k], dtype=np.float64), np.asarray(fx[k], dtype=np.float64)) <= tol, k
+    for name in ("visc", "buoy"):                                                # the oracle's own loop contracts to 1e-9 well inside 30 steps
+        assert int(fx[name + "_outer"]) <= 15 and 0.0 < float(fx[name + "_factor"]) < 0.5, name
+        assert rel(fx[name + "_w"], fx["unc_w"]) > 1e-3
+    assert float(fx["inner_visc"]) < float(fx["inner_unc"])                       # the more viscous inner stream is the slower one
