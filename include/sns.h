@@ -591,7 +591,7 @@ SNS_API int sns_element_viscosity(sns_handle h, const double* w_dev, double* nu_
  * was, bit for bit.  An assembled matrix stays what it was; a changed viscosity field makes the next preconditioner set-up
  * re-estimate its smoother damping, a changed body force does not.
  *   sns_set_mixture  the convenience for two miscible fluids: from a nodal P1 field m_dev (n_local doubles, typically species
- *                    0 of a scalar solve) it sets, in one small kernel (csrc/sns_fields.hip),
+ *                    0 of a scalar solve) it sets, in one small kernel (csrc/sns_form.hip),
  *                      nu_t = (1/Re) exp(log_viscosity_ratio * 1/4 sum_a m_a)   (log-mixing rule at the centroid: positive
  *                                                                               whatever over- or undershoot m has),
  *                      f_a  = m_a * buoyancy                                    (Boussinesq; buoyancy = Ri * g_hat).

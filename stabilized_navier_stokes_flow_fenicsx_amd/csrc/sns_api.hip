@@ -284,6 +284,29 @@ int ensure_hierarchy(sns_ctx* h, bool assembles_next = false) {
     return rc;
 }
 
+// The form state's answer to `request` (the table of policy::check_form_request) as the error of the entry point `who`.  The
+// table's dimension row (SNS_E_ARG) stands among the argument checks of some entry points, its state rows (SNS_E_STATE) after
+// them: ROWS_ARG / ROWS_STATE ask for one kind, so that a call with two things wrong reports what it always reported.
+enum FormRows { ROWS_ALL = 0, ROWS_ARG = SNS_E_ARG, ROWS_STATE = SNS_E_STATE };
+int form_allows(const sns_ctx* h, const char* who, policy::FormRequest request, FormRows rows = ROWS_ALL) {
+    const FormState& S = h->form;
+    const policy::FormVerdict v = policy::check_form_request(request, {h->dim, h->comm != nullptr, S.tt_on, S.vl_on, S.bf_on, S.ev_on});
+    if (v.error == SNS_OK || (rows != ROWS_ALL && v.error != rows)) return SNS_OK;
+    set_error(std::string(who) + ": " + v.tail);
+    return v.error;
+}
+
+// the end of a linear solve whose Dirichlet rows are identity rows: the reference's ILU-preconditioned solve returns them
+// exactly, a Krylov method under AMG only to its tolerance -- a converged solve hands back the exact data `val` under `mask`
+int solve_and_snap(sns_ctx* h, const double* b, double* x, const uint8_t* mask, const double* val, int* its, int* reason,
+                   double* rnorm) {
+    SNS_TRY(krylov(h, b, x, its, reason, rnorm));
+    if (*reason <= 0) return SNS_OK;
+    const int64_t nd = nred_of(h);
+    hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, mask, val, 1e300, x);
+    return sync_stream(h);
+}
+
 }  // namespace
 
 
@@ -338,17 +361,8 @@ int sns_set_options(sns_handle h, const sns_options* o) {
 
 int sns_set_form_variant(sns_handle h, double c_inverse, double lsic_scale, double pspg_sign, int one_point_quadrature) {
     if (!h) return SNS_E_ARG;
-    if (h->dim != 3) { set_error("sns_set_form_variant: 3-D handles only"); return SNS_E_ARG; }
-    FormVariant fv;
-    fv.ci = c_inverse;
-    fv.lsic = lsic_scale;
-    fv.pspg = pspg_sign;
-    if (one_point_quadrature) fv.qa = fv.qb = 0.25;
-    h->fv = fv;
-    h->has_matrix = false;
-    h->transposed = false;
-    h->pc_ready = false;
-    return SNS_OK;
+    SNS_TRY(form_allows(h, "sns_set_form_variant", policy::REQ_FORM_VARIANT));
+    return set_form_variant(h, c_inverse, lsic_scale, pspg_sign, one_point_quadrature);
 }
 
 int sns_get_options(sns_handle h, sns_options* o) {
@@ -532,36 +546,19 @@ int sns_residual_shape_gradient(sns_handle h, int form, const double* w, const d
         set_error(form == SNS_FORM_STOKES ? "sns_residual_shape_gradient: the Stokes forms are not supported" : "bad form");
         return SNS_E_ARG;
     }
-    if (h->comm) {
-        set_error("sns_residual_shape_gradient: not with a communicator attached (partitioned shape gradients are not built)");
-        return SNS_E_STATE;
-    }
-    if (h->vl_on) {
-        set_error("sns_residual_shape_gradient: not with a viscosity law set (the mesh derivative of nu_e is not built)");
-        return SNS_E_STATE;
-    }
-    if (h->bf_on || h->ev_on) {
-        set_error("sns_residual_shape_gradient: not with a body force or a viscosity field set (the mesh derivative is not built with them)");
-        return SNS_E_STATE;
-    }
+    SNS_TRY(form_allows(h, "sns_residual_shape_gradient", policy::REQ_SHAPE_GRADIENT));
     return residual_shape_gradient(h, w, lam, gX);
 }
 
 int sns_recover_gradient(sns_handle h, const double* w, double* G, double* D) {
     if (!h || !w || (!G && !D)) { set_error("sns_recover_gradient: null handle, state or both outputs null"); return SNS_E_ARG; }
-    if (h->comm) {
-        set_error("sns_recover_gradient: not with a communicator attached (partitioned gradient recovery is not built)");
-        return SNS_E_STATE;
-    }
+    SNS_TRY(form_allows(h, "sns_recover_gradient", policy::REQ_RECOVER_GRADIENT));
     return recover_gradient(h, w, G, D);
 }
 
 int sns_error_indicator(sns_handle h, const double* w, const double* G, double* eta2, double* gnorm2) {
     if (!h || !w || !eta2) { set_error("sns_error_indicator: null handle, state or eta2"); return SNS_E_ARG; }
-    if (h->comm) {
-        set_error("sns_error_indicator: not with a communicator attached (a partitioned indicator needs a halo exchange of G)");
-        return SNS_E_STATE;
-    }
+    SNS_TRY(form_allows(h, "sns_error_indicator", policy::REQ_ERROR_INDICATOR));
     return error_indicator(h, w, G, eta2, gnorm2);
 }
 
@@ -607,21 +604,16 @@ int sns_adjoint_solve(sns_handle h, const double* g, double* lam, int* its, int*
     if (!h || !g || !lam || !its || !reason || !rnorm) return SNS_E_ARG;
     SNS_TRY(transpose_operator(h));                      // (SNS_E_STATE / SNS_E_MESH: nothing was modified)
     int rc = ensure_hierarchy(h);
-    if (rc == SNS_OK) rc = krylov(h, g, lam, its, reason, rnorm);
-    // the Dirichlet rows AND columns of A are unit rows: lam_B = g_B exactly, and a converged solve hands that back (as
-    // sns_stokes_solve does with the Dirichlet data); the other rows' residual does not see it
-    if (rc == SNS_OK && *reason > 0) {
-        const int64_t nd = nred_of(h);
-        // (the mask of the operator that was transposed: the scalars' own while the scalar operator is the handle's matrix)
-        const uint8_t* mask = h->matrix_form == SNS_FORM_SCALAR ? h->sc_mask.get() : h->bc_mask.get();
-        hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, mask, g, 1e300, lam);
-        rc = sync_stream(h);
-    }
+    // the Dirichlet rows AND columns of A are unit rows: lam_B = g_B exactly, and a converged solve hands that back; the other
+    // rows' residual does not see it.  (The mask of the operator that was transposed: the scalars' own while the scalar operator
+    // is the handle's matrix)
+    const uint8_t* mask = h->matrix_form == SNS_FORM_SCALAR ? h->sc_mask.get() : h->bc_mask.get();
+    if (rc == SNS_OK) rc = solve_and_snap(h, g, lam, mask, g, its, reason, rnorm);
     // back to A, after a solve that did not converge too; a HIP or transport error leaves the device state undefined
     if (rc == SNS_E_HIP || rc == SNS_E_COMM) return rc;
     const std::string err = g_err;
     const int rb = transpose_operator(h);
-    h->pc_ready = false;
+    pc_stale(h);
     if (rc != SNS_OK) { set_error(err); return rc; }
     return rb;
 }
@@ -646,15 +638,7 @@ int sns_stokes_solve(sns_handle h, double* U, int* ksp_its, int* reason, double*
     SNS_TRY(ensure_hierarchy(h));
     hipLaunchKernelGGL(k_scale_copy, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, -1.0, h->nw_F, h->nw_F);
     HIP_TRY(hipMemsetAsync(U, 0, nd * sizeof(double), h->stream));
-    SNS_TRY(krylov(h, h->nw_F, U, ksp_its, reason, rnorm));
-    // the Dirichlet rows are identity rows: the reference's ILU-preconditioned solve returns them exactly, a Krylov
-    // method under AMG only to its tolerance -- a converged solve hands back the exact data as well
-    if (*reason > 0) {
-        hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, h->bc_mask, h->bc_val,
-                           1e300, U);
-        SNS_TRY(sync_stream(h));
-    }
-    return SNS_OK;
+    return solve_and_snap(h, h->nw_F, U, h->bc_mask, h->bc_val, ksp_its, reason, rnorm);
 }
 
 
@@ -752,20 +736,19 @@ static int newton_run(sns_ctx* h, double* w, int* its_out, int* reason_out, int*
     return SNS_OK;
 }
 
-// the argument checks of the two scalar-transport entry points (`who`: the name in front of the message)
+// the checks of the two scalar-transport entry points (`who`: the name in front of the message)
 static int scalar_check(const char* who, sns_ctx* h, const double* w, const double* kappa, double sigma, double theta,
                         const uint8_t* cmask, const double* cval, const void* out) {
     const std::string name(who);
     if (!h || !w || !kappa || !cmask || !cval || !out) { set_error(name + ": null handle or pointer"); return SNS_E_ARG; }
-    if (h->dim != 3) { set_error(name + ": 3-D handles only"); return SNS_E_ARG; }
+    SNS_TRY(form_allows(h, who, policy::REQ_SCALAR, ROWS_ARG));
     for (int k = 0; k < 4; ++k)
         if (!(kappa[k] > 0.0) || !std::isfinite(kappa[k])) { set_error(name + ": every kappa must be finite and > 0"); return SNS_E_ARG; }
     if (!(sigma >= 0.0) || !std::isfinite(sigma) || !(theta >= 0.0) || !std::isfinite(theta)) {
         set_error(name + ": sigma and theta must be finite and >= 0");
         return SNS_E_ARG;
     }
-    if (h->comm) { set_error(name + ": not with a communicator attached (partitioned scalar transport is not built)"); return SNS_E_STATE; }
-    return SNS_OK;
+    return form_allows(h, who, policy::REQ_SCALAR, ROWS_STATE);
 }
 
 int sns_scalar_system(sns_handle h, const double* w_dev, const double kappa[4], double sigma, double theta, const double* src_dev,
@@ -782,14 +765,7 @@ int sns_scalar_solve(sns_handle h, const double* w_dev, const double kappa[4], d
     SNS_TRY(ensure_newton_workspace(h));
     SNS_TRY(scalar_system(h, w_dev, kappa, sigma, theta, src_dev, cmask_dev, cval_dev, h->nw_F));
     SNS_TRY(ensure_hierarchy(h));
-    SNS_TRY(krylov(h, h->nw_F, c_dev, its, reason, rnorm));
-    // the Dirichlet rows are identity rows: a converged solve hands back the exact data (as sns_stokes_solve does)
-    if (*reason > 0) {
-        const int64_t nd = nred_of(h);
-        hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, cmask_dev, cval_dev, 1e300, c_dev);
-        SNS_TRY(sync_stream(h));
-    }
-    return SNS_OK;
+    return solve_and_snap(h, h->nw_F, c_dev, cmask_dev, cval_dev, its, reason, rnorm);
 }
 
 int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int* total_ksp, double* hist,
@@ -800,40 +776,21 @@ int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int
 
 int sns_set_time_term(sns_handle h, double sigma, double theta, const double* d_dev) {
     if (!h) return SNS_E_ARG;
-    if (h->dim != 3) { set_error("sns_set_time_term: 3-D handles only"); return SNS_E_ARG; }
+    const policy::FormRequest req = (sigma == 0.0 && theta == 0.0 && !d_dev) ? policy::REQ_CLEAR_TIME_TERM : policy::REQ_SET_TIME_TERM;
+    SNS_TRY(form_allows(h, "sns_set_time_term", req, ROWS_ARG));
     if (!(sigma >= 0.0) || !std::isfinite(sigma) || !(theta >= 0.0) || !std::isfinite(theta)) {
         set_error("sns_set_time_term: sigma and theta must be finite and >= 0");
         return SNS_E_ARG;
     }
     if (sigma > 0.0 && !d_dev) { set_error("sns_set_time_term: sigma > 0 needs a history vector"); return SNS_E_ARG; }
-    if (h->comm) { set_error("sns_set_time_term: not with a communicator attached (partitioned time stepping is not built)"); return SNS_E_STATE; }
-    if (h->vl_on && !(sigma == 0.0 && theta == 0.0 && !d_dev)) {
-        set_error("sns_set_time_term: not with a viscosity law set (the transient form has no law)");
-        return SNS_E_STATE;
-    }
-    if (sigma != h->tt.sigma || theta != h->tt.theta) {   // another operator: re-estimate the smoother's damping caps
-        h->est_form = -1;
-        h->pc_ready = false;
-    }
-    if (sigma == 0.0 && theta == 0.0 && !d_dev) {         // back to the steady form (the buffer stays with the handle)
-        h->tt.sigma = h->tt.theta = 0.0;
-        h->tt_on = false;
-        return refresh_history(h);                        // (a body force stays: the history is -f again)
-    }
-    const size_t ld = (size_t)ld_of(h);
-    if (!h->tt_d) SNS_TRY(h->tt_d.alloc(ld));
-    if (d_dev) HIP_TRY(hipMemcpyAsync(h->tt_d, d_dev, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    else HIP_TRY(hipMemsetAsync(h->tt_d, 0, ld * sizeof(double), h->stream));
-    h->tt.sigma = sigma;
-    h->tt.theta = theta;
-    h->tt_on = true;
-    SNS_TRY(refresh_history(h));                          // tt.d = the handle's d, or d - f under a body force
-    return sync_stream(h);                                // the caller may free d_dev
+    SNS_TRY(form_allows(h, "sns_set_time_term", req, ROWS_STATE));
+    return set_time_term(h, sigma, theta, d_dev);
 }
 
 int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double nu_inf_ratio) {
     if (!h) return SNS_E_ARG;
-    if (h->dim != 3) { set_error("sns_set_viscosity_law: 3-D handles only"); return SNS_E_ARG; }
+    const policy::FormRequest req = law == SNS_LAW_CARREAU ? policy::REQ_SET_CARREAU : policy::REQ_SET_NEWTONIAN;
+    SNS_TRY(form_allows(h, "sns_set_viscosity_law", req, ROWS_ARG));
     if (law != SNS_LAW_NEWTONIAN && law != SNS_LAW_CARREAU) { set_error("sns_set_viscosity_law: unknown law"); return SNS_E_ARG; }
     if (law == SNS_LAW_CARREAU) {
         if (!(lambda >= 0.0) || !std::isfinite(lambda)) { set_error("sns_set_viscosity_law: lambda must be finite and >= 0"); return SNS_E_ARG; }
@@ -843,65 +800,34 @@ int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double
             return SNS_E_ARG;
         }
     }
-    if (h->comm) { set_error("sns_set_viscosity_law: not with a communicator attached (partitioned handles have no law)"); return SNS_E_STATE; }
-    if (h->tt_on) { set_error("sns_set_viscosity_law: not with a time term set (the transient form has no law)"); return SNS_E_STATE; }
-    if (law == SNS_LAW_CARREAU && (h->bf_on || h->ev_on)) {
-        set_error("sns_set_viscosity_law: not with a body force or a viscosity field set");
-        return SNS_E_STATE;
-    }
-    ViscosityLaw vl;
-    if (law == SNS_LAW_CARREAU) { vl.lambda = lambda; vl.n = n; vl.r = nu_inf_ratio; }
-    const bool on = law == SNS_LAW_CARREAU;
-    if (on != h->vl_on || vl.lambda != h->vl.lambda || vl.n != h->vl.n || vl.r != h->vl.r) {
-        h->est_form = -1;                                 // another operator: re-estimate the smoother's damping caps
-        h->pc_ready = false;
-    }
-    h->vl = vl;
-    h->vl_on = on;
-    return SNS_OK;
+    SNS_TRY(form_allows(h, "sns_set_viscosity_law", req, ROWS_STATE));
+    return set_viscosity_law(h, law == SNS_LAW_CARREAU, lambda, n, nu_inf_ratio);
 }
 
 int sns_element_viscosity(sns_handle h, const double* w, double* nu_dev, double* gamma_dot_dev) {
     if (!h || !w) { set_error("sns_element_viscosity: null handle or state"); return SNS_E_ARG; }
-    if (h->dim != 3) { set_error("sns_element_viscosity: 3-D handles only"); return SNS_E_ARG; }
-    if (h->E > 0 && h->ev_on && nu_dev) {               // the field where one is set (gamma_dot below as without one)
-        HIP_TRY(hipMemcpyAsync(nu_dev, h->ev_nu, (size_t)h->E * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        nu_dev = nullptr;
-    }
-    if (h->E > 0 && (nu_dev || gamma_dot_dev)) {
-        const unsigned gt = (unsigned)((h->E + 255) / 256);
-        const double nu = 1.0 / h->opt.reynolds;
-        dispatch<1, 0>(h->vl_on, [&](auto V) {
-            hipLaunchKernelGGL((k_element_viscosity<V() != 0>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w, nu,
-                               h->vl, nu_dev, gamma_dot_dev);
-        });
-        HIP_TRY(hipGetLastError());
-    }
-    return sync_stream(h);
+    SNS_TRY(form_allows(h, "sns_element_viscosity", policy::REQ_ELEMENT_VISCOSITY));
+    return element_viscosity(h, w, nu_dev, gamma_dot_dev);
 }
 
-// the checks the three field setters share (`who`: the name in front of the message)
-static int fields_check(const char* who, sns_ctx* h) {
-    const std::string name(who);
-    if (!h) { set_error(name + ": null handle"); return SNS_E_ARG; }
-    if (h->dim != 3) { set_error(name + ": 3-D handles only"); return SNS_E_ARG; }
-    if (h->comm) { set_error(name + ": not with a communicator attached (partitioned handles have no external fields)"); return SNS_E_STATE; }
-    if (h->vl_on) { set_error(name + ": not with a viscosity law set"); return SNS_E_STATE; }
-    return SNS_OK;
+// the three field setters (`who`: the name in front of the message)
+static int field_request(const char* who, const sns_ctx* h) {
+    if (!h) { set_error(std::string(who) + ": null handle"); return SNS_E_ARG; }
+    return form_allows(h, who, policy::REQ_SET_FIELD);
 }
 
 int sns_set_body_force(sns_handle h, const double* f_dev) {
-    SNS_TRY(fields_check("sns_set_body_force", h));
+    SNS_TRY(field_request("sns_set_body_force", h));
     return set_body_force(h, f_dev);
 }
 
 int sns_set_element_viscosity(sns_handle h, const double* nu_dev) {
-    SNS_TRY(fields_check("sns_set_element_viscosity", h));
+    SNS_TRY(field_request("sns_set_element_viscosity", h));
     return set_element_viscosity(h, nu_dev);
 }
 
 int sns_set_mixture(sns_handle h, const double* m_dev, double log_viscosity_ratio, const double buoyancy[3]) {
-    SNS_TRY(fields_check("sns_set_mixture", h));
+    SNS_TRY(field_request("sns_set_mixture", h));
     if (!std::isfinite(log_viscosity_ratio)) { set_error("sns_set_mixture: the log viscosity ratio must be finite"); return SNS_E_ARG; }
     if (buoyancy && !(std::isfinite(buoyancy[0]) && std::isfinite(buoyancy[1]) && std::isfinite(buoyancy[2]))) {
         set_error("sns_set_mixture: the buoyancy must be finite");
@@ -916,18 +842,17 @@ int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, 
     if (order != 1 && order != 2) { set_error("sns_time_step: order must be 1 or 2"); return SNS_E_ARG; }
     if (!(dt > 0.0) || !std::isfinite(dt)) { set_error("sns_time_step: dt must be positive"); return SNS_E_ARG; }
     if (order == 2 && !wprev) { set_error("sns_time_step: BDF2 needs the state before w"); return SNS_E_ARG; }
-    if (h->dim != 3) { set_error("sns_time_step: 3-D handles only"); return SNS_E_ARG; }
+    SNS_TRY(form_allows(h, "sns_time_step", policy::REQ_TIME_STEP, ROWS_ARG));
     if (!(theta_coeff >= 0.0) || !std::isfinite(theta_coeff)) { set_error("sns_time_step: theta_coeff must be finite and >= 0"); return SNS_E_ARG; }
-    if (h->comm) { set_error("sns_time_step: not with a communicator attached (partitioned time stepping is not built)"); return SNS_E_STATE; }
-    if (h->vl_on) { set_error("sns_time_step: not with a viscosity law set (the transient form has no law)"); return SNS_E_STATE; }
+    SNS_TRY(form_allows(h, "sns_time_step", policy::REQ_TIME_STEP, ROWS_STATE));
     const int64_t ld = ld_of(h);
     const int g = vec_grid(ld);
     // BDF1: u_t = (u - u^n) / dt;  BDF2: u_t = (3 u - 4 u^n + u^(n-1)) / (2 dt).  d in a workspace vector (copied by
     // sns_set_time_term), the entry state in a buffer of its own (a step that does not converge restores it)
     double *d = nullptr, *w0 = nullptr;
     SNS_TRY(get_vec(h, VEC_SCRATCH, &d));
-    if (!h->tt_w0) SNS_TRY(h->tt_w0.alloc((size_t)ld));
-    w0 = h->tt_w0;
+    if (!h->form.tt_w0) SNS_TRY(h->form.tt_w0.alloc((size_t)ld));
+    w0 = h->form.tt_w0;
     const double sigma = (order == 1 ? 1.0 : 1.5) / dt;
     hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, ld, (order == 1 ? -1.0 : -2.0) / dt, w, d);
     if (order == 2) hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, h->stream, ld, 0.5 / dt, wprev, 1.0, d);

@@ -18,9 +18,10 @@ struct FormPass {
     ViscosityLaw vl;
 };
 
-// THE place where (corrected convection, ns_variant) becomes the <C, TT, VL, EV> of the 3-D NS assembly kernels: a new compile-time
+// THE place where (corrected convection, FormState::ns_variant) becomes the <C, TT, VL, EV> of the 3-D NS assembly kernels: a new compile-time
 // variant is added to the kernels' instantiation lists (csrc/sns_kernels.hip) and here, nowhere else.
 FormPass form_pass(const sns_ctx* h, int form) {
+    const FormState& S = h->form;
     const double nu = 1.0 / h->opt.reynolds;
     if (h->dim == 2 && form == SNS_FORM_NS)
         return {&k_fused_offdiag<SNS_FORM_UGN_2D, false>, &k_fused_diag<SNS_FORM_UGN_2D, false>, &k_fused_lift<SNS_FORM_UGN_2D, false>,
@@ -33,11 +34,11 @@ FormPass form_pass(const sns_ctx* h, int form) {
                 nullptr, nu, 0.0, TimeTerm(), ViscosityLaw()};
     FormPass k{};
     dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-        dispatch<3, 2, 1, 0>(ns_variant(h), [&](auto V) {
+        dispatch<3, 2, 1, 0>(S.ns_variant(), [&](auto V) {
             constexpr bool c = C() != 0, ev = V() == 3, tt = V() == 1 || ev, vl = V() == 2;
             k = {&k_fused_offdiag<SNS_FORM_NS, c, tt, vl, ev>, &k_fused_diag<SNS_FORM_NS, c, tt, vl, ev>,
                  &k_fused_lift<SNS_FORM_NS, c, tt, vl, ev>, &k_element<SNS_FORM_NS, c, tt, vl, ev>, &k_residual_tet<c, tt, vl, ev>,
-                 nu, 0.0, h->tt, h->vl};
+                 nu, 0.0, S.tt, S.vl};
         });
     });
     return k;
@@ -50,7 +51,7 @@ void launch_element_pass(sns_ctx* h, int form, const FormPass& K, policy::Elemen
     const unsigned g1 = (unsigned)((nc + 255) / 256), ge = (unsigned)((nc + EL_TETS_PER_BLOCK - 1) / EL_TETS_PER_BLOCK);
     if (kind == policy::ELEMENT_STAGED)
         hipLaunchKernelGGL(K.element, dim3(ge), dim3(256), 0, h->stream, nc, cells, h->pts, w, mask, h->bc_val, K.nu, store_K ? 1 : 0, Ke,
-                           Fe, h->fv, K.tt, K.vl);
+                           Fe, h->form.fv, K.tt, K.vl);
     else if (h->dim == 3)
         hipLaunchKernelGGL(K.residual_tet, dim3(g1), dim3(256), 0, h->stream, nc, cells, h->pts, w, K.nu, Fe, K.tt, K.vl);
     else if (form == SNS_FORM_NS)
@@ -80,18 +81,18 @@ int lift(sns_ctx* h, const FormPass& K, unsigned gd, const double* w, double* F)
     return SNS_OK;
 }
 
-// the fine operator was rewritten
-void matrix_changed(sns_ctx* h, int form) {
-    h->has_matrix = true;
-    h->transposed = h->pc_ready = false;
-    h->matrix_form = form;
-}
-
 policy::AssemblyFacts facts_of(const sns_ctx* h, int form, bool has_w, bool want_matrix, bool has_F) {
-    return {h->dim, form, has_w, want_matrix, has_F, h->opt.assembly_fused != 0, !h->fv.is_default(), h->E > 0};
+    return {h->dim, form, has_w, want_matrix, has_F, h->opt.assembly_fused != 0, !h->form.fv.is_default(), h->E > 0};
 }
 
 }  // namespace
+
+void matrix_changed(sns_ctx* h, int form, const double* scalar_par) {
+    h->has_matrix = true;
+    h->transposed = h->pc_ready = false;
+    h->matrix_form = form;
+    policy::stamp_operator(h->matrix_key, form, h->opt.reynolds, h->form.key(), scalar_par);
+}
 
 // The owner-lane passes are scratch-free: every BSR block (and every node residual) is computed by the lanes that own it.  The
 // staged route goes through the element scratch Ke / Fe and the gathers.  w == NULL with the Stokes form: the system of
@@ -191,7 +192,7 @@ int residual_moments(sns_ctx* h, int form, const double* w, const double* phi, d
             HIP_TRY(hipMemset(h->rm_nomask, 0, (size_t)ndof));
         }
         FormPass K = form_pass(h, form);
-        if (form == SNS_FORM_NS && h->ev_on) {           // the element kernels index the field by the cell of their pass
+        if (form == SNS_FORM_NS && h->form.ev_on) {           // the element kernels index the field by the cell of their pass
             SNS_TRY(support_nu(h, phi, nc));
             K.tt.nu_t = h->rm_nu;
         }

@@ -53,9 +53,34 @@ namespace sns {
 
 using namespace sns;
 
-// internal id of the scalar-transport operator in sns_ctx::matrix_form / est_form (beside SNS_FORM_STOKES, SNS_FORM_NS and the two
-// 2-D ids of csrc/sns_kernels.h); no public entry point takes it
+// internal id of the scalar-transport operator in sns_ctx::matrix_form and the operator keys (beside SNS_FORM_STOKES, SNS_FORM_NS
+// and the two 2-D ids of csrc/sns_kernels.h); no public entry point takes it
 #define SNS_FORM_SCALAR 4
+
+// The state of the 3-D NS form beside the options: what the setters of csrc/sns_form.hip write and form_pass
+// (csrc/sns_assemble.hip) hands to the kernels.  Which switches go together is policy::check_form_request's table.
+struct FormState {
+    FormVariant fv;                              // sns_set_form_variant (diagnostic; default = the reference's form)
+    // sns_set_time_term: the transient form.  tt.d points at tt_d, the handle's copy of the history (4*n doubles, allocated at
+    // the first set), or at tt_eff below; tt_on selects the TT instantiations of the NS assembly kernels
+    TimeTerm tt;
+    DevBuf<double> tt_d;
+    DevBuf<double> tt_w0;                        // sns_time_step: the state on entry
+    bool tt_on = false;
+    // sns_set_viscosity_law: the generalised-Newtonian form; vl_on selects the VL instantiations (never with tt_on)
+    ViscosityLaw vl;
+    bool vl_on = false;
+    // sns_set_body_force / sns_set_element_viscosity: the caller's f, the effective history tt_eff = d - f that tt.d points at
+    // while a force is on (d = tt_d under a time term, 0 without; rewritten whenever d or f changes; all zero for a viscosity
+    // field alone), and the per-cell nu_t behind tt.nu_t.  bf_on runs the TT instantiations, ev_on the EV ones (never with vl_on)
+    DevBuf<double> bf_f, tt_eff, ev_nu;
+    bool bf_on = false, ev_on = false;
+    uint64_t ev_generation = 0;                  // moves whenever ev_nu is written or a field is cleared: another operator
+    // the compile-time variant of the 3-D NS assembly kernels: 0 the reference's steady form, 1 TT (a time term or a body force,
+    // which rides in the effective history), 2 VL (a law; never with the others), 3 EV (a field; contains the time term)
+    int ns_variant() const { return ev_on ? 3 : (vl_on ? 2 : ((tt_on || bf_on) ? 1 : 0)); }
+    policy::FormKey key() const { return {tt.sigma, tt.theta, vl_on, vl.lambda, vl.n, vl.r, ev_generation}; }   // (of an operator assembled now)
+};
 
 struct sns_ctx {
     // Release order: ~sns_ctx waits for the device and destroys the graph exec and the streams; then the members go in reverse
@@ -106,22 +131,7 @@ struct sns_ctx {
     std::vector<DevBuf<double>> pong;                 // per level smoother ping-pong buffer
     DevBuf<int> d_piv;
     DevBuf<int> d_sing;
-    FormVariant fv;                              // sns_set_form_variant (diagnostic; default = the reference's form)
-    // sns_set_time_term: the transient 3-D NS form.  tt.d points at tt_d, the handle's copy of the history (4*n doubles,
-    // allocated at the first set), or at tt_eff below; tt_on selects the TT instantiations of the NS assembly kernels
-    TimeTerm tt;
-    DevBuf<double> tt_d;
-    DevBuf<double> tt_w0;                        // sns_time_step: the state on entry
-    bool tt_on = false;
-    // sns_set_viscosity_law: the generalised-Newtonian 3-D NS form; vl_on selects the VL instantiations (never with tt_on)
-    ViscosityLaw vl;
-    bool vl_on = false;
-    // sns_set_body_force / sns_set_element_viscosity (csrc/sns_fields.hip): the caller's f, the effective history tt_eff = d - f
-    // that tt.d points at while a force is on (d = tt_d under a time term, 0 without; rewritten whenever d or f changes; all zero
-    // for a viscosity field alone), and the per-cell nu_t behind tt.nu_t.  bf_on runs the TT instantiations, ev_on the EV ones
-    // (never with vl_on)
-    DevBuf<double> bf_f, tt_eff, ev_nu;
-    bool bf_on = false, ev_on = false;
+    FormState form;                              // the switches of the 3-D NS form and their buffers (csrc/sns_form.hip)
     DevBuf<double> rm_nu;                        // residual moments: nu_t of the compacted cells (capacity rm_cap)
     bool has_matrix = false, pc_ready = false;
     int pc_setups = 0;
@@ -135,11 +145,11 @@ struct sns_ctx {
     int matrix_form = -1;
     bool transposed = false;                     // vals holds A^T (sns_transpose_operator); every assembly clears it
     DevBuf<int32_t> tr_partner;                  // [nnzb] slot (i, j) -> slot (j, i), built at the first transpose (csrc/sns_transpose.hip)
-    int est_form = -1;                           // form of the matrix the levels' spectral estimates were last taken from
-    double est_re = 0.0;                         // ... and its Reynolds number
+    // which operator vals holds, and which one the levels' spectral estimates were last taken on (policy::OperatorKey): a set-up
+    // takes them again iff the two differ.  matrix_changed and transpose_operator write the first, pc_setup the second
+    policy::OperatorKey matrix_key, est_key;
     // sns_scalar_system (csrc/sns_scalar.hip): matrix_form = SNS_FORM_SCALAR while the scalar operator is the handle's matrix
     DevBuf<uint8_t> sc_mask;                     // the scalars' Dirichlet mask of the last scalar assembly (4*n, allocated at the first)
-    double sc_par[6] = {0, 0, 0, 0, 0, 0};       // ... and its kappa[4], sigma, theta (another set: the estimates are taken again)
     // reductions
     DevBuf<double> partial;                      // [max(65536*8, n/32)]
     DevBuf<double> partial2;                     // second stage of long reductions
@@ -238,7 +248,10 @@ int pc_setup(sns_ctx* h);
 // relies on the contents across a call into assemble / the estimates / the moments.
 enum VecSlot { VEC_KRYLOV = 0 /* .. 9, the Krylov methods */, VEC_ARNOLDI_IN = 12, VEC_SCRATCH = 13, VEC_SAVED_GUESS = 14 /* the retry */ };
 int get_vec(sns_ctx* h, size_t k, double** out);
-// csrc/sns_assemble.hip: the assembly driver over policy::plan_assembly, the residual moments on the same element pass
+// csrc/sns_assemble.hip: the assembly driver over policy::plan_assembly, the residual moments on the same element pass.
+// matrix_changed: the fine operator was rewritten by an assembly of `form` (scalar_par: a scalar assembly's kappa[4], sigma,
+// theta) -- the one place that says so: has_matrix, transposed, matrix_form, and matrix_key stamped from h->form and h->opt
+void matrix_changed(sns_ctx* h, int form, const double* scalar_par = nullptr);
 int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix);
 int timed_assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix);
 int residual_moments(sns_ctx* h, int form, const double* w, const double* phi, double out[4]);
@@ -264,8 +277,12 @@ int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, 
 // csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)
 int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sigma, double theta, const double* src,
                   const uint8_t* cmask, const double* cval, double* rhs);
-// csrc/sns_fields.hip: the external fields of the 3-D NS form (arguments checked by the entry points).  refresh_history points
-// tt.d at what the kernels read after d or f changed; support_nu gathers nu_t of the cells k_support_scatter keeps
+// csrc/sns_form.hip: the setters of the form state h->form and the query behind sns_element_viscosity (checked by the entry points).
+// refresh_history points tt.d at what the kernels read after d or f changed; support_nu gathers nu_t of the cells k_support_scatter keeps
+int set_form_variant(sns_ctx* h, double c_inverse, double lsic_scale, double pspg_sign, int one_point_quadrature);
+int set_time_term(sns_ctx* h, double sigma, double theta, const double* d);
+int set_viscosity_law(sns_ctx* h, bool carreau, double lambda, double n, double nu_inf_ratio);
+int element_viscosity(sns_ctx* h, const double* w, double* nu, double* gamma_dot);
 int refresh_history(sns_ctx* h);
 int set_body_force(sns_ctx* h, const double* f);
 int set_element_viscosity(sns_ctx* h, const double* nu);
@@ -296,6 +313,9 @@ inline int sync_stream(sns_ctx* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     return SNS_OK;
 }
+
+// the operator behind the preconditioner changed (a setter altered a value, the values were transposed): the next solve sets up
+inline void pc_stale(sns_ctx* h) { h->pc_ready = false; }
 
 
 inline void time_begin(sns_ctx* h, int mode, hipStream_t st = nullptr) {
@@ -485,11 +505,6 @@ inline void dispatch(int v, Fn&& fn) {
 
 template <class Fn>
 inline void with_fmt(int fmt, Fn&& fn) { dispatch<2, 1>(fmt, fn); }
-
-// the compile-time variant of the 3-D NS assembly kernels a handle runs: 0 the reference's steady form, 1 with a time term or
-// a body force (TT: the force rides in the effective history), 2 with a viscosity law (VL; never with the others), 3 with a
-// viscosity field (EV: contains the time term, so it serves the field with or without a time term or a force)
-inline int ns_variant(const sns_ctx* h) { return h->ev_on ? 3 : (h->vl_on ? 2 : ((h->tt_on || h->bf_on) ? 1 : 0)); }
 
 // a level's matrix copy in format F -- values and row scales (nullptr in fp32) -- and the same of M = A P (borrowed pointers)
 struct LpMat {

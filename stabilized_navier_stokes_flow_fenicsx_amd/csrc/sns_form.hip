@@ -1,5 +1,7 @@
-// External fields of the 3-D NS form (sns_set_body_force, sns_set_element_viscosity, sns_set_mixture; the reference has no
-// counterpart): a nodal P1 body force f and a per-cell viscosity nu_t, both in buffers the handle owns.
+// The setters of the form state h->form (FormState, csrc/sns_ctx.h): the form variant, the time term, the viscosity law and the
+// external fields (the reference has none): a nodal P1 body force f and a per-cell viscosity nu_t in buffers the handle owns.
+// What a handle's state refuses is asked by the entry points (policy::check_form_request); a setter that alters the operator
+// calls pc_stale, and the next assembly stamps the new values into the operator's key (matrix_changed).
 //   body force   no assembly code of its own: with u_t = sigma u + d the form takes a = u_t - f wherever it takes u_t, so the
 //                handle keeps the caller's d (tt_d), the caller's f (bf_f) and the effective history tt_eff = d - f, and the TT
 //                instantiations of the assembly kernels run on tt_eff (k_effective_history, whenever d or f changes; all
@@ -81,36 +83,100 @@ __global__ __launch_bounds__(256) void k_support_scatter_nu(int64_t n_cells, con
 
 }  // namespace
 
+int set_form_variant(sns_ctx* h, double c_inverse, double lsic_scale, double pspg_sign, int one_point_quadrature) {
+    FormVariant fv;
+    fv.ci = c_inverse;
+    fv.lsic = lsic_scale;
+    fv.pspg = pspg_sign;
+    if (one_point_quadrature) fv.qa = fv.qb = 0.25;
+    h->form.fv = fv;
+    h->has_matrix = h->transposed = false;                // (what was assembled is not the handle's form any more)
+    pc_stale(h);
+    return SNS_OK;
+}
+
+// sigma = theta = 0 without a history: back to the steady form
+int set_time_term(sns_ctx* h, double sigma, double theta, const double* d) {
+    FormState& S = h->form;
+    if (sigma != S.tt.sigma || theta != S.tt.theta) pc_stale(h);      // another operator
+    if (sigma == 0.0 && theta == 0.0 && !d) {             // (the buffer stays with the handle)
+        S.tt.sigma = S.tt.theta = 0.0;
+        S.tt_on = false;
+        return refresh_history(h);                        // (a body force stays: the history is -f again)
+    }
+    const size_t ld = (size_t)ld_of(h);
+    if (!S.tt_d) SNS_TRY(S.tt_d.alloc(ld));
+    if (d) HIP_TRY(hipMemcpyAsync(S.tt_d, d, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    else HIP_TRY(hipMemsetAsync(S.tt_d, 0, ld * sizeof(double), h->stream));
+    S.tt.sigma = sigma;
+    S.tt.theta = theta;
+    S.tt_on = true;
+    SNS_TRY(refresh_history(h));                          // tt.d = the handle's d, or d - f under a body force
+    return sync_stream(h);                                // the caller may free d
+}
+
+int set_viscosity_law(sns_ctx* h, bool carreau, double lambda, double n, double nu_inf_ratio) {
+    FormState& S = h->form;
+    ViscosityLaw vl;
+    if (carreau) { vl.lambda = lambda; vl.n = n; vl.r = nu_inf_ratio; }
+    if (carreau != S.vl_on || vl.lambda != S.vl.lambda || vl.n != S.vl.n || vl.r != S.vl.r) pc_stale(h);   // another operator
+    S.vl = vl;
+    S.vl_on = carreau;
+    return SNS_OK;
+}
+
+// nu_e and gamma_dot per cell at the state w (either may be null): the field where one is set, the law's value otherwise
+int element_viscosity(sns_ctx* h, const double* w, double* nu_dev, double* gamma_dot_dev) {
+    const FormState& S = h->form;
+    if (h->E > 0 && S.ev_on && nu_dev) {                  // (gamma_dot below as without a field)
+        HIP_TRY(hipMemcpyAsync(nu_dev, S.ev_nu, (size_t)h->E * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        nu_dev = nullptr;
+    }
+    if (h->E > 0 && (nu_dev || gamma_dot_dev)) {
+        const unsigned gt = (unsigned)((h->E + 255) / 256);
+        const double nu = 1.0 / h->opt.reynolds;
+        dispatch<1, 0>(S.vl_on, [&](auto V) {
+            hipLaunchKernelGGL((k_element_viscosity<V() != 0>), dim3(gt), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w, nu,
+                               S.vl, nu_dev, gamma_dot_dev);
+        });
+        HIP_TRY(hipGetLastError());
+    }
+    return sync_stream(h);
+}
+
 int refresh_history(sns_ctx* h) {
-    const double* d = h->tt_on ? h->tt_d.get() : nullptr;
-    const bool zero = h->ev_on && !h->bf_on && !d;        // the EV instantiations contain the time term: they read a history
-    if (!h->bf_on && !zero) {
-        h->tt.d = d;
+    FormState& S = h->form;
+    const double* d = S.tt_on ? S.tt_d.get() : nullptr;
+    const bool zero = S.ev_on && !S.bf_on && !d;        // the EV instantiations contain the time term: they read a history
+    if (!S.bf_on && !zero) {
+        S.tt.d = d;
         return SNS_OK;
     }
     const int64_t ld = ld_of(h);
-    if (!h->tt_eff) SNS_TRY(h->tt_eff.alloc((size_t)ld));
-    if (zero) HIP_TRY(hipMemsetAsync(h->tt_eff, 0, (size_t)ld * sizeof(double), h->stream));
-    else hipLaunchKernelGGL(k_effective_history, dim3(vec_grid(ld)), dim3(256), 0, h->stream, ld, d, h->bf_f, h->tt_eff);
+    if (!S.tt_eff) SNS_TRY(S.tt_eff.alloc((size_t)ld));
+    if (zero) HIP_TRY(hipMemsetAsync(S.tt_eff, 0, (size_t)ld * sizeof(double), h->stream));
+    else hipLaunchKernelGGL(k_effective_history, dim3(vec_grid(ld)), dim3(256), 0, h->stream, ld, d, S.bf_f, S.tt_eff);
     HIP_TRY(hipGetLastError());
-    h->tt.d = h->tt_eff;
+    S.tt.d = S.tt_eff;
     return SNS_OK;
 }
 
 int set_body_force(sns_ctx* h, const double* f) {
+    FormState& S = h->form;
     if (!f) {
-        h->bf_on = false;
+        S.bf_on = false;
         return refresh_history(h);
     }
     const size_t ld = (size_t)ld_of(h);
-    if (!h->bf_f) SNS_TRY(h->bf_f.alloc(ld));
-    HIP_TRY(hipMemcpyAsync(h->bf_f, f, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    h->bf_on = true;
+    if (!S.bf_f) SNS_TRY(S.bf_f.alloc(ld));
+    HIP_TRY(hipMemcpyAsync(S.bf_f, f, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    S.bf_on = true;
     SNS_TRY(refresh_history(h));
     return sync_stream(h);                                // the caller may free f
 }
 
 int set_element_viscosity(sns_ctx* h, const double* nu) {
+    FormState& S = h->form;
     if (nu) {
         const int gv = std::max(1, vec_grid(h->E));
         hipLaunchKernelGGL(k_count_bad_viscosity, dim3(gv), dim3(256), 0, h->stream, h->E, nu, h->partial);
@@ -118,16 +184,16 @@ int set_element_viscosity(sns_ctx* h, const double* nu) {
         double nbad = 1.0;
         SNS_TRY(fetch(h, h->d_scal + 61, 1, &nbad));
         if (nbad != 0.0) { set_error("sns_set_element_viscosity: every entry must be finite and > 0"); return SNS_E_ARG; }
-        if (!h->ev_nu) SNS_TRY(h->ev_nu.alloc((size_t)h->E));
-        HIP_TRY(hipMemcpyAsync(h->ev_nu, nu, (size_t)h->E * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        if (!S.ev_nu) SNS_TRY(S.ev_nu.alloc((size_t)h->E));
+        HIP_TRY(hipMemcpyAsync(S.ev_nu, nu, (size_t)h->E * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         SNS_TRY(sync_stream(h));                          // the caller may free nu
     }
-    if (nu || h->ev_on) {                                 // another operator: re-estimate the smoother's damping caps
-        h->est_form = -1;
-        h->pc_ready = false;
+    if (nu || S.ev_on) {                                  // another operator: the key of the next assembly differs
+        ++S.ev_generation;
+        pc_stale(h);
     }
-    h->ev_on = nu != nullptr;
-    h->tt.nu_t = h->ev_on ? h->ev_nu.get() : nullptr;
+    S.ev_on = nu != nullptr;
+    S.tt.nu_t = S.ev_on ? S.ev_nu.get() : nullptr;
     return refresh_history(h);
 }
 
@@ -154,7 +220,7 @@ int support_nu(sns_ctx* h, const double* phi, int64_t nc) {
     if (!h->rm_nu || (int64_t)h->rm_nu.count() < nc) SNS_TRY(h->rm_nu.alloc((size_t)std::max<int64_t>(nc, h->rm_cap)));
     const int64_t nb = (h->E + 255) / 256;
     hipLaunchKernelGGL(k_support_scatter_nu, dim3((unsigned)nb), dim3(256), 0, h->stream, h->E, h->tets, h->n_owned, phi, h->rm_off,
-                       h->ev_nu, h->rm_nu);
+                       h->form.ev_nu, h->rm_nu);
     return SNS_OK;
 }
 

@@ -4,7 +4,8 @@
 // hipGraph.  Pure host code over (options, a few global counts): no HIP, no handle, so that the table can be unit-tested on the
 // CPU (sns_host_cycle_policy, tests/test_host.py) and every rank of a partitioned run answers alike by construction.
 // The handle-side predicates of csrc/sns_cycle.hip / sns_setup.hip gather the facts and ask here; the numbers live nowhere else.
-// In the same idiom, at the end: the route of an assembly (plan_assembly, tests/assembly_plan_main.cpp).
+// In the same idiom, at the end: the route of an assembly (plan_assembly, tests/assembly_plan_main.cpp), what a handle's form
+// state allows (check_form_request, tests/form_request_main.cpp), which operator is a new one (OperatorKey, tests/operator_key_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -336,6 +337,112 @@ inline AssemblyPlan plan_assembly(const AssemblyFacts& f, bool violated = true) 
     p.gather_matrix = f.want_matrix;
     p.gather_residual = f.has_F;
     return p;
+}
+
+// ---- what a handle's form state allows (csrc/sns_form.hip; the matrix is in DESIGN.md) ---------------------------------------------
+// Facts: the handle (dim, a communicator attached) and the switches of the 3-D NS form that are on -- time term, viscosity law,
+// body force, viscosity field.
+struct FormFacts {
+    int dim = 3;
+    bool partitioned = false, tt_on = false, vl_on = false, bf_on = false, ev_on = false;
+};
+enum FormRequest {
+    REQ_SET_TIME_TERM = 0, REQ_CLEAR_TIME_TERM, REQ_SET_CARREAU, REQ_SET_NEWTONIAN, REQ_SET_FIELD /* set or clear: force, viscosity, mixture */,
+    REQ_TIME_STEP, REQ_SHAPE_GRADIENT, REQ_RECOVER_GRADIENT, REQ_ERROR_INDICATOR, REQ_SCALAR /* system or solve */,
+    REQ_ELEMENT_VISCOSITY /* the query */, REQ_FORM_VARIANT, REQ_COUNT
+};
+// error != SNS_OK: refused; the entry point's message is its name, ": " and `tail`
+struct FormVerdict {
+    int error = SNS_OK;
+    const char* tail = "";
+};
+enum FormFactBit { IS_NOT_3D = 1, IS_PARTITIONED = 2, HAS_TIME_TERM = 4, HAS_LAW = 8, HAS_FORCE = 16, HAS_FIELD = 32 };
+// A request is refused by its first row with one of `any_of` true.  Asymmetries kept as they grew: a Newtonian law
+// is refused under a time term though it sets nothing, and allowed under a force or a field; CLEARING a field is refused
+// while a law is set; the shape gradient and the two recovery requests never ask for the dimension.
+struct FormRule {
+    FormRequest request;
+    unsigned any_of;
+    int error;
+    const char* tail;
+};
+constexpr FormRule FORM_RULES[] = {
+    {REQ_SET_TIME_TERM, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {REQ_SET_TIME_TERM, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
+    {REQ_SET_TIME_TERM, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the transient form has no law)"},
+    {REQ_CLEAR_TIME_TERM, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {REQ_CLEAR_TIME_TERM, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
+    {REQ_SET_CARREAU, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {REQ_SET_CARREAU, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no law)"},
+    {REQ_SET_CARREAU, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the transient form has no law)"},
+    {REQ_SET_CARREAU, HAS_FORCE | HAS_FIELD, SNS_E_STATE, "not with a body force or a viscosity field set"},
+    {REQ_SET_NEWTONIAN, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {REQ_SET_NEWTONIAN, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no law)"},
+    {REQ_SET_NEWTONIAN, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the transient form has no law)"},
+    {REQ_SET_FIELD, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {REQ_SET_FIELD, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no external fields)"},
+    {REQ_SET_FIELD, HAS_LAW, SNS_E_STATE, "not with a viscosity law set"},
+    {REQ_TIME_STEP, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {REQ_TIME_STEP, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
+    {REQ_TIME_STEP, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the transient form has no law)"},
+    {REQ_SHAPE_GRADIENT, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned shape gradients are not built)"},
+    {REQ_SHAPE_GRADIENT, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the mesh derivative of nu_e is not built)"},
+    {REQ_SHAPE_GRADIENT, HAS_FORCE | HAS_FIELD, SNS_E_STATE,
+     "not with a body force or a viscosity field set (the mesh derivative is not built with them)"},
+    {REQ_RECOVER_GRADIENT, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned gradient recovery is not built)"},
+    {REQ_ERROR_INDICATOR, IS_PARTITIONED, SNS_E_STATE,
+     "not with a communicator attached (a partitioned indicator needs a halo exchange of G)"},
+    {REQ_SCALAR, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {REQ_SCALAR, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned scalar transport is not built)"},
+    {REQ_ELEMENT_VISCOSITY, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {REQ_FORM_VARIANT, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+};
+
+inline FormVerdict check_form_request(FormRequest request, const FormFacts& f) {
+    const unsigned facts = (f.dim != 3) * IS_NOT_3D | f.partitioned * IS_PARTITIONED | f.tt_on * HAS_TIME_TERM | f.vl_on * HAS_LAW |
+                           f.bf_on * HAS_FORCE | f.ev_on * HAS_FIELD;
+    for (const FormRule& r : FORM_RULES)
+        if (r.request == request && (facts & r.any_of)) return {r.error, r.tail};
+    return {};
+}
+
+// ---- which operator is it? (the spectral estimates of csrc/sns_setup.hip; the cases are in DESIGN.md) -----------------------------
+// What the fine operator's values depend on beside the state: the form's share (FormKey: time term, viscosity law, and a counter
+// that moves whenever the viscosity field is written or cleared) and the call's (the form id, the Reynolds number, the six
+// parameters of a scalar assembly, whether the values were transposed since).  The handle keeps the key of the operator in
+// levels[0].vals and the key of the operator the levels' estimates were taken on; a set-up takes them again iff the two differ.
+struct FormKey {
+    double sigma = 0.0, theta = 0.0;
+    bool law_on = false;
+    double lambda = 0.0, n = 1.0, r = 0.0;
+    uint64_t nu_generation = 0;
+    bool operator==(const FormKey& o) const {
+        return sigma == o.sigma && theta == o.theta && law_on == o.law_on && lambda == o.lambda && n == o.n && r == o.r &&
+               nu_generation == o.nu_generation;
+    }
+};
+struct OperatorKey {
+    int form = -1;                                          // (no operator: equal to no assembled one)
+    double reynolds = 0.0;
+    bool transposed = false;
+    FormKey f;
+    double scalar[6] = {0, 0, 0, 0, 0, 0};                  // kappa[4], sigma, theta of the last scalar assembly (kept by the flow assemblies)
+    bool operator==(const OperatorKey& o) const {
+        return form == o.form && reynolds == o.reynolds && transposed == o.transposed && f == o.f &&
+               std::equal(scalar, scalar + 6, o.scalar);
+    }
+};
+// an assembly of `form` rewrote the operator (scalar_par: the parameters of a scalar assembly, null for a flow assembly)
+inline void stamp_operator(OperatorKey& k, int form, double reynolds, const FormKey& f, const double* scalar_par = nullptr) {
+    k.form = form;
+    k.reynolds = reynolds;
+    k.transposed = false;
+    k.f = f;
+    if (scalar_par) std::copy(scalar_par, scalar_par + 6, k.scalar);
+}
+// (r3_estimates: SNS_R3_SPECTRAL_ESTIMATE, the every-fourth-set-up cadence alone)
+inline bool new_operator(const OperatorKey& matrix, const OperatorKey& estimated, bool r3_estimates) {
+    return !r3_estimates && !(matrix == estimated);
 }
 
 }  // namespace policy

@@ -201,13 +201,8 @@ int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sig
                        h->pts, w, P, src, cmask, cval, L.vals, rhs);
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     const hipError_t e = hipGetLastError();
-    // the fine operator was rewritten: the same contract as any assembly
-    h->has_matrix = true;
-    h->transposed = h->pc_ready = false;
-    h->matrix_form = SNS_FORM_SCALAR;
     const double par[6] = {kappa[0], kappa[1], kappa[2], kappa[3], sigma, theta};
-    if (std::memcmp(par, h->sc_par, sizeof(par)) != 0) h->est_form = -1;      // another operator: re-estimate the damping caps
-    std::memcpy(h->sc_par, par, sizeof(par));
+    matrix_changed(h, SNS_FORM_SCALAR, par);               // (another set of parameters is another operator)
     const int rc = sync_stream(h);                         // (the caller may free its arrays)
     HIP_TRY(e);
     SNS_TRY(rc);

@@ -850,7 +850,7 @@ int pc_setup(sns_ctx* h) {
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     const int nl = (h->opt.pc_type == SNS_PC_AMG) ? (int)h->levels.size() : 1;
     bool any_block = false;
-    const bool new_operator = !h->r3_estimates && (h->matrix_form != h->est_form || h->opt.reynolds != h->est_re);
+    const bool new_operator = policy::new_operator(h->matrix_key, h->est_key, h->r3_estimates);
     for (int l = 0; l < nl; ++l) {
         Level& L = h->levels[l];
         const int32_t rows = L.n_owned;
@@ -1028,8 +1028,7 @@ int pc_setup(sns_ctx* h) {
         return SNS_E_STATE;
     }
     ++h->pc_setups;
-    h->est_form = h->matrix_form;
-    h->est_re = h->opt.reynolds;
+    h->est_key = h->matrix_key;
     const bool check_sing = nl > 1 && (h->levels[nl - 1].dense_gj != nullptr || any_block);
     int* h_sing = reinterpret_cast<int*>(h->h_scal + 768);
     *h_sing = 0;

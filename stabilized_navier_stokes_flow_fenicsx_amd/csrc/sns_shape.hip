@@ -427,9 +427,9 @@ int residual_shape_gradient(sns_ctx* h, const double* w, const double* lam, doub
         hipLaunchKernelGGL(k_shape_tri, dim3(gc), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w, lam, nu, h->Fe);
     else
         dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-            dispatch<1, 0>(h->tt_on, [&](auto T) {
+            dispatch<1, 0>(h->form.tt_on, [&](auto T) {
                 hipLaunchKernelGGL((k_shape_tet<C() != 0, T() != 0>), dim3(gc), dim3(256), 0, h->stream, h->E, h->tets, h->pts, w,
-                                   lam, nu, h->Fe, h->fv, h->tt);
+                                   lam, nu, h->Fe, h->form.fv, h->form.tt);
             });
         });
     const int64_t nth = 4 * (int64_t)h->n;

@@ -92,8 +92,8 @@ int transpose_operator(sns_ctx* h) {
     hipLaunchKernelGGL(k_transpose_inplace, dim3((unsigned)((L.nnzb * 16 + 255) / 256)), dim3(256), 0, h->stream, L.nnzb,
                        h->tr_partner, L.vals);
     h->transposed = !h->transposed;
-    h->pc_ready = false;
-    h->est_form = -1;                                    // the damping caps were taken on the other operator: re-estimate
+    h->matrix_key.transposed = h->transposed;            // (the damping caps were taken on the other operator)
+    pc_stale(h);
     HIP_TRY(hipGetLastError());
     return sync_stream(h);
 }

@@ -1031,3 +1031,195 @@ def test_assembly_plan_table(tmp_path):
     # the fast residual path exists, and only for a state that satisfies its data on the reference's form
     fast = [c for c, r in zip(reachable, rows) if not r["error"] and r["route"] == STAGED and r["element"] == RESIDUAL]
     assert fast and all(c[0] == 3 and c[1] == NS and not c[3] and c[4] and not c[6] and c[7] and not c[8] for c in fast)
+
+
+def _policy_main(tmp_path, name):
+    """A stand-alone main over csrc/sns_policy.h (tests/<name>_main.cpp), built like the assembly plan's."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / name)
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
+                            "-I", os.path.join(ROOT, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
+                            os.path.join(ROOT, "tests", name + "_main.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    return exe
+
+
+def test_form_request_table(tmp_path):
+    """What a handle's form state refuses (csrc/sns_policy.h: policy::check_form_request, asked by the entry points of
+    csrc/sns_api.hip) for every request and all 2 x 2 x 2^4 combinations of its facts, against a transcription of the rules as
+    the entry points had them inline before the table -- in their order, with their texts -- written here and not derived from
+    the header."""
+    import itertools
+    import subprocess
+    exe = _policy_main(tmp_path, "form_request")
+    E_ARG, E_STATE = -1, -3                                                 # include/sns.h
+    (SET_TT, CLEAR_TT, SET_CARREAU, SET_NEWTONIAN, SET_FIELD, TIME_STEP, SHAPE, RECOVER, INDICATOR, SCALAR, ELEMENT_VISCOSITY,
+     VARIANT) = REQUESTS = range(12)                                        # policy::FormRequest
+    DIM = "3-D handles only"
+    COMM = "not with a communicator attached"
+
+    def expected(req, dim, part, tt, vl, bf, ev):
+        """(code, tail) of the first check that fails, in the order the entry point made them."""
+        checks = []
+        if req in (SET_TT, CLEAR_TT):                                      # sns_set_time_term
+            checks = [(dim != 3, E_ARG, DIM), (part, E_STATE, COMM + " (partitioned time stepping is not built)")]
+            if req == SET_TT:                                              # (clearing is allowed under a law)
+                checks.append((vl, E_STATE, "not with a viscosity law set (the transient form has no law)"))
+        elif req in (SET_CARREAU, SET_NEWTONIAN):                          # sns_set_viscosity_law
+            # a Newtonian "set" is refused under a time term as well, though it sets nothing ...
+            checks = [(dim != 3, E_ARG, DIM), (part, E_STATE, COMM + " (partitioned handles have no law)"),
+                      (tt, E_STATE, "not with a time term set (the transient form has no law)")]
+            if req == SET_CARREAU:                                         # ... but is allowed under a force or a field
+                checks.append((bf or ev, E_STATE, "not with a body force or a viscosity field set"))
+        elif req == SET_FIELD:                                             # the three field setters; clearing is refused under a law too
+            checks = [(dim != 3, E_ARG, DIM), (part, E_STATE, COMM + " (partitioned handles have no external fields)"),
+                      (vl, E_STATE, "not with a viscosity law set")]
+        elif req == TIME_STEP:
+            checks = [(dim != 3, E_ARG, DIM), (part, E_STATE, COMM + " (partitioned time stepping is not built)"),
+                      (vl, E_STATE, "not with a viscosity law set (the transient form has no law)")]
+        elif req == SHAPE:                                                 # (never asked for the dimension)
+            checks = [(part, E_STATE, COMM + " (partitioned shape gradients are not built)"),
+                      (vl, E_STATE, "not with a viscosity law set (the mesh derivative of nu_e is not built)"),
+                      (bf or ev, E_STATE, "not with a body force or a viscosity field set (the mesh derivative is not built with them)")]
+        elif req == RECOVER:
+            checks = [(part, E_STATE, COMM + " (partitioned gradient recovery is not built)")]
+        elif req == INDICATOR:
+            checks = [(part, E_STATE, COMM + " (a partitioned indicator needs a halo exchange of G)")]
+        elif req == SCALAR:
+            checks = [(dim != 3, E_ARG, DIM), (part, E_STATE, COMM + " (partitioned scalar transport is not built)")]
+        elif req in (ELEMENT_VISCOSITY, VARIANT):
+            checks = [(dim != 3, E_ARG, DIM)]
+        return next(((code, tail) for cond, code, tail in checks if cond), (0, ""))
+
+    combos = list(itertools.product(REQUESTS, (2, 3), *[(0, 1)] * 5))
+    assert len(combos) == 12 * 64
+    run = subprocess.run([exe], input="".join(" ".join(map(str, c)) + "\n" for c in combos), capture_output=True, text=True)
+    assert run.returncode == 0, run.returncode
+    lines = run.stdout.split("\n")
+    assert int(lines[0]) == len(REQUESTS)                                  # policy::REQ_COUNT: no request the matrix leaves out
+    got = [(int(code), tail) for code, tail in (ln.split("\t") for ln in lines[1:1 + len(combos)])]
+    for c, g in zip(combos, got):
+        assert g == expected(*c), (c, g)
+    # the texts the GPU tests look for (tests/test_gpu_*.py), byte for byte
+    tails = {t for _, t in got}
+    for text in ("3-D handles only", "viscosity law", "not with a communicator attached", "not with a time term set",
+                 "not with a body force or a viscosity field set"):
+        assert any(text in t for t in tails), text
+    assert "3-D handles only" in tails and "not with a body force or a viscosity field set" in tails
+
+
+def test_operator_key_sequences(tmp_path):
+    """Which set-ups take the levels' spectral estimates again: the operator keys (csrc/sns_policy.h: OperatorKey, replayed by
+    tests/operator_key_main.cpp) against a model of the flags the keys replaced -- est_form / est_re / sc_par, transcribed from
+    their writers as they were (sns_set_time_term, sns_set_viscosity_law, set_element_viscosity, transpose_operator,
+    scalar_system, pc_setup).  On regular sequences ("Operator keys") the decisions are identical; on the irregular
+    ones named there the keys decide as written there.  The every-fourth-set-up cadence is outside both."""
+    import subprocess
+    exe = _policy_main(tmp_path, "operator_key")
+    SIGMA, THETA, RE = (0.0, 10.0), (0.0, 400.0), (10.0, 50.0)
+    LAW = ("0 0 1 0", "1 2 0.5 0.05", "1 1 0.7 0")                           # off (the Newtonian defaults), two Carreau sets
+    SCALAR = ("1 0.1 0.01 1 0 0", "1 0.1 0.01 1 3 40")
+
+    def flags(seq):
+        """The flags' decisions, one per set-up."""
+        num = lambda k: tuple(float(ev.pop(0)) for _ in range(k))
+        est_form, est_re, sc_par, matrix_form = -1, 0.0, (0.0,) * 6, -1
+        sigma, theta, law, field, re = 0.0, 0.0, (0.0, 0.0, 1.0, 0.0), False, 1.0
+        out = ""
+        ev = seq.split()
+        while ev:
+            e = ev.pop(0)
+            if e in ("sigma", "theta"):                                    # sns_set_time_term: either value altered
+                v, = num(1)
+                if v != (sigma if e == "sigma" else theta):
+                    est_form = -1
+                sigma, theta = (v, theta) if e == "sigma" else (sigma, v)
+            elif e == "law":                                               # sns_set_viscosity_law: on / off or a parameter altered
+                v = num(4)
+                if v != law:
+                    est_form = -1
+                law = v
+            elif e == "field":                                             # set_element_viscosity: every set, and a clear of a set one
+                v = ev.pop(0) == "1"
+                if v or field:
+                    est_form = -1
+                field = v
+            elif e == "re":                                                # (an option: nothing written)
+                re, = num(1)
+            elif e == "transpose":
+                est_form = -1
+            elif e == "assemble":
+                matrix_form = int(ev.pop(0))
+            elif e == "scalar":
+                v = num(6)
+                matrix_form = 4
+                if v != sc_par:
+                    est_form = -1
+                sc_par = v
+            elif e == "setup":
+                out += "1" if (matrix_form != est_form or re != est_re) else "0"
+                est_form, est_re = matrix_form, re
+        return out
+
+    def keys(seqs):
+        run = subprocess.run([exe], input="".join(s + "\n" for s in seqs), capture_output=True, text=True)
+        assert run.returncode == 0, (run.returncode, run.stderr[-500:])
+        got = run.stdout.split("\n")[:len(seqs)]
+        assert len(got) == len(seqs)
+        return got
+
+    # regular sequences: rounds of one change (or none), the assembly that takes it up, a set-up.  A transpose comes as
+    # sns_adjoint_solve makes it: transpose, set-up, transpose back, and only then perhaps an assembly.
+    rng = np.random.default_rng(2024)
+    pick = lambda a: a[int(rng.integers(len(a)))]
+
+    def regular():
+        s = ["assemble %d" % rng.integers(2), "setup"]
+        for _ in range(int(rng.integers(4, 14))):
+            kind = int(rng.integers(9))
+            asm = "assemble %d" % rng.integers(2)
+            if kind == 0:
+                s += ["sigma %r" % pick(SIGMA), asm, "setup"]
+            elif kind == 1:
+                s += ["theta %r" % pick(THETA), asm, "setup"]
+            elif kind == 2:
+                s += ["law " + pick(LAW), asm, "setup"]
+            elif kind == 3:
+                s += ["field %d" % rng.integers(2), asm, "setup"]
+            elif kind == 4:
+                s += ["re %r" % pick(RE), asm, "setup"]
+            elif kind == 5:
+                s += ["scalar " + pick(SCALAR), "setup"]
+            elif kind == 6:
+                s += ["transpose", "setup", "transpose"] + ([asm] if rng.integers(2) else []) + ["setup"]
+            elif kind == 7:
+                s += [asm, "setup"]
+            else:
+                s += ["setup"]
+        return " ".join(s)
+
+    seqs = [regular() for _ in range(2500)]
+    got = keys(seqs)
+    want = [flags(s) for s in seqs]
+    assert got == want, next((s, g, w) for s, g, w in zip(seqs, got, want) if g != w)
+    assert sum(g.count("1") for g in got) > 5000 and sum(g.count("0") for g in got) > 2000     # both answers are exercised
+    # the irregular sequences of DESIGN.md, after "assemble 1 setup" (always 1): (events, the keys' decisions, the flags')
+    irregular = [
+        # a change, a set-up on the matrix assembled BEFORE it, then the assembly and its set-up: the estimates are taken on the
+        # new operator (the flags took them on the old matrix and kept them for the new one)
+        ("sigma 10.0 setup assemble 1 setup", "01", "10"),
+        ("re 50.0 setup assemble 1 setup", "01", "10"),
+        # A -> B -> A without a set-up in between: the operator is the one the estimates were taken on
+        ("sigma 10.0 sigma 0.0 assemble 1 setup", "0", "1"),
+        ("transpose transpose setup", "0", "1"),
+        ("transpose assemble 1 setup", "0", "1"),
+        # estimates taken on A^T, then an assembly: A again (the flags kept the estimates of A^T)
+        ("transpose setup assemble 1 setup", "11", "10"),
+    ]
+    got = keys(["assemble 1 setup " + s for s, _, _ in irregular])
+    for (s, want_keys, want_flags), g in zip(irregular, got):
+        assert g == "1" + want_keys, (s, g)
+        assert flags("assemble 1 setup " + s) == "1" + want_flags, s
