@@ -607,6 +607,49 @@ SNS_API int sns_set_body_force(sns_handle h, const double* f_dev);
 SNS_API int sns_set_element_viscosity(sns_handle h, const double* nu_dev);
 SNS_API int sns_set_mixture(sns_handle h, const double* m_dev, double log_viscosity_ratio, const double buoyancy[3]);
 
+/* Boundary terms (the reference has no counterpart: every form of it is a volume integral, every outlet do-nothing): facet
+ * integrals over a list of boundary facets the handle keeps (csrc/sns_boundary.hip).  A facet k has three nodes, area |Gamma_k|
+ * and the outward unit normal n_k -- outward = away from the fourth vertex of the tet that owns it.
+ *   sns_set_boundary_facets  facets_host: 3*n_facets node ids (any winding), facet_tets_host: the owning tet of each (host
+ *                            arrays, read before the call returns).  Builds the lists of the pass -- the facets rewound
+ *                            outward, the boundary rows, per row its (facet, vertex) entries (sns_host_facet_lists) -- and finds
+ *                            the BSR slot of every (facet, a, b) once, on the device.  Replaces an earlier list and CLEARS the
+ *                            data of the two setters below (they are per facet); n_facets = 0 clears facets and data.
+ *   sns_set_boundary_flow    the 3-D NS form gains
+ *                                R(w; v) += - int_Gamma t.v ds - int_Gamma beta_k (u.n)_- u.v ds,   (u.n)_- = min(u.n, 0).
+ *                            t_dev: 9*n_facets doubles [facet][vertex][component] in the vertex order of facets_host, P1 on each
+ *                            facet (it may jump between facets), integrated exactly by the facet mass matrix |Gamma|/12 (1 +
+ *                            delta_ab).  Under the reference's viscous term nu (grad u, grad v) t is the PSEUDO-traction
+ *                            nu d_n u - p n; under the stress-divergence form (a Carreau law or a viscosity field) it is the TRUE
+ *                            traction 2 nu eps(u) n - p n.  A pressure boundary is t = -p0 n.  beta_dev: n_facets doubles, each
+ *                            finite and >= 0, 0 switches the backflow term off on that facet; the term is taken with the 6-point
+ *                            degree-4 rule with positive weights (a1 = 0.445948490915965, w1 = 0.223381589678011, a2 =
+ *                            0.091576213509771, w2 = 0.109951743655322).  The Jacobian gains the exact derivative of the branch
+ *                            each quadrature point takes, -beta [(u.n)_- du.v + H(-u.n)(du.n) u.v], in the 3 x 3 velocity part
+ *                            of the facet's blocks; t and beta are held fixed.  The pressure rows get nothing.  NULL clears a term.
+ *   sns_set_boundary_scalar  the form of sns_scalar_system gains R_k(c; v) += int_Gamma (alpha_k c_k - g_k) v ds, i.e.
+ *                            kappa d_n c = alpha (c_ext - c) + q with g = alpha c_ext + q.  alpha_dev: 4*n_facets doubles
+ *                            [facet][species], each finite and >= 0; g_dev: 12*n_facets doubles [facet][vertex][species], P1 per
+ *                            facet.  Both by the facet mass matrix: alpha M_Gamma on the diagonal entries of the facet's blocks
+ *                            (the operator stays block diagonal over the species), int g v into rhs_dev.  NULL clears a term.
+ * The data is copied into buffers the handle owns; the calls return after the copy.  The terms are part of the raw form: rows of
+ * constrained dofs get nothing, columns of constrained dofs are not stored and their product with the Dirichlet defect goes into
+ * the lifting (F += J0[:,B](g - w_B), b -= A0[:,B] g).  From the call on every NS assembly -- sns_residual, sns_jacobian,
+ * sns_newton_solve, sns_time_step, sns_adjoint_solve's operator, sns_bench_assemble, fused or staged -- ends with one
+ * owner-computes pass over the boundary rows (4 lanes per row, no atomics, no scratch, bitwise reproducible), and
+ * sns_residual_moments adds phi . (the boundary residual without the Dirichlet rule).  The Stokes forms ignore both flow terms,
+ * as they ignore the time term and the body force.  With nothing set nothing is launched or allocated; clearing gives back the
+ * handle as it was, bit for bit.  Another beta or alpha -- set, cleared, or any entry changed -- is another operator: the next
+ * preconditioner set-up takes its spectral estimates again; t and g (and the same beta or alpha written again) change none.
+ * SNS_E_ARG: a null handle; a 2-D handle; a negative count or a null list; a beta or alpha that is negative or not finite
+ * (checked on the device: one reduction launch, one host read).  SNS_E_STATE: a communicator attached; flow or scalar data before
+ * facets are set.  SNS_E_MESH: a facet whose nodes are not three of the four nodes of its tet, a facet listed twice, a facet
+ * without area.  sns_residual_shape_gradient is refused (SNS_E_STATE) while t or beta is set: the mesh derivative of the facet
+ * terms is not built.  After a refusal the handle is untouched.                                                              */
+SNS_API int sns_set_boundary_facets(sns_handle h, int32_t n_facets, const int32_t* facets_host, const int64_t* facet_tets_host);
+SNS_API int sns_set_boundary_flow(sns_handle h, const double* t_dev /* 9*nf or NULL */, const double* beta_dev /* nf or NULL */);
+SNS_API int sns_set_boundary_scalar(sns_handle h, const double* alpha_dev /* 4*nf or NULL */, const double* g_dev /* 12*nf or NULL */);
+
 /* ---- introspection (tests, profiling) --------------------------------------*/
 /* device pointers of the assembled BSR4 operator (block row-major 4x4); the values are those of A^T while the handle
  * is transposed (sns_transpose_operator), like SNS_EXPORT_VALS below                                                */
@@ -727,6 +770,17 @@ SNS_API int sns_host_pattern(int32_t n_nodes, int64_t n_tets, const int32_t* tet
                      int64_t* nnzb_out,
                      int32_t* rowptr_out /*n_nodes+1*/, int32_t* colind_out /*nnzb*/,
                      int64_t* c_ptr_out /*nnzb+1*/, int32_t* c_idx_out /*16*n_tets*/);
+/* The lists of the boundary pass (sns_set_boundary_facets builds the same): from n_facets boundary facets (3 node ids each, any
+ * winding) and the tet that owns each, facets_out = the facets rewound so that (x1 - x0) x (x2 - x0) points away from the
+ * owner's fourth vertex (vertex 0 stays, vertices 1 and 2 change places where needed); rows_out = the boundary rows, i.e. the
+ * nodes of listed facets, ascending (at most min(n_nodes, 3*n_facets); their number in n_rows_out); row_ptr_out / row_fv_out =
+ * per boundary row its entries facet * 4 + local vertex (of the rewound facet) in ascending facet order.  Outputs may be NULL.
+ * SNS_E_MESH, with nothing written: a facet's nodes are not three of the four nodes of its tet, a facet is listed twice, a facet
+ * is degenerate (zero area).                                                                                                  */
+SNS_API int sns_host_facet_lists(int32_t n_nodes, int64_t n_tets, const int32_t* tets_host, const double* pts_host /*3*n_nodes*/,
+                     int32_t n_facets, const int32_t* facets_host /*3*n_facets*/, const int64_t* facet_tets_host /*n_facets*/,
+                     int32_t* facets_out /*3*n_facets*/, int32_t* n_rows_out, int32_t* rows_out, int32_t* row_ptr_out /*rows+1*/,
+                     int32_t* row_fv_out /*3*n_facets*/);
 /* size-limited greedy aggregation of the first n_active nodes of a pattern;
  * agg_out[n_nodes] gets the aggregate id (-1 for inactive nodes).             */
 SNS_API int sns_host_aggregate(int32_t n_nodes, const int32_t* rowptr, const int32_t* colind,

@@ -126,6 +126,9 @@ _SIGNATURES = [
     ("sns_set_body_force", C.c_int, [_H, _P]),
     ("sns_set_element_viscosity", C.c_int, [_H, _P]),
     ("sns_set_mixture", C.c_int, [_H, _P, C.c_double, C.POINTER(C.c_double)]),
+    ("sns_set_boundary_facets", C.c_int, [_H, C.c_int32, _P, _P]),
+    ("sns_set_boundary_flow", C.c_int, [_H, _P, _P]),
+    ("sns_set_boundary_scalar", C.c_int, [_H, _P, _P]),
     ("sns_newton_solve", C.c_int, [_H, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_double), C.c_int]),
     ("sns_get_bsr", C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P),
@@ -149,6 +152,7 @@ _SIGNATURES = [
     ("sns_locate_points", C.c_int, [C.c_int32, C.c_int64, _P, _P, C.c_int64, _P, C.c_double, _P, _P, C.POINTER(C.c_int64), _P]),
     ("sns_eval_p1", C.c_int, [C.c_int64, _P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
     ("sns_host_pattern", C.c_int, [C.c_int32, C.c_int64, _P, C.POINTER(C.c_int64), _P, _P, _P, _P]),
+    ("sns_host_facet_lists", C.c_int, [C.c_int32, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_int32), _P, _P, _P]),
     ("sns_host_aggregate", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int, _P, C.POINTER(C.c_int32)]),
     ("sns_host_aggregate_pts", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("sns_host_aggregate_strength", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int, _P, _P, C.POINTER(C.c_int32)]),
@@ -216,6 +220,31 @@ def host_pattern(n_nodes: int, tets):
     check(lib.sns_host_pattern(n_nodes, len(tets), tets.ctypes.data, C.byref(nnzb), rowptr.ctypes.data,
                                colind.ctypes.data, c_ptr.ctypes.data, c_idx.ctypes.data))
     return rowptr, colind, c_ptr, c_idx
+
+
+def host_facet_lists(points, tets, facets, facet_tets):
+    """(facets rewound outward (nf, 3), boundary rows, row_ptr, row_fv) of the boundary pass (sns_host_facet_lists, host only):
+    ``facets`` (nf, 3) node ids in any winding, ``facet_tets`` (nf,) the tet that owns each.  row_fv holds facet * 4 + local
+    vertex, per boundary row in ascending facet order.  Raises SnsError (SNS_E_MESH) for a facet that is no face of its tet, is
+    listed twice or has no area."""
+    import numpy as np
+    lib = load()
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    tets = np.ascontiguousarray(tets, dtype=np.int32).reshape(-1, 4)
+    facets = np.ascontiguousarray(facets, dtype=np.int32).reshape(-1, 3)
+    facet_tets = np.ascontiguousarray(facet_tets, dtype=np.int64).ravel()
+    nf = len(facets)
+    if len(facet_tets) != nf:
+        raise ValueError("one owning tet per facet")
+    out = np.empty((nf, 3), np.int32)
+    rows = np.empty(max(1, min(len(points), 3 * nf)), np.int32)
+    row_ptr = np.empty(len(rows) + 1, np.int32)
+    row_fv = np.empty(max(1, 3 * nf), np.int32)
+    nb = C.c_int32()
+    check(lib.sns_host_facet_lists(len(points), len(tets), tets.ctypes.data, points.ctypes.data, nf, facets.ctypes.data,
+                                   facet_tets.ctypes.data, out.ctypes.data, C.byref(nb), rows.ctypes.data, row_ptr.ctypes.data,
+                                   row_fv.ctypes.data))
+    return out, rows[:nb.value].copy(), row_ptr[:nb.value + 1].copy(), row_fv[:3 * nf].copy()
 
 
 def host_aggregate(rowptr, colind, n_active=None, max_agg=8, pts=None):

@@ -68,6 +68,12 @@ def duct_bcs(mesh: TetMesh, inlet_velocity=(1.0, 0.0, 0.0)) -> DirichletSet:
     ])
 
 
+def wall_only_bcs(mesh: TetMesh) -> DirichletSet:
+    """[wall u=0] and nothing else: no inflow profile, no pressure condition.  For flows driven through their open boundaries by
+    prescribed tractions (``FlowProblem.set_boundary_flow``), which also fix the pressure level."""
+    return DirichletSet(mesh, [_vel_bc(mesh.facet_nodes(mesh.meta["tags"]["wall"]), (0.0, 0.0, 0.0), mesh.points)])
+
+
 def channel_bcs(mesh: TetMesh, profile_1: Callable, profile_2: Callable) -> DirichletSet:
     """[wall, inlet_1, inlet_2, outlet] (NavierStokesChannelFlow.py:127-147).
 

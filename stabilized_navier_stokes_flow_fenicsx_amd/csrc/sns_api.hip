@@ -290,7 +290,8 @@ int ensure_hierarchy(sns_ctx* h, bool assembles_next = false) {
 enum FormRows { ROWS_ALL = 0, ROWS_ARG = SNS_E_ARG, ROWS_STATE = SNS_E_STATE };
 int form_allows(const sns_ctx* h, const char* who, policy::FormRequest request, FormRows rows = ROWS_ALL) {
     const FormState& S = h->form;
-    const policy::FormVerdict v = policy::check_form_request(request, {h->dim, h->comm != nullptr, S.tt_on, S.vl_on, S.bf_on, S.ev_on});
+    const policy::FormVerdict v =
+        policy::check_form_request(request, {h->dim, h->comm != nullptr, S.tt_on, S.vl_on, S.bf_on, S.ev_on, h->bnd.flow_on()});
     if (v.error == SNS_OK || (rows != ROWS_ALL && v.error != rows)) return SNS_OK;
     set_error(std::string(who) + ": " + v.tail);
     return v.error;
@@ -834,6 +835,34 @@ int sns_set_mixture(sns_handle h, const double* m_dev, double log_viscosity_rati
         return SNS_E_ARG;
     }
     return set_mixture(h, m_dev, log_viscosity_ratio, buoyancy);
+}
+
+// the three setters of the boundary terms (`who`: the name in front of the message)
+static int boundary_request(const char* who, const sns_ctx* h, policy::BoundaryRequest request) {
+    if (!h) { set_error(std::string(who) + ": null handle"); return SNS_E_ARG; }
+    const policy::FormVerdict v = policy::check_boundary_request(request, {h->dim, h->comm != nullptr, h->bnd.nf > 0});
+    if (v.error == SNS_OK) return SNS_OK;
+    set_error(std::string(who) + ": " + v.tail);
+    return v.error;
+}
+
+int sns_set_boundary_facets(sns_handle h, int32_t n_facets, const int32_t* facets_host, const int64_t* facet_tets_host) {
+    SNS_TRY(boundary_request("sns_set_boundary_facets", h, policy::BREQ_SET_FACETS));
+    if (n_facets < 0 || n_facets > (INT32_MAX - 3) / 9 || (n_facets > 0 && (!facets_host || !facet_tets_host))) {
+        set_error("sns_set_boundary_facets: bad facet count or null list");
+        return SNS_E_ARG;
+    }
+    return set_boundary_facets(h, n_facets, facets_host, facet_tets_host);
+}
+
+int sns_set_boundary_flow(sns_handle h, const double* t_dev, const double* beta_dev) {
+    SNS_TRY(boundary_request("sns_set_boundary_flow", h, policy::BREQ_SET_FLOW));
+    return set_boundary_flow(h, t_dev, beta_dev);
+}
+
+int sns_set_boundary_scalar(sns_handle h, const double* alpha_dev, const double* g_dev) {
+    SNS_TRY(boundary_request("sns_set_boundary_scalar", h, policy::BREQ_SET_SCALAR));
+    return set_boundary_scalar(h, alpha_dev, g_dev);
 }
 
 int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, double theta_coeff, int* its, int* reason,

@@ -1,5 +1,6 @@
 // Assembly side of the C-ABI layer: the driver of the route policy::plan_assembly (csrc/sns_policy.h) gives a call, and the residual
-// moments on the element pass of the same plan.  Host code only: no kernel of its own.  (shared internals in csrc/sns_ctx.h)
+// moments on the element pass of the same plan; both end with the boundary pass of csrc/sns_boundary.hip where facet terms are
+// set.  Host code only: no kernel of its own.  (shared internals in csrc/sns_ctx.h)
 #include "sns_ctx.h"
 
 namespace sns {
@@ -135,6 +136,9 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
     if (p.lift) SNS_TRY(lift(h, K, gd, w, F));
     if (p.bc_residual)
         hipLaunchKernelGGL(k_bc_residual, dim3(vec_grid(ndof)), dim3(256), 0, h->stream, ndof, h->bc_mask, h->bc_val, w, F);
+    // the facet terms of the 3-D NS form, on either route: after the volume passes have written vals and F (nothing set:
+    // nothing launched)
+    if (form == SNS_FORM_NS && h->dim == 3) SNS_TRY(boundary_flow(h, w, F, want_matrix ? L.vals.get() : nullptr));
     if (p.matrix) {
         // after a scalar-transport assembly (csrc/sns_scalar.hip) the hierarchy's transfers leave out the flow's Dirichlet dofs again
         if (h->matrix_form == SNS_FORM_SCALAR) SNS_TRY(fine_free_mask(h, h->bc_mask));
@@ -206,6 +210,8 @@ int residual_moments(sns_ctx* h, int form, const double* w, const double* phi, d
     HIP_TRY(hipGetLastError());
     SNS_TRY(fetch(h, h->d_scal + 104, 4, out));
     if (h->dim == 2) out[2] = 0.0;
+    // ... plus phi . (the boundary residual without the Dirichlet rule): R_raw stays the raw residual of the whole form
+    if (form == SNS_FORM_NS && h->dim == 3) SNS_TRY(boundary_moments(h, w, phi, out));
     return SNS_OK;
 }
 

@@ -79,7 +79,25 @@ struct FormState {
     // the compile-time variant of the 3-D NS assembly kernels: 0 the reference's steady form, 1 TT (a time term or a body force,
     // which rides in the effective history), 2 VL (a law; never with the others), 3 EV (a field; contains the time term)
     int ns_variant() const { return ev_on ? 3 : (vl_on ? 2 : ((tt_on || bf_on) ? 1 : 0)); }
-    policy::FormKey key() const { return {tt.sigma, tt.theta, vl_on, vl.lambda, vl.n, vl.r, ev_generation}; }   // (of an operator assembled now)
+    uint64_t boundary_generation = 0;            // moves whenever a boundary coefficient (beta, alpha) is written or cleared
+    policy::FormKey key() const {                // (of an operator assembled now)
+        return {tt.sigma, tt.theta, vl_on, vl.lambda, vl.n, vl.r, ev_generation, boundary_generation};
+    }
+};
+
+// The boundary terms (csrc/sns_boundary.hip): the facet lists of sns_set_boundary_facets and the data of sns_set_boundary_flow /
+// sns_set_boundary_scalar, all in buffers the handle owns.  Nothing is allocated before the first set; nf == 0: no facets.
+struct BoundaryState {
+    int32_t nf = 0, nb = 0;                      // facets, boundary rows
+    DevBuf<int32_t> facets;                      // [3 nf] rewound: (x1 - x0) x (x2 - x0) points out of the owning tet
+    DevBuf<int32_t> rows, row_ptr, row_fv;       // [nb], [nb + 1], [3 nf]: per row its entries facet * 4 + vertex, facets ascending
+    DevBuf<uint8_t> swapped;                     // [nf] the rewinding swapped vertices 1 and 2 (the callers' P1 data is brought into that order)
+    DevBuf<int32_t> slot;                        // [9 nf] BSR slot of block (node a, node b) of a facet at 9 f + 3 a + b
+    DevBuf<double> t, beta, alpha, g;            // [9 nf] traction, [nf], [4 nf], [12 nf], P1 data in the rewound vertex order; *_on: the term is set
+    bool t_on = false, beta_on = false, alpha_on = false, g_on = false;
+    DevBuf<double> rm;                           // [4 nb] sns_residual_moments: phi_i times the raw boundary residual of row i
+    bool flow_on() const { return nf > 0 && (t_on || beta_on); }
+    bool scalar_on() const { return nf > 0 && (alpha_on || g_on); }
 };
 
 struct sns_ctx {
@@ -132,6 +150,7 @@ struct sns_ctx {
     DevBuf<int> d_piv;
     DevBuf<int> d_sing;
     FormState form;                              // the switches of the 3-D NS form and their buffers (csrc/sns_form.hip)
+    BoundaryState bnd;                           // the facet terms and their lists (csrc/sns_boundary.hip)
     DevBuf<double> rm_nu;                        // residual moments: nu_t of the compacted cells (capacity rm_cap)
     bool has_matrix = false, pc_ready = false;
     int pc_setups = 0;
@@ -288,6 +307,15 @@ int set_body_force(sns_ctx* h, const double* f);
 int set_element_viscosity(sns_ctx* h, const double* nu);
 int set_mixture(sns_ctx* h, const double* m, double log_ratio, const double buoyancy[3]);
 int support_nu(sns_ctx* h, const double* phi, int64_t nc);
+// csrc/sns_boundary.hip: the setters of h->bnd (checked by the entry points) and the owner-computes pass over the boundary rows.
+// boundary_flow adds the traction and backflow terms to F and / or vals (either may be null) after the volume passes;
+// boundary_scalar the Robin terms to vals and rhs; boundary_moments sum_i phi_i (raw boundary residual of row i) to out[0..3]
+int set_boundary_facets(sns_ctx* h, int32_t n_facets, const int32_t* facets_host, const int64_t* facet_tets_host);
+int set_boundary_flow(sns_ctx* h, const double* t, const double* beta);
+int set_boundary_scalar(sns_ctx* h, const double* alpha, const double* g);
+int boundary_flow(sns_ctx* h, const double* w, double* F, double* vals);
+int boundary_scalar(sns_ctx* h, const uint8_t* cmask, const double* cval, double* vals, double* rhs);
+int boundary_moments(sns_ctx* h, const double* w, const double* phi, double out[4]);
 // ... and the fine level's free mask (with the per-aggregate counts derived from it) set to the complement of a Dirichlet mask
 int fine_free_mask(sns_ctx* h, const uint8_t* dirichlet_mask);
 // csrc/sns_aggregate.hip: aggregate_strength's map of the owned nodes, built on the device (amg_aggregation = 2)

@@ -7,6 +7,7 @@
 // (tet, a, b) -> block-slot relation is resolved ONCE and inverted, so the
 // device never searches and never needs atomics.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -656,9 +657,85 @@ void build_aggregation(const HostPattern& fine, int max_agg, HostAggregation& A)
     build_aggregation_active(fine, fine.n, max_agg, A);
 }
 
+// The lists of the boundary pass (csrc/sns_boundary.hip) from `nf` boundary facets and the tet that owns each: the facets rewound
+// so that (x1 - x0) x (x2 - x0) points away from the owner's fourth vertex, the boundary rows (the nodes of listed facets,
+// ascending) and per row its entries facet * 4 + local vertex in ascending facet order.  Throws, with nothing written, where a
+// facet's nodes are not three of the four nodes of its tet, a facet is listed twice or a facet has no area.
+void build_facet_lists(int32_t n, int64_t E, const int32_t* tets, const double* pts, int32_t nf, const int32_t* facets,
+                       const int64_t* ftets, HostFacetLists& L) {
+    HostFacetLists out;
+    out.facets.assign(facets, facets + 3 * (size_t)nf);
+    std::vector<std::array<int32_t, 3>> keys((size_t)nf);
+    for (int32_t k = 0; k < nf; ++k) {
+        int32_t* f = out.facets.data() + 3 * (size_t)k;
+        const int64_t t = ftets[k];
+        if (t < 0 || t >= E) throw std::runtime_error("boundary facet " + std::to_string(k) + ": owner tet out of range");
+        const int32_t* tv = tets + 4 * t;
+        int found = 0, opp = -1;
+        for (int a = 0; a < 4; ++a) {
+            const bool in = tv[a] == f[0] || tv[a] == f[1] || tv[a] == f[2];
+            if (in) ++found;
+            else opp = tv[a];
+        }
+        if (f[0] < 0 || f[1] < 0 || f[2] < 0 || f[0] >= n || f[1] >= n || f[2] >= n || f[0] == f[1] || f[0] == f[2] || f[1] == f[2] ||
+            found != 3 || opp < 0)
+            throw std::runtime_error("boundary facet " + std::to_string(k) + ": its nodes are not three of the four nodes of its tet");
+        const double *x0 = pts + 3 * (size_t)f[0], *x1 = pts + 3 * (size_t)f[1], *x2 = pts + 3 * (size_t)f[2], *xo = pts + 3 * (size_t)opp;
+        const double e1[3] = {x1[0] - x0[0], x1[1] - x0[1], x1[2] - x0[2]}, e2[3] = {x2[0] - x0[0], x2[1] - x0[1], x2[2] - x0[2]};
+        const double cr[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        const double a2 = cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2];
+        const double l2 = std::max(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+        if (!(a2 > 1e-28 * l2 * l2)) throw std::runtime_error("boundary facet " + std::to_string(k) + " is degenerate (zero area)");
+        const double out_dot = cr[0] * (x0[0] - xo[0]) + cr[1] * (x0[1] - xo[1]) + cr[2] * (x0[2] - xo[2]);
+        if (out_dot < 0.0) std::swap(f[1], f[2]);
+        keys[(size_t)k] = {f[0], f[1], f[2]};
+        std::sort(keys[(size_t)k].begin(), keys[(size_t)k].end());
+    }
+    std::sort(keys.begin(), keys.end());
+    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) throw std::runtime_error("a boundary facet is listed twice");
+    // rows: the nodes of listed facets; counting sort of the (facet, vertex) pairs by node keeps the facets ascending
+    std::vector<int32_t> count((size_t)n + 1, 0);
+    for (size_t e = 0; e < out.facets.size(); ++e) ++count[(size_t)out.facets[e] + 1];
+    std::vector<int32_t> row_of((size_t)n, -1);
+    out.row_ptr.push_back(0);
+    for (int32_t i = 0; i < n; ++i)
+        if (count[(size_t)i + 1] > 0) {
+            row_of[(size_t)i] = (int32_t)out.rows.size();
+            out.rows.push_back(i);
+            out.row_ptr.push_back(out.row_ptr.back() + count[(size_t)i + 1]);
+        }
+    out.row_fv.assign(out.facets.size(), 0);
+    std::vector<int32_t> fill(out.row_ptr.begin(), out.row_ptr.end() - 1);
+    for (int32_t k = 0; k < nf; ++k)
+        for (int a = 0; a < 3; ++a) out.row_fv[(size_t)fill[(size_t)row_of[(size_t)out.facets[3 * (size_t)k + a]]]++] = 4 * k + a;
+    L = std::move(out);
+}
+
 }  // namespace sns
 
 // ---- host-only C ABI (include/sns.h) ------------------------------------------------
+extern "C" int sns_host_facet_lists(int32_t n, int64_t E, const int32_t* tets, const double* pts, int32_t nf, const int32_t* facets,
+                                    const int64_t* facet_tets, int32_t* facets_out, int32_t* n_rows_out, int32_t* rows,
+                                    int32_t* row_ptr, int32_t* row_fv) {
+    if (n <= 0 || E < 0 || !tets || !pts || nf < 0 || (nf > 0 && (!facets || !facet_tets)) || nf > (INT32_MAX - 3) / 4) {
+        sns::set_error("sns_host_facet_lists: bad arguments");
+        return SNS_E_ARG;
+    }
+    sns::HostFacetLists L;
+    try {
+        sns::build_facet_lists(n, E, tets, pts, nf, facets, facet_tets, L);
+    } catch (const std::exception& e) {
+        sns::set_error(std::string("sns_host_facet_lists: ") + e.what());
+        return SNS_E_MESH;
+    }
+    if (n_rows_out) *n_rows_out = (int32_t)L.rows.size();
+    if (facets_out) std::copy(L.facets.begin(), L.facets.end(), facets_out);
+    if (rows) std::copy(L.rows.begin(), L.rows.end(), rows);
+    if (row_ptr) std::copy(L.row_ptr.begin(), L.row_ptr.end(), row_ptr);
+    if (row_fv) std::copy(L.row_fv.begin(), L.row_fv.end(), row_fv);
+    return SNS_OK;
+}
+
 extern "C" int sns_host_pattern(int32_t n, int64_t E, const int32_t* tets, int64_t* nnzb_out, int32_t* rowptr,
                                 int32_t* colind, int64_t* c_ptr, int32_t* c_idx) {
     if (n <= 0 || E < 0 || !tets) { sns::set_error("sns_host_pattern: bad arguments"); return SNS_E_ARG; }

@@ -49,6 +49,17 @@ void build_ap_pattern(const HostPattern& F, int32_t n_rows, const std::vector<in
 
 void build_pattern(int32_t n_nodes, int64_t n_tets, const int32_t* tets, HostPattern& P,
                    HostAssemblyMaps& M, int npe = 4);
+
+// the lists of the boundary pass (csrc/sns_boundary.hip), built once per sns_set_boundary_facets
+struct HostFacetLists {
+    std::vector<int32_t> facets;         // 3*nf, rewound: (x1 - x0) x (x2 - x0) points out of the owning tet
+    std::vector<int32_t> rows;           // the boundary rows: nodes of listed facets, ascending
+    std::vector<int32_t> row_ptr;        // rows+1
+    std::vector<int32_t> row_fv;         // 3*nf: facet * 4 + local vertex, per row in ascending facet order
+};
+// throws std::runtime_error (nothing written) for a facet that is no face of its tet, is listed twice or has no area
+void build_facet_lists(int32_t n_nodes, int64_t n_tets, const int32_t* tets, const double* pts, int32_t n_facets,
+                       const int32_t* facets, const int64_t* facet_tets, HostFacetLists& L);
 void build_aggregation(const HostPattern& fine, int max_agg, HostAggregation& A);
 // same, but only nodes [0, n_active) take part (distributed level 0: owned nodes only)
 void build_aggregation_active(const HostPattern& fine, int32_t n_active, int max_agg, HostAggregation& A);

@@ -5,7 +5,8 @@
 // CPU (sns_host_cycle_policy, tests/test_host.py) and every rank of a partitioned run answers alike by construction.
 // The handle-side predicates of csrc/sns_cycle.hip / sns_setup.hip gather the facts and ask here; the numbers live nowhere else.
 // In the same idiom, at the end: the route of an assembly (plan_assembly, tests/assembly_plan_main.cpp), what a handle's form
-// state allows (check_form_request, tests/form_request_main.cpp), which operator is a new one (OperatorKey, tests/operator_key_main.cpp).
+// state allows (check_form_request, tests/form_request_main.cpp) and what it allows of the boundary terms (check_boundary_request,
+// tests/boundary_request_main.cpp), which operator is a new one (OperatorKey, tests/operator_key_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -341,10 +342,11 @@ inline AssemblyPlan plan_assembly(const AssemblyFacts& f, bool violated = true) 
 
 // ---- what a handle's form state allows (csrc/sns_form.hip; the matrix is in DESIGN.md) ---------------------------------------------
 // Facts: the handle (dim, a communicator attached) and the switches of the 3-D NS form that are on -- time term, viscosity law,
-// body force, viscosity field.
+// body force, viscosity field, and a boundary traction or backflow coefficient (sns_set_boundary_flow).
 struct FormFacts {
     int dim = 3;
     bool partitioned = false, tt_on = false, vl_on = false, bf_on = false, ev_on = false;
+    bool boundary_flow_on = false;
 };
 enum FormRequest {
     REQ_SET_TIME_TERM = 0, REQ_CLEAR_TIME_TERM, REQ_SET_CARREAU, REQ_SET_NEWTONIAN, REQ_SET_FIELD /* set or clear: force, viscosity, mixture */,
@@ -356,7 +358,7 @@ struct FormVerdict {
     int error = SNS_OK;
     const char* tail = "";
 };
-enum FormFactBit { IS_NOT_3D = 1, IS_PARTITIONED = 2, HAS_TIME_TERM = 4, HAS_LAW = 8, HAS_FORCE = 16, HAS_FIELD = 32 };
+enum FormFactBit { IS_NOT_3D = 1, IS_PARTITIONED = 2, HAS_TIME_TERM = 4, HAS_LAW = 8, HAS_FORCE = 16, HAS_FIELD = 32, HAS_BOUNDARY_FLOW = 64 };
 // A request is refused by its first row with one of `any_of` true.  Asymmetries kept as they grew: a Newtonian law
 // is refused under a time term though it sets nothing, and allowed under a force or a field; CLEARING a field is refused
 // while a law is set; the shape gradient and the two recovery requests never ask for the dimension.
@@ -389,6 +391,8 @@ constexpr FormRule FORM_RULES[] = {
     {REQ_SHAPE_GRADIENT, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the mesh derivative of nu_e is not built)"},
     {REQ_SHAPE_GRADIENT, HAS_FORCE | HAS_FIELD, SNS_E_STATE,
      "not with a body force or a viscosity field set (the mesh derivative is not built with them)"},
+    {REQ_SHAPE_GRADIENT, HAS_BOUNDARY_FLOW, SNS_E_STATE,
+     "not with a boundary traction or backflow term set (the mesh derivative of the facet terms is not built)"},
     {REQ_RECOVER_GRADIENT, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned gradient recovery is not built)"},
     {REQ_ERROR_INDICATOR, IS_PARTITIONED, SNS_E_STATE,
      "not with a communicator attached (a partitioned indicator needs a halo exchange of G)"},
@@ -400,15 +404,48 @@ constexpr FormRule FORM_RULES[] = {
 
 inline FormVerdict check_form_request(FormRequest request, const FormFacts& f) {
     const unsigned facts = (f.dim != 3) * IS_NOT_3D | f.partitioned * IS_PARTITIONED | f.tt_on * HAS_TIME_TERM | f.vl_on * HAS_LAW |
-                           f.bf_on * HAS_FORCE | f.ev_on * HAS_FIELD;
+                           f.bf_on * HAS_FORCE | f.ev_on * HAS_FIELD | f.boundary_flow_on * HAS_BOUNDARY_FLOW;
     for (const FormRule& r : FORM_RULES)
+        if (r.request == request && (facts & r.any_of)) return {r.error, r.tail};
+    return {};
+}
+
+// ---- what a handle allows of the boundary terms (csrc/sns_boundary.hip; tests/boundary_request_main.cpp) ---------------------------
+// The three setters of the facet terms in a table of their own, in the idiom of the form requests: the handle's dimension, a
+// communicator attached, and whether facets are set (the data setters need them; setting or clearing facets never does).
+struct BoundaryFacts {
+    int dim = 3;
+    bool partitioned = false, has_facets = false;
+};
+enum BoundaryRequest { BREQ_SET_FACETS = 0, BREQ_SET_FLOW, BREQ_SET_SCALAR, BREQ_COUNT };
+enum BoundaryFactBit { B_IS_NOT_3D = 1, B_IS_PARTITIONED = 2, B_NO_FACETS = 4 };
+struct BoundaryRule {
+    BoundaryRequest request;
+    unsigned any_of;
+    int error;
+    const char* tail;
+};
+constexpr BoundaryRule BOUNDARY_RULES[] = {
+    {BREQ_SET_FACETS, B_IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {BREQ_SET_FACETS, B_IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
+    {BREQ_SET_FLOW, B_IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {BREQ_SET_FLOW, B_IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
+    {BREQ_SET_FLOW, B_NO_FACETS, SNS_E_STATE, "set the boundary facets first (sns_set_boundary_facets)"},
+    {BREQ_SET_SCALAR, B_IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {BREQ_SET_SCALAR, B_IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
+    {BREQ_SET_SCALAR, B_NO_FACETS, SNS_E_STATE, "set the boundary facets first (sns_set_boundary_facets)"},
+};
+inline FormVerdict check_boundary_request(BoundaryRequest request, const BoundaryFacts& f) {
+    const unsigned facts = (f.dim != 3) * B_IS_NOT_3D | f.partitioned * B_IS_PARTITIONED | (!f.has_facets) * B_NO_FACETS;
+    for (const BoundaryRule& r : BOUNDARY_RULES)
         if (r.request == request && (facts & r.any_of)) return {r.error, r.tail};
     return {};
 }
 
 // ---- which operator is it? (the spectral estimates of csrc/sns_setup.hip; the cases are in DESIGN.md) -----------------------------
 // What the fine operator's values depend on beside the state: the form's share (FormKey: time term, viscosity law, and a counter
-// that moves whenever the viscosity field is written or cleared) and the call's (the form id, the Reynolds number, the six
+// that moves whenever the viscosity field is written or cleared, another that moves whenever a boundary coefficient -- the
+// backflow beta, the Robin alpha -- is written or cleared) and the call's (the form id, the Reynolds number, the six
 // parameters of a scalar assembly, whether the values were transposed since).  The handle keeps the key of the operator in
 // levels[0].vals and the key of the operator the levels' estimates were taken on; a set-up takes them again iff the two differ.
 struct FormKey {
@@ -416,9 +453,10 @@ struct FormKey {
     bool law_on = false;
     double lambda = 0.0, n = 1.0, r = 0.0;
     uint64_t nu_generation = 0;
+    uint64_t boundary_generation = 0;
     bool operator==(const FormKey& o) const {
         return sigma == o.sigma && theta == o.theta && law_on == o.law_on && lambda == o.lambda && n == o.n && r == o.r &&
-               nu_generation == o.nu_generation;
+               nu_generation == o.nu_generation && boundary_generation == o.boundary_generation;
     }
 };
 struct OperatorKey {

@@ -199,6 +199,7 @@ int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sig
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     hipLaunchKernelGGL(k_scalar_system, dim3(grid), dim3(256), 0, h->stream, h->n, L.rowptr, L.colind, h->c_ptr, h->c_idx, h->tets,
                        h->pts, w, P, src, cmask, cval, L.vals, rhs);
+    SNS_TRY(boundary_scalar(h, cmask, cval, L.vals, rhs));     // the Robin terms (csrc/sns_boundary.hip; nothing set: nothing launched)
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     const hipError_t e = hipGetLastError();
     const double par[6] = {kappa[0], kappa[1], kappa[2], kappa[3], sigma, theta};

@@ -768,15 +768,17 @@ def strouhal_from_lift(t, cl, diameter: float = 0.1, u_mean: float = 1.0, skip: 
 
 
 def run_dfg2d2_slab(n: float = 2, dt: float = 0.01, n_steps: int = 800, *, theta_coeff: float = 4.0, corrected_convection: int = 1,
-                    device=None, verbose: bool = True, **options):
+                    device=None, verbose: bool = True, backflow_beta: float = 0.0, **options):
     """The unsteady DFG benchmark 2D-2 (Re = 100: inlet peak 1.5, mean 1.0, nu = 1e-3) through the 3-D kernels, on the
     one-cell slab of ``mesh2d.dfg2d_slab_problem(n, u_max=1.5)``.  NOT in the reference (which has no unsteady form and
     runs 2D-1 only); the steady sibling is ``test_gpu_2d``'s slab series.  Starts from the Stokes solution, steps with
     BDF2 (``solver.solve_unsteady``) and samples C_d(t), C_l(t) per step with the residual-based force
     (``functionals.reaction_force``, consistent with the step's time term).  Prints max C_d, max C_l and the Strouhal
     number of the lift's zero crossings next to the Schaefer-Turek brackets (3.22-3.24, 0.99-1.01, 0.295-0.305), which a
-    first-order P1-P1 discretisation on these meshes is not expected to hit.  Returns a dict with the time series, the
-    per-step records and the three numbers."""
+    first-order P1-P1 discretisation on these meshes is not expected to hit.  ``backflow_beta`` > 0 adds the backflow
+    term -beta (u.n)_- u.v on the outlet facets (``FlowProblem.set_boundary_flow``), which keeps a vortex that leaves through
+    the do-nothing outlet from feeding energy in; the default 0 sets nothing and gives the run without it.  Returns a dict
+    with the time series, the per-step records and the three numbers."""
     import torch
     from . import functionals as Fn, mesh2d as M2
     from .solver import FlowProblem, solve_unsteady
@@ -790,6 +792,9 @@ def run_dfg2d2_slab(n: float = 2, dt: float = 0.01, n_steps: int = 800, *, theta
     if rs.reason <= 0:
         raise RuntimeError(f"Stokes start did not converge (reason {rs.reason})")
     U.view(-1, 4)[:, 3] *= nu                              # (unit-viscosity Stokes pressure -> the NS scaling)
+    if backflow_beta > 0.0:
+        P.set_boundary_facets(m3.find(m3.meta["tags"]["outlet"]))
+        P.set_boundary_flow(backflow=backflow_beta)
     ob = m3.meta["tags"]["obstacle"]
     ts, cds, cls = [], [], []
 
@@ -816,3 +821,33 @@ def run_dfg2d2_slab(n: float = 2, dt: float = 0.01, n_steps: int = 800, *, theta
               flush=True)
     return dict(t=np.array(ts), cd=np.array(cds), cl=np.array(cls), records=recs, cd_max=cd_max, cl_max=cl_max, strouhal=st,
                 crossings=ncross, n_tets=m3.num_tets, seconds=seconds, w=w, points=m3.points)
+
+
+def run_pressure_driven_duct(cells=(12, 4, 4), length: float = 3.0, dp: float = 1.0, reynolds: float = 10.0, *, device=None,
+                             verbose: bool = True, **options):
+    """A duct driven by a pressure difference alone (NOT in the reference, whose inflows are all Dirichlet profiles): no-slip
+    on the wall and nothing else (``bcs.wall_only_bcs``), the traction -dp n on the inlet facets and 0 on the outlet facets
+    (``FlowProblem.set_boundary_flow``), Newton from rest.  Under the reference's viscous term the traction is the
+    pseudo-traction nu d_n u - p n, so the developed flow has p = dp at the inlet and 0 at the outlet.  Prints the flow rate
+    through the inlet and the outlet (outward fluxes of the P1 velocity, exact per facet).  Returns a dict with the state, the
+    two fluxes, the Newton result and the mesh."""
+    import torch
+    from .solver import FlowProblem
+    msh = M.duct_mesh(tuple(cells), float(length))
+    tags = msh.meta["tags"]
+    opts = dict(reynolds=float(reynolds), snes_rtol=1e-10, snes_atol=1e-12, ksp_rtol=1e-10)
+    opts.update(options)
+    P = FlowProblem(msh, B.wall_only_bcs(msh), device=device or f"cuda:{torch.cuda.current_device()}", **opts)
+    inlet, outlet = msh.find(tags["inlet"]), msh.find(tags["outlet"])
+    P.set_boundary_facets(np.concatenate([inlet, outlet]))
+    P.set_boundary_flow(pressure=np.concatenate([np.full(len(inlet), float(dp)), np.zeros(len(outlet))]))
+    w, res = P.newton_solve(P.zeros())
+    wh = w.cpu().numpy()
+    un = np.einsum("fac,fc->f", wh.reshape(-1, 4)[:, :3][msh.facets[P.boundary_facet_ids].astype(np.int64)], P.boundary_normals) / 3.0
+    flux = un * P.boundary_areas
+    q_in, q_out = -float(flux[:len(inlet)].sum()), float(flux[len(inlet):].sum())
+    P.close()
+    if verbose:
+        print(f"pressure-driven duct {tuple(cells)}, L {length}, dp {dp}, Re {reynolds}: Newton its {res.its} reason {res.reason}, "
+              f"flow rate in {q_in:.6e} out {q_out:.6e}", flush=True)
+    return dict(w=wh, q_in=q_in, q_out=q_out, newton=res, mesh=msh)

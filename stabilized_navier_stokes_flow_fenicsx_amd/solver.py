@@ -481,6 +481,99 @@ class FlowProblem:
         b = (C.c_double * 3)(*[float(x) for x in buoyancy])
         check(self.lib.sns_set_mixture(self.h, _ptr(m), float(log_viscosity_ratio), b))
 
+    # -- boundary terms (no counterpart in the reference: its forms are volume integrals, its outlets do-nothing) -------
+    def set_boundary_facets(self, facet_ids):
+        """The boundary facets the facet terms live on (sns_set_boundary_facets): indices into ``mesh.facets``.  Replaces an
+        earlier list and clears the data of ``set_boundary_flow`` / ``set_boundary_scalar`` (they are per facet); an empty list
+        is ``clear_boundary_terms``.  Keeps ``boundary_facet_ids``, and per listed facet ``boundary_normals`` (outward unit
+        normals: away from the fourth vertex of the owning tet) and ``boundary_areas``.  Per-facet and per-vertex data of the
+        two setters is in the order of this list and of the vertices of ``mesh.facets``.  Single-GPU 3-D problems."""
+        from .functionals import facet_parent_tets
+        ids = np.asarray(facet_ids, dtype=np.int64).ravel()
+        if len(ids) == 0:
+            return self.clear_boundary_terms()
+        if self.dim != 3:                                      # (the library's refusal, before the mesh is asked for tets)
+            z3, z1 = np.zeros(3, np.int32), np.zeros(1, np.int64)
+            check(self.lib.sns_set_boundary_facets(self.h, 1, z3.ctypes.data, z1.ctypes.data))
+        fn = np.ascontiguousarray(self.mesh.facets[ids], dtype=np.int32)
+        par = np.ascontiguousarray(facet_parent_tets(self.mesh, ids), dtype=np.int64)
+        check(self.lib.sns_set_boundary_facets(self.h, len(ids), fn.ctypes.data, par.ctypes.data))
+        P = self.mesh.points[fn.astype(np.int64)]
+        cr = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+        opp = self.mesh.tets[par].astype(np.int64).sum(axis=1) - fn.astype(np.int64).sum(axis=1)
+        cr *= np.sign(np.einsum("fi,fi->f", cr, P[:, 0] - self.mesh.points[opp]))[:, None]
+        nrm = np.linalg.norm(cr, axis=1)
+        self.boundary_facet_ids, self.boundary_normals, self.boundary_areas = ids, cr / nrm[:, None], 0.5 * nrm
+
+    def _facet_count(self) -> int:
+        ids = getattr(self, "boundary_facet_ids", None)
+        return 0 if ids is None else len(ids)
+
+    def _facet_dev(self, x):
+        return None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64).ravel()).to(self.device)
+
+    def set_boundary_flow(self, traction=None, pressure=None, backflow=None):
+        """Every NS assembly of this problem from now on has, on the facets of ``set_boundary_facets`` (sns_set_boundary_flow),
+
+            R(w; v) += - int t.v ds - int beta (u.n)_- u.v ds,      (u.n)_- = min(u.n, 0).
+
+        ``traction``: (3,), (nf, 3) or (nf, 3, 3) [facet][vertex][component], P1 per facet -- the pseudo-traction nu d_n u - p n
+        under the reference's viscous term, the true traction 2 nu eps(u) n - p n under a viscosity law or field.
+        ``pressure``: a scalar or one value per facet, added as t = -p n (a pressure boundary).  ``backflow``: beta >= 0, a
+        scalar or one value per facet; 0 switches the term off on that facet.  What is None is cleared; the Jacobian is the
+        exact derivative with t and beta held fixed.  ``residual_shape_gradient`` is refused while either is set."""
+        nf = self._facet_count()
+        t = None
+        if nf and (traction is not None or pressure is not None):
+            t = np.zeros((nf, 3, 3))
+            if traction is not None:
+                tr = np.asarray(traction, dtype=np.float64)
+                t += tr[:, None, :] if tr.shape == (nf, 3) else tr           # (3,) and (nf, 3, 3) broadcast as they are
+            if pressure is not None:
+                p = np.broadcast_to(np.asarray(pressure, dtype=np.float64), (nf,))
+                t -= (p[:, None] * self.boundary_normals)[:, None, :]
+        elif traction is not None or pressure is not None:
+            t = np.zeros(1)                                     # (no facets: the library refuses)
+        beta = None if backflow is None else np.broadcast_to(np.asarray(backflow, dtype=np.float64), (max(nf, 1),)).copy()
+        t, beta = self._facet_dev(t), self._facet_dev(beta)
+        check(self.lib.sns_set_boundary_flow(self.h, _ptr(t), _ptr(beta)))
+
+    def set_boundary_scalar(self, alpha=None, ambient=None, flux=None):
+        """Every ``scalar_system`` / ``scalar_solve`` of this problem from now on has, on the facets of ``set_boundary_facets``
+        (sns_set_boundary_scalar), R_k(c; v) += int (alpha_k c_k - g_k) v ds with g = alpha c_ext + q, i.e. the Robin condition
+        kappa d_n c = alpha (c_ext - c) + q.  For k species: ``alpha`` >= 0 a scalar, (k,) or (nf, k); ``ambient`` (c_ext) and
+        ``flux`` (q) a scalar, (k,), (nf, k) or P1 per facet (nf, 3, k).  alpha = None with a flux is the Neumann condition
+        kappa d_n c = q; all None clears both terms."""
+        nf = max(self._facet_count(), 1)
+        given = [np.asarray(x, dtype=np.float64) for x in (alpha, ambient, flux) if x is not None]
+        k = max([x.shape[-1] for x in given if x.ndim >= 1] + [1])
+        if not 1 <= k <= 4:
+            raise ValueError("boundary scalar data: one to four species")
+        if ambient is not None and alpha is None:
+            raise ValueError("an ambient value needs alpha")
+
+        def p1(x):                                             # -> (nf, 3, k)
+            x = np.asarray(x, dtype=np.float64)
+            return np.broadcast_to(x[:, None, :] if x.ndim == 2 else x, (nf, 3, k))
+
+        a4 = g4 = None
+        if alpha is not None:
+            a4 = np.zeros((nf, 4))
+            a4[:, :k] = np.broadcast_to(np.asarray(alpha, dtype=np.float64), (nf, k))
+        if ambient is not None or flux is not None:
+            g4 = np.zeros((nf, 3, 4))
+            if ambient is not None:
+                g4[:, :, :k] += a4[:, None, :k] * p1(ambient)
+            if flux is not None:
+                g4[:, :, :k] += p1(flux)
+        a4, g4 = self._facet_dev(a4), self._facet_dev(g4)
+        check(self.lib.sns_set_boundary_scalar(self.h, _ptr(a4), _ptr(g4)))
+
+    def clear_boundary_terms(self):
+        """No facets and no boundary data: back to the forms without facet terms, bit for bit."""
+        check(self.lib.sns_set_boundary_facets(self.h, 0, None, None))
+        self.boundary_facet_ids = self.boundary_normals = self.boundary_areas = None
+
     # -- scalar transport on the flow mesh (no counterpart in the reference, which traces streamlines instead) --------
     def _scalar_inputs(self, w, kappa, bcs, source):
         """Device arguments of the two scalar entry points, padded to four species: the unused ones are constrained to 0

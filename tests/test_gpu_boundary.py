@@ -1,0 +1,438 @@
+"""The boundary terms on the GPU (sns_set_boundary_facets, sns_set_boundary_flow, sns_set_boundary_scalar; FlowProblem
+.set_boundary_*; drivers.run_pressure_driven_duct), everything through the C-ABI.
+
+The reference has no facet integral; the yardstick is the test-side oracle tests/boundary_oracle.py (literal restatement,
+autograd Jacobian, LU-Newton) whose own checks -- two known answers among them -- are tests/test_host_boundary.py, and its
+single-tet cases in tests/golden/boundary_cases.npz.  Tolerances as in tests/test_gpu_fields.py: operators and residuals 1e-12
+relative, the two assembly routes against each other 1e-13, Krylov-converged fields 1e-6, J dw against central differences of
+the residual 1e-6.  The mesh is the jittered 4 x 3 x 3-cell duct unless said otherwise."""
+import numpy as np
+import pytest
+import torch
+
+import boundary_oracle as BO
+import fields_oracle as FO
+import scalar_oracle as SO
+from conftest import rel
+from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B
+from stabilized_navier_stokes_flow_fenicsx_amd import drivers as D
+from stabilized_navier_stokes_flow_fenicsx_amd import functionals as FN
+from stabilized_navier_stokes_flow_fenicsx_amd import mesh as M
+from stabilized_navier_stokes_flow_fenicsx_amd import mesh2d as M2
+from stabilized_navier_stokes_flow_fenicsx_amd.solver import FlowProblem, SnsError
+from test_gpu_adjoint import _adjoint_identity
+from test_host_boundary import FIXTURE, duct, hydrostatic_problem, robin_problem
+
+pytestmark = pytest.mark.gpu
+TIGHT = dict(ksp_rtol=1e-11, snes_rtol=1e-10, snes_atol=1e-14, snes_stol=1e-14)
+RE = 17.0
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()
+
+
+def _fields_close(a, b, tol=1e-6):
+    a, b = np.asarray(a).reshape(-1, 4), np.asarray(b).reshape(-1, 4)
+    return rel(a[:, :3], b[:, :3]) < tol and rel(a[:, 3], b[:, 3]) < tol
+
+
+def _system(P, wd):
+    F = P.zeros()
+    P.jacobian(wd, "ns", residual_out=F)
+    return P.bsr()[2].clone(), F.clone(), P.residual(wd, "ns")
+
+
+def _duct_case(seed, inlet_velocity=(1.0, 0.0, 0.0)):
+    """The duct with its boundary data, the inlet and outlet facets listed (beta on the outlet only, random tractions on both),
+    a random state that satisfies the data and one that violates it."""
+    rng = np.random.default_rng(seed)
+    m, par = duct()
+    mask, g = B.duct_bcs(m, inlet_velocity).flatten()
+    tags = m.meta["tags"]
+    inlet, outlet = m.find(tags["inlet"]), m.find(tags["outlet"])
+    ids = np.concatenate([inlet, outlet])
+    t = rng.normal(size=(len(ids), 3, 3))
+    beta = np.concatenate([np.zeros(len(inlet)), rng.uniform(0.5, 2.0, len(outlet))])
+    Bm = mask.astype(bool)
+    w = rng.normal(size=m.num_dofs) * 0.5
+    w[Bm] = g[Bm]
+    w2 = w.copy()
+    w2[np.nonzero(Bm)[0][::3]] += 0.3
+    return dict(m=m, par=par, mask=mask, g=g, ids=ids, facets=m.facets[ids], own=par[ids], t=t, beta=beta, w=w, w2=w2, rng=rng,
+                outlet=outlet)
+
+
+# ---- 1. one tet --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [1, 0])
+def test_one_tet_against_the_oracle(fused):
+    fx = np.load(FIXTURE)
+    none = (np.zeros(16, np.uint8), np.zeros(16))
+    tet = np.array([[0, 1, 2, 3]], np.int32)
+    for i in range(len(fx["X"])):
+        X, W = fx["X"][i], fx["W"][i]
+        m = M.TetMesh(np.ascontiguousarray(X), tet, fx["faces"].astype(np.int32), np.zeros(4, np.int32))
+        Fv, Jv = FO.raw(X, tet, W, RE)
+        Fo, Jo = Fv + fx["F"][i], Jv.toarray() + fx["J"][i]
+        P = FlowProblem(m, none, reynolds=RE, pc_type="bjacobi", assembly_fused=fused)
+        P.set_boundary_facets(np.arange(4))
+        P.set_boundary_flow(traction=fx["t"][i], backflow=fx["beta"][i])
+        F = P.zeros()
+        P.jacobian(_dev(W), "ns", residual_out=F)
+        eJ, eF = rel(P.to_scipy().toarray(), Jo), rel(F.cpu().numpy(), Fo)
+        eR = rel(P.residual(_dev(W), "ns").cpu().numpy(), Fo)
+        print(f"one tet {i} fused {fused}: J {eJ:.1e} F {eF:.1e} residual alone {eR:.1e}")
+        assert eJ < 1e-12 and eF < 1e-12 and eR < 1e-12, i
+        # the scalars' facet terms on the same tet, no Dirichlet node
+        kappa = np.array([1.0, 0.1, 0.5, 2.0])
+        A0, b0 = SO.raw(X, tet, W, kappa)
+        P.set_boundary_scalar(alpha=fx["alpha"][i], flux=fx["g"][i])
+        rhs = P.scalar_system(_dev(W), kappa, (np.zeros((4, 4), bool), np.zeros((4, 4))))
+        assert rel(P.to_scipy().toarray(), A0.toarray() + fx["scalar_A"][i]) < 1e-12, i
+        assert rel(rhs.cpu().numpy(), b0 + fx["scalar_b"][i]) < 1e-12, i
+        P.close()
+
+
+# ---- 2. global ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_fused_staged_and_oracle_agree_globally(corrected):
+    c = _duct_case(92)
+    m, rng = c["m"], c["rng"]
+    m.tets = np.ascontiguousarray(np.take_along_axis(m.tets, np.argsort(rng.random(m.tets.shape), axis=1), axis=1))
+    f, d = rng.normal(size=m.num_dofs), rng.normal(size=m.num_dofs)
+    nu = 10.0 ** rng.uniform(-2.0, 0.0, size=m.num_tets)
+    P = FlowProblem(m, (c["mask"], c["g"]), reynolds=RE, corrected_convection=corrected)
+    P.set_boundary_facets(c["ids"])
+    P.set_boundary_flow(traction=c["t"], backflow=c["beta"])
+    free = c["mask"] == 0
+    # the terms alone, then with a time term, a body force and a viscosity field
+    for kw in (dict(), dict(f=f, nu_t=nu, d=d, sigma=6.0, theta=900.0)):
+        if kw:
+            P.set_body_force(_dev(f))
+            P.set_element_viscosity(nu)
+            P.set_time_term(kw["sigma"], kw["theta"], _dev(d))
+        for state in (c["w"], c["w2"]):                             # w2: the lifting through boundary columns
+            Jo, Fo = BO.assemble(m.points, m.tets, state, RE, c["mask"], c["g"], c["facets"], c["own"], t=c["t"], beta=c["beta"],
+                                 corrected_convection=bool(corrected), **kw)
+            Jv, Fv = FO.assemble(m.points, m.tets, state, RE, c["mask"], c["g"], corrected_convection=bool(corrected), **kw)
+            assert abs(Jo - Jv).max() > 1e-3 * abs(Jo).max() and rel(Fv, Fo) > 1e-3      # (the terms are visible at this state)
+            got = []
+            for fused in (1, 0):
+                P.set_options(assembly_fused=fused)
+                F = P.zeros()
+                P.jacobian(_dev(state), "ns", residual_out=F)
+                got.append((P.to_scipy(), F.cpu().numpy()))
+                eJ, eF = abs(got[-1][0] - Jo).max() / abs(Jo).max(), rel(got[-1][1], Fo)
+                eR = rel(P.residual(_dev(state), "ns").cpu().numpy(), Fo)
+                print(f"global corrected {corrected} {sorted(kw)} fused {fused}: J {eJ:.1e} F {eF:.1e} residual alone {eR:.1e}")
+                assert eJ < 1e-12 and eF < 1e-12 and eR < 1e-12, (fused, sorted(kw))
+            assert abs(got[0][0] - got[1][0]).max() < 1e-13 * abs(got[1][0]).max()
+            assert rel(got[0][1], got[1][1]) < 1e-13
+        # J dw against central differences of the residual at the state that satisfies the data (free rows; dw_B = 0)
+        area, n = BO.facet_geometry(m.points, m.tets, c["facets"], c["own"])
+        un = np.einsum("qa,fac,fc->fq", BO.QPTS, c["w"].reshape(-1, 4)[:, :3][c["facets"].astype(np.int64)], n)[c["beta"] > 0]
+        # no quadrature point changes its branch within h |dw| (u.n == 0 exactly: a facet with its three nodes on the no-slip
+        # wall, which dw does not move)
+        assert abs(un[un != 0.0]).min() >= 1e-4 and un.min() < 0 < un.max()
+        dw = rng.normal(size=m.num_dofs) * free
+        h = 1e-6
+        P.jacobian(_dev(c["w"]), "ns")
+        Jdw = P.spmv(_dev(dw)).cpu().numpy()
+        fd = (P.residual(_dev(c["w"] + h * dw), "ns") - P.residual(_dev(c["w"] - h * dw), "ns")).cpu().numpy() / (2.0 * h)
+        e = rel(Jdw[free], fd[free])
+        print(f"global corrected {corrected} {sorted(kw)}: J dw against central differences {e:.1e}")
+        assert e < 1e-6
+    P.close()
+
+
+# ---- 3. hydrostatic state through the library -----------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [1, 0])
+def test_hydrostatic_state_through_the_library(fused):
+    m, par, w, f, t = hydrostatic_problem()
+    P = FlowProblem(m, (np.zeros(m.num_dofs, np.uint8), np.zeros(m.num_dofs)), reynolds=10.0, assembly_fused=fused)
+    P.set_body_force(_dev(f))
+    wd = _dev(w)
+    off = max(float(x.abs().max()) for x in _system(P, wd)[1:])
+    P.set_boundary_facets(np.arange(len(m.facets)))
+    P.set_boundary_flow(traction=t)
+    s = _system(P, wd)
+    on = max(float(s[1].abs().max()), float(s[2].abs().max()))
+    print(f"hydrostatic fused {fused}: max |F| with the traction {on:.2e}, without {off:.2e}")
+    assert on <= 1e-12
+    assert off >= 0.1
+    P.close()
+
+
+# ---- 4. pressure-driven duct -----------------------------------------------------------------------------------------------
+def test_pressure_driven_duct():
+    out = D.run_pressure_driven_duct((12, 4, 4), 3.0, 1.0, 10.0, **TIGHT)
+    m, res = out["mesh"], out["newton"]
+    assert m.num_nodes == 13 * 5 * 5 and res.reason > 0
+    tags = m.meta["tags"]
+    mask, g = B.wall_only_bcs(m).flatten()
+    inlet, outlet = m.find(tags["inlet"]), m.find(tags["outlet"])
+    ids = np.concatenate([inlet, outlet])
+    par = FN.facet_parent_tets(m, ids)
+    area, n = BO.facet_geometry(m.points, m.tets, m.facets[ids], par)
+    p = np.concatenate([np.ones(len(inlet)), np.zeros(len(outlet))])
+    t = np.broadcast_to((-p[:, None] * n)[:, None, :], (len(ids), 3, 3))
+    wo, its = BO.newton(m.points, m.tets, mask, g, 10.0, np.zeros(m.num_dofs), m.facets[ids], par, t=t)
+    print(f"pressure-driven duct: library its {res.its}, oracle its {its}, rel {rel(out['w'], wo):.2e}, flow rate in {out['q_in']:.6e} "
+          f"out {out['q_out']:.6e}")
+    assert out["q_in"] > 1e-3                                       # the pressure difference drives a flow from inlet to outlet
+    assert _fields_close(out["w"], wo)
+    # no pressure row is constrained and sum_i grad phi_i = 0, so the continuity rows sum to int div u = q_out - q_in: the two
+    # fluxes agree to the solver tolerance (1e-6, the bound of a Krylov-converged field) times the open surface area
+    assert abs(out["q_in"] - out["q_out"]) <= 1e-6 * area.sum()
+
+
+# ---- 5. scalar system ----------------------------------------------------------------------------------------------------
+def test_scalar_system_against_the_oracle():
+    c = _duct_case(95)
+    m, rng = c["m"], c["rng"]
+    nf, n = len(c["ids"]), m.num_nodes
+    kappa = np.array([1.0, 0.1, 1e-2, 0.5])
+    alpha = rng.uniform(0.0, 3.0, (nf, 4))
+    alpha[::4] = 0.0
+    gq = rng.normal(size=(nf, 3, 4))
+    cmask = rng.random((n, 4)) < 0.15
+    cmask[np.unique(c["facets"])[::3]] = True                       # scalar Dirichlet nodes on listed facets: rows skipped, columns lifted
+    cval = rng.normal(size=(n, 4))
+    P = FlowProblem(m, (c["mask"], c["g"]), reynolds=RE)
+    P.set_boundary_facets(c["ids"])
+    P.set_boundary_scalar(alpha=alpha, flux=gq)
+    for sigma, theta, src in ((0.0, 0.0, None), (0.7, 5.0, rng.normal(size=(n, 4)))):
+        Ao, bo = BO.scalar_assemble(m.points, m.tets, c["w"], kappa, cmask, np.where(cmask, cval, 0.0), c["facets"], c["own"],
+                                    alpha=alpha, g=gq, sigma=sigma, theta=theta, source=src)
+        rhs = P.scalar_system(_dev(c["w"]), kappa, (cmask, cval), sigma=sigma, theta=theta, source=src)
+        eA, eb = abs(P.to_scipy() - Ao).max() / abs(Ao).max(), rel(rhs.cpu().numpy(), bo)
+        print(f"scalar system sigma {sigma}: A {eA:.1e} b {eb:.1e}")
+        assert eA < 1e-12 and eb < 1e-12
+    A1 = P.bsr()[2].clone()
+    P.set_boundary_scalar()                                         # cleared: the operator without facet terms
+    P.scalar_system(_dev(c["w"]), kappa, (cmask, cval), sigma=0.7, theta=5.0)
+    assert not torch.equal(A1, P.bsr()[2])
+    P.close()
+
+
+def test_robin_known_answer_through_scalar_solve():
+    m, par, out, kappa, alpha, c_ext, q, cmask, cval, exact = robin_problem()
+    P = FlowProblem(m, B.duct_bcs(m).flatten(), reynolds=RE, ksp_rtol=1e-12)
+    P.set_boundary_facets(out)
+    P.set_boundary_scalar(alpha=alpha, ambient=c_ext, flux=q)
+    c, res = P.scalar_solve(P.zeros(), kappa, (cmask.astype(bool), cval))
+    e = abs(c.cpu().numpy() - exact).max()
+    print(f"robin through scalar_solve: its {res.its} reason {res.reason} max error {e:.2e}")
+    assert res.reason > 0 and e <= 1e-6
+    P.close()
+
+
+# ---- 6. side effects -----------------------------------------------------------------------------------------------------
+def _backflow_case():
+    """The duct driven backwards (inlet velocity -1: the fluid enters through the outlet), its Stokes state, beta on the outlet."""
+    c = _duct_case(96, inlet_velocity=(-1.0, 0.0, 0.0))
+    P = FlowProblem(c["m"], (c["mask"], c["g"]), reynolds=RE, **TIGHT)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    P.set_boundary_facets(c["ids"])
+    P.set_boundary_flow(backflow=c["beta"])
+    return c, P, U
+
+
+def test_adjoint_identity_with_backflow():
+    c, P, U = _backflow_case()
+    rng = c["rng"]
+    P.jacobian(U, "ns")
+    A = P.to_scipy()
+    Jv = FO.assemble(c["m"].points, c["m"].tets, U.cpu().numpy(), RE, c["mask"], c["g"])[0]
+    assert abs(A - Jv).max() > 1e-3 * abs(A).max()                  # (the backflow term is in the operator)
+    _adjoint_identity(P, A, rng.normal(size=c["m"].num_dofs), rng.normal(size=c["m"].num_dofs), "backflow")
+    P.close()
+
+
+def test_residual_moments_include_the_boundary_residual():
+    c = _duct_case(97)
+    m = c["m"]
+    P = FlowProblem(m, (c["mask"], c["g"]), reynolds=RE)
+    P.set_boundary_facets(c["ids"])
+    P.set_boundary_flow(traction=c["t"], backflow=c["beta"])
+    ind = np.zeros(m.num_nodes)
+    ind[np.unique(m.facets[c["outlet"]])] = 1.0
+    for state in (c["w"], c["w2"]):                                 # R_raw knows no Dirichlet rule
+        Fr, _ = BO.raw(m.points, m.tets, state, RE, c["facets"], c["own"], t=c["t"], beta=c["beta"], want_jac=False)
+        Fv, _ = FO.raw(m.points, m.tets, state, RE, want_jac=False)
+        for name, phi in (("one", np.ones(m.num_nodes)), ("outlet", ind)):
+            want = (phi[:, None] * Fr.reshape(-1, 4)).sum(axis=0)
+            without = (phi[:, None] * Fv.reshape(-1, 4)).sum(axis=0)
+            got = P.residual_moments(_dev(state), phi)
+            print(f"moments phi = {name}: rel {rel(got, want):.1e} (boundary share {rel(without, want):.1e})")
+            assert rel(got, want) < 1e-12 and rel(without, want) > 1e-3
+    P.close()
+
+
+def test_bdf2_step_with_backflow():
+    c, P, U = _backflow_case()
+    m = c["m"]
+    w0 = U.cpu().numpy()
+    dt, theta_coeff = 0.05, 4.0
+    wo, its = BO.step(m.points, m.tets, c["mask"], c["g"], RE, w0, w0, dt, 2, theta_coeff, c["facets"], c["own"], beta=c["beta"])
+    wv, _ = FO.step(m.points, m.tets, c["mask"], c["g"], RE, w0, w0, dt, 2, theta_coeff)
+    w, wprev = U.clone(), U.clone()
+    w, res = P.time_step(w, wprev, dt, order=2, theta_coeff=theta_coeff)
+    print(f"BDF2 step with backflow: its {res.its} (oracle {its}) reason {res.reason} rel {rel(w.cpu().numpy(), wo):.2e}; the step "
+          f"without the term differs by {rel(wv, wo):.2e}")
+    assert res.reason > 0 and _fields_close(w.cpu().numpy(), wo)
+    assert rel(wv, wo) > 1e-4                                       # (the term moves the step)
+    P.close()
+
+
+# ---- 7. contract -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [1, 0])
+def test_cleared_terms_are_bitwise_the_handle_as_it_was(fused):
+    c = _duct_case(98)
+    wd = _dev(c["w2"])
+    P = FlowProblem(c["m"], (c["mask"], c["g"]), reynolds=RE, assembly_fused=fused)
+    P.clear_boundary_terms()                                        # clearing what is not set, on a fresh handle
+    s0 = _system(P, wd)
+    phi = np.ones(c["m"].num_nodes)
+    m0 = P.residual_moments(wd, phi)
+    P.set_boundary_facets(c["ids"])
+    assert all(torch.equal(a, b) for a, b in zip(s0, _system(P, wd)))            # facets alone: nothing launched
+    P.set_boundary_flow(traction=c["t"], backflow=c["beta"])
+    s1 = _system(P, wd)
+    assert not torch.equal(s0[0], s1[0]) and not torch.equal(s0[1], s1[1]) and not torch.equal(s0[2], s1[2])
+    assert all(torch.equal(a, b) for a, b in zip(s1, _system(P, wd)))            # two runs of the pass: identical bits
+    assert not np.array_equal(m0, P.residual_moments(wd, phi))
+    P.set_boundary_flow()                                           # both terms cleared, the facets stay
+    assert all(torch.equal(a, b) for a, b in zip(s0, _system(P, wd)))
+    P.set_boundary_flow(traction=c["t"], backflow=c["beta"])
+    assert all(torch.equal(a, b) for a, b in zip(s1, _system(P, wd)))
+    P.clear_boundary_terms()
+    assert all(torch.equal(a, b) for a, b in zip(s0, _system(P, wd)))
+    assert np.array_equal(m0, P.residual_moments(wd, phi))
+    P.close()
+
+
+def test_boundary_buffers_go_with_the_handle():
+    from stabilized_navier_stokes_flow_fenicsx_amd import _lib
+    c = _duct_case(99)
+    base = int(_lib.load().sns_live_device_bytes())
+    P = FlowProblem(c["m"], (c["mask"], c["g"]), reynolds=RE)
+    P.jacobian(_dev(c["w"]), "ns", residual_out=P.zeros())
+    before = int(_lib.load().sns_live_device_bytes())
+    P.jacobian(_dev(c["w"]), "ns", residual_out=P.zeros())
+    assert int(_lib.load().sns_live_device_bytes()) == before       # nothing set: no buffer allocated
+    P.set_boundary_facets(c["ids"])
+    P.set_boundary_flow(traction=c["t"], backflow=c["beta"])
+    assert int(_lib.load().sns_live_device_bytes()) >= before + 8 * 10 * len(c["ids"])
+    P.clear_boundary_terms()
+    assert int(_lib.load().sns_live_device_bytes()) == before
+    P.close()
+    assert int(_lib.load().sns_live_device_bytes()) == base
+
+
+def test_refusals_leave_the_handle_untouched():
+    c = _duct_case(100)
+    m, wd = c["m"], _dev(c["w2"])
+    P = FlowProblem(m, (c["mask"], c["g"]), reynolds=RE)
+    s0 = _system(P, wd)
+
+    def same_bits(ref):
+        return all(torch.equal(a, b) for a, b in zip(ref, _system(P, wd)))
+
+    for call in (lambda: P.lib.sns_set_boundary_flow(P.h, wd.data_ptr(), None), lambda: P.lib.sns_set_boundary_scalar(P.h, wd.data_ptr(), None)):
+        assert call() == -3 and "set the boundary facets first" in P.lib.sns_last_error().decode()      # data before facets
+    assert same_bits(s0)
+    # facets the host lists refuse: a wrong owner, a facet twice
+    fn = np.ascontiguousarray(c["facets"], dtype=np.int32)
+    own = np.ascontiguousarray(c["own"], dtype=np.int64)
+    wrong = own.copy()
+    wrong[2] = next(t for t in range(m.num_tets) if not np.isin(fn[2], m.tets[t]).all())
+    assert P.lib.sns_set_boundary_facets(P.h, len(fn), fn.ctypes.data, wrong.ctypes.data) == -4
+    assert "sns_set_boundary_facets" in P.lib.sns_last_error().decode()
+    twice, own2 = np.ascontiguousarray(np.concatenate([fn, fn[:1]])), np.concatenate([own, own[:1]])
+    assert P.lib.sns_set_boundary_facets(P.h, len(twice), twice.ctypes.data, own2.ctypes.data) == -4
+    assert P.lib.sns_set_boundary_facets(P.h, -1, None, None) == -1 and P.lib.sns_set_boundary_facets(P.h, 3, None, None) == -1
+    assert same_bits(s0)
+    P.set_boundary_facets(c["ids"])
+    P.set_boundary_flow(traction=c["t"], backflow=c["beta"])
+    s1 = _system(P, wd)
+    assert P.lib.sns_set_boundary_facets(P.h, len(fn), fn.ctypes.data, wrong.ctypes.data) == -4      # the facets in force stay
+    for bad in (-1e-300, float("nan"), float("inf")):               # one bad entry among good ones
+        x = c["beta"].copy()
+        x[len(x) // 2] = bad
+        with pytest.raises(SnsError) as e:
+            P.set_boundary_flow(traction=c["t"], backflow=x)
+        assert e.value.code == -1 and "sns_set_boundary_flow" in str(e.value), bad
+        a = np.ones((len(c["ids"]), 4))
+        a[1, 2] = bad
+        with pytest.raises(SnsError) as e:
+            P.set_boundary_scalar(alpha=a)
+        assert e.value.code == -1 and "sns_set_boundary_scalar" in str(e.value), bad
+        assert same_bits(s1), bad
+    with pytest.raises(SnsError) as e:                              # the mesh derivative of the facet terms is not built
+        P.residual_shape_gradient(wd, wd)
+    assert e.value.code == -3 and "boundary traction or backflow" in str(e.value) and same_bits(s1)
+    P.set_boundary_flow()
+    P.set_boundary_scalar(alpha=np.ones(4))                         # (scalar data does not stand in the shape gradient's way)
+    P.residual_shape_gradient(wd, wd)
+    P.close()
+    # 2-D handles
+    m2 = M2.dfg_2d_mesh(0.5)
+    P2 = FlowProblem(m2, M2.dfg2d_bcs(m2).flatten(), reynolds=100.0)
+    with pytest.raises(SnsError) as e:
+        P2.set_boundary_facets([0])
+    assert e.value.code == -1 and "3-D handles only" in str(e.value)
+    assert P2.lib.sns_set_boundary_flow(P2.h, None, None) == -1 and P2.lib.sns_set_boundary_scalar(P2.h, None, None) == -1
+    P2.close()
+    # a handle with an owned / ghost split attached (no transport needed): SNS_E_STATE
+    from stabilized_navier_stokes_flow_fenicsx_amd import partition as PT
+    part = PT.build_local_part(m, c["mask"], c["g"], PT.rcb_partition(m.points, 2), 0, 2)
+    R = FlowProblem(part.mesh, (part.bc_mask, part.bc_val), part=part, group="local-only", reynolds=RE)
+    assert R.lib.sns_set_boundary_facets(R.h, 0, None, None) == -3
+    assert "not with a communicator attached" in R.lib.sns_last_error().decode()
+    assert R.lib.sns_set_boundary_flow(R.h, None, None) == -3 and R.lib.sns_set_boundary_scalar(R.h, None, None) == -3
+    R.close()
+
+
+def test_a_changed_beta_is_another_operator_a_changed_t_is_not():
+    """The second set-up of a handle takes the levels' spectral estimates again only for another operator (policy::OperatorKey):
+    after another beta the dampings are those of a fresh handle put directly into that state, as tests/test_gpu_form_state.py
+    reads them; another t with the same beta does not even make the preconditioner stale."""
+    m = M.duct_mesh(cells=(6, 3, 3))
+    mask, g = B.duct_bcs(m, (-1.0, 0.0, 0.0)).flatten()             # (driven backwards: the outlet's backflow term is active)
+    rng = np.random.default_rng(101)
+    outlet = m.find(m.meta["tags"]["outlet"])
+    t1, t2 = rng.normal(size=(2, len(outlet), 3, 3))
+    b = _dev(rng.standard_normal(m.num_dofs))
+
+    def handle(beta):
+        P = FlowProblem(m, (mask, g), reynolds=50.0)
+        P.set_boundary_facets(outlet)
+        P.set_boundary_flow(traction=t1, backflow=beta)
+        return P
+
+    P = handle(0.5)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    P.jacobian(U, "ns")
+    x, res = P.krylov_solve(b)
+    om1, ms1 = tuple(L["omega"] for L in P.hierarchy()), P.timings().pc_setup_ms
+    assert res.reason > 0 and len(om1) >= 2
+    P.set_boundary_flow(traction=t2, backflow=0.5)                  # another t: no operator changes
+    x, res = P.krylov_solve(b)
+    assert res.reason > 0 and P.timings().pc_setup_ms == ms1        # (no set-up ran)
+    P.set_boundary_flow(traction=t2, backflow=400.0)                # another beta
+    P.jacobian(U, "ns")
+    x, res = P.krylov_solve(b)
+    om2 = tuple(L["omega"] for L in P.hierarchy())
+    assert res.reason > 0 and P.timings().pc_setup_ms > ms1
+    fresh = handle(400.0)
+    fresh.jacobian(U, "ns")
+    xf, rf = fresh.krylov_solve(b)
+    omf = tuple(L["omega"] for L in fresh.hierarchy())
+    print(f"dampings: beta 0.5 {om1}, walked to beta 400 {om2}, fresh at beta 400 {omf}; its {res.its} / {rf.its}")
+    assert om2 == omf and res.its == rf.its and rel(x.cpu().numpy(), xf.cpu().numpy()) < 1e-6
+    assert om1 != omf                                               # (the check has teeth: a stale estimate would show)
+    fresh.close()
+    P.close()
