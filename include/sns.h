@@ -208,7 +208,7 @@ typedef struct {
                                stream, no staging copies.  0 = put + wait / unpack into the vector's ghost tail, then the passes of
                                round 4 (the RCCL transport always works that way, with pack + send / recv + unpack) */
     /* (retired in round 5, VERDICT r4 item 6: amg_fine_cycle -- the experimental V(0,1) / V(1,0) fine-level cycles, never the default
-       and untested since round 3 --, amg_growth_check -- its value 1 is the rule now, csrc/sns_setup.hip) */
+       and untested since round 3 --, amg_growth_check -- its value 1 is the rule now, csrc/sns_policy.h takes_growth_check) */
     int    amg_exact_sweeps; /* (round 5) 1 (default): on the window transports the aggregate-block-smoothed PARTITIONED levels >= 1 run
                                the single-GPU schedule (level 1: 1 + (amg_bnu_l1 + 1) sweeps, the coarse-grid correction inside the
                                first post-sweep) with EXACT global sweeps -- a flag wait per sweep, the put rides in the kernel that

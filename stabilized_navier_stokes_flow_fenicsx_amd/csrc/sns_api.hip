@@ -1,7 +1,7 @@
 // C-ABI layer (include/sns.h): handle life cycle, communicator attachment, the entry points of the hot path (residual /
 // Jacobian / SpMV / preconditioner / Krylov / Stokes / Newton) and the introspection getters.  Host code only launches kernels
-// and moves scalars; there is no CPU compute path.  (The setup, cycle and Krylov parts live in csrc/sns_setup.hip, sns_cycle.hip
-// and sns_krylov.hip; shared internals in csrc/sns_ctx.h; the hierarchy's policy in csrc/sns_policy.h.)  The handle owns its
+// and moves scalars; there is no CPU compute path.  (The setup, cycle and Krylov parts live in csrc/sns_setup.hip, sns_damping.hip,
+// sns_cycle.hip and sns_krylov.hip; shared internals in csrc/sns_ctx.h; the hierarchy's policy in csrc/sns_policy.h.)  The handle owns its
 // device memory and HIP objects by type (csrc/sns_devbuf.h): sns_destroy is `delete h`, and a failing create frees what it made.
 #include <atomic>
 
@@ -338,11 +338,7 @@ int sns_set_options(sns_handle h, const sns_options* o) {
                                         (o->amg_fused_post != h->opt.amg_fused_post) || (o->amg_f32_matrix != h->opt.amg_f32_matrix) ||
                                         (o->pc_type != h->opt.pc_type);
     h->opt = *o;
-    if (h->damping_backoff != 1.0) {                 // a retry's stronger damping does not outlive an options call
-        h->damping_backoff = 1.0;
-        h->pc_ready = false;
-        for (auto& L : h->levels) { L.lambda_max = 0.0; L.omega_checked = 0.0; L.ritz_limit = 0.0; }
-    }
+    damping_reset(h, DampingReset::AFTER_RETRY);      // a retry's stronger damping does not outlive an options call
     if (sweep_exchange_changed) {
         // rank-local sweeps rely on ghost tails that are never written (zero); sweeps with exchanges fill them
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -355,8 +351,7 @@ int sns_set_options(sns_handle h, const sns_options* o) {
     }
     h->plan = policy::plan_cycle(h->opt, h->facts);         // (the stored facts: no communication)
     if (pc_changed || damping_changed || plan_buffer_missing(h)) h->pc_ready = false;
-    if (damping_changed || pc_changed)
-        for (auto& L : h->levels) { L.lambda_max = 0.0; L.omega_checked = 0.0; L.ritz_limit = 0.0; }   // re-estimate and re-verify
+    if (damping_changed || pc_changed) damping_reset(h, DampingReset::ESTIMATES);   // re-estimate and re-verify
     return SNS_OK;
 }
 
@@ -992,7 +987,7 @@ int sns_get_hierarchy(sns_handle h, int32_t* nlevels, int64_t rows[16], int64_t 
         if (rows) rows[l] = L.n_owned;
         if (blocks) blocks[l] = L.nnzb;
         if (sweeps) sweeps[l] = l + 1 < (int)h->levels.size() ? h->plan.level[(size_t)l].nu : 0;   // the coarsest level is a dense inverse
-        if (omega) omega[l] = L.omega;
+        if (omega) omega[l] = L.damping.omega;
     }
     return SNS_OK;
 }

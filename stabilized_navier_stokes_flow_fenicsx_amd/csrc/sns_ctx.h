@@ -208,7 +208,8 @@ struct sns_ctx {
     bool first_sweep_done = false;                   // the V-cycle's fine-level first sweep was done by the Krylov kernel that wrote its input
     bool r3_estimates = false;                       // SNS_R3_SPECTRAL_ESTIMATE (tests of the retry path): round 3's policy -- spectral
                                                      // estimates every 4th setup whatever the operator (first Jacobians on the Stokes estimate)
-    double damping_backoff = 1.0;                    // < 1 after a failed AMG-preconditioned solve: all level dampings scaled (krylov())
+    double damping_backoff = 1.0;                    // < 1 after a failed AMG-preconditioned solve: all level dampings scaled
+                                                     // (damping_back_off, csrc/sns_damping.hip; back to 1 by damping_reset)
     int64_t ctr_retries = 0;                         // damping retries since sns_reset_timings
     int last_first_reason = 0;                       // reason of the FIRST attempt of the last solve (0 = no retry happened)
     // what the V-cycle runs (csrc/sns_policy.h): the hierarchy's structure, agreed over the ranks when it is built, and the plan the
@@ -261,6 +262,12 @@ int plan_hierarchy(sns_ctx* h);
 const char* plan_buffer_missing(const sns_ctx* h);
 int build_hierarchy(sns_ctx* h, const HostPattern& fine);
 int pc_setup(sns_ctx* h);
+// csrc/sns_damping.hip: the three transitions of the damping state (Level::damping, damping_backoff) -- decide: level l of nl at
+// a set-up, with the spectral estimates that are due; back off: after a retryable failure of a solve; reset: an options call
+enum class DampingReset { AFTER_RETRY /* only where a retry scaled the dampings: the factor too, and pc_ready */, ESTIMATES };
+int damping_decide(sns_ctx* h, int l, int nl, bool new_operator);
+void damping_back_off(sns_ctx* h);
+void damping_reset(sns_ctx* h, DampingReset what);
 // The workspace vectors h->kv (4*n doubles each, allocated in slot order up to the slot asked for).  VEC_SCRATCH serves the lifting's
 // BC defect, the snapped 2-D Stokes state, sns_time_step's BDF history, the moments' zero state and the zero vector of the three
 // spectral estimates.  What makes the sharing sound: every user writes the whole range it reads before reading it, and none

@@ -15,7 +15,7 @@ int coarse_cycle(sns_ctx* h, int l, const double* b, double* x) {
     // signature: the graph level, whether its first sweeps are done outside the graph, every omega, the plan rows from the level
     // above the graph down
     std::vector<double> sig = {(double)gl, (double)h->plan.rep_gather_first};
-    for (auto& L : h->levels) sig.push_back(L.omega);
+    for (auto& L : h->levels) sig.push_back(L.damping.omega);
     const std::vector<policy::LevelPlan> rows(h->plan.level.begin() + (gl - 1), h->plan.level.end());
     if (!h->coarse_graph || sig != h->graph_sig || rows != h->graph_rows) {
         h->coarse_graph.reset();
@@ -78,7 +78,7 @@ static void launch_restrict(sns_ctx* h, int l, bool fused, const double* x, cons
                     const LpMat A = lp_mat<F>(L);
                     hipLaunchKernelGGL((k_resid_restrict<F, M, G>), dim3(grid), dim3(256), 0, h->stream, C.n_owned, n_slots, slots,
                                        L.m_ptr, L.m_idx, L.free_mask, L.rowptr, L.colind, A.vals, A.scale, x, b, L.r, cb, dc,
-                                       (const void*)C.binv32, C.omega, zc, gs ? *gs : GhostSrc(), agp, pd);
+                                       (const void*)C.binv32, C.damping.omega, zc, gs ? *gs : GhostSrc(), agp, pd);
                 });
             });
         });
@@ -87,11 +87,11 @@ static void launch_restrict(sns_ctx* h, int l, bool fused, const double* x, cons
         const int32_t ns = 8 * C.n_blk;
         with_fmt(C.binv_fmt, [&](auto F) {
             hipLaunchKernelGGL((k_restrict_blk<F>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows, L.m_ptr,
-                               L.m_idx, L.free_mask, L.r, cb, (const void*)C.binv32, C.omega, zc, pd);
+                               L.m_idx, L.free_mask, L.r, cb, (const void*)C.binv32, C.damping.omega, zc, pd);
         });
     } else {
         hipLaunchKernelGGL(k_restrict, dim3((unsigned)((4 * (int64_t)C.n_owned + 255) / 256)), dim3(256), 0, h->stream,
-                           C.n_owned, L.m_ptr, L.m_idx, L.free_mask, L.r, cb, dc, C.omega, zc);
+                           C.n_owned, L.m_ptr, L.m_idx, L.free_mask, L.r, cb, dc, C.damping.omega, zc);
     }
 }
 
@@ -113,13 +113,13 @@ static void launch_post(sns_ctx* h, int l, const double* xc, const double* xc_ow
             dispatch<1, 0>(g.win[0] != nullptr, [&](auto G) {
                 hipLaunchKernelGGL((k_bpost<F, G>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L.blk_rows,
                                    L.ap_rowptr, apc, M.vals, M.scale, (const void*)L.binv32, xc, xc_own, x, (const double*)L.r,
-                                   L.omega, L.agg, L.free_mask, y, g, pd);
+                                   L.damping.omega, L.agg, L.free_mask, y, g, pd);
             });
         } else {
             // (nodal blocks: FINE 1 the fine level, 0 a coarse one, 2 the fine level of the window form)
             dispatch<2, 1, 0>(gc ? 2 : l == 0 ? 1 : 0, [&](auto FINE) {
                 hipLaunchKernelGGL((k_post_lp<F, FINE>), dim3((rows + 63) / 64), dim3(256), 0, h->stream, rows, L.ap_rowptr, apc,
-                                   M.vals, M.scale, xc, x, (const double*)L.r, L.dinv32, L.omega, L.agg, L.free_mask, y, g);
+                                   M.vals, M.scale, xc, x, (const double*)L.r, L.dinv32, L.damping.omega, L.agg, L.free_mask, y, g);
             });
         }
     });
@@ -142,7 +142,7 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     const policy::LevelPlan& Q = h->plan.level[(size_t)l];
     const policy::LevelPlan& QC = h->plan.level[(size_t)l + 1];
     const int32_t rows = L.n_owned;
-    const double om = L.omega;
+    const double om = L.damping.omega;
     const int nu_pre = Q.pre, nu_post = Q.post;
     double* cur = Q.start_odd ? h->pong[l] : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
     double* oth = (cur == x) ? h->pong[l] : x;
@@ -255,7 +255,7 @@ static int enter_replicated_tail(sns_ctx* h, int l, const double* b, double* x) 
         double* zc = h->plan.level[(size_t)h->rep_level].start_odd ? h->pong[h->rep_level] : C.x;
         with_fmt(C.binv_fmt, [&](auto F) {
             hipLaunchKernelGGL((k_bfirst_gather<F>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
-                               (const void*)C.binv32, C.omega, zc, C.b, h->rep_rowmap, comm_ag_get(cm));
+                               (const void*)C.binv32, C.damping.omega, zc, C.b, h->rep_rowmap, comm_ag_get(cm));
         });
     } else if (cm->windows() && h->opt.halo_windows && h->rep_doff &&
         (size_t)4 * h->rep_maxn * (size_t)cm->nranks <= cm->peer->ag_doubles) {
@@ -304,9 +304,9 @@ static int solve_last_level(sns_ctx* h, int l, const double* b, double* x) {
     double* oth = h->pong[l];
     if (rows == 0) return SNS_OK;
     hipLaunchKernelGGL(k_bjacobi, dim3((unsigned)((4 * (int64_t)rows + 255) / 256)), dim3(256), 0, h->stream, rows, L.dinv, b,
-                       L.omega, cur);
+                       L.damping.omega, cur);
     for (int s = 0; s < 8; ++s) {       // even count: result ends in x
-        launch_pc_spmv<SPMV_JACOBI>(h, L, h->plan.level[(size_t)l].lp_fmt, rows, cur, oth, b, L.omega);
+        launch_pc_spmv<SPMV_JACOBI>(h, L, h->plan.level[(size_t)l].lp_fmt, rows, cur, oth, b, L.damping.omega);
         std::swap(cur, oth);
     }
     return SNS_OK;
@@ -322,7 +322,7 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     Level& L = h->levels[l];
     Level& C = h->levels[l + 1];
     const int32_t rows = L.n_owned;
-    const double om = L.omega;
+    const double om = L.damping.omega;
     const int nu = Q.nu, nu_pre = Q.pre, nu_post = Q.post;
     double* cur = Q.start_odd ? h->pong[l] : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
     double* oth = (cur == x) ? h->pong[l] : x;

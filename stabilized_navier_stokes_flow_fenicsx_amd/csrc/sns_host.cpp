@@ -818,7 +818,7 @@ extern "C" int sns_host_boundary_rows(int32_t n_owned, const int32_t* rowptr, co
 
 // Eigenvalues of a small real upper-Hessenberg matrix (row-major n x n; entries below the first subdiagonal are ignored): shifted
 // QR with Givens rotations in complex arithmetic (Wilkinson shift, deflation, an exceptional shift every 10th sweep).  Serves the
-// Ritz values of the short Arnoldi process that bounds the smoother damping (sns_api.hip: arnoldi_ritz); n <= 32.
+// Ritz values of the short Arnoldi process that bounds the smoother damping (sns_damping.hip: arnoldi_ritz); n <= 32.
 extern "C" int sns_host_hessenberg_eigs(int n, const double* H, double* re, double* im) {
     if (n <= 0 || n > 32 || !H || !re || !im) return SNS_E_ARG;
     typedef std::complex<double> cd;

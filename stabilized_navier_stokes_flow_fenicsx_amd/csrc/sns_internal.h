@@ -7,6 +7,7 @@
 
 #include "sns.h"
 #include "sns_devbuf.h"
+#include "sns_policy.h"
 
 namespace sns {
 
@@ -114,11 +115,9 @@ struct Level {
     int dense_np = 0;
     DevBuf<double> dense_gj, dense_work;
     DevBuf<float> dense_x32;
-    // block-Jacobi damping actually used on this level (<= amg_omega, limited by 4/(3 |lambda|max(Dinv A)))
-    double omega = 0.8;
-    double lambda_max = 0.0;
-    double omega_checked = 0.0;          // damping that passed the growth test at the last fresh estimate
-    double ritz_limit = 0.0;             // stability limit of the damping from the Ritz values of S A (amg_ritz_limit; 0 = not estimated)
+    // block-Jacobi damping actually used on this level (damping.omega) and the estimates behind it; written by the three
+    // transitions of csrc/sns_damping.hip only
+    policy::LevelDamping damping;
 };
 
 void aggregate_nodes(const HostPattern& F, int32_t n_active, int max_agg, std::vector<int32_t>& agg, int32_t& nc,

@@ -68,12 +68,12 @@ static void bicg_update(sns_ctx* h, double* zdst, const double* sc, const double
         h->first_put_carried = pd0.sr_ptr != nullptr;
         with_fmt(L0.binv_fmt, [&](auto F) {
             hipLaunchKernelGGL((k_bfirst_bicg<F, OP>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L0.blk_rows,
-                               (const void*)L0.binv32, L0.omega, z1, sc, ph, sh, t, v, x, r, p, s, pd0);
+                               (const void*)L0.binv32, L0.damping.omega, z1, sc, ph, sh, t, v, x, r, p, s, pd0);
         });
     } else if (OP == 1) {
-        hipLaunchKernelGGL(k_bicg_s_first, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, s, L0.dinv32, L0.omega, z1);
+        hipLaunchKernelGGL(k_bicg_s_first, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, s, L0.dinv32, L0.damping.omega, z1);
     } else {
-        hipLaunchKernelGGL(k_bicg_xrp_first, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, v, x, r, p, L0.dinv32, L0.omega,
+        hipLaunchKernelGGL(k_bicg_xrp_first, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, v, x, r, p, L0.dinv32, L0.damping.omega,
                            z1);
     }
     h->first_sweep_done = true;
@@ -417,7 +417,8 @@ int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double
     h->ctr_host_syncs = h->ctr_allreduce = h->ctr_exchange = 0;
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     // A solve that BREAKS DOWN (or produces NaN/Inf) under the AMG preconditioner is retried ONCE, from the same initial
-    // guess, with every level's block-Jacobi damping scaled by 0.7 (opt.amg_retry_damping, default on): the damping
+    // guess, with every level's block-Jacobi damping backed off (damping_back_off, csrc/sns_damping.hip: policy::RETRY_FACTOR, no
+    // retry at or below policy::RETRY_FLOOR; opt.amg_retry_damping, default on): the damping
     // estimate (|lambda|max of Dinv A + a growth check on the dominant mode) is not a bound for a non-symmetric
     // operator, and at cell Reynolds numbers of 5-10 a slightly over-relaxed smoother is what breaks BiCGStab down
     // (measured: jittered 648 k-tet duct, Re 200: auto damping fails after 218 iterations, 0.7 x converges).  A solve
@@ -427,7 +428,7 @@ int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double
     // breakdown -- when its best residual has not halved for amg_retry_stall_its (100) iterations.  The smaller damping is kept for the later Jacobians of the handle until sns_set_options is called; the
     // retry count and the current factor are visible through sns_get_counters.  *its is the sum over both attempts
     // (<= 2 ksp_max_it).  Not in the reference; converging solves never see it.
-    const bool can_retry = h->opt.pc_type == SNS_PC_AMG && h->opt.amg_retry_damping != 0 && h->damping_backoff > 0.4;
+    const bool can_retry = policy::retry_offered(h->opt, h->damping_backoff);
     double* x0 = nullptr;
     if (can_retry) {
         SNS_TRY(get_vec(h, VEC_SAVED_GUESS, &x0));
@@ -444,19 +445,13 @@ int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double
         else { set_error("bad ksp_type"); return SNS_E_ARG; }
         SNS_TRY(rc);
         its_total += *its;
-        const bool retryable = *reason == SNS_KSP_DIVERGED_BREAKDOWN || *reason == SNS_KSP_DIVERGED_NANORINF ||
-                               *reason == SNS_KSP_STALLED;
-        if (!retryable || !can_retry || attempt == 1) break;
+        if (!policy::retryable(*reason) || !can_retry || attempt == 1) break;
         h->last_first_reason = *reason;
         ++h->ctr_retries;
-        h->damping_backoff *= 0.7;
+        damping_back_off(h);
         if (h->opt.monitor)
             std::printf("  KSP failed (reason %d after %d iterations): retrying with the smoother damping scaled by %.2f\n",
                         *reason, *its, h->damping_backoff);
-        for (auto& L : h->levels) {
-            L.omega *= 0.7;
-            if (L.omega_checked > 0.0) L.omega_checked *= 0.7;
-        }
         HIP_TRY(hipMemcpyAsync(x, x0, nred_of(h) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     }
     *its = its_total;

@@ -6,7 +6,8 @@
 // The handle-side predicates of csrc/sns_cycle.hip / sns_setup.hip gather the facts and ask here; the numbers live nowhere else.
 // In the same idiom, at the end: the route of an assembly (plan_assembly, tests/assembly_plan_main.cpp), what a handle's form
 // state allows (check_form_request, tests/form_request_main.cpp) and what it allows of the boundary terms (check_boundary_request,
-// tests/boundary_request_main.cpp), which operator is a new one (OperatorKey, tests/operator_key_main.cpp).
+// tests/boundary_request_main.cpp), which operator is a new one (OperatorKey, tests/operator_key_main.cpp), the damping of a
+// level's smoother (LevelDamping, tests/damping_policy_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -442,7 +443,7 @@ inline FormVerdict check_boundary_request(BoundaryRequest request, const Boundar
     return {};
 }
 
-// ---- which operator is it? (the spectral estimates of csrc/sns_setup.hip; the cases are in DESIGN.md) -----------------------------
+// ---- which operator is it? (the spectral estimates of csrc/sns_damping.hip; the cases are in DESIGN.md) -----------------------------
 // What the fine operator's values depend on beside the state: the form's share (FormKey: time term, viscosity law, and a counter
 // that moves whenever the viscosity field is written or cleared, another that moves whenever a boundary coefficient -- the
 // backflow beta, the Robin alpha -- is written or cleared) and the call's (the form id, the Reynolds number, the six
@@ -482,6 +483,67 @@ inline void stamp_operator(OperatorKey& k, int form, double reynolds, const Form
 inline bool new_operator(const OperatorKey& matrix, const OperatorKey& estimated, bool r3_estimates) {
     return !r3_estimates && !(matrix == estimated);
 }
+
+// ---- smoother damping (the transitions are in csrc/sns_damping.hip; the rule is in DESIGN.md, "Damping state") ---------------------
+// A level's damped block-Jacobi sweep x += w S (b - A x) and what its w was derived from: |lambda|max of S A (0: no estimate),
+// the stability limit of the dominant Ritz values (0: not estimated), the damping that passed the growth check at the last
+// fresh estimate (0: none).  The handle adds the factor of the retries (damping_backoff) and the count of set-ups (pc_setups).
+struct LevelDamping {
+    double omega = 0.8, lambda_max = 0.0, omega_checked = 0.0, ritz_limit = 0.0;
+};
+constexpr int ESTIMATE_EVERY = 4;                          // the spectrum moves little between the Jacobians of one Newton sequence
+constexpr double LAMBDA_CAP = 4.0 / 3.0;                   // w <= 4 / (3 |lambda|max), the smoothing-optimal damping
+constexpr int COMPOUNDING_SWEEPS = 3;                      // sweeps per cycle from which a level compounds an amplified mode
+constexpr double GROWTH_BOUND = 0.9;                       // a sweep must contract the dominant mode by >= 10 % ...
+constexpr double GROWTH_STEP = GROWTH_BOUND;               // ... and every trial that does not scales the damping by as much,
+constexpr int GROWTH_TRIALS = 6;                           // this many times at the most
+constexpr double RETRY_FACTOR = 0.7, RETRY_FLOOR = 0.4;    // a retry scales every damping; none is offered at or below the floor
+
+// the estimates of a level are taken at this set-up: it has none, every ESTIMATE_EVERY-th set-up, a new operator
+inline bool estimates_due(bool has_estimate, int pc_setups, bool new_operator) {
+    return !has_estimate || pc_setups % ESTIMATE_EVERY == 0 || new_operator;
+}
+// levels that run COMPOUNDING_SWEEPS or more sweeps per cycle and are not the last: the Ritz limit (amg_ritz_limit) and the growth check
+inline bool takes_growth_check(bool not_last, int sweeps_per_cycle) { return not_last && sweeps_per_cycle >= COMPOUNDING_SWEEPS; }
+inline bool takes_ritz_limit(const sns_options& o, bool not_last, int sweeps_per_cycle) {
+    return o.amg_ritz_limit && takes_growth_check(not_last, sweeps_per_cycle);
+}
+// the damping before the growth check: amg_omega, capped by |lambda|max where there is an estimate and by the Ritz limit where
+// the level takes one, each times the factor of the retries
+inline double capped_damping(double amg_omega, double backoff, double lambda_max, bool ritz, double ritz_limit) {
+    double w = amg_omega * backoff;
+    if (lambda_max > 0.0) w = std::min(amg_omega, LAMBDA_CAP / lambda_max) * backoff;
+    if (ritz && ritz_limit > 0.0) w = std::min(w, ritz_limit * backoff);
+    return w;
+}
+// the growth check: `growth(w, &g)` measures the growth per sweep of the dominant mode under w (an error code: passed on)
+template <class Growth>
+inline int checked_damping(double& w, Growth&& growth) {
+    for (int trial = 0; trial < GROWTH_TRIALS; ++trial) {
+        double g = 0.0;
+        if (const int rc = growth(w, &g)) return rc;
+        if (g < GROWTH_BOUND) break;
+        w *= GROWTH_STEP;
+    }
+    return SNS_OK;
+}
+// between fresh estimates a level stays at or below the damping that passed
+inline double held_damping(double w, double omega_checked) { return omega_checked > 0.0 ? std::min(w, omega_checked) : w; }
+// the retry of a failed solve: which reasons, whether one is offered, and what it does to the factor and to a level -- the
+// stored values are scaled in place, not derived again from the factor (two retries: (w 0.7) 0.7, not w 0.49)
+inline bool retryable(int reason) {
+    return reason == SNS_KSP_DIVERGED_BREAKDOWN || reason == SNS_KSP_DIVERGED_NANORINF || reason == SNS_KSP_STALLED;
+}
+inline bool retry_offered(const sns_options& o, double backoff) {
+    return o.pc_type == SNS_PC_AMG && o.amg_retry_damping != 0 && backoff > RETRY_FLOOR;
+}
+inline void back_off(double& backoff) { backoff *= RETRY_FACTOR; }
+inline void back_off(LevelDamping& d) {
+    d.omega *= RETRY_FACTOR;
+    if (d.omega_checked > 0.0) d.omega_checked *= RETRY_FACTOR;
+}
+// an options call: every estimate is taken and verified again (omega itself is rewritten by the next set-up)
+inline void forget_estimates(LevelDamping& d) { d.lambda_max = d.omega_checked = d.ritz_limit = 0.0; }
 
 }  // namespace policy
 }  // namespace sns

@@ -1,5 +1,5 @@
-// Setup side of the C-ABI layer: the symbolic AMG hierarchy (aggregation, halo plans per level, replicated tail), the spectral
-// estimates of the smoother damping, the numeric setup of the preconditioner and the workspace vectors.
+// Setup side of the C-ABI layer: the symbolic AMG hierarchy (aggregation, halo plans per level, replicated tail), the numeric
+// setup of the preconditioner as a list of stages and the workspace vectors.  (The smoother damping: csrc/sns_damping.hip.)
 // (shared internals in csrc/sns_ctx.h)
 #include "sns_ctx.h"
 
@@ -664,183 +664,167 @@ int plan_hierarchy(sns_ctx* h) {
 }
 
 
-// |lambda|max of Dinv*A on level l by a few power iterations (device resident; one host sync).
-// The damped block-Jacobi smoother x += w Dinv (b - A x) needs w*|lambda|max < 2; on the reference's
-// operator the fixed w = 0.9 already diverges at 10 M tets, so w is capped per level at the smoothing-optimal 4/(3 |lambda|max).  (Measured cliff on the coarse
-// levels of the 10 M-tet Jacobian: w = 0.80 converges in 45 iterations, w >= 0.82 overflows, although the
-// dominant mode itself is still damped there -- the offending mode is not the one of largest modulus.)
-int estimate_lambda_max(sns_ctx* h, int l, double* out) {
-    Level& L = h->levels[l];
-    const policy::LevelPlan& P = h->plan.level[(size_t)l];
+// ---- the stages of the numeric set-up: what pc_setup refreshes per level, in the order it calls them -----------------------------
+// the level above the replicated tail is only the source of the copy: all-gather my rows' blocks, scatter them into place
+static int refresh_replicated_source(sns_ctx* h, const Level& L) {
+    Level& C = h->levels[h->rep_level];
+    if (L.nnzb > 0)
+        HIP_TRY(hipMemcpyAsync(h->rep_vsend, L.vals, (size_t)L.nnzb * 16 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    SNS_TRY(comm_allgather(h->comm.get(), h->rep_vsend, h->rep_vrecv, (int)(h->rep_maxnz * 16), h->stream));
+    const int64_t nsrc = h->rep_maxnz * h->comm->nranks;
+    hipLaunchKernelGGL(k_scatter_blocks, dim3((unsigned)((nsrc * 8 + 255) / 256)), dim3(256), 0, h->stream, nsrc, h->rep_valmap,
+                       h->rep_vrecv, C.vals);
+    return SNS_OK;
+}
+
+// the smoother's inverses: the nodal D^-1 and, where the plan smooths with them, the aggregates' inverse diagonal blocks
+static int refresh_smoother_inverses(sns_ctx* h, const policy::LevelPlan& P, Level& L) {
     const int32_t rows = L.n_owned;
-    const int64_t nd = 4 * (int64_t)rows;
-    const int g = vec_grid(nd), g4 = (int)((nd + 255) / 256);
-    double* x = h->pong[l];
-    double* y = L.r;
-    double* z = L.x;
-    // deterministic start vector with all frequencies: x_i = 1 + (i*2654435761 mod 1024)/1024 via axpby on an iota is
-    // overkill; use b of the last solve if any, else the diagonal-inverse row sums: simplest robust choice = all ones
-    if (rows > 0) hipLaunchKernelGGL(k_fill_pattern, dim3(g), dim3(256), 0, h->stream, nd, x);
-    double* zero = nullptr;
-    if (P.lp_fmt != 0) {
-        SNS_TRY(get_vec(h, VEC_SCRATCH, &zero));                  // level sizes never exceed the fine level
-        if (nd > 0) HIP_TRY(hipMemsetAsync(zero, 0, nd * sizeof(double), h->stream));
+    if (rows > 0) hipLaunchKernelGGL(k_dinv, dim3((rows + 255) / 256), dim3(256), 0, h->stream, rows, L.diag, L.vals, L.dinv);
+    if (!P.blocks) return SNS_OK;
+    // from the fp64 operator (what the nodal D^-1 is to the point smoother), in the format of the level's matrix copy (fp32, or
+    // fp16 with row scales: half the bytes of a block sweep's extra stream)
+    const int bf = h->opt.amg_f32_matrix == 2 ? 2 : 1;
+    if (!L.binv32 || L.binv_fmt != bf) {
+        SNS_TRY(L.binv32.alloc(binv_bytes_per_block(bf) * (size_t)std::max(1, L.n_blk)));
+        L.binv_fmt = bf;
     }
-    double lam = 0.0;
-    const int iters = 12;
-    // distributed levels whose sweeps see exchanged ghost values are damped for the GLOBAL operator; purely
-    // rank-local sweeps (ghost values zero) for the rank-local one
-    const bool glob = P.ghost_sweeps();
-    for (int it = 0; it < iters; ++it) {
-        if (glob) SNS_TRY(exchange_level(h, l, x));
-        // the spectrum of the matrix the sweeps actually read: with a low-precision copy y = 0 - A~ x (the sign does not
-        // matter to ||Dinv A x||), half the bytes of the fp64 pass
-        if (P.lp_fmt != 0 && zero) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, P.lp_fmt, rows, x, y, zero, 0.0);
-        else launch_spmv<SPMV_AX>(h, L, rows, x, y, nullptr, 0.0, nullptr);
+    if (L.n_blk > 0)
+        with_fmt(bf, [&](auto F) {
+            hipLaunchKernelGGL((k_binv<F>), dim3((unsigned)((L.n_blk + 7) / 8)), dim3(256), 0, h->stream, L.n_blk, L.blk_rows,
+                               L.blk_of, L.rowptr, L.colind, L.vals, L.binv32, h->d_sing);
+        });
+    return SNS_OK;
+}
+
+// the low-precision copies the smoother reads: D^-1 as fp32, the operator as fp16 (with the fp16 M = A P of a level that has
+// one) or as fp32
+static int refresh_low_precision_copies(sns_ctx* h, const policy::LevelPlan& P, Level& L, bool not_last) {
+    if (P.lp_fmt == 0) return SNS_OK;
+    const int32_t rows = L.n_owned;
+    if (!L.dinv32) SNS_TRY(L.dinv32.alloc((size_t)16 * std::max(1, L.n)));
+    if (rows > 0)
+        hipLaunchKernelGGL(k_cvt_f32, dim3(vec_grid(16 * (int64_t)rows)), dim3(256), 0, h->stream, 16 * (int64_t)rows, L.dinv,
+                           L.dinv32);
+    if (h->opt.amg_f32_matrix == 2) {
+        if (!L.vals16) {
+            SNS_TRY(L.vals16.alloc(std::max<size_t>(1, (size_t)L.nnzb * 4) * sizeof(uint2)));
+            SNS_TRY(L.scale16.alloc((size_t)4 * std::max(1, L.n)));
+        }
+        // ONE pass over the level's fp64 operator writes its fp16 copy and, where the level has one, the fp16 copy of
+        // M = A P for the fused post-smoothing sweep (k_lp_copies16)
+        const bool with_m = not_last && L.ap_rowptr && L.ap_nib && h->opt.amg_fused_post;
+        if (with_m && !L.ap_vals16) {
+            SNS_TRY(L.ap_vals16.alloc(std::max<size_t>(1, (size_t)L.ap_nnz * 4) * sizeof(uint2)));
+            SNS_TRY(L.ap_scale16.alloc((size_t)4 * std::max(1, L.n)));
+        }
         if (rows > 0) {
-            if (P.blocks) launch_first_sweep(h, P, L, rows, y, 1.0, z);      // the smoother's own blocks
-            else hipLaunchKernelGGL(k_bjacobi, dim3(g4), dim3(256), 0, h->stream, rows, L.dinv, y, 1.0, z);
-            hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, nd, x, z, h->partial);   // (x.z, z.z)
+            const unsigned grid = (unsigned)((rows + 31) / 32);
+            if (with_m)
+                hipLaunchKernelGGL((k_lp_copies16<1>), dim3(grid), dim3(128), 0, h->stream, rows, L.rowptr, L.vals,
+                                   (uint2*)L.vals16.get(), L.scale16, L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.ap_nib, L.agg,
+                                   L.free_mask, (uint2*)L.ap_vals16.get(), L.ap_scale16);
+            else
+                hipLaunchKernelGGL((k_lp_copies16<0>), dim3(grid), dim3(128), 0, h->stream, rows, L.rowptr, L.vals,
+                                   (uint2*)L.vals16.get(), L.scale16, (const int32_t*)nullptr, (const int32_t*)nullptr,
+                                   (const int32_t*)nullptr, (const int32_t*)nullptr, (const uint64_t*)nullptr,
+                                   (const int32_t*)nullptr, (const uint8_t*)nullptr, (uint2*)nullptr, (float*)nullptr);
         }
-        if (glob) SNS_TRY(reduce_to(h, g, 2, h->d_scal + 16 + 2 * it));
-        else reduce_local(h, g, 2, h->d_scal + 16 + 2 * it);
-        // normalise with the device-side norm: x = z / ||z||  (scale read on device)
-        if (rows > 0)
-            hipLaunchKernelGGL(k_scale_by_rsqrt, dim3(g), dim3(256), 0, h->stream, nd, h->d_scal + 16 + 2 * it + 1, z, x);
     }
-    std::vector<double> v(2 * iters);
-    SNS_TRY(fetch(h, h->d_scal + 16, 2 * iters, v.data()));
-    // x was normalised each step, so ||z|| of the last steps estimates |lambda|max; take the max of the tail
-    for (int it = iters - 3; it < iters; ++it) lam = std::max(lam, std::sqrt(v[2 * it + 1]));
-    *out = lam;
+    if (h->opt.amg_f32_matrix != 2) {
+        if (!L.vals32) SNS_TRY(L.vals32.alloc((size_t)L.nnzb * 16));
+        if (L.nnzb > 0)
+            hipLaunchKernelGGL(k_cvt_f32, dim3(vec_grid(L.nnzb * 16)), dim3(256), 0, h->stream, L.nnzb * 16, L.vals, L.vals32);
+    }
     return SNS_OK;
 }
 
-
-// Stability limit of the smoother damping on level l from the dominant Ritz values of S A (S = the level's smoother blocks,
-// nodal or aggregate): M = 8 Arnoldi steps from the deterministic start vector of the power iteration (classical Gram-Schmidt
-// with one re-orthogonalisation, the FGMRES kernels; one host read per step), eigenvalues of the 8 x 8 Hessenberg matrix on the
-// host (sns_host_hessenberg_eigs).  |1 - w theta| < 1 needs w < 2 Re(theta) / |theta|^2: *limit = the minimum over the Ritz
-// values with |theta| >= 0.5 |theta|max (those a few Arnoldi steps have converged to).  The power iteration above sees the
-// modulus only; on a convection-dominated coarse level the dominant eigenvalues are complex, and a level that runs 1 + 6
-// sweeps amplifies a damping above the limit seven times per cycle (oracle/experiments/r4_damping.py).
-int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
-    constexpr int M = 8;
-    Level& L = h->levels[l];
-    const policy::LevelPlan& P = h->plan.level[(size_t)l];
+// numeric part of M = A P, straight into the level's low-precision format (no fp64 copy of M; fp16: written together with the
+// fp16 copy of A above).  (Allocated on a rank without rows too: the plan asks for it on every rank.)
+static int refresh_ap32(sns_ctx* h, const policy::LevelPlan& P, Level& L) {
+    if (!(L.ap_rowptr && h->opt.amg_fused_post && P.lp_fmt == 1)) return SNS_OK;
     const int32_t rows = L.n_owned;
-    const int64_t nd = 4 * (int64_t)rows;
-    *theta_max = 0.0;
-    *limit = 1e30;
-    // levels whose sweeps see exchanged ghost values (plan exact): the GLOBAL operator's Ritz values -- one exchange per Arnoldi
-    // step, the dots summed over the ranks; collective, so every rank goes through it whatever its row count.  (Levels that
-    // exchange per sweep by amg_sweep_exchange_rows / the fine level's single post-sweep: not estimated, as in round 4.)
-    const bool glob = P.exact != 0;
-    if (!glob && (rows <= 0 || P.ghost_sweeps())) return SNS_OK;
-    const int g = std::max(1, vec_grid(nd));           // (a rank without rows on a collective level still launches: empty loops, zero partials)
-    auto reduce = [&](int nred, double* dst) -> int {
-        if (glob) return reduce_to(h, g, nred, dst);
-        reduce_local(h, g, nred, dst);
-        return SNS_OK;
-    };
-    if (h->arn_V.count() < (size_t)(M + 1) * nd) SNS_TRY(h->arn_V.alloc((size_t)(M + 1) * nd));
-    double* V = h->arn_V;
-    double* y = L.r;
-    double* zero = nullptr;
-    double* xin = nullptr;                              // the SpMV input needs the level's full length (ghost tail = 0)
-    SNS_TRY(get_vec(h, VEC_SCRATCH, &zero));
-    SNS_TRY(get_vec(h, VEC_ARNOLDI_IN, &xin));
-    HIP_TRY(hipMemsetAsync(zero, 0, nd * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(xin, 0, 4 * (size_t)L.n * sizeof(double), h->stream));
-    double* sc = h->d_scal + 192;                      // [0, 8) pass-1 coefficients, [8, 16) pass 2, [16, 18) (w.w, w.w)
-    hipLaunchKernelGGL(k_fill_pattern, dim3(g), dim3(256), 0, h->stream, nd, V);
-    hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, nd, V, V, h->partial);
-    SNS_TRY(reduce(2, sc + 16));
-    hipLaunchKernelGGL(k_scale_by_rsqrt, dim3(g), dim3(256), 0, h->stream, nd, sc + 17, V, V);
-    std::vector<double> H((size_t)M * M, 0.0);
-    const bool lp = P.lp_fmt != 0;
-    int m_done = 0;
-    for (int j = 0; j < M; ++j) {
-        double* vj = V + (size_t)j * nd;
-        double* w = V + (size_t)(j + 1) * nd;
-        HIP_TRY(hipMemcpyAsync(xin, vj, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        if (glob) SNS_TRY(exchange_level(h, l, xin));
-        // y = -A~ v (the copy the sweeps read) resp. + A v; w = S A v
-        if (lp) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, P.lp_fmt, rows, xin, y, zero, 0.0);
-        else launch_spmv<SPMV_AX>(h, L, rows, xin, y, nullptr, 0.0, nullptr);
-        launch_first_sweep(h, P, L, rows, y, lp ? -1.0 : 1.0, w);
-        for (int pass = 0; pass < 2; ++pass) {
-            hipLaunchKernelGGL(k_multi_dot8, dim3(g), dim3(256), 0, h->stream, nd, j + 1, V, nd, w, h->partial);
-            SNS_TRY(reduce(8, sc + 8 * pass));
-            hipLaunchKernelGGL(k_multi_axpy8, dim3(g), dim3(256), 0, h->stream, nd, j + 1, V, nd, sc + 8 * pass, -1.0, w,
-                               (double*)nullptr);
-        }
-        hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, nd, w, w, h->partial);
-        SNS_TRY(reduce(2, sc + 16));
-        double v[18];
-        SNS_TRY(fetch(h, sc, 18, v));
-        for (int k = 0; k <= j; ++k) H[(size_t)k * M + j] = v[k] + v[8 + k];
-        m_done = j + 1;
-        const double wn = std::sqrt(std::max(0.0, v[16]));
-        if (!(wn > 1e-12) || j + 1 == M) break;        // invariant subspace (tiny levels) or done
-        H[(size_t)(j + 1) * M + j] = wn;
-        hipLaunchKernelGGL(k_scale_by_rsqrt, dim3(g), dim3(256), 0, h->stream, nd, sc + 17, w, w);
-    }
-    std::vector<double> Hm((size_t)m_done * m_done), re((size_t)m_done), im((size_t)m_done);
-    for (int i = 0; i < m_done; ++i)
-        for (int j = 0; j < m_done; ++j) Hm[(size_t)i * m_done + j] = H[(size_t)i * M + j];
-    if (sns_host_hessenberg_eigs(m_done, Hm.data(), re.data(), im.data()) != SNS_OK) return SNS_OK;
-    double tmax = 0.0;
-    for (int i = 0; i < m_done; ++i) tmax = std::max(tmax, std::hypot(re[i], im[i]));
-    double lim = 1e30;
-    for (int i = 0; i < m_done; ++i) {
-        const double a2 = re[i] * re[i] + im[i] * im[i];
-        if (std::sqrt(a2) < 0.5 * tmax || !(a2 > 0.0)) continue;
-        lim = std::min(lim, 2.0 * std::max(re[i], 0.0) / a2);
-    }
-    *theta_max = tmax;
-    *limit = lim;
+    if (!L.ap_vals32) SNS_TRY(L.ap_vals32.alloc((size_t)L.ap_nnz * 16));
+    if (rows > 0)
+        hipLaunchKernelGGL(k_ap_cvt32, dim3((unsigned)((4 * (int64_t)rows + 255) / 256)), dim3(256), 0, h->stream, rows,
+                           L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.vals, L.agg, L.free_mask, (float4*)L.ap_vals32.get());
     return SNS_OK;
 }
 
+// the Galerkin product: the operator of level l + 1 from level l's
+static void refresh_galerkin(sns_ctx* h, int l) {
+    const Level& L = h->levels[l];
+    Level& C = h->levels[l + 1];
+    const int64_t nth = C.nnzb * 8;
+    hipLaunchKernelGGL(k_galerkin, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, C.nnzb, L.r_ptr, L.r_idx, L.vals,
+                       h->slot_row[l + 1], C.colind, (l == 0) ? h->empty_c[0] : (const uint8_t*)nullptr, L.m_ptr, C.vals);
+}
 
-// Growth factor per sweep of the damped block-Jacobi iteration matrix G_w = I - w Dinv A on the
-// dominant mode of Dinv A (left in pong[l] by estimate_lambda_max).  |lambda|max alone does not bound
-// the stable damping of a NON-symmetric operator (|1 - w lambda| < 1 needs w < 2 Re(lambda)/|lambda|^2):
-// on the 10 M-tet Jacobian w = 0.8 converges and w = 0.85 on the coarse levels breaks BiCGStab down.
-int jacobi_growth(sns_ctx* h, int l, double omega, double* growth) {
+// the last level's direct solve, whichever the hierarchy was built with (alloc_coarsest_solver, build_hierarchy); none: smoothed
+static int refresh_coarsest_solver(sns_ctx* h, int l) {
     Level& L = h->levels[l];
-    const policy::LevelPlan& P = h->plan.level[(size_t)l];
-    const int32_t rows = L.n_owned;
-    const int64_t nd = 4 * (int64_t)rows;
-    const int g = vec_grid(nd);
-    double* x0 = h->pong[l];
-    double* xa = L.x;
-    double* xb = L.r;
-    double* zero = nullptr;
-    SNS_TRY(get_vec(h, VEC_SCRATCH, &zero));                      // level sizes never exceed the fine level
-    if (nd > 0) HIP_TRY(hipMemsetAsync(zero, 0, nd * sizeof(double), h->stream));
-    // keep x0 intact (it seeds later trials): first sweep x0 -> xa, then ping-pong xa <-> xb
-    const bool glob = P.ghost_sweeps();
-    if (glob) SNS_TRY(exchange_level(h, l, x0));
-    launch_sweep(h, P, L, rows, x0, xa, zero, omega);
-    double* cur = xa;
-    double* oth = xb;
-    const int sweeps = 6;
-    for (int s = 1; s < sweeps; ++s) {
-        if (s == 2 || s == sweeps - 1) {
-            if (rows > 0) hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, nd, cur, cur, h->partial);
-            if (glob) SNS_TRY(reduce_to(h, g, 2, h->d_scal + 48 + (s == 2 ? 0 : 2)));
-            else reduce_local(h, g, 2, h->d_scal + 48 + (s == 2 ? 0 : 2));
-        }
-        if (glob) SNS_TRY(exchange_level(h, l, cur));
-        launch_sweep(h, P, L, rows, cur, oth, zero, omega);
-        std::swap(cur, oth);
+    if (h->cg_N > 0) {
+        // distributed coarsest level: my rows of the GLOBAL dense matrix -> all-gather -> replicated inverse
+        const int N = h->cg_N, mr = 4 * h->cg_maxn;
+        HIP_TRY(hipMemsetAsync(h->cg_rows, 0, (size_t)mr * N * sizeof(double), h->stream));
+        const int64_t nth = L.nnzb * 16;
+        if (nth > 0)
+            hipLaunchKernelGGL(k_bsr_to_dense_map, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.n_owned,
+                               L.rowptr, L.colind, L.vals, h->cg_colmap, N, h->cg_rows);
+        // padding rows (ranks with fewer nodes than maxn) get a unit diagonal
+        hipLaunchKernelGGL(k_pad_identity, dim3(1), dim3(256), 0, h->stream, 4 * L.n_owned, mr, h->comm->rank * mr, N, h->cg_rows);
+        SNS_TRY(comm_allgather(h->comm.get(), h->cg_rows, h->cg_full, mr * N, h->stream));
+        hipLaunchKernelGGL(k_dense_inverse, dim3(1), dim3(1024), 0, h->stream, N, h->cg_full, h->d_piv, h->d_sing);
+    } else if (L.dense_gj) {
+        // blocked Gauss-Jordan inverse on the fp64 matrix cores, then its fp32 copy for the cycle's matvec
+        const int N = 4 * L.n, Np = L.dense_np;
+        HIP_TRY(hipMemsetAsync(L.dense_gj, 0, (size_t)Np * Np * sizeof(double), h->stream));
+        const int64_t nth = L.nnzb * 16;
+        hipLaunchKernelGGL(k_bsr_to_dense_ld, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.nnzb, h->slot_row[l],
+                           L.colind, L.vals, Np, L.dense_gj);
+        if (Np > N) hipLaunchKernelGGL(k_dense_pad_diag, dim3((Np - N + 255) / 256), dim3(256), 0, h->stream, N, Np, L.dense_gj);
+        // (the two-stream schedule of dense_gj_inverse is opt-in: measured, it is SLOWER -- 3.9 against 2.4 ms at N = 1900 --
+        // because the bulk update's 900 workgroups fill the chip and the pivot chain's few workgroups queue behind them)
+        if (!h->gj_stream && std::getenv("SNS_GJ_TWO_STREAMS") &&
+            hipStreamCreateWithFlags(h->gj_stream.put(), hipStreamNonBlocking) != hipSuccess) h->gj_stream.reset();
+        dense_gj_inverse(h->stream, h->gj_stream, Np, L.dense_gj, L.dense_work, h->d_sing);
+        const int64_t nn = (int64_t)Np * Np;
+        hipLaunchKernelGGL(k_dense_to_f32, dim3((unsigned)((nn / 4 + 255) / 256)), dim3(256), 0, h->stream, nn, L.dense_gj, L.dense_x32);
+    } else if (L.dense_inv) {
+        const int N = 4 * L.n;
+        HIP_TRY(hipMemsetAsync(L.dense_inv, 0, (size_t)N * N * sizeof(double), h->stream));
+        const int64_t nth = L.nnzb * 16;
+        hipLaunchKernelGGL(k_bsr_to_dense, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.n, L.rowptr, L.colind,
+                           L.vals, L.dense_inv);
+        hipLaunchKernelGGL(k_dense_inverse, dim3(1), dim3(1024), 0, h->stream, N, L.dense_inv, h->d_piv, h->d_sing);
     }
-    double v[4];
-    SNS_TRY(fetch(h, h->d_scal + 48, 4, v));             // ||x_2||^2, ||x_{sweeps-1}||^2
-    *growth = (v[0] > 0.0) ? std::pow(v[2] / v[0], 0.5 / (double)(sweeps - 1 - 2)) : 0.0;
-    // scratch vectors: only [0, nd) was written; ghost tails stay untouched
+    return SNS_OK;
+}
+
+// The end of a set-up, the stream drained and the singularity flag `sing` fetched: the verdict on the dense inverses over all
+// ranks, then the put groups of the peer transport.
+static int conclude_setup(sns_ctx* h, int nl, bool check_sing, int sing) {
+    if (check_sing) {
+        // The aggregate blocks' inverses are rank-local: one rank alone returning an error here would leave the others in the
+        // Krylov loop's collectives (an RCCL hang, a peer time-out).  The verdict is taken over all ranks (ADVICE r4).
+        double bad[1] = {sing != 0 ? 1.0 : 0.0};
+        SNS_TRY(global_sum(h, bad, 1));
+        if (bad[0] != 0.0) {
+            // (the elimination runs without pivoting across its 64 x 64 blocks: see csrc/sns_dense.hip for why that is safe on this
+            // operator class; if it ever is not, say so instead of preconditioning with garbage -- there is no fallback hierarchy)
+            HIP_TRY(hipMemset(h->d_sing, 0, sizeof(int)));
+            set_error("AMG setup: a dense inverse (coarsest level or an aggregate block" +
+                      std::string(sing != 0 ? "" : ", on another rank") + ") met a zero or non-finite pivot; set "
+                      "amg_dense_rows = 0 / amg_block_smooth = 0");
+            return SNS_E_STATE;
+        }
+    }
+    if (h->comm && h->comm->peer && h->opt.pc_type == SNS_PC_AMG)
+        for (int l = 0; l < nl && l < (int)h->comm->plans.size(); ++l) {
+            const Level& L = h->levels[l];
+            if (L.blk_rows && L.n_blk > 0 && L.binv32)        // the puts carried by this level's block kernels (comm_put_dst)
+                SNS_TRY(comm_plan_put_groups(h->comm.get(), h->comm->plans[l], L.blk_rows, 8 * L.n_blk, h->stream));
+        }
     return SNS_OK;
 }
 
@@ -853,174 +837,21 @@ int pc_setup(sns_ctx* h) {
     const bool new_operator = policy::new_operator(h->matrix_key, h->est_key, h->r3_estimates);
     for (int l = 0; l < nl; ++l) {
         Level& L = h->levels[l];
-        const int32_t rows = L.n_owned;
         if (h->rep_level > 0 && l == h->rep_level - 1) {
-            // level R is only the source of the replicated copy: all-gather my rows' blocks, scatter them into place
-            Level& C = h->levels[h->rep_level];
-            if (L.nnzb > 0)
-                HIP_TRY(hipMemcpyAsync(h->rep_vsend, L.vals, (size_t)L.nnzb * 16 * sizeof(double), hipMemcpyDeviceToDevice,
-                                       h->stream));
-            SNS_TRY(comm_allgather(h->comm.get(), h->rep_vsend, h->rep_vrecv, (int)(h->rep_maxnz * 16), h->stream));
-            const int64_t nsrc = h->rep_maxnz * h->comm->nranks;
-            hipLaunchKernelGGL(k_scatter_blocks, dim3((unsigned)((nsrc * 8 + 255) / 256)), dim3(256), 0, h->stream, nsrc,
-                               h->rep_valmap, h->rep_vrecv, C.vals);
+            SNS_TRY(refresh_replicated_source(h, L));
             continue;
         }
         const policy::LevelPlan& P = h->plan.level[(size_t)l];
-        if (rows > 0)
-            hipLaunchKernelGGL(k_dinv, dim3((rows + 255) / 256), dim3(256), 0, h->stream, rows, L.diag, L.vals, L.dinv);
-        if (P.blocks) {
-            // the aggregates' inverse diagonal blocks, from the fp64 operator (what the nodal D^-1 is to the point smoother)
-            // ... in the format of the level's matrix copy (fp32, or fp16 with row scales: half the bytes of a block sweep's extra stream)
-            const int bf = h->opt.amg_f32_matrix == 2 ? 2 : 1;
-            if (!L.binv32 || L.binv_fmt != bf) {
-                SNS_TRY(L.binv32.alloc(binv_bytes_per_block(bf) * (size_t)std::max(1, L.n_blk)));
-                L.binv_fmt = bf;
-            }
-            if (L.n_blk > 0)
-                with_fmt(bf, [&](auto F) {
-                    hipLaunchKernelGGL((k_binv<F>), dim3((unsigned)((L.n_blk + 7) / 8)), dim3(256), 0, h->stream, L.n_blk, L.blk_rows,
-                                       L.blk_of, L.rowptr, L.colind, L.vals, L.binv32, h->d_sing);
-                });
-            any_block = true;
-        }
-        L.omega = h->opt.amg_omega * h->damping_backoff;
-        const bool direct = l + 1 == nl && nl > 1 && (P.kind == SNS_LEVEL_DIRECT || P.kind == SNS_LEVEL_DIRECT_BLOCKED);   // solved
-        if (P.lp_fmt != 0) {
-            if (!L.dinv32) SNS_TRY(L.dinv32.alloc((size_t)16 * std::max(1, L.n)));
-            if (rows > 0)
-                hipLaunchKernelGGL(k_cvt_f32, dim3(vec_grid(16 * (int64_t)rows)), dim3(256), 0, h->stream, 16 * (int64_t)rows,
-                                   L.dinv, L.dinv32);
-            if (h->opt.amg_f32_matrix == 2) {
-                if (!L.vals16) {
-                    SNS_TRY(L.vals16.alloc(std::max<size_t>(1, (size_t)L.nnzb * 4) * sizeof(uint2)));
-                    SNS_TRY(L.scale16.alloc((size_t)4 * std::max(1, L.n)));
-                }
-                // ONE pass over the level's fp64 operator writes its fp16 copy and, where the level has one, the fp16 copy of
-                // M = A P for the fused post-smoothing sweep (k_lp_copies16)
-                const bool with_m = l + 1 < nl && L.ap_rowptr && L.ap_nib && h->opt.amg_fused_post;
-                if (with_m && !L.ap_vals16) {
-                    SNS_TRY(L.ap_vals16.alloc(std::max<size_t>(1, (size_t)L.ap_nnz * 4) * sizeof(uint2)));
-                    SNS_TRY(L.ap_scale16.alloc((size_t)4 * std::max(1, L.n)));
-                }
-                if (rows > 0) {
-                    const unsigned grid = (unsigned)((rows + 31) / 32);
-                    if (with_m)
-                        hipLaunchKernelGGL((k_lp_copies16<1>), dim3(grid), dim3(128), 0, h->stream, rows, L.rowptr, L.vals,
-                                           (uint2*)L.vals16.get(), L.scale16, L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.ap_nib, L.agg,
-                                           L.free_mask, (uint2*)L.ap_vals16.get(), L.ap_scale16);
-                    else
-                        hipLaunchKernelGGL((k_lp_copies16<0>), dim3(grid), dim3(128), 0, h->stream, rows, L.rowptr, L.vals,
-                                           (uint2*)L.vals16.get(), L.scale16, (const int32_t*)nullptr, (const int32_t*)nullptr,
-                                           (const int32_t*)nullptr, (const int32_t*)nullptr, (const uint64_t*)nullptr,
-                                           (const int32_t*)nullptr, (const uint8_t*)nullptr, (uint2*)nullptr, (float*)nullptr);
-                }
-            }
-            if (h->opt.amg_f32_matrix != 2) {
-                if (!L.vals32) SNS_TRY(L.vals32.alloc((size_t)L.nnzb * 16));
-                if (L.nnzb > 0)
-                    hipLaunchKernelGGL(k_cvt_f32, dim3(vec_grid(L.nnzb * 16)), dim3(256), 0, h->stream, L.nnzb * 16, L.vals,
-                                       L.vals32);
-            }
-        }
-        if (h->opt.pc_type == SNS_PC_AMG && !direct) {
-            // the spectrum moves little between the Jacobians of one Newton sequence: re-estimate every 4th setup
-            double lam = L.lambda_max;
-            // (collective when the level's sweeps use exchanged ghost values: every rank takes part, rows or not)
-            // ... but not from the Stokes operator to a Jacobian (or to another Reynolds number): round 3 took the first three
-            // Jacobians' damping from the Stokes solve's estimate, which is what let level 1 of the jittered 120 x 30 x 30 duct
-            // run at w = 0.72 where its own spectrum allows 0.48 (tests/test_gpu_parity.py::test_damping_backoff_...)
-            if ((rows > 0 || P.ghost_sweeps()) && (!(lam > 0.0) || (h->pc_setups & 3) == 0 || new_operator))
-                SNS_TRY(estimate_lambda_max(h, l, &lam));
-            const bool fresh = !(L.lambda_max > 0.0) || (h->pc_setups & 3) == 0 || new_operator;
-            L.lambda_max = lam;
-            if (lam > 0.0) L.omega = std::min(h->opt.amg_omega, (4.0 / 3.0) / lam) * h->damping_backoff;
-            // levels that run 3 or more sweeps per cycle: the stability limit of the dominant (complex) Ritz values as well
-            if (h->opt.amg_ritz_limit && l + 1 < nl) {
-                if (P.pre + P.post >= 3) {
-                    if (fresh && (rows > 0 || P.exact)) {
-                        double tmax = 0.0, lim = 1e30;
-                        SNS_TRY(arnoldi_ritz(h, l, &tmax, &lim));
-                        L.ritz_limit = lim;
-                        if (h->opt.monitor)
-                            std::printf("    AMG level %d: Ritz |theta|max %.4f, damping limit 2 Re/|theta|^2 = %.4f\n", l, tmax, lim);
-                    }
-                    if (L.ritz_limit > 0.0) L.omega = std::min(L.omega, L.ritz_limit * h->damping_backoff);
-                }
-            }
-            // the growth check of rounds 1-3 (back off until a sweep contracts the dominant mode by >= 10 %), on levels that run >= 3
-            // sweeps per cycle only: a level with two sweeps per cycle (the fine level, V(1,1)) does not compound an amplified mode,
-            // and backing its damping off for the sake of a few complex outliers weakens the smoothing of everything else
-            // (jittered 120 x 30 x 30 duct, Re 200: 56 iterations this way, 82 with the check on every level, 85 without it; the
-            // option that switched between the three, amg_growth_check, was retired in round 5)
-            const bool check_growth = l + 1 < nl && P.pre + P.post >= 3;
-            if (fresh && lam > 0.0 && !check_growth) L.omega_checked = 0.0;
-            if (fresh && lam > 0.0 && check_growth) {
-                // verify the damping on the dominant mode; back off until a sweep contracts it by >= 10 %
-                for (int trial = 0; trial < 6; ++trial) {
-                    double gr = 0.0;
-                    SNS_TRY(jacobi_growth(h, l, L.omega, &gr));
-                    if (h->opt.monitor) std::printf("    AMG level %d: omega %.4f growth/sweep on dominant mode %.4f\n", l, L.omega, gr);
-                    if (gr < 0.9) break;
-                    L.omega *= 0.9;
-                }
-                L.omega_checked = L.omega;
-            } else if (L.omega_checked > 0.0) {
-                L.omega = std::min(L.omega, L.omega_checked);
-            }
-            if (h->opt.monitor) std::printf("    AMG level %d: n %d |lambda|max(Dinv A) %.4f omega %.4f\n", l, rows, lam, L.omega);
-        }
-        if (l + 1 < nl && L.ap_rowptr && h->opt.amg_fused_post && P.lp_fmt == 1) {
-            // numeric part of M = A P, straight into the level's low-precision format (no fp64 copy of M; fp16: written together
-            // with the fp16 copy of A above).  (Allocated on a rank without rows too: the plan asks for it on every rank.)
-            if (!L.ap_vals32) SNS_TRY(L.ap_vals32.alloc((size_t)L.ap_nnz * 16));
-            if (rows > 0)
-                hipLaunchKernelGGL(k_ap_cvt32, dim3((unsigned)((4 * (int64_t)rows + 255) / 256)), dim3(256), 0, h->stream, rows,
-                                   L.ap_rowptr, L.ap_colind, L.ap_ptr, L.ap_idx, L.vals, L.agg, L.free_mask, (float4*)L.ap_vals32.get());
-        }
-        if (l + 1 < nl) {
-            Level& C = h->levels[l + 1];
-            const int64_t nth = C.nnzb * 8;
-            hipLaunchKernelGGL(k_galerkin, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, C.nnzb,
-                               L.r_ptr, L.r_idx, L.vals, h->slot_row[l + 1], C.colind,
-                               (l == 0) ? h->empty_c[0] : (const uint8_t*)nullptr, L.m_ptr, C.vals);
-        } else if (h->cg_N > 0 && nl > 1) {
-            // distributed coarsest level: my rows of the GLOBAL dense matrix -> all-gather -> replicated inverse
-            const int N = h->cg_N, mr = 4 * h->cg_maxn;
-            HIP_TRY(hipMemsetAsync(h->cg_rows, 0, (size_t)mr * N * sizeof(double), h->stream));
-            const int64_t nth = L.nnzb * 16;
-            if (nth > 0)
-                hipLaunchKernelGGL(k_bsr_to_dense_map, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream,
-                                   L.n_owned, L.rowptr, L.colind, L.vals, h->cg_colmap, N, h->cg_rows);
-            // padding rows (ranks with fewer nodes than maxn) get a unit diagonal
-            hipLaunchKernelGGL(k_pad_identity, dim3(1), dim3(256), 0, h->stream, 4 * L.n_owned, mr,
-                               h->comm->rank * mr, N, h->cg_rows);
-            SNS_TRY(comm_allgather(h->comm.get(), h->cg_rows, h->cg_full, mr * N, h->stream));
-            hipLaunchKernelGGL(k_dense_inverse, dim3(1), dim3(1024), 0, h->stream, N, h->cg_full, h->d_piv, h->d_sing);
-        } else if (L.dense_gj && nl > 1) {
-            // blocked Gauss-Jordan inverse on the fp64 matrix cores, then its fp32 copy for the cycle's matvec
-            const int N = 4 * L.n, Np = L.dense_np;
-            HIP_TRY(hipMemsetAsync(L.dense_gj, 0, (size_t)Np * Np * sizeof(double), h->stream));
-            const int64_t nth = L.nnzb * 16;
-            hipLaunchKernelGGL(k_bsr_to_dense_ld, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.nnzb,
-                               h->slot_row[l], L.colind, L.vals, Np, L.dense_gj);
-            if (Np > N) hipLaunchKernelGGL(k_dense_pad_diag, dim3((Np - N + 255) / 256), dim3(256), 0, h->stream, N, Np, L.dense_gj);
-            // (the two-stream schedule of dense_gj_inverse is opt-in: measured, it is SLOWER -- 3.9 against 2.4 ms at N = 1900 --
-            // because the bulk update's 900 workgroups fill the chip and the pivot chain's few workgroups queue behind them)
-            if (!h->gj_stream && std::getenv("SNS_GJ_TWO_STREAMS") &&
-                hipStreamCreateWithFlags(h->gj_stream.put(), hipStreamNonBlocking) != hipSuccess) h->gj_stream.reset();
-            dense_gj_inverse(h->stream, h->gj_stream, Np, L.dense_gj, L.dense_work, h->d_sing);
-            const int64_t nn = (int64_t)Np * Np;
-            hipLaunchKernelGGL(k_dense_to_f32, dim3((unsigned)((nn / 4 + 255) / 256)), dim3(256), 0, h->stream, nn, L.dense_gj,
-                               L.dense_x32);
-        } else if (L.dense_inv && nl > 1) {
-            const int N = 4 * L.n;
-            HIP_TRY(hipMemsetAsync(L.dense_inv, 0, (size_t)N * N * sizeof(double), h->stream));
-            const int64_t nth = L.nnzb * 16;
-            hipLaunchKernelGGL(k_bsr_to_dense, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.n,
-                               L.rowptr, L.colind, L.vals, L.dense_inv);
-            hipLaunchKernelGGL(k_dense_inverse, dim3(1), dim3(1024), 0, h->stream, N, L.dense_inv, h->d_piv,
-                               h->d_sing);
+        const bool not_last = l + 1 < nl;
+        SNS_TRY(refresh_smoother_inverses(h, P, L));
+        if (P.blocks) any_block = true;
+        SNS_TRY(refresh_low_precision_copies(h, P, L, not_last));
+        SNS_TRY(damping_decide(h, l, nl, new_operator));
+        if (not_last) {
+            SNS_TRY(refresh_ap32(h, P, L));
+            refresh_galerkin(h, l);
+        } else if (nl > 1) {
+            SNS_TRY(refresh_coarsest_solver(h, l));
         }
     }
     if (const char* miss = plan_buffer_missing(h)) {
@@ -1039,27 +870,7 @@ int pc_setup(sns_ctx* h) {
     HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     h->tm.pc_setup_ms += ms;
     HIP_TRY(hipGetLastError());
-    if (check_sing) {
-        // The aggregate blocks' inverses are rank-local: one rank alone returning an error here would leave the others in the
-        // Krylov loop's collectives (an RCCL hang, a peer time-out).  The verdict is taken over all ranks (ADVICE r4).
-        double bad[1] = {*h_sing != 0 ? 1.0 : 0.0};
-        SNS_TRY(global_sum(h, bad, 1));
-        if (bad[0] != 0.0) {
-            // (the elimination runs without pivoting across its 64 x 64 blocks: see csrc/sns_dense.hip for why that is safe on this
-            // operator class; if it ever is not, say so instead of preconditioning with garbage -- there is no fallback hierarchy)
-            HIP_TRY(hipMemset(h->d_sing, 0, sizeof(int)));
-            set_error("AMG setup: a dense inverse (coarsest level or an aggregate block" +
-                      std::string(*h_sing != 0 ? "" : ", on another rank") + ") met a zero or non-finite pivot; set "
-                      "amg_dense_rows = 0 / amg_block_smooth = 0");
-            return SNS_E_STATE;
-        }
-    }
-    if (h->comm && h->comm->peer && h->opt.pc_type == SNS_PC_AMG)
-        for (int l = 0; l < nl && l < (int)h->comm->plans.size(); ++l) {
-            const Level& L = h->levels[l];
-            if (L.blk_rows && L.n_blk > 0 && L.binv32)        // the puts carried by this level's block kernels (comm_put_dst)
-                SNS_TRY(comm_plan_put_groups(h->comm.get(), h->comm->plans[l], L.blk_rows, 8 * L.n_blk, h->stream));
-        }
+    SNS_TRY(conclude_setup(h, nl, check_sing, *h_sing));
     h->pc_ready = true;
     return SNS_OK;
 }

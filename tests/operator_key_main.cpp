@@ -3,7 +3,7 @@
 //   sigma V | theta V | law ON LAMBDA N R | field 1 (set) / 0 (clear) | re V | transpose | assemble FORM | scalar K0 K1 K2 K3 S T | setup
 // replayed as the library does -- the setters write the form's share of the key (the field: its generation, as
 // set_element_viscosity), an assembly stamps the key (matrix_changed), a transpose flips its flag, a set-up compares and takes
-// the key over (pc_setup); the every-fourth-set-up cadence is not part of it.  stdout: per sequence one 0 / 1 for every set-up.
+// the key over (pc_setup); the every-fourth-set-up cadence is not part of it (tests/damping_policy_main.cpp).  stdout: per sequence one 0 / 1 for every set-up.
 #include <iostream>
 #include <sstream>
 #include <string>

@@ -1223,3 +1223,165 @@ def test_operator_key_sequences(tmp_path):
     for (s, want_keys, want_flags), g in zip(irregular, got):
         assert g == "1" + want_keys, (s, g)
         assert flags("assemble 1 setup " + s) == "1" + want_flags, s
+
+
+def test_damping_predicates(tmp_path):
+    """When a level's spectral estimates are due and which levels take the Ritz limit and the growth check (csrc/sns_policy.h,
+    "smoother damping"; tests/damping_policy_main.cpp) over the full product of their facts, against the conditions as pc_setup
+    had them inline before the section existed, for a rank with rows on the level:
+
+        if ((rows > 0 || P.ghost_sweeps()) && (!(lam > 0.0) || (h->pc_setups & 3) == 0 || new_operator)) ... estimate_lambda_max
+        const bool fresh = !(L.lambda_max > 0.0) || (h->pc_setups & 3) == 0 || new_operator;
+        if (h->opt.amg_ritz_limit && l + 1 < nl) { if (P.pre + P.post >= 3) { ... arnoldi_ritz, the limit applied
+        const bool check_growth = l + 1 < nl && P.pre + P.post >= 3;
+    """
+    import itertools
+    import subprocess
+    exe = _policy_main(tmp_path, "damping_policy")
+    combos = list(itertools.product((0, 1), range(13), (0, 1), (0, 1), (0, 1), range(8)))
+    run = subprocess.run([exe], input="predicates\n" + "".join(" ".join(map(str, c)) + "\n" for c in combos),
+                         capture_output=True, text=True)
+    assert run.returncode == 0, (run.returncode, run.stderr[-500:])
+    got = [tuple(int(v) for v in ln.split()) for ln in run.stdout.split("\n")[:len(combos)]]
+    assert len(got) == len(combos)
+    for (has, setups, new_operator, ritz_option, not_last, sweeps), g in zip(combos, got):
+        fresh = (not has) or (setups & 3) == 0 or bool(new_operator)
+        takes_ritz = bool(ritz_option) and bool(not_last) and sweeps >= 3
+        check_growth = bool(not_last) and sweeps >= 3
+        assert g == (int(fresh), int(takes_ritz), int(check_growth)), ((has, setups, new_operator, ritz_option, not_last, sweeps), g)
+
+
+def test_damping_event_sequences(tmp_path):
+    """The levels' dampings over the life of a handle -- set-ups, retries, options calls -- as the three transitions of
+    csrc/sns_damping.hip make them from csrc/sns_policy.h (replayed by tests/damping_policy_main.cpp with synthetic estimator
+    values), bit for bit against a model transcribed from the code as it was inline before: pc_setup's per-level block,
+    krylov()'s retry (which scales the STORED omega and omega_checked by 0.7 in place and offers no retry once the factor is
+    at or below 0.4) and the two blocks of sns_set_options that zeroed the estimates."""
+    import struct
+    import subprocess
+    exe = _policy_main(tmp_path, "damping_policy")
+    rng = np.random.default_rng(4711)
+    seen = {"trials": set(), "levels": set(), "retries": set(), "no_estimate": 0, "ritz_binds": 0, "ritz_slack": 0, "held": 0,
+            "refused": 0, "resets": 0}
+
+    class L:
+        def __init__(self):
+            self.omega, self.lambda_max, self.omega_checked, self.ritz_limit = 0.8, 0.0, 0.0, 0.0
+
+    def model_setup(levels, amg_omega, backoff, ritz_option, direct_last, pc_setups, new_operator, synth):
+        nl = len(levels)
+        for l, (Lv, (sweeps, s_lam, s_ritz, s_growth)) in enumerate(zip(levels, synth)):
+            Lv.omega = amg_omega * backoff
+            if l + 1 == nl and nl > 1 and direct_last:
+                continue
+            lam = Lv.lambda_max
+            if not (lam > 0.0) or (pc_setups & 3) == 0 or new_operator:
+                lam = s_lam                                                   # estimate_lambda_max
+            fresh = not (Lv.lambda_max > 0.0) or (pc_setups & 3) == 0 or new_operator
+            Lv.lambda_max = lam
+            if lam > 0.0:
+                Lv.omega = min(amg_omega, (4.0 / 3.0) / lam) * backoff
+            else:
+                seen["no_estimate"] += 1
+            if ritz_option and l + 1 < nl:
+                if sweeps >= 3:
+                    if fresh:
+                        Lv.ritz_limit = s_ritz                                # arnoldi_ritz
+                    if Lv.ritz_limit > 0.0:
+                        seen["ritz_binds" if Lv.ritz_limit * backoff < Lv.omega else "ritz_slack"] += 1
+                        Lv.omega = min(Lv.omega, Lv.ritz_limit * backoff)
+            check_growth = l + 1 < nl and sweeps >= 3
+            if fresh and lam > 0.0 and not check_growth:
+                Lv.omega_checked = 0.0
+            if fresh and lam > 0.0 and check_growth:
+                trials = 0
+                for trial in range(6):
+                    gr = s_growth[trial]                                      # jacobi_growth(h, l, L.omega, &gr)
+                    if gr < 0.9:
+                        break
+                    Lv.omega *= 0.9
+                    trials += 1
+                seen["trials"].add(trials)
+                Lv.omega_checked = Lv.omega
+            elif Lv.omega_checked > 0.0:
+                seen["held"] += Lv.omega_checked < Lv.omega
+                Lv.omega = min(Lv.omega, Lv.omega_checked)
+
+    def sequence():
+        """(the event line, the model's dampings after every printing event)"""
+        nl = int(rng.integers(1, 6))
+        amg_omega = float(rng.choice((0.8, 0.9, 0.72, 1.0)))
+        ritz_option, direct_last = int(rng.integers(4) > 0), int(rng.integers(2))
+        ev = ["handle %d %r %d %d" % (nl, amg_omega, ritz_option, direct_last)]
+        levels, backoff, pc_setups, retries, want = [L() for _ in range(nl)], 1.0, 0, 0, []
+        seen["levels"].add(nl)
+        sweeps = [int(rng.choice((2, 3, 5, 7))) for _ in range(nl)]          # (a plan's: fixed between options calls)
+        n_setups, max_retries = int(rng.integers(1, 13)), int(rng.integers(0, 5))
+        while n_setups > 0:
+            kind = int(rng.integers(10))
+            if kind <= 5:
+                n_setups -= 1
+                new_operator = int(rng.integers(4) == 0)
+                synth = []
+                for l in range(nl):
+                    lam = 0.0 if rng.integers(8) == 0 else float(rng.uniform(0.8, 4.0))
+                    ritz = 1e30 if rng.integers(5) == 0 else float(rng.uniform(0.1, 2.5))
+                    k = int(rng.integers(0, 8))                               # trials that do not contract: 0 .. 6 (7: as 6)
+                    growth = [float(rng.uniform(0.9, 1.3)) if t < k else float(rng.uniform(0.2, 0.9 - 1e-9)) for t in range(6)]
+                    if rng.integers(6) == 0:
+                        growth[min(k, 5)] = 0.9                               # the bound itself does not pass
+                    synth.append((sweeps[l], lam, ritz, growth))
+                ev.append("setup %d %d " % (pc_setups, new_operator) +
+                          " ".join("%d %r %r %s" % (s, a, b, " ".join(map(repr, g))) for s, a, b, g in synth))
+                model_setup(levels, amg_omega, backoff, ritz_option, direct_last, pc_setups, new_operator, synth)
+                pc_setups += 1
+            elif kind <= 7:
+                if retries >= max_retries:
+                    continue
+                retries += 1
+                ev.append("retry")
+                if backoff > 0.4:                                             # can_retry
+                    backoff *= 0.7
+                    for Lv in levels:
+                        Lv.omega *= 0.7
+                        if Lv.omega_checked > 0.0:
+                            Lv.omega_checked *= 0.7
+                else:
+                    seen["refused"] += 1
+            else:                                                             # sns_set_options, with or without a new amg_omega
+                seen["resets"] += 1
+                ev.append("reset_retry")
+                if backoff != 1.0:
+                    backoff = 1.0
+                    for Lv in levels:
+                        Lv.lambda_max = Lv.omega_checked = Lv.ritz_limit = 0.0
+                want.append([Lv.omega for Lv in levels])
+                if kind == 9:
+                    continue
+                new_omega = float(rng.choice((0.8, 0.9, 0.72, 1.0)))
+                ev.append("amg_omega %r" % new_omega)
+                if new_omega != amg_omega:                                    # damping_changed
+                    ev.append("reset_estimates")
+                    for Lv in levels:
+                        Lv.lambda_max = Lv.omega_checked = Lv.ritz_limit = 0.0
+                    want.append([Lv.omega for Lv in levels])
+                amg_omega = new_omega
+                continue
+            want.append([Lv.omega for Lv in levels])
+        seen["retries"].add(retries)
+        return " ".join(ev), want
+
+    cases = [sequence() for _ in range(2500)]
+    run = subprocess.run([exe], input="sequences\n" + "".join(s + "\n" for s, _ in cases), capture_output=True, text=True)
+    assert run.returncode == 0, (run.returncode, run.stderr[-500:])
+    lines = run.stdout.split("\n")[:len(cases)]
+    assert len(lines) == len(cases)
+    bits = lambda v: struct.pack("<d", v)
+    for (s, want), ln in zip(cases, lines):
+        got = [[float.fromhex(t) for t in part.split()] for part in ln.split(";")]
+        assert len(got) == len(want), (s, ln)
+        for k, (g, w) in enumerate(zip(got, want)):
+            assert [bits(v) for v in g] == [bits(v) for v in w], (s, k, g, w)
+    # what the sequences covered
+    assert seen["trials"] == set(range(7)) and seen["levels"] == {1, 2, 3, 4, 5} and seen["retries"] >= {0, 1, 2, 3}
+    assert min(seen[k] for k in ("no_estimate", "ritz_binds", "ritz_slack", "held", "refused", "resets")) > 20, seen
