@@ -217,14 +217,11 @@ static int create_common(int dim, sns_handle* out, int32_t n_nodes, int64_t n_te
         SNS_TRY(h->od_order.upload(order));
     }
     h->levels.emplace_back();
-    h->slot_row.emplace_back();
-    h->empty_c.emplace_back();
-    h->pong.emplace_back();
-    SNS_TRY(upload_pattern(h->levels[0], P, h->slot_row[0], nullptr));
+    SNS_TRY(upload_pattern(h->levels[0], P, nullptr));
     h->levels[0].n_owned = n_nodes;
     SNS_TRY(alloc_level_vectors(h->levels[0]));
-    SNS_TRY(h->pong[0].alloc(4 * (size_t)n_nodes));
-    HIP_TRY(hipMemset(h->pong[0], 0, 4 * (size_t)n_nodes * sizeof(double)));
+    SNS_TRY(h->levels[0].pong.alloc(4 * (size_t)n_nodes));
+    HIP_TRY(hipMemset(h->levels[0].pong, 0, 4 * (size_t)n_nodes * sizeof(double)));
     {   // free mask of level 0 = !bc
         std::vector<uint8_t> fm((size_t)4 * n_nodes);
         for (size_t i = 0; i < fm.size(); ++i) fm[i] = bc_mask[i] ? 0 : 1;
@@ -346,7 +343,7 @@ int sns_set_options(sns_handle h, const sns_options* o) {
             Level& L = h->levels[l];
             const size_t nb = 4 * (size_t)L.n * sizeof(double);
             if (L.x) HIP_TRY(hipMemset(L.x, 0, nb));
-            if (l < h->pong.size() && h->pong[l]) HIP_TRY(hipMemset(h->pong[l], 0, nb));
+            if (L.pong) HIP_TRY(hipMemset(L.pong, 0, nb));
         }
     }
     h->plan = policy::plan_cycle(h->opt, h->facts);         // (the stored facts: no communication)

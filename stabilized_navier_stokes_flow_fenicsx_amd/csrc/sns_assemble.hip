@@ -117,7 +117,7 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         state = tmp;
     }
     if (p.offdiag)
-        hipLaunchKernelGGL(K.offdiag, dim3(go), dim3(256), 0, h->stream, h->n_od, h->od_order, h->c_ptr, h->c_idx, h->slot_row[0],
+        hipLaunchKernelGGL(K.offdiag, dim3(go), dim3(256), 0, h->stream, h->n_od, h->od_order, h->c_ptr, h->c_idx, h->levels[0].slot_row,
                            L.colind, h->tets, h->pts, state, h->bc_mask, K.nu, K.aux, L.vals, K.tt, K.vl);
     if (p.diag)
         hipLaunchKernelGGL(K.diag, dim3(gd), dim3(256), 0, h->stream, h->n_owned, L.diag, h->c_ptr, h->c_idx, h->tets, h->pts, state,
@@ -129,7 +129,7 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
         launch_element_pass(h, form, K, p.element, h->E, h->tets, w, h->bc_mask, p.store_K, h->Ke, p.Fe_out ? h->Fe.get() : nullptr);
     if (p.gather_matrix)
         hipLaunchKernelGGL(k_gather_matrix, dim3((unsigned)((L.nnzb * 8 + 255) / 256)), dim3(256), 0, h->stream, L.nnzb, h->c_ptr,
-                           h->c_idx, h->slot_row[0], L.colind, h->bc_mask, h->Ke, L.vals);
+                           h->c_idx, h->levels[0].slot_row, L.colind, h->bc_mask, h->Ke, L.vals);
     if (p.gather_residual)
         hipLaunchKernelGGL(k_gather_residual, dim3(gd), dim3(256), 0, h->stream, h->n_owned, h->nt_ptr, h->nt_idx, h->bc_mask,
                            h->bc_val, w, h->Fe, F);

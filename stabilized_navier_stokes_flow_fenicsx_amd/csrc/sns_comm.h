@@ -25,6 +25,7 @@
 #include <rccl/rccl.h>
 
 #include "sns_devbuf.h"
+#include "sns_internal.h"
 #include "sns_peer_dev.h"
 
 #include <condition_variable>
@@ -57,11 +58,9 @@ struct Peer {                                    // one rank's end of the direct
     long long timeout_ticks = 0;                 // bound of every device-side wait, in wall_clock64() ticks (100 MHz)
 };
 
-struct Plan {                                    // halo plan of one level (counts in nodes, 4 doubles each)
-    std::vector<int> nbr;                        // neighbour ranks, same order on both sides of a link
-    std::vector<int32_t> send_ptr, recv_ptr;     // host
-    std::vector<int32_t> h_send_idx, h_recv_idx; // host copies (hierarchy setup)
-    int32_t n_own = 0;                           // owned nodes of the level (the ghost nodes follow them)
+// halo plan of one level (counts in nodes, 4 doubles each): the host lists nbr, send_ptr, recv_ptr, h_send_idx, h_recv_idx and
+// n_own of HaloLists (csrc/sns_internal.h; the hierarchy build derives them per level) and what plan_upload makes of them
+struct Plan : HaloLists {
     bool identity_recv = false;                  // recv_idx[q] == n_own + q: the receive buffer IS the ghost tail, in order
     DevBuf<int32_t> send_idx, recv_idx;                 // device
     DevBuf<double> send_buf, recv_buf;                  // device, 4 doubles per node (RCCL staging)

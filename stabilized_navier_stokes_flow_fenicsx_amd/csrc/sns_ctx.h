@@ -144,9 +144,6 @@ struct sns_ctx {
     // while coarser levels are appended (a vector reallocation under a live Level& once handed a kernel dangling
     // pointers)
     std::deque<Level> levels;
-    std::vector<DevBuf<int32_t>> slot_row;            // per level
-    std::vector<DevBuf<uint8_t>> empty_c;             // per level (coarse side), level l -> empty flags of level l+1
-    std::vector<DevBuf<double>> pong;                 // per level smoother ping-pong buffer
     DevBuf<int> d_piv;
     DevBuf<int> d_sing;
     FormState form;                              // the switches of the 3-D NS form and their buffers (csrc/sns_form.hip)
@@ -220,9 +217,10 @@ struct sns_ctx {
     int cg_maxn = 0;                              // padded owned coarsest nodes per rank
     int cg_N = 0;                                 // 4 * nranks * cg_maxn (0 = not used)
     std::vector<int> cg_counts;                   // owned coarsest nodes of every rank
-    // multi-GPU: replicated tail of the hierarchy.  levels[rep_level] is a copy of the GLOBAL operator of level
-    // rep_level-1 held by every rank (all-gathered values); it and everything below is cycled redundantly on every
-    // rank without any exchange.  0 = none.
+    // multi-GPU: replicated tail of the hierarchy.  levels[rep_level - 1], the source, is the last partitioned level: it is not
+    // cycled, and levels[rep_level] holds the same operator over ALL ranks' rows on every rank (its values all-gathered from
+    // the source at every numeric setup); that copy and everything below it is cycled redundantly on every rank without any
+    // exchange.  0 = none.
     int rep_level = 0;
     int32_t rep_maxn = 0, rep_NG = 0, rep_off = 0;
     int64_t rep_maxnz = 0;
@@ -232,8 +230,6 @@ struct sns_ctx {
     DevBuf<int64_t> rep_doff, rep_dcnt;                 // [nranks] doubles: where rank r's right-hand side goes in the replicated level's b, and how much
     DevBuf<int32_t> cg_colmap;                    // local coarsest node -> global (padded) node id
     DevBuf<double> cg_rows, cg_full, cg_send, cg_recv;
-    std::vector<std::vector<int32_t>> ghost_gid;  // per level: (owner rank, owner-local id) of each ghost node
-    std::vector<std::vector<int32_t>> ghost_own;
     std::unique_ptr<HostPattern> pattern;      // kept until the (lazy) hierarchy build
     std::vector<double> host_pts;              // ... with the node coordinates (3 per node): the aggregation's strength filter on anisotropic meshes
     std::vector<int32_t> agg0;                 // the level-0 aggregate map as built (owned nodes; -1 elsewhere): SNS_EXPORT_AGG0
@@ -253,7 +249,7 @@ struct sns_ctx {
 namespace sns {
 // csrc/sns_setup.hip: symbolic hierarchy, numeric setup of the preconditioner, workspace vectors
 int alloc_level_vectors(Level& L);
-int upload_pattern(Level& L, const HostPattern& P, DevBuf<int32_t>& slot_row, hipStream_t s);
+int upload_pattern(Level& L, const HostPattern& P, hipStream_t s);
 int global_sum(sns_ctx* h, double* v, int count);
 int host_allgather(sns_ctx* h, const std::vector<double>& mine, std::vector<double>& all);
 int check_plan_symmetry(sns_ctx* h, const Plan& p, int level);

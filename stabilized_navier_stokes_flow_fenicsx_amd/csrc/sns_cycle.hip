@@ -64,7 +64,7 @@ static void launch_restrict(sns_ctx* h, int l, bool fused, const double* x, cons
     const policy::LevelPlan& QC = h->plan.level[(size_t)l + 1];
     const bool fuse = Q.fuses_next_first != 0;
     const float* dc = fuse ? C.dinv32 : nullptr;
-    double* zc = !fuse ? nullptr : QC.start_odd ? h->pong[l + 1] : C.x;   // (the coarse cycle is called with x = C.x)
+    double* zc = !fuse ? nullptr : QC.start_odd ? h->levels[l + 1].pong : C.x;   // (the coarse cycle is called with x = C.x)
     if (fused) {
         // mode of the coarse level's first sweep: 0 none, 1 nodal D^-1, 2 its aggregate blocks (walked in THEIR order)
         const int mode = !fuse ? 0 : (QC.blocks ? 2 : 1);
@@ -144,8 +144,8 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     const int32_t rows = L.n_owned;
     const double om = L.damping.omega;
     const int nu_pre = Q.pre, nu_post = Q.post;
-    double* cur = Q.start_odd ? h->pong[l] : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
-    double* oth = (cur == x) ? h->pong[l] : x;
+    double* cur = Q.start_odd ? h->levels[l].pong : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
+    double* oth = (cur == x) ? h->levels[l].pong : x;
     // The put of every exchange of this level's iterate rides in the kernel that PRODUCES the iterate (PutDst) where that is an
     // aggregate-block kernel: `carried` says whether the vector about to be exchanged has been put already
     const bool blk = Q.blocks != 0;
@@ -252,7 +252,7 @@ static int enter_replicated_tail(sns_ctx* h, int l, const double* b, double* x) 
         SNS_TRY(peer_check(cm));
         SNS_TRY(comm_host_barrier(cm, h->stream));
         const int32_t ns = 8 * C.n_blk;
-        double* zc = h->plan.level[(size_t)h->rep_level].start_odd ? h->pong[h->rep_level] : C.x;
+        double* zc = h->plan.level[(size_t)h->rep_level].start_odd ? C.pong : C.x;
         with_fmt(C.binv_fmt, [&](auto F) {
             hipLaunchKernelGGL((k_bfirst_gather<F>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
                                (const void*)C.binv32, C.damping.omega, zc, C.b, h->rep_rowmap, comm_ag_get(cm));
@@ -301,7 +301,7 @@ static int solve_last_level(sns_ctx* h, int l, const double* b, double* x) {
         return SNS_OK;
     }
     double* cur = x;
-    double* oth = h->pong[l];
+    double* oth = h->levels[l].pong;
     if (rows == 0) return SNS_OK;
     hipLaunchKernelGGL(k_bjacobi, dim3((unsigned)((4 * (int64_t)rows + 255) / 256)), dim3(256), 0, h->stream, rows, L.dinv, b,
                        L.damping.omega, cur);
@@ -324,8 +324,8 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     const int32_t rows = L.n_owned;
     const double om = L.damping.omega;
     const int nu = Q.nu, nu_pre = Q.pre, nu_post = Q.post;
-    double* cur = Q.start_odd ? h->pong[l] : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
-    double* oth = (cur == x) ? h->pong[l] : x;
+    double* cur = Q.start_odd ? h->levels[l].pong : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
+    double* oth = (cur == x) ? h->levels[l].pong : x;
     // distributed: on levels with few rows per rank the sweeps see the neighbours' current iterate (one small
     // exchange per sweep); on the big levels they stay rank-local (ghost values zero) and only the residual is exact
     const bool sx = Q.sx != 0;

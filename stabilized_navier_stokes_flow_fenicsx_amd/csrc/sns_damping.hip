@@ -18,7 +18,7 @@ static int estimate_lambda_max(sns_ctx* h, int l, double* out) {
     const int32_t rows = L.n_owned;
     const int64_t nd = 4 * (int64_t)rows;
     const int g = vec_grid(nd), g4 = (int)((nd + 255) / 256);
-    double* x = h->pong[l];
+    double* x = h->levels[l].pong;
     double* y = L.r;
     double* z = L.x;
     // deterministic start vector with all frequencies: x_i = 1 + (i*2654435761 mod 1024)/1024 via axpby on an iota is
@@ -148,7 +148,7 @@ static int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
 
 
 // Growth factor per sweep of the damped block-Jacobi iteration matrix G_w = I - w Dinv A on the
-// dominant mode of Dinv A (left in pong[l] by estimate_lambda_max).  |lambda|max alone does not bound
+// dominant mode of Dinv A (left in the level's pong by estimate_lambda_max).  |lambda|max alone does not bound
 // the stable damping of a NON-symmetric operator (|1 - w lambda| < 1 needs w < 2 Re(lambda)/|lambda|^2):
 // on the 10 M-tet Jacobian w = 0.8 converges and w = 0.85 on the coarse levels breaks BiCGStab down.
 static int jacobi_growth(sns_ctx* h, int l, double omega, double* growth) {
@@ -157,7 +157,7 @@ static int jacobi_growth(sns_ctx* h, int l, double omega, double* growth) {
     const int32_t rows = L.n_owned;
     const int64_t nd = 4 * (int64_t)rows;
     const int g = vec_grid(nd);
-    double* x0 = h->pong[l];
+    double* x0 = h->levels[l].pong;
     double* xa = L.x;
     double* xb = L.r;
     double* zero = nullptr;
@@ -223,7 +223,7 @@ int damping_decide(sns_ctx* h, int l, int nl, bool new_operator) {
     }
     d.omega = policy::capped_damping(o.amg_omega, h->damping_backoff, lam, ritz, d.ritz_limit);
     if (due && lam > 0.0 && policy::takes_growth_check(l + 1 < nl, P.pre + P.post)) {
-        // verify the damping on the dominant mode (left in pong[l] by estimate_lambda_max)
+        // verify the damping on the dominant mode (left in the level's pong by estimate_lambda_max)
         SNS_TRY(policy::checked_damping(d.omega, [&](double w, double* gr) {
             SNS_TRY(jacobi_growth(h, l, w, gr));
             if (o.monitor) std::printf("    AMG level %d: omega %.4f growth/sweep on dominant mode %.4f\n", l, w, *gr);

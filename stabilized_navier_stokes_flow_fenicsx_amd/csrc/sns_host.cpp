@@ -657,6 +657,143 @@ void build_aggregation(const HostPattern& fine, int max_agg, HostAggregation& A)
     build_aggregation_active(fine, fine.n, max_agg, A);
 }
 
+// ---- index logic of the distributed hierarchy build (what csrc/sns_setup.hip does between its collectives) -------------------
+std::vector<double> aggregate_centroids(const double* pts, int32_t n, const std::vector<int32_t>& agg, int32_t nc) {
+    std::vector<double> cp((size_t)3 * nc, 0.0);
+    std::vector<int32_t> cn((size_t)nc, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t I = agg[(size_t)i];
+        if (I < 0) continue;
+        for (int k = 0; k < 3; ++k) cp[3 * (size_t)I + k] += pts[3 * (size_t)i + k];
+        ++cn[(size_t)I];
+    }
+    for (int32_t I = 0; I < nc; ++I)
+        if (cn[(size_t)I]) for (int k = 0; k < 3; ++k) cp[3 * (size_t)I + k] /= (double)cn[(size_t)I];
+    return cp;
+}
+
+int coarse_halo_lists(const HaloLists& p, const std::vector<int32_t>& owner_agg, int32_t nc_owned, std::vector<int32_t>& agg,
+                      HaloLists& coarse, GhostIds& ghosts, int32_t& nc_total) {
+    nc_total = nc_owned;
+    coarse = HaloLists();
+    ghosts = GhostIds();
+    coarse.nbr = p.nbr;
+    coarse.n_own = nc_owned;
+    coarse.send_ptr.assign(1, 0);
+    coarse.recv_ptr.assign(1, 0);
+    std::vector<int32_t> u;
+    for (size_t k = 0; k < p.nbr.size(); ++k) {
+        // received from neighbour k: its distinct aggregates, ascending in ITS numbering, are my next ghost coarse nodes
+        u.clear();
+        for (int32_t q = p.recv_ptr[k]; q < p.recv_ptr[k + 1]; ++q) {
+            const int32_t rid = owner_agg[(size_t)p.h_recv_idx[(size_t)q]];
+            if (rid < 0) { set_error("hierarchy: ghost node without an aggregate on its owner"); return SNS_E_COMM; }
+            u.push_back(rid);
+        }
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());
+        for (int32_t q = p.recv_ptr[k]; q < p.recv_ptr[k + 1]; ++q) {
+            const int32_t gnode = p.h_recv_idx[(size_t)q];
+            agg[(size_t)gnode] = nc_total + (int32_t)(std::lower_bound(u.begin(), u.end(), owner_agg[(size_t)gnode]) - u.begin());
+        }
+        for (size_t q = 0; q < u.size(); ++q) {
+            coarse.h_recv_idx.push_back(nc_total + (int32_t)q);
+            ghosts.own.push_back(p.nbr[k]);
+            ghosts.gid.push_back(u[q]);
+        }
+        nc_total += (int32_t)u.size();
+        coarse.recv_ptr.push_back((int32_t)coarse.h_recv_idx.size());
+        // sent to neighbour k: the distinct aggregates of the nodes it has as ghosts, ascending -- the list it makes of them above
+        u.clear();
+        for (int32_t q = p.send_ptr[k]; q < p.send_ptr[k + 1]; ++q) u.push_back(agg[(size_t)p.h_send_idx[(size_t)q]]);
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());
+        coarse.h_send_idx.insert(coarse.h_send_idx.end(), u.begin(), u.end());
+        coarse.send_ptr.push_back((int32_t)coarse.h_send_idx.size());
+    }
+    return SNS_OK;
+}
+
+ReplicatedLayout replicated_layout(int nranks, const double* cnt) {
+    ReplicatedLayout lay;
+    lay.rows.resize((size_t)nranks);
+    lay.off.assign((size_t)nranks + 1, 0);
+    for (int r = 0; r < nranks; ++r) {
+        lay.rows[(size_t)r] = (int32_t)cnt[r];
+        lay.off[(size_t)r + 1] = lay.off[(size_t)r] + (int64_t)cnt[r];
+        lay.maxn = std::max(lay.maxn, (int32_t)cnt[r]);
+        lay.maxnz = std::max(lay.maxnz, (int64_t)cnt[nranks + r]);
+    }
+    lay.NG = (int32_t)lay.off[(size_t)nranks];
+    return lay;
+}
+
+int64_t replicated_id(const ReplicatedLayout& lay, int me, int32_t n_owned, const GhostIds& ghosts, int32_t j) {
+    if (j < n_owned) return lay.off[(size_t)me] + j;
+    const size_t q = (size_t)(j - n_owned);
+    if (q >= ghosts.own.size()) return -1;
+    return lay.off[(size_t)ghosts.own[q]] + ghosts.gid[q];
+}
+
+int replicated_record(const ReplicatedLayout& lay, int me, const HostPattern& cur, int32_t n_owned, const GhostIds& ghosts,
+                      std::vector<double>& mine) {
+    mine.assign(lay.record(), -1.0);
+    for (int32_t i = 0; i < lay.maxn; ++i) mine[(size_t)i] = i < n_owned ? (double)(cur.rowptr[i + 1] - cur.rowptr[i]) : 0.0;
+    for (int32_t s = 0; s < cur.rowptr[n_owned]; ++s) {
+        const int64_t gj = replicated_id(lay, me, n_owned, ghosts, cur.colind[(size_t)s]);
+        if (gj < 0) { set_error("replicated tail: ghost column without an owner record"); return SNS_E_STATE; }
+        mine[(size_t)lay.maxn + s] = (double)gj;
+    }
+    return SNS_OK;
+}
+
+int replicated_pattern(const ReplicatedLayout& lay, const std::vector<double>& all, HostPattern& G, std::vector<int32_t>& valmap,
+                       std::vector<int32_t>& rowmap) {
+    const int nr = (int)lay.rows.size();
+    const int32_t NG = lay.NG, maxn = lay.maxn;
+    const int64_t maxnz = lay.maxnz;
+    const size_t LEN = lay.record();
+    G = HostPattern();
+    G.n = NG;
+    G.rowptr.assign((size_t)NG + 1, 0);
+    valmap.assign((size_t)nr * maxnz, -1);
+    rowmap.assign((size_t)std::max(1, NG), 0);
+    for (int r = 0; r < nr; ++r)
+        for (int32_t i = 0; i < lay.rows[(size_t)r]; ++i) {
+            G.rowptr[(size_t)lay.off[(size_t)r] + i + 1] = (int32_t)all[r * LEN + i];
+            rowmap[(size_t)lay.off[(size_t)r] + i] = r * maxn + i;
+        }
+    for (int32_t g = 0; g < NG; ++g) G.rowptr[(size_t)g + 1] += G.rowptr[(size_t)g];
+    G.nnzb = G.rowptr[(size_t)NG];
+    G.colind.resize((size_t)G.nnzb);
+    G.diag.assign((size_t)NG, 0);
+    std::vector<std::pair<int32_t, int32_t>> ent;        // (global column, gathered slot) of a row, sorted by column
+    for (int r = 0; r < nr; ++r) {
+        int64_t src = 0;
+        for (int32_t i = 0; i < lay.rows[(size_t)r]; ++i) {
+            const int32_t g = (int32_t)lay.off[(size_t)r] + i;
+            const int32_t len = (int32_t)all[r * LEN + i];
+            ent.clear();
+            for (int32_t k = 0; k < len; ++k, ++src)
+                ent.emplace_back((int32_t)all[r * LEN + maxn + src], (int32_t)(r * maxnz + src));
+            std::sort(ent.begin(), ent.end());
+            bool has_diag = false;
+            for (int32_t k = 0; k < len; ++k) {
+                const int32_t slot = G.rowptr[(size_t)g] + k;
+                if (ent[k].first < 0 || ent[k].first >= NG || (k > 0 && ent[k].first == ent[k - 1].first)) {
+                    set_error("replicated tail: inconsistent global pattern");
+                    return SNS_E_STATE;
+                }
+                G.colind[(size_t)slot] = ent[k].first;
+                valmap[(size_t)ent[k].second] = slot;
+                if (ent[k].first == g) { G.diag[(size_t)g] = slot; has_diag = true; }
+            }
+            if (!has_diag) { set_error("replicated tail: row without a diagonal block"); return SNS_E_STATE; }
+        }
+    }
+    return SNS_OK;
+}
+
 // The lists of the boundary pass (csrc/sns_boundary.hip) from `nf` boundary facets and the tet that owns each: the facets rewound
 // so that (x1 - x0) x (x2 - x0) points away from the owner's fourth vertex, the boundary rows (the nodes of listed facets,
 // ascending) and per row its entries facet * 4 + local vertex in ascending facet order.  Throws, with nothing written, where a

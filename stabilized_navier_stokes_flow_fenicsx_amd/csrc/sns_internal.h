@@ -67,6 +67,48 @@ void build_aggregation_active(const HostPattern& fine, int32_t n_active, int max
 void build_coarse_from_agg(const HostPattern& F, int32_t n_owned_fine, const std::vector<int32_t>& agg_all,
                            int32_t nc_owned, int32_t nc_total, HostAggregation& A);
 
+// ---- host index logic of the distributed hierarchy build (sns_host.cpp; tests/hierarchy_host_main.cpp) ----------------------
+// the host half of a level's halo plan (counts in nodes); Plan (csrc/sns_comm.h) adds the device half
+struct HaloLists {
+    std::vector<int> nbr;                        // neighbour ranks, same order on both sides of a link
+    std::vector<int32_t> send_ptr, recv_ptr;     // per neighbour: its range of h_send_idx / h_recv_idx
+    std::vector<int32_t> h_send_idx, h_recv_idx; // local nodes sent / ghost nodes received
+    int32_t n_own = 0;                           // owned nodes of the level (the ghost nodes follow them)
+};
+// where a level's ghost nodes live: owner rank and owner-local id of ghost q (local node n_owned + q).  Owned by the build.
+struct GhostIds {
+    std::vector<int32_t> own, gid;
+};
+// the points of the coarse nodes: the centroids of the aggregates (members summed in node order, divided by their count)
+std::vector<double> aggregate_centroids(const double* pts, int32_t n, const std::vector<int32_t>& agg, int32_t nc);
+// The coarse level's halo lists from the finer level's `p` and `owner_agg` (per local node of the finer level; read at the ghost
+// nodes: the aggregate of the node on its owner, as exchanged).  Per link the distinct aggregates in ascending owner id become
+// the ghost coarse nodes nc_owned, nc_owned + 1, ... (agg's ghost entries are filled in with them) and the distinct aggregates
+// of the nodes sent the send list: both ends of a link sort the same set of ids, so the k-th sent is the k-th received.
+// SNS_E_COMM (text set) for a ghost node whose owner gave it no aggregate.
+int coarse_halo_lists(const HaloLists& p, const std::vector<int32_t>& owner_agg, int32_t nc_owned, std::vector<int32_t>& agg,
+                      HaloLists& coarse, GhostIds& ghosts, int32_t& nc_total);
+// The replicated level: rank r's rows[r] owned rows of the source level become rows off[r] .. of the global pattern.  What
+// every rank all-gathers is a record of maxn + maxnz doubles: [0, maxn) its row lengths, then the global column ids of its slots
+// (-1: padding).
+struct ReplicatedLayout {
+    std::vector<int32_t> rows;                   // per rank
+    std::vector<int64_t> off;                    // nranks + 1
+    int32_t maxn = 1, NG = 0;
+    int64_t maxnz = 1;
+    size_t record() const { return (size_t)maxn + (size_t)maxnz; }
+};
+ReplicatedLayout replicated_layout(int nranks, const double* rows_then_slots /* 2 * nranks, summed over the ranks */);
+// local column j of rank `me` (owned, or ghost q = j - n_owned) -> id in the replicated level; -1: a ghost without an owner record
+int64_t replicated_id(const ReplicatedLayout& lay, int me, int32_t n_owned, const GhostIds& ghosts, int32_t j);
+// rank `me`'s record; SNS_E_STATE (text set) for a ghost column without an owner record
+int replicated_record(const ReplicatedLayout& lay, int me, const HostPattern& cur, int32_t n_owned, const GhostIds& ghosts,
+                      std::vector<double>& mine);
+// the global pattern G from the ranks' records `all`, with valmap [nranks * maxnz]: gathered slot -> slot of G (-1: padding)
+// and rowmap [max(1, NG)]: row of G -> gathered row rank * maxn + i.  SNS_E_STATE (text set) for an inconsistent pattern
+int replicated_pattern(const ReplicatedLayout& lay, const std::vector<double>& all, HostPattern& G, std::vector<int32_t>& valmap,
+                       std::vector<int32_t>& rowmap);
+
 // ---- device-side level of the operator hierarchy ----------------------------
 // (move-only: every device array is owned by the level, csrc/sns_devbuf.h)
 struct Level {
@@ -77,6 +119,7 @@ struct Level {
     DevBuf<int32_t> rowptr, colind, diag;
     DevBuf<double> vals;                 // nnzb*16, block row-major
     DevBuf<double> dinv;                 // n*16
+    DevBuf<int32_t> slot_row;            // nnzb: block row of each slot
     DevBuf<float> vals32;                // fp32 copy of vals for the preconditioner passes (amg_f32_matrix)
     DevBuf<void> vals16;                 // fp16 copy, row-scaled (amg_f32_matrix = 2): 4 halfs per block row
     DevBuf<float> scale16;               // its scales, one per dof row
@@ -88,6 +131,8 @@ struct Level {
     DevBuf<int64_t> r_ptr;
     DevBuf<int32_t> r_idx;
     DevBuf<uint8_t> free_mask;           // 4*n: 1 where dof takes part in transfer (level 0: !bc), else all 1
+    DevBuf<uint8_t> empty_c;             // 4*nc, the fine level only.  Held by level l, it flags the dofs of level l + 1 (the coarse
+                                         // side): per aggregate and component, the members excluded from the transfer (k_empty_coarse)
     // M = A P of this level for the fused first post-smoothing sweep (k_post_lp): pattern + gather lists (symbolic, once),
     // values per numeric setup straight into the level's low-precision format (k_lp_copies16 / k_ap_cvt32)
     int64_t ap_nnz = 0;
@@ -106,6 +151,7 @@ struct Level {
     int binv_fmt = 0;
     // work vectors (4*n doubles)
     DevBuf<double> x, b, r;
+    DevBuf<double> pong;                 // the smoother's ping-pong buffer
     DevBuf<double> xg;                   // distributed runs: copy of the iterate whose ghost tail is exchanged
     // coarsest level: dense inverse (4n x 4n), row-major
     DevBuf<double> dense_inv;

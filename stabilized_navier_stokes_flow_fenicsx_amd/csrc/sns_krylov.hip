@@ -38,7 +38,7 @@ double* fused_first_sweep_target(sns_ctx* h, double* zdst) {
     if (P.blocks && L.n_blk <= 0) return nullptr;                // (aggregate blocks: k_bfirst_bicg, see fused_vector_kernel)
     if (h->rep_level == 1) return nullptr;                       // level 0 is only the source of the replicated copy
     double* x = (h->n > h->n_owned && !h->plan.fine_tails_unused) ? h->levels[0].x : zdst;   // (as pc_apply chooses the cycle's vector)
-    return P.start_odd ? h->pong[0] : x;
+    return P.start_odd ? h->levels[0].pong : x;
 }
 
 // the put that kernel carries (k_bfirst_bicg): empty unless the fine level runs the window form of the cycle

@@ -164,18 +164,18 @@ __global__ __launch_bounds__(256) void k_free_from_mask(int64_t ndof, const uint
 
 // The fine level's free mask follows the operator in the handle: the hierarchy's transfer operators leave out the Dirichlet dofs
 // of THAT operator -- the scalars' while the scalar operator is the handle's matrix, the flow's again from the next flow assembly
-// on (csrc/sns_assemble.hip).  The mask and the per-aggregate counts derived from it (empty_c[0], once the hierarchy exists) are
+// on (csrc/sns_assemble.hip).  The mask and the per-aggregate counts derived from it (levels[0].empty_c, once the hierarchy exists) are
 // rewritten in place; everything else that depends on them is rebuilt by the set-up every assembly makes stale.  Handles
 // without a communicator only (the ghost part of a partitioned handle's mask is not the complement of its Dirichlet mask).
 int fine_free_mask(sns_ctx* h, const uint8_t* dirichlet_mask) {
     Level& L = h->levels[0];
     const int64_t ld = ld_of(h);
     hipLaunchKernelGGL(k_free_from_mask, dim3(vec_grid(ld)), dim3(256), 0, h->stream, ld, dirichlet_mask, L.free_mask.get());
-    if (h->levels.size() > 1 && h->empty_c[0]) {
+    if (h->levels.size() > 1 && h->levels[0].empty_c) {
         const int32_t nc = h->levels[1].n_owned;
         if (nc > 0)
             hipLaunchKernelGGL(k_empty_coarse, dim3((unsigned)((4 * (int64_t)nc + 255) / 256)), dim3(256), 0, h->stream, nc, L.m_ptr,
-                               L.m_idx, L.free_mask, h->empty_c[0]);
+                               L.m_idx, L.free_mask, L.empty_c);
     }
     HIP_TRY(hipGetLastError());
     return SNS_OK;

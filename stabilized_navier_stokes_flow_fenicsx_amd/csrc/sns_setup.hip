@@ -17,7 +17,7 @@ int alloc_level_vectors(Level& L) {
 }
 
 
-int upload_pattern(Level& L, const HostPattern& P, DevBuf<int32_t>& slot_row, hipStream_t s) {
+int upload_pattern(Level& L, const HostPattern& P, hipStream_t s) {
     L.n = P.n;
     L.nnzb = P.nnzb;
     SNS_TRY(L.rowptr.upload(P.rowptr));
@@ -25,8 +25,8 @@ int upload_pattern(Level& L, const HostPattern& P, DevBuf<int32_t>& slot_row, hi
     SNS_TRY(L.diag.upload(P.diag));
     SNS_TRY(L.vals.alloc((size_t)P.nnzb * 16));
     SNS_TRY(L.dinv.alloc((size_t)P.n * 16));
-    SNS_TRY(slot_row.alloc((size_t)P.nnzb));
-    hipLaunchKernelGGL(k_fill_slot_row, dim3((P.n + 255) / 256), dim3(256), 0, s, P.n, L.rowptr, slot_row);
+    SNS_TRY(L.slot_row.alloc((size_t)P.nnzb));
+    hipLaunchKernelGGL(k_fill_slot_row, dim3((P.n + 255) / 256), dim3(256), 0, s, P.n, L.rowptr, L.slot_row);
     return SNS_OK;
 }
 
@@ -114,21 +114,23 @@ int connect_plan(sns_ctx* h, Plan& p) {
 }
 
 
-int append_level(sns_ctx* h, const HostPattern& P, int32_t n_owned, bool with_xg) {
+// Append a level with the pattern P (rows [0, n_owned) owned; n_global: its rows over all ranks): operator arrays, work vectors,
+// the ping-pong buffer and, with_xg, the exchanged copy of the iterate.  pong and xg hold 4 * max(1, n) doubles on every path
+// (a partitioned level of a rank with no row and no ghost on it used to get one double where the replicated tail gave four).
+// The only place that appends to h->levels after level 0; a std::deque: no reference to a finer level moves.
+static int append_level(sns_ctx* h, const HostPattern& P, int32_t n_owned, int64_t n_global, bool with_xg) {
     h->levels.emplace_back();
-    h->slot_row.emplace_back();
-    h->empty_c.emplace_back();
-    h->pong.emplace_back();
     Level& C = h->levels.back();
-    SNS_TRY(upload_pattern(C, P, h->slot_row.back(), h->stream));
+    SNS_TRY(upload_pattern(C, P, h->stream));
     C.n_owned = n_owned;
-    C.n_global = n_owned;                        // (append_level serves the replicated tail: every rank holds all rows)
+    C.n_global = n_global;
     SNS_TRY(alloc_level_vectors(C));
-    SNS_TRY(h->pong.back().alloc(4 * (size_t)std::max(1, C.n)));
-    HIP_TRY(hipMemset(h->pong.back(), 0, 4 * (size_t)std::max(1, C.n) * sizeof(double)));
+    const size_t nd = 4 * (size_t)std::max(1, C.n);
+    SNS_TRY(C.pong.alloc(nd));
+    HIP_TRY(hipMemset(C.pong, 0, nd * sizeof(double)));
     if (with_xg) {
-        SNS_TRY(C.xg.alloc(4 * (size_t)std::max(1, C.n)));
-        HIP_TRY(hipMemset(C.xg, 0, 4 * (size_t)std::max(1, C.n) * sizeof(double)));
+        SNS_TRY(C.xg.alloc(nd));
+        HIP_TRY(hipMemset(C.xg, 0, nd * sizeof(double)));
     }
     return SNS_OK;
 }
@@ -205,179 +207,186 @@ int alloc_coarsest_solver(sns_ctx* h, Level& last) {
     return SNS_OK;
 }
 
+// ... and of a hierarchy that ends partitioned: the global dense inverse, replicated on every rank (rank r's node i -> padded id
+// r * maxn + i; `ghosts`: the owners of the last level's ghost nodes).  Collective: one global sum.  Too large: smoothed.
+static int alloc_distributed_coarsest_solver(sns_ctx* h, Level& last, const GhostIds& ghosts) {
+    const Comm* c = h->comm.get();
+    std::vector<double> cnt(c->nranks, 0.0);
+    cnt[c->rank] = (double)last.n_owned;
+    SNS_TRY(global_sum(h, cnt.data(), c->nranks));
+    int maxn = 0;
+    h->cg_counts.resize(c->nranks);
+    for (int r = 0; r < c->nranks; ++r) { h->cg_counts[r] = (int)cnt[r]; maxn = std::max(maxn, (int)cnt[r]); }
+    const int N = 4 * c->nranks * std::max(1, maxn);
+    if (N > policy::DISTRIBUTED_DENSE_MAX_DOFS) return SNS_OK;
+    h->cg_maxn = std::max(1, maxn);
+    h->cg_N = N;
+    std::vector<int32_t> cmap((size_t)last.n, 0);
+    for (int32_t i = 0; i < last.n_owned; ++i) cmap[i] = c->rank * h->cg_maxn + i;
+    for (size_t q = 0; q < ghosts.own.size(); ++q) cmap[(size_t)last.n_owned + q] = ghosts.own[q] * h->cg_maxn + ghosts.gid[q];
+    SNS_TRY(h->cg_colmap.upload(cmap));
+    SNS_TRY(h->cg_rows.alloc((size_t)4 * h->cg_maxn * N));
+    SNS_TRY(h->cg_full.alloc((size_t)N * N));
+    SNS_TRY(h->cg_send.alloc((size_t)4 * h->cg_maxn));
+    SNS_TRY(h->cg_recv.alloc((size_t)N));
+    SNS_TRY(h->d_piv.alloc((size_t)N));
+    return SNS_OK;
+}
+
+
+// ---- the stages of the symbolic build: build_hierarchy and build_replicated_tail below call them in this order ------------------
+// The level being coarsened, carried from one step to the next and owned by the build: its local pattern (owned rows, then
+// empty ghost rows), its nodes' coordinates (coarse levels: the aggregates' centroids; empty: none, as in 2-D) and the owners of
+// its ghost nodes.
+struct Front {
+    HostPattern cur;
+    int32_t n_owned = 0;
+    std::vector<double> pts;
+    GhostIds ghosts;
+    const double* points() const { return pts.size() == (size_t)3 * cur.n ? pts.data() : nullptr; }
+};
+
+static int agg_size(const sns_options& o) { return std::min(255, std::max(2, o.amg_agg_size)); }
+
+// One coarsening step on the device: the transfer arrays of level l (pattern `f.cur`) from its aggregation A, its smoother blocks
+// and M = A P, then the coarse level appended (append_level).  Beside level 0 these two functions are the only place that fills or
+// appends a Level.  What differs between the callers is said by them:
+//   n_global  the coarse level's rows over all ranks (a replicated level: its own rows);
+//   with_ap   M = A P for the fused post-sweep: every level of a serial hierarchy and of the replicated tail; of the partitioned
+//             levels the fine one (its single post-sweep is the exact global sweep, the coarse ones smooth rank-locally) and, on
+//             the window transports, all of them (the exact-sweep cycle takes the fused post-sweep too);
+//   with_xg   the coarse level is partitioned: it exchanges halos.
+static int add_next_level(sns_ctx* h, int l, const Front& f, const HostAggregation& A, int64_t n_global, bool with_ap, bool with_xg) {
+    Level& L = h->levels[l];
+    L.nc = A.nc;
+    SNS_TRY(L.agg.upload(A.agg));
+    SNS_TRY(L.m_ptr.upload(A.m_ptr));
+    SNS_TRY(L.m_idx.upload(A.m_idx));
+    SNS_TRY(L.r_ptr.upload(A.r_ptr));
+    SNS_TRY(L.r_idx.upload(A.r_idx));
+    SNS_TRY(upload_block_rows(h, l, L, A.m_ptr, A.m_idx, A.nc));
+    if (with_ap) SNS_TRY(upload_ap(h, L, f.cur, f.n_owned, A.agg));
+    return append_level(h, A.coarse, A.nc, n_global, with_xg);
+}
+
+// carry the front forward: the coarse pattern, its nodes (the aggregates' centroids) and the owners of its ghosts
+static void advance(Front& f, HostAggregation& A, GhostIds&& ghosts) {
+    const double* pts = f.points();
+    f.pts = pts ? aggregate_centroids(pts, f.cur.n, A.agg, A.coarse.n) : std::vector<double>();
+    f.cur = std::move(A.coarse);
+    f.n_owned = A.nc;
+    f.ghosts = std::move(ghosts);
+}
+
+// the ranks' shares of the source level (collective: one global sum of 2 * nranks counts)
+static int agree_replicated_layout(sns_ctx* h, const Front& f, ReplicatedLayout& lay) {
+    const Comm* c = h->comm.get();
+    const int nr = c->nranks;
+    std::vector<double> cnt((size_t)2 * nr, 0.0);
+    cnt[c->rank] = (double)f.n_owned;
+    cnt[nr + c->rank] = (double)f.cur.rowptr[f.n_owned];
+    SNS_TRY(global_sum(h, cnt.data(), 2 * nr));
+    lay = replicated_layout(nr, cnt.data());
+    return SNS_OK;
+}
+
+// the global pattern from every rank's rows (collective: one all-gather -- which a rank with a bad ghost record does not reach)
+static int gather_replicated_pattern(sns_ctx* h, const Front& f, const ReplicatedLayout& lay, HostPattern& G,
+                                     std::vector<int32_t>& valmap, std::vector<int32_t>& rowmap) {
+    std::vector<double> mine, all;
+    SNS_TRY(replicated_record(lay, h->comm->rank, f.cur, f.n_owned, f.ghosts, mine));
+    SNS_TRY(host_allgather(h, mine, all));
+    return replicated_pattern(lay, all, G, valmap, rowmap);
+}
+
+// What the cycle knows of the replicated level R, appended next.  Window transports: the right-hand sides go straight to their
+// rows of it (comm_allgatherv: rep_doff / rep_dcnt), and the level above the source reads the coarse solution of its fused
+// correction + post-sweep straight from the replicated solution: the columns of its M = A P (local ids of the source level:
+// owned, then ghosts) in the replicated level's ids.
+static int record_replicated_level(sns_ctx* h, int R, const Front& f, const ReplicatedLayout& lay) {
+    const int nr = h->comm->nranks, me = h->comm->rank;
+    h->rep_level = (int)h->levels.size();
+    h->rep_maxn = lay.maxn;
+    h->rep_maxnz = lay.maxnz;
+    h->rep_NG = lay.NG;
+    h->rep_off = (int32_t)lay.off[me];
+    std::vector<int64_t> doff((size_t)nr), dcnt((size_t)nr);
+    for (int r = 0; r < nr; ++r) { doff[(size_t)r] = 4 * lay.off[r]; dcnt[(size_t)r] = 4 * (int64_t)lay.rows[r]; }
+    SNS_TRY(h->rep_doff.upload(doff));
+    SNS_TRY(h->rep_dcnt.upload(dcnt));
+    Level& A = h->levels[R - 1];
+    // (a rank without rows on that level uploads the empty list all the same: the plan asks whether it exists on every rank)
+    if (R < 2 || !A.ap_colind) return SNS_OK;
+    std::vector<int32_t> col((size_t)A.ap_nnz);
+    if (!col.empty()) HIP_TRY(hipMemcpy(col.data(), A.ap_colind, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (auto& j : col) {
+        const int64_t g = replicated_id(lay, me, f.n_owned, f.ghosts, j);
+        if (g < 0) { set_error("replicated tail: ghost aggregate without an owner record"); return SNS_E_STATE; }
+        j = (int32_t)g;
+    }
+    return A.ap_colind_rep.upload(col);
+}
+
+// the buffers the numeric set-up and the cycle move the source level's values and right-hand sides through
+static int alloc_replicated_transfer(sns_ctx* h, const ReplicatedLayout& lay, const std::vector<int32_t>& valmap,
+                                     const std::vector<int32_t>& rowmap) {
+    const size_t nr = (size_t)h->comm->nranks, maxn = (size_t)lay.maxn, maxnz = (size_t)lay.maxnz;
+    SNS_TRY(h->rep_valmap.upload(valmap));
+    SNS_TRY(h->rep_rowmap.upload(rowmap));
+    SNS_TRY(h->rep_vsend.alloc(maxnz * 16));
+    SNS_TRY(h->rep_vrecv.alloc(maxnz * 16 * nr));
+    SNS_TRY(h->rep_bsend.alloc(maxn * 4));
+    SNS_TRY(h->rep_brecv.alloc(maxn * 4 * nr));
+    HIP_TRY(hipMemset(h->rep_vsend, 0, maxnz * 16 * sizeof(double)));
+    HIP_TRY(hipMemset(h->rep_bsend, 0, maxn * 4 * sizeof(double)));
+    return SNS_OK;
+}
+
+// the replicated level's node coordinates, all-gathered like its pattern, so that its aggregation sees shapes, not only numbers
+// (collective: a global sum, and the all-gather where every rank has coordinates); empty: none
+static int gather_replicated_points(sns_ctx* h, const Front& f, const ReplicatedLayout& lay, std::vector<double>& gpts) {
+    gpts.clear();
+    double have[1] = {f.points() ? 0.0 : 1.0};
+    SNS_TRY(global_sum(h, have, 1));
+    if (have[0] != 0.0) return SNS_OK;
+    std::vector<double> pm((size_t)3 * lay.maxn, 0.0), pa;
+    for (int32_t i = 0; i < f.n_owned; ++i)
+        for (int k = 0; k < 3; ++k) pm[3 * (size_t)i + k] = f.pts[3 * (size_t)i + k];
+    SNS_TRY(host_allgather(h, pm, pa));
+    gpts.resize((size_t)3 * lay.NG);
+    for (size_t r = 0; r < lay.rows.size(); ++r)
+        for (int32_t i = 0; i < lay.rows[r]; ++i)
+            for (int k = 0; k < 3; ++k) gpts[3 * ((size_t)lay.off[r] + i) + k] = pa[r * pm.size() + 3 * (size_t)i + k];
+    return SNS_OK;
+}
+
 // Multi-GPU: from level R on, every rank holds the GLOBAL operator (values all-gathered at every numeric setup)
 // and cycles the rest of the hierarchy redundantly: no exchanges below R, and the smoothing there is the exact
 // global block-Jacobi instead of a rank-local one (thin partitions lose their convergence on the deep levels
-// otherwise).  `cur` is the local pattern of level R (owned rows, local column ids), collective over the ranks.
-int build_replicated_tail(sns_ctx* h, int R, const HostPattern& cur, int32_t n_owned, const std::vector<double>& cur_pts) {
+// otherwise).  `src` is the front at level R, the source of the copy: levels[R + 1] becomes the replicated level.  Collective.
+static int build_replicated_tail(sns_ctx* h, int R, const Front& src) {
     const sns_options& o = h->opt;
-    Comm* c = h->comm.get();
-    const int nr = c->nranks, me = c->rank;
-    std::vector<double> cnt((size_t)2 * nr, 0.0);
-    cnt[me] = (double)n_owned;
-    cnt[nr + me] = (double)cur.rowptr[n_owned];
-    SNS_TRY(global_sum(h, cnt.data(), 2 * nr));
-    std::vector<int64_t> off((size_t)nr + 1, 0);
-    int32_t maxn = 1;
-    int64_t maxnz = 1;
-    for (int r = 0; r < nr; ++r) {
-        off[r + 1] = off[r] + (int64_t)cnt[r];
-        maxn = std::max(maxn, (int32_t)cnt[r]);
-        maxnz = std::max(maxnz, (int64_t)cnt[nr + r]);
-    }
-    const int32_t NG = (int32_t)off[nr];
-    const std::vector<int32_t>& g_own = h->ghost_own[R];
-    const std::vector<int32_t>& g_gid = h->ghost_gid[R];
-    // [0, maxn): row lengths; [maxn, maxn + maxnz): global column ids of my slots
-    std::vector<double> mine((size_t)maxn + (size_t)maxnz, -1.0), all;
-    for (int32_t i = 0; i < maxn; ++i) mine[i] = i < n_owned ? (double)(cur.rowptr[i + 1] - cur.rowptr[i]) : 0.0;
-    for (int32_t sidx = 0; sidx < cur.rowptr[n_owned]; ++sidx) {
-        const int32_t j = cur.colind[sidx];
-        int64_t gj;
-        if (j < n_owned) gj = off[me] + j;
-        else {
-            const size_t q = (size_t)(j - n_owned);
-            if (q >= g_own.size()) { set_error("replicated tail: ghost column without an owner record"); return SNS_E_STATE; }
-            gj = off[g_own[q]] + g_gid[q];
-        }
-        mine[(size_t)maxn + sidx] = (double)gj;
-    }
-    SNS_TRY(host_allgather(h, mine, all));
-    HostPattern G;
-    G.n = NG;
-    G.rowptr.assign((size_t)NG + 1, 0);
-    std::vector<int32_t> valmap((size_t)nr * maxnz, -1), rowmap((size_t)std::max(1, NG), 0);
-    const size_t LEN = mine.size();
-    for (int r = 0; r < nr; ++r)
-        for (int32_t i = 0; i < (int32_t)cnt[r]; ++i) {
-            G.rowptr[(size_t)off[r] + i + 1] = (int32_t)all[r * LEN + i];
-            rowmap[(size_t)off[r] + i] = r * maxn + i;
-        }
-    for (int32_t g = 0; g < NG; ++g) G.rowptr[g + 1] += G.rowptr[g];
-    G.nnzb = G.rowptr[NG];
-    G.colind.resize((size_t)G.nnzb);
-    G.diag.assign((size_t)NG, 0);
-    std::vector<std::pair<int32_t, int32_t>> ent;
-    for (int r = 0; r < nr; ++r) {
-        int64_t src = 0;
-        for (int32_t i = 0; i < (int32_t)cnt[r]; ++i) {
-            const int32_t g = (int32_t)off[r] + i;
-            const int32_t len = (int32_t)all[r * LEN + i];
-            ent.clear();
-            for (int32_t k = 0; k < len; ++k, ++src)
-                ent.emplace_back((int32_t)all[r * LEN + maxn + src], (int32_t)(r * maxnz + src));
-            std::sort(ent.begin(), ent.end());
-            bool has_diag = false;
-            for (int32_t k = 0; k < len; ++k) {
-                const int32_t slot = G.rowptr[g] + k;
-                if (ent[k].first < 0 || ent[k].first >= NG || (k > 0 && ent[k].first == ent[k - 1].first)) {
-                    set_error("replicated tail: inconsistent global pattern");
-                    return SNS_E_STATE;
-                }
-                G.colind[slot] = ent[k].first;
-                valmap[ent[k].second] = slot;
-                if (ent[k].first == g) { G.diag[g] = slot; has_diag = true; }
-            }
-            if (!has_diag) { set_error("replicated tail: row without a diagonal block"); return SNS_E_STATE; }
-        }
-    }
-    h->rep_level = (int)h->levels.size();
-    h->rep_maxn = maxn;
-    h->rep_maxnz = maxnz;
-    h->rep_NG = NG;
-    h->rep_off = (int32_t)off[me];
-    {
-        // window transports: the right-hand sides go straight to their rows of the replicated level (comm_allgatherv) ...
-        std::vector<int64_t> doff((size_t)nr), dcnt((size_t)nr);
-        for (int r = 0; r < nr; ++r) { doff[(size_t)r] = 4 * off[r]; dcnt[(size_t)r] = 4 * (int64_t)cnt[r]; }
-        SNS_TRY(h->rep_doff.upload(doff));
-        SNS_TRY(h->rep_dcnt.upload(dcnt));
-        // ... and the level above the source reads the coarse solution of its fused correction + post-sweep straight from the
-        // replicated solution: the columns of its M = A P (local ids of level R: owned, then ghosts) in the replicated level's ids
-        Level& A = h->levels[R - 1];
-        // (a rank without rows on that level uploads the empty list all the same: the plan asks whether it exists on every rank)
-        if (R >= 2 && A.ap_colind) {
-            std::vector<int32_t> col((size_t)A.ap_nnz);
-            if (!col.empty()) HIP_TRY(hipMemcpy(col.data(), A.ap_colind, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            for (auto& j : col) {
-                if (j < n_owned) j = (int32_t)off[me] + j;
-                else {
-                    const size_t q = (size_t)(j - n_owned);
-                    if (q >= g_own.size()) { set_error("replicated tail: ghost aggregate without an owner record"); return SNS_E_STATE; }
-                    j = (int32_t)off[g_own[q]] + g_gid[q];
-                }
-            }
-            SNS_TRY(A.ap_colind_rep.upload(col));
-        }
-    }
-    SNS_TRY(append_level(h, G, NG, false));
-    h->ghost_own.emplace_back();
-    h->ghost_gid.emplace_back();
-    SNS_TRY(h->rep_valmap.upload(valmap));
-    SNS_TRY(h->rep_rowmap.upload(rowmap));
-    SNS_TRY(h->rep_vsend.alloc((size_t)maxnz * 16));
-    SNS_TRY(h->rep_vrecv.alloc((size_t)maxnz * 16 * nr));
-    SNS_TRY(h->rep_bsend.alloc((size_t)maxn * 4));
-    SNS_TRY(h->rep_brecv.alloc((size_t)maxn * 4 * nr));
-    HIP_TRY(hipMemset(h->rep_vsend, 0, (size_t)maxnz * 16 * sizeof(double)));
-    HIP_TRY(hipMemset(h->rep_bsend, 0, (size_t)maxn * 4 * sizeof(double)));
-    // the replicated level's node coordinates (all-gathered like its pattern), so that its aggregation sees shapes, not only numbers
-    std::vector<double> gpts;
-    {
-        double have[1] = {cur_pts.size() == (size_t)3 * cur.n ? 0.0 : 1.0};
-        SNS_TRY(global_sum(h, have, 1));
-        if (have[0] == 0.0) {
-            std::vector<double> pm((size_t)3 * maxn, 0.0), pa;
-            for (int32_t i = 0; i < n_owned; ++i)
-                for (int k = 0; k < 3; ++k) pm[3 * (size_t)i + k] = cur_pts[3 * (size_t)i + k];
-            SNS_TRY(host_allgather(h, pm, pa));
-            gpts.resize((size_t)3 * NG);
-            for (int r = 0; r < nr; ++r)
-                for (int32_t i = 0; i < (int32_t)cnt[r]; ++i)
-                    for (int k = 0; k < 3; ++k) gpts[3 * ((size_t)off[r] + i) + k] = pa[(size_t)r * pm.size() + 3 * (size_t)i + k];
-        }
-    }
+    ReplicatedLayout lay;
+    SNS_TRY(agree_replicated_layout(h, src, lay));
+    Front f;                                                  // the replicated level: every row owned, no ghosts
+    std::vector<int32_t> valmap, rowmap;
+    SNS_TRY(gather_replicated_pattern(h, src, lay, f.cur, valmap, rowmap));
+    SNS_TRY(record_replicated_level(h, R, src, lay));
+    SNS_TRY(append_level(h, f.cur, lay.NG, lay.NG, false));
+    SNS_TRY(alloc_replicated_transfer(h, lay, valmap, rowmap));
+    SNS_TRY(gather_replicated_points(h, src, lay, f.pts));
+    f.n_owned = lay.NG;
     // plain serial aggregation below (identical on every rank: same input, deterministic code)
-    HostPattern curp = std::move(G);
-    int32_t n_own = NG;
     for (int l = h->rep_level; (int)h->levels.size() < o.amg_max_levels + 1; ++l) {
-        if (n_own <= policy::coarsest_rows(o)) break;
+        if (f.n_owned <= policy::coarsest_rows(o)) break;
         std::vector<int32_t> agg;
         int32_t nc = 0;
-        aggregate_nodes(curp, n_own, std::min(255, std::max(2, o.amg_agg_size)), agg, nc,
-                        gpts.size() == (size_t)3 * n_own ? gpts.data() : nullptr);
-        if (nc >= n_own || nc == 0) break;
-        if (gpts.size() == (size_t)3 * n_own) {              // the next level's nodes: the aggregates' centroids
-            std::vector<double> cp((size_t)3 * nc, 0.0);
-            std::vector<int32_t> cn((size_t)nc, 0);
-            for (int32_t i = 0; i < n_own; ++i) {
-                const int32_t I = agg[i];
-                if (I < 0) continue;
-                for (int k = 0; k < 3; ++k) cp[3 * (size_t)I + k] += gpts[3 * (size_t)i + k];
-                ++cn[I];
-            }
-            for (int32_t I = 0; I < nc; ++I)
-                if (cn[I]) for (int k = 0; k < 3; ++k) cp[3 * (size_t)I + k] /= cn[I];
-            gpts = std::move(cp);
-        }
+        aggregate_nodes(f.cur, f.n_owned, agg_size(o), agg, nc, f.points());
+        if (nc >= f.n_owned || nc == 0) break;
         HostAggregation A;
-        build_coarse_from_agg(curp, n_own, agg, nc, nc, A);
-        {
-            Level& L = h->levels[l];
-            L.nc = nc;
-            SNS_TRY(L.agg.upload(A.agg));
-            SNS_TRY(L.m_ptr.upload(A.m_ptr));
-            SNS_TRY(L.m_idx.upload(A.m_idx));
-            SNS_TRY(L.r_ptr.upload(A.r_ptr));
-            SNS_TRY(L.r_idx.upload(A.r_idx));
-            SNS_TRY(upload_block_rows(h, l, L, A.m_ptr, A.m_idx, nc));
-            SNS_TRY(upload_ap(h, L, curp, n_own, A.agg));
-        }
-        SNS_TRY(append_level(h, A.coarse, nc, false));
-        h->ghost_own.emplace_back();
-        h->ghost_gid.emplace_back();
-        curp = std::move(A.coarse);
-        n_own = nc;
+        build_coarse_from_agg(f.cur, f.n_owned, agg, nc, nc, A);
+        SNS_TRY(add_next_level(h, l, f, A, nc, true, false));
+        advance(f, A, GhostIds());
     }
     SNS_TRY(alloc_coarsest_solver(h, h->levels.back()));
     h->tm.amg_levels = (int)h->levels.size() - 1;
@@ -419,198 +428,147 @@ static int aggregate_fine_by_strength(sns_ctx* h, const HostPattern& fine, const
     return SNS_OK;
 }
 
+// the front at the fine level, the fine rows over all ranks (collective: one global sum) and level 0's exchanged vector
+static int start_front(sns_ctx* h, const HostPattern& fine, bool dist, Front& f) {
+    f.cur = fine;
+    f.n_owned = h->n_owned;
+    f.pts = h->dim == 3 ? std::move(h->host_pts) : std::vector<double>();
+    h->host_pts = std::vector<double>();
+    h->fine_rematched_local = h->fine_rematched = false;
+    double ng[1] = {(double)h->n_owned};
+    SNS_TRY(global_sum(h, ng, 1));
+    h->n_global_fine = (int64_t)ng[0];
+    h->n_global_l1 = 0;
+    Level& L0 = h->levels[0];
+    L0.n_global = h->n_global_fine;
+    if (dist && !L0.xg) {
+        SNS_TRY(L0.xg.alloc(4 * (size_t)L0.n));
+        HIP_TRY(hipMemset(L0.xg, 0, 4 * (size_t)L0.n * sizeof(double)));
+    }
+    return SNS_OK;
+}
+
+// partitioned, l >= 1, amg_replicate_rows > 0: do the ranks hand level l over to the replicated tail?  (collective: two global sums)
+static int agree_replication(sns_ctx* h, bool dist, int l, int32_t n_owned, bool& replicate) {
+    replicate = false;
+    if (!(dist && l >= 1 && h->opt.amg_replicate_rows > 0)) return SNS_OK;
+    double g[1] = {(double)n_owned};
+    SNS_TRY(global_sum(h, g, 1));
+    // the replicated level must fit the scratch vectors sized by the local fine level
+    double fits[1] = {g[0] <= (double)h->n_owned ? 0.0 : 1.0};
+    SNS_TRY(global_sum(h, fits, 1));
+    replicate = policy::replicate_from(h->opt, l, (int64_t)g[0], fits[0] == 0.0);
+    return SNS_OK;
+}
+
+// does any rank have more rows than a coarsest level may (collective: one global sum)?  Serial: level l >= 1 is solved directly
+// as soon as the coarsest solver takes it
+static int agree_more_levels(sns_ctx* h, bool dist, int l, int32_t n_owned, bool& more) {
+    const sns_options& o = h->opt;
+    const int per_rank_coarse = dist ? std::max(1, o.amg_coarse_size / h->comm->nranks) : o.amg_coarse_size;
+    double flag[1] = {n_owned > per_rank_coarse ? 1.0 : 0.0};
+    SNS_TRY(global_sum(h, flag, 1));
+    more = flag[0] != 0.0 && !(!dist && l >= 1 && n_owned <= policy::coarsest_rows(o));
+    return SNS_OK;
+}
+
+// aggregate the owned nodes of level l (agg: -1 at the ghost nodes) and agree on the outcome (collective: one global sum):
+// nc_global aggregates over all ranks; progress: fewer than there were nodes, and not none
+static int aggregate_level(sns_ctx* h, int l, const Front& f, std::vector<int32_t>& agg, int32_t& nc_owned, int64_t& nc_global,
+                           bool& progress) {
+    nc_owned = 0;
+    if (l == 0 && h->opt.amg_aggregation >= 1) {
+        SNS_TRY(aggregate_fine_by_strength(h, f.cur, f.points(), agg, nc_owned));
+    } else {
+        aggregate_nodes(f.cur, f.n_owned, agg_size(h->opt), agg, nc_owned, f.points());
+    }
+    if (l == 0) h->agg0 = agg;
+    // (+ whether the hybrid re-matched level-0 nodes of some rank: the fine level's blocks are uploaded on every rank or none)
+    double prog[3] = {(double)f.n_owned, (double)nc_owned, (l == 0 && h->fine_rematched_local) ? 1.0 : 0.0};
+    SNS_TRY(global_sum(h, prog, 3));
+    if (l == 0) h->fine_rematched = prog[2] > 0.0;
+    nc_global = (int64_t)prog[1];
+    progress = !(prog[1] >= prog[0] || prog[1] == 0.0);
+    if (l == 0 && progress) h->n_global_l1 = nc_global;
+    return SNS_OK;
+}
+
+// Partitioned levels: the aggregate of every ghost node on its owner, through level l's exchange (the ids ride in the first
+// component of xg, which is left zero again), and from them the coarse level's halo lists, its ghosts' owners and the ghost
+// entries of agg (coarse_halo_lists, csrc/sns_host.cpp).
+static int exchange_aggregate_ids(sns_ctx* h, int l, const Front& f, int32_t nc_owned, std::vector<int32_t>& agg, Plan& cplan,
+                                  GhostIds& cghosts, int32_t& nc_total) {
+    Comm* c = h->comm.get();
+    Level& L = h->levels[l];
+    std::vector<double> ids((size_t)4 * f.cur.n, -1.0);
+    for (int32_t i = 0; i < f.n_owned; ++i) ids[(size_t)4 * i] = (double)agg[i];
+    HIP_TRY(hipMemcpy(L.xg, ids.data(), ids.size() * sizeof(double), hipMemcpyHostToDevice));
+    SNS_TRY(comm_exchange(c, c->plans[l], L.xg, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(ids.data(), L.xg, ids.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(L.xg, 0, ids.size() * sizeof(double)));
+    std::vector<int32_t> owner_agg((size_t)f.cur.n);
+    for (int32_t i = 0; i < f.cur.n; ++i) owner_agg[(size_t)i] = (int32_t)ids[(size_t)4 * i];
+    return coarse_halo_lists(c->plans[l], owner_agg, nc_owned, agg, cplan, cghosts, nc_total);
+}
+
+// the plan of the level just appended: checked, uploaded, wired to the neighbours' windows (collective: check_plan_symmetry's
+// all-gather and, on the peer transport, connect_plan's) and handed to the communicator
+static int attach_plan(sns_ctx* h, Plan& cplan, int level) {
+    SNS_TRY(check_plan_symmetry(h, cplan, level));
+    SNS_TRY(plan_upload(cplan));
+    SNS_TRY(connect_plan(h, cplan));
+    h->comm->plans.push_back(std::move(cplan));
+    return SNS_OK;
+}
+
+// levels[0].empty_c: per aggregate of the fine level and component, the members a Dirichlet condition keeps out of the transfer
+static int flag_empty_aggregates(sns_ctx* h) {
+    Level& L = h->levels[0];
+    SNS_TRY(L.empty_c.alloc(4 * (size_t)std::max(1, L.nc)));
+    if (L.nc > 0)
+        hipLaunchKernelGGL(k_empty_coarse, dim3((unsigned)((4 * (int64_t)L.nc + 255) / 256)), dim3(256), 0, h->stream, L.nc, L.m_ptr,
+                           L.m_idx, L.free_mask, L.empty_c);
+    return SNS_OK;
+}
+
 // Build the aggregation hierarchy (symbolic, once per mesh; collective over the ranks).
 // Aggregates never cross ranks, but the Galerkin operators keep every cross-rank coupling:
 // a ghost fine node's aggregate becomes a ghost coarse node, and each level gets its own
 // halo plan derived from the finer one.  With one rank this is plain serial aggregation.
+// Every rank walks the same stages and so the same collectives: each `break` and the hand-over are decided from agreed values.
 int build_hierarchy(sns_ctx* h, const HostPattern& fine) {
-    const sns_options& o = h->opt;
     Comm* c = h->comm.get();
     const bool dist = c && c->active() && c->nranks > 1;
-    HostPattern cur = fine;
-    int32_t n_owned = h->n_owned;
-    std::vector<double> cur_pts = h->dim == 3 ? std::move(h->host_pts) : std::vector<double>();   // coordinates of `cur`'s nodes (coarse: centroids)
-    h->host_pts = std::vector<double>();
-    h->fine_rematched_local = h->fine_rematched = false;
-    {
-        double ng[1] = {(double)h->n_owned};
-        SNS_TRY(global_sum(h, ng, 1));
-        h->n_global_fine = (int64_t)ng[0];
-        h->n_global_l1 = 0;
-        h->levels[0].n_global = h->n_global_fine;
-    }
-    h->ghost_gid.assign(1, {});
-    h->ghost_own.assign(1, {});
-    const int per_rank_coarse = dist ? std::max(1, o.amg_coarse_size / c->nranks) : o.amg_coarse_size;
-    if (dist && !h->levels[0].xg) {
-        SNS_TRY(h->levels[0].xg.alloc(4 * (size_t)h->levels[0].n));
-        HIP_TRY(hipMemset(h->levels[0].xg, 0, 4 * (size_t)h->levels[0].n * sizeof(double)));
-    }
-    for (int l = 0; l + 1 < o.amg_max_levels; ++l) {
-        if (dist && l >= 1 && o.amg_replicate_rows > 0) {
-            double g[1] = {(double)n_owned};
-            SNS_TRY(global_sum(h, g, 1));
-            // the replicated level must fit the scratch vectors sized by the local fine level
-            double fits[1] = {g[0] <= (double)h->n_owned ? 0.0 : 1.0};
-            SNS_TRY(global_sum(h, fits, 1));
-            if (policy::replicate_from(o, l, (int64_t)g[0], fits[0] == 0.0)) {
-                SNS_TRY(build_replicated_tail(h, l, cur, n_owned, cur_pts));
-                return plan_hierarchy(h);
-            }
+    Front f;
+    SNS_TRY(start_front(h, fine, dist, f));
+    for (int l = 0; l + 1 < h->opt.amg_max_levels; ++l) {
+        bool replicate = false, more = false, progress = false;
+        SNS_TRY(agree_replication(h, dist, l, f.n_owned, replicate));
+        if (replicate) {
+            SNS_TRY(build_replicated_tail(h, l, f));
+            return plan_hierarchy(h);
         }
-        double flag[1] = {n_owned > per_rank_coarse ? 1.0 : 0.0};
-        SNS_TRY(global_sum(h, flag, 1));
-        if (flag[0] == 0.0) break;
-        if (!dist && l >= 1 && n_owned <= policy::coarsest_rows(o)) break;       // serial: this level is solved directly
+        SNS_TRY(agree_more_levels(h, dist, l, f.n_owned, more));
+        if (!more) break;
         std::vector<int32_t> agg;
         int32_t nc_owned = 0;
-        const double* pts = cur_pts.size() == (size_t)3 * cur.n ? cur_pts.data() : nullptr;
-        if (l == 0 && o.amg_aggregation >= 1) {
-            SNS_TRY(aggregate_fine_by_strength(h, cur, pts, agg, nc_owned));
-        } else {
-            aggregate_nodes(cur, n_owned, std::min(255, std::max(2, o.amg_agg_size)), agg, nc_owned, pts);
-        }
-        if (l == 0) h->agg0 = agg;
-        // (+ whether the hybrid re-matched level-0 nodes of some rank: the fine level's blocks below are uploaded on every rank or none)
-        double prog[3] = {(double)n_owned, (double)nc_owned, (l == 0 && h->fine_rematched_local) ? 1.0 : 0.0};
-        SNS_TRY(global_sum(h, prog, 3));
-        if (l == 0) h->fine_rematched = prog[2] > 0.0;
-        if (prog[1] >= prog[0] || prog[1] == 0.0) break;      // no progress anywhere
-        if (l == 0) h->n_global_l1 = (int64_t)prog[1];
+        int64_t nc_global = 0;
+        SNS_TRY(aggregate_level(h, l, f, agg, nc_owned, nc_global, progress));
+        if (!progress) break;                                  // no progress anywhere
         int32_t nc_total = nc_owned;
         Plan cplan;
-        std::vector<int32_t> g_own, g_gid;                     // ghost coarse nodes: owner rank, owner-local id
-        Level& L = h->levels[l];
-        if (dist) {
-            const Plan& p = c->plans[l];
-            std::vector<double> ids((size_t)4 * cur.n, -1.0);
-            for (int32_t i = 0; i < n_owned; ++i) ids[(size_t)4 * i] = (double)agg[i];
-            HIP_TRY(hipMemcpy(L.xg, ids.data(), ids.size() * sizeof(double), hipMemcpyHostToDevice));
-            SNS_TRY(comm_exchange(c, p, L.xg, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            HIP_TRY(hipMemcpy(ids.data(), L.xg, ids.size() * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemset(L.xg, 0, ids.size() * sizeof(double)));
-            cplan.nbr = p.nbr;
-            cplan.n_own = nc_owned;
-            cplan.send_ptr.assign(1, 0);
-            cplan.recv_ptr.assign(1, 0);
-            for (size_t k = 0; k < p.nbr.size(); ++k) {
-                std::vector<int32_t> u;
-                for (int32_t q = p.recv_ptr[k]; q < p.recv_ptr[k + 1]; ++q) {
-                    const int32_t rid = (int32_t)ids[(size_t)4 * p.h_recv_idx[q]];
-                    if (rid < 0) { set_error("hierarchy: ghost node without an aggregate on its owner"); return SNS_E_COMM; }
-                    u.push_back(rid);
-                }
-                std::sort(u.begin(), u.end());
-                u.erase(std::unique(u.begin(), u.end()), u.end());
-                for (int32_t q = p.recv_ptr[k]; q < p.recv_ptr[k + 1]; ++q) {
-                    const int32_t gnode = p.h_recv_idx[q];
-                    const int32_t rid = (int32_t)ids[(size_t)4 * gnode];
-                    agg[gnode] = nc_total + (int32_t)(std::lower_bound(u.begin(), u.end(), rid) - u.begin());
-                }
-                for (size_t q = 0; q < u.size(); ++q) {
-                    cplan.h_recv_idx.push_back(nc_total + (int32_t)q);
-                    g_own.push_back(p.nbr[k]);
-                    g_gid.push_back(u[q]);
-                }
-                nc_total += (int32_t)u.size();
-                cplan.recv_ptr.push_back((int32_t)cplan.h_recv_idx.size());
-                std::vector<int32_t> sset;
-                for (int32_t q = p.send_ptr[k]; q < p.send_ptr[k + 1]; ++q) sset.push_back(agg[p.h_send_idx[q]]);
-                std::sort(sset.begin(), sset.end());
-                sset.erase(std::unique(sset.begin(), sset.end()), sset.end());
-                cplan.h_send_idx.insert(cplan.h_send_idx.end(), sset.begin(), sset.end());
-                cplan.send_ptr.push_back((int32_t)cplan.h_send_idx.size());
-            }
-        }
+        GhostIds cghosts;                                      // ghost coarse nodes: owner rank, owner-local id
+        if (dist) SNS_TRY(exchange_aggregate_ids(h, l, f, nc_owned, agg, cplan, cghosts, nc_total));
         HostAggregation A;
-        build_coarse_from_agg(cur, n_owned, agg, nc_owned, nc_total, A);
-        L.nc = nc_owned;
-        SNS_TRY(L.agg.upload(A.agg));
-        SNS_TRY(L.m_ptr.upload(A.m_ptr));
-        SNS_TRY(L.m_idx.upload(A.m_idx));
-        SNS_TRY(L.r_ptr.upload(A.r_ptr));
-        SNS_TRY(L.r_idx.upload(A.r_idx));
-        SNS_TRY(upload_block_rows(h, l, L, A.m_ptr, A.m_idx, nc_owned));
-        // M = A P for the fused first post-smoothing sweep: every level of a serial hierarchy; in a partitioned one the fine
-        // level only (its single post-sweep is the exact global sweep; the distributed coarse levels smooth rank-locally)
-        // ... and, on the window transports, every partitioned level: the exact-sweep cycle (plan exact) takes the fused post-sweep too
-        if (!dist || l == 0 || c->windows()) SNS_TRY(upload_ap(h, L, cur, n_owned, A.agg));
-        h->levels.emplace_back();
-        h->slot_row.emplace_back();
-        h->empty_c.emplace_back();
-        h->pong.emplace_back();
-        Level& C = h->levels.back();
-        if (&h->levels[l] != &L) { set_error("internal: level storage moved"); return SNS_E_STATE; }
-        SNS_TRY(upload_pattern(C, A.coarse, h->slot_row.back(), h->stream));
-        C.n_owned = nc_owned;
-        C.n_global = (int64_t)prog[1];
-        SNS_TRY(alloc_level_vectors(C));
-        SNS_TRY(h->pong.back().alloc(4 * (size_t)C.n));
-        HIP_TRY(hipMemset(h->pong.back(), 0, 4 * (size_t)C.n * sizeof(double)));
-        if (dist) {
-            SNS_TRY(C.xg.alloc(4 * (size_t)C.n));
-            HIP_TRY(hipMemset(C.xg, 0, 4 * (size_t)C.n * sizeof(double)));
-            SNS_TRY(check_plan_symmetry(h, cplan, l + 1));
-            SNS_TRY(plan_upload(cplan));
-            SNS_TRY(connect_plan(h, cplan));
-            c->plans.push_back(std::move(cplan));
-        }
-        h->ghost_own.push_back(std::move(g_own));
-        h->ghost_gid.push_back(std::move(g_gid));
-        if (l == 0) {
-            SNS_TRY(h->empty_c[0].alloc(4 * (size_t)std::max(1, nc_owned)));
-            if (nc_owned > 0)
-                hipLaunchKernelGGL(k_empty_coarse, dim3((unsigned)((4 * (int64_t)nc_owned + 255) / 256)), dim3(256), 0,
-                                   h->stream, nc_owned, L.m_ptr, L.m_idx, L.free_mask, h->empty_c[0]);
-        }
-        if (cur_pts.size() == (size_t)3 * cur.n) {
-            std::vector<double> cp((size_t)3 * nc_total, 0.0), cnt((size_t)nc_total, 0.0);
-            for (int32_t i = 0; i < cur.n; ++i) {
-                const int32_t I = A.agg[(size_t)i];
-                if (I < 0) continue;
-                for (int c3 = 0; c3 < 3; ++c3) cp[3 * (size_t)I + c3] += cur_pts[3 * (size_t)i + c3];
-                cnt[(size_t)I] += 1.0;
-            }
-            for (int32_t I = 0; I < nc_total; ++I)
-                if (cnt[(size_t)I] > 0.0) for (int c3 = 0; c3 < 3; ++c3) cp[3 * (size_t)I + c3] /= cnt[(size_t)I];
-            cur_pts = std::move(cp);
-        } else {
-            cur_pts.clear();
-        }
-        cur = std::move(A.coarse);
-        n_owned = nc_owned;
+        build_coarse_from_agg(f.cur, f.n_owned, agg, nc_owned, nc_total, A);
+        SNS_TRY(add_next_level(h, l, f, A, nc_global, !dist || l == 0 || c->windows(), dist));
+        if (dist) SNS_TRY(attach_plan(h, cplan, l + 1));
+        if (l == 0) SNS_TRY(flag_empty_aggregates(h));
+        advance(f, A, std::move(cghosts));
     }
     Level& last = h->levels.back();
-    if (h->levels.size() > 1) {
-        if (!dist) {
-            SNS_TRY(alloc_coarsest_solver(h, last));
-        } else {
-            // global dense coarsest solve, replicated on every rank: rank r's node i -> padded id r*maxn + i
-            std::vector<double> cnt(c->nranks, 0.0);
-            cnt[c->rank] = (double)last.n_owned;
-            SNS_TRY(global_sum(h, cnt.data(), c->nranks));
-            int maxn = 0;
-            h->cg_counts.resize(c->nranks);
-            for (int r = 0; r < c->nranks; ++r) { h->cg_counts[r] = (int)cnt[r]; maxn = std::max(maxn, (int)cnt[r]); }
-            const int N = 4 * c->nranks * std::max(1, maxn);
-            if (N <= policy::DISTRIBUTED_DENSE_MAX_DOFS) {
-                h->cg_maxn = std::max(1, maxn);
-                h->cg_N = N;
-                std::vector<int32_t> cmap((size_t)last.n, 0);
-                for (int32_t i = 0; i < last.n_owned; ++i) cmap[i] = c->rank * h->cg_maxn + i;
-                const auto& go = h->ghost_own.back();
-                const auto& gg = h->ghost_gid.back();
-                for (size_t q = 0; q < go.size(); ++q) cmap[(size_t)last.n_owned + q] = go[q] * h->cg_maxn + gg[q];
-                SNS_TRY(h->cg_colmap.upload(cmap));
-                SNS_TRY(h->cg_rows.alloc((size_t)4 * h->cg_maxn * N));
-                SNS_TRY(h->cg_full.alloc((size_t)N * N));
-                SNS_TRY(h->cg_send.alloc((size_t)4 * h->cg_maxn));
-                SNS_TRY(h->cg_recv.alloc((size_t)N));
-                SNS_TRY(h->d_piv.alloc((size_t)N));
-            }
-        }
-    }
+    if (h->levels.size() > 1) SNS_TRY(dist ? alloc_distributed_coarsest_solver(h, last, f.ghosts) : alloc_coarsest_solver(h, last));
     h->tm.amg_levels = (int)h->levels.size();
     return plan_hierarchy(h);
 }
@@ -757,7 +715,7 @@ static void refresh_galerkin(sns_ctx* h, int l) {
     Level& C = h->levels[l + 1];
     const int64_t nth = C.nnzb * 8;
     hipLaunchKernelGGL(k_galerkin, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, C.nnzb, L.r_ptr, L.r_idx, L.vals,
-                       h->slot_row[l + 1], C.colind, (l == 0) ? h->empty_c[0] : (const uint8_t*)nullptr, L.m_ptr, C.vals);
+                       C.slot_row, C.colind, (l == 0) ? L.empty_c.get() : (const uint8_t*)nullptr, L.m_ptr, C.vals);
 }
 
 // the last level's direct solve, whichever the hierarchy was built with (alloc_coarsest_solver, build_hierarchy); none: smoothed
@@ -780,7 +738,7 @@ static int refresh_coarsest_solver(sns_ctx* h, int l) {
         const int N = 4 * L.n, Np = L.dense_np;
         HIP_TRY(hipMemsetAsync(L.dense_gj, 0, (size_t)Np * Np * sizeof(double), h->stream));
         const int64_t nth = L.nnzb * 16;
-        hipLaunchKernelGGL(k_bsr_to_dense_ld, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.nnzb, h->slot_row[l],
+        hipLaunchKernelGGL(k_bsr_to_dense_ld, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, h->stream, L.nnzb, L.slot_row,
                            L.colind, L.vals, Np, L.dense_gj);
         if (Np > N) hipLaunchKernelGGL(k_dense_pad_diag, dim3((Np - N + 255) / 256), dim3(256), 0, h->stream, N, Np, L.dense_gj);
         // (the two-stream schedule of dense_gj_inverse is opt-in: measured, it is SLOWER -- 3.9 against 2.4 ms at N = 1900 --

@@ -77,7 +77,7 @@ int transpose_operator(sns_ctx* h) {
         hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), h->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_partner_slot, dim3((unsigned)((L.nnzb + 255) / 256)), dim3(256), 0, h->stream, L.nnzb, L.n, L.rowptr,
-                               L.colind, h->slot_row[0], partner, bad);
+                               L.colind, L.slot_row, partner, bad);
             e = hipMemcpyAsync(h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, h->stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);

@@ -465,6 +465,35 @@ def test_host_symbolic_setup_under_sanitizers(tmp_path):
     assert "active aggregation" in run.stdout and "ERROR" not in run.stderr
 
 
+def test_hierarchy_host_logic_on_simulated_ranks(tmp_path):
+    """The index logic of the distributed hierarchy build (csrc/sns_host.cpp: the aggregates' centroids, a coarse level's halo lists
+    from the finer ones and the exchanged aggregate ids, the replicated level's global pattern with valmap / rowmap, the id
+    mapping) on 2, 3 and 4 simulated x-slab ranks, a 2 x 2 block split with corner ghosts and a rank without rows
+    (tests/hierarchy_host_main.cpp, its own executable under AddressSanitizer + UBSan): bit for bit against the loops as they
+    stood inline in csrc/sns_setup.hip, the properties the exchange and the value scatter rely on, and the error returns."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "hierarchy_host")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fopenmp", "-fsanitize=address,undefined",
+                            "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-I", os.path.join(root, "include"),
+                            "-I", os.path.join(root, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
+                            os.path.join(root, "tests", "hierarchy_host_main.cpp"),
+                            os.path.join(root, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc", "sns_host.cpp"), "-o", exe],
+                           capture_output=True, text=True)
+    if build.returncode != 0 and "sanitize" in build.stderr:
+        pytest.skip("toolchain without sanitizer runtimes")
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True,
+                         env=dict(os.environ, OMP_NUM_THREADS="4", ASAN_OPTIONS="detect_leaks=0"))
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-2000:])
+    assert "all cases passed" in run.stdout and "ERROR" not in run.stdout and "ERROR" not in run.stderr
+    for case in ("x-slabs, 2 ranks", "x-slabs, 3 ranks", "x-slabs, 4 ranks", "2 x 2 blocks", "rank 1 without rows", "error returns"):
+        assert case in run.stdout, case
+
+
 def test_delaunay_channel_mesh_geometry_and_tags():
     """mesh.delaunay_channel_mesh (bench.py --config 4u; the unstructured stand-in for the reference's gmsh meshes,
     image2gmsh3D.py:445-486): watertight 4 x 1 x 1 box, channel tag set with the inlet split by facet centroid, node
