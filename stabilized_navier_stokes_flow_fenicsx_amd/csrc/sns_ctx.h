@@ -195,14 +195,10 @@ struct sns_ctx {
     bool no_overlap = false;
     bool team_overlap = false;                       // SNS_TEAM_OVERLAP: the team transport takes the two-stream path too (tests)
     DevBuf<double> arn_V;                             // Arnoldi basis of the damping estimate, 9 vectors of the largest level >= ... asked for
-    // the put half of a halo exchange carried by the kernel that produced the vector (PutDst, round 5): first_put_carried -- the
-    // Krylov kernel that ran the fine level's first sweep put it too; child_put_carried -- the restriction put the next level's first
-    // sweep; put_pending -- the last kernel of a window cycle put its result (the vector named), the next exchange of exactly that
-    // vector is comm_put_carried; pc_then_op -- the caller of pc_apply promises that an operator application of the result follows
-    // (only then may the fine level's last kernel carry the put: a round nobody consumes would void the windows' flow control)
-    bool first_put_carried = false, child_put_carried = false, pc_then_op = false;
-    const double* put_pending = nullptr;             // (borrowed: compared only)
-    bool first_sweep_done = false;                   // the V-cycle's fine-level first sweep was done by the Krylov kernel that wrote its input
+    // what one kernel of a solve hands to a later one: the fine level's first sweep done by the Krylov kernel, the puts carried by
+    // the kernels that produced a vector (PutDst), the caller's promise of an operator application (policy::Handoff: its
+    // transitions are the only writers; window_put below is where a carried put is taken)
+    policy::Handoff handoff;
     bool r3_estimates = false;                       // SNS_R3_SPECTRAL_ESTIMATE (tests of the retry path): round 3's policy -- spectral
                                                      // estimates every 4th setup whatever the operator (first Jacobians on the Stokes estimate)
     double damping_backoff = 1.0;                    // < 1 after a failed AMG-preconditioned solve: all level dampings scaled
@@ -472,55 +468,45 @@ inline int exchange_level(sns_ctx* h, int l, double* x) {
 
 inline int halo_exchange(sns_ctx* h, double* x) { return exchange_level(h, 0, x); }
 
+// an illegal transition of the hand-off state (policy::Handoff) ends the call: the protocol of the carried puts was broken
+inline int handoff_legal(bool legal, const char* what, int level) {
+    if (legal) return SNS_OK;
+    set_error(std::string("cycle hand-off: ") + what + " on level " + std::to_string(level));
+    return SNS_E_STATE;
+}
+
+// The put half of the exchange of level l's vector v over a window transport -- one exchange on the counter.  The one place
+// that asks whether the kernel that produced v has carried the put already, and the one caller of comm_put_carried
+inline int window_put(sns_ctx* h, int l, const double* v) {
+    Comm* c = h->comm.get();
+    ++h->ctr_exchange;
+    bool done = false;
+    SNS_TRY(handoff_legal(h->handoff.take_put(l, v, &done), "an exchange while the carried put of another vector is outstanding", l));
+    return done ? comm_put_carried(c, c->plans[l], h->stream) : comm_put(c, c->plans[l], v, h->stream);
+}
+
+// the buffer level l's cycle on x starts in, and the vector pc_apply(., z) cycles the fine level in: a partitioned fine level
+// must see zero ghost values, z's tail may hold halo data -- an internal buffer unless nothing reads a tail as zero
+inline double* cycle_start(sns_ctx* h, int l, double* x) { return policy::cycle_start(h->plan.level[(size_t)l], x, (double*)h->levels[l].pong); }
+inline double* fine_cycle_vector(sns_ctx* h, double* z) {
+    return (h->n > h->n_owned && !h->plan.fine_tails_unused) ? (double*)h->levels[0].x : z;
+}
+
 // Per-launch timing of the level-0 SpMV family (bench.py roofline leg): event pairs are
 // recorded around every fine-level launch while h->time_kernels is set and resolved after
 // the solve has synchronised.
 
 
-// Multi-GPU, level 0: a pass is either over every row (split 0), over the interior rows only (1: rows with a ghost
-// column, flagged in h->bnd_flag, are skipped) or over the boundary rows listed in h->bnd_rows (2).
-// Window transports (round 5): 3 = every row in one launch, the ghost entries read straight from the receive window `gs`.
+// Multi-GPU, level 0: a pass is over every row, over the interior rows only (rows with a ghost column, flagged in h->bnd_flag, are
+// skipped), over the boundary rows listed in h->bnd_rows, or -- window transports (round 5) -- over every row in one launch, the
+// ghost entries read straight from the receive window `gs`.  (The values are the kernels' SPLIT template arguments.)
+enum SplitMode { SPLIT_EVERY_ROW = 0, SPLIT_INTERIOR = 1, SPLIT_BOUNDARY_LIST = 2, SPLIT_WINDOW = 3 };
 struct Split {
-    int mode = 0;
+    int mode = SPLIT_EVERY_ROW;
     hipStream_t stream = nullptr;       // nullptr = the handle's stream
     int partial_off = 0;
     GhostSrc gs;
 };
-
-
-// y = A_l x (or fused variants).  rows = number of block rows computed.
-template <int MODE>
-void launch_spmv(sns_ctx* h, const Level& L, int32_t rows, const double* x, double* y, const double* b,
-                 double omega, const double* dotw, Split sp = Split()) {
-    hipStream_t st = sp.stream ? sp.stream : h->stream;
-    const bool fine = (&L == &h->levels[0]);
-    if (sp.mode == 2) rows = h->n_bnd;
-    const int grid = (rows + 31) / 32;
-    if (grid == 0) return;
-    if (fine && sp.mode == 1) {
-        time_begin(h, MODE, st);                      // multi-GPU: the interior pass is the bulk of a split launch
-        hipLaunchKernelGGL((k_spmv<MODE, 1, 1, 1>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, L.vals, x, y,
-                           b, L.dinv, omega, dotw, h->partial, (const int32_t*)nullptr, h->bnd_flag, sp.partial_off, GhostSrc());
-        time_end(h, st);
-    } else if (fine && sp.mode == 2) {
-        hipLaunchKernelGGL((k_spmv<MODE, 1, 1, 2>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, L.vals, x, y,
-                           b, L.dinv, omega, dotw, h->partial, h->bnd_rows, (const uint8_t*)nullptr, sp.partial_off, GhostSrc());
-    } else if (fine && sp.mode == 3) {
-        time_begin(h, MODE, st);
-        hipLaunchKernelGGL((k_spmv<MODE, 1, 1, 3>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, L.vals, x, y,
-                           b, L.dinv, omega, dotw, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0, sp.gs);
-        time_end(h, st);
-    } else if (fine) {
-        time_begin(h, MODE);
-        hipLaunchKernelGGL((k_spmv<MODE, 1, 1, 0>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, L.vals,
-                           x, y, b, L.dinv, omega, dotw, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0, GhostSrc());
-        time_end(h);
-    } else if constexpr (MODE != SPMV_AX_DOT) {
-        hipLaunchKernelGGL((k_spmv<MODE, 0, 0, 0>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, L.vals,
-                           x, y, b, L.dinv, omega, dotw, h->partial, (const int32_t*)nullptr, (const uint8_t*)nullptr, 0, GhostSrc());
-    }
-}
-
 
 // The format of a level's low-precision copies (amg_f32_matrix: 1 = fp32, 2 = fp16 with row scales; a plan's lp_fmt, a level's
 // binv_fmt) as a compile-time constant.  dispatch: fn(Int<V>()) for the V of Vs equal to v, the last of Vs where none is
@@ -536,6 +522,39 @@ inline void dispatch(int v, Fn&& fn) {
 
 template <class Fn>
 inline void with_fmt(int fmt, Fn&& fn) { dispatch<2, 1>(fmt, fn); }
+
+// One level pass under a split: launch(FINE, SPLIT, stream) with the two as compile-time constants -- a coarse level always over
+// every row -- and the per-launch timing of the fine level as `mode`: every launch but the boundary-list pass (the interior
+// pass is the bulk of a split launch)
+template <class Launch>
+void launch_split(sns_ctx* h, const Level& L, int mode, const Split& sp, Launch&& launch) {
+    hipStream_t st = sp.stream ? sp.stream : h->stream;
+    if (&L != &h->levels[0]) { launch(Int<0>(), Int<SPLIT_EVERY_ROW>(), st); return; }
+    if (sp.mode == SPLIT_BOUNDARY_LIST) { launch(Int<1>(), Int<SPLIT_BOUNDARY_LIST>(), st); return; }
+    hipStream_t timed = (sp.mode == SPLIT_INTERIOR || sp.mode == SPLIT_WINDOW) ? st : nullptr;   // (every row: the handle's stream)
+    time_begin(h, mode, timed);
+    dispatch<SPLIT_INTERIOR, SPLIT_WINDOW, SPLIT_EVERY_ROW>(sp.mode, [&](auto S) { launch(Int<1>(), S, st); });
+    time_end(h, timed);
+}
+
+// y = A_l x (or fused variants).  rows = number of block rows computed.
+template <int MODE>
+void launch_spmv(sns_ctx* h, const Level& L, int32_t rows, const double* x, double* y, const double* b,
+                 double omega, const double* dotw, Split sp = Split()) {
+    if (sp.mode == SPLIT_BOUNDARY_LIST) rows = h->n_bnd;
+    const int grid = (rows + 31) / 32;
+    if (grid == 0) return;
+    launch_split(h, L, MODE, sp, [&](auto FINE, auto S, hipStream_t st) {
+        if constexpr (FINE != 0 || MODE != SPMV_AX_DOT) {
+            const bool part = S == SPLIT_INTERIOR || S == SPLIT_BOUNDARY_LIST;
+            hipLaunchKernelGGL((k_spmv<MODE, FINE, FINE, S>), dim3(grid), dim3(256), 0, st, rows, L.rowptr, L.colind, L.vals, x, y,
+                               b, L.dinv, omega, dotw, h->partial, S == SPLIT_BOUNDARY_LIST ? h->bnd_rows : (const int32_t*)nullptr,
+                               S == SPLIT_INTERIOR ? h->bnd_flag : (const uint8_t*)nullptr, part ? sp.partial_off : 0,
+                               S == SPLIT_WINDOW ? sp.gs : GhostSrc());
+        }
+    });
+}
+
 
 // a level's matrix copy in format F -- values and row scales (nullptr in fp32) -- and the same of M = A P (borrowed pointers)
 struct LpMat {
@@ -567,26 +586,11 @@ void launch_pc_spmv(sns_ctx* h, const Level& L, int fmt, int32_t rows, const dou
         launch_spmv<MODE>(h, L, rows, x, y, b, omega, nullptr, sp);
         return;
     }
-    hipStream_t st = sp.stream ? sp.stream : h->stream;
-    const bool fine = (&L == &h->levels[0]);
     with_fmt(fmt, [&](auto F) {
-        if (fine && sp.mode == 1) {
-            time_begin(h, MODE, st);
-            launch_lp<MODE, 1, 1, F>(h, L, rows, st, x, y, b, omega);
-            time_end(h, st);
-        } else if (fine && sp.mode == 2) {
-            launch_lp<MODE, 1, 2, F>(h, L, h->n_bnd, st, x, y, b, omega);
-        } else if (fine && sp.mode == 3) {
-            time_begin(h, MODE, st);
-            launch_lp<MODE, 1, 3, F>(h, L, rows, st, x, y, b, omega, sp.gs);
-            time_end(h, st);
-        } else if (fine) {
-            time_begin(h, MODE);
-            launch_lp<MODE, 1, 0, F>(h, L, rows, st, x, y, b, omega);
-            time_end(h);
-        } else {
-            launch_lp<MODE, 0, 0, F>(h, L, rows, st, x, y, b, omega);
-        }
+        launch_split(h, L, MODE, sp, [&](auto FINE, auto S, hipStream_t st) {
+            launch_lp<MODE, FINE, S, F>(h, L, S == SPLIT_BOUNDARY_LIST ? h->n_bnd : rows, st, x, y, b, omega,
+                                        S == SPLIT_WINDOW ? sp.gs : GhostSrc());
+        });
     });
 }
 
@@ -613,12 +617,9 @@ int exchange_and_spmv(sns_ctx* h, double* xe, const double* x, double* y, const 
     if (dist && h->plan.fine_windows && xe == x) {
         // window transports: ONE put launch; the pass reads the ghost entries from the receive window and its boundary waves
         // wait for the neighbours' flags themselves -- no unpack, no boundary launch, no second stream
-        ++h->ctr_exchange;
-        if (h->put_pending == xe) SNS_TRY(comm_put_carried(c, c->plans[0], h->stream));    // (the cycle's last kernel put it)
-        else SNS_TRY(comm_put(c, c->plans[0], xe, h->stream));
-        h->put_pending = nullptr;
+        SNS_TRY(window_put(h, 0, xe));                   // (the cycle's last kernel may have put it)
         Split s3;
-        s3.mode = 3;
+        s3.mode = SPLIT_WINDOW;
         s3.gs = comm_ghost_src(c, c->plans[0]);
         pass(s3);
         h->dot_partials = (rows + 31) / 32;              // (one per workgroup in this form of the pass)
@@ -633,8 +634,8 @@ int exchange_and_spmv(sns_ctx* h, double* xe, const double* x, double* y, const 
     }
     const int gs = (rows + 31) / 32;                 // partial sums exist in the fp64 AX_DOT pass only
     Split s1, s2;
-    s1.mode = 1;
-    s2.mode = 2;
+    s1.mode = SPLIT_INTERIOR;
+    s2.mode = SPLIT_BOUNDARY_LIST;
     s2.partial_off = gs;
     if (MODE == SPMV_AX_DOT) { h->bnd_dot_blocks = (h->n_bnd + 31) / 32; h->dot_partials += 4 * h->bnd_dot_blocks; }   // ... of both launches
     if (c->nccl || (c->peer && !c->team) || h->team_overlap) {

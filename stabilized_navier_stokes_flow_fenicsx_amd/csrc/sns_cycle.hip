@@ -52,6 +52,21 @@ int coarse_cycle(sns_ctx* h, int l, const double* b, double* x) {
 
 // ---- the stages both forms of the cycle launch ----------------------------------------------------------------------------------
 
+// Where level l's coarse-grid problem lives.  rep_src: the level below is only the source of the replicated tail -- its right-hand
+// side is restricted straight into the all-gather's send buffer, and the correction is prolongated straight from this rank's rows
+// of the replicated solution (no copies)
+struct CoarseVectors {
+    bool rep_src;
+    double* cb;
+    const double* cx;
+};
+static CoarseVectors coarse_vectors(sns_ctx* h, int l) {
+    Level& C = h->levels[l + 1];
+    const bool rep_src = h->rep_level > 0 && l + 1 == h->rep_level - 1;
+    if (!rep_src) return {false, C.b, C.x};
+    return {true, h->rep_bsend, h->levels[h->rep_level].x + 4 * (size_t)h->rep_off};
+}
+
 // Restriction of level l's residual into the coarse right-hand side cb, with the coarse level's first sweep (into the buffer its
 // cycle starts from) where the plan fuses it.  fused: the residual b - A x is computed in the same launch (k_resid_restrict), else
 // L.r holds it (k_restrict_blk onto the coarse level's aggregate blocks, k_restrict).  gs: the ghost entries of x from this receive
@@ -62,9 +77,9 @@ static void launch_restrict(sns_ctx* h, int l, bool fused, const double* x, cons
     const Level& C = h->levels[l + 1];
     const policy::LevelPlan& Q = h->plan.level[(size_t)l];
     const policy::LevelPlan& QC = h->plan.level[(size_t)l + 1];
-    const bool fuse = Q.fuses_next_first != 0;
+    const bool fuse = policy::first_sweep_owner(h->plan, h->rep_level, l + 1) == policy::FIRST_SWEEP_RESTRICTION;
     const float* dc = fuse ? C.dinv32 : nullptr;
-    double* zc = !fuse ? nullptr : QC.start_odd ? h->levels[l + 1].pong : C.x;   // (the coarse cycle is called with x = C.x)
+    double* zc = fuse ? cycle_start(h, l + 1, C.x) : nullptr;   // (the coarse cycle is called with x = C.x)
     if (fused) {
         // mode of the coarse level's first sweep: 0 none, 1 nodal D^-1, 2 its aggregate blocks (walked in THEIR order)
         const int mode = !fuse ? 0 : (QC.blocks ? 2 : 1);
@@ -144,51 +159,41 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
     const int32_t rows = L.n_owned;
     const double om = L.damping.omega;
     const int nu_pre = Q.pre, nu_post = Q.post;
-    double* cur = Q.start_odd ? h->levels[l].pong : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
+    double* cur = cycle_start(h, l, x);
     double* oth = (cur == x) ? h->levels[l].pong : x;
     // The put of every exchange of this level's iterate rides in the kernel that PRODUCES the iterate (PutDst) where that is an
-    // aggregate-block kernel: `carried` says whether the vector about to be exchanged has been put already
+    // aggregate-block kernel: `carry` records it with the hand-off state, window_put -- every exchange -- asks there
     const bool blk = Q.blocks != 0;
     const PutDst pdl = (h->plan.fuse_puts && blk && rows > 0) ? comm_put_dst(c, P) : PutDst();
     const GhostSrc gs = comm_ghost_src(c, P);
-    bool carried = false;
-    if (l == 0 && h->first_sweep_done) carried = h->first_put_carried;
-    else if (l > 0 && h->plan.level[(size_t)l - 1].fuses_next_first) carried = h->child_put_carried;
-    else if (rows > 0) {
+    auto carry = [&](const PutDst& pd, int lv, const double* v) -> int {
+        return pd.sr_ptr ? handoff_legal(h->handoff.put_carried(lv, v), "a second carried put before the first was taken", lv) : SNS_OK;
+    };
+    const bool by_krylov = h->handoff.enter_level(l);
+    if (!by_krylov && rows > 0 && policy::first_sweep_owner(h->plan, h->rep_level, l) == policy::FIRST_SWEEP_LEVEL) {
         PutDst pd1 = pdl;
         launch_first_sweep(h, Q, L, rows, b, om, cur, &pd1);
-        carried = pd1.sr_ptr != nullptr;
+        SNS_TRY(carry(pd1, l, cur));
     }
-    h->first_put_carried = h->child_put_carried = false;
-    if (l == 0) h->first_sweep_done = false;
-    auto put = [&](const Plan& Q, const double* v, bool was_carried) -> int {
-        ++h->ctr_exchange;
-        return was_carried ? comm_put_carried(c, Q, h->stream) : comm_put(c, Q, v, h->stream);
-    };
     for (int s = 1; s < nu_pre; ++s) {                     // (level >= 1 only: the fine level runs one sweep per half cycle)
-        SNS_TRY(put(P, cur, carried));
-        carried = false;
+        SNS_TRY(window_put(h, l, cur));
         if (rows > 0 && blk) {
             launch_sweep(h, Q, L, rows, cur, oth, b, om, &gs, pdl);
-            carried = pdl.sr_ptr != nullptr;
+            SNS_TRY(carry(pdl, l, oth));
         }
         std::swap(cur, oth);
     }
-    const bool rep_src = h->rep_level > 0 && l + 1 == h->rep_level - 1;
-    double* cb = rep_src ? h->rep_bsend : C.b;
-    const double* cx = rep_src ? h->levels[h->rep_level].x + 4 * (size_t)h->rep_off : C.x;
-    const bool fuse = Q.fuses_next_first != 0;
+    const auto [rep_src, cb, cx] = coarse_vectors(h, l);
+    const bool fuse = policy::first_sweep_owner(h->plan, h->rep_level, l + 1) == policy::FIRST_SWEEP_RESTRICTION;
     // residual (+ restriction): the true residual needs the neighbours' iterate
-    SNS_TRY(put(P, cur, carried));
-    carried = false;
+    SNS_TRY(window_put(h, l, cur));
     // (the next level's first sweep, written by the restriction, is exchanged first thing in its cycle: put from here)
     const PutDst pdc = (h->plan.fuse_puts && fuse && QC.blocks && !rep_src && QC.windows && C.n_owned > 0 &&
                         (l == 0 || rows > 0))
                            ? comm_put_dst(c, c->plans[l + 1]) : PutDst();
-    h->child_put_carried = pdc.sr_ptr != nullptr;
     if (l == 0) {
         Split s3;
-        s3.mode = 3;
+        s3.mode = SPLIT_WINDOW;
         s3.gs = gs;
         if (rows > 0) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, Q.lp_fmt, rows, cur, L.r, b, 0.0, s3);
         if (C.n_owned > 0) launch_restrict(h, l, false, nullptr, nullptr, cb, nullptr, AgPut(), pdc);
@@ -198,6 +203,7 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
         const AgPut agp = (rep_src && h->plan.rep_gather_first) ? comm_ag_put(c, 4 * (int64_t)h->rep_maxn) : AgPut();
         launch_restrict(h, l, true, cur, b, cb, &gs, agp, pdc);
     }
+    SNS_TRY(carry(pdc, l + 1, cycle_start(h, l + 1, C.x)));
     SNS_TRY(coarse_cycle(h, l + 1, cb, rep_src ? nullptr : C.x));
     // fused coarse-grid correction + first post-smoothing sweep over M = A P; the ghost aggregates' part of the coarse solution:
     // level >= 1 above the replicated tail reads every entry from the replicated solution (M's columns renumbered into its ids,
@@ -209,31 +215,28 @@ int vcycle_windows(sns_ctx* h, int l, const double* b, double* x) {
         xc = h->levels[h->rep_level].x;
         apc = L.ap_colind_rep;
     } else {
-        SNS_TRY(put(c->plans[l + 1], cx, h->put_pending == cx));       // (the level below put its result with its last kernel)
+        SNS_TRY(window_put(h, l + 1, cx));                           // (the level below may have put its result with its last kernel)
         gc = comm_ghost_src(c, c->plans[l + 1]);
     }
-    h->put_pending = nullptr;
     // this level's result is exchanged next by the level above (its correction reads it) or, the fine level's, by the operator
     // application the caller of pc_apply has promised: the last kernel of the cycle puts it
-    const bool last_puts = pdl.sr_ptr && (l == 0 ? h->pc_then_op : h->plan.level[(size_t)l - 1].windows != 0);
+    const bool last_puts = pdl.sr_ptr && (l == 0 ? h->handoff.op_promised : h->plan.level[(size_t)l - 1].windows != 0);
     if (rows > 0) {                                        // (nodal blocks: the fine level only, see the plan's exact)
         const PutDst pd = (nu_post > 1 || last_puts) ? pdl : PutDst();
         launch_post(h, l, xc, cx, apc, cur, oth, &gc, pd);
-        carried = pd.sr_ptr != nullptr;
+        SNS_TRY(carry(pd, l, oth));
     }
     std::swap(cur, oth);
     for (int s = 1; s < nu_post; ++s) {
-        SNS_TRY(put(P, cur, carried));
-        carried = false;
+        SNS_TRY(window_put(h, l, cur));
         if (rows > 0 && blk) {
             const PutDst pd = (s + 1 < nu_post || last_puts) ? pdl : PutDst();
             launch_sweep(h, Q, L, rows, cur, oth, b, om, &gs, pd);
-            carried = pd.sr_ptr != nullptr;
+            SNS_TRY(carry(pd, l, oth));
         }
         std::swap(cur, oth);
     }
-    // cur == x by construction of the start buffer
-    h->put_pending = carried ? cur : nullptr;
+    // cur == x by construction of the start buffer: where the last kernel carried its put, the level is left with it recorded
     return SNS_OK;
 }
 
@@ -246,13 +249,13 @@ static int enter_replicated_tail(sns_ctx* h, int l, const double* b, double* x) 
     if (rows > 0 && b != h->rep_bsend)                   // (vcycle of the level above restricts straight into rep_bsend)
         HIP_TRY(hipMemcpyAsync(h->rep_bsend, b, 4 * (size_t)rows * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     Comm* cm = h->comm.get();
-    if (h->plan.rep_gather_first) {
+    if (policy::first_sweep_owner(h->plan, h->rep_level, h->rep_level) == policy::FIRST_SWEEP_GATHER) {
         // both halves of the all-gather ride in solver kernels: the residual + restriction of the level above has stored this
         // rank's piece into every rank's staging area, the first sweep of the replicated level waits for the pieces itself
         SNS_TRY(peer_check(cm));
         SNS_TRY(comm_host_barrier(cm, h->stream));
         const int32_t ns = 8 * C.n_blk;
-        double* zc = h->plan.level[(size_t)h->rep_level].start_odd ? C.pong : C.x;
+        double* zc = cycle_start(h, h->rep_level, C.x);
         with_fmt(C.binv_fmt, [&](auto F) {
             hipLaunchKernelGGL((k_bfirst_gather<F>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, C.blk_rows,
                                (const void*)C.binv32, C.damping.omega, zc, C.b, h->rep_rowmap, comm_ag_get(cm));
@@ -324,7 +327,7 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     const int32_t rows = L.n_owned;
     const double om = L.damping.omega;
     const int nu = Q.nu, nu_pre = Q.pre, nu_post = Q.post;
-    double* cur = Q.start_odd ? h->levels[l].pong : x;          // (after pre - 1 + post ping-pong swaps the result sits in x)
+    double* cur = cycle_start(h, l, x);
     double* oth = (cur == x) ? h->levels[l].pong : x;
     // distributed: on levels with few rows per rank the sweeps see the neighbours' current iterate (one small
     // exchange per sweep); on the big levels they stay rank-local (ghost values zero) and only the residual is exact
@@ -338,12 +341,11 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
         HIP_TRY(hipMemsetAsync(cur + 4 * (size_t)rows, 0, ghost4 * sizeof(double), h->stream));
         HIP_TRY(hipMemsetAsync(oth + 4 * (size_t)rows, 0, ghost4 * sizeof(double), h->stream));
     }
-    // first sweep from a zero guess: z = omega D^-1 b, with the D^-1 copy the other sweeps of this level read (already done
-    // by the restriction kernel of the level above where its plan fuses it)
-    if (rows > 0 && !(l > 0 && h->plan.level[(size_t)l - 1].fuses_next_first) && !(l == 0 && h->first_sweep_done) &&
-        !(h->rep_level > 0 && l == h->rep_level && h->plan.rep_gather_first))
+    // first sweep from a zero guess: z = omega D^-1 b, with the D^-1 copy the other sweeps of this level read (unless the Krylov
+    // kernel, the restriction of the level above or the gather into the replicated tail has done it)
+    const bool by_krylov = h->handoff.enter_level(l);
+    if (!by_krylov && rows > 0 && policy::first_sweep_owner(h->plan, h->rep_level, l) == policy::FIRST_SWEEP_LEVEL)
         launch_first_sweep(h, Q, L, rows, b, om, cur);
-    if (l == 0) h->first_sweep_done = false;
     for (int s = 1; s < nu_pre; ++s) {
         if (sx) SNS_TRY(exchange_level(h, l, cur));
         launch_sweep(h, Q, L, rows, cur, oth, b, om);
@@ -372,11 +374,7 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     } else if (!rr_fused) {
         launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, Q.lp_fmt, rows, cur, L.r, b, 0.0);
     }
-    // the level below is only the source of the replicated tail: its right-hand side is restricted straight into the all-gather's
-    // send buffer, and the correction is prolongated straight from this rank's rows of the replicated solution (no copies)
-    const bool rep_src = h->rep_level > 0 && l + 1 == h->rep_level - 1;
-    double* cb = rep_src ? h->rep_bsend : C.b;
-    const double* cx = rep_src ? h->levels[h->rep_level].x + 4 * (size_t)h->rep_off : C.x;
+    const auto [rep_src, cb, cx] = coarse_vectors(h, l);
     if (C.n_owned > 0) launch_restrict(h, l, rr_fused, xres, b, cb);
     SNS_TRY(coarse_cycle(h, l + 1, cb, rep_src ? nullptr : C.x));
     int s_first = 0;
@@ -426,12 +424,13 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
 
 
 static int pc_apply_inner(sns_ctx* h, const double* r, double* z);
-// (first_sweep_done is consumed by the cycle this call runs and by nothing else: cleared on every way out)
+// (what the Krylov kernel in front handed over is consumed by the cycle this call runs and by nothing else; of the cycle's own
+// hand-offs only the promised put of z outlives the call: policy::Handoff::end_pc_apply, on every way out)
 int pc_apply(sns_ctx* h, const double* r, double* z) {
     const int rc = pc_apply_inner(h, r, z);
-    h->first_sweep_done = h->first_put_carried = h->child_put_carried = h->pc_then_op = false;
-    if (rc != SNS_OK || h->put_pending != z) h->put_pending = nullptr;
-    return rc;
+    int level = -1;
+    const bool legal = h->handoff.end_pc_apply(rc == SNS_OK, z, &level);
+    return rc != SNS_OK ? rc : handoff_legal(legal, "pc_apply ends with a carried put nobody took", level);
 }
 
 static int pc_apply_inner(sns_ctx* h, const double* r, double* z) {
@@ -444,18 +443,15 @@ static int pc_apply_inner(sns_ctx* h, const double* r, double* z) {
             hipLaunchKernelGGL(k_bjacobi, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->stream, h->n_owned,
                                h->levels[0].dinv, r, 1.0, z);
             return SNS_OK;
-        case SNS_PC_AMG:
-            if (h->n > h->n_owned) {
-                // distributed: the per-rank V-cycle must see ZERO ghost values on level 0 (block-Jacobi across
-                // ranks, like PETSc's parallel default bjacobi).  z's ghost tail may hold halo data, so cycle
-                // in internal buffers whose tails are never written and copy the owned part out.
-                // (fine_tails_unused: nothing in the fine level's cycle reads a ghost tail as zero -- no internal buffer, no copy)
-                if (h->plan.fine_tails_unused) return vcycle(h, 0, r, z);
-                SNS_TRY(vcycle(h, 0, r, h->levels[0].x));
-                HIP_TRY(hipMemcpyAsync(z, h->levels[0].x, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-                return SNS_OK;
-            }
-            return vcycle(h, 0, r, z);
+        case SNS_PC_AMG: {
+            // distributed: the per-rank V-cycle must see ZERO ghost values on level 0 (block-Jacobi across ranks, like PETSc's
+            // parallel default bjacobi): where z's ghost tail could be read, cycle in an internal buffer whose tail is never
+            // written and copy the owned part out
+            double* x = fine_cycle_vector(h, z);
+            SNS_TRY(vcycle(h, 0, r, x));
+            if (x != z) HIP_TRY(hipMemcpyAsync(z, x, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            return SNS_OK;
+        }
     }
     set_error("bad pc_type");
     return SNS_E_ARG;

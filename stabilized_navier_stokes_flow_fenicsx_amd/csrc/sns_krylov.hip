@@ -29,16 +29,16 @@ int dot(sns_ctx* h, const double* x, const double* y, double* out) {
 
 // Can the Krylov kernel that writes the preconditioner's input also do the V-cycle's first fine-level sweep z = w D^-1 (input)
 // (k_bicg_s_first / k_bicg_xrp_first: one dependent launch and one read of the input less per cycle)?  Returns the buffer the
-// cycle of pc_apply(., zdst) starts from, or nullptr.  (n_owned, n_blk: a rank without rows or blocks launches nothing there)
+// cycle of pc_apply(., zdst) starts from, or nullptr.  The fine level must own its first sweep (not where it is solved directly
+// or is only the source of the replicated copy); n_owned, n_blk: a rank without rows or blocks launches nothing there
 double* fused_first_sweep_target(sns_ctx* h, double* zdst) {
-    if (h->opt.pc_type != SNS_PC_AMG || h->levels.size() < 2 || !h->pc_ready) return nullptr;
+    if (h->opt.pc_type != SNS_PC_AMG || !h->pc_ready) return nullptr;
+    if (policy::first_sweep_owner(h->plan, h->rep_level, 0) != policy::FIRST_SWEEP_LEVEL) return nullptr;
     const Level& L = h->levels[0];
     const policy::LevelPlan& P = h->plan.level[0];
     if (P.lp_fmt == 0 || L.n_owned <= 0) return nullptr;
     if (P.blocks && L.n_blk <= 0) return nullptr;                // (aggregate blocks: k_bfirst_bicg, see fused_vector_kernel)
-    if (h->rep_level == 1) return nullptr;                       // level 0 is only the source of the replicated copy
-    double* x = (h->n > h->n_owned && !h->plan.fine_tails_unused) ? h->levels[0].x : zdst;   // (as pc_apply chooses the cycle's vector)
-    return P.start_odd ? h->levels[0].pong : x;
+    return cycle_start(h, 0, fine_cycle_vector(h, zdst));
 }
 
 // the put that kernel carries (k_bfirst_bicg): empty unless the fine level runs the window form of the cycle
@@ -51,7 +51,7 @@ static PutDst fine_first_put(const sns_ctx* h) {
 // x / r update with the next p (k_bicg_xrp).  Where fused_first_sweep_target allows it, the same launch does the cycle's first
 // fine-level sweep: on the aggregate blocks (k_bfirst_bicg, carrying the put of the window form) or nodal
 template <int OP>
-static void bicg_update(sns_ctx* h, double* zdst, const double* sc, const double* ph, const double* sh, const double* t, const double* v,
+static int bicg_update(sns_ctx* h, double* zdst, const double* sc, const double* ph, const double* sh, const double* t, const double* v,
                         double* x, double* r, double* p, double* s) {
     const int64_t nd = nred_of(h);
     const int g = vec_grid(nd);
@@ -59,13 +59,13 @@ static void bicg_update(sns_ctx* h, double* zdst, const double* sc, const double
     if (!z1) {
         if (OP == 1) hipLaunchKernelGGL(k_bicg_s, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, s);
         else hipLaunchKernelGGL(k_bicg_xrp, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, v, x, r, p);
-        return;
+        return SNS_OK;
     }
     const Level& L0 = h->levels[0];
+    PutDst pd0;
     if (h->plan.level[0].blocks) {
         const int32_t ns = 8 * L0.n_blk;
-        const PutDst pd0 = fine_first_put(h);
-        h->first_put_carried = pd0.sr_ptr != nullptr;
+        pd0 = fine_first_put(h);
         with_fmt(L0.binv_fmt, [&](auto F) {
             hipLaunchKernelGGL((k_bfirst_bicg<F, OP>), dim3((unsigned)((ns + 63) / 64)), dim3(256), 0, h->stream, ns, L0.blk_rows,
                                (const void*)L0.binv32, L0.damping.omega, z1, sc, ph, sh, t, v, x, r, p, s, pd0);
@@ -76,7 +76,7 @@ static void bicg_update(sns_ctx* h, double* zdst, const double* sc, const double
         hipLaunchKernelGGL(k_bicg_xrp_first, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, v, x, r, p, L0.dinv32, L0.damping.omega,
                            z1);
     }
-    h->first_sweep_done = true;
+    return handoff_legal(h->handoff.krylov_did_first_sweep(z1, pd0.sr_ptr != nullptr), "a second carried put before the first was taken", 0);
 }
 
 
@@ -123,7 +123,7 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
         HIP_TRY(hipMemsetAsync(v, 0, nd * sizeof(double), h->stream));
         auto first_half = [&](bool p_done) -> int {       // p, ph = M p, v = A ph, alpha
             if (!p_done) hipLaunchKernelGGL(k_bicg_p, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, p);
-            h->pc_then_op = true;
+            h->handoff.promise_operator();
             SNS_TRY(pc_apply(h, p, ph));
             SNS_TRY(op_apply_dot(h, ph, v, rhat));        // v = A ph with the fused partial sums of <rhat, v>
             SNS_TRY(reduce_bicg<1>(h, h->dot_partials, red, sc));                  // alpha
@@ -134,8 +134,8 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
         double best_rn = rn;
         int best_it = 0;
         for (its = 1;; ++its) {
-            bicg_update<1>(h, sh, sc, nullptr, nullptr, nullptr, v, nullptr, r, nullptr, s);
-            h->pc_then_op = true;
+            SNS_TRY(bicg_update<1>(h, sh, sc, nullptr, nullptr, nullptr, v, nullptr, r, nullptr, s));
+            h->handoff.promise_operator();
             SNS_TRY(pc_apply(h, s, sh));
             SNS_TRY(op_apply(h, sh, t));
             hipLaunchKernelGGL(k_bicg_dots5, dim3(g), dim3(256), 0, h->stream, nd, s, t, rhat, h->partial);
@@ -146,7 +146,7 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
             // rides on the x / r update (k_bicg_xrp)
             const bool spec = its < o.ksp_max_it;
             if (spec) {
-                bicg_update<2>(h, ph, sc, ph, sh, t, v, x, r, p, s);
+                SNS_TRY(bicg_update<2>(h, ph, sc, ph, sh, t, v, x, r, p, s));
                 SNS_TRY(first_half(true));
             } else {
                 hipLaunchKernelGGL(k_bicg_xr, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, x, r);
@@ -411,9 +411,8 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
 int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm) {
     if (!h->has_matrix) { set_error("krylov_solve before a matrix was assembled"); return SNS_E_STATE; }
     if (!h->pc_ready && h->opt.pc_type != SNS_PC_NONE) SNS_TRY(pc_setup(h));
-    h->first_put_carried = h->child_put_carried = h->pc_then_op = false;
-    h->put_pending = nullptr;
-    h->first_sweep_done = false;                 // (a solve that ended in an error between setting and consuming it must not leak it)
+    int stale = -1;
+    SNS_TRY(handoff_legal(h->handoff.begin_solve(&stale), "a solve begins with a carried put nobody took", stale));
     h->ctr_host_syncs = h->ctr_allreduce = h->ctr_exchange = 0;
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     // A solve that BREAKS DOWN (or produces NaN/Inf) under the AMG preconditioner is retried ONCE, from the same initial

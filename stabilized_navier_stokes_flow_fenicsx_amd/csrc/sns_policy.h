@@ -7,7 +7,8 @@
 // In the same idiom, at the end: the route of an assembly (plan_assembly, tests/assembly_plan_main.cpp), what a handle's form
 // state allows (check_form_request, tests/form_request_main.cpp) and what it allows of the boundary terms (check_boundary_request,
 // tests/boundary_request_main.cpp), which operator is a new one (OperatorKey, tests/operator_key_main.cpp), the damping of a
-// level's smoother (LevelDamping, tests/damping_policy_main.cpp).
+// level's smoother (LevelDamping, tests/damping_policy_main.cpp), what a kernel of a solve hands to a later one (Handoff,
+// tests/handoff_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -271,6 +272,99 @@ inline CyclePlan plan_cycle(const sns_options& o, const Facts& f) {
     p.fuse_puts = f.fuse_puts;
     return p;
 }
+
+// ---- cycle hand-offs (csrc/sns_cycle.hip, sns_krylov.hip; the contract is in DESIGN.md, "Cycle hand-offs") --------------------------
+// Who does level l's first sweep z = w S b: the level's own cycle, the restriction of the level above (its plan's
+// fuses_next_first), the gather into the replicated tail (rep_gather_first), or nobody -- the last level is solved, the source of
+// the replicated copy is not cycled.  rep_level: first replicated level (0: none).  That the Krylov kernel in front of pc_apply
+// did the FINE level's is a run-time fact of the rank (Handoff::krylov_first), asked where the answer here is the level itself.
+enum FirstSweepOwner { FIRST_SWEEP_NOBODY = 0, FIRST_SWEEP_LEVEL = 1, FIRST_SWEEP_RESTRICTION = 2, FIRST_SWEEP_GATHER = 3 };
+inline FirstSweepOwner first_sweep_owner(const CyclePlan& p, int rep_level, int l) {
+    if (l < 0 || l + 1 >= (int)p.level.size() || (rep_level > 0 && l == rep_level - 1)) return FIRST_SWEEP_NOBODY;
+    if (l > 0 && p.level[(size_t)l - 1].fuses_next_first) return FIRST_SWEEP_RESTRICTION;
+    if (rep_level > 0 && l == rep_level && p.rep_gather_first) return FIRST_SWEEP_GATHER;
+    return FIRST_SWEEP_LEVEL;
+}
+// the buffer a level's cycle starts in: after pre - 1 + post ping-pong swaps the result sits in x
+template <class T>
+inline T* cycle_start(const LevelPlan& q, T* x, T* pong) { return q.start_odd ? pong : x; }
+
+// What one kernel of a solve hands to a later one across function boundaries, and the rule of the carried puts.  A kernel that
+// produces vector v of level l may carry the put half of v's halo exchange (PutDst): that advances the plan's round and flips the
+// parity of its receive window, so the next exchange of exactly v on that plan must wait for the carried put (comm_put_carried)
+// and must not put again.  Hence: a put is carried only where a consumer is promised; every carried put is taken by exactly one
+// exchange of that vector on that level; nothing but the promised result of pc_apply outlives the call.  Only the transitions
+// below write the members; each returns whether it was legal, and an illegal one leaves the state as it was (begin_solve and
+// end_pc_apply always leave it clean).  Vectors are names: compared, never dereferenced.
+// A replayed hipGraph runs no host code.  On a partitioned handle the graph covers the replicated tail, which has no windows,
+// and a serial handle has none at all: nothing here is moved by a level at or below plan.graph_level -- enter_level moves state
+// for level 0 alone, and no put is ever recorded or asked for on a level without the window form.
+struct Handoff {
+    bool krylov_first = false;               // the Krylov kernel that wrote pc_apply's input did the fine level's first sweep
+    bool op_promised = false;                // the caller of pc_apply promises an operator application of the result
+    std::vector<const void*> put;            // put[l]: the vector whose put on level l's plan is carried and not yet taken
+
+    int outstanding() const {                // first level with a carried put nobody has taken (-1: none)
+        for (size_t l = 0; l < put.size(); ++l)
+            if (put[l]) return (int)l;
+        return -1;
+    }
+    // a solve begins (krylov): nothing may be outstanding; *level (optional): the level that was
+    bool begin_solve(int* level = nullptr) {
+        const int bad = outstanding();
+        if (level) *level = bad;
+        krylov_first = op_promised = false;
+        put.clear();
+        return bad < 0;
+    }
+    // the Krylov kernel did the fine level's first sweep into v, the buffer its cycle starts in (carried: with the put of v)
+    bool krylov_did_first_sweep(const void* v, bool carried) {
+        if (carried && !put_carried(0, v)) return false;
+        krylov_first = true;
+        return true;
+    }
+    void promise_operator() { op_promised = true; }
+    // level l's cycle is entered: did the Krylov kernel do its first sweep?  (forgotten; the put that sweep carried stays
+    // recorded against its vector until the first exchange of the cycle takes it)
+    bool enter_level(int l) {
+        if (l != 0) return false;
+        const bool done = krylov_first;
+        krylov_first = false;
+        return done;
+    }
+    // a kernel of level l carried the put of the vector v it wrote: a sweep of l's cycle, the restriction above l that wrote
+    // l's first sweep, the last kernel of l's cycle (v its result, leaving the level).  One at a time per level
+    bool put_carried(int l, const void* v) {
+        if (l < 0 || !v) return false;
+        if ((size_t)l >= put.size()) put.resize((size_t)l + 1, nullptr);
+        if (put[(size_t)l]) return false;
+        put[(size_t)l] = v;
+        return true;
+    }
+    // THE consumption point, asked by every exchange over a window: is the put of v on level l's plan done already?  *done is
+    // true at most once per carried put.  Illegal while the put of another vector of the level is outstanding
+    bool take_put(int l, const void* v, bool* done) {
+        *done = false;
+        if (l < 0 || (size_t)l >= put.size() || !put[(size_t)l]) return l >= 0;
+        if (put[(size_t)l] != v) return false;
+        put[(size_t)l] = nullptr;
+        *done = true;
+        return true;
+    }
+    // pc_apply(., z) ends: keeps the carried put of the fine level's result, and only where that is z, the operator application
+    // was promised and the call succeeded.  Anything else outstanding after a successful call is illegal (*level: where);
+    // after a failed one it is dropped -- a solve that ended in an error must not leak a hand-off
+    bool end_pc_apply(bool ok, const void* z, int* level = nullptr) {
+        const void* keep = (ok && op_promised && !put.empty() && put[0] == z) ? z : nullptr;
+        if (keep) put[0] = nullptr;
+        const int bad = ok ? outstanding() : -1;
+        if (level) *level = bad;
+        krylov_first = op_promised = false;
+        put.clear();
+        if (keep) put.push_back(keep);
+        return bad < 0;
+    }
+};
 
 // ---- the route of an assembly (csrc/sns_assemble.hip; the table is in DESIGN.md) ------------------------------------------------------
 // Facts: the call (form; state, matrix, residual asked for) and the handle (dim, opt.assembly_fused, a perturbed form variant, a

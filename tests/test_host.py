@@ -1414,3 +1414,161 @@ def test_damping_event_sequences(tmp_path):
     # what the sequences covered
     assert seen["trials"] == set(range(7)) and seen["levels"] == {1, 2, 3, 4, 5} and seen["retries"] >= {0, 1, 2, 3}
     assert min(seen[k] for k in ("no_estimate", "ritz_binds", "ritz_slack", "held", "refused", "resets")) > 20, seen
+
+
+def _handoff_run(tmp_path, lines, **opt_kw):
+    """tests/handoff_main.cpp over the given request lines (options: the defaults and opt_kw)."""
+    import subprocess
+    from stabilized_navier_stokes_flow_fenicsx_amd import _lib
+    exe = _policy_main(tmp_path, "handoff")
+    opt = tmp_path / "handoff_opt.bin"
+    opt.write_bytes(ctypes.string_at(ctypes.byref(_lib.default_options(**opt_kw)), ctypes.sizeof(_lib.SnsOptions)))
+    run = subprocess.run([exe, str(opt)], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True)
+    assert run.returncode == 0, (run.returncode, run.stderr[-500:])
+    out = [ln for ln in run.stdout.split("\n") if ln.strip()]
+    assert len(out) == len(lines)
+    return out
+
+
+def _handoff_events(text):
+    """[(letter, [args], [legal, answers ...])] of a printed event sequence."""
+    ev = []
+    for tok in text.split():
+        head, _, res = tok.partition("=")
+        ev.append((head[0], [int(a) for a in head[1:].split(".") if a], [int(r) for r in res.split("/") if r]))
+    return ev
+
+
+# the hierarchies of the hand-off tests: (global rows per level, first replicated level).  2 to 5 levels; no replicated tail, a
+# tail entered from level 1 and from level 2
+_HANDOFF_SHAPES = [([3000, 400], 0), ([20000, 3000, 450], 0), ([150000, 20000, 3000, 400], 0), ([1000000, 150000, 20000, 3000, 400], 0),
+                   ([20000, 3000, 3000], 2), ([20000, 3000, 3000, 450, 60], 2), ([150000, 20000, 3000, 3000], 3),
+                   ([150000, 20000, 3000, 3000, 450], 3)]
+
+
+def test_cycle_handoff_sequences_of_the_library(built_lib, tmp_path):
+    """The hand-offs between the kernels of a solve (csrc/sns_policy.h: policy::Handoff -- the fine level's first sweep done by
+    the Krylov kernel, the puts carried by the kernels that produce a vector, the promised operator application) over the event
+    sequences the library emits: tests/handoff_main.cpp carries a transcription (events only) of bicg_update -> pc_apply ->
+    vcycle / vcycle_windows -> exchange_and_spmv and runs it on the plans of 2 ranks over a window transport.  Every transition is
+    legal, every carried put is taken exactly once and by the exchange of its own vector on its own level, nothing but the
+    promised result survives pc_apply, and without fuse_puts (SNS_NO_CARRIED_PUT) nothing is ever carried."""
+    import itertools
+    from stabilized_navier_stokes_flow_fenicsx_amd import _lib
+    BICGSTAB, FGMRES, TFQMR = range(3)
+    cases = [(rows, rep, fuse, krylov, method, empty, solves)
+             for (rows, rep), fuse, krylov, method in itertools.product(_HANDOFF_SHAPES, (1, 0), (1, 0), (BICGSTAB, FGMRES, TFQMR))
+             for empty, solves in ((99, 2), (0, 1), (1, 1))]
+    out = _handoff_run(tmp_path, ["S 2 %d %d %d %d %d %d %d %s" % (rep, fuse, krylov, method, empty, solves, len(rows), " ".join(map(str, rows)))
+                                  for rows, rep, fuse, krylov, method, empty, solves in cases])
+    seen = {"carried_levels": set(), "window_levels": set(), "krylov_carried": 0, "kept": 0, "plain_takes": 0, "two_window_levels": 0}
+    for (rows, rep, fuse, krylov, method, empty, solves), ln in zip(cases, out):
+        head, ok, text = (s.strip() for s in ln.split("|"))
+        glob, *levels = [list(map(int, part.split())) for part in head[1:].split(";")]
+        # the plan rows are those of the one policy function for that hierarchy
+        table = _lib.host_cycle_policy(rows, nranks=2, windows=True, rep_level=rep)
+        assert [(r["kind"], r["pre"], r["post"], r["exact"]) for r in table] == [tuple(q[:4]) for q in levels], (rows, rep)
+        assert glob[3] == fuse and glob[0] == 1 and levels[0][4] == 1                      # the fine level runs the window form
+        win = [l for l, q in enumerate(levels) if q[4]]
+        seen["window_levels"] |= set(win)
+        seen["two_window_levels"] += len([l for l in win if l >= 1]) >= 2
+        assert int(ok) == 1, (rows, rep, ln)
+        outstanding, promised, begun = {}, False, 0
+        for letter, args, res in _handoff_events(text):
+            assert res == [] or res[0] == 1, (letter, args, ln)                            # every transition is legal
+            if letter == "B":
+                assert not outstanding
+                begun += 1
+            elif letter == "O":
+                promised = True
+            elif letter in "KC":
+                l, v = (0, args[0]) if letter == "K" else args
+                if letter == "K" and not args[1]:
+                    continue
+                assert fuse and l in win and l not in outstanding, (letter, args, ln)
+                outstanding[l] = v
+                seen["carried_levels"].add(l)
+                seen["krylov_carried"] += letter == "K"
+            elif letter == "T":
+                l, v = args
+                if res[1]:
+                    assert outstanding.pop(l) == v, (args, ln)                             # its own vector, once
+                else:
+                    assert l not in outstanding, (args, ln)
+                    seen["plain_takes"] += 1
+            elif letter == "A":
+                rc, z = args
+                assert rc == 0 and (res[1], res[2]) == ((0, z) if outstanding else (-1, -1)), (args, res, ln)
+                assert outstanding in ({}, {0: z}) and (promised or not outstanding), (outstanding, ln)
+                seen["kept"] += bool(outstanding)
+                promised = False
+        assert not outstanding and begun == solves, ln
+        if not fuse:
+            assert not any(letter == "C" or (letter == "K" and args[1]) for letter, args, _ in _handoff_events(text))
+        if method != BICGSTAB or empty == 0:
+            assert "K" not in [e[0] for e in _handoff_events(text)]
+    # what the sequences covered: puts carried on the fine level and on two partitioned levels below it, by the Krylov kernel, kept
+    # across pc_apply for the promised operator; exchanges that had to put themselves
+    assert seen["carried_levels"] >= {0, 1, 2} and seen["window_levels"] >= {0, 1, 2} and seen["two_window_levels"] > 0
+    assert min(seen[k] for k in ("krylov_carried", "kept", "plain_takes")) > 20, seen
+
+
+def test_cycle_handoff_refuses_a_broken_protocol(tmp_path):
+    """... and the sequences policy::Handoff must refuse: a put taken twice is answered once; an exchange of another vector while
+    a carried put is outstanding; a second carried put on a level before the first is taken; a successful pc_apply left with a
+    child's put (or the fine level's, unpromised or of another vector); a solve begun with one outstanding -- the last two legal
+    after a failed call, which drops the state.  A refused transition leaves the state as it was."""
+    cases = [
+        ("B C 1 7 T 1 7 T 1 7", [[1], [1], [1, 1], [1, 0]]),                                        # the same put twice: done once
+        ("B C 1 7 T 1 8 T 1 7", [[1], [1], [0, 0], [1, 1]]),                                        # another vector: refused, the put stays
+        ("B C 1 7 T 2 8 T 0 8", [[1], [1], [1, 0], [1, 0]]),                                        # (another level is another plan)
+        ("B C 1 7 C 1 8 C 2 8 T 1 7 C 1 8", [[1], [1], [0], [1], [1, 1], [1]]),                     # a second carried put on the level
+        ("B K 7 1 K 8 1 N 0 N 0 T 0 7", [[1], [1], [0], [1, 1], [1, 0], [1, 1]]),                   # ... by the Krylov kernel
+        ("B K 7 0 N 1 N 0 N 0", [[1], [1], [1, 0], [1, 1], [1, 0]]),                                # the first sweep: the fine level's, once
+        ("B C 1 7 A 0 3 B", [[1], [1], [0, -1, -1], [1]]),                                          # a child's put left behind
+        ("B O C 0 3 A 0 3 T 0 3 B", [[1], [1], [1, 0, 3], [1, 1], [1]]),                            # the promised result: kept, then taken
+        ("B C 0 3 A 0 3 B", [[1], [1], [0, -1, -1], [1]]),                                          # ... unpromised
+        ("B O C 0 4 A 0 3", [[1], [1], [0, -1, -1]]),                                               # ... of another vector
+        ("B O C 0 3 C 2 9 A 0 3 T 0 3 B", [[1], [1], [1], [0, 0, 3], [1, 1], [1]]),                 # (z kept, the child's put refused)
+        ("B O C 0 3 A 0 3 B B", [[1], [1], [1, 0, 3], [0], [1]]),                                   # a solve begun with one outstanding
+        ("B C 1 7 B B", [[1], [1], [0], [1]]),
+        ("B O C 0 3 C 1 7 A -1 3 B", [[1], [1], [1], [1, -1, -1], [1]]),                            # after a failed call: dropped, legal
+        ("B K 7 1 A -3 3 N 0 T 0 7 B", [[1], [1], [1, -1, -1], [1, 0], [1, 0], [1]]),
+        ("C -1 7 T -1 7 C 0 0", [[0], [0, 0], [1]]),                                                # (no such level; vector 0 is a name too)
+    ]
+    out = _handoff_run(tmp_path, ["E " + seq for seq, _ in cases])
+    for (seq, want), ln in zip(cases, out):
+        assert [r for letter, _, r in _handoff_events(ln) if letter != "O"] == want, (seq, ln)      # (a promise is always legal)
+
+
+def test_first_sweep_owner_table(built_lib, tmp_path):
+    """Who does a level's first sweep (csrc/sns_policy.h: policy::first_sweep_owner) for every level of the hand-off tests' plans
+    and of the hierarchies on record, against a transcription of the five expressions the cycle had inline before -- vcycle,
+    vcycle_windows, launch_restrict, enter_replicated_tail, fused_first_sweep_target -- written here and not derived from the header."""
+    NOBODY, LEVEL, RESTRICTION, GATHER = range(4)                                            # policy::FirstSweepOwner
+    shapes = [(2, rows, rep) for rows, rep in _HANDOFF_SHAPES]
+    shapes += [(1, [1738576, 218044, 27436, 3800, 475], 0), (8, [1738576, 218044, 28880, 30027, 4454, 721, 136], 3),
+               (4, [1225, 218, 218, 37, 7], 2), (1, [500], 0)]
+    out = _handoff_run(tmp_path, ["W %d %d %d %s" % (nranks, rep, len(rows), " ".join(map(str, rows))) for nranks, rows, rep in shapes])
+    seen = set()
+    for (nranks, rows, rep), ln in zip(shapes, out):
+        gather_first, *cols, past_end = ln.split()
+        gather_first, nl = int(gather_first), len(rows)
+        fuses = [int(c.split(":")[0]) for c in cols]
+        owner = [int(c.split(":")[1]) for c in cols]
+        assert int(past_end) == NOBODY and len(owner) == nl
+        for l in range(nl):
+            # vcycle reaches its first sweep for a level that is neither the source of the replicated copy nor the last ...
+            cycled = not (rep > 0 and l == rep - 1) and l + 1 < nl
+            # ... and launches it unless (the Krylov kernel aside) one of these holds: vcycle's and vcycle_windows' clause,
+            by_restriction = l > 0 and fuses[l - 1]
+            # vcycle's and enter_replicated_tail's
+            by_gather = rep > 0 and l == rep and gather_first
+            assert (owner[l] == LEVEL) == bool(cycled and not by_restriction and not by_gather), (rows, rep, l)
+            assert (owner[l] == GATHER) == bool(cycled and by_gather) and (owner[l] == NOBODY) == (not cycled), (rows, rep, l)
+            # launch_restrict from level l - 1 writes it where that level's plan says so
+            assert (owner[l] == RESTRICTION) == bool(by_restriction), (rows, rep, l)
+            seen.add(owner[l])
+        # fused_first_sweep_target: not with a single level, not where level 0 is only the source of the copy
+        assert (owner[0] == LEVEL) == (nl >= 2 and rep != 1)
+    assert seen == {NOBODY, LEVEL, RESTRICTION, GATHER}
