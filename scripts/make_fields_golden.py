@@ -1,5 +1,5 @@
 """Writes tests/golden/fields_cases.npz, the fixture of the external-fields tests (tests/test_host_fields.py,
-tests/test_gpu_fields.py), from the CPU oracle tests/fields_oracle.py alone:
+tests/test_gpu_fields.py), from the CPU oracle tests/ns3d_oracle.py alone:
 
   el_X, el_W, el_D, el_F, el_nu,     the element cases: 4 regular + 3 sliver tets with random states, histories, forces, Re in
   el_Re, el_sigma, el_theta          [5, 200], nu_t in [0.2, 5] / Re (log-uniform), sigma in [1, 30], theta in [0, 1600]
@@ -77,8 +77,7 @@ def step_problem():
 
 
 def build():
-    import fields_oracle as FO
-    import viscosity_oracle as VO
+    import ns3d_oracle as NS
     rng = np.random.default_rng(20261)
     X = np.concatenate([random_tets(rng, 4), random_tets(rng, 3, sliver=True)])
     W = rng.normal(size=(7, 16))
@@ -86,24 +85,24 @@ def build():
     Re = rng.uniform(5.0, 200.0, size=7)
     nu = 10.0 ** rng.uniform(np.log10(0.2), np.log10(5.0), size=7) / Re
     sigma, theta = rng.uniform(1.0, 30.0, size=7), rng.uniform(0.0, 1600.0, size=7)
-    el_R = np.stack([np.concatenate([FO.element(X[i][None], W[i][None], Dn[i][None], Fn[i][None], nu[i:i + 1], Re[i], sigma[i], theta[i],
-                                                True, corrected_convection=c, want_jac=False)[0] for i in range(7)])
+    el_R = np.stack([np.concatenate([NS.element(X[i][None], W[i][None], Re[i], d=Dn[i][None], f=Fn[i][None], nu_t=nu[i:i + 1], sigma=sigma[i],
+                                                theta=theta[i], stress_div=True, corrected_convection=c, want_jac=False)[0] for i in range(7)])
                      for c in (False, True)])
     out = dict(el_X=X, el_W=W, el_D=Dn, el_F=Fn, el_nu=nu, el_Re=Re, el_sigma=sigma, el_theta=theta, el_R=el_R)
     # one BDF1 and one BDF2 step with both fields
     m, mask, g, w0, Re_s = step_problem()
-    nu_t, f = FO.mixture_fields(m.points, m.tets, smooth_m(m.points), Re_s, STEP["log_ratio"], STEP["buoyancy"])
-    w1, _ = FO.step(m.points, m.tets, mask, g, Re_s, w0, w0, STEP["dt"], 1, STEP["theta_coeff"], f=f, nu_t=nu_t)
-    w2, _ = FO.step(m.points, m.tets, mask, g, Re_s, w1, w0, STEP["dt"], 2, STEP["theta_coeff"], f=f, nu_t=nu_t)
+    nu_t, f = NS.mixture_fields(m.points, m.tets, smooth_m(m.points), Re_s, STEP["log_ratio"], STEP["buoyancy"])
+    w1, _ = NS.step(m.points, m.tets, mask, g, Re_s, w0, w0, STEP["dt"], 1, STEP["theta_coeff"], f=f, nu_t=nu_t)
+    w2, _ = NS.step(m.points, m.tets, mask, g, Re_s, w1, w0, STEP["dt"], 2, STEP["theta_coeff"], f=f, nu_t=nu_t)
     out.update(step_w1=w1, step_w2=w2)
     # the coupled fixed points
     m, mask, g, cm, cv = duct_problem()
     C = COUPLED
-    w0 = VO.stokes_start(m.points, m.tets, mask, g)
+    w0 = NS.stokes_start(m.points, m.tets, mask, g)
     out["duct_stokes"] = w0
     for name in ("visc", "buoy", "unc"):
         kw = C[name] if name != "unc" else dict(log_ratio=0.0, buoyancy=(0.0, 0.0, 0.0))
-        w, c, ch = FO.coupled(m.points, m.tets, mask, g, C["Re"], w0, C["kappa"], cm, cv, rtol=C["rtol"], **kw)
+        w, c, ch = NS.coupled(m.points, m.tets, mask, g, C["Re"], w0, C["kappa"], cm, cv, rtol=C["rtol"], **kw)
         out[name + "_w"], out[name + "_c"] = w, c
         if name != "unc":
             out[name + "_outer"], out[name + "_factor"] = len(ch), ch[-1] / ch[-2]

@@ -1,5 +1,5 @@
 """Writes tests/golden/viscosity_cases.npz, the fixture of the viscosity-law tests (tests/test_host_viscosity.py,
-tests/test_gpu_viscosity.py), from the CPU oracle tests/viscosity_oracle.py alone:
+tests/test_gpu_viscosity.py), from the CPU oracle tests/ns3d_oracle.py alone:
 
   el_X, el_W, el_Re, el_lam          the element cases: 4 regular + 3 sliver tets with random states, Re in [5, 200] and
                                      lambda in [0.1, 10] (log-uniform); the tests cross them with n and r
@@ -64,19 +64,19 @@ def newtonian_field(m, mask, g, Re, w0, tol=1e-12, max_it=40):
 
 
 def build():
-    import viscosity_oracle as VO
+    import ns3d_oracle as NS
     rng = np.random.default_rng(20260)
     X = np.concatenate([random_tets(rng, 4), random_tets(rng, 3, sliver=True)])
     W = rng.normal(size=(7, 16))
     Re = rng.uniform(5.0, 200.0, size=7)
     lam = 10.0 ** rng.uniform(-1.0, 1.0, size=7)
-    el_F = np.stack([np.concatenate([VO.element(X[i][None], W[i][None], Re[i], lam[i], 0.7, 0.05, corrected_convection=c,
+    el_F = np.stack([np.concatenate([NS.element(X[i][None], W[i][None], Re[i], law=(lam[i], 0.7, 0.05), corrected_convection=c,
                                                 want_jac=False)[0] for i in range(7)]) for c in (False, True)])
     m, mask, g = duct_problem()
     D = DUCT
-    w0 = VO.stokes_start(m.points, m.tets, mask, g)
-    w_law, _ = VO.newton(m.points, m.tets, mask, g, D["Re"], D["lam"], D["n"], D["r"], w0)
-    w_low, _ = VO.newton(m.points, m.tets, mask, g, D["Re"], D["lam"], D["n_low"], D["r"], w_law)
+    w0 = NS.stokes_start(m.points, m.tets, mask, g)
+    w_law, _ = NS.newton(m.points, m.tets, mask, g, D["Re"], w0, law=(D["lam"], D["n"], D["r"]))
+    w_low, _ = NS.newton(m.points, m.tets, mask, g, D["Re"], w_law, law=(D["lam"], D["n_low"], D["r"]))
     w_newt = newtonian_field(m, mask, g, D["Re"], w0)
     return dict(el_X=X, el_W=W, el_Re=Re, el_lam=lam, el_F=el_F, cells=np.array(D["cells"]), length=D["length"], jitter=D["jitter"],
                 Re=D["Re"], lam=D["lam"], n=D["n"], r=D["r"], n_low=D["n_low"], duct_stokes=w0, duct_law=w_law, duct_newton=w_newt,

@@ -11,9 +11,9 @@ normal), so per-vertex data is indexed as the caller gave it.
              beta (F,) by the 6-point degree-4 rule with positive weights (A1, W1, A2, W2 below, weights times |Gamma|)
     scalars  R_k(c; v) += int (alpha_k c_k - g_k) v ds                   alpha (F, 4), g P1 per facet (F, 3, 4)
 
-On top: global assembly with ``fields_oracle.raw`` / ``scalar_oracle.raw`` and the Dirichlet rule of ``oracle/assemble.py`` (the
-facet terms are part of the raw form: lifting through their columns, rows of constrained dofs replaced), Newton with a sparse
-LU, one BDF step.
+On top: the drivers of ``ns3d_oracle`` with the flow terms as their ``extra=`` (the facet terms are part of the raw form: lifting
+through their columns, rows of constrained dofs replaced), and ``scalar_oracle.raw`` with the Dirichlet rule of
+``oracle/assemble.py`` for the scalars.
 """
 from __future__ import annotations
 
@@ -24,7 +24,7 @@ import torch
 
 from oracle import assemble as asm
 
-import fields_oracle as FO
+import ns3d_oracle as NS
 import scalar_oracle as SO
 
 _T = torch.float64
@@ -98,56 +98,34 @@ def flow_raw(points, tets, w, facets, facet_tets, t=None, beta=None, want_jac=Tr
     return F, sp.coo_matrix((Je.ravel(), (rows, cols)), shape=(ndof, ndof)).tocsr()
 
 
-def raw(points, tets, w, Re, facets, facet_tets, *, t=None, beta=None, want_jac=True, **kw):
-    """Volume (``fields_oracle.raw``, its keywords) plus boundary: the raw residual and Jacobian of the whole form."""
-    F, J = FO.raw(points, tets, w, Re, want_jac=want_jac, **kw)
-    Fb, Jb = flow_raw(points, tets, w, facets, facet_tets, t, beta, want_jac)
-    return F + Fb, (J + Jb if want_jac else None)
+def _facet_terms(points, tets, facets, facet_tets, kw):
+    """Takes t= and beta= out of kw: the flow terms as the ``extra=`` of the shared drivers."""
+    t, beta = kw.pop("t", None), kw.pop("beta", None)
+    return lambda w, want_jac: flow_raw(points, tets, w, facets, facet_tets, t, beta, want_jac)
+
+
+def raw(points, tets, w, Re, facets, facet_tets, **kw):
+    """Volume (``ns3d_oracle.raw``, its keywords) plus boundary (t=, beta=): the raw residual and Jacobian of the whole form."""
+    extra = _facet_terms(points, tets, facets, facet_tets, kw)
+    return NS.raw(points, tets, w, Re, extra=extra, **kw)
 
 
 def assemble(points, tets, w, Re, mask, g, facets, facet_tets, **kw):
-    """(J, F) with the Dirichlet rule of oracle/assemble.assemble_ns applied to the whole raw form."""
-    F, J0 = raw(points, tets, w, Re, facets, facet_tets, **kw)
-    B = mask.astype(bool)
-    F = F + J0[:, B] @ (g[B] - w[B])
-    F[B] = w[B] - g[B]
-    return asm._apply_bc_matrix(J0, mask), F
+    """(J, F) of ``ns3d_oracle.assemble``: the Dirichlet rule applied to the whole raw form."""
+    extra = _facet_terms(points, tets, facets, facet_tets, kw)
+    return NS.assemble(points, tets, w, Re, mask, g, extra=extra, **kw)
 
 
-def newton(points, tets, mask, g, Re, w0, facets, facet_tets, *, tol=1e-12, max_it=40, **kw):
-    """``fields_oracle.newton`` with the boundary terms: sparse LU, backtracking.  Returns (w, its)."""
-    B = mask.astype(bool)
-    x = np.asarray(w0, dtype=np.float64).copy()
-    x[B] = g[B]
-    for it in range(max_it):
-        J, F = assemble(points, tets, x, Re, mask, g, facets, facet_tets, **kw)
-        y = spla.splu(sp.csc_matrix(J)).solve(F)
-        if np.linalg.norm(y) <= tol * max(np.linalg.norm(x), 1e-300):
-            return x - y, it + 1
-        f0, step = np.linalg.norm(F), 1.0
-        while step > 1e-3:
-            Ft, _ = raw(points, tets, x - step * y, Re, facets, facet_tets, want_jac=False, **kw)
-            Ft[B] = 0.0
-            if np.linalg.norm(Ft) < f0:
-                break
-            step *= 0.5
-        x = x - step * y
-    raise RuntimeError("oracle Newton did not converge")
+def newton(points, tets, mask, g, Re, w0, facets, facet_tets, **kw):
+    """``ns3d_oracle.newton`` with the boundary terms.  Returns (w, its)."""
+    extra = _facet_terms(points, tets, facets, facet_tets, kw)
+    return NS.newton(points, tets, mask, g, Re, w0, extra=extra, **kw)
 
 
-def step(points, tets, mask, g, Re, w, wprev, dt, order, theta_coeff, facets, facet_tets, *, tol=1e-11, max_it=30, **kw):
-    """One implicit BDF step (``fields_oracle.step``) with the boundary terms.  Returns (w, its)."""
-    sigma, d = (1.0 / dt, -w / dt) if order == 1 else (1.5 / dt, (-2.0 * w + 0.5 * wprev) / dt)
-    B = mask.astype(bool)
-    x = w.copy()
-    x[B] = g[B]
-    for it in range(max_it):
-        J, F = assemble(points, tets, x, Re, mask, g, facets, facet_tets, d=d, sigma=sigma, theta=theta_coeff / dt ** 2, **kw)
-        y = spla.splu(sp.csc_matrix(J)).solve(F)
-        x = x - y
-        if np.linalg.norm(y) <= tol * max(np.linalg.norm(x), 1e-300):
-            return x, it + 1
-    raise RuntimeError("oracle Newton did not converge")
+def step(points, tets, mask, g, Re, w, wprev, dt, order, theta_coeff, facets, facet_tets, **kw):
+    """One implicit BDF step (``ns3d_oracle.step``) with the boundary terms.  Returns (w, its)."""
+    extra = _facet_terms(points, tets, facets, facet_tets, kw)
+    return NS.step(points, tets, mask, g, Re, w, wprev, dt, order, theta_coeff, extra=extra, **kw)
 
 
 # ---- scalars --------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 The project's CPU forms are differentiable in the vertex coordinates, so the oracle is autograd over them, with no closed
 form shared with the HIP kernels:
 
-    3-D  ``tests/transient_oracle.transient_residual`` with X a tensor that requires grad (sigma = theta = 0, d = 0 is the
+    3-D  ``tests/ns3d_oracle.residual`` with X a tensor that requires grad (sigma = theta = 0, d = 0 is the
          steady form; ``forms_literal.VARIANT`` and ``corrected_convection`` apply as there),
     2-D  ``oracle.forms2d.ugn_residual_one`` under ``torch.func.jacrev(..., argnums=0)``.
 
@@ -17,7 +17,7 @@ import torch
 
 from oracle import forms2d as F2
 
-import transient_oracle as TO
+import ns3d_oracle as NS
 
 _T = torch.float64
 _C3 = [0, 1, 3]
@@ -27,8 +27,8 @@ _C3 = [0, 1, 3]
 def tet_cell_residuals(X, W, D, Re, sigma=0.0, theta=0.0, corrected_convection=False):
     """(E,16) element residuals as numpy; X (E,4,3), W (E,16), D (E,4,3)."""
     Wt = torch.as_tensor(np.asarray(W, dtype=np.float64), dtype=_T)
-    return TO.transient_residual(np.asarray(X, dtype=np.float64), Wt, D, Re, sigma, theta,
-                                 corrected_convection=corrected_convection).numpy()
+    return NS.residual(np.asarray(X, dtype=np.float64), Wt, Re, d=D, sigma=sigma, theta=theta,
+                       corrected_convection=corrected_convection).numpy()
 
 
 def tet_cell_gradients(X, W, Lam, D, Re, sigma=0.0, theta=0.0, corrected_convection=False):
@@ -36,7 +36,7 @@ def tet_cell_gradients(X, W, Lam, D, Re, sigma=0.0, theta=0.0, corrected_convect
     Xt = torch.as_tensor(np.asarray(X, dtype=np.float64), dtype=_T).clone().requires_grad_(True)
     Wt = torch.as_tensor(np.asarray(W, dtype=np.float64), dtype=_T)
     Lt = torch.as_tensor(np.asarray(Lam, dtype=np.float64), dtype=_T)
-    F = TO.transient_residual(Xt, Wt, D, Re, sigma, theta, corrected_convection=corrected_convection)
+    F = NS.residual(Xt, Wt, Re, d=D, sigma=sigma, theta=theta, corrected_convection=corrected_convection)
     (g,) = torch.autograd.grad((F * Lt).sum(), Xt)          # a tet's residual depends on its own vertices only
     return g.numpy()
 

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import boundary_oracle as BO
-import fields_oracle as FO
+import ns3d_oracle as NS
 import scalar_oracle as SO
 from conftest import rel
 from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B
@@ -72,7 +72,7 @@ def test_one_tet_against_the_oracle(fused):
     for i in range(len(fx["X"])):
         X, W = fx["X"][i], fx["W"][i]
         m = M.TetMesh(np.ascontiguousarray(X), tet, fx["faces"].astype(np.int32), np.zeros(4, np.int32))
-        Fv, Jv = FO.raw(X, tet, W, RE)
+        Fv, Jv = NS.raw(X, tet, W, RE)
         Fo, Jo = Fv + fx["F"][i], Jv.toarray() + fx["J"][i]
         P = FlowProblem(m, none, reynolds=RE, pc_type="bjacobi", assembly_fused=fused)
         P.set_boundary_facets(np.arange(4))
@@ -114,7 +114,7 @@ def test_fused_staged_and_oracle_agree_globally(corrected):
         for state in (c["w"], c["w2"]):                             # w2: the lifting through boundary columns
             Jo, Fo = BO.assemble(m.points, m.tets, state, RE, c["mask"], c["g"], c["facets"], c["own"], t=c["t"], beta=c["beta"],
                                  corrected_convection=bool(corrected), **kw)
-            Jv, Fv = FO.assemble(m.points, m.tets, state, RE, c["mask"], c["g"], corrected_convection=bool(corrected), **kw)
+            Jv, Fv = NS.assemble(m.points, m.tets, state, RE, c["mask"], c["g"], corrected_convection=bool(corrected), **kw)
             assert abs(Jo - Jv).max() > 1e-3 * abs(Jo).max() and rel(Fv, Fo) > 1e-3      # (the terms are visible at this state)
             got = []
             for fused in (1, 0):
@@ -244,7 +244,7 @@ def test_adjoint_identity_with_backflow():
     rng = c["rng"]
     P.jacobian(U, "ns")
     A = P.to_scipy()
-    Jv = FO.assemble(c["m"].points, c["m"].tets, U.cpu().numpy(), RE, c["mask"], c["g"])[0]
+    Jv = NS.assemble(c["m"].points, c["m"].tets, U.cpu().numpy(), RE, c["mask"], c["g"])[0]
     assert abs(A - Jv).max() > 1e-3 * abs(A).max()                  # (the backflow term is in the operator)
     _adjoint_identity(P, A, rng.normal(size=c["m"].num_dofs), rng.normal(size=c["m"].num_dofs), "backflow")
     P.close()
@@ -260,7 +260,7 @@ def test_residual_moments_include_the_boundary_residual():
     ind[np.unique(m.facets[c["outlet"]])] = 1.0
     for state in (c["w"], c["w2"]):                                 # R_raw knows no Dirichlet rule
         Fr, _ = BO.raw(m.points, m.tets, state, RE, c["facets"], c["own"], t=c["t"], beta=c["beta"], want_jac=False)
-        Fv, _ = FO.raw(m.points, m.tets, state, RE, want_jac=False)
+        Fv, _ = NS.raw(m.points, m.tets, state, RE, want_jac=False)
         for name, phi in (("one", np.ones(m.num_nodes)), ("outlet", ind)):
             want = (phi[:, None] * Fr.reshape(-1, 4)).sum(axis=0)
             without = (phi[:, None] * Fv.reshape(-1, 4)).sum(axis=0)
@@ -276,7 +276,7 @@ def test_bdf2_step_with_backflow():
     w0 = U.cpu().numpy()
     dt, theta_coeff = 0.05, 4.0
     wo, its = BO.step(m.points, m.tets, c["mask"], c["g"], RE, w0, w0, dt, 2, theta_coeff, c["facets"], c["own"], beta=c["beta"])
-    wv, _ = FO.step(m.points, m.tets, c["mask"], c["g"], RE, w0, w0, dt, 2, theta_coeff)
+    wv, _ = NS.step(m.points, m.tets, c["mask"], c["g"], RE, w0, w0, dt, 2, theta_coeff)
     w, wprev = U.clone(), U.clone()
     w, res = P.time_step(w, wprev, dt, order=2, theta_coeff=theta_coeff)
     print(f"BDF2 step with backflow: its {res.its} (oracle {its}) reason {res.reason} rel {rel(w.cpu().numpy(), wo):.2e}; the step "

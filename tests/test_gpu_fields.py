@@ -1,7 +1,7 @@
 """Body force and per-cell viscosity field of the 3-D NS form on the GPU (sns_set_body_force, sns_set_element_viscosity,
 sns_set_mixture; solver.solve_coupled_flow), everything through the C-ABI.
 
-The reference has no right-hand side and a constant viscosity; the yardstick is the test-side oracle tests/fields_oracle.py
+The reference has no right-hand side and a constant viscosity; the yardstick is the test-side oracle tests/ns3d_oracle.py
 (literal restatement, autograd Jacobian, LU-Newton, the same fixed-point loop) whose own checks are tests/test_host_fields.py,
 and its fields in tests/golden/fields_cases.npz.  Tolerances as in tests/test_gpu_viscosity.py and tests/test_gpu_transient.py:
 operators and residuals 1e-12 relative, the two assembly paths against each other 1e-13, Krylov-converged fields 1e-6, J dw
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-import fields_oracle as FO
+import ns3d_oracle as NS
 from conftest import rel
 from oracle import forms_literal as FL
 from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B
@@ -68,8 +68,9 @@ def test_element_matrices_against_the_oracle(corrected):
         sigma, theta = float(fx["el_sigma"][i]), float(fx["el_theta"][i])
         oracle = {}
         for bf, ev, tt in COMBOS:
-            oracle[(bf, ev, tt)] = FO.element(X[i][None], W[None], D[None] if tt else None, Fn[None] if bf else None, nu if ev else None, Re,
-                                              sigma if tt else 0.0, theta if tt else 0.0, bool(ev), corrected_convection=bool(corrected))
+            oracle[(bf, ev, tt)] = NS.element(X[i][None], W[None], Re, d=D[None] if tt else None, f=Fn[None] if bf else None, nu_t=nu if ev else None,
+                                              sigma=sigma if tt else 0.0, theta=theta if tt else 0.0, stress_div=bool(ev),
+                                              corrected_convection=bool(corrected))
         assert rel(oracle[(1, 1, 1)][0][0], fx["el_R"][corrected][i]) < 1e-12      # (the fixture's record)
         for fused in (0, 1):
             P = FlowProblem(_one_tet(X[i]), none, reynolds=Re, corrected_convection=corrected, pc_type="bjacobi", assembly_fused=fused)
@@ -122,7 +123,7 @@ def test_fused_staged_and_oracle_agree_globally(corrected):
             P.set_element_viscosity(nu)
             P.set_time_term(kw["sigma"], kw["theta"], _dev(d))
         for state in (w, w2):
-            Jo, Fo = FO.assemble(m.points, m.tets, state, Re, mask, g, corrected_convection=bool(corrected), **kw)
+            Jo, Fo = NS.assemble(m.points, m.tets, state, Re, mask, g, corrected_convection=bool(corrected), **kw)
             got = []
             for fused in (1, 0):
                 P.set_options(assembly_fused=fused)
@@ -148,7 +149,7 @@ def test_perturbed_form_variant_with_both_fields(corrected):
         FL.VARIANT.update(ci=144.0, lsic=4.0, pspg=-1.0, one_point=True)
         for i in range(2):
             W, Fn, nu = rng.normal(size=16), rng.normal(size=(4, 3)), np.array([0.07 * (i + 1)])
-            Fo, Jo = FO.element(X[i][None], W[None], None, Fn[None], nu, 40.0, 0.0, 0.0, True, corrected_convection=bool(corrected))
+            Fo, Jo = NS.element(X[i][None], W[None], 40.0, f=Fn[None], nu_t=nu, stress_div=True, corrected_convection=bool(corrected))
             P = FlowProblem(_one_tet(X[i]), none, reynolds=40.0, corrected_convection=corrected, pc_type="bjacobi")
             P.set_form_variant(c_inverse=144.0, lsic_scale=4.0, pspg_sign=-1.0, one_point_quadrature=True)
             P.set_body_force(_dev(_dofs(Fn, rng)))
@@ -365,7 +366,7 @@ def test_set_mixture_against_the_oracle():
     m, mask, g = _channel()
     mm = rng.uniform(-0.2, 1.2, size=m.num_nodes)                  # over- and undershoots
     Re, lr, bu = 30.0, float(np.log(20.0)), (0.3, -2.0, 0.7)
-    nu_o, f_o = FO.mixture_fields(m.points, m.tets, mm, Re, lr, bu)
+    nu_o, f_o = NS.mixture_fields(m.points, m.tets, mm, Re, lr, bu)
     w = rng.normal(size=m.num_dofs) * 0.5
     w[mask.astype(bool)] = g[mask.astype(bool)]
     wd = _dev(w)
@@ -477,7 +478,7 @@ def test_residual_moments_with_both_fields_against_the_oracle():
     fx = np.load(FIXTURE)
     m, mask, g, _, _ = G.duct_problem()
     P = FlowProblem(m, (mask, g), reynolds=C["Re"])
-    nu_t, f = FO.mixture_fields(m.points, m.tets, fx["visc_c"], C["Re"], np.log(4.0), (0.4, -2.0, 0.1))
+    nu_t, f = NS.mixture_fields(m.points, m.tets, fx["visc_c"], C["Re"], np.log(4.0), (0.4, -2.0, 0.1))
     P.set_mixture(fx["visc_c"], np.log(4.0), (0.4, -2.0, 0.1))
     wh = fx["visc_w"] + 0.05 * rng.normal(size=m.num_dofs)         # (may violate the Dirichlet data: raw residual)
     base = dict(FL.VARIANT)
@@ -486,7 +487,7 @@ def test_residual_moments_with_both_fields_against_the_oracle():
             if variant:
                 FL.VARIANT.update(ci=144.0, lsic=4.0)
                 P.set_form_variant(c_inverse=144.0, lsic_scale=4.0)
-            F, _ = FO.raw(m.points, m.tets, wh, C["Re"], f=f, nu_t=nu_t, want_jac=False)
+            F, _ = NS.raw(m.points, m.tets, wh, C["Re"], f=f, nu_t=nu_t, want_jac=False)
             for phi in (rng.uniform(-1.0, 1.0, size=m.num_nodes), (m.points[:, 0] < 0.5).astype(np.float64)):
                 out = P.residual_moments(_dev(wh), phi)
                 ref = (phi[:, None] * F.reshape(-1, 4)).sum(axis=0)

@@ -1,7 +1,7 @@
 """Generalised-Newtonian (Carreau) viscosity of the 3-D NS form on the GPU (sns_set_viscosity_law, sns_element_viscosity;
 solver.newton_with_law_continuation), everything through the C-ABI.
 
-The reference has a constant viscosity; the yardstick is the test-side oracle tests/viscosity_oracle.py (literal restatement,
+The reference has a constant viscosity; the yardstick is the test-side oracle tests/ns3d_oracle.py (literal restatement,
 autograd Jacobian, LU-Newton) whose own checks are tests/test_host_viscosity.py, and its fields in
 tests/golden/viscosity_cases.npz.  Tolerances as in tests/test_gpu_transient.py: operators 1e-12 relative, the two assembly
 paths against each other 1e-13, Krylov-converged fields 1e-6, J dw against central differences of the residual 1e-6."""
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-import viscosity_oracle as VO
+import ns3d_oracle as NS
 from conftest import rel
 from oracle import forms_literal as FL
 from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B
@@ -54,7 +54,7 @@ def test_element_matrices_against_the_oracle(corrected):
     for i in range(len(X)):
         W, Re, lam = Ws[i], float(fx["el_Re"][i]), float(fx["el_lam"][i])
         assert 5.0 <= Re <= 200.0 and 0.1 <= lam <= 10.0
-        oracle = {nr: VO.element(X[i][None], W[None], Re, lam, *nr, corrected_convection=bool(corrected)) for nr in N_R}
+        oracle = {nr: NS.element(X[i][None], W[None], Re, law=(lam, *nr), corrected_convection=bool(corrected)) for nr in N_R}
         assert rel(oracle[(0.7, 0.05)][0][0], fx["el_F"][corrected][i]) < 1e-12        # (the fixture's record)
         for fused in (0, 1):
             P = FlowProblem(_one_tet(X[i]), none, reynolds=Re, corrected_convection=corrected, pc_type="bjacobi", assembly_fused=fused)
@@ -83,7 +83,7 @@ def test_perturbed_form_variant_with_a_law(corrected):
         FL.VARIANT.update(ci=144.0, lsic=4.0, pspg=-1.0, one_point=True)
         for i in range(2):
             W = rng.normal(size=16)
-            Fo, Jo = VO.element(X[i][None], W[None], 40.0, 2.0, 0.4, 0.05, corrected_convection=bool(corrected))
+            Fo, Jo = NS.element(X[i][None], W[None], 40.0, law=(2.0, 0.4, 0.05), corrected_convection=bool(corrected))
             P = FlowProblem(_one_tet(X[i]), none, reynolds=40.0, corrected_convection=corrected, pc_type="bjacobi")
             P.set_form_variant(c_inverse=144.0, lsic_scale=4.0, pspg_sign=-1.0, one_point_quadrature=True)
             P.set_viscosity_law(2.0, 0.4, 0.05)
@@ -118,7 +118,7 @@ def test_fused_staged_and_oracle_agree_globally(corrected):
     P = FlowProblem(m, (mask, g), reynolds=Re, corrected_convection=corrected)
     P.set_viscosity_law(*law)
     for state in (w, w2):
-        Jo, Fo = VO.assemble(m.points, m.tets, state, Re, *law, mask, g, **kw)
+        Jo, Fo = NS.assemble(m.points, m.tets, state, Re, mask, g, law=law, **kw)
         got = []
         for fused in (1, 0):
             P.set_options(assembly_fused=fused)
@@ -224,7 +224,7 @@ def test_newton_on_the_duct_matches_the_lu_oracle(duct_runs):
 
 def test_element_viscosity_against_the_oracle(duct_runs):
     m, _, wl, _, _, _, nu, gd = duct_runs
-    nu_o, gd_o = VO.element_viscosity(m.points, m.tets, wl, D["Re"], *LAW)
+    nu_o, gd_o = NS.element_viscosity(m.points, m.tets, wl, D["Re"], *LAW)
     assert np.abs(nu / nu_o - 1.0).max() < 1e-13
     assert np.abs(gd - gd_o).max() < 1e-13 * gd_o.max()
     assert nu.max() <= 1.0 / D["Re"] and nu.min() >= D["r"] / D["Re"]
@@ -261,14 +261,14 @@ def test_residual_moments_with_the_law_against_the_oracle():
             if variant:
                 FL.VARIANT.update(ci=144.0, lsic=4.0)
                 P.set_form_variant(c_inverse=144.0, lsic_scale=4.0)
-            F, _ = VO.raw(m.points, m.tets, wh, D["Re"], *LAW, want_jac=False)
+            F, _ = NS.raw(m.points, m.tets, wh, D["Re"], law=LAW, want_jac=False)
             for phi in (rng.uniform(-1.0, 1.0, size=m.num_nodes), (m.points[:, 0] < 0.5).astype(np.float64)):
                 out = P.residual_moments(_dev(wh), phi)
                 ref = (phi[:, None] * F.reshape(-1, 4)).sum(axis=0)
                 assert np.abs(out - ref).max() <= 1e-12 * np.linalg.norm(ref), (variant, out, ref)
     finally:
         FL.VARIANT.update(base)
-    Fs, _ = VO.raw(m.points, m.tets, wh, D["Re"], 0.0, 1.0, 0.0, want_jac=False)
+    Fs, _ = NS.raw(m.points, m.tets, wh, D["Re"], law=(0.0, 1.0, 0.0), want_jac=False)
     assert np.abs(F - Fs).max() > 1e-6 * np.abs(Fs).max()          # (the law's residual is another residual)
     P.close()
 

@@ -18,7 +18,7 @@ from conftest import GOLDEN
 torch = pytest.importorskip("torch")
 
 import boundary_oracle as BO  # noqa: E402
-import fields_oracle as FO  # noqa: E402
+import ns3d_oracle as NS  # noqa: E402
 import scalar_oracle as SO  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,7 +57,7 @@ def hydrostatic_problem():
 
 def test_hydrostatic_state_has_no_residual():
     m, par, w, f, t = hydrostatic_problem()
-    Fv, _ = FO.raw(m.points, m.tets, w, 10.0, f=f, want_jac=False)
+    Fv, _ = NS.raw(m.points, m.tets, w, 10.0, f=f, want_jac=False)
     Fb, _ = BO.flow_raw(m.points, m.tets, w, m.facets, par, t, None, want_jac=False)
     print("hydrostatic: volume alone", abs(Fv).max(), "volume + boundary", abs(Fv + Fb).max())
     assert abs(Fv).max() > 0.1                                  # (the volume part alone is far from zero)

@@ -1,7 +1,8 @@
-"""The 3-D NS form with a body force and a per-cell viscosity field on the CPU: the test-side oracle (tests/fields_oracle.py)
-against the two oracles it generalises (tests/transient_oracle.py, tests/viscosity_oracle.py), the patch test with a body force on
-the oracle itself, the binding of the three new entry points, and the fixture tests/golden/fields_cases.npz against its recipe
-scripts/make_fields_golden.py (the GPU tests reproduce its fields)."""
+"""The 3-D NS form with a body force and a per-cell viscosity field on the CPU: the test-side oracle (tests/ns3d_oracle.py)
+against the records of the two per-feature oracles it took over (tests/golden/ns3d_parity.npz, recipe
+scripts/make_ns3d_parity_golden.py), the patch test with a body force on the oracle itself, the binding of the three new entry
+points, and the fixture tests/golden/fields_cases.npz against its recipe scripts/make_fields_golden.py (the GPU tests reproduce
+its fields)."""
 import importlib.util
 import os
 
@@ -12,12 +13,11 @@ from conftest import GOLDEN, rel
 
 torch = pytest.importorskip("torch")
 
-import fields_oracle as FO  # noqa: E402
-import transient_oracle as TO  # noqa: E402
-import viscosity_oracle as VO  # noqa: E402
+import ns3d_oracle as NS  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(GOLDEN, "fields_cases.npz")
+PARITY = os.path.join(GOLDEN, "ns3d_parity.npz")          # what transient_residual and law_residual returned before they were merged
 
 
 def golden_script():
@@ -55,15 +55,17 @@ def test_without_fields_it_is_the_transient_oracle(corrected):
     rng = np.random.default_rng(72)
     X = golden_script().random_tets(rng, 6)
     W, D = rng.normal(size=(6, 16)), rng.normal(size=(6, 4, 3))
-    for sigma, theta in ((0.0, 0.0), (7.0, 0.0), (20.0, 1600.0)):
-        a = FO.residual(X, torch.as_tensor(W), D, None, np.full(6, 1.0 / 37.0), 37.0, sigma, theta, False, corrected_convection=corrected)
-        b = TO.transient_residual(X, torch.as_tensor(W), D, 37.0, sigma, theta, corrected_convection=corrected)
-        assert rel(a.numpy(), b.numpy()) < 1e-14
+    rec = np.load(PARITY)
+    for k, (sigma, theta) in enumerate(((0.0, 0.0), (7.0, 0.0), (20.0, 1600.0))):
+        a = NS.residual(X, torch.as_tensor(W), 37.0, d=D, nu_t=np.full(6, 1.0 / 37.0), sigma=sigma, theta=theta, stress_div=False,
+                        corrected_convection=corrected)
+        b = rec[f"transient_c{int(corrected)}_s{k}"]                              # transient_residual with the history D
+        assert rel(a.numpy(), b) < 1e-14
         # ... and a force is a history of the other sign
         F = rng.normal(size=(6, 4, 3))
-        a = FO.residual(X, torch.as_tensor(W), D, F, None, 37.0, sigma, theta, False, corrected_convection=corrected)
-        b = TO.transient_residual(X, torch.as_tensor(W), D - F, 37.0, sigma, theta, corrected_convection=corrected)
-        assert rel(a.numpy(), b.numpy()) < 1e-14
+        a = NS.residual(X, torch.as_tensor(W), 37.0, d=D, f=F, sigma=sigma, theta=theta, stress_div=False, corrected_convection=corrected)
+        b = rec[f"transient_force_c{int(corrected)}_s{k}"]                        # transient_residual with the history D - F
+        assert rel(a.numpy(), b) < 1e-14
 
 
 @pytest.mark.parametrize("corrected", [False, True])
@@ -71,12 +73,18 @@ def test_uniform_stress_divergence_form_is_the_law_at_n_one(corrected):
     rng = np.random.default_rng(73)
     X = golden_script().random_tets(rng, 6)
     W = rng.normal(size=(6, 16))
-    a = FO.residual(X, torch.as_tensor(W), None, None, None, 37.0, 0.0, 0.0, True, corrected_convection=corrected)
-    b = VO.law_residual(X, torch.as_tensor(W), 37.0, 2.5, 1.0, 0.05, corrected_convection=corrected)
-    assert rel(a.numpy(), b.numpy()) < 1e-14
+    a = NS.residual(X, torch.as_tensor(W), 37.0, stress_div=True, corrected_convection=corrected)
+    b = np.load(PARITY)[f"law_c{int(corrected)}"]                                 # law_residual with (2.5, 1.0, 0.05)
+    assert rel(a.numpy(), b) < 1e-14
     nu = 10.0 ** rng.uniform(-3.0, 0.0, size=6)
-    c = FO.residual(X, torch.as_tensor(W), None, None, nu, 37.0, 0.0, 0.0, True, corrected_convection=corrected)
+    c = NS.residual(X, torch.as_tensor(W), 37.0, nu_t=nu, stress_div=True, corrected_convection=corrected)
     assert rel(c.numpy(), a.numpy()) > 1e-3                                       # (the field is something)
+
+
+def test_a_law_and_a_viscosity_field_exclude_each_other():
+    X, W = np.random.default_rng(75).normal(size=(1, 4, 3)), torch.zeros(1, 16, dtype=torch.float64)
+    with pytest.raises(ValueError):                                               # as the library refuses the pair
+        NS.residual(X, W, 37.0, law=(2.5, 0.5, 0.05), nu_t=np.full(1, 0.1))
 
 
 def test_autograd_jacobian_against_central_differences():
@@ -84,14 +92,14 @@ def test_autograd_jacobian_against_central_differences():
     X = golden_script().random_tets(rng, 4)
     W, D, F = rng.normal(size=(4, 16)), rng.normal(size=(4, 4, 3)), rng.normal(size=(4, 4, 3))
     nu = 10.0 ** rng.uniform(-2.0, 0.0, size=4)
-    args = (D, F, nu, 20.0, 5.0, 100.0, True)
-    _, J = FO.element(X, W, *args)
+    form = dict(d=D, f=F, nu_t=nu, sigma=5.0, theta=100.0, stress_div=True)
+    _, J = NS.element(X, W, 20.0, **form)
     h = 1e-6
     for k in range(16):
         dW = np.zeros_like(W)
         dW[:, k] = h
-        Fp, _ = FO.element(X, W + dW, *args, want_jac=False)
-        Fm, _ = FO.element(X, W - dW, *args, want_jac=False)
+        Fp, _ = NS.element(X, W + dW, 20.0, want_jac=False, **form)
+        Fm, _ = NS.element(X, W - dW, 20.0, want_jac=False, **form)
         assert rel(J[:, :, k], (Fp - Fm) / (2 * h)) < 1e-7
 
 
@@ -99,10 +107,10 @@ def test_mixture_fields_closed_form():
     pts = np.array([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 1]])
     tets = np.array([[0, 1, 2, 3], [1, 2, 3, 4]], np.int32)
     m = np.array([0.0, 1.0, 1.0, 0.0, 2.0])
-    nu, f = FO.mixture_fields(pts, tets, m, 8.0, np.log(16.0), (0.0, -3.0, 0.5))
+    nu, f = NS.mixture_fields(pts, tets, m, 8.0, np.log(16.0), (0.0, -3.0, 0.5))
     assert rel(nu, [0.125 * 4.0, 0.125 * 16.0]) < 1e-15                           # 16^(1/2), 16^1
     assert np.array_equal(f.reshape(5, 4), m[:, None] * np.array([0.0, -3.0, 0.5, 0.0])[None, :])
-    nu, f = FO.mixture_fields(pts, tets, -m, 8.0, 50.0, (0.0, 0.0, 0.0))          # undershoot: still positive
+    nu, f = NS.mixture_fields(pts, tets, -m, 8.0, 50.0, (0.0, 0.0, 0.0))          # undershoot: still positive
     assert np.all(nu > 0.0) and not f.any()
 
 
@@ -110,11 +118,11 @@ def test_patch_test_with_a_body_force_on_the_oracle():
     m, mask, g, w, f, Re = patch_problem()
     free = mask == 0
     for kw in (dict(), dict(nu_t=np.full(m.num_tets, 0.37))):                     # the reference's viscous form; the stress-divergence form
-        _, F = FO.assemble(m.points, m.tets, w, Re, mask, g, f=f, corrected_convection=True, **kw)
-        _, F0 = FO.assemble(m.points, m.tets, w, Re, mask, g, corrected_convection=True, **kw)
+        _, F = NS.assemble(m.points, m.tets, w, Re, mask, g, f=f, corrected_convection=True, **kw)
+        _, F0 = NS.assemble(m.points, m.tets, w, Re, mask, g, corrected_convection=True, **kw)
         print(f"patch test {sorted(kw)}: max |F_free| {np.abs(F[free]).max():.2e}, with the force cleared {np.abs(F0[free]).max():.2e}")
         assert np.abs(F[free]).max() <= 1e-12 * np.abs(F0[free]).max()
-    x, _ = FO.newton(m.points, m.tets, mask, g, Re, np.where(free, 0.0, w), f=f, corrected_convection=True)
+    x, _ = NS.newton(m.points, m.tets, mask, g, Re, np.where(free, 0.0, w), f=f, corrected_convection=True)
     assert rel(x, w) < 1e-10
 
 

@@ -1,4 +1,4 @@
-"""The transient 3-D NS form on the CPU: the test-side oracle (tests/transient_oracle.py) against the literal steady
+"""The transient 3-D NS form on the CPU: the test-side oracle (tests/ns3d_oracle.py) against the literal steady
 restatement, its own autograd Jacobian against central differences, the mass block against its closed form, the BDF
 coefficients, and the observed order of the oracle's time stepper on the small duct whose fields at T are the fixture
 tests/golden/transient_duct_8x3x3.npz (the GPU tests reproduce them)."""
@@ -12,7 +12,7 @@ from conftest import GOLDEN, rel
 
 torch = pytest.importorskip("torch")
 
-import transient_oracle as TO  # noqa: E402
+import ns3d_oracle as NS  # noqa: E402
 
 # the stepping case (also used by tests/test_gpu_transient.py): 432-tet duct, Re 50, from the Stokes solution, theta = 0 so
 # that the spatial operator does not depend on dt.  T = 0.8 and dt = 0.1, 0.05, 0.025 against dt/16 = 0.00625 were chosen
@@ -46,7 +46,7 @@ def oracle_fields(order):
     out = {}
     for k in CASE["refine"]:
         n = k * CASE["n0"]
-        out[k] = TO.march(m.points, m.tets, mask, g, CASE["Re"], w0, CASE["T"] / n, n, order, 0.0)[-1]
+        out[k] = NS.march(m.points, m.tets, mask, g, CASE["Re"], w0, CASE["T"] / n, n, order, 0.0)[-1]
     return out
 
 
@@ -63,7 +63,7 @@ def test_steady_limit_is_the_literal_steady_form(corrected):
     rng = np.random.default_rng(5)
     X = _random_tets(rng, 6)
     W = rng.normal(size=(6, 16))
-    F, _ = TO.element(X, W, np.zeros((6, 4, 3)), 37.0, 0.0, 0.0, corrected_convection=corrected, want_jac=False)
+    F, _ = NS.element(X, W, 37.0, d=np.zeros((6, 4, 3)), corrected_convection=corrected, want_jac=False)
     for e in range(6):
         Fo = FL.ns_residual_literal(X[e], torch.as_tensor(W[e]), 37.0, corrected_convection=corrected).numpy()
         assert rel(F[e], Fo) < 1e-13
@@ -75,13 +75,13 @@ def test_autograd_jacobian_against_central_differences(corrected):
     X = _random_tets(rng, 4)
     W, D = rng.normal(size=(4, 16)), rng.normal(size=(4, 4, 3))
     kw = dict(corrected_convection=corrected)
-    _, J = TO.element(X, W, D, 20.0, 3.0, 7.0, **kw)
+    _, J = NS.element(X, W, 20.0, d=D, sigma=3.0, theta=7.0, **kw)
     h = 1e-6
     for k in range(16):
         dW = np.zeros_like(W)
         dW[:, k] = h
-        Fp, _ = TO.element(X, W + dW, D, 20.0, 3.0, 7.0, want_jac=False, **kw)
-        Fm, _ = TO.element(X, W - dW, D, 20.0, 3.0, 7.0, want_jac=False, **kw)
+        Fp, _ = NS.element(X, W + dW, 20.0, d=D, sigma=3.0, theta=7.0, want_jac=False, **kw)
+        Fm, _ = NS.element(X, W - dW, 20.0, d=D, sigma=3.0, theta=7.0, want_jac=False, **kw)
         assert rel(J[:, :, k], (Fp - Fm) / (2 * h)) < 1e-7
 
 
@@ -93,8 +93,8 @@ def test_mass_block_closed_form():
     W = np.zeros((5, 16))
     W[:, 3::4] = rng.normal(size=(5, 4))                                       # u = 0, some pressure
     D = np.zeros((5, 4, 3))
-    _, J1 = TO.element(X, W, D, 10.0, 1.0, 0.0)
-    _, J0 = TO.element(X, W, D, 10.0, 0.0, 0.0)
+    _, J1 = NS.element(X, W, 10.0, d=D, sigma=1.0)
+    _, J0 = NS.element(X, W, 10.0, d=D)
     M = (J1 - J0).reshape(5, 4, 4, 4, 4)                                       # [e, a, c, b, d]
     det = np.abs(np.linalg.det(np.stack([X[:, 1] - X[:, 0], X[:, 2] - X[:, 0], X[:, 3] - X[:, 0]], axis=2)))
     want = det[:, None, None, None, None] / 120.0 * (1 + np.eye(4))[None, :, None, :, None] * np.eye(3)[None, None, :, None, :]
@@ -107,10 +107,10 @@ def test_bdf_coefficients_differentiate_polynomials_exactly(order):
     for deg in range(order + 1):
         f = lambda t: t ** deg + 0.5
         df = deg * t1 ** (deg - 1) if deg else 0.0
-        sigma, d = TO.bdf(order, dt, np.array([f(t1 - dt)]), np.array([f(t1 - 2 * dt)]))
+        sigma, d = NS.bdf(order, dt, np.array([f(t1 - dt)]), np.array([f(t1 - 2 * dt)]))
         assert abs(sigma * f(t1) + d[0] - df) < 1e-12
     f = lambda t: t ** (order + 1)                                             # ... and not one degree more
-    sigma, d = TO.bdf(order, dt, np.array([f(t1 - dt)]), np.array([f(t1 - 2 * dt)]))
+    sigma, d = NS.bdf(order, dt, np.array([f(t1 - dt)]), np.array([f(t1 - 2 * dt)]))
     assert abs(sigma * f(t1) + d[0] - (order + 1) * t1 ** order) > 1e-3
 
 
@@ -131,13 +131,13 @@ def test_oracle_stepper_shows_the_scheme_order_and_is_the_fixture(order):
 
 def test_step_by_step_arrays_of_the_fixture_are_the_oracle():
     """w0 and steps_bdf{1,2}_tc{0,4} (what tests/test_gpu_transient.py compares single steps with): the Stokes start and four
-    steps of dt = 0.05 by ``transient_oracle.march``, theta = 0 and theta = 4 / dt^2."""
+    steps of dt = 0.05 by ``ns3d_oracle.march``, theta = 0 and theta = 4 / dt^2."""
     fx = np.load(FIXTURE)
     m, mask, g, w0 = stepping_problem()
     assert rel(fx["w0"], w0) < 1e-12
     for order in (1, 2):
         for tc in (0.0, 4.0):
-            h = TO.march(m.points, m.tets, mask, g, CASE["Re"], w0, 0.05, 4, order, tc)
+            h = NS.march(m.points, m.tets, mask, g, CASE["Re"], w0, 0.05, 4, order, tc)
             assert rel(fx[f"steps_bdf{order}_tc{int(tc)}"], np.stack(h)) < 1e-9, (order, tc)
 
 
@@ -149,5 +149,5 @@ def write_fixture(path=FIXTURE):
         for k, v in oracle_fields(order).items():
             out[f"bdf{order}_x{k}"] = v
         for tc in (0.0, 4.0):
-            out[f"steps_bdf{order}_tc{int(tc)}"] = np.stack(TO.march(m.points, m.tets, mask, g, CASE["Re"], w0, 0.05, 4, order, tc))
+            out[f"steps_bdf{order}_tc{int(tc)}"] = np.stack(NS.march(m.points, m.tets, mask, g, CASE["Re"], w0, 0.05, 4, order, tc))
     np.savez_compressed(path, **out)

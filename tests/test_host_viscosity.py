@@ -1,4 +1,4 @@
-"""The generalised-Newtonian (Carreau) 3-D NS form on the CPU: the test-side oracle (tests/viscosity_oracle.py) against the
+"""The generalised-Newtonian (Carreau) 3-D NS form on the CPU: the test-side oracle (tests/ns3d_oracle.py) against the
 literal Newtonian restatement plus the transpose term of the stress-divergence form, its own autograd Jacobian against
 central differences, the law against its closed form in pure shear, the binding of the two new entry points, and the fixture
 tests/golden/viscosity_cases.npz against its recipe scripts/make_viscosity_golden.py (the GPU tests reproduce its fields)."""
@@ -12,7 +12,7 @@ from conftest import GOLDEN, rel
 
 torch = pytest.importorskip("torch")
 
-import viscosity_oracle as VO  # noqa: E402
+import ns3d_oracle as NS  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(GOLDEN, "viscosity_cases.npz")
@@ -32,8 +32,8 @@ def test_lambda_zero_is_the_literal_form_plus_the_transpose_term(corrected):
     X = golden_script().random_tets(rng, 6)
     W = rng.normal(size=(6, 16))
     for lam, n in ((0.0, 0.4), (2.5, 1.0)):                                    # either switches the law off: nu_e = nu0
-        F, _ = VO.element(X, W, 37.0, lam, n, 0.05, corrected_convection=corrected, want_jac=False)
-        T = VO.transpose_term(X, W, 37.0).numpy()
+        F, _ = NS.element(X, W, 37.0, law=(lam, n, 0.05), corrected_convection=corrected, want_jac=False)
+        T = NS.transpose_term(X, W, 37.0).numpy()
         for e in range(6):
             Fo = FL.ns_residual_literal(X[e], torch.as_tensor(W[e]), 37.0, corrected_convection=corrected).numpy()
             assert rel(F[e], Fo + T[e]) < 1e-13
@@ -46,15 +46,15 @@ def test_autograd_jacobian_against_central_differences(corrected):
     X = golden_script().random_tets(rng, 4)
     W = rng.normal(size=(4, 16))
     kw = dict(corrected_convection=corrected)
-    _, J = VO.element(X, W, 20.0, 3.0, 0.5, 0.01, **kw)
-    _, J1 = VO.element(X, W, 20.0, 3.0, 1.0, 0.01, **kw)
+    _, J = NS.element(X, W, 20.0, law=(3.0, 0.5, 0.01), **kw)
+    _, J1 = NS.element(X, W, 20.0, law=(3.0, 1.0, 0.01), **kw)
     assert rel(J, J1) > 1e-2                                                   # (the law's derivative is in it)
     h = 1e-6
     for k in range(16):
         dW = np.zeros_like(W)
         dW[:, k] = h
-        Fp, _ = VO.element(X, W + dW, 20.0, 3.0, 0.5, 0.01, want_jac=False, **kw)
-        Fm, _ = VO.element(X, W - dW, 20.0, 3.0, 0.5, 0.01, want_jac=False, **kw)
+        Fp, _ = NS.element(X, W + dW, 20.0, law=(3.0, 0.5, 0.01), want_jac=False, **kw)
+        Fm, _ = NS.element(X, W - dW, 20.0, law=(3.0, 0.5, 0.01), want_jac=False, **kw)
         assert rel(J[:, :, k], (Fp - Fm) / (2 * h)) < 1e-7
 
 
@@ -66,12 +66,12 @@ def test_pure_shear_gives_the_closed_form():
         W = np.zeros((8, 4, 4))
         W[:, :, 0] = g * X[:, :, 1]
         W[:, :, 3] = rng.normal(size=(8, 4))                                   # (the pressure does not enter)
-        s = VO.shear_rate2(X, W.reshape(8, 16)).numpy()
+        s = NS.shear_rate2(X, W.reshape(8, 16)).numpy()
         assert rel(s, np.full(8, g * g)) < 1e-12
         want = (1.0 / Re) * (r + (1.0 - r) * (1.0 + lam ** 2 * g * g) ** ((n - 1.0) / 2.0))
-        assert rel(VO.carreau(torch.as_tensor(s), 1.0 / Re, lam, n, r).numpy(), np.full(8, want)) < 1e-12
+        assert rel(NS.carreau(torch.as_tensor(s), 1.0 / Re, lam, n, r).numpy(), np.full(8, want)) < 1e-12
         pts, tets = X.reshape(-1, 3), np.arange(32, dtype=np.int32).reshape(8, 4)
-        nu, gd = VO.element_viscosity(pts, tets, W.reshape(-1), Re, lam, n, r)
+        nu, gd = NS.element_viscosity(pts, tets, W.reshape(-1), Re, lam, n, r)
         assert rel(nu, np.full(8, want)) < 1e-12 and rel(gd, np.full(8, abs(g))) < 1e-12
 
 
