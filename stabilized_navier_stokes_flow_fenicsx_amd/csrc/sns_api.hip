@@ -241,6 +241,7 @@ static int create_common(int dim, sns_handle* out, int32_t n_nodes, int64_t n_te
     h->tm = sns_timings{};
     h->graph_disabled = std::getenv("SNS_NO_GRAPH") != nullptr;
     h->r3_estimates = std::getenv("SNS_R3_SPECTRAL_ESTIMATE") != nullptr;
+    h->plain_step = std::getenv("SNS_PLAIN_STEP") != nullptr;
     h->pattern.reset(new HostPattern(std::move(P)));
     h->host_pts.assign(points, points + (size_t)3 * n_nodes);
     SNS_TRY(plan_hierarchy(h.get()));                     // (the fine level alone until the hierarchy is built)
@@ -296,9 +297,10 @@ int form_allows(const sns_ctx* h, const char* who, policy::FormRequest request, 
 
 // the end of a linear solve whose Dirichlet rows are identity rows: the reference's ILU-preconditioned solve returns them
 // exactly, a Krylov method under AMG only to its tolerance -- a converged solve hands back the exact data `val` under `mask`
+// (zero_guess: the caller zeroed x itself on the handle's stream)
 int solve_and_snap(sns_ctx* h, const double* b, double* x, const uint8_t* mask, const double* val, int* its, int* reason,
-                   double* rnorm) {
-    SNS_TRY(krylov(h, b, x, its, reason, rnorm));
+                   double* rnorm, bool zero_guess = false) {
+    SNS_TRY(krylov(h, b, x, its, reason, rnorm, zero_guess));
     if (*reason <= 0) return SNS_OK;
     const int64_t nd = nred_of(h);
     hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, mask, val, 1e300, x);
@@ -631,7 +633,7 @@ int sns_stokes_solve(sns_handle h, double* U, int* ksp_its, int* reason, double*
     SNS_TRY(ensure_hierarchy(h));
     hipLaunchKernelGGL(k_scale_copy, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, -1.0, h->nw_F, h->nw_F);
     HIP_TRY(hipMemsetAsync(U, 0, nd * sizeof(double), h->stream));
-    return solve_and_snap(h, h->nw_F, U, h->bc_mask, h->bc_val, ksp_its, reason, rnorm);
+    return solve_and_snap(h, h->nw_F, U, h->bc_mask, h->bc_val, ksp_its, reason, rnorm, true);
 }
 
 
@@ -664,16 +666,16 @@ static int newton_run(sns_ctx* h, double* w, int* its_out, int* reason_out, int*
         HIP_TRY(hipMemsetAsync(y, 0, nd * sizeof(double), h->stream));
         int kits = 0, kreason = 0;
         double krn = 0;
-        SNS_TRY(krylov(h, F, y, &kits, &kreason, &krn));
+        // (y was zeroed here, on the solve's stream; J y of the returned iterate comes back with it where the method has it)
+        double* Jy = Fn;                                     // borrow
+        bool have_Jy = false;
+        SNS_TRY(krylov(h, F, y, &kits, &kreason, &krn, true, Jy, &have_Jy));
         ksp_total += kits;
         if (kreason < 0) { reason = SNS_SNES_DIVERGED_LINEAR_SOLVE; break; }
         // bt line search (cubic backtracking, alpha 1e-4), x_new = x - lambda y
         double initslope;
-        {
-            double* Jy = Fn;                                 // borrow
-            SNS_TRY(op_apply(h, y, Jy));
-            SNS_TRY(dot(h, F, Jy, &initslope));
-        }
+        if (!have_Jy) SNS_TRY(op_apply(h, y, Jy));
+        SNS_TRY(dot(h, F, Jy, &initslope));
         if (initslope > 0) initslope = -initslope;
         if (initslope == 0) initslope = -1.0;
         double ynorm;

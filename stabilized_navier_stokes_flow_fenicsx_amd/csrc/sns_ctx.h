@@ -112,6 +112,7 @@ struct sns_ctx {
         cap_stream.reset();
         gj_stream.reset();
         side_stream.reset();
+        setup_stream.reset();
     }
     sns_options opt;
     int device = 0;
@@ -192,6 +193,12 @@ struct sns_ctx {
     int32_t n_bnd = 0;
     Stream side_stream;
     Event ev_x, ev_side;
+    // the set-up on two streams (policy::StepPlan::setup_two_streams): the stream of the coarse chain, created once at the
+    // greatest priority; the events main -> chain (the operator is assembled), chain -> main per level (its operator is
+    // written) and at the end
+    Stream setup_stream;
+    Event ev_setup_fork, ev_setup_join;
+    std::vector<Event> ev_setup_level;
     bool no_overlap = false;
     bool team_overlap = false;                       // SNS_TEAM_OVERLAP: the team transport takes the two-stream path too (tests)
     DevBuf<double> arn_V;                             // Arnoldi basis of the damping estimate, 9 vectors of the largest level >= ... asked for
@@ -201,6 +208,15 @@ struct sns_ctx {
     policy::Handoff handoff;
     bool r3_estimates = false;                       // SNS_R3_SPECTRAL_ESTIMATE (tests of the retry path): round 3's policy -- spectral
                                                      // estimates every 4th setup whatever the operator (first Jacobians on the Stokes estimate)
+    bool plain_step = false;                         // SNS_PLAIN_STEP (tests, profiles): policy::plan_step answers with the schedule of
+                                                     // the solve as it was -- every operator pass, the whole speculative half iteration
+    // the preconditioner application pc_apply_begin has opened and pc_apply_finish / pc_apply_abandon has not closed yet: its
+    // result vector and, where the fine level's cycle was cut behind the restriction, the cycle's vector and ping-pong buffers
+    struct PendingCycle {
+        bool open = false, cut = false;
+        const double* b = nullptr;
+        double *z = nullptr, *x = nullptr, *cur = nullptr, *oth = nullptr;
+    } pc_pending;
     double damping_backoff = 1.0;                    // < 1 after a failed AMG-preconditioned solve: all level dampings scaled
                                                      // (damping_back_off, csrc/sns_damping.hip; back to 1 by damping_reset)
     int64_t ctr_retries = 0;                         // damping retries since sns_reset_timings
@@ -258,6 +274,7 @@ int pc_setup(sns_ctx* h);
 // a set-up, with the spectral estimates that are due; back off: after a retryable failure of a solve; reset: an options call
 enum class DampingReset { AFTER_RETRY /* only where a retry scaled the dampings: the factor too, and pc_ready */, ESTIMATES };
 int damping_decide(sns_ctx* h, int l, int nl, bool new_operator);
+bool damping_estimates_due(const sns_ctx* h, int l, int nl, bool new_operator);   // (decide would launch estimators on level l)
 void damping_back_off(sns_ctx* h);
 void damping_reset(sns_ctx* h, DampingReset what);
 // The workspace vectors h->kv (4*n doubles each, allocated in slot order up to the slot asked for).  VEC_SCRATCH serves the lifting's
@@ -277,11 +294,21 @@ int residual_moments(sns_ctx* h, int form, const double* w, const double* phi, d
 int vcycle(sns_ctx* h, int l, const double* b, double* x);
 int coarse_cycle(sns_ctx* h, int l, const double* b, double* x);
 int pc_apply(sns_ctx* h, const double* r, double* z);
+// ... in two stages (policy::StepPlan::staged_speculation): begin queues the application up to the point where it can be cut --
+// the fine level's cycle through its restriction where `split`, else all of it --, finish the rest; abandon drops an opened
+// application whose result nobody will read, through the clean-up of a failed pc_apply
+int pc_apply_begin(sns_ctx* h, const double* r, double* z, bool split);
+int pc_apply_finish(sns_ctx* h);
+void pc_apply_abandon(sns_ctx* h);
+policy::StepPlan step_plan(const sns_ctx* h, bool zero_guess_vouched, bool estimates_due = true);
 int op_apply(sns_ctx* h, double* x, double* y);
 int op_apply_dot(sns_ctx* h, double* x, double* y, const double* dotw);
 int op_residual(sns_ctx* h, double* x, const double* b, double* r);
 // csrc/sns_krylov.hip: BiCGStab / TFQMR / FGMRES and the solve driver with the damping retry
-int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm);
+// zero_guess: the caller zeroed x itself on the handle's stream; ax / ax_done: a buffer for A x of the returned iterate, and
+// whether the method left it there (else the caller applies the operator itself)
+int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm, bool zero_guess = false, double* ax = nullptr,
+           bool* ax_done = nullptr);
 // csrc/sns_strength.hip: the strength of the fine-level couplings (amg_aggregation = 1, SNS_EXPORT_STRENGTH)
 int compute_strength(sns_ctx* h, float* out, double* scale);
 // csrc/sns_transpose.hip: flip the fine operator between A and A^T in place

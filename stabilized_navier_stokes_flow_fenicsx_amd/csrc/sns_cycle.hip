@@ -316,17 +316,17 @@ static int solve_last_level(sns_ctx* h, int l, const double* b, double* x) {
 }
 
 
-// V-cycle on level l: x <- approx A_l^-1 b  (x overwritten; zero initial guess)
-int vcycle(sns_ctx* h, int l, const double* b, double* x) {
-    if (h->rep_level > 0 && l == h->rep_level - 1) return enter_replicated_tail(h, l, b, x);
-    if (l + 1 == (int)h->levels.size()) return solve_last_level(h, l, b, x);
+// The plain form of the cycle on a level with a level below it, in two halves: the head runs through the restriction of the
+// residual into the coarse right-hand side (with the next level's first sweep where the plan fuses it), the tail is the coarse
+// cycle and everything behind it.  cur / oth: the ping-pong buffers as the head leaves them.  vcycle runs one behind the other;
+// pc_apply_begin / pc_apply_finish cut the fine level's between them
+static int vcycle_head(sns_ctx* h, int l, const double* b, double* x, double** cur_out, double** oth_out) {
     const policy::LevelPlan& Q = h->plan.level[(size_t)l];
-    if (Q.windows) return vcycle_windows(h, l, b, x);
     Level& L = h->levels[l];
     Level& C = h->levels[l + 1];
     const int32_t rows = L.n_owned;
     const double om = L.damping.omega;
-    const int nu = Q.nu, nu_pre = Q.pre, nu_post = Q.post;
+    const int nu_pre = Q.pre;
     double* cur = cycle_start(h, l, x);
     double* oth = (cur == x) ? h->levels[l].pong : x;
     // distributed: on levels with few rows per rank the sweeps see the neighbours' current iterate (one small
@@ -374,8 +374,22 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     } else if (!rr_fused) {
         launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, Q.lp_fmt, rows, cur, L.r, b, 0.0);
     }
+    if (C.n_owned > 0) launch_restrict(h, l, rr_fused, xres, b, coarse_vectors(h, l).cb);
+    *cur_out = cur;
+    *oth_out = oth;
+    return SNS_OK;
+}
+
+static int vcycle_tail(sns_ctx* h, int l, const double* b, double* cur, double* oth) {
+    const policy::LevelPlan& Q = h->plan.level[(size_t)l];
+    Level& L = h->levels[l];
+    Level& C = h->levels[l + 1];
+    const int32_t rows = L.n_owned;
+    const double om = L.damping.omega;
+    const int nu = Q.nu, nu_post = Q.post;
+    const bool sx = Q.sx != 0, px = Q.px != 0;
+    const size_t ghost4 = 4 * (size_t)(L.n - rows);
     const auto [rep_src, cb, cx] = coarse_vectors(h, l);
-    if (C.n_owned > 0) launch_restrict(h, l, rr_fused, xres, b, cb);
     SNS_TRY(coarse_cycle(h, l + 1, cb, rep_src ? nullptr : C.x));
     int s_first = 0;
     // Fused coarse-grid correction + first post-smoothing sweep (k_post_lp): z = (cur + P xc) + om Dinv (r - M xc) with
@@ -422,6 +436,16 @@ int vcycle(sns_ctx* h, int l, const double* b, double* x) {
     return SNS_OK;
 }
 
+// V-cycle on level l: x <- approx A_l^-1 b  (x overwritten; zero initial guess)
+int vcycle(sns_ctx* h, int l, const double* b, double* x) {
+    if (h->rep_level > 0 && l == h->rep_level - 1) return enter_replicated_tail(h, l, b, x);
+    if (l + 1 == (int)h->levels.size()) return solve_last_level(h, l, b, x);
+    if (h->plan.level[(size_t)l].windows) return vcycle_windows(h, l, b, x);
+    double *cur, *oth;
+    SNS_TRY(vcycle_head(h, l, b, x, &cur, &oth));
+    return vcycle_tail(h, l, b, cur, oth);
+}
+
 
 static int pc_apply_inner(sns_ctx* h, const double* r, double* z);
 // (what the Krylov kernel in front handed over is consumed by the cycle this call runs and by nothing else; of the cycle's own
@@ -455,6 +479,74 @@ static int pc_apply_inner(sns_ctx* h, const double* r, double* z) {
     }
     set_error("bad pc_type");
     return SNS_E_ARG;
+}
+
+// whether the fine level of the AMG preconditioner runs the plain form of the cycle with a level below it: the form
+// pc_apply_begin can cut behind the restriction
+static bool fine_plain_cycle(const sns_ctx* h) {
+    return h->opt.pc_type == SNS_PC_AMG && h->pc_ready && h->levels.size() >= 2 && h->plan.level.size() == h->levels.size() &&
+           h->rep_level != 1 && !h->plan.level[0].windows;
+}
+
+// the facts of policy::plan_step gathered from the handle -- asked by the solve driver and by the set-up, nowhere else
+policy::StepPlan step_plan(const sns_ctx* h, bool zero_guess_vouched, bool estimates_due) {
+    policy::StepFacts f;
+    f.nranks = h->comm ? std::max(2, h->comm->nranks) : 1;      // (a communicator attached: partitioned, whatever its size)
+    f.ksp_type = h->opt.ksp_type;
+    f.pc_type = h->opt.pc_type;
+    f.fine_plain_cycle = fine_plain_cycle(h);
+    f.zero_guess_vouched = zero_guess_vouched;
+    f.estimates_due = estimates_due;
+    f.plain_step = h->plain_step;
+    return policy::plan_step(f);
+}
+
+// pc_apply in two stages.  The hand-off transitions keep their order -- enter_level in the head, end_pc_apply when the
+// application ends, in finish or, for an application nobody will read, in abandon (as after a failed pc_apply: whatever the
+// Krylov kernel in front handed over is dropped with it)
+int pc_apply_begin(sns_ctx* h, const double* r, double* z, bool split) {
+    if (h->pc_pending.open) { set_error("pc_apply_begin: the application before was not finished"); return SNS_E_STATE; }
+    if (!split || !fine_plain_cycle(h)) {
+        SNS_TRY(pc_apply(h, r, z));
+        h->pc_pending = {};
+        h->pc_pending.open = true;
+        return SNS_OK;
+    }
+    sns_ctx::PendingCycle pc;
+    pc.open = pc.cut = true;
+    pc.b = r;
+    pc.z = z;
+    pc.x = fine_cycle_vector(h, z);
+    const int rc = vcycle_head(h, 0, r, pc.x, &pc.cur, &pc.oth);
+    if (rc != SNS_OK) {
+        (void)h->handoff.end_pc_apply(false, z);
+        return rc;
+    }
+    h->pc_pending = pc;
+    return SNS_OK;
+}
+
+int pc_apply_finish(sns_ctx* h) {
+    const sns_ctx::PendingCycle pc = h->pc_pending;
+    h->pc_pending = {};
+    if (!pc.open) { set_error("pc_apply_finish without pc_apply_begin"); return SNS_E_STATE; }
+    if (!pc.cut) return SNS_OK;
+    int rc = vcycle_tail(h, 0, pc.b, pc.cur, pc.oth);
+    if (rc == SNS_OK && pc.x != pc.z) {
+        if (hipMemcpyAsync(pc.z, pc.x, nred_of(h) * sizeof(double), hipMemcpyDeviceToDevice, h->stream) != hipSuccess) {
+            set_error("pc_apply_finish: hipMemcpyAsync failed");
+            rc = SNS_E_HIP;
+        }
+    }
+    int level = -1;
+    const bool legal = h->handoff.end_pc_apply(rc == SNS_OK, pc.z, &level);
+    return rc != SNS_OK ? rc : handoff_legal(legal, "pc_apply ends with a carried put nobody took", level);
+}
+
+void pc_apply_abandon(sns_ctx* h) {
+    const sns_ctx::PendingCycle pc = h->pc_pending;
+    h->pc_pending = {};
+    if (pc.open && pc.cut) (void)h->handoff.end_pc_apply(false, pc.z);
 }
 
 

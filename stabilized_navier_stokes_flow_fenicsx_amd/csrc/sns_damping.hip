@@ -188,6 +188,19 @@ static int jacobi_growth(sns_ctx* h, int l, double omega, double* growth) {
 }
 
 
+// the last level where it is solved directly: no sweeps, no estimates
+static bool level_solved(const sns_ctx* h, int l, int nl) {
+    const policy::LevelPlan& P = h->plan.level[(size_t)l];
+    return l + 1 == nl && nl > 1 && (P.kind == SNS_LEVEL_DIRECT || P.kind == SNS_LEVEL_DIRECT_BLOCKED);
+}
+
+// whether damping_decide takes estimates on level l at this set-up (where not, it is host arithmetic alone)
+bool damping_estimates_due(const sns_ctx* h, int l, int nl, bool new_operator) {
+    if (h->opt.pc_type != SNS_PC_AMG || level_solved(h, l, nl)) return false;
+    return policy::estimates_due(h->levels[l].damping.lambda_max > 0.0, h->pc_setups, new_operator);
+}
+
+
 // Decide: the damping of level l (of the nl levels the preconditioner cycles) at a set-up -- the estimators that are due,
 // then the rule of csrc/sns_policy.h.  The spectrum moves little between the Jacobians of one Newton sequence, so the estimates
 // are taken every fourth set-up -- but not from the Stokes operator to a Jacobian (or to another Reynolds number): round 3 took
@@ -205,12 +218,11 @@ int damping_decide(sns_ctx* h, int l, int nl, bool new_operator) {
     policy::LevelDamping& d = L.damping;
     const policy::LevelPlan& P = h->plan.level[(size_t)l];
     const int32_t rows = L.n_owned;
-    const bool direct = l + 1 == nl && nl > 1 && (P.kind == SNS_LEVEL_DIRECT || P.kind == SNS_LEVEL_DIRECT_BLOCKED);   // solved
-    if (o.pc_type != SNS_PC_AMG || direct) {
+    if (o.pc_type != SNS_PC_AMG || level_solved(h, l, nl)) {
         d.omega = policy::capped_damping(o.amg_omega, h->damping_backoff, 0.0, false, 0.0);
         return SNS_OK;
     }
-    const bool due = policy::estimates_due(d.lambda_max > 0.0, h->pc_setups, new_operator);
+    const bool due = damping_estimates_due(h, l, nl, new_operator);
     // (collective when the level's sweeps use exchanged ghost values: every rank takes part, rows or not)
     if (due && (rows > 0 || P.ghost_sweeps())) SNS_TRY(estimate_lambda_max(h, l, &d.lambda_max));
     const double lam = d.lambda_max;

@@ -87,8 +87,14 @@ static int bicg_update(sns_ctx* h, double* zdst, const double* sc, const double*
 // reads (||r||^2, flags) once per iteration, asynchronously: the copy is enqueued, then the x/r update and the
 // FIRST HALF of the next iteration (p, M p, A M p, <rhat, v>, alpha: none of it touches x or r) are enqueued
 // behind it, and only then does the host wait for the copy's event -- the GPU never idles on the stopping test.
+// Where the step plan stages that speculation (policy::plan_step: serial handles), only the update and the head of M p -- the
+// fine level's cycle through its restriction -- are enqueued before the wait, the rest once the host knows that the iteration
+// goes on: the queued head outlasts a host wake-up many times over, and a solve that ends throws the head away, not the half.
 // A converged claim is confirmed by the explicitly computed ||r|| before the loop is left.
-int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out, double* rnorm_out, int stall_window) {
+// The plan also says whether r0 = b - A x0 needs its operator pass (not from a guess the caller vouches to be zero: r0 = b) and
+// whether the pass behind the reported true residual leaves A x in `ax` (*ax_done: it did), the residual being b minus that.
+int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out, double* rnorm_out, int stall_window,
+             const policy::StepPlan& plan, double* ax, bool* ax_done) {
     const sns_options& o = h->opt;
     const int64_t nd = nred_of(h);
     const int g = vec_grid(nd);
@@ -101,7 +107,8 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
     if (!h->ev_it) HIP_TRY(hipEventCreateWithFlags(h->ev_it.put(), hipEventDisableTiming));
     double bnorm, rn;
     SNS_TRY(norm2(h, b, &bnorm));
-    SNS_TRY(op_residual(h, x, b, r));
+    if (plan.skip_zero_guess_residual) HIP_TRY(hipMemcpyAsync(r, b, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    else SNS_TRY(op_residual(h, x, b, r));
     // ||r0||^2 stays on the device as the first rho (rhat = r0); the host needs it for the start-up test
     hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, nd, r, r, h->partial);
     SNS_TRY(reduce_to(h, g, 2, red));
@@ -121,15 +128,25 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
         HIP_TRY(hipMemcpyAsync(rhat, r, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         HIP_TRY(hipMemsetAsync(p, 0, nd * sizeof(double), h->stream));
         HIP_TRY(hipMemsetAsync(v, 0, nd * sizeof(double), h->stream));
-        auto first_half = [&](bool p_done) -> int {       // p, ph = M p, v = A ph, alpha
+        // p, ph = M p, v = A ph, alpha -- in two stages: through the head of M p, and the rest
+        auto first_half_begin = [&](bool p_done) -> int {
             if (!p_done) hipLaunchKernelGGL(k_bicg_p, dim3(g), dim3(256), 0, h->stream, nd, r, sc, v, p);
             h->handoff.promise_operator();
-            SNS_TRY(pc_apply(h, p, ph));
+            return pc_apply_begin(h, p, ph, plan.split_cycle);
+        };
+        auto first_half_finish = [&]() -> int {
+            SNS_TRY(pc_apply_finish(h));
             SNS_TRY(op_apply_dot(h, ph, v, rhat));        // v = A ph with the fused partial sums of <rhat, v>
             SNS_TRY(reduce_bicg<1>(h, h->dot_partials, red, sc));                  // alpha
             return SNS_OK;
         };
-        SNS_TRY(first_half(false));
+        // (an opened application is dropped on every way out of the loop that does not finish it)
+        struct DropPending {
+            sns_ctx* h;
+            ~DropPending() { pc_apply_abandon(h); }
+        } drop_pending{h};
+        SNS_TRY(first_half_begin(false));
+        SNS_TRY(first_half_finish());
         const double rn0 = rn;
         double best_rn = rn;
         int best_it = 0;
@@ -143,11 +160,12 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
             HIP_TRY(hipMemcpyAsync(hpin, sc + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipEventRecord(h->ev_it, h->stream));
             // speculative first half of the next iteration, enqueued BEFORE the host looks at this one's result; its p-update
-            // rides on the x / r update (k_bicg_xrp)
+            // rides on the x / r update (k_bicg_xrp).  Staged: its rest follows the look, below
             const bool spec = its < o.ksp_max_it;
             if (spec) {
                 SNS_TRY(bicg_update<2>(h, ph, sc, ph, sh, t, v, x, r, p, s));
-                SNS_TRY(first_half(true));
+                SNS_TRY(first_half_begin(true));
+                if (!plan.staged_speculation) SNS_TRY(first_half_finish());
             } else {
                 hipLaunchKernelGGL(k_bicg_xr, dim3(g), dim3(256), 0, h->stream, nd, sc, ph, sh, s, t, x, r);
             }
@@ -183,11 +201,20 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
                 break;
             }
             if (flags & 4) { reason = SNS_KSP_DIVERGED_BREAKDOWN; ++its; break; }   // rho == 0 stops the NEXT iteration
+            if (plan.staged_speculation) SNS_TRY(first_half_finish());             // the iteration goes on
         }
+        pc_apply_abandon(h);
         // the stopping test runs on the RECURRENCE residual (as PETSc's bcgs does); what is reported is the true one,
         // ||b - A x|| of the returned iterate, from one more operator pass (0.5 ms of a 145-ms solve at 10 M tets)
         if (reason != SNS_KSP_DIVERGED_NANORINF) {
-            SNS_TRY(op_residual(h, x, b, t));
+            if (plan.export_ax && ax) {
+                // the same pass as A x, b - (A x) formed with the one rounding op_residual's epilogue has
+                SNS_TRY(op_apply(h, x, ax));
+                hipLaunchKernelGGL(k_axpbypcz, dim3(g), dim3(256), 0, h->stream, nd, 1.0, b, -1.0, ax, 0.0, t);
+                *ax_done = true;
+            } else {
+                SNS_TRY(op_residual(h, x, b, t));
+            }
             SNS_TRY(norm2(h, t, &rn));
         }
     }
@@ -408,12 +435,17 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
 }
 
 
-int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm) {
+int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm, bool zero_guess, double* ax, bool* ax_done) {
+    bool ax_unused = false;
+    if (!ax_done) ax_done = &ax_unused;
+    *ax_done = false;
     if (!h->has_matrix) { set_error("krylov_solve before a matrix was assembled"); return SNS_E_STATE; }
     if (!h->pc_ready && h->opt.pc_type != SNS_PC_NONE) SNS_TRY(pc_setup(h));
     int stale = -1;
     SNS_TRY(handoff_legal(h->handoff.begin_solve(&stale), "a solve begins with a carried put nobody took", stale));
+    h->pc_pending = {};
     h->ctr_host_syncs = h->ctr_allreduce = h->ctr_exchange = 0;
+    const policy::StepPlan plan = step_plan(h, zero_guess);
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     // A solve that BREAKS DOWN (or produces NaN/Inf) under the AMG preconditioner is retried ONCE, from the same initial
     // guess, with every level's block-Jacobi damping backed off (damping_back_off, csrc/sns_damping.hip: policy::RETRY_FACTOR, no
@@ -437,8 +469,10 @@ int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double
     h->last_first_reason = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         int rc;
+        *ax_done = false;
+        // (the retry starts from the saved guess: a zero guess is the same zero vector again)
         if (h->opt.ksp_type == SNS_KSP_BICGSTAB)
-            rc = bicgstab(h, b, x, its, reason, rnorm, (can_retry && attempt == 0) ? h->opt.amg_retry_stall_its : 0);
+            rc = bicgstab(h, b, x, its, reason, rnorm, (can_retry && attempt == 0) ? h->opt.amg_retry_stall_its : 0, plan, ax, ax_done);
         else if (h->opt.ksp_type == SNS_KSP_FGMRES) rc = fgmres(h, b, x, its, reason, rnorm);
         else if (h->opt.ksp_type == SNS_KSP_TFQMR) rc = tfqmr(h, b, x, its, reason, rnorm);
         else { set_error("bad ksp_type"); return SNS_E_ARG; }

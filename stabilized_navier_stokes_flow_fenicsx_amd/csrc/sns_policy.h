@@ -8,7 +8,7 @@
 // state allows (check_form_request, tests/form_request_main.cpp) and what it allows of the boundary terms (check_boundary_request,
 // tests/boundary_request_main.cpp), which operator is a new one (OperatorKey, tests/operator_key_main.cpp), the damping of a
 // level's smoother (LevelDamping, tests/damping_policy_main.cpp), what a kernel of a solve hands to a later one (Handoff,
-// tests/handoff_main.cpp).
+// tests/handoff_main.cpp), what a solve and a set-up may leave out of their fixed cost (plan_step, tests/step_plan_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -638,6 +638,44 @@ inline void back_off(LevelDamping& d) {
 }
 // an options call: every estimate is taken and verified again (omega itself is rewritten by the next set-up)
 inline void forget_estimates(LevelDamping& d) { d.lambda_max = d.omega_checked = d.ritz_limit = 0.0; }
+
+// ---- the fixed cost of a linear solve (csrc/sns_krylov.hip, sns_cycle.hip; DESIGN.md, "The fixed cost of a solve") ----------------
+// Work a BiCGStab solve queues that its result does not need, and where it may be left out: on a SERIAL handle only -- a
+// partitioned one keeps its schedule, its hand-offs are pinned as they are.  Facts: the ranks of the handle; the Krylov method
+// and the preconditioner; fine_plain_cycle -- the preconditioner's fine level runs the plain form of the cycle and has a level
+// below it (vcycle, not vcycle_windows, not the replicated tail, not a single level); zero_guess_vouched -- the caller zeroed
+// the guess itself on the solve's stream; estimates_due -- a level takes its spectral estimates at this set-up (asked by the
+// set-up alone); plain_step -- the switch SNS_PLAIN_STEP (not an option), today's schedule whatever else.
+struct StepFacts {
+    int nranks = 1, ksp_type = SNS_KSP_BICGSTAB, pc_type = SNS_PC_AMG;
+    bool fine_plain_cycle = false, zero_guess_vouched = false, estimates_due = true, plain_step = false;
+};
+// skip_zero_guess_residual: r0 is a copy of b, no operator pass.  export_ax: the pass behind the reported true residual is
+// A x into the caller's buffer (the residual is b minus that), where the caller asks for it.  staged_speculation: the
+// speculative half iteration is queued in two stages around the host's look at the residual -- the x / r / p update and the
+// head of the preconditioner before, the rest after and only if the iteration goes on.  split_cycle: that head is the fine
+// level's cycle through the restriction (else the whole application: it is cheap, or cannot be cut).  setup_two_streams: the
+// set-up's latency-bound chain -- the Galerkin products down the levels, the last level's inverse -- runs on a stream of its own
+// beside the levels' bandwidth-bound passes; not while estimates are taken, which solve on the levels as they are refreshed
+struct StepPlan {
+    bool skip_zero_guess_residual = false, export_ax = false, staged_speculation = false, split_cycle = false,
+         setup_two_streams = false;
+    bool operator==(const StepPlan& o) const {
+        return skip_zero_guess_residual == o.skip_zero_guess_residual && export_ax == o.export_ax &&
+               staged_speculation == o.staged_speculation && split_cycle == o.split_cycle && setup_two_streams == o.setup_two_streams;
+    }
+};
+inline StepPlan plan_step(const StepFacts& f) {
+    StepPlan p;
+    if (f.nranks != 1 || f.plain_step || f.ksp_type != SNS_KSP_BICGSTAB) return p;
+    p.skip_zero_guess_residual = f.zero_guess_vouched;
+    p.export_ax = true;
+    // under the AMG preconditioner only what can be cut is staged: a cycle of another form runs whole, as it always did
+    p.split_cycle = f.pc_type == SNS_PC_AMG && f.fine_plain_cycle;
+    p.staged_speculation = f.pc_type != SNS_PC_AMG || p.split_cycle;
+    p.setup_two_streams = f.pc_type == SNS_PC_AMG && !f.estimates_due;
+    return p;
+}
 
 }  // namespace policy
 }  // namespace sns

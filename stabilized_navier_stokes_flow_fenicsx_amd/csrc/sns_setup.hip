@@ -787,12 +787,49 @@ static int conclude_setup(sns_ctx* h, int nl, bool check_sing, int sing) {
 }
 
 
+// the stream and the events of the two-stream set-up, made once per handle: non-blocking, at the greatest priority the device
+// offers -- the chain's few workgroups must not queue behind the bulk passes' (what made SNS_GJ_TWO_STREAMS slower)
+static int setup_chain_ready(sns_ctx* h, int nl) {
+    if (!h->setup_stream) {
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(h->setup_stream.put(), hipStreamNonBlocking, greatest));
+        HIP_TRY(hipEventCreateWithFlags(h->ev_setup_fork.put(), hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(h->ev_setup_join.put(), hipEventDisableTiming));
+    }
+    while ((int)h->ev_setup_level.size() < nl) {
+        h->ev_setup_level.emplace_back();
+        HIP_TRY(hipEventCreateWithFlags(h->ev_setup_level.back().put(), hipEventDisableTiming));
+    }
+    return SNS_OK;
+}
+
+// One stream: per level its smoother inverses, low-precision copies, damping, M = A P, then the Galerkin product into the next
+// (the last level: its direct solve).  Two streams (policy::plan_step; no estimates due, so that the damping is host arithmetic):
+// the chain -- every Galerkin product, the last level's solver -- on h->setup_stream, the rest on the handle's stream, a level
+// >= 1 after the product that wrote its operator; joined before the singularity flag is read.
 int pc_setup(sns_ctx* h) {
     if (!h->has_matrix) { set_error("pc_setup before a matrix was assembled"); return SNS_E_STATE; }
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     const int nl = (h->opt.pc_type == SNS_PC_AMG) ? (int)h->levels.size() : 1;
     bool any_block = false;
     const bool new_operator = policy::new_operator(h->matrix_key, h->est_key, h->r3_estimates);
+    bool estimates_due = false;
+    for (int l = 0; l < nl; ++l) estimates_due = estimates_due || damping_estimates_due(h, l, nl, new_operator);
+    const bool two = step_plan(h, false, estimates_due).setup_two_streams;
+    hipStream_t const user = h->stream;
+    // (the chain's launches go through the same stage functions: they launch on h->stream)
+    struct OnChain {
+        sns_ctx* h;
+        hipStream_t user;
+        OnChain(sns_ctx* hh, bool two) : h(hh), user(hh->stream) { if (two) h->stream = h->setup_stream; }
+        ~OnChain() { h->stream = user; }
+    };
+    if (two) {
+        SNS_TRY(setup_chain_ready(h, nl));
+        HIP_TRY(hipEventRecord(h->ev_setup_fork, user));
+        HIP_TRY(hipStreamWaitEvent(h->setup_stream, h->ev_setup_fork, 0));
+    }
     for (int l = 0; l < nl; ++l) {
         Level& L = h->levels[l];
         if (h->rep_level > 0 && l == h->rep_level - 1) {
@@ -801,16 +838,24 @@ int pc_setup(sns_ctx* h) {
         }
         const policy::LevelPlan& P = h->plan.level[(size_t)l];
         const bool not_last = l + 1 < nl;
+        if (two && l >= 1) HIP_TRY(hipStreamWaitEvent(user, h->ev_setup_level[(size_t)l], 0));
         SNS_TRY(refresh_smoother_inverses(h, P, L));
         if (P.blocks) any_block = true;
         SNS_TRY(refresh_low_precision_copies(h, P, L, not_last));
         SNS_TRY(damping_decide(h, l, nl, new_operator));
         if (not_last) {
             SNS_TRY(refresh_ap32(h, P, L));
+            OnChain chain(h, two);
             refresh_galerkin(h, l);
+            if (two) HIP_TRY(hipEventRecord(h->ev_setup_level[(size_t)l + 1], h->setup_stream));
         } else if (nl > 1) {
+            OnChain chain(h, two);
             SNS_TRY(refresh_coarsest_solver(h, l));
         }
+    }
+    if (two) {
+        HIP_TRY(hipEventRecord(h->ev_setup_join, h->setup_stream));
+        HIP_TRY(hipStreamWaitEvent(user, h->ev_setup_join, 0));
     }
     if (const char* miss = plan_buffer_missing(h)) {
         set_error(std::string("AMG setup: the cycle's plan needs ") + miss + ", which the setup did not allocate");
