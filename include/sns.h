@@ -427,6 +427,39 @@ SNS_API int sns_recover_gradient(sns_handle h, const double* w_dev, double* G_de
  * Writes nothing of the handle.  SNS_E_ARG: null handle / w / eta2.  SNS_E_STATE: a handle with a communicator attached (the
  * indicator would need a halo exchange of G).  Returns after the outputs are written. */
 SNS_API int sns_error_indicator(sns_handle h, const double* w_dev, const double* G_dev, double* eta2_dev, double* gnorm2_dev);
+/* Linear stability of a steady state (the reference has no counterpart: its forms are steady, its Newton converges to unstable
+ * steady states without complaint, and nothing in it asks whether the state it returns exists physically).  The linearised
+ * transient problem at a state w is B x_t + J x = 0: J the steady Jacobian, B = dR/du_t the Petrov-Galerkin mass operator of
+ * the stabilised 3-D NS form at theta = 0 and u_t = 0,
+ *       momentum rows (a, i), columns (b, j):  sum_q w_q N_b (N_a + tau_q u_q.grad N_a) delta_ij    (corrected_convection; the
+ *                                              reference's own test function dot(u, grad v): tau_q u_i d_j N_a N_b beside the mass)
+ *       pressure rows a, columns (b, j):       pspg_sign sum_q w_q tau_q N_b d_j N_a                (B has no pressure columns)
+ *   with the quadrature points, tau_q (C_I, nu or the field's nu_t under the root) and the PSPG sign of the handle's present
+ *   form -- by definition B = J(sigma = 1, d = -u) - J(sigma = 0) of sns_jacobian under sns_set_time_term, which is affine in
+ *   sigma where u_t = 0.  Body force and boundary terms do not enter B.  Rows and columns of constrained dofs are zero.
+ * sns_mass_apply: y = B(w) x, matrix-free -- no second operator is stored (B has J's pattern and would cost what J costs): one
+ *   owner-computes pass over the node -> cell lists, 4 lanes per row, no atomics, no element scratch, a fixed summation order
+ *   (bitwise reproducible).  The pressure and constrained entries of x are ignored; a time term on the handle is ignored too.
+ *   SNS_E_ARG: null handle / pointer, a 2-D handle.  SNS_E_STATE: a communicator attached, a viscosity law set.
+ * sns_stability_arnoldi: plain Arnoldi (no restart) on S = (J + shift B)^-1 B, whose Ritz values theta give the eigenvalues
+ *   lambda = shift - 1/theta of J x = -lambda B x nearest the shift (x ~ exp(lambda t): Re lambda > 0 is an unstable mode).
+ *   With shift > 0 the time term (sigma = shift, theta = 0, d = -shift u(w)) is set, sns_jacobian runs at w, the start vector
+ *   (column 0 of V on entry) is zeroed on the constrained dofs, sent through S once (out of the null space of B) and
+ *   normalised; then m steps, each one mass pass, one Krylov solve from a zero guess with the handle's ksp / pc options and
+ *   damping retry, and classical Gram-Schmidt with one re-orthogonalisation.  A step whose norm after orthogonalisation is
+ *   below breakdown_rel times the norm before ends the process (the Krylov space is invariant).  V_dev: (m + 1) * 4*n_local
+ *   doubles, the orthonormal basis by columns, zero behind the last one reached; H_host: (m + 1) x m, row major,
+ *   S V_m = V_{m+1} H, zero beyond m_done.  *reason: 1 all m steps, 2 breakdown (m_done columns, the subdiagonal entry of the
+ *   last is 0), < 0 the SNS_KSP_* reason of an inner solve that did not converge (m_done = the steps completed; the call still
+ *   returns SNS_OK).  On return the time term is cleared again (not after SNS_E_HIP); the assembled matrix stays J + shift B.
+ *   SNS_E_ARG: null handle / pointer, a 2-D handle, m outside [2, 64], shift negative or not finite, breakdown_rel outside
+ *   (0, 1).  SNS_E_STATE: a communicator attached, a time term set, a viscosity law set.
+ * Not built: adjoint (left) modes and structural sensitivity (they need B^T), restarted or Krylov-Schur iterations, complex or
+ * negative shifts. */
+SNS_API int sns_mass_apply(sns_handle h, const double* w_dev, const double* x_dev, double* y_dev);
+SNS_API int sns_stability_arnoldi(sns_handle h, const double* w_dev, double shift, int m, double breakdown_rel,
+                                  double* V_dev /* (m+1) * 4*n_local; column 0 = start vector on entry */,
+                                  double* H_host /* (m+1) x m, row major */, int* m_done, int* total_ksp_its, int* reason);
 /* MatMult with the assembled operator: y = A x (halo exchange inside).  Acts on whatever
  * the handle holds: y = A^T x after sns_transpose_operator.                   */
 SNS_API int sns_spmv(sns_handle h, const double* x_dev, double* y_dev);

@@ -557,6 +557,47 @@ int sns_error_indicator(sns_handle h, const double* w, const double* G, double* 
     return error_indicator(h, w, G, eta2, gnorm2);
 }
 
+// the two entry points of the stability analysis (`who`: the name in front of the message)
+static int stability_request(const char* who, const sns_ctx* h, policy::StabilityRequest request, const policy::ArnoldiArgs& a = {}) {
+    const policy::FormVerdict v = policy::check_stability_request(request, {h->dim, h->comm != nullptr, h->form.tt_on, h->form.vl_on}, a);
+    if (v.error == SNS_OK) return SNS_OK;
+    set_error(std::string(who) + ": " + v.tail);
+    return v.error;
+}
+
+int sns_mass_apply(sns_handle h, const double* w, const double* x, double* y) {
+    if (!h || !w || !x || !y) { set_error("sns_mass_apply: null handle or pointer"); return SNS_E_ARG; }
+    SNS_TRY(stability_request("sns_mass_apply", h, policy::SREQ_MASS_APPLY));
+    return mass_apply(h, w, x, y);
+}
+
+int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H, int* m_done,
+                          int* total_ksp_its, int* reason) {
+    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
+        set_error("sns_stability_arnoldi: null handle or pointer");
+        return SNS_E_ARG;
+    }
+    SNS_TRY(stability_request("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, {m, shift, breakdown_rel}));
+    // J + shift B = the assembly with u_t = shift (u - u(w)): sigma = shift, theta = 0, d = -shift u(w) (pressure slots unused)
+    if (shift > 0.0) {
+        double* d = nullptr;
+        SNS_TRY(get_vec(h, VEC_SCRATCH, &d));
+        const int64_t ld = ld_of(h);
+        hipLaunchKernelGGL(k_scale_copy, dim3(vec_grid(ld)), dim3(256), 0, h->stream, ld, -shift, w, d);
+        SNS_TRY(set_time_term(h, shift, 0.0, d));
+    }
+    int rc = timed_assemble(h, SNS_FORM_NS, w, nullptr, true);
+    if (rc == SNS_OK) rc = ensure_hierarchy(h);
+    if (rc == SNS_OK) rc = arnoldi_run(h, w, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+    // the steady form again, after a solve that did not converge and after an argument or state error of the steps above
+    // too; a HIP error leaves the device state undefined.  The assembled matrix stays J + shift B
+    if (rc == SNS_E_HIP || shift == 0.0) return rc;
+    const std::string err = g_err;
+    const int rb = set_time_term(h, 0.0, 0.0, nullptr);
+    if (rc != SNS_OK) { set_error(err); return rc; }
+    return rb;
+}
+
 int sns_spmv(sns_handle h, const double* x, double* y) {
     if (!h || !x || !y) return SNS_E_ARG;
     if (!h->has_matrix) { set_error("spmv before a matrix was assembled"); return SNS_E_STATE; }

@@ -319,6 +319,10 @@ int residual_shape_gradient(sns_ctx* h, const double* w, const double* lam, doub
 // fields D), and the Zienkiewicz-Zhu indicator per cell (G null: recovered into a temporary)
 int recover_gradient(sns_ctx* h, const double* w, double* G, double* D);
 int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, double* gnorm2);
+// csrc/sns_stability.hip: the mass pass y = B(w) x and the shift-invert Arnoldi process
+int mass_apply(sns_ctx* h, const double* w, const double* x, double* y);
+int arnoldi_run(sns_ctx* h, const double* w, int m, double breakdown_rel, double* V, double* H, int* m_done, int* total_its,
+                int* reason);
 // csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)
 int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sigma, double theta, const double* src,
                   const uint8_t* cmask, const double* cval, double* rhs);
@@ -481,6 +485,28 @@ inline int fetch(sns_ctx* h, const double* src_dev, int count, double* out) {
     ++h->ctr_host_syncs;
     SNS_TRY(peer_check(h->comm.get()));          // (peer transport: a collective behind this result may have given up waiting)
     std::memcpy(out, h->h_scal, count * sizeof(double));
+    return SNS_OK;
+}
+
+
+// One pass of classical Gram-Schmidt of w against nv columns of V (leading dimension ld), in chunks of 8: the loop FGMRES, the
+// Arnoldi process of the damping estimate (csrc/sns_damping.hip) and the one of the stability analysis (csrc/sns_stability.hip)
+// run twice per step.  coef[c0..c0+8) = the chunk's local sums of V^T w; then finish(), where the caller completes the sums over
+// the ranks and may queue further sums of the w it still sees; then w -= V coef.  nd entries per vector, g = the grid of the sums.
+template <class Finish>
+inline int gram_schmidt_pass(sns_ctx* h, int64_t nd, int g, int nv, const double* V, int64_t ld, double* w, double* coef,
+                             Finish&& finish) {
+    for (int c0 = 0; c0 < nv; c0 += 8) {
+        const int cn = std::min(8, nv - c0);
+        hipLaunchKernelGGL(k_multi_dot8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld, ld, w, h->partial);
+        reduce_local(h, g, 8, coef + c0);
+    }
+    SNS_TRY(finish());
+    for (int c0 = 0; c0 < nv; c0 += 8) {
+        const int cn = std::min(8, nv - c0);
+        hipLaunchKernelGGL(k_multi_axpy8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld, ld, coef + c0, -1.0, w,
+                           (double*)nullptr);
+    }
     return SNS_OK;
 }
 

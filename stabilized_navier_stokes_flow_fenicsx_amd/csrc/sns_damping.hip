@@ -112,12 +112,9 @@ static int arnoldi_ritz(sns_ctx* h, int l, double* theta_max, double* limit) {
         if (lp) launch_pc_spmv<SPMV_B_MINUS_AX>(h, L, P.lp_fmt, rows, xin, y, zero, 0.0);
         else launch_spmv<SPMV_AX>(h, L, rows, xin, y, nullptr, 0.0, nullptr);
         launch_first_sweep(h, P, L, rows, y, lp ? -1.0 : 1.0, w);
-        for (int pass = 0; pass < 2; ++pass) {
-            hipLaunchKernelGGL(k_multi_dot8, dim3(g), dim3(256), 0, h->stream, nd, j + 1, V, nd, w, h->partial);
-            SNS_TRY(reduce(8, sc + 8 * pass));
-            hipLaunchKernelGGL(k_multi_axpy8, dim3(g), dim3(256), 0, h->stream, nd, j + 1, V, nd, sc + 8 * pass, -1.0, w,
-                               (double*)nullptr);
-        }
+        for (int pass = 0; pass < 2; ++pass)               // (M = 8: one chunk)
+            SNS_TRY(gram_schmidt_pass(h, nd, g, j + 1, V, nd, w, sc + 8 * pass,
+                                      [&]() -> int { return glob ? allreduce(h, sc + 8 * pass, 8) : SNS_OK; }));
         hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, nd, w, w, h->partial);
         SNS_TRY(reduce(2, sc + 16));
         double v[18];

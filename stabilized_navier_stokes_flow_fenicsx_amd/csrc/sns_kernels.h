@@ -51,6 +51,59 @@ struct ViscosityLaw {
     double lambda = 0.0, n = 1.0, r = 0.0;
 };
 
+// The metric of one tet for evaluations of the 3-D NS form that hold a whole cell in one lane (the per-tet viscosity in
+// csrc/sns_kernels.hip, the mass pass in csrc/sns_stability.hip; the assembly kernels keep the text they were tuned with, the
+// same expressions in the same order): from the vertices X,
+// g[a] = grad phi_a (rows of K = J^-1, g[0] = -(their sum)), G = K^T K (:232-235) with tr G and G:G, and det J.  The quadrature
+// weight is |det| / 24; cells of either orientation count with |det|.
+struct TetMetric {
+    double g[4][3];
+    double G[3][3];
+    double trG, GG, det;
+};
+__device__ __forceinline__ void tet_metric(const double X[4][3], TetMetric& T) {
+    double J[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        J[i][0] = X[1][i] - X[0][i];
+        J[i][1] = X[2][i] - X[0][i];
+        J[i][2] = X[3][i] - X[0][i];
+    }
+    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+    const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+    const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
+    const double id = 1.0 / det;
+    double K[3][3];
+    K[0][0] = c00 * id; K[1][0] = c01 * id; K[2][0] = c02 * id;
+    K[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
+    K[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
+    K[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
+    K[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
+    K[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
+    K[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        T.g[1][j] = K[0][j]; T.g[2][j] = K[1][j]; T.g[3][j] = K[2][j];
+        T.g[0][j] = -(K[0][j] + K[1][j] + K[2][j]);
+    }
+    T.trG = 0.0;
+    T.GG = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            T.G[i][j] = K[0][i] * K[0][j] + K[1][i] * K[1][j] + K[2][i] * K[2][j];
+            T.GG += T.G[i][j] * T.G[i][j];
+            if (i == j) T.trG += T.G[i][j];
+        }
+    T.det = det;
+}
+// tau of the G-metric SUPG / PSPG term (:237-238): theta the time term's share, C_I = 36 in the reference's form
+__device__ __forceinline__ double supg_tau(double theta, double uGu, double c_inverse, double nu, double GG) {
+    return 1.0 / sqrt(theta + uGu + c_inverse * nu * nu * GG);
+}
+
 template <int FORM, bool corrected, bool TT = false, bool VL = false, bool EV = false>
 __global__ void k_element(int64_t n_tets, const int32_t* tets, const double* pts, const double* w,
                           const uint8_t* bc_mask, const double* bc_val, double nu, int store_K, double* Ke,

@@ -1533,34 +1533,14 @@ __global__ __launch_bounds__(256) void k_element_viscosity(int64_t n_tets, const
         const double2 w0 = *reinterpret_cast<const double2*>(wp);
         U[a][0] = w0.x; U[a][1] = w0.y; U[a][2] = wp[2];
     }
-    double J[3][3];
+    TetMetric T;
+    tet_metric(X, T);
+    const double (&g)[4][3] = T.g;
+    double gu[3][3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        J[i][0] = X[1][i] - X[0][i];
-        J[i][1] = X[2][i] - X[0][i];
-        J[i][2] = X[3][i] - X[0][i];
-    }
-    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-    const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-    const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-    const double id = 1.0 / det;
-    double K[3][3];
-    K[0][0] = c00 * id; K[1][0] = c01 * id; K[2][0] = c02 * id;
-    K[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-    K[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-    K[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-    K[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-    K[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-    K[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-    double g[4][3], gu[3][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        g[1][j] = K[0][j]; g[2][j] = K[1][j]; g[3][j] = K[2][j];
-        g[0][j] = -(K[0][j] + K[1][j] + K[2][j]);
+    for (int j = 0; j < 3; ++j)
 #pragma unroll
         for (int i = 0; i < 3; ++i) gu[i][j] = U[0][i] * g[0][j] + U[1][i] * g[1][j] + U[2][i] * g[2][j] + U[3][i] * g[3][j];
-    }
     const double s = shear_rate2(gu);
     double nu_t = nu;
     if constexpr (LAW) {

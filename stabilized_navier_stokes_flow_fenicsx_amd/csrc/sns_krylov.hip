@@ -361,24 +361,12 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
             // norm follows from ||w - V h2||^2 = w.w - |h2|^2 (V orthonormal).
             for (int pass = 0; pass < 2; ++pass) {
                 double* dh = pass == 0 ? dh1 : dh2;
-                for (int c0 = 0; c0 < nv; c0 += 8) {
-                    const int cn = std::min(8, nv - c0);
-                    hipLaunchKernelGGL(k_multi_dot8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld, ld,
-                                       w, h->partial);
-                    reduce_local(h, g, 8, dh + c0);
-                }
-                if (pass == 1) {
+                SNS_TRY(gram_schmidt_pass(h, nd, g, nv, V, ld, w, dh, [&]() -> int {
+                    if (pass == 0) return allreduce(h, dh, nv);
                     hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, nd, w, w, h->partial);
                     reduce_local(h, g, 2, dh + (m + 8));          // k_dot2 emits (x.y, y.y): both are w.w here
-                    SNS_TRY(allreduce(h, dh, m + 10));
-                } else {
-                    SNS_TRY(allreduce(h, dh, nv));
-                }
-                for (int c0 = 0; c0 < nv; c0 += 8) {
-                    const int cn = std::min(8, nv - c0);
-                    hipLaunchKernelGGL(k_multi_axpy8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld,
-                                       ld, dh + c0, -1.0, w, (double*)nullptr);
-                }
+                    return allreduce(h, dh, m + 10);
+                }));
             }
             // one device->host transfer per iteration: h1[0..nv), h2[0..nv), w.w
             SNS_TRY(fetch(h, h->d_h, 2 * S, hcol.data()));

@@ -537,6 +537,34 @@ inline FormVerdict check_boundary_request(BoundaryRequest request, const Boundar
     return {};
 }
 
+// ---- what a handle allows of the stability analysis (csrc/sns_stability.hip; tests/stability_request_main.cpp) ----------------------
+// The two entry points in a function of their own, in the idiom of the form requests: argument errors first (the dimension, then
+// for the Arnoldi process m in [2, 64], a finite shift >= 0 and breakdown_rel in (0, 1)), then the state -- a communicator, a
+// viscosity law (the mass operator of the law's form is not built), and for the Arnoldi process a time term (it sets its own).
+// The mass pass ignores a time term: B is taken at theta = 0 and u_t = 0 whatever the handle's history.
+constexpr int STABILITY_M_MIN = 2, STABILITY_M_MAX = 64;
+struct StabilityFacts {
+    int dim = 3;
+    bool partitioned = false, tt_on = false, vl_on = false;
+};
+struct ArnoldiArgs {
+    int m = STABILITY_M_MAX;
+    double shift = 0.0, breakdown_rel = 1e-6;
+};
+enum StabilityRequest { SREQ_MASS_APPLY = 0, SREQ_ARNOLDI, SREQ_COUNT };
+inline FormVerdict check_stability_request(StabilityRequest request, const StabilityFacts& f, const ArnoldiArgs& a = {}) {
+    if (f.dim != 3) return {SNS_E_ARG, "3-D handles only"};
+    if (request == SREQ_ARNOLDI) {
+        if (a.m < STABILITY_M_MIN || a.m > STABILITY_M_MAX) return {SNS_E_ARG, "m must lie in [2, 64]"};
+        if (!(a.shift >= 0.0) || !(a.shift <= 1.7976931348623157e308)) return {SNS_E_ARG, "the shift must be finite and >= 0"};
+        if (!(a.breakdown_rel > 0.0) || !(a.breakdown_rel < 1.0)) return {SNS_E_ARG, "breakdown_rel must lie in (0, 1)"};
+    }
+    if (f.partitioned) return {SNS_E_STATE, "not with a communicator attached (partitioned stability analysis is not built)"};
+    if (f.vl_on) return {SNS_E_STATE, "not with a viscosity law set (the mass operator of the law's form is not built)"};
+    if (request == SREQ_ARNOLDI && f.tt_on) return {SNS_E_STATE, "not with a time term set (the analysis sets its own and clears it)"};
+    return {};
+}
+
 // ---- which operator is it? (the spectral estimates of csrc/sns_damping.hip; the cases are in DESIGN.md) -----------------------------
 // What the fine operator's values depend on beside the state: the form's share (FormKey: time term, viscosity law, and a counter
 // that moves whenever the viscosity field is written or cleared, another that moves whenever a boundary coefficient -- the

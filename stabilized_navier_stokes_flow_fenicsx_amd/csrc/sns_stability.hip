@@ -1,0 +1,227 @@
+// Linear stability of a steady state w of the 3-D NS form (sns_mass_apply, sns_stability_arnoldi; the reference has no
+// counterpart: its forms are steady and it never asks whether the state it returns is stable).  The linearised transient problem
+// is B x_t + J x = 0 with J the steady Jacobian at w and B = dR/du_t the Petrov-Galerkin mass operator of the stabilised form,
+//     B[(a,i),(b,j)] = sum_q w_q N_b (N_a + tau_q u_q.g_a) delta_ij      (corrected_convection; the reference's own SUPG test
+//                                                                          function dot(u, grad v) gives tau_q u_i g_a[j] N_b)
+//     B[(a,p),(b,j)] = pspg sum_q w_q tau_q N_b g_a[j]                    (no pressure columns),
+// at theta = 0 and u_t = 0, with the points, tau, C_I, the PSPG sign and nu (constant or per cell) of the handle's form: by
+// definition B = J(sigma = 1, d = -u) - J(sigma = 0) of the assembly, which is affine in sigma where u_t = 0.  The leading
+// eigenvalues lambda of J x = -lambda B x follow from Arnoldi on S = (J + s B)^-1 B: theta Ritz value of S, lambda = s - 1/theta.
+//   k_mass_apply   y = B(w) x, matrix-free, owner-computes, one pass over the node -> cell lists: 4 lanes per row.  Lane l of a
+//                  row takes the cells l, l + 4, ... of the row's list and forms all 4 components of that cell's share -- the
+//                  geometry is computed once per (row, cell), not once per component -- and the 4 partial rows are summed inside
+//                  the group, (l0 + l1) + (l2 + l3), before lane c stores component c.  No atomics, no element scratch, a fixed
+//                  order: bitwise reproducible.  Constrained rows are 0; constrained and pressure entries of x are not read as
+//                  values.  No second BSR operator is stored: B has J's pattern and would cost what J costs.
+//   arnoldi_run    plain Arnoldi without restart on S: per step one mass pass, one Krylov solve from a zero guess with the
+//                  handle's options and damping retry (krylov(), as it is), classical Gram-Schmidt with one re-orthogonalisation
+//                  (gram_schmidt_pass, csrc/sns_ctx.h).  One host read per step.
+// Out of scope: adjoint (left) modes and structural sensitivity, which need B^T; restarted or Krylov-Schur iterations; complex
+// or negative shifts; 2-D and partitioned handles; the Carreau law.
+#include "sns_ctx.h"
+
+namespace sns {
+namespace {
+
+// one cell's share of row (node, local vertex a): acc[0..2] momentum, acc[3] the PSPG row
+template <bool corrected>
+__device__ __forceinline__ void mass_cell(const int32_t* __restrict__ tets, const double* __restrict__ pts,
+                                          const double* __restrict__ w, const double* __restrict__ x,
+                                          const uint8_t* __restrict__ bc_mask, int64_t t, int a, double nu, const FormVariant& fv,
+                                          double acc[4]) {
+    const int4 tv = *reinterpret_cast<const int4*>(tets + 4 * t);
+    const int32_t nd[4] = {tv.x, tv.y, tv.z, tv.w};
+    double X[4][3], U[4][3], Z[4][3];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const int64_t o = 4 * (int64_t)nd[v];
+        const double* pp = pts + 3 * (int64_t)nd[v];
+        X[v][0] = pp[0]; X[v][1] = pp[1]; X[v][2] = pp[2];
+        const double2 u01 = *reinterpret_cast<const double2*>(w + o);
+        U[v][0] = u01.x; U[v][1] = u01.y; U[v][2] = w[o + 2];
+        const double2 x01 = *reinterpret_cast<const double2*>(x + o);
+        const uint32_t mk = *reinterpret_cast<const uint32_t*>(bc_mask + o);      // the node's 4 mask bytes
+        Z[v][0] = (mk & 0xFFu) ? 0.0 : x01.x;
+        Z[v][1] = (mk & 0xFF00u) ? 0.0 : x01.y;
+        Z[v][2] = (mk & 0xFF0000u) ? 0.0 : x[o + 2];
+    }
+    TetMetric T;
+    tet_metric(X, T);
+    const double wd = fabs(T.det) * (1.0 / 24.0);
+    double ga[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ga[j] = a == 0 ? T.g[0][j] : (a == 1 ? T.g[1][j] : (a == 2 ? T.g[2][j] : T.g[3][j]));
+    double usum[3], zsum[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        usum[j] = fv.qa * (((U[0][j] + U[1][j]) + U[2][j]) + U[3][j]);
+        zsum[j] = fv.qa * (((Z[0][j] + Z[1][j]) + Z[2][j]) + Z[3][j]);
+    }
+    const double dq = fv.qb - fv.qa;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        double u[3], z[3], Gu[3], uGu = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            u[j] = usum[j] + dq * U[q][j];
+            z[j] = zsum[j] + dq * Z[q][j];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            Gu[i] = T.G[i][0] * u[0] + T.G[i][1] * u[1] + T.G[i][2] * u[2];
+            uGu += u[i] * Gu[i];
+        }
+        const double tw = wd * supg_tau(0.0, uGu, fv.ci, nu, T.GG);
+        const double pa = wd * (q == a ? fv.qb : fv.qa);
+        const double gz = ga[0] * z[0] + ga[1] * z[1] + ga[2] * z[2];
+        if (corrected) {
+            const double c = pa + tw * (u[0] * ga[0] + u[1] * ga[1] + u[2] * ga[2]);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) acc[i] += c * z[i];
+        } else {
+            const double c = tw * gz;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) acc[i] += pa * z[i] + c * u[i];
+        }
+        acc[3] += (fv.pspg * tw) * gz;
+    }
+}
+
+// lane (i, l): cells l, l + 4, ... of row i; then lane c stores y[4 i + c].  nu_t: the per-cell viscosity or null
+template <bool corrected>
+__global__ __launch_bounds__(256) void k_mass_apply(int32_t n, const int64_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
+                                                    const int32_t* __restrict__ tets, const double* __restrict__ pts,
+                                                    const double* __restrict__ w, const double* __restrict__ x,
+                                                    const uint8_t* __restrict__ bc_mask, double nu, const double* __restrict__ nu_t,
+                                                    FormVariant fv, double* __restrict__ y) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = gid >> 2;
+    const int l = (int)(gid & 3);
+    const bool live = i < n;                               // (all 4 lanes of a group agree; nobody leaves before the moves)
+    const int64_t k1 = live ? nt_ptr[i + 1] : 0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t k = (live ? nt_ptr[i] : 0) + l; k < k1; k += 4) {
+        const int32_t id = nt_idx[k];                      // tet * 4 + local vertex
+        const int64_t t = (int64_t)(id >> 2);
+        mass_cell<corrected>(tets, pts, w, x, bc_mask, t, id & 3, nu_t ? nu_t[t] : nu, fv, acc);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        acc[c] += __shfl_xor(acc[c], 1, 4);
+        acc[c] += __shfl_xor(acc[c], 2, 4);
+    }
+    if (!live) return;
+    const double v = l == 0 ? acc[0] : (l == 1 ? acc[1] : (l == 2 ? acc[2] : acc[3]));
+    y[4 * i + l] = bc_mask[4 * i + l] ? 0.0 : v;
+}
+
+__global__ __launch_bounds__(256) void k_zero_constrained(int64_t ndof, const uint8_t* __restrict__ bc_mask, double* __restrict__ x) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ndof; i += (int64_t)gridDim.x * blockDim.x)
+        if (bc_mask[i]) x[i] = 0.0;
+}
+
+void launch_mass(sns_ctx* h, const double* w, const double* x, double* y) {
+    if (h->n == 0) return;
+    const FormState& S = h->form;
+    const dim3 grid((unsigned)((4 * (int64_t)h->n + 255) / 256));
+    const double nu = 1.0 / h->opt.reynolds;
+    const double* nu_t = S.ev_on ? S.ev_nu.get() : nullptr;
+    dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
+        hipLaunchKernelGGL((k_mass_apply<C() != 0>), grid, dim3(256), 0, h->stream, h->n, h->nt_ptr, h->nt_idx, h->tets, h->pts, w, x,
+                           h->bc_mask, nu, nu_t, S.fv, y);
+    });
+}
+
+}  // namespace
+
+// handle, pointers and the form state were checked by the entry point
+int mass_apply(sns_ctx* h, const double* w, const double* x, double* y) {
+    launch_mass(h, w, x, y);
+    HIP_TRY(hipGetLastError());
+    return sync_stream(h);
+}
+
+// The Arnoldi process on S = (J + shift B)^-1 B; the operator J + shift B is assembled and the hierarchy exists (the entry
+// point).  V: (m + 1) columns of 4*n doubles, column 0 the start vector; H: (m + 1) x m, row major, zero beyond m_done.
+// *reason: 1 all m steps done, 2 breakdown (the Krylov space is invariant: m_done columns, H[m_done][m_done - 1] = 0 and the
+// column of V behind them zero), < 0 the KSP reason of an inner solve that did not converge (m_done = the steps completed).
+int arnoldi_run(sns_ctx* h, const double* w, int m, double breakdown_rel, double* V, double* H, int* m_done, int* total_its,
+                int* reason) {
+    const int64_t ld = ld_of(h);
+    const int g = std::max(1, vec_grid(ld));
+    constexpr int CS = policy::STABILITY_M_MAX + 8;        // stride of one coefficient block (chunks of 8)
+    DevBuf<double> b, co;                                  // b = B v; co: pass-1 and pass-2 coefficients, then (w.w, .) before and after
+    SNS_TRY(b.alloc((size_t)ld));
+    SNS_TRY(co.alloc((size_t)2 * CS + 4));
+    std::fill(H, H + (size_t)(m + 1) * m, 0.0);
+    *m_done = 0;
+    *total_its = 0;
+    *reason = 1;
+    // w = S v, from a zero guess; false: the inner solve did not converge (*reason holds why)
+    auto apply_S = [&](const double* v, double* out, bool* ok) -> int {
+        launch_mass(h, w, v, b);
+        HIP_TRY(hipMemsetAsync(out, 0, (size_t)ld * sizeof(double), h->stream));
+        int its = 0, kr = 0;
+        double rn = 0.0;
+        SNS_TRY(krylov(h, b, out, &its, &kr, &rn, true));
+        *total_its += its;
+        *ok = kr > 0;
+        if (!*ok) *reason = kr;
+        else hipLaunchKernelGGL(k_zero_constrained, dim3(g), dim3(256), 0, h->stream, ld, h->bc_mask, out);    // (identity rows: 0 up to the tolerance)
+        return SNS_OK;
+    };
+    auto norm_sq = [&](const double* v, double* dst) {
+        hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, ld, v, v, h->partial);
+        reduce_local(h, g, 2, dst);
+    };
+    // the start vector: constrained dofs zeroed, one application of S (it leaves the null space of B), unit norm
+    bool ok = true;
+    double* v1 = V + (size_t)ld;
+    hipLaunchKernelGGL(k_zero_constrained, dim3(g), dim3(256), 0, h->stream, ld, h->bc_mask, V);
+    SNS_TRY(apply_S(V, v1, &ok));
+    if (!ok) {
+        HIP_TRY(hipMemsetAsync(v1, 0, (size_t)m * ld * sizeof(double), h->stream));
+        return sync_stream(h);
+    }
+    double hv[2 * CS + 4];
+    norm_sq(v1, co + 2 * CS);
+    SNS_TRY(fetch(h, co + 2 * CS, 2, hv));
+    const double n0 = std::sqrt(hv[0]);
+    if (!(n0 > 0.0) || !std::isfinite(n0)) {               // S v = 0: the start vector lies in the null space of B
+        *reason = 2;
+        HIP_TRY(hipMemsetAsync(V, 0, (size_t)(m + 1) * ld * sizeof(double), h->stream));
+        return sync_stream(h);
+    }
+    hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, ld, 1.0 / n0, v1, V);
+    for (int j = 0; j < m; ++j) {
+        double* wj = V + (size_t)(j + 1) * ld;
+        SNS_TRY(apply_S(V + (size_t)j * ld, wj, &ok));
+        if (!ok) {
+            HIP_TRY(hipMemsetAsync(wj, 0, (size_t)ld * sizeof(double), h->stream));
+            break;
+        }
+        const int nv = j + 1;
+        norm_sq(wj, co + 2 * CS);
+        for (int pass = 0; pass < 2; ++pass)
+            SNS_TRY(gram_schmidt_pass(h, ld, g, nv, V, ld, wj, co + pass * CS, []() -> int { return SNS_OK; }));
+        norm_sq(wj, co + 2 * CS + 2);
+        SNS_TRY(fetch(h, co, 2 * CS + 4, hv));
+        for (int k = 0; k < nv; ++k) H[(size_t)k * m + j] = hv[k] + hv[CS + k];
+        *m_done = nv;
+        const double before = std::sqrt(hv[2 * CS]), after = std::sqrt(hv[2 * CS + 2]);
+        if (!(after > breakdown_rel * before)) {           // (a NaN ends the process here too)
+            *reason = 2;
+            HIP_TRY(hipMemsetAsync(wj, 0, (size_t)ld * sizeof(double), h->stream));
+            break;
+        }
+        H[(size_t)(j + 1) * m + j] = after;
+        hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, ld, 1.0 / after, wj, wj);
+    }
+    // the columns of V the process never reached
+    const int used = *m_done + 1;
+    if (used < m + 1) HIP_TRY(hipMemsetAsync(V + (size_t)used * ld, 0, (size_t)(m + 1 - used) * ld * sizeof(double), h->stream));
+    HIP_TRY(hipGetLastError());
+    return sync_stream(h);
+}
+
+}  // namespace sns

@@ -332,6 +332,7 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
     out = dict(msh=msh_f, w=wg, u=wg.reshape(-1, 4)[:, :3].copy(), p=wg.reshape(-1, 4)[:, 3].copy(), Re=Re, img_fname=img_fname,
                channel_mesh_size=channel_mesh_size, flowrate_ratio=flowrate_ratio, newton=Pf.last_newton)
     derived = _derived_fields(Pf, w)
+    _stability(Pf, w)
     if derived is not None:
         out["derived"] = derived
     conc = coupled[1] if coupled is not None else _scalar_transport(Pf, w, msh_f)
@@ -402,6 +403,7 @@ def duct_stokes_main(argv=None):
         write_xdmf("StokesDuctPressure", msh, "f", p)
         write_xdmf("StokesDuctVelcoity", msh, "f", u)             # (sic) file name of the reference :255
     _write_derived_fields(_derived_fields(P, U), msh, lambda label: f"StokesDuct{label}")
+    _stability(P, U)
     conc = coupled[1] if coupled is not None else _scalar_transport(P, U, msh)
     if conc is not None and _rank() == 0:
         write_xdmf("StokesDuctConcentration", msh, "Concentration", conc)
@@ -548,6 +550,31 @@ def _write_derived_fields(fields, msh, path_of):
         return
     for label, name in zip(("Vorticity", "QCriterion", "ShearRate"), DERIVED_FIELD_NAMES):
         write_xdmf(path_of(label), msh, name, fields[name])
+
+
+def _stability(P, w):
+    """SNS_STABILITY=<n_modes>[,<shift>] (opt-in; single-GPU runs): after the solve, the leading eigenvalues of the transient
+    operator linearised at the state ``w`` (``solver.linear_stability``, the 3-D NS form at the problem's Reynolds number), one
+    printed line per converged mode: lambda, the frequency Im lambda / 2 pi and the residual estimate.  Re lambda > 0 is a
+    growing mode: the steady state is unstable.  Nothing without the switch: files and stdout stay as they are."""
+    spec = os.environ.get("SNS_STABILITY", "")
+    if not spec:
+        return None
+    if getattr(P, "part", None) is not None:
+        if _rank() == 0:
+            print("SNS_STABILITY: the stability analysis runs on single-GPU problems only; skipped", flush=True)
+        return None
+    parts = spec.split(",")
+    n_modes, shift = int(parts[0]), (float(parts[1]) if len(parts) > 1 else 0.0)
+    from .solver import SnsError, linear_stability, print_stability
+    try:
+        res = linear_stability(P, w, n_modes=n_modes, shift=shift)
+    except SnsError as e:                                 # (a viscosity law, a 2-D problem: the library says which)
+        if _rank() == 0:
+            print(f"SNS_STABILITY: skipped ({e})", flush=True)
+        return None
+    print_stability(res, _rank())
+    return res
 
 
 def _sensitivity():
@@ -726,6 +753,7 @@ def dfg_3d_main(argv=None):
         write_xdmf("DFGValidationPressureNavierStokes", msh, "Pressure", wg.reshape(-1, 4)[:, 3].copy())
         write_xdmf("DFGValidationVelocityNavierStokes", msh, "Velocity", wg.reshape(-1, 4)[:, :3].copy())
     _write_derived_fields(_derived_fields(P, w), msh, lambda label: f"DFGValidation{label}NavierStokes")
+    _stability(P, w)
     if _sensitivity():
         sc = Fn.drag_lift_coefficients(np.ones(3))[0]
         ob = msh.meta["tags"]["obstacle"]

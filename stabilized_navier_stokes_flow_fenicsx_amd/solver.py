@@ -50,6 +50,24 @@ class NewtonResult:
     ptc_steps: int = 0          # pseudo-steps taken before the closing solve (solver.pseudo_transient_solve)
 
 
+@dataclass
+class ArnoldiResult:
+    m_done: int                 # columns of H (and Ritz values) the process produced
+    reason: int                 # 1 all m steps, 2 breakdown (invariant Krylov space), < 0 the KSP reason of a failed inner solve
+    ksp_its: int                # Krylov iterations over all inner solves
+
+
+@dataclass
+class StabilityResult:
+    eigenvalues: np.ndarray     # (n,) complex, descending real part: the least stable first
+    modes: torch.Tensor         # (n, ndof) complex128 on the device, unit 2-norm, largest-modulus entry real and positive
+    estimates: np.ndarray       # (n,) residual estimates |h_{m+1,m} e_m^T y| / |theta|
+    converged: np.ndarray       # (n,) bool: estimate <= tol
+    m_done: int
+    ksp_its: int
+    reason: int
+
+
 class FlowProblem:
     """Mesh + Dirichlet data + operator hierarchy on one GPU (one per rank).  ``mesh`` is a ``TetMesh`` (3-D
     G-metric forms) or a ``mesh2d.TriMesh`` (2-D UGN forms of the lid-driven / DFG-2D scripts; "stokes" and "ns"
@@ -331,6 +349,35 @@ class FlowProblem:
         gn2 = torch.empty(E, dtype=torch.float64, device=self.device)
         check(self.lib.sns_error_indicator(self.h, _ptr(w), _ptr(G), _ptr(eta2), _ptr(gn2)))
         return eta2, gn2
+
+    # -- linear stability (no counterpart in the reference) -----------------------------------------------------------
+    def mass_apply(self, w, x, out=None) -> torch.Tensor:
+        """``B(w) x`` (sns_mass_apply): B = dR/du_t of the present 3-D NS form at the state ``w`` -- Galerkin mass plus the SUPG
+        and PSPG parts of u_t, with the form's tau, form variant and viscosity field -- applied matrix-free in one pass, bitwise
+        reproducible.  Rows of constrained dofs are 0; pressure and constrained entries of ``x`` are ignored.  Single-GPU 3-D
+        problems."""
+        w, x = self._vec(w), self._vec(x)
+        out = self.zeros() if out is None else self._vec(out)
+        check(self.lib.sns_mass_apply(self.h, _ptr(w), _ptr(x), _ptr(out)))
+        return out
+
+    def stability_arnoldi(self, w, shift: float = 0.0, m: int = 64, start=None, breakdown_rel: float = 1e-6):
+        """``m`` steps of shift-invert Arnoldi on (J + shift B)^-1 B at the steady state ``w`` (sns_stability_arnoldi), with
+        the problem's ksp / pc options for the inner solves.  Returns ``(V, H, ArnoldiResult)``: V a device tensor
+        (m + 1, ndof) whose rows are the orthonormal basis, H numpy (m + 1, m).  ``start``: a dof vector, by default
+        cos(1 + 0.37 i) over the dofs.  Afterwards the handle's matrix is J + shift B and its form is steady again."""
+        w = self._vec(w)
+        m = int(m)
+        V = torch.zeros(max(m, 0) + 1, self.ndof, dtype=torch.float64, device=self.device)   # (m outside [2, 64]: the library refuses)
+        if start is None:
+            V[0] = torch.cos(1.0 + 0.37 * torch.arange(self.ndof, dtype=torch.float64, device=self.device))
+        else:
+            V[0] = self._vec(start)
+        H = np.zeros((max(m, 0) + 1, max(m, 0)))
+        done, its, reason = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.sns_stability_arnoldi(self.h, _ptr(w), float(shift), m, float(breakdown_rel), _ptr(V), H.ctypes.data,
+                                             C.byref(done), C.byref(its), C.byref(reason)))
+        return V, H, ArnoldiResult(done.value, reason.value, its.value)
 
     def spmv(self, x, out=None) -> torch.Tensor:
         x = self._vec(x)
@@ -1158,6 +1205,74 @@ def zz_estimate(problem: FlowProblem, w):
     eta = s ** 0.5
     den = (float(gn2.sum()) + s) ** 0.5
     return eta, (eta / den if den > 0.0 else 0.0), eta2
+
+
+def ritz_pairs(H, m_done: int, shift: float = 0.0):
+    """Eigenvalue estimates from the Hessenberg matrix of ``FlowProblem.stability_arnoldi`` (pure numpy): with (theta, y) the
+    eigenpairs of H[:m_done, :m_done], |y| = 1, returns ``(lam, Y, est)``: lam = shift - 1/theta, the eigenvalues of
+    J x = -lam B x (x ~ exp(lam t)), sorted by descending real part so that the least stable comes first (of a conjugate pair
+    the one with positive imaginary part first); Y[:, k] the Ritz coefficient vector of lam[k]; est[k] =
+    |h_{m+1,m} e_m^T y_k| / |theta_k|, the residual of the pair in the Arnoldi relation relative to its Ritz value.  A Ritz value
+    theta = 0 (an infinite eigenvalue) sorts last with an infinite estimate."""
+    H = np.asarray(H, dtype=np.float64)
+    k = int(m_done)
+    if k < 1:
+        return np.zeros(0, complex), np.zeros((0, 0), complex), np.zeros(0)
+    theta, Y = np.linalg.eig(H[:k, :k])
+    Y = Y / np.linalg.norm(Y, axis=0)
+    sub = abs(H[k, k - 1]) if H.shape[0] > k else 0.0
+    zero = theta == 0.0
+    safe = np.where(zero, 1.0, theta)
+    lam = np.where(zero, -np.inf, shift - 1.0 / safe)
+    est = np.where(zero, np.inf, sub * np.abs(Y[k - 1]) / np.abs(safe))
+    order = np.lexsort((-lam.imag, -lam.real))
+    return lam[order], Y[:, order], est[order]
+
+
+def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0.0, m: int = 64, tol: float = 1e-7,
+                     ksp_rtol: float = 1e-10) -> StabilityResult:
+    """Leading eigenvalues and modes of the linearised transient operator B x_t + J x = 0 at the steady state ``w``: is the
+    state stable (every Re lam < 0), and if not, at which frequency Im lam / 2 pi does it go?  ``m`` steps of shift-invert
+    Arnoldi (``FlowProblem.stability_arnoldi``) with the inner tolerance ``ksp_rtol`` (the problem's options are restored
+    afterwards), ``ritz_pairs`` on the host, ``n_modes`` modes formed as V y on the device: the least stable of the pairs whose residual
+    estimate is at most ``tol`` (``converged``), least stable first, and behind them, if fewer converged, the others by
+    ascending estimate.  Eigenvalues nearest the shift converge first: shift = 0 finds
+    those of smallest modulus, which are the least stable ones of a flow near its first instability."""
+    old = problem.options.ksp_rtol
+    problem.set_options(ksp_rtol=float(ksp_rtol))
+    try:
+        V, H, res = problem.stability_arnoldi(w, shift=shift, m=m)
+    finally:
+        problem.set_options(ksp_rtol=old)
+    lam, Y, est = ritz_pairs(H, res.m_done, shift)
+    # the converged pairs in ritz_pairs' order, then the others by their estimate: an unconverged Ritz value near theta = 0 (the
+    # infinite eigenvalues of the pencil; B has no pressure columns) has an arbitrary, often huge positive, real part
+    ok = est <= tol
+    pick = np.concatenate([np.nonzero(ok)[0], np.nonzero(~ok)[0][np.argsort(est[~ok], kind="stable")]])[:max(0, int(n_modes))]
+    lam, Y, est = lam[pick], Y[:, pick], est[pick]
+    n = len(pick)
+    k = res.m_done
+    if n:
+        Vk = V[:k].T
+        Yr = torch.from_numpy(np.ascontiguousarray(Y.real)).to(V.device)
+        Yi = torch.from_numpy(np.ascontiguousarray(Y.imag)).to(V.device)
+        modes = torch.complex(Vk @ Yr, Vk @ Yi).T.contiguous()
+        modes = modes / torch.linalg.vector_norm(modes, dim=1, keepdim=True)
+        big = modes.gather(1, modes.abs().argmax(dim=1, keepdim=True))
+        modes = modes * (big.conj() / big.abs())
+    else:
+        modes = torch.zeros(0, problem.ndof, dtype=torch.complex128, device=V.device)
+    return StabilityResult(lam, modes, est, est <= tol, res.m_done, res.ksp_its, res.reason)
+
+
+def print_stability(result: StabilityResult, rank: int = 0):
+    """One line per converged mode: lam, the frequency Im lam / 2 pi, the residual estimate."""
+    if rank != 0:
+        return
+    for lam, est, ok in zip(result.eigenvalues, result.estimates, result.converged):
+        if ok:
+            print(f"Stability mode: lambda = {lam.real:+.6e} {lam.imag:+.6e}i  frequency = {lam.imag / (2.0 * np.pi):.6e}  estimate = {est:.2e}",
+                  flush=True)
 
 
 def solve_navier_stokes(problem: FlowProblem, w: torch.Tensor, rank: int = 0, continuation=False, ptc_dt0: float = 1.0):
