@@ -454,12 +454,30 @@ SNS_API int sns_error_indicator(sns_handle h, const double* w_dev, const double*
  *   returns SNS_OK).  On return the time term is cleared again (not after SNS_E_HIP); the assembled matrix stays J + shift B.
  *   SNS_E_ARG: null handle / pointer, a 2-D handle, m outside [2, 64], shift negative or not finite, breakdown_rel outside
  *   (0, 1).  SNS_E_STATE: a communicator attached, a time term set, a viscosity law set.
- * Not built: adjoint (left) modes and structural sensitivity (they need B^T), restarted or Krylov-Schur iterations, complex or
- * negative shifts. */
+ * The left (adjoint) problem J^T z = -lambda B^T z, i.e. z^T J = -lambda z^T B, has the same eigenvalues; its modes z say where
+ *   an eigenvalue is sensitive: with a right mode x of the same lambda, d lambda = -z^T (dJ + lambda dB) x / (z^T B x) to first
+ *   order (the matrices are real: the pairing is the unconjugated z^T B x).  B^T is by definition the transpose of the B above.
+ * sns_mass_apply_transpose: y = B(w)^T z, matrix-free, the same owner-computes pass (4 lanes per row, no atomics, no scratch,
+ *   bitwise reproducible); B^T is as little stored as B (B is strongly non-symmetric, so B x cannot stand in).  On a cell grad z
+ *   is constant, so momentum row (a, i) is  sum_q w_q N_a z_i(q) + (sum_q w_q tau_q N_a u_q).grad z_i + pspg_sign (sum_q w_q
+ *   tau_q N_a) d_i z_p  (corrected_convection; the reference's test function has sum_j (sum_q w_q tau_q N_a u_q)_j d_i z_j in
+ *   the middle).  Unlike B x it READS the pressure entries of z (the PSPG rows of B); constrained entries of z -- a constrained
+ *   pressure dof included -- are read as 0.  Pressure rows and constrained rows of y are 0.  Errors as sns_mass_apply.
+ * sns_stability_arnoldi_left: the same process on S_L = (J + shift B)^-T B^T with the same arguments, results and reasons: the
+ *   operator is assembled as above, transposed in place (sns_transpose_operator), the hierarchy of the transposed operator is
+ *   set up, each step is one transposed mass pass and one Krylov solve.  On return the operator is transposed back and the
+ *   hierarchy marked stale (as sns_adjoint_solve does; after a solve that did not converge too, not after SNS_E_HIP), the time
+ *   term is cleared: the handle holds J + shift B, untransposed, and its form is steady.  Errors as sns_stability_arnoldi.
+ * Not built: restarted or Krylov-Schur iterations, complex or negative shifts, the sensitivity of an eigenvalue to a steady
+ * forcing (it needs the Hessian of the residual). */
 SNS_API int sns_mass_apply(sns_handle h, const double* w_dev, const double* x_dev, double* y_dev);
 SNS_API int sns_stability_arnoldi(sns_handle h, const double* w_dev, double shift, int m, double breakdown_rel,
                                   double* V_dev /* (m+1) * 4*n_local; column 0 = start vector on entry */,
                                   double* H_host /* (m+1) x m, row major */, int* m_done, int* total_ksp_its, int* reason);
+SNS_API int sns_mass_apply_transpose(sns_handle h, const double* w_dev, const double* z_dev, double* y_dev);
+SNS_API int sns_stability_arnoldi_left(sns_handle h, const double* w_dev, double shift, int m, double breakdown_rel,
+                                       double* V_dev /* (m+1) * 4*n_local; column 0 = start vector on entry */,
+                                       double* H_host /* (m+1) x m, row major */, int* m_done, int* total_ksp_its, int* reason);
 /* MatMult with the assembled operator: y = A x (halo exchange inside).  Acts on whatever
  * the handle holds: y = A^T x after sns_transpose_operator.                   */
 SNS_API int sns_spmv(sns_handle h, const double* x_dev, double* y_dev);

@@ -557,7 +557,7 @@ int sns_error_indicator(sns_handle h, const double* w, const double* G, double* 
     return error_indicator(h, w, G, eta2, gnorm2);
 }
 
-// the two entry points of the stability analysis (`who`: the name in front of the message)
+// the entry points of the stability analysis (`who`: the name in front of the message)
 static int stability_request(const char* who, const sns_ctx* h, policy::StabilityRequest request, const policy::ArnoldiArgs& a = {}) {
     const policy::FormVerdict v = policy::check_stability_request(request, {h->dim, h->comm != nullptr, h->form.tt_on, h->form.vl_on}, a);
     if (v.error == SNS_OK) return SNS_OK;
@@ -571,13 +571,16 @@ int sns_mass_apply(sns_handle h, const double* w, const double* x, double* y) {
     return mass_apply(h, w, x, y);
 }
 
-int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H, int* m_done,
-                          int* total_ksp_its, int* reason) {
-    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
-        set_error("sns_stability_arnoldi: null handle or pointer");
-        return SNS_E_ARG;
-    }
-    SNS_TRY(stability_request("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, {m, shift, breakdown_rel}));
+int sns_mass_apply_transpose(sns_handle h, const double* w, const double* z, double* y) {
+    if (!h || !w || !z || !y) { set_error("sns_mass_apply_transpose: null handle or pointer"); return SNS_E_ARG; }
+    SNS_TRY(stability_request("sns_mass_apply_transpose", h, policy::SREQ_MASS_APPLY_TRANSPOSE));
+    return mass_apply_transpose(h, w, z, y);
+}
+
+// both Arnoldi entry points behind their checks.  left: the operator is flipped between the assembly and the set-up and flipped
+// back afterwards with the hierarchy marked stale, as sns_adjoint_solve does
+static int stability_arnoldi(sns_ctx* h, bool left, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,
+                             int* m_done, int* total_ksp_its, int* reason) {
     // J + shift B = the assembly with u_t = shift (u - u(w)): sigma = shift, theta = 0, d = -shift u(w) (pressure slots unused)
     if (shift > 0.0) {
         double* d = nullptr;
@@ -587,15 +590,48 @@ int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, do
         SNS_TRY(set_time_term(h, shift, 0.0, d));
     }
     int rc = timed_assemble(h, SNS_FORM_NS, w, nullptr, true);
+    bool flipped = false;
+    if (left && rc == SNS_OK) {
+        rc = transpose_operator(h);                      // (SNS_E_STATE / SNS_E_MESH: nothing was modified)
+        flipped = rc == SNS_OK;
+    }
     if (rc == SNS_OK) rc = ensure_hierarchy(h);
-    if (rc == SNS_OK) rc = arnoldi_run(h, w, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
-    // the steady form again, after a solve that did not converge and after an argument or state error of the steps above
-    // too; a HIP error leaves the device state undefined.  The assembled matrix stays J + shift B
-    if (rc == SNS_E_HIP || shift == 0.0) return rc;
+    if (rc == SNS_OK) rc = arnoldi_run(h, w, left, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+    // the untransposed operator and the steady form again, after a solve that did not converge and after an argument or state
+    // error of the steps above too; a HIP error leaves the device state undefined.  The assembled matrix stays J + shift B
+    if (rc == SNS_E_HIP || (!flipped && shift == 0.0)) return rc;
     const std::string err = g_err;
-    const int rb = set_time_term(h, 0.0, 0.0, nullptr);
+    int rb = SNS_OK;
+    if (flipped) {
+        rb = transpose_operator(h);
+        pc_stale(h);
+    }
+    if (shift != 0.0) {
+        const int rt = set_time_term(h, 0.0, 0.0, nullptr);
+        if (rb == SNS_OK) rb = rt;
+    }
     if (rc != SNS_OK) { set_error(err); return rc; }
     return rb;
+}
+
+int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H, int* m_done,
+                          int* total_ksp_its, int* reason) {
+    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
+        set_error("sns_stability_arnoldi: null handle or pointer");
+        return SNS_E_ARG;
+    }
+    SNS_TRY(stability_request("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, {m, shift, breakdown_rel}));
+    return stability_arnoldi(h, false, w, shift, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+}
+
+int sns_stability_arnoldi_left(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,
+                               int* m_done, int* total_ksp_its, int* reason) {
+    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
+        set_error("sns_stability_arnoldi_left: null handle or pointer");
+        return SNS_E_ARG;
+    }
+    SNS_TRY(stability_request("sns_stability_arnoldi_left", h, policy::SREQ_ARNOLDI_LEFT, {m, shift, breakdown_rel}));
+    return stability_arnoldi(h, true, w, shift, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
 }
 
 int sns_spmv(sns_handle h, const double* x, double* y) {

@@ -319,10 +319,12 @@ int residual_shape_gradient(sns_ctx* h, const double* w, const double* lam, doub
 // fields D), and the Zienkiewicz-Zhu indicator per cell (G null: recovered into a temporary)
 int recover_gradient(sns_ctx* h, const double* w, double* G, double* D);
 int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, double* gnorm2);
-// csrc/sns_stability.hip: the mass pass y = B(w) x and the shift-invert Arnoldi process
+// csrc/sns_stability.hip: the mass passes y = B(w) x and y = B(w)^T z, and the shift-invert Arnoldi process (left: on
+// (J + shift B)^-T B^T, with the transposed operator in the handle)
 int mass_apply(sns_ctx* h, const double* w, const double* x, double* y);
-int arnoldi_run(sns_ctx* h, const double* w, int m, double breakdown_rel, double* V, double* H, int* m_done, int* total_its,
-                int* reason);
+int mass_apply_transpose(sns_ctx* h, const double* w, const double* z, double* y);
+int arnoldi_run(sns_ctx* h, const double* w, bool left, int m, double breakdown_rel, double* V, double* H, int* m_done,
+                int* total_its, int* reason);
 // csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)
 int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sigma, double theta, const double* src,
                   const uint8_t* cmask, const double* cval, double* rhs);

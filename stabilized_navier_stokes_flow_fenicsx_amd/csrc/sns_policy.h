@@ -551,8 +551,12 @@ struct ArnoldiArgs {
     int m = STABILITY_M_MAX;
     double shift = 0.0, breakdown_rel = 1e-6;
 };
-enum StabilityRequest { SREQ_MASS_APPLY = 0, SREQ_ARNOLDI, SREQ_COUNT };
+// The left-hand kinds (sns_mass_apply_transpose, sns_stability_arnoldi_left; tests/stability_left_request_main.cpp) follow the
+// right-hand ones and are refused exactly as those are: SREQ_COUNT stays the number of right-hand kinds, SREQ_KINDS counts all.
+enum StabilityRequest { SREQ_MASS_APPLY = 0, SREQ_ARNOLDI, SREQ_COUNT, SREQ_MASS_APPLY_TRANSPOSE = SREQ_COUNT, SREQ_ARNOLDI_LEFT, SREQ_KINDS };
 inline FormVerdict check_stability_request(StabilityRequest request, const StabilityFacts& f, const ArnoldiArgs& a = {}) {
+    if (request == SREQ_MASS_APPLY_TRANSPOSE) request = SREQ_MASS_APPLY;
+    if (request == SREQ_ARNOLDI_LEFT) request = SREQ_ARNOLDI;
     if (f.dim != 3) return {SNS_E_ARG, "3-D handles only"};
     if (request == SREQ_ARNOLDI) {
         if (a.m < STABILITY_M_MIN || a.m > STABILITY_M_MAX) return {SNS_E_ARG, "m must lie in [2, 64]"};

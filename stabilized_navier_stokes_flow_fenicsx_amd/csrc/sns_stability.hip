@@ -16,8 +16,19 @@
 //   arnoldi_run    plain Arnoldi without restart on S: per step one mass pass, one Krylov solve from a zero guess with the
 //                  handle's options and damping retry (krylov(), as it is), classical Gram-Schmidt with one re-orthogonalisation
 //                  (gram_schmidt_pass, csrc/sns_ctx.h).  One host read per step.
-// Out of scope: adjoint (left) modes and structural sensitivity, which need B^T; restarted or Krylov-Schur iterations; complex
-// or negative shifts; 2-D and partitioned handles; the Carreau law.
+//   k_mass_apply_t y = B(w)^T z, the same pass for the left (adjoint) problem J^T z = -lambda B^T z: B^T is by definition the
+//                  transpose of the B above.  On a cell grad z_c is constant (P1), so with pa = w_q N_a(q), ta = w_q tau_q N_a(q)
+//                  row (a, i) is  sum_q pa z_i(q) + (sum_q ta u_q).grad z_i + pspg (sum_q ta) d_i z_p   (corrected_convection;
+//                  the reference's test function: the middle term is sum_j (sum_q ta u_q)_j d_i z_j), pressure rows are 0 (B
+//                  has no pressure columns).  The first sum is taken in closed form (z is linear on the cell), which leaves the
+//                  quadrature loop with u and tau alone: 16 entries of z are dead before it starts.  Unlike B x the pass reads the pressure entries of z (the PSPG rows of B);
+//                  constrained entries of z, a constrained pressure dof included, are read as 0 (the rows of B there are 0).
+//                  Same shape, same reproducibility: 4 lanes per row, grad z formed once per (row, cell), (l0 + l1) + (l2 + l3).
+//   arnoldi_run    with `left` the same process on S_L = (J + s B)^-T B^T: the mass pass is the transposed one, the operator
+//                  the handle holds is the transposed one (the entry point flips it and flips it back); nothing else differs.
+//                  Its Ritz vectors z satisfy z^T J = -lambda z^T B; the matrices are real, the pairing is z^T B x unconjugated.
+// Out of scope: restarted or Krylov-Schur iterations; complex or negative shifts; sensitivity to a steady forcing (it needs the
+// Hessian of the residual); 2-D and partitioned handles; the Carreau law.
 #include "sns_ctx.h"
 
 namespace sns {
@@ -115,20 +126,122 @@ __global__ __launch_bounds__(256) void k_mass_apply(int32_t n, const int64_t* __
     y[4 * i + l] = bc_mask[4 * i + l] ? 0.0 : v;
 }
 
+// one cell's share of row (node, local vertex a) of B^T z: acc[0..2] (the pressure rows of B^T are 0)
+template <bool corrected>
+__device__ __forceinline__ void mass_cell_t(const int32_t* __restrict__ tets, const double* __restrict__ pts,
+                                            const double* __restrict__ w, const double* __restrict__ z,
+                                            const uint8_t* __restrict__ bc_mask, int64_t t, int a, double nu, const FormVariant& fv,
+                                            double acc[3]) {
+    const int4 tv = *reinterpret_cast<const int4*>(tets + 4 * t);
+    const int32_t nd[4] = {tv.x, tv.y, tv.z, tv.w};
+    double X[4][3], U[4][3], Z[4][4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const int64_t o = 4 * (int64_t)nd[v];
+        const double* pp = pts + 3 * (int64_t)nd[v];
+        X[v][0] = pp[0]; X[v][1] = pp[1]; X[v][2] = pp[2];
+        const double2 u01 = *reinterpret_cast<const double2*>(w + o);
+        U[v][0] = u01.x; U[v][1] = u01.y; U[v][2] = w[o + 2];
+        const double2 z01 = *reinterpret_cast<const double2*>(z + o);
+        const double2 z23 = *reinterpret_cast<const double2*>(z + o + 2);
+        const uint32_t mk = *reinterpret_cast<const uint32_t*>(bc_mask + o);      // the node's 4 mask bytes, the pressure's too
+        Z[v][0] = (mk & 0xFFu) ? 0.0 : z01.x;
+        Z[v][1] = (mk & 0xFF00u) ? 0.0 : z01.y;
+        Z[v][2] = (mk & 0xFF0000u) ? 0.0 : z23.x;
+        Z[v][3] = (mk & 0xFF000000u) ? 0.0 : z23.y;
+    }
+    TetMetric T;
+    tet_metric(X, T);
+    const double wd = fabs(T.det) * (1.0 / 24.0);
+    // grad z_c, constant on the cell: dz[c][k] = d_k z_c
+    double dz[4][3];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dz[c][k] = ((T.g[0][k] * Z[0][c] + T.g[1][k] * Z[1][c]) + T.g[2][k] * Z[2][c]) + T.g[3][k] * Z[3][c];
+    // the Galerkin part needs no quadrature loop: z is linear on the cell, so with S = sum_v Z[v] and na(q) = N_a(q),
+    // sum_q na(q) z(q) = sum_q na(q) (qa S + dq Z[q]) = 2 qa (qa + qb) S + dq^2 Z[a]
+    const double dq = fv.qb - fv.qa;
+    const double ms = wd * (2.0 * fv.qa * (fv.qa + fv.qb)), ma = wd * (dq * dq);
+    double usum[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        usum[j] = fv.qa * (((U[0][j] + U[1][j]) + U[2][j]) + U[3][j]);
+        const double za = a == 0 ? Z[0][j] : (a == 1 ? Z[1][j] : (a == 2 ? Z[2][j] : Z[3][j]));
+        acc[j] += ms * (((Z[0][j] + Z[1][j]) + Z[2][j]) + Z[3][j]) + ma * za;
+    }
+    double tu[3] = {0.0, 0.0, 0.0}, ts = 0.0;             // sum_q ta u_q, sum_q ta:  ta = w_q tau_q N_a(q)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        double u[3], Gu[3], uGu = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) u[j] = usum[j] + dq * U[q][j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            Gu[i] = T.G[i][0] * u[0] + T.G[i][1] * u[1] + T.G[i][2] * u[2];
+            uGu += u[i] * Gu[i];
+        }
+        const double ta = (wd * supg_tau(0.0, uGu, fv.ci, nu, T.GG)) * (q == a ? fv.qb : fv.qa);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tu[i] += ta * u[i];
+        ts += ta;
+    }
+    const double ps = fv.pspg * ts;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double conv = corrected ? (tu[0] * dz[i][0] + tu[1] * dz[i][1]) + tu[2] * dz[i][2]
+                                      : (tu[0] * dz[0][i] + tu[1] * dz[1][i]) + tu[2] * dz[2][i];
+        acc[i] += conv + ps * dz[3][i];
+    }
+}
+
+// lane (i, l): cells l, l + 4, ... of row i; then lane c stores y[4 i + c], lane 3 the pressure row's 0
+template <bool corrected>
+__global__ __launch_bounds__(256) void k_mass_apply_t(int32_t n, const int64_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
+                                                      const int32_t* __restrict__ tets, const double* __restrict__ pts,
+                                                      const double* __restrict__ w, const double* __restrict__ z,
+                                                      const uint8_t* __restrict__ bc_mask, double nu, const double* __restrict__ nu_t,
+                                                      FormVariant fv, double* __restrict__ y) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = gid >> 2;
+    const int l = (int)(gid & 3);
+    const bool live = i < n;                               // (all 4 lanes of a group agree; nobody leaves before the moves)
+    const int64_t k1 = live ? nt_ptr[i + 1] : 0;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int64_t k = (live ? nt_ptr[i] : 0) + l; k < k1; k += 4) {
+        const int32_t id = nt_idx[k];                      // tet * 4 + local vertex
+        const int64_t t = (int64_t)(id >> 2);
+        mass_cell_t<corrected>(tets, pts, w, z, bc_mask, t, id & 3, nu_t ? nu_t[t] : nu, fv, acc);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        acc[c] += __shfl_xor(acc[c], 1, 4);
+        acc[c] += __shfl_xor(acc[c], 2, 4);
+    }
+    if (!live) return;
+    const double v = l == 0 ? acc[0] : (l == 1 ? acc[1] : (l == 2 ? acc[2] : 0.0));
+    y[4 * i + l] = bc_mask[4 * i + l] ? 0.0 : v;
+}
+
 __global__ __launch_bounds__(256) void k_zero_constrained(int64_t ndof, const uint8_t* __restrict__ bc_mask, double* __restrict__ x) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ndof; i += (int64_t)gridDim.x * blockDim.x)
         if (bc_mask[i]) x[i] = 0.0;
 }
 
-void launch_mass(sns_ctx* h, const double* w, const double* x, double* y) {
+// y = B(w) x, or with `left` y = B(w)^T x
+void launch_mass(sns_ctx* h, bool left, const double* w, const double* x, double* y) {
     if (h->n == 0) return;
     const FormState& S = h->form;
     const dim3 grid((unsigned)((4 * (int64_t)h->n + 255) / 256));
     const double nu = 1.0 / h->opt.reynolds;
     const double* nu_t = S.ev_on ? S.ev_nu.get() : nullptr;
     dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
-        hipLaunchKernelGGL((k_mass_apply<C() != 0>), grid, dim3(256), 0, h->stream, h->n, h->nt_ptr, h->nt_idx, h->tets, h->pts, w, x,
-                           h->bc_mask, nu, nu_t, S.fv, y);
+        if (left)
+            hipLaunchKernelGGL((k_mass_apply_t<C() != 0>), grid, dim3(256), 0, h->stream, h->n, h->nt_ptr, h->nt_idx, h->tets, h->pts, w,
+                               x, h->bc_mask, nu, nu_t, S.fv, y);
+        else
+            hipLaunchKernelGGL((k_mass_apply<C() != 0>), grid, dim3(256), 0, h->stream, h->n, h->nt_ptr, h->nt_idx, h->tets, h->pts, w, x,
+                               h->bc_mask, nu, nu_t, S.fv, y);
     });
 }
 
@@ -136,7 +249,13 @@ void launch_mass(sns_ctx* h, const double* w, const double* x, double* y) {
 
 // handle, pointers and the form state were checked by the entry point
 int mass_apply(sns_ctx* h, const double* w, const double* x, double* y) {
-    launch_mass(h, w, x, y);
+    launch_mass(h, false, w, x, y);
+    HIP_TRY(hipGetLastError());
+    return sync_stream(h);
+}
+
+int mass_apply_transpose(sns_ctx* h, const double* w, const double* z, double* y) {
+    launch_mass(h, true, w, z, y);
     HIP_TRY(hipGetLastError());
     return sync_stream(h);
 }
@@ -145,7 +264,8 @@ int mass_apply(sns_ctx* h, const double* w, const double* x, double* y) {
 // point).  V: (m + 1) columns of 4*n doubles, column 0 the start vector; H: (m + 1) x m, row major, zero beyond m_done.
 // *reason: 1 all m steps done, 2 breakdown (the Krylov space is invariant: m_done columns, H[m_done][m_done - 1] = 0 and the
 // column of V behind them zero), < 0 the KSP reason of an inner solve that did not converge (m_done = the steps completed).
-int arnoldi_run(sns_ctx* h, const double* w, int m, double breakdown_rel, double* V, double* H, int* m_done, int* total_its,
+// left: the process on (J + shift B)^-T B^T -- the mass pass is the transposed one, and the entry point has flipped the operator.
+int arnoldi_run(sns_ctx* h, const double* w, bool left, int m, double breakdown_rel, double* V, double* H, int* m_done, int* total_its,
                 int* reason) {
     const int64_t ld = ld_of(h);
     const int g = std::max(1, vec_grid(ld));
@@ -159,7 +279,7 @@ int arnoldi_run(sns_ctx* h, const double* w, int m, double breakdown_rel, double
     *reason = 1;
     // w = S v, from a zero guess; false: the inner solve did not converge (*reason holds why)
     auto apply_S = [&](const double* v, double* out, bool* ok) -> int {
-        launch_mass(h, w, v, b);
+        launch_mass(h, left, w, v, b);
         HIP_TRY(hipMemsetAsync(out, 0, (size_t)ld * sizeof(double), h->stream));
         int its = 0, kr = 0;
         double rn = 0.0;

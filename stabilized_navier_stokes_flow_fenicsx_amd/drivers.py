@@ -332,7 +332,9 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
     out = dict(msh=msh_f, w=wg, u=wg.reshape(-1, 4)[:, :3].copy(), p=wg.reshape(-1, 4)[:, 3].copy(), Re=Re, img_fname=img_fname,
                channel_mesh_size=channel_mesh_size, flowrate_ratio=flowrate_ratio, newton=Pf.last_newton)
     derived = _derived_fields(Pf, w)
-    _stability(Pf, w)
+    stab = _stability(Pf, w)
+    if stab is not None:
+        out["stability"] = stab
     if derived is not None:
         out["derived"] = derived
     conc = coupled[1] if coupled is not None else _scalar_transport(Pf, w, msh_f)
@@ -348,6 +350,7 @@ def navier_stokes_channel_main(argv=None):
     folder, _ = make_output_folder(r["Re"], r["img_fname"], r["channel_mesh_size"])
     save_navier_stokes_solution(r["u"], r["p"], r["msh"], folder, r["Re"])
     _write_derived_fields(r.get("derived"), r["msh"], lambda label: os.path.join(folder, f"Re{r['Re']}Channel{label}"))
+    _write_wavemaker(r.get("stability"), r["msh"], os.path.join(folder, f"Re{r['Re']}ChannelWavemaker"))
     if r.get("concentration") is not None and _rank() == 0:
         write_xdmf(os.path.join(folder, f"Re{r['Re']}ChannelConcentration"), r["msh"], "Concentration", r["concentration"])
     write_run_metadata(folder, r["Re"], r["img_fname"], r["flowrate_ratio"], r["channel_mesh_size"], r["msh"])
@@ -403,7 +406,7 @@ def duct_stokes_main(argv=None):
         write_xdmf("StokesDuctPressure", msh, "f", p)
         write_xdmf("StokesDuctVelcoity", msh, "f", u)             # (sic) file name of the reference :255
     _write_derived_fields(_derived_fields(P, U), msh, lambda label: f"StokesDuct{label}")
-    _stability(P, U)
+    _write_wavemaker(_stability(P, U), msh, "StokesDuctWavemaker")
     conc = coupled[1] if coupled is not None else _scalar_transport(P, U, msh)
     if conc is not None and _rank() == 0:
         write_xdmf("StokesDuctConcentration", msh, "Concentration", conc)
@@ -567,14 +570,48 @@ def _stability(P, w):
     parts = spec.split(",")
     n_modes, shift = int(parts[0]), (float(parts[1]) if len(parts) > 1 else 0.0)
     from .solver import SnsError, linear_stability, print_stability
+    sens = os.environ.get("SNS_STABILITY_SENSITIVITY", "0") == "1"
     try:
-        res = linear_stability(P, w, n_modes=n_modes, shift=shift)
+        res = linear_stability(P, w, n_modes=n_modes, shift=shift, left=True) if sens else linear_stability(P, w, n_modes=n_modes, shift=shift)
     except SnsError as e:                                 # (a viscosity law, a 2-D problem: the library says which)
         if _rank() == 0:
             print(f"SNS_STABILITY: skipped ({e})", flush=True)
         return None
     print_stability(res, _rank())
+    if sens:
+        _stability_sensitivity(P, w, res)
     return res
+
+
+def _stability_sensitivity(P, w, res):
+    """SNS_STABILITY_SENSITIVITY=1 beside SNS_STABILITY: for the leading converged mode that has a left partner, one printed
+    line -- d lambda / d Re (``solver.eigenvalue_reynolds_sensitivity``) and the linear estimate of the critical Reynolds number
+    -- and the wavemaker map (``solver.structural_sensitivity``) as ``res.wavemaker`` (numpy, one value per node), which the
+    script writes as a ...Wavemaker field beside its other files."""
+    from .solver import SnsError, eigenvalue_reynolds_sensitivity, structural_sensitivity
+    res.wavemaker = None
+    lead = [k for k, ok in enumerate(res.left_converged) if ok]
+    if not lead:
+        if _rank() == 0:
+            print("SNS_STABILITY_SENSITIVITY: no converged mode with a converged left partner; skipped", flush=True)
+        return
+    k = lead[0]
+    try:
+        res.wavemaker = structural_sensitivity(P, w, res, k).cpu().numpy()
+        dlam, Re_c = eigenvalue_reynolds_sensitivity(P, w, res, k)
+    except (SnsError, RuntimeError) as e:
+        if _rank() == 0:
+            print(f"SNS_STABILITY_SENSITIVITY: skipped ({e})", flush=True)
+        return
+    if _rank() == 0:
+        lam = res.eigenvalues[k]
+        print(f"Stability sensitivity: lambda = {lam.real:+.6e} {lam.imag:+.6e}i  dlambda/dRe = {dlam.real:+.6e} {dlam.imag:+.6e}i  "
+              f"Re_c estimate = {Re_c:.6e}", flush=True)
+
+
+def _write_wavemaker(res, msh, path_noext):
+    if res is not None and getattr(res, "wavemaker", None) is not None and _rank() == 0:
+        write_xdmf(path_noext, msh, "Wavemaker", res.wavemaker)
 
 
 def _sensitivity():
@@ -753,7 +790,7 @@ def dfg_3d_main(argv=None):
         write_xdmf("DFGValidationPressureNavierStokes", msh, "Pressure", wg.reshape(-1, 4)[:, 3].copy())
         write_xdmf("DFGValidationVelocityNavierStokes", msh, "Velocity", wg.reshape(-1, 4)[:, :3].copy())
     _write_derived_fields(_derived_fields(P, w), msh, lambda label: f"DFGValidation{label}NavierStokes")
-    _stability(P, w)
+    _write_wavemaker(_stability(P, w), msh, "DFGValidationWavemakerNavierStokes")
     if _sensitivity():
         sc = Fn.drag_lift_coefficients(np.ones(3))[0]
         ob = msh.meta["tags"]["obstacle"]

@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import time
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -66,6 +67,14 @@ class StabilityResult:
     m_done: int
     ksp_its: int
     reason: int
+    # linear_stability(left=True) only:
+    shift: float = 0.0
+    left_modes: Optional[torch.Tensor] = None     # (n, ndof) complex128: z with z^T J = -lam z^T B, scaled so that z^T B x = 1 (unconjugated); 0 where unpaired
+    left_converged: Optional[np.ndarray] = None   # (n,) bool: the right pair converged and has a converged left partner
+    left_eigenvalues: Optional[np.ndarray] = None  # (n,) complex: the partner's own Ritz value (nan where unpaired)
+    left_m_done: int = 0
+    left_ksp_its: int = 0
+    left_reason: int = 0
 
 
 class FlowProblem:
@@ -361,11 +370,26 @@ class FlowProblem:
         check(self.lib.sns_mass_apply(self.h, _ptr(w), _ptr(x), _ptr(out)))
         return out
 
-    def stability_arnoldi(self, w, shift: float = 0.0, m: int = 64, start=None, breakdown_rel: float = 1e-6):
+    def mass_apply_transpose(self, w, z, out=None) -> torch.Tensor:
+        """``B(w)^T z`` (sns_mass_apply_transpose): the transpose of the operator of ``mass_apply``, matrix-free in one pass,
+        bitwise reproducible -- the mass pass of the left (adjoint) eigenproblem J^T z = -lam B^T z.  Unlike ``mass_apply`` it
+        reads the pressure entries of ``z`` (the PSPG rows of B); constrained entries of ``z`` are read as 0.  Pressure rows
+        and rows of constrained dofs are 0.  Single-GPU 3-D problems."""
+        w, z = self._vec(w), self._vec(z)
+        out = self.zeros() if out is None else self._vec(out)
+        check(self.lib.sns_mass_apply_transpose(self.h, _ptr(w), _ptr(z), _ptr(out)))
+        return out
+
+    def stability_arnoldi(self, w, shift: float = 0.0, m: int = 64, start=None, breakdown_rel: float = 1e-6, side: str = "right"):
         """``m`` steps of shift-invert Arnoldi on (J + shift B)^-1 B at the steady state ``w`` (sns_stability_arnoldi), with
         the problem's ksp / pc options for the inner solves.  Returns ``(V, H, ArnoldiResult)``: V a device tensor
         (m + 1, ndof) whose rows are the orthonormal basis, H numpy (m + 1, m).  ``start``: a dof vector, by default
-        cos(1 + 0.37 i) over the dofs.  Afterwards the handle's matrix is J + shift B and its form is steady again."""
+        cos(1 + 0.37 i) over the dofs.  Afterwards the handle's matrix is J + shift B and its form is steady again.
+        ``side="left"``: the same process on (J + shift B)^-T B^T (sns_stability_arnoldi_left), whose Ritz vectors are the
+        left (adjoint) modes; the operator is transposed for the call and transposed back."""
+        if side not in ("right", "left"):
+            raise ValueError("side must be 'right' or 'left'")
+        run = self.lib.sns_stability_arnoldi if side == "right" else self.lib.sns_stability_arnoldi_left
         w = self._vec(w)
         m = int(m)
         V = torch.zeros(max(m, 0) + 1, self.ndof, dtype=torch.float64, device=self.device)   # (m outside [2, 64]: the library refuses)
@@ -375,8 +399,8 @@ class FlowProblem:
             V[0] = self._vec(start)
         H = np.zeros((max(m, 0) + 1, max(m, 0)))
         done, its, reason = C.c_int(), C.c_int(), C.c_int()
-        check(self.lib.sns_stability_arnoldi(self.h, _ptr(w), float(shift), m, float(breakdown_rel), _ptr(V), H.ctypes.data,
-                                             C.byref(done), C.byref(its), C.byref(reason)))
+        check(run(self.h, _ptr(w), float(shift), m, float(breakdown_rel), _ptr(V), H.ctypes.data, C.byref(done), C.byref(its),
+                  C.byref(reason)))
         return V, H, ArnoldiResult(done.value, reason.value, its.value)
 
     def spmv(self, x, out=None) -> torch.Tensor:
@@ -1229,19 +1253,62 @@ def ritz_pairs(H, m_done: int, shift: float = 0.0):
     return lam[order], Y[:, order], est[order]
 
 
+def pair_left_right(lam_right, lam_left, shift: float = 0.0, rtol: float = 1e-5):
+    """Which left Ritz value belongs to which right one (pure numpy): ``partner[k]`` = the index into ``lam_left`` of the value
+    nearest ``lam_right[k]``, or -1.  A pair is accepted only if the two differ by at most ``rtol`` |lam - shift| -- both sides
+    are Ritz values of shift-inverted operators, theta = 1 / (shift - lam), whose relative error is what the residual estimate
+    controls, so |lam - shift| is the scale on which two estimates of one eigenvalue agree -- and a left value serves one right
+    value only, the nearest; candidates are taken in ascending distance.  Whatever is left over stays -1: flagged, not guessed.
+    Non-finite values never pair."""
+    lr, ll = np.asarray(lam_right, dtype=complex), np.asarray(lam_left, dtype=complex)
+    partner = np.full(len(lr), -1, dtype=np.int64)
+    if len(lr) == 0 or len(ll) == 0:
+        return partner
+    with np.errstate(invalid="ignore"):
+        dist = np.abs(lr[:, None] - ll[None, :])
+        ok = np.isfinite(dist) & (dist <= rtol * np.abs(lr - shift)[:, None])
+    taken = np.zeros(len(ll), dtype=bool)
+    for flat in np.argsort(np.where(ok, dist, np.inf), axis=None, kind="stable"):
+        k, j = divmod(int(flat), len(ll))
+        if not ok[k, j]:
+            break
+        if partner[k] < 0 and not taken[j]:
+            partner[k], taken[j] = j, True
+    return partner
+
+
+def _complex_apply(op, x):
+    """op (real, linear, device vector -> device vector) on a complex device vector."""
+    return torch.complex(op(x.real.contiguous()), op(x.imag.contiguous()))
+
+
+def mode_pairing(problem: FlowProblem, w, z, x):
+    """z^T B(w) x of a left and a right mode (complex device vectors), unconjugated: the matrices are real.  Python complex."""
+    Bx = _complex_apply(lambda v: problem.mass_apply(w, v), x)
+    return complex(torch.sum(z * Bx))
+
+
 def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0.0, m: int = 64, tol: float = 1e-7,
-                     ksp_rtol: float = 1e-10) -> StabilityResult:
+                     ksp_rtol: float = 1e-10, left: bool = False, pair_rtol: float = 1e-5) -> StabilityResult:
     """Leading eigenvalues and modes of the linearised transient operator B x_t + J x = 0 at the steady state ``w``: is the
     state stable (every Re lam < 0), and if not, at which frequency Im lam / 2 pi does it go?  ``m`` steps of shift-invert
     Arnoldi (``FlowProblem.stability_arnoldi``) with the inner tolerance ``ksp_rtol`` (the problem's options are restored
     afterwards), ``ritz_pairs`` on the host, ``n_modes`` modes formed as V y on the device: the least stable of the pairs whose residual
     estimate is at most ``tol`` (``converged``), least stable first, and behind them, if fewer converged, the others by
     ascending estimate.  Eigenvalues nearest the shift converge first: shift = 0 finds
-    those of smallest modulus, which are the least stable ones of a flow near its first instability."""
+    those of smallest modulus, which are the least stable ones of a flow near its first instability.
+
+    ``left=True`` runs the left process too (``stability_arnoldi(side="left")``, as many steps, the same tolerance) and pairs
+    every selected right pair that converged with the converged left Ritz pair of nearest eigenvalue (``pair_left_right`` with
+    ``pair_rtol``): ``left_converged`` says which entries have a partner, ``left_modes`` holds z = V_L y_L scaled so that
+    z^T B x = 1 with the right mode as returned (unconjugated; z^T J = -lam z^T B), zero where there is none, and
+    ``left_eigenvalues`` the partner's own Ritz value.  The other fields are what they are without it."""
     old = problem.options.ksp_rtol
     problem.set_options(ksp_rtol=float(ksp_rtol))
     try:
         V, H, res = problem.stability_arnoldi(w, shift=shift, m=m)
+        if left:
+            VL, HL, resL = problem.stability_arnoldi(w, shift=shift, m=m, side="left")
     finally:
         problem.set_options(ksp_rtol=old)
     lam, Y, est = ritz_pairs(H, res.m_done, shift)
@@ -1262,7 +1329,90 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
         modes = modes * (big.conj() / big.abs())
     else:
         modes = torch.zeros(0, problem.ndof, dtype=torch.complex128, device=V.device)
-    return StabilityResult(lam, modes, est, est <= tol, res.m_done, res.ksp_its, res.reason)
+    result = StabilityResult(lam, modes, est, est <= tol, res.m_done, res.ksp_its, res.reason, float(shift))
+    if not left:
+        return result
+    lamL, YL, estL = ritz_pairs(HL, resL.m_done, shift)
+    okL = np.nonzero(estL <= tol)[0]
+    partner = pair_left_right(np.where(result.converged, lam, np.nan), lamL[okL], shift, pair_rtol)
+    zs = torch.zeros_like(modes)
+    lam_left = np.full(n, np.nan + 0j)
+    VLk = VL[:resL.m_done].T
+    for k in np.nonzero(partner >= 0)[0]:
+        j = okL[partner[k]]
+        y = np.ascontiguousarray(YL[:, j])
+        z = torch.complex(VLk @ torch.from_numpy(y.real.copy()).to(V.device), VLk @ torch.from_numpy(y.imag.copy()).to(V.device))
+        zs[k] = z / mode_pairing(problem, w, z, modes[k])
+        lam_left[k] = lamL[j]
+    result.left_modes, result.left_converged, result.left_eigenvalues = zs, partner >= 0, lam_left
+    result.left_m_done, result.left_ksp_its, result.left_reason = resL.m_done, resL.ksp_its, resL.reason
+    return result
+
+
+def _mode_pair(result: StabilityResult, k: int):
+    if result.left_modes is None:
+        raise ValueError("the result has no left modes: run linear_stability(..., left=True)")
+    if not result.left_converged[k]:
+        raise ValueError(f"mode {k} has no converged left partner")
+    return complex(result.eigenvalues[k]), result.modes[k], result.left_modes[k]
+
+
+def structural_sensitivity(problem: FlowProblem, w, result: StabilityResult, k: int = 0) -> torch.Tensor:
+    """The wavemaker map of mode ``k`` of a ``linear_stability(..., left=True)`` result: per node
+    |z_u(node)| |x_u(node)| / |z^T B x| over the three velocity components, a device tensor of n_nodes.  It bounds the drift of
+    the eigenvalue under a local feedback dJ = C delta(node) (|d lam| <= |C| times the map): where it is large the
+    instability lives.  Invariant under a rescaling of x or z."""
+    _, x, z = _mode_pair(result, k)
+    zu = torch.linalg.vector_norm(z.view(-1, 4)[:, :3], dim=1)
+    xu = torch.linalg.vector_norm(x.view(-1, 4)[:, :3], dim=1)
+    return zu * xu / abs(mode_pairing(problem, w, z, x))
+
+
+def eigenvalue_drift(problem: FlowProblem, w, result: StabilityResult, k: int, dJx, dBx=None) -> complex:
+    """First-order change of eigenvalue ``k`` under a perturbation (dJ, dB) of the pencil J x = -lam B x:
+    d lam = -z^T (dJ x + lam dB x) / (z^T B x), from the caller's ``dJx`` = dJ . x (and ``dBx`` = dB . x, if B changes too):
+    complex device vectors, x = ``result.modes[k]``."""
+    lam, x, z = _mode_pair(result, k)
+    t = dJx if dBx is None else dJx + lam * dBx
+    return -complex(torch.sum(z * t)) / mode_pairing(problem, w, z, x)
+
+
+def eigenvalue_reynolds_sensitivity(problem: FlowProblem, w, result: StabilityResult, k: int = 0, rel_step: float = 1e-3,
+                                    newton_tol: float = 1e-11):
+    """``(dlam_dRe, Re_c)``: the total derivative of eigenvalue ``k`` with respect to the Reynolds number, the change of the
+    base flow included, and the linear estimate Re_c = Re - real(lam) / real(dlam/dRe) of where the mode crosses the imaginary
+    axis (nan if the real part does not move).
+
+    Two Newton solves from ``w`` at Re (1 +- rel_step) give the steady states there; at each, ``jacobian`` + ``spmv`` and
+    ``mass_apply`` on the real and imaginary part of x give J x and B x; their central differences are dJ x and dB x of
+    ``eigenvalue_drift``.  No eigenproblem is solved again.  The error is O(rel_step^2): the second-order term of the
+    perturbation series (3e-8 relative at 1e-3, 3e-6 at 1e-2 for the leading mode of the (6, 3, 3) test duct against the
+    difference of dense spectra), plus the error of the two states over rel_step -- which is why the two Newton solves run
+    with snes_rtol = snes_stol = ``newton_tol`` and snes_atol = newton_tol / 100 (restored afterwards) and why ``w`` should be
+    converged as well.  Afterwards the problem has its Reynolds number and options back and holds the steady Jacobian at
+    ``w``, untransposed."""
+    lam, x, z = _mode_pair(result, k)
+    w = problem._vec(w)
+    Re = float(problem.options.reynolds)
+    old = {name: getattr(problem.options, name) for name in ("snes_rtol", "snes_atol", "snes_stol")}
+    Jx, Bx = [], []
+    try:
+        problem.set_options(snes_rtol=float(newton_tol), snes_stol=float(newton_tol), snes_atol=0.01 * float(newton_tol))
+        for sign in (1.0, -1.0):
+            problem.set_options(reynolds=Re * (1.0 + sign * rel_step))
+            ws, nres = problem.newton_solve(w.clone())
+            if nres.reason <= 0:
+                raise RuntimeError(f"eigenvalue_reynolds_sensitivity: Newton at Re {Re * (1.0 + sign * rel_step):g} ended with reason {nres.reason}")
+            problem.jacobian(ws, "ns")
+            Jx.append(_complex_apply(problem.spmv, x))
+            Bx.append(_complex_apply(lambda v: problem.mass_apply(ws, v), x))
+    finally:
+        problem.set_options(reynolds=Re, **old)
+        problem.jacobian(w, "ns")
+    h = 2.0 * rel_step * Re
+    dlam = eigenvalue_drift(problem, w, result, k, (Jx[0] - Jx[1]) / h, (Bx[0] - Bx[1]) / h)
+    Re_c = Re - lam.real / dlam.real if dlam.real != 0.0 else float("nan")
+    return dlam, Re_c
 
 
 def print_stability(result: StabilityResult, rank: int = 0):

@@ -1,0 +1,267 @@
+"""CPU checks behind the left stability modes (sns_mass_apply_transpose, sns_stability_arnoldi_left, solver.pair_left_right):
+the closed forms of B^T z that k_mass_apply_t implements against the transpose of the oracle's B = J(1) - J(0), which pins the
+kernel's formula before any GPU run; the left process of the oracle against the dense spectrum; biorthogonality; the
+perturbation formula for d lam / d Re against the central difference of dense spectra at re-converged states; the pairing rule;
+the request rules of the two new kinds through their stand-alone main; the binding of the entry points.  The bounds are
+conditions on the oracle and on pure-numpy code, not on the GPU code."""
+import ctypes as C
+import itertools
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import left_modes_oracle as LO
+import stability_oracle as SO
+from conftest import ROOT
+from oracle import forms_literal as FL
+from stabilized_navier_stokes_flow_fenicsx_amd import solver as S
+
+E_ARG, E_STATE = -1, -3
+TOL = 1e-7
+
+
+# ---- 1. the closed forms of B^T z ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", ["plain", "corrected", "form_variant", "viscosity_field"])
+@pytest.mark.parametrize("name", ["duct633", "duct322"])
+def test_closed_form_is_the_transpose_of_the_oracle_mass(name, variant):
+    """y = B^T z from the per-element closed forms equals (J(1) - J(0))^T z to round-off: 1e-13 of max |y| (a few hundred
+    products of O(1) factors per entry, fp64).  z is random in every slot, the constrained ones and the pressure included, so
+    the test also says which entries are read: B has zero rows on constrained dofs (read as 0) and PSPG rows (pressure read)."""
+    c = SO.case(name)
+    rng = np.random.default_rng(5)
+    z = rng.standard_normal(len(c.w))
+    form, kw, base = {}, {}, dict(FL.VARIANT)
+    try:
+        if variant == "corrected":
+            form = kw = dict(corrected_convection=True)
+        if variant == "form_variant":
+            FL.VARIANT.update(ci=144.0, pspg=-1.0, one_point=True)
+        if variant == "viscosity_field":
+            form = kw = dict(nu_t=(1.0 / c.Re) * np.exp(rng.uniform(-1.5, 1.5, len(c.mesh.tets))))
+        B = c.mass(**form)
+        y = LO.mass_transpose_closed_form(c.mesh.points, c.mesh.tets, c.w, z, c.Re, c.mask, **kw)
+    finally:
+        FL.VARIANT.update(base)
+    ref = B.T @ z
+    err = np.abs(y - ref).max() / np.abs(ref).max()
+    asym = abs(B - B.T).max() / abs(B).max()
+    print(name, variant, "max|dy| / max|y| =", err, " max|B - B^T| / max|B| =", asym)
+    assert err <= 1e-13
+    assert asym > 0.1                                           # B x could not stand in for B^T z
+    assert not y[3::4].any() and not y[c.constrained].any()
+    # the pressure entries of z matter, the constrained ones do not
+    z2 = z.copy()
+    z2[c.constrained] = 7.0
+    z3 = z.copy()
+    z3[3::4] += np.where(c.constrained[3::4], 0.0, 1.0) * rng.standard_normal(len(z) // 4)
+    try:
+        if variant == "form_variant":
+            FL.VARIANT.update(ci=144.0, pspg=-1.0, one_point=True)
+        y2 = LO.mass_transpose_closed_form(c.mesh.points, c.mesh.tets, c.w, z2, c.Re, c.mask, **kw)
+        y3 = LO.mass_transpose_closed_form(c.mesh.points, c.mesh.tets, c.w, z3, c.Re, c.mask, **kw)
+    finally:
+        FL.VARIANT.update(base)
+    assert np.array_equal(y2, y)
+    assert np.abs(y3 - y).max() > 1e-6 * np.abs(y).max()
+
+
+# ---- 2. the left process and the spectra ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,shift", [("duct633", 0.0), ("duct633", 2.0), ("duct833", 0.0), ("duct833", 2.0)])
+def test_left_arnoldi_of_the_oracle_matches_the_dense_spectrum(name, shift):
+    """The conditions test_host_stability.py puts on the right process, on the left one (exact solves): orthogonality and the
+    Arnoldi relation at round-off, at least 20 pairs with estimate <= 1e-7, each a dense eigenvalue to 1e-6, the six dense
+    eigenvalues nearest the shift matched to 1e-8.  And the dense spectrum of the transposed pencil is the dense spectrum:
+    the 20 eigenvalues nearest the shift to 1e-8 (QZ on a non-normal pencil of 300 to 400 dofs)."""
+    c = SO.case(name)
+    J, B = c.operators()
+    V, H, m_done, ratios = LO.left_arnoldi(J, B, c.constrained, shift=shift)
+    assert m_done == 64
+    assert SO.orthogonality(V, 65) < 5e-15
+    assert LO.left_relation(J, B, c.constrained, shift, V, H, 64) < 1e-13
+    lam, Y, est = S.ritz_pairs(H, m_done, shift)
+    conv = est <= TOL
+    dense = SO.dense_spectrum(J, B, c.constrained)
+    six = dense[np.argsort(np.abs(dense - shift))][:6]
+    print(name, shift, "converged", conv.sum(), "worst", SO.nearest(dense, lam[conv]).max(), "six", SO.nearest(lam[conv], six).max())
+    assert conv.sum() >= 20
+    assert SO.nearest(dense, lam[conv]).max() < 1e-6
+    assert SO.nearest(lam[conv], six).max() < 1e-8
+    dense_t = SO.dense_spectrum(*LO.transposed(J, B), c.constrained)
+    twenty = dense[np.argsort(np.abs(dense - shift))][:20]
+    both = SO.nearest(dense_t, twenty).max()
+    print("left vs right dense spectrum, 20 nearest the shift:", both, "finite eigenvalues", len(dense), len(dense_t))
+    assert len(dense_t) == len(dense) and both < 1e-8
+
+
+# ---- 3. biorthogonality --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["duct633", "duct833"])
+def test_left_and_right_modes_are_biorthogonal(name):
+    """Exact pairs: Z^T B X is the identity (off-diagonal 1e-8: QZ vectors of a non-normal pencil); they satisfy both
+    eigenproblems; the pairing is far from degenerate (|z^T B x| / (|z| |B x|) >= 1e-3 for the six leading modes: the reciprocal
+    is the eigenvalue's condition number, and 1e3 of it turns residuals of 1e-7 into eigenvalue errors of 1e-4).  Ritz pairs of
+    the two oracle processes (estimate <= 1e-7, shift 0): the six nearest the shift pair one to one by solver.pair_left_right
+    and Z^T B X has an off-diagonal below 1e-5 of its smallest diagonal entry -- two vectors with relative residuals r <= 1e-7
+    are orthogonal up to r over the relative gap of their eigenvalues, at least 1e-2 among these."""
+    c = SO.case(name)
+    J, B = c.operators()
+    lam, X, Z = LO.exact_pairs(J, B, c.constrained)
+    near = np.argsort(np.abs(lam))[:12]
+    M = Z[:, near].T @ (B @ X[:, near])
+    off = np.abs(M - np.eye(12)).max()
+    res_r = max(SO.mode_residual(J, B, lam[k], X[:, k]) for k in near)
+    res_l = max(LO.left_mode_residual(J, B, lam[k], Z[:, k]) for k in near)
+    cond = np.array([abs(Z[:, k] @ (B @ X[:, k])) / (np.linalg.norm(Z[:, k]) * np.linalg.norm(B @ X[:, k])) for k in near[:6]])
+    print(name, "exact pairs: |Z^T B X - I|", off, "residuals", res_r, res_l, "pairing cosines", cond)
+    assert off < 1e-8 and res_r < 1e-9 and res_l < 1e-9
+    assert cond.min() >= 1e-3
+    # Ritz pairs of the two processes
+    Vr, Hr, kr, _ = SO.arnoldi(J, B, c.constrained)
+    Vl, Hl, kl, _ = LO.left_arnoldi(J, B, c.constrained)
+    lr, Yr, er = S.ritz_pairs(Hr, kr, 0.0)
+    ll, Yl, el = S.ritz_pairs(Hl, kl, 0.0)
+    okr, okl = np.nonzero(er <= TOL)[0], np.nonzero(el <= TOL)[0]
+    six = okr[np.argsort(np.abs(lr[okr]))][:6]
+    partner = S.pair_left_right(lr[six], ll[okl])
+    assert (partner >= 0).all() and len(set(partner)) == 6
+    Xr = Vr[:kr].T @ Yr[:, six]
+    Zl = Vl[:kl].T @ Yl[:, okl[partner]]
+    M = Zl.T @ (B @ Xr)
+    d = np.abs(np.diag(M))
+    off = np.abs(M - np.diag(np.diag(M))).max() / d.min()
+    gaps = np.abs(lr[six][:, None] - lr[six][None, :]) / np.abs(lr[six])[:, None]
+    print(name, "Ritz pairs: off-diagonal / smallest diagonal", off, "smallest relative gap", gaps[gaps > 0].min())
+    assert gaps[gaps > 0].min() >= 1e-2
+    assert off < 1e-5
+
+
+# ---- 4. the sensitivity formula ------------------------------------------------------------------------------------------------
+def test_the_perturbation_formula_against_the_difference_of_dense_spectra():
+    """d lam / d Re of the leading eigenvalue of duct633: -z^T (dJ + lam dB) x / (z^T B x), with dJ and dB central differences
+    between the re-converged states at Re (1 +- eps) and exact modes, against the central difference of the dense spectra at
+    those states.  The two differ by the second-order term of the perturbation series alone: at most 1e-4 relative at
+    eps = 1e-3, and a hundred times that at eps = 1e-2 (asserted within a factor 2 of 100)."""
+    name = "duct633"
+    c = SO.case(name)
+    lam, X, Z = LO.exact_pairs(*c.operators(), c.constrained)
+    gap = {}
+    for eps in (1e-2, 1e-3):
+        formula = LO.reynolds_formula(name, lam[0], Z[:, 0], X[:, 0], eps)
+        fd = LO.reynolds_fd(name, lam[0], eps)
+        gap[eps] = abs(formula - fd) / abs(fd)
+        print("eps", eps, "lam", lam[0], "formula", formula, "fd", fd, "relative gap", gap[eps])
+    assert gap[1e-3] <= 1e-4
+    assert 50.0 <= gap[1e-2] / gap[1e-3] <= 200.0
+
+
+# ---- 5. the pairing ------------------------------------------------------------------------------------------------------------
+def test_pairing_flags_a_missing_partner():
+    """Synthetic values: a conjugate pair goes to the right members, a value without a partner within rtol |lam - shift| gets
+    -1, a left value is used once, nan and empty inputs pair nothing.  Then the oracle's processes: a left run of 48 steps has
+    fewer converged pairs than a right run of 64; every right pair is either paired with the same eigenvalue or flagged."""
+    right = np.array([-0.5 + 2.0j, -0.5 - 2.0j, -1.0, -3.0, np.nan])
+    left = np.array([-0.5 - 2.0j + 1e-9, -1.0 + 2e-4, -0.5 + 2.0j - 1e-9j, -3.0 + 1e-7])
+    assert S.pair_left_right(right, left).tolist() == [2, 0, -1, 3, -1]                # -1.0: off by 2e-4 > 1e-5
+    assert S.pair_left_right(right, left, rtol=1e-3).tolist() == [2, 0, 1, 3, -1]
+    assert S.pair_left_right(right, left, shift=-1.0, rtol=1e-3).tolist() == [2, 0, -1, 3, -1]   # |lam - shift| = 0 there
+    assert S.pair_left_right([-1.0, -1.0 + 1e-8], [-1.0]).tolist() == [0, -1]          # one left value, one right value
+    assert S.pair_left_right([], left).tolist() == [] and S.pair_left_right(right, []).tolist() == [-1] * 5
+    c = SO.case("duct633")
+    J, B = c.operators()
+    Vr, Hr, kr, _ = SO.arnoldi(J, B, c.constrained)
+    Vl, Hl, kl, _ = LO.left_arnoldi(J, B, c.constrained, m=48)
+    lr, _, er = S.ritz_pairs(Hr, kr, 0.0)
+    ll, _, el = S.ritz_pairs(Hl, kl, 0.0)
+    lr, ll = lr[er <= TOL], ll[el <= TOL]
+    partner = S.pair_left_right(lr, ll)
+    print("right converged", len(lr), "left converged", len(ll), "paired", (partner >= 0).sum())
+    assert 0 < len(ll) < len(lr)
+    assert (partner >= 0).sum() == len(ll) and (partner < 0).sum() == len(lr) - len(ll)
+    hit = partner >= 0
+    assert np.abs(lr[hit] - ll[partner[hit]]).max() <= 1e-5 * np.abs(lr[hit]).max()
+
+
+# ---- 6. the request rules of the new kinds ---------------------------------------------------------------------------------------
+def test_left_request_rules(tmp_path):
+    """check_stability_request for SREQ_MASS_APPLY_TRANSPOSE and SREQ_ARNOLDI_LEFT, every combination of the facts and a sweep
+    of the arguments, against a transcription of the rules written here: argument errors first (dimension, m, shift,
+    breakdown_rel), then the state (communicator, law, time term; the mass pass ignores a time term and the arguments) -- and
+    against the right-hand kind's verdict for the same question, which must be the same."""
+    exe = str(tmp_path / "stability_left_request")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
+                            "-I", os.path.join(ROOT, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
+                            os.path.join(ROOT, "tests", "stability_left_request_main.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    MASS_T, ARNOLDI_L = 0, 1
+
+    def expected(req, dim, part, tt, vl, m, shift, brel):
+        shift, brel = float(shift), float(brel)
+        checks = [(dim != 3, E_ARG, "3-D handles only")]
+        if req == ARNOLDI_L:
+            checks += [(not 2 <= m <= 64, E_ARG, "m must lie in [2, 64]"),
+                       (not (shift >= 0.0 and math.isfinite(shift)), E_ARG, "the shift must be finite and >= 0"),
+                       (not 0.0 < brel < 1.0, E_ARG, "breakdown_rel must lie in (0, 1)")]
+        checks += [(part, E_STATE, "not with a communicator attached (partitioned stability analysis is not built)"),
+                   (vl, E_STATE, "not with a viscosity law set (the mass operator of the law's form is not built)")]
+        if req == ARNOLDI_L:
+            checks.append((tt, E_STATE, "not with a time term set (the analysis sets its own and clears it)"))
+        return next(((code, tail) for cond, code, tail in checks if cond), (0, ""))
+
+    facts = list(itertools.product((MASS_T, ARNOLDI_L), (2, 3), (0, 1), (0, 1), (0, 1)))
+    args = [(64, "0", "1e-6"), (2, "2.5", "0.5"), (1, "0", "1e-6"), (65, "0", "1e-6"), (0, "0", "1e-6"), (-3, "0", "1e-6"),
+            (32, "-1e-300", "1e-6"), (32, "-2", "1e-6"), (32, "nan", "1e-6"), (32, "inf", "1e-6"), (32, "1e308", "1e-6"),
+            (32, "0", "0"), (32, "0", "1"), (32, "0", "-0.1"), (32, "0", "nan"), (32, "0", "1.5"), (32, "0", "1e-300"),
+            (65, "nan", "2"), (1, "-1", "0")]
+    combos = [f + a for f in facts for a in args]
+    text = "".join(" ".join(map(str, c)) + "\n" for c in combos)
+    run = subprocess.run([exe], input=text, capture_output=True, text=True)
+    assert run.returncode == 0, run.returncode
+    lines = run.stdout.split("\n")
+    assert lines[0].split() == ["2", "2", "3", "4"]            # the right-hand count stays 2; the new kinds follow it
+    rows = [ln.split("\t") for ln in lines[1:1 + len(combos)]]
+    assert len(rows) == len(combos)
+    got = set()
+    for c, (lc, lt, rc, rt) in zip(combos, rows):
+        assert (int(lc), lt) == expected(*c), (c, lc, lt)
+        assert (lc, lt) == (rc, rt), c
+        got.add((int(lc), lt))
+    assert got >= {(0, ""), (E_ARG, "3-D handles only"), (E_ARG, "m must lie in [2, 64]"),
+                   (E_ARG, "the shift must be finite and >= 0"), (E_ARG, "breakdown_rel must lie in (0, 1)"),
+                   (E_STATE, "not with a communicator attached (partitioned stability analysis is not built)"),
+                   (E_STATE, "not with a viscosity law set (the mass operator of the law's form is not built)"),
+                   (E_STATE, "not with a time term set (the analysis sets its own and clears it)")}
+
+
+# ---- 7. the binding --------------------------------------------------------------------------------------------------------------
+def test_left_entry_points_are_bound(built_lib):
+    """Symbols, argtypes, header declarations; a null handle is SNS_E_ARG before any GPU call (this machine has none); the ABI
+    version is the one the right-hand entry points came with."""
+    from stabilized_navier_stokes_flow_fenicsx_amd import _lib
+    H, P, D, I = C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_int)
+    hdr = open(os.path.join(ROOT, "include", "sns.h")).read()
+    for name in ("sns_mass_apply_transpose", "sns_stability_arnoldi_left"):
+        assert name in _lib.SYMBOLS and hasattr(built_lib, name)
+        assert ("SNS_API int %s(" % name) in hdr
+    nm = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
+    assert " T sns_mass_apply_transpose\n" in nm and " T sns_stability_arnoldi_left\n" in nm
+    assert built_lib.sns_mass_apply_transpose.argtypes == [H, P, P, P] and built_lib.sns_mass_apply_transpose.restype == C.c_int
+    assert built_lib.sns_stability_arnoldi_left.argtypes == [H, P, D, C.c_int, D, P, P, I, I, I]
+    assert built_lib.sns_stability_arnoldi_left.restype == C.c_int
+    buf = (C.c_double * 16)()
+    a = C.addressof(buf)
+    k = C.c_int()
+    assert built_lib.sns_mass_apply_transpose(None, a, a, a) == E_ARG
+    assert b"sns_mass_apply_transpose: null" in built_lib.sns_last_error()
+    assert built_lib.sns_stability_arnoldi_left(None, a, 0.0, 4, 1e-6, a, a, C.byref(k), C.byref(k), C.byref(k)) == E_ARG
+    assert b"sns_stability_arnoldi_left: null" in built_lib.sns_last_error()
+    assert built_lib.sns_abi_version() == 8
+
+
+def test_stability_result_keeps_its_fields():
+    """The left-mode fields of StabilityResult come after the existing ones and default to 'absent'."""
+    r = S.StabilityResult(np.zeros(0, complex), None, np.zeros(0), np.zeros(0, bool), 0, 0, 1)
+    assert r.left_modes is None and r.left_converged is None and r.shift == 0.0
+    with pytest.raises(ValueError):
+        S.structural_sensitivity(None, None, r, 0)
