@@ -468,8 +468,26 @@ SNS_API int sns_error_indicator(sns_handle h, const double* w_dev, const double*
  *   set up, each step is one transposed mass pass and one Krylov solve.  On return the operator is transposed back and the
  *   hierarchy marked stale (as sns_adjoint_solve does; after a solve that did not converge too, not after SNS_E_HIP), the time
  *   term is cleared: the handle holds J + shift B, untransposed, and its form is steady.  Errors as sns_stability_arnoldi.
- * Not built: restarted or Krylov-Schur iterations, complex or negative shifts, the sensitivity of an eigenvalue to a steady
- * forcing (it needs the Hessian of the residual). */
+ * sns_jacobian_state_gradient: the Hessian pass.  For real dof vectors x, z and real scalars c_jac, c_mass,
+ *   g_k = sum_ij z~_i x~_j d( c_jac J_ij(w) + c_mass B_ij(w) ) / d w_k  on the unconstrained dofs k and 0 on the constrained
+ *   ones: g = grad_w [ z~^T (c_jac J(w) + c_mass B(w)) x~ ] with x~, z~ held fixed -- J = dR_raw/dw of the handle's steady form
+ *   (form variant, corrected_convection, nu constant or the viscosity field held fixed), B the operator above, x~ and z~ the
+ *   vectors with every constrained entry (all four mask bytes of a node, the pressure's too) read as 0.  Pressure rows of g
+ *   are not zero in general (the SUPG / PSPG terms tau(u) grad p . (..u..) couple p and u at second order); the viscous term is
+ *   linear in u and drops out.  With a left and a right mode of lambda scaled to z^T B x = 1 the sensitivity of lambda to the
+ *   base flow is grad_w lambda = -(H_J(z, x) + lambda H_B(z, x)), four real pairs of passes (solver.py:
+ *   eigenvalue_base_flow_sensitivity), and to a steady forcing B^T J^-T grad_w lambda + D_w[B^T z][x]
+ *   (eigenvalue_forcing_sensitivity).  One lane per tet differentiates the cell's scalar by hand, tangent along x then reverse
+ *   mode; 16 values per tet go to the handle's element scratch and are gathered per row in the fixed order of the node ->
+ *   cell lists: no atomics, bitwise reproducible, and doubling both coefficients doubles every bit.  Nothing of the handle
+ *   besides the element scratch is written: operator, hierarchy, form and damping state stay what they were.
+ *   SNS_E_ARG: null handle / pointer, a 2-D handle, a coefficient that is not finite.  SNS_E_STATE, the handle untouched: a
+ *   communicator attached, a viscosity law, a time term, a body force (J then depends on f through dM/dw(w, -f), a second
+ *   contraction that is not built) or a backflow coefficient (sns_set_boundary_flow: quadratic in u, its Hessian is not built)
+ *   set.  A boundary traction alone (constant in w) and a viscosity field are allowed.
+ * Not built: restarted or Krylov-Schur iterations, complex or negative shifts; of the sensitivities, base flows with a body
+ * force or a backflow term, the sensitivity to forcing on Dirichlet nodes, and the exact form of E = D_w[B^T z][x] (the
+ * forcing sensitivity takes it by a central difference of sns_mass_apply_transpose). */
 SNS_API int sns_mass_apply(sns_handle h, const double* w_dev, const double* x_dev, double* y_dev);
 SNS_API int sns_stability_arnoldi(sns_handle h, const double* w_dev, double shift, int m, double breakdown_rel,
                                   double* V_dev /* (m+1) * 4*n_local; column 0 = start vector on entry */,
@@ -478,6 +496,8 @@ SNS_API int sns_mass_apply_transpose(sns_handle h, const double* w_dev, const do
 SNS_API int sns_stability_arnoldi_left(sns_handle h, const double* w_dev, double shift, int m, double breakdown_rel,
                                        double* V_dev /* (m+1) * 4*n_local; column 0 = start vector on entry */,
                                        double* H_host /* (m+1) x m, row major */, int* m_done, int* total_ksp_its, int* reason);
+SNS_API int sns_jacobian_state_gradient(sns_handle h, const double* w_dev, const double* x_dev, const double* z_dev,
+                                        double c_jac, double c_mass, double* g_dev);
 /* MatMult with the assembled operator: y = A x (halo exchange inside).  Acts on whatever
  * the handle holds: y = A^T x after sns_transpose_operator.                   */
 SNS_API int sns_spmv(sns_handle h, const double* x_dev, double* y_dev);

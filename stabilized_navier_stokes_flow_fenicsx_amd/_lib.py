@@ -120,6 +120,7 @@ _SIGNATURES = [
     ("sns_mass_apply_transpose", C.c_int, [_H, _P, _P, _P]),
     ("sns_stability_arnoldi_left", C.c_int, [_H, _P, C.c_double, C.c_int, C.c_double, _P, _P, C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("sns_jacobian_state_gradient", C.c_int, [_H, _P, _P, _P, C.c_double, C.c_double, _P]),
     ("sns_scalar_system", C.c_int, [_H, _P, C.POINTER(C.c_double), C.c_double, C.c_double, _P, _P, _P, _P]),
     ("sns_scalar_solve", C.c_int, [_H, _P, C.POINTER(C.c_double), C.c_double, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_int),
                                    C.POINTER(C.c_int), C.POINTER(C.c_double)]),

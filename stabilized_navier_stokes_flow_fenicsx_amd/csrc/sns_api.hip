@@ -577,6 +577,20 @@ int sns_mass_apply_transpose(sns_handle h, const double* w, const double* z, dou
     return mass_apply_transpose(h, w, z, y);
 }
 
+int sns_jacobian_state_gradient(sns_handle h, const double* w, const double* x, const double* z, double c_jac, double c_mass,
+                                double* g) {
+    if (!h || !w || !x || !z || !g) { set_error("sns_jacobian_state_gradient: null handle or pointer"); return SNS_E_ARG; }
+    const FormState& S = h->form;
+    const policy::FormVerdict v = policy::check_state_gradient_request(
+        {h->dim, h->comm != nullptr, S.tt_on, S.vl_on, S.bf_on, S.ev_on, h->bnd.nf > 0 && h->bnd.t_on, h->bnd.nf > 0 && h->bnd.beta_on},
+        c_jac, c_mass);
+    if (v.error != SNS_OK) {
+        set_error(std::string("sns_jacobian_state_gradient: ") + v.tail);
+        return v.error;
+    }
+    return jacobian_state_gradient(h, w, x, z, c_jac, c_mass, g);
+}
+
 // both Arnoldi entry points behind their checks.  left: the operator is flipped between the assembly and the set-up and flipped
 // back afterwards with the hierarchy marked stale, as sns_adjoint_solve does
 static int stability_arnoldi(sns_ctx* h, bool left, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,

@@ -325,6 +325,8 @@ int mass_apply(sns_ctx* h, const double* w, const double* x, double* y);
 int mass_apply_transpose(sns_ctx* h, const double* w, const double* z, double* y);
 int arnoldi_run(sns_ctx* h, const double* w, bool left, int m, double breakdown_rel, double* V, double* H, int* m_done,
                 int* total_its, int* reason);
+// csrc/sns_hessian.hip: g = grad_w [ z~^T (c_jac J(w) + c_mass B(w)) x~ ] by one element pass (uses the element scratch Fe)
+int jacobian_state_gradient(sns_ctx* h, const double* w, const double* x, const double* z, double c_jac, double c_mass, double* g);
 // csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)
 int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sigma, double theta, const double* src,
                   const uint8_t* cmask, const double* cval, double* rhs);

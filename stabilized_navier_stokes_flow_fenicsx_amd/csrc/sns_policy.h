@@ -569,6 +569,28 @@ inline FormVerdict check_stability_request(StabilityRequest request, const Stabi
     return {};
 }
 
+// ---- what a handle allows of the Hessian pass (csrc/sns_hessian.hip; tests/state_gradient_request_main.cpp) ------------------------
+// sns_jacobian_state_gradient in a function of its own, in the idiom above: argument errors first (the dimension, finite
+// coefficients), then the state.  Refused: a communicator, a viscosity law, a time term, a body force (J then depends on f through
+// dM/dw(w, -f): a second contraction that is not built) and a backflow coefficient on the boundary facets (that term is
+// quadratic in u; its Hessian is not built).  Allowed: a viscosity field (the viscous term stays linear in u) and a boundary
+// traction alone (constant in w).
+struct StateGradientFacts {
+    int dim = 3;
+    bool partitioned = false, tt_on = false, vl_on = false, bf_on = false, ev_on = false;
+    bool traction_on = false, backflow_on = false;
+};
+inline FormVerdict check_state_gradient_request(const StateGradientFacts& f, double c_jac = 1.0, double c_mass = 0.0) {
+    if (f.dim != 3) return {SNS_E_ARG, "3-D handles only"};
+    if (!(c_jac - c_jac == 0.0) || !(c_mass - c_mass == 0.0)) return {SNS_E_ARG, "the coefficients must be finite"};
+    if (f.partitioned) return {SNS_E_STATE, "not with a communicator attached (the partitioned Hessian pass is not built)"};
+    if (f.vl_on) return {SNS_E_STATE, "not with a viscosity law set (the second derivative of nu_e is not built)"};
+    if (f.tt_on) return {SNS_E_STATE, "not with a time term set (the pass is taken on the steady form)"};
+    if (f.bf_on) return {SNS_E_STATE, "not with a body force set (J depends on f through the stabilisation's weighting: that contraction is not built)"};
+    if (f.backflow_on) return {SNS_E_STATE, "not with a backflow coefficient set (the Hessian of the backflow term is not built)"};
+    return {};
+}
+
 // ---- which operator is it? (the spectral estimates of csrc/sns_damping.hip; the cases are in DESIGN.md) -----------------------------
 // What the fine operator's values depend on beside the state: the form's share (FormKey: time term, viscosity law, and a counter
 // that moves whenever the viscosity field is written or cleared, another that moves whenever a boundary coefficient -- the

@@ -27,8 +27,10 @@
 //   arnoldi_run    with `left` the same process on S_L = (J + s B)^-T B^T: the mass pass is the transposed one, the operator
 //                  the handle holds is the transposed one (the entry point flips it and flips it back); nothing else differs.
 //                  Its Ritz vectors z satisfy z^T J = -lambda z^T B; the matrices are real, the pairing is z^T B x unconjugated.
-// Out of scope: restarted or Krylov-Schur iterations; complex or negative shifts; sensitivity to a steady forcing (it needs the
-// Hessian of the residual); 2-D and partitioned handles; the Carreau law.
+// The sensitivity of an eigenvalue to the base flow and to a steady forcing contracts the modes with the Hessian of the residual:
+// csrc/sns_hessian.hip.  Out of scope: restarted or Krylov-Schur iterations; complex or negative shifts; of the sensitivities,
+// base flows with a body force or a backflow term, forcing on Dirichlet nodes and the exact form of E = D_w[B^T z][x]; 2-D and
+// partitioned handles; the Carreau law.
 #include "sns_ctx.h"
 
 namespace sns {

@@ -571,8 +571,9 @@ def _stability(P, w):
     n_modes, shift = int(parts[0]), (float(parts[1]) if len(parts) > 1 else 0.0)
     from .solver import SnsError, linear_stability, print_stability
     sens = os.environ.get("SNS_STABILITY_SENSITIVITY", "0") == "1"
+    forcing = os.environ.get("SNS_STABILITY_FORCING", "0") == "1"
     try:
-        res = linear_stability(P, w, n_modes=n_modes, shift=shift, left=True) if sens else linear_stability(P, w, n_modes=n_modes, shift=shift)
+        res = linear_stability(P, w, n_modes=n_modes, shift=shift, left=True) if sens or forcing else linear_stability(P, w, n_modes=n_modes, shift=shift)
     except SnsError as e:                                 # (a viscosity law, a 2-D problem: the library says which)
         if _rank() == 0:
             print(f"SNS_STABILITY: skipped ({e})", flush=True)
@@ -580,6 +581,8 @@ def _stability(P, w):
     print_stability(res, _rank())
     if sens:
         _stability_sensitivity(P, w, res)
+    if forcing:
+        _stability_forcing(P, w, res)
     return res
 
 
@@ -609,9 +612,43 @@ def _stability_sensitivity(P, w, res):
               f"Re_c estimate = {Re_c:.6e}", flush=True)
 
 
+def _stability_forcing(P, w, res):
+    """SNS_STABILITY_FORCING=1 beside SNS_STABILITY: for the leading converged mode that has a left partner, the sensitivity of
+    its eigenvalue to a steady body force (``solver.eigenvalue_forcing_sensitivity`` as a nodal density) as
+    ``res.forcing_sensitivity`` (numpy complex, n_nodes x 3: the real part moves the growth rate, the imaginary part the
+    frequency), which the script writes as ...GrowthRateForcingSensitivity and ...FrequencyForcingSensitivity fields beside the
+    ...Wavemaker field, and one printed line: the node and position of the largest |Re grad_f lambda|."""
+    from .solver import SnsError, eigenvalue_forcing_sensitivity
+    res.forcing_sensitivity = None
+    lead = [k for k, ok in enumerate(res.left_converged) if ok]
+    if not lead:
+        if _rank() == 0:
+            print("SNS_STABILITY_FORCING: no converged mode with a converged left partner; skipped", flush=True)
+        return
+    k = lead[0]
+    try:
+        g = eigenvalue_forcing_sensitivity(P, w, res, k, density=True)
+    except (SnsError, RuntimeError) as e:                 # (a body force or a backflow term on the problem: the library says which)
+        if _rank() == 0:
+            print(f"SNS_STABILITY_FORCING: skipped ({e})", flush=True)
+        return
+    res.forcing_sensitivity = g.view(-1, 4)[:, :3].cpu().numpy()
+    if _rank() == 0:
+        mag = np.linalg.norm(res.forcing_sensitivity.real, axis=1)
+        top = int(mag.argmax())
+        x = np.asarray(P.mesh.points)[top]
+        lam = res.eigenvalues[k]
+        print(f"Stability forcing sensitivity: lambda = {lam.real:+.6e} {lam.imag:+.6e}i  max |Re grad_f lambda| = {mag[top]:.6e} "
+              f"at node {top}, x = ({x[0]:.6g}, {x[1]:.6g}, {x[2]:.6g})", flush=True)
+
+
 def _write_wavemaker(res, msh, path_noext):
     if res is not None and getattr(res, "wavemaker", None) is not None and _rank() == 0:
         write_xdmf(path_noext, msh, "Wavemaker", res.wavemaker)
+    if res is not None and getattr(res, "forcing_sensitivity", None) is not None and _rank() == 0:
+        for name, part in (("GrowthRateForcingSensitivity", res.forcing_sensitivity.real), ("FrequencyForcingSensitivity", res.forcing_sensitivity.imag)):
+            head, base = os.path.split(path_noext)
+            write_xdmf(os.path.join(head, base.replace("Wavemaker", name)), msh, name, np.ascontiguousarray(part))
 
 
 def _sensitivity():

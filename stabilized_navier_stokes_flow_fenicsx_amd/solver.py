@@ -380,6 +380,18 @@ class FlowProblem:
         check(self.lib.sns_mass_apply_transpose(self.h, _ptr(w), _ptr(z), _ptr(out)))
         return out
 
+    def jacobian_state_gradient(self, w, x, z, c_jac: float = 1.0, c_mass: float = 0.0, out=None) -> torch.Tensor:
+        """The Hessian pass (sns_jacobian_state_gradient): ``g = grad_w [ z~^T (c_jac J(w) + c_mass B(w)) x~ ]`` for real dof
+        vectors ``x``, ``z`` held fixed -- J the steady Jacobian of the present 3-D NS form (form variant, corrected_convection,
+        a viscosity field held fixed), B the operator of ``mass_apply``, x~ and z~ the vectors with every constrained entry read
+        as 0.  g is 0 on constrained dofs; its pressure rows are not zero in general.  One element pass, bitwise reproducible;
+        nothing of the problem besides the element scratch is written.  Refused (SnsError) with a body force, a backflow
+        coefficient, a time term or a viscosity law set; a boundary traction alone is allowed.  Single-GPU 3-D problems."""
+        w, x, z = self._vec(w), self._vec(x), self._vec(z)
+        out = self.zeros() if out is None else self._vec(out)
+        check(self.lib.sns_jacobian_state_gradient(self.h, _ptr(w), _ptr(x), _ptr(z), float(c_jac), float(c_mass), _ptr(out)))
+        return out
+
     def stability_arnoldi(self, w, shift: float = 0.0, m: int = 64, start=None, breakdown_rel: float = 1e-6, side: str = "right"):
         """``m`` steps of shift-invert Arnoldi on (J + shift B)^-1 B at the steady state ``w`` (sns_stability_arnoldi), with
         the problem's ksp / pc options for the inner solves.  Returns ``(V, H, ArnoldiResult)``: V a device tensor
@@ -1413,6 +1425,108 @@ def eigenvalue_reynolds_sensitivity(problem: FlowProblem, w, result: StabilityRe
     dlam = eigenvalue_drift(problem, w, result, k, (Jx[0] - Jx[1]) / h, (Bx[0] - Bx[1]) / h)
     Re_c = Re - lam.real / dlam.real if dlam.real != 0.0 else float("nan")
     return dlam, Re_c
+
+
+def _sensitivity_pair(problem: FlowProblem, result, k: int, pair):
+    """(lam, x, z) of mode ``k`` of ``result``, or of ``pair`` = (lam, x, z) given directly: complex device vectors."""
+    if pair is None:
+        return _mode_pair(result, k)
+    lam, x, z = pair
+
+    def dev(v):
+        v = torch.as_tensor(v).to(device=problem.device, dtype=torch.complex128).contiguous()
+        if v.numel() != problem.ndof:
+            raise ValueError(f"expected a mode of {problem.ndof} entries")
+        return v
+    return complex(lam), dev(x), dev(z)
+
+
+def _bilinear_complex(op, z, x):
+    """op(z, x) -- real, bilinear, on real device vectors -- extended to complex z and x: four passes."""
+    zr, zi, xr, xi = z.real.contiguous(), z.imag.contiguous(), x.real.contiguous(), x.imag.contiguous()
+    return torch.complex(op(zr, xr) - op(zi, xi), op(zr, xi) + op(zi, xr))
+
+
+def eigenvalue_base_flow_sensitivity(problem: FlowProblem, w, result: StabilityResult = None, k: int = 0, pair=None) -> torch.Tensor:
+    """The sensitivity of eigenvalue ``k`` of a ``linear_stability(..., left=True)`` result to the base flow, a complex device
+    vector over the dofs:
+
+        grad_w lam = -s / (z^T B x),    s = H_J(z, x) + lam H_B(z, x),    H_A(z, x) = grad_w [ z~^T A(w) x~ ]
+
+    so that the first-order drift under a change dw of the base flow (whatever causes it) is d lam = grad_w lam . dw,
+    unconjugated.  J and B are real: with z = z_r + i z_i, x = x_r + i x_i, lam = a + i b this is
+    ``jacobian_state_gradient`` on four real pairs, each with (c_jac, c_mass) = (1, a) and (0, b) -- eight passes.  Entries of
+    constrained dofs are 0.  ``pair=(lam, x, z)`` supplies a mode directly instead of ``result`` / ``k``.  Nothing of the
+    problem is changed."""
+    lam, x, z = _sensitivity_pair(problem, result, k, pair)
+    w = problem._vec(w)
+    a, b = lam.real, lam.imag
+    s1 = _bilinear_complex(lambda zz, xx: problem.jacobian_state_gradient(w, xx, zz, 1.0, a), z, x)
+    sb = _bilinear_complex(lambda zz, xx: problem.jacobian_state_gradient(w, xx, zz, 0.0, b), z, x)
+    s = s1 + 1j * sb                                         # H_J + a H_B + i b H_B
+    return -s / mode_pairing(problem, w, z, x)
+
+
+def lumped_volumes(mesh) -> np.ndarray:
+    """Per node a quarter of the incident tets' volumes (host, from the mesh)."""
+    X = np.asarray(mesh.points, dtype=np.float64)[np.asarray(mesh.tets)]
+    vol = np.abs(np.linalg.det(np.stack([X[:, 1] - X[:, 0], X[:, 2] - X[:, 0], X[:, 3] - X[:, 0]], axis=2))) / 6.0
+    out = np.zeros(len(mesh.points))
+    np.add.at(out, np.asarray(mesh.tets).reshape(-1), np.repeat(0.25 * vol, 4))
+    return out
+
+
+def eigenvalue_forcing_sensitivity(problem: FlowProblem, w, result: StabilityResult = None, k: int = 0, pair=None,
+                                   fd_rel: float = 1e-5, density: bool = False, ksp_rtol: float = 1e-10) -> torch.Tensor:
+    """The sensitivity of eigenvalue ``k`` to a steady body force (passive control: where to push the flow, or where to put
+    a small body, to move the eigenvalue), a complex device vector of 4 n entries with the pressure slots 0:
+
+        grad_f lam = B^T J^-T grad_w lam  +  E / (z^T B x),        E = D_w[ B(w)^T z ][x],
+
+    so that d lam = grad_f lam . df to first order for a nodal force df as ``set_body_force`` takes it, the re-converged base
+    flow included.  dR/df = -B(w) gives dw = J^-1 B df and the first term (``eigenvalue_base_flow_sensitivity``); the Jacobian
+    also depends on f explicitly, dJ/df[df] = -D_w[B(w) df] -- the stabilisation's own dependence on u in the weighting of f,
+    with no counterpart in the continuous theory -- which is the second term.  It is not small on coarse meshes.
+
+    This holds for forces that vanish on velocity-constrained dofs: the mass passes read those entries as 0, the result is 0
+    there, and the sensitivity to forcing on Dirichlet nodes is not computed.
+
+    J^-T is two ``adjoint_solve`` calls (real and imaginary part) on J(w), which is assembled here, with the inner tolerance
+    ``ksp_rtol`` (the problem's own is restored afterwards); B^T is ``mass_apply_transpose``.  E is the one approximation in
+    the function: the central difference of ``mass_apply_transpose`` along x~ with the step ``fd_rel`` max|w_u| / max|x_u|,
+    real and imaginary parts combined bilinearly (eight passes); its error is O(step^2) on a term that is smooth in w.
+    ``density=True`` divides each node's entries by its lumped volume (``lumped_volumes``) so that maps compare across
+    meshes.  Afterwards the problem holds J(w), untransposed."""
+    lam, x, z = _sensitivity_pair(problem, result, k, pair)
+    w = problem._vec(w)
+    pairing = mode_pairing(problem, w, z, x)
+    gw = eigenvalue_base_flow_sensitivity(problem, w, pair=(lam, x, z))
+    old = problem.options.ksp_rtol
+    problem.set_options(ksp_rtol=float(ksp_rtol))
+    try:
+        problem.jacobian(w, "ns")
+        parts = []
+        for g in (gw.real.contiguous(), gw.imag.contiguous()):
+            y, res = problem.adjoint_solve(g)
+            if res.reason <= 0:
+                raise RuntimeError(f"eigenvalue_forcing_sensitivity: the adjoint solve ended with reason {res.reason}")
+            parts.append(problem.mass_apply_transpose(w, y))
+    finally:
+        problem.set_options(ksp_rtol=old)
+    first = torch.complex(parts[0], parts[1])
+    free = torch.from_numpy(problem.bc_mask == 0).to(problem.device)
+    wu = float(w.view(-1, 4)[:, :3].abs().max())
+    xu = float(torch.view_as_real(x).view(-1, 4, 2)[:, :3].abs().max())
+    h = float(fd_rel) * wu / xu
+
+    def dBt(zz, xx):
+        step = h * torch.where(free, xx, torch.zeros_like(xx))
+        return (problem.mass_apply_transpose(w + step, zz) - problem.mass_apply_transpose(w - step, zz)) / (2.0 * h)
+    out = first + _bilinear_complex(dBt, z, x) / pairing
+    if density:
+        vol = torch.from_numpy(lumped_volumes(problem.mesh)).to(problem.device)
+        out = (out.view(-1, 4) / vol[:, None]).reshape(-1)
+    return out
 
 
 def print_stability(result: StabilityResult, rank: int = 0):
