@@ -282,17 +282,41 @@ int ensure_hierarchy(sns_ctx* h, bool assembles_next = false) {
     return rc;
 }
 
-// The form state's answer to `request` (the table of policy::check_form_request) as the error of the entry point `who`.  The
-// table's dimension row (SNS_E_ARG) stands among the argument checks of some entry points, its state rows (SNS_E_STATE) after
-// them: ROWS_ARG / ROWS_STATE ask for one kind, so that a call with two things wrong reports what it always reported.
-enum FormRows { ROWS_ALL = 0, ROWS_ARG = SNS_E_ARG, ROWS_STATE = SNS_E_STATE };
-int form_allows(const sns_ctx* h, const char* who, policy::FormRequest request, FormRows rows = ROWS_ALL) {
-    const FormState& S = h->form;
-    const policy::FormVerdict v =
-        policy::check_form_request(request, {h->dim, h->comm != nullptr, S.tt_on, S.vl_on, S.bf_on, S.ev_on, h->bnd.flow_on()});
-    if (v.error == SNS_OK || (rows != ROWS_ALL && v.error != rows)) return SNS_OK;
-    set_error(std::string(who) + ": " + v.tail);
+// A verdict of csrc/sns_policy.h as the error of the entry point `who`
+int refused(const char* who, const policy::Verdict& v) {
+    if (v.error != SNS_OK) set_error(std::string(who) + ": " + v.tail);
     return v.error;
+}
+// THE gate: the handle's answer to `request` of `family` (the table policy::RULES, asked with facts_of(h)).  A family's
+// dimension row (SNS_E_ARG) stands among the argument checks of some entry points, its state rows (SNS_E_STATE) after them:
+// ROWS_ARG / ROWS_STATE ask for one kind, so that a call with two things wrong reports what it always reported.
+using policy::ROWS_ALL;
+using policy::ROWS_ARG;
+using policy::ROWS_STATE;
+int allows(const sns_ctx* h, const char* who, policy::Family family, int request, policy::Rows rows = ROWS_ALL) {
+    return refused(who, policy::check_request(family, request, facts_of(h), rows));
+}
+
+// Handle state borrowed for one call and given back at its end (sns_adjoint_solve, the Arnoldi entry points): the fine operator
+// flipped in place (`flipped`) and a time term set for the call (`time_term`).  rc: the call's result so far.  After a solve
+// that did not converge and after an argument or state error the handle gets the untransposed operator back, with the hierarchy
+// marked stale, and the steady form; the first error keeps its text.  A HIP or transport error leaves the device state
+// undefined: nothing more is queued.  (The Arnoldi entry points refuse partitioned handles, so SNS_E_COMM reaches here from
+// sns_adjoint_solve alone.)
+int give_back(sns_ctx* h, int rc, bool flipped, bool time_term) {
+    if (rc == SNS_E_HIP || rc == SNS_E_COMM || (!flipped && !time_term)) return rc;
+    const std::string err = g_err;
+    int rb = SNS_OK;
+    if (flipped) {
+        rb = transpose_operator(h);
+        pc_stale(h);
+    }
+    if (time_term) {
+        const int rt = set_time_term(h, 0.0, 0.0, nullptr);
+        if (rb == SNS_OK) rb = rt;
+    }
+    if (rc != SNS_OK) { set_error(err); return rc; }
+    return rb;
 }
 
 // the end of a linear solve whose Dirichlet rows are identity rows: the reference's ILU-preconditioned solve returns them
@@ -356,7 +380,7 @@ int sns_set_options(sns_handle h, const sns_options* o) {
 
 int sns_set_form_variant(sns_handle h, double c_inverse, double lsic_scale, double pspg_sign, int one_point_quadrature) {
     if (!h) return SNS_E_ARG;
-    SNS_TRY(form_allows(h, "sns_set_form_variant", policy::REQ_FORM_VARIANT));
+    SNS_TRY(allows(h, "sns_set_form_variant", policy::FAMILY_FORM, policy::REQ_FORM_VARIANT));
     return set_form_variant(h, c_inverse, lsic_scale, pspg_sign, one_point_quadrature);
 }
 
@@ -541,60 +565,56 @@ int sns_residual_shape_gradient(sns_handle h, int form, const double* w, const d
         set_error(form == SNS_FORM_STOKES ? "sns_residual_shape_gradient: the Stokes forms are not supported" : "bad form");
         return SNS_E_ARG;
     }
-    SNS_TRY(form_allows(h, "sns_residual_shape_gradient", policy::REQ_SHAPE_GRADIENT));
+    SNS_TRY(allows(h, "sns_residual_shape_gradient", policy::FAMILY_FORM, policy::REQ_SHAPE_GRADIENT));
     return residual_shape_gradient(h, w, lam, gX);
 }
 
 int sns_recover_gradient(sns_handle h, const double* w, double* G, double* D) {
     if (!h || !w || (!G && !D)) { set_error("sns_recover_gradient: null handle, state or both outputs null"); return SNS_E_ARG; }
-    SNS_TRY(form_allows(h, "sns_recover_gradient", policy::REQ_RECOVER_GRADIENT));
+    SNS_TRY(allows(h, "sns_recover_gradient", policy::FAMILY_FORM, policy::REQ_RECOVER_GRADIENT));
     return recover_gradient(h, w, G, D);
 }
 
 int sns_error_indicator(sns_handle h, const double* w, const double* G, double* eta2, double* gnorm2) {
     if (!h || !w || !eta2) { set_error("sns_error_indicator: null handle, state or eta2"); return SNS_E_ARG; }
-    SNS_TRY(form_allows(h, "sns_error_indicator", policy::REQ_ERROR_INDICATOR));
+    SNS_TRY(allows(h, "sns_error_indicator", policy::FAMILY_FORM, policy::REQ_ERROR_INDICATOR));
     return error_indicator(h, w, G, eta2, gnorm2);
-}
-
-// the entry points of the stability analysis (`who`: the name in front of the message)
-static int stability_request(const char* who, const sns_ctx* h, policy::StabilityRequest request, const policy::ArnoldiArgs& a = {}) {
-    const policy::FormVerdict v = policy::check_stability_request(request, {h->dim, h->comm != nullptr, h->form.tt_on, h->form.vl_on}, a);
-    if (v.error == SNS_OK) return SNS_OK;
-    set_error(std::string(who) + ": " + v.tail);
-    return v.error;
 }
 
 int sns_mass_apply(sns_handle h, const double* w, const double* x, double* y) {
     if (!h || !w || !x || !y) { set_error("sns_mass_apply: null handle or pointer"); return SNS_E_ARG; }
-    SNS_TRY(stability_request("sns_mass_apply", h, policy::SREQ_MASS_APPLY));
+    SNS_TRY(allows(h, "sns_mass_apply", policy::FAMILY_STABILITY, policy::SREQ_MASS_APPLY));
     return mass_apply(h, w, x, y);
 }
 
 int sns_mass_apply_transpose(sns_handle h, const double* w, const double* z, double* y) {
     if (!h || !w || !z || !y) { set_error("sns_mass_apply_transpose: null handle or pointer"); return SNS_E_ARG; }
-    SNS_TRY(stability_request("sns_mass_apply_transpose", h, policy::SREQ_MASS_APPLY_TRANSPOSE));
+    SNS_TRY(allows(h, "sns_mass_apply_transpose", policy::FAMILY_STABILITY, policy::SREQ_MASS_APPLY_TRANSPOSE));
     return mass_apply_transpose(h, w, z, y);
 }
 
 int sns_jacobian_state_gradient(sns_handle h, const double* w, const double* x, const double* z, double c_jac, double c_mass,
                                 double* g) {
+    const char* who = "sns_jacobian_state_gradient";
     if (!h || !w || !x || !z || !g) { set_error("sns_jacobian_state_gradient: null handle or pointer"); return SNS_E_ARG; }
-    const FormState& S = h->form;
-    const policy::FormVerdict v = policy::check_state_gradient_request(
-        {h->dim, h->comm != nullptr, S.tt_on, S.vl_on, S.bf_on, S.ev_on, h->bnd.nf > 0 && h->bnd.t_on, h->bnd.nf > 0 && h->bnd.beta_on},
-        c_jac, c_mass);
-    if (v.error != SNS_OK) {
-        set_error(std::string("sns_jacobian_state_gradient: ") + v.tail);
-        return v.error;
-    }
+    SNS_TRY(allows(h, who, policy::FAMILY_STATE_GRADIENT, policy::GREQ_STATE_GRADIENT, ROWS_ARG));
+    SNS_TRY(refused(who, policy::check_state_gradient_args(c_jac, c_mass)));
+    SNS_TRY(allows(h, who, policy::FAMILY_STATE_GRADIENT, policy::GREQ_STATE_GRADIENT, ROWS_STATE));
     return jacobian_state_gradient(h, w, x, z, c_jac, c_mass, g);
 }
 
-// both Arnoldi entry points behind their checks.  left: the operator is flipped between the assembly and the set-up and flipped
-// back afterwards with the hierarchy marked stale, as sns_adjoint_solve does
-static int stability_arnoldi(sns_ctx* h, bool left, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,
-                             int* m_done, int* total_ksp_its, int* reason) {
+// both Arnoldi entry points (`who`: the name in front of the message).  SREQ_ARNOLDI_LEFT: the operator is flipped between the
+// assembly and the set-up and given back afterwards, as sns_adjoint_solve does
+static int stability_arnoldi(const char* who, sns_ctx* h, policy::StabilityRequest request, const double* w, double shift, int m,
+                             double breakdown_rel, double* V, double* H, int* m_done, int* total_ksp_its, int* reason) {
+    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
+        set_error(std::string(who) + ": null handle or pointer");
+        return SNS_E_ARG;
+    }
+    SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_ARG));
+    SNS_TRY(refused(who, policy::check_arnoldi_args({m, shift, breakdown_rel})));
+    SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_STATE));
+    const bool left = request == policy::SREQ_ARNOLDI_LEFT;
     // J + shift B = the assembly with u_t = shift (u - u(w)): sigma = shift, theta = 0, d = -shift u(w) (pressure slots unused)
     if (shift > 0.0) {
         double* d = nullptr;
@@ -611,41 +631,18 @@ static int stability_arnoldi(sns_ctx* h, bool left, const double* w, double shif
     }
     if (rc == SNS_OK) rc = ensure_hierarchy(h);
     if (rc == SNS_OK) rc = arnoldi_run(h, w, left, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
-    // the untransposed operator and the steady form again, after a solve that did not converge and after an argument or state
-    // error of the steps above too; a HIP error leaves the device state undefined.  The assembled matrix stays J + shift B
-    if (rc == SNS_E_HIP || (!flipped && shift == 0.0)) return rc;
-    const std::string err = g_err;
-    int rb = SNS_OK;
-    if (flipped) {
-        rb = transpose_operator(h);
-        pc_stale(h);
-    }
-    if (shift != 0.0) {
-        const int rt = set_time_term(h, 0.0, 0.0, nullptr);
-        if (rb == SNS_OK) rb = rt;
-    }
-    if (rc != SNS_OK) { set_error(err); return rc; }
-    return rb;
+    return give_back(h, rc, flipped, shift > 0.0);       // (the assembled matrix stays J + shift B)
 }
 
 int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H, int* m_done,
                           int* total_ksp_its, int* reason) {
-    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
-        set_error("sns_stability_arnoldi: null handle or pointer");
-        return SNS_E_ARG;
-    }
-    SNS_TRY(stability_request("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, {m, shift, breakdown_rel}));
-    return stability_arnoldi(h, false, w, shift, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+    return stability_arnoldi("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, w, shift, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
 }
 
 int sns_stability_arnoldi_left(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,
                                int* m_done, int* total_ksp_its, int* reason) {
-    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
-        set_error("sns_stability_arnoldi_left: null handle or pointer");
-        return SNS_E_ARG;
-    }
-    SNS_TRY(stability_request("sns_stability_arnoldi_left", h, policy::SREQ_ARNOLDI_LEFT, {m, shift, breakdown_rel}));
-    return stability_arnoldi(h, true, w, shift, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+    return stability_arnoldi("sns_stability_arnoldi_left", h, policy::SREQ_ARNOLDI_LEFT, w, shift, m, breakdown_rel, V, H, m_done,
+                             total_ksp_its, reason);
 }
 
 int sns_spmv(sns_handle h, const double* x, double* y) {
@@ -695,13 +692,7 @@ int sns_adjoint_solve(sns_handle h, const double* g, double* lam, int* its, int*
     // is the handle's matrix)
     const uint8_t* mask = h->matrix_form == SNS_FORM_SCALAR ? h->sc_mask.get() : h->bc_mask.get();
     if (rc == SNS_OK) rc = solve_and_snap(h, g, lam, mask, g, its, reason, rnorm);
-    // back to A, after a solve that did not converge too; a HIP or transport error leaves the device state undefined
-    if (rc == SNS_E_HIP || rc == SNS_E_COMM) return rc;
-    const std::string err = g_err;
-    const int rb = transpose_operator(h);
-    pc_stale(h);
-    if (rc != SNS_OK) { set_error(err); return rc; }
-    return rb;
+    return give_back(h, rc, true, false);                // back to A, after a solve that did not converge too
 }
 
 
@@ -827,14 +818,14 @@ static int scalar_check(const char* who, sns_ctx* h, const double* w, const doub
                         const uint8_t* cmask, const double* cval, const void* out) {
     const std::string name(who);
     if (!h || !w || !kappa || !cmask || !cval || !out) { set_error(name + ": null handle or pointer"); return SNS_E_ARG; }
-    SNS_TRY(form_allows(h, who, policy::REQ_SCALAR, ROWS_ARG));
+    SNS_TRY(allows(h, who, policy::FAMILY_FORM, policy::REQ_SCALAR, ROWS_ARG));
     for (int k = 0; k < 4; ++k)
         if (!(kappa[k] > 0.0) || !std::isfinite(kappa[k])) { set_error(name + ": every kappa must be finite and > 0"); return SNS_E_ARG; }
     if (!(sigma >= 0.0) || !std::isfinite(sigma) || !(theta >= 0.0) || !std::isfinite(theta)) {
         set_error(name + ": sigma and theta must be finite and >= 0");
         return SNS_E_ARG;
     }
-    return form_allows(h, who, policy::REQ_SCALAR, ROWS_STATE);
+    return allows(h, who, policy::FAMILY_FORM, policy::REQ_SCALAR, ROWS_STATE);
 }
 
 int sns_scalar_system(sns_handle h, const double* w_dev, const double kappa[4], double sigma, double theta, const double* src_dev,
@@ -863,20 +854,20 @@ int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int
 int sns_set_time_term(sns_handle h, double sigma, double theta, const double* d_dev) {
     if (!h) return SNS_E_ARG;
     const policy::FormRequest req = (sigma == 0.0 && theta == 0.0 && !d_dev) ? policy::REQ_CLEAR_TIME_TERM : policy::REQ_SET_TIME_TERM;
-    SNS_TRY(form_allows(h, "sns_set_time_term", req, ROWS_ARG));
+    SNS_TRY(allows(h, "sns_set_time_term", policy::FAMILY_FORM, req, ROWS_ARG));
     if (!(sigma >= 0.0) || !std::isfinite(sigma) || !(theta >= 0.0) || !std::isfinite(theta)) {
         set_error("sns_set_time_term: sigma and theta must be finite and >= 0");
         return SNS_E_ARG;
     }
     if (sigma > 0.0 && !d_dev) { set_error("sns_set_time_term: sigma > 0 needs a history vector"); return SNS_E_ARG; }
-    SNS_TRY(form_allows(h, "sns_set_time_term", req, ROWS_STATE));
+    SNS_TRY(allows(h, "sns_set_time_term", policy::FAMILY_FORM, req, ROWS_STATE));
     return set_time_term(h, sigma, theta, d_dev);
 }
 
 int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double nu_inf_ratio) {
     if (!h) return SNS_E_ARG;
     const policy::FormRequest req = law == SNS_LAW_CARREAU ? policy::REQ_SET_CARREAU : policy::REQ_SET_NEWTONIAN;
-    SNS_TRY(form_allows(h, "sns_set_viscosity_law", req, ROWS_ARG));
+    SNS_TRY(allows(h, "sns_set_viscosity_law", policy::FAMILY_FORM, req, ROWS_ARG));
     if (law != SNS_LAW_NEWTONIAN && law != SNS_LAW_CARREAU) { set_error("sns_set_viscosity_law: unknown law"); return SNS_E_ARG; }
     if (law == SNS_LAW_CARREAU) {
         if (!(lambda >= 0.0) || !std::isfinite(lambda)) { set_error("sns_set_viscosity_law: lambda must be finite and >= 0"); return SNS_E_ARG; }
@@ -886,20 +877,20 @@ int sns_set_viscosity_law(sns_handle h, int law, double lambda, double n, double
             return SNS_E_ARG;
         }
     }
-    SNS_TRY(form_allows(h, "sns_set_viscosity_law", req, ROWS_STATE));
+    SNS_TRY(allows(h, "sns_set_viscosity_law", policy::FAMILY_FORM, req, ROWS_STATE));
     return set_viscosity_law(h, law == SNS_LAW_CARREAU, lambda, n, nu_inf_ratio);
 }
 
 int sns_element_viscosity(sns_handle h, const double* w, double* nu_dev, double* gamma_dot_dev) {
     if (!h || !w) { set_error("sns_element_viscosity: null handle or state"); return SNS_E_ARG; }
-    SNS_TRY(form_allows(h, "sns_element_viscosity", policy::REQ_ELEMENT_VISCOSITY));
+    SNS_TRY(allows(h, "sns_element_viscosity", policy::FAMILY_FORM, policy::REQ_ELEMENT_VISCOSITY));
     return element_viscosity(h, w, nu_dev, gamma_dot_dev);
 }
 
 // the three field setters (`who`: the name in front of the message)
 static int field_request(const char* who, const sns_ctx* h) {
     if (!h) { set_error(std::string(who) + ": null handle"); return SNS_E_ARG; }
-    return form_allows(h, who, policy::REQ_SET_FIELD);
+    return allows(h, who, policy::FAMILY_FORM, policy::REQ_SET_FIELD);
 }
 
 int sns_set_body_force(sns_handle h, const double* f_dev) {
@@ -923,16 +914,13 @@ int sns_set_mixture(sns_handle h, const double* m_dev, double log_viscosity_rati
 }
 
 // the three setters of the boundary terms (`who`: the name in front of the message)
-static int boundary_request(const char* who, const sns_ctx* h, policy::BoundaryRequest request) {
+static int boundary_setter(const char* who, const sns_ctx* h, policy::BoundaryRequest request) {
     if (!h) { set_error(std::string(who) + ": null handle"); return SNS_E_ARG; }
-    const policy::FormVerdict v = policy::check_boundary_request(request, {h->dim, h->comm != nullptr, h->bnd.nf > 0});
-    if (v.error == SNS_OK) return SNS_OK;
-    set_error(std::string(who) + ": " + v.tail);
-    return v.error;
+    return allows(h, who, policy::FAMILY_BOUNDARY, request);
 }
 
 int sns_set_boundary_facets(sns_handle h, int32_t n_facets, const int32_t* facets_host, const int64_t* facet_tets_host) {
-    SNS_TRY(boundary_request("sns_set_boundary_facets", h, policy::BREQ_SET_FACETS));
+    SNS_TRY(boundary_setter("sns_set_boundary_facets", h, policy::BREQ_SET_FACETS));
     if (n_facets < 0 || n_facets > (INT32_MAX - 3) / 9 || (n_facets > 0 && (!facets_host || !facet_tets_host))) {
         set_error("sns_set_boundary_facets: bad facet count or null list");
         return SNS_E_ARG;
@@ -941,12 +929,12 @@ int sns_set_boundary_facets(sns_handle h, int32_t n_facets, const int32_t* facet
 }
 
 int sns_set_boundary_flow(sns_handle h, const double* t_dev, const double* beta_dev) {
-    SNS_TRY(boundary_request("sns_set_boundary_flow", h, policy::BREQ_SET_FLOW));
+    SNS_TRY(boundary_setter("sns_set_boundary_flow", h, policy::BREQ_SET_FLOW));
     return set_boundary_flow(h, t_dev, beta_dev);
 }
 
 int sns_set_boundary_scalar(sns_handle h, const double* alpha_dev, const double* g_dev) {
-    SNS_TRY(boundary_request("sns_set_boundary_scalar", h, policy::BREQ_SET_SCALAR));
+    SNS_TRY(boundary_setter("sns_set_boundary_scalar", h, policy::BREQ_SET_SCALAR));
     return set_boundary_scalar(h, alpha_dev, g_dev);
 }
 
@@ -956,9 +944,9 @@ int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, 
     if (order != 1 && order != 2) { set_error("sns_time_step: order must be 1 or 2"); return SNS_E_ARG; }
     if (!(dt > 0.0) || !std::isfinite(dt)) { set_error("sns_time_step: dt must be positive"); return SNS_E_ARG; }
     if (order == 2 && !wprev) { set_error("sns_time_step: BDF2 needs the state before w"); return SNS_E_ARG; }
-    SNS_TRY(form_allows(h, "sns_time_step", policy::REQ_TIME_STEP, ROWS_ARG));
+    SNS_TRY(allows(h, "sns_time_step", policy::FAMILY_FORM, policy::REQ_TIME_STEP, ROWS_ARG));
     if (!(theta_coeff >= 0.0) || !std::isfinite(theta_coeff)) { set_error("sns_time_step: theta_coeff must be finite and >= 0"); return SNS_E_ARG; }
-    SNS_TRY(form_allows(h, "sns_time_step", policy::REQ_TIME_STEP, ROWS_STATE));
+    SNS_TRY(allows(h, "sns_time_step", policy::FAMILY_FORM, policy::REQ_TIME_STEP, ROWS_STATE));
     const int64_t ld = ld_of(h);
     const int g = vec_grid(ld);
     // BDF1: u_t = (u - u^n) / dt;  BDF2: u_t = (3 u - 4 u^n + u^(n-1)) / (2 dt).  d in a workspace vector (copied by

@@ -58,7 +58,7 @@ using namespace sns;
 #define SNS_FORM_SCALAR 4
 
 // The state of the 3-D NS form beside the options: what the setters of csrc/sns_form.hip write and form_pass
-// (csrc/sns_assemble.hip) hands to the kernels.  Which switches go together is policy::check_form_request's table.
+// (csrc/sns_assemble.hip) hands to the kernels.  Which switches go together is the table policy::RULES.
 struct FormState {
     FormVariant fv;                              // sns_set_form_variant (diagnostic; default = the reference's form)
     // sns_set_time_term: the transient form.  tt.d points at tt_d, the handle's copy of the history (4*n doubles, allocated at
@@ -378,6 +378,13 @@ inline int sync_stream(sns_ctx* h) {
 
 // the operator behind the preconditioner changed (a setter altered a value, the values were transposed): the next solve sets up
 inline void pc_stale(sns_ctx* h) { h->pc_ready = false; }
+
+// the facts every request rule of policy::RULES is asked with: the one place that reads them off a handle
+inline policy::HandleFacts facts_of(const sns_ctx* h) {
+    const FormState& S = h->form;
+    const BoundaryState& B = h->bnd;
+    return {h->dim, h->comm != nullptr, S.tt_on, S.vl_on, S.bf_on, S.ev_on, B.nf > 0, B.nf > 0 && B.t_on, B.nf > 0 && B.beta_on};
+}
 
 
 inline void time_begin(sns_ctx* h, int mode, hipStream_t st = nullptr) {

@@ -4,9 +4,9 @@
 // hipGraph.  Pure host code over (options, a few global counts): no HIP, no handle, so that the table can be unit-tested on the
 // CPU (sns_host_cycle_policy, tests/test_host.py) and every rank of a partitioned run answers alike by construction.
 // The handle-side predicates of csrc/sns_cycle.hip / sns_setup.hip gather the facts and ask here; the numbers live nowhere else.
-// In the same idiom, at the end: the route of an assembly (plan_assembly, tests/assembly_plan_main.cpp), what a handle's form
-// state allows (check_form_request, tests/form_request_main.cpp) and what it allows of the boundary terms (check_boundary_request,
-// tests/boundary_request_main.cpp), which operator is a new one (OperatorKey, tests/operator_key_main.cpp), the damping of a
+// In the same idiom, at the end: the route of an assembly (plan_assembly, tests/assembly_plan_main.cpp), what a handle's state
+// allows of every entry point that can refuse (HandleFacts and the one table RULES, tests/request_main.cpp), which operator is
+// a new one (OperatorKey, tests/operator_key_main.cpp), the damping of a
 // level's smoother (LevelDamping, tests/damping_policy_main.cpp), what a kernel of a solve hands to a later one (Handoff,
 // tests/handoff_main.cpp), what a solve and a set-up may leave out of their fixed cost (plan_step, tests/step_plan_main.cpp).
 #pragma once
@@ -435,160 +435,162 @@ inline AssemblyPlan plan_assembly(const AssemblyFacts& f, bool violated = true) 
     return p;
 }
 
-// ---- what a handle's form state allows (csrc/sns_form.hip; the matrix is in DESIGN.md) ---------------------------------------------
-// Facts: the handle (dim, a communicator attached) and the switches of the 3-D NS form that are on -- time term, viscosity law,
-// body force, viscosity field, and a boundary traction or backflow coefficient (sns_set_boundary_flow).
-struct FormFacts {
+// ---- what a handle's state allows (asked by the entry points of csrc/sns_api.hip; the table is in DESIGN.md, "Form state") ----------
+// Facts: the handle (dim, a communicator attached), the switches of the 3-D NS form that are on -- time term, viscosity law, body
+// force, viscosity field --, whether boundary facets are set, and a traction / a backflow coefficient set on facets that exist
+// ("a boundary flow term is on" is either of the two: HAS_BOUNDARY_FLOW).  Built from a handle in one place (facts_of,
+// csrc/sns_ctx.h) for every family of requests; a family reads the facts its rows name and no other.
+struct HandleFacts {
     int dim = 3;
     bool partitioned = false, tt_on = false, vl_on = false, bf_on = false, ev_on = false;
-    bool boundary_flow_on = false;
+    bool has_facets = false, traction_on = false, backflow_on = false;
 };
+enum FactBit {
+    IS_NOT_3D = 1, IS_PARTITIONED = 2, HAS_TIME_TERM = 4, HAS_LAW = 8, HAS_FORCE = 16, HAS_FIELD = 32, NO_FACETS = 64, HAS_TRACTION = 128,
+    HAS_BACKFLOW = 256, HAS_BOUNDARY_FLOW = HAS_TRACTION | HAS_BACKFLOW
+};
+// The families: the setters and passes of the 3-D NS form; the three setters of the facet terms (csrc/sns_boundary.hip); the
+// stability analysis (csrc/sns_stability.hip) -- SREQ_COUNT is the number of right-hand kinds, SREQ_KINDS counts all: the
+// left-hand kinds (sns_mass_apply_transpose, sns_stability_arnoldi_left) follow the right-hand ones and are refused exactly as
+// those are --; the Hessian pass (sns_jacobian_state_gradient, csrc/sns_hessian.hip), one request.
+enum Family { FAMILY_FORM = 0, FAMILY_BOUNDARY, FAMILY_STABILITY, FAMILY_STATE_GRADIENT };
 enum FormRequest {
     REQ_SET_TIME_TERM = 0, REQ_CLEAR_TIME_TERM, REQ_SET_CARREAU, REQ_SET_NEWTONIAN, REQ_SET_FIELD /* set or clear: force, viscosity, mixture */,
     REQ_TIME_STEP, REQ_SHAPE_GRADIENT, REQ_RECOVER_GRADIENT, REQ_ERROR_INDICATOR, REQ_SCALAR /* system or solve */,
     REQ_ELEMENT_VISCOSITY /* the query */, REQ_FORM_VARIANT, REQ_COUNT
 };
+enum BoundaryRequest { BREQ_SET_FACETS = 0, BREQ_SET_FLOW, BREQ_SET_SCALAR, BREQ_COUNT };
+enum StabilityRequest { SREQ_MASS_APPLY = 0, SREQ_ARNOLDI, SREQ_COUNT, SREQ_MASS_APPLY_TRANSPOSE = SREQ_COUNT, SREQ_ARNOLDI_LEFT, SREQ_KINDS };
+constexpr int GREQ_STATE_GRADIENT = 0;
 // error != SNS_OK: refused; the entry point's message is its name, ": " and `tail`
-struct FormVerdict {
+struct Verdict {
     int error = SNS_OK;
     const char* tail = "";
 };
-enum FormFactBit { IS_NOT_3D = 1, IS_PARTITIONED = 2, HAS_TIME_TERM = 4, HAS_LAW = 8, HAS_FORCE = 16, HAS_FIELD = 32, HAS_BOUNDARY_FLOW = 64 };
-// A request is refused by its first row with one of `any_of` true.  Asymmetries kept as they grew: a Newtonian law
-// is refused under a time term though it sets nothing, and allowed under a force or a field; CLEARING a field is refused
-// while a law is set; the shape gradient and the two recovery requests never ask for the dimension.
-struct FormRule {
-    FormRequest request;
+// A request is refused by its first row with one of `any_of` true; in every family the SNS_E_ARG rows (the dimension) stand
+// before the SNS_E_STATE rows.  Asymmetries kept as they grew: a Newtonian law is refused under a time term though
+// it sets nothing, and allowed under a force or a field; CLEARING a field is refused while a law is set; the shape gradient
+// and the two recovery requests never ask for the dimension; setting or clearing facets never needs facets; the mass pass
+// ignores a time term (B is taken at theta = 0 and u_t = 0 whatever the handle's history) while the Arnoldi process sets its
+// own; the Hessian pass allows a viscosity field (the viscous term stays linear in u) and a traction alone (constant in w), and
+// refuses a body force (J then depends on f through dM/dw(w, -f): a second contraction that is not built) and a backflow
+// coefficient (that term is quadratic in u; its Hessian is not built).
+struct Rule {
+    Family family;
+    int request;
     unsigned any_of;
-    int error;
+    int code;
     const char* tail;
 };
-constexpr FormRule FORM_RULES[] = {
-    {REQ_SET_TIME_TERM, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {REQ_SET_TIME_TERM, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
-    {REQ_SET_TIME_TERM, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the transient form has no law)"},
-    {REQ_CLEAR_TIME_TERM, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {REQ_CLEAR_TIME_TERM, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
-    {REQ_SET_CARREAU, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {REQ_SET_CARREAU, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no law)"},
-    {REQ_SET_CARREAU, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the transient form has no law)"},
-    {REQ_SET_CARREAU, HAS_FORCE | HAS_FIELD, SNS_E_STATE, "not with a body force or a viscosity field set"},
-    {REQ_SET_NEWTONIAN, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {REQ_SET_NEWTONIAN, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no law)"},
-    {REQ_SET_NEWTONIAN, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the transient form has no law)"},
-    {REQ_SET_FIELD, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {REQ_SET_FIELD, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no external fields)"},
-    {REQ_SET_FIELD, HAS_LAW, SNS_E_STATE, "not with a viscosity law set"},
-    {REQ_TIME_STEP, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {REQ_TIME_STEP, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
-    {REQ_TIME_STEP, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the transient form has no law)"},
-    {REQ_SHAPE_GRADIENT, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned shape gradients are not built)"},
-    {REQ_SHAPE_GRADIENT, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the mesh derivative of nu_e is not built)"},
-    {REQ_SHAPE_GRADIENT, HAS_FORCE | HAS_FIELD, SNS_E_STATE,
+constexpr Rule RULES[] = {
+    {FAMILY_FORM, REQ_SET_TIME_TERM, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_SET_TIME_TERM, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
+    {FAMILY_FORM, REQ_SET_TIME_TERM, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the transient form has no law)"},
+    {FAMILY_FORM, REQ_CLEAR_TIME_TERM, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_CLEAR_TIME_TERM, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
+    {FAMILY_FORM, REQ_SET_CARREAU, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_SET_CARREAU, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no law)"},
+    {FAMILY_FORM, REQ_SET_CARREAU, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the transient form has no law)"},
+    {FAMILY_FORM, REQ_SET_CARREAU, HAS_FORCE | HAS_FIELD, SNS_E_STATE, "not with a body force or a viscosity field set"},
+    {FAMILY_FORM, REQ_SET_NEWTONIAN, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_SET_NEWTONIAN, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no law)"},
+    {FAMILY_FORM, REQ_SET_NEWTONIAN, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the transient form has no law)"},
+    {FAMILY_FORM, REQ_SET_FIELD, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_SET_FIELD, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned handles have no external fields)"},
+    {FAMILY_FORM, REQ_SET_FIELD, HAS_LAW, SNS_E_STATE, "not with a viscosity law set"},
+    {FAMILY_FORM, REQ_TIME_STEP, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_TIME_STEP, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned time stepping is not built)"},
+    {FAMILY_FORM, REQ_TIME_STEP, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the transient form has no law)"},
+    {FAMILY_FORM, REQ_SHAPE_GRADIENT, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned shape gradients are not built)"},
+    {FAMILY_FORM, REQ_SHAPE_GRADIENT, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the mesh derivative of nu_e is not built)"},
+    {FAMILY_FORM, REQ_SHAPE_GRADIENT, HAS_FORCE | HAS_FIELD, SNS_E_STATE,
      "not with a body force or a viscosity field set (the mesh derivative is not built with them)"},
-    {REQ_SHAPE_GRADIENT, HAS_BOUNDARY_FLOW, SNS_E_STATE,
+    {FAMILY_FORM, REQ_SHAPE_GRADIENT, HAS_BOUNDARY_FLOW, SNS_E_STATE,
      "not with a boundary traction or backflow term set (the mesh derivative of the facet terms is not built)"},
-    {REQ_RECOVER_GRADIENT, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned gradient recovery is not built)"},
-    {REQ_ERROR_INDICATOR, IS_PARTITIONED, SNS_E_STATE,
+    {FAMILY_FORM, REQ_RECOVER_GRADIENT, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned gradient recovery is not built)"},
+    {FAMILY_FORM, REQ_ERROR_INDICATOR, IS_PARTITIONED, SNS_E_STATE,
      "not with a communicator attached (a partitioned indicator needs a halo exchange of G)"},
-    {REQ_SCALAR, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {REQ_SCALAR, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned scalar transport is not built)"},
-    {REQ_ELEMENT_VISCOSITY, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {REQ_FORM_VARIANT, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_SCALAR, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_SCALAR, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned scalar transport is not built)"},
+    {FAMILY_FORM, REQ_ELEMENT_VISCOSITY, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_FORM, REQ_FORM_VARIANT, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+
+    {FAMILY_BOUNDARY, BREQ_SET_FACETS, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_BOUNDARY, BREQ_SET_FACETS, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
+    {FAMILY_BOUNDARY, BREQ_SET_FLOW, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_BOUNDARY, BREQ_SET_FLOW, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
+    {FAMILY_BOUNDARY, BREQ_SET_FLOW, NO_FACETS, SNS_E_STATE, "set the boundary facets first (sns_set_boundary_facets)"},
+    {FAMILY_BOUNDARY, BREQ_SET_SCALAR, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_BOUNDARY, BREQ_SET_SCALAR, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
+    {FAMILY_BOUNDARY, BREQ_SET_SCALAR, NO_FACETS, SNS_E_STATE, "set the boundary facets first (sns_set_boundary_facets)"},
+
+    {FAMILY_STABILITY, SREQ_MASS_APPLY, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_STABILITY, SREQ_MASS_APPLY, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned stability analysis is not built)"},
+    {FAMILY_STABILITY, SREQ_MASS_APPLY, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the mass operator of the law's form is not built)"},
+    {FAMILY_STABILITY, SREQ_ARNOLDI, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_STABILITY, SREQ_ARNOLDI, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned stability analysis is not built)"},
+    {FAMILY_STABILITY, SREQ_ARNOLDI, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the mass operator of the law's form is not built)"},
+    {FAMILY_STABILITY, SREQ_ARNOLDI, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the analysis sets its own and clears it)"},
+
+    {FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (the partitioned Hessian pass is not built)"},
+    {FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the second derivative of nu_e is not built)"},
+    {FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the pass is taken on the steady form)"},
+    {FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, HAS_FORCE, SNS_E_STATE,
+     "not with a body force set (J depends on f through the stabilisation's weighting: that contraction is not built)"},
+    {FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, HAS_BACKFLOW, SNS_E_STATE,
+     "not with a backflow coefficient set (the Hessian of the backflow term is not built)"},
 };
 
-inline FormVerdict check_form_request(FormRequest request, const FormFacts& f) {
+// The one lookup.  An entry point's own value checks stand between the family's SNS_E_ARG rows and its SNS_E_STATE rows:
+// ROWS_ARG / ROWS_STATE ask for the verdict only where it is of that kind, so that a call with two things wrong reports what it
+// always reported.
+enum Rows { ROWS_ALL = 0, ROWS_ARG = SNS_E_ARG, ROWS_STATE = SNS_E_STATE };
+inline Verdict check_request(Family family, int request, const HandleFacts& f, Rows rows = ROWS_ALL) {
+    if (family == FAMILY_STABILITY && request >= SREQ_COUNT) request -= SREQ_COUNT;      // the left-hand kinds: the right-hand rows
     const unsigned facts = (f.dim != 3) * IS_NOT_3D | f.partitioned * IS_PARTITIONED | f.tt_on * HAS_TIME_TERM | f.vl_on * HAS_LAW |
-                           f.bf_on * HAS_FORCE | f.ev_on * HAS_FIELD | f.boundary_flow_on * HAS_BOUNDARY_FLOW;
-    for (const FormRule& r : FORM_RULES)
-        if (r.request == request && (facts & r.any_of)) return {r.error, r.tail};
+                           f.bf_on * HAS_FORCE | f.ev_on * HAS_FIELD | (!f.has_facets) * NO_FACETS | f.traction_on * HAS_TRACTION |
+                           f.backflow_on * HAS_BACKFLOW;
+    for (const Rule& r : RULES)
+        if (r.family == family && r.request == request && (facts & r.any_of))
+            return (rows == ROWS_ALL || r.code == rows) ? Verdict{r.code, r.tail} : Verdict{};
     return {};
 }
-
-// ---- what a handle allows of the boundary terms (csrc/sns_boundary.hip; tests/boundary_request_main.cpp) ---------------------------
-// The three setters of the facet terms in a table of their own, in the idiom of the form requests: the handle's dimension, a
-// communicator attached, and whether facets are set (the data setters need them; setting or clearing facets never does).
-struct BoundaryFacts {
-    int dim = 3;
-    bool partitioned = false, has_facets = false;
-};
-enum BoundaryRequest { BREQ_SET_FACETS = 0, BREQ_SET_FLOW, BREQ_SET_SCALAR, BREQ_COUNT };
-enum BoundaryFactBit { B_IS_NOT_3D = 1, B_IS_PARTITIONED = 2, B_NO_FACETS = 4 };
-struct BoundaryRule {
-    BoundaryRequest request;
-    unsigned any_of;
-    int error;
-    const char* tail;
-};
-constexpr BoundaryRule BOUNDARY_RULES[] = {
-    {BREQ_SET_FACETS, B_IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {BREQ_SET_FACETS, B_IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
-    {BREQ_SET_FLOW, B_IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {BREQ_SET_FLOW, B_IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
-    {BREQ_SET_FLOW, B_NO_FACETS, SNS_E_STATE, "set the boundary facets first (sns_set_boundary_facets)"},
-    {BREQ_SET_SCALAR, B_IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
-    {BREQ_SET_SCALAR, B_IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned boundary terms are not built)"},
-    {BREQ_SET_SCALAR, B_NO_FACETS, SNS_E_STATE, "set the boundary facets first (sns_set_boundary_facets)"},
-};
-inline FormVerdict check_boundary_request(BoundaryRequest request, const BoundaryFacts& f) {
-    const unsigned facts = (f.dim != 3) * B_IS_NOT_3D | f.partitioned * B_IS_PARTITIONED | (!f.has_facets) * B_NO_FACETS;
-    for (const BoundaryRule& r : BOUNDARY_RULES)
-        if (r.request == request && (facts & r.any_of)) return {r.error, r.tail};
-    return {};
+// ... and with the verdict of the call's own arguments in its place
+inline Verdict check_request(Family family, int request, const HandleFacts& f, const Verdict& arguments) {
+    Verdict v = check_request(family, request, f, ROWS_ARG);
+    if (v.error == SNS_OK) v = arguments;
+    if (v.error == SNS_OK) v = check_request(family, request, f, ROWS_STATE);
+    return v;
 }
 
-// ---- what a handle allows of the stability analysis (csrc/sns_stability.hip; tests/stability_request_main.cpp) ----------------------
-// The two entry points in a function of their own, in the idiom of the form requests: argument errors first (the dimension, then
-// for the Arnoldi process m in [2, 64], a finite shift >= 0 and breakdown_rel in (0, 1)), then the state -- a communicator, a
-// viscosity law (the mass operator of the law's form is not built), and for the Arnoldi process a time term (it sets its own).
-// The mass pass ignores a time term: B is taken at theta = 0 and u_t = 0 whatever the handle's history.
+// The arguments of the Arnoldi process: m in [2, 64], a finite shift >= 0 and breakdown_rel in (0, 1)
 constexpr int STABILITY_M_MIN = 2, STABILITY_M_MAX = 64;
-struct StabilityFacts {
-    int dim = 3;
-    bool partitioned = false, tt_on = false, vl_on = false;
-};
 struct ArnoldiArgs {
     int m = STABILITY_M_MAX;
     double shift = 0.0, breakdown_rel = 1e-6;
 };
-// The left-hand kinds (sns_mass_apply_transpose, sns_stability_arnoldi_left; tests/stability_left_request_main.cpp) follow the
-// right-hand ones and are refused exactly as those are: SREQ_COUNT stays the number of right-hand kinds, SREQ_KINDS counts all.
-enum StabilityRequest { SREQ_MASS_APPLY = 0, SREQ_ARNOLDI, SREQ_COUNT, SREQ_MASS_APPLY_TRANSPOSE = SREQ_COUNT, SREQ_ARNOLDI_LEFT, SREQ_KINDS };
-inline FormVerdict check_stability_request(StabilityRequest request, const StabilityFacts& f, const ArnoldiArgs& a = {}) {
-    if (request == SREQ_MASS_APPLY_TRANSPOSE) request = SREQ_MASS_APPLY;
-    if (request == SREQ_ARNOLDI_LEFT) request = SREQ_ARNOLDI;
-    if (f.dim != 3) return {SNS_E_ARG, "3-D handles only"};
-    if (request == SREQ_ARNOLDI) {
-        if (a.m < STABILITY_M_MIN || a.m > STABILITY_M_MAX) return {SNS_E_ARG, "m must lie in [2, 64]"};
-        if (!(a.shift >= 0.0) || !(a.shift <= 1.7976931348623157e308)) return {SNS_E_ARG, "the shift must be finite and >= 0"};
-        if (!(a.breakdown_rel > 0.0) || !(a.breakdown_rel < 1.0)) return {SNS_E_ARG, "breakdown_rel must lie in (0, 1)"};
-    }
-    if (f.partitioned) return {SNS_E_STATE, "not with a communicator attached (partitioned stability analysis is not built)"};
-    if (f.vl_on) return {SNS_E_STATE, "not with a viscosity law set (the mass operator of the law's form is not built)"};
-    if (request == SREQ_ARNOLDI && f.tt_on) return {SNS_E_STATE, "not with a time term set (the analysis sets its own and clears it)"};
+inline Verdict check_arnoldi_args(const ArnoldiArgs& a) {
+    if (a.m < STABILITY_M_MIN || a.m > STABILITY_M_MAX) return {SNS_E_ARG, "m must lie in [2, 64]"};
+    if (!(a.shift >= 0.0) || !(a.shift <= 1.7976931348623157e308)) return {SNS_E_ARG, "the shift must be finite and >= 0"};
+    if (!(a.breakdown_rel > 0.0) || !(a.breakdown_rel < 1.0)) return {SNS_E_ARG, "breakdown_rel must lie in (0, 1)"};
+    return {};
+}
+// ... and the coefficients of the Hessian pass
+inline Verdict check_state_gradient_args(double c_jac, double c_mass) {
+    if (!(c_jac - c_jac == 0.0) || !(c_mass - c_mass == 0.0)) return {SNS_E_ARG, "the coefficients must be finite"};
     return {};
 }
 
-// ---- what a handle allows of the Hessian pass (csrc/sns_hessian.hip; tests/state_gradient_request_main.cpp) ------------------------
-// sns_jacobian_state_gradient in a function of its own, in the idiom above: argument errors first (the dimension, finite
-// coefficients), then the state.  Refused: a communicator, a viscosity law, a time term, a body force (J then depends on f through
-// dM/dw(w, -f): a second contraction that is not built) and a backflow coefficient on the boundary facets (that term is
-// quadratic in u; its Hessian is not built).  Allowed: a viscosity field (the viscous term stays linear in u) and a boundary
-// traction alone (constant in w).
-struct StateGradientFacts {
-    int dim = 3;
-    bool partitioned = false, tt_on = false, vl_on = false, bf_on = false, ev_on = false;
-    bool traction_on = false, backflow_on = false;
-};
-inline FormVerdict check_state_gradient_request(const StateGradientFacts& f, double c_jac = 1.0, double c_mass = 0.0) {
-    if (f.dim != 3) return {SNS_E_ARG, "3-D handles only"};
-    if (!(c_jac - c_jac == 0.0) || !(c_mass - c_mass == 0.0)) return {SNS_E_ARG, "the coefficients must be finite"};
-    if (f.partitioned) return {SNS_E_STATE, "not with a communicator attached (the partitioned Hessian pass is not built)"};
-    if (f.vl_on) return {SNS_E_STATE, "not with a viscosity law set (the second derivative of nu_e is not built)"};
-    if (f.tt_on) return {SNS_E_STATE, "not with a time term set (the pass is taken on the steady form)"};
-    if (f.bf_on) return {SNS_E_STATE, "not with a body force set (J depends on f through the stabilisation's weighting: that contraction is not built)"};
-    if (f.backflow_on) return {SNS_E_STATE, "not with a backflow coefficient set (the Hessian of the backflow term is not built)"};
-    return {};
+// The four families as the host tests ask them (tests/request_main.cpp)
+inline Verdict check_form_request(FormRequest request, const HandleFacts& f) { return check_request(FAMILY_FORM, request, f); }
+inline Verdict check_boundary_request(BoundaryRequest request, const HandleFacts& f) { return check_request(FAMILY_BOUNDARY, request, f); }
+inline Verdict check_stability_request(StabilityRequest request, const HandleFacts& f, const ArnoldiArgs& a = {}) {
+    const bool arnoldi = request == SREQ_ARNOLDI || request == SREQ_ARNOLDI_LEFT;
+    return check_request(FAMILY_STABILITY, request, f, arnoldi ? check_arnoldi_args(a) : Verdict{});
+}
+inline Verdict check_state_gradient_request(const HandleFacts& f, double c_jac = 1.0, double c_mass = 0.0) {
+    return check_request(FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, f, check_state_gradient_args(c_jac, c_mass));
 }
 
 // ---- which operator is it? (the spectral estimates of csrc/sns_damping.hip; the cases are in DESIGN.md) -----------------------------

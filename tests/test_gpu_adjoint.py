@@ -221,6 +221,28 @@ def test_adjoint_identity(case, opts):
     P.close()
 
 
+def test_an_unconverged_adjoint_solve_gives_the_operator_back():
+    """One BiCGStab iteration against a tolerance it cannot meet: sns_adjoint_solve returns without an error, and the handle
+    holds A again bit for bit with its hierarchy marked stale, as after a solve that converged."""
+    m = M.duct_mesh((6, 3, 3), 2.0)
+    P = FlowProblem(m, B.duct_bcs(m).flatten(), reynolds=RE_DUCT)
+    U, res = P.stokes_solve()
+    assert res.reason > 0
+    P.set_options(ksp_rtol=1e-14, ksp_max_it=1)
+    P.jacobian(U, "ns")
+    va0 = P.bsr()[2].cpu().numpy().copy()
+    g = torch.from_numpy(np.random.default_rng(5).normal(size=P.ndof)).cuda()
+    lam, ra = P.adjoint_solve(g)                                      # returns SNS_OK: no exception
+    print("reason", ra.reason, "its", ra.its, "rnorm", ra.rnorm)
+    assert ra.reason <= 0
+    assert not P.operator_transposed
+    assert np.array_equal(_bits(P.bsr()[2].cpu().numpy()), _bits(va0))
+    with pytest.raises(SnsError) as e:
+        P.pc_apply(P.zeros())
+    assert e.value.code == -3 and "pc_apply before pc_setup" in str(e.value)
+    P.close()
+
+
 # ---- sensitivities -------------------------------------------------------------------------------------------------------
 def _fd_band(J_of_re, Re, delta):
     """Central differences D(delta), D(delta / 2) of J over Re (1 +- delta), their Richardson value and the band the

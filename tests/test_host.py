@@ -6,7 +6,9 @@ import re
 import numpy as np
 import pytest
 
+import request_gate as RG
 from conftest import ROOT
+from request_gate import policy_main as _policy_main
 from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B, mesh as M
 
 
@@ -1062,28 +1064,11 @@ def test_assembly_plan_table(tmp_path):
     assert fast and all(c[0] == 3 and c[1] == NS and not c[3] and c[4] and not c[6] and c[7] and not c[8] for c in fast)
 
 
-def _policy_main(tmp_path, name):
-    """A stand-alone main over csrc/sns_policy.h (tests/<name>_main.cpp), built like the assembly plan's."""
-    import shutil
-    import subprocess
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / name)
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
-                            "-I", os.path.join(ROOT, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
-                            os.path.join(ROOT, "tests", name + "_main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
-    return exe
-
-
 def test_form_request_table(tmp_path):
     """What a handle's form state refuses (csrc/sns_policy.h: policy::check_form_request, asked by the entry points of
-    csrc/sns_api.hip) for every request and all 2 x 2 x 2^4 combinations of its facts, against a transcription of the rules as
-    the entry points had them inline before the table -- in their order, with their texts -- written here and not derived from
-    the header."""
-    import itertools
-    import subprocess
-    exe = _policy_main(tmp_path, "form_request")
+    csrc/sns_api.hip) for every request and all 2 x 2^8 combinations of the handle's facts, against a transcription of the rules
+    as the entry points had them inline before the table -- in their order, with their texts -- written here and not derived
+    from the header; the shape gradient's rule of the boundary terms, the last of its request, on top of it."""
     E_ARG, E_STATE = -1, -3                                                 # include/sns.h
     (SET_TT, CLEAR_TT, SET_CARREAU, SET_NEWTONIAN, SET_FIELD, TIME_STEP, SHAPE, RECOVER, INDICATOR, SCALAR, ELEMENT_VISCOSITY,
      VARIANT) = REQUESTS = range(12)                                        # policy::FormRequest
@@ -1123,15 +1108,22 @@ def test_form_request_table(tmp_path):
             checks = [(dim != 3, E_ARG, DIM)]
         return next(((code, tail) for cond, code, tail in checks if cond), (0, ""))
 
-    combos = list(itertools.product(REQUESTS, (2, 3), *[(0, 1)] * 5))
-    assert len(combos) == 12 * 64
-    run = subprocess.run([exe], input="".join(" ".join(map(str, c)) + "\n" for c in combos), capture_output=True, text=True)
-    assert run.returncode == 0, run.returncode
-    lines = run.stdout.split("\n")
-    assert int(lines[0]) == len(REQUESTS)                                  # policy::REQ_COUNT: no request the matrix leaves out
-    got = [(int(code), tail) for code, tail in (ln.split("\t") for ln in lines[1:1 + len(combos)])]
-    for c, g in zip(combos, got):
-        assert g == expected(*c), (c, g)
+    combos = [(req, f, ()) for req in REQUESTS for f in RG.FACTS]
+    assert len(combos) == 12 * 2 * 2 ** 8
+    header, rows = RG.ask(tmp_path, "f", combos)
+    assert header["REQ_COUNT"] == len(REQUESTS)                            # policy::REQ_COUNT: no request the matrix leaves out
+    got = [(int(code), tail) for code, tail in rows]
+    # the boundary flow is a traction or a backflow coefficient: the rule fires exactly where every earlier rule of the shape
+    # gradient passed, and for no other request
+    BND = "not with a boundary traction or backflow term set (the mesh derivative of the facet terms is not built)"
+    seen = False
+    for (req, f, _), g in zip(combos, got):
+        want = expected(req, *f[:RG.EV + 1])
+        if req == SHAPE and (f[RG.TRACTION] or f[RG.BACKFLOW]) and want == (0, ""):
+            want = (E_STATE, BND)
+            seen = True
+        assert g == want, (req, f, g)
+    assert seen
     # the texts the GPU tests look for (tests/test_gpu_*.py), byte for byte
     tails = {t for _, t in got}
     for text in ("3-D handles only", "viscosity law", "not with a communicator attached", "not with a time term set",

@@ -5,7 +5,6 @@ allows (csrc/sns_policy.h: check_boundary_request) against a transcription, and 
 against its recipe scripts/make_boundary_golden.py (the GPU tests run its cases through the library)."""
 import ctypes
 import importlib.util
-import itertools
 import os
 import shutil
 import subprocess
@@ -19,6 +18,7 @@ torch = pytest.importorskip("torch")
 
 import boundary_oracle as BO  # noqa: E402
 import ns3d_oracle as NS  # noqa: E402
+import request_gate as RG  # noqa: E402
 import scalar_oracle as SO  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -226,15 +226,9 @@ def test_new_symbols_are_bound(built_lib):
 
 
 def test_boundary_request_table(tmp_path):
-    """check_boundary_request for every request and all combinations of its facts, and check_form_request's new rule, against a
-    transcription written here and not derived from the header."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "boundary_request")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
-                            "-I", os.path.join(ROOT, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
-                            os.path.join(ROOT, "tests", "boundary_request_main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
+    """check_boundary_request for every request and all combinations of the handle's facts against a transcription written here
+    and not derived from the header.  (The rule the boundary terms added to the shape gradient is checked with its request, in
+    tests/test_host.py::test_form_request_table.)"""
     E_ARG, E_STATE = -1, -3
     SET_FACETS, SET_FLOW, SET_SCALAR = range(3)
     COMM = "not with a communicator attached (partitioned boundary terms are not built)"
@@ -245,29 +239,14 @@ def test_boundary_request_table(tmp_path):
             checks.append((not facets, E_STATE, "set the boundary facets first (sns_set_boundary_facets)"))
         return next(((code, tail) for cond, code, tail in checks if cond), (0, ""))
 
-    bcombos = list(itertools.product(range(3), (2, 3), (0, 1), (0, 1)))
-    # the shape gradient (request 6 of policy::FormRequest) with the seventh fact; two other requests that must not see it
-    SHAPE, RECOVER, TIME_STEP = 6, 7, 5
-    fcombos = list(itertools.product((SHAPE, RECOVER, TIME_STEP), (2, 3), *[(0, 1)] * 6))
-    text = "".join("b " + " ".join(map(str, c)) + "\n" for c in bcombos) + "".join("f " + " ".join(map(str, c)) + "\n" for c in fcombos)
-    run = subprocess.run([exe], input=text, capture_output=True, text=True)
-    assert run.returncode == 0, run.returncode
-    lines = run.stdout.split("\n")
-    assert int(lines[0]) == 3                                   # policy::BREQ_COUNT
-    got = [(int(code), tail) for code, tail in (ln.split("\t") for ln in lines[1:1 + len(bcombos) + len(fcombos)])]
-    for c, g in zip(bcombos, got):
-        assert g == expected(*c), (c, g)
-    BND = "not with a boundary traction or backflow term set (the mesh derivative of the facet terms is not built)"
-    seen = False
-    for c, g in zip(fcombos, got[len(bcombos):]):
-        req, dim, part, tt, vl, bf, ev, bnd = c
-        without = got[len(bcombos) + fcombos.index((req, dim, part, tt, vl, bf, ev, 0))]
-        if req == SHAPE and bnd and without == (0, ""):         # the new rule is the LAST of its request: earlier texts stay
-            assert g == (E_STATE, BND), (c, g)
-            seen = True
-        else:
-            assert g == without, (c, g)
-    assert seen
+    bcombos = [(req, f, ()) for req in range(3) for f in RG.FACTS]
+    header, rows = RG.ask(tmp_path, "b", bcombos)
+    assert header["BREQ_COUNT"] == 3                            # policy::BREQ_COUNT
+    got = [(int(code), tail) for code, tail in rows]
+    for (req, f, _), g in zip(bcombos, got):
+        assert g == expected(req, f[RG.DIM], f[RG.PART], f[RG.FACETS]), (req, f, g)
+    assert set(got) == {(0, ""), (E_ARG, "3-D handles only"), (E_STATE, COMM),
+                        (E_STATE, "set the boundary facets first (sns_set_boundary_facets)")}
 
 
 def test_fixture_matches_its_recipe():

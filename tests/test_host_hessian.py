@@ -15,6 +15,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 import hessian_oracle as HO
+import request_gate as RG
 import stability_oracle as SO
 from conftest import ROOT
 from oracle import forms_literal as FL
@@ -168,10 +169,6 @@ def test_the_pieces_of_the_forcing_sensitivity():
 def test_request_rules(tmp_path):
     """check_state_gradient_request over every combination of the facts and a sweep of the coefficients, against a transcription
     of the rules written here: argument errors first (dimension, finite coefficients), then the state."""
-    exe = str(tmp_path / "state_gradient_request")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                            os.path.join(ROOT, "tests", "state_gradient_request_main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
     tails = dict(part="not with a communicator attached (the partitioned Hessian pass is not built)",
                  vl="not with a viscosity law set (the second derivative of nu_e is not built)",
                  tt="not with a time term set (the pass is taken on the steady form)",
@@ -187,16 +184,17 @@ def test_request_rules(tmp_path):
 
     facts = list(itertools.product((2, 3), *([(0, 1)] * 7)))
     coeffs = [("1", "0"), ("0", "1"), ("1", "0.7"), ("-2.5", "1e300"), ("nan", "0"), ("0", "nan"), ("inf", "1"), ("1", "-inf")]
-    combos = [f + a for f in facts for a in coeffs]
-    run = subprocess.run([exe], input="".join(" ".join(map(str, q)) + "\n" for q in combos), capture_output=True, text=True)
-    assert run.returncode == 0, run.returncode
-    lines = run.stdout.split("\n")
-    assert lines[0].split() == ["2", "4"]                      # StabilityRequest is neither renumbered nor extended
-    rows = [ln.split("\t") for ln in lines[1:1 + len(combos)]]
-    assert len(rows) == len(combos)
+    def read(f):                                               # the eight facts the transcription takes, in its order
+        return f[:RG.EV + 1] + (f[RG.TRACTION], f[RG.BACKFLOW])
+
+    assert set(facts) == {read(f) for f in RG.FACTS}
+    combos = [(0, f, a) for f in RG.FACTS for a in coeffs]     # all nine facts of the handle
+    assert len(combos) == 2 * 2 ** 8 * 8
+    header, rows = RG.ask(tmp_path, "g", combos)
+    assert [header[k] for k in ("SREQ_COUNT", "SREQ_KINDS")] == [2, 4]     # StabilityRequest is neither renumbered nor extended
     got = set()
-    for q, (code, tail) in zip(combos, rows):
-        assert (int(code), tail) == expected(*q), (q, code, tail)
+    for (_, f, a), (code, tail) in zip(combos, rows):
+        assert (int(code), tail) == expected(*read(f), *a), (f, a, code, tail)
         got.add((int(code), tail))
     assert got == {(0, ""), (E_ARG, "3-D handles only"), (E_ARG, "the coefficients must be finite")} | {(E_STATE, t) for t in tails.values()}
     # allowed: a traction alone, a viscosity field, both

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import left_modes_oracle as LO
+import request_gate as RG
 import stability_oracle as SO
 from conftest import ROOT
 from oracle import forms_literal as FL
@@ -189,11 +190,6 @@ def test_left_request_rules(tmp_path):
     of the arguments, against a transcription of the rules written here: argument errors first (dimension, m, shift,
     breakdown_rel), then the state (communicator, law, time term; the mass pass ignores a time term and the arguments) -- and
     against the right-hand kind's verdict for the same question, which must be the same."""
-    exe = str(tmp_path / "stability_left_request")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
-                            "-I", os.path.join(ROOT, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
-                            os.path.join(ROOT, "tests", "stability_left_request_main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
     MASS_T, ARNOLDI_L = 0, 1
 
     def expected(req, dim, part, tt, vl, m, shift, brel):
@@ -214,18 +210,16 @@ def test_left_request_rules(tmp_path):
             (32, "-1e-300", "1e-6"), (32, "-2", "1e-6"), (32, "nan", "1e-6"), (32, "inf", "1e-6"), (32, "1e308", "1e-6"),
             (32, "0", "0"), (32, "0", "1"), (32, "0", "-0.1"), (32, "0", "nan"), (32, "0", "1.5"), (32, "0", "1e-300"),
             (65, "nan", "2"), (1, "-1", "0")]
-    combos = [f + a for f in facts for a in args]
-    text = "".join(" ".join(map(str, c)) + "\n" for c in combos)
-    run = subprocess.run([exe], input=text, capture_output=True, text=True)
-    assert run.returncode == 0, run.returncode
-    lines = run.stdout.split("\n")
-    assert lines[0].split() == ["2", "2", "3", "4"]            # the right-hand count stays 2; the new kinds follow it
-    rows = [ln.split("\t") for ln in lines[1:1 + len(combos)]]
-    assert len(rows) == len(combos)
+    assert set(facts) == {(req,) + f[:RG.VL + 1] for req in (MASS_T, ARNOLDI_L) for f in RG.FACTS}
+    combos = [(req, f, a) for req in (MASS_T, ARNOLDI_L) for f in RG.FACTS for a in args]  # all nine facts of the handle
+    assert len(combos) == 2 * 2 * 2 ** 8 * 19
+    # the right-hand count stays 2; the new kinds follow it: asked as kinds 2 and 3 of policy::StabilityRequest, 4 in all
+    header, rows = RG.ask(tmp_path, "s", [(2 + req, f, a) for req, f, a in combos])
+    assert [header[k] for k in ("SREQ_COUNT", "SREQ_KINDS")] == [2, 4]
     got = set()
-    for c, (lc, lt, rc, rt) in zip(combos, rows):
-        assert (int(lc), lt) == expected(*c), (c, lc, lt)
-        assert (lc, lt) == (rc, rt), c
+    for (req, f, a), (lc, lt, rc, rt) in zip(combos, rows):
+        assert (int(lc), lt) == expected(req, *f[:RG.VL + 1], *a), (req, f, a, lc, lt)
+        assert (lc, lt) == (rc, rt), (req, f, a)
         got.add((int(lc), lt))
     assert got >= {(0, ""), (E_ARG, "3-D handles only"), (E_ARG, "m must lie in [2, 64]"),
                    (E_ARG, "the shift must be finite and >= 0"), (E_ARG, "breakdown_rel must lie in (0, 1)"),

@@ -7,11 +7,11 @@ import ctypes as C
 import itertools
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import request_gate as RG
 import stability_oracle as SO
 from conftest import ROOT
 from stabilized_navier_stokes_flow_fenicsx_amd import solver as S
@@ -23,11 +23,6 @@ def test_stability_request_rules(tmp_path):
     """check_stability_request for both requests, every combination of the facts and a sweep of the arguments, against a
     transcription of the issue's rules written here and not derived from the header: argument errors first (dimension, m,
     shift, breakdown_rel), then the state (communicator, law, time term; the mass pass ignores a time term and the arguments)."""
-    exe = str(tmp_path / "stability_request")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
-                            "-I", os.path.join(ROOT, "stabilized_navier_stokes_flow_fenicsx_amd", "csrc"),
-                            os.path.join(ROOT, "tests", "stability_request_main.cpp"), "-o", exe], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
     MASS, ARNOLDI = 0, 1
 
     def expected(req, dim, part, tt, vl, m, shift, brel):
@@ -48,16 +43,14 @@ def test_stability_request_rules(tmp_path):
             (32, "-1e-300", "1e-6"), (32, "-2", "1e-6"), (32, "nan", "1e-6"), (32, "inf", "1e-6"), (32, "1e308", "1e-6"),
             (32, "0", "0"), (32, "0", "1"), (32, "0", "-0.1"), (32, "0", "nan"), (32, "0", "1.5"), (32, "0", "1e-300"),
             (65, "nan", "2"), (1, "-1", "0")]
-    combos = [f + a for f in facts for a in args]
-    text = "".join(" ".join(map(str, c)) + "\n" for c in combos)
-    run = subprocess.run([exe], input=text, capture_output=True, text=True)
-    assert run.returncode == 0, run.returncode
-    lines = run.stdout.split("\n")
-    assert lines[0].split() == ["2", "2", "64"]                 # SREQ_COUNT, the bounds of m
-    got = [(int(code), tail) for code, tail in (ln.split("\t") for ln in lines[1:1 + len(combos)])]
-    assert len(got) == len(combos)
-    for c, g in zip(combos, got):
-        assert g == expected(*c), (c, g)
+    assert set(facts) == {(req,) + f[:RG.VL + 1] for req in (MASS, ARNOLDI) for f in RG.FACTS}
+    combos = [(req, f, a) for req in (MASS, ARNOLDI) for f in RG.FACTS for a in args]      # all nine facts of the handle
+    assert len(combos) == 2 * 2 * 2 ** 8 * 19
+    header, rows = RG.ask(tmp_path, "s", combos)
+    assert [header[k] for k in ("SREQ_COUNT", "STABILITY_M_MIN", "STABILITY_M_MAX")] == [2, 2, 64]   # SREQ_COUNT, the bounds of m
+    got = [(int(code), tail) for code, tail in rows]
+    for (req, f, a), g in zip(combos, got):
+        assert g == expected(req, *f[:RG.VL + 1], *a), (req, f, a, g)
     # every verdict of the rules occurs in the sweep
     assert {g for g in got} >= {(0, ""), (E_ARG, "3-D handles only"), (E_ARG, "m must lie in [2, 64]"),
                                 (E_STATE, "not with a time term set (the analysis sets its own and clears it)")}
