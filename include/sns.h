@@ -498,6 +498,30 @@ SNS_API int sns_stability_arnoldi_left(sns_handle h, const double* w_dev, double
                                        double* H_host /* (m+1) x m, row major */, int* m_done, int* total_ksp_its, int* reason);
 SNS_API int sns_jacobian_state_gradient(sns_handle h, const double* w_dev, const double* x_dev, const double* z_dev,
                                         double c_jac, double c_mass, double* g_dev);
+/* The raw Jacobian and the Dirichlet values of a live handle (no counterpart in the reference).
+ * sns_raw_jacobian_apply: y = J0(w) x for transposed == 0, y = J0(w)^T x otherwise, J0 = dR_raw/dw the exact Gateaux derivative
+ *   of the raw residual sns_residual_moments sums -- without lifting and without the Dirichlet rows' w_B - g.  With K_t the
+ *   element Jacobian of cell t,  y[4i+c] = sum_{t containing i, a = loc(i,t)} sum_b sum_d K_t[(a,c),(b,d)] x[4 n_b + d],  and
+ *   K_t[(b,d),(a,c)] in its place for the transpose.  No mask is applied anywhere: x is used as given on constrained dofs and
+ *   every row of y is written; w need not satisfy the Dirichlet data.  2-D handles: the uz rows and columns are 0.  The pass
+ *   follows what the handle's NS assembly follows -- corrected_convection, a set time term (sigma, theta, d), the Carreau law,
+ *   a body force, a viscosity field -- and its free x free blocks are the assembled Jacobian's own arithmetic (the same block
+ *   code).  The [B, free] block is what differentiates the residual-based force (functionals.reaction_force_gradient), the
+ *   [free, B] block what differentiates the state with respect to the Dirichlet values (solver.dirichlet_sensitivity); the
+ *   assembled operator holds neither.  Matrix-free, one pass over the node -> cell lists, 4 lanes per row, quad sums in a fixed
+ *   order: no atomics, no scratch, bitwise reproducible.  Nothing of the handle is written.  form: SNS_FORM_NS (the G-metric
+ *   form on 3-D handles, the UGN form on 2-D handles, with the branch every conditional takes at the state).
+ *   SNS_E_ARG: null handle / pointer, x_dev == y_dev, a form other than SNS_FORM_NS.  SNS_E_STATE: a communicator attached, a
+ *   backflow coefficient set (the backflow term's share of J0 is not built; a traction alone is constant in w and allowed), a
+ *   perturbed form variant (sns_set_form_variant: the block code holds the reference's constants only).
+ * sns_set_dirichlet_values: new Dirichlet VALUES for a live handle, 4 * n_nodes doubles on the host.  The mask stays what
+ *   sns_create got; entries of unconstrained dofs are ignored and the uz slots of a 2-D handle stay 0.  Every later residual,
+ *   Jacobian and solve takes the new values, bit for bit as a handle created with them; an assembled matrix, the hierarchy and
+ *   the smoother's estimates stay what they were (none depends on the values).  Synchronises the handle's stream.
+ *   SNS_E_ARG, the handle untouched: null handle / pointer, a non-finite value on a constrained dof.  SNS_E_STATE: a
+ *   communicator attached. */
+SNS_API int sns_raw_jacobian_apply(sns_handle h, int form, const double* w_dev, const double* x_dev, int transposed, double* y_dev);
+SNS_API int sns_set_dirichlet_values(sns_handle h, const double* bc_val_host);
 /* MatMult with the assembled operator: y = A x (halo exchange inside).  Acts on whatever
  * the handle holds: y = A^T x after sns_transpose_operator.                   */
 SNS_API int sns_spmv(sns_handle h, const double* x_dev, double* y_dev);

@@ -603,6 +603,40 @@ int sns_jacobian_state_gradient(sns_handle h, const double* w, const double* x, 
     return jacobian_state_gradient(h, w, x, z, c_jac, c_mass, g);
 }
 
+int sns_raw_jacobian_apply(sns_handle h, int form, const double* w, const double* x, int transposed, double* y) {
+    const char* who = "sns_raw_jacobian_apply";
+    if (!h || !w || !x || !y) { set_error("sns_raw_jacobian_apply: null handle or pointer"); return SNS_E_ARG; }
+    SNS_TRY(allows(h, who, policy::FAMILY_RAW_JACOBIAN, policy::JREQ_APPLY, ROWS_ARG));
+    SNS_TRY(refused(who, policy::check_raw_jacobian_args({form, x == y, !h->form.fv.is_default()})));
+    SNS_TRY(allows(h, who, policy::FAMILY_RAW_JACOBIAN, policy::JREQ_APPLY, ROWS_STATE));
+    return raw_jacobian_apply(h, w, x, transposed != 0, y);
+}
+
+// The values alone move: the mask, and with it the pattern, the free mask of the hierarchy and every assembled value, stay.
+// bc_val and gext are the two buffers derived from the values; every kernel reads them at its launch, nothing caches them.
+int sns_set_dirichlet_values(sns_handle h, const double* bc_val_host) {
+    const char* who = "sns_set_dirichlet_values";
+    if (!h || !bc_val_host) { set_error("sns_set_dirichlet_values: null handle or pointer"); return SNS_E_ARG; }
+    SNS_TRY(allows(h, who, policy::FAMILY_RAW_JACOBIAN, policy::JREQ_SET_DIRICHLET));
+    const size_t nd = (size_t)ld_of(h);
+    std::vector<uint8_t> mask(nd);
+    std::vector<double> val(nd), ge(nd);
+    SNS_TRY(sync_stream(h));                                // (kernels queued before the call read the old values)
+    HIP_TRY(hipMemcpy(mask.data(), h->bc_mask, nd, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(val.data(), h->bc_val, nd * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nd; ++i) {
+        if (mask[i]) {
+            const double g = (h->dim == 2 && (i & 3) == 2) ? 0.0 : bc_val_host[i];      // the unused z component of a 2-D handle
+            if (!(g - g == 0.0)) { set_error("sns_set_dirichlet_values: non-finite value on a constrained dof"); return SNS_E_ARG; }
+            val[i] = g;
+        }
+        ge[i] = mask[i] ? val[i] : 0.0;
+    }
+    HIP_TRY(hipMemcpy(h->bc_val, val.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->gext, ge.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+    return SNS_OK;
+}
+
 // both Arnoldi entry points (`who`: the name in front of the message).  SREQ_ARNOLDI_LEFT: the operator is flipped between the
 // assembly and the set-up and given back afterwards, as sns_adjoint_solve does
 static int stability_arnoldi(const char* who, sns_ctx* h, policy::StabilityRequest request, const double* w, double shift, int m,

@@ -12,6 +12,7 @@ struct FormPass {
     decltype(&k_fused_offdiag<SNS_FORM_NS, false>) offdiag;
     decltype(&k_fused_diag<SNS_FORM_NS, false>) diag;
     decltype(&k_fused_lift<SNS_FORM_NS, false>) lift;
+    decltype(&k_raw_jacobian_apply<SNS_FORM_NS, false>) raw;
     decltype(&k_element<SNS_FORM_NS, false>) element;
     decltype(&k_residual_tet<false>) residual_tet;
     double nu, aux;
@@ -26,20 +27,20 @@ FormPass form_pass(const sns_ctx* h, int form) {
     const double nu = 1.0 / h->opt.reynolds;
     if (h->dim == 2 && form == SNS_FORM_NS)
         return {&k_fused_offdiag<SNS_FORM_UGN_2D, false>, &k_fused_diag<SNS_FORM_UGN_2D, false>, &k_fused_lift<SNS_FORM_UGN_2D, false>,
-                nullptr, nullptr, nu, 0.0, TimeTerm(), ViscosityLaw()};
+                &k_raw_jacobian_apply<SNS_FORM_UGN_2D, false>, nullptr, nullptr, nu, 0.0, TimeTerm(), ViscosityLaw()};
     if (h->dim == 2)
-        return {&k_fused_offdiag<SNS_FORM_STOKES_2D, false>, &k_fused_diag<SNS_FORM_STOKES_2D, false>, nullptr, nullptr, nullptr,
+        return {&k_fused_offdiag<SNS_FORM_STOKES_2D, false>, &k_fused_diag<SNS_FORM_STOKES_2D, false>, nullptr, nullptr, nullptr, nullptr,
                 h->opt.stokes_viscosity, h->opt.stokes_beta, TimeTerm(), ViscosityLaw()};
     if (form != SNS_FORM_NS)
-        return {&k_fused_offdiag<SNS_FORM_STOKES, false>, &k_fused_diag<SNS_FORM_STOKES, false>, nullptr, &k_element<SNS_FORM_STOKES, false>,
-                nullptr, nu, 0.0, TimeTerm(), ViscosityLaw()};
+        return {&k_fused_offdiag<SNS_FORM_STOKES, false>, &k_fused_diag<SNS_FORM_STOKES, false>, nullptr, nullptr,
+                &k_element<SNS_FORM_STOKES, false>, nullptr, nu, 0.0, TimeTerm(), ViscosityLaw()};
     FormPass k{};
     dispatch<1, 0>(h->opt.corrected_convection != 0, [&](auto C) {
         dispatch<3, 2, 1, 0>(S.ns_variant(), [&](auto V) {
             constexpr bool c = C() != 0, ev = V() == 3, tt = V() == 1 || ev, vl = V() == 2;
             k = {&k_fused_offdiag<SNS_FORM_NS, c, tt, vl, ev>, &k_fused_diag<SNS_FORM_NS, c, tt, vl, ev>,
-                 &k_fused_lift<SNS_FORM_NS, c, tt, vl, ev>, &k_element<SNS_FORM_NS, c, tt, vl, ev>, &k_residual_tet<c, tt, vl, ev>,
-                 nu, 0.0, S.tt, S.vl};
+                 &k_fused_lift<SNS_FORM_NS, c, tt, vl, ev>, &k_raw_jacobian_apply<SNS_FORM_NS, c, tt, vl, ev>,
+                 &k_element<SNS_FORM_NS, c, tt, vl, ev>, &k_residual_tet<c, tt, vl, ev>, nu, 0.0, S.tt, S.vl};
         });
     });
     return k;
@@ -146,6 +147,18 @@ int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix)
     }
     HIP_TRY(hipGetLastError());
     return SNS_OK;
+}
+
+// y = J0(w) x or J0(w)^T x by the NS form's raw-Jacobian pass (handle, pointers and the form state were checked by the entry
+// point).  Reads the mesh, the form state and the node -> cell lists; writes y and nothing of the handle.
+int raw_jacobian_apply(sns_ctx* h, const double* w, const double* x, bool transposed, double* y) {
+    if (h->n == 0) return SNS_OK;
+    const FormPass K = form_pass(h, SNS_FORM_NS);
+    const unsigned g = (unsigned)((4 * (int64_t)h->n + 255) / 256);
+    hipLaunchKernelGGL(K.raw, dim3(g), dim3(256), 0, h->stream, h->n, h->nt_ptr, h->nt_idx, h->tets, h->pts, w, x, K.nu,
+                       transposed ? 1 : 0, y, K.tt, K.vl);
+    HIP_TRY(hipGetLastError());
+    return sync_stream(h);
 }
 
 int timed_assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix) {

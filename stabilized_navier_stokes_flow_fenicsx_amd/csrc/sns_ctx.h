@@ -290,6 +290,8 @@ void matrix_changed(sns_ctx* h, int form, const double* scalar_par = nullptr);
 int assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix);
 int timed_assemble(sns_ctx* h, int form, const double* w, double* F, bool want_matrix);
 int residual_moments(sns_ctx* h, int form, const double* w, const double* phi, double out[4]);
+// ... and the NS form's raw Jacobian applied matrix-free: y = J0(w) x, or J0(w)^T x (writes y alone; synchronises)
+int raw_jacobian_apply(sns_ctx* h, const double* w, const double* x, bool transposed, double* y);
 // csrc/sns_cycle.hip: the V-cycle, the preconditioner and operator applications
 int vcycle(sns_ctx* h, int l, const double* b, double* x);
 int coarse_cycle(sns_ctx* h, int l, const double* b, double* x);

@@ -121,6 +121,11 @@ template <int FORM, bool corrected, bool TT = false, bool VL = false, bool EV = 
 __global__ void k_fused_lift(int32_t n_rows, const int32_t* diag, const int64_t* c_ptr, const int32_t* c_idx,
                              const int32_t* tets, const double* pts, const double* w, const uint8_t* bc_mask,
                              const double* dl, double nu, double* F, TimeTerm tt, ViscosityLaw vl);
+// y = J0(w) x (transposed != 0: J0(w)^T x), J0 the Jacobian of the raw form: no Dirichlet mask, every row written
+template <int FORM, bool corrected, bool TT = false, bool VL = false, bool EV = false>
+__global__ void k_raw_jacobian_apply(int32_t n_rows, const int64_t* nt_ptr, const int32_t* nt_idx, const int32_t* tets,
+                                     const double* pts, const double* w, const double* x, double nu, int transposed, double* y,
+                                     TimeTerm tt, ViscosityLaw vl);
 __global__ void k_bc_defect(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, const double* w, double* dl);
 template <bool corrected, bool TT = false, bool VL = false, bool EV = false>
 __global__ void k_residual_tet(int64_t n_tets, const int32_t* tets, const double* pts, const double* w, double nu,

@@ -452,8 +452,9 @@ enum FactBit {
 // The families: the setters and passes of the 3-D NS form; the three setters of the facet terms (csrc/sns_boundary.hip); the
 // stability analysis (csrc/sns_stability.hip) -- SREQ_COUNT is the number of right-hand kinds, SREQ_KINDS counts all: the
 // left-hand kinds (sns_mass_apply_transpose, sns_stability_arnoldi_left) follow the right-hand ones and are refused exactly as
-// those are --; the Hessian pass (sns_jacobian_state_gradient, csrc/sns_hessian.hip), one request.
-enum Family { FAMILY_FORM = 0, FAMILY_BOUNDARY, FAMILY_STABILITY, FAMILY_STATE_GRADIENT };
+// those are --; the Hessian pass (sns_jacobian_state_gradient, csrc/sns_hessian.hip), one request; the raw Jacobian
+// (sns_raw_jacobian_apply) and the Dirichlet values of a live handle (sns_set_dirichlet_values), two requests.
+enum Family { FAMILY_FORM = 0, FAMILY_BOUNDARY, FAMILY_STABILITY, FAMILY_STATE_GRADIENT, FAMILY_RAW_JACOBIAN };
 enum FormRequest {
     REQ_SET_TIME_TERM = 0, REQ_CLEAR_TIME_TERM, REQ_SET_CARREAU, REQ_SET_NEWTONIAN, REQ_SET_FIELD /* set or clear: force, viscosity, mixture */,
     REQ_TIME_STEP, REQ_SHAPE_GRADIENT, REQ_RECOVER_GRADIENT, REQ_ERROR_INDICATOR, REQ_SCALAR /* system or solve */,
@@ -462,6 +463,7 @@ enum FormRequest {
 enum BoundaryRequest { BREQ_SET_FACETS = 0, BREQ_SET_FLOW, BREQ_SET_SCALAR, BREQ_COUNT };
 enum StabilityRequest { SREQ_MASS_APPLY = 0, SREQ_ARNOLDI, SREQ_COUNT, SREQ_MASS_APPLY_TRANSPOSE = SREQ_COUNT, SREQ_ARNOLDI_LEFT, SREQ_KINDS };
 constexpr int GREQ_STATE_GRADIENT = 0;
+enum RawJacobianRequest { JREQ_APPLY = 0, JREQ_SET_DIRICHLET, JREQ_COUNT };
 // error != SNS_OK: refused; the entry point's message is its name, ": " and `tail`
 struct Verdict {
     int error = SNS_OK;
@@ -474,7 +476,9 @@ struct Verdict {
 // ignores a time term (B is taken at theta = 0 and u_t = 0 whatever the handle's history) while the Arnoldi process sets its
 // own; the Hessian pass allows a viscosity field (the viscous term stays linear in u) and a traction alone (constant in w), and
 // refuses a body force (J then depends on f through dM/dw(w, -f): a second contraction that is not built) and a backflow
-// coefficient (that term is quadratic in u; its Hessian is not built).
+// coefficient (that term is quadratic in u; its Hessian is not built); the raw-Jacobian pass serves 2-D handles and every
+// switch of the form (its blocks are the assembly's own) and refuses only a backflow coefficient, whose share of J0 lives in
+// the boundary pass and is not built matrix-free; a traction alone is constant in w.
 struct Rule {
     Family family;
     int request;
@@ -540,6 +544,12 @@ constexpr Rule RULES[] = {
      "not with a body force set (J depends on f through the stabilisation's weighting: that contraction is not built)"},
     {FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, HAS_BACKFLOW, SNS_E_STATE,
      "not with a backflow coefficient set (the Hessian of the backflow term is not built)"},
+
+    {FAMILY_RAW_JACOBIAN, JREQ_APPLY, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (the partitioned raw-Jacobian pass is not built)"},
+    {FAMILY_RAW_JACOBIAN, JREQ_APPLY, HAS_BACKFLOW, SNS_E_STATE,
+     "not with a backflow coefficient set (the backflow term's share of the raw Jacobian is not built)"},
+    {FAMILY_RAW_JACOBIAN, JREQ_SET_DIRICHLET, IS_PARTITIONED, SNS_E_STATE,
+     "not with a communicator attached (partitioned handles keep the Dirichlet values they were created with)"},
 };
 
 // The one lookup.  An entry point's own value checks stand between the family's SNS_E_ARG rows and its SNS_E_STATE rows:
@@ -582,7 +592,21 @@ inline Verdict check_state_gradient_args(double c_jac, double c_mass) {
     return {};
 }
 
-// The four families as the host tests ask them (tests/request_main.cpp)
+// ... and the arguments of the raw-Jacobian pass: the NS form, distinct vectors, the reference's constants (the block code
+// holds no others: a perturbed form variant is the call's own verdict, not a fact of the table)
+struct RawJacobianArgs {
+    int form = SNS_FORM_NS;
+    bool aliased = false, variant = false;
+};
+inline Verdict check_raw_jacobian_args(const RawJacobianArgs& a) {
+    if (a.form == SNS_FORM_STOKES) return {SNS_E_ARG, "the Stokes forms are not supported"};
+    if (a.form != SNS_FORM_NS) return {SNS_E_ARG, "bad form"};
+    if (a.aliased) return {SNS_E_ARG, "x and y must not be the same vector"};
+    if (a.variant) return {SNS_E_STATE, "not with a perturbed form variant set (the pass holds the reference's constants only)"};
+    return {};
+}
+
+// The families as the host tests ask them (tests/request_main.cpp; the raw Jacobian's: tests/rawjac_request_main.cpp)
 inline Verdict check_form_request(FormRequest request, const HandleFacts& f) { return check_request(FAMILY_FORM, request, f); }
 inline Verdict check_boundary_request(BoundaryRequest request, const HandleFacts& f) { return check_request(FAMILY_BOUNDARY, request, f); }
 inline Verdict check_stability_request(StabilityRequest request, const HandleFacts& f, const ArnoldiArgs& a = {}) {
@@ -591,6 +615,9 @@ inline Verdict check_stability_request(StabilityRequest request, const HandleFac
 }
 inline Verdict check_state_gradient_request(const HandleFacts& f, double c_jac = 1.0, double c_mass = 0.0) {
     return check_request(FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, f, check_state_gradient_args(c_jac, c_mass));
+}
+inline Verdict check_raw_jacobian_request(RawJacobianRequest request, const HandleFacts& f, const RawJacobianArgs& a = {}) {
+    return check_request(FAMILY_RAW_JACOBIAN, request, f, request == JREQ_APPLY ? check_raw_jacobian_args(a) : Verdict{});
 }
 
 // ---- which operator is it? (the spectral estimates of csrc/sns_damping.hip; the cases are in DESIGN.md) -----------------------------

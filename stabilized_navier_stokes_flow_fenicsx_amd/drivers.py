@@ -507,6 +507,27 @@ def _print_reynolds_sensitivities(P, w, wg, grads, grads_nu, names):
     return out
 
 
+def _print_inlet_sensitivities(P, w, grads, names):
+    """SNS_INLET_SENSITIVITY=1 (opt-in; single-GPU runs): for the functionals whose gradients are the rows of ``grads``, the
+    derivative with respect to the amplitude of the inlet profile at the converged state -- dJ/dg of
+    solver.dirichlet_sensitivity (one adjoint solve and one raw-Jacobian pass each) contracted with g on the inlet's velocity
+    dofs, the only Dirichlet dofs of these problems whose value is not 0."""
+    from .solver import dirichlet_sensitivity
+    if getattr(P, "part", None) is not None:
+        if _rank() == 0:
+            print("SNS_INLET_SENSITIVITY: adjoint solves run on single-GPU problems only; skipped", flush=True)
+        return None
+    amp = np.where(P.bc_mask.astype(bool), P.bc_val, 0.0)
+    amp[3::4] = 0.0
+    out = []
+    for name, g in zip(names, grads):
+        dJ, _, res = dirichlet_sensitivity(P, w, g)
+        d = float(dJ.cpu().numpy() @ amp)
+        print(f"d{name}/d(inlet amplitude): {d} (adjoint solve: {res.its} its, reason {res.reason})", flush=True)
+        out.append(d)
+    return out
+
+
 def _print_radius_sensitivities(P, msh, w, wg, nu):
     """SNS_SHAPE_SENSITIVITY=1 (opt-in; single-GPU runs): dC_d/dr and dC_l/dr, r the cylinder radius, at the converged
     state: the node gradients of solver.shape_sensitivity (one adjoint solve and one element pass each) contracted with
@@ -787,6 +808,8 @@ def dfg_2d_main(argv=None):
         _print_reynolds_sensitivities(P, w, wg, G0 + nu * (G1 - G0), G1 - G0, ("C_d", "C_l"))
     if os.environ.get("SNS_SHAPE_SENSITIVITY", "0") == "1":
         _print_radius_sensitivities(P, msh, w, wg, nu)
+    if os.environ.get("SNS_INLET_SENSITIVITY", "0") == "1":
+        _print_inlet_sensitivities(P, w, M2.drag_lift_2d_gradient(msh, nu), ("C_d", "C_l"))
     r = P.last_newton
     P.close()
     return msh, wg, (cd, cl), r
@@ -833,6 +856,9 @@ def dfg_3d_main(argv=None):
         ob = msh.meta["tags"]["obstacle"]
         G1, G0 = sc * Fn.boundary_traction_gradient(msh, 1.0, ob)[:2], sc * Fn.boundary_traction_gradient(msh, 0.0, ob)[:2]
         _print_reynolds_sensitivities(P, w, wg, G0 + nu * (G1 - G0), G1 - G0, ("C_d", "C_l"))
+    if os.environ.get("SNS_INLET_SENSITIVITY", "0") == "1":
+        sc = Fn.drag_lift_coefficients(np.ones(3))[0]
+        _print_inlet_sensitivities(P, w, sc * Fn.boundary_traction_gradient(msh, nu, msh.meta["tags"]["obstacle"])[:2], ("C_d", "C_l"))
     r = P.last_newton
     P.close()
     return msh, wg, (cd, cl), r

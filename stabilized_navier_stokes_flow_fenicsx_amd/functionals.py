@@ -222,3 +222,39 @@ def reaction_force(problem, w, tag: int, *, mesh: TetMesh | None = None, rim_tag
             raise ValueError("reaction_force: pass the tagged global mesh of this partitioned problem")
     phi = tag_node_weights(mesh, tag, rim_tags=rim_tags, rim_weight=rim_weight, part=part)
     return -problem.residual_moments(w, phi, form)[:3]
+
+
+def reaction_force_gradient(problem, w, tag: int, *, mesh: TetMesh | None = None, rim_tags=(), rim_weight: float = 1.0):
+    """d(reaction_force)/dw at fixed Re as a device tensor (3, ndof): row c is ``-J0(w)^T (phi e_c)``, J0 the Jacobian of the raw
+    residual (``FlowProblem.raw_jacobian_apply``, one transposed pass per component) and phi the weights ``reaction_force``
+    tests with.  The rows are not zero on Dirichlet dofs: the force of a state depends on the values the state takes there.  As
+    the grad_J of ``solver.reynolds_sensitivity`` / ``shape_sensitivity`` / ``dirichlet_sensitivity`` they are used as they
+    are; the explicit parts are ``reaction_force_reynolds_derivative`` and ``-problem.residual_shape_gradient(w, phi e_c)``.
+    Single-GPU problems, NS form."""
+    import torch
+    m = problem.mesh if mesh is None else mesh
+    phi = torch.from_numpy(tag_node_weights(m, tag, rim_tags=rim_tags, rim_weight=rim_weight)).to(problem.device)
+    out = torch.empty(3, problem.ndof, dtype=torch.float64, device=problem.device)
+    z = problem.zeros()
+    for c in range(3):
+        z.zero_()
+        z[c::4] = phi
+        problem.raw_jacobian_apply(w, z, transpose=True, out=out[c])
+    return out.neg_()
+
+
+def reaction_force_reynolds_derivative(problem, w, tag: int, rel_step: float = 1e-4, *, mesh: TetMesh | None = None, rim_tags=(),
+                                       rim_weight: float = 1.0) -> np.ndarray:
+    """The explicit part d(reaction_force)/dRe at fixed ``w`` as a 3-vector: central difference of ``residual_moments`` at
+    Re (1 +- rel_step), mirroring ``solver.residual_reynolds_derivative``; the problem's options are restored afterwards."""
+    m = problem.mesh if mesh is None else mesh
+    phi = tag_node_weights(m, tag, rim_tags=rim_tags, rim_weight=rim_weight)
+    Re = float(problem.options.reynolds)
+    try:
+        problem.set_options(reynolds=Re * (1.0 + rel_step))
+        Fp = -problem.residual_moments(w, phi, "ns")[:3]
+        problem.set_options(reynolds=Re * (1.0 - rel_step))
+        Fm = -problem.residual_moments(w, phi, "ns")[:3]
+    finally:
+        problem.set_options(reynolds=Re)
+    return (Fp - Fm) / (2.0 * Re * rel_step)

@@ -392,6 +392,39 @@ class FlowProblem:
         check(self.lib.sns_jacobian_state_gradient(self.h, _ptr(w), _ptr(x), _ptr(z), float(c_jac), float(c_mass), _ptr(out)))
         return out
 
+    def raw_jacobian_apply(self, w, x, transpose: bool = False, out=None) -> torch.Tensor:
+        """``J0(w) x``, or ``J0(w)^T x`` with ``transpose`` (sns_raw_jacobian_apply): J0 = dR_raw/dw, the Jacobian of the raw NS
+        residual of ``residual_moments`` -- no lifting, no Dirichlet rows, no mask anywhere: ``x`` is used as given on
+        constrained dofs and every row of the result is written; ``w`` need not satisfy its Dirichlet data.  The pass follows
+        corrected_convection, a set time term, the Carreau law, a body force and a viscosity field as the assembly does, and on
+        the free x free blocks it is the assembled Jacobian's arithmetic.  Matrix-free, one pass, bitwise reproducible; nothing
+        of the problem is written.  2-D problems: the u_z rows and columns are 0.  Refused (SnsError) with a backflow
+        coefficient or a perturbed form variant set, with ``out`` the same tensor as ``x``, and on partitioned problems."""
+        w, x = self._vec(w), self._vec(x)
+        out = self.zeros() if out is None else self._vec(out)
+        check(self.lib.sns_raw_jacobian_apply(self.h, FORM_NS, _ptr(w), _ptr(x), int(bool(transpose)), _ptr(out)))
+        return out
+
+    def set_dirichlet_values(self, g):
+        """New Dirichlet VALUES for this problem (sns_set_dirichlet_values): ``g`` holds 4 * n_nodes entries (numpy or a
+        tensor); the mask stays, entries of unconstrained dofs are ignored, the u_z slots of a 2-D problem stay 0.  Every later
+        residual, Jacobian and solve takes them, bit for bit as a problem created with them; an assembled matrix stays what it
+        was.  Refreshes the host copy ``bc_val`` and the device copy ``g_dev``.  A non-finite value on a constrained dof is
+        refused and leaves the problem untouched.  Single-GPU problems."""
+        if isinstance(g, torch.Tensor):
+            g = g.detach().cpu().numpy()
+        g = np.ascontiguousarray(g, dtype=np.float64).ravel()
+        if g.shape != (self.ndof,):
+            raise ValueError(f"expected {self.ndof} Dirichlet values")
+        check(self.lib.sns_set_dirichlet_values(self.h, g.ctypes.data))
+        B = self.bc_mask.astype(bool)
+        val = self.bc_val.copy()
+        val[B] = g[B]
+        if self.dim == 2:
+            val[2::4] = 0.0
+        self.bc_val = val
+        self.g_dev = torch.from_numpy(self.bc_val).to(self.device)
+
     def stability_arnoldi(self, w, shift: float = 0.0, m: int = 64, start=None, breakdown_rel: float = 1e-6, side: str = "right"):
         """``m`` steps of shift-invert Arnoldi on (J + shift B)^-1 B at the steady state ``w`` (sns_stability_arnoldi), with
         the problem's ksp / pc options for the inner solves.  Returns ``(V, H, ArnoldiResult)``: V a device tensor
@@ -1010,19 +1043,27 @@ def newton_with_law_continuation(problem: FlowProblem, w: torch.Tensor, steps: i
     return w, res
 
 
-def solve_unsteady(problem: FlowProblem, w0, dt: float, n_steps: int, order: int = 2, theta_coeff: float = 4.0, callback=None):
+def solve_unsteady(problem: FlowProblem, w0, dt: float, n_steps: int, order: int = 2, theta_coeff: float = 4.0, callback=None,
+                   dirichlet=None):
     """``n_steps`` implicit steps of size ``dt`` from the state ``w0`` (not modified): BDF1 for the first step, then BDF
     of the given order (1 or 2).  ``callback(step, t, w)`` runs after every converged step (step = 1.., t = step dt) with
     the time term of that step still set -- the place to sample forces (``functionals.reaction_force``) or write output.
     Stops at the first step that does not converge.  Returns (w, records): the final state and one dict per step with
     ``its``, ``ksp_its`` and ``reason``.  NOT in the reference.  The problem keeps the last step's time term;
-    ``problem.clear_time_term()`` returns it to the steady form."""
+    ``problem.clear_time_term()`` returns it to the steady form.
+
+    ``dirichlet``: an optional callable t -> g (4 * n_nodes Dirichlet values, numpy or tensor) for a ramped or pulsatile
+    inflow: before step n + 1 the problem's values are set to g((n + 1) dt) (``FlowProblem.set_dirichlet_values``); the
+    step starts from u^n, which then violates them, and its first Newton update carries the lifting term.  The problem keeps the values of the last step.  None: the values the problem
+    has, and not one call more."""
     if order not in (1, 2):
         raise ValueError("order must be 1 or 2")
     w = problem._vec(w0).clone()
     wprev = w.clone()
     records = []
     for step in range(1, int(n_steps) + 1):
+        if dirichlet is not None:
+            problem.set_dirichlet_values(dirichlet(step * dt))
         _, res = problem.time_step(w, wprev, dt, order=1 if step == 1 else order, theta_coeff=theta_coeff)
         records.append(dict(its=res.its, ksp_its=res.ksp_its, reason=res.reason))
         if res.reason <= 0:
@@ -1212,9 +1253,10 @@ def shape_sensitivity(problem: FlowProblem, w, grad_J, dJ_dX_explicit=None):
         (n_nodes, 3) for a directional derivative: ``(dJdX * V).sum()``.
       * The components on interior nodes are mesh-motion terms of the discrete problem; they vanish only in the limit h -> 0.
 
-    The residual-based force (``functionals.reaction_force``) cannot serve as J here: its dJ/dw needs the Dirichlet-row x
-    free-column block of the UNCONSTRAINED Jacobian, which the handle does not hold (the assembled operator has unit rows
-    there).  Its explicit part alone is ``-problem.residual_shape_gradient(w, phi e_c)``.
+    The residual-based force (``functionals.reaction_force``) serves as J too: its dJ/dw needs the Dirichlet-row x
+    free-column block of the UNCONSTRAINED Jacobian, which the assembled operator does not hold (it has unit rows there) and
+    the raw-Jacobian pass applies matrix-free -- ``grad_J`` = a row of ``functionals.reaction_force_gradient(problem, w, tag)``,
+    ``dJ_dX_explicit`` = ``-problem.residual_shape_gradient(w, phi e_c)`` with phi = ``functionals.tag_node_weights``.
 
     Returns (dJ/dX as a device tensor (n_nodes, 3), lam, KrylovResult of the adjoint solve).  The handle is left as
     ``reynolds_sensitivity`` leaves it: the Jacobian at w assembled, the caller's options.  Single-GPU problems."""
@@ -1229,6 +1271,36 @@ def shape_sensitivity(problem: FlowProblem, w, grad_J, dJ_dX_explicit=None):
         if not isinstance(e, torch.Tensor):
             e = torch.from_numpy(np.ascontiguousarray(e, dtype=np.float64))
         dJ += e.to(dJ.device).reshape(dJ.shape)
+    return dJ, lam, res
+
+
+def dirichlet_sensitivity(problem: FlowProblem, w, grad_J):
+    """Gradient dJ/dg of a functional J(w(g)) with respect to EVERY Dirichlet value at a converged state ``w`` (F(w; g) = 0),
+    for the price of one adjoint solve and one raw-Jacobian pass.  With f the free and B the constrained dofs, the residual is
+
+        F_f(w; g) = R_raw(w)_f + J0[f,B] (g - w_B),        F_B(w; g) = w_B - g,
+
+    so at a state that satisfies its data (w_B = g) the assembled operator is A = [[J0[f,f], 0], [0, I]] and
+    dF/dg = [J0[f,B]; -I].  With A^T lam = grad_J (lam_B = grad_J[B]) and lam~ = lam zeroed on B,
+
+        dJ/dg = -lam . dF/dg = grad_J[B] - (J0^T lam~)[B]
+
+    on the constrained dofs, and 0 on the unconstrained ones.  ``grad_J``: dJ/dw as a dof vector (numpy or device), used as
+    given on the constrained dofs too -- a row of ``functionals.reaction_force_gradient`` is not zero there.  Contract the
+    result with a direction of the data, e.g. ``dJdg @ g_inlet`` for the amplitude of an inlet profile.
+
+    Returns (dJ/dg as a device dof vector, lam, KrylovResult of the adjoint solve).  The handle is left as
+    ``reynolds_sensitivity`` leaves it: the Jacobian at w assembled, the caller's options.  Single-GPU problems."""
+    w = problem._vec(w)
+    g = problem._vec(grad_J if isinstance(grad_J, torch.Tensor) else np.asarray(grad_J, dtype=np.float64).ravel())
+    problem.jacobian(w, "ns")
+    lam, res = problem.adjoint_solve(g)
+    B = torch.from_numpy(problem.bc_mask.astype(bool)).to(lam.device)
+    lt = lam.clone()
+    lt[B] = 0.0
+    y = problem.raw_jacobian_apply(w, lt, transpose=True)
+    dJ = torch.zeros_like(g)
+    dJ[B] = g[B] - y[B]
     return dJ, lam, res
 
 
