@@ -441,7 +441,7 @@ SNS_API int sns_error_indicator(sns_handle h, const double* w_dev, const double*
  *   owner-computes pass over the node -> cell lists, 4 lanes per row, no atomics, no element scratch, a fixed summation order
  *   (bitwise reproducible).  The pressure and constrained entries of x are ignored; a time term on the handle is ignored too.
  *   SNS_E_ARG: null handle / pointer, a 2-D handle.  SNS_E_STATE: a communicator attached, a viscosity law set.
- * sns_stability_arnoldi: plain Arnoldi (no restart) on S = (J + shift B)^-1 B, whose Ritz values theta give the eigenvalues
+ * sns_stability_arnoldi: plain Arnoldi (one cycle; restarts: below) on S = (J + shift B)^-1 B, whose Ritz values theta give the eigenvalues
  *   lambda = shift - 1/theta of J x = -lambda B x nearest the shift (x ~ exp(lambda t): Re lambda > 0 is an unstable mode).
  *   With shift > 0 the time term (sigma = shift, theta = 0, d = -shift u(w)) is set, sns_jacobian runs at w, the start vector
  *   (column 0 of V on entry) is zeroed on the constrained dofs, sent through S once (out of the null space of B) and
@@ -485,7 +485,28 @@ SNS_API int sns_error_indicator(sns_handle h, const double* w_dev, const double*
  *   communicator attached, a viscosity law, a time term, a body force (J then depends on f through dM/dw(w, -f), a second
  *   contraction that is not built) or a backflow coefficient (sns_set_boundary_flow: quadratic in u, its Hessian is not built)
  *   set.  A boundary traction alone (constant in w) and a viscosity field are allowed.
- * Not built: restarted or Krylov-Schur iterations, complex or negative shifts; of the sensitivities, base flows with a body
+ * Thick restart (Stewart's Krylov-Schur) of the process above, for meshes on which (m + 1) basis vectors at m = 64 do not fit
+ *   or modes that 64 steps do not reach.  One restart is: the ordered real Schur form H[:m, :m] = Z T Z^T on the host with the
+ *   `keep` Ritz values of largest modulus (the eigenvalues nearest the shift) leading (solver.py: krylov_schur_truncate; this
+ *   library holds no C implementation of it, sns_host_hessenberg_eigs gives the Ritz values); Q = blockdiag(Z[:, :k], 1) and
+ *   H_k = [T[:k, :k]; H[m, :m] Z[:, :k]]; sns_basis_rotate(h, m + 1, k + 1, Q, V); H_k written into the leading (k + 1) x k
+ *   block of H (row stride m); sns_stability_arnoldi_extend(..., k, m, ...).
+ * sns_basis_rotate: V[:, 0:n_out] <- V[:, 0:n_in] Q in place, then columns n_out .. n_in - 1 of V zeroed; columns from n_in on
+ *   are not touched.  V_dev by columns with leading dimension 4*n_local, Q_host n_in x n_out, row major.  One lane per dof holds
+ *   its n_in values in registers before it stores any (no second copy of V exists at any time), Q is staged in LDS, every sum
+ *   runs over the columns in ascending order: no atomics, bitwise reproducible, one streaming pass (n_in * 4*n_local * 8 B read
+ *   and as many written).  Works on any handle (a vector operation on the handle's stream); synchronises the stream before it
+ *   returns.  SNS_E_ARG: null handle / pointer, n_in outside [1, 65], n_out outside [1, n_in], a non-finite entry of Q.
+ * sns_stability_arnoldi_extend: continues a Krylov decomposition from column k.  On entry columns 0 .. k of V are orthonormal
+ *   with zeros on the constrained dofs and the leading (k + 1) x k block of H (row stride m) satisfies S V_k = V_{k+1} H_k --
+ *   the caller's contract, not verified.  The operator is assembled, flipped for left != 0, set up and given back exactly as by
+ *   sns_stability_arnoldi[_left] (stateless per call on purpose: the handle ends in the same state); there is no start vector
+ *   treatment; the rest of H is zeroed and steps j = k .. m - 1 run as above, orthogonalising against all j + 1 columns, so
+ *   column j of H is full above the subdiagonal.  m_done = k + the steps completed; reasons, breakdown and the zeroing of the
+ *   columns not reached as above.  Errors as sns_stability_arnoldi[_left] by `left`, and SNS_E_ARG for k outside [1, m - 1]
+ *   (after the other arguments, before the state).
+ * Not built: explicit locking / deflation of converged pairs, selections other than "nearest the shift", a C implementation of
+ * the ordered Schur form, complex or negative shifts; of the sensitivities, base flows with a body
  * force or a backflow term, the sensitivity to forcing on Dirichlet nodes, and the exact form of E = D_w[B^T z][x] (the
  * forcing sensitivity takes it by a central difference of sns_mass_apply_transpose). */
 SNS_API int sns_mass_apply(sns_handle h, const double* w_dev, const double* x_dev, double* y_dev);
@@ -498,6 +519,12 @@ SNS_API int sns_stability_arnoldi_left(sns_handle h, const double* w_dev, double
                                        double* H_host /* (m+1) x m, row major */, int* m_done, int* total_ksp_its, int* reason);
 SNS_API int sns_jacobian_state_gradient(sns_handle h, const double* w_dev, const double* x_dev, const double* z_dev,
                                         double c_jac, double c_mass, double* g_dev);
+SNS_API int sns_stability_arnoldi_extend(sns_handle h, const double* w_dev, double shift, int k, int m, double breakdown_rel,
+                                         int left, double* V_dev /* (m+1) * 4*n_local; columns 0 .. k on entry */,
+                                         double* H_host /* (m+1) x m, row major; the leading (k+1) x k block on entry */,
+                                         int* m_done, int* total_ksp_its, int* reason);
+SNS_API int sns_basis_rotate(sns_handle h, int n_in, int n_out, const double* Q_host /* n_in x n_out, row major */,
+                             double* V_dev /* n_in * 4*n_local */);
 /* The raw Jacobian and the Dirichlet values of a live handle (no counterpart in the reference).
  * sns_raw_jacobian_apply: y = J0(w) x for transposed == 0, y = J0(w)^T x otherwise, J0 = dR_raw/dw the exact Gateaux derivative
  *   of the raw residual sns_residual_moments sums -- without lifting and without the Dirichlet rows' w_B - g.  With K_t the

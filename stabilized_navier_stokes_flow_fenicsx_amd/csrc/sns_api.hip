@@ -637,16 +637,19 @@ int sns_set_dirichlet_values(sns_handle h, const double* bc_val_host) {
     return SNS_OK;
 }
 
-// both Arnoldi entry points (`who`: the name in front of the message).  SREQ_ARNOLDI_LEFT: the operator is flipped between the
-// assembly and the set-up and given back afterwards, as sns_adjoint_solve does
-static int stability_arnoldi(const char* who, sns_ctx* h, policy::StabilityRequest request, const double* w, double shift, int m,
-                             double breakdown_rel, double* V, double* H, int* m_done, int* total_ksp_its, int* reason) {
+// the Arnoldi entry points (`who`: the name in front of the message).  SREQ_ARNOLDI_LEFT: the operator is flipped between the
+// assembly and the set-up and given back afterwards, as sns_adjoint_solve does.  k = 0: a fresh process; k >= 1
+// (sns_stability_arnoldi_extend): the caller's decomposition continued from column k
+static int stability_arnoldi(const char* who, sns_ctx* h, policy::StabilityRequest request, const double* w, double shift, int k, int m,
+                             double breakdown_rel, double* V, double* H, int* m_done, int* total_ksp_its, int* reason,
+                             bool extend = false) {
     if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
         set_error(std::string(who) + ": null handle or pointer");
         return SNS_E_ARG;
     }
     SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_ARG));
-    SNS_TRY(refused(who, policy::check_arnoldi_args({m, shift, breakdown_rel})));
+    SNS_TRY(refused(who, extend ? policy::check_arnoldi_extend_args({m, shift, breakdown_rel}, k)
+                                : policy::check_arnoldi_args({m, shift, breakdown_rel})));
     SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_STATE));
     const bool left = request == policy::SREQ_ARNOLDI_LEFT;
     // J + shift B = the assembly with u_t = shift (u - u(w)): sigma = shift, theta = 0, d = -shift u(w) (pressure slots unused)
@@ -664,19 +667,36 @@ static int stability_arnoldi(const char* who, sns_ctx* h, policy::StabilityReque
         flipped = rc == SNS_OK;
     }
     if (rc == SNS_OK) rc = ensure_hierarchy(h);
-    if (rc == SNS_OK) rc = arnoldi_run(h, w, left, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+    if (rc == SNS_OK) rc = arnoldi_run(h, w, left, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
     return give_back(h, rc, flipped, shift > 0.0);       // (the assembled matrix stays J + shift B)
 }
 
 int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H, int* m_done,
                           int* total_ksp_its, int* reason) {
-    return stability_arnoldi("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, w, shift, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+    return stability_arnoldi("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, w, shift, 0, m, breakdown_rel, V, H, m_done, total_ksp_its,
+                             reason);
 }
 
 int sns_stability_arnoldi_left(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,
                                int* m_done, int* total_ksp_its, int* reason) {
-    return stability_arnoldi("sns_stability_arnoldi_left", h, policy::SREQ_ARNOLDI_LEFT, w, shift, m, breakdown_rel, V, H, m_done,
+    return stability_arnoldi("sns_stability_arnoldi_left", h, policy::SREQ_ARNOLDI_LEFT, w, shift, 0, m, breakdown_rel, V, H, m_done,
                              total_ksp_its, reason);
+}
+
+int sns_stability_arnoldi_extend(sns_handle h, const double* w, double shift, int k, int m, double breakdown_rel, int left, double* V,
+                                 double* H, int* m_done, int* total_ksp_its, int* reason) {
+    return stability_arnoldi("sns_stability_arnoldi_extend", h, left ? policy::SREQ_ARNOLDI_LEFT : policy::SREQ_ARNOLDI, w, shift, k, m,
+                             breakdown_rel, V, H, m_done, total_ksp_its, reason, true);
+}
+
+int sns_basis_rotate(sns_handle h, int n_in, int n_out, const double* Q, double* V) {
+    const char* who = "sns_basis_rotate";
+    if (!h || !Q || !V) { set_error("sns_basis_rotate: null handle or pointer"); return SNS_E_ARG; }
+    if (n_in < 1 || n_in > policy::STABILITY_M_MAX + 1) { set_error(std::string(who) + ": n_in must lie in [1, 65]"); return SNS_E_ARG; }
+    if (n_out < 1 || n_out > n_in) { set_error(std::string(who) + ": n_out must lie in [1, n_in]"); return SNS_E_ARG; }
+    for (int t = 0; t < n_in * n_out; ++t)
+        if (!(Q[t] - Q[t] == 0.0)) { set_error(std::string(who) + ": non-finite entry of Q"); return SNS_E_ARG; }
+    return basis_rotate(h, n_in, n_out, Q, V);
 }
 
 int sns_spmv(sns_handle h, const double* x, double* y) {

@@ -322,11 +322,13 @@ int residual_shape_gradient(sns_ctx* h, const double* w, const double* lam, doub
 int recover_gradient(sns_ctx* h, const double* w, double* G, double* D);
 int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, double* gnorm2);
 // csrc/sns_stability.hip: the mass passes y = B(w) x and y = B(w)^T z, and the shift-invert Arnoldi process (left: on
-// (J + shift B)^-T B^T, with the transposed operator in the handle)
+// (J + shift B)^-T B^T, with the transposed operator in the handle) from column k0 (0: a fresh process; >= 1: the caller's
+// decomposition continued), and the in-place compression of its basis V[:, 0:n_out] <- V[:, 0:n_in] Q (Q on the host)
 int mass_apply(sns_ctx* h, const double* w, const double* x, double* y);
 int mass_apply_transpose(sns_ctx* h, const double* w, const double* z, double* y);
-int arnoldi_run(sns_ctx* h, const double* w, bool left, int m, double breakdown_rel, double* V, double* H, int* m_done,
+int arnoldi_run(sns_ctx* h, const double* w, bool left, int k0, int m, double breakdown_rel, double* V, double* H, int* m_done,
                 int* total_its, int* reason);
+int basis_rotate(sns_ctx* h, int n_in, int n_out, const double* Q, double* V);
 // csrc/sns_hessian.hip: g = grad_w [ z~^T (c_jac J(w) + c_mass B(w)) x~ ] by one element pass (uses the element scratch Fe)
 int jacobian_state_gradient(sns_ctx* h, const double* w, const double* x, const double* z, double c_jac, double c_mass, double* g);
 // csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)

@@ -586,6 +586,14 @@ inline Verdict check_arnoldi_args(const ArnoldiArgs& a) {
     if (!(a.breakdown_rel > 0.0) || !(a.breakdown_rel < 1.0)) return {SNS_E_ARG, "breakdown_rel must lie in (0, 1)"};
     return {};
 }
+// ... and of its continuation from column k (sns_stability_arnoldi_extend): those, then k in [1, m - 1].  The call is asked
+// as SREQ_ARNOLDI / SREQ_ARNOLDI_LEFT: it is refused where they are, and has no kind of its own
+inline Verdict check_arnoldi_extend_args(const ArnoldiArgs& a, int k) {
+    const Verdict v = check_arnoldi_args(a);
+    if (v.error != SNS_OK) return v;
+    if (k < 1 || k > a.m - 1) return {SNS_E_ARG, "k must lie in [1, m - 1]"};
+    return {};
+}
 // ... and the coefficients of the Hessian pass
 inline Verdict check_state_gradient_args(double c_jac, double c_mass) {
     if (!(c_jac - c_jac == 0.0) || !(c_mass - c_mass == 0.0)) return {SNS_E_ARG, "the coefficients must be finite"};
@@ -612,6 +620,10 @@ inline Verdict check_boundary_request(BoundaryRequest request, const HandleFacts
 inline Verdict check_stability_request(StabilityRequest request, const HandleFacts& f, const ArnoldiArgs& a = {}) {
     const bool arnoldi = request == SREQ_ARNOLDI || request == SREQ_ARNOLDI_LEFT;
     return check_request(FAMILY_STABILITY, request, f, arnoldi ? check_arnoldi_args(a) : Verdict{});
+}
+// (tests/extend_request_main.cpp) request: SREQ_ARNOLDI or SREQ_ARNOLDI_LEFT
+inline Verdict check_stability_extend_request(StabilityRequest request, const HandleFacts& f, const ArnoldiArgs& a, int k) {
+    return check_request(FAMILY_STABILITY, request, f, check_arnoldi_extend_args(a, k));
 }
 inline Verdict check_state_gradient_request(const HandleFacts& f, double c_jac = 1.0, double c_mass = 0.0) {
     return check_request(FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, f, check_state_gradient_args(c_jac, c_mass));

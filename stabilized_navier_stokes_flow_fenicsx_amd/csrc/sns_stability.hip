@@ -28,9 +28,22 @@
 //                  the handle holds is the transposed one (the entry point flips it and flips it back); nothing else differs.
 //                  Its Ritz vectors z satisfy z^T J = -lambda z^T B; the matrices are real, the pairing is z^T B x unconjugated.
 // The sensitivity of an eigenvalue to the base flow and to a steady forcing contracts the modes with the Hessian of the residual:
-// csrc/sns_hessian.hip.  Out of scope: restarted or Krylov-Schur iterations; complex or negative shifts; of the sensitivities,
-// base flows with a body force or a backflow term, forcing on Dirichlet nodes and the exact form of E = D_w[B^T z][x]; 2-D and
-// partitioned handles; the Carreau law.
+// csrc/sns_hessian.hip.
+// Thick restart (Stewart's Krylov-Schur; sns_stability_arnoldi_extend, sns_basis_rotate): the ordered Schur form of H is taken on
+// the host by the caller (solver.py: krylov_schur_truncate), the device does the two things that touch V:
+//   k_basis_rotate V[:, 0:n_out] <- V[:, 0:n_in] Q in place, columns n_out .. n_in - 1 zeroed.  Rows are independent: one lane owns
+//                  one dof, loads its n_in values into registers (a compile-time-indexed row of NMAX = 17, 33 or 65 doubles,
+//                  coalesced per column across the wave), and only then forms and stores the n_out outputs -- no lane stores a
+//                  column another output of its row still has to read, and no other lane reads its row.  Q sits in LDS (at
+//                  most 65 x 65 doubles = 33.8 KB), read as a broadcast.  Every sum runs over the columns in ascending order:
+//                  no atomics, bitwise reproducible.  One streaming pass: reads and writes n_in * ndof * 8 B each.
+//   arnoldi_run    with a first column k0 >= 1 continues a Krylov decomposition S V_k = V_{k+1} H_k the caller holds: no start
+//                  vector treatment, the leading (k0 + 1) x k0 block of H kept, steps j = k0 .. m - 1 as ever.  Gram-Schmidt runs
+//                  against all j + 1 columns, so the columns of H are full above the subdiagonal and its row k0 is full.
+// Out of scope: explicit locking / deflation of converged pairs; selections other than "nearest the shift"; a C implementation of
+// the ordered Schur form (C callers have the two device primitives and sns_host_hessenberg_eigs); complex or negative shifts; of
+// the sensitivities, base flows with a body force or a backflow term, forcing on Dirichlet nodes and the exact form of
+// E = D_w[B^T z][x]; 2-D and partitioned handles; the Carreau law.
 #include "sns_ctx.h"
 
 namespace sns {
@@ -230,6 +243,28 @@ __global__ __launch_bounds__(256) void k_zero_constrained(int64_t ndof, const ui
         if (bc_mask[i]) x[i] = 0.0;
 }
 
+// V[:, 0:n_out] <- V[:, 0:n_in] Q, columns n_out .. n_in - 1 zeroed; Q: n_in x n_out, row major.  One lane per row; the row
+// lives in registers (every index into `row` is a compile-time constant) before the first store.  n_in <= NMAX.
+template <int NMAX>
+__global__ __launch_bounds__(256) void k_basis_rotate(int64_t ld, int n_in, int n_out, const double* __restrict__ Q, double* V) {
+    extern __shared__ double Qs[];
+    for (int t = threadIdx.x; t < n_in * n_out; t += blockDim.x) Qs[t] = Q[t];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ld) return;
+    double row[NMAX];
+#pragma unroll
+    for (int c = 0; c < NMAX; ++c) row[c] = c < n_in ? V[(size_t)c * ld + i] : 0.0;
+    for (int j = 0; j < n_out; ++j) {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < NMAX; ++c)
+            if (c < n_in) acc += row[c] * Qs[c * n_out + j];
+        V[(size_t)j * ld + i] = acc;
+    }
+    for (int j = n_out; j < n_in; ++j) V[(size_t)j * ld + i] = 0.0;
+}
+
 // y = B(w) x, or with `left` y = B(w)^T x
 void launch_mass(sns_ctx* h, bool left, const double* w, const double* x, double* y) {
     if (h->n == 0) return;
@@ -262,21 +297,44 @@ int mass_apply_transpose(sns_ctx* h, const double* w, const double* z, double* y
     return sync_stream(h);
 }
 
+// V[:, 0:n_out] <- V[:, 0:n_in] Q in place over ld_of(h) rows (Q on the host, n_in x n_out, row major; checked by the entry
+// point); columns n_out .. n_in - 1 are zeroed.  Synchronises.
+int basis_rotate(sns_ctx* h, int n_in, int n_out, const double* Q, double* V) {
+    const int64_t ld = ld_of(h);
+    const size_t nq = (size_t)n_in * n_out;
+    DevBuf<double> q;
+    SNS_TRY(q.alloc(nq));
+    HIP_TRY(hipMemcpyAsync(q, Q, nq * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (ld > 0) {
+        const dim3 grid((unsigned)((ld + 255) / 256));
+        const size_t lds = nq * sizeof(double);
+        if (n_in <= 17) hipLaunchKernelGGL((k_basis_rotate<17>), grid, dim3(256), lds, h->stream, ld, n_in, n_out, q, V);
+        else if (n_in <= 33) hipLaunchKernelGGL((k_basis_rotate<33>), grid, dim3(256), lds, h->stream, ld, n_in, n_out, q, V);
+        else hipLaunchKernelGGL((k_basis_rotate<policy::STABILITY_M_MAX + 1>), grid, dim3(256), lds, h->stream, ld, n_in, n_out, q, V);
+        HIP_TRY(hipGetLastError());
+    }
+    return sync_stream(h);                                 // (q and the caller's Q live until here)
+}
+
 // The Arnoldi process on S = (J + shift B)^-1 B; the operator J + shift B is assembled and the hierarchy exists (the entry
 // point).  V: (m + 1) columns of 4*n doubles, column 0 the start vector; H: (m + 1) x m, row major, zero beyond m_done.
 // *reason: 1 all m steps done, 2 breakdown (the Krylov space is invariant: m_done columns, H[m_done][m_done - 1] = 0 and the
 // column of V behind them zero), < 0 the KSP reason of an inner solve that did not converge (m_done = the steps completed).
 // left: the process on (J + shift B)^-T B^T -- the mass pass is the transposed one, and the entry point has flipped the operator.
-int arnoldi_run(sns_ctx* h, const double* w, bool left, int m, double breakdown_rel, double* V, double* H, int* m_done, int* total_its,
-                int* reason) {
+// k0 >= 1: continue the decomposition S V_k0 = V_{k0+1} H_k0 the caller holds in columns 0 .. k0 of V and the leading
+// (k0 + 1) x k0 block of H (kept; the rest of H is zeroed): no start vector treatment, steps j = k0 .. m - 1, m_done starts at k0.
+int arnoldi_run(sns_ctx* h, const double* w, bool left, int k0, int m, double breakdown_rel, double* V, double* H, int* m_done,
+                int* total_its, int* reason) {
     const int64_t ld = ld_of(h);
     const int g = std::max(1, vec_grid(ld));
     constexpr int CS = policy::STABILITY_M_MAX + 8;        // stride of one coefficient block (chunks of 8)
     DevBuf<double> b, co;                                  // b = B v; co: pass-1 and pass-2 coefficients, then (w.w, .) before and after
     SNS_TRY(b.alloc((size_t)ld));
     SNS_TRY(co.alloc((size_t)2 * CS + 4));
-    std::fill(H, H + (size_t)(m + 1) * m, 0.0);
-    *m_done = 0;
+    for (int r = 0; r < m + 1; ++r)
+        for (int c = 0; c < m; ++c)
+            if (r > k0 || c >= k0) H[(size_t)r * m + c] = 0.0;
+    *m_done = k0;
     *total_its = 0;
     *reason = 1;
     // w = S v, from a zero guess; false: the inner solve did not converge (*reason holds why)
@@ -296,26 +354,28 @@ int arnoldi_run(sns_ctx* h, const double* w, bool left, int m, double breakdown_
         hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, h->stream, ld, v, v, h->partial);
         reduce_local(h, g, 2, dst);
     };
-    // the start vector: constrained dofs zeroed, one application of S (it leaves the null space of B), unit norm
     bool ok = true;
-    double* v1 = V + (size_t)ld;
-    hipLaunchKernelGGL(k_zero_constrained, dim3(g), dim3(256), 0, h->stream, ld, h->bc_mask, V);
-    SNS_TRY(apply_S(V, v1, &ok));
-    if (!ok) {
-        HIP_TRY(hipMemsetAsync(v1, 0, (size_t)m * ld * sizeof(double), h->stream));
-        return sync_stream(h);
-    }
     double hv[2 * CS + 4];
-    norm_sq(v1, co + 2 * CS);
-    SNS_TRY(fetch(h, co + 2 * CS, 2, hv));
-    const double n0 = std::sqrt(hv[0]);
-    if (!(n0 > 0.0) || !std::isfinite(n0)) {               // S v = 0: the start vector lies in the null space of B
-        *reason = 2;
-        HIP_TRY(hipMemsetAsync(V, 0, (size_t)(m + 1) * ld * sizeof(double), h->stream));
-        return sync_stream(h);
+    if (k0 == 0) {
+        // the start vector: constrained dofs zeroed, one application of S (it leaves the null space of B), unit norm
+        double* v1 = V + (size_t)ld;
+        hipLaunchKernelGGL(k_zero_constrained, dim3(g), dim3(256), 0, h->stream, ld, h->bc_mask, V);
+        SNS_TRY(apply_S(V, v1, &ok));
+        if (!ok) {
+            HIP_TRY(hipMemsetAsync(v1, 0, (size_t)m * ld * sizeof(double), h->stream));
+            return sync_stream(h);
+        }
+        norm_sq(v1, co + 2 * CS);
+        SNS_TRY(fetch(h, co + 2 * CS, 2, hv));
+        const double n0 = std::sqrt(hv[0]);
+        if (!(n0 > 0.0) || !std::isfinite(n0)) {           // S v = 0: the start vector lies in the null space of B
+            *reason = 2;
+            HIP_TRY(hipMemsetAsync(V, 0, (size_t)(m + 1) * ld * sizeof(double), h->stream));
+            return sync_stream(h);
+        }
+        hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, ld, 1.0 / n0, v1, V);
     }
-    hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, ld, 1.0 / n0, v1, V);
-    for (int j = 0; j < m; ++j) {
+    for (int j = k0; j < m; ++j) {
         double* wj = V + (size_t)(j + 1) * ld;
         SNS_TRY(apply_S(V + (size_t)j * ld, wj, &ok));
         if (!ok) {

@@ -580,7 +580,10 @@ def _stability(P, w):
     """SNS_STABILITY=<n_modes>[,<shift>] (opt-in; single-GPU runs): after the solve, the leading eigenvalues of the transient
     operator linearised at the state ``w`` (``solver.linear_stability``, the 3-D NS form at the problem's Reynolds number), one
     printed line per converged mode: lambda, the frequency Im lambda / 2 pi and the residual estimate.  Re lambda > 0 is a
-    growing mode: the steady state is unstable.  Nothing without the switch: files and stdout stay as they are."""
+    growing mode: the steady state is unstable.  Nothing without the switch: files and stdout stay as they are.
+    SNS_STABILITY_RESTARTS=<max_restarts>[,<m>[,<keep>]] beside it: the thick-restarted process of ``linear_stability`` (a basis
+    of m + 1 vectors instead of 65; m defaults to 64, keep to the function's default) and one more printed line, the restarts
+    taken.  Without that variable the call and the output are what they are without it."""
     spec = os.environ.get("SNS_STABILITY", "")
     if not spec:
         return None
@@ -593,13 +596,26 @@ def _stability(P, w):
     from .solver import SnsError, linear_stability, print_stability
     sens = os.environ.get("SNS_STABILITY_SENSITIVITY", "0") == "1"
     forcing = os.environ.get("SNS_STABILITY_FORCING", "0") == "1"
+    restart = {}
+    rspec = os.environ.get("SNS_STABILITY_RESTARTS", "")
+    if rspec:
+        rparts = rspec.split(",")
+        restart = dict(max_restarts=int(rparts[0]))
+        if len(rparts) > 1:
+            restart["m"] = int(rparts[1])
+        if len(rparts) > 2:
+            restart["keep"] = int(rparts[2])
     try:
-        res = linear_stability(P, w, n_modes=n_modes, shift=shift, left=True) if sens or forcing else linear_stability(P, w, n_modes=n_modes, shift=shift)
+        res = (linear_stability(P, w, n_modes=n_modes, shift=shift, left=True, **restart) if sens or forcing
+               else linear_stability(P, w, n_modes=n_modes, shift=shift, **restart))
     except SnsError as e:                                 # (a viscosity law, a 2-D problem: the library says which)
         if _rank() == 0:
             print(f"SNS_STABILITY: skipped ({e})", flush=True)
         return None
     print_stability(res, _rank())
+    if restart and _rank() == 0:
+        print(f"Stability restarts: right {res.restarts}" + (f", left {res.left_restarts}" if sens or forcing else "") +
+              f" of at most {restart['max_restarts']} (reason {res.reason}, m_done {res.m_done})", flush=True)
     if sens:
         _stability_sensitivity(P, w, res)
     if forcing:

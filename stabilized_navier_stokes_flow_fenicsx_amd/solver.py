@@ -75,6 +75,9 @@ class StabilityResult:
     left_m_done: int = 0
     left_ksp_its: int = 0
     left_reason: int = 0
+    # linear_stability(max_restarts > 0) only: thick restarts taken by the right and by the left process
+    restarts: int = 0
+    left_restarts: int = 0
 
 
 class FlowProblem:
@@ -447,6 +450,45 @@ class FlowProblem:
         check(run(self.h, _ptr(w), float(shift), m, float(breakdown_rel), _ptr(V), H.ctypes.data, C.byref(done), C.byref(its),
                   C.byref(reason)))
         return V, H, ArnoldiResult(done.value, reason.value, its.value)
+
+    def stability_arnoldi_extend(self, w, V, H, k: int, shift: float = 0.0, breakdown_rel: float = 1e-6, side: str = "right"):
+        """Continue the Krylov decomposition a previous ``stability_arnoldi`` (or this method) left in ``V`` (device tensor
+        (m + 1, ndof)) and ``H`` (numpy (m + 1, m)) from column ``k`` (sns_stability_arnoldi_extend): rows 0 .. k of V orthonormal
+        with zeros on the constrained dofs, H[:k + 1, :k] with S V_k = V_{k+1} H_k -- what ``krylov_schur_truncate`` and
+        ``basis_rotate`` leave; the contract is the caller's and is not verified.  Both are modified in place: steps k .. m - 1
+        run as in ``stability_arnoldi`` (same ``w``, ``shift`` and ``side`` as the run being continued), orthogonalising
+        against every earlier column, so H is no longer Hessenberg: use ``krylov_ritz_pairs``.  Returns ``ArnoldiResult``
+        (m_done = k + the steps completed; ksp_its of this call).  The handle ends as after ``stability_arnoldi``."""
+        if side not in ("right", "left"):
+            raise ValueError("side must be 'right' or 'left'")
+        if not (isinstance(H, np.ndarray) and H.dtype == np.float64 and H.ndim == 2 and H.flags.c_contiguous and
+                H.shape[0] == H.shape[1] + 1):
+            raise ValueError("H must be the C-contiguous float64 (m + 1, m) array of stability_arnoldi")
+        m = H.shape[1]
+        if not (isinstance(V, torch.Tensor) and V.dtype == torch.float64 and V.shape == (m + 1, self.ndof) and V.is_contiguous()
+                and V.device.type == "cuda"):
+            raise ValueError("V must be the contiguous float64 (m + 1, ndof) device tensor of stability_arnoldi")
+        w = self._vec(w)
+        done, its, reason = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.sns_stability_arnoldi_extend(self.h, _ptr(w), float(shift), int(k), m, float(breakdown_rel), int(side == "left"),
+                                                    _ptr(V), H.ctypes.data, C.byref(done), C.byref(its), C.byref(reason)))
+        return ArnoldiResult(done.value, reason.value, its.value)
+
+    def basis_rotate(self, V, Q):
+        """``V[:n_out] <- Q^T V[:n_in]`` in place, i.e. the basis vectors (the rows of ``V``, as ``stability_arnoldi`` returns
+        them) recombined by the columns of ``Q`` (numpy (n_in, n_out), n_out <= n_in <= 65), then rows n_out .. n_in - 1 zeroed;
+        rows from n_in on stay (sns_basis_rotate, k_basis_rotate).  No second copy of V is made; bitwise reproducible."""
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        if Q.ndim != 2:
+            raise ValueError("Q must be (n_in, n_out)")
+        n_in, n_out = Q.shape
+        if not (isinstance(V, torch.Tensor) and V.dtype == torch.float64 and V.ndim == 2 and V.shape[1] == self.ndof and
+                V.is_contiguous() and V.device.type == "cuda"):
+            raise ValueError("V must be a contiguous float64 (rows, ndof) device tensor")
+        if V.shape[0] < n_in:
+            raise ValueError(f"V has {V.shape[0]} rows, Q asks for {n_in}")
+        check(self.lib.sns_basis_rotate(self.h, n_in, n_out, Q.ctypes.data, _ptr(V)))
+        return V
 
     def spmv(self, x, out=None) -> torch.Tensor:
         x = self._vec(x)
@@ -1337,6 +1379,64 @@ def ritz_pairs(H, m_done: int, shift: float = 0.0):
     return lam[order], Y[:, order], est[order]
 
 
+def krylov_ritz_pairs(H, m_done: int, shift: float = 0.0):
+    """``ritz_pairs`` for the H of a Krylov decomposition S V_k = V_k H[:k, :k] + v_{k+1} H[k, :k] whose last row is full -- what
+    ``FlowProblem.stability_arnoldi_extend`` leaves after a thick restart: the same ``(lam, Y, est)`` in the same order, with
+    est[j] = |H[k, :k] y_j| / |theta_j|.  On a Hessenberg H the estimate is the one of ``ritz_pairs`` up to rounding."""
+    H = np.asarray(H, dtype=np.float64)
+    k = int(m_done)
+    if k < 1:
+        return np.zeros(0, complex), np.zeros((0, 0), complex), np.zeros(0)
+    theta, Y = np.linalg.eig(H[:k, :k])
+    Y = Y / np.linalg.norm(Y, axis=0)
+    coupling = np.abs(H[k, :k] @ Y) if H.shape[0] > k else np.zeros(k)
+    zero = theta == 0.0
+    safe = np.where(zero, 1.0, theta)
+    lam = np.where(zero, -np.inf, shift - 1.0 / safe)
+    est = np.where(zero, np.inf, coupling / np.abs(safe))
+    order = np.lexsort((-lam.imag, -lam.real))
+    return lam[order], Y[:, order], est[order]
+
+
+def krylov_schur_truncate(H, m_done: int, keep: int):
+    """The host half of one thick restart (Stewart's Krylov-Schur; pure numpy and scipy.linalg): with m = ``m_done`` and the
+    decomposition S V_m = V_m H[:m, :m] + v_{m+1} H[m, :m], the ordered real Schur form H[:m, :m] = Z T Z^T with the ``keep``
+    Ritz values of largest modulus -- the eigenvalues nearest the shift -- leading.  A conjugate pair is never split: if the
+    cut falls inside one, one fewer is kept (one more if that would leave none).  Returns ``(k, Q, Hk)``:
+    Q = blockdiag(Z[:, :k], 1), (m + 1) x (k + 1), for ``FlowProblem.basis_rotate``, and Hk = [T[:k, :k]; H[m, :m] Z[:, :k]],
+    (k + 1) x k, the leading block of the H that ``stability_arnoldi_extend`` continues: S (V Q)_k = (V Q)_{k+1} Hk.  The whole
+    last row of H enters: after the first restart it is full.  1 <= keep <= m - 1."""
+    import scipy.linalg as sla
+    H = np.asarray(H, dtype=np.float64)
+    m, keep = int(m_done), int(keep)
+    if not (2 <= m <= H.shape[1] and H.shape[0] > m):
+        raise ValueError("m_done must lie in [2, m] and H must hold row m_done")
+    if not 1 <= keep <= m - 1:
+        raise ValueError("keep must lie in [1, m_done - 1]")
+    A = H[:m, :m]
+    theta = np.linalg.eigvals(A)
+    theta = theta[np.argsort(-np.abs(theta), kind="stable")]
+    pair_tol = 1e-12 * max(np.abs(theta[0]), np.finfo(float).tiny)
+
+    def splits(k):                                         # theta[k - 1] and theta[k] are the two members of one pair
+        return theta[k - 1].imag != 0.0 and abs(theta[k] - np.conj(theta[k - 1])) <= pair_tol
+
+    k = keep
+    if splits(k):
+        k = k - 1 if k > 1 else 2
+    if not 1 <= k <= m - 1:
+        raise ValueError("no cut between 1 and m_done - 1 that keeps a conjugate pair together")
+    cut = 0.5 * (np.abs(theta[k - 1]) + np.abs(theta[k]))
+    T, Z, sdim = sla.schur(A, output="real", sort=lambda re, im: np.hypot(re, im) > cut)
+    if sdim != k or (T[k, k - 1] != 0.0):
+        raise np.linalg.LinAlgError(f"the ordered Schur form kept {sdim} Ritz values, not {k}: two moduli at the cut coincide")
+    Q = np.zeros((m + 1, k + 1))
+    Q[:m, :k] = Z[:, :k]
+    Q[m, k] = 1.0
+    Hk = np.vstack([T[:k, :k], H[m, :m] @ Z[:, :k]])
+    return k, Q, Hk
+
+
 def pair_left_right(lam_right, lam_left, shift: float = 0.0, rtol: float = 1e-5):
     """Which left Ritz value belongs to which right one (pure numpy): ``partner[k]`` = the index into ``lam_left`` of the value
     nearest ``lam_right[k]``, or -1.  A pair is accepted only if the two differ by at most ``rtol`` |lam - shift| -- both sides
@@ -1372,8 +1472,37 @@ def mode_pairing(problem: FlowProblem, w, z, x):
     return complex(torch.sum(z * Bx))
 
 
+def default_keep(m: int, n_modes: int) -> int:
+    """How many Ritz directions a thick restart of ``linear_stability`` keeps by default: min(m - 2, max(n_modes + 2, m // 2))."""
+    return min(int(m) - 2, max(int(n_modes) + 2, int(m) // 2))
+
+
+def _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, side, breakdown_rel):
+    """One side of ``linear_stability(max_restarts > 0)``: ``stability_arnoldi``, then estimates, truncate, ``basis_rotate``,
+    ``stability_arnoldi_extend`` until the ``n_modes`` Ritz pairs of largest |theta| (nearest the shift) all have an estimate
+    <= tol, ``max_restarts`` is reached, the space is invariant (reason 2) or an inner solve failed (reason < 0).  Returns
+    (V, H, ArnoldiResult with the Krylov iterations of all cycles, restarts)."""
+    V, H, res = problem.stability_arnoldi(w, shift=shift, m=m, side=side, breakdown_rel=breakdown_rel)
+    its, restarts = res.ksp_its, 0
+    while res.reason == 1 and restarts < max_restarts:
+        lam, _, est = krylov_ritz_pairs(H, res.m_done, shift)
+        with np.errstate(invalid="ignore"):
+            lead = np.argsort(np.abs(lam - shift), kind="stable")[:max(0, int(n_modes))]
+        if (est[lead] <= tol).all():
+            break
+        k, Q, Hk = krylov_schur_truncate(H, res.m_done, keep)
+        problem.basis_rotate(V, Q)
+        H[:] = 0.0
+        H[:k + 1, :k] = Hk
+        res = problem.stability_arnoldi_extend(w, V, H, k, shift=shift, side=side, breakdown_rel=breakdown_rel)
+        its += res.ksp_its
+        restarts += 1
+    return V, H, ArnoldiResult(res.m_done, res.reason, its), restarts
+
+
 def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0.0, m: int = 64, tol: float = 1e-7,
-                     ksp_rtol: float = 1e-10, left: bool = False, pair_rtol: float = 1e-5) -> StabilityResult:
+                     ksp_rtol: float = 1e-10, left: bool = False, pair_rtol: float = 1e-5, max_restarts: int = 0,
+                     keep: Optional[int] = None, breakdown_rel: float = 1e-6) -> StabilityResult:
     """Leading eigenvalues and modes of the linearised transient operator B x_t + J x = 0 at the steady state ``w``: is the
     state stable (every Re lam < 0), and if not, at which frequency Im lam / 2 pi does it go?  ``m`` steps of shift-invert
     Arnoldi (``FlowProblem.stability_arnoldi``) with the inner tolerance ``ksp_rtol`` (the problem's options are restored
@@ -1386,16 +1515,48 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
     every selected right pair that converged with the converged left Ritz pair of nearest eigenvalue (``pair_left_right`` with
     ``pair_rtol``): ``left_converged`` says which entries have a partner, ``left_modes`` holds z = V_L y_L scaled so that
     z^T B x = 1 with the right mode as returned (unconjugated; z^T J = -lam z^T B), zero where there is none, and
-    ``left_eigenvalues`` the partner's own Ritz value.  The other fields are what they are without it."""
+    ``left_eigenvalues`` the partner's own Ritz value.  The other fields are what they are without it.
+
+    ``max_restarts > 0`` turns the process into a thick-restarted one (Stewart's Krylov-Schur), so that ``m`` can be small --
+    the basis is (m + 1) ndof doubles per side, 13 or 17 vectors instead of 65 -- and a mode that m steps do not reach is
+    iterated on instead of reported unconverged: after the first ``m`` steps, while the ``n_modes`` Ritz pairs nearest the shift
+    are not all within ``tol`` and fewer than ``max_restarts`` restarts were taken, the ``keep`` Ritz directions nearest the
+    shift are kept (``krylov_schur_truncate``; one fewer where the cut would split a conjugate pair), the basis is compressed
+    onto them in place (``FlowProblem.basis_rotate``) and the same process goes on from column ``keep``
+    (``FlowProblem.stability_arnoldi_extend``): m - keep solves per restart.  A breakdown (reason 2: the space is invariant)
+    and a failed inner solve (reason < 0) end the side as they end the unrestarted process.  The left side runs the same loop.
+    Selection, normalisation, phase, pairing and the scaling z^T B x = 1 are then those above, on the final H and V with the
+    estimates of ``krylov_ritz_pairs``; ``restarts`` / ``left_restarts`` say how many were taken, ``ksp_its`` counts all cycles.
+    ``keep`` defaults to min(m - 2, max(n_modes + 2, m // 2)): it must leave head-room above ``n_modes`` -- on the test ducts
+    (m, keep, n_modes) = (10, 4, 3) stagnated for 30 restarts where (12, 6, 4) converged in 8 -- and below m.  With
+    ``max_restarts = 0`` the function is the unrestarted one, bit for bit.  What a restarted run looks for is the ``n_modes``
+    eigenvalues NEAREST THE SHIFT and nothing else: a less stable eigenvalue farther away, which 64 unrestarted steps may reach
+    in passing (on the (6,3,3) test duct -5.35 +- 6.07i, |lam| = 8.1, behind four nearer ones), is not kept; move the shift or
+    raise ``n_modes`` and ``keep`` if the least stable mode need not be the one nearest the shift.  ``breakdown_rel`` (restarted runs only) is handed to
+    every cycle: on a space that is invariant after a few steps it has to sit above what the inner tolerance leaves of the
+    step's norm.  Not built: explicit locking / deflation of
+    converged pairs, selections other than "nearest the shift" (rightmost Re lam wanders), complex or negative shifts."""
+    max_restarts = int(max_restarts)
+    if max_restarts > 0:
+        keep = default_keep(m, n_modes) if keep is None else int(keep)
+        if not 1 <= keep <= int(m) - 1:
+            raise ValueError("keep must lie in [1, m - 1]")
     old = problem.options.ksp_rtol
     problem.set_options(ksp_rtol=float(ksp_rtol))
+    restarts = restartsL = 0
     try:
-        V, H, res = problem.stability_arnoldi(w, shift=shift, m=m)
-        if left:
-            VL, HL, resL = problem.stability_arnoldi(w, shift=shift, m=m, side="left")
+        if max_restarts > 0:
+            V, H, res, restarts = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "right", breakdown_rel)
+            if left:
+                VL, HL, resL, restartsL = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "left", breakdown_rel)
+        else:
+            V, H, res = problem.stability_arnoldi(w, shift=shift, m=m)
+            if left:
+                VL, HL, resL = problem.stability_arnoldi(w, shift=shift, m=m, side="left")
     finally:
         problem.set_options(ksp_rtol=old)
-    lam, Y, est = ritz_pairs(H, res.m_done, shift)
+    pairs_of = krylov_ritz_pairs if max_restarts > 0 else ritz_pairs
+    lam, Y, est = pairs_of(H, res.m_done, shift)
     # the converged pairs in ritz_pairs' order, then the others by their estimate: an unconverged Ritz value near theta = 0 (the
     # infinite eigenvalues of the pencil; B has no pressure columns) has an arbitrary, often huge positive, real part
     ok = est <= tol
@@ -1414,9 +1575,10 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
     else:
         modes = torch.zeros(0, problem.ndof, dtype=torch.complex128, device=V.device)
     result = StabilityResult(lam, modes, est, est <= tol, res.m_done, res.ksp_its, res.reason, float(shift))
+    result.restarts = restarts
     if not left:
         return result
-    lamL, YL, estL = ritz_pairs(HL, resL.m_done, shift)
+    lamL, YL, estL = pairs_of(HL, resL.m_done, shift)
     okL = np.nonzero(estL <= tol)[0]
     partner = pair_left_right(np.where(result.converged, lam, np.nan), lamL[okL], shift, pair_rtol)
     zs = torch.zeros_like(modes)
@@ -1430,6 +1592,7 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
         lam_left[k] = lamL[j]
     result.left_modes, result.left_converged, result.left_eigenvalues = zs, partner >= 0, lam_left
     result.left_m_done, result.left_ksp_its, result.left_reason = resL.m_done, resL.ksp_its, resL.reason
+    result.left_restarts = restartsL
     return result
 
 
