@@ -1,7 +1,8 @@
-// C-ABI layer (include/sns.h): handle life cycle, communicator attachment, the entry points of the hot path (residual /
-// Jacobian / SpMV / preconditioner / Krylov / Stokes / Newton) and the introspection getters.  Host code only launches kernels
-// and moves scalars; there is no CPU compute path.  (The setup, cycle and Krylov parts live in csrc/sns_setup.hip, sns_damping.hip,
-// sns_cycle.hip and sns_krylov.hip; shared internals in csrc/sns_ctx.h; the hierarchy's policy in csrc/sns_policy.h.)  The handle owns its
+// C-ABI layer (include/sns.h): handle life cycle, communicator attachment, the introspection getters and bench hooks, and the
+// entry points of the hot path (residual / Jacobian / SpMV / preconditioner / Krylov / Stokes / Newton / ...), which check their
+// arguments, ask the request gate and make one call into sns::.  There is no CPU compute path.  (The solve drivers live in
+// csrc/sns_solve.hip, the setup, cycle and Krylov parts in csrc/sns_setup.hip, sns_damping.hip, sns_cycle.hip and sns_krylov.hip;
+// shared internals in csrc/sns_ctx.h; the policy of the hierarchy, the gate and the drivers in csrc/sns_policy.h.)  The handle owns its
 // device memory and HIP objects by type (csrc/sns_devbuf.h): sns_destroy is `delete h`, and a failing create frees what it made.
 #include <atomic>
 
@@ -10,6 +11,7 @@
 namespace sns {
 static thread_local std::string g_err;
 void set_error(const std::string& s) { g_err = s; }
+const std::string& last_error() { return g_err; }
 
 // the allocator behind every DevBuf, and the bytes it has handed out and not got back (sns_live_device_bytes)
 static std::atomic<int64_t> g_live_bytes{0};
@@ -266,22 +268,6 @@ int sns_create_2d(sns_handle* out, int32_t n_nodes, int64_t n_tris, const double
 
 namespace {
 
-// assembles_next: the caller (a solve driver) assembles next -- with amg_aggregation = 1, 2 or 3, which aggregates the fine level by the
-// assembled operator, the hierarchy waits for that assembly (the driver calls here again once it is done); any other caller
-// without an assembled operator gets SNS_E_STATE and the handle stays as it was
-int ensure_hierarchy(sns_ctx* h, bool assembles_next = false) {
-    if (!h->pattern) return SNS_OK;                       // already built
-    if (h->opt.pc_type != SNS_PC_AMG) return SNS_OK;      // built when (if) AMG is first asked for
-    if (h->opt.amg_aggregation >= 1 && !h->has_matrix) {
-        if (assembles_next) return SNS_OK;
-        set_error("amg_aggregation = " + std::to_string(h->opt.amg_aggregation) + ": the hierarchy is built from the assembled operator; assemble first");
-        return SNS_E_STATE;
-    }
-    int rc = build_hierarchy(h, *h->pattern);
-    h->pattern.reset();
-    return rc;
-}
-
 // A verdict of csrc/sns_policy.h as the error of the entry point `who`
 int refused(const char* who, const policy::Verdict& v) {
     if (v.error != SNS_OK) set_error(std::string(who) + ": " + v.tail);
@@ -295,40 +281,6 @@ using policy::ROWS_ARG;
 using policy::ROWS_STATE;
 int allows(const sns_ctx* h, const char* who, policy::Family family, int request, policy::Rows rows = ROWS_ALL) {
     return refused(who, policy::check_request(family, request, facts_of(h), rows));
-}
-
-// Handle state borrowed for one call and given back at its end (sns_adjoint_solve, the Arnoldi entry points): the fine operator
-// flipped in place (`flipped`) and a time term set for the call (`time_term`).  rc: the call's result so far.  After a solve
-// that did not converge and after an argument or state error the handle gets the untransposed operator back, with the hierarchy
-// marked stale, and the steady form; the first error keeps its text.  A HIP or transport error leaves the device state
-// undefined: nothing more is queued.  (The Arnoldi entry points refuse partitioned handles, so SNS_E_COMM reaches here from
-// sns_adjoint_solve alone.)
-int give_back(sns_ctx* h, int rc, bool flipped, bool time_term) {
-    if (rc == SNS_E_HIP || rc == SNS_E_COMM || (!flipped && !time_term)) return rc;
-    const std::string err = g_err;
-    int rb = SNS_OK;
-    if (flipped) {
-        rb = transpose_operator(h);
-        pc_stale(h);
-    }
-    if (time_term) {
-        const int rt = set_time_term(h, 0.0, 0.0, nullptr);
-        if (rb == SNS_OK) rb = rt;
-    }
-    if (rc != SNS_OK) { set_error(err); return rc; }
-    return rb;
-}
-
-// the end of a linear solve whose Dirichlet rows are identity rows: the reference's ILU-preconditioned solve returns them
-// exactly, a Krylov method under AMG only to its tolerance -- a converged solve hands back the exact data `val` under `mask`
-// (zero_guess: the caller zeroed x itself on the handle's stream)
-int solve_and_snap(sns_ctx* h, const double* b, double* x, const uint8_t* mask, const double* val, int* its, int* reason,
-                   double* rnorm, bool zero_guess = false) {
-    SNS_TRY(krylov(h, b, x, its, reason, rnorm, zero_guess));
-    if (*reason <= 0) return SNS_OK;
-    const int64_t nd = nred_of(h);
-    hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, mask, val, 1e300, x);
-    return sync_stream(h);
 }
 
 }  // namespace
@@ -637,12 +589,10 @@ int sns_set_dirichlet_values(sns_handle h, const double* bc_val_host) {
     return SNS_OK;
 }
 
-// the Arnoldi entry points (`who`: the name in front of the message).  SREQ_ARNOLDI_LEFT: the operator is flipped between the
-// assembly and the set-up and given back afterwards, as sns_adjoint_solve does.  k = 0: a fresh process; k >= 1
-// (sns_stability_arnoldi_extend): the caller's decomposition continued from column k
-static int stability_arnoldi(const char* who, sns_ctx* h, policy::StabilityRequest request, const double* w, double shift, int k, int m,
-                             double breakdown_rel, double* V, double* H, int* m_done, int* total_ksp_its, int* reason,
-                             bool extend = false) {
+// the checks of the Arnoldi entry points (`who`: the name in front of the message; extend: k is an argument too)
+static int arnoldi_checked(const char* who, sns_ctx* h, policy::StabilityRequest request, const double* w, double shift, int k, int m,
+                           double breakdown_rel, double* V, double* H, int* m_done, int* total_ksp_its, int* reason,
+                           bool extend = false) {
     if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
         set_error(std::string(who) + ": null handle or pointer");
         return SNS_E_ARG;
@@ -651,41 +601,24 @@ static int stability_arnoldi(const char* who, sns_ctx* h, policy::StabilityReque
     SNS_TRY(refused(who, extend ? policy::check_arnoldi_extend_args({m, shift, breakdown_rel}, k)
                                 : policy::check_arnoldi_args({m, shift, breakdown_rel})));
     SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_STATE));
-    const bool left = request == policy::SREQ_ARNOLDI_LEFT;
-    // J + shift B = the assembly with u_t = shift (u - u(w)): sigma = shift, theta = 0, d = -shift u(w) (pressure slots unused)
-    if (shift > 0.0) {
-        double* d = nullptr;
-        SNS_TRY(get_vec(h, VEC_SCRATCH, &d));
-        const int64_t ld = ld_of(h);
-        hipLaunchKernelGGL(k_scale_copy, dim3(vec_grid(ld)), dim3(256), 0, h->stream, ld, -shift, w, d);
-        SNS_TRY(set_time_term(h, shift, 0.0, d));
-    }
-    int rc = timed_assemble(h, SNS_FORM_NS, w, nullptr, true);
-    bool flipped = false;
-    if (left && rc == SNS_OK) {
-        rc = transpose_operator(h);                      // (SNS_E_STATE / SNS_E_MESH: nothing was modified)
-        flipped = rc == SNS_OK;
-    }
-    if (rc == SNS_OK) rc = ensure_hierarchy(h);
-    if (rc == SNS_OK) rc = arnoldi_run(h, w, left, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
-    return give_back(h, rc, flipped, shift > 0.0);       // (the assembled matrix stays J + shift B)
+    return sns::stability_arnoldi(h, w, shift, request == policy::SREQ_ARNOLDI_LEFT, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
 }
 
 int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H, int* m_done,
                           int* total_ksp_its, int* reason) {
-    return stability_arnoldi("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, w, shift, 0, m, breakdown_rel, V, H, m_done, total_ksp_its,
+    return arnoldi_checked("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, w, shift, 0, m, breakdown_rel, V, H, m_done, total_ksp_its,
                              reason);
 }
 
 int sns_stability_arnoldi_left(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,
                                int* m_done, int* total_ksp_its, int* reason) {
-    return stability_arnoldi("sns_stability_arnoldi_left", h, policy::SREQ_ARNOLDI_LEFT, w, shift, 0, m, breakdown_rel, V, H, m_done,
+    return arnoldi_checked("sns_stability_arnoldi_left", h, policy::SREQ_ARNOLDI_LEFT, w, shift, 0, m, breakdown_rel, V, H, m_done,
                              total_ksp_its, reason);
 }
 
 int sns_stability_arnoldi_extend(sns_handle h, const double* w, double shift, int k, int m, double breakdown_rel, int left, double* V,
                                  double* H, int* m_done, int* total_ksp_its, int* reason) {
-    return stability_arnoldi("sns_stability_arnoldi_extend", h, left ? policy::SREQ_ARNOLDI_LEFT : policy::SREQ_ARNOLDI, w, shift, k, m,
+    return arnoldi_checked("sns_stability_arnoldi_extend", h, left ? policy::SREQ_ARNOLDI_LEFT : policy::SREQ_ARNOLDI, w, shift, k, m,
                              breakdown_rel, V, H, m_done, total_ksp_its, reason, true);
 }
 
@@ -739,132 +672,12 @@ int sns_operator_is_transposed(sns_handle h, int* flag) {
 
 int sns_adjoint_solve(sns_handle h, const double* g, double* lam, int* its, int* reason, double* rnorm) {
     if (!h || !g || !lam || !its || !reason || !rnorm) return SNS_E_ARG;
-    SNS_TRY(transpose_operator(h));                      // (SNS_E_STATE / SNS_E_MESH: nothing was modified)
-    int rc = ensure_hierarchy(h);
-    // the Dirichlet rows AND columns of A are unit rows: lam_B = g_B exactly, and a converged solve hands that back; the other
-    // rows' residual does not see it.  (The mask of the operator that was transposed: the scalars' own while the scalar operator
-    // is the handle's matrix)
-    const uint8_t* mask = h->matrix_form == SNS_FORM_SCALAR ? h->sc_mask.get() : h->bc_mask.get();
-    if (rc == SNS_OK) rc = solve_and_snap(h, g, lam, mask, g, its, reason, rnorm);
-    return give_back(h, rc, true, false);                // back to A, after a solve that did not converge too
-}
-
-
-// the four work vectors of the Stokes and Newton drivers (4*n doubles each, zeroed), allocated at the first solve
-static int ensure_newton_workspace(sns_ctx* h) {
-    if (h->nw_t) return SNS_OK;
-    const size_t ld = (size_t)ld_of(h);
-    for (DevBuf<double>* v : {&h->nw_F, &h->nw_y, &h->nw_w, &h->nw_t}) SNS_TRY(v->alloc(ld));
-    for (DevBuf<double>* v : {&h->nw_F, &h->nw_y, &h->nw_w, &h->nw_t}) HIP_TRY(hipMemset(*v, 0, ld * sizeof(double)));
-    return SNS_OK;
+    return adjoint_solve(h, g, lam, its, reason, rnorm);
 }
 
 int sns_stokes_solve(sns_handle h, double* U, int* ksp_its, int* reason, double* rnorm) {
     if (!h || !U || !ksp_its || !reason || !rnorm) return SNS_E_ARG;
-    SNS_TRY(ensure_hierarchy(h, true));
-    const int64_t nd = nred_of(h), ld = ld_of(h);
-    SNS_TRY(ensure_newton_workspace(h));
-    // one Newton step of the linear problem from w = 0:  A U = -F(0),  F(0) = lifting, F_B = -g   (:198-214)
-    SNS_TRY(timed_assemble(h, SNS_FORM_STOKES, nullptr, h->nw_F, true));
-    SNS_TRY(ensure_hierarchy(h));
-    hipLaunchKernelGGL(k_scale_copy, dim3(vec_grid(nd)), dim3(256), 0, h->stream, nd, -1.0, h->nw_F, h->nw_F);
-    HIP_TRY(hipMemsetAsync(U, 0, nd * sizeof(double), h->stream));
-    return solve_and_snap(h, h->nw_F, U, h->bc_mask, h->bc_val, ksp_its, reason, rnorm, true);
-}
-
-
-// The Newton loop (newtonls + bt of the reference, :255-272) on whatever NS form the handle carries: the steady form for
-// sns_newton_solve, the transient form of the step for sns_time_step.
-static int newton_run(sns_ctx* h, double* w, int* its_out, int* reason_out, int* total_ksp, double* hist, int hist_cap) {
-    SNS_TRY(ensure_hierarchy(h, true));
-    const sns_options& o = h->opt;
-    const int64_t nd = nred_of(h), ld = ld_of(h);
-    const int g = vec_grid(nd);
-    SNS_TRY(ensure_newton_workspace(h));
-    double *F = h->nw_F, *y = h->nw_y, *wn = h->nw_w, *Fn = h->nw_t;
-    int ksp_total = 0, nh = 0;
-    auto record = [&](double f) { if (hist && nh < hist_cap) hist[nh] = f; ++nh; };
-    SNS_TRY(halo_exchange(h, w));
-    SNS_TRY(timed_assemble(h, SNS_FORM_NS, w, F, true));
-    SNS_TRY(ensure_hierarchy(h));
-    double f, f0;
-    SNS_TRY(norm2(h, F, &f));
-    f0 = f;
-    record(f);
-    if (o.monitor) std::printf("  0 SNES Function norm %.12e\n", f);
-    int reason = 0, it = 0;
-    if (!(f == f)) reason = SNS_SNES_DIVERGED_FNORM_NAN;
-    else if (f < o.snes_atol) reason = SNS_SNES_CONVERGED_FNORM_ABS;
-    while (!reason) {
-        if (it >= o.snes_max_it) { reason = SNS_SNES_DIVERGED_MAX_IT; break; }
-        ++it;
-        // J y = F
-        HIP_TRY(hipMemsetAsync(y, 0, nd * sizeof(double), h->stream));
-        int kits = 0, kreason = 0;
-        double krn = 0;
-        // (y was zeroed here, on the solve's stream; J y of the returned iterate comes back with it where the method has it)
-        double* Jy = Fn;                                     // borrow
-        bool have_Jy = false;
-        SNS_TRY(krylov(h, F, y, &kits, &kreason, &krn, true, Jy, &have_Jy));
-        ksp_total += kits;
-        if (kreason < 0) { reason = SNS_SNES_DIVERGED_LINEAR_SOLVE; break; }
-        // bt line search (cubic backtracking, alpha 1e-4), x_new = x - lambda y
-        double initslope;
-        if (!have_Jy) SNS_TRY(op_apply(h, y, Jy));
-        SNS_TRY(dot(h, F, Jy, &initslope));
-        if (initslope > 0) initslope = -initslope;
-        if (initslope == 0) initslope = -1.0;
-        double ynorm;
-        SNS_TRY(norm2(h, y, &ynorm));
-        const double ls_alpha = 1e-4;
-        double lam = 1.0, gn = 0.0;
-        auto trial = [&](double l) -> int {
-            HIP_TRY(hipMemcpyAsync(wn, w, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, h->stream, nd, -l, y, 1.0, wn);
-            SNS_TRY(halo_exchange(h, wn));
-            SNS_TRY(timed_assemble(h, SNS_FORM_NS, wn, Fn, false));
-            return norm2(h, Fn, &gn);
-        };
-        SNS_TRY(trial(lam));
-        bool ok = 0.5 * gn * gn <= 0.5 * f * f + lam * ls_alpha * initslope;
-        if (!ok && gn == gn) {
-            double lamprev = lam, gprev = gn;
-            double lamtemp = -initslope / (gn * gn - f * f - 2.0 * lam * initslope);
-            lam = std::min(std::max(lamtemp, 0.1 * lam), 0.5 * lam);
-            for (int k = 0; k < 40; ++k) {
-                SNS_TRY(trial(lam));
-                if (0.5 * gn * gn <= 0.5 * f * f + lam * ls_alpha * initslope) { ok = true; break; }
-                const double t1 = 0.5 * (gn * gn - f * f) - lam * initslope;
-                const double t2 = 0.5 * (gprev * gprev - f * f) - lamprev * initslope;
-                const double a = (t1 / (lam * lam) - t2 / (lamprev * lamprev)) / (lam - lamprev);
-                const double bq = (-lamprev * t1 / (lam * lam) + lam * t2 / (lamprev * lamprev)) / (lam - lamprev);
-                const double d = std::max(bq * bq - 3 * a * initslope, 0.0);
-                lamtemp = (a == 0) ? -initslope / (2.0 * bq) : (-bq + std::sqrt(d)) / (3.0 * a);
-                lamprev = lam;
-                gprev = gn;
-                lam = std::min(std::max(lamtemp, 0.1 * lam), 0.5 * lam);
-            }
-        }
-        if (!ok) { reason = (gn == gn) ? SNS_SNES_DIVERGED_LINE_SEARCH : SNS_SNES_DIVERGED_FNORM_NAN; break; }
-        HIP_TRY(hipMemcpyAsync(w, wn, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        // Dirichlet dofs within round-off of their data become exact (no lifting term from here on, :65)
-        hipLaunchKernelGGL(k_snap_bc, dim3(vec_grid(ld)), dim3(256), 0, h->stream, ld, h->bc_mask, h->bc_val, 1e-12, w);
-        double xnorm;
-        SNS_TRY(norm2(h, w, &xnorm));
-        f = gn;
-        record(f);
-        if (o.monitor) std::printf("%3d SNES Function norm %.12e  (ksp its %d, lambda %.3g)\n", it, f, kits, lam);
-        if (f < o.snes_atol) reason = SNS_SNES_CONVERGED_FNORM_ABS;
-        else if (f <= o.snes_rtol * f0) reason = SNS_SNES_CONVERGED_FNORM_RELATIVE;
-        else if (lam * ynorm < o.snes_stol * xnorm) reason = SNS_SNES_CONVERGED_SNORM_RELATIVE;
-        if (reason) break;
-        if (it >= o.snes_max_it) { reason = SNS_SNES_DIVERGED_MAX_IT; break; }   // no Jacobian after the last iteration
-        SNS_TRY(timed_assemble(h, SNS_FORM_NS, w, F, true));
-    }
-    *its_out = it;
-    *reason_out = reason;
-    if (total_ksp) *total_ksp = ksp_total;
-    return SNS_OK;
+    return stokes_solve(h, U, ksp_its, reason, rnorm);
 }
 
 // the checks of the two scalar-transport entry points (`who`: the name in front of the message)
@@ -892,11 +705,7 @@ int sns_scalar_solve(sns_handle h, const double* w_dev, const double kappa[4], d
                      const uint8_t* cmask_dev, const double* cval_dev, double* c_dev, int* its, int* reason, double* rnorm) {
     SNS_TRY(scalar_check("sns_scalar_solve", h, w_dev, kappa, sigma, theta, cmask_dev, cval_dev, c_dev));
     if (!its || !reason || !rnorm) { set_error("sns_scalar_solve: null output"); return SNS_E_ARG; }
-    SNS_TRY(ensure_hierarchy(h, true));
-    SNS_TRY(ensure_newton_workspace(h));
-    SNS_TRY(scalar_system(h, w_dev, kappa, sigma, theta, src_dev, cmask_dev, cval_dev, h->nw_F));
-    SNS_TRY(ensure_hierarchy(h));
-    return solve_and_snap(h, h->nw_F, c_dev, cmask_dev, cval_dev, its, reason, rnorm);
+    return scalar_solve(h, w_dev, kappa, sigma, theta, src_dev, cmask_dev, cval_dev, c_dev, its, reason, rnorm);
 }
 
 int sns_newton_solve(sns_handle h, double* w, int* its_out, int* reason_out, int* total_ksp, double* hist,
@@ -1001,30 +810,7 @@ int sns_time_step(sns_handle h, double* w, double* wprev, double dt, int order, 
     SNS_TRY(allows(h, "sns_time_step", policy::FAMILY_FORM, policy::REQ_TIME_STEP, ROWS_ARG));
     if (!(theta_coeff >= 0.0) || !std::isfinite(theta_coeff)) { set_error("sns_time_step: theta_coeff must be finite and >= 0"); return SNS_E_ARG; }
     SNS_TRY(allows(h, "sns_time_step", policy::FAMILY_FORM, policy::REQ_TIME_STEP, ROWS_STATE));
-    const int64_t ld = ld_of(h);
-    const int g = vec_grid(ld);
-    // BDF1: u_t = (u - u^n) / dt;  BDF2: u_t = (3 u - 4 u^n + u^(n-1)) / (2 dt).  d in a workspace vector (copied by
-    // sns_set_time_term), the entry state in a buffer of its own (a step that does not converge restores it)
-    double *d = nullptr, *w0 = nullptr;
-    SNS_TRY(get_vec(h, VEC_SCRATCH, &d));
-    if (!h->form.tt_w0) SNS_TRY(h->form.tt_w0.alloc((size_t)ld));
-    w0 = h->form.tt_w0;
-    const double sigma = (order == 1 ? 1.0 : 1.5) / dt;
-    hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, ld, (order == 1 ? -1.0 : -2.0) / dt, w, d);
-    if (order == 2) hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, h->stream, ld, 0.5 / dt, wprev, 1.0, d);
-    HIP_TRY(hipMemcpyAsync(w0, w, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    SNS_TRY(sns_set_time_term(h, sigma, theta_coeff / (dt * dt), d));
-    const int rc = newton_run(h, w, its, reason, ksp_its, nullptr, 0);
-    if (rc != SNS_OK) {                                   // the entry state also where the loop gave up with an error
-        if (rc != SNS_E_HIP) (void)hipMemcpy(w, w0, ld * sizeof(double), hipMemcpyDeviceToDevice);
-        return rc;
-    }
-    if (*reason > 0) {
-        if (wprev) HIP_TRY(hipMemcpyAsync(wprev, w0, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    } else {
-        HIP_TRY(hipMemcpyAsync(w, w0, ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    }
-    return sync_stream(h);
+    return time_step(h, w, wprev, dt, order, theta_coeff, its, reason, ksp_its);
 }
 
 

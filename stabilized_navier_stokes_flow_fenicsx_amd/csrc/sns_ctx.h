@@ -1,4 +1,4 @@
-// Shared internals of the C-ABI layer (csrc/sns_api.hip and the setup / cycle / Krylov / ... translation units beside it): the
+// Shared internals of the C-ABI layer (csrc/sns_api.hip and the setup / cycle / Krylov / solve / ... translation units beside it): the
 // context behind an sns_handle, the error helpers, the launch helpers of the level passes and the functions the translation
 // units call across each other.  The context owns its device memory and HIP objects by type (csrc/sns_devbuf.h): there is no
 // free list, ~sns_ctx releases everything.  Not installed; the public surface is include/sns.h.
@@ -311,6 +311,23 @@ int op_residual(sns_ctx* h, double* x, const double* b, double* r);
 // whether the method left it there (else the caller applies the operator itself)
 int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm, bool zero_guess = false, double* ax = nullptr,
            bool* ax_done = nullptr);
+// csrc/sns_solve.hip: the solve drivers behind the entry points (which have checked the arguments) and their shared pieces.
+// ensure_hierarchy builds the lazy hierarchy (assembles_next: the caller assembles next, so an operator-based aggregation may
+// wait); solve_and_snap is krylov plus the exact Dirichlet data `val` under `mask` after a converged solve; give_back returns the
+// operator flipped and the time term set for one call.  newton_run works on whatever NS form the handle carries
+int ensure_hierarchy(sns_ctx* h, bool assembles_next = false);
+int ensure_newton_workspace(sns_ctx* h);
+int solve_and_snap(sns_ctx* h, const double* b, double* x, const uint8_t* mask, const double* val, int* its, int* reason, double* rnorm,
+                   bool zero_guess = false);
+int give_back(sns_ctx* h, int rc, bool flipped, bool time_term);
+int newton_run(sns_ctx* h, double* w, int* its, int* reason, int* total_ksp, double* hist, int hist_cap);
+int stokes_solve(sns_ctx* h, double* U, int* ksp_its, int* reason, double* rnorm);
+int time_step(sns_ctx* h, double* w, double* wprev, double dt, int order, double theta_coeff, int* its, int* reason, int* ksp_its);
+int scalar_solve(sns_ctx* h, const double* w, const double kappa[4], double sigma, double theta, const double* src, const uint8_t* cmask,
+                 const double* cval, double* c, int* its, int* reason, double* rnorm);
+int adjoint_solve(sns_ctx* h, const double* g, double* lam, int* its, int* reason, double* rnorm);
+int stability_arnoldi(sns_ctx* h, const double* w, double shift, bool left, int k, int m, double breakdown_rel, double* V, double* H,
+                      int* m_done, int* total_ksp_its, int* reason);
 // csrc/sns_strength.hip: the strength of the fine-level couplings (amg_aggregation = 1, SNS_EXPORT_STRENGTH)
 int compute_strength(sns_ctx* h, float* out, double* scale);
 // csrc/sns_transpose.hip: flip the fine operator between A and A^T in place

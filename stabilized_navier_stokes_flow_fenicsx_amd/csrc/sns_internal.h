@@ -173,5 +173,6 @@ void aggregate_nodes(const HostPattern& F, int32_t n_active, int max_agg, std::v
 void aggregate_strength(const HostPattern& F, int32_t n_active, int max_agg, const float* strength, std::vector<int32_t>& agg,
                         int32_t& nc);
 void set_error(const std::string& s);
+const std::string& last_error();               // the calling thread's text (sns_last_error)
 
 }  // namespace sns

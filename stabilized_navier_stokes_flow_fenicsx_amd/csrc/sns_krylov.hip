@@ -122,7 +122,7 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
     if (o.monitor) std::printf("  0 KSP Residual norm %.12e\n", rn);
     int its = 0, reason = 0;
     if (!(rn == rn)) reason = SNS_KSP_DIVERGED_NANORINF;
-    else if (rn <= tol) reason = (rn <= o.ksp_atol) ? SNS_KSP_CONVERGED_ATOL : SNS_KSP_CONVERGED_RTOL;
+    else reason = policy::ksp_converged(rn, tol, o.ksp_atol);
     if (!reason && o.ksp_max_it < 1) reason = SNS_KSP_DIVERGED_ITS;
     if (!reason) {
         HIP_TRY(hipMemcpyAsync(rhat, r, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -181,9 +181,8 @@ int bicgstab(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_o
                 // the three-term formula can lose digits when ||r|| << ||s||: confirm with the vector itself
                 double rtrue;
                 SNS_TRY(norm2(h, r, &rtrue));
-                if (rtrue <= tol) {
+                if ((reason = policy::ksp_converged(rtrue, tol, o.ksp_atol))) {
                     rn = rtrue;
-                    reason = (rn <= o.ksp_atol) ? SNS_KSP_CONVERGED_ATOL : SNS_KSP_CONVERGED_RTOL;
                     break;
                 }
             }
@@ -253,7 +252,7 @@ int tfqmr(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out,
     if (o.monitor) std::printf("  0 KSP Residual norm %.12e\n", rn);
     int its = 0, reason = 0;
     if (!(rn == rn)) reason = SNS_KSP_DIVERGED_NANORINF;
-    else if (rn <= tol) reason = (rn <= o.ksp_atol) ? SNS_KSP_CONVERGED_ATOL : SNS_KSP_CONVERGED_RTOL;
+    else reason = policy::ksp_converged(rn, tol, o.ksp_atol);
     if (!reason) {
         HIP_TRY(hipMemcpyAsync(y1, w, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(rt, w, nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -302,8 +301,8 @@ int tfqmr(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out,
         SNS_TRY(op_residual(h, x, b, w));
         SNS_TRY(norm2(h, w, &rn));
         if (!reason) {
-            if (done && rn <= 10.0 * tol) reason = (rn <= o.ksp_atol) ? SNS_KSP_CONVERGED_ATOL : SNS_KSP_CONVERGED_RTOL;
-            else reason = SNS_KSP_DIVERGED_ITS;
+            if (done) reason = policy::ksp_converged(rn, 10.0 * tol, o.ksp_atol);
+            if (!reason) reason = SNS_KSP_DIVERGED_ITS;
         }
     }
     *its_out = its;
@@ -343,7 +342,7 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
     if (o.monitor) std::printf("  0 KSP Residual norm %.12e\n", rn);
     while (!reason) {
         if (!(rn == rn) || std::isinf(rn)) { reason = SNS_KSP_DIVERGED_NANORINF; break; }
-        if (rn <= tol) { reason = (rn <= o.ksp_atol) ? SNS_KSP_CONVERGED_ATOL : SNS_KSP_CONVERGED_RTOL; break; }
+        if ((reason = policy::ksp_converged(rn, tol, o.ksp_atol))) break;
         if (its >= o.ksp_max_it) { reason = SNS_KSP_DIVERGED_ITS; break; }
         hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, nd, 1.0 / rn, r, V);
         std::fill(gv.begin(), gv.end(), 0.0);

@@ -8,7 +8,8 @@
 // allows of every entry point that can refuse (HandleFacts and the one table RULES, tests/request_main.cpp), which operator is
 // a new one (OperatorKey, tests/operator_key_main.cpp), the damping of a
 // level's smoother (LevelDamping, tests/damping_policy_main.cpp), what a kernel of a solve hands to a later one (Handoff,
-// tests/handoff_main.cpp), what a solve and a set-up may leave out of their fixed cost (plan_step, tests/step_plan_main.cpp).
+// tests/handoff_main.cpp), what a solve and a set-up may leave out of their fixed cost (plan_step, tests/step_plan_main.cpp), when
+// the Krylov and Newton loops stop and which step the line search tries next (LineSearch, tests/newton_policy_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -771,6 +772,69 @@ inline StepPlan plan_step(const StepFacts& f) {
     p.setup_two_streams = f.pc_type == SNS_PC_AMG && !f.estimates_due;
     return p;
 }
+
+// ---- the nonlinear drivers (csrc/sns_solve.hip; the contract is in DESIGN.md, "Nonlinear drivers") ----------------------------------
+// The stopping rules of the Krylov methods and of the Newton loop, and the reference's bt line search (cubic backtracking), as
+// arithmetic on a handful of doubles: the drivers launch and measure, the answers come from here.
+// a residual norm at or below tol = max(ksp_rtol ||b||, ksp_atol) ends a linear solve; which of the two it met is the reason
+inline int ksp_converged(double rn, double tol, double atol) {
+    if (!(rn <= tol)) return 0;
+    return rn <= atol ? SNS_KSP_CONVERGED_ATOL : SNS_KSP_CONVERGED_RTOL;
+}
+// the Newton loop before its first step (f = ||F|| of the guess) and after step `it` (f0: the norm at the start; step_norm =
+// lambda ||y||; x_norm = ||w|| after the step).  0: go on.  The iteration limit comes last and is asked BEFORE the next
+// Jacobian is assembled: no Jacobian after the last iteration
+inline int snes_start(double f, const sns_options& o) {
+    if (!(f == f)) return SNS_SNES_DIVERGED_FNORM_NAN;
+    if (f < o.snes_atol) return SNS_SNES_CONVERGED_FNORM_ABS;
+    return o.snes_max_it <= 0 ? SNS_SNES_DIVERGED_MAX_IT : 0;
+}
+inline int snes_after_step(double f, double f0, double step_norm, double x_norm, int it, const sns_options& o) {
+    if (f < o.snes_atol) return SNS_SNES_CONVERGED_FNORM_ABS;
+    if (f <= o.snes_rtol * f0) return SNS_SNES_CONVERGED_FNORM_RELATIVE;
+    if (step_norm < o.snes_stol * x_norm) return SNS_SNES_CONVERGED_SNORM_RELATIVE;
+    return it >= o.snes_max_it ? SNS_SNES_DIVERGED_MAX_IT : 0;
+}
+// The line search along x - lambda y.  f: ||F|| at the current state; initslope: F . (J y) as measured -- made a descent slope
+// here (a positive one is negated, zero becomes -1).  lambda() is the step to try, the first is 1; offer(gn) takes ||F|| at that
+// trial.  A trial is accepted by sufficient decrease (ls_alpha); after the first rejection the next step minimises the
+// quadratic through f, the slope and the trial, after every later one the cubic through the last two trials, each kept within
+// [0.1, 0.5] of the step before.  ls_max_it trials follow the first.  A NaN at the first trial and a non-finite norm at a
+// later one end the search with FAIL_NAN (no later trial could be accepted).  No device access, no handle.
+constexpr double ls_alpha = 1e-4;
+constexpr int ls_max_it = 40;
+struct LineSearch {
+    enum Answer { ACCEPT = 0, TRY_AGAIN, FAIL_LINE_SEARCH, FAIL_NAN };
+    LineSearch(double f_, double initslope) : f(f_), slope(initslope > 0 ? -initslope : initslope) {
+        if (slope == 0) slope = -1.0;
+    }
+    double lambda() const { return lam; }
+    Answer offer(double gn) {
+        const bool first = trials++ == 0;
+        if (0.5 * gn * gn <= 0.5 * f * f + lam * ls_alpha * slope) return ACCEPT;
+        if (first ? !(gn == gn) : !std::isfinite(gn)) return FAIL_NAN;
+        if (trials > ls_max_it) return FAIL_LINE_SEARCH;
+        double lamtemp;
+        if (first) {
+            lamtemp = -slope / (gn * gn - f * f - 2.0 * lam * slope);
+        } else {
+            const double t1 = 0.5 * (gn * gn - f * f) - lam * slope;
+            const double t2 = 0.5 * (gprev * gprev - f * f) - lamprev * slope;
+            const double a = (t1 / (lam * lam) - t2 / (lamprev * lamprev)) / (lam - lamprev);
+            const double bq = (-lamprev * t1 / (lam * lam) + lam * t2 / (lamprev * lamprev)) / (lam - lamprev);
+            const double d = std::max(bq * bq - 3 * a * slope, 0.0);
+            lamtemp = (a == 0) ? -slope / (2.0 * bq) : (-bq + std::sqrt(d)) / (3.0 * a);
+        }
+        lamprev = lam;
+        gprev = gn;
+        lam = std::min(std::max(lamtemp, 0.1 * lam), 0.5 * lam);
+        return TRY_AGAIN;
+    }
+
+   private:
+    double f, slope, lam = 1.0, lamprev = 1.0, gprev = 0.0;
+    int trials = 0;
+};
 
 }  // namespace policy
 }  // namespace sns

@@ -56,7 +56,7 @@ def _worker(rank, world, port, kind, q):
         err_halo = np.abs(xt.numpy() - x[gdof]).max()
         yl = Jl[:no] @ xt.numpy()
         err_spmv = np.abs(yl - (Jg @ x)[gdof[:no]]).max()
-        # interior / boundary split of the multi-GPU SpMV (exchange_and_spmv in csrc/sns_api.hip): rows without a
+        # interior / boundary split of the multi-GPU SpMV (exchange_and_spmv in csrc/sns_ctx.h): rows without a
         # ghost column are computed from the OWNED part of x alone, i.e. before the halo has arrived; only the rows
         # sns_host_boundary_rows lists wait for it
         from stabilized_navier_stokes_flow_fenicsx_amd import _lib
@@ -101,7 +101,7 @@ def _worker(rank, world, port, kind, q):
             n_allreduce[0] += 1
             return t.numpy()
 
-        # the product's latency-lean BiCGStab (csrc/sns_api.hip:bicgstab): TWO all-reduces per iteration --
+        # the product's latency-lean BiCGStab (csrc/sns_krylov.hip:bicgstab): TWO all-reduces per iteration --
         # <rhat, v>, then (t.s, t.t, rhat.s, rhat.t, s.s) from which omega, the next rho and ||r||^2 follow
         n_allreduce = [0]
         xk = np.zeros(no)

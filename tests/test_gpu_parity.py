@@ -262,6 +262,32 @@ def test_newton_from_bc_violating_guess_uses_lifting(gpu):
     P.close()
 
 
+@pytest.mark.parametrize("Re", [1000.0, 400.0])
+def test_newton_that_backtracks_matches_oracle_history(gpu, Re):
+    """The bt line search at work: the cavity from w = 0 rejects full steps.  The oracle's LU-Newton accepts lambda = 1, 0.05, 0.1,
+    0.236, 0.201, 0.429, 1, ... at Re 1000 (13 iterations: a quadratic step at the lower clamp, interior quadratics, a cubic step
+    at the upper clamp) and 1, 0.1, 0.266, 1, ... at Re 400 (9 iterations).  Bound on ||F||: the oracle's own inexact run (BiCGStab,
+    block Jacobi, ksp_rtol 1e-10) stays within 2.4e-6 (Re 1000) and 6e-9 (Re 400) of its LU history, so 1e-4 is 40 x that
+    sensitivity, while a wrong lambda (branch, clamp or sign) moves the next ||F|| by tens of percent."""
+    from oracle import solve as S
+    from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B, mesh as M
+    m = M.cavity_mesh(4)
+    mask, g = B.cavity_bcs(m).flatten()
+    w0 = np.zeros(m.num_dofs)
+    wo, info = S.newton(m.points, m.tets, w0, Re, mask, g, linear="lu")
+    assert min(info["lambdas"]) < 0.5                                # (the case is what it says: the oracle backtracks)
+    P = gpu(m, (mask, g), reynolds=Re, ksp_type="bicgstab", pc_type="bjacobi", ksp_rtol=1e-10)
+    w, res = P.newton_solve(_dev(w0))
+    k = min(len(res.fnorms), len(info["fnorms"])) - 1
+    dev = np.abs(np.array(res.fnorms[:k]) / np.array(info["fnorms"][:k]) - 1.0)
+    print(f"backtracking Newton Re {Re:g}: its {res.its} / {info['its']}, reason {res.reason} / {info['reason']}, "
+          f"max ||F|| deviation {dev.max():.3e}, lambdas {np.round(info['lambdas'], 3).tolist()}")
+    assert res.its == info["its"] and res.reason == info["reason"]
+    assert np.allclose(res.fnorms[:-1], info["fnorms"][:-1], rtol=1e-4, atol=0.0)
+    assert rel(w.cpu().numpy().reshape(-1, 4)[:, :3], wo.reshape(-1, 4)[:, :3]) < 1e-6
+    P.close()
+
+
 def test_reference_driver_mirror(gpu, capsys):
     from stabilized_navier_stokes_flow_fenicsx_amd import bcs as B, mesh as M
     from stabilized_navier_stokes_flow_fenicsx_amd.solver import solve_navier_stokes, solve_stokes_problem
