@@ -505,8 +505,31 @@ SNS_API int sns_error_indicator(sns_handle h, const double* w_dev, const double*
  *   column j of H is full above the subdiagonal.  m_done = k + the steps completed; reasons, breakdown and the zeroing of the
  *   columns not reached as above.  Errors as sns_stability_arnoldi[_left] by `left`, and SNS_E_ARG for k outside [1, m - 1]
  *   (after the other arguments, before the state).
+ * Complex and negative shifts s = shift_re + i shift_im: shift-invert in real Arnoldi arithmetic (Parlett & Saad) on
+ *   S = Re[(J + s B)^-1 B], a real operator with the eigenvectors of the pencil, so V, H, sns_basis_rotate and the truncation are
+ *   what they are above.  A Ritz value theta of S belongs to lambda with theta = (a - lambda) / ((s - lambda)(conj(s) - lambda)),
+ *   a = shift_re: two candidates per theta, told apart by their true residual (solver.py: shifted_eigenpairs).  The inner system
+ *   is complex, (P + c B) y = b with P = J + pc_shift B the real matrix the handle assembles and preconditions, c = s - pc_shift.
+ *   Complex device vectors are PLANAR: 4*n_local real parts, then 4*n_local imaginary parts, each in the layout of a state vector.
+ * sns_shifted_apply: y = A x + (c_re + i c_im) B(w) x, or with transpose != 0 ... B(w)^T x, for planar complex x, y (which must
+ *   not overlap); A is whatever matrix the handle holds (for the left problem the caller has flipped it).  Two operator passes
+ *   fill y, one pair mass pass adds c B x to both parts (the geometry and tau of a cell formed once for both; each part summed
+ *   in the order of sns_mass_apply[_transpose]; no atomics, bitwise reproducible); with c = 0 the result is the operator pass's.
+ *   Entries of x are masked as the mass passes mask them.  SNS_E_ARG: null handle / pointer, a 2-D handle, a part of c not
+ *   finite.  SNS_E_STATE: a communicator attached, a viscosity law set, no matrix assembled.
+ * sns_shifted_solve: (A + c B) x = b by right-preconditioned complex FGMRES -- restart gmres_restart (at most 200), stopping by
+ *   ksp_rtol / ksp_atol / ksp_max_it, the preconditioner of A applied to each part, no damping retry; x holds the initial guess
+ *   on entry; *reason an SNS_KSP_* reason, *rnorm the true residual norm.  A solve that does not converge returns SNS_OK and
+ *   says so in *reason.  Errors as sns_shifted_apply.
+ * sns_stability_arnoldi_shifted: the process on Re[(J + s B)^-1 B] (left != 0: on Re[(J + s B)^-T B^T]).  k = 0: a fresh process
+ *   as sns_stability_arnoldi[_left] runs it; k >= 1: the continuation of sns_stability_arnoldi_extend.  J + pc_shift B is
+ *   assembled through the time term (pc_shift = 0: the plain J) and set up; each step is one mass pass, one complex solve of
+ *   (P + (s - pc_shift) B) y = B v from a zero guess, and the real part of y.  V, H, m_done, reason and the state of the handle
+ *   on return -- J + pc_shift B, untransposed, the form steady -- as there.  shift_im = 0 serves negative real shifts.
+ *   SNS_E_ARG: null handle / pointer, a 2-D handle, m outside [2, 64], k outside [0, m - 1], a shift part or pc_shift not
+ *   finite, pc_shift < 0, breakdown_rel outside (0, 1).  SNS_E_STATE: as sns_stability_arnoldi.
  * Not built: explicit locking / deflation of converged pairs, selections other than "nearest the shift", a C implementation of
- * the ordered Schur form, complex or negative shifts; of the sensitivities, base flows with a body
+ * the ordered Schur form, a complex Arnoldi basis; of the sensitivities, base flows with a body
  * force or a backflow term, the sensitivity to forcing on Dirichlet nodes, and the exact form of E = D_w[B^T z][x] (the
  * forcing sensitivity takes it by a central difference of sns_mass_apply_transpose). */
 SNS_API int sns_mass_apply(sns_handle h, const double* w_dev, const double* x_dev, double* y_dev);
@@ -525,6 +548,16 @@ SNS_API int sns_stability_arnoldi_extend(sns_handle h, const double* w_dev, doub
                                          int* m_done, int* total_ksp_its, int* reason);
 SNS_API int sns_basis_rotate(sns_handle h, int n_in, int n_out, const double* Q_host /* n_in x n_out, row major */,
                              double* V_dev /* n_in * 4*n_local */);
+SNS_API int sns_shifted_apply(sns_handle h, const double* w_dev, double c_re, double c_im, int transpose,
+                              const double* x_dev /* 2 * 4*n_local, planar */, double* y_dev /* 2 * 4*n_local, planar */);
+SNS_API int sns_shifted_solve(sns_handle h, const double* w_dev, double c_re, double c_im, int transpose,
+                              const double* b_dev /* 2 * 4*n_local, planar */, double* x_dev /* 2 * 4*n_local; the guess on entry */,
+                              int* its, int* reason, double* rnorm);
+SNS_API int sns_stability_arnoldi_shifted(sns_handle h, const double* w_dev, double shift_re, double shift_im, double pc_shift,
+                                          int k, int m, double breakdown_rel, int left,
+                                          double* V_dev /* (m+1) * 4*n_local; column 0 = start vector (k = 0), columns 0 .. k */,
+                                          double* H_host /* (m+1) x m, row major; the leading (k+1) x k block on entry (k >= 1) */,
+                                          int* m_done, int* total_ksp_its, int* reason);
 /* The raw Jacobian and the Dirichlet values of a live handle (no counterpart in the reference).
  * sns_raw_jacobian_apply: y = J0(w) x for transposed == 0, y = J0(w)^T x otherwise, J0 = dR_raw/dw the exact Gateaux derivative
  *   of the raw residual sns_residual_moments sums -- without lifting and without the Dirichlet rows' w_B - g.  With K_t the

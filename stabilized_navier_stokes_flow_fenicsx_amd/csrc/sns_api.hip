@@ -622,6 +622,44 @@ int sns_stability_arnoldi_extend(sns_handle h, const double* w, double shift, in
                              breakdown_rel, V, H, m_done, total_ksp_its, reason, true);
 }
 
+int sns_stability_arnoldi_shifted(sns_handle h, const double* w, double shift_re, double shift_im, double pc_shift, int k, int m,
+                                  double breakdown_rel, int left, double* V, double* H, int* m_done, int* total_ksp_its, int* reason) {
+    const char* who = "sns_stability_arnoldi_shifted";
+    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
+        set_error(std::string(who) + ": null handle or pointer");
+        return SNS_E_ARG;
+    }
+    const policy::StabilityRequest request = left ? policy::SREQ_ARNOLDI_LEFT : policy::SREQ_ARNOLDI;
+    SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_ARG));
+    SNS_TRY(refused(who, policy::check_shifted_args({m, k, shift_re, shift_im, pc_shift, breakdown_rel})));
+    SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_STATE));
+    const double c[2] = {shift_re - pc_shift, shift_im};   // J + s B = (J + pc_shift B) + c B
+    return sns::stability_arnoldi(h, w, pc_shift, left != 0, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason, c);
+}
+
+// the checks of the two calls on the complex operator A + c B (`who`: the name in front of the message)
+static int shifted_operator_checked(const char* who, sns_ctx* h, bool pointers, double c_re, double c_im, int transpose) {
+    if (!h || !pointers) { set_error(std::string(who) + ": null handle or pointer"); return SNS_E_ARG; }
+    const policy::StabilityRequest request = transpose ? policy::SREQ_MASS_APPLY_TRANSPOSE : policy::SREQ_MASS_APPLY;
+    SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_ARG));
+    SNS_TRY(refused(who, policy::check_shifted_coefficient(c_re, c_im)));
+    SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_STATE));
+    if (!h->has_matrix) { set_error(std::string(who) + " before a matrix was assembled"); return SNS_E_STATE; }
+    return SNS_OK;
+}
+
+int sns_shifted_apply(sns_handle h, const double* w, double c_re, double c_im, int transpose, const double* x, double* y) {
+    SNS_TRY(shifted_operator_checked("sns_shifted_apply", h, w && x && y, c_re, c_im, transpose));
+    return shifted_apply(h, w, c_re, c_im, transpose != 0, x, y);
+}
+
+int sns_shifted_solve(sns_handle h, const double* w, double c_re, double c_im, int transpose, const double* b, double* x, int* its,
+                      int* reason, double* rnorm) {
+    SNS_TRY(shifted_operator_checked("sns_shifted_solve", h, w && b && x && its && reason && rnorm, c_re, c_im, transpose));
+    SNS_TRY(ensure_hierarchy(h));
+    return shifted_solve(h, w, c_re, c_im, transpose != 0, b, x, its, reason, rnorm);
+}
+
 int sns_basis_rotate(sns_handle h, int n_in, int n_out, const double* Q, double* V) {
     const char* who = "sns_basis_rotate";
     if (!h || !Q || !V) { set_error("sns_basis_rotate: null handle or pointer"); return SNS_E_ARG; }

@@ -327,7 +327,7 @@ int scalar_solve(sns_ctx* h, const double* w, const double kappa[4], double sigm
                  const double* cval, double* c, int* its, int* reason, double* rnorm);
 int adjoint_solve(sns_ctx* h, const double* g, double* lam, int* its, int* reason, double* rnorm);
 int stability_arnoldi(sns_ctx* h, const double* w, double shift, bool left, int k, int m, double breakdown_rel, double* V, double* H,
-                      int* m_done, int* total_ksp_its, int* reason);
+                      int* m_done, int* total_ksp_its, int* reason, const double* c = nullptr);
 // csrc/sns_strength.hip: the strength of the fine-level couplings (amg_aggregation = 1, SNS_EXPORT_STRENGTH)
 int compute_strength(sns_ctx* h, float* out, double* scale);
 // csrc/sns_transpose.hip: flip the fine operator between A and A^T in place
@@ -343,9 +343,24 @@ int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, 
 // decomposition continued), and the in-place compression of its basis V[:, 0:n_out] <- V[:, 0:n_in] Q (Q on the host)
 int mass_apply(sns_ctx* h, const double* w, const double* x, double* y);
 int mass_apply_transpose(sns_ctx* h, const double* w, const double* z, double* y);
+// c: null, or the complex coefficient (re, im) of the shifted step -- S = Re[(A + c B)^-1 B] with A the handle's matrix
 int arnoldi_run(sns_ctx* h, const double* w, bool left, int k0, int m, double breakdown_rel, double* V, double* H, int* m_done,
-                int* total_its, int* reason);
+                int* total_its, int* reason, const double* c = nullptr);
 int basis_rotate(sns_ctx* h, int n_in, int n_out, const double* Q, double* V);
+// csrc/sns_shifted.hip: the complex operator y = A x + c B(w) x (left: B^T; A is the handle's matrix as it stands) on planar
+// complex vectors -- 4 n real parts, then 4 n imaginary parts -- and its solve by right-preconditioned complex FGMRES with the
+// handle's options.  CfgmresWork: the solver's own buffers (basis, preconditioned basis, coefficients), kept by whoever solves
+// more than once
+struct CfgmresWork {
+    DevBuf<double> V, Z, co;
+    int m = 0;
+    int reserve(sns_ctx* h);
+};
+int shifted_apply(sns_ctx* h, const double* w, double c_re, double c_im, bool left, const double* x, double* y);
+int cfgmres(sns_ctx* h, const double* w, double c_re, double c_im, bool left, const double* b, double* x, int* its, int* reason,
+            double* rnorm, CfgmresWork& ws);
+int shifted_solve(sns_ctx* h, const double* w, double c_re, double c_im, bool left, const double* b, double* x, int* its, int* reason,
+                  double* rnorm);
 // csrc/sns_hessian.hip: g = grad_w [ z~^T (c_jac J(w) + c_mass B(w)) x~ ] by one element pass (uses the element scratch Fe)
 int jacobian_state_gradient(sns_ctx* h, const double* w, const double* x, const double* z, double c_jac, double c_mass, double* g);
 // csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)

@@ -194,6 +194,8 @@ __global__ void k_bicg_xrp_first(int64_t n, const double* sc, const double* ph, 
 __global__ void k_multi_dot8(int64_t n, int nv, const double* V, int64_t ldv, const double* w, double* partial);
 __global__ void k_multi_axpy8(int64_t n, int nv, const double* V, int64_t ldv, const double* h, double sign,
                               double* w, double* partial);
+__global__ void k_cdot8(int64_t n, int nv, const double* V, int64_t ldv, const double* w, double* partial);
+__global__ void k_caxpy8(int64_t n, int nv, const double* V, int64_t ldv, const double* h, double sign, double* w);
 __global__ void k_scale_copy(int64_t n, double a, const double* x, double* y);
 __global__ void k_restrict(int32_t nc, const int32_t* m_ptr, const int32_t* m_idx, const uint8_t* free_mask,
                            const double* r, double* bc, const float* dinv32_c, double omega_c, double* z_c);

@@ -1751,6 +1751,50 @@ __global__ __launch_bounds__(256) void k_multi_axpy8(int64_t n, int nv, const do
     if (partial) block_reduce_store<1>(acc, partial);
 }
 
+// Complex FGMRES (csrc/sns_shifted.hip) on planar vectors -- n real parts, then n imaginary parts; ldv = the stride of one basis
+// vector, 2 n or more.  h[k] = V_k^H w for k < nv <= 8: partial[16 block + 2 k] = sum v_re w_re + v_im w_im, [.. + 2 k + 1] =
+// sum v_re w_im - v_im w_re.  One pass: every entry of the chunk of V and of w is read once.
+__global__ __launch_bounds__(256) void k_cdot8(int64_t n, int nv, const double* __restrict__ V, int64_t ldv,
+                                               const double* __restrict__ w, double* __restrict__ partial) {
+    double acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const double wr = w[i], wi = w[n + i];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k < nv) {
+                const double vr = V[k * ldv + i], vi = V[k * ldv + n + i];
+                acc[2 * k] += vr * wr + vi * wi;
+                acc[2 * k + 1] += vr * wi - vi * wr;
+            }
+    }
+    block_reduce_store<16>(acc, partial);
+}
+
+// ... and w += sign * sum_k h[k] V_k (k < nv <= 8; h on the device, (re, im) interleaved as k_cdot8 leaves it)
+__global__ __launch_bounds__(256) void k_caxpy8(int64_t n, int nv, const double* __restrict__ V, int64_t ldv,
+                                                const double* __restrict__ h, double sign, double* __restrict__ w) {
+    double hr[8], hi[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        hr[k] = (k < nv) ? sign * h[2 * k] : 0.0;
+        hi[k] = (k < nv) ? sign * h[2 * k + 1] : 0.0;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        double wr = w[i], wi = w[n + i];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k < nv) {
+                const double vr = V[k * ldv + i], vi = V[k * ldv + n + i];
+                wr += hr[k] * vr - hi[k] * vi;
+                wi += hr[k] * vi + hi[k] * vr;
+            }
+        w[i] = wr;
+        w[n + i] = wi;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_scale_copy(int64_t n, double a, const double* x, double* y) {  // x may alias y
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         y[i] = a * x[i];

@@ -595,6 +595,27 @@ inline Verdict check_arnoldi_extend_args(const ArnoldiArgs& a, int k) {
     if (k < 1 || k > a.m - 1) return {SNS_E_ARG, "k must lie in [1, m - 1]"};
     return {};
 }
+// ... and of the process with a complex or negative shift s = shift_re + i shift_im on top of the assembled J + pc_shift B
+// (sns_stability_arnoldi_shifted; k = 0 a fresh process, k >= 1 a continuation): m, k in [0, m - 1], finite shift parts, a
+// finite pc_shift >= 0, breakdown_rel.  Asked as SREQ_ARNOLDI / SREQ_ARNOLDI_LEFT, like the continuation
+struct ShiftedArgs {
+    int m = STABILITY_M_MAX, k = 0;
+    double shift_re = 0.0, shift_im = 0.0, pc_shift = 0.0, breakdown_rel = 1e-6;
+};
+inline Verdict check_shifted_args(const ShiftedArgs& a) {
+    auto finite = [](double v) { return v - v == 0.0; };
+    if (a.m < STABILITY_M_MIN || a.m > STABILITY_M_MAX) return {SNS_E_ARG, "m must lie in [2, 64]"};
+    if (a.k < 0 || a.k > a.m - 1) return {SNS_E_ARG, "k must lie in [0, m - 1]"};
+    if (!finite(a.shift_re) || !finite(a.shift_im)) return {SNS_E_ARG, "both parts of the shift must be finite"};
+    if (!finite(a.pc_shift) || !(a.pc_shift >= 0.0)) return {SNS_E_ARG, "pc_shift must be finite and >= 0"};
+    if (!(a.breakdown_rel > 0.0) || !(a.breakdown_rel < 1.0)) return {SNS_E_ARG, "breakdown_rel must lie in (0, 1)"};
+    return {};
+}
+// ... and the coefficient of the complex operator A + c B (sns_shifted_apply, sns_shifted_solve: asked as SREQ_MASS_APPLY[_TRANSPOSE])
+inline Verdict check_shifted_coefficient(double c_re, double c_im) {
+    if (!(c_re - c_re == 0.0) || !(c_im - c_im == 0.0)) return {SNS_E_ARG, "both parts of c must be finite"};
+    return {};
+}
 // ... and the coefficients of the Hessian pass
 inline Verdict check_state_gradient_args(double c_jac, double c_mass) {
     if (!(c_jac - c_jac == 0.0) || !(c_mass - c_mass == 0.0)) return {SNS_E_ARG, "the coefficients must be finite"};
@@ -625,6 +646,13 @@ inline Verdict check_stability_request(StabilityRequest request, const HandleFac
 // (tests/extend_request_main.cpp) request: SREQ_ARNOLDI or SREQ_ARNOLDI_LEFT
 inline Verdict check_stability_extend_request(StabilityRequest request, const HandleFacts& f, const ArnoldiArgs& a, int k) {
     return check_request(FAMILY_STABILITY, request, f, check_arnoldi_extend_args(a, k));
+}
+// (tests/shifted_request_main.cpp) the process: SREQ_ARNOLDI or SREQ_ARNOLDI_LEFT; the operator: SREQ_MASS_APPLY[_TRANSPOSE]
+inline Verdict check_stability_shifted_request(StabilityRequest request, const HandleFacts& f, const ShiftedArgs& a) {
+    return check_request(FAMILY_STABILITY, request, f, check_shifted_args(a));
+}
+inline Verdict check_shifted_operator_request(StabilityRequest request, const HandleFacts& f, double c_re, double c_im) {
+    return check_request(FAMILY_STABILITY, request, f, check_shifted_coefficient(c_re, c_im));
 }
 inline Verdict check_state_gradient_request(const HandleFacts& f, double c_jac = 1.0, double c_mass = 0.0) {
     return check_request(FAMILY_STATE_GRADIENT, GREQ_STATE_GRADIENT, f, check_state_gradient_args(c_jac, c_mass));

@@ -202,9 +202,11 @@ int adjoint_solve(sns_ctx* h, const double* g, double* lam, int* its, int* reaso
 }
 
 // left: the operator is flipped between the assembly and the set-up and given back afterwards, as adjoint_solve does.  k = 0: a
-// fresh process; k >= 1 (sns_stability_arnoldi_extend): the caller's decomposition continued from column k
+// fresh process; k >= 1 (sns_stability_arnoldi_extend): the caller's decomposition continued from column k.  c (sns_stability_
+// arnoldi_shifted): the complex coefficient of the shifted step on top of the assembled J + shift B, which is then the matrix
+// the preconditioner is built for
 int stability_arnoldi(sns_ctx* h, const double* w, double shift, bool left, int k, int m, double breakdown_rel, double* V, double* H,
-                      int* m_done, int* total_ksp_its, int* reason) {
+                      int* m_done, int* total_ksp_its, int* reason, const double* c) {
     // J + shift B = the assembly with u_t = shift (u - u(w)): sigma = shift, theta = 0, d = -shift u(w) (pressure slots unused)
     if (shift > 0.0) {
         double* d = nullptr;
@@ -220,7 +222,7 @@ int stability_arnoldi(sns_ctx* h, const double* w, double shift, bool left, int 
         flipped = rc == SNS_OK;
     }
     if (rc == SNS_OK) rc = ensure_hierarchy(h);
-    if (rc == SNS_OK) rc = arnoldi_run(h, w, left, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+    if (rc == SNS_OK) rc = arnoldi_run(h, w, left, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason, c);
     return give_back(h, rc, flipped, shift > 0.0);       // (the assembled matrix stays J + shift B)
 }
 

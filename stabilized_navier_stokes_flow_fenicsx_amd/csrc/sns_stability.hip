@@ -40,8 +40,9 @@
 //   arnoldi_run    with a first column k0 >= 1 continues a Krylov decomposition S V_k = V_{k+1} H_k the caller holds: no start
 //                  vector treatment, the leading (k0 + 1) x k0 block of H kept, steps j = k0 .. m - 1 as ever.  Gram-Schmidt runs
 //                  against all j + 1 columns, so the columns of H are full above the subdiagonal and its row k0 is full.
+// Complex and negative shifts (sns_stability_arnoldi_shifted): csrc/sns_shifted.hip; here only apply_S of arnoldi_run differs.
 // Out of scope: explicit locking / deflation of converged pairs; selections other than "nearest the shift"; a C implementation of
-// the ordered Schur form (C callers have the two device primitives and sns_host_hessenberg_eigs); complex or negative shifts; of
+// the ordered Schur form (C callers have the two device primitives and sns_host_hessenberg_eigs); of
 // the sensitivities, base flows with a body force or a backflow term, forcing on Dirichlet nodes and the exact form of
 // E = D_w[B^T z][x]; 2-D and partitioned handles; the Carreau law.
 #include "sns_ctx.h"
@@ -323,14 +324,22 @@ int basis_rotate(sns_ctx* h, int n_in, int n_out, const double* Q, double* V) {
 // left: the process on (J + shift B)^-T B^T -- the mass pass is the transposed one, and the entry point has flipped the operator.
 // k0 >= 1: continue the decomposition S V_k0 = V_{k0+1} H_k0 the caller holds in columns 0 .. k0 of V and the leading
 // (k0 + 1) x k0 block of H (kept; the rest of H is zeroed): no start vector treatment, steps j = k0 .. m - 1, m_done starts at k0.
+// c: the shifted step (csrc/sns_shifted.hip) -- S = Re[(A + c B)^-1 B], A the matrix the handle holds: the right-hand side is
+// B v + 0 i, the solve the complex one from a zero guess, w its real part; everything else is the process above.
 int arnoldi_run(sns_ctx* h, const double* w, bool left, int k0, int m, double breakdown_rel, double* V, double* H, int* m_done,
-                int* total_its, int* reason) {
+                int* total_its, int* reason, const double* c) {
     const int64_t ld = ld_of(h);
     const int g = std::max(1, vec_grid(ld));
     constexpr int CS = policy::STABILITY_M_MAX + 8;        // stride of one coefficient block (chunks of 8)
     DevBuf<double> b, co;                                  // b = B v; co: pass-1 and pass-2 coefficients, then (w.w, .) before and after
-    SNS_TRY(b.alloc((size_t)ld));
+    DevBuf<double> cy;                                     // the shifted step's complex solution (b then holds B v + 0 i)
+    CfgmresWork cw;
+    SNS_TRY(b.alloc((size_t)(c ? 2 : 1) * ld));
     SNS_TRY(co.alloc((size_t)2 * CS + 4));
+    if (c) {
+        SNS_TRY(cy.alloc((size_t)2 * ld));
+        HIP_TRY(hipMemsetAsync(b + ld, 0, (size_t)ld * sizeof(double), h->stream));
+    }
     for (int r = 0; r < m + 1; ++r)
         for (int c = 0; c < m; ++c)
             if (r > k0 || c >= k0) H[(size_t)r * m + c] = 0.0;
@@ -340,10 +349,16 @@ int arnoldi_run(sns_ctx* h, const double* w, bool left, int k0, int m, double br
     // w = S v, from a zero guess; false: the inner solve did not converge (*reason holds why)
     auto apply_S = [&](const double* v, double* out, bool* ok) -> int {
         launch_mass(h, left, w, v, b);
-        HIP_TRY(hipMemsetAsync(out, 0, (size_t)ld * sizeof(double), h->stream));
         int its = 0, kr = 0;
         double rn = 0.0;
-        SNS_TRY(krylov(h, b, out, &its, &kr, &rn, true));
+        if (c) {
+            HIP_TRY(hipMemsetAsync(cy, 0, (size_t)2 * ld * sizeof(double), h->stream));
+            SNS_TRY(cfgmres(h, w, c[0], c[1], left, b, cy, &its, &kr, &rn, cw));
+            HIP_TRY(hipMemcpyAsync(out, cy, (size_t)ld * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        } else {
+            HIP_TRY(hipMemsetAsync(out, 0, (size_t)ld * sizeof(double), h->stream));
+            SNS_TRY(krylov(h, b, out, &its, &kr, &rn, true));
+        }
         *total_its += its;
         *ok = kr > 0;
         if (!*ok) *reason = kr;

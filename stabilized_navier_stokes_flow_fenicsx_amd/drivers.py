@@ -583,7 +583,10 @@ def _stability(P, w):
     growing mode: the steady state is unstable.  Nothing without the switch: files and stdout stay as they are.
     SNS_STABILITY_RESTARTS=<max_restarts>[,<m>[,<keep>]] beside it: the thick-restarted process of ``linear_stability`` (a basis
     of m + 1 vectors instead of 65; m defaults to 64, keep to the function's default) and one more printed line, the restarts
-    taken.  Without that variable the call and the output are what they are without it."""
+    taken.  Without that variable the call and the output are what they are without it.
+    SNS_STABILITY_SHIFT_IMAG=<b> beside it: the shift becomes the complex <shift> + <b> i (``linear_stability`` with a complex
+    shift: the eigenvalues nearest a point off the real axis, where a Hopf pair sits; <shift> may then be negative, and b = 0
+    serves a negative real shift).  Without that variable the call and the output are what they are without it."""
     spec = os.environ.get("SNS_STABILITY", "")
     if not spec:
         return None
@@ -593,6 +596,9 @@ def _stability(P, w):
         return None
     parts = spec.split(",")
     n_modes, shift = int(parts[0]), (float(parts[1]) if len(parts) > 1 else 0.0)
+    imag = os.environ.get("SNS_STABILITY_SHIFT_IMAG", "")
+    if imag:
+        shift = complex(shift, float(imag))
     from .solver import SnsError, linear_stability, print_stability
     sens = os.environ.get("SNS_STABILITY_SENSITIVITY", "0") == "1"
     forcing = os.environ.get("SNS_STABILITY_FORCING", "0") == "1"

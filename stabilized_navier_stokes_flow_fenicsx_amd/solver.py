@@ -62,13 +62,13 @@ class ArnoldiResult:
 class StabilityResult:
     eigenvalues: np.ndarray     # (n,) complex, descending real part: the least stable first
     modes: torch.Tensor         # (n, ndof) complex128 on the device, unit 2-norm, largest-modulus entry real and positive
-    estimates: np.ndarray       # (n,) residual estimates |h_{m+1,m} e_m^T y| / |theta|
+    estimates: np.ndarray       # (n,) residual estimates |h_{m+1,m} e_m^T y| / |theta| (a complex shift: true residuals)
     converged: np.ndarray       # (n,) bool: estimate <= tol
     m_done: int
     ksp_its: int
     reason: int
     # linear_stability(left=True) only:
-    shift: float = 0.0
+    shift: float = 0.0          # (the complex shift of a complex-shift run)
     left_modes: Optional[torch.Tensor] = None     # (n, ndof) complex128: z with z^T J = -lam z^T B, scaled so that z^T B x = 1 (unconjugated); 0 where unpaired
     left_converged: Optional[np.ndarray] = None   # (n,) bool: the right pair converged and has a converged left partner
     left_eigenvalues: Optional[np.ndarray] = None  # (n,) complex: the partner's own Ritz value (nan where unpaired)
@@ -489,6 +489,82 @@ class FlowProblem:
             raise ValueError(f"V has {V.shape[0]} rows, Q asks for {n_in}")
         check(self.lib.sns_basis_rotate(self.h, n_in, n_out, Q.ctypes.data, _ptr(V)))
         return V
+
+    # -- complex and negative shifts: the library's complex vectors are planar (real parts, then imaginary parts) --------
+    def _planar(self, x) -> torch.Tensor:
+        """A complex (or real) dof vector as the planar float64 tensor of 2 * ndof the library reads."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x))
+        x = x.to(self.device)
+        if x.shape != (self.ndof,):
+            raise ValueError(f"expected a dof vector of {self.ndof} entries")
+        if x.is_complex():
+            return torch.cat([x.real.to(torch.float64), x.imag.to(torch.float64)]).contiguous()
+        return torch.cat([x.to(torch.float64), torch.zeros(self.ndof, dtype=torch.float64, device=self.device)]).contiguous()
+
+    def _unplanar(self, y) -> torch.Tensor:
+        return torch.complex(y[:self.ndof], y[self.ndof:])
+
+    def shifted_apply(self, w, c, x, transpose: bool = False) -> torch.Tensor:
+        """``A x + c B(w) x`` for a complex scalar ``c`` and a complex dof vector ``x`` (sns_shifted_apply): A is the matrix the
+        problem holds as it stands -- after ``jacobian(w)`` the Jacobian J, after a stability run J + pc_shift B --, B the
+        operator of ``mass_apply``, with ``transpose`` that of ``mass_apply_transpose`` (the caller flips A itself:
+        ``transpose_operator``).  Two operator passes and one pair mass pass, bitwise reproducible; with c = 0 the bits of
+        ``spmv`` on each part.  Returns a complex128 device tensor.  Single-GPU 3-D problems."""
+        w, xp = self._vec(w), self._planar(x)
+        c = complex(c)
+        out = torch.empty_like(xp)
+        check(self.lib.sns_shifted_apply(self.h, _ptr(w), c.real, c.imag, int(bool(transpose)), _ptr(xp), _ptr(out)))
+        return self._unplanar(out)
+
+    def shifted_solve(self, w, c, b, x0=None, transpose: bool = False):
+        """``(A + c B(w)) x = b`` by right-preconditioned complex FGMRES (sns_shifted_solve) with the problem's gmres_restart,
+        ksp_rtol / ksp_atol / ksp_max_it and the preconditioner of A on each part; A and ``transpose`` as in
+        ``shifted_apply``.  Returns (x complex128, KrylovResult); ``rnorm`` is the true residual norm, a solve that did not
+        converge says so in ``reason`` and leaves the problem usable."""
+        w, bp = self._vec(w), self._planar(b)
+        c = complex(c)
+        x = torch.zeros_like(bp) if x0 is None else self._planar(x0)
+        its, reason, rn = C.c_int(), C.c_int(), C.c_double()
+        check(self.lib.sns_shifted_solve(self.h, _ptr(w), c.real, c.imag, int(bool(transpose)), _ptr(bp), _ptr(x), C.byref(its),
+                                         C.byref(reason), C.byref(rn)))
+        return self._unplanar(x), KrylovResult(its.value, reason.value, rn.value)
+
+    def stability_arnoldi_shifted(self, w, shift, pc_shift: Optional[float] = None, m: int = 64, start=None,
+                                  breakdown_rel: float = 1e-6, side: str = "right", V=None, H=None, k: int = 0):
+        """Shift-invert Arnoldi with a complex or negative ``shift`` s in real arithmetic (sns_stability_arnoldi_shifted): the
+        process of ``stability_arnoldi`` on Re[(J + s B)^-1 B] (``side="left"``: Re[(J + s B)^-T B^T]), whose basis and H are
+        real.  The problem assembles and preconditions P = J + pc_shift B (``pc_shift`` >= 0, by default |s|); each step solves
+        the complex system (P + (s - pc_shift) B) y = B v (``shifted_solve``'s method) and keeps Re y.  ``k = 0``: a fresh
+        process, returns ``(V, H, ArnoldiResult)`` as ``stability_arnoldi``.  ``k >= 1`` with the ``V`` and ``H`` of an earlier
+        call: the continuation of ``stability_arnoldi_extend``, in place.  The eigenvalues follow from H by
+        ``solver.shifted_eigenpairs``, not ``ritz_pairs``.  Afterwards the problem's matrix is J + pc_shift B."""
+        if side not in ("right", "left"):
+            raise ValueError("side must be 'right' or 'left'")
+        s = complex(shift)
+        pc_shift = abs(s) if pc_shift is None else float(pc_shift)
+        w = self._vec(w)
+        if V is None:
+            m = int(m)
+            V = torch.zeros(max(m, 0) + 1, self.ndof, dtype=torch.float64, device=self.device)
+            if start is None:
+                V[0] = torch.cos(1.0 + 0.37 * torch.arange(self.ndof, dtype=torch.float64, device=self.device))
+            else:
+                V[0] = self._vec(start)
+            H = np.zeros((max(m, 0) + 1, max(m, 0)))
+        else:
+            if not (isinstance(H, np.ndarray) and H.dtype == np.float64 and H.ndim == 2 and H.flags.c_contiguous and
+                    H.shape[0] == H.shape[1] + 1):
+                raise ValueError("H must be the C-contiguous float64 (m + 1, m) array of stability_arnoldi_shifted")
+            m = H.shape[1]
+            if not (isinstance(V, torch.Tensor) and V.dtype == torch.float64 and V.shape == (m + 1, self.ndof) and V.is_contiguous()
+                    and V.device.type == "cuda"):
+                raise ValueError("V must be the contiguous float64 (m + 1, ndof) device tensor of stability_arnoldi_shifted")
+        done, its, reason = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.sns_stability_arnoldi_shifted(self.h, _ptr(w), s.real, s.imag, pc_shift, int(k), m, float(breakdown_rel),
+                                                     int(side == "left"), _ptr(V), H.ctypes.data, C.byref(done), C.byref(its),
+                                                     C.byref(reason)))
+        return V, H, ArnoldiResult(done.value, reason.value, its.value)
 
     def spmv(self, x, out=None) -> torch.Tensor:
         x = self._vec(x)
@@ -1477,32 +1553,106 @@ def default_keep(m: int, n_modes: int) -> int:
     return min(int(m) - 2, max(int(n_modes) + 2, int(m) // 2))
 
 
-def _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, side, breakdown_rel):
+def _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, side, breakdown_rel, pc_shift=None):
     """One side of ``linear_stability(max_restarts > 0)``: ``stability_arnoldi``, then estimates, truncate, ``basis_rotate``,
     ``stability_arnoldi_extend`` until the ``n_modes`` Ritz pairs of largest |theta| (nearest the shift) all have an estimate
     <= tol, ``max_restarts`` is reached, the space is invariant (reason 2) or an inner solve failed (reason < 0).  Returns
-    (V, H, ArnoldiResult with the Krylov iterations of all cycles, restarts)."""
-    V, H, res = problem.stability_arnoldi(w, shift=shift, m=m, side=side, breakdown_rel=breakdown_rel)
+    (V, H, ArnoldiResult with the Krylov iterations of all cycles, restarts).  ``pc_shift`` given (a complex ``shift``): the
+    same loop over ``stability_arnoldi_shifted``, with the true residuals of ``shifted_eigenpairs`` as the estimates."""
+    shifted = pc_shift is not None
+    if shifted:
+        V, H, res = problem.stability_arnoldi_shifted(w, shift, pc_shift, m=m, side=side, breakdown_rel=breakdown_rel)
+    else:
+        V, H, res = problem.stability_arnoldi(w, shift=shift, m=m, side=side, breakdown_rel=breakdown_rel)
     its, restarts = res.ksp_its, 0
     while res.reason == 1 and restarts < max_restarts:
-        lam, _, est = krylov_ritz_pairs(H, res.m_done, shift)
-        with np.errstate(invalid="ignore"):
-            lead = np.argsort(np.abs(lam - shift), kind="stable")[:max(0, int(n_modes))]
+        if shifted:
+            lam, _, est, theta = shifted_eigenpairs(problem, w, V, H, res.m_done, shift, pc_shift, side)
+            lead = np.argsort(-np.abs(theta), kind="stable")[:max(0, int(n_modes))]
+        else:
+            lam, _, est = krylov_ritz_pairs(H, res.m_done, shift)
+            with np.errstate(invalid="ignore"):
+                lead = np.argsort(np.abs(lam - shift), kind="stable")[:max(0, int(n_modes))]
         if (est[lead] <= tol).all():
             break
         k, Q, Hk = krylov_schur_truncate(H, res.m_done, keep)
         problem.basis_rotate(V, Q)
         H[:] = 0.0
         H[:k + 1, :k] = Hk
-        res = problem.stability_arnoldi_extend(w, V, H, k, shift=shift, side=side, breakdown_rel=breakdown_rel)
+        if shifted:
+            _, _, res = problem.stability_arnoldi_shifted(w, shift, pc_shift, side=side, breakdown_rel=breakdown_rel, V=V, H=H, k=k)
+        else:
+            res = problem.stability_arnoldi_extend(w, V, H, k, shift=shift, side=side, breakdown_rel=breakdown_rel)
         its += res.ksp_its
         restarts += 1
     return V, H, ArnoldiResult(res.m_done, res.reason, its), restarts
 
 
+def shifted_roots(theta, shift):
+    """The two eigenvalue candidates behind a Ritz value ``theta`` of S = Re[(J + s B)^-1 B], s = a + i b (pure numpy): an
+    eigenvalue lam of J x = -lam B x has theta = (a - lam) / ((s - lam)(conj(s) - lam)), i.e.
+    theta lam^2 + (1 - 2 a theta) lam + (theta |s|^2 - a) = 0, whose roots are a - r and a - b^2 / r with
+    r = (1 + sqrt(1 - 4 b^2 theta^2)) / (2 theta) (the product of the two r is b^2: no cancellation for small b theta).  With
+    b = 0 the first is the real-shift formula a - 1 / theta and the second is the shift itself.  Returns (lam1, lam2)."""
+    s = complex(shift)
+    a, b2 = s.real, s.imag * s.imag
+    theta = np.asarray(theta, dtype=complex)
+    r = (1.0 + np.sqrt(1.0 - 4.0 * b2 * theta * theta)) / (2.0 * theta)
+    return a - r, a - b2 / r
+
+
+def shifted_eigenpairs(problem: FlowProblem, w, V, H, m_done: int, shift, pc_shift: float, side: str = "right"):
+    """Eigenvalue estimates from the V and H of ``FlowProblem.stability_arnoldi_shifted`` (Hessenberg or, after a thick restart,
+    with a full last row).  Per Ritz pair (theta, y) of H[:m_done, :m_done], |y| = 1: x = V y, the two candidates of
+    ``shifted_roots``, and of them the one with the smaller TRUE residual |J x + lam B x| / (|lam| |B x|) -- one
+    ``shifted_apply`` at c = lam - pc_shift per candidate and two mass passes, so the problem must hold J + pc_shift B, as it
+    does after the Arnoldi call; ``side="left"``: the operator flipped for the duration and B^T.  That residual is the
+    estimate: it is what says whether a pair converged.  Of a conjugate pair of Ritz values only the member with Im theta > 0 is
+    evaluated; its partner gets the conjugates.  Returns ``(lam, Y, est, theta)`` in the order of ``ritz_pairs`` (descending
+    real part, the least stable first); theta = 0 (an infinite eigenvalue) sorts last with an infinite estimate."""
+    if side not in ("right", "left"):
+        raise ValueError("side must be 'right' or 'left'")
+    H = np.asarray(H, dtype=np.float64)
+    k = int(m_done)
+    if k < 1:
+        return np.zeros(0, complex), np.zeros((0, 0), complex), np.zeros(0), np.zeros(0, complex)
+    s, p, left = complex(shift), float(pc_shift), side == "left"
+    theta, Y = np.linalg.eig(H[:k, :k])
+    theta, Y = theta.astype(complex), Y.astype(complex)
+    Y = Y / np.linalg.norm(Y, axis=0)
+    lam, est = np.full(k, -np.inf + 0j), np.full(k, np.inf)
+    mass = problem.mass_apply_transpose if left else problem.mass_apply
+    Vk = V[:k].T
+    if left:
+        problem.transpose_operator()
+    try:
+        j = 0
+        while j < k:
+            pair = theta[j].imag > 0.0 and j + 1 < k and theta[j + 1] == np.conj(theta[j])
+            if theta[j] != 0.0:
+                y = Y[:, j]
+                x = torch.complex(Vk @ torch.from_numpy(y.real.copy()).to(V.device), Vk @ torch.from_numpy(y.imag.copy()).to(V.device))
+                nb = float(torch.linalg.vector_norm(_complex_apply(lambda v: mass(w, v), x)))
+                for cand in shifted_roots(theta[j], s):
+                    cand = complex(cand)
+                    if not np.isfinite(cand) or cand == 0.0 or not nb > 0.0:
+                        continue
+                    r = float(torch.linalg.vector_norm(problem.shifted_apply(w, cand - p, x, transpose=left))) / (abs(cand) * nb)
+                    if r < est[j]:
+                        lam[j], est[j] = cand, r
+            if pair:
+                lam[j + 1], est[j + 1], Y[:, j + 1] = np.conj(lam[j]), est[j], np.conj(Y[:, j])
+            j += 2 if pair else 1
+    finally:
+        if left:
+            problem.transpose_operator()
+    order = np.lexsort((-lam.imag, -lam.real))
+    return lam[order], Y[:, order], est[order], theta[order]
+
+
 def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0.0, m: int = 64, tol: float = 1e-7,
                      ksp_rtol: float = 1e-10, left: bool = False, pair_rtol: float = 1e-5, max_restarts: int = 0,
-                     keep: Optional[int] = None, breakdown_rel: float = 1e-6) -> StabilityResult:
+                     keep: Optional[int] = None, breakdown_rel: float = 1e-6, pc_shift: Optional[float] = None) -> StabilityResult:
     """Leading eigenvalues and modes of the linearised transient operator B x_t + J x = 0 at the steady state ``w``: is the
     state stable (every Re lam < 0), and if not, at which frequency Im lam / 2 pi does it go?  ``m`` steps of shift-invert
     Arnoldi (``FlowProblem.stability_arnoldi``) with the inner tolerance ``ksp_rtol`` (the problem's options are restored
@@ -1534,9 +1684,24 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
     in passing (on the (6,3,3) test duct -5.35 +- 6.07i, |lam| = 8.1, behind four nearer ones), is not kept; move the shift or
     raise ``n_modes`` and ``keep`` if the least stable mode need not be the one nearest the shift.  ``breakdown_rel`` (restarted runs only) is handed to
     every cycle: on a space that is invariant after a few steps it has to sit above what the inner tolerance leaves of the
-    step's norm.  Not built: explicit locking / deflation of
-    converged pairs, selections other than "nearest the shift" (rightmost Re lam wanders), complex or negative shifts."""
+    step's norm.
+
+    A ``complex`` shift s = a + i b (and only that type: a ``float`` goes where it always went, bit for bit) runs shift-invert in
+    real Arnoldi arithmetic on Re[(J + s B)^-1 B] (``FlowProblem.stability_arnoldi_shifted``; Parlett & Saad): the eigenvalues
+    nearest s AND nearest conj(s), so a Hopf pair far from the real axis is reached directly, and a < 0 is allowed
+    (``complex(a, 0)`` is a negative real shift).  The basis stays real, so restarts, ``left=True``, pairing and scaling are the
+    ones above; eigenvalues and estimates come from ``shifted_eigenpairs``: ``estimates`` then holds TRUE residuals
+    |J x + lam B x| / (|lam| |B x|), and ``tol`` is compared with those.  ``pc_shift`` >= 0 (default |s|): the real shift of the
+    matrix J + pc_shift B that is assembled and preconditioned; the inner solver is a complex FGMRES whatever ksp_type says.
+    Not built: explicit locking / deflation of converged pairs, selections other than "nearest the shift" (rightmost Re lam
+    wanders), a complex Arnoldi basis."""
     max_restarts = int(max_restarts)
+    cx = isinstance(shift, (complex, np.complexfloating))
+    if cx:
+        shift = complex(shift)
+        pc_shift = abs(shift) if pc_shift is None else float(pc_shift)
+    elif pc_shift is not None:
+        raise ValueError("pc_shift belongs to a complex shift")
     if max_restarts > 0:
         keep = default_keep(m, n_modes) if keep is None else int(keep)
         if not 1 <= keep <= int(m) - 1:
@@ -1545,7 +1710,16 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
     problem.set_options(ksp_rtol=float(ksp_rtol))
     restarts = restartsL = 0
     try:
-        if max_restarts > 0:
+        if cx and max_restarts > 0:
+            V, H, res, restarts = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "right", breakdown_rel, pc_shift)
+            if left:
+                VL, HL, resL, restartsL = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "left", breakdown_rel,
+                                                             pc_shift)
+        elif cx:
+            V, H, res = problem.stability_arnoldi_shifted(w, shift, pc_shift, m=m)
+            if left:
+                VL, HL, resL = problem.stability_arnoldi_shifted(w, shift, pc_shift, m=m, side="left")
+        elif max_restarts > 0:
             V, H, res, restarts = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "right", breakdown_rel)
             if left:
                 VL, HL, resL, restartsL = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "left", breakdown_rel)
@@ -1555,7 +1729,11 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
                 VL, HL, resL = problem.stability_arnoldi(w, shift=shift, m=m, side="left")
     finally:
         problem.set_options(ksp_rtol=old)
-    pairs_of = krylov_ritz_pairs if max_restarts > 0 else ritz_pairs
+    if cx:
+        def pairs_of(Hs, k, _, Vs=None, side="right"):
+            return shifted_eigenpairs(problem, w, V if Vs is None else Vs, Hs, k, shift, pc_shift, side)[:3]
+    else:
+        pairs_of = krylov_ritz_pairs if max_restarts > 0 else ritz_pairs
     lam, Y, est = pairs_of(H, res.m_done, shift)
     # the converged pairs in ritz_pairs' order, then the others by their estimate: an unconverged Ritz value near theta = 0 (the
     # infinite eigenvalues of the pencil; B has no pressure columns) has an arbitrary, often huge positive, real part
@@ -1574,11 +1752,11 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
         modes = modes * (big.conj() / big.abs())
     else:
         modes = torch.zeros(0, problem.ndof, dtype=torch.complex128, device=V.device)
-    result = StabilityResult(lam, modes, est, est <= tol, res.m_done, res.ksp_its, res.reason, float(shift))
+    result = StabilityResult(lam, modes, est, est <= tol, res.m_done, res.ksp_its, res.reason, shift if cx else float(shift))
     result.restarts = restarts
     if not left:
         return result
-    lamL, YL, estL = pairs_of(HL, resL.m_done, shift)
+    lamL, YL, estL = pairs_of(HL, resL.m_done, shift, VL, "left") if cx else pairs_of(HL, resL.m_done, shift)
     okL = np.nonzero(estL <= tol)[0]
     partner = pair_left_right(np.where(result.converged, lam, np.nan), lamL[okL], shift, pair_rtol)
     zs = torch.zeros_like(modes)
@@ -1594,6 +1772,23 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
     result.left_m_done, result.left_ksp_its, result.left_reason = resL.m_done, resL.ksp_its, resL.reason
     result.left_restarts = restartsL
     return result
+
+
+def harmonic_response(problem: FlowProblem, w, omega: float, f):
+    """The frequency response of the flow linearised at the steady state ``w`` to a harmonic body force f exp(i omega t):
+    q = (J + i omega B)^-1 B f, so that q exp(i omega t) solves B x_t + J x = B f exp(i omega t).  ``f``: a real or complex dof
+    vector (pressure and constrained entries are ignored, as ``mass_apply`` ignores them).  The Jacobian is assembled at ``w``,
+    its hierarchy preconditions the complex solve (``FlowProblem.shifted_solve`` at c = i omega, with the problem's ksp
+    options).  Returns (q complex128 device tensor, KrylovResult); |q| against omega is the gain curve, whose peak sits at the
+    frequency of the least damped mode."""
+    problem.jacobian(w)
+    f = f if isinstance(f, torch.Tensor) else torch.as_tensor(np.asarray(f))
+    f = f.to(problem.device)
+    if f.is_complex():
+        b = _complex_apply(lambda v: problem.mass_apply(w, v), f)
+    else:
+        b = problem.mass_apply(w, f)
+    return problem.shifted_solve(w, 1j * float(omega), b)
 
 
 def _mode_pair(result: StabilityResult, k: int):

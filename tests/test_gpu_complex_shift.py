@@ -1,0 +1,393 @@
+"""The stability analysis with a complex or negative shift on the GPU (sns_shifted_apply / k_mass_axpy_pair, sns_shifted_solve /
+cfgmres with k_cdot8 and k_caxpy8, sns_stability_arnoldi_shifted; solver.linear_stability(shift=complex),
+solver.harmonic_response), everything through the C-ABI.
+
+The yardstick is the test-side oracle tests/complex_shift_oracle.py (scipy's complex sparse LU on the oracle's J and B, numpy
+Arnoldi on Re[(J + s B)^-1 B]), whose own checks are tests/test_host_complex_shift.py.  Cases: the ducts (6,3,3) Re 50 -- 448
+dofs, no multiple of the block of 256, node -> cell lists of every length mod 4 --, (8,3,3) Re 200 and (3,2,2).  Bounds: the
+operator 1e-12 relative to the largest entry of the result (the project's operator standard); against the composition of the
+single-vector passes 1e-13 (the rounding of the epilogue); a solve's residual with the ORACLE's matrices 10 x ksp_rtol (recursive
+versus true residual and the 1e-12 operator difference, as tests/test_gpu_stability.py grants); orthogonality 1e-12; what depends
+on the inner tolerance -- the Arnoldi relation, the eigenvalues -- 10 x what the oracle's emulation of that tolerance gives,
+computed here at run time."""
+import functools
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import torch
+
+import complex_shift_oracle as CO
+import stability_oracle as SO
+from oracle import forms_literal as FL
+from stabilized_navier_stokes_flow_fenicsx_amd import mesh2d as M2
+from stabilized_navier_stokes_flow_fenicsx_amd import solver as S
+from stabilized_navier_stokes_flow_fenicsx_amd.solver import FlowProblem, SnsError
+
+pytestmark = pytest.mark.gpu
+INNER = 1e-10
+TOL = 1e-7
+SHIFT = -5 + 6j
+RECORDED = [-5.35278 + 6.06606j, -5.94101 + 5.83224j, -6.34740 + 4.67745j]           # duct633, Im > 0
+KSP_DIVERGED_ITS = -3
+
+
+def _dev(x):
+    x = np.ascontiguousarray(x)
+    return torch.from_numpy(x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)).cuda()
+
+
+def _problem(c, **kw):
+    return FlowProblem(c.mesh, (c.mask, c.g), reynolds=c.Re, **kw)
+
+
+def _hold(P, c, wd, p):
+    """The problem's matrix becomes J + p B, as a shifted run assembles it."""
+    if p > 0.0:
+        P.set_time_term(p, 0.0, _dev(-p * c.w))
+    P.jacobian(wd)
+    if p > 0.0:
+        P.clear_time_term()
+
+
+@functools.lru_cache(maxsize=None)
+def dense_spectrum(name):
+    c = SO.case(name)
+    return SO.dense_spectrum(*c.operators(), c.constrained)
+
+
+# ---- 1. the complex operator -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("transpose", [False, True])
+@pytest.mark.parametrize("variant", ["plain", "corrected", "form_variant", "viscosity_field"])
+def test_shifted_apply_against_the_oracle(variant, transpose):
+    c = SO.case("duct633")
+    rng = np.random.default_rng(83)
+    n = len(c.w)
+    x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+    cc, p = (SHIFT - abs(SHIFT)), abs(SHIFT)
+    form, base = {}, dict(FL.VARIANT)
+    P = _problem(c, corrected_convection=int(variant == "corrected"))
+    try:
+        if variant == "corrected":
+            form = dict(corrected_convection=True)
+        if variant == "form_variant":
+            FL.VARIANT.update(ci=144.0, pspg=-1.0, one_point=True)
+            P.set_form_variant(c_inverse=144.0, pspg_sign=-1.0, one_point_quadrature=True)
+        if variant == "viscosity_field":
+            nu = (1.0 / c.Re) * np.exp(rng.uniform(-1.5, 1.5, len(c.mesh.tets)))
+            form = dict(nu_t=nu)
+            P.set_element_viscosity(nu)
+        A, B = c.jacobian(p, **form), c.mass(**form)
+    finally:
+        FL.VARIANT.update(base)
+    if transpose:
+        A, B = sp.csr_matrix(A.T), sp.csr_matrix(B.T)
+    wd, xd = _dev(c.w), _dev(x)
+    _hold(P, c, wd, p)
+    if transpose:
+        P.transpose_operator()
+    ref = CO.operator(A, B, cc) @ x
+    y = P.shifted_apply(wd, cc, xd, transpose=transpose)
+    err = np.abs(y.cpu().numpy() - ref).max() / np.abs(ref).max()
+    print(variant, transpose, "max|dy| / max|y_ref| =", err)
+    assert err <= 1e-12
+    assert torch.equal(y, P.shifted_apply(wd, cc, xd, transpose=transpose))            # two calls: identical bits
+    # c = 0: the bits of the operator pass on each part
+    y0 = P.shifted_apply(wd, 0.0, xd, transpose=transpose)
+    ar, ai = P.spmv(xd.real.contiguous()).clone(), P.spmv(xd.imag.contiguous()).clone()
+    assert torch.equal(y0.real, ar) and torch.equal(y0.imag, ai)
+    # the composition of the single-vector passes: the same sums per part, the rounding of the epilogue apart
+    mass = P.mass_apply_transpose if transpose else P.mass_apply
+    br, bi = mass(wd, xd.real.contiguous()).clone(), mass(wd, xd.imag.contiguous()).clone()
+    comp = torch.complex(ar + (cc.real * br - cc.imag * bi), ai + (cc.real * bi + cc.imag * br))
+    d = float((y - comp).abs().max() / y.abs().max())
+    print(variant, transpose, "against the composition", d)
+    assert d <= 1e-13
+    # entries of x the single-vector pass ignores do not reach the B part: y - A x stays
+    x2 = x.copy()
+    x2[c.constrained] += rng.standard_normal(c.constrained.sum()) + 1j * rng.standard_normal(c.constrained.sum())
+    if not transpose:
+        x2[3::4] += rng.standard_normal(n // 4) + 1j * rng.standard_normal(n // 4)     # (B^T reads the pressure entries)
+    x2d = _dev(x2)
+    y2 = P.shifted_apply(wd, cc, x2d, transpose=transpose)
+    a2 = torch.complex(P.spmv(x2d.real.contiguous()).clone(), P.spmv(x2d.imag.contiguous()).clone())
+    d2 = float(((y2 - a2) - (y - torch.complex(ar, ai))).abs().max() / max(float(y.abs().max()), float(y2.abs().max())))
+    print(variant, transpose, "B part under ignored entries", d2)
+    assert d2 <= 1e-13
+    # rows of B that are 0: constrained rows (and, transposed, pressure rows) hold the operator pass's bits
+    yn, an = y.cpu().numpy(), torch.complex(ar, ai).cpu().numpy()
+    assert np.array_equal(yn[c.constrained], an[c.constrained])
+    if transpose:
+        assert np.array_equal(yn[3::4], an[3::4])
+    P.close()
+
+
+# ---- 2. the complex solve ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("transpose", [False, True])
+@pytest.mark.parametrize("restart", [100, 20])
+@pytest.mark.parametrize("name", ["duct633", "duct833"])
+def test_shifted_solve_against_the_oracle(name, restart, transpose):
+    c = SO.case(name)
+    J, B = c.operators()
+    rng = np.random.default_rng(29)
+    n = len(c.w)
+    s = SHIFT if name == "duct633" else -2 + 8j
+    p = abs(s)
+    cc = s - p
+    A = c.jacobian(p)
+    if transpose:
+        A, B = sp.csr_matrix(A.T), sp.csr_matrix(B.T)
+    M = CO.operator(A, B, cc)
+    b = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+    P = _problem(c, ksp_rtol=INNER, gmres_restart=restart)
+    wd = _dev(c.w)
+    _hold(P, c, wd, p)
+    if transpose:
+        P.transpose_operator()
+    x, res = P.shifted_solve(wd, cc, _dev(b), transpose=transpose)
+    true = np.linalg.norm(b - M @ x.cpu().numpy()) / np.linalg.norm(b)
+    print(name, restart, transpose, "its", res.its, "reason", res.reason, "reported", res.rnorm / np.linalg.norm(b), "oracle's", true)
+    assert res.reason > 0 and res.its > 0
+    assert true <= 10.0 * INNER
+    if restart == 20 and name == "duct633" and not transpose:
+        assert res.its > restart                                                       # restarts did occur
+        # a guess is used: from the solution the solve ends at once; from a perturbed one it converges again
+        x1, r1 = P.shifted_solve(wd, cc, _dev(b), x0=x, transpose=transpose)
+        assert r1.reason > 0 and r1.its <= 1
+        # an exhausted ksp_max_it is reported and leaves the handle usable
+        P.set_options(ksp_max_it=3)
+        x3, r3 = P.shifted_solve(wd, cc, _dev(b), transpose=transpose)
+        assert (r3.reason, r3.its) == (KSP_DIVERGED_ITS, 3) and r3.rnorm > INNER * np.linalg.norm(b)
+        P.set_options(ksp_max_it=10000)
+        x4, r4 = P.shifted_solve(wd, cc, _dev(b), transpose=transpose)
+        assert r4.reason > 0 and r4.its == res.its and torch.equal(x4, x)              # ... and reproducible to the bit
+    P.close()
+
+
+def test_harmonic_response_is_the_shifted_solve():
+    c = SO.case("duct633")
+    J, B = c.operators()
+    rng = np.random.default_rng(3)
+    f = np.where(c.constrained, 0.0, rng.standard_normal(len(c.w)))
+    omega = 6.0
+    P = _problem(c, ksp_rtol=INNER, gmres_restart=100)
+    q, res = S.harmonic_response(P, _dev(c.w), omega, _dev(f))
+    P.close()
+    b = B @ f
+    true = np.linalg.norm(b - CO.operator(J, B, 1j * omega) @ q.cpu().numpy()) / np.linalg.norm(b)
+    print("harmonic response: its", res.its, "relative residual with the oracle's matrices", true)
+    assert res.reason > 0 and true <= 10.0 * INNER
+
+
+# ---- 3. the process ----------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def gpu_run(side):
+    c = SO.case("duct633")
+    P = _problem(c, ksp_rtol=INNER, gmres_restart=100)
+    V, H, res = P.stability_arnoldi_shifted(_dev(c.w), SHIFT, m=24, side=side)
+    after = (P.operator_transposed, abs(P.to_scipy() - c.jacobian(abs(SHIFT))).max() / abs(c.jacobian(abs(SHIFT))).max())
+    P.set_time_term(1.0, 0.0, P.zeros())                                               # (allowed again: none is set)
+    P.clear_time_term()
+    P.close()
+    return V.cpu().numpy(), H, res, after
+
+
+@functools.lru_cache(maxsize=None)
+def emulation(side):
+    """The oracle's process at the inner tolerance: its relation and the worst distance of a converged pair to the dense spectrum."""
+    c = SO.case("duct633")
+    J, B = c.operators()
+    left = side == "left"
+    Jm, Bm = (sp.csr_matrix(J.T), sp.csr_matrix(B.T)) if left else (J, B)
+    V, H, m_done, _ = CO.arnoldi(J, B, c.constrained, SHIFT, m=24, inner_rtol=INNER, left=left)
+    lam, _, res = CO.recover(Jm, Bm, V, H, m_done, SHIFT)
+    return dict(relation=CO.relation(Jm, Bm, c.constrained, SHIFT, V, H, m_done), worst=SO.nearest(dense_spectrum("duct633"), lam[res <= TOL]).max(),
+                converged=int((res <= TOL).sum()))
+
+
+@pytest.mark.parametrize("side", ["right", "left"])
+def test_shifted_arnoldi_basis_relation_and_eigenvalues(side):
+    c = SO.case("duct633")
+    J, B = c.operators()
+    Jm, Bm = (sp.csr_matrix(J.T), sp.csr_matrix(B.T)) if side == "left" else (J, B)
+    V, H, res, (flipped, dA) = gpu_run(side)
+    emu = emulation(side)
+    assert (res.m_done, res.reason) == (24, 1) and res.ksp_its > 24
+    orth = SO.orthogonality(V, 25)
+    rel = CO.relation(Jm, Bm, c.constrained, SHIFT, V, H, 24)
+    lam, _, r = CO.recover(Jm, Bm, V, H, 24, SHIFT)
+    conv = r <= TOL
+    worst = SO.nearest(dense_spectrum("duct633"), lam[conv]).max()
+    print(side, "orthogonality", orth, "relation", rel, "emulation", emu["relation"], "ksp its", res.ksp_its, "converged", conv.sum(),
+          "emulation", emu["converged"], "worst", worst, "emulation", emu["worst"])
+    assert orth <= 1e-12
+    assert rel <= 10.0 * emu["relation"]
+    assert conv.sum() >= 6 and worst <= 10.0 * emu["worst"]
+    for want in RECORDED:
+        assert np.abs(lam[conv] - want).min() <= 1e-5 and np.abs(lam[conv] - np.conj(want)).min() <= 1e-5
+    assert not V[:, c.constrained].any() and not H[np.tril_indices(25, -2, 24)].any()
+    # the handle afterwards: untransposed, J + pc_shift B, the form steady (gpu_run set and cleared a time term)
+    assert not flipped and dA <= 1e-12
+
+
+def test_linear_stability_with_a_complex_shift():
+    c = SO.case("duct633")
+    J, B = c.operators()
+    wd = _dev(c.w)
+    fresh = _problem(c)
+    w_ref, n_ref = fresh.newton_solve(_dev(SO.case("duct633").w * 0.9 + 0.1 * c.g))
+    fresh.close()
+    P = _problem(c, gmres_restart=100)
+    r = S.linear_stability(P, wd, n_modes=8, shift=SHIFT, m=24, tol=TOL, ksp_rtol=INNER, left=True)
+    assert P.options.ksp_rtol == 1e-8 and not P.operator_transposed and r.shift == SHIFT
+    X, Z = r.modes.cpu().numpy(), r.left_modes.cpu().numpy()
+    for want in RECORDED:
+        for target in (want, np.conj(want)):
+            j = int(np.abs(r.eigenvalues - target).argmin())
+            true = SO.mode_residual(J, B, r.eigenvalues[j], X[j])
+            print(target, "->", r.eigenvalues[j], "estimate", r.estimates[j], "oracle's residual", true, "z^T B x", Z[j] @ (B @ X[j]))
+            assert abs(r.eigenvalues[j] - target) <= 1e-5 and r.converged[j] and r.left_converged[j]
+            assert true <= 10.0 * TOL
+            assert abs(Z[j] @ (B @ X[j]) - 1.0) <= 1e-8
+    assert SO.nearest(dense_spectrum("duct633"), r.eigenvalues[r.converged]).max() <= 10.0 * TOL
+    # the wavemaker and the Reynolds sensitivity take the result unchanged
+    k = int(np.abs(r.eigenvalues - RECORDED[0]).argmin())
+    assert torch.isfinite(S.structural_sensitivity(P, wd, r, k)).all()
+    d_lam, _ = S.eigenvalue_reynolds_sensitivity(P, wd, r, k=k)
+    assert np.isfinite(d_lam)
+    # restarted, m = 12: the same pairs
+    r2 = S.linear_stability(P, wd, n_modes=6, shift=SHIFT, m=12, tol=TOL, ksp_rtol=INNER, max_restarts=40)
+    print("restarts", r2.restarts, r2.eigenvalues, r2.estimates)
+    assert 1 <= r2.restarts < 40 and r2.reason == 1 and r2.m_done == 12 and r2.converged.all()
+    for want in RECORDED:
+        assert np.abs(r2.eigenvalues - want).min() <= 1e-5 and np.abs(r2.eigenvalues - np.conj(want)).min() <= 1e-5
+    # a negative real shift
+    r3 = S.linear_stability(P, wd, n_modes=3, shift=complex(-6.0, 0.0), m=16, tol=TOL, ksp_rtol=INNER, max_restarts=40)
+    dense = dense_spectrum("duct633")
+    target = dense[np.argsort(np.abs(dense + 6.0))][:3]
+    print("shift -6: restarts", r3.restarts, r3.eigenvalues, "nearest", target)
+    assert r3.converged.all() and SO.nearest(np.concatenate([r3.eigenvalues, r3.eigenvalues.conj()]), target).max() <= 10.0 * TOL
+    # the handle afterwards solves a Newton step as a fresh one does
+    w2, n2 = P.newton_solve(_dev(c.w * 0.9 + 0.1 * c.g))
+    print("Newton afterwards: its", n2.its, "reason", n2.reason, "fresh handle: its", n_ref.its, "reason", n_ref.reason)
+    assert n2.reason > 0 and n2.reason == n_ref.reason
+    assert float((w2 - w_ref).abs().max()) <= 1e-9 * float(w_ref.abs().max())
+    P.close()
+
+
+def test_a_float_shift_goes_where_it_went():
+    """linear_stability with a float shift: the result of the real entry points composed by hand, bit for bit, and not one
+    call of the new ones."""
+    c = SO.case("duct633")
+    wd = _dev(c.w)
+    P = _problem(c)
+    called = []
+    for name in ("stability_arnoldi_shifted", "shifted_apply", "shifted_solve"):
+        setattr(P, name, lambda *a, _n=name, **kw: called.append(_n))
+    r = S.linear_stability(P, wd, n_modes=6, shift=2.5, m=16, tol=TOL, ksp_rtol=INNER)
+    P.close()
+    Q = _problem(c, ksp_rtol=INNER)
+    V, H, res = Q.stability_arnoldi(wd, shift=2.5, m=16)
+    Q.close()
+    lam, Y, est = S.ritz_pairs(H, res.m_done, 2.5)
+    ok = est <= TOL
+    pick = np.concatenate([np.nonzero(ok)[0], np.nonzero(~ok)[0][np.argsort(est[~ok], kind="stable")]])[:6]
+    assert called == [] and isinstance(r.shift, float) and r.shift == 2.5
+    assert np.array_equal(r.eigenvalues, lam[pick]) and np.array_equal(r.estimates, est[pick])
+    assert (r.m_done, r.ksp_its, r.reason) == (res.m_done, res.ksp_its, res.reason)
+
+
+def test_an_unconverged_inner_solve_ends_the_shifted_process_quietly():
+    c = SO.case("duct633")
+    P = _problem(c, ksp_max_it=1)
+    wd = _dev(c.w)
+    before = P.residual(wd).clone()
+    r = S.linear_stability(P, wd, n_modes=4, shift=SHIFT, m=12, tol=TOL, ksp_rtol=1e-14, left=True, max_restarts=20)
+    print("reason", r.reason, r.left_reason, "m_done", r.m_done, r.left_m_done)
+    assert r.reason == KSP_DIVERGED_ITS and r.left_reason == KSP_DIVERGED_ITS and r.m_done == 0 and r.left_m_done == 0
+    assert r.restarts == 0 and len(r.eigenvalues) == 0
+    assert torch.equal(P.residual(wd), before) and not P.operator_transposed
+    P.close()
+
+
+# ---- 4. refusals -------------------------------------------------------------------------------------------------------------------
+def test_refusals_of_the_complex_shift_calls():
+    c = SO.case("duct322")
+    P = _problem(c)
+    wd = _dev(c.w)
+    x = torch.zeros(P.ndof, dtype=torch.complex128, device="cuda")
+    with pytest.raises(SnsError) as e:
+        P.shifted_apply(wd, 1j, x)                                                     # no matrix yet
+    assert e.value.code == -3 and "sns_shifted_apply" in str(e.value)
+    P.jacobian(wd)
+    for bad in (complex(float("nan"), 0.0), complex(0.0, float("inf"))):
+        for call in (lambda: P.shifted_apply(wd, bad, x), lambda: P.shifted_solve(wd, bad, x)):
+            with pytest.raises(SnsError) as e:
+                call()
+            assert e.value.code == -1 and str(e.value).endswith("both parts of c must be finite")
+    for kw, text in ((dict(m=1), "m must lie in [2, 64]"), (dict(m=65), "m must lie in [2, 64]"),
+                     (dict(shift=complex(float("nan"), 1.0)), "both parts of the shift must be finite"),
+                     (dict(pc_shift=-1.0), "pc_shift must be finite and >= 0"), (dict(pc_shift=float("inf")), "pc_shift must be finite and >= 0"),
+                     (dict(breakdown_rel=0.0), "breakdown_rel must lie in (0, 1)")):
+        args = dict(shift=SHIFT, m=8)
+        args.update(kw)
+        for side in ("right", "left"):
+            with pytest.raises(SnsError) as e:
+                P.stability_arnoldi_shifted(wd, side=side, **args)
+            assert e.value.code == -1 and str(e.value).endswith("sns_stability_arnoldi_shifted: " + text), (kw, side)
+    V, H = torch.zeros(9, P.ndof, dtype=torch.float64, device="cuda"), np.zeros((9, 8))
+    for k in (-1, 8):
+        with pytest.raises(SnsError) as e:
+            P.stability_arnoldi_shifted(wd, SHIFT, V=V, H=H, k=k)
+        assert e.value.code == -1 and str(e.value).endswith("k must lie in [0, m - 1]")
+    # the state: the existing texts
+    P.set_time_term(1.0, 0.0, P.zeros())
+    for side in ("right", "left"):
+        with pytest.raises(SnsError) as e:
+            P.stability_arnoldi_shifted(wd, SHIFT, m=8, side=side)
+        assert e.value.code == -3 and str(e.value).endswith("not with a time term set (the analysis sets its own and clears it)")
+    P.shifted_apply(wd, 1j, x)                                                         # (the operator ignores a time term, as the mass pass does)
+    P.clear_time_term()
+    P.set_viscosity_law(0.5, 0.7)
+    for call in (lambda: P.stability_arnoldi_shifted(wd, SHIFT, m=8), lambda: P.stability_arnoldi_shifted(wd, SHIFT, m=8, side="left"),
+                 lambda: P.shifted_apply(wd, 1j, x), lambda: P.shifted_apply(wd, 1j, x, transpose=True), lambda: P.shifted_solve(wd, 1j, x)):
+        with pytest.raises(SnsError) as e:
+            call()
+        assert e.value.code == -3 and str(e.value).endswith("not with a viscosity law set (the mass operator of the law's form is not built)")
+    P.clear_viscosity_law()
+    with pytest.raises(ValueError):
+        P.stability_arnoldi_shifted(wd, SHIFT, m=8, side="both")
+    with pytest.raises(ValueError):
+        P.shifted_apply(wd, 1j, x[:-1])
+    P.close()
+    # 2-D handles
+    m2 = M2.dfg_2d_mesh(0.5)
+    P2 = FlowProblem(m2, M2.dfg2d_bcs(m2).flatten(), reynolds=100.0)
+    x2 = torch.zeros(P2.ndof, dtype=torch.complex128, device="cuda")
+    for call in (lambda: P2.stability_arnoldi_shifted(P2.zeros(), SHIFT, m=8), lambda: P2.shifted_apply(P2.zeros(), 1j, x2),
+                 lambda: P2.shifted_solve(P2.zeros(), 1j, x2, transpose=True)):
+        with pytest.raises(SnsError) as e:
+            call()
+        assert e.value.code == -1 and str(e.value).endswith("3-D handles only")
+    P2.close()
+
+
+# ---- 5. the scripts' switch ------------------------------------------------------------------------------------------------------
+def test_the_driver_switch_makes_the_shift_complex(monkeypatch, capsys):
+    """SNS_STABILITY_SHIFT_IMAG beside SNS_STABILITY: the shift becomes complex; alone it does nothing."""
+    from stabilized_navier_stokes_flow_fenicsx_amd import drivers as D
+    c = SO.case("duct633")
+    P = _problem(c, gmres_restart=100)
+    wd = _dev(c.w)
+    for name in ("SNS_STABILITY_SENSITIVITY", "SNS_STABILITY_FORCING", "SNS_STABILITY", "SNS_STABILITY_RESTARTS"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setenv("SNS_STABILITY_SHIFT_IMAG", "6")
+    assert D._stability(P, wd) is None and capsys.readouterr().out == ""
+    monkeypatch.setenv("SNS_STABILITY", "4,-5")
+    monkeypatch.setenv("SNS_STABILITY_RESTARTS", "40,12")
+    r = D._stability(P, wd)
+    lines = capsys.readouterr().out.splitlines()
+    P.close()
+    assert r.shift == SHIFT and r.converged.all()
+    assert len(lines) == 5 and all(ln.startswith("Stability mode:") for ln in lines[:4]) and lines[4].startswith("Stability restarts:")
+    assert np.abs(r.eigenvalues - RECORDED[0]).min() <= 1e-5
