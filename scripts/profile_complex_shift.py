@@ -1,4 +1,4 @@
-"""Writes profiles/complex_shift.txt: the cost record of the stability analysis with a complex or negative shift (k_mass_axpy_pair,
+"""Writes profiles/complex_shift.txt: the cost record of the stability analysis with a complex or negative shift (k_mass_pass<., ., 2>,
 k_cdot8, k_caxpy8; sns_shifted_apply, sns_shifted_solve, sns_stability_arnoldi_shifted; solver.linear_stability(shift=complex)).
 
   0  per kernel of the feature, the VGPR / SGPR / scratch / LDS / occupancy figures of the gfx950 compile
@@ -28,7 +28,7 @@ for p in (ROOT, HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
 OUT = os.path.join(ROOT, "profiles", "complex_shift.txt")
-KERNELS = (("sns_shifted.hip", "k_mass_axpy_pair"), ("sns_kernels.hip", "k_cdot8"), ("sns_kernels.hip", "k_caxpy8"))
+KERNELS = (("sns_stability.hip", "k_mass_pass"), ("sns_kernels.hip", "k_cdot8"), ("sns_kernels.hip", "k_caxpy8"))
 
 
 def _progress(what):
@@ -160,7 +160,7 @@ def main():
                 L.append("   %-52s %s" % (r["name"], {k: v for k, v in r.items() if k != "name"}))
                 scratch = max(scratch, r.get("ScratchSize", 0))
     L.append(f"   scratch over the kernels of the feature: {scratch} bytes/lane" + ("" if scratch == 0 else "   NON-ZERO: a kernel spills"))
-    L.append("   k_mass_axpy_pair<corrected, transposed>: the single-vector passes hold 118 - 134 VGPRs; the second part costs the difference")
+    L.append("   k_mass_pass<corrected, transposed, NP>: the single-vector passes (NP = 1) hold 118 - 134 VGPRs; the second part (NP = 2) costs the difference")
     L.append("1  Bytes and memory -- arithmetic, not measured")
     L.append("   one complex operator application reads the operator twice (two passes) and the mesh data of the mass pass ONCE; the four "
              "separate passes read the mesh data twice and need three more vector passes to combine c B x into y")

@@ -1,7 +1,7 @@
-"""Writes profiles/stability_left.txt: the cost record of the left stability modes (k_mass_apply_t, sns_stability_arnoldi_left,
+"""Writes profiles/stability_left.txt: the cost record of the left stability modes (k_mass_pass<., true, 1>, sns_stability_arnoldi_left,
 solver.linear_stability(left=True), solver.eigenvalue_reynolds_sensitivity).
 
-  0  per kernel, the VGPR / SGPR / scratch / occupancy figures of the gfx950 compile, the transposed pass beside k_mass_apply
+  0  per kernel, the VGPR / SGPR / scratch / occupancy figures of the gfx950 compile, the transposed pass beside the forward one
      (scripts/profile_stability.py's reader); needs hipcc, no GPU
   A  on an MI355X, at the 300 x 75 x 75 duct (10.1 M tets) of profiles/stability.txt: ms of one B^T pass and one B pass on the
      same mesh in the same process -- warm-up, device-event timing, median and range of the repeats -- and their ratio beside
@@ -174,9 +174,9 @@ def main():
     rows = resource_usage()
     for r in rows:
         L.append("   %-40s %s" % (r["name"], {k: v for k, v in r.items() if k != "name"}))
-    scratch = max(r.get("ScratchSize", 0) for r in rows if "k_mass_apply_t" in r["name"])
-    L.append(f"   scratch of k_mass_apply_t: {scratch} bytes/lane" + ("" if scratch == 0 else "   NON-ZERO: the pass spills"))
-    L.append("   k_mass_apply_t holds grad z (12 values) beside the metric where k_mass_apply holds none: more VGPRs, one wave per SIMD fewer; "
+    scratch = max(r.get("ScratchSize", 0) for r in rows if "k_mass_pass<" in r["name"] and ", true, 1>" in r["name"])
+    L.append(f"   scratch of the transposed pass k_mass_pass<., true, 1>: {scratch} bytes/lane" + ("" if scratch == 0 else "   NON-ZERO: the pass spills"))
+    L.append("   the transposed pass holds grad z (12 values) beside the metric where the forward pass holds none: more VGPRs, one wave per SIMD fewer; "
              "capped at 128 VGPRs (__launch_bounds__(256, 4)) it spills 36 bytes/lane, so it is not capped")
     import torch
     gpu = torch.cuda.is_available()

@@ -589,52 +589,47 @@ int sns_set_dirichlet_values(sns_handle h, const double* bc_val_host) {
     return SNS_OK;
 }
 
-// the checks of the Arnoldi entry points (`who`: the name in front of the message; extend: k is an argument too)
-static int arnoldi_checked(const char* who, sns_ctx* h, policy::StabilityRequest request, const double* w, double shift, int k, int m,
-                           double breakdown_rel, double* V, double* H, int* m_done, int* total_ksp_its, int* reason,
-                           bool extend = false) {
-    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
-        set_error(std::string(who) + ": null handle or pointer");
-        return SNS_E_ARG;
-    }
-    SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_ARG));
-    SNS_TRY(refused(who, extend ? policy::check_arnoldi_extend_args({m, shift, breakdown_rel}, k)
-                                : policy::check_arnoldi_args({m, shift, breakdown_rel})));
-    SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_STATE));
-    return sns::stability_arnoldi(h, w, shift, request == policy::SREQ_ARNOLDI_LEFT, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
-}
-
-int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H, int* m_done,
-                          int* total_ksp_its, int* reason) {
-    return arnoldi_checked("sns_stability_arnoldi", h, policy::SREQ_ARNOLDI, w, shift, 0, m, breakdown_rel, V, H, m_done, total_ksp_its,
-                             reason);
-}
-
-int sns_stability_arnoldi_left(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,
-                               int* m_done, int* total_ksp_its, int* reason) {
-    return arnoldi_checked("sns_stability_arnoldi_left", h, policy::SREQ_ARNOLDI_LEFT, w, shift, 0, m, breakdown_rel, V, H, m_done,
-                             total_ksp_its, reason);
-}
-
-int sns_stability_arnoldi_extend(sns_handle h, const double* w, double shift, int k, int m, double breakdown_rel, int left, double* V,
-                                 double* H, int* m_done, int* total_ksp_its, int* reason) {
-    return arnoldi_checked("sns_stability_arnoldi_extend", h, left ? policy::SREQ_ARNOLDI_LEFT : policy::SREQ_ARNOLDI, w, shift, k, m,
-                             breakdown_rel, V, H, m_done, total_ksp_its, reason, true);
-}
-
-int sns_stability_arnoldi_shifted(sns_handle h, const double* w, double shift_re, double shift_im, double pc_shift, int k, int m,
-                                  double breakdown_rel, int left, double* V, double* H, int* m_done, int* total_ksp_its, int* reason) {
-    const char* who = "sns_stability_arnoldi_shifted";
+// the checks of the Arnoldi entry points and the run (`who`: the name in front of the message; args: the outcome of the
+// argument rule of the entry point, reported between the two halves of the state's rules; c: the shifted step's coefficient)
+// The verdict is formed by the caller before the pointers are looked at: an argument rule reads scalars and dereferences nothing
+static int arnoldi_checked(const char* who, sns_ctx* h, bool left, const policy::Verdict& args, const double* w, double shift, int k,
+                           int m, double breakdown_rel, double* V, double* H, int* m_done, int* total_ksp_its, int* reason,
+                           const double* c = nullptr) {
     if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
         set_error(std::string(who) + ": null handle or pointer");
         return SNS_E_ARG;
     }
     const policy::StabilityRequest request = left ? policy::SREQ_ARNOLDI_LEFT : policy::SREQ_ARNOLDI;
     SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_ARG));
-    SNS_TRY(refused(who, policy::check_shifted_args({m, k, shift_re, shift_im, pc_shift, breakdown_rel})));
+    SNS_TRY(refused(who, args));
     SNS_TRY(allows(h, who, policy::FAMILY_STABILITY, request, ROWS_STATE));
+    return sns::stability_arnoldi(h, w, shift, left, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason, c);
+}
+
+int sns_stability_arnoldi(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H, int* m_done,
+                          int* total_ksp_its, int* reason) {
+    return arnoldi_checked("sns_stability_arnoldi", h, false, policy::check_arnoldi_args({m, shift, breakdown_rel}), w, shift, 0, m,
+                           breakdown_rel, V, H, m_done, total_ksp_its, reason);
+}
+
+int sns_stability_arnoldi_left(sns_handle h, const double* w, double shift, int m, double breakdown_rel, double* V, double* H,
+                               int* m_done, int* total_ksp_its, int* reason) {
+    return arnoldi_checked("sns_stability_arnoldi_left", h, true, policy::check_arnoldi_args({m, shift, breakdown_rel}), w, shift, 0, m,
+                           breakdown_rel, V, H, m_done, total_ksp_its, reason);
+}
+
+int sns_stability_arnoldi_extend(sns_handle h, const double* w, double shift, int k, int m, double breakdown_rel, int left, double* V,
+                                 double* H, int* m_done, int* total_ksp_its, int* reason) {
+    return arnoldi_checked("sns_stability_arnoldi_extend", h, left != 0, policy::check_arnoldi_extend_args({m, shift, breakdown_rel}, k), w,
+                           shift, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason);
+}
+
+int sns_stability_arnoldi_shifted(sns_handle h, const double* w, double shift_re, double shift_im, double pc_shift, int k, int m,
+                                  double breakdown_rel, int left, double* V, double* H, int* m_done, int* total_ksp_its, int* reason) {
     const double c[2] = {shift_re - pc_shift, shift_im};   // J + s B = (J + pc_shift B) + c B
-    return sns::stability_arnoldi(h, w, pc_shift, left != 0, k, m, breakdown_rel, V, H, m_done, total_ksp_its, reason, c);
+    return arnoldi_checked("sns_stability_arnoldi_shifted", h, left != 0,
+                           policy::check_shifted_args({m, k, shift_re, shift_im, pc_shift, breakdown_rel}), w, pc_shift, k, m, breakdown_rel,
+                           V, H, m_done, total_ksp_its, reason, c);
 }
 
 // the checks of the two calls on the complex operator A + c B (`who`: the name in front of the message)

@@ -311,6 +311,9 @@ int op_residual(sns_ctx* h, double* x, const double* b, double* r);
 // whether the method left it there (else the caller applies the operator itself)
 int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm, bool zero_guess = false, double* ax = nullptr,
            bool* ax_done = nullptr);
+// ... and the frame of a solve: what opens one (`who`: the caller in "<who> before a matrix was assembled") and what closes it
+int solve_open(sns_ctx* h, const char* who);
+int solve_close(sns_ctx* h, int its);
 // csrc/sns_solve.hip: the solve drivers behind the entry points (which have checked the arguments) and their shared pieces.
 // ensure_hierarchy builds the lazy hierarchy (assembles_next: the caller assembles next, so an operator-based aggregation may
 // wait); solve_and_snap is krylov plus the exact Dirichlet data `val` under `mask` after a converged solve; give_back returns the
@@ -343,6 +346,9 @@ int error_indicator(sns_ctx* h, const double* w, const double* G, double* eta2, 
 // decomposition continued), and the in-place compression of its basis V[:, 0:n_out] <- V[:, 0:n_in] Q (Q on the host)
 int mass_apply(sns_ctx* h, const double* w, const double* x, double* y);
 int mass_apply_transpose(sns_ctx* h, const double* w, const double* z, double* y);
+// ... queued on the handle's stream: y = B x (left: B^T x), and for planar complex x, y the pair pass y += c B x
+void launch_mass(sns_ctx* h, bool left, const double* w, const double* x, double* y);
+void launch_mass_pair(sns_ctx* h, bool left, const double* w, double c_re, double c_im, const double* x, double* y);
 // c: null, or the complex coefficient (re, im) of the shifted step -- S = Re[(A + c B)^-1 B] with A the handle's matrix
 int arnoldi_run(sns_ctx* h, const double* w, bool left, int k0, int m, double breakdown_rel, double* V, double* H, int* m_done,
                 int* total_its, int* reason, const double* c = nullptr);
@@ -540,20 +546,31 @@ inline int fetch(sns_ctx* h, const double* src_dev, int count, double* out) {
 // Arnoldi process of the damping estimate (csrc/sns_damping.hip) and the one of the stability analysis (csrc/sns_stability.hip)
 // run twice per step.  coef[c0..c0+8) = the chunk's local sums of V^T w; then finish(), where the caller completes the sums over
 // the ranks and may queue further sums of the w it still sees; then w -= V coef.  nd entries per vector, g = the grid of the sums.
-template <class Finish>
+// CPLX: the same pass of the complex FGMRES (csrc/sns_shifted.hip) on planar complex vectors -- nd entries per part, ld the
+// distance of two columns --: V^H w by k_cdot8, 16 sums per chunk, the coefficients (re, im) interleaved.
+// basis_axpy is the second half on its own, w += sign * V coef: the pass ends with it, a solver's x += Z y is it.
+template <bool CPLX = false>
+inline void basis_axpy(sns_ctx* h, int64_t nd, int g, int nv, const double* V, int64_t ld, const double* coef, double sign, double* w) {
+    for (int c0 = 0; c0 < nv; c0 += 8) {
+        const int cn = std::min(8, nv - c0);
+        if constexpr (CPLX)
+            hipLaunchKernelGGL(k_caxpy8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld, ld, coef + 2 * c0, sign, w);
+        else
+            hipLaunchKernelGGL(k_multi_axpy8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld, ld, coef + c0, sign, w,
+                               (double*)nullptr);
+    }
+}
+
+template <bool CPLX = false, class Finish>
 inline int gram_schmidt_pass(sns_ctx* h, int64_t nd, int g, int nv, const double* V, int64_t ld, double* w, double* coef,
                              Finish&& finish) {
     for (int c0 = 0; c0 < nv; c0 += 8) {
         const int cn = std::min(8, nv - c0);
-        hipLaunchKernelGGL(k_multi_dot8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld, ld, w, h->partial);
-        reduce_local(h, g, 8, coef + c0);
+        hipLaunchKernelGGL(CPLX ? k_cdot8 : k_multi_dot8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld, ld, w, h->partial);
+        reduce_local(h, g, CPLX ? 16 : 8, coef + (CPLX ? 2 : 1) * c0);
     }
     SNS_TRY(finish());
-    for (int c0 = 0; c0 < nv; c0 += 8) {
-        const int cn = std::min(8, nv - c0);
-        hipLaunchKernelGGL(k_multi_axpy8, dim3(g), dim3(256), 0, h->stream, nd, cn, V + (size_t)c0 * ld, ld, coef + c0, -1.0, w,
-                           (double*)nullptr);
-    }
+    basis_axpy<CPLX>(h, nd, g, nv, V, ld, coef, -1.0, w);
     return SNS_OK;
 }
 

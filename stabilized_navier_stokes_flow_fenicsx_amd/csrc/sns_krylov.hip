@@ -331,7 +331,8 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
     const int S = m + 16;                 // stride of one coefficient block
     double* dh1 = h->d_h;                 // pass-1 coefficients [0, m+8)
     double* dh2 = h->d_h + S;             // pass-2 coefficients [0, m+8), then (w.w, w.w) at [m+8, m+10)
-    std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), gv(m + 1), y(m), hcol(2 * (m + 16));
+    policy::GivensLsq<double> lsq(m);
+    std::vector<double> hcol(2 * (m + 16));
     double bnorm, rn;
     SNS_TRY(norm2(h, b, &bnorm));
     const double tol = std::max(o.ksp_rtol * bnorm, o.ksp_atol);
@@ -345,10 +346,8 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
         if ((reason = policy::ksp_converged(rn, tol, o.ksp_atol))) break;
         if (its >= o.ksp_max_it) { reason = SNS_KSP_DIVERGED_ITS; break; }
         hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, nd, 1.0 / rn, r, V);
-        std::fill(gv.begin(), gv.end(), 0.0);
-        gv[0] = rn;
+        lsq.restart(rn);
         int j = 0;
-        double res = rn;
         for (; j < m && its < o.ksp_max_it; ++j) {
             double* vj = V + (size_t)j * ld;
             double* zj = Z + (size_t)j * ld;
@@ -369,10 +368,9 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
             }
             // one device->host transfer per iteration: h1[0..nv), h2[0..nv), w.w
             SNS_TRY(fetch(h, h->d_h, 2 * S, hcol.data()));
-            double* Hj = &H[(size_t)j * (m + 1)];             // column j
             double h2sq = 0.0;
             for (int k = 0; k < nv; ++k) {
-                Hj[k] = hcol[k] + hcol[S + k];
+                hcol[k] += hcol[S + k];                        // column j
                 h2sq += hcol[S + k] * hcol[S + k];
             }
             const double ww = hcol[S + (m + 8)];
@@ -380,38 +378,16 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
             double wn;
             if (!(wn2 > 1e-6 * ww)) SNS_TRY(norm2(h, w, &wn));   // heavy cancellation: measure it
             else wn = std::sqrt(wn2);
-            Hj[nv] = wn;
             if (wn > 0.0) hipLaunchKernelGGL(k_scale_copy, dim3(g), dim3(256), 0, h->stream, nd, 1.0 / wn, w, w);
-            for (int k = 0; k < j; ++k) {                      // previous rotations
-                const double t0 = cs[k] * Hj[k] + sn[k] * Hj[k + 1];
-                Hj[k + 1] = -sn[k] * Hj[k] + cs[k] * Hj[k + 1];
-                Hj[k] = t0;
-            }
-            const double den = std::hypot(Hj[j], Hj[j + 1]);
-            cs[j] = den > 0 ? Hj[j] / den : 1.0;
-            sn[j] = den > 0 ? Hj[j + 1] / den : 0.0;
-            Hj[j] = den;
-            Hj[j + 1] = 0.0;
-            gv[j + 1] = -sn[j] * gv[j];
-            gv[j] = cs[j] * gv[j];
-            res = std::fabs(gv[j + 1]);
+            const double res = lsq.push_column(j, hcol.data(), wn);
             ++its;
             if (o.monitor) std::printf("%3d KSP Residual norm %.12e\n", its, res);
             if (res <= tol || wn == 0.0 || !(res == res)) { ++j; break; }
         }
         // y = H^-1 g ; x += Z y
-        for (int k = j - 1; k >= 0; --k) {
-            double sacc = gv[k];
-            for (int q = k + 1; q < j; ++q) sacc -= H[(size_t)q * (m + 1) + k] * y[q];
-            y[k] = sacc / H[(size_t)k * (m + 1) + k];
-        }
-        HIP_TRY(hipMemcpyAsync(dh1, y.data(), j * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));             // y is a stack-lifetime host buffer
-        for (int c0 = 0; c0 < j; c0 += 8) {
-            const int cn = std::min(8, j - c0);
-            hipLaunchKernelGGL(k_multi_axpy8, dim3(g), dim3(256), 0, h->stream, nd, cn, Z + (size_t)c0 * ld, ld,
-                               dh1 + c0, 1.0, x, (double*)nullptr);
-        }
+        HIP_TRY(hipMemcpyAsync(dh1, lsq.solve(j).data(), j * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));             // (y is rewritten at the next restart)
+        basis_axpy(h, nd, g, j, Z, ld, dh1, 1.0, x);
         SNS_TRY(op_residual(h, x, b, r));
         SNS_TRY(norm2(h, r, &rn));
     }
@@ -422,18 +398,38 @@ int fgmres(sns_ctx* h, const double* b, double* x, int* its_out, int* reason_out
 }
 
 
-int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm, bool zero_guess, double* ax, bool* ax_done) {
-    bool ax_unused = false;
-    if (!ax_done) ax_done = &ax_unused;
-    *ax_done = false;
-    if (!h->has_matrix) { set_error("krylov_solve before a matrix was assembled"); return SNS_E_STATE; }
+// The frame of a linear solve, for krylov() and for cfgmres (csrc/sns_shifted.hip).  solve_open (`who` names the caller in the
+// refusal): a matrix, the preconditioner set up if that is due, the hand-off state and the counters of a new solve, the clock
+// started.  solve_close: the clock stopped and read behind a synchronise, the iterations and the kernel times booked
+int solve_open(sns_ctx* h, const char* who) {
+    if (!h->has_matrix) { set_error(std::string(who) + " before a matrix was assembled"); return SNS_E_STATE; }
     if (!h->pc_ready && h->opt.pc_type != SNS_PC_NONE) SNS_TRY(pc_setup(h));
     int stale = -1;
     SNS_TRY(handoff_legal(h->handoff.begin_solve(&stale), "a solve begins with a carried put nobody took", stale));
     h->pc_pending = {};
     h->ctr_host_syncs = h->ctr_allreduce = h->ctr_exchange = 0;
-    const policy::StepPlan plan = step_plan(h, zero_guess);
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    return SNS_OK;
+}
+
+int solve_close(sns_ctx* h, int its) {
+    HIP_TRY(hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    h->tm.krylov_ms += ms;
+    h->tm.ksp_its += its;
+    time_collect(h);
+    HIP_TRY(hipGetLastError());
+    return SNS_OK;
+}
+
+int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double* rnorm, bool zero_guess, double* ax, bool* ax_done) {
+    bool ax_unused = false;
+    if (!ax_done) ax_done = &ax_unused;
+    *ax_done = false;
+    SNS_TRY(solve_open(h, "krylov_solve"));
+    const policy::StepPlan plan = step_plan(h, zero_guess);
     // A solve that BREAKS DOWN (or produces NaN/Inf) under the AMG preconditioner is retried ONCE, from the same initial
     // guess, with every level's block-Jacobi damping backed off (damping_back_off, csrc/sns_damping.hip: policy::RETRY_FACTOR, no
     // retry at or below policy::RETRY_FLOOR; opt.amg_retry_damping, default on): the damping
@@ -477,15 +473,7 @@ int krylov(sns_ctx* h, const double* b, double* x, int* its, int* reason, double
     *its = its_total;
     h->last_ctr[0] = h->ctr_host_syncs; h->last_ctr[1] = h->ctr_allreduce; h->last_ctr[2] = h->ctr_exchange;
     SNS_TRY(halo_exchange(h, x));                          // leave the solution's ghost tail current
-    HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->tm.krylov_ms += ms;
-    h->tm.ksp_its += *its;
-    time_collect(h);
-    HIP_TRY(hipGetLastError());
-    return SNS_OK;
+    return solve_close(h, *its);
 }
 
 

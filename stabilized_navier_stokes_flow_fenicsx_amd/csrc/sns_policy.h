@@ -9,11 +9,14 @@
 // a new one (OperatorKey, tests/operator_key_main.cpp), the damping of a
 // level's smoother (LevelDamping, tests/damping_policy_main.cpp), what a kernel of a solve hands to a later one (Handoff,
 // tests/handoff_main.cpp), what a solve and a set-up may leave out of their fixed cost (plan_step, tests/step_plan_main.cpp), when
-// the Krylov and Newton loops stop and which step the line search tries next (LineSearch, tests/newton_policy_main.cpp).
+// the Krylov and Newton loops stop and which step the line search tries next (LineSearch, tests/newton_policy_main.cpp), the
+// Givens least-squares problem of the two FGMRES loops (GivensLsq, tests/givens_lsq_main.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "sns.h"
@@ -862,6 +865,67 @@ struct LineSearch {
    private:
     double f, slope, lam = 1.0, lamprev = 1.0, gprev = 0.0;
     int trials = 0;
+};
+
+// ---- the least-squares problem of FGMRES (csrc/sns_krylov.hip: fgmres, T = double; csrc/sns_shifted.hip: cfgmres, T =
+// std::complex<double>; tests/givens_lsq_main.cpp) ------------------------------------------------------------------------------------
+// min |beta e1 - H y| over a cycle of at most m columns by Givens rotations [cs, sn; -conj(sn), cs] with cs real.  restart(beta)
+// opens a cycle; push_column(j, h, wn) takes column j -- its j + 1 Gram-Schmidt coefficients and the norm wn >= 0 of what was
+// left --, applies the earlier rotations, forms the new one and returns the residual estimate |g[j + 1]|; solve(j) is the
+// minimiser over the first j columns.  H is stored by columns of m + 1.  The two types differ in the new rotation alone, and
+// each keeps its own formula: the real one is not the complex one at zero imaginary part, the two do not round alike.
+// No device access, no handle.
+inline double givens_conj(double v) { return v; }
+inline std::complex<double> givens_conj(const std::complex<double>& v) { return std::conj(v); }
+template <class T>
+struct GivensLsq {
+    int m;
+    std::vector<T> H, sn, g, y;
+    std::vector<double> cs;
+    explicit GivensLsq(int m_) : m(m_), H((size_t)(m_ + 1) * m_, T(0.0)), sn(m_), g(m_ + 1), y(m_), cs(m_) {}
+    void restart(double beta) {
+        std::fill(g.begin(), g.end(), T(0.0));
+        g[0] = beta;
+    }
+    double push_column(int j, const T* h, double wn) {
+        T* Hj = &H[(size_t)j * (m + 1)];
+        for (int k = 0; k <= j; ++k) Hj[k] = h[k];
+        Hj[j + 1] = wn;
+        for (int k = 0; k < j; ++k) {                      // previous rotations
+            const T t0 = cs[k] * Hj[k] + sn[k] * Hj[k + 1];
+            Hj[k + 1] = -givens_conj(sn[k]) * Hj[k] + cs[k] * Hj[k + 1];
+            Hj[k] = t0;
+        }
+        if constexpr (std::is_same<T, double>::value) {
+            const double den = std::hypot(Hj[j], wn);
+            cs[j] = den > 0 ? Hj[j] / den : 1.0;
+            sn[j] = den > 0 ? wn / den : 0.0;
+            Hj[j] = den;
+        } else {
+            const double aa = std::abs(Hj[j]), den = std::hypot(aa, wn);
+            if (den > 0.0 && aa > 0.0) {
+                cs[j] = aa / den;
+                sn[j] = (Hj[j] / aa) * (wn / den);
+                Hj[j] = Hj[j] * (den / aa);
+            } else {
+                cs[j] = den > 0.0 ? 0.0 : 1.0;
+                sn[j] = den > 0.0 ? 1.0 : 0.0;
+                Hj[j] = wn;
+            }
+        }
+        Hj[j + 1] = 0.0;
+        g[j + 1] = -givens_conj(sn[j]) * g[j];
+        g[j] = cs[j] * g[j];
+        return std::abs(g[j + 1]);
+    }
+    const std::vector<T>& solve(int j) {                   // y = H^-1 g over the leading j columns
+        for (int k = j - 1; k >= 0; --k) {
+            T sacc = g[k];
+            for (int q = k + 1; q < j; ++q) sacc -= H[(size_t)q * (m + 1) + k] * y[q];
+            y[k] = sacc / H[(size_t)k * (m + 1) + k];
+        }
+        return y;
+    }
 };
 
 }  // namespace policy

@@ -428,6 +428,28 @@ class FlowProblem:
         self.bc_val = val
         self.g_dev = torch.from_numpy(self.bc_val).to(self.device)
 
+    def _arnoldi_basis(self, m, start):
+        """``(m, V, H)`` of a fresh Arnoldi process: V zero but for row 0, the start vector (by default cos(1 + 0.37 i) over the
+        dofs), H zero.  (m outside [2, 64]: the library refuses.)"""
+        m = int(m)
+        V = torch.zeros(max(m, 0) + 1, self.ndof, dtype=torch.float64, device=self.device)
+        if start is None:
+            V[0] = torch.cos(1.0 + 0.37 * torch.arange(self.ndof, dtype=torch.float64, device=self.device))
+        else:
+            V[0] = self._vec(start)
+        return m, V, np.zeros((max(m, 0) + 1, max(m, 0)))
+
+    def _check_basis(self, V, H, who: str) -> int:
+        """The ``V`` and ``H`` a caller hands back to the method ``who`` are the ones it was given; returns m."""
+        if not (isinstance(H, np.ndarray) and H.dtype == np.float64 and H.ndim == 2 and H.flags.c_contiguous and
+                H.shape[0] == H.shape[1] + 1):
+            raise ValueError(f"H must be the C-contiguous float64 (m + 1, m) array of {who}")
+        m = H.shape[1]
+        if not (isinstance(V, torch.Tensor) and V.dtype == torch.float64 and V.shape == (m + 1, self.ndof) and V.is_contiguous()
+                and V.device.type == "cuda"):
+            raise ValueError(f"V must be the contiguous float64 (m + 1, ndof) device tensor of {who}")
+        return m
+
     def stability_arnoldi(self, w, shift: float = 0.0, m: int = 64, start=None, breakdown_rel: float = 1e-6, side: str = "right"):
         """``m`` steps of shift-invert Arnoldi on (J + shift B)^-1 B at the steady state ``w`` (sns_stability_arnoldi), with
         the problem's ksp / pc options for the inner solves.  Returns ``(V, H, ArnoldiResult)``: V a device tensor
@@ -439,13 +461,7 @@ class FlowProblem:
             raise ValueError("side must be 'right' or 'left'")
         run = self.lib.sns_stability_arnoldi if side == "right" else self.lib.sns_stability_arnoldi_left
         w = self._vec(w)
-        m = int(m)
-        V = torch.zeros(max(m, 0) + 1, self.ndof, dtype=torch.float64, device=self.device)   # (m outside [2, 64]: the library refuses)
-        if start is None:
-            V[0] = torch.cos(1.0 + 0.37 * torch.arange(self.ndof, dtype=torch.float64, device=self.device))
-        else:
-            V[0] = self._vec(start)
-        H = np.zeros((max(m, 0) + 1, max(m, 0)))
+        m, V, H = self._arnoldi_basis(m, start)
         done, its, reason = C.c_int(), C.c_int(), C.c_int()
         check(run(self.h, _ptr(w), float(shift), m, float(breakdown_rel), _ptr(V), H.ctypes.data, C.byref(done), C.byref(its),
                   C.byref(reason)))
@@ -461,13 +477,7 @@ class FlowProblem:
         (m_done = k + the steps completed; ksp_its of this call).  The handle ends as after ``stability_arnoldi``."""
         if side not in ("right", "left"):
             raise ValueError("side must be 'right' or 'left'")
-        if not (isinstance(H, np.ndarray) and H.dtype == np.float64 and H.ndim == 2 and H.flags.c_contiguous and
-                H.shape[0] == H.shape[1] + 1):
-            raise ValueError("H must be the C-contiguous float64 (m + 1, m) array of stability_arnoldi")
-        m = H.shape[1]
-        if not (isinstance(V, torch.Tensor) and V.dtype == torch.float64 and V.shape == (m + 1, self.ndof) and V.is_contiguous()
-                and V.device.type == "cuda"):
-            raise ValueError("V must be the contiguous float64 (m + 1, ndof) device tensor of stability_arnoldi")
+        m = self._check_basis(V, H, "stability_arnoldi")
         w = self._vec(w)
         done, its, reason = C.c_int(), C.c_int(), C.c_int()
         check(self.lib.sns_stability_arnoldi_extend(self.h, _ptr(w), float(shift), int(k), m, float(breakdown_rel), int(side == "left"),
@@ -545,21 +555,9 @@ class FlowProblem:
         pc_shift = abs(s) if pc_shift is None else float(pc_shift)
         w = self._vec(w)
         if V is None:
-            m = int(m)
-            V = torch.zeros(max(m, 0) + 1, self.ndof, dtype=torch.float64, device=self.device)
-            if start is None:
-                V[0] = torch.cos(1.0 + 0.37 * torch.arange(self.ndof, dtype=torch.float64, device=self.device))
-            else:
-                V[0] = self._vec(start)
-            H = np.zeros((max(m, 0) + 1, max(m, 0)))
+            m, V, H = self._arnoldi_basis(m, start)
         else:
-            if not (isinstance(H, np.ndarray) and H.dtype == np.float64 and H.ndim == 2 and H.flags.c_contiguous and
-                    H.shape[0] == H.shape[1] + 1):
-                raise ValueError("H must be the C-contiguous float64 (m + 1, m) array of stability_arnoldi_shifted")
-            m = H.shape[1]
-            if not (isinstance(V, torch.Tensor) and V.dtype == torch.float64 and V.shape == (m + 1, self.ndof) and V.is_contiguous()
-                    and V.device.type == "cuda"):
-                raise ValueError("V must be the contiguous float64 (m + 1, ndof) device tensor of stability_arnoldi_shifted")
+            m = self._check_basis(V, H, "stability_arnoldi_shifted")
         done, its, reason = C.c_int(), C.c_int(), C.c_int()
         check(self.lib.sns_stability_arnoldi_shifted(self.h, _ptr(w), s.real, s.imag, pc_shift, int(k), m, float(breakdown_rel),
                                                      int(side == "left"), _ptr(V), H.ctypes.data, C.byref(done), C.byref(its),
@@ -1554,11 +1552,12 @@ def default_keep(m: int, n_modes: int) -> int:
 
 
 def _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, side, breakdown_rel, pc_shift=None):
-    """One side of ``linear_stability(max_restarts > 0)``: ``stability_arnoldi``, then estimates, truncate, ``basis_rotate``,
-    ``stability_arnoldi_extend`` until the ``n_modes`` Ritz pairs of largest |theta| (nearest the shift) all have an estimate
-    <= tol, ``max_restarts`` is reached, the space is invariant (reason 2) or an inner solve failed (reason < 0).  Returns
-    (V, H, ArnoldiResult with the Krylov iterations of all cycles, restarts).  ``pc_shift`` given (a complex ``shift``): the
-    same loop over ``stability_arnoldi_shifted``, with the true residuals of ``shifted_eigenpairs`` as the estimates."""
+    """One side of ``linear_stability`` (``max_restarts = 0``: the first call alone): ``stability_arnoldi``, then estimates,
+    truncate, ``basis_rotate``, ``stability_arnoldi_extend`` until the ``n_modes`` Ritz pairs of largest |theta| (nearest the
+    shift) all have an estimate <= tol, ``max_restarts`` is reached, the space is invariant (reason 2) or an inner solve failed
+    (reason < 0).  Returns (V, H, ArnoldiResult with the Krylov iterations of all cycles, restarts).  ``pc_shift`` given (a
+    complex ``shift``): the same loop over ``stability_arnoldi_shifted``, with the true residuals of ``shifted_eigenpairs`` as
+    the estimates."""
     shifted = pc_shift is not None
     if shifted:
         V, H, res = problem.stability_arnoldi_shifted(w, shift, pc_shift, m=m, side=side, breakdown_rel=breakdown_rel)
@@ -1710,23 +1709,12 @@ def linear_stability(problem: FlowProblem, w, n_modes: int = 6, shift: float = 0
     problem.set_options(ksp_rtol=float(ksp_rtol))
     restarts = restartsL = 0
     try:
-        if cx and max_restarts > 0:
-            V, H, res, restarts = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "right", breakdown_rel, pc_shift)
-            if left:
-                VL, HL, resL, restartsL = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "left", breakdown_rel,
-                                                             pc_shift)
-        elif cx:
-            V, H, res = problem.stability_arnoldi_shifted(w, shift, pc_shift, m=m)
-            if left:
-                VL, HL, resL = problem.stability_arnoldi_shifted(w, shift, pc_shift, m=m, side="left")
-        elif max_restarts > 0:
-            V, H, res, restarts = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "right", breakdown_rel)
-            if left:
-                VL, HL, resL, restartsL = _restarted_arnoldi(problem, w, shift, m, n_modes, tol, max_restarts, keep, "left", breakdown_rel)
-        else:
-            V, H, res = problem.stability_arnoldi(w, shift=shift, m=m)
-            if left:
-                VL, HL, resL = problem.stability_arnoldi(w, shift=shift, m=m, side="left")
+        # (without restarts the loop of _restarted_arnoldi does not run, and breakdown_rel is the methods' default)
+        cycle = dict(shift=shift, m=m, n_modes=n_modes, tol=tol, max_restarts=max_restarts, keep=keep, pc_shift=pc_shift,
+                     breakdown_rel=breakdown_rel if max_restarts > 0 else 1e-6)
+        V, H, res, restarts = _restarted_arnoldi(problem, w, side="right", **cycle)
+        if left:
+            VL, HL, resL, restartsL = _restarted_arnoldi(problem, w, side="left", **cycle)
     finally:
         problem.set_options(ksp_rtol=old)
     if cx:

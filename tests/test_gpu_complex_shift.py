@@ -1,4 +1,4 @@
-"""The stability analysis with a complex or negative shift on the GPU (sns_shifted_apply / k_mass_axpy_pair, sns_shifted_solve /
+"""The stability analysis with a complex or negative shift on the GPU (sns_shifted_apply / k_mass_pass<., ., 2>, sns_shifted_solve /
 cfgmres with k_cdot8 and k_caxpy8, sns_stability_arnoldi_shifted; solver.linear_stability(shift=complex),
 solver.harmonic_response), everything through the C-ABI.
 
@@ -120,6 +120,41 @@ def test_shifted_apply_against_the_oracle(variant, transpose):
     if transpose:
         assert np.array_equal(yn[3::4], an[3::4])
     P.close()
+
+
+def _ulps(a, b):
+    """The largest difference of two float64 tensors in units of the last place of b, and the rows that differ."""
+    a, b = a.cpu().numpy(), b.cpu().numpy()
+    rows = np.nonzero(a != b)[0]
+    return (float((np.abs(a - b)[rows] / np.spacing(np.abs(b[rows]))).max()) if len(rows) else 0.0), rows
+
+
+@pytest.mark.parametrize("transpose", [False, True])
+@pytest.mark.parametrize("corrected", [0, 1])
+def test_the_pair_pass_is_the_single_vector_pass(corrected, transpose):
+    """The pair pass (NP = 2 of k_mass_pass) is the single-vector pass (NP = 1), exactly: for a real x the real part of
+    A x + 1 B x is spmv(x) + mass(w, x) formed with one addition -- the epilogue is 1 t_re - 0 t_im on a zero imaginary sum --,
+    and the imaginary part of A x + i B x is mass(w, x); every row, the constrained rows and (transposed) the pressure rows
+    included.  Bit for bit: the two instantiations run the same statements per part in the same order."""
+    c = SO.case("duct633")
+    rng = np.random.default_rng(57)
+    x = _dev(rng.standard_normal(len(c.w)))
+    P = _problem(c, corrected_convection=corrected)
+    wd = _dev(c.w)
+    _hold(P, c, wd, abs(SHIFT))
+    if transpose:
+        P.transpose_operator()
+    mass = P.mass_apply_transpose if transpose else P.mass_apply
+    ax, bx = P.spmv(x).clone(), mass(wd, x).clone()
+    y1 = P.shifted_apply(wd, 1.0, x, transpose=transpose)
+    yi = P.shifted_apply(wd, 1j, x, transpose=transpose)
+    P.close()
+    for what, got, want in (("Re(A x + B x) against spmv + mass", y1.real, ax + bx), ("Im(A x + i B x) against mass", yi.imag, bx)):
+        worst, rows = _ulps(got, want)
+        print("corrected", corrected, "transpose", transpose, what, ": largest difference", worst, "ulp on", len(rows), "rows", rows[:16])
+    assert torch.equal(y1.real, ax + bx)
+    assert torch.equal(yi.imag, bx)
+    assert torch.equal(y1.imag, torch.zeros_like(bx)) and torch.equal(yi.real, ax)
 
 
 # ---- 2. the complex solve ----------------------------------------------------------------------------------------------------------

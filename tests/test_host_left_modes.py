@@ -1,5 +1,5 @@
 """CPU checks behind the left stability modes (sns_mass_apply_transpose, sns_stability_arnoldi_left, solver.pair_left_right):
-the closed forms of B^T z that k_mass_apply_t implements against the transpose of the oracle's B = J(1) - J(0), which pins the
+the closed forms of B^T z that the transposed mass pass (mass_cell_t of csrc/sns_stability.hip) implements against the transpose of the oracle's B = J(1) - J(0), which pins the
 kernel's formula before any GPU run; the left process of the oracle against the dense spectrum; biorthogonality; the
 perturbation formula for d lam / d Re against the central difference of dense spectra at re-converged states; the pairing rule;
 the request rules of the two new kinds through their stand-alone main; the binding of the entry points.  The bounds are
