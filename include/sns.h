@@ -485,6 +485,26 @@ SNS_API int sns_error_indicator(sns_handle h, const double* w_dev, const double*
  *   communicator attached, a viscosity law, a time term, a body force (J then depends on f through dM/dw(w, -f), a second
  *   contraction that is not built) or a backflow coefficient (sns_set_boundary_flow: quadratic in u, its Hessian is not built)
  *   set.  A boundary traction alone (constant in w) and a viscosity field are allowed.
+ * sns_jacobian_shape_gradient: the eigenvalue shape pass, the mesh derivative of the same contraction.  For real dof vectors x, z
+ *   and real scalars c_jac, c_mass,
+ *       gX[3 k + j] = d/dX[k][j] [ z~^T ( c_jac J0(w; X) + c_mass B(w; X) ) x~ ],   k = local node, j = 0..2,
+ *   J0 = dR_raw/dw the steady Jacobian of the raw form (no lifting, no Dirichlet rows; with x~ and z~ masked it is the assembled
+ *   J on the free dofs), B the operator above, x~ and z~ as for sns_jacobian_state_gradient.  Held fixed: w, x~, z~, the mask
+ *   and the Dirichlet values AT THE NODES, nu or the per-cell viscosity field, the form variant.  Nothing drops out here: the
+ *   viscous and pressure terms are linear in w but carry grad phi_a and |det J|.  gX_dev (3*n_local doubles) is overwritten;
+ *   nodes of no cell get 0; an empty mesh writes zeros.  With a left and a right mode of lambda the explicit part of
+ *   d lambda / dX is -(S_J(z, x) + lambda S_B(z, x)) / (z^T B x), four real pairs of passes with (c_jac, c_mass) = (1, Re lambda)
+ *   and (0, Im lambda); the base-flow path adds -mu . dF/dX with A^T mu = grad_w lambda (solver.py:
+ *   eigenvalue_shape_sensitivity).  One lane per tet differentiates the cell's scalar of the Hessian pass in its 12 vertex
+ *   coordinates by hand, tangent along x then reverse mode through K = J^-1, G and |det J|; 16 values per tet go to the
+ *   handle's element scratch -- after the call the Fe array of sns_get_element_scratch / SNS_EXPORT_FE holds Ge [n_cells][a][4]
+ *   = the cell's gradient with respect to its vertex a, slot 3 zero, as after sns_residual_shape_gradient -- and are summed per
+ *   node in the fixed order of the node -> cell lists: no atomics, bitwise reproducible, and doubling both coefficients doubles
+ *   every bit.  Nothing of the handle besides the element scratch is written.  Errors exactly as sns_jacobian_state_gradient
+ *   (the same request rows): SNS_E_ARG for a null handle / pointer, a 2-D handle, a coefficient that is not finite;
+ *   SNS_E_STATE, the handle untouched, with a communicator attached, a viscosity law, a time term, a body force or a backflow
+ *   coefficient set (their mesh derivatives inside the contraction are not built); a traction alone and a viscosity field are
+ *   allowed (the facet terms do not enter J0's cell part; a traction is constant in w).
  * Thick restart (Stewart's Krylov-Schur) of the process above, for meshes on which (m + 1) basis vectors at m = 64 do not fit
  *   or modes that 64 steps do not reach.  One restart is: the ordered real Schur form H[:m, :m] = Z T Z^T on the host with the
  *   `keep` Ritz values of largest modulus (the eigenvalues nearest the shift) leading (solver.py: krylov_schur_truncate; this
@@ -542,6 +562,8 @@ SNS_API int sns_stability_arnoldi_left(sns_handle h, const double* w_dev, double
                                        double* H_host /* (m+1) x m, row major */, int* m_done, int* total_ksp_its, int* reason);
 SNS_API int sns_jacobian_state_gradient(sns_handle h, const double* w_dev, const double* x_dev, const double* z_dev,
                                         double c_jac, double c_mass, double* g_dev);
+SNS_API int sns_jacobian_shape_gradient(sns_handle h, const double* w_dev, const double* x_dev, const double* z_dev,
+                                        double c_jac, double c_mass, double* gX_dev /* 3*n_local */);
 SNS_API int sns_stability_arnoldi_extend(sns_handle h, const double* w_dev, double shift, int k, int m, double breakdown_rel,
                                          int left, double* V_dev /* (m+1) * 4*n_local; columns 0 .. k on entry */,
                                          double* H_host /* (m+1) x m, row major; the leading (k+1) x k block on entry */,

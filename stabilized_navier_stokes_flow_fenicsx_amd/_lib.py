@@ -121,6 +121,7 @@ _SIGNATURES = [
     ("sns_stability_arnoldi_left", C.c_int, [_H, _P, C.c_double, C.c_int, C.c_double, _P, _P, C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("sns_jacobian_state_gradient", C.c_int, [_H, _P, _P, _P, C.c_double, C.c_double, _P]),
+    ("sns_jacobian_shape_gradient", C.c_int, [_H, _P, _P, _P, C.c_double, C.c_double, _P]),
     ("sns_stability_arnoldi_extend", C.c_int, [_H, _P, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _P, _P, C.POINTER(C.c_int),
                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("sns_basis_rotate", C.c_int, [_H, C.c_int, C.c_int, _P, _P]),

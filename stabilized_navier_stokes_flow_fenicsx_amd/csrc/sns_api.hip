@@ -555,6 +555,16 @@ int sns_jacobian_state_gradient(sns_handle h, const double* w, const double* x, 
     return jacobian_state_gradient(h, w, x, z, c_jac, c_mass, g);
 }
 
+int sns_jacobian_shape_gradient(sns_handle h, const double* w, const double* x, const double* z, double c_jac, double c_mass,
+                                double* gX) {
+    const char* who = "sns_jacobian_shape_gradient";
+    if (!h || !w || !x || !z || !gX) { set_error("sns_jacobian_shape_gradient: null handle or pointer"); return SNS_E_ARG; }
+    SNS_TRY(allows(h, who, policy::FAMILY_STATE_GRADIENT, policy::GREQ_STATE_GRADIENT, ROWS_ARG));
+    SNS_TRY(refused(who, policy::check_state_gradient_args(c_jac, c_mass)));
+    SNS_TRY(allows(h, who, policy::FAMILY_STATE_GRADIENT, policy::GREQ_STATE_GRADIENT, ROWS_STATE));
+    return jacobian_shape_gradient(h, w, x, z, c_jac, c_mass, gX);
+}
+
 int sns_raw_jacobian_apply(sns_handle h, int form, const double* w, const double* x, int transposed, double* y) {
     const char* who = "sns_raw_jacobian_apply";
     if (!h || !w || !x || !y) { set_error("sns_raw_jacobian_apply: null handle or pointer"); return SNS_E_ARG; }

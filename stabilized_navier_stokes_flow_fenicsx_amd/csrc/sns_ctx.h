@@ -369,6 +369,7 @@ int shifted_solve(sns_ctx* h, const double* w, double c_re, double c_im, bool le
                   double* rnorm);
 // csrc/sns_hessian.hip: g = grad_w [ z~^T (c_jac J(w) + c_mass B(w)) x~ ] by one element pass (uses the element scratch Fe)
 int jacobian_state_gradient(sns_ctx* h, const double* w, const double* x, const double* z, double c_jac, double c_mass, double* g);
+int jacobian_shape_gradient(sns_ctx* h, const double* w, const double* x, const double* z, double c_jac, double c_mass, double* gX);
 // csrc/sns_scalar.hip: the four-species transport operator into the fine level's vals and its right-hand side (synchronises)
 int scalar_system(sns_ctx* h, const double* w, const double kappa[4], double sigma, double theta, const double* src,
                   const uint8_t* cmask, const double* cval, double* rhs);

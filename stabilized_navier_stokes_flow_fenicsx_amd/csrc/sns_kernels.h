@@ -136,6 +136,9 @@ __global__ void k_element_viscosity(int64_t n_tets, const int32_t* tets, const d
                                     ViscosityLaw vl, double* nu_e, double* gamma_dot);
 __global__ void k_residual_tri(int64_t n_tris, const int32_t* tets, const double* pts, const double* w, double nu,
                                double* Fe);
+// csrc/sns_shape.hip: gX[3 i + j] <- sum over the cells of node i of Ge[16 t + 4 a + j] in list order (the shape gradient's and
+// the eigenvalue shape pass's gather)
+__global__ void k_gather_shape(int32_t n_rows, const int64_t* nt_ptr, const int32_t* nt_idx, const double* Ge, double* gX);
 __global__ void k_bc_residual(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, const double* w, double* F);
 __global__ void k_snap_bc(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, double rel_tol, double* w);
 __global__ void k_count_bc_violations(int64_t ndof, const uint8_t* bc_mask, const double* bc_val, const double* w,

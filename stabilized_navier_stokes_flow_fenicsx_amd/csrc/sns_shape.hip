@@ -379,7 +379,8 @@ __global__ __launch_bounds__(256) void k_shape_tri(int64_t n_tris, const int32_t
 }
 
 // gX[3 i + j] <- sum over the cells of node i of Ge[16 t + 4 a + j], in list order (8 ids, then their 8 entries, as
-// k_gather_residual); lane (i, j), the lanes j = 3 idle
+// k_gather_residual); lane (i, j), the lanes j = 3 idle.  Declared in sns_kernels.h: the eigenvalue shape pass
+// (csrc/sns_eigshape.hip) stages its cells in the same layout and launches this kernel too
 __global__ __launch_bounds__(256) void k_gather_shape(int32_t n_rows, const int64_t* __restrict__ nt_ptr,
                                                       const int32_t* __restrict__ nt_idx, const double* __restrict__ Ge,
                                                       double* __restrict__ gX) {

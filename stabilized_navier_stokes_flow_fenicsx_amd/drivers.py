@@ -602,6 +602,7 @@ def _stability(P, w):
     from .solver import SnsError, linear_stability, print_stability
     sens = os.environ.get("SNS_STABILITY_SENSITIVITY", "0") == "1"
     forcing = os.environ.get("SNS_STABILITY_FORCING", "0") == "1"
+    shape = os.environ.get("SNS_STABILITY_SHAPE", "0") == "1"
     restart = {}
     rspec = os.environ.get("SNS_STABILITY_RESTARTS", "")
     if rspec:
@@ -612,7 +613,7 @@ def _stability(P, w):
         if len(rparts) > 2:
             restart["keep"] = int(rparts[2])
     try:
-        res = (linear_stability(P, w, n_modes=n_modes, shift=shift, left=True, **restart) if sens or forcing
+        res = (linear_stability(P, w, n_modes=n_modes, shift=shift, left=True, **restart) if sens or forcing or shape
                else linear_stability(P, w, n_modes=n_modes, shift=shift, **restart))
     except SnsError as e:                                 # (a viscosity law, a 2-D problem: the library says which)
         if _rank() == 0:
@@ -620,12 +621,14 @@ def _stability(P, w):
         return None
     print_stability(res, _rank())
     if restart and _rank() == 0:
-        print(f"Stability restarts: right {res.restarts}" + (f", left {res.left_restarts}" if sens or forcing else "") +
+        print(f"Stability restarts: right {res.restarts}" + (f", left {res.left_restarts}" if sens or forcing or shape else "") +
               f" of at most {restart['max_restarts']} (reason {res.reason}, m_done {res.m_done})", flush=True)
     if sens:
         _stability_sensitivity(P, w, res)
     if forcing:
         _stability_forcing(P, w, res)
+    if shape:
+        _stability_shape(P, w, res)
     return res
 
 
@@ -685,11 +688,48 @@ def _stability_forcing(P, w, res):
               f"at node {top}, x = ({x[0]:.6g}, {x[1]:.6g}, {x[2]:.6g})", flush=True)
 
 
+def _stability_shape(P, w, res):
+    """SNS_STABILITY_SHAPE=1 beside SNS_STABILITY: for the leading converged mode that has a left partner, the sensitivity of
+    its eigenvalue to every node coordinate (``solver.eigenvalue_shape_sensitivity``) as ``res.shape_sensitivity`` (numpy
+    complex, n_nodes x 3: the real part moves the growth rate, the imaginary part the frequency), which the script writes as
+    ...GrowthRateShapeSensitivity and ...FrequencyShapeSensitivity fields beside the ...Wavemaker field, and one printed line:
+    the boundary node and position of the largest |Re d lambda / dX| (where to reshape the wall; interior components are
+    mesh-motion terms of the discrete problem)."""
+    from .solver import SnsError, eigenvalue_shape_sensitivity
+    res.shape_sensitivity = None
+    lead = [k for k, ok in enumerate(res.left_converged) if ok]
+    if not lead:
+        if _rank() == 0:
+            print("SNS_STABILITY_SHAPE: no converged mode with a converged left partner; skipped", flush=True)
+        return
+    k = lead[0]
+    try:
+        g = eigenvalue_shape_sensitivity(P, w, res, k)
+    except (SnsError, RuntimeError) as e:                 # (a time term, a body force, a traction: the library says which)
+        if _rank() == 0:
+            print(f"SNS_STABILITY_SHAPE: skipped ({e})", flush=True)
+        return
+    res.shape_sensitivity = g.cpu().numpy()
+    if _rank() == 0:
+        mag = np.linalg.norm(res.shape_sensitivity.real, axis=1)
+        facets = np.asarray(P.mesh.facets)
+        bnd = np.unique(facets) if facets.size else np.arange(len(mag))
+        top = int(bnd[mag[bnd].argmax()])
+        x = np.asarray(P.mesh.points)[top]
+        lam = res.eigenvalues[k]
+        print(f"Stability shape sensitivity: lambda = {lam.real:+.6e} {lam.imag:+.6e}i  max |Re dlambda/dX| on the boundary = "
+              f"{mag[top]:.6e} at node {top}, x = ({x[0]:.6g}, {x[1]:.6g}, {x[2]:.6g})", flush=True)
+
+
 def _write_wavemaker(res, msh, path_noext):
     if res is not None and getattr(res, "wavemaker", None) is not None and _rank() == 0:
         write_xdmf(path_noext, msh, "Wavemaker", res.wavemaker)
     if res is not None and getattr(res, "forcing_sensitivity", None) is not None and _rank() == 0:
         for name, part in (("GrowthRateForcingSensitivity", res.forcing_sensitivity.real), ("FrequencyForcingSensitivity", res.forcing_sensitivity.imag)):
+            head, base = os.path.split(path_noext)
+            write_xdmf(os.path.join(head, base.replace("Wavemaker", name)), msh, name, np.ascontiguousarray(part))
+    if res is not None and getattr(res, "shape_sensitivity", None) is not None and _rank() == 0:
+        for name, part in (("GrowthRateShapeSensitivity", res.shape_sensitivity.real), ("FrequencyShapeSensitivity", res.shape_sensitivity.imag)):
             head, base = os.path.split(path_noext)
             write_xdmf(os.path.join(head, base.replace("Wavemaker", name)), msh, name, np.ascontiguousarray(part))
 

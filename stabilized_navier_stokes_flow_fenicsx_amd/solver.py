@@ -395,6 +395,22 @@ class FlowProblem:
         check(self.lib.sns_jacobian_state_gradient(self.h, _ptr(w), _ptr(x), _ptr(z), float(c_jac), float(c_mass), _ptr(out)))
         return out
 
+    def jacobian_shape_gradient(self, w, x, z, c_jac: float = 1.0, c_mass: float = 0.0, out=None) -> torch.Tensor:
+        """The eigenvalue shape pass (sns_jacobian_shape_gradient): ``gX = d/dX [ z~^T (c_jac J0(w; X) + c_mass B(w; X)) x~ ]``
+        as a device tensor (n_nodes, 3), the derivative of the contraction of ``jacobian_state_gradient`` with respect to every
+        node coordinate at fixed ``w``, ``x``, ``z``, Dirichlet values (held at the nodes) and viscosity.  x~ and z~ are the
+        vectors with every constrained entry read as 0; their pressure entries matter.  One element pass, exact derivative,
+        bitwise reproducible; overwrites the problem's element scratch (``export(SNS_EXPORT_FE, ...)``), nothing else.
+        Refused (SnsError) as ``jacobian_state_gradient`` is: with a body force, a backflow coefficient, a time term or a
+        viscosity law set; a boundary traction alone and a viscosity field are allowed.  Single-GPU 3-D problems."""
+        w, x, z = self._vec(w), self._vec(x), self._vec(z)
+        if out is None:
+            out = torch.empty(self.n_local, 3, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.device.type != "cuda" or not out.is_contiguous() or out.numel() != 3 * self.n_local:
+            raise ValueError(f"out: expected a contiguous float64 device tensor of {3 * self.n_local} entries")
+        check(self.lib.sns_jacobian_shape_gradient(self.h, _ptr(w), _ptr(x), _ptr(z), float(c_jac), float(c_mass), _ptr(out)))
+        return out
+
     def raw_jacobian_apply(self, w, x, transpose: bool = False, out=None) -> torch.Tensor:
         """``J0(w) x``, or ``J0(w)^T x`` with ``transpose`` (sns_raw_jacobian_apply): J0 = dR_raw/dw, the Jacobian of the raw NS
         residual of ``residual_moments`` -- no lifting, no Dirichlet rows, no mask anywhere: ``x`` is used as given on
@@ -1945,6 +1961,52 @@ def eigenvalue_forcing_sensitivity(problem: FlowProblem, w, result: StabilityRes
         vol = torch.from_numpy(lumped_volumes(problem.mesh)).to(problem.device)
         out = (out.view(-1, 4) / vol[:, None]).reshape(-1)
     return out
+
+
+def eigenvalue_shape_sensitivity(problem: FlowProblem, w, result: StabilityResult = None, k: int = 0, pair=None,
+                                 ksp_rtol: float = 1e-10, return_parts: bool = False):
+    """The sensitivity of eigenvalue ``k`` to the geometry (where to reshape a wall or a body to damp a mode or shift its
+    frequency), a complex device tensor (n_nodes, 3) over EVERY node coordinate at a converged state ``w``:
+
+        d lam / dX = -( S_J(z, x) + lam S_B(z, x) ) / (z^T B x)  -  mu . dF/dX,      A^T mu = grad_w lam,  mu_B := 0,
+        S_A(z, x) = d/dX [ z~^T A(w; X) x~ ]   (``jacobian_shape_gradient``),
+
+    so that d lam = sum(d lam / dX * V), unconjugated, to first order under a deformation field V (n_nodes, 3), the
+    re-converged base flow included.  The first term is the explicit dependence of the pencil J x = -lam B x on the mesh at a
+    fixed base flow: with z = z_r + i z_i, x = x_r + i x_i, lam = a + i b it is the pass on four real pairs, each with
+    (c_jac, c_mass) = (1, a) and (0, b) -- eight passes.  The second is the path through the base flow: F(w; X) = 0 gives
+    dw = -A^-1 dF/dX dX, and grad_w lam is ``eigenvalue_base_flow_sensitivity``; it is ``shape_sensitivity`` with
+    grad_J = grad_w lam, on the real and on the imaginary part (two adjoint solves with the inner tolerance ``ksp_rtol``; the
+    problem's own is restored afterwards).  Neither term is negligible.  Assumptions, as for ``shape_sensitivity``:
+
+      * the Dirichlet values are held AT THE NODES and do not follow the coordinates: a node of an inlet that moves keeps its
+        value, and the constrained entries of the modes stay 0;
+      * the components on interior nodes are mesh-motion terms of the discrete problem; they vanish only in the limit h -> 0.
+
+    ``pair=(lam, x, z)`` supplies a mode directly instead of ``result`` / ``k``.  ``return_parts=True`` returns
+    ``(total, explicit, path)``.  Raises RuntimeError if an adjoint solve does not converge.  Afterwards the problem holds
+    J(w), untransposed.  Refused where ``jacobian_shape_gradient`` or ``residual_shape_gradient`` is."""
+    lam, x, z = _sensitivity_pair(problem, result, k, pair)
+    w = problem._vec(w)
+    a, b = lam.real, lam.imag
+    s1 = _bilinear_complex(lambda zz, xx: problem.jacobian_shape_gradient(w, xx, zz, 1.0, a), z, x)
+    sb = _bilinear_complex(lambda zz, xx: problem.jacobian_shape_gradient(w, xx, zz, 0.0, b), z, x)
+    explicit = -(s1 + 1j * sb) / mode_pairing(problem, w, z, x)         # S_J + a S_B + i b S_B
+    gw = eigenvalue_base_flow_sensitivity(problem, w, pair=(lam, x, z))
+    old = problem.options.ksp_rtol
+    problem.set_options(ksp_rtol=float(ksp_rtol))
+    try:
+        parts = []
+        for g in (gw.real.contiguous(), gw.imag.contiguous()):
+            dX, _, res = shape_sensitivity(problem, w, g)
+            if res.reason <= 0:
+                raise RuntimeError(f"eigenvalue_shape_sensitivity: the adjoint solve ended with reason {res.reason}")
+            parts.append(dX)
+    finally:
+        problem.set_options(ksp_rtol=old)
+    path = torch.complex(parts[0], parts[1])
+    total = explicit + path
+    return (total, explicit, path) if return_parts else total
 
 
 def print_stability(result: StabilityResult, rank: int = 0):
