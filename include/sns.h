@@ -580,6 +580,47 @@ SNS_API int sns_stability_arnoldi_shifted(sns_handle h, const double* w_dev, dou
                                           double* V_dev /* (m+1) * 4*n_local; column 0 = start vector (k = 0), columns 0 .. k */,
                                           double* H_host /* (m+1) x m, row major; the leading (k+1) x k block on entry (k >= 1) */,
                                           int* m_done, int* total_ksp_its, int* reason);
+/* Resolvent analysis of a steady state w of the 3-D NS form (no counterpart in the reference): how strongly the linearised flow
+ * amplifies a harmonic body force f exp(i omega t), and which force it amplifies most.  The response is q = R f,
+ * R = (J + i omega B)^-1 B; the gains are the singular values of R with the response in kinetic energy, q^H Q q, and the forcing
+ * in the lumped volume norm, f^H M_L f.  Complex device vectors are planar, as above.
+ * sns_energy_apply: y = Q x, Q = D_chi M D_chi with M the consistent P1 Galerkin mass matrix on the three velocity components
+ *   (on a tet M_ab = |det J| (1 + delta_ab) / 120; pressure rows and columns 0) and D_chi the nodal weight chi_dev (n_local
+ *   doubles; NULL: all ones), which restricts the norm to a region.  parts = 1: real x, y of 4*n_local; parts = 2: planar complex
+ *   x, y, each part summed exactly as parts = 1 sums it.  Matrix-free, one pass over the node -> cell lists, no atomics, bitwise
+ *   reproducible.  Constrained entries of x are read as 0, pressure entries are not read; constrained rows and pressure rows of y
+ *   are 0.  x and y must not be the same vector.  Reads the mesh and the mask alone: a viscosity law or a time term does not
+ *   refuse it.  SNS_E_ARG: null handle / pointer (chi_dev may be NULL), a 2-D handle, parts not 1 or 2, x_dev == y_dev.
+ *   SNS_E_STATE: a communicator attached.
+ * sns_lumped_volumes: m_i = sum over the cells of node i of |det J| / 24 (a quarter of their volumes) into the three velocity
+ *   slots of node i, 0 into its pressure slot; no mask.  Same pass, same order, bitwise reproducible.  Errors as
+ *   sns_energy_apply without its arguments.
+ * sns_resolvent_lanczos: m steps without restart of the Hermitian Krylov process on
+ *       T = S B^T (J + i omega B)^-H Q_q (J + i omega B)^-1 B S,     S = D_f M_L^-1/2 on the velocity dofs, 0 elsewhere,
+ *   whose eigenvalues are the squared gains; with a Ritz vector g the optimal forcing is f = S g, of unit M_L norm where
+ *   chi_f = 1.  chi_f_dev, chi_q_dev: nodal weights of the forcing and of the response (n_local doubles each; NULL: all ones).
+ *   J is assembled at w as the steady form and set up; per step: S, the pair mass pass, the complex solve of
+ *   (J + i omega B) q = b from a zero guess (the method of sns_shifted_solve, the handle's ksp options), the energy pass, the
+ *   operator flipped in place and set up, the solve of (J^T - i omega B^T) y = r, the operator flipped back and set up, the
+ *   transposed pair mass pass, S, classical Gram-Schmidt with one re-orthogonalisation in the complex inner product, and the
+ *   breakdown test by the norm ratio against breakdown_rel.  Column 0 of V is the start vector on entry; the call zeroes its
+ *   pressure and constrained entries and normalises it.  V: (m + 1) planar complex columns of 2 * 4*n_local doubles, zero behind
+ *   the last one reached; H: (m + 1) x m complex, row major, (re, im) interleaved, T V_m = V_{m+1} H.  *reason: 1 all m steps,
+ *   2 breakdown (the Krylov space is invariant: m_done columns; m_done = 0: the mask annihilates the start vector), < 0 the
+ *   SNS_KSP_* reason of an inner solve that did not converge -- the call then returns SNS_OK with m_done = the steps completed.
+ *   On every return except SNS_E_HIP the handle holds J untransposed, its hierarchy set up, no time term.
+ *   SNS_E_ARG: null handle / pointer (the weights may be NULL), a 2-D handle, m outside [2, 64], omega not finite, breakdown_rel
+ *   outside (0, 1), V_dev the same vector as w_dev or a weight.  SNS_E_STATE: as sns_stability_arnoldi.
+ * Not built: 2-D and partitioned handles, the Carreau law, restarts of this process, norms other than kinetic energy over lumped
+ * volume, forcing through Dirichlet data, gain sensitivities, transient growth. */
+SNS_API int sns_energy_apply(sns_handle h, const double* chi_dev /* n_local or NULL */, int parts /* 1 or 2 */,
+                             const double* x_dev, double* y_dev);
+SNS_API int sns_lumped_volumes(sns_handle h, double* m_dev /* 4*n_local */);
+SNS_API int sns_resolvent_lanczos(sns_handle h, const double* w_dev, double omega, int m, double breakdown_rel,
+                                  const double* chi_f_dev /* n_local or NULL */, const double* chi_q_dev /* n_local or NULL */,
+                                  double* V_dev /* (m+1) * 2 * 4*n_local; column 0 = start vector on entry */,
+                                  double* H_host /* (m+1) x m complex, row major, (re, im) interleaved */,
+                                  int* m_done, int* total_ksp_its, int* reason);
 /* The raw Jacobian and the Dirichlet values of a live handle (no counterpart in the reference).
  * sns_raw_jacobian_apply: y = J0(w) x for transposed == 0, y = J0(w)^T x otherwise, J0 = dR_raw/dw the exact Gateaux derivative
  *   of the raw residual sns_residual_moments sums -- without lifting and without the Dirichlet rows' w_B - g.  With K_t the

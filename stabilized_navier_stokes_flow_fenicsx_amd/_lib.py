@@ -130,6 +130,10 @@ _SIGNATURES = [
                                     C.POINTER(C.c_double)]),
     ("sns_stability_arnoldi_shifted", C.c_int, [_H, _P, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _P, _P,
                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("sns_energy_apply", C.c_int, [_H, _P, C.c_int, _P, _P]),
+    ("sns_lumped_volumes", C.c_int, [_H, _P]),
+    ("sns_resolvent_lanczos", C.c_int, [_H, _P, C.c_double, C.c_int, C.c_double, _P, _P, _P, _P, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("sns_raw_jacobian_apply", C.c_int, [_H, C.c_int, _P, _P, C.c_int, _P]),
     ("sns_set_dirichlet_values", C.c_int, [_H, _P]),
     ("sns_scalar_system", C.c_int, [_H, _P, C.POINTER(C.c_double), C.c_double, C.c_double, _P, _P, _P, _P]),

@@ -665,6 +665,34 @@ int sns_shifted_solve(sns_handle h, const double* w, double c_re, double c_im, i
     return shifted_solve(h, w, c_re, c_im, transpose != 0, b, x, its, reason, rnorm);
 }
 
+int sns_energy_apply(sns_handle h, const double* chi, int parts, const double* x, double* y) {
+    const char* who = "sns_energy_apply";
+    if (!h || !x || !y) { set_error("sns_energy_apply: null handle or pointer"); return SNS_E_ARG; }
+    SNS_TRY(allows(h, who, policy::FAMILY_RESOLVENT, policy::RREQ_ENERGY, ROWS_ARG));
+    SNS_TRY(refused(who, policy::check_energy_args({parts, x == y})));
+    SNS_TRY(allows(h, who, policy::FAMILY_RESOLVENT, policy::RREQ_ENERGY, ROWS_STATE));
+    return energy_apply(h, chi, parts, x, y);
+}
+
+int sns_lumped_volumes(sns_handle h, double* m) {
+    if (!h || !m) { set_error("sns_lumped_volumes: null handle or pointer"); return SNS_E_ARG; }
+    SNS_TRY(allows(h, "sns_lumped_volumes", policy::FAMILY_RESOLVENT, policy::RREQ_ENERGY));
+    return lumped_volumes(h, m);
+}
+
+int sns_resolvent_lanczos(sns_handle h, const double* w, double omega, int m, double breakdown_rel, const double* chi_f,
+                          const double* chi_q, double* V, double* H, int* m_done, int* total_ksp_its, int* reason) {
+    const char* who = "sns_resolvent_lanczos";
+    if (!h || !w || !V || !H || !m_done || !total_ksp_its || !reason) {
+        set_error("sns_resolvent_lanczos: null handle or pointer");
+        return SNS_E_ARG;
+    }
+    SNS_TRY(allows(h, who, policy::FAMILY_RESOLVENT, policy::RREQ_LANCZOS, ROWS_ARG));
+    SNS_TRY(refused(who, policy::check_resolvent_args({m, omega, breakdown_rel, V == w || V == chi_f || V == chi_q})));
+    SNS_TRY(allows(h, who, policy::FAMILY_RESOLVENT, policy::RREQ_LANCZOS, ROWS_STATE));
+    return resolvent_lanczos(h, w, omega, m, breakdown_rel, chi_f, chi_q, V, H, m_done, total_ksp_its, reason);
+}
+
 int sns_basis_rotate(sns_handle h, int n_in, int n_out, const double* Q, double* V) {
     const char* who = "sns_basis_rotate";
     if (!h || !Q || !V) { set_error("sns_basis_rotate: null handle or pointer"); return SNS_E_ARG; }

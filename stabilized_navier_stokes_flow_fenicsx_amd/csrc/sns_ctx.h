@@ -367,6 +367,14 @@ int cfgmres(sns_ctx* h, const double* w, double c_re, double c_im, bool left, co
             double* rnorm, CfgmresWork& ws);
 int shifted_solve(sns_ctx* h, const double* w, double c_re, double c_im, bool left, const double* b, double* x, int* its, int* reason,
                   double* rnorm);
+// csrc/sns_resolvent.hip: the energy pass y = D_chi M D_chi x (chi null: all ones; parts = 2: planar complex x, y), the lumped
+// nodal volumes in the layout of a state vector, and the Hermitian Krylov process on
+// T = S B^T (J + i omega B)^-H Q (J + i omega B)^-1 B S, which assembles J, flips it twice per step and leaves it untransposed
+void launch_energy(sns_ctx* h, const double* chi, int parts, const double* x, double* y);
+int energy_apply(sns_ctx* h, const double* chi, int parts, const double* x, double* y);
+int lumped_volumes(sns_ctx* h, double* m);
+int resolvent_lanczos(sns_ctx* h, const double* w, double omega, int m, double breakdown_rel, const double* chi_f, const double* chi_q,
+                      double* V, double* H, int* m_done, int* total_its, int* reason);
 // csrc/sns_hessian.hip: g = grad_w [ z~^T (c_jac J(w) + c_mass B(w)) x~ ] by one element pass (uses the element scratch Fe)
 int jacobian_state_gradient(sns_ctx* h, const double* w, const double* x, const double* z, double c_jac, double c_mass, double* g);
 int jacobian_shape_gradient(sns_ctx* h, const double* w, const double* x, const double* z, double c_jac, double c_mass, double* gX);

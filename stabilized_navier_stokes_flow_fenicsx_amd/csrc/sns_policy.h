@@ -457,8 +457,10 @@ enum FactBit {
 // stability analysis (csrc/sns_stability.hip) -- SREQ_COUNT is the number of right-hand kinds, SREQ_KINDS counts all: the
 // left-hand kinds (sns_mass_apply_transpose, sns_stability_arnoldi_left) follow the right-hand ones and are refused exactly as
 // those are --; the Hessian pass (sns_jacobian_state_gradient, csrc/sns_hessian.hip), one request; the raw Jacobian
-// (sns_raw_jacobian_apply) and the Dirichlet values of a live handle (sns_set_dirichlet_values), two requests.
-enum Family { FAMILY_FORM = 0, FAMILY_BOUNDARY, FAMILY_STABILITY, FAMILY_STATE_GRADIENT, FAMILY_RAW_JACOBIAN };
+// (sns_raw_jacobian_apply) and the Dirichlet values of a live handle (sns_set_dirichlet_values), two requests; the resolvent
+// analysis (csrc/sns_resolvent.hip), two requests: the passes that touch no form (sns_energy_apply, sns_lumped_volumes) and the
+// process (sns_resolvent_lanczos).
+enum Family { FAMILY_FORM = 0, FAMILY_BOUNDARY, FAMILY_STABILITY, FAMILY_STATE_GRADIENT, FAMILY_RAW_JACOBIAN, FAMILY_RESOLVENT };
 enum FormRequest {
     REQ_SET_TIME_TERM = 0, REQ_CLEAR_TIME_TERM, REQ_SET_CARREAU, REQ_SET_NEWTONIAN, REQ_SET_FIELD /* set or clear: force, viscosity, mixture */,
     REQ_TIME_STEP, REQ_SHAPE_GRADIENT, REQ_RECOVER_GRADIENT, REQ_ERROR_INDICATOR, REQ_SCALAR /* system or solve */,
@@ -468,6 +470,7 @@ enum BoundaryRequest { BREQ_SET_FACETS = 0, BREQ_SET_FLOW, BREQ_SET_SCALAR, BREQ
 enum StabilityRequest { SREQ_MASS_APPLY = 0, SREQ_ARNOLDI, SREQ_COUNT, SREQ_MASS_APPLY_TRANSPOSE = SREQ_COUNT, SREQ_ARNOLDI_LEFT, SREQ_KINDS };
 constexpr int GREQ_STATE_GRADIENT = 0;
 enum RawJacobianRequest { JREQ_APPLY = 0, JREQ_SET_DIRICHLET, JREQ_COUNT };
+enum ResolventRequest { RREQ_ENERGY = 0 /* the energy pass, the lumped volumes */, RREQ_LANCZOS, RREQ_COUNT };
 // error != SNS_OK: refused; the entry point's message is its name, ": " and `tail`
 struct Verdict {
     int error = SNS_OK;
@@ -482,7 +485,9 @@ struct Verdict {
 // refuses a body force (J then depends on f through dM/dw(w, -f): a second contraction that is not built) and a backflow
 // coefficient (that term is quadratic in u; its Hessian is not built); the raw-Jacobian pass serves 2-D handles and every
 // switch of the form (its blocks are the assembly's own) and refuses only a backflow coefficient, whose share of J0 lives in
-// the boundary pass and is not built matrix-free; a traction alone is constant in w.
+// the boundary pass and is not built matrix-free; a traction alone is constant in w; the energy pass and the lumped volumes
+// read the mesh and the mask alone, so a law or a time term does not refuse them, while the resolvent process is refused where
+// the Arnoldi process is, in its words.
 struct Rule {
     Family family;
     int request;
@@ -554,6 +559,13 @@ constexpr Rule RULES[] = {
      "not with a backflow coefficient set (the backflow term's share of the raw Jacobian is not built)"},
     {FAMILY_RAW_JACOBIAN, JREQ_SET_DIRICHLET, IS_PARTITIONED, SNS_E_STATE,
      "not with a communicator attached (partitioned handles keep the Dirichlet values they were created with)"},
+
+    {FAMILY_RESOLVENT, RREQ_ENERGY, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_RESOLVENT, RREQ_ENERGY, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned stability analysis is not built)"},
+    {FAMILY_RESOLVENT, RREQ_LANCZOS, IS_NOT_3D, SNS_E_ARG, "3-D handles only"},
+    {FAMILY_RESOLVENT, RREQ_LANCZOS, IS_PARTITIONED, SNS_E_STATE, "not with a communicator attached (partitioned stability analysis is not built)"},
+    {FAMILY_RESOLVENT, RREQ_LANCZOS, HAS_LAW, SNS_E_STATE, "not with a viscosity law set (the mass operator of the law's form is not built)"},
+    {FAMILY_RESOLVENT, RREQ_LANCZOS, HAS_TIME_TERM, SNS_E_STATE, "not with a time term set (the analysis sets its own and clears it)"},
 };
 
 // The one lookup.  An entry point's own value checks stand between the family's SNS_E_ARG rows and its SNS_E_STATE rows:
@@ -639,7 +651,33 @@ inline Verdict check_raw_jacobian_args(const RawJacobianArgs& a) {
     return {};
 }
 
-// The families as the host tests ask them (tests/request_main.cpp; the raw Jacobian's: tests/rawjac_request_main.cpp)
+// ... and the arguments of the resolvent family.  The energy pass: parts in {1, 2}, distinct vectors (the lumped volumes have
+// no argument to check: the default).  The process: m in [2, 64], a finite omega, breakdown_rel in (0, 1), and a basis that is
+// neither the state nor a weight vector
+struct EnergyArgs {
+    int parts = 1;
+    bool aliased = false;
+};
+inline Verdict check_energy_args(const EnergyArgs& a) {
+    if (a.parts != 1 && a.parts != 2) return {SNS_E_ARG, "parts must be 1 or 2"};
+    if (a.aliased) return {SNS_E_ARG, "x and y must not be the same vector"};
+    return {};
+}
+struct ResolventArgs {
+    int m = STABILITY_M_MAX;
+    double omega = 0.0, breakdown_rel = 1e-6;
+    bool aliased = false;
+};
+inline Verdict check_resolvent_args(const ResolventArgs& a) {
+    if (a.m < STABILITY_M_MIN || a.m > STABILITY_M_MAX) return {SNS_E_ARG, "m must lie in [2, 64]"};
+    if (!(a.omega - a.omega == 0.0)) return {SNS_E_ARG, "omega must be finite"};
+    if (!(a.breakdown_rel > 0.0) || !(a.breakdown_rel < 1.0)) return {SNS_E_ARG, "breakdown_rel must lie in (0, 1)"};
+    if (a.aliased) return {SNS_E_ARG, "V must not be the state or a weight vector"};
+    return {};
+}
+
+// The families as the host tests ask them (tests/request_main.cpp; the raw Jacobian's: tests/rawjac_request_main.cpp; the
+// resolvent's: tests/resolvent_request_main.cpp)
 inline Verdict check_form_request(FormRequest request, const HandleFacts& f) { return check_request(FAMILY_FORM, request, f); }
 inline Verdict check_boundary_request(BoundaryRequest request, const HandleFacts& f) { return check_request(FAMILY_BOUNDARY, request, f); }
 inline Verdict check_stability_request(StabilityRequest request, const HandleFacts& f, const ArnoldiArgs& a = {}) {
@@ -662,6 +700,13 @@ inline Verdict check_state_gradient_request(const HandleFacts& f, double c_jac =
 }
 inline Verdict check_raw_jacobian_request(RawJacobianRequest request, const HandleFacts& f, const RawJacobianArgs& a = {}) {
     return check_request(FAMILY_RAW_JACOBIAN, request, f, request == JREQ_APPLY ? check_raw_jacobian_args(a) : Verdict{});
+}
+
+inline Verdict check_resolvent_energy_request(const HandleFacts& f, const EnergyArgs& a = {}) {
+    return check_request(FAMILY_RESOLVENT, RREQ_ENERGY, f, check_energy_args(a));
+}
+inline Verdict check_resolvent_lanczos_request(const HandleFacts& f, const ResolventArgs& a = {}) {
+    return check_request(FAMILY_RESOLVENT, RREQ_LANCZOS, f, check_resolvent_args(a));
 }
 
 // ---- which operator is it? (the spectral estimates of csrc/sns_damping.hip; the cases are in DESIGN.md) -----------------------------

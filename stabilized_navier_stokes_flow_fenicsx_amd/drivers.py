@@ -335,6 +335,9 @@ def solve_NS_flow(argv=None, *, coarse_mesh_size: float = 0.1, device="cuda:0", 
     stab = _stability(Pf, w)
     if stab is not None:
         out["stability"] = stab
+    resolvent = _resolvent(Pf, w)
+    if resolvent is not None:
+        out["resolvent"] = resolvent
     if derived is not None:
         out["derived"] = derived
     conc = coupled[1] if coupled is not None else _scalar_transport(Pf, w, msh_f)
@@ -351,6 +354,7 @@ def navier_stokes_channel_main(argv=None):
     save_navier_stokes_solution(r["u"], r["p"], r["msh"], folder, r["Re"])
     _write_derived_fields(r.get("derived"), r["msh"], lambda label: os.path.join(folder, f"Re{r['Re']}Channel{label}"))
     _write_wavemaker(r.get("stability"), r["msh"], os.path.join(folder, f"Re{r['Re']}ChannelWavemaker"))
+    _write_resolvent(r.get("resolvent"), r["msh"], os.path.join(folder, f"Re{r['Re']}ChannelOptimalForcing"))
     if r.get("concentration") is not None and _rank() == 0:
         write_xdmf(os.path.join(folder, f"Re{r['Re']}ChannelConcentration"), r["msh"], "Concentration", r["concentration"])
     write_run_metadata(folder, r["Re"], r["img_fname"], r["flowrate_ratio"], r["channel_mesh_size"], r["msh"])
@@ -407,6 +411,7 @@ def duct_stokes_main(argv=None):
         write_xdmf("StokesDuctVelcoity", msh, "f", u)             # (sic) file name of the reference :255
     _write_derived_fields(_derived_fields(P, U), msh, lambda label: f"StokesDuct{label}")
     _write_wavemaker(_stability(P, U), msh, "StokesDuctWavemaker")
+    _write_resolvent(_resolvent(P, U), msh, "StokesDuctOptimalForcing")
     conc = coupled[1] if coupled is not None else _scalar_transport(P, U, msh)
     if conc is not None and _rank() == 0:
         write_xdmf("StokesDuctConcentration", msh, "Concentration", conc)
@@ -630,6 +635,49 @@ def _stability(P, w):
     if shape:
         _stability_shape(P, w, res)
     return res
+
+
+def _resolvent(P, w):
+    """SNS_RESOLVENT=<n_modes>,<omega>[,<omega>...] (opt-in; single-GPU runs): after the solve, the resolvent analysis of the flow
+    linearised at the state ``w`` (``solver.resolvent_analysis``, the 3-D NS form at the problem's Reynolds number) at every
+    frequency listed, one printed line per frequency and mode: omega, the gain sigma and the residual estimate.  Returns the
+    result at the frequency of largest leading gain, whose leading forcing and response the scripts write as ...OptimalForcing
+    and ...OptimalResponse fields (nodal velocity magnitudes) beside their other files.  Nothing without the switch: files and
+    stdout stay as they are."""
+    spec = os.environ.get("SNS_RESOLVENT", "")
+    if not spec:
+        return None
+    if getattr(P, "part", None) is not None:
+        if _rank() == 0:
+            print("SNS_RESOLVENT: the resolvent analysis runs on single-GPU problems only; skipped", flush=True)
+        return None
+    parts = spec.split(",")
+    if len(parts) < 2:
+        raise ValueError("SNS_RESOLVENT=<n_modes>,<omega>[,<omega>...]")
+    n_modes, omegas = int(parts[0]), [float(v) for v in parts[1:]]
+    from .solver import SnsError, print_resolvent, resolvent_analysis
+    best = None
+    for omega in omegas:
+        try:
+            res = resolvent_analysis(P, w, omega, n_modes=n_modes)
+        except SnsError as e:                             # (a viscosity law, a 2-D problem: the library says which)
+            if _rank() == 0:
+                print(f"SNS_RESOLVENT: skipped ({e})", flush=True)
+            return None
+        print_resolvent(res, _rank())
+        if len(res.gains) and (best is None or res.gains[0] > best.gains[0]):
+            best = res
+    return best
+
+
+def _write_resolvent(res, msh, path_noext):
+    """``path_noext`` names the ...OptimalForcing file; the response goes beside it."""
+    if res is None or not len(res.gains) or _rank() != 0:
+        return
+    head, base = os.path.split(path_noext)
+    for name, mode in (("OptimalForcing", res.forcing_modes[0]), ("OptimalResponse", res.response_modes[0])):
+        mag = mode.reshape(-1, 4)[:, :3].abs().pow(2).sum(dim=1).sqrt().cpu().numpy()
+        write_xdmf(os.path.join(head, base.replace("OptimalForcing", name)), msh, name, np.ascontiguousarray(mag))
 
 
 def _stability_sensitivity(P, w, res):
@@ -913,6 +961,7 @@ def dfg_3d_main(argv=None):
         write_xdmf("DFGValidationVelocityNavierStokes", msh, "Velocity", wg.reshape(-1, 4)[:, :3].copy())
     _write_derived_fields(_derived_fields(P, w), msh, lambda label: f"DFGValidation{label}NavierStokes")
     _write_wavemaker(_stability(P, w), msh, "DFGValidationWavemakerNavierStokes")
+    _write_resolvent(_resolvent(P, w), msh, "DFGValidationOptimalForcingNavierStokes")
     if _sensitivity():
         sc = Fn.drag_lift_coefficients(np.ones(3))[0]
         ob = msh.meta["tags"]["obstacle"]

@@ -580,6 +580,66 @@ class FlowProblem:
                                                      C.byref(reason)))
         return V, H, ArnoldiResult(done.value, reason.value, its.value)
 
+    # -- resolvent analysis (no counterpart in the reference) ----------------------------------------------------------
+    def _nodal_weight(self, weight, name: str):
+        """A nodal weight (n_local entries, numpy or a tensor) as a contiguous float64 device tensor; None stays None."""
+        if weight is None:
+            return None
+        if not isinstance(weight, torch.Tensor):
+            weight = torch.as_tensor(np.asarray(weight, dtype=np.float64))
+        weight = weight.to(self.device, torch.float64).contiguous()
+        if weight.shape != (self.n_local,):
+            raise ValueError(f"{name}: expected one weight per node ({self.n_local})")
+        return weight
+
+    def energy_apply(self, x, weight=None) -> torch.Tensor:
+        """``Q x`` with Q = D M D (sns_energy_apply): M the consistent P1 Galerkin mass matrix on the three velocity
+        components, D the nodal ``weight`` (one entry per node; None: all ones), so that x^H Q x is the kinetic energy of the
+        weighted field.  ``x``: a real dof vector (the result is float64) or a complex one (complex128; each part is summed
+        exactly as a real vector is).  Matrix-free in one pass, bitwise reproducible; constrained entries of ``x`` are read as
+        0, pressure entries are not read, constrained and pressure rows of the result are 0.  Single-GPU 3-D problems."""
+        chi = self._nodal_weight(weight, "weight")
+        if x.is_complex() if isinstance(x, torch.Tensor) else np.iscomplexobj(x):
+            xp = self._planar(x)
+            out = torch.empty_like(xp)
+            check(self.lib.sns_energy_apply(self.h, _ptr(chi), 2, _ptr(xp), _ptr(out)))
+            return self._unplanar(out)
+        x = self._vec(x)
+        out = self.zeros()
+        check(self.lib.sns_energy_apply(self.h, _ptr(chi), 1, _ptr(x), _ptr(out)))
+        return out
+
+    def lumped_volumes(self) -> torch.Tensor:
+        """The lumped nodal volumes as a dof vector (sns_lumped_volumes): a quarter of the incident tets' volumes in the three
+        velocity slots of every node, 0 in its pressure slot; no mask.  Bitwise reproducible.  Single-GPU 3-D problems."""
+        out = self.zeros()
+        check(self.lib.sns_lumped_volumes(self.h, _ptr(out)))
+        return out
+
+    def resolvent_lanczos(self, w, omega: float, m: int = 24, start=None, breakdown_rel: float = 1e-6, forcing_weight=None,
+                          response_weight=None):
+        """``m`` steps of the Hermitian Krylov process on T = S B^T (J + i omega B)^-H Q (J + i omega B)^-1 B S at the steady
+        state ``w`` (sns_resolvent_lanczos), whose eigenvalues are the squared resolvent gains: Q the operator of
+        ``energy_apply`` with ``response_weight``, S = D_f M_L^-1/2 with M_L the ``lumped_volumes`` and D_f the
+        ``forcing_weight`` (nodal weights; None: all ones).  The inner solves take the problem's ksp / pc options.  Returns
+        ``(V, H, ArnoldiResult)``: V a complex128 device tensor (m + 1, ndof) whose rows are the orthonormal basis, H numpy
+        complex (m + 1, m) with T V_m = V_{m+1} H.  ``start``: a real or complex dof vector, by default cos(1 + 0.37 i) over
+        the dofs; its pressure and constrained entries are zeroed.  Afterwards the problem's matrix is J, untransposed and set
+        up.  An inner solve that does not converge ends the process quietly: ``reason`` < 0, ``m_done`` the steps completed."""
+        w = self._vec(w)
+        m = int(m)
+        chi_f, chi_q = self._nodal_weight(forcing_weight, "forcing_weight"), self._nodal_weight(response_weight, "response_weight")
+        V = torch.zeros(max(m, 0) + 1, 2 * self.ndof, dtype=torch.float64, device=self.device)
+        if start is None:
+            V[0, :self.ndof] = torch.cos(1.0 + 0.37 * torch.arange(self.ndof, dtype=torch.float64, device=self.device))
+        else:
+            V[0] = self._planar(start)
+        H = np.zeros((max(m, 0) + 1, max(m, 0)), dtype=np.complex128)
+        done, its, reason = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.sns_resolvent_lanczos(self.h, _ptr(w), float(omega), m, float(breakdown_rel), _ptr(chi_f), _ptr(chi_q), _ptr(V),
+                                             H.ctypes.data, C.byref(done), C.byref(its), C.byref(reason)))
+        return torch.complex(V[:, :self.ndof], V[:, self.ndof:]), H, ArnoldiResult(done.value, reason.value, its.value)
+
     def spmv(self, x, out=None) -> torch.Tensor:
         x = self._vec(x)
         out = self.zeros() if out is None else self._vec(out)
@@ -1793,6 +1853,98 @@ def harmonic_response(problem: FlowProblem, w, omega: float, f):
     else:
         b = problem.mass_apply(w, f)
     return problem.shifted_solve(w, 1j * float(omega), b)
+
+
+@dataclass
+class ResolventResult:
+    omega: float
+    gains: np.ndarray           # (n,) sigma_k, descending: |q|_Q = sigma |f|_ML for the optimal pairs
+    forcing_modes: torch.Tensor  # (n, ndof) complex128 on the device: f_k = S V s_k, of unit lumped-volume norm where the forcing weight is 1
+    response_modes: torch.Tensor  # (n, ndof) complex128: q_k = R f_k / sigma_k by one forward solve each, of unit energy norm
+    residuals: np.ndarray       # (n,) the estimates |h_{m+1,m}| |last component of s_k|, on the scale of sigma^2
+    converged: np.ndarray       # (n,) bool: estimate <= tol * sigma_1^2
+    m_done: int
+    ksp_its: int                # the process's inner solves and the forward solves of the response modes
+    reason: int                 # of the process: 1 all m steps, 2 breakdown, < 0 the KSP reason of a failed inner solve
+
+
+def resolvent_ritz(H, m_done: int):
+    """The Ritz pairs of the Hermitian Krylov process of ``FlowProblem.resolvent_lanczos`` (numpy only): the eigenpairs of the
+    Hermitian part of H[:m_done, :m_done] in descending order of the eigenvalue -- the squared gains -- and per pair the
+    residual estimate |h_{m_done+1, m_done}| |last component of the eigenvector|.  Returns (theta (k,), S (k, k) with unit
+    columns, estimates (k,)); m_done = 0: three empty arrays."""
+    k = int(m_done)
+    H = np.asarray(H)
+    if k <= 0:
+        return np.zeros(0), np.zeros((0, 0), dtype=np.complex128), np.zeros(0)
+    Hk = H[:k, :k]
+    theta, Y = np.linalg.eigh(0.5 * (Hk + Hk.conj().T))
+    order = np.argsort(-theta, kind="stable")
+    theta, Y = theta[order], Y[:, order]
+    beta = abs(H[k, k - 1]) if H.shape[0] > k else 0.0
+    return theta, Y, beta * np.abs(Y[k - 1, :])
+
+
+def resolvent_analysis(problem: FlowProblem, w, omega: float, n_modes: int = 3, m: int = 24, tol: float = 1e-6, forcing_weight=None,
+                       response_weight=None, ksp_rtol: float = 1e-10) -> ResolventResult:
+    """The leading resolvent gains of the flow linearised at the steady state ``w`` at the frequency ``omega``, with the optimal
+    forcings and their responses: the largest singular values sigma_k of R = (J + i omega B)^-1 B with the response measured in
+    kinetic energy (``FlowProblem.energy_apply`` with ``response_weight``) and the forcing in the lumped volume norm
+    (``forcing_weight`` restricts it to where the weight is not 0).  ``m`` steps of ``FlowProblem.resolvent_lanczos`` with the
+    inner tolerance ``ksp_rtol`` (the problem's options are restored afterwards), ``resolvent_ritz`` on the host, the ``n_modes``
+    leading pairs: f_k = S V s_k, and q_k = R f_k / sigma_k by one forward solve each (``harmonic_response``'s), scaled to unit
+    energy norm.  A pair whose estimate exceeds ``tol`` sigma_1^2 is returned and flagged in ``converged``, never dropped.  For
+    a stable flow sigma_1 over omega is the gain curve (``resolvent_gain_curve``); its peak says which frequency the flow
+    amplifies most, f_1 where to force it and q_1 what answers."""
+    w = problem._vec(w)
+    old = problem.options.ksp_rtol
+    problem.set_options(ksp_rtol=float(ksp_rtol))
+    try:
+        V, H, res = problem.resolvent_lanczos(w, omega, m=m, forcing_weight=forcing_weight, response_weight=response_weight)
+        theta, Y, est = resolvent_ritz(H, res.m_done)
+        n = min(max(0, int(n_modes)), len(theta))
+        theta, Y, est = theta[:n], Y[:, :n], est[:n]
+        gains = np.sqrt(np.maximum(theta, 0.0))
+        ml = problem.lumped_volumes()
+        chi = problem._nodal_weight(forcing_weight, "forcing_weight")
+        scale = torch.where(ml > 0.0, 1.0 / torch.sqrt(torch.where(ml > 0.0, ml, torch.ones_like(ml))), torch.zeros_like(ml))
+        scale[torch.from_numpy(problem.bc_mask.astype(bool)).to(problem.device)] = 0.0
+        if chi is not None:
+            scale = scale * chi.repeat_interleave(4)
+        Yd = torch.from_numpy(np.ascontiguousarray(Y.T)).to(problem.device)          # (n, m_done)
+        F = (Yd @ V[:res.m_done]) * scale if n else torch.zeros(0, problem.ndof, dtype=torch.complex128, device=problem.device)
+        Q = torch.zeros_like(F)
+        its = res.ksp_its
+        for k in range(n):
+            q, kres = harmonic_response(problem, w, omega, F[k])
+            its += kres.its
+            qn = float(torch.sqrt(torch.vdot(q, problem.energy_apply(q, response_weight)).real))
+            Q[k] = q / qn if qn > 0.0 else q
+    finally:
+        problem.set_options(ksp_rtol=old)
+    conv = est <= tol * (theta[0] if n else 0.0)
+    return ResolventResult(float(omega), gains, F, Q, est, conv, res.m_done, its, res.reason)
+
+
+def resolvent_gain_curve(problem: FlowProblem, w, omegas, **kw) -> np.ndarray:
+    """The leading resolvent gain sigma_1 at every frequency of ``omegas`` (``resolvent_analysis`` with n_modes = 1 unless
+    ``kw`` says otherwise; nan where the process produced no pair)."""
+    kw.setdefault("n_modes", 1)
+    out = np.full(len(omegas), np.nan)
+    for i, om in enumerate(omegas):
+        r = resolvent_analysis(problem, w, float(om), **kw)
+        if len(r.gains):
+            out[i] = r.gains[0]
+    return out
+
+
+def print_resolvent(result: ResolventResult, rank: int = 0):
+    if rank != 0:
+        return
+    for k in range(len(result.gains)):
+        flag = "" if result.converged[k] else "  (not converged)"
+        print(f"Resolvent gain: omega {result.omega:.6g} sigma {result.gains[k]:.8e} residual estimate {result.residuals[k]:.2e}{flag}",
+              flush=True)
 
 
 def _mode_pair(result: StabilityResult, k: int):
